@@ -10,17 +10,18 @@ SAN-M decoder x16 -> vocab GEMM -> last-index arg-max, + the gather of hypothese
 over one batch per GPU, audio already resident in HBM when the timed region starts.  K steps are timed; by default TWO
 steps are in flight per GPU (`--in-flight`, round 4): two engines on the device, each with its own stream and workspaces,
 take the steps alternately, so the kernels of step k + 1 fill the CUs that step k's kernels leave idle (tile-round tails,
-the decoder's small launches, memory-bound tile ends).  Every step still runs the whole path over a whole batch and its ids
-are checked; `ms_per_step` = timed wall time / K, `ms_first_step_alone` = the first timed step, which runs alone.
+the decoder's small launches, memory-bound tile ends).  Every step still runs the whole path over a whole batch (`--full`
+checks that every engine's ids agree); `ms_per_step` = timed wall time / K, `ms_first_step_alone` = the first timed step, which runs alone.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Multi-GPU: one process per GPU; utterances are independent, so each rank recognises its own
 shard (weak scaling, no data-path collective); RCCL is used for the one-off weight broadcast
 (rank 0 -> all) and the per-step gather of hypotheses.
 
-The JSON line also carries
+A plain run sets up, warms up, times K steps and prints the headline line; `--dump-outputs DIR` also writes the last timed
+step's outputs as DIR/<name>.npy.  With `--full` the JSON line also carries (among the objects --help lists)
   roofline     — the dominant kernel class = the encoder GEMM class with the largest share of the step
                  (chosen by an untimed profiling step), timed live with HIP events on the engine stream
                  during the first timed step: algorithmic FLOPs / avg duration against the 2.5 PFLOP/s
@@ -268,6 +269,20 @@ def golden_check(tag, ids, token_num=None, margin=None):
             "token_num_near_ties_resolved_differently": tn_diff, "L": [int(ids.shape[1]), int(gi.shape[1])],
             "rows_checked": int(B), "near_tie_rows_skipped_without_token_num": skipped,
             "margin": margin, "oracle": "%s CPU oracle, tests/golden/bench_%s.npz" % ("int8 (DynamicQuantizeLinear + MatMulInteger)" if tag.endswith("_int8") else "fp32", tag)}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: every array as d/<name>.npy, integers as float64 (exact for ids and counts), floats as float32."""
+    conv = {k: np.asarray(v, dtype=np.float64 if np.issubdtype(np.asarray(v).dtype, np.integer) else np.float32)
+            for k, v in arrays.items()}
+    total = sum(a.nbytes for a in conv.values())
+    assert total <= DUMP_LIMIT_BYTES, "outputs of %d bytes exceed the dump limit" % total
+    os.makedirs(d, exist_ok=True)
+    for k, a in conv.items():
+        np.save(os.path.join(d, k + ".npy"), a)
 
 
 def respawn_under_torchrun(n: int) -> int:
@@ -597,6 +612,11 @@ def group_main(args):
         res = grp.recognize(audio, hotwords=hw)
     dt = time.perf_counter() - t0
     assert res.L > 0 and res.token_ids.shape == (B, res.L) and (res.token_num > 0).all()
+    if args.dump_outputs:
+        outs = {"token_ids": res.token_ids, "token_num": res.token_num}
+        if res.cif_peak is not None:
+            outs["cif_peak"] = res.cif_peak
+        dump_outputs(args.dump_outputs, outs)
     per = B // n
     chk = golden_check(args.model, res.token_ids[:per], res.token_num[:per]) if seconds == (10 if sv else SECONDS) else None
     assert chk is None or chk["ok"], chk
@@ -664,7 +684,19 @@ def main():
     ap.add_argument("--group-devices", default="",
                     help="comma-separated device ordinals for --group (default 0..N-1; a repeated ordinal runs several "
                          "engines on one GPU without a communicator — how the 1-GPU box exercises the sharding)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the per-class profiling step and roofline, one-in-flight and "
+                         "after-idle steps, the host-memory rate, the ids against the oracles' golden files, the `exact` twin, "
+                         "the via_recognizer object and the CPU baseline (a plain run sets up, warms up, times --steps steps and "
+                         "prints the result line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last timed step computed (ids, token counts, CIF peaks of a "
+                         "timestamp model) as DIR/<name>.npy in float32 / float64")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.via == "recognizer":
+        ap.error("--dump-outputs is not supported with --via recognizer")
 
     if args.config == 2:
         args.model = "sensevoice"
@@ -773,41 +805,43 @@ def main():
     run_steps(0, args.warmup * E)
     for e_ in engs:
         e_.sync()
-    # ---- which kernel class does the roofline object describe?  An UNTIMED profiling step over every class: the
-    # encoder GEMM class with the largest share of the step is the "dominant kernel" (every rank takes the same
-    # decision from its own measurement of the same launches; rank 0's is printed)
-    eng.profile_reset()
-    eng.profile_select("")
-    eng.profile(True)
-    eng.run_staged()
-    eng.sync()
-    eng.profile(False)
-    class_ms = {}
-    for cls in CLASSES:
-        ms, cnt, fpl = eng.profile_get(cls)
-        if cnt:
-            class_ms[cls] = {"ms": round(ms, 4), "launches": cnt, "kernel": eng.profile_kernel(cls) or None,
-                             "tflops": round(fpl * cnt / (ms * 1e-3) / 1e12, 1) if ms > 0 and fpl > 0 else None}
-    dominant = max(GEMM_SHAPES, key=lambda c: class_ms.get(c, {"ms": 0.0})["ms"])
-    if use_dist:                                             # one decision for the whole job: rank 0's
-        pick = [dominant]
-        dist.broadcast_object_list(pick, src=0)
-        dominant = pick[0]
-    dom_kernel = eng.profile_kernel(dominant)
-    torch.cuda.synchronize()
-    if use_dist:
-        dist.barrier()
-    eng.profile_reset()
-    eng.profile_select(dominant)
-    eng.profile(True)
+    if args.full:
+        # ---- which kernel class does the roofline object describe?  An UNTIMED profiling step over every class: the
+        # encoder GEMM class with the largest share of the step is the "dominant kernel" (every rank takes the same
+        # decision from its own measurement of the same launches; rank 0's is printed)
+        eng.profile_reset()
+        eng.profile_select("")
+        eng.profile(True)
+        eng.run_staged()
+        eng.sync()
+        eng.profile(False)
+        class_ms = {}
+        for cls in CLASSES:
+            ms, cnt, fpl = eng.profile_get(cls)
+            if cnt:
+                class_ms[cls] = {"ms": round(ms, 4), "launches": cnt, "kernel": eng.profile_kernel(cls) or None,
+                                 "tflops": round(fpl * cnt / (ms * 1e-3) / 1e12, 1) if ms > 0 and fpl > 0 else None}
+        dominant = max(GEMM_SHAPES, key=lambda c: class_ms.get(c, {"ms": 0.0})["ms"])
+        if use_dist:                                         # one decision for the whole job: rank 0's
+            pick = [dominant]
+            dist.broadcast_object_list(pick, src=0)
+            dominant = pick[0]
+        dom_kernel = eng.profile_kernel(dominant)
+        torch.cuda.synchronize()
+        if use_dist:
+            dist.barrier()
+        eng.profile_reset()
+        eng.profile_select(dominant)
+        eng.profile(True)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    # the FIRST timed step runs alone on engine 0 with the dominant class event-timed (50 launches; an event pair costs ~4 us
-    # of device time, 50 pairs per step would tax `value` by ~1.4 %): the roofline object describes the kernel with the chip
-    # to itself; from the second step on E steps are in flight
+    # the FIRST timed step runs alone on engine 0 (with --full: with the dominant class event-timed, 50 launches; an event pair
+    # costs ~4 us of device time, 50 pairs per step would tax `value` by ~1.4 %): the roofline object describes the kernel with
+    # the chip to itself; from the second step on E steps are in flight
     run_steps(0, 1)
     eng.sync()
-    eng.profile(False)
+    if args.full:
+        eng.profile(False)
     solo_ms = (time.perf_counter() - t0) * 1e3
     run_steps(1, args.steps - 1)
     for e_ in engs:
@@ -816,15 +850,70 @@ def main():
     if use_dist:
         dist.barrier()
     dt = time.perf_counter() - t0
-    eng.profile(False)
     rank_ms = None
-    allgather_ms = None
     if use_dist:
         mine_t = torch.tensor([dt], dtype=torch.float64, device=dev)
         every = torch.empty(world, dtype=torch.float64, device=dev)
         dist.all_gather_into_tensor(every, mine_t)             # every rank's own wall time of the timed region
         rank_ms = [float(x) / args.steps * 1e3 for x in every.cpu()]
         dt = max(float(x) for x in every.cpu())                # the job's time = the slowest rank's
+    last_e = (args.steps - 1) % E                           # the engine that ran the last timed step
+    res = engs[last_e].fetch()
+    # the timed steps must have produced a real transcript-shaped result: every utterance decoded, ids in range
+    assert res.L > 0 and res.token_ids.shape == (B, res.L), (res.L, res.token_ids.shape)
+    assert (res.token_ids >= 0).all() and (res.token_ids < eng.vocab).all()
+    assert (res.token_num > 0).all()
+    if args.dump_outputs and rank == 0:
+        outs = {"token_ids": res.token_ids, "token_num": res.token_num}
+        if res.cif_peak is not None:
+            outs["cif_peak"] = res.cif_peak
+        if use_dist:                                         # what every rank holds after the last timed step's all-gather
+            outs["token_ids_all_ranks"] = gathered["ids"].cpu().numpy()
+        dump_outputs(args.dump_outputs, outs)
+    if rank == 0:
+        audio_s = world * B * seconds * args.steps
+        value = audio_s / dt
+        flops_step = eng.last_flops()
+        out = {
+            "metric": "RTFx (audio-sec/wall-sec), %s offline, batch %dx%ds per GPU%s"
+                      % ("sensevoice-small" if sv else "paraformer-large", B, seconds,
+                         ", %d batches in flight per GPU" % E if E > 1 else ""),
+            "value": value, "unit": "audio-sec/wall-sec", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None,
+            "dtype": "int8 (u8 x u8 -> i32 Linear layers as model.int8.onnx; f16 attention)" if int8 else ("f32 as f16 pairs (hi + 2^-11 lo: 22-bit operands, three f16 MFMA products, fp32 accumulate); fp32-MFMA attention" if exact else ("f32" if fp32 else "f16")), "data": "synthetic",
+            "config": {"workload": "%s offline%s, batch %dx%d s synthetic 16 kHz per GPU "
+                                   "(BASELINE.json configs[%d]), seeded synthetic weights"
+                                   % ("sensevoice-small (use_itn on)" if sv else ("SeACo-paraformer, 21 hotwords" if args.model == "seaco" else "paraformer-large-zh"),
+                                      " + BiCIF timestamp head" if args.timestamp_head else "", B, seconds,
+                                      2 if sv else (4 if args.timestamp_head else (3 if world * B == 1024 else 1))),
+                       "global_batch": world * B, "samples_per_utt": samples, "T_lfr": eng.num_frames(samples), "L": int(res.L),
+                       "parallelism": "dp%d (utterance shards, no data-path collective)%s" % (
+                           world, "; %d batches in flight per GPU (engines on one device, consecutive steps alternate)" % E if E > 1 else ""),
+                       "steps_in_flight": E},
+            "ms_first_step_alone": solo_ms,          # the first timed step, run with nothing else in flight (--full: and 50 event pairs)
+            "rtf": dt / audio_s, "utt_per_s": world * B * args.steps / dt,
+            "rccl_ranks": world if use_dist else 0,
+            "per_rank_ms_per_step": {"min": min(rank_ms), "max": max(rank_ms), "all": [round(x, 4) for x in rank_ms]} if rank_ms else None,
+            "ids_sha1": ids_checksum(res.token_ids),   # rank 0's [B, L] ids of the last timed step
+            "token_num_sum": int(res.token_num.sum()),
+            "algorithmic_tflop_per_step_per_gpu": flops_step / 1e12,
+            "whole_path_tflops_per_gpu": flops_step * args.steps / dt / 1e12,
+            "whole_path_frac_of_mfma_peak": flops_step * args.steps / dt / 1e12 / PEAK_F16_TFLOPS,
+        }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out))
+        if use_dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        for e_ in engs:
+            e_.close()
+        return
+
+    eng.profile(False)
+    allgather_ms = None
+    if use_dist:
         # the hypothesis all-gather alone (outside the timed region; inside it the collective overlaps the next step)
         torch.cuda.synchronize()
         last_gathered = gathered["ids"]
@@ -834,7 +923,6 @@ def main():
         torch.cuda.synchronize()
         allgather_ms = (time.perf_counter() - ta) / 10 * 1e3
         gathered["ids"] = last_gathered                        # the check below is on the last TIMED step's gather
-    last_e = (args.steps - 1) % E                           # the engine that ran the last timed step
     # for comparison, outside the timed region: a few steps strictly one at a time on the engine that ran the last step
     serial_ms = None
     if E > 1:
@@ -858,15 +946,10 @@ def main():
                 engs[last_e].sync()
                 acc += time.perf_counter() - t1
             after_idle["%.1f" % idle_ms] = acc / 4 * 1e3
-    res = engs[last_e].fetch()
     ms_dom, n_dom, fpl_dom = eng.profile_get(dominant)
     for e_ in engs:                                          # every engine computed the same batch: concurrency must not change a single id
         r2 = e_.fetch()
         assert r2.L == res.L and (r2.token_ids == res.token_ids).all() and (r2.token_num == res.token_num).all()
-    # the timed steps must have produced a real transcript-shaped result: every utterance decoded, ids in range
-    assert res.L > 0 and res.token_ids.shape == (B, res.L), (res.L, res.token_ids.shape)
-    assert (res.token_ids >= 0).all() and (res.token_ids < eng.vocab).all()
-    assert (res.token_num > 0).all()
     if use_dist:
         g = gathered["ids"].cpu().numpy()                   # the last gather = the last timed step's
         assert g.shape == (world * B, LCAP) and (g[rank * B:(rank + 1) * B, :res.L] == res.token_ids).all()
@@ -919,9 +1002,6 @@ def main():
         host_ms = (time.perf_counter() - t1) / 3 * 1e3
 
     if rank == 0:
-        audio_s = world * B * seconds * args.steps
-        value = audio_s / dt
-        flops_step = eng.last_flops()
         args_steps_timed = 1                      # the dominant class is event-timed during the FIRST timed step only
         tail_share = 0.0
         avg_s = (ms_dom / max(n_dom, 1)) * 1e-3
@@ -945,48 +1025,23 @@ def main():
                      # (+ the f16 LayerNorm result when the row-complete kernel carries the next LayerNorm)
                      "gemm_ffn2": dom_rows * (Kk * 2 + Nn * 4 + Nn * 4 + (Nn * 2 if "gemm_rc" in dom_kernel else 0)) + Nn * Kk * 2}[dominant]
         headline = not int8 and not fp32 and not sv and args.model == "paraformer" and not args.timestamp_head and B == BATCH_PER_GPU and seconds == SECONDS
-        out = {
-            "metric": "RTFx (audio-sec/wall-sec), %s offline, batch %dx%ds per GPU%s"
-                      % ("sensevoice-small" if sv else "paraformer-large", B, seconds,
-                         ", %d batches in flight per GPU" % E if E > 1 else ""),
-            "value": value, "unit": "audio-sec/wall-sec", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None,
-            "dtype": "int8 (u8 x u8 -> i32 Linear layers as model.int8.onnx; f16 attention)" if int8 else ("f32 as f16 pairs (hi + 2^-11 lo: 22-bit operands, three f16 MFMA products, fp32 accumulate); fp32-MFMA attention" if exact else ("f32" if fp32 else "f16")), "data": "synthetic",
-            "config": {"workload": "%s offline%s, batch %dx%d s synthetic 16 kHz per GPU "
-                                   "(BASELINE.json configs[%d]), seeded synthetic weights"
-                                   % ("sensevoice-small (use_itn on)" if sv else ("SeACo-paraformer, 21 hotwords" if args.model == "seaco" else "paraformer-large-zh"),
-                                      " + BiCIF timestamp head" if args.timestamp_head else "", B, seconds,
-                                      2 if sv else (4 if args.timestamp_head else (3 if world * B == 1024 else 1))),
-                       "global_batch": world * B, "samples_per_utt": samples, "T_lfr": eng.num_frames(samples), "L": int(res.L),
-                       "parallelism": "dp%d (utterance shards, no data-path collective)%s" % (
-                           world, "; %d batches in flight per GPU (engines on one device, consecutive steps alternate)" % E if E > 1 else ""),
-                       "steps_in_flight": E},
-            "ms_first_step_alone": solo_ms,          # the first timed step, run with nothing else in flight (and 50 event pairs)
+        out.update({
             # first-class twin of `value`: the same job strictly one step at a time — the figure rounds 1-3 reported
             "ms_per_step_one_in_flight": serial_ms if E > 1 else dt / args.steps * 1e3,
             "serial_step_ms_after_idle_ms": after_idle,
             "value_one_in_flight": (world * B * seconds / (serial_ms * 1e-3)) if (E > 1 and serial_ms) else value,
-            "rtf": dt / audio_s, "utt_per_s": world * B * args.steps / dt,
-            "rccl_ranks": world if use_dist else 0,
-            "per_rank_ms_per_step": {"min": min(rank_ms), "max": max(rank_ms), "all": [round(x, 4) for x in rank_ms]} if rank_ms else None,
             "allgather_ms": allgather_ms,           # one [B, LCAP] int64 all_gather_into_tensor + sync, alone (untimed extra calls)
-            "ids_sha1": ids_checksum(res.token_ids),   # rank 0's [B, L] ids of the last timed step
             "ids_vs_fp32_oracle": ids_check,
             "ids_vs_int8_oracle": ids_check_int8,
             # north_star "identical token output", strictly: every position of every utterance and every token_num
             "identical_to_fp32_oracle": (bool(ids_check["agree_all_positions"] == 1.0 and ids_check["token_num_near_ties_resolved_differently"] == 0)
                                          if ids_check else None),
-            "token_num_sum": int(res.token_num.sum()),
             "host_audio_ms_per_batch": host_ms,     # one GPU's batch incl. H2D of the audio and D2H of the ids
             "host_audio_rtfx": B * seconds / (host_ms * 1e-3) if host_ms else None,
-            "algorithmic_tflop_per_step_per_gpu": flops_step / 1e12,
-            "whole_path_tflops_per_gpu": flops_step * args.steps / dt / 1e12,
-            "whole_path_frac_of_mfma_peak": flops_step * args.steps / dt / 1e12 / PEAK_F16_TFLOPS,
             "roofline": roofline_object(dom_kernel, dominant, dom_rows, Nn, Kk, what, fpl_dom, alg_bytes, avg_s, n_dom, int8,
                                         pmc_traffic(dom_kernel.split(" [")[0]) if headline else None),
             "class_ms_per_step": class_ms,            # untimed profiling step (HIP events around every launch)
-        }
+        })
         if world == 1 and not int8 and not fp32 and not args.no_exact and ids_check is not None and B in (BATCH_PER_GPU, 64):
             # north_star: "identical token output" — the token-identical mode on the same workload, same box, same run
             for e_ in engs:

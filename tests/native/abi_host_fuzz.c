@@ -1,5 +1,5 @@
 /* Random-input driver for the host-only entry points of the C-ABI (include/paraformer_hip.h: pf_host_*), linked against
-   a copy of the library built with -fsanitize=address,undefined (tools/sanitize_host.sh).  Every call must return a
+   a copy of the library built with AddressSanitizer + UBSan (tools/sanitize_host.sh).  Every call must return a
    status — never crash, never read or write outside what its arguments describe.
      usage: abi_host_fuzz <iterations> */
 #include <math.h>

@@ -1,6 +1,6 @@
 // Sanitizer harness for the copy helpers of the recognizer's staged uploads (csrc/copycrew.cpp): several caller threads copy
 // buffers of many sizes through ONE crew at the same time (each call splits into shares, helpers and callers take them), crews are
-// created and destroyed while idle, spinning and asleep.  Built with -fsanitize=thread / address by tests/test_native_host.py.
+// created and destroyed while idle, spinning and asleep.  Built with ThreadSanitizer / AddressSanitizer by tests/test_native_host.py.
 //   usage: copycrew_sanitize <iterations>
 #include <chrono>
 #include <cstdio>

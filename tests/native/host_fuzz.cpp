@@ -1,5 +1,5 @@
 // Mutation fuzz of the host-side parsers that read files a user hands over (csrc/json.h: PFW header / asr.json;
-// csrc/hostutil.cpp: asr.yaml, am.mvn, tokens, RIFF/WAVE, resampler, UTF-8), built with -fsanitize=address,undefined
+// csrc/hostutil.cpp: asr.yaml, am.mvn, tokens, RIFF/WAVE, resampler, UTF-8), built with AddressSanitizer + UBSan
 // (tests/test_native_host.py builds and runs it).  Every input either parses or throws pf::Error; nothing else.
 //   usage: host_fuzz <iterations> <scratch dir>
 #include <cstdio>

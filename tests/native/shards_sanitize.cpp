@@ -1,5 +1,5 @@
 // Sanitizer harness for the shard runner of pf_group (csrc/shards.cpp): start / run / fail / stop, thousands of times,
-// under -fsanitize=thread or -fsanitize=address (tests/test_shards_cpu.py builds and runs it).  Found in round 3: worker
+// under ThreadSanitizer or AddressSanitizer (tests/test_shards_cpu.py builds and runs it).  Found in round 3: worker
 // threads started inside the loop that was still growing `workers_` (a crash once in ~5 runs of the CPU suite).
 //   usage: shards_sanitize <iterations>
 #include <cstdio>

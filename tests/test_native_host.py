@@ -165,7 +165,7 @@ def test_recognizer_without_device_fails_loudly(tmp_path):
 @pytest.mark.timeout(300)
 def test_host_parsers_under_sanitizers(tmp_path):
     """csrc/json.h + csrc/hostutil.cpp (PFW header / asr.json / asr.yaml / am.mvn / RIFF-WAVE / resampler / UTF-8) built
-    with -fsanitize=address,undefined and fed mutated files (tests/native/host_fuzz.cpp): every input parses or is
+    with AddressSanitizer + UBSan on the host code and fed mutated files (tests/native/host_fuzz.cpp): every input parses or is
     rejected with a pf::Error, no report.  (Round 3: `"lfr_n": 1e400` used to be cast to int — now PF_ERR_FORMAT.)"""
     import shutil
     import subprocess
@@ -175,7 +175,8 @@ def test_host_parsers_under_sanitizers(tmp_path):
         pytest.skip("no hipcc")
     cs = os.path.join(root, "aliparaformerasr_amd", "csrc")
     exe = str(tmp_path / "host_fuzz")
-    b = subprocess.run([hipcc, "-x", "hip", "--offload-arch=gfx950", "-g", "-O1", "-fsanitize=address,undefined", "-fno-omit-frame-pointer",
+    b = subprocess.run([hipcc, "-x", "hip", "--offload-arch=gfx950", "-g", "-O1", "-fsanitize=address,undefined", "-fno-gpu-sanitize",
+                        "-fno-omit-frame-pointer",
                         "-std=c++17", "-I" + cs, os.path.join(root, "tests", "native", "host_fuzz.cpp"), os.path.join(cs, "hostutil.cpp"),
                         "-o", exe], capture_output=True, text=True)
     if b.returncode != 0:
@@ -191,7 +192,7 @@ def test_host_parsers_under_sanitizers(tmp_path):
 @pytest.mark.parametrize("san", ["thread", "address"])
 def test_copy_helpers_under_sanitizers(san, tmp_path):
     """csrc/copycrew.cpp (the helper threads that share the host side of a staged AddSamples upload: spinning and sleeping helpers,
-    shares taken by helpers and callers alike, several callers on one crew) under -fsanitize=thread / address: every copy exact,
+    shares taken by helpers and callers alike, several callers on one crew) under ThreadSanitizer / AddressSanitizer: every copy exact,
     nothing written outside the destination, no report."""
     import shutil
     import subprocess
@@ -201,7 +202,8 @@ def test_copy_helpers_under_sanitizers(san, tmp_path):
         pytest.skip("no hipcc")
     exe = str(tmp_path / ("copycrew_" + san))
     cs = os.path.join(root, "aliparaformerasr_amd", "csrc")
-    b = subprocess.run([hipcc, "-x", "hip", "--offload-arch=gfx950", "-g", "-O1", "-fsanitize=" + san, "-fno-omit-frame-pointer", "-std=c++17",
+    b = subprocess.run([hipcc, "-x", "hip", "--offload-arch=gfx950", "-g", "-O1", "-fsanitize=" + san, "-fno-gpu-sanitize",
+                        "-fno-omit-frame-pointer", "-std=c++17",
                         "-I" + cs, os.path.join(root, "tests", "native", "copycrew_sanitize.cpp"), os.path.join(cs, "copycrew.cpp"),
                         "-o", exe, "-lpthread"], capture_output=True, text=True)
     if b.returncode != 0:
@@ -216,7 +218,7 @@ def test_copy_helpers_under_sanitizers(san, tmp_path):
 @pytest.mark.skipif(not os.environ.get("PF_SANITIZE_FULL"), reason="set PF_SANITIZE_FULL=1: rebuilds the whole library with ASan + UBSan (minutes)")
 @pytest.mark.timeout(3000)
 def test_every_host_entry_point_under_sanitizers(tmp_path):
-    """tools/sanitize_host.sh: the full library with -fsanitize=address,undefined, every pf_host_* entry point driven
+    """tools/sanitize_host.sh: the full library's host code under AddressSanitizer + UBSan, every pf_host_* entry point driven
     with random arguments (tests/native/abi_host_fuzz.c), plus the shard-runner and parser harnesses."""
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

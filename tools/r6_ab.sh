@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 cp aliparaformerasr_amd/csrc/$F /tmp/new_$F
 run() {
   for e in 1 2; do
-    python bench.py --steps 30 --warmup 5 --in-flight $e --no-cpu-baseline --no-via-recognizer --no-exact "$@" 2>/dev/null | python -c "
+    python bench.py --full --steps 30 --warmup 5 --in-flight $e --no-cpu-baseline --no-via-recognizer --no-exact "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('   in-flight $e: ms/step %.3f  dominant %.1f us  classes' % (d['ms_per_step'], d['roofline']['avg_us']), {k:round(v['ms'],3) for k,v in d['class_ms_per_step'].items() if v['ms']>0.2})"
