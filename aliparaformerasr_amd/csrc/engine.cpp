@@ -56,29 +56,11 @@ Engine::Engine(const pf_engine_config& cfg) {
            "math_mode must be 0 (f16 MFMA), 1 (fp32 MFMA), 2 (dynamic int8 as model.int8.onnx, int8 MFMA) or 3 (exact: split-f16 products)");
   fp32_mode_ = cfg.math_mode == 1 || cfg.math_mode == 3;
   x3_mode_ = cfg.math_mode == 3;
-  // math_mode 3 keeps the fp32-MFMA attention by default: with x3 operands in the attention too (PF_X3_ATTN=1: 47.0 instead of
-  // 50.8 ms per 32 x 30 s) 2 of the 5344 ids of the benchmark batch leave the fp32 oracle's — scores are exponentiated, and a
-  // 22-bit product is 4x an fp32 product's error; the Linears tolerate it (identity holds), the softmax does not
-  { const char* e = getenv("PF_X3_ATTN"); if (e && e[0]) x3_attn_ = atoi(e); }
-  { const char* e = getenv("PF_X3_FUSE"); if (e && e[0] == '0') x3_fuse_ = false; }
-  { const char* e = getenv("PF_X3_ONE"); if (e && e[0] == '0') x3_one_ = false; }
   int8_mode_ = cfg.math_mode == 2;
-  { const char* e = getenv("PF_NO_RC"); no_rc_ = e && e[0] == '1'; }
-  { const char* e = getenv("PF_LSTM_STEPS"); lstm_steps_ = e && e[0] == '1'; }
-  { const char* e = getenv("PF_DEC_FUSE"); if (e && e[0]) dec_fuse_ = atoi(e) & 7; }
-  { const char* e = getenv("PF_DEC_H32"); dec_h32_ = e && e[0] == '1'; }
-  { const char* e = getenv("PF_SMALL_NOFUSE"); no_small_fuse_ = e && e[0] == '1'; }   // A/B: short-input GEMMs without the FSMN epilogue / LayerNorm-in-reduction forms   // A/B switch for tools/: decoder launch fusions
-  { const char* e = getenv("PF_QKV_SPLIT"); if (e && e[0]) qkv_split_ = e[0] != '0'; }   // A/B: Q | K blocked + V row-major from the 256 x 192 kernel (k_gemm_qkv.hip)
   { const char* e = getenv("PF_QKV_MIN"); if (e && e[0]) qkv_split_min_tiles_ = atoi(e); }
   { const char* e = getenv("PF_QKV_FILL"); if (e && e[0]) qkv_split_min_fill_ = atoi(e); }
-  { const char* e = getenv("PF_RC_FFN2"); if (e && e[0]) rc_ffn2_ = e[0] != '0'; }   // A/B switch for tools/: the unfused encoder sequence
-  { const char* e = getenv("PF_FFN_FUSED"); if (e && e[0]) ffn_fused_ = e[0] != '0'; }   // A/B: the whole FFN block in one launch (k_ffn.hip)
   { const char* e = getenv("PF_FFN_MIN"); if (e && e[0]) ffn_fused_min_rows_ = atoi(e); }
-  { const char* e = getenv("PF_DEC_FFN"); if (e && e[0]) dec_ffn_fused_ = e[0] != '0'; }
-  { const char* e = getenv("PF_DEC_OUT_CHAIN"); if (e && e[0]) dec_out_chain_ = e[0] != '0'; }
-  { const char* e = getenv("PF_DEC_MID"); if (e && e[0]) dec_mid_ = e[0] != '0'; }     // A/B: finishing pass + norm2 + FSMN + norm3 + q in one launch (k_decmid.hip)
-  { const char* e = getenv("PF_ATTN_FFN"); if (e && e[0]) attn_ffn_ = e[0] != '0'; }
-  { const char* e = getenv("PF_QKV_TAIL"); if (e && e[0]) qkv_tail_ = e[0] != '0'; }
+  { const char* e = getenv("PF_DEC_MID"); if (e && e[0]) dec_mid_ = e[0] != '0'; }     // the decoder's middle as the launches it replaces (tests compare both forms)
 
   // host-only validation BEFORE anything is uploaded (a bad am.mvn must not cost a 0.9 GB upload per retry)
   std::vector<float> shift, scale;
@@ -478,7 +460,7 @@ void Engine::load_weights(const pf_engine_config& cfg) {
     L.w1 = make_lin(p + ".ffn.w1", true);
     L.w2 = make_lin(p + ".ffn.w2", true);
     PF_CHECK(L.qkv.K == d_in && L.qkv.N == 3 * D, PF_ERR_FORMAT, "weights: qkv shape mismatch in " + p);
-    if (qkv_split_ && D == 512 && mc_.heads == 4 && !fp32_mode_ && !int8_mode_) {
+    if (!fp32_mode_ && !int8_mode_) {
       // the same weight with its rows in the tile order of gemm_qkvp_kernel (k_gemm_qkv.hip)
       L.qkv_p = (half_t*)dalloc((size_t)1536 * L.qkv.Kpad * 2);
       L.qkv_bias_p = (float*)dalloc(1536 * 4);
@@ -486,14 +468,14 @@ void Engine::load_weights(const pf_engine_config& cfg) {
     }
     PF_CHECK(L.out.N == D && L.out.K == D && L.w1.K == D && L.w1.N == mc_.ffn && L.w2.N == D && L.w2.K == L.w1.N,
              PF_ERR_FORMAT, "weights: attn.out / ffn shape mismatch in " + p);
-    if (ffn_fused_ && ffn_fused_applicable(D, mc_.ffn) && !fp32_mode_ && !int8_mode_ && L.w1.w && L.w2.w) {
+    if (ffn_fused_applicable(D, mc_.ffn) && !fp32_mode_ && !int8_mode_) {
       // W1 and W2 once more, in the fragment order the fused FFN kernel streams (4 MiB per layer)
       L.ffn_wt = (half_t*)dalloc(ffn_fused_weight_bytes());
       launch_ffn_retile(stream_, L.w1.w, L.w1.Kpad, L.w2.w, L.w2.Kpad, L.ffn_wt);
-      if (attn_ffn_ && L.out.w && L.out.bias && mc_.kernel == 11) {
+      if (mc_.kernel == 11) {
         L.out_wt = (half_t*)dalloc(ffn_outproj_weight_bytes());
         launch_ffn_retile_out(stream_, L.out.w, L.out.Kpad, L.out_wt);
-        if (qkv_tail_ && L.qkv_p && L.qkv.Kpad == D && L.qkv.bias) {
+        if (L.qkv.Kpad == D) {
           L.qkv_t = (half_t*)dalloc(3 * ffn_outproj_weight_bytes());
           for (int part = 0; part < 3; ++part)
             launch_ffn_retile_out(stream_, L.qkv.w + (size_t)part * D * L.qkv.Kpad, L.qkv.Kpad,
@@ -647,7 +629,7 @@ void Engine::load_weights(const pf_engine_config& cfg) {
       L.kv32.w32 = kvw.dev; L.kv32.bias = kvbias.dev; L.kv32.N = 2 * D; L.kv32.K = D;
       L.kv32.w = dec_kv_all_.w + (size_t)i * 2 * D * D; L.kv32.Kpad = D;
       L.ffn_img = make_dec_ffn_image(L.w1, L.ffn_norm, L.w2);
-      if (L.ffn_img && dec_out_chain_ && L.out.w && L.out.bias && L.out.Kpad == D) {
+      if (L.ffn_img) {
         L.out_wt = (half_t*)dalloc(ffn_outproj_weight_bytes());
         launch_ffn_retile_out(stream_, L.out.w, L.out.Kpad, L.out_wt);
       }
@@ -742,7 +724,7 @@ void Engine::load_weights(const pf_engine_config& cfg) {
 // The decoder's FFN block for the split form of ffn_fused_kernel (k_ffn.hip): W1, gamma_F (.) W2 (from the fp32 tensor, one
 // rounding), b1, colsum(gamma_F (.) W2), W2 beta_F.  Null when the form does not apply (mode, shape).
 half_t* Engine::make_dec_ffn_image(const Lin& w1, const LNp& fn, const Lin& w2) {
-  if (!dec_ffn_fused_ || !ffn_fused_ || fp32_mode_ || int8_mode_ || !ffn_fused_applicable(w1.K, w1.N) || w2.N != w1.K || w2.K != w1.N ||
+  if (fp32_mode_ || int8_mode_ || !ffn_fused_applicable(w1.K, w1.N) || w2.N != w1.K || w2.K != w1.N ||
       !w1.w || !w1.bias || !w2.w32 || w2.bias || w1.Kpad != w1.K || fn.D != w1.N)
     return nullptr;
   half_t* img = (half_t*)dalloc(ffn_dec_image_bytes());
@@ -1048,15 +1030,48 @@ void Engine::build_pe(int T) {
   pe_T_ = Tn;
 }
 
-// One SAN-M encoder layer = 5 launches: [LayerNorm fused into the previous launch] QKV GEMM -> attention ->
-// row-complete out-projection (+ bias + residual + FSMN memory from the V slice + LayerNorm norm2 -> xn16) ->
-// FFN-up (blocked hidden) -> row-complete FFN-down (+ bias + residual + the NEXT LayerNorm `nx` -> its outputs).
+// One SAN-M encoder layer.  Fused layer tail = 3 launches (2 with the Q | K | V tail of the previous layer): QKV GEMM ->
+// attention -> out-projection + FSMN memory + norm2 + FFN block + the NEXT LayerNorm `nx`.  Row-complete form = 5 launches:
+// [LayerNorm fused into the previous launch] QKV GEMM -> attention -> row-complete out-projection (+ bias + residual +
+// FSMN memory from the V slice + LayerNorm norm2 -> xn16) -> FFN-up (blocked hidden) -> row-complete FFN-down (+ bias +
+// residual + `nx` -> its outputs).  Short-input and un-fused forms: see the predicates below.
 // Entry: xn16_ holds LayerNorm norm1 of the residual stream (written by the previous layer's FFN-down, by the
 // position-encoding kernel for layer 0, or by the stand-alone LayerNorm for the first tp layer).
 void Engine::enc_layer(const EncLayer& L, int first, const float* speech_dev, int B, int T, const EncNext& nx) {
   const int D = mc_.d_model, M = B * T, F = mc_.ffn;
   const float qscale = 1.0f / std::sqrt((float)(D / mc_.heads));
   const int lda = first ? L.qkv.Kpad : D;
+  // ---- which form this layer takes, from (M, T), the FSMN kernel size, the FFN width and the layer's weight images
+  // short inputs (M <= 512 rows): every GEMM goes to k_gemm_small.hip, which has no row-complete epilogue and no blocked
+  // layout but takes the FSMN memory as an epilogue term and the LayerNorm behind FFN-down in its reduction
+  const bool small = M <= gemm_small_max_rows() && small_ws_;
+  // the split FFN-down form must really apply to (M, F) — e.g. F = 4096 needs 16 splits, whose partials outgrow the
+  // scratch beyond 256 rows: then the regular kernels run instead of failing the utterance
+  auto split_ok = [&](int rows, const Lin& w2, const half_t* Aop) {
+    GemmSmallArgs t{};
+    t.M = rows; t.N = w2.N; t.K = w2.Kpad; t.A = Aop; t.lda = w2.Kpad; t.W = w2.w; t.ldw = w2.Kpad; t.ws = small_ws_;
+    t.post_ln_g = nx.ln.g; t.post_ln_b = nx.ln.b;
+    return gemm_small_applicable(t);
+  };
+  const bool short_form = small && F > 576 && mc_.kernel == 11 && split_ok(M, L.w2, h16_);
+  // row-complete form: out-projection and FFN-down carry bias + residual + (FSMN memory) + the LayerNorm behind them.
+  // Otherwise (FSMN kernel size other than 11, utterances shorter than 8 frames, a short input the form above does not
+  // take) the un-fused sequence runs
+  const bool rc = mc_.kernel == 11 && T >= 8 && !small;
+  // Q | K blocked + V row-major from the persistent 256 x 192 kernel when the row-complete out-projection (the reader of
+  // the row-major V) runs and the launch has at least a round of tiles
+  // (chosen by idle rounds: 32 x 500 rows are 504 tiles = 1.97 rounds on 256 CUs — 1.88 vs 2.06 ms per step for the 50 layers;
+  // SenseVoice's 10 944 rows are 344 tiles = 1.34 rounds: 2.45 vs 2.30 ms alone, but 10.19 vs 10.73 ms per step with two steps in
+  // flight — the second engine's kernels take the CUs its short second round leaves — so the fill bar is 60 %)
+  const int qt = 8 * cdiv(M, 256);
+  const bool split = rc && L.qkv_p && qt >= qkv_split_min_tiles_ && qt * 100 >= qkv_split_min_fill_ * (int)round_up(qt, cus_) &&
+                     gemm_qkvp_applicable(M, L.qkv.Kpad, lda, L.qkv.Kpad, D);
+  // fused layer tail: everything behind the attention in one launch per 64-row tile (out_wt is only built beside ffn_wt)
+  const bool fused = rc && L.out_wt && M >= ffn_fused_min_rows_;
+  // ... with the NEXT layer's Q | K | V projection behind the block when that layer would take the same (blocked-layout)
+  // path on the same rows: LayerNorm_next(x) then never visits HBM either
+  const bool tail = fused && split && nx.next && nx.next->qkv_t && nx.next->out_wt && nx.n16 == xn16_ && !nx.n32;
+
   if (first == 1) {
     prof_begin("layernorm", 0);
     launch_posenc_ln_tab(stream_, speech_dev, B, T, mc_.feat_dim, std::sqrt((float)D), (const float*)ws_pe_.p,
@@ -1074,18 +1089,7 @@ void Engine::enc_layer(const EncLayer& L, int first, const float* speech_dev, in
   a.q_rstride = a.k_rstride = a.v_rstride = 3 * D;
   a.o_bstride = (int64_t)T * D; a.o_rstride = D;
   a.B = B; a.H = mc_.heads; a.Lq = T; a.Lk = T;
-  // short inputs (M <= 512 rows): every GEMM goes to k_gemm_small.hip, which has no row-complete epilogue and no blocked
-  // layout but takes the FSMN memory as an epilogue term and the LayerNorm behind FFN-down in its reduction
-  const bool small = M <= gemm_small_max_rows() && small_ws_;
-  // the split FFN-down form must really apply to (M, F) — e.g. F = 4096 needs 16 splits, whose partials outgrow the
-  // scratch beyond 256 rows: then the regular kernels run instead of failing the utterance
-  auto split_ok = [&](int rows, const Lin& w2, const half_t* Aop) {
-    GemmSmallArgs t{};
-    t.M = rows; t.N = w2.N; t.K = w2.Kpad; t.A = Aop; t.lda = w2.Kpad; t.W = w2.w; t.ldw = w2.Kpad; t.ws = small_ws_;
-    t.post_ln_g = nx.ln.g; t.post_ln_b = nx.ln.b;
-    return gemm_small_applicable(t);
-  };
-  if (small && D == 512 && F % 64 == 0 && F > 576 && mc_.kernel == 11 && !no_small_fuse_ && split_ok(M, L.w2, h16_)) {
+  if (short_form) {
     // 7 launches: QKV | attention | out-projection + FSMN memory + residual | norm2 | FFN-up | FFN-down partials | their
     // sum + bias + residual + the LayerNorm behind the block (next norm1 / after_norm)
     gemm("gemm_qkv", L.qkv, xn16_, lda, M, nullptr, 0, qkv16_, 3 * D, nullptr, 0, nullptr, 0, false, D, qscale);
@@ -1108,17 +1112,8 @@ void Engine::enc_layer(const EncLayer& L, int first, const float* speech_dev, in
     gemm_small_call("gemm_ffn2", L.w2, dn);
     return;
   }
-  const bool rc = mc_.kernel == 11 && T >= 8 && !no_rc_ && !small;
-  // Q | K blocked + V row-major from the persistent 256 x 192 kernel when the row-complete out-projection (the reader of
-  // the row-major V) runs and the launch has at least a round of tiles
   const half_t* v16 = qkv16_ + 2 * D;
   int ldv = 3 * D;
-  // (chosen by idle rounds: 32 x 500 rows are 504 tiles = 1.97 rounds on 256 CUs — 1.88 vs 2.06 ms per step for the 50 layers;
-  // SenseVoice's 10 944 rows are 344 tiles = 1.34 rounds: 2.45 vs 2.30 ms alone, but 10.19 vs 10.73 ms per step with two steps in
-  // flight — the second engine's kernels take the CUs its short second round leaves — so the fill bar is 60 %)
-  const int qt = 8 * cdiv(M, 256);
-  const bool split = rc && L.qkv_p && qt >= qkv_split_min_tiles_ && qt * 100 >= qkv_split_min_fill_ * (int)round_up(qt, cus_) &&
-                     gemm_qkvp_applicable(M, L.qkv.Kpad, lda, L.qkv.Kpad, D);
   const bool pre = qkv_done_;                                  // written by the previous layer's launch (its Q | K | V tail)
   qkv_done_ = false;
   PF_CHECK(!pre || split, PF_ERR_DEVICE, "encoder: a projected Q | K | V without its consumer");
@@ -1141,7 +1136,7 @@ void Engine::enc_layer(const EncLayer& L, int first, const float* speech_dev, in
   prof_begin("attn_self", 4.0 * B * (double)T * T * D);
   launch_attention(stream_, a);
   prof_end("attn_self");
-  if (rc && L.ffn_wt && L.out_wt && M >= ffn_fused_min_rows_) {
+  if (fused) {
     // out-projection + bias + residual + FSMN memory + norm2 + the whole FFN block + the NEXT LayerNorm: ONE launch per 64-row
     // tile (k_ffn.hip, OP = 1): norm2's result never leaves LDS, x_mid goes through a scratch the same lanes read back
     FfnFusedArgs f{};
@@ -1150,9 +1145,6 @@ void Engine::enc_layer(const EncLayer& L, int first, const float* speech_dev, in
     f.Wt = L.ffn_wt; f.b1 = L.w1.bias; f.b2 = L.w2.bias; f.M = M;
     f.resid = first ? nullptr : x_; f.ldr = D; f.out_x = nx.keep_x ? x_ : nullptr; f.ldx = D;
     f.ln_g = nx.ln.g; f.ln_b = nx.ln.b; f.eps = 1e-12f; f.out_n16 = nx.n16; f.ldn16 = D; f.out_n32 = nx.n32; f.ldn32 = D;
-    // the NEXT layer's Q | K | V projection behind the block when that layer would take the same (blocked-layout) path on
-    // the same rows: LayerNorm_next(x) then never visits HBM either
-    const bool tail = split && nx.next && nx.next->qkv_t && nx.next->ffn_wt && nx.next->out_wt && nx.n16 == xn16_ && !nx.n32;
     double flops = 2.0 * M * (double)D * D + 4.0 * M * (double)D * F;
     if (tail) {
       f.Wqt = nx.next->qkv_t; f.bq = nx.next->qkv.bias; f.out_qk = qkv16_; f.out_v = vbufs[v_pp_ ^ 1]; f.ldvo = D; f.qscale = qscale;
@@ -1175,7 +1167,6 @@ void Engine::enc_layer(const EncLayer& L, int first, const float* speech_dev, in
     launch_gemm_rc(stream_, g);
     prof_end("gemm_out");
   } else {
-    // fallback (FSMN kernel size other than 11, utterances shorter than 8 frames, PF_NO_RC=1): the unfused sequence
     prof_begin("fsmn", 0);
     launch_fsmn_enc(stream_, qkv16_ + 2 * D, 3 * D, L.fsmn_wT, B, T, D, mc_.kernel, fsm_);
     prof_end("fsmn");
@@ -1184,26 +1175,13 @@ void Engine::enc_layer(const EncLayer& L, int first, const float* speech_dev, in
     launch_layernorm(stream_, x_, M, D, L.norm2.g, L.norm2.b, xn16_, D, nullptr, 0);
     prof_end("layernorm");
   }
-  if (rc && L.ffn_wt && M >= ffn_fused_min_rows_) {
-    // the whole feed-forward block + the NEXT LayerNorm in one launch (k_ffn.hip, round 5): the [M, 2048] hidden stays in
-    // LDS.  Measured against gemm_bigp_kernel + the row-complete FFN-down: see DESIGN.md 4.1g; PF_FFN_FUSED=0 restores them
-    FfnFusedArgs f{};
-    f.A = xn16_; f.lda = D; f.Wt = L.ffn_wt; f.b1 = L.w1.bias; f.b2 = L.w2.bias; f.M = M;
-    f.resid = x_; f.ldr = D; f.out_x = nx.keep_x ? x_ : nullptr; f.ldx = D;
-    f.ln_g = nx.ln.g; f.ln_b = nx.ln.b; f.eps = 1e-12f; f.out_n16 = nx.n16; f.ldn16 = D; f.out_n32 = nx.n32; f.ldn32 = D;
-    prof_begin("gemm_ffn", 4.0 * M * (double)D * F);
-    launch_ffn_fused(stream_, f);
-    prof_end("gemm_ffn");
-    return;
-  }
   // the FFN hidden lives in the blocked activation layout (kernels.h): FFN-up stores its fragments as whole
   // lines without the LDS transposition, FFN-down's LDS-DMA reads 1 KiB contiguous pieces
-  const int blk = (F % 64 == 0 && !small) ? 1 : 0;
+  const int blk = small ? 0 : 1;
   gemm("gemm_ffn1", L.w1, xn16_, D, M, nullptr, 0, h16_, F, nullptr, 0, nullptr, 0, true, 0, 1.f, true, blk);
-  if (rc && rc_ffn2_ && blk) {
-    // row-complete FFN-down (+ the next LayerNorm), default since round 4: 53.6 us against 47.6 + 9-11 us for the persistent
-    // 256 x 128 kernel + its LayerNorm launch (same box, same session: 12.86 -> 12.67 ms per step with one step in flight,
-    // 11.32 -> 11.06 with two; round 3 had measured the opposite, 67.7 vs 57.5 us).  PF_RC_FFN2=0 restores the two launches.
+  if (rc) {
+    // row-complete FFN-down (+ the next LayerNorm): 53.6 us against 47.6 + 9-11 us for the persistent 256 x 128 kernel +
+    // its LayerNorm launch
     GemmRcArgs f{};
     f.A = h16_; f.lda = F; f.a_blocked = 1; f.W = L.w2.w; f.ldw = L.w2.Kpad; f.bias = L.w2.bias; f.M = M; f.K = L.w2.Kpad;
     f.resid = x_; f.ldr = D; f.out_x = nx.keep_x ? x_ : nullptr; f.ldx = D;
@@ -1270,21 +1248,13 @@ void Engine::encoder(const float* speech_dev, int B, int T, bool pre_encoded) {
 // FFN-up of a decoder block and the LayerNorm(F) behind it: leaves the normalised hidden in h16.  FFN-up writes the
 // hidden as f16 (ReLU output, one rounding — the oracle's 16-bit mode rounds at the same point) and the LayerNorm runs
 // in place on it: 40 -> 18 us for the GEMM (no fp32 row-segment epilogue) and a third of the LayerNorm's bytes at
-// M = 5344.  PF_DEC_H32=1 keeps the fp32 round trip (h32 must then be non-null).
-void Engine::dec_ffn_hidden(const char* cls, const Lin& w1, const LNp& fn, const half_t* xn16, int lda, int rows, float* h32,
-                            half_t* h16) {
+// M = 5344.
+void Engine::dec_ffn_hidden(const char* cls, const Lin& w1, const LNp& fn, const half_t* xn16, int lda, int rows, half_t* h16) {
   const int F = w1.N;
-  if (dec_h32_ && h32) {
-    gemm(cls, w1, xn16, lda, rows, h32, F, nullptr, 0, nullptr, 0, nullptr, 0, true, 0, 1.f);
-    prof_begin("layernorm", 0);
-    launch_layernorm(stream_, h32, rows, F, fn.g, fn.b, h16, F, nullptr, 0);
-    prof_end("layernorm");
-  } else {
-    gemm(cls, w1, xn16, lda, rows, nullptr, 0, h16, F, nullptr, 0, nullptr, 0, true, 0, 1.f);
-    prof_begin("layernorm", 0);
-    launch_layernorm_f16(stream_, h16, rows, F, fn.g, fn.b, h16);
-    prof_end("layernorm");
-  }
+  gemm(cls, w1, xn16, lda, rows, nullptr, 0, h16, F, nullptr, 0, nullptr, 0, true, 0, 1.f);
+  prof_begin("layernorm", 0);
+  launch_layernorm_f16(stream_, h16, rows, F, fn.g, fn.b, h16);
+  prof_end("layernorm");
 }
 
 void Engine::predictor_and_decoder(int B, int T, bool want_logits) {
@@ -1333,14 +1303,14 @@ void Engine::predictor_and_decoder(int B, int T, bool want_logits) {
   size_t off = 0;
   auto carve = [&](size_t bytes) { size_t o = off; off += round_up((int64_t)bytes, (int64_t)kAlign); return o; };
   const size_t o_x = carve(Mdp * D * 4), o_xn = carve(Mdp * D * 2);
-  const size_t o_h32 = carve(Mdp * F * 4), o_h16 = carve(Mdp * F * 2), o_t = carve(Mdp * D * 4), o_tn = carve(Mdp * D * 4);
+  const size_t o_h16 = carve(Mdp * F * 2), o_t = carve(Mdp * D * 4), o_tn = carve(Mdp * D * 4);
   const size_t o_q = carve(Mdp * D * 2), o_ctx = carve(Mdp * D * 2), o_lg = carve((size_t)Mdp * round_up(V, 4) * 4), o_ids = carve((size_t)Md * 8);
   const size_t o_x2 = carve(Mdp * D * 4);
   ensure(ws_dec_, off);
   char* base = (char*)ws_dec_.p;
   float* xd = (float*)(base + o_x); half_t* xdn16 = (half_t*)(base + o_xn);
   float* xd_alt = (float*)(base + o_x2);               // the residual stream ping-pongs when the out-projection rides in front of the next FFN launch
-  float* hd32 = (float*)(base + o_h32); half_t* hd16 = (half_t*)(base + o_h16);
+  half_t* hd16 = (half_t*)(base + o_h16);
   float* t32 = (float*)(base + o_t); float* tn32 = (float*)(base + o_tn);
   half_t* qd16 = (half_t*)(base + o_q); half_t* ctxd16 = (half_t*)(base + o_ctx);
   logits_ = (float*)(base + o_lg); ids_dev_ = (int64_t*)(base + o_ids);
@@ -1360,23 +1330,20 @@ void Engine::predictor_and_decoder(int B, int T, bool want_logits) {
     PF_HIP(hipMemcpyAsync(e0, xd, (size_t)Md * D * 4, hipMemcpyDeviceToDevice, stream_));
   }
 
-  // Decoder layer = 9 launches: norm1 | FFN-up (f16 hidden) | LayerNorm(2048) in place | FFN-down | norm2 | FSMN memory +
-  // norm3 (one kernel, dec_fuse_ bit 1) | q | cross attention | out-projection + residual.  The row-complete GEMM can
-  // take norm2 (bit 4) and the next block's norm1 (bit 2) as epilogues, but at M = B*L = 5344 it runs on 84 CUs only:
-  // measured 47 vs 29.5 + 5.6 us (FFN-down) and 21 vs 16 + 5.6 us (out-projection), so both stay off (PF_DEC_FUSE=7
-  // enables them for experiments).
-  bool dsmall = Md <= gemm_small_max_rows() && small_ws_ && D == 512 && F % 64 == 0 && F > 576 && !no_small_fuse_;
+  // Generic decoder layer = 9 launches: norm1 | FFN-up (f16 hidden) | LayerNorm(2048) in place | FFN-down | norm2 | FSMN
+  // memory + norm3 (one kernel) | q | cross attention | out-projection + residual.
+  // ---- which forms the decoder takes, from Md, the FFN width and the layers' weight images
+  // short inputs: the split FFN-down form of k_gemm_small.hip with the LayerNorm behind the block in its reduction
+  bool dsmall = Md <= gemm_small_max_rows() && small_ws_ && F > 576;
   if (dsmall) {                                        // the split FFN-down form must apply to (Md, F), else the regular kernels
     GemmSmallArgs t{};
     t.M = Md; t.N = D; t.K = dec_final_w2_.Kpad; t.A = hd16; t.lda = F; t.W = dec_final_w2_.w; t.ldw = dec_final_w2_.Kpad;
     t.ws = small_ws_; t.post_ln_g = dec_after_.g; t.post_ln_b = dec_after_.b;
     dsmall = gemm_small_applicable(t);
   }
-  const bool f_fsmn = (dec_fuse_ & 1) != 0, f_out = (dec_fuse_ & 2) != 0 && !dsmall, f_ffn2 = (dec_fuse_ & 4) != 0;
-  bool have_n1 = false;                                // xdn16 already holds norm1(xd) of the coming block
   // out-projection chain (k_ffn.hip, OP = 2): layer i's cross-attention out-projection + residual + the next norm1 run in
   // front of the NEXT block's split FFN launch; `pend` = the layer whose context (ctxd16) still waits for its projection
-  bool chain = dec_out_chain_ && !dsmall && dec_final_img_ != nullptr;
+  bool chain = !dsmall && dec_final_img_ != nullptr;
   for (int i = 0; i < nd && chain; ++i) chain = dec_[i].ffn_img && dec_[i].out_wt;
   const DecLayer* pend = nullptr;
   // ffn_dec: norm1 -> w_1 + ReLU -> LayerNorm(2048) -> w_2 (no bias) [-> LayerNorm `post`]; leaves t32 (unfused) or
@@ -1386,12 +1353,11 @@ void Engine::predictor_and_decoder(int B, int T, bool want_logits) {
     if (img && !dsmall) {
       // norm1 | the whole block in the split form of the fused FFN kernel + its finishing pass (LayerNorm over the hidden
       // applied from row statistics, then `post`): 2 launches for FFN-up | LayerNorm(2048) | FFN-down | LayerNorm
-      if (!have_n1 && !pend) {
+      if (!pend) {
         prof_begin("layernorm", 0);
         launch_layernorm(stream_, xd, Md, D, n1.g, n1.b, xdn16, D, nullptr, 0);
         prof_end("layernorm");
       }
-      have_n1 = false;
       ensure(ws_decffn_, ffn_dec_workspace_bytes(Md));
       FfnDecArgs f{};
       f.A = xdn16; f.lda = D; f.img = img; f.ws = ws_decffn_.p; f.M = Md; f.eps_hidden = 1e-12f;
@@ -1407,47 +1373,32 @@ void Engine::predictor_and_decoder(int B, int T, bool want_logits) {
       if (pend) { std::swap(xd, xd_alt); pend = nullptr; }
       return;
     }
+    // generic and short-input forms: norm1 | FFN-up | LayerNorm(2048) in place | FFN-down ...
+    prof_begin("layernorm", 0);
+    launch_layernorm(stream_, xd, Md, D, n1.g, n1.b, xdn16, D, nullptr, 0);
+    prof_end("layernorm");
+    dec_ffn_hidden("gemm_dec_ffn1", w1, fn, xdn16, D, Md, hd16);
     if (dsmall) {
-      // short inputs: norm1 | FFN-up | LayerNorm(2048) in place | FFN-down partials | their sum + the LayerNorm behind it
-      prof_begin("layernorm", 0);
-      launch_layernorm(stream_, xd, Md, D, n1.g, n1.b, xdn16, D, nullptr, 0);
-      prof_end("layernorm");
-      dec_ffn_hidden("gemm_dec_ffn1", w1, fn, xdn16, D, Md, hd32, hd16);
+      // ... as partials | their sum + the LayerNorm behind it
       GemmSmallArgs dn{};
       dn.M = Md; dn.A = hd16; dn.lda = F;
       dn.post_ln_g = post.g; dn.post_ln_b = post.b; dn.post_n16 = n16; dn.ldn16 = D; dn.post_n32 = n32; dn.ldn32 = D;
       gemm_small_call("gemm_dec_ffn2", w2, dn, false);
-      have_n1 = false;
       return;
     }
-    if (!have_n1) {
-      prof_begin("layernorm", 0);
-      launch_layernorm(stream_, xd, Md, D, n1.g, n1.b, xdn16, D, nullptr, 0);
-      prof_end("layernorm");
-    }
-    have_n1 = false;
-    dec_ffn_hidden("gemm_dec_ffn1", w1, fn, xdn16, D, Md, hd32, hd16);
-    if (f_ffn2) {
-      GemmRcArgs g{};
-      g.A = hd16; g.lda = F; g.W = w2.w; g.ldw = w2.Kpad; g.bias = nullptr; g.M = Md; g.K = w2.Kpad;
-      g.ln_g = post.g; g.ln_b = post.b; g.eps = 1e-12f;
-      g.out_n32 = n32; g.ldn32 = D; g.out_n16 = n16; g.ldn16 = D;
-      prof_begin("gemm_dec_ffn2", 2.0 * Md * (double)D * F);
-      launch_gemm_rc(stream_, g);
-      prof_end("gemm_dec_ffn2");
-    } else {
-      gemm("gemm_dec_ffn2", w2, hd16, F, Md, t32, D, nullptr, 0, nullptr, 0, nullptr, 0, false, 0, 1.f, false);
-      prof_begin("layernorm", 0);
-      launch_layernorm(stream_, t32, Md, D, post.g, post.b, n16, D, n32, n32 ? D : 0);
-      prof_end("layernorm");
-    }
+    // ... | the LayerNorm behind it.  (The row-complete GEMM with that LayerNorm as its epilogue runs on 84 CUs only at
+    // M = B * L = 5344: 47 against 29.5 + 5.6 us.)
+    gemm("gemm_dec_ffn2", w2, hd16, F, Md, t32, D, nullptr, 0, nullptr, 0, nullptr, 0, false, 0, 1.f, false);
+    prof_begin("layernorm", 0);
+    launch_layernorm(stream_, t32, Md, D, post.g, post.b, n16, D, n32, n32 ? D : 0);
+    prof_end("layernorm");
   };
 
   for (int i = 0; i < nd; ++i) {
     const DecLayer& Lr = dec_[i];
     // round 6: the finishing pass of the split FFN form, norm2, the FSMN memory, the residual, norm3 and the q-projection in ONE
     // launch (k_decmid.hip): a decoder layer = split FFN | middle | cross-attention
-    const bool mid = dec_mid_ && Lr.ffn_img && Lr.q_wt && !dsmall && D == 512 && mc_.kernel == 11;
+    const bool mid = dec_mid_ && Lr.ffn_img && Lr.q_wt && !dsmall && mc_.kernel == 11;
     mid_next = mid;
     ffn_dec(Lr.norm1, Lr.w1, Lr.ffn_norm, Lr.w2, Lr.ffn_img, Lr.norm2, tn32, nullptr);
     mid_next = false;
@@ -1465,7 +1416,7 @@ void Engine::predictor_and_decoder(int B, int T, bool want_logits) {
       PF_CHECK(mid_done, PF_ERR_UNSUPPORTED, "decoder: the fused middle launch does not cover this geometry");
     }
     bool fused = mid_done;
-    if (f_fsmn && !mid_done) {
+    if (!mid_done) {
       prof_begin("fsmn", 0);
       fused = launch_fsmn_dec_ln(stream_, tn32, Lr.fsmn_wT, plan_.token_num, B, L, D, mc_.kernel, xd, Lr.norm3.g, Lr.norm3.b, xdn16);
       prof_end("fsmn");
@@ -1490,16 +1441,6 @@ void Engine::predictor_and_decoder(int B, int T, bool want_logits) {
     prof_end("attn_cross");
     if (chain) {
       pend = &Lr;
-    } else if (f_out) {
-      const LNp& nxt = i + 1 < nd ? dec_[i + 1].norm1 : dec_final_norm1_;
-      GemmRcArgs g{};
-      g.A = ctxd16; g.lda = D; g.W = Lr.out.w; g.ldw = Lr.out.Kpad; g.bias = Lr.out.bias; g.M = Md; g.K = Lr.out.Kpad;
-      g.resid = xd; g.ldr = D; g.out_x = xd; g.ldx = D;
-      g.ln_g = nxt.g; g.ln_b = nxt.b; g.eps = 1e-12f; g.out_n16 = xdn16; g.ldn16 = D;
-      prof_begin("gemm_dec_out", 2.0 * Md * (double)D * D);
-      launch_gemm_rc(stream_, g);
-      prof_end("gemm_dec_out");
-      have_n1 = true;
     } else {
       gemm("gemm_dec_out", Lr.out, ctxd16, D, Md, xd, D, nullptr, 0, xd, D, nullptr, 0, false, 0, 1.f);
     }
@@ -1520,7 +1461,7 @@ void Engine::predictor_and_decoder(int B, int T, bool want_logits) {
 void Engine::start_timestamp_head(int B, int T) {
   {
     static const int ts_side = env_int("PF_TS_STREAM", 1);
-    if (ts_side && !lstm_steps_) {
+    if (ts_side) {
       // beside the decoder, on its own stream: everything timestamp_head enqueues (two GEMMs, the persistent recurrence,
       // the peaks and their copy to the host) goes to ts_stream_, which waits for the CIF scan (= the encoder too)
       PF_HIP(hipStreamWaitEvent(ts_stream_, ev_enc_, 0));    // (token_num — the CIF scan — is waited for in front of the peaks only)
@@ -1591,7 +1532,7 @@ void Engine::online_decoder(const float* enc, int B, int Tc, const float* embeds
   size_t off = 0;
   auto carve = [&](size_t bytes) { size_t o = off; off += round_up((int64_t)bytes, (int64_t)kAlign); return o; };
   const size_t o_e32 = carve((size_t)M * D * 4), o_e16 = carve((size_t)Mp * D * 2), o_kv = carve((size_t)Mp * std::max(nd, 1) * 2 * D * 2);
-  const size_t o_x = carve((size_t)Mdp * D * 4), o_xn = carve((size_t)Mdp * D * 2), o_h32 = carve((size_t)Mdp * F * 4);
+  const size_t o_x = carve((size_t)Mdp * D * 4), o_xn = carve((size_t)Mdp * D * 2);
   const size_t o_h16 = carve((size_t)Mdp * F * 2), o_t = carve((size_t)Mdp * D * 4), o_tn = carve((size_t)Mdp * D * 4);
   const size_t o_q = carve((size_t)Mdp * D * 2), o_ctx = carve((size_t)Mdp * D * 2), o_lg = carve((size_t)Mdp * ldV * 4);
   const size_t o_ids = carve((size_t)Md * 8), o_len = carve((size_t)B * 4);
@@ -1600,7 +1541,7 @@ void Engine::online_decoder(const float* enc, int B, int Tc, const float* embeds
   char* base = (char*)ws_dec_.p;
   float* e32 = (float*)(base + o_e32); half_t* e16 = (half_t*)(base + o_e16); half_t* kv16 = (half_t*)(base + o_kv);
   float* xd = (float*)(base + o_x); half_t* xdn16 = (half_t*)(base + o_xn);
-  float* hd32 = (float*)(base + o_h32); half_t* hd16 = (half_t*)(base + o_h16);
+  half_t* hd16 = (half_t*)(base + o_h16);
   float* t32 = (float*)(base + o_t); float* tn32 = (float*)(base + o_tn);
   half_t* qd16 = (half_t*)(base + o_q); half_t* ctxd16 = (half_t*)(base + o_ctx);
   float* lg = (float*)(base + o_lg); int64_t* ids = (int64_t*)(base + o_ids); int32_t* lens = (int32_t*)(base + o_len);
@@ -1616,7 +1557,7 @@ void Engine::online_decoder(const float* enc, int B, int Tc, const float* embeds
   if (nd > 0) gemm("gemm_dec_kv", dec_kv_all_, e16, D, M, nullptr, 0, kv16, ldkv, nullptr, 0, nullptr, 0, false, 0, 1.f);
   auto ffn_dec = [&](const LNp& n1, const Lin& w1, const LNp& fn, const Lin& w2) {
     launch_layernorm(stream_, xd, Md, D, n1.g, n1.b, xdn16, D, nullptr, 0);
-    dec_ffn_hidden("gemm_dec_ffn1", w1, fn, xdn16, D, Md, hd32, hd16);
+    dec_ffn_hidden("gemm_dec_ffn1", w1, fn, xdn16, D, Md, hd16);
     gemm("gemm_dec_ffn2", w2, hd16, F, Md, t32, D, nullptr, 0, nullptr, 0, nullptr, 0, false, 0, 1.f, false);
   };
   for (int i = 0; i < nd; ++i) {
@@ -1746,7 +1687,7 @@ void Engine::seaco_head(int B, int L, const float* e0, const float* hid32, bool 
     prof_begin("layernorm", 0);
     launch_layernorm(stream_, xs, R, D, n1.g, n1.b, xn16, D, nullptr, 0);
     prof_end("layernorm");
-    dec_ffn_hidden("gemm_seaco", w1, fn, xn16, D, R, h32, h16);
+    dec_ffn_hidden("gemm_seaco", w1, fn, xn16, D, R, h16);
     gemm("gemm_seaco", w2, h16, Fs, R, t32, D, nullptr, 0, nullptr, 0, nullptr, 0, false, 0, 1.f, false);
   };
   for (int i = 0; i < ns; ++i) {
@@ -1816,16 +1757,14 @@ void Engine::timestamp_head(int B, int T) {
   PF_HIP(hipMemsetAsync(cs, 0, (size_t)2 * B * D * 4, stream_));
   LstmArgs a{};
   a.whh = ts_whh_; a.xg = xg; a.hstate = hs; a.cstate = cs; a.hout = hout; a.B = B; a.T3 = T3; a.D = D; a.ndir = 2;
-  // the recurrence: ONE persistent launch (W_hh resident in registers, h exchanged through write-through stores and
-  // an arrival counter, k_bicif.hip) when every workgroup fits on the device at once; otherwise (B > 64, or
-  // PF_LSTM_STEPS=1) the 3T dependent launches, captured once per (shape, workspace) into a hipGraph and replayed
-  bool persistent = false;
-  if (!lstm_steps_) {
-    unsigned* sw = (unsigned*)(base + o_sw);
-    persistent = launch_lstm_persistent(stream_, a, sw);
-    if (persistent) lstm_err_ = sw + 63;
-  }
-  if (!persistent) {
+  // the recurrence: ONE persistent launch (W_hh resident in registers, h exchanged through a ring of write-through
+  // stores, k_bicif.hip) when every workgroup fits on the device at once; otherwise (B > 64) the 3T dependent launches,
+  // captured once per (shape, workspace) into a hipGraph and replayed
+  unsigned* sw = (unsigned*)(base + o_sw);
+  const bool persistent = launch_lstm_persistent(stream_, a, sw);
+  if (persistent) {
+    lstm_err_ = sw + 63;
+  } else {
     if (!lstm_graph_exec_ || lstm_graph_key_.xg != xg || lstm_graph_key_.B != B || lstm_graph_key_.T3 != T3) {
       if (lstm_graph_exec_) { hipGraphExecDestroy(lstm_graph_exec_); lstm_graph_exec_ = nullptr; }
       hipGraph_t g = nullptr;

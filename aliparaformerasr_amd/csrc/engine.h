@@ -231,7 +231,7 @@ class Engine {
             half_t* out16, int ld16, const float* resid, int ldr, const float* add2, int ld2, bool relu,
             int scale_cols, float scale, bool bias = true, int blocked = 0);   // blocked: 1 = out_f16 blocked, 2 = A blocked
   void gemm_small_call(const char* cls, const Lin& w, GemmSmallArgs g, bool bias = true);
-  void dec_ffn_hidden(const char* cls, const Lin& w1, const LNp& fn, const half_t* xn16, int lda, int rows, float* h32, half_t* h16);
+  void dec_ffn_hidden(const char* cls, const Lin& w1, const LNp& fn, const half_t* xn16, int lda, int rows, half_t* h16);
   void prof_begin(const char* cls, double flops);
   void prof_end(const char* cls);
 
@@ -255,34 +255,21 @@ class Engine {
   bool ts_pending_ = false, ts_defer_copy_ = false;
   size_t ts_copy_floats_ = 0;
   void join_ts();
-  bool no_rc_ = false, rc_ffn2_ = true, lstm_steps_ = false;
-  bool qkv_tail_ = true;             // PF_QKV_TAIL: the next layer's Q | K | V projection behind the fused block, same launch
-  bool attn_ffn_ = true;             // PF_ATTN_FFN: out-projection + FSMN + norm2 in front of the fused FFN block, one launch
-  bool ffn_fused_ = true;            // PF_FFN_FUSED: the encoder FFN block as one launch (k_ffn.hip)
   void own_hardware_queue_ts();
   void own_hardware_queue();         // round 6: the main stream must not share a hardware queue with another live engine's (see engine.cpp)
   bool dec_mid_ = true;              // PF_DEC_MID: finishing pass + norm2 + FSMN + residual + norm3 + q-projection in one launch (k_decmid.hip)
-  bool dec_out_chain_ = true;        // PF_DEC_OUT_CHAIN: a decoder layer's out-projection + the next norm1 in front of the next FFN launch
-  bool dec_ffn_fused_ = true;        // PF_DEC_FFN: the decoder's FFN block (with its LayerNorm over the hidden) as the split form of the same kernel
   int ffn_fused_min_rows_ = 1200;    // PF_FFN_MIN: below, 64-row tiles leave most CUs idle and the persistent kernels tie or win (tools/mid_rows.py)
-  bool no_small_fuse_ = false;
-  bool dec_h32_ = false;             // PF_DEC_H32=1: decoder FFN hidden through fp32 (A/B switch)
-  int dec_fuse_ = 1;                 // bit 1: FSMN + norm3, bit 2: out-projection + next norm1, bit 4: FFN-down + norm2 (row-complete GEMM)
-  bool qkv_split_ = true;            // PF_QKV_SPLIT=0: the row-major 256 x 128 kernel for Q | K | V
   int qkv_split_min_tiles_ = 256;    // PF_QKV_MIN: least number of 256 x 192 tiles for which the split form is chosen
   int qkv_split_min_fill_ = 60;      // PF_QKV_FILL: ... and least fill (percent) of its rounds of tiles (85 was the break-even with ONE step in
                                      // flight; with two, the other engine's kernels run on the CUs a short last round leaves)
   int cus_ = 256;                    // compute units the persistent kernels size their grids for (cu_limit)
   unsigned* lstm_err_ = nullptr;     // device time-out word of the last persistent LSTM launch (checked at the next result sync)
   void check_async_errors();         // after a stream sync: raises what a kernel of the finished forward reported through a flag word
-  int x3_attn_ = 0;                  // PF_X3_ATTN (math_mode 3): 0 = fp32-MFMA attention, 1 = x3 operands throughout, 2 = fp32 scores + x3 P V
   void attention32(const float* q, int64_t q_bs, int q_rs, const float* k, int64_t k_bs, int k_rs, const float* v, int64_t v_bs, int v_rs,
                    float* o, int64_t o_bs, int o_rs, int B, int H, int Lq, int Lk, bool only_operand = false);
   // LayerNorm of the fp32 graph whose result is ONLY the A operand of gemm32 calls that follow (xn names it): in math_mode 3
   // (D = 512, above the short-input threshold) it is written as that operand pair and xn is not touched
   void layernorm32(const float* x, int M, int D, const LNp& ln, float* xn);
-  bool x3_one_ = true;               // PF_X3_ONE=0: an x3 Linear as two launches with an [M, N] fp32 intermediate (round 5's first form; A/B)
-  bool x3_fuse_ = true;              // PF_X3_FUSE=0: LayerNorm / attention write fp32 and gemm32 splits (A/B)
   bool x3a_pair_only_ = false;       // x3a_src_ exists ONLY as the pair in ws_x3a_ (its fp32 form was never written)
   bool x3_mode_ = false;             // math_mode 3: the fp32 graph with every large Linear as three f16 MFMA products of (hi, lo') operand pairs
   void x3_forget(const float* W);          // drops W's cached pair image (stand-alone ops: their weights live in a scratch arena)

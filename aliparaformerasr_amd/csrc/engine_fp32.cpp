@@ -31,8 +31,7 @@ enum { F_X = 0, F_XN, F_Q, F_K, F_V, F_CTX, F_FS, F_H, F_T, F_COUNT };
 // (hi | lo') pair by the product's epilogue and `out` is not touched; kX3InPair — A is that pair (the `A` pointer is ignored in
 // mode 3).  Mode 1 ignores both flags.  resid2: a second fp32 addend with the row stride of resid (the FSMN memory beside the
 // residual stream).
-// attention of the fp32 graph: math_mode 1 on the fp32 matrix path; math_mode 3: PF_X3_ATTN = 0 the same, 1 = x3 operands
-// throughout, 2 = fp32 scores (what is exponentiated stays exact) + x3 operands for P V
+// attention of the fp32 graph: on the fp32 matrix path in math_mode 1 and 3 alike
 void Engine::attention32(const float* q, int64_t q_bs, int q_rs, const float* k, int64_t k_bs, int k_rs, const float* v, int64_t v_bs,
                          int v_rs, float* o, int64_t o_bs, int o_rs, int B, int H, int Lq, int Lk, bool only_operand) {
   const char* acls = (q_rs == k_rs && Lq == Lk) ? "attn32_self" : "attn32_cross";
@@ -41,7 +40,7 @@ void Engine::attention32(const float* q, int64_t q_bs, int q_rs, const float* k,
   // only_operand: o [B * Lq, H * 128] (dense rows) is nothing but the A operand of the gemm32 that follows — in math_mode 3 the
   // fp32-MFMA kernel's epilogue writes it as that product's (hi | lo') pair (no fp32 context, no split pass)
   const int Dm = H * 128, M = B * Lq;
-  if (only_operand && x3_mode_ && x3_fuse_ && x3_attn_ == 0 && o_rs == Dm && o_bs == (int64_t)Lq * Dm && Dm % 64 == 0 && M > gemm_small_max_rows()) {
+  if (only_operand && x3_mode_ && o_rs == Dm && o_bs == (int64_t)Lq * Dm && Dm % 64 == 0 && M > gemm_small_max_rows()) {
     const int64_t Mp = round_up(M, 256) + 128;
     ensure(ws_x3a_, (size_t)Mp * 2 * Dm * 2);
     half_t* a2 = (half_t*)ws_x3a_.p;
@@ -50,15 +49,13 @@ void Engine::attention32(const float* q, int64_t q_bs, int q_rs, const float* k,
       return;
     }
   }
-  if (x3_mode_ && x3_attn_ == 1) launch_attention_x3(stream_, q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, o, o_bs, o_rs, B, H, Lq, Lk, false);
-  else if (x3_mode_ && x3_attn_ == 2) launch_attention_x3(stream_, q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, o, o_bs, o_rs, B, H, Lq, Lk, true);
-  else launch_attention_f32(stream_, q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, o, o_bs, o_rs, B, H, Lq, Lk);
+  launch_attention_f32(stream_, q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, o, o_bs, o_rs, B, H, Lq, Lk);
 }
 
 void Engine::layernorm32(const float* x, int M, int D, const LNp& ln, float* xn) {
   prof_begin("layernorm", 0);
   struct End { Engine* e; ~End() { e->prof_end("layernorm"); } } end_{this};
-  if (x3_mode_ && x3_fuse_ && D == 512 && M > gemm_small_max_rows()) {
+  if (x3_mode_ && D == 512 && M > gemm_small_max_rows()) {
     const int64_t Mp = round_up(M, 256) + 128;
     ensure(ws_x3a_, (size_t)Mp * 2 * D * 2);
     half_t* a2 = (half_t*)ws_x3a_.p;
@@ -82,7 +79,7 @@ void Engine::gemm32_impl(const float* A, int lda, const float* W, int ldw, const
                          const float* resid, int ldr, bool relu, int scale_cols, float scale, int flags, const float* resid2) {
   // (a q-scale on the leading columns only — the fused Q | K | V product — is an option of the one-launch form's epilogue)
   const bool part_scale = scale_cols > 0 && scale_cols < N;
-  const bool x3 = x3_mode_ && M >= 64 && ldw == K && (!part_scale || (x3_one_ && scale_cols % 64 == 0 && M > gemm_small_max_rows())) &&
+  const bool x3 = x3_mode_ && M >= 64 && ldw == K && (!part_scale || (scale_cols % 64 == 0 && M > gemm_small_max_rows())) &&
                   (ldc % 4) == 0 && (!resid || ldr % 4 == 0);
   const bool pair_ok = x3 && M > gemm_small_max_rows();
   if (!x3) {
@@ -129,7 +126,7 @@ void Engine::gemm32_impl(const float* A, int lda, const float* W, int ldw, const
     ensure(ws_x3h_, (size_t)Mp * 2 * Np64 * 2);
     PF_CHECK((void*)ws_x3h_.p != (void*)a2, PF_ERR_UNSUPPORTED, "gemm32: chained operand pairs");
   }
-  if (x3_one_ && pair_ok) {
+  if (pair_ok) {
     // ONE launch: the K loop walks the cross terms first ([hi_x | lo'_x] x [lo'_W | hi_W], depth 2 Kp), scales the accumulators
     // by 2^-11, steps the cursors back (A to hi_x, W to hi_W) and adds hi_x hi_W^T (depth Kp) on top — small terms first, one
     // fp32 accumulator, no [M, N] intermediate written and read back (FFN-up: 2 x 131 MB per layer), half the launches
@@ -181,7 +178,7 @@ void Engine::enc_layer_fp32(const EncLayer& L, bool first, const float* speech_d
   const float* Wq = L.qkv.w32;
   // math_mode 3 above the short-input threshold: Q | K | V as ONE x3 product of N = 3 D (the weight is stored [Q | K | V] rows;
   // q-scale on the first D columns) into the three consecutive buffers read as one [M, 3 D] matrix
-  const bool qkv_one = x3_mode_ && x3_one_ && x3_fuse_ && M > gemm_small_max_rows() && mc_.kernel == 11 && D % 64 == 0 &&
+  const bool qkv_one = x3_mode_ && M > gemm_small_max_rows() && mc_.kernel == 11 && D % 64 == 0 &&
                        f[F_K] == f[F_Q] + (size_t)M * D && f[F_V] == f[F_K] + (size_t)M * D;
   cls32_ = "gemm32_qkv";
   if (qkv_one) {
@@ -363,7 +360,7 @@ void Engine::timestamp_head_fp32(int B, int T) {
   const size_t o_al = carve((size_t)M3 * 4), o_pk = carve((size_t)M3 * 4);
   // math_mode 3: the recurrence as ONE persistent launch with (hi, lo') pair operands (k_bicif.hip, lstm_ring_kernel<true>): room for
   // both directions' input gates, the four pair slots of h and the sync words
-  const bool x3_rec = x3_mode_ && x3_fuse_ && !lstm_steps_ && D == 512 && (D / 8) * 2 * ((B + 31) / 32) <= cus_;
+  const bool x3_rec = x3_mode_ && D == 512 && (D / 8) * 2 * ((B + 31) / 32) <= cus_;
   const size_t o_xg2 = x3_rec ? carve((size_t)(M3 + 256) * 8 * D * 4) : 0, o_hs = x3_rec ? carve((size_t)2 * 4 * B * 2 * D * 2) : 0, o_sw = x3_rec ? carve(256) : 0;
   ensure(ws_ts_, off);
   char* base = (char*)ws_ts_.p;

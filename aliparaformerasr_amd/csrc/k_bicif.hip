@@ -85,15 +85,10 @@ __global__ __launch_bounds__(256) void lstm_step_kernel(LstmArgs a) {
 
 // ------------------------------------------------------------------------------------------------------------
 // PERSISTENT recurrence: ONE launch runs all T3 steps.  Same work split as lstm_step_kernel (a workgroup = 8 hidden
-// units x 4 gates x one tile of 32 utterances, its 4 waves split K), but
-//   * the workgroup's W_hh slice (32 rows x 512 x f16 = 32 VGPRs per lane) is loaded ONCE and stays in registers,
-//     the cell state lives in a register;
-//   * h is exchanged between the D/8 workgroups of one (direction, utterance tile) through the global ping-pong
-//     buffer, hand-off per the CDNA guide's recipe R1: 16-byte write-through (sc1) stores of the new h slice, every
-//     storing wave drains vmcnt, ONE lane adds to a monotonic arrival counter; consumers poll that word (relaxed,
-//     bounded spin with s_sleep) and then read h with sc1 loads (L2-served, never this CU's stale L1);
-//   * step s may overwrite the buffer step s-1 read: a workgroup arrives at the step-(s-1) counter only AFTER its
-//     reads of that step, and nobody starts step s before all arrivals — no further ordering is needed.
+// units x 4 gates x one tile of 32 utterances, its 4 compute waves split K), but the workgroup's W_hh slice (32 rows x
+// 512 x f16 = 32 VGPRs per lane) is loaded ONCE and stays in registers, the cell state lives in a register, and h is
+// exchanged between the D/8 workgroups of one (direction, utterance tile) through global memory with 16-byte
+// write-through (sc1) stores and sc1 loads (L2-served, never this CU's stale L1).
 // All (D/8) * ndir * tiles workgroups must be resident at once (launcher checks against the CU count); every spin
 // is bounded: on time-out the kernel raises *err and every workgroup leaves.
 // eight 16-byte sc1 loads (offsets 0, 32, .., 224 bytes) issued back to back, ONE wait: the loads and their wait live
@@ -117,96 +112,7 @@ __device__ __forceinline__ void st16_sc1(half_t* p, h8v v) {
   asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
 }
 
-__global__ __launch_bounds__(256) void lstm_persistent_kernel(LstmArgs a, unsigned* __restrict__ cnt, unsigned* __restrict__ err) {
-  const int D = a.D;
-  const int ub = blockIdx.x, dir = blockIdx.y, bt = blockIdx.z;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int r = lane & 31, kg = lane >> 5;
-  const int nub = gridDim.x;                                // producers per (direction, tile)
-  unsigned* my_cnt = cnt + (dir * gridDim.z + bt);
-  __shared__ float red[4][16][64];
-  __shared__ _Float16 hx[32][8];                            // new h slice: [utterance][unit] -> 16-byte rows
-  __shared__ int s_abort;
-
-  // W_hh rows of this lane, K slice of this wave: resident for the whole launch
-  const half_t* wrow = a.whh + ((size_t)dir * 4 * D + (size_t)(r & 3) * D + ub * 8 + (r >> 2)) * D;
-  const int kspan = D / 4;                                  // 128 (D = 512)
-  h8v av[8];
-#pragma unroll
-  for (int s = 0; s < 8; ++s) av[s] = *reinterpret_cast<const h8v*>(wrow + wave * kspan + s * 16 + kg * 8);
-
-  const int bb = min(bt * 32 + r, a.B - 1);                 // utterance whose h row this lane feeds to the MFMA
-  const int b = bt * 32 + r;                                // utterance of this lane's cell
-  const int uq = ub * 8 + 2 * wave + kg;                    // hidden unit of this lane's cell
-  float c = 0.f;
-  if (threadIdx.x == 0) s_abort = 0;
-  __syncthreads();
-
-  for (int step = 0; step < a.T3; ++step) {
-    const int t = dir == 0 ? step : a.T3 - 1 - step;
-    const int pp = step & 1;
-    const half_t* hprev = a.hstate + (size_t)(dir * 2 + pp) * a.B * D;
-    half_t* hnext = a.hstate + (size_t)(dir * 2 + (pp ^ 1)) * a.B * D;
-    // the cell's own inputs do not depend on h: requested before the wait
-    const float* xgp = a.xg + ((size_t)bb * a.T3 + t) * (size_t)(a.ndir * 4 * D) + (size_t)dir * 4 * D + uq;
-    const float xi = xgp[0], xf = xgp[D], xc = xgp[2 * D], xo = xgp[3 * D];
-    if (step > 0) {
-      if (threadIdx.x == 0) {
-        const unsigned want = (unsigned)step * (unsigned)nub;
-        unsigned spins = 0;
-        while (__hip_atomic_load(my_cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < want) {
-          __builtin_amdgcn_s_sleep(2);
-          if (++spins > (1u << 22) || __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
-            __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            s_abort = 1;
-            break;
-          }
-        }
-      }
-      __syncthreads();
-      if (s_abort) return;
-    }
-    const half_t* hrow = hprev + (size_t)bb * D + wave * kspan + kg * 8;
-    f16v acc;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-    h8v bv[8];
-    // one wait per load measured FASTER than eight loads behind one wait (6.5-6.8 vs 7.8 ms for the 1500 steps, same
-    // session, tools/lstm_ab.sh): 512 waves issuing 8 write-through-coherent loads at once queue behind each other and
-    // behind the pollers.  a.step is free in the persistent form: PF_LSTM_VAR=1 selects the batched form for experiments
-    if (a.step == 1) ld8x16_sc1(hrow, bv);
-    else {
-#pragma unroll
-      for (int s = 0; s < 8; ++s) {
-        h8v v;
-        asm volatile("global_load_dwordx4 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=&v"(v) : "v"(hrow + s * 16) : "memory");
-        bv[s] = v;
-      }
-    }
-#pragma unroll
-    for (int s = 0; s < 8; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(av[s], bv[s], acc, 0, 0, 0);
-#pragma unroll
-    for (int i = 0; i < 16; ++i) red[wave][i][lane] = acc[i];
-    __syncthreads();
-    float g[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-      g[q] = (red[0][4 * wave + q][lane] + red[1][4 * wave + q][lane]) + (red[2][4 * wave + q][lane] + red[3][4 * wave + q][lane]);
-    const float gi = g[0] + xi, gf = g[1] + xf, gg = g[2] + xc, go = g[3] + xo;
-    c = sigmoidf_(gf) * c + sigmoidf_(gi) * tanhf(gg);
-    const float h = sigmoidf_(go) * tanhf(c);
-    hx[r][2 * wave + kg] = (_Float16)h;
-    if (b < a.B) a.hout[((size_t)b * a.T3 + t) * (size_t)(a.ndir * D) + (size_t)dir * D + uq] = h;
-    __syncthreads();
-    if (wave == 0 && lane < 32 && bt * 32 + lane < a.B)       // 32 x 16 bytes, write-through
-      st16_sc1(hnext + (size_t)(bt * 32 + lane) * D + ub * 8, *reinterpret_cast<const h8v*>(&hx[lane][0]));
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // every storing wave drains (R1)
-    __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_fetch_add(my_cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-
-// ---- ring form of the persistent recurrence (default): the h exchange carries its own arrival information.
+// ---- ring form of the persistent recurrence: the h exchange carries its own arrival information.
 // h lives in FOUR slots per direction.  Step s reads slot s % 4 (h_{s-1}), writes h_s into slot (s + 1) % 4 and — once the
 // workgroup holds all of h_{s-1}, i.e. every workgroup of its group has finished reading slot (s + 3) % 4 (the input of
 // step s - 1) — overwrites its own 16-byte granules of slot (s + 3) % 4 with a POISON pattern (f16 NaNs; a hidden state
@@ -218,7 +124,7 @@ __global__ __launch_bounds__(256) void lstm_persistent_kernel(LstmArgs a, unsign
 // h_{s-2}: it received that producer's h_{s+1}, which wave 0 of the producer stored in step s + 1 after that step's
 // polls, and every poll ends in s_waitcnt vmcnt(0) — which also retired wave 0's poison store of step s (memory
 // operations of a wave retire in order).  A granule is written by one 16-byte store of one lane (observed untorn on
-// gfx950; the poison test reads its first word).  Bounded spins + the error word as in the counter form.
+// gfx950; the poison test reads its first word).  Spins are bounded; a time-out raises the error word.
 // hstate: [ndir][4][B][D], slot 0 zero, slots 1-3 poison.
 // X3 (math_mode 3, the exact mode's timestamp head): W_hh and h travel as (hi, lo') f16 pairs — 22 mantissa bits — and a step's
 // product is hi_W lo'_h + lo'_W hi_h (16 MFMAs), the accumulators x 2^-11, + hi_W hi_h (8 MFMAs) in one fp32 accumulator, as the
@@ -372,20 +278,13 @@ bool launch_lstm_persistent(hipStream_t s, const LstmArgs& a, unsigned* sync_wor
   if (wgs > cus || a.ndir * tiles > 60) return false;       // every workgroup must be resident: one per CU at most
   PF_HIP(hipMemsetAsync(sync_words, 0, 64 * sizeof(unsigned), s));
   LstmArgs b = a;
-  static const int var = env_int("PF_LSTM_VAR", 2);          // PF_LSTM_VAR: 2 = ring form (default), 0 / 1 = arrival-counter form
-  if (var == 2) {
-    static const int delay = env_int("PF_LSTM_DELAY", 13);   // PF_LSTM_DELAY: x 2 x 64 clocks before the first (full) load of a step
-    b.step = delay;
-    // hstate [ndir][4][B][D]: slot 0 = h_{-1} = 0, slots 1 to 3 poison
-    const size_t slot = (size_t)a.B * a.D * 2;
-    PF_HIP(hipMemsetAsync(a.hstate, 0xFF, (size_t)a.ndir * 4 * slot, s));
-    for (int d = 0; d < a.ndir; ++d) PF_HIP(hipMemsetAsync(reinterpret_cast<char*>(a.hstate) + (size_t)d * 4 * slot, 0, slot, s));
-    hipLaunchKernelGGL(lstm_ring_kernel<false>, dim3(a.D / 8, a.ndir, tiles), dim3(320), 0, s, b, sync_words + 63);
-  } else {
-    PF_HIP(hipMemsetAsync(a.hstate, 0, (size_t)a.ndir * 2 * a.B * a.D * 2, s));
-    b.step = var;
-    hipLaunchKernelGGL(lstm_persistent_kernel, dim3(a.D / 8, a.ndir, tiles), dim3(256), 0, s, b, sync_words, sync_words + 63);
-  }
+  static const int delay = env_int("PF_LSTM_DELAY", 13);     // PF_LSTM_DELAY: x 2 x 64 clocks before the first (full) load of a step
+  b.step = delay;
+  // hstate [ndir][4][B][D]: slot 0 = h_{-1} = 0, slots 1 to 3 poison
+  const size_t slot = (size_t)a.B * a.D * 2;
+  PF_HIP(hipMemsetAsync(a.hstate, 0xFF, (size_t)a.ndir * 4 * slot, s));
+  for (int d = 0; d < a.ndir; ++d) PF_HIP(hipMemsetAsync(reinterpret_cast<char*>(a.hstate) + (size_t)d * 4 * slot, 0, slot, s));
+  hipLaunchKernelGGL(lstm_ring_kernel<false>, dim3(a.D / 8, a.ndir, tiles), dim3(320), 0, s, b, sync_words + 63);
   PF_HIP(hipGetLastError());
   return true;
 }

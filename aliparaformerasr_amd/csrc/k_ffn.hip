@@ -1146,26 +1146,20 @@ void launch_ffn_fused(hipStream_t s, const FfnFusedArgs& a) {
   PF_CHECK(op || a.A, PF_ERR_INVALID_ARG, "ffn_fused: missing operand");
   static std::mutex init_mu;
   static bool attr_set[64] = {false};
-  static int rot_mask = 7, pf = 8, xd = 2, abl = 0;
+  static int abl = 0;
   int dev = 0;
   PF_HIP(hipGetDevice(&dev));
   {
     std::lock_guard<std::mutex> lk(init_mu);
     if (!attr_set[dev & 63]) {
-      PF_HIP(hipFuncSetAttribute((const void*)ffn_fused_kernel<8, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, FF_LDS));
       PF_HIP(hipFuncSetAttribute((const void*)ffn_fused_kernel<8, 0, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, FF_LDS));
-      PF_HIP(hipFuncSetAttribute((const void*)ffn_fused_kernel<8, 0, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, FF_LDS));
-      PF_HIP(hipFuncSetAttribute((const void*)ffn_fused_kernel<12, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, FF_LDS));
       PF_HIP(hipFuncSetAttribute((const void*)ffn_fused_kernel<8, 0, 2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, FF_LDS));
       PF_HIP(hipFuncSetAttribute((const void*)ffn_fused_kernel<8, 0, 2, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, FF_LDS));
-      if (const char* e = getenv("PF_FFN_ROT")) rot_mask = atoi(e) & 7;      // 0 | 1 | 3 | 7: chunk-order rotation period - 1
       if (const char* e = getenv("PF_FFN_ABL")) abl = atoi(e);
-      if (const char* e = getenv("PF_FFN_XD")) xd = atoi(e);                 // LDS fragment reads 1 | 2 | 3 k-steps ahead
-      if (const char* e = getenv("PF_FFN_PF")) pf = atoi(e);                 // 8 | 12 fragments in flight per wave (16 spills)
       attr_set[dev & 63] = true;
     }
   }
-  d.rot_mask = rot_mask;
+  d.rot_mask = 7;                                       // chunk-order rotation period - 1
   const dim3 grid((unsigned)cdiv(a.M, FF_BM));
 #ifdef PF_FFN_ABLATIONS
   if (abl) {
@@ -1200,19 +1194,8 @@ void launch_ffn_fused(hipStream_t s, const FfnFusedArgs& a) {
     PF_HIP(hipGetLastError());
     return;
   }
-  if (pf >= 12) {                                       // 12 fragments in flight, LDS reads one k-step ahead
-    note_gemm_kernel("ffn_fused_kernel<12, 0, 1, 0, 0, 0>");
-    hipLaunchKernelGGL((ffn_fused_kernel<12, 0, 1>), grid, dim3(512), FF_LDS, s, d);
-  } else if (xd >= 3) {
-    note_gemm_kernel("ffn_fused_kernel<8, 0, 3, 0, 0, 0>");
-    hipLaunchKernelGGL((ffn_fused_kernel<8, 0, 3>), grid, dim3(512), FF_LDS, s, d);
-  } else if (xd == 2) {
-    note_gemm_kernel("ffn_fused_kernel<8, 0, 2, 0, 0, 0>");
-    hipLaunchKernelGGL((ffn_fused_kernel<8, 0, 2>), grid, dim3(512), FF_LDS, s, d);
-  } else {
-    note_gemm_kernel("ffn_fused_kernel<8, 0, 1, 0, 0, 0>");
-    hipLaunchKernelGGL((ffn_fused_kernel<8, 0, 1>), grid, dim3(512), FF_LDS, s, d);
-  }
+  note_gemm_kernel("ffn_fused_kernel<8, 0, 2, 0, 0, 0>");
+  hipLaunchKernelGGL((ffn_fused_kernel<8, 0, 2>), grid, dim3(512), FF_LDS, s, d);
   PF_HIP(hipGetLastError());
 }
 

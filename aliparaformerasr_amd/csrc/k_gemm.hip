@@ -864,26 +864,24 @@ void launch_gemm(hipStream_t s, const GemmArgs& a) {
     }
   }
   {
-    // blocked-layout results (FFN-up): the persistent 256 x 256-tile kernel (k_gemm_big.hip); PF_BIGP=0 keeps this file's kernel
-    static const int use_bigp = [] { const char* e = getenv("PF_BIGP"); return (e && e[0] == '0') ? 0 : ((e && e[0] == '2') ? 2 : 1); }();   // 2: whenever it applies and fills the chip once
+    // blocked-layout results (FFN-up): the persistent 256 x 256-tile kernel (k_gemm_big.hip)
     const bool can = gemm_bigp_applicable(a);
     PF_CHECK(a.force_mi != 5 || can, PF_ERR_INVALID_ARG, "gemm: the persistent 256 x 256 kernel does not apply to this problem");
     // by rounds: a 256 x 256 tile costs ~1.9 tiles of this file's kernel; whichever schedule has less idle tail wins
     // (M = 16000: 504 tiles = 2 rounds vs 1008 = 4 -> persistent; SenseVoice M = 10944: 344 = 2 rounds vs 688 = 3 -> this kernel)
     const int t_big = cdiv(a.M, 256) * (a.N / 256), t_pp3 = cdiv(a.M, 256) * cdiv(a.N, GEMM_BN);
     const bool fewer_rounds = t_big >= cus[dev] && 1.9 * cdiv(t_big, cus[dev]) <= (double)cdiv(t_pp3, cus[dev]);
-    if (can && (a.force_mi == 5 || (a.force_mi == 0 && use_bigp && (fewer_rounds || (use_bigp == 2 && t_big >= cus[dev]))))) {
+    if (can && (a.force_mi == 5 || (a.force_mi == 0 && fewer_rounds))) {
       launch_gemm_bigp(s, a, cus[dev]);
       return;
     }
   }
   // tile height by rounds: a 128-row tile costs ~0.58 of a 256-row one (half the MFMAs, two thirds of the operand
   // bytes); whichever schedule has the shorter last round wins (decoder FFN-up, M = 5344: 336 tiles = 2 rounds vs
-  // 672 = 3 x 0.58).  PF_GEMM_ROUNDS=0 keeps the tile-count rule alone.
-  static const int by_rounds = [] { const char* e = getenv("PF_GEMM_ROUNDS"); return (e && e[0] == '0') ? 0 : 1; }();
+  // 672 = 3 x 0.58).
   const int t2 = cdiv(d.M, 256) * cdiv(d.N, GEMM_BN), t1 = cdiv(d.M, 128) * cdiv(d.N, GEMM_BN);
   const bool few = (float)t2 < mi_x * cus[dev];
-  const bool rounds1 = by_rounds && 0.58 * cdiv(t1, cus[dev]) < (double)cdiv(t2, cus[dev]);
+  const bool rounds1 = 0.58 * cdiv(t1, cus[dev]) < (double)cdiv(t2, cus[dev]);
   const int mi = a.force_mi ? (a.force_mi == 1 ? 1 : 2) : ((few || rounds1) ? 1 : 2);
   PF_CHECK(a.force_mi != 6, PF_ERR_UNSUPPORTED, "gemm: the k-step-32 kernel was removed in round 5 (numbers: profiles/round4_k32_microbench.txt)");
   d.tiles_m = cdiv(d.M, 128 * mi);

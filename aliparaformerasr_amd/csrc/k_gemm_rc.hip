@@ -50,7 +50,6 @@ constexpr int RC_W_BYTES = RC_BN * RC_ROWB;              // 64 KiB
 constexpr int RC_STAGE = RC_A_BYTES + RC_W_BYTES;        // 72 KiB
 constexpr int RC_XROW = RC_BN * 4 + 16;                  // epilogue tile: 16-byte skew per row (conflict-free dump)
 constexpr int RC_LDS = 2 * RC_STAGE > RC_BM * RC_XROW ? 2 * RC_STAGE : RC_BM * RC_XROW;   // 144 KiB
-constexpr int RC_TOUCH = 8 * 256;                        // + a dead 256-byte line per wave: target of the A prefetch touches (PFD > 0)
 
 __device__ __forceinline__ void rc_glds16(const void* g, void* l) {
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
@@ -125,6 +124,7 @@ __device__ __forceinline__ void rc_fsmn(float4 (&x)[8], const h4 (&win)[FK > 0 ?
 // before it is consumed, finds the activation rows in L2: A is the only COLD operand of this kernel (each row block is read
 // by exactly one workgroup, straight from HBM / the Infinity Cache), and with one stage in flight a cold line's latency is
 // exposed every step.  The touch is a tenth vector-memory operation per wave and step: the counted waits say 10, not 9.
+// Only PFD = 0 is instantiated (the touches measured slightly slower); a PFD > 0 launch needs 8 x 256 bytes of LDS beyond RC_LDS.
 template <int FK, int PFD>
 __global__ __launch_bounds__(512, 1) void gemm_rc_kernel(RcDev p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -376,7 +376,6 @@ void launch_gemm_rc(hipStream_t s, const GemmRcArgs& a) {
   d.eps = a.eps;
   static std::mutex init_mu;                         // engines on different devices launch from different threads
   static bool attr_set[64] = {false};
-  static int rc_pfd = 0;                             // PF_RC_PFD = 4 | 8: A prefetch touches that many k-steps ahead (deep projections without an FSMN term)
   int dev = 0;
   PF_HIP(hipGetDevice(&dev));
   {
@@ -384,23 +383,13 @@ void launch_gemm_rc(hipStream_t s, const GemmRcArgs& a) {
     if (!attr_set[dev & 63]) {
       PF_HIP(hipFuncSetAttribute((const void*)gemm_rc_kernel<0, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, RC_LDS));
       PF_HIP(hipFuncSetAttribute((const void*)gemm_rc_kernel<11, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, RC_LDS));
-      PF_HIP(hipFuncSetAttribute((const void*)gemm_rc_kernel<0, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, RC_LDS + RC_TOUCH));
-      PF_HIP(hipFuncSetAttribute((const void*)gemm_rc_kernel<0, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, RC_LDS + RC_TOUCH));
-      if (const char* e = getenv("PF_RC_PFD")) rc_pfd = atoi(e);
       attr_set[dev & 63] = true;
     }
   }
   const dim3 grid((unsigned)cdiv(a.M, RC_BM));
-  const int nk = a.K / RC_BK;                        // (the names are the ones the rocprofv3 kernel trace shows)
-  if (a.fsmn_v) {
+  if (a.fsmn_v) {                                    // (the names are the ones the rocprofv3 kernel trace shows)
     note_gemm_kernel("gemm_rc_kernel<11, 0>");
     hipLaunchKernelGGL((gemm_rc_kernel<11, 0>), grid, dim3(512), RC_LDS, s, d);
-  } else if (rc_pfd >= 8 && nk > 8) {
-    note_gemm_kernel("gemm_rc_kernel<0, 8>");
-    hipLaunchKernelGGL((gemm_rc_kernel<0, 8>), grid, dim3(512), RC_LDS + RC_TOUCH, s, d);
-  } else if (rc_pfd >= 4 && nk > 4) {
-    note_gemm_kernel("gemm_rc_kernel<0, 4>");
-    hipLaunchKernelGGL((gemm_rc_kernel<0, 4>), grid, dim3(512), RC_LDS + RC_TOUCH, s, d);
   } else {
     note_gemm_kernel("gemm_rc_kernel<0, 0>");
     hipLaunchKernelGGL((gemm_rc_kernel<0, 0>), grid, dim3(512), RC_LDS, s, d);

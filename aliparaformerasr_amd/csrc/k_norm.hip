@@ -201,15 +201,9 @@ static void ln_dispatch(hipStream_t s, const float* x, int64_t rows, int D, cons
   PF_CHECK(D % 4 == 0 && D <= 64 * 4 * 8, PF_ERR_INVALID_ARG, "layernorm: unsupported width");
   if (rows == 0) return;
   if (!POSENC && D == 512 && rows >= 4096 && (!out16 || ld16 == D)) {
-    static const int rows_per_wave = env_int("PF_LN_ROWS", 2);   // PF_LN_ROWS: 1 keeps the one-row kernel (A/B switch)
-    if (rows_per_wave == 2 || rows_per_wave == 4) {
-      const int R = rows_per_wave;
-      const dim3 g2((unsigned)((rows + 4 * R - 1) / (4 * R))), b2(256);
-      if (R == 2) hipLaunchKernelGGL(layernorm512_kernel<2>, g2, b2, 0, s, x, rows, gamma, beta, out16, ld16, out32, ld32);
-      else hipLaunchKernelGGL(layernorm512_kernel<4>, g2, b2, 0, s, x, rows, gamma, beta, out16, ld16, out32, ld32);
-      PF_HIP(hipGetLastError());
-      return;
-    }
+    hipLaunchKernelGGL(layernorm512_kernel<2>, dim3((unsigned)((rows + 7) / 8)), dim3(256), 0, s, x, rows, gamma, beta, out16, ld16, out32, ld32);
+    PF_HIP(hipGetLastError());
+    return;
   }
   const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
   const int nv = (D / 4 + 63) / 64;

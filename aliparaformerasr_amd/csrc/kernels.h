@@ -217,9 +217,6 @@ bool launch_attention_f32_pair(hipStream_t s, const float* q, int64_t q_bs, int 
                                const float* v, int64_t v_bs, int v_rs, half_t* pair, int64_t p_bs, int p_rs, int p_lo, int B, int H, int Lq, int Lk);
 // x [rows, K] fp32 -> out [rows, 2 Kp] f16 = hi | lo' (swap: lo' | hi), lo' = f16((x - hi) * 2^11); Kp % 4 == 0, pad columns zeroed
 void launch_split_x3(hipStream_t s, const float* x, int64_t rows, int K, int ldx, half_t* out, int ldo, int Kp, int swap);
-// the same attention with x3 operands (22-bit pairs on the f16 matrix cores): math_mode 3
-void launch_attention_x3(hipStream_t s, const float* q, int64_t q_bs, int q_rs, const float* k, int64_t k_bs, int k_rs,
-                         const float* v, int64_t v_bs, int v_rs, float* o, int64_t o_bs, int o_rs, int B, int H, int Lq, int Lk, bool scores_f32 = false);
 void launch_im2col_f32(hipStream_t s, const float* H, int B, int T, int D, int l_order, int r_order, float* out);
 void launch_add_f32(hipStream_t s, float* x, const float* y, int64_t n);     // x += y
 void launch_spin(hipStream_t s, unsigned long long cycles);                  // one wave spinning ~cycles shader clocks (queue probe)
@@ -325,7 +322,7 @@ struct LstmArgs {
 };
 void launch_lstm_step(hipStream_t s, const LstmArgs& a);
 // all T3 steps in one launch (a.step ignored; hstate / cstate zeroed by the caller; cstate is not used: the cell
-// state lives in registers).  sync_words: >= 64 device words (arrival counters + [63] = time-out flag, zeroed here).
+// state lives in registers).  sync_words: >= 64 device words ([63] = time-out flag, zeroed here).
 // false = not applicable (more workgroups than CUs): use launch_lstm_step per step.
 bool launch_lstm_persistent(hipStream_t s, const LstmArgs& a, unsigned* sync_words);
 // the same recurrence with (hi, lo') pair operands (math_mode 3): whh = [ndir][4D][2D] pair rows, hstate [ndir][4][B][2D]

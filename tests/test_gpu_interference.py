@@ -94,8 +94,8 @@ def test_operators_are_bit_stable_beside_a_busy_second_engine():
 @pytest.mark.timeout(600)
 def test_timestamp_head_beside_the_decoder_changes_nothing():
     """The BiCIF head runs on its own stream beside the decoder (Engine::forward): ids and peaks must equal the
-    single-stream order's, call after call (PF_TS_STREAM is read once per process: compare through the ring / counter forms
-    of the recurrence instead, which share nothing but the result)."""
+    single-stream order's, call after call (PF_TS_STREAM is read once per process: the calls here, whose overlap with the
+    decoder differs from one to the next, are compared with each other instead)."""
     from aliparaformerasr_amd.engine import Engine
     cfg = W.paraformer_large_config(enc_layers=2, dec_layers=2, timestamp_head=True)
     eng = Engine(weights=W.pack_pfw(cfg, W.synth_weights(cfg, 5)), cmvn=W.synth_cmvn(), device=0)

@@ -1,7 +1,7 @@
 """Times the fused encoder FFN block (k_ffn.hip, one launch) through pf_op_ffn_fused against the two launches it replaces
 (pf_op_gemm_ex FFN-up on the persistent 256 x 256 kernel + pf_op_gemm_rc FFN-down with the LayerNorm epilogue), HIP events
 around the launches only, cold (first launch after the upload) and warm (PF_OP_REPEAT back-to-back launches).
-    M=16000 PF_FFN_PF=12 PF_FFN_ROT=7 python tools/bench_ffn.py"""
+    M=16000 python tools/bench_ffn.py"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 os.environ.setdefault("PF_OP_REPEAT", "8")

@@ -1,7 +1,7 @@
 """Where does the fused encoder launch (k_ffn.hip, 64-row tiles) start to pay?  Whole-path time for batches whose encoder
 row count M = B x T lies between the short-input path (M <= 512) and the benchmark (M = 16 000), with the fused forms forced
-on from 513 rows (PF_FFN_MIN=513) and off (PF_FFN_FUSED=0).  Run once per setting:
-    PF_FFN_MIN=513 python tools/mid_rows.py ; PF_FFN_FUSED=0 PF_ATTN_FFN=0 python tools/mid_rows.py ; python tools/mid_rows.py"""
+on from 513 rows (PF_FFN_MIN=513) and off for every batch here (PF_FFN_MIN=100000: the row-complete form).  Run once per setting:
+    PF_FFN_MIN=513 python tools/mid_rows.py ; PF_FFN_MIN=100000 python tools/mid_rows.py ; python tools/mid_rows.py"""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from aliparaformerasr_amd import weights as W
