@@ -23,6 +23,10 @@ PF_ERR_TOKENS = -8
 PF_ERR_NULL_SAMPLES = -9
 PF_ERR_RECOGNITION = -10
 
+# pf_engine_set_decode / pf_recognizer_set_decode
+PF_DECODE_SCORES = 1
+PF_DECODE_CTC = 2
+
 
 class PfEngineConfig(C.Structure):
     _fields_ = [
@@ -101,6 +105,12 @@ SIGNATURES = {
     "pf_sync": (C.c_int, [_vp]),
     "pf_fetch": (C.c_int, [_vp, _P(PfBatchOut)]),
     "pf_fetch_ids_device": (C.c_int, [_vp, _vp, C.c_int32, _i32]),
+    "pf_engine_set_decode": (C.c_int, [_vp, C.c_int32]),
+    "pf_fetch_scores": (C.c_int, [_vp, _f, C.c_int64, _i32]),
+    "pf_fetch_ctc": (C.c_int, [_vp, _i64, _i32, _i32, _f, C.c_int32, _i32, _i32]),
+    "pf_op_ctc_collapse": (C.c_int, [_vp, _i64, _f, _i32, C.c_int32, C.c_int32, C.c_int32, _i64, _i32, _i32, _f, C.c_int32, _i32]),
+    "pf_recognizer_set_decode": (C.c_int, [_vp, C.c_int32]),
+    "pf_stream_scores": (C.c_int, [_vp, _P(_f), _i32]),
     "pf_host_group_sim": (C.c_int, [C.c_int32, C.c_int32, _i32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _i64,
                                     C.c_int32, _i32, _i32]),
     "pf_profile_enable": (C.c_int, [_vp, C.c_int32]),

@@ -295,6 +295,37 @@ int pf_fetch_ids_device(pf_engine* h, int64_t* ids_dev, int32_t l_cap, int32_t* 
   PF_CATCH
 }
 
+int pf_engine_set_decode(pf_engine* h, int32_t flags) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->set_decode(flags);
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_fetch_scores(pf_engine* h, float* scores, int64_t cap, int32_t* L_out) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->fetch_scores(scores, cap, L_out);
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_fetch_ctc(pf_engine* h, int64_t* ids, int32_t* first, int32_t* last, float* score, int32_t cap, int32_t* n,
+                 int32_t* n_max) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->fetch_ctc(ids, first, last, score, cap, n, n_max);
+  return PF_OK;
+  PF_CATCH
+}
+
 int pf_profile_enable(pf_engine* h, int32_t on) {
   PF_TRY
   E(h)->profile_enable(on != 0);
@@ -460,6 +491,19 @@ int pf_op_argmax(pf_engine* h, const float* x, int64_t rows, int32_t V, int64_t*
   NEED(x); NEED(ids);
   std::lock_guard<std::mutex> lk(e->mutex());
   e->op_argmax(x, rows, V, ids);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_op_ctc_collapse(pf_engine* h, const int64_t* ids, const float* scores, const int32_t* lens, int32_t B, int32_t T,
+                       int32_t blank, int64_t* ids_out, int32_t* first_out, int32_t* last_out, float* score_out, int32_t cap,
+                       int32_t* n_out) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  NEED(ids); NEED(scores); NEED(lens); NEED(ids_out); NEED(first_out); NEED(last_out); NEED(score_out); NEED(n_out);
+  PF_CHECK(B >= 0 && T > 0 && cap > 0, PF_ERR_INVALID_ARG, "ctc_collapse: bad shape");
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->op_ctc_collapse(ids, scores, lens, B, T, blank, ids_out, first_out, last_out, score_out, cap, n_out);
   return PF_OK;
   PF_CATCH
 }
@@ -914,6 +958,24 @@ int pf_stream_tokens(pf_stream* h, const int64_t** ids, int32_t* n) {
   Stream* s = S(h);
   if (ids) *ids = s->Tokens.data();
   if (n) *n = (int32_t)s->Tokens.size();
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_stream_scores(pf_stream* h, const float** scores, int32_t* n) {
+  PF_TRY
+  Stream* s = S(h);
+  if (scores) *scores = s->Scores.data();
+  if (n) *n = (int32_t)s->Scores.size();
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_recognizer_set_decode(pf_recognizer* h, int32_t flags) {
+  PF_TRY
+  std::shared_ptr<Recognizer> r = R(h);
+  PF_CHECK(!r->disposed(), PF_ERR_DISPOSED, "OfflineRecognizer");
+  r->SetDecode(flags);
   return PF_OK;
   PF_CATCH
 }

@@ -950,6 +950,8 @@ void Engine::run_staged(bool want_logits) {
   launch_lfr_cmvn_pad(stream_, (const float*)ws_fbank_.p, meta + 2 * (B + 1), t80d, B, T, fc_.lfr_m, fc_.lfr_n,
                       fc_.n_mels, cmvn_shift_, cmvn_scale_, cmvn_shift_ ? 1 : 0, 1, (float*)ws_speech_.p, sv_prompt_, P);
   prof_end("lfr_cmvn_pad");
+  dec_len_.resize(B);
+  for (int b = 0; b < B; ++b) dec_len_[b] = P + num_lfr_frames(st_n_[b]);
   forward_device((const float*)ws_speech_.p, B, T + P, want_logits);
 }
 
@@ -1449,11 +1451,12 @@ void Engine::predictor_and_decoder(int B, int T, bool want_logits) {
   logits_ld_ = (int)round_up(V, 4);                 // fp32 rows stay 16-byte aligned for any vocabulary size
   gemm("gemm_vocab", dec_out_, xdn16, D, Md, logits_, logits_ld_, nullptr, 0, nullptr, 0, nullptr, 0, false, 0, 1.f);
   prof_begin("argmax", 0);
-  launch_argmax(stream_, logits_, Md, V, logits_ld_, want_logits ? 2 : 1, ids_dev_);
+  launch_argmax(stream_, logits_, Md, V, logits_ld_, want_logits ? 2 : 1, ids_dev_, score_buf(Md));
   prof_end("argmax");
   if (bias_branch) seaco_head(B, L, e0, hid32, want_logits);
   join_ts();
   PF_HIP(hipMemcpyAsync(last_.ids.data(), ids_dev_, (size_t)Md * 8, hipMemcpyDeviceToHost, stream_));
+  queue_decode_results(B, L);
 }
 
 // Starts the BiCIF timestamp head of the current forward: beside the decoder on its own stream (default), or in line.
@@ -1804,19 +1807,69 @@ void Engine::sensevoice_head(int B, int T, bool want_logits) {
   logits_ld_ = (int)round_up(V, 4);
   gemm("gemm_vocab", ctc_, H16_, D, M, logits_, logits_ld_, nullptr, 0, nullptr, 0, nullptr, 0, false, 0, 1.f);
   prof_begin("argmax", 0);
-  launch_argmax(stream_, logits_, M, V, logits_ld_, want_logits ? 2 : 1, ids_dev_);
+  launch_argmax(stream_, logits_, M, V, logits_ld_, want_logits ? 2 : 1, ids_dev_, score_buf(M));
   prof_end("argmax");
   last_.B = B; last_.L = T; last_.V = V; last_.T = T;
   last_.ids.assign((size_t)M, 0);
   last_.token_num.assign(B, T);
   last_.fire_count.assign(B, T);
   PF_HIP(hipMemcpyAsync(last_.ids.data(), ids_dev_, (size_t)M * 8, hipMemcpyDeviceToHost, stream_));
+  queue_decode_results(B, T);
+}
+
+// ------------------------------------------------------------------ decoding extras ---------
+void Engine::set_decode(int flags) {
+  PF_CHECK((flags & ~(PF_DECODE_SCORES | PF_DECODE_CTC)) == 0, PF_ERR_INVALID_ARG, "set_decode: unknown flag bits");
+  if (flags & PF_DECODE_CTC) {
+    PF_CHECK(mc_.kind_id() == 1, PF_ERR_UNSUPPORTED, "PF_DECODE_CTC: only a SenseVoice model has a CTC head");
+    flags |= PF_DECODE_SCORES;
+  }
+  // the SeACo bias merge replaces rows of the result after the arg-max; their scores would need a path of their own
+  PF_CHECK(flags == 0 || !mc_.seaco, PF_ERR_UNSUPPORTED, "PF_DECODE_SCORES: not available for a SeACo model");
+  decode_flags_ = flags;
+}
+
+float* Engine::score_buf(int64_t rows) {
+  if (!decode_flags_) return nullptr;
+  ensure(ws_score_, (size_t)std::max<int64_t>(rows, 1) * 4);
+  return (float*)ws_score_.p;
+}
+
+void Engine::queue_decode_results(int B, int L) {
+  std::vector<int32_t>& len = ctc_len_;              // (a member: the host-to-device copy below may read it after this call returns)
+  len.clear();
+  len.swap(dec_len_);                                // consumed: a later forward without lengths decodes every row
+  if (!decode_flags_ || B * L == 0) return;
+  const float* sc = (const float*)ws_score_.p;
+  last_.scores.resize((size_t)B * L);
+  PF_HIP(hipMemcpyAsync(last_.scores.data(), sc, (size_t)B * L * 4, hipMemcpyDeviceToHost, stream_));
+  if (!(decode_flags_ & PF_DECODE_CTC)) return;
+  if ((int)len.size() != B) len.assign(B, L);
+  for (int b = 0; b < B; ++b) len[b] = std::min(std::max(len[b], 0), L);
+  const int cap = L;
+  const size_t words = HostBatchOut::ctc_words(B, cap);
+  ensure(ws_ctc_, words * 8 + (size_t)B * 4);
+  last_.ctc.resize(words);
+  last_.ctc_cap = cap;
+  int64_t* ids_o = (int64_t*)ws_ctc_.p;
+  int32_t* first_o = (int32_t*)(ids_o + (size_t)B * cap);
+  int32_t* last_o = first_o + (size_t)B * cap;
+  float* score_o = (float*)(last_o + (size_t)B * cap);
+  int32_t* n_o = last_o + 2 * (size_t)B * cap;
+  int32_t* len_d = (int32_t*)((char*)ws_ctc_.p + words * 8);
+  PF_HIP(hipMemcpyAsync(len_d, len.data(), (size_t)B * 4, hipMemcpyHostToDevice, stream_));
+  prof_begin("ctc_collapse", 0);
+  launch_ctc_collapse(stream_, ids_dev_, sc, len_d, B, L, 0, cap, n_o, ids_o, first_o, last_o, score_o);
+  prof_end("ctc_collapse");
+  PF_HIP(hipMemcpyAsync(last_.ctc.data(), ws_ctc_.p, words * 8, hipMemcpyDeviceToHost, stream_));
 }
 
 void Engine::forward_device(const float* speech_dev, int B, int T, bool want_logits) {
   PF_HIP(hipSetDevice(device_));
   PF_CHECK(B > 0 && T > 0, PF_ERR_INVALID_ARG, "forward: empty batch");
   last_logits_ = want_logits;
+  last_.decode_flags = decode_flags_;
+  last_.scores.clear(); last_.ctc.clear(); last_.ctc_cap = 0;
   if (fp32_mode_) { forward_fp32(speech_dev, B, T, want_logits); return; }
   if (int8_mode_) { forward_int8(speech_dev, B, T, want_logits); return; }
   encoder(speech_dev, B, T);
@@ -1855,6 +1908,12 @@ uint64_t Engine::register_uid() {
 void Engine::unregister_uid(uint64_t id) {
   std::lock_guard<std::mutex> lk(g_live_mu);
   g_live.erase(id);
+}
+
+// the calling thread's slot of engine `uid` (null: none published, or already released)
+static const HostBatchOut* t_slots_find(uint64_t uid) {
+  auto it = t_slots.find(uid);
+  return it == t_slots.end() ? nullptr : &it->second;
 }
 
 void Engine::publish_thread_result() {
@@ -1936,6 +1995,43 @@ void Engine::fetch(pf_batch_out* out) {
   // the call that receives the ids completes the learn-L-then-fetch protocol: release the slot (a B*L*V host
   // copy of the log-probs may hang off it)
   if (slot && out->token_ids) t_slots.erase(it);
+}
+
+void Engine::fetch_scores(float* scores, int64_t cap, int32_t* L_out) {
+  PF_HIP(hipStreamSynchronize(stream_));
+  check_async_errors();
+  auto it = t_slots_find(uid_);
+  const HostBatchOut& r = it ? *it : last_;
+  PF_CHECK(r.decode_flags & PF_DECODE_SCORES, PF_ERR_INVALID_ARG, "fetch_scores: PF_DECODE_SCORES was not set for the last forward");
+  if (L_out) *L_out = r.L;
+  const int64_t need = (int64_t)r.B * r.L;
+  if (!scores) return;
+  PF_CHECK(cap >= need, PF_ERR_CAPACITY, "scores capacity < B*L = " + std::to_string(need));
+  if (need > 0) std::memcpy(scores, r.scores.data(), (size_t)need * 4);
+}
+
+void Engine::fetch_ctc(int64_t* ids, int32_t* first, int32_t* last, float* score, int32_t cap, int32_t* n, int32_t* n_max) {
+  PF_HIP(hipStreamSynchronize(stream_));
+  check_async_errors();
+  auto it = t_slots_find(uid_);
+  const HostBatchOut& r = it ? *it : last_;
+  PF_CHECK(r.decode_flags & PF_DECODE_CTC, PF_ERR_INVALID_ARG, "fetch_ctc: PF_DECODE_CTC was not set for the last forward");
+  const int B = r.B;
+  const bool have = !r.ctc.empty();
+  int mx = 0;
+  for (int b = 0; b < B && have; ++b) mx = std::max(mx, r.ctc_n()[b]);
+  if (n_max) *n_max = mx;
+  if (n) for (int b = 0; b < B; ++b) n[b] = have ? r.ctc_n()[b] : 0;
+  if (!ids && !first && !last && !score) return;
+  PF_CHECK(cap >= mx, PF_ERR_CAPACITY, "ctc capacity " + std::to_string(cap) + " < n_max = " + std::to_string(mx));
+  for (int b = 0; b < B && have; ++b) {
+    const size_t src = (size_t)b * r.ctc_cap, dst = (size_t)b * cap;
+    const size_t k = (size_t)std::min(cap, r.ctc_cap);
+    if (ids) { std::memcpy(ids + dst, r.ctc_ids() + src, k * 8); std::fill(ids + dst + k, ids + dst + cap, (int64_t)-1); }
+    if (first) { std::memcpy(first + dst, r.ctc_first() + src, k * 4); std::fill(first + dst + k, first + dst + cap, -1); }
+    if (last) { std::memcpy(last + dst, r.ctc_last() + src, k * 4); std::fill(last + dst + k, last + dst + cap, -1); }
+    if (score) { std::memcpy(score + dst, r.ctc_score() + src, k * 4); std::fill(score + dst + k, score + dst + cap, 0.f); }
+  }
 }
 
 }  // namespace pf

@@ -119,6 +119,15 @@ class Engine {
   // SeACo: hotword ids [n, 10] (PadList output, EmbedSeacoModel.cs:70-123) used by the following forwards;
   // n = 0 -> bias_embed [B,0,512]: the bias branch is skipped and the ASR log-probs are returned
   void set_hotwords(const int32_t* hw, int n);
+  // Decoding extras of the forwards that follow (PF_DECODE_* of paraformer_hip.h; 0 = the reference behaviour, nothing
+  // extra is launched).  SCORES: the log-prob of every arg-max position [B, L].  CTC (SenseVoice only, implies SCORES):
+  // the collapse of k_ctc.hip over the first n_b frames of each utterance, right behind the arg-max on stream_.
+  void set_decode(int flags);
+  int decode_flags() const { return decode_flags_; }
+  void fetch_scores(float* scores, int64_t cap, int32_t* L_out);
+  void fetch_ctc(int64_t* ids, int32_t* first, int32_t* last, float* score, int32_t cap, int32_t* n, int32_t* n_max);
+  void op_ctc_collapse(const int64_t* ids, const float* scores, const int32_t* lens, int B, int T, int blank, int64_t* ids_out,
+                       int32_t* first_out, int32_t* last_out, float* score_out, int cap, int32_t* n_out);
   // ---- streaming seams (OnlineRecognizer.cs EncoderProj / DecoderProj) ------
   void online_encoder(const float* speech, int B, int Tc, float* enc_out, float* alphas_out);
   void online_decoder(const float* enc, int B, int Tc, const float* embeds, int L, const int32_t* embeds_len,
@@ -357,6 +366,12 @@ class Engine {
   int64_t st_total_frames_ = 0;
   const float* st_audio_ext_ = nullptr;   // base of the externally staged audio (stage_device_audio); null: ws_audio_
   HostBatchOut last_;
+  int decode_flags_ = 0;
+  std::vector<int32_t> dec_len_;     // n_b of the forward being queued (valid rows per utterance); empty: every row of the batch
+  std::vector<int32_t> ctc_len_;     // the lengths the queued collapse reads (clamped to [0, L]); alive until the next forward
+  DevBuf ws_score_, ws_ctc_;         // arg-max log-probs [B * L]; the collapse's len [B] and result block (HostBatchOut::ctc)
+  float* score_buf(int64_t rows);    // where the arg-max leaves its winners' values; null without decode flags
+  void queue_decode_results(int B, int L);   // behind the ids copy: the scores' copy, the collapse and its copy
   uint64_t uid_ = 0;                 // key of this engine in the per-thread result store
   static uint64_t register_uid();
   static void unregister_uid(uint64_t id);

@@ -254,12 +254,13 @@ void Engine::forward_fp32(const float* speech_dev, int B, int T, bool want_logit
     ensure(ws_dec_, o2);
     logits_ = (float*)((char*)ws_dec_.p + o_lg); ids_dev_ = (int64_t*)((char*)ws_dec_.p + o_ids); logits_ld_ = ldV;
     gemm32(H32_, D, ctc_.w32, D, ctc_.bias, M, V, D, logits_, ldV, nullptr, 0, false, 0, 1.f);
-    launch_argmax(stream_, logits_, M, V, ldV, want_logits ? 2 : 1, ids_dev_);
+    launch_argmax(stream_, logits_, M, V, ldV, want_logits ? 2 : 1, ids_dev_, score_buf(M));
     last_.B = B; last_.L = T; last_.V = V; last_.T = T;
     last_.ids.assign((size_t)M, 0);
     last_.token_num.assign(B, T);
     last_.fire_count.assign(B, T);
     PF_HIP(hipMemcpyAsync(last_.ids.data(), ids_dev_, (size_t)M * 8, hipMemcpyDeviceToHost, stream_));
+    queue_decode_results(B, T);
     last_flops_ = 0;
     return;
   }
@@ -325,10 +326,11 @@ void Engine::forward_fp32(const float* speech_dev, int B, int T, bool want_logit
   launch_layernorm(stream_, t32, Md, D, dec_after_.g, dec_after_.b, nullptr, 0, xn, D);
   cls32_ = "gemm32_vocab";
   gemm32(xn, D, dec_out_.w32, D, dec_out_.bias, Md, V, D, logits_, ldV, nullptr, 0, false, 0, 1.f);
-  launch_argmax(stream_, logits_, Md, V, ldV, want_logits ? 2 : 1, ids_dev_);
+  launch_argmax(stream_, logits_, Md, V, ldV, want_logits ? 2 : 1, ids_dev_, score_buf(Md));
   cls32_ = "gemm32_misc";
   if (bias_branch) seaco_head_fp32(B, L, e0, xn, want_logits);      // xn = the ASR decoder's after_norm hidden
   PF_HIP(hipMemcpyAsync(last_.ids.data(), ids_dev_, (size_t)Md * 8, hipMemcpyDeviceToHost, stream_));
+  queue_decode_results(B, L);
 }
 
 // ---- fp32 forms of the two heads (math_mode 1): the same graphs as timestamp_head / seaco_head with fp32 weights and
@@ -472,6 +474,7 @@ void Engine::forward_feats_host(const float* speech, int B, int T, bool want_log
   const size_t n = (size_t)B * T * mc_.feat_dim;
   ensure(ws_speech_, n * 4);
   PF_HIP(hipMemcpyAsync(ws_speech_.p, speech, n * 4, hipMemcpyHostToDevice, stream_));
+  dec_len_.clear();                                   // no lengths exist here: every row of the batch is valid
   forward_device((const float*)ws_speech_.p, B, T, want_logits);
 }
 
@@ -501,6 +504,8 @@ void Engine::model_proj_host(const float* const* speech, const int32_t* n_floats
   PF_HIP(hipMemcpyAsync(nd, n_floats, (size_t)B * 4, hipMemcpyHostToDevice, stream_));
   ensure(ws_speech_, (size_t)B * maxf * 4);
   launch_pad_sentinel(stream_, rag, offd, nd, B, maxf, (float*)ws_speech_.p);
+  dec_len_.resize(B);
+  for (int b = 0; b < B; ++b) dec_len_[b] = n_floats[b] / W;
   forward_device((const float*)ws_speech_.p, B, T, want_logits);
 }
 }  // namespace pf

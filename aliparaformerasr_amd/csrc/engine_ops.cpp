@@ -54,6 +54,35 @@ void Engine::op_argmax(const float* x, int64_t rows, int V, int64_t* ids) {
   PF_HIP(hipStreamSynchronize(stream_));
 }
 
+void Engine::op_ctc_collapse(const int64_t* ids, const float* scores, const int32_t* lens, int B, int T, int blank,
+                             int64_t* ids_out, int32_t* first_out, int32_t* last_out, float* score_out, int cap, int32_t* n_out) {
+  PF_HIP(hipSetDevice(device_));
+  if (B == 0) return;
+  const size_t in = (size_t)B * T, out = (size_t)B * cap;
+  // ids | ids_out (int64), then scores | score_out | first | last | lens | n (4-byte)
+  ensure(ws_tmp_, (in + out) * 8 + (in + 3 * out + 2 * (size_t)B) * 4);
+  int64_t* d_ids = (int64_t*)ws_tmp_.p;
+  int64_t* d_io = d_ids + in;
+  float* d_sc = (float*)(d_io + out);
+  float* d_so = d_sc + in;
+  int32_t* d_fo = (int32_t*)(d_so + out);
+  int32_t* d_lo = d_fo + out;
+  int32_t* d_len = d_lo + out;
+  int32_t* d_n = d_len + B;
+  PF_HIP(hipMemcpyAsync(d_ids, ids, in * 8, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipMemcpyAsync(d_sc, scores, in * 4, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipMemcpyAsync(d_len, lens, (size_t)B * 4, hipMemcpyHostToDevice, stream_));
+  launch_ctc_collapse(stream_, d_ids, d_sc, d_len, B, T, blank, cap, d_n, d_io, d_fo, d_lo, d_so);
+  PF_HIP(hipMemcpyAsync(ids_out, d_io, out * 8, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipMemcpyAsync(first_out, d_fo, out * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipMemcpyAsync(last_out, d_lo, out * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipMemcpyAsync(score_out, d_so, out * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipMemcpyAsync(n_out, d_n, (size_t)B * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipStreamSynchronize(stream_));
+  for (int b = 0; b < B; ++b)
+    PF_CHECK(n_out[b] <= cap, PF_ERR_CAPACITY, "ctc_collapse: capacity " + std::to_string(cap) + " < " + std::to_string(n_out[b]) + " tokens");
+}
+
 void Engine::op_gemm(const float* A, const float* W, const float* bias, int M, int N, int K, int epi, float* C) {
   PF_HIP(hipSetDevice(device_));
   if (M == 0 || N == 0) return;

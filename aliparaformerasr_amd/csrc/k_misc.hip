@@ -777,9 +777,10 @@ __device__ __forceinline__ VI vi_later(VI a, VI b) {
 // MODE 0: scan the values as given (stand-alone op).  MODE 1: scan the log-probs, do not store them.
 // MODE 2: scan the log-probs and store them in place.  NV > 0: the row (V <= 256 * NV) is held in registers
 // (one global read); NV == 0: the row is re-read (it stays in this CU's L1/L2).
-template <int MODE, int NV>
-__global__ __launch_bounds__(256) void argmax_kernel(float* __restrict__ x, int64_t rows, int V, int ldx,
-                                                     int64_t* __restrict__ ids) {
+// SC: also leave the winner's value in best_out[row] — bit for bit what MODE 2 stores at that index.
+template <int MODE, int NV, bool SC>
+__device__ __forceinline__ void argmax_body(float* __restrict__ x, int64_t rows, int V, int ldx, int64_t* __restrict__ ids,
+                                            float* __restrict__ best_out) {
   __shared__ float s_v[4];
   __shared__ int s_i[4];
   __shared__ int s_nan[4];
@@ -897,9 +898,36 @@ __global__ __launch_bounds__(256) void argmax_kernel(float* __restrict__ x, int6
     result = V - 1;                          // row of -inf only
   }
   if (tid == 0) ids[row] = result;
+  if constexpr (SC) {
+    if (last_nan < 0) {
+      if (tid == 0) best_out[row] = best.v;
+    } else if ((result & 255) == tid) {      // rare path: the thread that visited `result` forms its value again
+      float v = 0.f;
+      if constexpr (NV > 0) {
+#pragma unroll
+        for (int j = 0; j < NV; ++j) if (tid + 256 * j == result) v = val(j, result);
+      } else {
+        v = MODE == 2 ? xr[result] : val(0, result);
+      }
+      best_out[row] = v;
+    }
+  }
 }
 
-void launch_argmax(hipStream_t s, float* x, int64_t rows, int V, int ldx, int mode, int64_t* ids) {
+template <int MODE, int NV>
+__global__ __launch_bounds__(256) void argmax_kernel(float* __restrict__ x, int64_t rows, int V, int ldx,
+                                                     int64_t* __restrict__ ids) {
+  argmax_body<MODE, NV, false>(x, rows, V, ldx, ids, nullptr);
+}
+// the same scan for a caller that keeps the per-position confidence (PF_DECODE_SCORES); launched only on request, so a
+// pipeline without decode flags runs the instantiations above
+template <int MODE, int NV>
+__global__ __launch_bounds__(256) void argmax_score_kernel(float* __restrict__ x, int64_t rows, int V, int ldx,
+                                                           int64_t* __restrict__ ids, float* __restrict__ best_out) {
+  argmax_body<MODE, NV, true>(x, rows, V, ldx, ids, best_out);
+}
+
+void launch_argmax(hipStream_t s, float* x, int64_t rows, int V, int ldx, int mode, int64_t* ids, float* best_out) {
   if (rows == 0) return;
   const dim3 g((unsigned)rows), b(256);
   const bool small = V <= 256 * 36;          // paraformer's 8404-entry vocabulary: 33 values per thread
@@ -907,14 +935,22 @@ void launch_argmax(hipStream_t s, float* x, int64_t rows, int V, int ldx, int mo
                                              // re-reading form took 0.74 ms for 10 880 rows = 1.5 TB/s)
 #define PF_AM(MODE)                                                                                    \
   do {                                                                                                 \
-    if (small) hipLaunchKernelGGL((argmax_kernel<MODE, 36>), g, b, 0, s, x, rows, V, ldx, ids);      \
+    if (best_out) PF_AMS(MODE);                                                                        \
+    else if (small) hipLaunchKernelGGL((argmax_kernel<MODE, 36>), g, b, 0, s, x, rows, V, ldx, ids); \
     else if (mid) hipLaunchKernelGGL((argmax_kernel<MODE, 100>), g, b, 0, s, x, rows, V, ldx, ids);  \
     else hipLaunchKernelGGL((argmax_kernel<MODE, 0>), g, b, 0, s, x, rows, V, ldx, ids);             \
+  } while (0)
+#define PF_AMS(MODE)                                                                                                 \
+  do {                                                                                                               \
+    if (small) hipLaunchKernelGGL((argmax_score_kernel<MODE, 36>), g, b, 0, s, x, rows, V, ldx, ids, best_out);    \
+    else if (mid) hipLaunchKernelGGL((argmax_score_kernel<MODE, 100>), g, b, 0, s, x, rows, V, ldx, ids, best_out); \
+    else hipLaunchKernelGGL((argmax_score_kernel<MODE, 0>), g, b, 0, s, x, rows, V, ldx, ids, best_out);           \
   } while (0)
   if (mode == 0) PF_AM(0);
   else if (mode == 1) PF_AM(1);
   else PF_AM(2);
 #undef PF_AM
+#undef PF_AMS
   PF_HIP(hipGetLastError());
 }
 

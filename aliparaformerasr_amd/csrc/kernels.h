@@ -342,6 +342,13 @@ void launch_seaco_merge(hipStream_t s, const float* dha, int ld_dha, const int64
                         int nobias, int copy_logits, float* logits, int ld_logits, int64_t* ids);
 // last-index arg-max over rows of width V.  mode 0: over the values as given; 1: over the log-probs
 // y = (x - max) - log(sum exp(x - max)) (what the reference scans), y not stored; 2: same, y stored in place
-void launch_argmax(hipStream_t s, float* x, int64_t rows, int V, int ldx, int mode, int64_t* ids);
+// best_out (optional, [rows]): the value at the winning index, as mode 2 stores it (the position's confidence)
+void launch_argmax(hipStream_t s, float* x, int64_t rows, int V, int ldx, int mode, int64_t* ids, float* best_out = nullptr);
+// ------------------------------------------------------------------ CTC ------
+// CTC collapse of per-frame ids [B, T] with their log-probs [B, T] over the first len[b] frames of each row (k_ctc.hip):
+// n_out[b] tokens, and per token (arrays [B, cap], frame order) id, first / last frame and the run's largest log-prob;
+// slots past n_out[b] hold -1 / -1 / -1 / 0.  A token whose slot is >= cap is counted but not stored.
+void launch_ctc_collapse(hipStream_t s, const int64_t* ids, const float* score, const int32_t* len, int B, int T, int blank,
+                         int cap, int32_t* n_out, int64_t* ids_out, int32_t* first_out, int32_t* last_out, float* score_out);
 
 }  // namespace pf

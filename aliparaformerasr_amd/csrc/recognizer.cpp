@@ -460,7 +460,26 @@ Recognizer::Recognizer(const std::string& model, const std::string& config, cons
 
 std::shared_ptr<Engine> Recognizer::make_engine() {
   std::shared_ptr<void> img = image_;                // the engine points into the image: it must outlive the engine
-  return std::shared_ptr<Engine>(new Engine(ec_), [img](Engine* e) { delete e; });
+  std::shared_ptr<Engine> e(new Engine(ec_), [img](Engine* p) { delete p; });
+  if (decode_flags_) e->set_decode(decode_flags_);
+  return e;
+}
+
+void Recognizer::SetDecode(int flags) {
+  std::vector<std::shared_ptr<Engine>> es;
+  {
+    std::lock_guard<std::mutex> lk(mu_);
+    if (disposed_ || engines_.empty()) throw Error(PF_ERR_DISPOSED, "OfflineRecognizer");
+    es = engines_;
+  }
+  // engine 0 first: it refuses what the model kind does not offer before anything is stored.  An engine's mutex is held
+  // by the call in flight on it: its flags change between forwards (Forward also applies them under its lease, which
+  // covers an engine that joined the pool meanwhile)
+  for (size_t i = 0; i < es.size(); ++i) {
+    std::lock_guard<std::mutex> lk(es[i]->mutex());
+    es[i]->set_decode(flags);
+    if (i == 0) decode_flags_ = es[0]->decode_flags();
+  }
 }
 
 int Recognizer::feature_floats(int64_t n) {
@@ -815,6 +834,8 @@ void Recognizer::Forward(const std::vector<Stream*>& streams) {
     const ModelCfg& mc = e->model();
     const int W = mc.feat_dim;
     const int B = (int)streams.size();
+    if (e->decode_flags() != decode_flags_) e->set_decode(decode_flags_);
+    const int dflags = e->decode_flags();
     fc.lap(0);
     if (!all_dev && sv) {
       // SenseVoice split-embed variant: prepend [emb(lang), emb(1), emb(2), emb(textnorm)] to Speech
@@ -890,13 +911,39 @@ void Recognizer::Forward(const std::vector<Stream*>& streams) {
     std::vector<float> peak((size_t)B * std::max(P, 1));
     if (P > 0) { out.cif_peak = peak.data(); out.cif_peak_cap = (int64_t)peak.size(); }
     e->fetch(&out);
+    // decoding extras (SetDecode): host copies of what the forward left beside the ids
+    std::vector<float> scores;
+    std::vector<int64_t> c_ids; std::vector<int32_t> c_first, c_last, c_n; std::vector<float> c_score;
+    int c_cap = 0;
+    if (dflags & PF_DECODE_CTC) {
+      int32_t n_max = 0;
+      c_n.resize(B);
+      e->fetch_ctc(nullptr, nullptr, nullptr, nullptr, 0, c_n.data(), &n_max);
+      c_cap = std::max(n_max, 1);
+      c_ids.resize((size_t)B * c_cap); c_first.resize(c_ids.size()); c_last.resize(c_ids.size()); c_score.resize(c_ids.size());
+      e->fetch_ctc(c_ids.data(), c_first.data(), c_last.data(), c_score.data(), c_cap, nullptr, nullptr);
+    } else if (dflags & PF_DECODE_SCORES) {
+      scores.resize((size_t)B * std::max(L, 1));
+      e->fetch_scores(scores.data(), (int64_t)scores.size(), nullptr);
+    }
     fc.lap(5);
     lease.release();                      // the device work of this call is over: the text stage below needs no engine
     for (int b = 0; b < B; ++b) {
       Stream* s = streams[b];
       s->Tokens.assign(ids.begin() + (size_t)b * out.l_cap, ids.begin() + (size_t)b * out.l_cap + L);   // :187
+      s->Scores.clear();
+      if (dflags == PF_DECODE_SCORES) s->Scores.assign(scores.begin() + (size_t)b * L, scores.begin() + (size_t)b * L + L);
       s->Timestamps.reserve(s->Timestamps.size() + (size_t)L);
-      if (P > 0) {
+      if (dflags & PF_DECODE_CTC) {
+        // the collapsed hypothesis instead of the per-frame ids: one [begin, end] pair per token from its first / last frame
+        // (a frame = lfr_n x 10 ms; the four prompt rows carry no audio, so a run inside them gets {0, 0})
+        const size_t o = (size_t)b * c_cap;
+        const int n = c_n[b], ms = conf_.lfr_n * 10, Pr = 4;
+        s->Tokens.assign(c_ids.begin() + o, c_ids.begin() + o + n);
+        s->Scores.assign(c_score.begin() + o, c_score.begin() + o + n);
+        for (int k = 0; k < n; ++k)
+          s->Timestamps.push_back({ms * std::max(c_first[o + k] - Pr, 0), ms * std::max(c_last[o + k] + 1 - Pr, 0)});
+      } else if (P > 0) {
         // :172-183: the peak row and ALL L arg-max ids go to time_stamp_lfr6_onnx
         TsList ts = time_stamp_lfr6(peak.data() + (size_t)b * P, P, s->Tokens);
         for (auto& t2 : ts) s->Timestamps.push_back(t2);

@@ -122,6 +122,7 @@ class Stream {
   std::vector<std::vector<int32_t>> Hotwords;
   std::vector<int64_t> Tokens{0, 0};                          // OfflineStream.cs:26
   TsList Timestamps;
+  std::vector<float> Scores;                                  // of the last GetResults (Recognizer::SetDecode); empty without a flag
   void RemoveChunk();                                         // OfflineStream.cs:69-79
   bool disposed = false;
   std::shared_ptr<Recognizer> owner;
@@ -140,6 +141,10 @@ class Recognizer : public std::enable_shared_from_this<Recognizer> {
   void GetResults(const std::vector<Stream*>& streams);
   const std::vector<ResultEntity>& results_of_this_thread();
   void Dispose();                                             // waits for calls in flight, then frees the engines
+  // Decoding extras (PF_DECODE_*) of every GetResults that follows, on every engine of the pool, present and future.  With
+  // PF_DECODE_CTC (SenseVoice) Forward leaves the collapsed ids, [begin, end] milliseconds per token and the token scores
+  // in the streams; DecodeMulti, RemoveChunk and the Q8 branch run unchanged on those Tokens.
+  void SetDecode(int flags);
   bool disposed() const { return disposed_.load(); }
   // engine 0 (nullptr once disposed): what pf_recognizer_engine hands out; callers lock engine->mutex() themselves
   std::shared_ptr<Engine> engine() { std::lock_guard<std::mutex> lk(mu_); return engines_.empty() ? nullptr : engines_[0]; }
@@ -232,6 +237,7 @@ class Recognizer : public std::enable_shared_from_this<Recognizer> {
   std::vector<std::vector<int32_t>> hotwords_;
   uint64_t uid_ = 0;                                          // key of this recognizer in the per-thread result store
   std::atomic<bool> disposed_{false};
+  std::atomic<int> decode_flags_{0};
   friend class Stream;
 };
 

@@ -32,6 +32,19 @@ struct HostBatchOut { // results of a forward, host side
   int peak_len = 0;
   std::vector<float> logits;       // [B, L, V] host copy (per-thread result slots only)
   bool has_logits = false;
+  // decoding extras (Engine::set_decode); empty without the flag
+  int decode_flags = 0;
+  std::vector<float> scores;       // [B, L] log-prob of ids[b, l]
+  // CTC collapse as the kernel leaves it, one block: ids [B, cap] int64 | first [B, cap] | last [B, cap] int32 |
+  // score [B, cap] fp32 | n [B] int32
+  std::vector<int64_t> ctc;
+  int ctc_cap = 0;
+  static size_t ctc_words(int B, int cap) { return (size_t)B * cap + ((size_t)B * cap * 12 + (size_t)B * 4 + 7) / 8; }
+  const int64_t* ctc_ids() const { return ctc.data(); }
+  const int32_t* ctc_first() const { return (const int32_t*)(ctc.data() + (size_t)B * ctc_cap); }
+  const int32_t* ctc_last() const { return ctc_first() + (size_t)B * ctc_cap; }
+  const float* ctc_score() const { return (const float*)(ctc_last() + (size_t)B * ctc_cap); }
+  const int32_t* ctc_n() const { return ctc_last() + 2 * (size_t)B * ctc_cap; }
 };
 
 // rendezvous of the G worker threads with a max-reduction; abort() releases every waiter with an Error

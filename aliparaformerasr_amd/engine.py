@@ -16,14 +16,31 @@ def _f32(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
+class CtcResult:
+    """The CTC collapse of a batch (PF_DECODE_CTC): n [B] token counts; ids (int64), first / last (frame indices in the
+    row, prompt rows included) and score (the run's largest frame log-prob), each [B, max(n)]; slots past n[b] hold
+    -1 / -1 / -1 / 0."""
+
+    def __init__(self, n, ids, first, last, score):
+        self.n, self.ids, self.first, self.last, self.score = n, ids, first, last, score
+
+    def tokens(self, b):
+        """[(id, first, last, score)] of utterance b."""
+        k = int(self.n[b])
+        return list(zip(self.ids[b, :k].tolist(), self.first[b, :k].tolist(), self.last[b, :k].tolist(),
+                        self.score[b, :k].tolist()))
+
+
 class BatchResult:
-    def __init__(self, token_ids, token_num, L, V, logits=None, cif_peak=None):
+    def __init__(self, token_ids, token_num, L, V, logits=None, cif_peak=None, scores=None, ctc=None):
         self.token_ids = token_ids      # [B, L] int64
         self.token_num = token_num      # [B] int32
         self.L = L
         self.V = V
         self.logits = logits            # [B, L, V] float32 log-probs or None
         self.cif_peak = cif_peak        # [B, 3*Tmax] float32 us_cif_peak (timestamp models) or None
+        self.scores = scores            # [B, L] float32 log-prob of token_ids (Engine.set_decode) or None
+        self.ctc = ctc                  # CtcResult (Engine.set_decode(PF_DECODE_CTC)) or None
 
 
 def _build_config(weights, weights_path, weights_device_ptr, weights_bytes, cmvn, mvn_path, device, dither, snip_edges,
@@ -65,8 +82,33 @@ def _build_config(weights, weights_path, weights_device_ptr, weights_bytes, cmvn
     return cfg, keep
 
 
-def _collect_result(lib, fetch_fn, call, B, want_logits):
-    """The learn-L-then-fetch protocol shared by pf_engine and pf_group handles."""
+def _i32p(a: np.ndarray):
+    return a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def _fetch_decode(lib, h, B, L, flags):
+    """scores / CTC result of the calling thread's last forward (before the pf_fetch that takes the ids)."""
+    scores = ctc = None
+    if flags & N.PF_DECODE_SCORES:
+        scores = np.zeros((B, L), np.float32)
+        N.check(lib.pf_fetch_scores(h, _fp(scores), scores.size, None))
+    if flags & N.PF_DECODE_CTC:
+        n, n_max = np.zeros(B, np.int32), C.c_int32()
+        N.check(lib.pf_fetch_ctc(h, None, None, None, None, 0, _i32p(n), n_max))
+        cap = max(n_max.value, 1)
+        ids = np.zeros((B, cap), np.int64)
+        first, last = np.zeros((B, cap), np.int32), np.zeros((B, cap), np.int32)
+        score = np.zeros((B, cap), np.float32)
+        N.check(lib.pf_fetch_ctc(h, ids.ctypes.data_as(C.POINTER(C.c_int64)), _i32p(first), _i32p(last), _fp(score), cap,
+                                 None, None))
+        k = n_max.value
+        ctc = CtcResult(n, ids[:, :k].copy(), first[:, :k].copy(), last[:, :k].copy(), score[:, :k].copy())
+    return scores, ctc
+
+
+def _collect_result(lib, fetch_fn, call, B, want_logits, decode=None):
+    """The learn-L-then-fetch protocol shared by pf_engine and pf_group handles.  decode = (engine handle, flags):
+    also the decoding extras of an engine with Engine.set_decode flags."""
     out = N.PfBatchOut()
     out.struct_size = C.sizeof(N.PfBatchOut)
     N.check(call(out))                       # first pass: learn L, V (no buffers)
@@ -86,8 +128,11 @@ def _collect_result(lib, fetch_fn, call, B, want_logits):
         logits = np.zeros((B, L, V), np.float32)
         out.logits = _fp(logits)
         out.logits_cap = logits.size
+    scores = ctc = None
+    if decode is not None and decode[1]:
+        scores, ctc = _fetch_decode(lib, decode[0], B, L, decode[1])
     N.check(fetch_fn(C.byref(out)))
-    return BatchResult(ids[:, :L].copy(), tn, L, V, logits, peak)
+    return BatchResult(ids[:, :L].copy(), tn, L, V, logits, peak, scores, ctc)
 
 
 class Engine:
@@ -107,6 +152,7 @@ class Engine:
         kind, vocab, feat, ts = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
         N.check(self._lib.pf_engine_info(self._h, kind, vocab, feat, ts))
         self.kind, self.vocab, self.feat_dim = kind.value, vocab.value, feat.value
+        self._decode = 0
 
     def close(self):
         if getattr(self, "_h", None):
@@ -144,7 +190,30 @@ class Engine:
 
     # ---- forward ------------------------------------------------------------
     def _collect(self, call, B, want_logits):
-        return _collect_result(self._lib, lambda o: self._lib.pf_fetch(self._h, o), call, B, want_logits)
+        return _collect_result(self._lib, lambda o: self._lib.pf_fetch(self._h, o), call, B, want_logits,
+                               (self._h, self._decode))
+
+    def set_decode(self, flags: int):
+        """Decoding extras of the forwards that follow (_native.PF_DECODE_SCORES | PF_DECODE_CTC; 0 = off, the reference
+        behaviour): BatchResult.scores, and for a SenseVoice model BatchResult.ctc."""
+        N.check(self._lib.pf_engine_set_decode(self._h, int(flags)))
+        self._decode = int(flags) | (N.PF_DECODE_SCORES if int(flags) & N.PF_DECODE_CTC else 0)
+
+    def op_ctc_collapse(self, ids, scores, lens, blank=0, cap=None) -> CtcResult:
+        """The pipeline's CTC collapse kernel on caller data: ids / scores [B, T], lens [B]."""
+        y = np.ascontiguousarray(ids, dtype=np.int64)
+        sc = _f32(scores)
+        ln = np.ascontiguousarray(lens, dtype=np.int32)
+        B, T = y.shape
+        cap = T if cap is None else cap
+        n = np.zeros(B, np.int32)
+        io = np.zeros((B, cap), np.int64)
+        fo, lo = np.zeros((B, cap), np.int32), np.zeros((B, cap), np.int32)
+        so = np.zeros((B, cap), np.float32)
+        i64 = C.POINTER(C.c_int64)
+        N.check(self._lib.pf_op_ctc_collapse(self._h, y.ctypes.data_as(i64), _fp(sc), _i32p(ln), B, T, blank,
+                                             io.ctypes.data_as(i64), _i32p(fo), _i32p(lo), _fp(so), cap, _i32p(n)))
+        return CtcResult(n, io, fo, lo, so)
 
     @staticmethod
     def _hw(hotwords):

@@ -1,7 +1,7 @@
 """Command-line harness mirroring AliParaformerAsr.Examples (`-type offline` and `-type online`).
 
     python -m aliparaformerasr_amd.examples -type offline -method batch -base <dir> -model <name> \
-        [-accuracy int8] [-threads 2] -files a.wav b.wav
+        [-accuracy int8] [-threads 2] [-decode ctc|frames] -files a.wav b.wav
     python -m aliparaformerasr_amd.examples -type online -method one -base <dir> -model <name> -files a.wav
 
 Mirrors (file:line in /root/reference/AliParaformerAsr.Examples):
@@ -18,7 +18,9 @@ Mirrors (file:line in /root/reference/AliParaformerAsr.Examples):
   * `-type online` (Program.cs:290-297) — OnlineAliParaformerAsrRecognizer.cs:8-279: encoder / decoder file selection
     (:43-63), at most TWO media files (:121-171), 9600-sample chunks (AudioHelper.GetFileChunkSamples :80-127) plus six
     400-sample silence chunks (:160-163), one AddSamples + GetResult + printed text per chunk (:181-194; only the "one"
-    method exists upstream — the batch loop is commented out there), timing lines :272-279."""
+    method exists upstream — the batch loop is commented out there), timing lines :272-279.
+Not in the reference: `-decode ctc` (offline, SenseVoice models) prints the CTC-collapsed hypothesis with per-token
+timestamps (OfflineRecognizer.SetDecode); `-decode frames`, the default, is the reference's one id per frame."""
 from __future__ import annotations
 
 import ctypes as C
@@ -108,7 +110,7 @@ def _result_line(r) -> str:
 
 
 def offline_recognizer(method="one", model="paraformer-seaco-large-zh-timestamp-onnx-offline", accuracy="int8",
-                       threads=2, files=None, base=None, out=sys.stdout):
+                       threads=2, files=None, base=None, out=sys.stdout, decode="frames"):
     from .offline_recognizer import OfflineRecognizer
     base = base or os.getcwd()
     sel = select_model_files(base, model, accuracy)
@@ -117,6 +119,8 @@ def offline_recognizer(method="one", model="paraformer-seaco-large-zh-timestamp-
         return None
     t0 = time.perf_counter()
     rec = OfflineRecognizer(threadsNum=threads, **sel)
+    if decode == "ctc":
+        rec.SetDecode(ctc=True)
     print("init_models_elapsed_milliseconds:%s" % ((time.perf_counter() - t0) * 1e3), file=out)
     if not files:
         files = []
@@ -273,6 +277,11 @@ def parse_args(argv, env=None):
             if i + 1 < len(argv):
                 i += 1
                 cfg[key] = argv[i]
+        elif a == "-decode":
+            i += 1
+            if i >= len(argv) or argv[i].lower() not in ("ctc", "frames"):
+                raise ValueError("The decode type must be ctc or frames")
+            cfg["decode"] = argv[i].lower()
         elif a == "-threads":
             try:
                 i += 1
@@ -306,7 +315,7 @@ def main(argv=None):
                           cfg["modelBasePath"] or None)
     elif cfg["recognizerType"] == "offline":
         offline_recognizer(cfg["methodType"], cfg["modelName"], cfg["modelAccuracy"], cfg["threads"], cfg["files"],
-                           cfg["modelBasePath"] or None)
+                           cfg["modelBasePath"] or None, decode=cfg.get("decode", "frames"))
     else:
         print("the recognizer type must be online or offline")
         return 2

@@ -155,6 +155,14 @@ class OfflineStream:
         _ck(self._lib.pf_stream_set_tokens(self._h, a, len(value)))
 
     @property
+    def Scores(self) -> List[float]:
+        """Scores of the last GetResults, parallel to Tokens (OfflineRecognizer.SetDecode; empty without it)."""
+        p = C.POINTER(C.c_float)()
+        n = C.c_int32()
+        _ck(self._lib.pf_stream_scores(self._h, C.byref(p), n))
+        return [p[i] for i in range(n.value)]
+
+    @property
     def Timestamps(self) -> List[List[int]]:
         n = C.c_int32()
         _ck(self._lib.pf_stream_num_timestamps(self._h, n))
@@ -239,6 +247,14 @@ class OfflineRecognizer:
         s = C.c_void_p()
         _ck(self._lib.pf_recognizer_create_stream(self._h, C.byref(s)))
         return OfflineStream(_lib=self._lib, _handle=s, _recognizer=self)
+
+    def SetDecode(self, ctc: bool = False, scores: bool = False) -> None:
+        """Decoding beyond the reference's, for every GetResults that follows (off by default).  ctc (SenseVoice): the
+        streams' Tokens are the CTC-collapsed ids (repeats merged, blanks dropped, nothing read past the utterance's own
+        frames), Timestamps one [begin, end] pair in milliseconds per token, Scores the token confidences (log-probs).
+        scores alone: Scores is the log-prob of every position of Tokens; Tokens / Timestamps stay as they are."""
+        flags = (N.PF_DECODE_CTC if ctc else 0) | (N.PF_DECODE_SCORES if scores else 0)
+        _ck(self._lib.pf_recognizer_set_decode(self._h, flags))
 
     def GetResult(self, stream: OfflineStream) -> OfflineRecognizerResultEntity:
         return self.GetResults([stream])[0]

@@ -109,6 +109,19 @@ namespace AliParaformerAsr.Hip
             }
         }
 
+        /// <summary>Not in the reference: scores (log-probs) of the last GetResults, parallel to Tokens — token confidences
+        /// after OfflineRecognizer.SetDecode(ctc: true), per-position values after SetDecode(scores: true), else empty.</summary>
+        public List<float> Scores
+        {
+            get
+            {
+                ParaformerHip.Check(ParaformerHip.pf_stream_scores(Handle, out IntPtr p, out int n));
+                var a = new float[n];
+                if (n > 0) Marshal.Copy(p, a, 0, n);
+                return new List<float>(a);
+            }
+        }
+
         public List<int[]> Timestamps                                           // OfflineStream.cs:33
         {
             get
@@ -155,6 +168,14 @@ namespace AliParaformerAsr.Hip
         /// (OfflineRecognizer.cs:110-198), so a server calls it from several threads; here every call takes a free engine of the
         /// pool (same device, one copy of the weights) — created on demand up to $PF_RECOGNIZER_ENGINES (default 2).</summary>
         public int NumEngines { get { int n = ParaformerHip.pf_recognizer_num_engines(_r); ParaformerHip.Check(n < 0 ? n : 0); return n; } }
+
+        /// <summary>Not in the reference: decoding beyond it for every GetResults that follows (off by default).  ctc (SenseVoice
+        /// models): the streams' Tokens are the CTC-collapsed ids (repeats merged, blanks dropped, nothing read past the
+        /// utterance's own frames), Timestamps one [begin, end] pair in milliseconds per token, Scores the token confidences.
+        /// scores alone: Scores holds the log-prob of every position of Tokens.</summary>
+        public void SetDecode(bool ctc = false, bool scores = false)
+            => ParaformerHip.Check(ParaformerHip.pf_recognizer_set_decode(_r, (ctc ? ParaformerHip.PF_DECODE_CTC : 0) |
+                                                                              (scores ? ParaformerHip.PF_DECODE_SCORES : 0)));
 
         public OfflineStream CreateOfflineStream()
         {

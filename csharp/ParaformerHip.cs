@@ -66,6 +66,13 @@ namespace AliParaformerAsr.Native
                                                                 int[]? hotwords, int nHotwords, ref PfBatchOut o);
         [DllImport(Lib)] internal static extern int pf_fetch(IntPtr e, ref PfBatchOut o);
         [DllImport(Lib)] internal static extern int pf_fetch_ids_device(IntPtr e, IntPtr idsDev, int lCap, out int L);
+        // decoding extras (additions to ABI 6): PF_DECODE_SCORES = 1, PF_DECODE_CTC = 2 (CTC collapse with per-token first /
+        // last frame and score, SenseVoice); fetch them BEFORE the pf_fetch that receives token_ids
+        internal const int PF_DECODE_SCORES = 1, PF_DECODE_CTC = 2;
+        [DllImport(Lib)] internal static extern int pf_engine_set_decode(IntPtr e, int flags);
+        [DllImport(Lib)] internal static extern int pf_fetch_scores(IntPtr e, [Out] float[]? scores, long cap, out int L);
+        [DllImport(Lib)] internal static extern int pf_fetch_ctc(IntPtr e, [Out] long[]? ids, [Out] int[]? first, [Out] int[]? last,
+                                                                [Out] float[]? score, int cap, [Out] int[]? n, out int nMax);
 
         // ---- several GPUs in one process (paraformer_hip.h section 4b) ------------------------------------------
         [DllImport(Lib)] internal static extern int pf_group_create(ref PfEngineConfig cfg, int[] devices, int nDevices, out IntPtr group);
@@ -101,6 +108,8 @@ namespace AliParaformerAsr.Native
         [DllImport(Lib)] internal static extern int pf_stream_get_hotwords(IntPtr s, [Out] int[] ids, int idsCap, [Out] int[] lens, int lensCap, out int nHotwords);
         [DllImport(Lib)] internal static extern int pf_stream_num_feature_floats(IntPtr s, out int n);
         [DllImport(Lib)] internal static extern int pf_stream_tokens(IntPtr s, out IntPtr ids, out int n);
+        [DllImport(Lib)] internal static extern int pf_recognizer_set_decode(IntPtr r, int flags);
+        [DllImport(Lib)] internal static extern int pf_stream_scores(IntPtr s, out IntPtr scores, out int n);
         // ABI 6: the rest of OfflineStream's public surface (OfflineStream.cs:20-34)
         [DllImport(Lib)] internal static extern int pf_stream_create([MarshalAs(UnmanagedType.LPUTF8Str)] string mvnPath, int fs, int nMels, int lfrM, int lfrN,
                                                                     int snipEdges, float dither, [MarshalAs(UnmanagedType.LPUTF8Str)] string window, out IntPtr stream);

@@ -191,6 +191,33 @@ int pf_fetch(pf_engine* e, pf_batch_out* out);
    caller, the host copy the reference makes of the logits tensor (OfflineProjOfParaformer.cs:73-79). */
 int pf_fetch_ids_device(pf_engine* e, int64_t* ids_dev, int32_t l_cap, int32_t* L_out);
 
+/* ---- Decoding extras (additions to ABI 6; default 0 = the reference behaviour, bit for bit) ------------------------
+   pf_engine_set_decode sets flags for the forwards that FOLLOW on this engine (like pf_engine_set_hotwords):
+     PF_DECODE_SCORES  keep s[b, l], the log-prob of the arg-max id at every position [B, L] — the value the arg-max
+                       compared, (x - max) - log(sum exp(x - max)).  paraformer and SenseVoice, every math_mode.
+     PF_DECODE_CTC     implies SCORES.  SenseVoice only.  The CTC collapse the reference leaves commented out
+                       (OfflineRecognizer.cs:153-168) runs on the device right behind the arg-max: over the first n_b frames
+                       of utterance b a token starts at frame t when y[t] != 0 (blank) and (t == 0 or y[t] != y[t-1]) and
+                       extends while y stays equal ("a a _ a b b" -> a, a, b).  Per token: id, first / last frame (indices in
+                       the row, prompt rows included) and score = the largest s[t] of its run.
+   n_b = 4 + pf_frontend_num_frames(n_samples[b]) for pf_recognize / pf_stage_audio + pf_run_staged,
+         speech_len_floats[b] / feat_dim for pf_model_proj, Tmax for pf_forward_feats (no lengths exist there).
+   The encoder still runs every row at the batch length (quirk Q2): frame ids of a short utterance depend on its batch
+   mates; the collapse only stops reading at n_b.
+   PF_ERR_UNSUPPORTED: PF_DECODE_CTC on a paraformer / SeACo model, any flag on a SeACo model.
+   The fetch calls read the calling thread's last forward, like pf_fetch — call them BEFORE the pf_fetch that receives
+   token_ids (it releases the thread's slot).  PF_ERR_INVALID_ARG when that forward ran without the flag. */
+#define PF_DECODE_SCORES 1
+#define PF_DECODE_CTC 2
+int pf_engine_set_decode(pf_engine* e, int32_t flags);
+/* scores [B, L] (NULL: only learn L); PF_ERR_CAPACITY when cap < B * L */
+int pf_fetch_scores(pf_engine* e, float* scores, int64_t cap, int32_t* L_out);
+/* n [B] token counts and *n_max their maximum (both optional); ids / first / last / score: arrays [B, cap], each
+   optional, slots >= n[b] hold -1 / -1 / -1 / 0.  All four NULL: only learn n and n_max.  PF_ERR_CAPACITY when
+   cap < n_max (n and n_max are filled in first). */
+int pf_fetch_ctc(pf_engine* e, int64_t* ids, int32_t* first, int32_t* last, float* score, int32_t cap, int32_t* n,
+                 int32_t* n_max);
+
 /* ------------------------------------------------------------------------ */
 /* 4b. Multi-GPU inside one process: one engine, one host thread and one HIP stream per listed
  *     device.  The reference builds a single ORT session (OfflineRecognizer.cs:23); what shards is the utterance
@@ -255,6 +282,11 @@ int pf_op_lfr_cmvn_pad(pf_engine* e, const float* const* fbank, const int32_t* t
                        int32_t apply_sentinel, float* out, int64_t out_cap, int32_t* tmax_out);
 /* last-index arg-max over the trailing dim: x [rows, V] -> ids [rows]. */
 int pf_op_argmax(pf_engine* e, const float* x, int64_t rows, int32_t V, int64_t* ids_out);
+/* exactly the pipeline's CTC collapse kernel (k_ctc.hip) on caller data: ids / scores [B, T], lens [B] (clamped to
+   [0, T]); outputs as pf_fetch_ctc, arrays [B, cap].  PF_ERR_CAPACITY (n_out filled in) when a row has more than cap tokens */
+int pf_op_ctc_collapse(pf_engine* e, const int64_t* ids, const float* scores, const int32_t* lens, int32_t B, int32_t T,
+                       int32_t blank, int64_t* ids_out, int32_t* first_out, int32_t* last_out, float* score_out, int32_t cap,
+                       int32_t* n_out);
 /* C = A[M,K] * W[N,K]^T + bias, f16 operands / f32 accumulate; epilogue 0 none, 1 relu,
    2 = f16 result store (the path the pipeline uses), returned widened to fp32. */
 /* One dynamically quantised Linear, the building block of math_mode 2 (the reference's default model.int8.onnx:
@@ -462,6 +494,14 @@ int pf_result_timestamp(pf_recognizer* r, int32_t i, int32_t j, const int32_t** 
 int pf_result_num_timestamps(pf_recognizer* r, int32_t i, int32_t* n);
 /* stream.Tokens after Forward (raw ids, OfflineRecognizer.cs:187). */
 int pf_stream_tokens(pf_stream* s, const int64_t** ids, int32_t* n);
+/* Decoding extras for every engine of the recognizer's pool, present and future (PF_DECODE_*, see pf_engine_set_decode).
+   With PF_DECODE_CTC (SenseVoice) GetResults leaves in each stream the COLLAPSED ids as Tokens, one
+   [begin, end] pair in milliseconds per token as Timestamps (ms = lfr_n * 10, P = 4 prompt rows:
+   begin = ms * max(first - P, 0), end = ms * max(last + 1 - P, 0)) and the token scores; with PF_DECODE_SCORES alone
+   Tokens / Timestamps stay as they are and the scores are the [L] per-position row. */
+int pf_recognizer_set_decode(pf_recognizer* r, int32_t flags);
+/* scores of the stream's last GetResults, parallel to pf_stream_tokens (n = 0 without a decode flag) */
+int pf_stream_scores(pf_stream* s, const float** scores, int32_t* n);
 
 /* ABI 6: the rest of OfflineStream's public surface (OfflineStream.cs:20-34).  Only the reference's own Forward touches
    these members, but "same public signatures" means a caller may.
