@@ -27,6 +27,38 @@ PF_ERR_RECOGNITION = -10
 PF_DECODE_SCORES = 1
 PF_DECODE_CTC = 2
 
+# PCM intake (pf_pcm_format, pf_pcm_desc.flags)
+PF_PCM_U8, PF_PCM_S16, PF_PCM_S24, PF_PCM_S32, PF_PCM_F32, PF_PCM_F64, PF_PCM_ALAW, PF_PCM_MULAW = range(1, 9)
+PF_PCM_DOWNMIX_ALWAYS = 1
+# name -> (pf_pcm_format, bytes per value, numpy dtype a caller's array must have; 24-bit values travel as bytes)
+PCM_FORMATS = {"u8": (PF_PCM_U8, 1, "u1"), "s16": (PF_PCM_S16, 2, "<i2"), "s24": (PF_PCM_S24, 3, "u1"),
+               "s32": (PF_PCM_S32, 4, "<i4"), "f32": (PF_PCM_F32, 4, "<f4"), "f64": (PF_PCM_F64, 8, "<f8"),
+               "alaw": (PF_PCM_ALAW, 1, "u1"), "mulaw": (PF_PCM_MULAW, 1, "u1")}
+
+
+class PfPcmDesc(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("format", C.c_int32), ("sample_rate", C.c_int32), ("channels", C.c_int32),
+                ("flags", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+def pcm_desc(sample_rate, channels=1, format="s16", downmix_always=False) -> "PfPcmDesc":
+    fmt = PCM_FORMATS[format][0] if isinstance(format, str) else int(format)
+    return PfPcmDesc(C.sizeof(PfPcmDesc), fmt, int(sample_rate), int(channels), PF_PCM_DOWNMIX_ALWAYS if downmix_always else 0)
+
+
+def pcm_bytes(data, format="s16"):
+    """bytes / bytearray / memoryview, or a numpy array of the format's dtype -> (contiguous uint8 array, n_values)."""
+    import numpy as np
+    _code, bps, dt = PCM_FORMATS[format] if isinstance(format, str) else \
+        next(v for v in PCM_FORMATS.values() if v[0] == int(format))
+    if isinstance(data, np.ndarray):
+        if data.dtype != np.dtype(dt):
+            raise TypeError("PCM format %s takes a numpy array of dtype %s (or bytes), not %s" % (format, np.dtype(dt), data.dtype))
+        raw = np.ascontiguousarray(data).reshape(-1).view(np.uint8)
+    else:
+        raw = np.frombuffer(data, np.uint8)
+    return raw, raw.size // bps
+
 
 class PfEngineConfig(C.Structure):
     _fields_ = [
@@ -91,6 +123,12 @@ SIGNATURES = {
     "pf_model_proj": (C.c_int, [_vp, _P(_f), _i32, C.c_int32, _i32, C.c_int32, _P(PfBatchOut)]),
     "pf_recognize": (C.c_int, [_vp, _P(_f), _i64, C.c_int32, _i32, C.c_int32, _P(PfBatchOut)]),
     "pf_stage_audio": (C.c_int, [_vp, _P(_f), _i64, C.c_int32]),
+    "pf_pcm_num_samples": (C.c_int, [_P(PfPcmDesc), C.c_int32, C.c_int64, _i64]),
+    "pf_stage_pcm": (C.c_int, [_vp, _P(_vp), _i64, _P(PfPcmDesc), C.c_int32, C.c_int32]),
+    "pf_recognize_pcm": (C.c_int, [_vp, _P(_vp), _i64, _P(PfPcmDesc), C.c_int32, C.c_int32, _i32, C.c_int32, _P(PfBatchOut)]),
+    "pf_op_pcm_convert": (C.c_int, [_vp, _vp, C.c_int64, _P(PfPcmDesc), _f, C.c_int64, _i64]),
+    "pf_stream_add_pcm": (C.c_int, [_vp, _vp, C.c_int64, _P(PfPcmDesc)]),
+    "pf_host_wav_info": (C.c_int, [C.c_char_p, _P(PfPcmDesc), _i64, _i64, C.POINTER(C.c_double)]),
     "pf_engine_set_hotwords": (C.c_int, [_vp, C.POINTER(C.c_int32), C.c_int32]),
     "pf_run_staged": (C.c_int, [_vp]),
     "pf_host_wav_read": (C.c_int, [C.c_char_p, _f, C.c_int64, _i64, _i32, _i32, C.POINTER(C.c_double)]),

@@ -235,6 +235,42 @@ int pf_recognize(pf_engine* h, const float* const* samples, const int64_t* n, in
   PF_CATCH
 }
 
+int pf_pcm_num_samples(const pf_pcm_desc* desc, int32_t fs, int64_t n_values, int64_t* n_out) {
+  PF_TRY
+  NEED(desc); NEED(n_out);
+  *n_out = pcm_plan(*desc, fs, n_values).n_out;
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_stage_pcm(pf_engine* h, const void* const* data, const int64_t* n_values, const pf_pcm_desc* descs, int32_t n_descs,
+                 int32_t B) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  NEED(data); NEED(n_values); NEED(descs);
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->stage_pcm(data, n_values, descs, n_descs, B);
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_recognize_pcm(pf_engine* h, const void* const* data, const int64_t* n_values, const pf_pcm_desc* descs, int32_t n_descs,
+                     int32_t B, const int32_t* hotwords, int32_t n_hotwords, pf_batch_out* out) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  NEED(out); NEED(data); NEED(n_values); NEED(descs);
+  std::lock_guard<std::mutex> lk(e->mutex());
+  if (e->model().seaco) e->set_hotwords(hotwords, hotwords ? n_hotwords : 0);
+  e->stage_pcm(data, n_values, descs, n_descs, B);
+  e->run_staged(want_logits(out));
+  e->publish_thread_result();
+  e->fetch(out);
+  return PF_OK;
+  PF_CATCH
+}
+
 int pf_engine_set_hotwords(pf_engine* h, const int32_t* hotwords, int32_t n_hotwords) {
   PF_TRY
   std::shared_ptr<Engine> eh_ = E(h);
@@ -494,6 +530,18 @@ int pf_op_argmax(pf_engine* h, const float* x, int64_t rows, int32_t V, int64_t*
   return PF_OK;
   PF_CATCH
 }
+int pf_op_pcm_convert(pf_engine* h, const void* data, int64_t n_values, const pf_pcm_desc* desc, float* out, int64_t cap,
+                      int64_t* n_out) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  NEED(desc);
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->op_pcm_convert(data, n_values, *desc, out, cap, n_out);
+  return PF_OK;
+  PF_CATCH
+}
+
 int pf_op_ctc_collapse(pf_engine* h, const int64_t* ids, const float* scores, const int32_t* lens, int32_t B, int32_t T,
                        int32_t blank, int64_t* ids_out, int32_t* first_out, int32_t* last_out, float* score_out, int32_t cap,
                        int32_t* n_out) {
@@ -835,6 +883,16 @@ int pf_stream_add_samples(pf_stream* h, const float* samples, int64_t n) {
   Stream* s = S(h);
   PF_CHECK(!s->owner || !s->owner->disposed(), PF_ERR_DISPOSED, "OfflineRecognizer");
   s->AddSamples(samples, n);
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_stream_add_pcm(pf_stream* h, const void* data, int64_t n_values, const pf_pcm_desc* desc) {
+  PF_TRY
+  Stream* s = S(h);
+  NEED(desc);
+  PF_CHECK(!s->owner || !s->owner->disposed(), PF_ERR_DISPOSED, "OfflineRecognizer");
+  s->AddPcm(data, n_values, *desc);
   return PF_OK;
   PF_CATCH
 }
@@ -1397,6 +1455,22 @@ int pf_host_resample(const float* src, int64_t n, int32_t sr_in, int32_t sr_out,
     PF_CHECK(cap >= (int64_t)v.size(), PF_ERR_CAPACITY, "resample: output capacity too small");
     if (!v.empty()) std::memcpy(out, v.data(), v.size() * 4);
   }
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_host_wav_info(const char* path, pf_pcm_desc* desc, int64_t* data_offset, int64_t* data_bytes, double* duration_ms) {
+  PF_TRY
+  NEED(path);
+  const WavInfo w = wav_info_file(path);
+  if (desc) {
+    std::memset(desc, 0, sizeof(*desc));
+    desc->struct_size = (int32_t)sizeof(*desc);
+    desc->format = w.format; desc->sample_rate = w.sample_rate; desc->channels = w.channels;
+  }
+  if (data_offset) *data_offset = (int64_t)w.data_offset;
+  if (data_bytes) *data_bytes = (int64_t)w.data_bytes;
+  if (duration_ms) *duration_ms = w.duration_ms;
   return PF_OK;
   PF_CATCH
 }

@@ -120,7 +120,7 @@ void Engine::release() {
   if (fb_) { fbank_tables_destroy(fb_); fb_ = nullptr; }
   for (void* p : owned_) hipFree(p);
   owned_.clear();
-  DevBuf* bufs[] = {&ws_f32_, &ws_audio_, &ws_meta_, &ws_fbank_, &ws_speech_, &ws_enc_, &ws_dec_, &ws_kv_, &ws_pe_, &ws_tmp_,
+  DevBuf* bufs[] = {&ws_f32_, &ws_pcm_, &ws_audio_, &ws_meta_, &ws_fbank_, &ws_speech_, &ws_enc_, &ws_dec_, &ws_kv_, &ws_pe_, &ws_tmp_,
                     &ws_ts_, &ws_seaco_, &ws_seaco_in_, &ws_seaco_hw_, &ws_q_, &ws_qf_, &ws_seaco_q_, &ws_x3a_, &ws_x3t_, &ws_x3h_};
   x3_pair_live_ = false; x3a_src_ = nullptr; x3a_pair_only_ = false;
   x3w_.clear();
@@ -889,6 +889,56 @@ void Engine::stage_audio(const float* const* samples, const int64_t* n, int B, i
   for (int b = 0; b < B; ++b)
     if (n[b] > 0)
       PF_HIP(hipMemcpyAsync((float*)ws_audio_.p + meta[b], samples[b], n[b] * 4, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipMemcpyAsync(ws_meta_.p, meta.data(), meta.size() * 8, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipMemcpyAsync((char*)ws_meta_.p + meta.size() * 8, st_t80_.data(), (size_t)B * 4, hipMemcpyHostToDevice,
+                        stream_));
+  PF_HIP(hipStreamSynchronize(stream_));
+}
+
+void Engine::stage_pcm(const void* const* data, const int64_t* n_values, const pf_pcm_desc* descs, int n_descs, int B, int force_T) {
+  PF_CHECK(B >= 0, PF_ERR_INVALID_ARG, "negative batch");
+  PF_CHECK(n_descs == B || n_descs == 1, PF_ERR_INVALID_ARG, "stage_pcm: n_descs must be 1 or B");
+  PF_HIP(hipSetDevice(device_));
+  st_audio_ext_ = nullptr;
+  st_B_ = B;
+  st_n_.resize(B);
+  st_t80_.resize(B);
+  std::vector<int64_t> meta(3 * (size_t)(B + 1), 0);   // audio_off | n_samples | frame_off
+  std::vector<PcmJob> jobs((size_t)B);
+  std::vector<size_t> raw_bytes((size_t)B);
+  int64_t tot = 0, frames = 0, raw_tot = 0, max_out = 0;
+  int tmax = 0;
+  for (int b = 0; b < B; ++b) {
+    const pf_pcm_desc& d = descs[n_descs == 1 ? 0 : b];
+    const PcmPlan p = pcm_plan(d, fc_.fs, n_values[b]);
+    PF_CHECK(data[b] || n_values[b] == 0, PF_ERR_INVALID_ARG, "pcm: null data");
+    raw_bytes[b] = (size_t)n_values[b] * p.bytes_per_value;
+    jobs[b] = PcmJob{raw_tot, tot, p.n_mono, p.n_out, p.ratio, d.format, p.downmix ? 1 : 0, p.resample ? 1 : 0, 0};
+    st_n_[b] = p.n_out;
+    meta[b] = tot;
+    meta[(B + 1) + b] = p.n_out;
+    meta[2 * (B + 1) + b] = frames;
+    st_t80_[b] = num_fbank_frames(p.n_out);
+    tot += round_up(p.n_out, 4);
+    raw_tot += round_up((int64_t)raw_bytes[b], 16);
+    frames += st_t80_[b];
+    tmax = std::max(tmax, num_lfr_frames(p.n_out));
+    max_out = std::max(max_out, p.n_out);
+  }
+  meta[2 * (B + 1) + B] = frames;
+  st_total_frames_ = frames;
+  st_T_ = std::max(tmax, force_T);
+  const size_t jobs_off = (size_t)round_up(std::max<int64_t>(raw_tot, 16), 256);
+  ensure(ws_pcm_, jobs_off + std::max<size_t>(jobs.size(), 1) * sizeof(PcmJob));
+  ensure(ws_audio_, (size_t)std::max<int64_t>(tot, 1) * 4);
+  ensure(ws_meta_, meta.size() * 8 + (size_t)B * 4 + 64);
+  for (int b = 0; b < B; ++b)
+    if (raw_bytes[b] > 0)
+      PF_HIP(hipMemcpyAsync((char*)ws_pcm_.p + jobs[b].in_off, data[b], raw_bytes[b], hipMemcpyHostToDevice, stream_));
+  if (B > 0) PF_HIP(hipMemcpyAsync((char*)ws_pcm_.p + jobs_off, jobs.data(), jobs.size() * sizeof(PcmJob), hipMemcpyHostToDevice, stream_));
+  prof_begin("pcm_to_samples", 0);
+  launch_pcm_to_samples(stream_, (const PcmJob*)((char*)ws_pcm_.p + jobs_off), B, max_out, ws_pcm_.p, (float*)ws_audio_.p);
+  prof_end("pcm_to_samples");
   PF_HIP(hipMemcpyAsync(ws_meta_.p, meta.data(), meta.size() * 8, hipMemcpyHostToDevice, stream_));
   PF_HIP(hipMemcpyAsync((char*)ws_meta_.p + meta.size() * 8, st_t80_.data(), (size_t)B * 4, hipMemcpyHostToDevice,
                         stream_));

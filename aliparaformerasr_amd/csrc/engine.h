@@ -99,6 +99,10 @@ class Engine {
   void model_proj_host(const float* const* speech, const int32_t* n_floats, int B, bool want_logits);
   // force_T > 0: pad to at least force_T LFR frames (a shard of a larger batch pads to the GLOBAL maximum, PadHelper.cs:25)
   void stage_audio(const float* const* samples, const int64_t* n, int B, int force_T = 0);
+  // stage_audio for raw PCM (paraformer_hip.h "PCM intake"): the raw bytes are uploaded and pcm_to_samples_kernel (k_pcm.hip)
+  // writes the float samples into the layout stage_audio fills — everything behind it (frame counts, force_T, decode
+  // lengths, the dither's per-sample counters) follows from the per-utterance n_out.  descs: n_descs == B, or 1 for all
+  void stage_pcm(const void* const* data, const int64_t* n_values, const pf_pcm_desc* descs, int n_descs, int B, int force_T = 0);
   void run_staged(bool want_logits);
   void fetch(pf_batch_out* out);
   void fetch_ids_device(int64_t* ids_dev, int l_cap, int32_t* L_out);   // last forward's ids -> caller's device buffer [B, l_cap], -1 padded
@@ -126,6 +130,7 @@ class Engine {
   int decode_flags() const { return decode_flags_; }
   void fetch_scores(float* scores, int64_t cap, int32_t* L_out);
   void fetch_ctc(int64_t* ids, int32_t* first, int32_t* last, float* score, int32_t cap, int32_t* n, int32_t* n_max);
+  void op_pcm_convert(const void* data, int64_t n_values, const pf_pcm_desc& desc, float* out, int64_t cap, int64_t* n_out);
   void op_ctc_collapse(const int64_t* ids, const float* scores, const int32_t* lens, int B, int T, int blank, int64_t* ids_out,
                        int32_t* first_out, int32_t* last_out, float* score_out, int cap, int32_t* n_out);
   // ---- streaming seams (OnlineRecognizer.cs EncoderProj / DecoderProj) ------
@@ -349,6 +354,7 @@ class Engine {
   float* small_ws_ = nullptr;        // short-input GEMM: split partials
   float* cif_conv_w32_ = nullptr;    // fp32 mode: the CIF conv as a [D][taps*D] GEMM operand
   float* ts_up_w32_ = nullptr;       // fp32 mode: the transposed conv as a [(j, out)][in] GEMM operand
+  DevBuf ws_pcm_;                   // stage_pcm: the raw bytes of the batch | its PcmJob table
   DevBuf ws_audio_, ws_meta_, ws_fbank_, ws_speech_, ws_enc_, ws_dec_, ws_decffn_, ws_kv_, ws_pe_, ws_tmp_, ws_ts_, ws_seaco_, ws_seaco_in_, ws_seaco_hw_;
   bool seaco_hw_valid_ = false;     // ws_seaco_hw_ holds the embedder output / K,V rows of the CURRENT hot-word list (f16 path)
   int pe_T_ = 0;

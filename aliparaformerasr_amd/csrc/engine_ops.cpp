@@ -54,6 +54,20 @@ void Engine::op_argmax(const float* x, int64_t rows, int V, int64_t* ids) {
   PF_HIP(hipStreamSynchronize(stream_));
 }
 
+void Engine::op_pcm_convert(const void* data, int64_t n_values, const pf_pcm_desc& desc, float* out, int64_t cap, int64_t* n_out) {
+  const PcmPlan p = pcm_plan(desc, fc_.fs, n_values);
+  PF_CHECK(data || n_values == 0, PF_ERR_INVALID_ARG, "pcm: null data");
+  if (n_out) *n_out = p.n_out;
+  if (!out) return;
+  PF_CHECK(cap >= p.n_out, PF_ERR_CAPACITY, "pcm_convert: out capacity < " + std::to_string(p.n_out));
+  const void* arr[1] = {data};
+  const int64_t nn[1] = {n_values};
+  stage_pcm(arr, nn, &desc, 1, 1);                       // upload + the pipeline's launch, into the staged-sample layout
+  if (p.n_out == 0) return;
+  PF_HIP(hipMemcpyAsync(out, ws_audio_.p, (size_t)p.n_out * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipStreamSynchronize(stream_));
+}
+
 void Engine::op_ctc_collapse(const int64_t* ids, const float* scores, const int32_t* lens, int B, int T, int blank,
                              int64_t* ids_out, int32_t* first_out, int32_t* last_out, float* score_out, int cap, int32_t* n_out) {
   PF_HIP(hipSetDevice(device_));

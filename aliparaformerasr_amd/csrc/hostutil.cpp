@@ -264,61 +264,149 @@ bool is_wav_header(const std::string& path) {
 static uint32_t rd32(const char* p) { uint32_t v; std::memcpy(&v, p, 4); return v; }
 static uint16_t rd16(const char* p) { uint16_t v; std::memcpy(&v, p, 2); return v; }
 
-WavData decode_wav_file(const std::string& path) {
-  std::vector<char> b;
-  read_binary_file(path, b);
-  PF_CHECK(b.size() >= 12 && std::memcmp(b.data(), "RIFF", 4) == 0 && std::memcmp(b.data() + 8, "WAVE", 4) == 0,
+// The RIFF chunk walk (fmt + data) shared by decode_wav_file and pf_host_wav_info.  `b` holds the first `have` bytes of a file of
+// `size` bytes: sizes are judged against the file, bytes are read from the prefix; *need_more is set (and nothing else is valid)
+// when the walk wants a byte beyond the prefix
+static WavInfo wav_info_prefix(const char* b, size_t have, size_t size, const std::string& path, bool* need_more) {
+  *need_more = false;
+  PF_CHECK(size >= 12 && have >= 12 && std::memcmp(b, "RIFF", 4) == 0 && std::memcmp(b + 8, "WAVE", 4) == 0,
            PF_ERR_FORMAT, "not a RIFF/WAVE file: " + path);
   size_t pos = 12;
   int fmt_tag = 0, bits = 0, block_align = 0;
-  WavData w;
-  const char* data = nullptr;
-  size_t data_bytes = 0;
-  while (pos + 8 <= b.size()) {
-    const uint32_t sz = rd32(b.data() + pos + 4);
-    const char* body = b.data() + pos + 8;
-    const size_t avail = b.size() - (pos + 8);
-    if (std::memcmp(b.data() + pos, "fmt ", 4) == 0 && sz >= 16 && avail >= 16) {
+  WavInfo w;
+  bool have_data = false;
+  while (pos + 8 <= size) {
+    if (pos + 8 > have) { *need_more = true; return w; }
+    const uint32_t sz = rd32(b + pos + 4);
+    const char* body = b + pos + 8;
+    const size_t avail = size - (pos + 8);
+    if (std::memcmp(b + pos, "fmt ", 4) == 0 && sz >= 16 && avail >= 16) {
+      if (pos + 8 + std::min<size_t>(avail, 26) > have) { *need_more = true; return w; }
       fmt_tag = rd16(body); w.channels = rd16(body + 2); w.sample_rate = (int)rd32(body + 4);
       block_align = rd16(body + 12); bits = rd16(body + 14);
       if (fmt_tag == 0xFFFE && sz >= 26 && avail >= 26) fmt_tag = rd16(body + 24);   // WAVE_FORMAT_EXTENSIBLE sub-format
-    } else if (std::memcmp(b.data() + pos, "data", 4) == 0) {
-      data = body; data_bytes = std::min<size_t>(sz, avail);
+    } else if (std::memcmp(b + pos, "data", 4) == 0) {
+      have_data = true; w.data_offset = pos + 8; w.data_bytes = std::min<size_t>(sz, avail);
       break;
     }
     pos += 8 + (size_t)sz + (sz & 1);
   }
-  PF_CHECK(data && w.channels > 0 && w.sample_rate > 0 && block_align > 0, PF_ERR_FORMAT, "wav: missing fmt/data chunk: " + path);
-  const int bps = bits / 8;
+  PF_CHECK(have_data && w.channels > 0 && w.sample_rate > 0 && block_align > 0, PF_ERR_FORMAT, "wav: missing fmt/data chunk: " + path);
   // PCM 8 / 16 / 24 / 32, IEEE float 32 / 64, G.711 A-law (6) and mu-law (7): what NAudio's AudioFileReader turns into float samples
   // for a RIFF/WAVE file (the G.711 forms through a codec that expands them to 16-bit PCM first)
-  PF_CHECK((fmt_tag == 1 && (bits == 8 || bits == 16 || bits == 24 || bits == 32)) || (fmt_tag == 3 && (bits == 32 || bits == 64)) ||
-               ((fmt_tag == 6 || fmt_tag == 7) && bits == 8),
-           PF_ERR_UNSUPPORTED, "wav: unsupported sample format");
-  const size_t n = data_bytes / bps;
-  w.samples.resize(n);
+  if (fmt_tag == 1 && bits == 8) w.format = PF_PCM_U8;
+  else if (fmt_tag == 1 && bits == 16) w.format = PF_PCM_S16;
+  else if (fmt_tag == 1 && bits == 24) w.format = PF_PCM_S24;
+  else if (fmt_tag == 1 && bits == 32) w.format = PF_PCM_S32;
+  else if (fmt_tag == 3 && bits == 32) w.format = PF_PCM_F32;
+  else if (fmt_tag == 3 && bits == 64) w.format = PF_PCM_F64;
+  else if (fmt_tag == 6 && bits == 8) w.format = PF_PCM_ALAW;
+  else if (fmt_tag == 7 && bits == 8) w.format = PF_PCM_MULAW;
+  else throw Error(PF_ERR_UNSUPPORTED, "wav: unsupported sample format");
+  w.duration_ms = (double)(w.data_bytes / block_align) * 1000.0 / w.sample_rate;
+  return w;
+}
+
+WavInfo wav_info(const std::vector<char>& b, const std::string& path) {
+  bool more = false;
+  return wav_info_prefix(b.data(), b.size(), b.size(), path, &more);
+}
+
+// the same from the file, reading the header region only: 64 KiB first, the whole file when a chunk in front of `data` is longer
+WavInfo wav_info_file(const std::string& path) {
+  std::ifstream f(path, std::ios::binary);
+  PF_CHECK((bool)f, PF_ERR_IO, "cannot open file: " + path);
+  f.seekg(0, std::ios::end);
+  const size_t size = (size_t)std::max<std::streamoff>(f.tellg(), 0);
+  std::vector<char> b(std::min<size_t>(size, (size_t)64 << 10));
+  f.seekg(0);
+  if (!b.empty()) f.read(b.data(), (std::streamsize)b.size());
+  PF_CHECK(b.empty() || (size_t)f.gcount() == b.size(), PF_ERR_IO, "cannot read file: " + path);
+  bool more = false;
+  WavInfo w = wav_info_prefix(b.data(), b.size(), size, path, &more);
+  if (!more) return w;
+  read_binary_file(path, b);
+  return wav_info(b, path);
+}
+
+int pcm_bytes_per_value(int format) {
+  switch (format) {
+    case PF_PCM_U8: case PF_PCM_ALAW: case PF_PCM_MULAW: return 1;
+    case PF_PCM_S16: return 2;
+    case PF_PCM_S24: return 3;
+    case PF_PCM_S32: case PF_PCM_F32: return 4;
+    case PF_PCM_F64: return 8;
+  }
+  throw Error(PF_ERR_INVALID_ARG, "pcm: unknown format " + std::to_string(format));
+}
+
+void pcm_decode(const void* data, size_t n, int format, float* out) {
+  const int bps = pcm_bytes_per_value(format);
   const unsigned char* d = (const unsigned char*)data;
   for (size_t i = 0; i < n; ++i) {
     const unsigned char* q = d + i * bps;
     float v;
-    if (fmt_tag == 7) {                                  // ITU-T G.711 mu-law: ~byte = sign | exponent (3) | mantissa (4)
+    if (format == PF_PCM_MULAW) {                        // ITU-T G.711 mu-law: ~byte = sign | exponent (3) | mantissa (4)
       const int u = (~q[0]) & 0xFF;
       const int mag = ((((u & 0x0F) << 3) + 0x84) << ((u >> 4) & 7)) - 0x84;
       v = (float)((u & 0x80) ? -mag : mag) / 32768.0f;
-    } else if (fmt_tag == 6) {                           // A-law: byte ^ 0x55, sign bit set = positive
+    } else if (format == PF_PCM_ALAW) {                  // A-law: byte ^ 0x55, sign bit set = positive
       const int a = q[0] ^ 0x55, e = (a >> 4) & 7, m = a & 0x0F;
       const int mag = e == 0 ? (m << 4) + 8 : ((m << 4) + 0x108) << (e - 1);
       v = (float)((a & 0x80) ? mag : -mag) / 32768.0f;
-    } else if (fmt_tag == 3 && bits == 64) { double d; std::memcpy(&d, q, 8); v = (float)d; }
-    else if (fmt_tag == 3) { std::memcpy(&v, q, 4); }
-    else if (bits == 16) { int16_t x; std::memcpy(&x, q, 2); v = x / 32768.0f; }
-    else if (bits == 24) { int32_t x = (int32_t)((uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)(int8_t)q[2] << 16)); v = x / 8388608.0f; }
-    else if (bits == 32) { int32_t x; std::memcpy(&x, q, 4); v = x / 2147483648.0f; }
+    } else if (format == PF_PCM_F64) { double d; std::memcpy(&d, q, 8); v = (float)d; }
+    else if (format == PF_PCM_F32) { std::memcpy(&v, q, 4); }
+    else if (format == PF_PCM_S16) { int16_t x; std::memcpy(&x, q, 2); v = x / 32768.0f; }
+    else if (format == PF_PCM_S24) { int32_t x = (int32_t)((uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)(int8_t)q[2] << 16)); v = x / 8388608.0f; }
+    else if (format == PF_PCM_S32) { int32_t x; std::memcpy(&x, q, 4); v = x / 2147483648.0f; }
     else { v = q[0] / 128.0f - 1.0f; }
-    w.samples[i] = v;
+    out[i] = v;
   }
-  w.duration_ms = (double)(data_bytes / block_align) * 1000.0 / w.sample_rate;
+}
+
+WavData decode_wav_file(const std::string& path) {
+  std::vector<char> b;
+  read_binary_file(path, b);
+  const WavInfo wi = wav_info(b, path);
+  WavData w;
+  w.sample_rate = wi.sample_rate; w.channels = wi.channels; w.duration_ms = wi.duration_ms;
+  const size_t n = wi.data_bytes / pcm_bytes_per_value(wi.format);
+  w.samples.resize(n);
+  pcm_decode(b.data() + wi.data_offset, n, wi.format, w.samples.data());
   return w;
+}
+
+PcmPlan pcm_plan(const pf_pcm_desc& d, int fs, int64_t n_values) {
+  PF_CHECK(d.struct_size == (int32_t)sizeof(pf_pcm_desc), PF_ERR_INVALID_ARG, "pf_pcm_desc.struct_size mismatch");
+  PF_CHECK(d.channels == 1 || d.channels == 2, PF_ERR_INVALID_ARG, "pcm: only 1 or 2 channels");
+  PF_CHECK(d.sample_rate > 0 && fs > 0, PF_ERR_INVALID_ARG, "pcm: sample rates must be positive");
+  PF_CHECK(n_values >= 0 && n_values <= INT32_MAX, PF_ERR_INVALID_ARG, "pcm: value count must be in [0, 2^31 - 1]");
+  PcmPlan p;
+  p.bytes_per_value = pcm_bytes_per_value(d.format);
+  p.resample = d.sample_rate != fs;                                     // GetFileSample: resampled (and down-mixed) only then
+  p.downmix = d.channels == 2 && (p.resample || (d.flags & PF_PCM_DOWNMIX_ALWAYS));
+  p.n_mono = p.downmix ? n_values / 2 : n_values;
+  p.ratio = (double)d.sample_rate / fs;
+  p.n_out = p.n_mono;
+  if (p.resample) {
+    const double r = n_values == 0 ? 0.0 : std::nearbyint((double)p.n_mono / p.ratio);   // Math.Round: half to even
+    PF_CHECK(r <= (double)INT32_MAX, PF_ERR_INVALID_ARG, "pcm: resampled length exceeds 2^31 - 1");
+    p.n_out = std::max((int64_t)r, (int64_t)0);
+  }
+  return p;
+}
+
+std::vector<float> pcm_to_samples(const void* data, int64_t n_values, const pf_pcm_desc& d, int fs) {
+  const PcmPlan p = pcm_plan(d, fs, n_values);
+  std::vector<float> x((size_t)n_values);
+  pcm_decode(data, (size_t)n_values, d.format, x.data());
+  if (p.resample) return resample_linear(x, d.sample_rate, fs, d.channels);
+  if (p.downmix) {
+    std::vector<float> m((size_t)p.n_mono);
+    for (size_t i = 0; i < m.size(); ++i) m[i] = (x[2 * i] + x[2 * i + 1]) * 0.5f;
+    return m;
+  }
+  return x;
 }
 
 std::vector<float> resample_linear(const std::vector<float>& src, int sr_in, int sr_out, int channels) {

@@ -45,6 +45,18 @@ bool is_wav_header(const std::string& path);
 // samples, PCM8 -> b/128-1, PCM16 -> /32768, PCM24 -> /8388608, PCM32 -> /2147483648, float32 as is.
 struct WavData { std::vector<float> samples; int sample_rate = 0, channels = 0; double duration_ms = 0; };
 WavData decode_wav_file(const std::string& path);
+// decode_wav_file's header walk without the sample loop (pf_host_wav_info): format = pf_pcm_format, the payload's place in the file
+struct WavInfo { int format = 0, sample_rate = 0, channels = 0; size_t data_offset = 0, data_bytes = 0; double duration_ms = 0; };
+WavInfo wav_info(const std::vector<char>& file, const std::string& path);
+WavInfo wav_info_file(const std::string& path);                 // the same, reading only the header region of the file
+// the sample loop on memory: n values of `format` (pf_pcm_format) -> float
+int pcm_bytes_per_value(int format);                           // throws PF_ERR_INVALID_ARG for an unknown format
+void pcm_decode(const void* data, size_t n_values, int format, float* out);
+// PCM intake (paraformer_hip.h "PCM intake"): what GetFileSample does to n_values interleaved values of `d` for an engine at
+// rate fs — validated (PF_ERR_INVALID_ARG) and sized here, carried out by pcm_to_samples on the host or k_pcm.hip on the device
+struct PcmPlan { bool resample = false, downmix = false; int bytes_per_value = 0; int64_t n_mono = 0, n_out = 0; double ratio = 1.0; };
+PcmPlan pcm_plan(const pf_pcm_desc& d, int fs, int64_t n_values);
+std::vector<float> pcm_to_samples(const void* data, int64_t n_values, const pf_pcm_desc& d, int fs);
 // Resample(sourceData, sourceSampleRate, targetSampleRate, sourceChannels) (:223-279): stereo -> mono
 // average first, then linear interpolation in double precision; target length = Round(n / ratio) (banker's)
 std::vector<float> resample_linear(const std::vector<float>& src, int sr_in, int sr_out, int channels);

@@ -351,4 +351,13 @@ void launch_argmax(hipStream_t s, float* x, int64_t rows, int V, int ldx, int mo
 void launch_ctc_collapse(hipStream_t s, const int64_t* ids, const float* score, const int32_t* len, int B, int T, int blank,
                          int cap, int32_t* n_out, int64_t* ids_out, int32_t* first_out, int32_t* last_out, float* score_out);
 
+// ---------------------------------------------------------------- PCM intake (k_pcm.hip) ------
+// One utterance of a pcm_to_samples launch: n raw values of `format` (pf_pcm_format) at raw + in_off (bytes, 16-byte aligned)
+// -> n_out float samples at samples + out_off (floats, a multiple of 4).  n_mono = values after the optional down-mix;
+// resample: out[i] interpolates the mono sequence at i * ratio (hostutil.h PcmPlan).
+struct PcmJob { int64_t in_off, out_off, n_mono, n_out; double ratio; int32_t format, downmix, resample, reserved; };
+void launch_pcm_to_samples(hipStream_t s, const PcmJob* jobs_dev, int B, int64_t max_n_out, const void* raw, float* samples);
+// the same kernel for ONE utterance, its job passed in the kernel arguments (no table in device memory)
+void launch_pcm_to_samples_one(hipStream_t s, const PcmJob& job, const void* raw, float* samples);
+
 }  // namespace pf

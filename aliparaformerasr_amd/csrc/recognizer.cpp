@@ -281,6 +281,10 @@ static int conf_lfr_frames(const ConfEntity& c, int64_t n) {
 
 void Stream::wait_device_audio() {
   if (dev_ev_pending) { hipEventSynchronize(dev_ev); dev_ev_pending = false; }
+  if (dev_raw) {                                        // AddPcm's kernel has read it
+    if (owner) owner->audio_free(dev_raw, dev_raw_bytes);
+    dev_raw = nullptr; dev_raw_bytes = 0;
+  }
 }
 
 void Stream::drop_device_audio() {
@@ -350,6 +354,50 @@ void Stream::AddSamples(const float* samples, int64_t n) {
   Speech.insert(Speech.end(), feats.begin(), feats.end());
   has_speech = true;
   SpeechLength = (int)Speech.size();
+}
+
+void Stream::AddPcm(const void* data, int64_t n_values, const pf_pcm_desc& d) {
+  if (disposed) throw Error(PF_ERR_DISPOSED, "OfflineStream");
+  PF_CHECK(data || n_values <= 0, PF_ERR_INVALID_ARG, "pcm: null data");
+  if (!data) throw Error(PF_ERR_NULL_SAMPLES, "source");
+  const int fs = owner ? owner->conf_.fs : uconf.fs;
+  const PcmPlan p = pcm_plan(d, fs, n_values);
+  if (owner && owner->disposed()) throw Error(PF_ERR_DISPOSED, "OfflineRecognizer");
+  if (owner && !has_speech && !device_form && owner->device_streams()) {
+    // device form: as AddSamples' first call, with the conversion as one launch behind the upload
+    size_t got = 0, got_raw = 0;
+    float* ds = nullptr; float* raw = nullptr;
+    bool on_device = true;
+    try {
+      if (p.n_out > 0) {
+        const size_t rb = (size_t)n_values * p.bytes_per_value;
+        ds = owner->audio_alloc((size_t)p.n_out * 4, &got);
+        raw = owner->audio_alloc(rb, &got_raw);
+        const PcmJob job{0, 0, p.n_mono, p.n_out, p.ratio, d.format, p.downmix ? 1 : 0, p.resample ? 1 : 0, 0};
+        const std::function<void(hipStream_t)> convert = [&](hipStream_t st) { launch_pcm_to_samples_one(st, job, raw, ds); };
+        owner->upload(raw, (const float*)data, rb, &dev_ev, &dev_ev_pending, &convert);
+      }
+    } catch (const Error& ex) {
+      (void)hipGetLastError();                                      // clear the sticky out-of-memory status
+      if (ds || raw) (void)hipDeviceSynchronize();                  // (pieces of a staged upload may be in flight)
+      if (ds) owner->audio_free(ds, got);
+      if (raw) owner->audio_free(raw, got_raw);
+      dev_ev_pending = false;
+      if (ex.code == PF_ERR_DISPOSED) throw;
+      on_device = false;
+    }
+    if (on_device) {
+      dev_audio = ds; dev_bytes = got; dev_n = p.n_out;
+      dev_raw = raw; dev_raw_bytes = got_raw;
+      device_form = true;
+      has_speech = true;
+      SpeechLength = owner->feature_floats(p.n_out);
+      return;
+    }
+  }
+  static const float kNone = 0.f;
+  const std::vector<float> x = pcm_to_samples(data, n_values, d, fs);
+  AddSamples(x.empty() ? &kNone : x.data(), (int64_t)x.size());
 }
 
 void Stream::Dispose() {
@@ -610,7 +658,8 @@ bool Recognizer::seen_before(const void* p, size_t bytes) {
   return false;
 }
 
-void Recognizer::upload(float* dst, const float* src, size_t bytes, hipEvent_t* ev, bool* pending) {
+void Recognizer::upload(float* dst, const float* src, size_t bytes, hipEvent_t* ev, bool* pending,
+                        const std::function<void(hipStream_t)>* after) {
   UpTimer whole(g_up_ns);
   if (kUpTiming && (++g_up_calls % 256) == 0)
     fprintf(stderr, "[upload] %lld calls: %.1f us per call, host copy %.1f, ring waits %.1f\n", (long long)g_up_calls, g_up_ns / 1e3 / g_up_calls,
@@ -639,6 +688,12 @@ void Recognizer::upload(float* dst, const float* src, size_t bytes, hipEvent_t* 
   if (!staged || !ln.pin) {
     PF_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ln.s));
     PF_HIP(hipStreamSynchronize(ln.s));                // the samples are on the device when AddSamples returns
+    if (after && ev) {
+      (*after)(ln.s);
+      if (!*ev) PF_HIP(hipEventCreateWithFlags(ev, hipEventDisableTiming));
+      PF_HIP(hipEventRecord(*ev, ln.s));
+      *pending = true;
+    }
     return;
   }
   if (!ln.sp) {
@@ -686,6 +741,7 @@ void Recognizer::upload(float* dst, const float* src, size_t bytes, hipEvent_t* 
     ln.head = off + nb;
     done += nb;
   }
+  if (after) (*after)(ln.sp);
   if (!*ev) PF_HIP(hipEventCreateWithFlags(ev, hipEventDisableTiming));
   PF_HIP(hipEventRecord(*ev, ln.sp));
   *pending = true;
@@ -901,6 +957,8 @@ void Recognizer::Forward(const std::vector<Stream*>& streams) {
     std::memset(&out, 0, sizeof(out));
     out.struct_size = sizeof(out);
     e->fetch(&out);                       // sync; learn L
+    for (Stream* s : streams)
+      if (s->dev_raw) s->wait_device_audio();   // AddPcm streams: the conversion has run, the raw bytes go back to the cache
     if (timed_step) note_step(t_step);
     fc.lap(4);
     const int L = out.L;

@@ -7,6 +7,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <deque>
+#include <functional>
 #include <initializer_list>
 #include <map>
 #include <array>
@@ -107,6 +108,11 @@ class Stream {
   ConfEntity uconf; std::vector<float> ushift, uscale;        // unbound form only
   std::vector<std::vector<float>> pending;                    // AddSamples calls not yet replayed
   void AddSamples(const float* samples, int64_t n);          // OfflineStream.cs:36-57
+  // AddSamples for raw PCM (paraformer_hip.h "PCM intake").  First call on an owned stream: the raw bytes go through the copy
+  // lane, pcm_to_samples_kernel runs on the lane's stream behind the last DMA piece and dev_ev is recorded behind the kernel —
+  // dev_audio / dev_n then hold what AddSamples of the converted floats would have left.  Every other case converts on the
+  // host (pcm_to_samples, the same arithmetic) and continues through AddSamples.
+  void AddPcm(const void* data, int64_t n_values, const pf_pcm_desc& d);
   void Dispose();                                             // OfflineStream.cs:81-121: drops the buffers
   std::vector<float> Speech;                                  // OfflineInputEntity.Speech (host form)
   bool has_speech = false;                                    // Speech != null
@@ -115,6 +121,7 @@ class Stream {
   bool device_form = false;
   float* dev_audio = nullptr; size_t dev_bytes = 0; int64_t dev_n = 0;
   hipEvent_t dev_ev = nullptr; bool dev_ev_pending = false;   // recorded behind the last DMA piece of dev_audio (staged uploads)
+  float* dev_raw = nullptr; size_t dev_raw_bytes = 0;         // AddPcm: the raw bytes the kernel behind dev_ev reads; back to the cache once it has completed
   void wait_device_audio();                                   // host-side wait for that event
   void materialize();                                         // device form -> host form (features computed and read back)
   void drop_device_audio();
@@ -175,7 +182,9 @@ class Recognizer : public std::enable_shared_from_this<Recognizer> {
   void audio_free(float* p, size_t bytes);
   // host -> device on a copy lane.  Returns when `src` may be reused; with `ev` (staged form) the bytes are on the device when
   // *ev has completed and *pending is set — without staging the call is synchronous and *pending stays false
-  void upload(float* dst, const float* src, size_t bytes, hipEvent_t* ev = nullptr, bool* pending = nullptr);
+  // `after` (AddPcm): launches that follow the bytes on the lane's stream, in front of *ev (which is then recorded on both paths)
+  void upload(float* dst, const float* src, size_t bytes, hipEvent_t* ev = nullptr, bool* pending = nullptr,
+              const std::function<void(hipStream_t)>* after = nullptr);
   int device() const { return device_; }
   bool device_streams() const { return device_streams_; }     // new streams keep their first AddSamples call's audio on the device
   int feature_floats(int64_t n_samples);                      // what GetFbank + LfrCmvn return for n samples (float count)

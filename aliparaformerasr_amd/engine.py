@@ -215,6 +215,53 @@ class Engine:
                                              io.ctypes.data_as(i64), _i32p(fo), _i32p(lo), _fp(so), cap, _i32p(n)))
         return CtcResult(n, io, fo, lo, so)
 
+    # ---- PCM intake: raw interleaved values in, converted on the device (include/paraformer_hip.h "PCM intake") ----
+    @staticmethod
+    def _pcm_args(pcm_list, descs):
+        """pcm_list: per utterance bytes or a numpy array of the format's dtype; descs: one _native.PfPcmDesc for all, or a
+        list of B.  -> (data pointers, value counts, desc array, n_descs, B, keep-alive)"""
+        B = len(pcm_list)
+        dl = [descs] if isinstance(descs, N.PfPcmDesc) else list(descs)
+        assert len(dl) in (1, B), "one desc, or one per utterance"
+        raws = [N.pcm_bytes(x, dl[0 if len(dl) == 1 else b].format) for b, x in enumerate(pcm_list)]
+        ptrs = (C.c_void_p * max(B, 1))(*[r.ctypes.data if r.size else None for r, _n in raws])
+        ns = (C.c_int64 * max(B, 1))(*[n for _r, n in raws])
+        da = (N.PfPcmDesc * len(dl))(*dl)
+        return ptrs, ns, da, len(dl), B, raws
+
+    def pcm_num_samples(self, desc, n_values: int, fs: int = 16000) -> int:
+        n = C.c_int64()
+        N.check(self._lib.pf_pcm_num_samples(C.byref(desc), fs, n_values, C.byref(n)))
+        return n.value
+
+    def op_pcm_convert(self, data, desc) -> np.ndarray:
+        """The pipeline's PCM intake kernel on caller data -> the float32 samples it hands to the fbank."""
+        raw, n = N.pcm_bytes(data, desc.format)
+        n_out = C.c_int64()
+        N.check(self._lib.pf_op_pcm_convert(self._h, None if raw.size == 0 else raw.ctypes.data, n, C.byref(desc), None, 0, C.byref(n_out)))
+        out = np.zeros(max(n_out.value, 1), np.float32)
+        N.check(self._lib.pf_op_pcm_convert(self._h, raw.ctypes.data if raw.size else out.ctypes.data, n, C.byref(desc), _fp(out),
+                                            out.size, C.byref(n_out)))
+        return out[: n_out.value]
+
+    def stage_pcm(self, pcm_list, descs):
+        ptrs, ns, da, nd, B, _keep = self._pcm_args(pcm_list, descs)
+        N.check(self._lib.pf_stage_pcm(self._h, ptrs, ns, da, nd, B))
+        self._staged_B = B
+
+    def recognize_pcm(self, pcm_list, descs, want_logits=False, hotwords=None) -> BatchResult:
+        hp, hn, _keep_hw = self._hw(hotwords)
+        ptrs, ns, da, nd, B, _keep = self._pcm_args(pcm_list, descs)
+        dummy = np.zeros(1, np.float32)
+
+        def call(out):
+            if want_logits:
+                out.logits = _fp(dummy)
+                out.logits_cap = 1
+            rc = self._lib.pf_recognize_pcm(self._h, ptrs, ns, da, nd, B, hp, hn, C.byref(out))
+            return 0 if (want_logits and rc == N.PF_ERR_CAPACITY) else rc
+        return self._collect(call, B, want_logits)
+
     @staticmethod
     def _hw(hotwords):
         """SeACo hotword ids [N,10] int32 (PadList output) -> (pointer, N); None -> (NULL, 0)."""

@@ -1,7 +1,7 @@
 """Command-line harness mirroring AliParaformerAsr.Examples (`-type offline` and `-type online`).
 
     python -m aliparaformerasr_amd.examples -type offline -method batch -base <dir> -model <name> \
-        [-accuracy int8] [-threads 2] [-decode ctc|frames] -files a.wav b.wav
+        [-accuracy int8] [-threads 2] [-decode ctc|frames] [-intake host|device] -files a.wav b.wav
     python -m aliparaformerasr_amd.examples -type online -method one -base <dir> -model <name> -files a.wav
 
 Mirrors (file:line in /root/reference/AliParaformerAsr.Examples):
@@ -20,7 +20,10 @@ Mirrors (file:line in /root/reference/AliParaformerAsr.Examples):
     400-sample silence chunks (:160-163), one AddSamples + GetResult + printed text per chunk (:181-194; only the "one"
     method exists upstream — the batch loop is commented out there), timing lines :272-279.
 Not in the reference: `-decode ctc` (offline, SenseVoice models) prints the CTC-collapsed hypothesis with per-token
-timestamps (OfflineRecognizer.SetDecode); `-decode frames`, the default, is the reference's one id per frame."""
+timestamps (OfflineRecognizer.SetDecode); `-decode frames`, the default, is the reference's one id per frame.
+`-intake device` (offline) reads only the wav header on the host (pf_host_wav_info) and hands the payload to
+OfflineStream.AddPcm raw: decode, down-mix and resample run on the device and give the samples GetFileSample gives;
+`-intake host`, the default, is the path above, untouched."""
 from __future__ import annotations
 
 import ctypes as C
@@ -41,6 +44,18 @@ def get_file_sample(path: str):
     out = np.zeros(max(n.value, 1), np.float32)
     N.check(lib.pf_host_wav_read(path.encode(), out.ctypes.data_as(C.POINTER(C.c_float)), out.size, n, sr, ch, dur))
     return out[: n.value], dur.value
+
+
+def get_file_pcm(path: str):
+    """The file as OfflineStream.AddPcm takes it -> (payload bytes, sample_rate, channels, format name, duration_ms)."""
+    desc = N.PfPcmDesc(); off = C.c_int64(); nb = C.c_int64(); dur = C.c_double()
+    N.check(N.load().pf_host_wav_info(path.encode(), C.byref(desc), C.byref(off), C.byref(nb), C.byref(dur)))
+    with open(path, "rb") as f:
+        f.seek(off.value)
+        payload = f.read(nb.value)
+    name = next(k for k, v in N.PCM_FORMATS.items() if v[0] == desc.format)
+    bps = N.PCM_FORMATS[name][1]
+    return payload[: len(payload) // bps * bps], desc.sample_rate, desc.channels, name, dur.value
 
 
 def is_audio_by_header(path: str) -> bool:
@@ -110,7 +125,7 @@ def _result_line(r) -> str:
 
 
 def offline_recognizer(method="one", model="paraformer-seaco-large-zh-timestamp-onnx-offline", accuracy="int8",
-                       threads=2, files=None, base=None, out=sys.stdout, decode="frames"):
+                       threads=2, files=None, base=None, out=sys.stdout, decode="frames", intake="host"):
     from .offline_recognizer import OfflineRecognizer
     base = base or os.getcwd()
     sel = select_model_files(base, model, accuracy)
@@ -130,7 +145,11 @@ def offline_recognizer(method="one", model="paraformer-seaco-large-zh-timestamp-
     for f in files:
         if not os.path.isfile(f) or not is_audio_by_header(f):
             continue
-        s, dur = get_file_sample(f)
+        if intake == "device":
+            pcm = get_file_pcm(f)
+            s, dur = pcm[:4], pcm[4]
+        else:
+            s, dur = get_file_sample(f)
         paths.append(f); samples.append(s); total_ms += dur
     if not samples:
         print("No media file is read!", file=out)
@@ -139,12 +158,18 @@ def offline_recognizer(method="one", model="paraformer-seaco-large-zh-timestamp-
     t0 = time.perf_counter()
     method = method or "batch"
     results = []
+
+    def add(st, s):
+        if isinstance(s, tuple):
+            st.AddPcm(s[0], s[1], s[2], s[3])
+        else:
+            st.AddSamples(s)
     print("Recognition results:\r\n", file=out)
     try:
         if method == "one":
             for p, s in zip(paths, samples):
                 st = rec.CreateOfflineStream()
-                st.AddSamples(s)
+                add(st, s)
                 r = rec.GetResult(st)
                 results.append(r)
                 print(p, file=out); print(_result_line(r), file=out); print("", file=out)
@@ -152,7 +177,7 @@ def offline_recognizer(method="one", model="paraformer-seaco-large-zh-timestamp-
             streams = []
             for s in samples:
                 st = rec.CreateOfflineStream()
-                st.AddSamples(s)
+                add(st, s)
                 streams.append(st)
             results = rec.GetResults(streams)
             for p, r in zip(paths, results):
@@ -282,6 +307,11 @@ def parse_args(argv, env=None):
             if i >= len(argv) or argv[i].lower() not in ("ctc", "frames"):
                 raise ValueError("The decode type must be ctc or frames")
             cfg["decode"] = argv[i].lower()
+        elif a == "-intake":
+            i += 1
+            if i >= len(argv) or argv[i].lower() not in ("host", "device"):
+                raise ValueError("The intake type must be host or device")
+            cfg["intake"] = argv[i].lower()
         elif a == "-threads":
             try:
                 i += 1
@@ -315,7 +345,7 @@ def main(argv=None):
                           cfg["modelBasePath"] or None)
     elif cfg["recognizerType"] == "offline":
         offline_recognizer(cfg["methodType"], cfg["modelName"], cfg["modelAccuracy"], cfg["threads"], cfg["files"],
-                           cfg["modelBasePath"] or None, decode=cfg.get("decode", "frames"))
+                           cfg["modelBasePath"] or None, decode=cfg.get("decode", "frames"), intake=cfg.get("intake", "host"))
     else:
         print("the recognizer type must be online or offline")
         return 2

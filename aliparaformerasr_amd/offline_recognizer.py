@@ -118,6 +118,18 @@ class OfflineStream:
         x = np.ascontiguousarray(samples, dtype=np.float32)
         _ck(self._lib.pf_stream_add_samples(self._h, x.ctypes.data_as(C.POINTER(C.c_float)), x.shape[0]))
 
+    def AddPcm(self, data, sample_rate: int, channels: int = 1, format: str = "s16", downmix_always: bool = False) -> None:
+        """AddSamples for audio as callers hold it: raw interleaved PCM (bytes, or a numpy array of the format's dtype —
+        "u8", "s16", "s24" (bytes), "s32", "f32", "f64", "alaw", "mulaw") at any rate, mono or stereo.  Decoded, down-mixed and
+        resampled to the model's rate exactly as the Examples' GetFileSample does (a stereo stream AT the model's rate stays
+        interleaved unless downmix_always), on the device for the first call on a recognizer's stream."""
+        if data is None:
+            _ck(self._lib.pf_stream_add_pcm(self._h, None, 0, C.byref(N.pcm_desc(sample_rate, channels, format, downmix_always))))
+            return
+        raw, n = N.pcm_bytes(data, format)
+        keep = raw if raw.size else np.zeros(1, np.uint8)
+        _ck(self._lib.pf_stream_add_pcm(self._h, keep.ctypes.data, n, C.byref(N.pcm_desc(sample_rate, channels, format, downmix_always))))
+
     @property
     def Hotwords(self) -> Optional[List[List[int]]]:
         n = C.c_int32()

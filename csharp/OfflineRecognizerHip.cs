@@ -28,6 +28,25 @@ namespace AliParaformerAsr.Hip
         public void AddSamples(float[] samples)
             => ParaformerHip.Check(ParaformerHip.pf_stream_add_samples(Handle, samples, samples == null ? 0 : samples.LongLength));
 
+        /// <summary>Not in the reference: AddSamples for audio as a caller holds it — raw interleaved PCM of `format`
+        /// (ParaformerHip.PF_PCM_*) at any rate, mono or stereo.  Decoded, down-mixed and resampled to the model's rate exactly
+        /// as the Examples' GetFileSample does (a stereo stream AT the model's rate stays interleaved unless downmixAlways), on
+        /// the device for the first call on a recognizer's stream.</summary>
+        public void AddPcm(byte[] data, int sampleRate, int channels, int format = ParaformerHip.PF_PCM_S16, bool downmixAlways = false)
+        {
+            PfPcmDesc d = PfPcmDesc.Of(format, sampleRate, channels, downmixAlways);
+            int bytesPerValue = format == ParaformerHip.PF_PCM_S16 ? 2 : format == ParaformerHip.PF_PCM_S24 ? 3
+                              : format == ParaformerHip.PF_PCM_S32 || format == ParaformerHip.PF_PCM_F32 ? 4 : format == ParaformerHip.PF_PCM_F64 ? 8 : 1;
+            ParaformerHip.Check(ParaformerHip.pf_stream_add_pcm(Handle, data, data == null ? 0 : data.LongLength / bytesPerValue, ref d));
+        }
+
+        /// <summary>16-bit PCM as most capture APIs deliver it.</summary>
+        public void AddPcm(short[] samples, int sampleRate, int channels = 1, bool downmixAlways = false)
+        {
+            PfPcmDesc d = PfPcmDesc.Of(ParaformerHip.PF_PCM_S16, sampleRate, channels, downmixAlways);
+            ParaformerHip.Check(ParaformerHip.pf_stream_add_pcm(Handle, samples, samples == null ? 0 : samples.LongLength, ref d));
+        }
+
         /// <summary>OfflineStream.cs:58-68: the entity Forward reads.  A snapshot: features that live on the device are
         /// computed and read back for it.</summary>
         public OfflineInputEntity GetDecodeChunk() => OfflineInputEntity;

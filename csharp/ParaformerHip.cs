@@ -30,6 +30,19 @@ namespace AliParaformerAsr.Native
         public int reserved0, reserved1, reserved2;
     }
 
+    /// <summary>pf_pcm_desc: what a block of raw interleaved PCM holds (paraformer_hip.h "PCM intake").  format: 1 u8, 2 s16,
+    /// 3 s24, 4 s32, 5 float32, 6 float64, 7 A-law, 8 mu-law; flags: PF_PCM_DOWNMIX_ALWAYS = 1.</summary>
+    [StructLayout(LayoutKind.Sequential)]
+    internal struct PfPcmDesc
+    {
+        public int struct_size, format, sample_rate, channels, flags, reserved0, reserved1, reserved2;
+        internal static PfPcmDesc Of(int format, int sampleRate, int channels, bool downmixAlways = false) => new PfPcmDesc
+        {
+            struct_size = Marshal.SizeOf<PfPcmDesc>(), format = format, sample_rate = sampleRate, channels = channels,
+            flags = downmixAlways ? ParaformerHip.PF_PCM_DOWNMIX_ALWAYS : 0,
+        };
+    }
+
     /// <summary>pf_batch_out: capacities in, L / V / cif_peak_len and the filled buffers out.</summary>
     [StructLayout(LayoutKind.Sequential)]
     internal struct PfBatchOut
@@ -74,6 +87,15 @@ namespace AliParaformerAsr.Native
         [DllImport(Lib)] internal static extern int pf_fetch_ctc(IntPtr e, [Out] long[]? ids, [Out] int[]? first, [Out] int[]? last,
                                                                 [Out] float[]? score, int cap, [Out] int[]? n, out int nMax);
 
+        // PCM intake (additions to ABI 6): raw interleaved values, decoded / down-mixed / resampled on the device in front of the
+        // fbank, bit for bit what GetFileSample (Examples/Utils/AudioHelper.cs:12-32) returns; nValues counts interleaved values
+        internal const int PF_PCM_U8 = 1, PF_PCM_S16 = 2, PF_PCM_S24 = 3, PF_PCM_S32 = 4, PF_PCM_F32 = 5, PF_PCM_F64 = 6, PF_PCM_ALAW = 7,
+                           PF_PCM_MULAW = 8, PF_PCM_DOWNMIX_ALWAYS = 1;
+        [DllImport(Lib)] internal static extern int pf_pcm_num_samples(ref PfPcmDesc desc, int fs, long nValues, out long nOut);
+        [DllImport(Lib)] internal static extern int pf_stage_pcm(IntPtr e, IntPtr[] data, long[] nValues, PfPcmDesc[] descs, int nDescs, int B);
+        [DllImport(Lib)] internal static extern int pf_recognize_pcm(IntPtr e, IntPtr[] data, long[] nValues, PfPcmDesc[] descs, int nDescs,
+                                                                    int B, int[]? hotwords, int nHotwords, ref PfBatchOut o);
+
         // ---- several GPUs in one process (paraformer_hip.h section 4b) ------------------------------------------
         [DllImport(Lib)] internal static extern int pf_group_create(ref PfEngineConfig cfg, int[] devices, int nDevices, out IntPtr group);
         [DllImport(Lib)] internal static extern void pf_group_destroy(IntPtr group);
@@ -104,6 +126,8 @@ namespace AliParaformerAsr.Native
         [DllImport(Lib)] internal static extern int pf_recognizer_num_engines(IntPtr r);   // engines of the pool ($PF_RECOGNIZER_ENGINES)
         [DllImport(Lib)] internal static extern int pf_recognizer_create_stream(IntPtr r, out IntPtr stream);
         [DllImport(Lib)] internal static extern int pf_stream_add_samples(IntPtr s, float[]? samples, long n);
+        [DllImport(Lib)] internal static extern int pf_stream_add_pcm(IntPtr s, byte[]? data, long nValues, ref PfPcmDesc desc);
+        [DllImport(Lib)] internal static extern int pf_stream_add_pcm(IntPtr s, short[]? data, long nValues, ref PfPcmDesc desc);
         [DllImport(Lib)] internal static extern int pf_stream_set_hotwords(IntPtr s, int[]? ids, int[]? lens, int nHotwords);
         [DllImport(Lib)] internal static extern int pf_stream_get_hotwords(IntPtr s, [Out] int[] ids, int idsCap, [Out] int[] lens, int lensCap, out int nHotwords);
         [DllImport(Lib)] internal static extern int pf_stream_num_feature_floats(IntPtr s, out int n);

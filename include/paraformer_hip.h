@@ -218,6 +218,37 @@ int pf_fetch_scores(pf_engine* e, float* scores, int64_t cap, int32_t* L_out);
 int pf_fetch_ctc(pf_engine* e, int64_t* ids, int32_t* first, int32_t* last, float* score, int32_t cap, int32_t* n,
                  int32_t* n_max);
 
+/* ---- PCM intake (additions to ABI 6) --------------------------------------------------------------------------------
+   The audio in the form callers hold it — a wav payload, PCM off a socket — uploaded RAW and turned into the engine's
+   float32 mono samples at `fs` by one kernel (csrc/k_pcm.hip) in front of the unchanged fbank.  The result is bit for bit
+   what pf_host_wav_read / pf_host_resample produce, i.e. the reference's GetFileSample (Examples/Utils/AudioHelper.cs
+   :12-32), quirks included:
+     decode    PCM8 b/128-1, PCM16 /32768, PCM24 /8388608, PCM32 /2147483648, float32 unchanged, float64 narrowed,
+               G.711 A-law / mu-law expanded to 16-bit first;
+     resample  ONLY when sample_rate != fs: stereo is averaged ((l + r) * 0.5f, a trailing unpaired value dropped), then
+               linear interpolation in float64, Round(n / ratio) (half to even) output samples (Resample :223-279);
+     quirk     at sample_rate == fs nothing is resampled and NOTHING IS DOWN-MIXED: a stereo stream at the native rate
+               comes out interleaved, as upstream.  PF_PCM_DOWNMIX_ALWAYS averages the channels at the native rate too.
+   n_values counts INTERLEAVED values (data bytes / bytes per value), not frames.
+   PF_ERR_INVALID_ARG: data NULL with n_values > 0, channels not 1 or 2, sample_rate <= 0, unknown format, n_values above
+   2^31 - 1 (the host definition indexes with int), struct_size mismatch.
+   Out of scope: the streaming recognizer's AddSamples (resampling across chunks needs a carried phase the reference's
+   one-shot Resample does not define), pf_group_*, more than two channels, compressed containers, sinc / polyphase
+   filtering (the reference's linear interpolation is the definition, aliasing included). */
+typedef enum pf_pcm_format { PF_PCM_U8 = 1, PF_PCM_S16, PF_PCM_S24, PF_PCM_S32, PF_PCM_F32, PF_PCM_F64, PF_PCM_ALAW, PF_PCM_MULAW } pf_pcm_format;
+#define PF_PCM_DOWNMIX_ALWAYS 1
+typedef struct pf_pcm_desc { int32_t struct_size, format, sample_rate, channels, flags, reserved[3]; } pf_pcm_desc;
+/* Host only: the sample count the conversion yields (to size buffers, or for pf_frontend_num_frames). */
+int pf_pcm_num_samples(const pf_pcm_desc* desc, int32_t fs, int64_t n_values, int64_t* n_out);
+/* pf_stage_audio for raw PCM: utterance b = n_values[b] values at data[b], described by descs[b] (n_descs == B) or by
+   descs[0] (n_descs == 1).  Followed by pf_run_staged / pf_fetch, unchanged. */
+int pf_stage_pcm(pf_engine* e, const void* const* data, const int64_t* n_values, const pf_pcm_desc* descs, int32_t n_descs,
+                 int32_t B);
+/* pf_recognize for raw PCM: hotwords, the per-thread result slot and PF_DECODE_* as there
+   (n_b = 4 + pf_frontend_num_frames(pf_pcm_num_samples(...))). */
+int pf_recognize_pcm(pf_engine* e, const void* const* data, const int64_t* n_values, const pf_pcm_desc* descs,
+                     int32_t n_descs, int32_t B, const int32_t* hotwords, int32_t n_hotwords, pf_batch_out* out);
+
 /* ------------------------------------------------------------------------ */
 /* 4b. Multi-GPU inside one process: one engine, one host thread and one HIP stream per listed
  *     device.  The reference builds a single ORT session (OfflineRecognizer.cs:23); what shards is the utterance
@@ -287,6 +318,10 @@ int pf_op_argmax(pf_engine* e, const float* x, int64_t rows, int32_t V, int64_t*
 int pf_op_ctc_collapse(pf_engine* e, const int64_t* ids, const float* scores, const int32_t* lens, int32_t B, int32_t T,
                        int32_t blank, int64_t* ids_out, int32_t* first_out, int32_t* last_out, float* score_out, int32_t cap,
                        int32_t* n_out);
+/* exactly the pipeline's PCM intake kernel (k_pcm.hip) on caller data: the float samples it hands to the fbank.
+   out == NULL: only learn *n_out.  PF_ERR_CAPACITY (n_out filled in) when cap < n_out. */
+int pf_op_pcm_convert(pf_engine* e, const void* data, int64_t n_values, const pf_pcm_desc* desc, float* out, int64_t cap,
+                      int64_t* n_out);
 /* C = A[M,K] * W[N,K]^T + bias, f16 operands / f32 accumulate; epilogue 0 none, 1 relu,
    2 = f16 result store (the path the pipeline uses), returned widened to fp32. */
 /* One dynamically quantised Linear, the building block of math_mode 2 (the reference's default model.int8.onnx:
@@ -468,6 +503,12 @@ int pf_recognizer_create_stream(pf_recognizer* r, pf_stream** out);     /* Creat
    flight — whatever reads the samples later (pf_recognizer_get_results, a second pf_stream_add_samples, pf_stream_free) waits
    for it by itself. */
 int pf_stream_add_samples(pf_stream* s, const float* samples, int64_t n);
+/* AddSamples for raw PCM (see "PCM intake" above).  The FIRST call on a stream of a recognizer uploads the raw bytes through
+   the same copy lane and converts them on the device behind the last DMA piece: the stream then holds exactly what
+   pf_stream_add_samples of the converted floats would have left, and the call returns as early.  Every other case (a second
+   call, a pf_stream_create stream not adopted yet, PF_RECOGNIZER_DEVICE_STREAMS=0, no device memory) converts on the host
+   with the same arithmetic and continues as pf_stream_add_samples.  data == NULL -> PF_ERR_NULL_SAMPLES. */
+int pf_stream_add_pcm(pf_stream* s, const void* data, int64_t n_values, const pf_pcm_desc* desc);
 /* stream.Hotwords = List<int[]> (flattened ids + per-hotword lengths); n_hotwords < 0 sets null. */
 int pf_stream_set_hotwords(pf_stream* s, const int32_t* ids, const int32_t* lens, int32_t n_hotwords);
 int pf_stream_get_hotwords(pf_stream* s, int32_t* ids, int32_t ids_cap, int32_t* lens,
@@ -600,6 +641,11 @@ int pf_host_wav_read(const char* path, float* out, int64_t cap, int64_t* n_out, 
 int pf_host_resample(const float* src, int64_t n, int32_t sr_in, int32_t sr_out, int32_t channels, float* out,
                      int64_t cap, int64_t* n_out);
 int pf_host_is_audio(const char* path, int32_t* is_audio);
+/* The header walk of pf_host_wav_read WITHOUT the sample loop: what the file holds (desc: format, rate, channels; flags 0) and
+   where (data_offset / data_bytes of the payload inside the file, data_bytes clamped to the file; n_values = data_bytes /
+   bytes per value), so a caller hands the payload over raw (pf_stream_add_pcm, pf_recognize_pcm).  Each output may be NULL.
+   PF_ERR_IO missing file, PF_ERR_FORMAT not RIFF/WAVE or no fmt / data chunk, PF_ERR_UNSUPPORTED other sample formats. */
+int pf_host_wav_info(const char* path, pf_pcm_desc* desc, int64_t* data_offset, int64_t* data_bytes, double* duration_ms);
 
 #ifdef __cplusplus
 }
