@@ -41,6 +41,14 @@ class PfPcmDesc(C.Structure):
                 ("flags", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
+class PfAttnDesc(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("kind", C.c_int32), ("layout", C.c_int32), ("shared_kv", C.c_int32),
+                ("o_ld", C.c_int32), ("form", C.c_int32), ("ldkv", C.c_int32), ("kv_off", C.c_int32)]
+
+
+PF_ATTN_CANARY = 0x4D2B
+
+
 def pcm_desc(sample_rate, channels=1, format="s16", downmix_always=False) -> "PfPcmDesc":
     fmt = PCM_FORMATS[format][0] if isinstance(format, str) else int(format)
     return PfPcmDesc(C.sizeof(PfPcmDesc), fmt, int(sample_rate), int(channels), PF_PCM_DOWNMIX_ALWAYS if downmix_always else 0)
@@ -176,6 +184,8 @@ SIGNATURES = {
     "pf_op_layernorm": (C.c_int, [_vp, _f, _f, _f, C.c_int64, C.c_int32, _f]),
     "pf_op_attention": (C.c_int, [_vp, _f, _f, _f, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f]),
     "pf_op_fsmn": (C.c_int, [_vp, _f, _f, _f, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f]),
+    "pf_op_attention_ex": (C.c_int, [_vp, _f, _f, _f, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P(PfAttnDesc), _f, _vp, C.c_int64, _f,
+                                     _i32]),
     "pf_op_qkv_attention": (C.c_int, [_vp, _f, _f, _f, C.c_int32, C.c_int32, C.c_int32, _f, _f, _f, _f]),
     "pf_op_cif": (C.c_int, [_vp, _f, _f, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, _f, _i32, _i32, _i32]),
     "pf_op_encoder": (C.c_int, [_vp, _f, C.c_int32, C.c_int32, _f]),

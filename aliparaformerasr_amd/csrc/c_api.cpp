@@ -737,6 +737,18 @@ int pf_op_attention(pf_engine* h, const float* q, const float* k, const float* v
   return PF_OK;
   PF_CATCH
 }
+int pf_op_attention_ex(pf_engine* h, const float* q, const float* k, const float* v, int32_t B, int32_t Lq, int32_t Lk,
+                       int32_t heads, const pf_attn_desc* desc, float* out, void* raw, int64_t raw_bytes, float* range_out,
+                       int32_t* ran) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  NEED(q); NEED(k); NEED(v); NEED(desc); NEED(out); NEED(raw); NEED(ran);
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->op_attention_ex(q, k, v, B, Lq, Lk, heads, *desc, out, raw, raw_bytes, range_out, ran);
+  return PF_OK;
+  PF_CATCH
+}
 int pf_op_qkv_attention(pf_engine* h, const float* x, const float* w, const float* bias, int32_t B, int32_t T, int32_t K,
                         float* q_out, float* k_out, float* v_out, float* ctx_out) {
   PF_TRY

@@ -162,6 +162,8 @@ class Engine {
   void op_logsoftmax_argmax(const float* x, int64_t rows, int V, float* y, int64_t* ids);
   void op_layernorm(const float* x, const float* g, const float* b, int64_t rows, int D, float* y);
   void op_attention(const float* q, const float* k, const float* v, int B, int Lq, int Lk, int H, float* o);
+  void op_attention_ex(const float* q, const float* k, const float* v, int B, int Lq, int Lk, int H, const pf_attn_desc& ds, float* out,
+                       void* raw, int64_t raw_bytes, float* range_out, int32_t* ran);
   void op_qkv_attention(const float* x, const float* w, const float* bias, int B, int T, int K, float* q_out, float* k_out,
                         float* v_out, float* ctx_out);
   void op_fsmn(const float* v, const float* w, const float* mask, int B, int T, int D, int k, float* y);

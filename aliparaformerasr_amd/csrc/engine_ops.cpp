@@ -6,6 +6,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <set>
 
 #include "hostutil.h"
@@ -704,6 +705,128 @@ void Engine::op_attention(const float* q, const float* k, const float* v, int B,
     o[i] = (float)hv;
   }
   (void)oo32;
+}
+
+// The attention kernels on caller data, launched as the pipeline launches them (packed / interleaved / blocked operands, shared
+// K | V, output strides, forced workgroup form, range output), for the conformance tests.  Every device buffer is built on the
+// host: operand buffers hold the NaN pattern of their type (0x7E00 / a quiet NaN) except the valid elements, with at least 256
+// rows of slack behind each, so a read past the contract shows as a NaN in the result and never touches unmapped memory; the
+// output buffer holds PF_ATTN_CANARY except what the kernel stores, and comes back whole.
+void Engine::op_attention_ex(const float* q, const float* k, const float* v, int B, int Lq, int Lk, int H, const pf_attn_desc& ds, float* out,
+                             void* raw, int64_t raw_bytes, float* range_out, int32_t* ran) {
+  PF_HIP(hipSetDevice(device_));
+  PF_CHECK(ds.struct_size == (int32_t)sizeof(pf_attn_desc), PF_ERR_INVALID_ARG, "pf_attn_desc.struct_size mismatch");
+  PF_CHECK(B > 0 && Lq > 0 && Lk > 0 && H > 0, PF_ERR_INVALID_ARG, "attention_ex: empty input");
+  const int Dm = H * 128, kind = ds.kind, layout = ds.layout, Bk = ds.shared_kv ? 1 : B;
+  const int o_ld = ds.o_ld ? ds.o_ld : Dm;
+  PF_CHECK(kind >= 0 && kind <= 2 && layout >= 0 && layout <= 3, PF_ERR_INVALID_ARG, "attention_ex: kind is 0..2, layout 0..3");
+  PF_CHECK(o_ld >= Dm, PF_ERR_INVALID_ARG, "attention_ex: o_ld < heads * 128");
+  PF_CHECK(layout != 1 || (Lq == Lk && !ds.shared_kv), PF_ERR_INVALID_ARG, "attention_ex: the packed layout is self-attention");
+  PF_CHECK(layout != 3 || (Lq == Lk && !ds.shared_kv && kind == 0), PF_ERR_INVALID_ARG, "attention_ex: the blocked layout is f16 self-attention");
+  PF_CHECK(layout != 2 || (ds.kv_off >= 0 && ds.kv_off % 8 == 0 && ds.ldkv % 8 == 0 && ds.ldkv >= ds.kv_off + 2 * Dm), PF_ERR_INVALID_ARG,
+           "attention_ex: ldkv / kv_off");
+  PF_CHECK(kind == 0 || (!ds.form && !range_out), PF_ERR_INVALID_ARG, "attention_ex: form and range belong to the f16 kernel");
+  PF_CHECK(quant_scratch_bytes() >= 256 * 2 * sizeof(float), PF_ERR_UNSUPPORTED, "attention_ex: the range output is 256 pairs");
+  const size_t es = kind == 0 ? 2 : 4;                         // operand element size
+  const int64_t kSlack = 256;
+  const int64_t nq = (int64_t)B * Lq, nk = (int64_t)Bk * Lk;
+  // operand matrices: rows x ld elements each; q / k / v = (matrix, column offset)
+  int64_t rows[3] = {0, 0, 0}, ld[3] = {0, 0, 0};
+  int mat[3] = {0, 1, 2}, col[3] = {0, 0, 0};
+  if (layout == 0) { rows[0] = nq + kSlack; rows[1] = rows[2] = nk + kSlack; ld[0] = ld[1] = ld[2] = Dm; }
+  else if (layout == 1) { rows[0] = nq + kSlack; ld[0] = 3 * Dm; mat[1] = mat[2] = 0; col[1] = Dm; col[2] = 2 * Dm; }
+  else if (layout == 2) { rows[0] = nq + kSlack; ld[0] = Dm; rows[1] = nk + kSlack; ld[1] = ds.ldkv; mat[2] = 1; col[1] = ds.kv_off; col[2] = ds.kv_off + Dm; }
+  else { rows[0] = round_up(nq, 32) + kSlack; ld[0] = 2 * Dm; mat[1] = 0; col[1] = Dm; rows[2] = nk + kSlack; ld[2] = Dm; }
+  const int64_t orow = kind == 2 ? 2 * (int64_t)o_ld : o_ld;   // output row in elements (kind 2: hi | lo')
+  const size_t oes = kind == 1 ? 4 : 2;
+  const size_t obytes = (size_t)(nq + kSlack) * orow * oes;
+  PF_CHECK(raw_bytes == (int64_t)obytes, PF_ERR_INVALID_ARG, "attention_ex: raw_bytes must be " + std::to_string(obytes));
+  size_t off = 0;
+  auto carve = [&](size_t bytes) { size_t o2 = off; off += round_up((int64_t)bytes, (int64_t)kAlign); return o2; };
+  size_t om[3];
+  for (int m = 0; m < 3; ++m) om[m] = carve((size_t)rows[m] * ld[m] * es);
+  const size_t oo = carve(obytes), org = carve(quant_scratch_bytes());
+  ensure(ws_tmp_, off);
+  char* base = (char*)ws_tmp_.p;
+  // host images
+  std::vector<std::vector<uint16_t>> img16(3);
+  std::vector<std::vector<float>> img32(3);
+  const float qnan = std::numeric_limits<float>::quiet_NaN();
+  for (int m = 0; m < 3; ++m) {
+    if (kind == 0) img16[m].assign((size_t)rows[m] * ld[m], (uint16_t)0x7E00);
+    else img32[m].assign((size_t)rows[m] * ld[m], qnan);
+  }
+  auto put = [&](int which, const float* src, int64_t n_rows) {
+    const int m = mat[which];
+    for (int64_t r = 0; r < n_rows; ++r)
+      for (int c = 0; c < Dm; ++c) {
+        const float x = src[(size_t)r * Dm + c];
+        size_t at;
+        if (layout == 3 && which < 2) {
+          const int cc = col[which] + c;
+          at = (((size_t)(r >> 5) * (2 * Dm / 8) + (cc >> 3)) * 32 + (r & 31)) * 8 + (cc & 7);
+        } else {
+          at = (size_t)r * ld[m] + col[which] + c;
+        }
+        if (kind == 0) { const half_t hx = (half_t)x; std::memcpy(&img16[m][at], &hx, 2); }
+        else img32[m][at] = x;
+      }
+  };
+  put(0, q, nq); put(1, k, nk); put(2, v, nk);
+  for (int m = 0; m < 3; ++m)
+    if (rows[m]) PF_HIP(hipMemcpyAsync(base + om[m], kind == 0 ? (const void*)img16[m].data() : (const void*)img32[m].data(),
+                                       (size_t)rows[m] * ld[m] * es, hipMemcpyHostToDevice, stream_));
+  std::vector<uint16_t> oimg(obytes / 2, (uint16_t)PF_ATTN_CANARY);
+  PF_HIP(hipMemcpyAsync(base + oo, oimg.data(), obytes, hipMemcpyHostToDevice, stream_));
+  std::vector<float> rimg(quant_scratch_bytes() / 4, qnan);
+  PF_HIP(hipMemcpyAsync(base + org, rimg.data(), rimg.size() * 4, hipMemcpyHostToDevice, stream_));
+  const int64_t q_bs = (int64_t)Lq * ld[mat[0]], k_bs = ds.shared_kv ? 0 : (int64_t)Lk * ld[mat[1]], v_bs = ds.shared_kv ? 0 : (int64_t)Lk * ld[mat[2]];
+  *ran = 1;
+  if (kind == 0) {
+    AttnArgs a{};
+    a.q = (half_t*)(base + om[mat[0]]) + col[0]; a.k = (half_t*)(base + om[mat[1]]) + col[1]; a.v = (half_t*)(base + om[mat[2]]) + col[2];
+    a.q_bstride = q_bs; a.k_bstride = k_bs; a.v_bstride = v_bs;
+    a.q_rstride = (int)ld[mat[0]]; a.k_rstride = (int)ld[mat[1]]; a.v_rstride = (int)ld[mat[2]];
+    if (layout == 3) {
+      a.q = a.k = (half_t*)(base + om[0]);
+      a.qk_blocked = 1; a.blk_groups = 2 * Dm / 8; a.blk_brows = Lq; a.blk_kgrp = Dm / 8;
+      a.q_rstride = a.k_rstride = 8;                        // ignored (alignment checks only)
+    }
+    a.o = (half_t*)(base + oo); a.o_bstride = (int64_t)Lq * o_ld; a.o_rstride = o_ld;
+    a.B = B; a.H = H; a.Lq = Lq; a.Lk = Lk;
+    a.force_nw = ds.form;
+    a.range = range_out ? (float*)(base + org) : nullptr;
+    launch_attention(stream_, a);
+  } else {
+    const float* qd = (const float*)(base + om[mat[0]]) + col[0];
+    const float* kd = (const float*)(base + om[mat[1]]) + col[1];
+    const float* vd = (const float*)(base + om[mat[2]]) + col[2];
+    if (kind == 1)
+      launch_attention_f32(stream_, qd, q_bs, (int)ld[mat[0]], kd, k_bs, (int)ld[mat[1]], vd, v_bs, (int)ld[mat[2]], (float*)(base + oo),
+                           (int64_t)Lq * o_ld, o_ld, B, H, Lq, Lk);
+    else if (!launch_attention_f32_pair(stream_, qd, q_bs, (int)ld[mat[0]], kd, k_bs, (int)ld[mat[1]], vd, v_bs, (int)ld[mat[2]],
+                                        (half_t*)(base + oo), (int64_t)Lq * 2 * o_ld, 2 * o_ld, o_ld, B, H, Lq, Lk))
+      *ran = 0;
+  }
+  PF_HIP(hipMemcpyAsync(raw, base + oo, obytes, hipMemcpyDeviceToHost, stream_));
+  if (range_out) PF_HIP(hipMemcpyAsync(range_out, base + org, 256 * 2 * sizeof(float), hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipStreamSynchronize(stream_));
+  for (int64_t r = 0; r < nq; ++r)
+    for (int c = 0; c < Dm; ++c) {
+      float val;
+      if (kind == 1) {
+        val = ((const float*)raw)[(size_t)r * o_ld + c];
+      } else {
+        half_t hi, lo;
+        std::memcpy(&hi, (const uint16_t*)raw + (size_t)r * orow + c, 2);
+        val = (float)hi;
+        if (kind == 2) {
+          std::memcpy(&lo, (const uint16_t*)raw + (size_t)r * orow + o_ld + c, 2);
+          val += (float)lo * (1.0f / 2048.0f);
+        }
+      }
+      out[(size_t)r * Dm + c] = val;
+    }
 }
 
 // The encoder's fused Q | K | V projection and its self-attention as enc_layer() launches them for long inputs: the persistent

@@ -507,7 +507,7 @@ namespace pf {
 // grid of the launch below: 256-query workgroups when they cover the chip, else 128-query ones
 static int attention_grid(const AttnArgs& a, int cus, bool& nw8) {
   const int wg8 = ((a.Lq + 255) / 256) * a.B * a.H;
-  nw8 = wg8 >= cus;
+  nw8 = a.force_nw ? a.force_nw == 8 : wg8 >= cus;
   return nw8 ? wg8 : ((a.Lq + ATT_BQ - 1) / ATT_BQ) * a.B * a.H;
 }
 static int attention_cus() {
@@ -540,6 +540,7 @@ void launch_attention(hipStream_t s, const AttnArgs& a) {
   d.blk = a.qk_blocked ? 1 : 0; d.blk_groups = a.blk_groups; d.blk_brows = a.blk_brows; d.blk_kgrp = a.blk_kgrp;
   PF_CHECK(!a.qk_blocked || (a.q == a.k && a.blk_groups > 0 && a.blk_brows >= a.Lq && a.blk_brows >= a.Lk), PF_ERR_INVALID_ARG,
            "attention: blocked Q | K needs one matrix and its geometry");
+  PF_CHECK(a.force_nw == 0 || a.force_nw == 4 || a.force_nw == 8, PF_ERR_INVALID_ARG, "attention: force_nw is 0, 4 or 8");
   PF_CHECK(!a.range || attention_reports_range(a), PF_ERR_INVALID_ARG, "attention: a range output needs a grid of at most 256 workgroups");
   PF_CHECK(a.q_rstride % 8 == 0 && a.k_rstride % 8 == 0 && a.v_rstride % 8 == 0 && a.o_rstride % 4 == 0,
            PF_ERR_INVALID_ARG, "attention: row strides must keep 16-byte alignment");

@@ -191,7 +191,10 @@ __global__ __launch_bounds__(256) void attn_f32_mfma_kernel(const float* __restr
   const float inv = 1.0f / l_run;
   if (opair) {
     // math_mode 3: the context is only the A operand of the out-projection — it leaves as that product's (hi | lo') pair
-    // (o_bs / o_rs then index the pair matrix, p_lo = column offset of the lo' half)
+    // (o_bs / o_rs then index the pair matrix, p_lo = column offset of the lo' half).  No contraction here: fused into
+    // fma(oacc, inv, -hi), the difference would be taken from the unrounded product, lo' would carry bits below the fp32
+    // value's last place and the pair would differ from split_x3_kernel's of the fp32 result (the fallback's).
+#pragma clang fp contract(off)
     typedef _Float16 h4 __attribute__((ext_vector_type(4)));
     half_t* pp = opair + (size_t)b * o_bs + (size_t)(q0 + l31) * o_rs + h * 128;
 #pragma unroll

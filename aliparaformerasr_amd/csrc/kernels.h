@@ -265,6 +265,7 @@ struct AttnArgs {
   // groups per row (128), utterance b starts at row b * blk_brows, head h's Q columns are groups 16 h .., its K columns
   // groups blk_kgrp + 16 h ..; the q / k strides are ignored, V and the output stay row-major
   int qk_blocked, blk_groups, blk_brows, blk_kgrp;
+  int force_nw;                                       // 0 = choose by shape; 4 / 8 = the 128- / 256-query workgroup (stand-alone op tests)
 };
 void launch_attention(hipStream_t s, const AttnArgs& a);
 bool attention_reports_range(const AttnArgs& a);      // the launch has at most 256 workgroups (one {min, max} pair each)

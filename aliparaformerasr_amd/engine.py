@@ -644,6 +644,27 @@ class Engine:
         N.check(self._lib.pf_op_attention(self._h, _fp(q), _fp(k), _fp(v), B, Lq, Lk, heads, _fp(o)))
         return o
 
+    def op_attention_ex(self, q, k, v, heads=4, kind=0, layout=0, shared_kv=False, o_ld=0, form=0, ldkv=0, kv_off=0,
+                        want_range=False) -> dict:
+        """The attention kernels launched as the pipeline launches them (pf_op_attention_ex in the header).  Returns
+        out [B, Lq, Dm] fp32; raw = the WHOLE output buffer as 16-bit (kinds 0 / 2) or 32-bit (kind 1) words,
+        [B*Lq + 256, o_ld] (kind 2: [.., 2*o_ld] = hi | lo'), canary PF_ATTN_CANARY where nothing was stored;
+        range = the 256 {min, max} pairs or None; ran = False when the kind-2 launcher declined."""
+        q, k, v = _f32(q), _f32(k), _f32(v)
+        B, Lq, Dm = q.shape
+        Lk = k.shape[1]
+        assert Dm == heads * 128 and k.shape == v.shape and k.shape[0] == (1 if shared_kv else B)
+        ld = o_ld or Dm
+        rows = B * Lq + 256
+        raw = np.zeros((rows, 2 * ld if kind == 2 else ld), np.uint32 if kind == 1 else np.uint16)
+        out = np.zeros_like(q)
+        rng = np.zeros((256, 2), np.float32) if want_range else None
+        ran = C.c_int32(0)
+        d = N.PfAttnDesc(C.sizeof(N.PfAttnDesc), kind, layout, 1 if shared_kv else 0, o_ld, form, ldkv, kv_off)
+        N.check(self._lib.pf_op_attention_ex(self._h, _fp(q), _fp(k), _fp(v), B, Lq, Lk, heads, C.byref(d), _fp(out),
+                                             raw.ctypes.data, raw.nbytes, _fp(rng) if want_range else None, C.byref(ran)))
+        return {"out": out, "raw": raw, "range": rng, "ran": bool(ran.value)}
+
     def op_fsmn(self, v, w, mask=None) -> np.ndarray:
         v, w = _f32(v), _f32(w)
         B, T, D = v.shape

@@ -302,7 +302,7 @@ int pf_last_flops(pf_engine* e, double* flops);
 /* ------------------------------------------------------------------------ */
 /* 5. Stand-alone device ops exposed for parity tests (tests/ call these through
  *    the C ABI).  pf_op_gemm_ex / pf_op_gemm_rc / pf_op_ffn / pf_op_fsmn_enc / pf_op_fsmn_dec /
- *    pf_op_logsoftmax_argmax / pf_op_attention / pf_op_layernorm / pf_op_cif /
+ *    pf_op_logsoftmax_argmax / pf_op_attention / pf_op_attention_ex / pf_op_layernorm / pf_op_cif /
  *    pf_op_lfr_cmvn_pad launch exactly the kernels (and kernel variants) the
  *    pipeline launches; pf_op_gemm chooses its variant by shape like the
  *    pipeline does; pf_op_fsmn is a generic fp32 FSMN (arbitrary mask) that the
@@ -454,6 +454,26 @@ int pf_op_layernorm(pf_engine* e, const float* x, const float* gamma, const floa
    converted to f16 on device as the pipeline does). */
 int pf_op_attention(pf_engine* e, const float* q, const float* k, const float* v,
                     int32_t B, int32_t Lq, int32_t Lk, int32_t heads, float* out);
+/* The attention kernels launched the way the pipeline launches them, for conformance tests (tests/attn_ref.py).
+   q [B,Lq,H*128], k / v [B,Lk,H*128] ([1,Lk,H*128] with shared_kv) are fp32 host arrays; the op lays them out itself:
+     kind    0 = the f16 kernel (k_attn.hip); 1 = the fp32 kernels (MFMA form, or one query per workgroup when the
+             output breaks the 16-byte rule); 2 = the fp32 MFMA form writing the (hi | lo') f16 pair, lo' o_ld columns
+             behind hi in rows of 2 * o_ld; `out` then receives hi + lo' * 2^-11
+     layout  0 = three contiguous matrices; 1 = packed [B*T, 3*Dm] = q | k | v, row stride 3*Dm (Lq == Lk);
+             2 = q contiguous, K | V side by side in [B*Lk, ldkv] at column kv_off (ldkv >= kv_off + 2*Dm, both % 8 == 0);
+             3 = Q | K in one blocked [rows, 2*Dm] f16 matrix built on the host, V row-major (kind 0, Lq == Lk)
+     shared_kv   k / v batch stride 0 (layouts 0 and 2)
+     o_ld    output row stride in elements (0 = Dm); form 0 = by shape, 4 / 8 = the 4- / 8-wave workgroup (kind 0)
+   Every device operand and its >= 256 rows of slack hold the NaN pattern of its type except the valid elements; the
+   output buffer (B*Lq + 256 rows of o_ld elements; 2*o_ld for kind 2) is pre-filled with the 16-bit pattern
+   PF_ATTN_CANARY and comes back whole in `raw` (raw_bytes must be its size).  range_out: NULL, or 512 floats = the 256
+   {min, max} pairs of the kernel's range output (kind 0; the buffer is NaN-filled before the launch).  *ran = 0 when
+   the kind-2 launcher reports that the MFMA form does not apply (nothing was launched), else 1. */
+#define PF_ATTN_CANARY 0x4D2B
+typedef struct pf_attn_desc { int32_t struct_size, kind, layout, shared_kv, o_ld, form, ldkv, kv_off; } pf_attn_desc;
+int pf_op_attention_ex(pf_engine* e, const float* q, const float* k, const float* v, int32_t B, int32_t Lq, int32_t Lk,
+                       int32_t heads, const pf_attn_desc* desc, float* out, void* raw, int64_t raw_bytes, float* range_out,
+                       int32_t* ran);
 /* The encoder's fused Q | K | V projection (d_model 512, 4 heads) and its self-attention as the pipeline launches them
    for long inputs: persistent 256 x 192 GEMM (q scaled by 1/sqrt(128); Q and K in the blocked activation layout, V
    row-major) + the attention kernel reading that layout.  x [B*T, K], w [1536, K] = [Q | K | V] rows, bias [1536] or

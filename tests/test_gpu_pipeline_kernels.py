@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 import torch
 
+import attn_ref as AR
 from aliparaformerasr_amd import weights as W
 from oracle import model as om
 
@@ -524,7 +525,30 @@ def test_qkv_split_kernel_and_attention_on_the_blocked_layout(eng):
                                    rtol=2e-3, atol=2e-3)
         ctx_ref = eng.op_attention(q.reshape(B, T, 512), k.reshape(B, T, 512), v.reshape(B, T, 512), 4).reshape(M, 512)
         np.testing.assert_array_equal(ctx, ctx_ref, err_msg=f"attention B={B} T={T}")
-
+    # ... and against an independent reference, so that the equality above does not rest on the attention kernel alone: a
+    # select-style input at (3, 77, 560).  Row r of x holds the +-1 code of the key it selects, its own code and its values;
+    # the weights copy them into every head (Q x 1, K x 16: winner 128 * 16 / sqrt(128) = 181, the next at most 153; V with
+    # a factor per head), so ctx[r, head h] is v[selected row, head h] exactly and within the f16 kernel's bound of attn_ref
+    B, T, K = 3, 77, 560
+    pick = rng.integers(0, T, (B, T))
+    pick[:, 0], pick[:, 1] = T - 1, 0
+    label = np.stack([rng.choice(4096, T, replace=False) for _ in range(B)])
+    x = np.zeros((B, T, K), np.float32)
+    x[:, :, 0:128] = AR.code(np.take_along_axis(label, pick, axis=1))
+    x[:, :, 128:256] = AR.code(label)
+    x[:, :, 256:384] = AR._values(rng, (B, T, 128))
+    w = np.zeros((1536, K), np.float32)
+    d = np.arange(128)
+    for h, fv in enumerate((1.0, -1.0, 2.0, 0.5)):
+        w[h * 128 + d, d] = 1.0
+        w[512 + h * 128 + d, 128 + d] = 16.0
+        w[1024 + h * 128 + d, 256 + d] = fv
+    q, k, v, ctx = (a.reshape(B, T, 512) for a in eng.op_qkv_attention(x.reshape(B * T, K), w, None, B, T))
+    ref = AR.attn_ref(q, k, v, 4)
+    assert np.isfinite(ctx).all()
+    ratio = np.abs(ctx - ref.O) / AR.bound(ref, 0, T)
+    assert ratio.max() <= 1.0, (ratio.max(), np.unravel_index(np.argmax(ratio), ratio.shape))
+    np.testing.assert_array_equal(ctx, np.stack([v[b, pick[b]] for b in range(B)]), err_msg="select on the blocked layout")
 
 
 
