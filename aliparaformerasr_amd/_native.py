@@ -26,6 +26,9 @@ PF_ERR_RECOGNITION = -10
 # pf_engine_set_decode / pf_recognizer_set_decode
 PF_DECODE_SCORES = 1
 PF_DECODE_CTC = 2
+PF_DECODE_TOPK = 8
+PF_TOPK_MAX = 8
+PF_NBEST_MAX = 64
 
 # PCM intake (pf_pcm_format, pf_pcm_desc.flags)
 PF_PCM_U8, PF_PCM_S16, PF_PCM_S24, PF_PCM_S32, PF_PCM_F32, PF_PCM_F64, PF_PCM_ALAW, PF_PCM_MULAW = range(1, 9)
@@ -156,6 +159,15 @@ SIGNATURES = {
     "pf_fetch_ctc": (C.c_int, [_vp, _i64, _i32, _i32, _f, C.c_int32, _i32, _i32]),
     "pf_op_ctc_collapse": (C.c_int, [_vp, _i64, _f, _i32, C.c_int32, C.c_int32, C.c_int32, _i64, _i32, _i32, _f, C.c_int32, _i32]),
     "pf_recognizer_set_decode": (C.c_int, [_vp, C.c_int32]),
+    "pf_engine_set_topk": (C.c_int, [_vp, C.c_int32]),
+    "pf_fetch_topk": (C.c_int, [_vp, _i64, _f, _i32, C.c_int64, _i32, _i32]),
+    "pf_op_topk": (C.c_int, [_vp, _f, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _i64, _f, _i32]),
+    "pf_host_nbest": (C.c_int, [_i64, _f, _i32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _i32, _P(C.c_double), _i32]),
+    "pf_recognizer_set_nbest": (C.c_int, [_vp, C.c_int32, C.c_int32]),
+    "pf_stream_token_alternatives": (C.c_int, [_vp, _P(_i64), _P(_f), _i32, _i32]),
+    "pf_stream_num_alternatives": (C.c_int, [_vp, _i32]),
+    "pf_stream_alternative": (C.c_int, [_vp, C.c_int32, _P(_i64), _i32, _P(C.c_double), _P(C.c_char_p), _i32]),
+    "pf_stream_alternative_token": (C.c_int, [_vp, C.c_int32, C.c_int32, _P(C.c_char_p)]),
     "pf_stream_scores": (C.c_int, [_vp, _P(_f), _i32]),
     "pf_host_group_sim": (C.c_int, [C.c_int32, C.c_int32, _i32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _i64,
                                     C.c_int32, _i32, _i32]),

@@ -362,6 +362,35 @@ int pf_fetch_ctc(pf_engine* h, int64_t* ids, int32_t* first, int32_t* last, floa
   PF_CATCH
 }
 
+int pf_engine_set_topk(pf_engine* h, int32_t k) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->set_topk(k);
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_fetch_topk(pf_engine* h, int64_t* ids, float* val, int32_t* n, int64_t cap_rows, int32_t* L_out, int32_t* K_out) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->fetch_topk(ids, val, n, cap_rows, L_out, K_out);
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_host_nbest(const int64_t* /*ids*/, const float* val, const int32_t* n, int32_t L, int32_t K, int32_t n_free, int32_t N,
+                  int32_t* out_ranks, double* out_scores, int32_t* n_out) {
+  PF_TRY
+  NEED(val); NEED(n); NEED(out_ranks); NEED(out_scores); NEED(n_out);
+  *n_out = host_nbest(val, n, L, K, n_free, N, out_ranks, out_scores);
+  return PF_OK;
+  PF_CATCH
+}
+
 int pf_profile_enable(pf_engine* h, int32_t on) {
   PF_TRY
   E(h)->profile_enable(on != 0);
@@ -542,6 +571,18 @@ int pf_op_pcm_convert(pf_engine* h, const void* data, int64_t n_values, const pf
   PF_CATCH
 }
 
+int pf_op_topk(pf_engine* h, const float* x, int64_t rows, int32_t V, int32_t ld, int32_t K, int64_t* ids, float* val,
+               int32_t* n) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  NEED(x); NEED(ids); NEED(val); NEED(n);
+  PF_CHECK(rows >= 0 && V > 0 && ld >= V && K >= 1 && K <= PF_TOPK_MAX, PF_ERR_INVALID_ARG, "topk: bad shape");
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->op_topk(x, rows, V, ld, K, ids, val, n);
+  return PF_OK;
+  PF_CATCH
+}
 int pf_op_ctc_collapse(pf_engine* h, const int64_t* ids, const float* scores, const int32_t* lens, int32_t B, int32_t T,
                        int32_t blank, int64_t* ids_out, int32_t* first_out, int32_t* last_out, float* score_out, int32_t cap,
                        int32_t* n_out) {
@@ -1046,6 +1087,62 @@ int pf_recognizer_set_decode(pf_recognizer* h, int32_t flags) {
   std::shared_ptr<Recognizer> r = R(h);
   PF_CHECK(!r->disposed(), PF_ERR_DISPOSED, "OfflineRecognizer");
   r->SetDecode(flags);
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_recognizer_set_nbest(pf_recognizer* h, int32_t N, int32_t K) {
+  PF_TRY
+  std::shared_ptr<Recognizer> r = R(h);
+  PF_CHECK(!r->disposed(), PF_ERR_DISPOSED, "OfflineRecognizer");
+  r->SetNBest(N, K);
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_stream_token_alternatives(pf_stream* h, const int64_t** ids, const float** val, int32_t* n_tokens, int32_t* K) {
+  PF_TRY
+  Stream* s = S(h);
+  if (ids) *ids = s->AltIds.data();
+  if (val) *val = s->AltVal.data();
+  if (n_tokens) *n_tokens = s->AltK > 0 ? (int32_t)(s->AltIds.size() / (size_t)s->AltK) : 0;
+  if (K) *K = s->AltK;
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_stream_num_alternatives(pf_stream* h, int32_t* n) {
+  PF_TRY
+  Stream* s = S(h);
+  NEED(n);
+  *n = (int32_t)s->Alternatives.size();
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_stream_alternative(pf_stream* h, int32_t i, const int64_t** ids, int32_t* n_ids, double* score, const char** text_utf8,
+                          int32_t* n_tokens) {
+  PF_TRY
+  Stream* s = S(h);
+  PF_CHECK(i >= 0 && i < (int32_t)s->Alternatives.size(), PF_ERR_INVALID_ARG, "alternative index out of range");
+  const Alternative& a = s->Alternatives[(size_t)i];
+  if (ids) *ids = a.ids.data();
+  if (n_ids) *n_ids = (int32_t)a.ids.size();
+  if (score) *score = a.score;
+  if (text_utf8) *text_utf8 = a.res.Text.c_str();
+  if (n_tokens) *n_tokens = (int32_t)a.res.Tokens.size();
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_stream_alternative_token(pf_stream* h, int32_t i, int32_t j, const char** utf8) {
+  PF_TRY
+  Stream* s = S(h);
+  NEED(utf8);
+  PF_CHECK(i >= 0 && i < (int32_t)s->Alternatives.size(), PF_ERR_INVALID_ARG, "alternative index out of range");
+  const Alternative& a = s->Alternatives[(size_t)i];
+  PF_CHECK(j >= 0 && j < (int32_t)a.res.Tokens.size(), PF_ERR_INVALID_ARG, "token index out of range");
+  *utf8 = a.res.Tokens[(size_t)j].c_str();
   return PF_OK;
   PF_CATCH
 }

@@ -1501,7 +1501,7 @@ void Engine::predictor_and_decoder(int B, int T, bool want_logits) {
   logits_ld_ = (int)round_up(V, 4);                 // fp32 rows stay 16-byte aligned for any vocabulary size
   gemm("gemm_vocab", dec_out_, xdn16, D, Md, logits_, logits_ld_, nullptr, 0, nullptr, 0, nullptr, 0, false, 0, 1.f);
   prof_begin("argmax", 0);
-  launch_argmax(stream_, logits_, Md, V, logits_ld_, want_logits ? 2 : 1, ids_dev_, score_buf(Md));
+  launch_argmax(stream_, logits_, Md, V, logits_ld_, argmax_mode(want_logits), ids_dev_, score_buf(Md));
   prof_end("argmax");
   if (bias_branch) seaco_head(B, L, e0, hid32, want_logits);
   join_ts();
@@ -1857,7 +1857,7 @@ void Engine::sensevoice_head(int B, int T, bool want_logits) {
   logits_ld_ = (int)round_up(V, 4);
   gemm("gemm_vocab", ctc_, H16_, D, M, logits_, logits_ld_, nullptr, 0, nullptr, 0, nullptr, 0, false, 0, 1.f);
   prof_begin("argmax", 0);
-  launch_argmax(stream_, logits_, M, V, logits_ld_, want_logits ? 2 : 1, ids_dev_, score_buf(M));
+  launch_argmax(stream_, logits_, M, V, logits_ld_, argmax_mode(want_logits), ids_dev_, score_buf(M));
   prof_end("argmax");
   last_.B = B; last_.L = T; last_.V = V; last_.T = T;
   last_.ids.assign((size_t)M, 0);
@@ -1869,7 +1869,8 @@ void Engine::sensevoice_head(int B, int T, bool want_logits) {
 
 // ------------------------------------------------------------------ decoding extras ---------
 void Engine::set_decode(int flags) {
-  PF_CHECK((flags & ~(PF_DECODE_SCORES | PF_DECODE_CTC)) == 0, PF_ERR_INVALID_ARG, "set_decode: unknown flag bits");
+  PF_CHECK((flags & ~(PF_DECODE_SCORES | PF_DECODE_CTC | PF_DECODE_TOPK)) == 0, PF_ERR_INVALID_ARG, "set_decode: unknown flag bits");
+  if (flags & PF_DECODE_TOPK) flags |= PF_DECODE_SCORES;
   if (flags & PF_DECODE_CTC) {
     PF_CHECK(mc_.kind_id() == 1, PF_ERR_UNSUPPORTED, "PF_DECODE_CTC: only a SenseVoice model has a CTC head");
     flags |= PF_DECODE_SCORES;
@@ -1877,6 +1878,11 @@ void Engine::set_decode(int flags) {
   // the SeACo bias merge replaces rows of the result after the arg-max; their scores would need a path of their own
   PF_CHECK(flags == 0 || !mc_.seaco, PF_ERR_UNSUPPORTED, "PF_DECODE_SCORES: not available for a SeACo model");
   decode_flags_ = flags;
+}
+
+void Engine::set_topk(int k) {
+  PF_CHECK(k >= 1 && k <= PF_TOPK_MAX, PF_ERR_INVALID_ARG, "set_topk: K must be 1 .. " + std::to_string(PF_TOPK_MAX));
+  topk_k_ = k;
 }
 
 float* Engine::score_buf(int64_t rows) {
@@ -1893,6 +1899,22 @@ void Engine::queue_decode_results(int B, int L) {
   const float* sc = (const float*)ws_score_.p;
   last_.scores.resize((size_t)B * L);
   PF_HIP(hipMemcpyAsync(last_.scores.data(), sc, (size_t)B * L * 4, hipMemcpyDeviceToHost, stream_));
+  if (decode_flags_ & PF_DECODE_TOPK) {
+    // the arg-max ran in its store-in-place form (argmax_mode): logits_ holds the log-probs it scanned
+    const int64_t rows = (int64_t)B * L;
+    const int K = topk_k_;
+    const size_t words = HostBatchOut::topk_words(rows, K);
+    ensure(ws_topk_, words * 8);
+    last_.topk.resize(words);
+    last_.topk_k = K;
+    int64_t* ids_o = (int64_t*)ws_topk_.p;
+    float* val_o = (float*)(ids_o + (size_t)rows * K);
+    int32_t* n_o = (int32_t*)(val_o + (size_t)rows * K);
+    prof_begin("topk", 0);
+    launch_topk(stream_, logits_, rows, last_.V, logits_ld_, K, ids_o, val_o, n_o);
+    prof_end("topk");
+    PF_HIP(hipMemcpyAsync(last_.topk.data(), ws_topk_.p, ((size_t)rows * K * 12 + (size_t)rows * 4), hipMemcpyDeviceToHost, stream_));
+  }
   if (!(decode_flags_ & PF_DECODE_CTC)) return;
   if ((int)len.size() != B) len.assign(B, L);
   for (int b = 0; b < B; ++b) len[b] = std::min(std::max(len[b], 0), L);
@@ -1920,6 +1942,7 @@ void Engine::forward_device(const float* speech_dev, int B, int T, bool want_log
   last_logits_ = want_logits;
   last_.decode_flags = decode_flags_;
   last_.scores.clear(); last_.ctc.clear(); last_.ctc_cap = 0;
+  last_.topk.clear(); last_.topk_k = 0;
   if (fp32_mode_) { forward_fp32(speech_dev, B, T, want_logits); return; }
   if (int8_mode_) { forward_int8(speech_dev, B, T, want_logits); return; }
   encoder(speech_dev, B, T);
@@ -2058,6 +2081,24 @@ void Engine::fetch_scores(float* scores, int64_t cap, int32_t* L_out) {
   if (!scores) return;
   PF_CHECK(cap >= need, PF_ERR_CAPACITY, "scores capacity < B*L = " + std::to_string(need));
   if (need > 0) std::memcpy(scores, r.scores.data(), (size_t)need * 4);
+}
+
+void Engine::fetch_topk(int64_t* ids, float* val, int32_t* n, int64_t cap_rows, int32_t* L_out, int32_t* K_out) {
+  PF_HIP(hipStreamSynchronize(stream_));
+  check_async_errors();
+  auto it = t_slots_find(uid_);
+  const HostBatchOut& r = it ? *it : last_;
+  PF_CHECK(r.decode_flags & PF_DECODE_TOPK, PF_ERR_INVALID_ARG, "fetch_topk: PF_DECODE_TOPK was not set for the last forward");
+  if (L_out) *L_out = r.L;
+  if (K_out) *K_out = r.topk_k;
+  if (!ids && !val && !n) return;
+  const int64_t rows = (int64_t)r.B * r.L;
+  PF_CHECK(cap_rows >= rows, PF_ERR_CAPACITY, "topk capacity < B*L = " + std::to_string(rows));
+  if (rows == 0 || r.topk.empty()) return;
+  const size_t K = (size_t)r.topk_k;
+  if (ids) std::memcpy(ids, r.topk_ids(), (size_t)rows * K * 8);
+  if (val) std::memcpy(val, r.topk_val(), (size_t)rows * K * 4);
+  if (n) std::memcpy(n, r.topk_n(), (size_t)rows * 4);
 }
 
 void Engine::fetch_ctc(int64_t* ids, int32_t* first, int32_t* last, float* score, int32_t cap, int32_t* n, int32_t* n_max) {

@@ -130,6 +130,12 @@ class Engine {
   int decode_flags() const { return decode_flags_; }
   void fetch_scores(float* scores, int64_t cap, int32_t* L_out);
   void fetch_ctc(int64_t* ids, int32_t* first, int32_t* last, float* score, int32_t cap, int32_t* n, int32_t* n_max);
+  // TOPK (implies SCORES): the K best (id, log-prob) of every position [B, L, K] by k_topk.hip, right behind the arg-max,
+  // which then stores its log-probs in place (mode 2, the form a logits request already runs).  K: 1 .. PF_TOPK_MAX.
+  void set_topk(int k);
+  int topk() const { return topk_k_; }
+  void fetch_topk(int64_t* ids, float* val, int32_t* n, int64_t cap_rows, int32_t* L_out, int32_t* K_out);
+  void op_topk(const float* x, int64_t rows, int V, int ld, int K, int64_t* ids, float* val, int32_t* n);
   void op_pcm_convert(const void* data, int64_t n_values, const pf_pcm_desc& desc, float* out, int64_t cap, int64_t* n_out);
   void op_ctc_collapse(const int64_t* ids, const float* scores, const int32_t* lens, int B, int T, int blank, int64_t* ids_out,
                        int32_t* first_out, int32_t* last_out, float* score_out, int cap, int32_t* n_out);
@@ -379,6 +385,10 @@ class Engine {
   std::vector<int32_t> ctc_len_;     // the lengths the queued collapse reads (clamped to [0, L]); alive until the next forward
   DevBuf ws_score_, ws_ctc_;         // arg-max log-probs [B * L]; the collapse's len [B] and result block (HostBatchOut::ctc)
   float* score_buf(int64_t rows);    // where the arg-max leaves its winners' values; null without decode flags
+  int topk_k_ = 4;                   // K of PF_DECODE_TOPK
+  DevBuf ws_topk_;                   // the top-k result block (HostBatchOut::topk); allocated with the flag only
+  // the arg-max form of a pipeline head: the top-k kernel reads the log-probs the arg-max leaves in place
+  int argmax_mode(bool want_logits) const { return (want_logits || (decode_flags_ & PF_DECODE_TOPK)) ? 2 : 1; }
   void queue_decode_results(int B, int L);   // behind the ids copy: the scores' copy, the collapse and its copy
   uint64_t uid_ = 0;                 // key of this engine in the per-thread result store
   static uint64_t register_uid();

@@ -254,7 +254,7 @@ void Engine::forward_fp32(const float* speech_dev, int B, int T, bool want_logit
     ensure(ws_dec_, o2);
     logits_ = (float*)((char*)ws_dec_.p + o_lg); ids_dev_ = (int64_t*)((char*)ws_dec_.p + o_ids); logits_ld_ = ldV;
     gemm32(H32_, D, ctc_.w32, D, ctc_.bias, M, V, D, logits_, ldV, nullptr, 0, false, 0, 1.f);
-    launch_argmax(stream_, logits_, M, V, ldV, want_logits ? 2 : 1, ids_dev_, score_buf(M));
+    launch_argmax(stream_, logits_, M, V, ldV, argmax_mode(want_logits), ids_dev_, score_buf(M));
     last_.B = B; last_.L = T; last_.V = V; last_.T = T;
     last_.ids.assign((size_t)M, 0);
     last_.token_num.assign(B, T);
@@ -326,7 +326,7 @@ void Engine::forward_fp32(const float* speech_dev, int B, int T, bool want_logit
   launch_layernorm(stream_, t32, Md, D, dec_after_.g, dec_after_.b, nullptr, 0, xn, D);
   cls32_ = "gemm32_vocab";
   gemm32(xn, D, dec_out_.w32, D, dec_out_.bias, Md, V, D, logits_, ldV, nullptr, 0, false, 0, 1.f);
-  launch_argmax(stream_, logits_, Md, V, ldV, want_logits ? 2 : 1, ids_dev_, score_buf(Md));
+  launch_argmax(stream_, logits_, Md, V, ldV, argmax_mode(want_logits), ids_dev_, score_buf(Md));
   cls32_ = "gemm32_misc";
   if (bias_branch) seaco_head_fp32(B, L, e0, xn, want_logits);      // xn = the ASR decoder's after_norm hidden
   PF_HIP(hipMemcpyAsync(last_.ids.data(), ids_dev_, (size_t)Md * 8, hipMemcpyDeviceToHost, stream_));

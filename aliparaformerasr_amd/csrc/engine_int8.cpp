@@ -246,7 +246,7 @@ void Engine::forward_int8(const float* speech_dev, int B, int T, bool want_logit
     logits_ = (float*)((char*)ws_dec_.p + o_lg); ids_dev_ = (int64_t*)((char*)ws_dec_.p + o_ids); logits_ld_ = ldV;
     qgemm("gemm_vocab", ctc_, true, H32_, nullptr, D, (int)M, logits_, ldV, nullptr, 0, nullptr, 0, nullptr, 0, false, 0, 1.f);
     prof_begin("argmax", 0);
-    launch_argmax(stream_, logits_, M, V, ldV, want_logits ? 2 : 1, ids_dev_, score_buf(M));
+    launch_argmax(stream_, logits_, M, V, ldV, argmax_mode(want_logits), ids_dev_, score_buf(M));
     prof_end("argmax");
     last_.B = B; last_.L = T; last_.V = V; last_.T = T;
     last_.ids.assign((size_t)M, 0);
@@ -358,7 +358,7 @@ void Engine::forward_int8(const float* speech_dev, int B, int T, bool want_logit
     qgemm("gemm_vocab", dec_out_, true, t32, nullptr, D, Md, logits_, ldV, nullptr, 0, nullptr, 0, nullptr, 0, false, 0, 1.f, &dec_after_);
   }
   prof_begin("argmax", 0);
-  launch_argmax(stream_, logits_, Md, V, ldV, want_logits ? 2 : 1, ids_dev_, score_buf(Md));
+  launch_argmax(stream_, logits_, Md, V, ldV, argmax_mode(want_logits), ids_dev_, score_buf(Md));
   prof_end("argmax");
   if (bias_branch) seaco_head(B, L, e0, hid32, want_logits);
   join_ts();

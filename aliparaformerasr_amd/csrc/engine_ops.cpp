@@ -69,6 +69,24 @@ void Engine::op_pcm_convert(const void* data, int64_t n_values, const pf_pcm_des
   PF_HIP(hipStreamSynchronize(stream_));
 }
 
+void Engine::op_topk(const float* x, int64_t rows, int V, int ld, int K, int64_t* ids, float* val, int32_t* n) {
+  PF_HIP(hipSetDevice(device_));
+  if (rows == 0) return;
+  const size_t in = (size_t)rows * ld, out = (size_t)rows * K;
+  // ids (int64), then val | n | x (4-byte)
+  ensure(ws_tmp_, out * 8 + (out + (size_t)rows + in) * 4);
+  int64_t* d_ids = (int64_t*)ws_tmp_.p;
+  float* d_val = (float*)(d_ids + out);
+  int32_t* d_n = (int32_t*)(d_val + out);
+  float* d_x = (float*)(d_n + rows);
+  PF_HIP(hipMemcpyAsync(d_x, x, in * 4, hipMemcpyHostToDevice, stream_));
+  launch_topk(stream_, d_x, rows, V, ld, K, d_ids, d_val, d_n);
+  PF_HIP(hipMemcpyAsync(ids, d_ids, out * 8, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipMemcpyAsync(val, d_val, out * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipMemcpyAsync(n, d_n, (size_t)rows * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipStreamSynchronize(stream_));
+}
+
 void Engine::op_ctc_collapse(const int64_t* ids, const float* scores, const int32_t* lens, int B, int T, int blank,
                              int64_t* ids_out, int32_t* first_out, int32_t* last_out, float* score_out, int cap, int32_t* n_out) {
   PF_HIP(hipSetDevice(device_));

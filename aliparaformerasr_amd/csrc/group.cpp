@@ -171,6 +171,9 @@ void Group::recognize(const float* const* samples, const int64_t* n, int B, cons
   PF_CHECK(B >= 0 && (B == 0 || (samples && n)), PF_ERR_INVALID_ARG, "pf_group_recognize: bad arguments");
   merged_ = HostBatchOut();
   merged_logits_ = want_logits;
+  // the gather carries ids / token counts / log-probs only: the per-position alternatives have no merged form here
+  for (auto& e : eng_)
+    PF_CHECK(!(e->decode_flags() & PF_DECODE_TOPK), PF_ERR_UNSUPPORTED, "pf_group: PF_DECODE_TOPK is not available for a group forward");
   if (B == 0) return;
   int Tg = 0;                                         // the reference pads to the BATCH maximum (PadHelper.cs:25)
   for (int b = 0; b < B; ++b) {

@@ -7,9 +7,11 @@
 #include <cmath>
 #include <cstring>
 
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <queue>
 #include <sstream>
 
 namespace pf {
@@ -441,6 +443,66 @@ std::vector<float> get_file_sample(const std::string& path, double* duration_ms)
   if (duration_ms) *duration_ms = w.duration_ms;
   if (w.sample_rate != 16000) return resample_linear(w.samples, w.sample_rate, 16000, w.channels);
   return w.samples;
+}
+
+// ------------------------------------------------------------------ n-best ---------------
+namespace {
+struct NbNode {
+  double score;
+  std::vector<uint8_t> r;     // ranks (K <= PF_TOPK_MAX)
+  int last;                   // the position the last step raised (children raise positions >= last)
+};
+// true when a comes AFTER b in the list (std::priority_queue keeps the "largest")
+struct NbAfter {
+  bool operator()(const NbNode& a, const NbNode& b) const {
+    if (a.score != b.score) return a.score < b.score;
+    return std::lexicographical_compare(b.r.begin(), b.r.end(), a.r.begin(), a.r.end());
+  }
+};
+double nb_score(const float* val, int L, int K, const std::vector<uint8_t>& r) {
+  double s = 0.0;
+  for (int l = 0; l < L; ++l) s += (double)val[(size_t)l * K + r[(size_t)l]];
+  return s;
+}
+}  // namespace
+
+int host_nbest(const float* val, const int32_t* n, int L, int K, int n_free, int N, int32_t* out_ranks, double* out_scores) {
+  if (!val || !n || !out_ranks || !out_scores) throw Error(PF_ERR_INVALID_ARG, "nbest: null argument");
+  if (L < 1 || K < 1 || K > PF_TOPK_MAX || N < 1 || N > PF_NBEST_MAX || n_free < 0 || n_free > L)
+    throw Error(PF_ERR_INVALID_ARG, "nbest: bad L / K / N / n_free");
+  for (int l = 0; l < L; ++l) {
+    if (n[l] < 0 || n[l] > K) throw Error(PF_ERR_INVALID_ARG, "nbest: n[l] outside 0 .. K");
+    if (n[l] == 0) return 0;                             // a position with no ranked entry: no rank vector exists
+    for (int k = 0; k < n[l]; ++k) {
+      const float v = val[(size_t)l * K + k];
+      if (v != v || v == INFINITY) throw Error(PF_ERR_INVALID_ARG, "nbest: NaN or +inf among the ranked values");
+    }
+  }
+  std::priority_queue<NbNode, std::vector<NbNode>, NbAfter> heap;
+  NbNode root;
+  root.r.assign((size_t)L, 0);
+  root.score = nb_score(val, L, K, root.r);
+  root.last = 0;
+  heap.push(std::move(root));
+  int got = 0;
+  while (got < N && !heap.empty()) {
+    NbNode cur = heap.top();
+    heap.pop();
+    for (int l = 0; l < L; ++l) out_ranks[(size_t)got * L + l] = cur.r[(size_t)l];
+    out_scores[got] = cur.score;
+    ++got;
+    if (got == N) break;
+    for (int l = cur.last; l < n_free; ++l) {
+      if (cur.r[(size_t)l] + 1 >= n[l]) continue;
+      NbNode ch;
+      ch.r = cur.r;
+      ++ch.r[(size_t)l];
+      ch.last = l;
+      ch.score = nb_score(val, L, K, ch.r);              // from scratch: the sum's rounding is that of the definition
+      heap.push(std::move(ch));
+    }
+  }
+  return got;
 }
 
 }  // namespace pf

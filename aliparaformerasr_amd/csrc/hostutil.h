@@ -64,6 +64,15 @@ std::vector<float> resample_linear(const std::vector<float>& src, int sr_in, int
 // 16 kHz — a 16 kHz stereo file is handed over interleaved, exactly as upstream does.
 std::vector<float> get_file_sample(const std::string& path, double* duration_ms);
 
+// ---- n-best list of one utterance from its per-position top-k lists (paraformer_hip.h "Top-k and n-best") ----------
+// val / n: [L, K] / [L] as launch_topk leaves them.  A hypothesis is a rank vector r[0..L) with r[l] < n[l] and r[l] == 0 for
+// l >= n_free; its score is the float64 sum of val[l, r[l]] added from l = 0 up.  Listed by descending score, ties to the
+// lexicographically smaller rank vector; at most N (1 .. 64).  out_ranks [N, L], out_scores [N]; returns how many exist.
+// Exact: a best-first walk in which every vector has ONE parent (its last non-zero rank lowered by one), which never scores
+// lower and never sorts later, so the heap always holds the next hypothesis.  PF_ERR_INVALID_ARG for a ranked value that is
+// NaN or +inf (their sums would not order).
+int host_nbest(const float* val, const int32_t* n, int L, int K, int n_free, int N, int32_t* out_ranks, double* out_scores);
+
 // UTF-8 <-> code points
 std::vector<uint32_t> utf8_decode(const std::string& s);
 std::string utf8_encode(uint32_t cp);

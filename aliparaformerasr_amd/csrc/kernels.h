@@ -351,6 +351,11 @@ void launch_argmax(hipStream_t s, float* x, int64_t rows, int V, int ldx, int mo
 // slots past n_out[b] hold -1 / -1 / -1 / 0.  A token whose slot is >= cap is counted but not stored.
 void launch_ctc_collapse(hipStream_t s, const int64_t* ids, const float* score, const int32_t* len, int B, int T, int blank,
                          int cap, int32_t* n_out, int64_t* ids_out, int32_t* first_out, int32_t* last_out, float* score_out);
+// ------------------------------------------------------------------ top-k ------
+// The K (1 .. 8) best entries of each row of x [rows, V] (row stride ldx >= V) in the arg-max's order (k_topk.hip): larger
+// value first, of equal values the larger index; NaN never ranked.  ids [rows, K] / val [rows, K]: slots past
+// n[row] = min(K, non-NaN entries) hold -1 / -inf.  Every output slot is written.
+void launch_topk(hipStream_t s, const float* x, int64_t rows, int V, int ldx, int K, int64_t* ids, float* val, int32_t* n);
 
 // ---------------------------------------------------------------- PCM intake (k_pcm.hip) ------
 // One utterance of a pcm_to_samples launch: n raw values of `format` (pf_pcm_format) at raw + in_off (bytes, 16-byte aligned)

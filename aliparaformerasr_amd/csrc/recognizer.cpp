@@ -509,11 +509,30 @@ Recognizer::Recognizer(const std::string& model, const std::string& config, cons
 std::shared_ptr<Engine> Recognizer::make_engine() {
   std::shared_ptr<void> img = image_;                // the engine points into the image: it must outlive the engine
   std::shared_ptr<Engine> e(new Engine(ec_), [img](Engine* p) { delete p; });
-  if (decode_flags_) e->set_decode(decode_flags_);
+  if (decode_flags_) { e->set_topk(topk_k_); e->set_decode(decode_flags_); }
   return e;
 }
 
 void Recognizer::SetDecode(int flags) {
+  set_decode_all(flags | (nbest_n_ > 0 ? PF_DECODE_TOPK : 0), topk_k_);
+  user_flags_ = flags;
+}
+
+void Recognizer::SetNBest(int N, int K) {
+  if (N < 0 || N > PF_NBEST_MAX || K < 0 || K > PF_TOPK_MAX) throw Error(PF_ERR_INVALID_ARG, "SetNBest: N is 0 .. 64, K is 0 .. 8");
+  if (N == 0) {
+    set_decode_all(user_flags_ & ~PF_DECODE_TOPK, topk_k_);
+    user_flags_ = user_flags_ & ~PF_DECODE_TOPK;
+    nbest_n_ = 0;
+    return;
+  }
+  // frames of a CTC model are not independent tokens: a sum over frame ranks is no hypothesis score
+  if (N > 1 && engine_kind_ == "sensevoicesmall") throw Error(PF_ERR_UNSUPPORTED, "SetNBest: N > 1 needs a paraformer model (SenseVoice offers K alone)");
+  set_decode_all(user_flags_ | PF_DECODE_TOPK, K == 0 ? 4 : K);
+  nbest_n_ = N;
+}
+
+void Recognizer::set_decode_all(int flags, int k) {
   std::vector<std::shared_ptr<Engine>> es;
   {
     std::lock_guard<std::mutex> lk(mu_);
@@ -526,7 +545,8 @@ void Recognizer::SetDecode(int flags) {
   for (size_t i = 0; i < es.size(); ++i) {
     std::lock_guard<std::mutex> lk(es[i]->mutex());
     es[i]->set_decode(flags);
-    if (i == 0) decode_flags_ = es[0]->decode_flags();
+    es[i]->set_topk(k);
+    if (i == 0) { decode_flags_ = es[0]->decode_flags(); topk_k_ = k; }
   }
 }
 
@@ -891,6 +911,7 @@ void Recognizer::Forward(const std::vector<Stream*>& streams) {
     const int W = mc.feat_dim;
     const int B = (int)streams.size();
     if (e->decode_flags() != decode_flags_) e->set_decode(decode_flags_);
+    if (e->topk() != topk_k_) e->set_topk(topk_k_);
     const int dflags = e->decode_flags();
     fc.lap(0);
     if (!all_dev && sv) {
@@ -968,6 +989,8 @@ void Recognizer::Forward(const std::vector<Stream*>& streams) {
     const int P = out.cif_peak_len;                                    // 3*Tmax for timestamp models (:172-183)
     std::vector<float> peak((size_t)B * std::max(P, 1));
     if (P > 0) { out.cif_peak = peak.data(); out.cif_peak_cap = (int64_t)peak.size(); }
+    std::vector<int32_t> tnum;                                         // the n-best list varies only below an utterance's own count
+    if (dflags & PF_DECODE_TOPK) { tnum.resize(B); out.token_num = tnum.data(); }
     e->fetch(&out);
     // decoding extras (SetDecode): host copies of what the forward left beside the ids
     std::vector<float> scores;
@@ -980,17 +1003,30 @@ void Recognizer::Forward(const std::vector<Stream*>& streams) {
       c_cap = std::max(n_max, 1);
       c_ids.resize((size_t)B * c_cap); c_first.resize(c_ids.size()); c_last.resize(c_ids.size()); c_score.resize(c_ids.size());
       e->fetch_ctc(c_ids.data(), c_first.data(), c_last.data(), c_score.data(), c_cap, nullptr, nullptr);
-    } else if (dflags & PF_DECODE_SCORES) {
+    }
+    if ((dflags & PF_DECODE_SCORES) && (!(dflags & PF_DECODE_CTC) || (dflags & PF_DECODE_TOPK))) {
       scores.resize((size_t)B * std::max(L, 1));
       e->fetch_scores(scores.data(), (int64_t)scores.size(), nullptr);
     }
+    std::vector<int64_t> k_ids; std::vector<float> k_val; std::vector<int32_t> k_n;
+    int K = 0;
+    if (dflags & PF_DECODE_TOPK) {
+      int32_t k = 0;
+      e->fetch_topk(nullptr, nullptr, nullptr, 0, nullptr, &k);
+      K = k;
+      const size_t rows = (size_t)B * std::max(L, 1);
+      k_ids.resize(rows * K); k_val.resize(rows * K); k_n.resize(rows);
+      e->fetch_topk(k_ids.data(), k_val.data(), k_n.data(), (int64_t)rows, nullptr, nullptr);
+    }
+    const int nbest = nbest_n_;
+    const bool want_scores = (dflags & ~PF_DECODE_TOPK) == PF_DECODE_SCORES && (!(dflags & PF_DECODE_TOPK) || (user_flags_ & PF_DECODE_SCORES));
     fc.lap(5);
     lease.release();                      // the device work of this call is over: the text stage below needs no engine
     for (int b = 0; b < B; ++b) {
       Stream* s = streams[b];
       s->Tokens.assign(ids.begin() + (size_t)b * out.l_cap, ids.begin() + (size_t)b * out.l_cap + L);   // :187
       s->Scores.clear();
-      if (dflags == PF_DECODE_SCORES) s->Scores.assign(scores.begin() + (size_t)b * L, scores.begin() + (size_t)b * L + L);
+      if (want_scores) s->Scores.assign(scores.begin() + (size_t)b * L, scores.begin() + (size_t)b * L + L);
       s->Timestamps.reserve(s->Timestamps.size() + (size_t)L);
       if (dflags & PF_DECODE_CTC) {
         // the collapsed hypothesis instead of the per-frame ids: one [begin, end] pair per token from its first / last frame
@@ -1007,6 +1043,39 @@ void Recognizer::Forward(const std::vector<Stream*>& streams) {
         for (auto& t2 : ts) s->Timestamps.push_back(t2);
       } else {
         for (int l = 0; l < L; ++l) s->Timestamps.push_back({0, 0});                                    // :151,:188
+      }
+      s->AltIds.clear(); s->AltVal.clear(); s->AltK = 0; s->Alternatives.clear();
+      if (K > 0 && L > 0) {
+        const size_t r0 = (size_t)b * L;
+        s->AltK = K;
+        if (dflags & PF_DECODE_CTC) {
+          // per collapsed token: the alternatives of the run's peak frame — the first frame whose log-prob is the token's
+          // score bit for bit
+          const size_t o = (size_t)b * c_cap;
+          for (int k = 0; k < c_n[b]; ++k) {
+            int t = c_first[o + k];
+            for (int u = c_first[o + k]; u <= c_last[o + k]; ++u)
+              if (std::memcmp(&scores[r0 + u], &c_score[o + k], 4) == 0) { t = u; break; }
+            s->AltIds.insert(s->AltIds.end(), k_ids.begin() + (r0 + t) * K, k_ids.begin() + (r0 + t + 1) * K);
+            s->AltVal.insert(s->AltVal.end(), k_val.begin() + (r0 + t) * K, k_val.begin() + (r0 + t + 1) * K);
+          }
+        } else {
+          s->AltIds.assign(k_ids.begin() + r0 * K, k_ids.begin() + (r0 + L) * K);
+          s->AltVal.assign(k_val.begin() + r0 * K, k_val.begin() + (r0 + L) * K);
+        }
+        if (nbest > 1 && !sv) {
+          std::vector<int32_t> ranks((size_t)nbest * L);
+          std::vector<double> sc((size_t)nbest);
+          const int n_free = std::min(L, std::max(tnum[b], 0));
+          const int got = host_nbest(k_val.data() + r0 * K, k_n.data() + r0, L, K, n_free, nbest, ranks.data(), sc.data());
+          s->Alternatives.resize((size_t)got);
+          for (int i = 0; i < got; ++i) {
+            Alternative& a = s->Alternatives[(size_t)i];
+            a.score = sc[(size_t)i];
+            a.ids.resize((size_t)L);
+            for (int l = 0; l < L; ++l) a.ids[(size_t)l] = k_ids[(r0 + l) * K + ranks[(size_t)i * L + l]];
+          }
+        }
       }
       if (all_dev && sv && s->Tokens.size() <= 2) {
         // quirk Q8 on the device form: the reference has prepended the query rows to Speech IN PLACE, and a stream whose
@@ -1042,6 +1111,8 @@ void Recognizer::GetResults(const std::vector<Stream*>& streams) {
   FwdClock fc;
   std::vector<ResultEntity> out;
   for (Stream* s : streams) out.push_back(decode_multi_one(token_table_, s->Tokens, s->Timestamps));
+  for (Stream* s : streams)                                   // the n-best list goes through the same DecodeMulti
+    for (Alternative& a : s->Alternatives) a.res = decode_multi_one(token_table_, a.ids, s->Timestamps);
   fc.lap(7);
   fwd_report();
   {

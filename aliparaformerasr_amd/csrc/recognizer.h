@@ -73,6 +73,13 @@ struct TokenTable {
   std::vector<uint8_t> kind;
 };
 ResultEntity decode_multi_one(const TokenTable& table, const std::vector<int64_t>& ids, const TsList& timestamps);
+// One entry of a stream's n-best list (Recognizer::SetNBest): the ids of every position, the float64 sum of their log-probs
+// and what DecodeMulti makes of them
+struct Alternative {
+  std::vector<int64_t> ids;
+  double score = 0;
+  ResultEntity res;
+};
 // time_stamp_lfr6_onnx (OfflineRecognizer.cs:200-302); throws PF_ERR_RECOGNITION where the C#
 // would throw inside Forward's try block.
 TsList time_stamp_lfr6(const float* us_cif_peak, int n, const std::vector<int64_t>& tokens);
@@ -130,6 +137,12 @@ class Stream {
   std::vector<int64_t> Tokens{0, 0};                          // OfflineStream.cs:26
   TsList Timestamps;
   std::vector<float> Scores;                                  // of the last GetResults (Recognizer::SetDecode); empty without a flag
+  // of the last GetResults (Recognizer::SetNBest); empty without it.  TokenAlternatives: AltK (id, log-prob) pairs per entry
+  // of Tokens, [n_tokens, AltK], slots past a position's count -1 / -inf
+  std::vector<int64_t> AltIds;
+  std::vector<float> AltVal;
+  int AltK = 0;
+  std::vector<Alternative> Alternatives;
   void RemoveChunk();                                         // OfflineStream.cs:69-79
   bool disposed = false;
   std::shared_ptr<Recognizer> owner;
@@ -152,6 +165,9 @@ class Recognizer : public std::enable_shared_from_this<Recognizer> {
   // PF_DECODE_CTC (SenseVoice) Forward leaves the collapsed ids, [begin, end] milliseconds per token and the token scores
   // in the streams; DecodeMulti, RemoveChunk and the Q8 branch run unchanged on those Tokens.
   void SetDecode(int flags);
+  // Alternatives (paraformer_hip.h "Top-k and n-best"): N = 0 off; N >= 1: PF_DECODE_TOPK with K (0 = 4) on every engine beside
+  // the SetDecode flags — TokenAlternatives in every stream, and for paraformer with N > 1 the n-best list
+  void SetNBest(int N, int K);
   bool disposed() const { return disposed_.load(); }
   // engine 0 (nullptr once disposed): what pf_recognizer_engine hands out; callers lock engine->mutex() themselves
   std::shared_ptr<Engine> engine() { std::lock_guard<std::mutex> lk(mu_); return engines_.empty() ? nullptr : engines_[0]; }
@@ -246,7 +262,11 @@ class Recognizer : public std::enable_shared_from_this<Recognizer> {
   std::vector<std::vector<int32_t>> hotwords_;
   uint64_t uid_ = 0;                                          // key of this recognizer in the per-thread result store
   std::atomic<bool> disposed_{false};
-  std::atomic<int> decode_flags_{0};
+  std::atomic<int> decode_flags_{0};                          // what the engines run: user_flags_ | TOPK while nbest_n_ > 0
+  std::atomic<int> user_flags_{0};                            // as given to SetDecode
+  std::atomic<int> nbest_n_{0};
+  std::atomic<int> topk_k_{4};
+  void set_decode_all(int flags, int k);
   friend class Stream;
 };
 

@@ -45,6 +45,13 @@ struct HostBatchOut { // results of a forward, host side
   const int32_t* ctc_last() const { return ctc_first() + (size_t)B * ctc_cap; }
   const float* ctc_score() const { return (const float*)(ctc_last() + (size_t)B * ctc_cap); }
   const int32_t* ctc_n() const { return ctc_last() + 2 * (size_t)B * ctc_cap; }
+  // top-k alternatives as the kernel leaves them, one block: ids [B * L, K] int64 | val [B * L, K] fp32 | n [B * L] int32
+  std::vector<int64_t> topk;
+  int topk_k = 0;
+  static size_t topk_words(int64_t rows, int K) { return (size_t)rows * K + ((size_t)rows * K * 4 + (size_t)rows * 4 + 7) / 8; }
+  const int64_t* topk_ids() const { return topk.data(); }
+  const float* topk_val() const { return (const float*)(topk.data() + (size_t)B * L * topk_k); }
+  const int32_t* topk_n() const { return (const int32_t*)(topk_val() + (size_t)B * L * topk_k); }
 };
 
 // rendezvous of the G worker threads with a max-reduction; abort() releases every waiter with an Error

@@ -31,8 +31,36 @@ class CtcResult:
                         self.score[b, :k].tolist()))
 
 
+class TopkResult:
+    """The K best entries of every position (PF_DECODE_TOPK): ids [B, L, K] int64, val [B, L, K] float32 log-probs,
+    n [B, L] ranked entries; slots past n hold -1 / -inf.  Order: larger value first, of equal values the larger id."""
+
+    def __init__(self, ids, val, n):
+        self.ids, self.val, self.n = ids, val, n
+        self.K = ids.shape[-1]
+
+
+def host_nbest(val, n, n_free, n_best, ids=None):
+    """The exact n-best list of one utterance from its top-k lists val [L, K], n [L] (pf_host_nbest): (ranks [m, L] int32,
+    scores [m] float64) with m <= n_best, by descending score, ties to the lexicographically smaller rank vector;
+    positions l >= n_free keep rank 0.  ids [L, K] (optional): the hypotheses' ids [m, L] are returned as a third item."""
+    v = _f32(val)
+    nn = np.ascontiguousarray(n, dtype=np.int32)
+    L, K = v.shape
+    ranks = np.zeros((n_best, L), np.int32)
+    scores = np.zeros(n_best, np.float64)
+    got = C.c_int32()
+    N.check(N.load().pf_host_nbest(None, _fp(v), _i32p(nn), L, K, int(n_free), int(n_best), _i32p(ranks),
+                                   scores.ctypes.data_as(C.POINTER(C.c_double)), got))
+    ranks, scores = ranks[: got.value].copy(), scores[: got.value].copy()
+    if ids is None:
+        return ranks, scores
+    y = np.asarray(ids)
+    return ranks, scores, y[np.arange(L)[None, :], ranks]
+
+
 class BatchResult:
-    def __init__(self, token_ids, token_num, L, V, logits=None, cif_peak=None, scores=None, ctc=None):
+    def __init__(self, token_ids, token_num, L, V, logits=None, cif_peak=None, scores=None, ctc=None, topk=None):
         self.token_ids = token_ids      # [B, L] int64
         self.token_num = token_num      # [B] int32
         self.L = L
@@ -41,6 +69,7 @@ class BatchResult:
         self.cif_peak = cif_peak        # [B, 3*Tmax] float32 us_cif_peak (timestamp models) or None
         self.scores = scores            # [B, L] float32 log-prob of token_ids (Engine.set_decode) or None
         self.ctc = ctc                  # CtcResult (Engine.set_decode(PF_DECODE_CTC)) or None
+        self.topk = topk                # TopkResult (Engine.set_decode(PF_DECODE_TOPK)) or None
 
 
 def _build_config(weights, weights_path, weights_device_ptr, weights_bytes, cmvn, mvn_path, device, dither, snip_edges,
@@ -106,6 +135,17 @@ def _fetch_decode(lib, h, B, L, flags):
     return scores, ctc
 
 
+def _fetch_topk(lib, h, B, L):
+    k = C.c_int32()
+    N.check(lib.pf_fetch_topk(h, None, None, None, 0, None, k))
+    K = k.value
+    ids = np.zeros((B, L, K), np.int64)
+    val = np.zeros((B, L, K), np.float32)
+    n = np.zeros((B, L), np.int32)
+    N.check(lib.pf_fetch_topk(h, ids.ctypes.data_as(C.POINTER(C.c_int64)), _fp(val), _i32p(n), B * L, None, None))
+    return TopkResult(ids, val, n)
+
+
 def _collect_result(lib, fetch_fn, call, B, want_logits, decode=None):
     """The learn-L-then-fetch protocol shared by pf_engine and pf_group handles.  decode = (engine handle, flags):
     also the decoding extras of an engine with Engine.set_decode flags."""
@@ -131,8 +171,11 @@ def _collect_result(lib, fetch_fn, call, B, want_logits, decode=None):
     scores = ctc = None
     if decode is not None and decode[1]:
         scores, ctc = _fetch_decode(lib, decode[0], B, L, decode[1])
+    topk = None
+    if decode is not None and decode[1] & N.PF_DECODE_TOPK:
+        topk = _fetch_topk(lib, decode[0], B, L)
     N.check(fetch_fn(C.byref(out)))
-    return BatchResult(ids[:, :L].copy(), tn, L, V, logits, peak, scores, ctc)
+    return BatchResult(ids[:, :L].copy(), tn, L, V, logits, peak, scores, ctc, topk)
 
 
 class Engine:
@@ -197,7 +240,30 @@ class Engine:
         """Decoding extras of the forwards that follow (_native.PF_DECODE_SCORES | PF_DECODE_CTC; 0 = off, the reference
         behaviour): BatchResult.scores, and for a SenseVoice model BatchResult.ctc."""
         N.check(self._lib.pf_engine_set_decode(self._h, int(flags)))
-        self._decode = int(flags) | (N.PF_DECODE_SCORES if int(flags) & N.PF_DECODE_CTC else 0)
+        self._decode = int(flags) | (N.PF_DECODE_SCORES if int(flags) & (N.PF_DECODE_CTC | N.PF_DECODE_TOPK) else 0)
+
+    def set_topk(self, k: int):
+        """K of PF_DECODE_TOPK (1 .. _native.PF_TOPK_MAX, default 4) for the forwards that follow."""
+        N.check(self._lib.pf_engine_set_topk(self._h, int(k)))
+
+    def fetch_topk(self, B: int) -> TopkResult:
+        """The top-k lists of the calling thread's last forward of B utterances (before the fetch that takes its ids)."""
+        L = C.c_int32()
+        N.check(self._lib.pf_fetch_topk(self._h, None, None, None, 0, L, None))
+        return _fetch_topk(self._lib, self._h, B, L.value)
+
+    host_nbest = staticmethod(host_nbest)
+
+    def op_topk(self, x, K=4, V=None) -> TopkResult:
+        """The pipeline's top-k kernel on caller data: x [rows, ld], the first V (default ld) entries of each row."""
+        a = _f32(x)
+        rows, ld = a.shape
+        V = ld if V is None else V
+        ids = np.zeros((rows, K), np.int64)
+        val = np.zeros((rows, K), np.float32)
+        n = np.zeros(rows, np.int32)
+        N.check(self._lib.pf_op_topk(self._h, _fp(a), rows, V, ld, K, ids.ctypes.data_as(C.POINTER(C.c_int64)), _fp(val), _i32p(n)))
+        return TopkResult(ids, val, n)
 
     def op_ctc_collapse(self, ids, scores, lens, blank=0, cap=None) -> CtcResult:
         """The pipeline's CTC collapse kernel on caller data: ids / scores [B, T], lens [B]."""

@@ -1,7 +1,7 @@
 """Command-line harness mirroring AliParaformerAsr.Examples (`-type offline` and `-type online`).
 
     python -m aliparaformerasr_amd.examples -type offline -method batch -base <dir> -model <name> \
-        [-accuracy int8] [-threads 2] [-decode ctc|frames] [-intake host|device] -files a.wav b.wav
+        [-accuracy int8] [-threads 2] [-decode ctc|frames] [-intake host|device] [-nbest N [-topk K]] -files a.wav b.wav
     python -m aliparaformerasr_amd.examples -type online -method one -base <dir> -model <name> -files a.wav
 
 Mirrors (file:line in /root/reference/AliParaformerAsr.Examples):
@@ -23,7 +23,9 @@ Not in the reference: `-decode ctc` (offline, SenseVoice models) prints the CTC-
 timestamps (OfflineRecognizer.SetDecode); `-decode frames`, the default, is the reference's one id per frame.
 `-intake device` (offline) reads only the wav header on the host (pf_host_wav_info) and hands the payload to
 OfflineStream.AddPcm raw: decode, down-mix and resample run on the device and give the samples GetFileSample gives;
-`-intake host`, the default, is the path above, untouched."""
+`-intake host`, the default, is the path above, untouched.
+`-nbest N [-topk K]` (offline, paraformer models; OfflineRecognizer.SetNBest) prints under each result line the N best
+hypotheses, one `nbest[i] score:<sum of log-probs> text:<text>` line each, best first; line 0 is the result itself."""
 from __future__ import annotations
 
 import ctypes as C
@@ -124,8 +126,12 @@ def _result_line(r) -> str:
     return '{"text": "%s","tokens":[%s],"timestamps":[%s]}' % (r.Text, toks, ts)
 
 
+def _nbest_lines(stream) -> list:
+    return ['nbest[%d] score:%.6f text:%s' % (i, a.Score, a.Text) for i, a in enumerate(stream.Alternatives)]
+
+
 def offline_recognizer(method="one", model="paraformer-seaco-large-zh-timestamp-onnx-offline", accuracy="int8",
-                       threads=2, files=None, base=None, out=sys.stdout, decode="frames", intake="host"):
+                       threads=2, files=None, base=None, out=sys.stdout, decode="frames", intake="host", nbest=0, topk=4):
     from .offline_recognizer import OfflineRecognizer
     base = base or os.getcwd()
     sel = select_model_files(base, model, accuracy)
@@ -136,6 +142,8 @@ def offline_recognizer(method="one", model="paraformer-seaco-large-zh-timestamp-
     rec = OfflineRecognizer(threadsNum=threads, **sel)
     if decode == "ctc":
         rec.SetDecode(ctc=True)
+    if nbest:
+        rec.SetNBest(nbest, topk)
     print("init_models_elapsed_milliseconds:%s" % ((time.perf_counter() - t0) * 1e3), file=out)
     if not files:
         files = []
@@ -172,7 +180,10 @@ def offline_recognizer(method="one", model="paraformer-seaco-large-zh-timestamp-
                 add(st, s)
                 r = rec.GetResult(st)
                 results.append(r)
-                print(p, file=out); print(_result_line(r), file=out); print("", file=out)
+                print(p, file=out); print(_result_line(r), file=out)
+                for ln in _nbest_lines(st) if nbest else ():
+                    print(ln, file=out)
+                print("", file=out)
         elif method == "batch":
             streams = []
             for s in samples:
@@ -180,8 +191,11 @@ def offline_recognizer(method="one", model="paraformer-seaco-large-zh-timestamp-
                 add(st, s)
                 streams.append(st)
             results = rec.GetResults(streams)
-            for p, r in zip(paths, results):
-                print(p, file=out); print(_result_line(r), file=out); print("", file=out)
+            for p, r, st in zip(paths, results, streams):
+                print(p, file=out); print(_result_line(r), file=out)
+                for ln in _nbest_lines(st) if nbest else ():
+                    print(ln, file=out)
+                print("", file=out)
     except Exception as ex:          # the reference prints the message and carries on to the timing lines
         print(str(ex), file=out)
     rec.Dispose()
@@ -312,6 +326,16 @@ def parse_args(argv, env=None):
             if i >= len(argv) or argv[i].lower() not in ("host", "device"):
                 raise ValueError("The intake type must be host or device")
             cfg["intake"] = argv[i].lower()
+        elif a in ("-nbest", "-topk"):
+            lo, hi = (1, N.PF_NBEST_MAX) if a == "-nbest" else (1, N.PF_TOPK_MAX)
+            try:
+                i += 1
+                v = int(argv[i])
+            except (IndexError, ValueError):
+                v = 0
+            if not lo <= v <= hi:
+                raise ValueError("The %s value must be an integer from %d to %d" % (a[1:], lo, hi))
+            cfg[a[1:]] = v
         elif a == "-threads":
             try:
                 i += 1
@@ -329,6 +353,10 @@ def parse_args(argv, env=None):
         i += 1
     if cfg["recognizerType"] is None:
         raise ValueError("You must specify the recognizer type (-type online/offline)")
+    if "topk" in cfg and "nbest" not in cfg:
+        raise ValueError("-topk goes with -nbest")
+    if "nbest" in cfg and cfg["recognizerType"] != "offline":
+        raise ValueError("-nbest is an offline option")
     return cfg
 
 
@@ -345,7 +373,8 @@ def main(argv=None):
                           cfg["modelBasePath"] or None)
     elif cfg["recognizerType"] == "offline":
         offline_recognizer(cfg["methodType"], cfg["modelName"], cfg["modelAccuracy"], cfg["threads"], cfg["files"],
-                           cfg["modelBasePath"] or None, decode=cfg.get("decode", "frames"), intake=cfg.get("intake", "host"))
+                           cfg["modelBasePath"] or None, decode=cfg.get("decode", "frames"), intake=cfg.get("intake", "host"),
+                           nbest=cfg.get("nbest", 0), topk=cfg.get("topk", 4))
     else:
         print("the recognizer type must be online or offline")
         return 2

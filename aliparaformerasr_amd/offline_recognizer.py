@@ -65,6 +65,16 @@ class OfflineRecognizerResultEntity:
 
 
 @dataclass
+class Alternative:
+    """One entry of OfflineStream.Alternatives: the ids of every position, Score = the sum of their log-probs, and the Text /
+    Tokens DecodeMulti makes of them."""
+    Ids: List[int] = field(default_factory=list)
+    Score: float = 0.0
+    Text: str = ""
+    Tokens: List[str] = field(default_factory=list)
+
+
+@dataclass
 class FrontendConfEntity:
     """Model/FrontendConfEntity.cs:6-28 (defaults included)."""
     fs: int = 16000
@@ -175,6 +185,35 @@ class OfflineStream:
         return [p[i] for i in range(n.value)]
 
     @property
+    def TokenAlternatives(self) -> List[List[tuple]]:
+        """Per entry of Tokens the K best (id, log-prob) pairs of the last GetResults, best first (OfflineRecognizer.SetNBest;
+        empty without it).  Slots a position could not fill hold (-1, -inf)."""
+        pi, pv = C.POINTER(C.c_int64)(), C.POINTER(C.c_float)()
+        n, k = C.c_int32(), C.c_int32()
+        _ck(self._lib.pf_stream_token_alternatives(self._h, C.byref(pi), C.byref(pv), n, k))
+        K = k.value
+        return [[(pi[t * K + j], pv[t * K + j]) for j in range(K)] for t in range(n.value)]
+
+    @property
+    def Alternatives(self) -> List["Alternative"]:
+        """The n-best list of the last GetResults (paraformer, OfflineRecognizer.SetNBest with N > 1; else empty): by
+        descending Score; entry 0 is the result itself."""
+        n = C.c_int32()
+        _ck(self._lib.pf_stream_num_alternatives(self._h, n))
+        out = []
+        for i in range(n.value):
+            p, k, sc, txt, nt = C.POINTER(C.c_int64)(), C.c_int32(), C.c_double(), C.c_char_p(), C.c_int32()
+            _ck(self._lib.pf_stream_alternative(self._h, i, C.byref(p), k, C.byref(sc), C.byref(txt), nt))
+            toks = []
+            for j in range(nt.value):
+                t = C.c_char_p()
+                _ck(self._lib.pf_stream_alternative_token(self._h, i, j, C.byref(t)))
+                toks.append((t.value or b"").decode("utf-8"))
+            out.append(Alternative(Ids=[p[m] for m in range(k.value)], Score=sc.value,
+                                   Text=(txt.value or b"").decode("utf-8"), Tokens=toks))
+        return out
+
+    @property
     def Timestamps(self) -> List[List[int]]:
         n = C.c_int32()
         _ck(self._lib.pf_stream_num_timestamps(self._h, n))
@@ -267,6 +306,13 @@ class OfflineRecognizer:
         scores alone: Scores is the log-prob of every position of Tokens; Tokens / Timestamps stay as they are."""
         flags = (N.PF_DECODE_CTC if ctc else 0) | (N.PF_DECODE_SCORES if scores else 0)
         _ck(self._lib.pf_recognizer_set_decode(self._h, flags))
+
+    def SetNBest(self, N: int, K: int = 4) -> None:
+        """Alternatives for every GetResults that follows (off by default; N = 0 turns them off again).  Each stream then
+        carries TokenAlternatives, the K (1 .. 8) best (id, log-prob) pairs per token, and — paraformer models, N > 1 —
+        Alternatives, the exact N-best (<= 64) hypotheses with their scores.  Tokens, Timestamps, Scores and the result
+        text stay as they are."""
+        _ck(self._lib.pf_recognizer_set_nbest(self._h, int(N), int(K)))
 
     def GetResult(self, stream: OfflineStream) -> OfflineRecognizerResultEntity:
         return self.GetResults([stream])[0]

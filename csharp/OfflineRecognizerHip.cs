@@ -141,6 +141,51 @@ namespace AliParaformerAsr.Hip
             }
         }
 
+        /// <summary>Not in the reference: per entry of Tokens the K best (id, log-prob) pairs of the last GetResults, best first
+        /// (OfflineRecognizer.SetNBest; empty without it).  Slots a position could not fill hold (-1, -inf).</summary>
+        public List<(long Id, float LogProb)[]> TokenAlternatives
+        {
+            get
+            {
+                ParaformerHip.Check(ParaformerHip.pf_stream_token_alternatives(Handle, out IntPtr pi, out IntPtr pv, out int n, out int k));
+                var ids = new long[n * k]; var val = new float[n * k];
+                if (n * k > 0) { Marshal.Copy(pi, ids, 0, n * k); Marshal.Copy(pv, val, 0, n * k); }
+                var r = new List<(long, float)[]>(n);
+                for (int t = 0; t < n; t++)
+                {
+                    var row = new (long, float)[k];
+                    for (int j = 0; j < k; j++) row[j] = (ids[t * k + j], val[t * k + j]);
+                    r.Add(row);
+                }
+                return r;
+            }
+        }
+
+        /// <summary>Not in the reference: the n-best list of the last GetResults (paraformer models, SetNBest with N &gt; 1; else
+        /// empty), by descending Score; entry 0 is the result itself.</summary>
+        public List<Alternative> Alternatives
+        {
+            get
+            {
+                ParaformerHip.Check(ParaformerHip.pf_stream_num_alternatives(Handle, out int n));
+                var r = new List<Alternative>(n);
+                for (int i = 0; i < n; i++)
+                {
+                    ParaformerHip.Check(ParaformerHip.pf_stream_alternative(Handle, i, out IntPtr p, out int k, out double score,
+                                                                            out IntPtr txt, out int nt));
+                    var a = new Alternative { Ids = new long[k], Score = score, Text = Marshal.PtrToStringUTF8(txt) ?? "" };
+                    if (k > 0) Marshal.Copy(p, a.Ids, 0, k);
+                    for (int j = 0; j < nt; j++)
+                    {
+                        ParaformerHip.Check(ParaformerHip.pf_stream_alternative_token(Handle, i, j, out IntPtr t));
+                        a.Tokens.Add(Marshal.PtrToStringUTF8(t) ?? "");
+                    }
+                    r.Add(a);
+                }
+                return r;
+            }
+        }
+
         public List<int[]> Timestamps                                           // OfflineStream.cs:33
         {
             get
@@ -172,6 +217,16 @@ namespace AliParaformerAsr.Hip
         ~OfflineStream() { if (Handle != IntPtr.Zero) { ParaformerHip.pf_stream_free(Handle); Handle = IntPtr.Zero; } }
     }
 
+    /// <summary>One entry of OfflineStream.Alternatives: the ids of every position, Score = the sum of their log-probs, and the
+    /// Text / Tokens DecodeMulti makes of them.</summary>
+    public sealed class Alternative
+    {
+        public long[] Ids = new long[0];
+        public double Score;
+        public string Text = "";
+        public List<string> Tokens = new List<string>();
+    }
+
     public sealed class OfflineRecognizer : IDisposable
     {
         private IntPtr _r;
@@ -195,6 +250,12 @@ namespace AliParaformerAsr.Hip
         public void SetDecode(bool ctc = false, bool scores = false)
             => ParaformerHip.Check(ParaformerHip.pf_recognizer_set_decode(_r, (ctc ? ParaformerHip.PF_DECODE_CTC : 0) |
                                                                               (scores ? ParaformerHip.PF_DECODE_SCORES : 0)));
+
+        /// <summary>Not in the reference: alternatives for every GetResults that follows (off by default; N = 0 turns them off
+        /// again).  Each stream then carries TokenAlternatives, the K (1 .. 8) best (id, log-prob) pairs per token, and —
+        /// paraformer models, N &gt; 1 — Alternatives, the exact N-best (&lt;= 64) hypotheses with their scores.  Tokens,
+        /// Timestamps, Scores and the result text stay as they are.</summary>
+        public void SetNBest(int N, int K = 4) => ParaformerHip.Check(ParaformerHip.pf_recognizer_set_nbest(_r, N, K));
 
         public OfflineStream CreateOfflineStream()
         {

@@ -86,6 +86,15 @@ namespace AliParaformerAsr.Native
         [DllImport(Lib)] internal static extern int pf_fetch_scores(IntPtr e, [Out] float[]? scores, long cap, out int L);
         [DllImport(Lib)] internal static extern int pf_fetch_ctc(IntPtr e, [Out] long[]? ids, [Out] int[]? first, [Out] int[]? last,
                                                                 [Out] float[]? score, int cap, [Out] int[]? n, out int nMax);
+        // top-k and n-best (additions to ABI 6): PF_DECODE_TOPK keeps the K (1 .. PF_TOPK_MAX, default 4) best (id, log-prob)
+        // pairs of every position, larger value first and of equal values the larger id; pf_host_nbest turns one utterance's
+        // lists into its exact N-best rank vectors (N <= PF_NBEST_MAX)
+        internal const int PF_DECODE_TOPK = 8, PF_TOPK_MAX = 8, PF_NBEST_MAX = 64;
+        [DllImport(Lib)] internal static extern int pf_engine_set_topk(IntPtr e, int k);
+        [DllImport(Lib)] internal static extern int pf_fetch_topk(IntPtr e, [Out] long[]? ids, [Out] float[]? val, [Out] int[]? n, long capRows,
+                                                                 out int L, out int K);
+        [DllImport(Lib)] internal static extern int pf_host_nbest(long[]? ids, float[] val, int[] n, int L, int K, int nFree, int N,
+                                                                 [Out] int[] outRanks, [Out] double[] outScores, out int nOut);
 
         // PCM intake (additions to ABI 6): raw interleaved values, decoded / down-mixed / resampled on the device in front of the
         // fbank, bit for bit what GetFileSample (Examples/Utils/AudioHelper.cs:12-32) returns; nValues counts interleaved values
@@ -134,6 +143,12 @@ namespace AliParaformerAsr.Native
         [DllImport(Lib)] internal static extern int pf_stream_tokens(IntPtr s, out IntPtr ids, out int n);
         [DllImport(Lib)] internal static extern int pf_recognizer_set_decode(IntPtr r, int flags);
         [DllImport(Lib)] internal static extern int pf_stream_scores(IntPtr s, out IntPtr scores, out int n);
+        [DllImport(Lib)] internal static extern int pf_recognizer_set_nbest(IntPtr r, int N, int K);
+        [DllImport(Lib)] internal static extern int pf_stream_token_alternatives(IntPtr s, out IntPtr ids, out IntPtr val, out int nTokens, out int K);
+        [DllImport(Lib)] internal static extern int pf_stream_num_alternatives(IntPtr s, out int n);
+        [DllImport(Lib)] internal static extern int pf_stream_alternative(IntPtr s, int i, out IntPtr ids, out int nIds, out double score,
+                                                                         out IntPtr textUtf8, out int nTokens);
+        [DllImport(Lib)] internal static extern int pf_stream_alternative_token(IntPtr s, int i, int j, out IntPtr utf8);
         // ABI 6: the rest of OfflineStream's public surface (OfflineStream.cs:20-34)
         [DllImport(Lib)] internal static extern int pf_stream_create([MarshalAs(UnmanagedType.LPUTF8Str)] string mvnPath, int fs, int nMels, int lfrM, int lfrN,
                                                                     int snipEdges, float dither, [MarshalAs(UnmanagedType.LPUTF8Str)] string window, out IntPtr stream);

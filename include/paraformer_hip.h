@@ -218,6 +218,36 @@ int pf_fetch_scores(pf_engine* e, float* scores, int64_t cap, int32_t* L_out);
 int pf_fetch_ctc(pf_engine* e, int64_t* ids, int32_t* first, int32_t* last, float* score, int32_t cap, int32_t* n,
                  int32_t* n_max);
 
+/* ---- Top-k and n-best (additions to ABI 6; nothing is launched or allocated without the flag) --------------------------
+   PF_DECODE_TOPK (pf_engine_set_decode; implies SCORES; paraformer and SenseVoice, every math_mode; PF_ERR_UNSUPPORTED for
+   a SeACo model and for a pf_group forward): behind the arg-max one kernel (csrc/k_topk.hip) selects at every position
+   [B, L] the K best entries of the log-prob row y the arg-max scanned — bit for bit the row a logits request returns.
+   ORDER: entry a ranks before entry b when y[a] > y[b], or y[a] == y[b] and a > b (of equal values the LARGER index first,
+   the reference loop's tie rule; -0.0 == +0.0).  NaN entries are never ranked.  n = min(K, non-NaN entries of the row);
+   slots r >= n hold id -1 and value -inf.  For a row without NaN rank 0 is the arg-max id and its value is the
+   pf_fetch_scores value of that position (a row with a NaN is all NaN in log-softmax form: n = 0).
+   K: pf_engine_set_topk, 1 .. PF_TOPK_MAX, default 4, for the forwards that follow.
+   The flag is bit 8: pf_engine_set_decode(e, 4) has been answered with PF_ERR_INVALID_ARG since the decoding extras exist
+   and callers (and the decode tests) rely on that answer for an unknown bit, so bit 4 stays unassigned. */
+#define PF_DECODE_TOPK 8
+#define PF_TOPK_MAX 8
+#define PF_NBEST_MAX 64
+int pf_engine_set_topk(pf_engine* e, int32_t k);
+/* ids [B * L, K] int64, val [B * L, K] fp32, n [B * L] int32 of the calling thread's last forward, each optional; all three
+   NULL: only learn *L_out and *K_out.  PF_ERR_CAPACITY when cap_rows < B * L; PF_ERR_INVALID_ARG when that forward ran
+   without the flag.  Call it BEFORE the pf_fetch that receives token_ids (it releases the thread's slot). */
+int pf_fetch_topk(pf_engine* e, int64_t* ids, float* val, int32_t* n, int64_t cap_rows, int32_t* L_out, int32_t* K_out);
+/* The exact n-best list of ONE utterance from its top-k lists (pure host code).  Paraformer positions are independent given
+   the audio, so a hypothesis is a rank vector r[0..L) with r[l] < n[l], and r[l] == 0 for l >= n_free =
+   min(L, token_num[b]) (positions past the utterance's own token count keep the 1-best id, as the reference does there:
+   hypothesis 0 is the existing result id for id).  Its score is the float64 sum of the fp32 values val[l, r[l]] added from
+   l = 0 up.  Listed by descending score, ties to the lexicographically smaller rank vector; hypotheses are not
+   de-duplicated by text.  ids (optional, unused by the enumeration), val [L, K], n [L]; N: 1 .. PF_NBEST_MAX.
+   out_ranks [N, L], out_scores [N], *n_out = how many exist (<= N; 0 when some n[l] == 0).
+   PF_ERR_INVALID_ARG for a ranked value that is NaN or +inf. */
+int pf_host_nbest(const int64_t* ids, const float* val, const int32_t* n, int32_t L, int32_t K, int32_t n_free, int32_t N,
+                  int32_t* out_ranks, double* out_scores, int32_t* n_out);
+
 /* ---- PCM intake (additions to ABI 6) --------------------------------------------------------------------------------
    The audio in the form callers hold it — a wav payload, PCM off a socket — uploaded RAW and turned into the engine's
    float32 mono samples at `fs` by one kernel (csrc/k_pcm.hip) in front of the unchanged fbank.  The result is bit for bit
@@ -322,6 +352,10 @@ int pf_op_ctc_collapse(pf_engine* e, const int64_t* ids, const float* scores, co
    out == NULL: only learn *n_out.  PF_ERR_CAPACITY (n_out filled in) when cap < n_out. */
 int pf_op_pcm_convert(pf_engine* e, const void* data, int64_t n_values, const pf_pcm_desc* desc, float* out, int64_t cap,
                       int64_t* n_out);
+/* exactly the pipeline's top-k kernel (k_topk.hip) on the values as given: x [rows, ld] (ld >= V; nothing at or beyond V is
+   read in a row), K: 1 .. PF_TOPK_MAX; ids [rows, K], val [rows, K], n [rows] as pf_fetch_topk. */
+int pf_op_topk(pf_engine* e, const float* x, int64_t rows, int32_t V, int32_t ld, int32_t K, int64_t* ids, float* val,
+               int32_t* n);
 /* C = A[M,K] * W[N,K]^T + bias, f16 operands / f32 accumulate; epilogue 0 none, 1 relu,
    2 = f16 result store (the path the pipeline uses), returned widened to fp32. */
 /* One dynamically quantised Linear, the building block of math_mode 2 (the reference's default model.int8.onnx:
@@ -563,6 +597,25 @@ int pf_stream_tokens(pf_stream* s, const int64_t** ids, int32_t* n);
 int pf_recognizer_set_decode(pf_recognizer* r, int32_t flags);
 /* scores of the stream's last GetResults, parallel to pf_stream_tokens (n = 0 without a decode flag) */
 int pf_stream_scores(pf_stream* s, const float** scores, int32_t* n);
+/* Alternatives (see "Top-k and n-best").  N = 0: off (K ignored).  N >= 1 (<= PF_NBEST_MAX), K: 1 .. PF_TOPK_MAX (0 = 4):
+   PF_DECODE_TOPK with that K on every engine of the pool, present and future, beside the flags of pf_recognizer_set_decode.
+   After GetResults each stream carries TokenAlternatives: K (id, log-prob) pairs per entry of Tokens —
+     paraformer: per position;  SenseVoice without PF_DECODE_CTC: per frame;
+     SenseVoice with PF_DECODE_CTC: those of the FIRST frame of the token's run whose score equals the token's score bit
+     for bit (the run's peak frame).
+   and, for a paraformer recognizer with N > 1, Alternatives: up to N hypotheses (ids, score, text, tokens) in
+   pf_host_nbest order, each decoded by the same DecodeMulti as the result; alternative 0 is the result itself.
+   N > 1 on a SenseVoice recognizer -> PF_ERR_UNSUPPORTED (its frames are not independent tokens); any N >= 1 on SeACo too.
+   Tokens, Timestamps, Scores and the result text are what they are without it. */
+int pf_recognizer_set_nbest(pf_recognizer* r, int32_t N, int32_t K);
+/* ids / val: [*n_tokens, *K], parallel to pf_stream_tokens; slots past a position's n hold -1 / -inf.  *n_tokens = 0
+   without pf_recognizer_set_nbest.  The pointers stay valid until the stream's next GetResults. */
+int pf_stream_token_alternatives(pf_stream* s, const int64_t** ids, const float** val, int32_t* n_tokens, int32_t* K);
+int pf_stream_num_alternatives(pf_stream* s, int32_t* n);
+/* alternative i: its ids [*n_ids], score, text and the number of decoded tokens (each optional) */
+int pf_stream_alternative(pf_stream* s, int32_t i, const int64_t** ids, int32_t* n_ids, double* score, const char** text_utf8,
+                          int32_t* n_tokens);
+int pf_stream_alternative_token(pf_stream* s, int32_t i, int32_t j, const char** utf8);
 
 /* ABI 6: the rest of OfflineStream's public surface (OfflineStream.cs:20-34).  Only the reference's own Forward touches
    these members, but "same public signatures" means a caller may.
