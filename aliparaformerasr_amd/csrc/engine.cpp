@@ -599,60 +599,13 @@ void Engine::load_weights(const pf_engine_config& cfg) {
     else PF_HIP(hipFree(tmp));
   }
   // decoder
-  const int nd = mc_.dec_layers;
-  if (nd > 0) {
-    dec_kv_all_.N = nd * 2 * D; dec_kv_all_.K = D; dec_kv_all_.Kpad = D;
-    dec_kv_all_.w = (half_t*)dalloc((size_t)round_up(dec_kv_all_.N, 128) * D * 2);
-    PF_HIP(hipMemsetAsync(dec_kv_all_.w, 0, (size_t)round_up(dec_kv_all_.N, 128) * D * 2, stream_));
-    float* kvb = (float*)dalloc((size_t)dec_kv_all_.N * 4);
-    dec_kv_all_.bias = kvb;
-    for (int i = 0; i < nd; ++i) {
-      const std::string p = "decoder.layers." + std::to_string(i);
-      DecLayer L;
-      L.norm1 = make_ln(p + ".norm1", D);
-      L.w1 = make_lin(p + ".ffn.w1", true);
-      L.ffn_norm = make_ln(p + ".ffn.norm", L.w1.N);
-      L.w2 = make_lin(p + ".ffn.w2", false);
-      L.norm2 = make_ln(p + ".norm2", D);
-      L.fsmn_wT = make_fsmn_wT(p + ".fsmn.weight");
-      L.norm3 = make_ln(p + ".norm3", D);
-      L.q = make_lin(p + ".src.q", true);
-      L.out = make_lin(p + ".src.out", true);
-      PF_CHECK(L.w1.K == D && L.w1.N == mc_.ffn && L.w2.N == D && L.w2.K == L.w1.N && L.q.N == D && L.q.K == D &&
-                   L.out.N == D && L.out.K == D,
-               PF_ERR_FORMAT, "weights: decoder layer shape mismatch in " + p);
-      const Tensor& kvw = tensor(p + ".src.kv.weight");
-      const Tensor& kvbias = tensor(p + ".src.kv.bias");
-      PF_CHECK(kvw.numel == (int64_t)2 * D * D && kvbias.numel == 2 * D, PF_ERR_FORMAT, "weights: src.kv shape in " + p);
-      launch_f32_to_f16(stream_, kvw.dev, 2 * D, D, D, dec_kv_all_.w + (size_t)i * 2 * D * D, D);
-      PF_HIP(hipMemcpyAsync(kvb + (size_t)i * 2 * D, kvbias.dev, 2 * D * 4, hipMemcpyDeviceToDevice, stream_));
-      L.kv32.w32 = kvw.dev; L.kv32.bias = kvbias.dev; L.kv32.N = 2 * D; L.kv32.K = D;
-      L.kv32.w = dec_kv_all_.w + (size_t)i * 2 * D * D; L.kv32.Kpad = D;
-      L.ffn_img = make_dec_ffn_image(L.w1, L.ffn_norm, L.w2);
-      if (L.ffn_img) {
-        L.out_wt = (half_t*)dalloc(ffn_outproj_weight_bytes());
-        launch_ffn_retile_out(stream_, L.out.w, L.out.Kpad, L.out_wt);
-      }
-      if (L.ffn_img && dec_mid_ && L.q.w && L.q.bias && L.q.Kpad == D && L.q.N == D) {
-        L.q_wt = (half_t*)dalloc(ffn_outproj_weight_bytes());
-        launch_ffn_retile_out(stream_, L.q.w, L.q.Kpad, L.q_wt);
-      }
-      dec_.push_back(L);
-    }
-  }
-  dec_final_norm1_ = make_ln("decoder.final.norm1", D);
-  dec_final_w1_ = make_lin("decoder.final.ffn.w1", true);
-  dec_final_ffn_norm_ = make_ln("decoder.final.ffn.norm", dec_final_w1_.N);
-  dec_final_w2_ = make_lin("decoder.final.ffn.w2", false);
-  dec_after_ = make_ln("decoder.after_norm", D);
-  dec_final_img_ = make_dec_ffn_image(dec_final_w1_, dec_final_ffn_norm_, dec_final_w2_);
-  dec_out_ = make_lin("decoder.output", true);
-  PF_CHECK(dec_out_.N == mc_.vocab && dec_out_.K == D && dec_final_w1_.K == D && dec_final_w1_.N == mc_.ffn &&
-               dec_final_w2_.N == D && dec_final_w2_.K == dec_final_w1_.N,
+  dec_ = load_dec_stack("decoder", mc_.dec_layers, mc_.ffn, mc_.kernel, true);
+  dec_.out = make_lin("decoder.output", true);
+  PF_CHECK(dec_.out.N == mc_.vocab && dec_.out.K == D && dec_.final_w1.K == D && dec_.final_w1.N == mc_.ffn &&
+               dec_.final_w2.N == D && dec_.final_w2.K == dec_.final_w1.N,
            PF_ERR_FORMAT, "weights: decoder.final / decoder.output shapes");
   // SeACo: hotword embedder (Embedding + LSTM stack) and the bias decoder
   if (mc_.seaco) {
-    const int ns = mc_.seaco_layers;
     const Tensor& ew = tensor("seaco.embed.weight");
     PF_CHECK(ew.shape.size() == 2 && ew.shape[1] == D, PF_ERR_FORMAT, "weights: seaco.embed.weight shape");
     seaco_embed_w_ = ew.dev;
@@ -679,46 +632,69 @@ void Engine::load_weights(const pf_engine_config& cfg) {
       L.ih.bias = gb;
       seaco_lstm_.push_back(L);
     }
-    if (ns > 0) {
-      seaco_kv_all_.N = ns * 2 * D; seaco_kv_all_.K = D; seaco_kv_all_.Kpad = D;
-      seaco_kv_all_.w = (half_t*)dalloc((size_t)round_up(seaco_kv_all_.N, 128) * D * 2);
-      PF_HIP(hipMemsetAsync(seaco_kv_all_.w, 0, (size_t)round_up(seaco_kv_all_.N, 128) * D * 2, stream_));
-      float* kvb = (float*)dalloc((size_t)seaco_kv_all_.N * 4);
-      seaco_kv_all_.bias = kvb;
-      for (int i = 0; i < ns; ++i) {
-        const std::string p = "seaco.decoder.layers." + std::to_string(i);
-        DecLayer L;
-        L.norm1 = make_ln(p + ".norm1", D);
-        L.w1 = make_lin(p + ".ffn.w1", true);
-        L.ffn_norm = make_ln(p + ".ffn.norm", L.w1.N);
-        L.w2 = make_lin(p + ".ffn.w2", false);
-        L.norm2 = make_ln(p + ".norm2", D);
-        L.fsmn_wT = make_fsmn_wT(p + ".fsmn.weight", mc_.seaco_kernel);
-        L.norm3 = make_ln(p + ".norm3", D);
-        L.q = make_lin(p + ".src.q", true);
-        L.out = make_lin(p + ".src.out", true);
-        PF_CHECK(L.w1.K == D && L.w2.N == D && L.w2.K == L.w1.N && L.q.N == D && L.q.K == D && L.out.N == D && L.out.K == D,
-                 PF_ERR_FORMAT, "weights: seaco decoder layer shape mismatch in " + p);
-        const Tensor& kvw = tensor(p + ".src.kv.weight");
-        const Tensor& kvbias = tensor(p + ".src.kv.bias");
-        PF_CHECK(kvw.numel == (int64_t)2 * D * D && kvbias.numel == 2 * D, PF_ERR_FORMAT, "weights: src.kv shape in " + p);
-        PF_CHECK(L.w1.N == mc_.seaco_ffn, PF_ERR_FORMAT, "weights: seaco ffn width != seaco_ffn");
-        launch_f32_to_f16(stream_, kvw.dev, 2 * D, D, D, seaco_kv_all_.w + (size_t)i * 2 * D * D, D);
-        PF_HIP(hipMemcpyAsync(kvb + (size_t)i * 2 * D, kvbias.dev, 2 * D * 4, hipMemcpyDeviceToDevice, stream_));
-        L.kv32.w32 = kvw.dev; L.kv32.bias = kvbias.dev; L.kv32.N = 2 * D; L.kv32.K = D;
-        L.kv32.w = seaco_kv_all_.w + (size_t)i * 2 * D * D; L.kv32.Kpad = D;
-        sdec_.push_back(L);
-      }
-    }
-    seaco_final_norm1_ = make_ln("seaco.decoder.final.norm1", D);
-    seaco_final_w1_ = make_lin("seaco.decoder.final.ffn.w1", true);
-    seaco_final_ffn_norm_ = make_ln("seaco.decoder.final.ffn.norm", seaco_final_w1_.N);
-    seaco_final_w2_ = make_lin("seaco.decoder.final.ffn.w2", false);
-    seaco_after_ = make_ln("seaco.decoder.after_norm", D);
-    seaco_out_ = make_lin("seaco.output", true);
-    PF_CHECK(seaco_out_.N == mc_.vocab, PF_ERR_FORMAT, "weights: seaco.output rows != vocab");
+    bias_dec_ = load_dec_stack("seaco.decoder", mc_.seaco_layers, mc_.seaco_ffn, mc_.seaco_kernel, false);
+    bias_dec_.out = make_lin("seaco.output", true);
+    PF_CHECK(bias_dec_.out.N == mc_.vocab, PF_ERR_FORMAT, "weights: seaco.output rows != vocab");
   }
   PF_HIP(hipStreamSynchronize(stream_));
+}
+
+// One decoder stack: `prefix`.layers.N, `prefix`.final, `prefix`.after_norm.  The K | V projections of all layers are also
+// kept as ONE f16 Linear [n_layers * 2D, D] (kv_all): they depend on the memory alone and go out as one GEMM.
+DecStack Engine::load_dec_stack(const std::string& prefix, int n_layers, int ffn, int fsmn_k, bool fused_images) {
+  const int D = mc_.d_model;
+  const bool asr = prefix == "decoder";
+  DecStack S;
+  S.ffn = ffn; S.fsmn_k = fsmn_k;
+  if (n_layers > 0) {
+    Lin& kva = S.kv_all;
+    kva.N = n_layers * 2 * D; kva.K = D; kva.Kpad = D;
+    kva.w = (half_t*)dalloc((size_t)round_up(kva.N, 128) * D * 2);
+    PF_HIP(hipMemsetAsync(kva.w, 0, (size_t)round_up(kva.N, 128) * D * 2, stream_));
+    float* kvb = (float*)dalloc((size_t)kva.N * 4);
+    kva.bias = kvb;
+    for (int i = 0; i < n_layers; ++i) {
+      const std::string p = prefix + ".layers." + std::to_string(i);
+      DecLayer L;
+      L.norm1 = make_ln(p + ".norm1", D);
+      L.w1 = make_lin(p + ".ffn.w1", true);
+      L.ffn_norm = make_ln(p + ".ffn.norm", L.w1.N);
+      L.w2 = make_lin(p + ".ffn.w2", false);
+      L.norm2 = make_ln(p + ".norm2", D);
+      L.fsmn_wT = make_fsmn_wT(p + ".fsmn.weight", fsmn_k);
+      L.norm3 = make_ln(p + ".norm3", D);
+      L.q = make_lin(p + ".src.q", true);
+      L.out = make_lin(p + ".src.out", true);
+      PF_CHECK(L.w1.K == D && (!asr || L.w1.N == ffn) && L.w2.N == D && L.w2.K == L.w1.N && L.q.N == D && L.q.K == D &&
+                   L.out.N == D && L.out.K == D,
+               PF_ERR_FORMAT, std::string("weights: ") + (asr ? "" : "seaco ") + "decoder layer shape mismatch in " + p);
+      const Tensor& kvw = tensor(p + ".src.kv.weight");
+      const Tensor& kvbias = tensor(p + ".src.kv.bias");
+      PF_CHECK(kvw.numel == (int64_t)2 * D * D && kvbias.numel == 2 * D, PF_ERR_FORMAT, "weights: src.kv shape in " + p);
+      PF_CHECK(asr || L.w1.N == ffn, PF_ERR_FORMAT, "weights: seaco ffn width != seaco_ffn");
+      launch_f32_to_f16(stream_, kvw.dev, 2 * D, D, D, kva.w + (size_t)i * 2 * D * D, D);
+      PF_HIP(hipMemcpyAsync(kvb + (size_t)i * 2 * D, kvbias.dev, 2 * D * 4, hipMemcpyDeviceToDevice, stream_));
+      L.kv32.w32 = kvw.dev; L.kv32.bias = kvbias.dev; L.kv32.N = 2 * D; L.kv32.K = D;
+      L.kv32.w = kva.w + (size_t)i * 2 * D * D; L.kv32.Kpad = D;
+      if (fused_images) L.ffn_img = make_dec_ffn_image(L.w1, L.ffn_norm, L.w2);
+      if (L.ffn_img) {
+        L.out_wt = (half_t*)dalloc(ffn_outproj_weight_bytes());
+        launch_ffn_retile_out(stream_, L.out.w, L.out.Kpad, L.out_wt);
+      }
+      if (L.ffn_img && dec_mid_ && L.q.w && L.q.bias && L.q.Kpad == D && L.q.N == D) {
+        L.q_wt = (half_t*)dalloc(ffn_outproj_weight_bytes());
+        launch_ffn_retile_out(stream_, L.q.w, L.q.Kpad, L.q_wt);
+      }
+      S.layers.push_back(L);
+    }
+  }
+  S.final_norm1 = make_ln(prefix + ".final.norm1", D);
+  S.final_w1 = make_lin(prefix + ".final.ffn.w1", true);
+  S.final_ffn_norm = make_ln(prefix + ".final.ffn.norm", S.final_w1.N);
+  S.final_w2 = make_lin(prefix + ".final.ffn.w2", false);
+  S.after = make_ln(prefix + ".after_norm", D);
+  if (fused_images) S.final_img = make_dec_ffn_image(S.final_w1, S.final_ffn_norm, S.final_w2);
+  return S;
 }
 
 // The decoder's FFN block for the split form of ffn_fused_kernel (k_ffn.hip): W1, gamma_F (.) W2 (from the fp32 tensor, one
@@ -1309,6 +1285,67 @@ void Engine::dec_ffn_hidden(const char* cls, const Lin& w1, const LNp& fn, const
   prof_end("layernorm");
 }
 
+// cross-attention of a decoder layer: q / o dense [B * L, D] f16, K / V rows kv_rs apart and kv_bs per utterance (0: shared)
+AttnArgs Engine::cross_attn_args(const half_t* q, const half_t* k, const half_t* v, int kv_rs, int64_t kv_bs, half_t* o, int B, int L, int Lk) const {
+  const int D = mc_.d_model;
+  AttnArgs a{};
+  a.q = q; a.q_bstride = (int64_t)L * D; a.q_rstride = D;
+  a.k = k; a.v = v;
+  a.k_bstride = a.v_bstride = kv_bs; a.k_rstride = a.v_rstride = kv_rs;
+  a.o = o; a.o_bstride = (int64_t)L * D; a.o_rstride = D;
+  a.B = B; a.H = mc_.heads; a.Lq = L; a.Lk = Lk;
+  return a;
+}
+
+DecBufs Engine::carve_dec16(Arena& a, int64_t rows, int F, bool with_h32) {
+  const int D = mc_.d_model;
+  DecBufs d;
+  d.x = a.take<float>((size_t)rows * D * 4); d.xn16 = a.take<half_t>((size_t)rows * D * 2);
+  if (with_h32) d.h32 = a.take<float>((size_t)rows * F * 4);      // math_mode 2 runs the bias decoder in this arena (decoder_int8)
+  d.h16 = a.take<half_t>((size_t)rows * F * 2); d.t32 = a.take<float>((size_t)rows * D * 4); d.tn32 = a.take<float>((size_t)rows * D * 4);
+  d.q16 = a.take<half_t>((size_t)rows * D * 2); d.ctx16 = a.take<half_t>((size_t)rows * D * 2);
+  return d;
+}
+
+// The decoder stack in its plain form, 9 launches a layer: norm1 | FFN-up (f16 hidden) | LayerNorm(F) in place | FFN-down | norm2 |
+// FSMN memory + residual | norm3 | q | cross attention | out-projection + residual; then the final block's FFN (-> t32).  The SeACo
+// bias decoder and the streaming seam run it; the ASR decoder's fused and short-input forms are predictor_and_decoder's own walk.
+void Engine::decoder16(const DecStack& S, const DecRun& r) {
+  const int D = mc_.d_model, R = r.B * r.L;
+  const DecBufs& b = r.b;
+  const float qscale = 1.0f / std::sqrt((float)(D / mc_.heads));
+  const size_t cache = (size_t)r.B * D * (S.fsmn_k - 1);   // one layer's slice of the streaming caches
+  auto norm = [&](const float* x, const LNp& ln, half_t* n16, float* n32) {
+    prof_begin("layernorm", 0);
+    launch_layernorm(stream_, x, R, D, ln.g, ln.b, n16, n16 ? D : 0, n32, n32 ? D : 0);
+    prof_end("layernorm");
+  };
+  auto ffn_dec = [&](const LNp& n1, const Lin& w1, const LNp& fn, const Lin& w2) {
+    norm(b.x, n1, b.xn16, nullptr);
+    dec_ffn_hidden(r.cls_ffn1, w1, fn, b.xn16, D, R, b.h16);
+    gemm(r.cls_ffn2, w2, b.h16, S.ffn, R, b.t32, D, nullptr, 0, nullptr, 0, nullptr, 0, false, 0, 1.f, false);
+  };
+  for (size_t i = 0; i < S.layers.size(); ++i) {
+    const DecLayer& Lr = S.layers[i];
+    ffn_dec(Lr.norm1, Lr.w1, Lr.ffn_norm, Lr.w2);
+    norm(b.t32, Lr.norm2, nullptr, b.tn32);
+    prof_begin("fsmn", 0);
+    if (r.cache_in)
+      launch_fsmn_dec_stream(stream_, b.tn32, Lr.fsmn_wT, r.token_num, r.cache_in + i * cache, r.B, r.L, D, S.fsmn_k, b.x, r.cache_out + i * cache);
+    else
+      launch_fsmn_dec(stream_, b.tn32, Lr.fsmn_wT, r.token_num, r.B, r.L, D, S.fsmn_k, b.x);
+    prof_end("fsmn");
+    norm(b.x, Lr.norm3, b.xn16, nullptr);
+    gemm(r.cls_q, Lr.q, b.xn16, D, R, nullptr, 0, b.q16, D, nullptr, 0, nullptr, 0, false, D, qscale);
+    const half_t* k16 = (const half_t*)r.kv + i * 2 * D;
+    prof_begin(r.cls_attn, 4.0 * r.B * (double)r.L * r.Lk * D);
+    launch_attention(stream_, cross_attn_args(b.q16, k16, k16 + D, r.kv_rs, r.kv_bs, b.ctx16, r.B, r.L, r.Lk));
+    prof_end(r.cls_attn);
+    gemm(r.cls_out, Lr.out, b.ctx16, D, R, b.x, D, nullptr, 0, b.x, D, nullptr, 0, false, 0, 1.f);
+  }
+  ffn_dec(S.final_norm1, S.final_w1, S.final_ffn_norm, S.final_w2);
+}
+
 void Engine::predictor_and_decoder(int B, int T, bool want_logits) {
   const int D = mc_.d_model, F = mc_.ffn, V = mc_.vocab;
   const int M = B * T, T1 = T + 1;
@@ -1335,13 +1372,13 @@ void Engine::predictor_and_decoder(int B, int T, bool want_logits) {
   // The cross-attention K/V projections of all decoder layers depend on the encoder output only, not on the decoder
   // length: they go out BEFORE the length is read back and keep the device busy during the host round trip (and,
   // in a multi-device group, during the rendez-vous that agrees on the batch-wide length).
-  const int nd = (int)dec_.size();
+  const int nd = (int)dec_.layers.size();
   const int64_t Mp = round_up(M, 128) + 128;
   const int ldkv = std::max(nd, 1) * 2 * D;
   ensure(ws_kv_, (size_t)Mp * ldkv * 2);
   half_t* kv16 = (half_t*)ws_kv_.p;
   if (nd > 0)
-    gemm("gemm_dec_kv", dec_kv_all_, H16_, D, M, nullptr, 0, kv16, ldkv, nullptr, 0, nullptr, 0, false, 0, 1.f);
+    gemm("gemm_dec_kv", dec_.kv_all, H16_, D, M, nullptr, 0, kv16, ldkv, nullptr, 0, nullptr, 0, false, 0, 1.f);
   // the path's only host sync: the decoder length L is data dependent.  The read-back rides a side stream that waits
   // for the CIF scan alone.
   int32_t L = read_back_plan(B);       // (the K / V GEMM above is queued BEHIND the event this waits for: nothing waits for the GEMM)
@@ -1352,20 +1389,15 @@ void Engine::predictor_and_decoder(int B, int T, bool want_logits) {
 
   const int Md = B * L;
   const int64_t Mdp = round_up(Md, 128) + 128;
-  size_t off = 0;
-  auto carve = [&](size_t bytes) { size_t o = off; off += round_up((int64_t)bytes, (int64_t)kAlign); return o; };
-  const size_t o_x = carve(Mdp * D * 4), o_xn = carve(Mdp * D * 2);
-  const size_t o_h16 = carve(Mdp * F * 2), o_t = carve(Mdp * D * 4), o_tn = carve(Mdp * D * 4);
-  const size_t o_q = carve(Mdp * D * 2), o_ctx = carve(Mdp * D * 2), o_lg = carve((size_t)Mdp * round_up(V, 4) * 4), o_ids = carve((size_t)Md * 8);
-  const size_t o_x2 = carve(Mdp * D * 4);
-  ensure(ws_dec_, off);
-  char* base = (char*)ws_dec_.p;
-  float* xd = (float*)(base + o_x); half_t* xdn16 = (half_t*)(base + o_xn);
-  float* xd_alt = (float*)(base + o_x2);               // the residual stream ping-pongs when the out-projection rides in front of the next FFN launch
-  half_t* hd16 = (half_t*)(base + o_h16);
-  float* t32 = (float*)(base + o_t); float* tn32 = (float*)(base + o_tn);
-  half_t* qd16 = (half_t*)(base + o_q); half_t* ctxd16 = (half_t*)(base + o_ctx);
-  logits_ = (float*)(base + o_lg); ids_dev_ = (int64_t*)(base + o_ids);
+  float* xd_alt = nullptr;                             // the residual stream ping-pongs when the out-projection rides in front of the next FFN launch
+  const DecBufs w = carve_into(ws_dec_, kAlign, [&](Arena& a) {
+    const DecBufs d = carve_dec16(a, Mdp, F, false);
+    logits_ = a.take<float>((size_t)Mdp * round_up(V, 4) * 4); ids_dev_ = a.take<int64_t>((size_t)Md * 8);
+    xd_alt = a.take<float>(Mdp * D * 4);
+    return d;
+  });
+  float* xd = w.x; half_t* xdn16 = w.xn16; half_t* hd16 = w.h16; float* t32 = w.t32; float* tn32 = w.tn32;
+  half_t* qd16 = w.q16; half_t* ctxd16 = w.ctx16;
   const float qscale = 1.0f / std::sqrt((float)(D / mc_.heads));
 
   prof_begin("cif_misc", 0);
@@ -1389,14 +1421,14 @@ void Engine::predictor_and_decoder(int B, int T, bool want_logits) {
   bool dsmall = Md <= gemm_small_max_rows() && small_ws_ && F > 576;
   if (dsmall) {                                        // the split FFN-down form must apply to (Md, F), else the regular kernels
     GemmSmallArgs t{};
-    t.M = Md; t.N = D; t.K = dec_final_w2_.Kpad; t.A = hd16; t.lda = F; t.W = dec_final_w2_.w; t.ldw = dec_final_w2_.Kpad;
-    t.ws = small_ws_; t.post_ln_g = dec_after_.g; t.post_ln_b = dec_after_.b;
+    t.M = Md; t.N = D; t.K = dec_.final_w2.Kpad; t.A = hd16; t.lda = F; t.W = dec_.final_w2.w; t.ldw = dec_.final_w2.Kpad;
+    t.ws = small_ws_; t.post_ln_g = dec_.after.g; t.post_ln_b = dec_.after.b;
     dsmall = gemm_small_applicable(t);
   }
   // out-projection chain (k_ffn.hip, OP = 2): layer i's cross-attention out-projection + residual + the next norm1 run in
   // front of the NEXT block's split FFN launch; `pend` = the layer whose context (ctxd16) still waits for its projection
-  bool chain = !dsmall && dec_final_img_ != nullptr;
-  for (int i = 0; i < nd && chain; ++i) chain = dec_[i].ffn_img && dec_[i].out_wt;
+  bool chain = !dsmall && dec_.final_img != nullptr;
+  for (int i = 0; i < nd && chain; ++i) chain = dec_.layers[i].ffn_img && dec_.layers[i].out_wt;
   const DecLayer* pend = nullptr;
   // ffn_dec: norm1 -> w_1 + ReLU -> LayerNorm(2048) -> w_2 (no bias) [-> LayerNorm `post`]; leaves t32 (unfused) or
   // post(t) in n32 / n16
@@ -1447,7 +1479,7 @@ void Engine::predictor_and_decoder(int B, int T, bool want_logits) {
   };
 
   for (int i = 0; i < nd; ++i) {
-    const DecLayer& Lr = dec_[i];
+    const DecLayer& Lr = dec_.layers[i];
     // round 6: the finishing pass of the split FFN form, norm2, the FSMN memory, the residual, norm3 and the q-projection in ONE
     // launch (k_decmid.hip): a decoder layer = split FFN | middle | cross-attention
     const bool mid = dec_mid_ && Lr.ffn_img && Lr.q_wt && !dsmall && mc_.kernel == 11;
@@ -1482,14 +1514,9 @@ void Engine::predictor_and_decoder(int B, int T, bool want_logits) {
       prof_end("layernorm");
     }
     if (!mid_done) gemm("gemm_dec_q", Lr.q, xdn16, D, Md, nullptr, 0, qd16, D, nullptr, 0, nullptr, 0, false, D, qscale);
-    AttnArgs a{};
-    a.q = qd16; a.q_bstride = (int64_t)L * D; a.q_rstride = D;
-    a.k = kv16 + (size_t)i * 2 * D; a.v = kv16 + (size_t)i * 2 * D + D;
-    a.k_bstride = a.v_bstride = (int64_t)T * ldkv; a.k_rstride = a.v_rstride = ldkv;
-    a.o = ctxd16; a.o_bstride = (int64_t)L * D; a.o_rstride = D;
-    a.B = B; a.H = mc_.heads; a.Lq = L; a.Lk = T;
+    const half_t* k16 = kv16 + (size_t)i * 2 * D;
     prof_begin("attn_cross", 4.0 * B * (double)L * T * D);
-    launch_attention(stream_, a);
+    launch_attention(stream_, cross_attn_args(qd16, k16, k16 + D, ldkv, (int64_t)T * ldkv, ctxd16, B, L, T));
     prof_end("attn_cross");
     if (chain) {
       pend = &Lr;
@@ -1497,9 +1524,9 @@ void Engine::predictor_and_decoder(int B, int T, bool want_logits) {
       gemm("gemm_dec_out", Lr.out, ctxd16, D, Md, xd, D, nullptr, 0, xd, D, nullptr, 0, false, 0, 1.f);
     }
   }
-  ffn_dec(dec_final_norm1_, dec_final_w1_, dec_final_ffn_norm_, dec_final_w2_, dec_final_img_, dec_after_, hid32, xdn16);
+  ffn_dec(dec_.final_norm1, dec_.final_w1, dec_.final_ffn_norm, dec_.final_w2, dec_.final_img, dec_.after, hid32, xdn16);
   logits_ld_ = (int)round_up(V, 4);                 // fp32 rows stay 16-byte aligned for any vocabulary size
-  gemm("gemm_vocab", dec_out_, xdn16, D, Md, logits_, logits_ld_, nullptr, 0, nullptr, 0, nullptr, 0, false, 0, 1.f);
+  gemm("gemm_vocab", dec_.out, xdn16, D, Md, logits_, logits_ld_, nullptr, 0, nullptr, 0, nullptr, 0, false, 0, 1.f);
   prof_begin("argmax", 0);
   launch_argmax(stream_, logits_, Md, V, logits_ld_, argmax_mode(want_logits), ids_dev_, score_buf(Md));
   prof_end("argmax");
@@ -1578,61 +1605,35 @@ void Engine::online_decoder(const float* enc, int B, int Tc, const float* embeds
            "online_decoder: bad arguments");
   PF_CHECK(mc_.kernel == 11, PF_ERR_UNSUPPORTED, "online_decoder: FSMN kernel 11 (cache of 10 columns) only");
   PF_HIP(hipSetDevice(device_));
-  const int D = mc_.d_model, F = mc_.ffn, V = mc_.vocab, nd = (int)dec_.size(), CW = mc_.kernel - 1;
+  const int D = mc_.d_model, F = mc_.ffn, V = mc_.vocab, nd = (int)dec_.layers.size(), CW = mc_.kernel - 1;
   const int M = B * Tc, Md = B * L;
   const int64_t Mp = round_up(M, 128) + 128, Mdp = round_up(Md, 128) + 128;
   const int ldV = (int)round_up(V, 4);
-  size_t off = 0;
-  auto carve = [&](size_t bytes) { size_t o = off; off += round_up((int64_t)bytes, (int64_t)kAlign); return o; };
-  const size_t o_e32 = carve((size_t)M * D * 4), o_e16 = carve((size_t)Mp * D * 2), o_kv = carve((size_t)Mp * std::max(nd, 1) * 2 * D * 2);
-  const size_t o_x = carve((size_t)Mdp * D * 4), o_xn = carve((size_t)Mdp * D * 2);
-  const size_t o_h16 = carve((size_t)Mdp * F * 2), o_t = carve((size_t)Mdp * D * 4), o_tn = carve((size_t)Mdp * D * 4);
-  const size_t o_q = carve((size_t)Mdp * D * 2), o_ctx = carve((size_t)Mdp * D * 2), o_lg = carve((size_t)Mdp * ldV * 4);
-  const size_t o_ids = carve((size_t)Md * 8), o_len = carve((size_t)B * 4);
-  const size_t o_ci = carve((size_t)nd * B * D * CW * 4), o_co = carve((size_t)nd * B * D * CW * 4);
-  ensure(ws_dec_, off);
-  char* base = (char*)ws_dec_.p;
-  float* e32 = (float*)(base + o_e32); half_t* e16 = (half_t*)(base + o_e16); half_t* kv16 = (half_t*)(base + o_kv);
-  float* xd = (float*)(base + o_x); half_t* xdn16 = (half_t*)(base + o_xn);
-  half_t* hd16 = (half_t*)(base + o_h16);
-  float* t32 = (float*)(base + o_t); float* tn32 = (float*)(base + o_tn);
-  half_t* qd16 = (half_t*)(base + o_q); half_t* ctxd16 = (half_t*)(base + o_ctx);
-  float* lg = (float*)(base + o_lg); int64_t* ids = (int64_t*)(base + o_ids); int32_t* lens = (int32_t*)(base + o_len);
-  float* ci = (float*)(base + o_ci); float* co = (float*)(base + o_co);
+  float* e32 = nullptr; half_t* e16 = nullptr; half_t* kv16 = nullptr; float* lg = nullptr; int64_t* ids = nullptr; int32_t* lens = nullptr;
+  float* ci = nullptr; float* co = nullptr;
+  DecRun r;
+  r.b = carve_into(ws_dec_, kAlign, [&](Arena& a) {
+    e32 = a.take<float>((size_t)M * D * 4); e16 = a.take<half_t>((size_t)Mp * D * 2); kv16 = a.take<half_t>((size_t)Mp * std::max(nd, 1) * 2 * D * 2);
+    const DecBufs d = carve_dec16(a, Mdp, F, false);
+    lg = a.take<float>((size_t)Mdp * ldV * 4); ids = a.take<int64_t>((size_t)Md * 8); lens = a.take<int32_t>((size_t)B * 4);
+    ci = a.take<float>((size_t)nd * B * D * CW * 4); co = a.take<float>((size_t)nd * B * D * CW * 4);
+    return d;
+  });
+  float* xd = r.b.x; float* t32 = r.b.t32; half_t* xdn16 = r.b.xn16;
   PF_HIP(hipMemsetAsync(e16, 0, (size_t)Mp * D * 2, stream_));
   PF_HIP(hipMemcpyAsync(e32, enc, (size_t)M * D * 4, hipMemcpyHostToDevice, stream_));
   launch_f32_to_f16(stream_, e32, M, D, D, e16, D);
   PF_HIP(hipMemcpyAsync(xd, embeds, (size_t)Md * D * 4, hipMemcpyHostToDevice, stream_));
   PF_HIP(hipMemcpyAsync(lens, embeds_len, (size_t)B * 4, hipMemcpyHostToDevice, stream_));
   PF_HIP(hipMemcpyAsync(ci, caches_in, (size_t)nd * B * D * CW * 4, hipMemcpyHostToDevice, stream_));
-  const float qscale = 1.0f / std::sqrt((float)(D / mc_.heads));
   const int ldkv = nd * 2 * D;
-  if (nd > 0) gemm("gemm_dec_kv", dec_kv_all_, e16, D, M, nullptr, 0, kv16, ldkv, nullptr, 0, nullptr, 0, false, 0, 1.f);
-  auto ffn_dec = [&](const LNp& n1, const Lin& w1, const LNp& fn, const Lin& w2) {
-    launch_layernorm(stream_, xd, Md, D, n1.g, n1.b, xdn16, D, nullptr, 0);
-    dec_ffn_hidden("gemm_dec_ffn1", w1, fn, xdn16, D, Md, hd16);
-    gemm("gemm_dec_ffn2", w2, hd16, F, Md, t32, D, nullptr, 0, nullptr, 0, nullptr, 0, false, 0, 1.f, false);
-  };
-  for (int i = 0; i < nd; ++i) {
-    const DecLayer& Lr = dec_[i];
-    ffn_dec(Lr.norm1, Lr.w1, Lr.ffn_norm, Lr.w2);
-    launch_layernorm(stream_, t32, Md, D, Lr.norm2.g, Lr.norm2.b, nullptr, 0, tn32, D);
-    launch_fsmn_dec_stream(stream_, tn32, Lr.fsmn_wT, lens, ci + (size_t)i * B * D * CW, B, L, D, mc_.kernel, xd,
-                           co + (size_t)i * B * D * CW);
-    launch_layernorm(stream_, xd, Md, D, Lr.norm3.g, Lr.norm3.b, xdn16, D, nullptr, 0);
-    gemm("gemm_dec_q", Lr.q, xdn16, D, Md, nullptr, 0, qd16, D, nullptr, 0, nullptr, 0, false, D, qscale);
-    AttnArgs a{};
-    a.q = qd16; a.q_bstride = (int64_t)L * D; a.q_rstride = D;
-    a.k = kv16 + (size_t)i * 2 * D; a.v = kv16 + (size_t)i * 2 * D + D;
-    a.k_bstride = a.v_bstride = (int64_t)Tc * ldkv; a.k_rstride = a.v_rstride = ldkv;
-    a.o = ctxd16; a.o_bstride = (int64_t)L * D; a.o_rstride = D;
-    a.B = B; a.H = mc_.heads; a.Lq = L; a.Lk = Tc;
-    launch_attention(stream_, a);
-    gemm("gemm_dec_out", Lr.out, ctxd16, D, Md, xd, D, nullptr, 0, xd, D, nullptr, 0, false, 0, 1.f);
-  }
-  ffn_dec(dec_final_norm1_, dec_final_w1_, dec_final_ffn_norm_, dec_final_w2_);
-  launch_layernorm(stream_, t32, Md, D, dec_after_.g, dec_after_.b, xdn16, D, nullptr, 0);
-  gemm("gemm_vocab", dec_out_, xdn16, D, Md, lg, ldV, nullptr, 0, nullptr, 0, nullptr, 0, false, 0, 1.f);
+  if (nd > 0) gemm("gemm_dec_kv", dec_.kv_all, e16, D, M, nullptr, 0, kv16, ldkv, nullptr, 0, nullptr, 0, false, 0, 1.f);
+  r.B = B; r.L = L; r.token_num = lens;
+  r.kv = kv16; r.kv_rs = ldkv; r.kv_bs = (int64_t)Tc * ldkv; r.Lk = Tc;
+  r.cache_in = ci; r.cache_out = co;
+  decoder16(dec_, r);
+  launch_layernorm(stream_, t32, Md, D, dec_.after.g, dec_.after.b, xdn16, D, nullptr, 0);
+  gemm("gemm_vocab", dec_.out, xdn16, D, Md, lg, ldV, nullptr, 0, nullptr, 0, nullptr, 0, false, 0, 1.f);
   launch_argmax(stream_, lg, Md, V, ldV, logits_out ? 2 : 1, ids);
   if (logits_out) PF_HIP(hipMemcpy2DAsync(logits_out, (size_t)V * 4, lg, (size_t)ldV * 4, (size_t)V * 4, Md, hipMemcpyDeviceToHost, stream_));
   PF_HIP(hipMemcpyAsync(ids_out, ids, (size_t)Md * 8, hipMemcpyDeviceToHost, stream_));
@@ -1654,13 +1655,11 @@ void Engine::set_hotwords(const int32_t* hw, int n) {
 // over B), so its K/V projections are computed once and every (utterance, head) attends the same rows.  The
 // bias decoder runs once on 2*B*L rows: [CIF embeds ; ASR decoder hidden].
 void Engine::seaco_head(int B, int L, const float* e0, const float* hid32, bool want_logits) {
-  const int D = mc_.d_model, V = mc_.vocab, Fs = mc_.seaco_ffn, ns = (int)sdec_.size();
+  const int D = mc_.d_model, V = mc_.vocab, Fs = mc_.seaco_ffn, ns = (int)bias_dec_.layers.size();
   const int N = n_hotwords_, J = 10, NJ = N * J;
   const int Md = B * L, R = 2 * Md;
   const int64_t NJp = round_up(NJ, 128) + 128, Rp = round_up(R, 128) + 128, Mdp = round_up(Md, 128) + 128;
   const int ldV = (int)round_up(V, 4);
-  size_t off = 0;
-  auto carve = [&](size_t bytes) { size_t o = off; off += round_up((int64_t)bytes, (int64_t)kAlign); return o; };
   // the hot-word side (ids, embedder, its K / V rows) lives in its own buffer and is computed once per hot-word LIST, not
   // once per call: it is a function of the weights and the list alone (the reference re-runs model_eb every call,
   // OfflineProjOfSeacoParaformer.cs:83-111, with the same result)
@@ -1671,25 +1670,20 @@ void Engine::seaco_head(int B, int L, const float* e0, const float* hid32, bool 
   const size_t o_cs = hcarve((size_t)N * D * 4), o_kv = hcarve((size_t)NJp * std::max(ns, 1) * 2 * D * 2);
   if (!ws_seaco_hw_.p || ws_seaco_hw_.bytes < hoff) seaco_hw_valid_ = false;
   ensure(ws_seaco_hw_, hoff);
-  const size_t o_x = carve((size_t)Rp * D * 4), o_xn = carve((size_t)Rp * D * 2), o_h32 = carve((size_t)Rp * Fs * 4);
-  const size_t o_h16 = carve((size_t)Rp * Fs * 2), o_t = carve((size_t)Rp * D * 4), o_tn = carve((size_t)Rp * D * 4);
-  const size_t o_q = carve((size_t)Rp * D * 2), o_ctx = carve((size_t)Rp * D * 2), o_hid = carve((size_t)Rp * D * 4);
-  const size_t o_m16 = carve((size_t)Mdp * D * 2), o_dha = carve((size_t)Mdp * ldV * 4), o_did = carve((size_t)Md * 8);
-  const size_t o_tn2 = carve((size_t)2 * B * 4);
-  ensure(ws_seaco_, off);
-  char* base = (char*)ws_seaco_.p;
+  float* hid = nullptr; half_t* m16 = nullptr; float* dha = nullptr; int64_t* dha_ids = nullptr; int32_t* tn2 = nullptr;
+  DecRun r;
+  r.b = carve_into(ws_seaco_, kAlign, [&](Arena& a) {
+    const DecBufs d = carve_dec16(a, Rp, Fs, true);
+    hid = a.take<float>((size_t)Rp * D * 4); m16 = a.take<half_t>((size_t)Mdp * D * 2);
+    dha = a.take<float>((size_t)Mdp * ldV * 4); dha_ids = a.take<int64_t>((size_t)Md * 8); tn2 = a.take<int32_t>((size_t)2 * B * 4);
+    return d;
+  });
+  float* xs = r.b.x; float* t32 = r.b.t32;
   char* hbase = (char*)ws_seaco_hw_.p;
   int32_t* ids = (int32_t*)(hbase + o_ids);
   float* e32 = (float*)(hbase + o_e32); half_t* in16 = (half_t*)(hbase + o_in16);
   float* xg = (float*)(hbase + o_xg); float* hout = (float*)(hbase + o_ho);
   half_t* hs = (half_t*)(hbase + o_hs); float* cs = (float*)(hbase + o_cs);
-  float* xs = (float*)(base + o_x); half_t* xn16 = (half_t*)(base + o_xn);
-  float* h32 = (float*)(base + o_h32); half_t* h16 = (half_t*)(base + o_h16);
-  float* t32 = (float*)(base + o_t); float* tn32 = (float*)(base + o_tn);
-  half_t* q16 = (half_t*)(base + o_q); half_t* ctx16 = (half_t*)(base + o_ctx);
-  float* hid = (float*)(base + o_hid); half_t* m16 = (half_t*)(base + o_m16);
-  float* dha = (float*)(base + o_dha); int64_t* dha_ids = (int64_t*)(base + o_did);
-  int32_t* tn2 = (int32_t*)(base + o_tn2);
   half_t* kv16 = (half_t*)(hbase + o_kv);
   const int ldkv = ns * 2 * D;
 
@@ -1711,7 +1705,7 @@ void Engine::seaco_head(int B, int L, const float* e0, const float* hid32, bool 
     prof_end("seaco_embed");
   }
   if (ns > 0 && !int8_mode_)
-    gemm("gemm_seaco", seaco_kv_all_, in16, D, NJ, nullptr, 0, kv16, ldkv, nullptr, 0, nullptr, 0, false, 0, 1.f);
+    gemm("gemm_seaco", bias_dec_.kv_all, in16, D, NJ, nullptr, 0, kv16, ldkv, nullptr, 0, nullptr, 0, false, 0, 1.f);
   if (ns > 0 && int8_mode_) seaco_kv_int8(hout, in16, NJ, kv16, ldkv);
   seaco_hw_valid_ = true;
   }
@@ -1721,61 +1715,35 @@ void Engine::seaco_head(int B, int L, const float* e0, const float* hid32, bool 
   PF_HIP(hipMemcpyAsync(xs + (size_t)Md * D, hid32, (size_t)Md * D * 4, hipMemcpyDeviceToDevice, stream_));
   PF_HIP(hipMemcpyAsync(tn2, plan_.token_num, (size_t)B * 4, hipMemcpyDeviceToDevice, stream_));
   PF_HIP(hipMemcpyAsync(tn2 + B, plan_.token_num, (size_t)B * 4, hipMemcpyDeviceToDevice, stream_));
-  const float qscale = 1.0f / std::sqrt((float)(D / mc_.heads));
+  r.B = 2 * B; r.L = L; r.token_num = tn2;
+  r.kv = kv16; r.kv_rs = ldkv; r.kv_bs = 0; r.Lk = NJ;                  // one bias_embed for every utterance
+  r.cls_ffn1 = r.cls_ffn2 = r.cls_q = r.cls_out = "gemm_seaco"; r.cls_attn = "attn_seaco";
   if (int8_mode_) {
-    // math_mode 2: the bias decoder's Linears are MatMulInteger pairs in model.int8.onnx like the ASR decoder's
-    seaco_decoder_int8(B, L, NJ, xs, h32, t32, tn32, q16, ctx16, kv16, ldkv, tn2, hid);
-    seaco_decoder_int8(B, L, NJ, xs + (size_t)Md * D, h32, t32, tn32, q16, ctx16, kv16, ldkv, tn2, hid + (size_t)Md * D);
-    prof_begin("seaco_merge", 0);
-    launch_add_f32(stream_, hid, hid + (size_t)Md * D, (int64_t)Md * D);
-    prof_end("seaco_merge");
-    qgemm("gemm_seaco", seaco_out_, true, hid, nullptr, D, Md, dha, ldV, nullptr, 0, nullptr, 0, nullptr, 0, false, 0, 1.f);
-    prof_begin("seaco_merge", 0);
-    launch_argmax(stream_, dha, Md, V, ldV, 2, dha_ids);
-    launch_seaco_merge(stream_, dha, ldV, dha_ids, Md, V, mc_.seaco_nobias, want_logits ? 1 : 0, logits_, logits_ld_, ids_dev_);
-    prof_end("seaco_merge");
-    return;
+    // math_mode 2: the bias decoder's Linears are MatMulInteger pairs in model.int8.onnx like the ASR decoder's.  The graph runs
+    // the decoder twice — on the CIF embeds and on the ASR decoder hidden — and each run has its own DynamicQuantizeLinear nodes,
+    // i.e. its own per-tensor ranges: the f16 path's single pass over 2 * B * L rows would merge the two ranges, so this mode
+    // runs one pass of B * L rows per half
+    r.B = B;
+    for (int half = 0; half < 2; ++half) {
+      r.b.x = xs + (size_t)half * Md * D;
+      decoder_int8(bias_dec_, r);
+      prof_begin("layernorm", 0);
+      launch_layernorm(stream_, t32, Md, D, bias_dec_.after.g, bias_dec_.after.b, nullptr, 0, hid + (size_t)half * Md * D, D);
+      prof_end("layernorm");
+    }
+  } else {
+    decoder16(bias_dec_, r);
+    prof_begin("layernorm", 0);
+    launch_layernorm(stream_, t32, R, D, bias_dec_.after.g, bias_dec_.after.b, nullptr, 0, hid, D);
+    prof_end("layernorm");
   }
-  auto ffn_dec = [&](const LNp& n1, const Lin& w1, const LNp& fn, const Lin& w2) {
-    prof_begin("layernorm", 0);
-    launch_layernorm(stream_, xs, R, D, n1.g, n1.b, xn16, D, nullptr, 0);
-    prof_end("layernorm");
-    dec_ffn_hidden("gemm_seaco", w1, fn, xn16, D, R, h16);
-    gemm("gemm_seaco", w2, h16, Fs, R, t32, D, nullptr, 0, nullptr, 0, nullptr, 0, false, 0, 1.f, false);
-  };
-  for (int i = 0; i < ns; ++i) {
-    const DecLayer& Lr = sdec_[i];
-    ffn_dec(Lr.norm1, Lr.w1, Lr.ffn_norm, Lr.w2);
-    prof_begin("layernorm", 0);
-    launch_layernorm(stream_, t32, R, D, Lr.norm2.g, Lr.norm2.b, nullptr, 0, tn32, D);
-    prof_end("layernorm");
-    prof_begin("fsmn", 0);
-    launch_fsmn_dec(stream_, tn32, Lr.fsmn_wT, tn2, 2 * B, L, D, mc_.seaco_kernel, xs);
-    prof_end("fsmn");
-    prof_begin("layernorm", 0);
-    launch_layernorm(stream_, xs, R, D, Lr.norm3.g, Lr.norm3.b, xn16, D, nullptr, 0);
-    prof_end("layernorm");
-    gemm("gemm_seaco", Lr.q, xn16, D, R, nullptr, 0, q16, D, nullptr, 0, nullptr, 0, false, D, qscale);
-    AttnArgs a{};
-    a.q = q16; a.q_bstride = (int64_t)L * D; a.q_rstride = D;
-    a.k = kv16 + (size_t)i * 2 * D; a.v = kv16 + (size_t)i * 2 * D + D;
-    a.k_bstride = a.v_bstride = 0; a.k_rstride = a.v_rstride = ldkv;      // one bias_embed for every utterance
-    a.o = ctx16; a.o_bstride = (int64_t)L * D; a.o_rstride = D;
-    a.B = 2 * B; a.H = mc_.heads; a.Lq = L; a.Lk = NJ;
-    prof_begin("attn_seaco", 4.0 * 2 * B * (double)L * NJ * D);
-    launch_attention(stream_, a);
-    prof_end("attn_seaco");
-    gemm("gemm_seaco", Lr.out, ctx16, D, R, xs, D, nullptr, 0, xs, D, nullptr, 0, false, 0, 1.f);
-  }
-  ffn_dec(seaco_final_norm1_, seaco_final_w1_, seaco_final_ffn_norm_, seaco_final_w2_);
-  prof_begin("layernorm", 0);
-  launch_layernorm(stream_, t32, R, D, seaco_after_.g, seaco_after_.b, nullptr, 0, hid, D);
-  prof_end("layernorm");
   // ---- merged = cif_attended + dec_attended -> hotword_output_layer -> NO-BIAS merge with the ASR rows
   prof_begin("seaco_merge", 0);
-  launch_add_to_f16(stream_, hid, hid + (size_t)Md * D, Md, D, m16);
+  if (int8_mode_) launch_add_f32(stream_, hid, hid + (size_t)Md * D, (int64_t)Md * D);
+  else launch_add_to_f16(stream_, hid, hid + (size_t)Md * D, Md, D, m16);
   prof_end("seaco_merge");
-  gemm("gemm_seaco", seaco_out_, m16, D, Md, dha, ldV, nullptr, 0, nullptr, 0, nullptr, 0, false, 0, 1.f);
+  if (int8_mode_) qgemm("gemm_seaco", bias_dec_.out, true, hid, nullptr, D, Md, dha, ldV, nullptr, 0, nullptr, 0, nullptr, 0, false, 0, 1.f);
+  else gemm("gemm_seaco", bias_dec_.out, m16, D, Md, dha, ldV, nullptr, 0, nullptr, 0, nullptr, 0, false, 0, 1.f);
   prof_begin("seaco_merge", 0);
   launch_argmax(stream_, dha, Md, V, ldV, 2, dha_ids);   // the NO-BIAS decision below is taken on the log-probs too
   launch_seaco_merge(stream_, dha, ldV, dha_ids, Md, V, mc_.seaco_nobias, want_logits ? 1 : 0, logits_, logits_ld_, ids_dev_);

@@ -69,6 +69,40 @@ struct DecLayer {
   half_t* out_wt = nullptr;    // the cross-attention out-projection weight in that kernel's fragment order: the NEXT block's launch runs it
   half_t* q_wt = nullptr;      // the cross-attention query projection in the same fragment order (k_decmid.hip; null: not built)
 };
+// the weights of one decoder stack (the ASR decoder, the SeACo bias decoder): layers, the final FFN block, after_norm, the
+// output layer and the K | V projections of all layers as one Linear [layers * 2D, D] (Engine::load_dec_stack)
+struct DecStack {
+  std::vector<DecLayer> layers;
+  LNp final_norm1, final_ffn_norm, after;
+  Lin final_w1, final_w2, out, kv_all;
+  half_t* final_img = nullptr;   // the final block's image for the split FFN form (DecLayer::ffn_img)
+  int ffn = 0, fsmn_k = 0;
+};
+// the activation buffers of one decoder walk [rows, *]; every arithmetic carves the ones its walk uses (Engine::carve_dec*)
+struct DecBufs {
+  float* x = nullptr; float* t32 = nullptr; float* tn32 = nullptr;                                   // residual stream, FFN-down result, norm2 of it
+  half_t* xn16 = nullptr; half_t* h16 = nullptr; half_t* q16 = nullptr; half_t* ctx16 = nullptr;     // f16 walks; int8: q16, ctx16
+  float* xn32 = nullptr; float* h32 = nullptr; float* hn32 = nullptr; float* q32 = nullptr; float* ctx32 = nullptr;   // fp32 walk; int8: h32
+};
+// one run of a decoder walk (decoder16 / decoder32 / decoder_int8): layers + the final block's FFN, FFN-down result left in t32
+struct DecRun {
+  int B = 0, L = 0;                        // rows = B * L; B is also the batch count of token_num
+  const int32_t* token_num = nullptr;
+  // K | V of layer i: kv + i * 2D with the strides below (projected ahead for all layers), or what kv_layer(i) returns (it
+  // enqueues that layer's projection; V = K + D either way).  kv_bs = 0: one set of rows for every utterance
+  const void* kv = nullptr; int kv_rs = 0; int64_t kv_bs = 0; int Lk = 0;
+  std::function<const void*(int)> kv_layer;
+  DecBufs b;
+  const char* cls_ffn1 = "gemm_dec_ffn1"; const char* cls_ffn2 = "gemm_dec_ffn2"; const char* cls_q = "gemm_dec_q";
+  const char* cls_out = "gemm_dec_out"; const char* cls_attn = "attn_cross";
+  bool operand_only = false;               // fp32: norm1 / norm3 / the context feed gemm32 alone (layernorm32, attention32 only_operand)
+  const float* cache_in = nullptr; float* cache_out = nullptr;   // f16 plain walk: the streaming FSMN with its caches [layers, B, D, k - 1]
+};
+// carves aligned buffers out of one allocation; with base == nullptr it only measures (Engine::carve_into)
+struct Arena {
+  char* base = nullptr; size_t align = 256; size_t off = 0;
+  template <class T> T* take(size_t bytes) { const size_t o = off; off += (bytes + align - 1) / align * align; return base ? (T*)(base + o) : nullptr; }
+};
 
 struct DevBuf {       // grow-only device allocation
   void* p = nullptr;
@@ -143,7 +177,7 @@ class Engine {
   void online_encoder(const float* speech, int B, int Tc, float* enc_out, float* alphas_out);
   void online_decoder(const float* enc, int B, int Tc, const float* embeds, int L, const int32_t* embeds_len,
                       const float* caches_in, float* logits_out, int64_t* ids_out, float* caches_out);
-  int dec_layers() const { return (int)dec_.size(); }
+  int dec_layers() const { return (int)dec_.layers.size(); }
 
   // ---- stand-alone ops (parity tests) -------------------------------------
   void op_lfr_cmvn_pad(const float* const* fbank, const int32_t* t80, int B, int sentinel, float* out,
@@ -204,6 +238,9 @@ class Engine {
   bool has_tensor(const std::string& name) const { return tensors_.count(name) != 0; }
   Lin make_lin(const std::string& prefix, bool bias);
   half_t* make_dec_ffn_image(const Lin& w1, const LNp& fn, const Lin& w2);
+  // layers, final block and after_norm of `prefix` (".layers.N", ".final", ".after_norm"); the caller loads `out`.  fused_images:
+  // also the weight images of the split FFN / fused middle forms (the ASR decoder alone takes those forms)
+  DecStack load_dec_stack(const std::string& prefix, int n_layers, int ffn, int fsmn_k, bool fused_images);
   LNp make_ln(const std::string& prefix, int width);
   void release();
   float* make_fsmn_wT(const std::string& name, int K = 0);
@@ -234,8 +271,7 @@ class Engine {
                      half_t* out16, int ld16, const float* resid, int ldr, const float* add2, int ld2, bool relu, int scale_cols,
                      float scale, const LNp* ln, int range);
   void seaco_kv_int8(const float* hw32, const half_t* hw16, int NJ, half_t* kv16, int ldkv);
-  void seaco_decoder_int8(int B, int L, int NJ, float* xs, float* h32, float* t32, float* tn32, half_t* q16, half_t* ctx16,
-                          const half_t* kv16, int ldkv, const int32_t* tn2, float* hid);
+  void decoder_int8(const DecStack& S, const DecRun& r);
   enum { kRangeOut = 1, kRangeIn = 2 };
   // quantise an activation tensor into `dst` (min / max pass, quantise pass); ln: of LayerNorm(x32), which is never stored
   void quantize_act(const QAct& dst, int kpad, const float* x32, const half_t* x16, int ldx, int64_t M, int K, const LNp* ln,
@@ -254,6 +290,18 @@ class Engine {
             int scale_cols, float scale, bool bias = true, int blocked = 0);   // blocked: 1 = out_f16 blocked, 2 = A blocked
   void gemm_small_call(const char* cls, const Lin& w, GemmSmallArgs g, bool bias = true);
   void dec_ffn_hidden(const char* cls, const Lin& w1, const LNp& fn, const half_t* xn16, int lda, int rows, half_t* h16);
+  void decoder16(const DecStack& S, const DecRun& r);      // f16: the plain nine-launch layer (bias decoder, streaming seam)
+  void decoder32(const DecStack& S, const DecRun& r);      // math_mode 1 / 3
+  AttnArgs cross_attn_args(const half_t* q, const half_t* k, const half_t* v, int kv_rs, int64_t kv_bs, half_t* o, int B, int L, int Lk) const;
+  // the walk buffers in the order every arena keeps them; rows = the arena's padded row count
+  DecBufs carve_dec16(Arena& a, int64_t rows, int F, bool with_h32);
+  DecBufs carve_dec32(Arena& a, int64_t rows, int F);
+  DecBufs carve_dec8(Arena& a, int64_t rows, int F);
+  template <class Fn> auto carve_into(DevBuf& ws, size_t align, Fn fn) {   // fn(Arena&) lays the arena out: once to measure, once in place
+    Arena m{nullptr, align}, a{nullptr, align};
+    fn(m); ensure(ws, m.off); a.base = (char*)ws.p;
+    return fn(a);
+  }
   void prof_begin(const char* cls, double flops);
   void prof_end(const char* cls);
 
@@ -329,17 +377,13 @@ class Engine {
   std::map<std::string, Tensor> tensors_;
   std::vector<void*> owned_;        // every other device allocation
   std::vector<EncLayer> enc_, tp_;
-  std::vector<DecLayer> dec_;
-  LNp enc_after_, tp_norm_, dec_final_norm1_, dec_final_ffn_norm_, dec_after_;
-  Lin cif_conv_, dec_kv_all_, dec_final_w1_, dec_final_w2_, dec_out_, ctc_;
-  half_t* dec_final_img_ = nullptr;  // the final block's image for the split FFN form (DecLayer::ffn_img)
+  DecStack dec_, bias_dec_;         // ASR decoder, SeACo bias decoder
+  LNp enc_after_, tp_norm_;
+  Lin cif_conv_, ctc_;
   const float* cif_out_w_ = nullptr;
   const float* cif_out_b_ = nullptr;
   struct LstmLayer { Lin ih; half_t* whh = nullptr; };
-  std::vector<DecLayer> sdec_;      // SeACo bias decoder
   std::vector<LstmLayer> seaco_lstm_;
-  Lin seaco_kv_all_, seaco_final_w1_, seaco_final_w2_, seaco_out_;
-  LNp seaco_final_norm1_, seaco_final_ffn_norm_, seaco_after_;
   const float* seaco_embed_w_ = nullptr;
   std::vector<int32_t> hotwords_;   // [n_hotwords_, 10]
   int n_hotwords_ = 0;

@@ -213,6 +213,47 @@ void Engine::enc_layer_fp32(const EncLayer& L, bool first, const float* speech_d
   cls32_ = "gemm32_misc";
 }
 
+DecBufs Engine::carve_dec32(Arena& a, int64_t rows, int F) {
+  const int D = mc_.d_model;
+  DecBufs d;
+  d.x = a.take<float>((size_t)rows * D * 4); d.xn32 = a.take<float>((size_t)rows * D * 4);
+  d.h32 = a.take<float>((size_t)rows * F * 4); d.hn32 = a.take<float>((size_t)rows * F * 4);
+  d.t32 = a.take<float>((size_t)rows * D * 4); d.tn32 = a.take<float>((size_t)rows * D * 4);
+  d.q32 = a.take<float>((size_t)rows * D * 4); d.ctx32 = a.take<float>((size_t)rows * D * 4);
+  return d;
+}
+
+// The decoder stack of the fp32 graph, one launch per node; leaves the final block's FFN-down result in t32.  The gemm32 calls
+// take the caller's cls32_.
+void Engine::decoder32(const DecStack& S, const DecRun& r) {
+  const int D = mc_.d_model, F = S.ffn, R = r.B * r.L;
+  const DecBufs& b = r.b;
+  const float qscale = 1.0f / std::sqrt((float)(D / mc_.heads));
+  auto norm_operand = [&](const LNp& ln) {                 // LayerNorm(x) -> xn32, the A operand of the gemm32 behind it
+    if (r.operand_only) layernorm32(b.x, R, D, ln, b.xn32);
+    else launch_layernorm(stream_, b.x, R, D, ln.g, ln.b, nullptr, 0, b.xn32, D);
+  };
+  auto ffn_dec = [&](const LNp& n1, const Lin& w1, const LNp& fn, const Lin& w2) {
+    norm_operand(n1);
+    gemm32(b.xn32, D, w1.w32, D, w1.bias, R, F, D, b.h32, F, nullptr, 0, true, 0, 1.f);
+    launch_layernorm(stream_, b.h32, R, F, fn.g, fn.b, nullptr, 0, b.hn32, F);
+    gemm32(b.hn32, F, w2.w32, F, nullptr, R, D, F, b.t32, D, nullptr, 0, false, 0, 1.f);
+  };
+  for (size_t i = 0; i < S.layers.size(); ++i) {
+    const DecLayer& Lr = S.layers[i];
+    ffn_dec(Lr.norm1, Lr.w1, Lr.ffn_norm, Lr.w2);
+    launch_layernorm(stream_, b.t32, R, D, Lr.norm2.g, Lr.norm2.b, nullptr, 0, b.tn32, D);
+    launch_fsmn_dec(stream_, b.tn32, Lr.fsmn_wT, r.token_num, r.B, r.L, D, S.fsmn_k, b.x);
+    norm_operand(Lr.norm3);
+    gemm32(b.xn32, D, Lr.q.w32, D, Lr.q.bias, R, D, D, b.q32, D, nullptr, 0, false, D, qscale);
+    const float* k = r.kv_layer ? (const float*)r.kv_layer((int)i) : (const float*)r.kv + i * 2 * D;
+    attention32(b.q32, (int64_t)r.L * D, D, k, r.kv_bs, r.kv_rs, k + D, r.kv_bs, r.kv_rs, b.ctx32, (int64_t)r.L * D, D, r.B, mc_.heads, r.L,
+                r.Lk, r.operand_only);
+    gemm32(b.ctx32, D, Lr.out.w32, D, Lr.out.bias, R, D, D, b.x, D, b.x, D, false, 0, 1.f);
+  }
+  ffn_dec(S.final_norm1, S.final_w1, S.final_ffn_norm, S.final_w2);
+}
+
 void Engine::forward_fp32(const float* speech_dev, int B, int T, bool want_logits) {
   const int D = mc_.d_model, F = mc_.ffn, V = mc_.vocab, Fd = mc_.feat_dim, M = B * T, T1 = T + 1;
   const int taps = mc_.cif_l_order + mc_.cif_r_order + 1;
@@ -282,17 +323,15 @@ void Engine::forward_fp32(const float* speech_dev, int B, int T, bool want_logit
   if (L == 0) return;
   // ---- decoder
   const int Md = B * L;
-  size_t o2 = 0;
-  auto c2 = [&](size_t bytes) { size_t o = o2; o2 += round_up((int64_t)bytes, (int64_t)kAlign); return o; };
-  const size_t o_x = c2((size_t)Md * D * 4), o_xn = c2((size_t)Md * D * 4), o_h = c2((size_t)Md * F * 4), o_hn = c2((size_t)Md * F * 4);
-  const size_t o_t = c2((size_t)Md * D * 4), o_tn2 = c2((size_t)Md * D * 4), o_q = c2((size_t)Md * D * 4), o_ctx = c2((size_t)Md * D * 4);
-  const size_t o_kv = c2((size_t)M * 2 * D * 4), o_lg = c2((size_t)Md * ldV * 4), o_ids = c2((size_t)Md * 8);
-  ensure(ws_dec_, o2);
-  char* b2 = (char*)ws_dec_.p;
-  float* xd = (float*)(b2 + o_x); float* xn = (float*)(b2 + o_xn); float* hd = (float*)(b2 + o_h); float* hn = (float*)(b2 + o_hn);
-  float* t32 = (float*)(b2 + o_t); float* tn32 = (float*)(b2 + o_tn2); float* qd = (float*)(b2 + o_q); float* cx = (float*)(b2 + o_ctx);
-  float* kv = (float*)(b2 + o_kv);
-  logits_ = (float*)(b2 + o_lg); ids_dev_ = (int64_t*)(b2 + o_ids); logits_ld_ = ldV;
+  float* kv = nullptr;
+  DecRun r;
+  r.b = carve_into(ws_dec_, kAlign, [&](Arena& a) {
+    const DecBufs d = carve_dec32(a, Md, F);
+    kv = a.take<float>((size_t)M * 2 * D * 4); logits_ = a.take<float>((size_t)Md * ldV * 4); ids_dev_ = a.take<int64_t>((size_t)Md * 8);
+    return d;
+  });
+  float* xd = r.b.x; float* xn = r.b.xn32; float* t32 = r.b.t32;
+  logits_ld_ = ldV;
   if (mc_.cif_cumsum) launch_cif_gather_cumsum(stream_, H32_, alphas_, B, T, D, T1, plan_, L, xd);
   else launch_cif_gather(stream_, H32_, B, T, D, T1, plan_, L, xd);
   const bool bias_branch = mc_.seaco && n_hotwords_ > 0;
@@ -302,30 +341,19 @@ void Engine::forward_fp32(const float* speech_dev, int B, int T, bool want_logit
     e0 = (float*)ws_seaco_in_.p;
     PF_HIP(hipMemcpyAsync(e0, xd, (size_t)Md * D * 4, hipMemcpyDeviceToDevice, stream_));
   }
-  const float qscale = 1.0f / std::sqrt((float)(D / mc_.heads));
   cls32_ = "gemm32_dec";
-  auto ffn_dec = [&](const LNp& n1, const Lin& w1, const LNp& fn, const Lin& w2) {
-    layernorm32(xd, Md, D, n1, xn);
-    gemm32(xn, D, w1.w32, D, w1.bias, Md, F, D, hd, F, nullptr, 0, true, 0, 1.f);
-    launch_layernorm(stream_, hd, Md, F, fn.g, fn.b, nullptr, 0, hn, F);
-    gemm32(hn, F, w2.w32, F, nullptr, Md, D, F, t32, D, nullptr, 0, false, 0, 1.f);
+  r.B = B; r.L = L; r.token_num = plan_.token_num;
+  r.kv_rs = 2 * D; r.kv_bs = (int64_t)T * 2 * D; r.Lk = T;
+  r.kv_layer = [&](int i) -> const void* {                 // layer i's K | V of the encoder memory
+    const Lin& w = dec_.layers[i].kv32;
+    gemm32(H32_, D, w.w32, D, w.bias, M, 2 * D, D, kv, 2 * D, nullptr, 0, false, 0, 1.f);
+    return kv;
   };
-  for (size_t i = 0; i < dec_.size(); ++i) {
-    const DecLayer& Lr = dec_[i];
-    ffn_dec(Lr.norm1, Lr.w1, Lr.ffn_norm, Lr.w2);
-    launch_layernorm(stream_, t32, Md, D, Lr.norm2.g, Lr.norm2.b, nullptr, 0, tn32, D);
-    launch_fsmn_dec(stream_, tn32, Lr.fsmn_wT, plan_.token_num, B, L, D, mc_.kernel, xd);
-    layernorm32(xd, Md, D, Lr.norm3, xn);
-    gemm32(xn, D, Lr.q.w32, D, Lr.q.bias, Md, D, D, qd, D, nullptr, 0, false, D, qscale);
-    gemm32(H32_, D, Lr.kv32.w32, D, Lr.kv32.bias, M, 2 * D, D, kv, 2 * D, nullptr, 0, false, 0, 1.f);
-    attention32(qd, (int64_t)L * D, D, kv, (int64_t)T * 2 * D, 2 * D, kv + D, (int64_t)T * 2 * D, 2 * D, cx,
-                         (int64_t)L * D, D, B, mc_.heads, L, T, true);
-    gemm32(cx, D, Lr.out.w32, D, Lr.out.bias, Md, D, D, xd, D, xd, D, false, 0, 1.f);
-  }
-  ffn_dec(dec_final_norm1_, dec_final_w1_, dec_final_ffn_norm_, dec_final_w2_);
-  launch_layernorm(stream_, t32, Md, D, dec_after_.g, dec_after_.b, nullptr, 0, xn, D);
+  r.operand_only = true;
+  decoder32(dec_, r);
+  launch_layernorm(stream_, t32, Md, D, dec_.after.g, dec_.after.b, nullptr, 0, xn, D);
   cls32_ = "gemm32_vocab";
-  gemm32(xn, D, dec_out_.w32, D, dec_out_.bias, Md, V, D, logits_, ldV, nullptr, 0, false, 0, 1.f);
+  gemm32(xn, D, dec_.out.w32, D, dec_.out.bias, Md, V, D, logits_, ldV, nullptr, 0, false, 0, 1.f);
   launch_argmax(stream_, logits_, Md, V, ldV, argmax_mode(want_logits), ids_dev_, score_buf(Md));
   cls32_ = "gemm32_misc";
   if (bias_branch) seaco_head_fp32(B, L, e0, xn, want_logits);      // xn = the ASR decoder's after_norm hidden
@@ -403,27 +431,23 @@ void Engine::timestamp_head_fp32(int B, int T) {
 }
 
 void Engine::seaco_head_fp32(int B, int L, const float* e0, const float* hid_asr, bool want_logits) {
-  const int D = mc_.d_model, V = mc_.vocab, Fs = mc_.seaco_ffn, ns = (int)sdec_.size();
+  const int D = mc_.d_model, V = mc_.vocab, Fs = mc_.seaco_ffn;
   const int N = n_hotwords_, J = 10, NJ = N * J;
   const int Md = B * L, R = 2 * Md;
   const int ldV = (int)round_up(V, 4);
-  size_t off = 0;
-  auto carve = [&](size_t bytes) { size_t o = off; off += round_up((int64_t)bytes, (int64_t)kAlign); return o; };
-  const size_t o_ids = carve((size_t)NJ * 4), o_e = carve((size_t)NJ * D * 4), o_e2 = carve((size_t)NJ * D * 4), o_xg = carve((size_t)NJ * 4 * D * 4);
-  const size_t o_g = carve((size_t)N * 4 * D * 4), o_hb = carve((size_t)N * D * 4), o_cb = carve((size_t)N * D * 4);
-  const size_t o_kv = carve((size_t)NJ * 2 * D * 4), o_x = carve((size_t)R * D * 4), o_xn = carve((size_t)R * D * 4);
-  const size_t o_h = carve((size_t)R * Fs * 4), o_hn = carve((size_t)R * Fs * 4), o_t = carve((size_t)R * D * 4), o_tn = carve((size_t)R * D * 4);
-  const size_t o_q = carve((size_t)R * D * 4), o_cx = carve((size_t)R * D * 4), o_hid = carve((size_t)R * D * 4);
-  const size_t o_dha = carve((size_t)Md * ldV * 4), o_did = carve((size_t)Md * 8), o_tn2 = carve((size_t)2 * B * 4);
-  ensure(ws_seaco_, off);
-  char* base = (char*)ws_seaco_.p;
-  int32_t* ids = (int32_t*)(base + o_ids);
-  float* ea = (float*)(base + o_e); float* eb = (float*)(base + o_e2); float* xg = (float*)(base + o_xg);
-  float* gates = (float*)(base + o_g); float* hb = (float*)(base + o_hb); float* cb = (float*)(base + o_cb);
-  float* kv = (float*)(base + o_kv); float* xs = (float*)(base + o_x); float* xn = (float*)(base + o_xn);
-  float* hd = (float*)(base + o_h); float* hn = (float*)(base + o_hn); float* t32 = (float*)(base + o_t); float* tn32 = (float*)(base + o_tn);
-  float* qd = (float*)(base + o_q); float* cx = (float*)(base + o_cx); float* hid = (float*)(base + o_hid);
-  float* dha = (float*)(base + o_dha); int64_t* dha_ids = (int64_t*)(base + o_did); int32_t* tn2 = (int32_t*)(base + o_tn2);
+  int32_t* ids = nullptr; float* ea = nullptr; float* eb = nullptr; float* xg = nullptr; float* gates = nullptr; float* hb = nullptr;
+  float* cb = nullptr; float* kv = nullptr; float* hid = nullptr; float* dha = nullptr; int64_t* dha_ids = nullptr; int32_t* tn2 = nullptr;
+  DecRun r;
+  r.b = carve_into(ws_seaco_, kAlign, [&](Arena& a) {
+    ids = a.take<int32_t>((size_t)NJ * 4); ea = a.take<float>((size_t)NJ * D * 4); eb = a.take<float>((size_t)NJ * D * 4);
+    xg = a.take<float>((size_t)NJ * 4 * D * 4); gates = a.take<float>((size_t)N * 4 * D * 4);
+    hb = a.take<float>((size_t)N * D * 4); cb = a.take<float>((size_t)N * D * 4); kv = a.take<float>((size_t)NJ * 2 * D * 4);
+    const DecBufs d = carve_dec32(a, R, Fs);
+    hid = a.take<float>((size_t)R * D * 4); dha = a.take<float>((size_t)Md * ldV * 4); dha_ids = a.take<int64_t>((size_t)Md * 8);
+    tn2 = a.take<int32_t>((size_t)2 * B * 4);
+    return d;
+  });
+  float* xs = r.b.x; float* t32 = r.b.t32;
   // ---- hotword embedder: Embedding -> LSTM stack (all J outputs kept), rows n * J + j
   PF_HIP(hipMemcpyAsync(ids, hotwords_.data(), (size_t)NJ * 4, hipMemcpyHostToDevice, stream_));
   launch_embed_gather(stream_, seaco_embed_w_, ids, NJ, D, (int)tensor("seaco.embed.weight").shape[0], ea, nullptr);
@@ -441,29 +465,18 @@ void Engine::seaco_head_fp32(int B, int L, const float* e0, const float* hid_asr
   PF_HIP(hipMemcpyAsync(xs + (size_t)Md * D, hid_asr, (size_t)Md * D * 4, hipMemcpyDeviceToDevice, stream_));
   PF_HIP(hipMemcpyAsync(tn2, plan_.token_num, (size_t)B * 4, hipMemcpyDeviceToDevice, stream_));
   PF_HIP(hipMemcpyAsync(tn2 + B, plan_.token_num, (size_t)B * 4, hipMemcpyDeviceToDevice, stream_));
-  const float qscale = 1.0f / std::sqrt((float)(D / mc_.heads));
-  auto ffn_dec = [&](const LNp& n1, const Lin& w1, const LNp& fn, const Lin& w2) {
-    launch_layernorm(stream_, xs, R, D, n1.g, n1.b, nullptr, 0, xn, D);
-    gemm32(xn, D, w1.w32, D, w1.bias, R, Fs, D, hd, Fs, nullptr, 0, true, 0, 1.f);
-    launch_layernorm(stream_, hd, R, Fs, fn.g, fn.b, nullptr, 0, hn, Fs);
-    gemm32(hn, Fs, w2.w32, Fs, nullptr, R, D, Fs, t32, D, nullptr, 0, false, 0, 1.f);
+  r.B = 2 * B; r.L = L; r.token_num = tn2;
+  r.kv_rs = 2 * D; r.kv_bs = 0; r.Lk = NJ;                 // one bias_embed for every utterance
+  r.kv_layer = [&](int i) -> const void* {
+    const Lin& w = bias_dec_.layers[i].kv32;
+    gemm32(bias_embed, D, w.w32, D, w.bias, NJ, 2 * D, D, kv, 2 * D, nullptr, 0, false, 0, 1.f);
+    return kv;
   };
-  for (int i = 0; i < ns; ++i) {
-    const DecLayer& Lr = sdec_[i];
-    ffn_dec(Lr.norm1, Lr.w1, Lr.ffn_norm, Lr.w2);
-    launch_layernorm(stream_, t32, R, D, Lr.norm2.g, Lr.norm2.b, nullptr, 0, tn32, D);
-    launch_fsmn_dec(stream_, tn32, Lr.fsmn_wT, tn2, 2 * B, L, D, mc_.seaco_kernel, xs);
-    launch_layernorm(stream_, xs, R, D, Lr.norm3.g, Lr.norm3.b, nullptr, 0, xn, D);
-    gemm32(xn, D, Lr.q.w32, D, Lr.q.bias, R, D, D, qd, D, nullptr, 0, false, D, qscale);
-    gemm32(bias_embed, D, Lr.kv32.w32, D, Lr.kv32.bias, NJ, 2 * D, D, kv, 2 * D, nullptr, 0, false, 0, 1.f);
-    attention32(qd, (int64_t)L * D, D, kv, 0, 2 * D, kv + D, 0, 2 * D, cx, (int64_t)L * D, D, 2 * B, mc_.heads, L, NJ);
-    gemm32(cx, D, Lr.out.w32, D, Lr.out.bias, R, D, D, xs, D, xs, D, false, 0, 1.f);
-  }
-  ffn_dec(seaco_final_norm1_, seaco_final_w1_, seaco_final_ffn_norm_, seaco_final_w2_);
-  launch_layernorm(stream_, t32, R, D, seaco_after_.g, seaco_after_.b, nullptr, 0, hid, D);
+  decoder32(bias_dec_, r);
+  launch_layernorm(stream_, t32, R, D, bias_dec_.after.g, bias_dec_.after.b, nullptr, 0, hid, D);
   // ---- merged = cif_attended + dec_attended -> hotword_output_layer -> NO-BIAS merge with the ASR rows
   launch_add_f32(stream_, hid, hid + (size_t)Md * D, (int64_t)Md * D);
-  gemm32(hid, D, seaco_out_.w32, D, seaco_out_.bias, Md, V, D, dha, ldV, nullptr, 0, false, 0, 1.f);
+  gemm32(hid, D, bias_dec_.out.w32, D, bias_dec_.out.bias, Md, V, D, dha, ldV, nullptr, 0, false, 0, 1.f);
   launch_argmax(stream_, dha, Md, V, ldV, 2, dha_ids);
   launch_seaco_merge(stream_, dha, ldV, dha_ids, Md, V, mc_.seaco_nobias, want_logits ? 1 : 0, logits_, logits_ld_, ids_dev_);
 }

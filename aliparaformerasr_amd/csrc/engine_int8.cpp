@@ -285,18 +285,17 @@ void Engine::forward_int8(const float* speech_dev, int B, int T, bool want_logit
   // ---- decoder
   const int Md = B * L;
   const int64_t Mdp = round_up(Md, 128) + 128;
-  size_t o2 = 0;
-  auto c2 = [&](size_t bytes) { size_t o = o2; o2 += round_up((int64_t)bytes, (int64_t)kAlignQ); return o; };
-  const size_t o_xd = c2(Mdp * D * 4), o_hd = c2(Mdp * F * 4);
-  const size_t o_td = c2(Mdp * D * 4), o_tn2 = c2(Mdp * D * 4), o_q = c2(Mdp * D * 2), o_cx = c2(Mdp * D * 2);
-  const size_t o_kv = c2((size_t)Mp * 2 * D * 2), o_lg = c2((size_t)Mdp * ldV * 4), o_ids = c2((size_t)Md * 8);
-  const size_t o_qh = c2((size_t)(Mp + 256) * round_up(D, 128)), o_qhr = c2((size_t)(Mp + 256) * 4), o_qhp = c2(64);
-  ensure(ws_dec_, o2);
-  char* b2 = (char*)ws_dec_.p;
-  float* xd = (float*)(b2 + o_xd); float* hd = (float*)(b2 + o_hd);
-  float* t32 = (float*)(b2 + o_td); float* tn32 = (float*)(b2 + o_tn2);
-  half_t* qd16 = (half_t*)(b2 + o_q); half_t* cx16 = (half_t*)(b2 + o_cx); half_t* kv16 = (half_t*)(b2 + o_kv);
-  logits_ = (float*)(b2 + o_lg); ids_dev_ = (int64_t*)(b2 + o_ids); logits_ld_ = ldV;
+  half_t* kv16 = nullptr;
+  QAct qH;                                             // the quantised encoder memory (below)
+  DecRun r;
+  r.b = carve_into(ws_dec_, kAlignQ, [&](Arena& a) {
+    const DecBufs d = carve_dec8(a, Mdp, F);
+    kv16 = a.take<half_t>((size_t)Mp * 2 * D * 2); logits_ = a.take<float>((size_t)Mdp * ldV * 4); ids_dev_ = a.take<int64_t>((size_t)Md * 8);
+    qH.a = a.take<int8_t>((size_t)(Mp + 256) * round_up(D, 128)); qH.rowsum = a.take<int32_t>((size_t)(Mp + 256) * 4); qH.params = a.take<float>(64);
+    return d;
+  });
+  float* xd = r.b.x; float* t32 = r.b.t32;
+  logits_ld_ = ldV;
   prof_begin("cif_misc", 0);
   if (mc_.cif_cumsum) launch_cif_gather_cumsum(stream_, H32_, alphas_, B, T, D, T1, plan_, L, xd);
   else launch_cif_gather(stream_, H32_, B, T, D, T1, plan_, L, xd);
@@ -310,52 +309,26 @@ void Engine::forward_int8(const float* speech_dev, int B, int T, bool want_logit
     hid32 = e0 + (size_t)Mdp * D;
     PF_HIP(hipMemcpyAsync(e0, xd, (size_t)Md * D * 4, hipMemcpyDeviceToDevice, stream_));
   }
-  auto ffn_dec = [&](const LNp& n1, const Lin& w1, const LNp& fn, const Lin& w2) {
-    qgemm("gemm_dec_ffn1", w1, true, xd, nullptr, D, Md, hd, F, nullptr, 0, nullptr, 0, nullptr, 0, true, 0, 1.f, &n1);
-    qgemm("gemm_dec_ffn2", w2, false, hd, nullptr, F, Md, t32, D, nullptr, 0, nullptr, 0, nullptr, 0, false, 0, 1.f, &fn);
-  };
   // K / V of the encoder memory: every layer's MatMul quantises the SAME tensor — one DynamicQuantizeLinear result here
-  QAct qH;
-  {
-    const int kp = (int)round_up(D, 128);
-    qH.a = (int8_t*)(b2 + o_qh); qH.rowsum = (int32_t*)(b2 + o_qhr); qH.params = (float*)(b2 + o_qhp);
-    quantize_act(qH, kp, H32_, nullptr, D, M, D, nullptr);
-  }
-  for (size_t i = 0; i < dec_.size(); ++i) {
-    const DecLayer& Lr = dec_[i];
-    ffn_dec(Lr.norm1, Lr.w1, Lr.ffn_norm, Lr.w2);
-    prof_begin("layernorm", 0);
-    launch_layernorm(stream_, t32, Md, D, Lr.norm2.g, Lr.norm2.b, nullptr, 0, tn32, D);
-    prof_end("layernorm");
-    prof_begin("fsmn", 0);
-    launch_fsmn_dec(stream_, tn32, Lr.fsmn_wT, plan_.token_num, B, L, D, mc_.kernel, xd);
-    prof_end("fsmn");
-    qgemm("gemm_dec_q", Lr.q, true, xd, nullptr, D, Md, nullptr, 0, qd16, D, nullptr, 0, nullptr, 0, false, D, qscale, &Lr.norm3);
-    if (lin_quantised(Lr.kv32))
-      qgemm("gemm_dec_kv", Lr.kv32, true, nullptr, nullptr, D, (int)M, nullptr, 0, kv16, 2 * D, nullptr, 0, nullptr, 0, false, 0, 1.f, nullptr, &qH);
+  quantize_act(qH, (int)round_up(D, 128), H32_, nullptr, D, M, D, nullptr);
+  r.B = B; r.L = L; r.token_num = plan_.token_num;
+  r.kv_rs = 2 * D; r.kv_bs = (int64_t)T * 2 * D; r.Lk = T;
+  r.kv_layer = [&](int i) -> const void* {
+    const Lin& kv = dec_.layers[i].kv32;
+    if (lin_quantised(kv))
+      qgemm("gemm_dec_kv", kv, true, nullptr, nullptr, D, (int)M, nullptr, 0, kv16, 2 * D, nullptr, 0, nullptr, 0, false, 0, 1.f, nullptr, &qH);
     else
-      gemm("gemm_dec_kv", Lr.kv32, H16_, D, (int)M, nullptr, 0, kv16, 2 * D, nullptr, 0, nullptr, 0, false, 0, 1.f);
-    AttnArgs a{};
-    a.q = qd16; a.q_bstride = (int64_t)L * D; a.q_rstride = D;
-    a.k = kv16; a.v = kv16 + D; a.k_bstride = a.v_bstride = (int64_t)T * 2 * D; a.k_rstride = a.v_rstride = 2 * D;
-    a.o = cx16; a.o_bstride = (int64_t)L * D; a.o_rstride = D;
-    a.B = B; a.H = mc_.heads; a.Lq = L; a.Lk = T;
-    const bool cx_range = attention_reports_range(a);
-    a.range = cx_range ? q_part_ : nullptr;
-    prof_begin("attn_cross", 4.0 * B * (double)L * T * D);
-    launch_attention(stream_, a);
-    prof_end("attn_cross");
-    qgemm("gemm_dec_out", Lr.out, true, nullptr, cx16, D, Md, xd, D, nullptr, 0, xd, D, nullptr, 0, false, 0, 1.f, nullptr, nullptr,
-          cx_range ? kRangeIn : 0);
-  }
-  ffn_dec(dec_final_norm1_, dec_final_w1_, dec_final_ffn_norm_, dec_final_w2_);
+      gemm("gemm_dec_kv", kv, H16_, D, (int)M, nullptr, 0, kv16, 2 * D, nullptr, 0, nullptr, 0, false, 0, 1.f);
+    return kv16;
+  };
+  decoder_int8(dec_, r);
   if (bias_branch) {                                   // the bias decoder's second input: the after_norm hidden itself
     prof_begin("layernorm", 0);
-    launch_layernorm(stream_, t32, Md, D, dec_after_.g, dec_after_.b, nullptr, 0, hid32, D);
+    launch_layernorm(stream_, t32, Md, D, dec_.after.g, dec_.after.b, nullptr, 0, hid32, D);
     prof_end("layernorm");
-    qgemm("gemm_vocab", dec_out_, true, hid32, nullptr, D, Md, logits_, ldV, nullptr, 0, nullptr, 0, nullptr, 0, false, 0, 1.f);
+    qgemm("gemm_vocab", dec_.out, true, hid32, nullptr, D, Md, logits_, ldV, nullptr, 0, nullptr, 0, nullptr, 0, false, 0, 1.f);
   } else {
-    qgemm("gemm_vocab", dec_out_, true, t32, nullptr, D, Md, logits_, ldV, nullptr, 0, nullptr, 0, nullptr, 0, false, 0, 1.f, &dec_after_);
+    qgemm("gemm_vocab", dec_.out, true, t32, nullptr, D, Md, logits_, ldV, nullptr, 0, nullptr, 0, nullptr, 0, false, 0, 1.f, &dec_.after);
   }
   prof_begin("argmax", 0);
   launch_argmax(stream_, logits_, Md, V, ldV, argmax_mode(want_logits), ids_dev_, score_buf(Md));
@@ -379,8 +352,8 @@ void Engine::seaco_kv_int8(const float* hw32, const half_t* hw16, int NJ, half_t
   char* b = (char*)ws_seaco_q_.p;
   q.a = (int8_t*)b; q.rowsum = (int32_t*)(b + (size_t)rp * kp); q.params = (float*)(b + (size_t)rp * kp + (size_t)rp * 4);
   quantize_act(q, kp, hw32, nullptr, D, NJ, D, nullptr);
-  for (size_t i = 0; i < sdec_.size(); ++i) {
-    const Lin& kv = sdec_[i].kv32;
+  for (size_t i = 0; i < bias_dec_.layers.size(); ++i) {
+    const Lin& kv = bias_dec_.layers[i].kv32;
     // a [NJ, 2D] slice of the [NJ, ns * 2D] buffer: f16-only results with a row stride of ldkv
     if (lin_quantised(kv))
       qgemm("gemm_seaco", kv, true, nullptr, nullptr, D, NJ, nullptr, 0, kv16 + i * 2 * D, ldkv, nullptr, 0, nullptr, 0, false, 0, 1.f, nullptr, &q);
@@ -389,46 +362,47 @@ void Engine::seaco_kv_int8(const float* hw32, const half_t* hw16, int NJ, half_t
   }
 }
 
-// ONE pass of the bias decoder over R = B * L rows (xs); leaves after_norm(x) in hid [R, D].  The graph runs the decoder
-// twice — on the CIF embeds and on the ASR decoder hidden — and each run has its own DynamicQuantizeLinear nodes, i.e. its
-// own per-tensor ranges: the f16 path's single pass over 2 * B * L rows would merge the two ranges, so this mode runs two.
-void Engine::seaco_decoder_int8(int B, int L, int NJ, float* xs, float* h32, float* t32, float* tn32, half_t* q16, half_t* ctx16,
-                                const half_t* kv16, int ldkv, const int32_t* tn2, float* hid) {
-  const int D = mc_.d_model, Fs = mc_.seaco_ffn, R = B * L;
+DecBufs Engine::carve_dec8(Arena& a, int64_t rows, int F) {
+  const int D = mc_.d_model;
+  DecBufs d;
+  d.x = a.take<float>((size_t)rows * D * 4); d.h32 = a.take<float>((size_t)rows * F * 4);
+  d.t32 = a.take<float>((size_t)rows * D * 4); d.tn32 = a.take<float>((size_t)rows * D * 4);
+  d.q16 = a.take<half_t>((size_t)rows * D * 2); d.ctx16 = a.take<half_t>((size_t)rows * D * 2);
+  return d;
+}
+
+// The decoder stack in math_mode 2: every Linear a qgemm with the LayerNorm in front of it folded into its quantise pass;
+// leaves the final block's FFN-down result in t32.
+void Engine::decoder_int8(const DecStack& S, const DecRun& r) {
+  const int D = mc_.d_model, F = S.ffn, R = r.B * r.L;
+  const DecBufs& b = r.b;
   const float qscale = 1.0f / std::sqrt((float)(D / mc_.heads));
   if (!q_part_) q_part_ = (float*)dalloc(quant_scratch_bytes());
   auto ffn_dec = [&](const LNp& n1, const Lin& w1, const LNp& fn, const Lin& w2) {
-    qgemm("gemm_seaco", w1, true, xs, nullptr, D, R, h32, Fs, nullptr, 0, nullptr, 0, nullptr, 0, true, 0, 1.f, &n1);
-    qgemm("gemm_seaco", w2, false, h32, nullptr, Fs, R, t32, D, nullptr, 0, nullptr, 0, nullptr, 0, false, 0, 1.f, &fn);
+    qgemm(r.cls_ffn1, w1, true, b.x, nullptr, D, R, b.h32, F, nullptr, 0, nullptr, 0, nullptr, 0, true, 0, 1.f, &n1);
+    qgemm(r.cls_ffn2, w2, false, b.h32, nullptr, F, R, b.t32, D, nullptr, 0, nullptr, 0, nullptr, 0, false, 0, 1.f, &fn);
   };
-  for (size_t i = 0; i < sdec_.size(); ++i) {
-    const DecLayer& Lr = sdec_[i];
+  for (size_t i = 0; i < S.layers.size(); ++i) {
+    const DecLayer& Lr = S.layers[i];
     ffn_dec(Lr.norm1, Lr.w1, Lr.ffn_norm, Lr.w2);
     prof_begin("layernorm", 0);
-    launch_layernorm(stream_, t32, R, D, Lr.norm2.g, Lr.norm2.b, nullptr, 0, tn32, D);
+    launch_layernorm(stream_, b.t32, R, D, Lr.norm2.g, Lr.norm2.b, nullptr, 0, b.tn32, D);
     prof_end("layernorm");
     prof_begin("fsmn", 0);
-    launch_fsmn_dec(stream_, tn32, Lr.fsmn_wT, tn2, B, L, D, mc_.seaco_kernel, xs);
+    launch_fsmn_dec(stream_, b.tn32, Lr.fsmn_wT, r.token_num, r.B, r.L, D, S.fsmn_k, b.x);
     prof_end("fsmn");
-    qgemm("gemm_seaco", Lr.q, true, xs, nullptr, D, R, nullptr, 0, q16, D, nullptr, 0, nullptr, 0, false, D, qscale, &Lr.norm3);
-    AttnArgs a{};
-    a.q = q16; a.q_bstride = (int64_t)L * D; a.q_rstride = D;
-    a.k = kv16 + i * 2 * D; a.v = kv16 + i * 2 * D + D;
-    a.k_bstride = a.v_bstride = 0; a.k_rstride = a.v_rstride = ldkv;
-    a.o = ctx16; a.o_bstride = (int64_t)L * D; a.o_rstride = D;
-    a.B = B; a.H = mc_.heads; a.Lq = L; a.Lk = NJ;
-    const bool cx_range = attention_reports_range(a);
+    qgemm(r.cls_q, Lr.q, true, b.x, nullptr, D, R, nullptr, 0, b.q16, D, nullptr, 0, nullptr, 0, false, D, qscale, &Lr.norm3);
+    const half_t* k16 = r.kv_layer ? (const half_t*)r.kv_layer((int)i) : (const half_t*)r.kv + i * 2 * D;
+    AttnArgs a = cross_attn_args(b.q16, k16, k16 + D, r.kv_rs, r.kv_bs, b.ctx16, r.B, r.L, r.Lk);
+    const bool cx_range = attention_reports_range(a);     // the context's {min, max} from the attention epilogue: no min / max pass
     a.range = cx_range ? q_part_ : nullptr;
-    prof_begin("attn_seaco", 4.0 * B * (double)L * NJ * D);
+    prof_begin(r.cls_attn, 4.0 * r.B * (double)r.L * r.Lk * D);
     launch_attention(stream_, a);
-    prof_end("attn_seaco");
-    qgemm("gemm_seaco", Lr.out, true, nullptr, ctx16, D, R, xs, D, nullptr, 0, xs, D, nullptr, 0, false, 0, 1.f, nullptr, nullptr,
+    prof_end(r.cls_attn);
+    qgemm(r.cls_out, Lr.out, true, nullptr, b.ctx16, D, R, b.x, D, nullptr, 0, b.x, D, nullptr, 0, false, 0, 1.f, nullptr, nullptr,
           cx_range ? kRangeIn : 0);
   }
-  ffn_dec(seaco_final_norm1_, seaco_final_w1_, seaco_final_ffn_norm_, seaco_final_w2_);
-  prof_begin("layernorm", 0);
-  launch_layernorm(stream_, t32, R, D, seaco_after_.g, seaco_after_.b, nullptr, 0, hid, D);
-  prof_end("layernorm");
+  ffn_dec(S.final_norm1, S.final_w1, S.final_ffn_norm, S.final_w2);
 }
 
 // stand-alone operator (parity tests): one dynamically quantised Linear, nothing cached
