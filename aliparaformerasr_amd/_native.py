@@ -27,6 +27,7 @@ PF_ERR_RECOGNITION = -10
 PF_DECODE_SCORES = 1
 PF_DECODE_CTC = 2
 PF_DECODE_TOPK = 8
+PF_DECODE_CTC_BEAM = 16
 PF_TOPK_MAX = 8
 PF_NBEST_MAX = 64
 
@@ -164,6 +165,13 @@ SIGNATURES = {
     "pf_op_topk": (C.c_int, [_vp, _f, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _i64, _f, _i32]),
     "pf_host_nbest": (C.c_int, [_i64, _f, _i32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _i32, _P(C.c_double), _i32]),
     "pf_recognizer_set_nbest": (C.c_int, [_vp, C.c_int32, C.c_int32]),
+    "pf_engine_set_ctc_beam": (C.c_int, [_vp, C.c_int32, C.c_int32]),
+    "pf_fetch_ctc_beam": (C.c_int, [_vp, _i64, _i32, _P(C.c_double), C.c_int32, _i32, _i32]),
+    "pf_host_ctc_beam": (C.c_int, [_f, C.c_int64, _i64, _f, _i32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _i64, _i32,
+                                   _P(C.c_double), C.c_int32, _i32]),
+    "pf_op_ctc_beam": (C.c_int, [_vp, _f, _i64, _f, _i32, _i32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                 _i64, _i32, _P(C.c_double), C.c_int32, _i32]),
+    "pf_recognizer_set_ctc_beam": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32]),
     "pf_stream_token_alternatives": (C.c_int, [_vp, _P(_i64), _P(_f), _i32, _i32]),
     "pf_stream_num_alternatives": (C.c_int, [_vp, _i32]),
     "pf_stream_alternative": (C.c_int, [_vp, C.c_int32, _P(_i64), _i32, _P(C.c_double), _P(C.c_char_p), _i32]),

@@ -391,6 +391,36 @@ int pf_host_nbest(const int64_t* /*ids*/, const float* val, const int32_t* n, in
   PF_CATCH
 }
 
+int pf_engine_set_ctc_beam(pf_engine* h, int32_t W, int32_t N) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->set_ctc_beam(W, N);
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_fetch_ctc_beam(pf_engine* h, int64_t* ids, int32_t* len, double* score, int32_t cap, int32_t* n_hyp, int32_t* len_max) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->fetch_ctc_beam(ids, len, score, cap, n_hyp, len_max, nullptr);
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_host_ctc_beam(const float* blank_lp, int64_t blank_stride, const int64_t* ids, const float* val, const int32_t* n, int32_t T,
+                     int32_t K, int32_t blank, int32_t W, int32_t N, int64_t* out_ids, int32_t* out_len, double* out_score,
+                     int32_t cap, int32_t* n_hyp) {
+  PF_TRY
+  NEED(n_hyp);
+  *n_hyp = host_ctc_beam(blank_lp, blank_stride, ids, val, n, T, K, blank, W, N, out_ids, out_len, out_score, cap);
+  return PF_OK;
+  PF_CATCH
+}
+
 int pf_profile_enable(pf_engine* h, int32_t on) {
   PF_TRY
   E(h)->profile_enable(on != 0);
@@ -583,6 +613,22 @@ int pf_op_topk(pf_engine* h, const float* x, int64_t rows, int32_t V, int32_t ld
   return PF_OK;
   PF_CATCH
 }
+int pf_op_ctc_beam(pf_engine* h, const float* blank_lp, const int64_t* ids, const float* val, const int32_t* n, const int32_t* lens,
+                   int32_t B, int32_t T, int32_t K, int32_t blank, int32_t W, int32_t N, int64_t* out_ids, int32_t* out_len,
+                   double* out_score, int32_t cap, int32_t* n_hyp) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  NEED(lens); NEED(out_ids); NEED(out_len); NEED(out_score); NEED(n_hyp);
+  PF_CHECK(B >= 0 && T >= 0 && cap >= 1 && K >= 1 && K <= PF_TOPK_MAX && N >= 1 && N <= W && W <= PF_NBEST_MAX, PF_ERR_INVALID_ARG,
+           "ctc_beam: bad shape (1 <= N <= W <= 64, 1 <= K <= 8, cap >= 1)");
+  if ((int64_t)B * T > 0) { NEED(blank_lp); NEED(ids); NEED(val); NEED(n); }
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->op_ctc_beam(blank_lp, ids, val, n, lens, B, T, K, blank, W, N, out_ids, out_len, out_score, cap, n_hyp);
+  return PF_OK;
+  PF_CATCH
+}
+
 int pf_op_ctc_collapse(pf_engine* h, const int64_t* ids, const float* scores, const int32_t* lens, int32_t B, int32_t T,
                        int32_t blank, int64_t* ids_out, int32_t* first_out, int32_t* last_out, float* score_out, int32_t cap,
                        int32_t* n_out) {
@@ -1096,6 +1142,15 @@ int pf_recognizer_set_nbest(pf_recognizer* h, int32_t N, int32_t K) {
   std::shared_ptr<Recognizer> r = R(h);
   PF_CHECK(!r->disposed(), PF_ERR_DISPOSED, "OfflineRecognizer");
   r->SetNBest(N, K);
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_recognizer_set_ctc_beam(pf_recognizer* h, int32_t N, int32_t W, int32_t K) {
+  PF_TRY
+  std::shared_ptr<Recognizer> r = R(h);
+  PF_CHECK(!r->disposed(), PF_ERR_DISPOSED, "OfflineRecognizer");
+  r->SetCtcBeam(N, W, K);
   return PF_OK;
   PF_CATCH
 }

@@ -1837,7 +1837,12 @@ void Engine::sensevoice_head(int B, int T, bool want_logits) {
 
 // ------------------------------------------------------------------ decoding extras ---------
 void Engine::set_decode(int flags) {
-  PF_CHECK((flags & ~(PF_DECODE_SCORES | PF_DECODE_CTC | PF_DECODE_TOPK)) == 0, PF_ERR_INVALID_ARG, "set_decode: unknown flag bits");
+  PF_CHECK((flags & ~(PF_DECODE_SCORES | PF_DECODE_CTC | PF_DECODE_TOPK | PF_DECODE_CTC_BEAM)) == 0, PF_ERR_INVALID_ARG,
+           "set_decode: unknown flag bits");
+  if (flags & PF_DECODE_CTC_BEAM) {
+    PF_CHECK(mc_.kind_id() == 1 && !mc_.seaco, PF_ERR_UNSUPPORTED, "PF_DECODE_CTC_BEAM: only a SenseVoice model has a CTC head");
+    flags |= PF_DECODE_TOPK;
+  }
   if (flags & PF_DECODE_TOPK) flags |= PF_DECODE_SCORES;
   if (flags & PF_DECODE_CTC) {
     PF_CHECK(mc_.kind_id() == 1, PF_ERR_UNSUPPORTED, "PF_DECODE_CTC: only a SenseVoice model has a CTC head");
@@ -1851,6 +1856,12 @@ void Engine::set_decode(int flags) {
 void Engine::set_topk(int k) {
   PF_CHECK(k >= 1 && k <= PF_TOPK_MAX, PF_ERR_INVALID_ARG, "set_topk: K must be 1 .. " + std::to_string(PF_TOPK_MAX));
   topk_k_ = k;
+}
+
+void Engine::set_ctc_beam(int W, int N) {
+  PF_CHECK(N >= 1 && N <= W && W <= PF_NBEST_MAX, PF_ERR_INVALID_ARG, "set_ctc_beam: 1 <= N <= W <= " + std::to_string(PF_NBEST_MAX));
+  beam_w_ = W;
+  beam_n_ = N;
 }
 
 float* Engine::score_buf(int64_t rows) {
@@ -1867,6 +1878,10 @@ void Engine::queue_decode_results(int B, int L) {
   const float* sc = (const float*)ws_score_.p;
   last_.scores.resize((size_t)B * L);
   PF_HIP(hipMemcpyAsync(last_.scores.data(), sc, (size_t)B * L * 4, hipMemcpyDeviceToHost, stream_));
+  if (decode_flags_ & (PF_DECODE_CTC | PF_DECODE_CTC_BEAM)) {
+    if ((int)len.size() != B) len.assign(B, L);
+    for (int b = 0; b < B; ++b) len[b] = std::min(std::max(len[b], 0), L);
+  }
   if (decode_flags_ & PF_DECODE_TOPK) {
     // the arg-max ran in its store-in-place form (argmax_mode): logits_ holds the log-probs it scanned
     const int64_t rows = (int64_t)B * L;
@@ -1882,10 +1897,31 @@ void Engine::queue_decode_results(int B, int L) {
     launch_topk(stream_, logits_, rows, last_.V, logits_ld_, K, ids_o, val_o, n_o);
     prof_end("topk");
     PF_HIP(hipMemcpyAsync(last_.topk.data(), ws_topk_.p, ((size_t)rows * K * 12 + (size_t)rows * 4), hipMemcpyDeviceToHost, stream_));
+    if (decode_flags_ & PF_DECODE_CTC_BEAM) {
+      // the search reads the lists just made and the blank column (id 0) of the in-place log-prob rows
+      const int W = beam_w_, Nh = beam_n_, cap = L;
+      const size_t bwords = HostBatchOut::beam_words(B, Nh, cap);
+      const size_t nodes = (size_t)B * ((size_t)L * W + 1);
+      ensure(ws_beam_, bwords * 8 + (size_t)B * 4 + nodes * 8);
+      last_.beam.resize(bwords);
+      last_.beam_n = Nh;
+      last_.beam_cap = cap;
+      double* score_o = (double*)ws_beam_.p;
+      int32_t* bids_o = (int32_t*)(score_o + (size_t)B * Nh);
+      int32_t* blen_o = bids_o + (size_t)B * Nh * cap;
+      int32_t* nhyp_o = blen_o + (size_t)B * Nh;
+      int32_t* len_d = (int32_t*)((char*)ws_beam_.p + bwords * 8);
+      int32_t* node_par = len_d + B;
+      int32_t* node_tok = node_par + nodes;
+      PF_HIP(hipMemcpyAsync(len_d, len.data(), (size_t)B * 4, hipMemcpyHostToDevice, stream_));
+      prof_begin("ctc_beam", 0);
+      launch_ctc_beam(stream_, logits_, logits_ld_, ids_o, val_o, n_o, len_d, B, L, K, 0, W, Nh, cap, node_par, node_tok, bids_o,
+                      blen_o, score_o, nhyp_o);
+      prof_end("ctc_beam");
+      PF_HIP(hipMemcpyAsync(last_.beam.data(), ws_beam_.p, bwords * 8, hipMemcpyDeviceToHost, stream_));
+    }
   }
   if (!(decode_flags_ & PF_DECODE_CTC)) return;
-  if ((int)len.size() != B) len.assign(B, L);
-  for (int b = 0; b < B; ++b) len[b] = std::min(std::max(len[b], 0), L);
   const int cap = L;
   const size_t words = HostBatchOut::ctc_words(B, cap);
   ensure(ws_ctc_, words * 8 + (size_t)B * 4);
@@ -1911,6 +1947,7 @@ void Engine::forward_device(const float* speech_dev, int B, int T, bool want_log
   last_.decode_flags = decode_flags_;
   last_.scores.clear(); last_.ctc.clear(); last_.ctc_cap = 0;
   last_.topk.clear(); last_.topk_k = 0;
+  last_.beam.clear(); last_.beam_n = 0; last_.beam_cap = 0;
   if (fp32_mode_) { forward_fp32(speech_dev, B, T, want_logits); return; }
   if (int8_mode_) { forward_int8(speech_dev, B, T, want_logits); return; }
   encoder(speech_dev, B, T);
@@ -2067,6 +2104,33 @@ void Engine::fetch_topk(int64_t* ids, float* val, int32_t* n, int64_t cap_rows, 
   if (ids) std::memcpy(ids, r.topk_ids(), (size_t)rows * K * 8);
   if (val) std::memcpy(val, r.topk_val(), (size_t)rows * K * 4);
   if (n) std::memcpy(n, r.topk_n(), (size_t)rows * 4);
+}
+
+void Engine::fetch_ctc_beam(int64_t* ids, int32_t* len, double* score, int32_t cap, int32_t* n_hyp, int32_t* len_max, int32_t* N_out) {
+  PF_HIP(hipStreamSynchronize(stream_));
+  check_async_errors();
+  auto it = t_slots_find(uid_);
+  const HostBatchOut& r = it ? *it : last_;
+  PF_CHECK(r.decode_flags & PF_DECODE_CTC_BEAM, PF_ERR_INVALID_ARG, "fetch_ctc_beam: PF_DECODE_CTC_BEAM was not set for the last forward");
+  const int B = r.B, Nh = r.beam_n;
+  const bool have = !r.beam.empty();
+  int mx = 0;
+  for (int x = 0; x < B * Nh && have; ++x) mx = std::max(mx, r.beam_len()[x]);
+  if (len_max) *len_max = mx;
+  if (N_out) *N_out = Nh;
+  if (n_hyp) for (int b = 0; b < B; ++b) n_hyp[b] = have ? r.beam_nhyp()[b] : 0;
+  if (!have) return;
+  if (len) std::memcpy(len, r.beam_len(), (size_t)B * Nh * 4);
+  if (score) std::memcpy(score, r.beam_score(), (size_t)B * Nh * 8);
+  if (!ids) return;
+  PF_CHECK(cap >= mx, PF_ERR_CAPACITY, "ctc_beam capacity " + std::to_string(cap) + " < len_max = " + std::to_string(mx));
+  for (int x = 0; x < B * Nh; ++x) {
+    const int32_t* src = r.beam_ids() + (size_t)x * r.beam_cap;
+    int64_t* dst = ids + (size_t)x * cap;
+    const int k = std::min(cap, r.beam_cap);
+    for (int p = 0; p < k; ++p) dst[p] = src[p];
+    std::fill(dst + k, dst + cap, (int64_t)-1);
+  }
 }
 
 void Engine::fetch_ctc(int64_t* ids, int32_t* first, int32_t* last, float* score, int32_t cap, int32_t* n, int32_t* n_max) {

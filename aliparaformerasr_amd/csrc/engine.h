@@ -170,6 +170,14 @@ class Engine {
   int topk() const { return topk_k_; }
   void fetch_topk(int64_t* ids, float* val, int32_t* n, int64_t cap_rows, int32_t* L_out, int32_t* K_out);
   void op_topk(const float* x, int64_t rows, int V, int ld, int K, int64_t* ids, float* val, int32_t* n);
+  // CTC_BEAM (SenseVoice; implies TOPK and SCORES): behind the top-k launch one kernel (k_ctcbeam.hip) runs a prefix beam
+  // search of width W over every utterance's frames and keeps the N best labelings.  1 <= N <= W <= 64, default 16 / 16.
+  void set_ctc_beam(int W, int N);
+  int ctc_beam_w() const { return beam_w_; }
+  int ctc_beam_n() const { return beam_n_; }
+  void fetch_ctc_beam(int64_t* ids, int32_t* len, double* score, int32_t cap, int32_t* n_hyp, int32_t* len_max, int32_t* N_out);
+  void op_ctc_beam(const float* blank_lp, const int64_t* ids, const float* val, const int32_t* n, const int32_t* lens, int B, int T,
+                   int K, int blank, int W, int N, int64_t* out_ids, int32_t* out_len, double* out_score, int cap, int32_t* n_hyp);
   void op_pcm_convert(const void* data, int64_t n_values, const pf_pcm_desc& desc, float* out, int64_t cap, int64_t* n_out);
   void op_ctc_collapse(const int64_t* ids, const float* scores, const int32_t* lens, int B, int T, int blank, int64_t* ids_out,
                        int32_t* first_out, int32_t* last_out, float* score_out, int cap, int32_t* n_out);
@@ -432,6 +440,8 @@ class Engine {
   int topk_k_ = 4;                   // K of PF_DECODE_TOPK
   DevBuf ws_topk_;                   // the top-k result block (HostBatchOut::topk); allocated with the flag only
   // the arg-max form of a pipeline head: the top-k kernel reads the log-probs the arg-max leaves in place
+  int beam_w_ = 16, beam_n_ = 16;    // W / N of PF_DECODE_CTC_BEAM
+  DevBuf ws_beam_;                   // the beam result block (HostBatchOut::beam) | len [B] | prefix nodes; allocated with the flag only
   int argmax_mode(bool want_logits) const { return (want_logits || (decode_flags_ & PF_DECODE_TOPK)) ? 2 : 1; }
   void queue_decode_results(int B, int L);   // behind the ids copy: the scores' copy, the collapse and its copy
   uint64_t uid_ = 0;                 // key of this engine in the per-thread result store

@@ -87,6 +87,43 @@ void Engine::op_topk(const float* x, int64_t rows, int V, int ld, int K, int64_t
   PF_HIP(hipStreamSynchronize(stream_));
 }
 
+void Engine::op_ctc_beam(const float* blank_lp, const int64_t* ids, const float* val, const int32_t* n, const int32_t* lens, int B,
+                         int T, int K, int blank, int W, int N, int64_t* out_ids, int32_t* out_len, double* out_score, int cap,
+                         int32_t* n_hyp) {
+  PF_HIP(hipSetDevice(device_));
+  if (B == 0) return;
+  const size_t rows = (size_t)B * T, hyp = (size_t)B * N, nodes = (size_t)B * ((size_t)T * W + 1);
+  // 8-byte items first: score | ids in; then the 4-byte ones
+  const size_t words4 = rows * K + rows + rows + (size_t)B + hyp * cap + hyp + (size_t)B + 2 * nodes;
+  ensure(ws_tmp_, (hyp + rows * K) * 8 + words4 * 4);
+  double* d_score = (double*)ws_tmp_.p;
+  int64_t* d_ids = (int64_t*)(d_score + hyp);
+  float* d_val = (float*)(d_ids + rows * K);
+  float* d_lb = d_val + rows * K;
+  int32_t* d_n = (int32_t*)(d_lb + rows);
+  int32_t* d_len = d_n + rows;
+  int32_t* d_oids = d_len + B;
+  int32_t* d_olen = d_oids + hyp * cap;
+  int32_t* d_nhyp = d_olen + hyp;
+  int32_t* d_par = d_nhyp + B;
+  int32_t* d_tok = d_par + nodes;
+  if (rows > 0) {
+    PF_HIP(hipMemcpyAsync(d_ids, ids, rows * K * 8, hipMemcpyHostToDevice, stream_));
+    PF_HIP(hipMemcpyAsync(d_val, val, rows * K * 4, hipMemcpyHostToDevice, stream_));
+    PF_HIP(hipMemcpyAsync(d_lb, blank_lp, rows * 4, hipMemcpyHostToDevice, stream_));
+    PF_HIP(hipMemcpyAsync(d_n, n, rows * 4, hipMemcpyHostToDevice, stream_));
+  }
+  PF_HIP(hipMemcpyAsync(d_len, lens, (size_t)B * 4, hipMemcpyHostToDevice, stream_));
+  launch_ctc_beam(stream_, d_lb, 1, d_ids, d_val, d_n, d_len, B, T, K, blank, W, N, cap, d_par, d_tok, d_oids, d_olen, d_score, d_nhyp);
+  std::vector<int32_t> h_ids(hyp * cap);
+  if (hyp * cap > 0) PF_HIP(hipMemcpyAsync(h_ids.data(), d_oids, hyp * cap * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipMemcpyAsync(out_len, d_olen, hyp * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipMemcpyAsync(out_score, d_score, hyp * 8, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipMemcpyAsync(n_hyp, d_nhyp, (size_t)B * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipStreamSynchronize(stream_));
+  for (size_t x = 0; x < hyp * cap; ++x) out_ids[x] = h_ids[x];
+}
+
 void Engine::op_ctc_collapse(const int64_t* ids, const float* scores, const int32_t* lens, int B, int T, int blank,
                              int64_t* ids_out, int32_t* first_out, int32_t* last_out, float* score_out, int cap, int32_t* n_out) {
   PF_HIP(hipSetDevice(device_));

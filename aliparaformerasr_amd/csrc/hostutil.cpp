@@ -505,4 +505,127 @@ int host_nbest(const float* val, const int32_t* n, int L, int K, int n_free, int
   return got;
 }
 
+// ------------------------------------------------------------------ CTC prefix beam search ---------------
+namespace {
+const double kNegInf = -INFINITY;
+inline double beam_lse(double a, double b) {
+  if (a == kNegInf) return b;
+  if (b == kNegInf) return a;
+  const double m = a > b ? a : b;
+  return m + std::log1p(std::exp(-std::fabs(a - b)));
+}
+inline uint64_t beam_hash(uint64_t h, int c) {
+  h = (h ^ ((uint64_t)(uint32_t)c + 0x9E3779B97F4A7C15ull)) * 0x100000001B3ull;
+  return h ^ (h >> 29);
+}
+struct BeamEntry {
+  double pb, pnb;
+  uint64_t hash;
+  int node, par, tok, len;
+};
+struct BeamCand {
+  double tot, pb, pnb;
+  int idx;
+};
+}  // namespace
+
+int host_ctc_beam(const float* blank_lp, int64_t blank_stride, const int64_t* ids, const float* val, const int32_t* n, int T, int K,
+                  int blank, int W, int N, int64_t* out_ids, int32_t* out_len, double* out_score, int cap) {
+  if (!out_ids || !out_len || !out_score || (T > 0 && (!blank_lp || !ids || !val || !n)))
+    throw Error(PF_ERR_INVALID_ARG, "ctc_beam: null argument");
+  if (T < 0 || K < 1 || K > PF_TOPK_MAX || N < 1 || N > W || W > PF_NBEST_MAX || cap < 0 || blank_stride < 1)
+    throw Error(PF_ERR_INVALID_ARG, "ctc_beam: bad T / K / W / N / cap");
+  for (int h = 0; h < N; ++h) { out_len[h] = 0; out_score[h] = kNegInf; }
+  std::fill(out_ids, out_ids + (size_t)N * cap, (int64_t)-1);
+  for (int t = 0; t < T; ++t) {
+    if (n[t] < 0 || n[t] > K) throw Error(PF_ERR_INVALID_ARG, "ctc_beam: n[t] outside 0 .. K");
+    const float lb = blank_lp[(size_t)t * blank_stride];
+    if (n[t] == 0 || lb != lb) return 0;
+  }
+  // node 0 is the empty prefix; a chain of (parent, token) spells a prefix backwards
+  std::vector<int> npar(1, -1), ntok(1, -1);
+  auto same_prefix = [&](int a, int b) {           // equally long by the caller's filter
+    while (a != b) {
+      if (a <= 0 || b <= 0) return false;
+      if (ntok[(size_t)a] != ntok[(size_t)b]) return false;
+      a = npar[(size_t)a];
+      b = npar[(size_t)b];
+    }
+    return true;
+  };
+  std::vector<BeamEntry> beam(1, BeamEntry{0.0, kNegInf, 0x243F6A8885A308D3ull, 0, -1, -1, 0}), next;
+  std::vector<BeamCand> cand;
+  std::vector<double> merged;
+  const int K1 = K + 1;
+  for (int t = 0; t < T; ++t) {
+    const int64_t* id = ids + (size_t)t * K;
+    const float* lp = val + (size_t)t * K;
+    const int nt = n[t];
+    const double lb = (double)blank_lp[(size_t)t * blank_stride];
+    const int nbeam = (int)beam.size();
+    cand.assign((size_t)nbeam * K1, BeamCand{kNegInf, kNegInf, kNegInf, 0});
+    merged.assign((size_t)nbeam, kNegInf);
+    for (int i = 0; i < nbeam; ++i) {
+      const BeamEntry& p = beam[(size_t)i];
+      const double tot = beam_lse(p.pb, p.pnb);
+      BeamCand& st = cand[(size_t)i * K1];
+      st.pb = tot + lb;
+      for (int r = 0; r < nt; ++r) {
+        const int c = (int)id[r];
+        if (c == blank || c < 0) continue;
+        if (p.len > 0 && c == p.tok) st.pnb = p.pnb + (double)lp[r];
+        const double base = (p.len > 0 && c == p.tok) ? p.pb : tot;
+        if (base == kNegInf) continue;
+        const double value = base + (double)lp[r];
+        const uint64_t h = beam_hash(p.hash, c);
+        int hit = -1;
+        for (int q = 0; q < nbeam; ++q) {
+          const BeamEntry& e = beam[(size_t)q];
+          if (e.len == p.len + 1 && e.tok == c && e.hash == h && same_prefix(e.par, p.node)) hit = q;
+        }
+        if (hit >= 0) merged[(size_t)hit] = value;               // at most one extension meets one entry
+        else cand[(size_t)i * K1 + 1 + r].pnb = value;
+      }
+    }
+    std::vector<int> live;
+    for (int j = 0; j < nbeam * K1; ++j) {
+      BeamCand& c = cand[(size_t)j];
+      c.idx = j;
+      if (j % K1 == 0) c.pnb = beam_lse(c.pnb, merged[(size_t)(j / K1)]);
+      c.tot = beam_lse(c.pb, c.pnb);
+      if (c.tot > kNegInf) live.push_back(j);
+    }
+    std::sort(live.begin(), live.end(), [&](int a, int b) {
+      const double x = cand[(size_t)a].tot, y = cand[(size_t)b].tot;
+      return x != y ? x > y : a < b;
+    });
+    if ((int)live.size() > W) live.resize((size_t)W);
+    next.clear();
+    for (int j : live) {
+      const BeamCand& c = cand[(size_t)j];
+      const BeamEntry& p = beam[(size_t)(j / K1)];
+      if (j % K1 == 0) {
+        next.push_back(BeamEntry{c.pb, c.pnb, p.hash, p.node, p.par, p.tok, p.len});
+      } else {
+        const int tok = (int)id[j % K1 - 1];
+        npar.push_back(p.node);
+        ntok.push_back(tok);
+        next.push_back(BeamEntry{c.pb, c.pnb, beam_hash(p.hash, tok), (int)npar.size() - 1, p.node, tok, p.len + 1});
+      }
+    }
+    beam.swap(next);
+  }
+  const int nh = std::min(N, (int)beam.size());
+  for (int h = 0; h < nh; ++h)
+    if (beam[(size_t)h].len > cap) throw Error(PF_ERR_CAPACITY, "ctc_beam: a hypothesis of " + std::to_string(beam[(size_t)h].len) + " tokens > cap");
+  for (int h = 0; h < nh; ++h) {
+    const BeamEntry& e = beam[(size_t)h];
+    int node = e.node;
+    for (int p = e.len - 1; p >= 0; --p) { out_ids[(size_t)h * cap + p] = ntok[(size_t)node]; node = npar[(size_t)node]; }
+    out_len[h] = e.len;
+    out_score[h] = beam_lse(e.pb, e.pnb);
+  }
+  return nh;
+}
+
 }  // namespace pf

@@ -73,6 +73,14 @@ std::vector<float> get_file_sample(const std::string& path, double* duration_ms)
 // NaN or +inf (their sums would not order).
 int host_nbest(const float* val, const int32_t* n, int L, int K, int n_free, int N, int32_t* out_ranks, double* out_scores);
 
+// ---- CTC prefix beam search of one utterance (paraformer_hip.h "CTC beam search"; the definition is tests/ctcbeam_ref.py) ----
+// The host twin of k_ctcbeam.hip: blank_lp[t * blank_stride], ids / val [T, K], n [T] -> the N best of a beam of width W
+// (1 <= N <= W <= 64).  out_ids [N, cap] (-1 past a hypothesis' length), out_len [N] (0), out_score [N] (-inf): every slot is
+// written.  Returns the number of hypotheses: 0 when a frame has n[t] == 0 or a NaN blank log-prob.  PF_ERR_CAPACITY when a
+// hypothesis is longer than cap (cap >= T always suffices).  Prefixes are back-pointer chains compared by token sequence.
+int host_ctc_beam(const float* blank_lp, int64_t blank_stride, const int64_t* ids, const float* val, const int32_t* n, int T, int K,
+                  int blank, int W, int N, int64_t* out_ids, int32_t* out_len, double* out_score, int cap);
+
 // UTF-8 <-> code points
 std::vector<uint32_t> utf8_decode(const std::string& s);
 std::string utf8_encode(uint32_t cp);

@@ -356,6 +356,16 @@ void launch_ctc_collapse(hipStream_t s, const int64_t* ids, const float* score, 
 // value first, of equal values the larger index; NaN never ranked.  ids [rows, K] / val [rows, K]: slots past
 // n[row] = min(K, non-NaN entries) hold -1 / -inf.  Every output slot is written.
 void launch_topk(hipStream_t s, const float* x, int64_t rows, int V, int ldx, int K, int64_t* ids, float* val, int32_t* n);
+// ------------------------------------------------------------------ CTC prefix beam search ------
+// Per utterance b the N best labelings of a prefix beam search of width W over the frames t < min(max(len[b], 0), T), from
+// the frames' top-k lists ids / val [B * T, K], n [B * T] (as launch_topk leaves them) and the blank log-prob
+// blank_lp[(b * T + t) * blank_stride] (k_ctcbeam.hip; the definition is tests/ctcbeam_ref.py).  1 <= N <= W <= 64,
+// 1 <= K <= PF_TOPK_MAX.  node_par / node_tok: workspaces of B * (T * W + 1) int32 each.  out_ids [B, N, cap] (int32; -1 past
+// a hypothesis' length; a token at or beyond cap is counted but not stored), out_len [B, N] (0), out_score [B, N] float64
+// (-inf), n_hyp [B]: every slot is written.  Nothing at or beyond len[b] or n[row] is read.
+void launch_ctc_beam(hipStream_t s, const float* blank_lp, int64_t blank_stride, const int64_t* ids, const float* val,
+                     const int32_t* n, const int32_t* len, int B, int T, int K, int blank, int W, int N, int cap, int32_t* node_par,
+                     int32_t* node_tok, int32_t* out_ids, int32_t* out_len, double* out_score, int32_t* n_hyp);
 
 // ---------------------------------------------------------------- PCM intake (k_pcm.hip) ------
 // One utterance of a pcm_to_samples launch: n raw values of `format` (pf_pcm_format) at raw + in_off (bytes, 16-byte aligned)

@@ -509,26 +509,46 @@ Recognizer::Recognizer(const std::string& model, const std::string& config, cons
 std::shared_ptr<Engine> Recognizer::make_engine() {
   std::shared_ptr<void> img = image_;                // the engine points into the image: it must outlive the engine
   std::shared_ptr<Engine> e(new Engine(ec_), [img](Engine* p) { delete p; });
-  if (decode_flags_) { e->set_topk(topk_k_); e->set_decode(decode_flags_); }
+  if (decode_flags_) { e->set_topk(topk_k_); e->set_ctc_beam(beam_w_, std::min<int>(beam_n_, beam_w_)); e->set_decode(decode_flags_); }
   return e;
 }
 
 void Recognizer::SetDecode(int flags) {
-  set_decode_all(flags | (nbest_n_ > 0 ? PF_DECODE_TOPK : 0), topk_k_);
+  set_decode_all(flags | (nbest_n_ > 0 ? PF_DECODE_TOPK : 0) | (beam_on_ ? PF_DECODE_CTC_BEAM : 0), topk_k_);
   user_flags_ = flags;
+}
+
+void Recognizer::SetCtcBeam(int N, int W, int K) {
+  if (N < 0 || N > PF_NBEST_MAX || W < 0 || W > PF_NBEST_MAX || K < 0 || K > PF_TOPK_MAX || (N > 0 && W > 0 && W < N))
+    throw Error(PF_ERR_INVALID_ARG, "SetCtcBeam: N is 0 .. 64, W is 0 or N .. 64, K is 0 .. 8");
+  if (N == 0) {
+    beam_on_ = false;
+    set_decode_all(user_flags_ | (nbest_n_ > 0 ? PF_DECODE_TOPK : 0), topk_k_);
+    return;
+  }
+  if (engine_kind_ != "sensevoicesmall") throw Error(PF_ERR_UNSUPPORTED, "SetCtcBeam: only a SenseVoice model has a CTC head");
+  beam_w_ = W == 0 ? std::max(16, N) : W;
+  beam_n_ = N;
+  beam_on_ = true;
+  try {
+    set_decode_all(user_flags_ | (nbest_n_ > 0 ? PF_DECODE_TOPK : 0) | PF_DECODE_CTC_BEAM, K == 0 ? 4 : K);
+  } catch (...) {
+    beam_on_ = false;
+    throw;
+  }
 }
 
 void Recognizer::SetNBest(int N, int K) {
   if (N < 0 || N > PF_NBEST_MAX || K < 0 || K > PF_TOPK_MAX) throw Error(PF_ERR_INVALID_ARG, "SetNBest: N is 0 .. 64, K is 0 .. 8");
   if (N == 0) {
-    set_decode_all(user_flags_ & ~PF_DECODE_TOPK, topk_k_);
+    set_decode_all((user_flags_ & ~PF_DECODE_TOPK) | (beam_on_ ? PF_DECODE_CTC_BEAM : 0), topk_k_);
     user_flags_ = user_flags_ & ~PF_DECODE_TOPK;
     nbest_n_ = 0;
     return;
   }
   // frames of a CTC model are not independent tokens: a sum over frame ranks is no hypothesis score
   if (N > 1 && engine_kind_ == "sensevoicesmall") throw Error(PF_ERR_UNSUPPORTED, "SetNBest: N > 1 needs a paraformer model (SenseVoice offers K alone)");
-  set_decode_all(user_flags_ | PF_DECODE_TOPK, K == 0 ? 4 : K);
+  set_decode_all(user_flags_ | PF_DECODE_TOPK | (beam_on_ ? PF_DECODE_CTC_BEAM : 0), K == 0 ? 4 : K);
   nbest_n_ = N;
 }
 
@@ -546,6 +566,7 @@ void Recognizer::set_decode_all(int flags, int k) {
     std::lock_guard<std::mutex> lk(es[i]->mutex());
     es[i]->set_decode(flags);
     es[i]->set_topk(k);
+    es[i]->set_ctc_beam(beam_w_, std::min<int>(beam_n_, beam_w_));
     if (i == 0) { decode_flags_ = es[0]->decode_flags(); topk_k_ = k; }
   }
 }
@@ -912,6 +933,7 @@ void Recognizer::Forward(const std::vector<Stream*>& streams) {
     const int B = (int)streams.size();
     if (e->decode_flags() != decode_flags_) e->set_decode(decode_flags_);
     if (e->topk() != topk_k_) e->set_topk(topk_k_);
+    if (e->ctc_beam_w() != beam_w_ || e->ctc_beam_n() != beam_n_) e->set_ctc_beam(beam_w_, std::min<int>(beam_n_, beam_w_));
     const int dflags = e->decode_flags();
     fc.lap(0);
     if (!all_dev && sv) {
@@ -1018,8 +1040,21 @@ void Recognizer::Forward(const std::vector<Stream*>& streams) {
       k_ids.resize(rows * K); k_val.resize(rows * K); k_n.resize(rows);
       e->fetch_topk(k_ids.data(), k_val.data(), k_n.data(), (int64_t)rows, nullptr, nullptr);
     }
+    // the beam search's hypotheses (SetCtcBeam): ids [B, Nb, b_cap], lengths, float64 totals
+    std::vector<int64_t> b_ids; std::vector<int32_t> b_len, b_nhyp; std::vector<double> b_score;
+    int Nb = 0, b_cap = 0;
+    if (dflags & PF_DECODE_CTC_BEAM) {
+      int32_t len_max = 0, nb = 0;
+      b_nhyp.resize(B);
+      e->fetch_ctc_beam(nullptr, nullptr, nullptr, 0, b_nhyp.data(), &len_max, &nb);
+      Nb = nb;
+      b_cap = std::max(len_max, 1);
+      b_ids.resize((size_t)B * Nb * b_cap); b_len.resize((size_t)B * Nb); b_score.resize((size_t)B * Nb);
+      e->fetch_ctc_beam(b_ids.data(), b_len.data(), b_score.data(), b_cap, nullptr, nullptr, nullptr);
+    }
     const int nbest = nbest_n_;
-    const bool want_scores = (dflags & ~PF_DECODE_TOPK) == PF_DECODE_SCORES && (!(dflags & PF_DECODE_TOPK) || (user_flags_ & PF_DECODE_SCORES));
+    const int extras = PF_DECODE_TOPK | PF_DECODE_CTC_BEAM;      // neither changes what Scores holds
+    const bool want_scores = (dflags & ~extras) == PF_DECODE_SCORES && (!(dflags & extras) || (user_flags_ & PF_DECODE_SCORES));
     fc.lap(5);
     lease.release();                      // the device work of this call is over: the text stage below needs no engine
     for (int b = 0; b < B; ++b) {
@@ -1077,6 +1112,14 @@ void Recognizer::Forward(const std::vector<Stream*>& streams) {
           }
         }
       }
+      for (int i = 0; i < (Nb > 0 ? b_nhyp[b] : 0); ++i) {
+        const size_t x = (size_t)b * Nb + i;
+        Alternative a;
+        a.score = b_score[x];
+        a.ctc = true;
+        a.ids.assign(b_ids.begin() + x * b_cap, b_ids.begin() + x * b_cap + b_len[x]);
+        s->Alternatives.push_back(std::move(a));
+      }
       if (all_dev && sv && s->Tokens.size() <= 2) {
         // quirk Q8 on the device form: the reference has prepended the query rows to Speech IN PLACE, and a stream whose
         // chunk RemoveChunk keeps (at most two ids) carries them into its next call: give it the host form with them
@@ -1112,7 +1155,8 @@ void Recognizer::GetResults(const std::vector<Stream*>& streams) {
   std::vector<ResultEntity> out;
   for (Stream* s : streams) out.push_back(decode_multi_one(token_table_, s->Tokens, s->Timestamps));
   for (Stream* s : streams)                                   // the n-best list goes through the same DecodeMulti
-    for (Alternative& a : s->Alternatives) a.res = decode_multi_one(token_table_, a.ids, s->Timestamps);
+    for (Alternative& a : s->Alternatives)                    // (a beam hypothesis has no per-token times: {0, 0} each)
+      a.res = decode_multi_one(token_table_, a.ids, a.ctc ? TsList(a.ids.size(), TsVec{0, 0}) : s->Timestamps);
   fc.lap(7);
   fwd_report();
   {

@@ -78,6 +78,7 @@ ResultEntity decode_multi_one(const TokenTable& table, const std::vector<int64_t
 struct Alternative {
   std::vector<int64_t> ids;
   double score = 0;
+  bool ctc = false;            // a labeling of the CTC beam search (SetCtcBeam): its own length, score = log of the summed alignments
   ResultEntity res;
 };
 // time_stamp_lfr6_onnx (OfflineRecognizer.cs:200-302); throws PF_ERR_RECOGNITION where the C#
@@ -168,6 +169,9 @@ class Recognizer : public std::enable_shared_from_this<Recognizer> {
   // Alternatives (paraformer_hip.h "Top-k and n-best"): N = 0 off; N >= 1: PF_DECODE_TOPK with K (0 = 4) on every engine beside
   // the SetDecode flags — TokenAlternatives in every stream, and for paraformer with N > 1 the n-best list
   void SetNBest(int N, int K);
+  // SenseVoice only (paraformer_hip.h "CTC beam search"): N = 0 off; N >= 1: PF_DECODE_CTC_BEAM with beam width W (0 = max(16, N))
+  // and top-k K (0 = 4) on every engine — Alternatives holds up to N labelings by descending CTC score
+  void SetCtcBeam(int N, int W, int K);
   bool disposed() const { return disposed_.load(); }
   // engine 0 (nullptr once disposed): what pf_recognizer_engine hands out; callers lock engine->mutex() themselves
   std::shared_ptr<Engine> engine() { std::lock_guard<std::mutex> lk(mu_); return engines_.empty() ? nullptr : engines_[0]; }
@@ -266,6 +270,8 @@ class Recognizer : public std::enable_shared_from_this<Recognizer> {
   std::atomic<int> user_flags_{0};                            // as given to SetDecode
   std::atomic<int> nbest_n_{0};
   std::atomic<int> topk_k_{4};
+  std::atomic<int> beam_w_{16}, beam_n_{16};
+  std::atomic<bool> beam_on_{false};
   void set_decode_all(int flags, int k);
   friend class Stream;
 };

@@ -52,6 +52,14 @@ struct HostBatchOut { // results of a forward, host side
   const int64_t* topk_ids() const { return topk.data(); }
   const float* topk_val() const { return (const float*)(topk.data() + (size_t)B * L * topk_k); }
   const int32_t* topk_n() const { return (const int32_t*)(topk_val() + (size_t)B * L * topk_k); }
+  // CTC beam search as the kernel leaves it, one block: score [B, N] float64 | ids [B, N, cap] int32 | len [B, N] | n_hyp [B]
+  std::vector<int64_t> beam;
+  int beam_n = 0, beam_cap = 0;
+  static size_t beam_words(int B, int N, int cap) { return (size_t)B * N + ((size_t)B * N * cap * 4 + (size_t)B * N * 4 + (size_t)B * 4 + 7) / 8; }
+  const double* beam_score() const { return (const double*)beam.data(); }
+  const int32_t* beam_ids() const { return (const int32_t*)(beam.data() + (size_t)B * beam_n); }
+  const int32_t* beam_len() const { return beam_ids() + (size_t)B * beam_n * beam_cap; }
+  const int32_t* beam_nhyp() const { return beam_len() + (size_t)B * beam_n; }
 };
 
 // rendezvous of the G worker threads with a max-reduction; abort() releases every waiter with an Error

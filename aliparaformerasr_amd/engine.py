@@ -59,8 +59,48 @@ def host_nbest(val, n, n_free, n_best, ids=None):
     return ranks, scores, y[np.arange(L)[None, :], ranks]
 
 
+class CtcBeamResult:
+    """The labelings a CTC prefix beam search kept (PF_DECODE_CTC_BEAM): n_hyp [B]; ids [B, N, cap] int64 (-1 past a
+    hypothesis' length), len [B, N], score [B, N] float64 (the log of the summed alignments; -inf past n_hyp[b])."""
+
+    def __init__(self, n_hyp, ids, len_, score):
+        self.n_hyp, self.ids, self.len, self.score = n_hyp, ids, len_, score
+        self.N = score.shape[-1]
+
+    def hyps(self, b=0):
+        """[(ids tuple, score)] of utterance b, best first."""
+        return [(tuple(self.ids[b, i, : int(self.len[b, i])].tolist()), float(self.score[b, i])) for i in range(int(self.n_hyp[b]))]
+
+
+def _dp(a):
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def _i64p(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int64))
+
+
+def host_ctc_beam(blank_lp, ids, val, n, W, n_best=None, blank=0, cap=None, blank_stride=1) -> CtcBeamResult:
+    """The beam search of ONE utterance in host code (pf_host_ctc_beam, the twin of the device kernel): blank_lp
+    [T * blank_stride], ids / val [T, K], n [T] -> CtcBeamResult with B = 1."""
+    y = np.ascontiguousarray(ids, dtype=np.int64)
+    v = _f32(val)
+    nn = np.ascontiguousarray(n, dtype=np.int32)
+    lb = _f32(blank_lp).reshape(-1)
+    T, K = y.shape
+    n_best = W if n_best is None else n_best
+    cap = max(T, 1) if cap is None else cap
+    oi = np.zeros((1, max(n_best, 0), cap), np.int64)
+    ol = np.zeros((1, max(n_best, 0)), np.int32)
+    sc = np.zeros((1, max(n_best, 0)), np.float64)
+    nh = np.zeros(1, np.int32)
+    N.check(N.load().pf_host_ctc_beam(_fp(lb), int(blank_stride), _i64p(y), _fp(v), _i32p(nn), T, K, int(blank), int(W), int(n_best),
+                                      _i64p(oi), _i32p(ol), _dp(sc), cap, _i32p(nh)))
+    return CtcBeamResult(nh, oi, ol, sc)
+
+
 class BatchResult:
-    def __init__(self, token_ids, token_num, L, V, logits=None, cif_peak=None, scores=None, ctc=None, topk=None):
+    def __init__(self, token_ids, token_num, L, V, logits=None, cif_peak=None, scores=None, ctc=None, topk=None, beam=None):
         self.token_ids = token_ids      # [B, L] int64
         self.token_num = token_num      # [B] int32
         self.L = L
@@ -70,6 +110,7 @@ class BatchResult:
         self.scores = scores            # [B, L] float32 log-prob of token_ids (Engine.set_decode) or None
         self.ctc = ctc                  # CtcResult (Engine.set_decode(PF_DECODE_CTC)) or None
         self.topk = topk                # TopkResult (Engine.set_decode(PF_DECODE_TOPK)) or None
+        self.beam = beam                # CtcBeamResult (Engine.set_decode(PF_DECODE_CTC_BEAM)) or None
 
 
 def _build_config(weights, weights_path, weights_device_ptr, weights_bytes, cmvn, mvn_path, device, dither, snip_edges,
@@ -146,6 +187,18 @@ def _fetch_topk(lib, h, B, L):
     return TopkResult(ids, val, n)
 
 
+def _fetch_ctc_beam(lib, h, B, n_best):
+    nh = np.zeros(B, np.int32)
+    mx = C.c_int32()
+    N.check(lib.pf_fetch_ctc_beam(h, None, None, None, 0, _i32p(nh), mx))
+    cap = max(mx.value, 1)
+    ids = np.zeros((B, n_best, cap), np.int64)
+    ln = np.zeros((B, n_best), np.int32)
+    sc = np.zeros((B, n_best), np.float64)
+    N.check(lib.pf_fetch_ctc_beam(h, _i64p(ids), _i32p(ln), _dp(sc), cap, None, None))
+    return CtcBeamResult(nh, ids, ln, sc)
+
+
 def _collect_result(lib, fetch_fn, call, B, want_logits, decode=None):
     """The learn-L-then-fetch protocol shared by pf_engine and pf_group handles.  decode = (engine handle, flags):
     also the decoding extras of an engine with Engine.set_decode flags."""
@@ -174,8 +227,11 @@ def _collect_result(lib, fetch_fn, call, B, want_logits, decode=None):
     topk = None
     if decode is not None and decode[1] & N.PF_DECODE_TOPK:
         topk = _fetch_topk(lib, decode[0], B, L)
+    beam = None
+    if decode is not None and decode[1] & N.PF_DECODE_CTC_BEAM:
+        beam = _fetch_ctc_beam(lib, decode[0], B, decode[2])
     N.check(fetch_fn(C.byref(out)))
-    return BatchResult(ids[:, :L].copy(), tn, L, V, logits, peak, scores, ctc, topk)
+    return BatchResult(ids[:, :L].copy(), tn, L, V, logits, peak, scores, ctc, topk, beam)
 
 
 class Engine:
@@ -196,6 +252,7 @@ class Engine:
         N.check(self._lib.pf_engine_info(self._h, kind, vocab, feat, ts))
         self.kind, self.vocab, self.feat_dim = kind.value, vocab.value, feat.value
         self._decode = 0
+        self._beam_n = 16
 
     def close(self):
         if getattr(self, "_h", None):
@@ -234,13 +291,41 @@ class Engine:
     # ---- forward ------------------------------------------------------------
     def _collect(self, call, B, want_logits):
         return _collect_result(self._lib, lambda o: self._lib.pf_fetch(self._h, o), call, B, want_logits,
-                               (self._h, self._decode))
+                               (self._h, self._decode, self._beam_n))
 
     def set_decode(self, flags: int):
         """Decoding extras of the forwards that follow (_native.PF_DECODE_SCORES | PF_DECODE_CTC; 0 = off, the reference
         behaviour): BatchResult.scores, and for a SenseVoice model BatchResult.ctc."""
         N.check(self._lib.pf_engine_set_decode(self._h, int(flags)))
-        self._decode = int(flags) | (N.PF_DECODE_SCORES if int(flags) & (N.PF_DECODE_CTC | N.PF_DECODE_TOPK) else 0)
+        f = int(flags) | (N.PF_DECODE_TOPK if int(flags) & N.PF_DECODE_CTC_BEAM else 0)
+        self._decode = f | (N.PF_DECODE_SCORES if f & (N.PF_DECODE_CTC | N.PF_DECODE_TOPK) else 0)
+
+    def set_ctc_beam(self, W: int = 16, n_best: int = 16):
+        """Beam width W and list length n_best (1 <= n_best <= W <= 64, default 16 / 16) of PF_DECODE_CTC_BEAM for the
+        forwards that follow."""
+        N.check(self._lib.pf_engine_set_ctc_beam(self._h, int(W), int(n_best)))
+        self._beam_n = int(n_best)
+
+    host_ctc_beam = staticmethod(host_ctc_beam)
+
+    def op_ctc_beam(self, blank_lp, ids, val, n, lens, W, n_best=None, blank=0, cap=None, out=None) -> CtcBeamResult:
+        """The pipeline's beam search kernel on caller data: blank_lp [B, T], ids / val [B, T, K], n [B, T], lens [B].
+        out = (ids [B, N, cap] int64, len [B, N] int32, score [B, N] float64, n_hyp [B] int32): write into these arrays."""
+        y = np.ascontiguousarray(ids, dtype=np.int64)
+        v = _f32(val)
+        nn = np.ascontiguousarray(n, dtype=np.int32)
+        lb = _f32(blank_lp)
+        ln = np.ascontiguousarray(lens, dtype=np.int32)
+        B, T, K = y.shape
+        n_best = W if n_best is None else n_best
+        cap = max(T, 1) if cap is None else cap
+        if out is None:
+            out = (np.zeros((B, max(n_best, 0), cap), np.int64), np.zeros((B, max(n_best, 0)), np.int32),
+                   np.zeros((B, max(n_best, 0)), np.float64), np.zeros(B, np.int32))
+        oi, ol, sc, nh = out
+        N.check(self._lib.pf_op_ctc_beam(self._h, _fp(lb), _i64p(y), _fp(v), _i32p(nn), _i32p(ln), B, T, K, int(blank), int(W),
+                                         int(n_best), _i64p(oi), _i32p(ol), _dp(sc), cap, _i32p(nh)))
+        return CtcBeamResult(nh, oi, ol, sc)
 
     def set_topk(self, k: int):
         """K of PF_DECODE_TOPK (1 .. _native.PF_TOPK_MAX, default 4) for the forwards that follow."""

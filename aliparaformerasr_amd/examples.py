@@ -1,7 +1,7 @@
 """Command-line harness mirroring AliParaformerAsr.Examples (`-type offline` and `-type online`).
 
     python -m aliparaformerasr_amd.examples -type offline -method batch -base <dir> -model <name> \
-        [-accuracy int8] [-threads 2] [-decode ctc|frames] [-intake host|device] [-nbest N [-topk K]] -files a.wav b.wav
+        [-accuracy int8] [-threads 2] [-decode ctc|frames] [-intake host|device] [-nbest N [-topk K] [-beam W]] -files a.wav b.wav
     python -m aliparaformerasr_amd.examples -type online -method one -base <dir> -model <name> -files a.wav
 
 Mirrors (file:line in /root/reference/AliParaformerAsr.Examples):
@@ -25,7 +25,9 @@ timestamps (OfflineRecognizer.SetDecode); `-decode frames`, the default, is the 
 OfflineStream.AddPcm raw: decode, down-mix and resample run on the device and give the samples GetFileSample gives;
 `-intake host`, the default, is the path above, untouched.
 `-nbest N [-topk K]` (offline, paraformer models; OfflineRecognizer.SetNBest) prints under each result line the N best
-hypotheses, one `nbest[i] score:<sum of log-probs> text:<text>` line each, best first; line 0 is the result itself."""
+hypotheses, one `nbest[i] score:<sum of log-probs> text:<text>` line each, best first; line 0 is the result itself.
+`-nbest N -beam W` (offline, SenseVoice models; OfflineRecognizer.SetCtcBeam) prints the N best labelings of a CTC prefix
+beam search of width W in the same form; the score is the log of the summed alignments."""
 from __future__ import annotations
 
 import ctypes as C
@@ -131,7 +133,8 @@ def _nbest_lines(stream) -> list:
 
 
 def offline_recognizer(method="one", model="paraformer-seaco-large-zh-timestamp-onnx-offline", accuracy="int8",
-                       threads=2, files=None, base=None, out=sys.stdout, decode="frames", intake="host", nbest=0, topk=4):
+                       threads=2, files=None, base=None, out=sys.stdout, decode="frames", intake="host", nbest=0, topk=4,
+                       beam=0):
     from .offline_recognizer import OfflineRecognizer
     base = base or os.getcwd()
     sel = select_model_files(base, model, accuracy)
@@ -142,7 +145,9 @@ def offline_recognizer(method="one", model="paraformer-seaco-large-zh-timestamp-
     rec = OfflineRecognizer(threadsNum=threads, **sel)
     if decode == "ctc":
         rec.SetDecode(ctc=True)
-    if nbest:
+    if nbest and beam:
+        rec.SetCtcBeam(nbest, beam, topk)
+    elif nbest:
         rec.SetNBest(nbest, topk)
     print("init_models_elapsed_milliseconds:%s" % ((time.perf_counter() - t0) * 1e3), file=out)
     if not files:
@@ -326,8 +331,8 @@ def parse_args(argv, env=None):
             if i >= len(argv) or argv[i].lower() not in ("host", "device"):
                 raise ValueError("The intake type must be host or device")
             cfg["intake"] = argv[i].lower()
-        elif a in ("-nbest", "-topk"):
-            lo, hi = (1, N.PF_NBEST_MAX) if a == "-nbest" else (1, N.PF_TOPK_MAX)
+        elif a in ("-nbest", "-topk", "-beam"):
+            lo, hi = (1, N.PF_TOPK_MAX) if a == "-topk" else (1, N.PF_NBEST_MAX)
             try:
                 i += 1
                 v = int(argv[i])
@@ -355,6 +360,10 @@ def parse_args(argv, env=None):
         raise ValueError("You must specify the recognizer type (-type online/offline)")
     if "topk" in cfg and "nbest" not in cfg:
         raise ValueError("-topk goes with -nbest")
+    if "beam" in cfg and "nbest" not in cfg:
+        raise ValueError("-beam goes with -nbest")
+    if "beam" in cfg and cfg["beam"] < cfg["nbest"]:
+        raise ValueError("The beam value must not be smaller than the nbest value")
     if "nbest" in cfg and cfg["recognizerType"] != "offline":
         raise ValueError("-nbest is an offline option")
     return cfg
@@ -374,7 +383,7 @@ def main(argv=None):
     elif cfg["recognizerType"] == "offline":
         offline_recognizer(cfg["methodType"], cfg["modelName"], cfg["modelAccuracy"], cfg["threads"], cfg["files"],
                            cfg["modelBasePath"] or None, decode=cfg.get("decode", "frames"), intake=cfg.get("intake", "host"),
-                           nbest=cfg.get("nbest", 0), topk=cfg.get("topk", 4))
+                           nbest=cfg.get("nbest", 0), topk=cfg.get("topk", 4), beam=cfg.get("beam", 0))
     else:
         print("the recognizer type must be online or offline")
         return 2

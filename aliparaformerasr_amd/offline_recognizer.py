@@ -196,8 +196,8 @@ class OfflineStream:
 
     @property
     def Alternatives(self) -> List["Alternative"]:
-        """The n-best list of the last GetResults (paraformer, OfflineRecognizer.SetNBest with N > 1; else empty): by
-        descending Score; entry 0 is the result itself."""
+        """The n-best list of the last GetResults (paraformer, OfflineRecognizer.SetNBest with N > 1: entry 0 is the result
+        itself; SenseVoice, OfflineRecognizer.SetCtcBeam: the beam search's labelings; else empty), by descending Score."""
         n = C.c_int32()
         _ck(self._lib.pf_stream_num_alternatives(self._h, n))
         out = []
@@ -313,6 +313,14 @@ class OfflineRecognizer:
         Alternatives, the exact N-best (<= 64) hypotheses with their scores.  Tokens, Timestamps, Scores and the result
         text stay as they are."""
         _ck(self._lib.pf_recognizer_set_nbest(self._h, int(N), int(K)))
+
+    def SetCtcBeam(self, N: int, W: int = 0, K: int = 4) -> None:
+        """SenseVoice models: a CTC prefix beam search on the device for every GetResults that follows (off by default;
+        N = 0 turns it off again).  Each stream's Alternatives then holds up to N (<= 64) labelings by descending Score —
+        the float64 log of the summed alignments the search kept — found with beam width W (0 = max(16, N)) over the K
+        (1 .. 8) best ids per frame.  Tokens, Timestamps, Scores and the result text stay as they are; entry 0 is the
+        search's best, which need not be the result."""
+        _ck(self._lib.pf_recognizer_set_ctc_beam(self._h, int(N), int(W), int(K)))
 
     def GetResult(self, stream: OfflineStream) -> OfflineRecognizerResultEntity:
         return self.GetResults([stream])[0]

@@ -257,6 +257,12 @@ namespace AliParaformerAsr.Hip
         /// Timestamps, Scores and the result text stay as they are.</summary>
         public void SetNBest(int N, int K = 4) => ParaformerHip.Check(ParaformerHip.pf_recognizer_set_nbest(_r, N, K));
 
+        /// <summary>Not in the reference: SenseVoice models only.  A CTC prefix beam search on the device for every GetResults that
+        /// follows (off by default; N = 0 turns it off again): each stream's Alternatives holds up to N (&lt;= 64) labelings by
+        /// descending Score (the log of the summed alignments), found with beam width W (0 = max(16, N)) over the K (1 .. 8) best
+        /// ids per frame.  Tokens, Timestamps, Scores and the result text stay as they are.</summary>
+        public void SetCtcBeam(int N, int W = 0, int K = 4) => ParaformerHip.Check(ParaformerHip.pf_recognizer_set_ctc_beam(_r, N, W, K));
+
         public OfflineStream CreateOfflineStream()
         {
             ParaformerHip.Check(ParaformerHip.pf_recognizer_create_stream(_r, out IntPtr s));

@@ -93,6 +93,15 @@ namespace AliParaformerAsr.Native
         [DllImport(Lib)] internal static extern int pf_engine_set_topk(IntPtr e, int k);
         [DllImport(Lib)] internal static extern int pf_fetch_topk(IntPtr e, [Out] long[]? ids, [Out] float[]? val, [Out] int[]? n, long capRows,
                                                                  out int L, out int K);
+        // CTC beam search (additions to ABI 6): PF_DECODE_CTC_BEAM (SenseVoice; implies TOPK and SCORES) keeps the N best labelings
+        // of a prefix beam search of width W (1 <= N <= W <= PF_NBEST_MAX, default 16 / 16) with their float64 scores
+        internal const int PF_DECODE_CTC_BEAM = 16;
+        [DllImport(Lib)] internal static extern int pf_engine_set_ctc_beam(IntPtr e, int W, int N);
+        [DllImport(Lib)] internal static extern int pf_fetch_ctc_beam(IntPtr e, [Out] long[]? ids, [Out] int[]? len, [Out] double[]? score, int cap,
+                                                                     [Out] int[]? nHyp, out int lenMax);
+        [DllImport(Lib)] internal static extern int pf_host_ctc_beam(float[] blankLp, long blankStride, long[] ids, float[] val, int[] n, int T, int K,
+                                                                    int blank, int W, int N, [Out] long[] outIds, [Out] int[] outLen,
+                                                                    [Out] double[] outScore, int cap, out int nHyp);
         [DllImport(Lib)] internal static extern int pf_host_nbest(long[]? ids, float[] val, int[] n, int L, int K, int nFree, int N,
                                                                  [Out] int[] outRanks, [Out] double[] outScores, out int nOut);
 
@@ -144,6 +153,7 @@ namespace AliParaformerAsr.Native
         [DllImport(Lib)] internal static extern int pf_recognizer_set_decode(IntPtr r, int flags);
         [DllImport(Lib)] internal static extern int pf_stream_scores(IntPtr s, out IntPtr scores, out int n);
         [DllImport(Lib)] internal static extern int pf_recognizer_set_nbest(IntPtr r, int N, int K);
+        [DllImport(Lib)] internal static extern int pf_recognizer_set_ctc_beam(IntPtr r, int N, int W, int K);
         [DllImport(Lib)] internal static extern int pf_stream_token_alternatives(IntPtr s, out IntPtr ids, out IntPtr val, out int nTokens, out int K);
         [DllImport(Lib)] internal static extern int pf_stream_num_alternatives(IntPtr s, out int n);
         [DllImport(Lib)] internal static extern int pf_stream_alternative(IntPtr s, int i, out IntPtr ids, out int nIds, out double score,

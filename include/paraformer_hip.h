@@ -248,6 +248,41 @@ int pf_fetch_topk(pf_engine* e, int64_t* ids, float* val, int32_t* n, int64_t ca
 int pf_host_nbest(const int64_t* ids, const float* val, const int32_t* n, int32_t L, int32_t K, int32_t n_free, int32_t N,
                   int32_t* out_ranks, double* out_scores, int32_t* n_out);
 
+/* ---- CTC beam search (additions to ABI 6; nothing is launched or allocated without the flag) ---------------------------
+   PF_DECODE_CTC_BEAM (pf_engine_set_decode; SenseVoice only, every math_mode; implies TOPK and SCORES; independent of
+   PF_DECODE_CTC; PF_ERR_UNSUPPORTED for a paraformer or SeACo model and for a pf_group forward): behind the top-k launch one
+   kernel (csrc/k_ctcbeam.hip) runs a CTC prefix beam search per utterance and keeps its N best LABELINGS.  Under CTC the
+   probability of a labeling is the sum over all of its alignments; the search sums the alignments it keeps.
+   INPUTS per utterance b: the frames t < n_b (the count PF_DECODE_CTC uses, prompt rows included), the blank (id 0) log-prob
+   of each frame and the frame's top-k list (K of pf_engine_set_topk) exactly as pf_fetch_topk returns it.  fp32 inputs are
+   widened to float64; all scores are float64.  lse(a, b) = max + log1p(exp(-|a - b|)); an argument of -inf gives the other.
+   The beam is an ordered list of at most W entries (prefix, pb, pnb), at first [((), 0, -inf)].  At frame t the candidates C_t
+   are the listed entries r < n[t] whose id is not blank.  For beam entry i in rank order, last token e, tot = lse(pb, pnb):
+     stay     (candidate index i*(K+1)):      pb' = tot + lb[t]; pnb' = pnb + lp_t(e) when the prefix is non-empty and e in C_t,
+              else -inf
+     extend c (candidate index i*(K+1)+1+r):  pnb' = (c == e ? pb : tot) + lp_t(c), pb' = -inf; dropped when the base is -inf
+     merge    prefix + c is the prefix of another beam entry q: no candidate of its own, pnb'_q = lse(pnb'_q, value)
+     select   candidates whose total lse(pb', pnb') is -inf are discarded; the W best by total stay, ties to the smaller
+              candidate index; that order is the new beam's order.
+   After the last frame the first N entries are the hypotheses: ids, length, score = total.  n_hyp[b] = 0 when a frame t < n_b
+   has n[t] == 0 or a NaN blank log-prob.  Hypothesis 0 is the search's best, NOT necessarily the collapsed arg-max ids;
+   token_ids, pf_fetch_scores, pf_fetch_ctc and pf_fetch_topk are what they are without the flag.
+   W / N: pf_engine_set_ctc_beam, 1 <= N <= W <= PF_NBEST_MAX, default 16 / 16, for the forwards that follow.
+   The flag is bit 16; bits 4 and 64 stay unassigned (PF_ERR_INVALID_ARG). */
+#define PF_DECODE_CTC_BEAM 16
+int pf_engine_set_ctc_beam(pf_engine* e, int32_t W, int32_t N);
+/* ids [B, N, cap] int64 (-1 past a hypothesis' length), len [B, N] (0 past n_hyp), score [B, N] float64 (-inf past n_hyp),
+   n_hyp [B], each optional; N is the one in force at the forward.  *len_max = the longest hypothesis of the batch; ids with
+   cap < *len_max -> PF_ERR_CAPACITY (len_max, n_hyp, len and score filled in).  PF_ERR_INVALID_ARG when that forward ran
+   without the flag.  Call it BEFORE the pf_fetch that receives token_ids (it releases the thread's slot). */
+int pf_fetch_ctc_beam(pf_engine* e, int64_t* ids, int32_t* len, double* score, int32_t cap, int32_t* n_hyp, int32_t* len_max);
+/* The same search for ONE utterance in plain host code (the twin of the kernel): blank_lp[t * blank_stride], ids / val [T, K],
+   n [T]; out_ids [N, cap], out_len [N], out_score [N] filled as above, *n_hyp.  PF_ERR_CAPACITY when a hypothesis is longer
+   than cap (cap >= T always suffices). */
+int pf_host_ctc_beam(const float* blank_lp, int64_t blank_stride, const int64_t* ids, const float* val, const int32_t* n, int32_t T,
+                     int32_t K, int32_t blank, int32_t W, int32_t N, int64_t* out_ids, int32_t* out_len, double* out_score,
+                     int32_t cap, int32_t* n_hyp);
+
 /* ---- PCM intake (additions to ABI 6) --------------------------------------------------------------------------------
    The audio in the form callers hold it — a wav payload, PCM off a socket — uploaded RAW and turned into the engine's
    float32 mono samples at `fs` by one kernel (csrc/k_pcm.hip) in front of the unchanged fbank.  The result is bit for bit
@@ -356,6 +391,12 @@ int pf_op_pcm_convert(pf_engine* e, const void* data, int64_t n_values, const pf
    read in a row), K: 1 .. PF_TOPK_MAX; ids [rows, K], val [rows, K], n [rows] as pf_fetch_topk. */
 int pf_op_topk(pf_engine* e, const float* x, int64_t rows, int32_t V, int32_t ld, int32_t K, int64_t* ids, float* val,
                int32_t* n);
+/* exactly the pipeline's beam search kernel (k_ctcbeam.hip) on caller arrays: blank_lp [B * T] (dense), ids / val [B * T, K],
+   n [B * T], lens [B] (clamped to 0 .. T; nothing at or beyond lens[b] or n[row] is read); outputs as pf_fetch_ctc_beam with
+   a token at or beyond cap counted in len but not stored. */
+int pf_op_ctc_beam(pf_engine* e, const float* blank_lp, const int64_t* ids, const float* val, const int32_t* n, const int32_t* lens,
+                   int32_t B, int32_t T, int32_t K, int32_t blank, int32_t W, int32_t N, int64_t* out_ids, int32_t* out_len,
+                   double* out_score, int32_t cap, int32_t* n_hyp);
 /* C = A[M,K] * W[N,K]^T + bias, f16 operands / f32 accumulate; epilogue 0 none, 1 relu,
    2 = f16 result store (the path the pipeline uses), returned widened to fp32. */
 /* One dynamically quantised Linear, the building block of math_mode 2 (the reference's default model.int8.onnx:
@@ -608,6 +649,13 @@ int pf_stream_scores(pf_stream* s, const float** scores, int32_t* n);
    N > 1 on a SenseVoice recognizer -> PF_ERR_UNSUPPORTED (its frames are not independent tokens); any N >= 1 on SeACo too.
    Tokens, Timestamps, Scores and the result text are what they are without it. */
 int pf_recognizer_set_nbest(pf_recognizer* r, int32_t N, int32_t K);
+/* SenseVoice only (see "CTC beam search"; PF_ERR_UNSUPPORTED otherwise).  N = 0: off.  N >= 1 (<= PF_NBEST_MAX), W = 0
+   (max(16, N)) or N .. 64, K = 0 (4) or 1 .. PF_TOPK_MAX: PF_DECODE_CTC_BEAM on every engine of the pool, present and future,
+   beside the flags of pf_recognizer_set_decode.  After GetResults each stream's Alternatives holds up to N labelings by
+   descending score (ids of their own length, score = the float64 total, text and tokens by the same DecodeMulti as the
+   result); TokenAlternatives is filled as with pf_recognizer_set_nbest(1, K).  Tokens, Timestamps, Scores and the result
+   text are what they are without it; alternative 0 is the search's best, not necessarily the result. */
+int pf_recognizer_set_ctc_beam(pf_recognizer* r, int32_t N, int32_t W, int32_t K);
 /* ids / val: [*n_tokens, *K], parallel to pf_stream_tokens; slots past a position's n hold -1 / -inf.  *n_tokens = 0
    without pf_recognizer_set_nbest.  The pointers stay valid until the stream's next GetResults. */
 int pf_stream_token_alternatives(pf_stream* s, const int64_t** ids, const float** val, int32_t* n_tokens, int32_t* K);

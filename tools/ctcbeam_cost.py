@@ -1,0 +1,117 @@
+"""What PF_DECODE_CTC_BEAM costs on the SenseVoice bench workload (sensevoice-small 64 x 10 s, audio staged, one step in
+flight), in ONE process: a step with PF_DECODE_TOPK alone and with the beam search behind it, alternating blocks, medians;
+the device time of the `ctc_beam` class; and the host twin (pf_host_ctc_beam, one thread) over the same fetched lists and
+blank column, compared hypothesis by hypothesis with what the device kept.
+
+    python tools/ctcbeam_cost.py [--settings 16:4,64:8] [--steps 20] [--blocks 3] [--nbest 0]
+
+`--settings` lists W:K pairs (N = W unless --nbest is given).  `--settings none` never touches the beam API and times the
+TOPK-alone legs only, so the same file also runs on a build that predates the flag (the parent's step time)."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from aliparaformerasr_amd import _native as N                     # noqa: E402
+from aliparaformerasr_amd import weights as W                     # noqa: E402
+from aliparaformerasr_amd.engine import Engine                    # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--settings", default="16:4,64:8")
+ap.add_argument("--steps", type=int, default=20)
+ap.add_argument("--blocks", type=int, default=3)
+ap.add_argument("--warmup", type=int, default=5)
+ap.add_argument("--nbest", type=int, default=0)
+ap.add_argument("--batch", type=int, default=64)
+ap.add_argument("--seconds", type=int, default=10)
+args = ap.parse_args()
+settings = [] if args.settings == "none" else [tuple(int(x) for x in s.split(":")) for s in args.settings.split(",")]
+B = args.batch
+
+cfg = W.sensevoice_small_config(use_itn=True)
+eng = Engine(weights=W.pack_pfw(cfg, W.synth_weights(cfg, 42)), cmvn=W.synth_cmvn(), device=0)
+audio = [W.synth_audio(args.seconds * 16000, u) for u in range(B)]
+eng.stage_audio(audio)
+
+# legs: ("topk", K) and ("beam", W, K)
+legs = []
+for K in sorted({k for _, k in settings} or {4, 8}):
+    legs.append(("topk", K))
+legs += [("beam", w, k) for w, k in settings]
+
+
+def set_leg(leg):
+    if leg[0] == "topk":
+        eng.set_decode(N.PF_DECODE_TOPK)
+        eng.set_topk(leg[1])
+    else:
+        eng.set_decode(N.PF_DECODE_CTC_BEAM)
+        eng.set_topk(leg[2])
+        eng.set_ctc_beam(leg[1], args.nbest or leg[1])
+
+
+def step():
+    t0 = time.perf_counter()
+    eng.run_staged()
+    eng.sync()
+    return (time.perf_counter() - t0) * 1e3
+
+
+for leg in legs:
+    set_leg(leg)
+    for _ in range(args.warmup):
+        step()
+times = {leg: [] for leg in legs}
+for _ in range(args.blocks):
+    for leg in legs:
+        set_leg(leg)
+        step()
+        times[leg] += [step() for _ in range(args.steps)]
+out = {"model": "sensevoice", "batch": B, "seconds": args.seconds, "steps_per_leg": args.steps * args.blocks, "legs": {}}
+for leg in legs:
+    t = sorted(times[leg])
+    name = "topk_k%d" % leg[1] if leg[0] == "topk" else "beam_w%d_k%d" % (leg[1], leg[2])
+    rec = {"median_ms": round(statistics.median(t), 4), "p10_ms": round(t[len(t) // 10], 4), "p90_ms": round(t[(len(t) * 9) // 10], 4)}
+    set_leg(leg)
+    for cls in ("topk",) + (("ctc_beam",) if leg[0] == "beam" else ()):      # event-timed, one untimed step per class
+        eng.profile_reset()
+        eng.profile_select(cls)
+        eng.profile(True)
+        eng.run_staged()
+        eng.sync()
+        eng.profile(False)
+        ms, n, _ = eng.profile_get(cls)
+        if n:
+            rec[cls + "_kernel_ms"] = round(ms, 4)
+    out["legs"][name] = rec
+
+# the host twin over the same lists: one forward with the log-probs (for the blank column), utterance by utterance on this thread
+for w, k in settings:
+    eng.set_decode(N.PF_DECODE_CTC_BEAM)
+    eng.set_topk(k)
+    nb = args.nbest or w
+    eng.set_ctc_beam(w, nb)
+    r = eng.recognize(audio, want_logits=True)
+    rows = [4 + eng.frontend(a).shape[0] for a in audio]
+    lb = np.ascontiguousarray(r.logits[:, :, 0])
+    del r.logits
+    t0 = time.perf_counter()
+    host = [eng.host_ctc_beam(lb[b, :rows[b]], r.topk.ids[b, :rows[b]], r.topk.val[b, :rows[b]], r.topk.n[b, :rows[b]], w, nb)
+            for b in range(B)]
+    host_ms = (time.perf_counter() - t0) * 1e3
+    same_ids = sum(host[b].hyps(0) == r.beam.hyps(b) or [h[0] for h in host[b].hyps(0)] == [h[0] for h in r.beam.hyps(b)] for b in range(B))
+    worst = 0.0
+    for b in range(B):
+        for (_, a), (_, c) in zip(host[b].hyps(0), r.beam.hyps(b)):
+            worst = max(worst, abs(a - c) / (16 * rows[b] * 2.0 ** -53 * max(1.0, abs(c))))
+    out["legs"]["beam_w%d_k%d" % (w, k)].update({
+        "host_twin_ms_per_batch": round(host_ms, 3), "L": r.L, "utterances_with_identical_lists": int(same_ids),
+        "worst_score_difference_in_tolerances": round(worst, 4), "hypotheses": int(r.beam.n_hyp.sum()),
+        "longest_hypothesis": int(r.beam.len.max())})
+print(json.dumps(out))
+eng.close()
