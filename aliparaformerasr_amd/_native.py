@@ -28,6 +28,8 @@ PF_DECODE_SCORES = 1
 PF_DECODE_CTC = 2
 PF_DECODE_TOPK = 8
 PF_DECODE_CTC_BEAM = 16
+PF_DECODE_ALIGN = 32
+PF_ALIGN_MAX_TOKENS = 1023
 PF_TOPK_MAX = 8
 PF_NBEST_MAX = 64
 
@@ -172,6 +174,15 @@ SIGNATURES = {
     "pf_op_ctc_beam": (C.c_int, [_vp, _f, _i64, _f, _i32, _i32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                  _i64, _i32, _P(C.c_double), C.c_int32, _i32]),
     "pf_recognizer_set_ctc_beam": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32]),
+    "pf_engine_set_align_targets": (C.c_int, [_vp, _i64, _i32, C.c_int32, C.c_int32]),
+    "pf_fetch_align": (C.c_int, [_vp, _f, _P(C.c_double), _i32, _i32, _i32, _i32, _f, C.c_int32, _i32, _i32]),
+    "pf_host_ctc_align": (C.c_int, [_f, C.c_int64, C.c_int32, C.c_int32, _i64, C.c_int32, _f, _P(C.c_double), _i32, _i32, _i32, _f]),
+    "pf_op_ctc_align": (C.c_int, [_vp, _f, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _i32, _i32, _i32, C.c_int32, C.c_int32,
+                                  _f, _P(C.c_double), _i32, _i32, _i32, _f]),
+    "pf_recognizer_set_align": (C.c_int, [_vp, C.c_int32]),
+    "pf_stream_set_align_ids": (C.c_int, [_vp, _i64, C.c_int32]),
+    "pf_stream_alignment": (C.c_int, [_vp, _P(_i32), _P(_f), _i32, _f, _P(C.c_double), _i32]),
+    "pf_stream_alternative_timestamps": (C.c_int, [_vp, C.c_int32, _P(_i32), _i32, _P(C.c_double)]),
     "pf_stream_token_alternatives": (C.c_int, [_vp, _P(_i64), _P(_f), _i32, _i32]),
     "pf_stream_num_alternatives": (C.c_int, [_vp, _i32]),
     "pf_stream_alternative": (C.c_int, [_vp, C.c_int32, _P(_i64), _i32, _P(C.c_double), _P(C.c_char_p), _i32]),

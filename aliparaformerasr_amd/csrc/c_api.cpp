@@ -421,6 +421,36 @@ int pf_host_ctc_beam(const float* blank_lp, int64_t blank_stride, const int64_t*
   PF_CATCH
 }
 
+int pf_engine_set_align_targets(pf_engine* h, const int64_t* ids, const int32_t* len, int32_t B, int32_t cap) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->set_align_targets(ids, len, B, cap);
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_fetch_align(pf_engine* h, float* path_score, double* loglik, int32_t* ok, int32_t* len, int32_t* first, int32_t* last,
+                   float* tok_score, int32_t cap, int32_t* H, int32_t* len_max) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->fetch_align(path_score, loglik, ok, len, first, last, tok_score, cap, H, len_max);
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_host_ctc_align(const float* lp, int64_t ld, int32_t T, int32_t V, const int64_t* y, int32_t U, float* path_score,
+                      double* loglik, int32_t* ok, int32_t* first, int32_t* last, float* tok_score) {
+  PF_TRY
+  NEED(ok);
+  *ok = host_ctc_align(lp, ld, T, V, y, U, path_score, loglik, first, last, tok_score);
+  return PF_OK;
+  PF_CATCH
+}
+
 int pf_profile_enable(pf_engine* h, int32_t on) {
   PF_TRY
   E(h)->profile_enable(on != 0);
@@ -625,6 +655,24 @@ int pf_op_ctc_beam(pf_engine* h, const float* blank_lp, const int64_t* ids, cons
   if ((int64_t)B * T > 0) { NEED(blank_lp); NEED(ids); NEED(val); NEED(n); }
   std::lock_guard<std::mutex> lk(e->mutex());
   e->op_ctc_beam(blank_lp, ids, val, n, lens, B, T, K, blank, W, N, out_ids, out_len, out_score, cap, n_hyp);
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_op_ctc_align(pf_engine* h, const float* lp, int32_t B, int32_t T, int32_t V, int32_t ld, const int32_t* tgt,
+                    const int32_t* tlen, const int32_t* lens, int32_t H, int32_t cap, float* path_score, double* loglik,
+                    int32_t* ok, int32_t* first, int32_t* last, float* tok_score) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  PF_CHECK(B >= 0 && B <= 65535 && T >= 0 && H >= 0 && cap >= 1 && V >= 1 && ld >= V, PF_ERR_INVALID_ARG,
+           "ctc_align: bad shape (cap >= 1, ld >= V >= 1, B <= 65535)");
+  if ((int64_t)B * H > 0) {
+    NEED(tgt); NEED(tlen); NEED(lens); NEED(path_score); NEED(loglik); NEED(ok); NEED(first); NEED(last); NEED(tok_score);
+    if (T > 0) NEED(lp);
+  }
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->op_ctc_align(lp, B, T, V, ld, tgt, tlen, lens, H, cap, path_score, loglik, ok, first, last, tok_score);
   return PF_OK;
   PF_CATCH
 }
@@ -1151,6 +1199,55 @@ int pf_recognizer_set_ctc_beam(pf_recognizer* h, int32_t N, int32_t W, int32_t K
   std::shared_ptr<Recognizer> r = R(h);
   PF_CHECK(!r->disposed(), PF_ERR_DISPOSED, "OfflineRecognizer");
   r->SetCtcBeam(N, W, K);
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_recognizer_set_align(pf_recognizer* h, int32_t on) {
+  PF_TRY
+  std::shared_ptr<Recognizer> r = R(h);
+  PF_CHECK(!r->disposed(), PF_ERR_DISPOSED, "OfflineRecognizer");
+  r->SetAlign(on != 0);
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_stream_set_align_ids(pf_stream* h, const int64_t* ids, int32_t n) {
+  PF_TRY
+  Stream* s = S(h);
+  if (n < 0) { s->AlignIds.clear(); s->has_align = false; return PF_OK; }
+  if (n > 0) NEED(ids);
+  PF_CHECK(n <= PF_ALIGN_MAX_TOKENS, PF_ERR_CAPACITY, "a target of more than PF_ALIGN_MAX_TOKENS ids");
+  const int64_t V = s->owner ? (int64_t)s->owner->tokens().size() : INT64_MAX;
+  for (int i = 0; i < n; ++i) PF_CHECK(ids[i] >= 1 && ids[i] < V, PF_ERR_INVALID_ARG, "a target id outside [1, V)");
+  s->AlignIds.assign(ids, ids + n);
+  s->has_align = true;
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_stream_alignment(pf_stream* h, const int32_t** begin_end, const float** tok_score, int32_t* n, float* path_score,
+                        double* loglik, int32_t* ok) {
+  PF_TRY
+  Stream* s = S(h);
+  if (begin_end) *begin_end = s->AlignTs.data();
+  if (tok_score) *tok_score = s->AlignTok.data();
+  if (n) *n = s->AlignN;
+  if (path_score) *path_score = s->AlignPath;
+  if (loglik) *loglik = s->AlignLoglik;
+  if (ok) *ok = s->AlignOk;
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_stream_alternative_timestamps(pf_stream* h, int32_t i, const int32_t** begin_end, int32_t* n, double* loglik) {
+  PF_TRY
+  Stream* s = S(h);
+  PF_CHECK(i >= 0 && i < (int32_t)s->Alternatives.size(), PF_ERR_INVALID_ARG, "alternative index out of range");
+  const Alternative& a = s->Alternatives[(size_t)i];
+  if (begin_end) *begin_end = a.ts.data();
+  if (n) *n = (int32_t)(a.ts.size() / 2);
+  if (loglik) *loglik = a.loglik;
   return PF_OK;
   PF_CATCH
 }

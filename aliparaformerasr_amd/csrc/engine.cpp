@@ -1837,8 +1837,12 @@ void Engine::sensevoice_head(int B, int T, bool want_logits) {
 
 // ------------------------------------------------------------------ decoding extras ---------
 void Engine::set_decode(int flags) {
-  PF_CHECK((flags & ~(PF_DECODE_SCORES | PF_DECODE_CTC | PF_DECODE_TOPK | PF_DECODE_CTC_BEAM)) == 0, PF_ERR_INVALID_ARG,
-           "set_decode: unknown flag bits");
+  PF_CHECK((flags & ~(PF_DECODE_SCORES | PF_DECODE_CTC | PF_DECODE_TOPK | PF_DECODE_CTC_BEAM | PF_DECODE_ALIGN)) == 0,
+           PF_ERR_INVALID_ARG, "set_decode: unknown flag bits");
+  if (flags & PF_DECODE_ALIGN) {
+    PF_CHECK(mc_.kind_id() == 1 && !mc_.seaco, PF_ERR_UNSUPPORTED, "PF_DECODE_ALIGN: only a SenseVoice model has a CTC head");
+    flags |= PF_DECODE_SCORES;
+  }
   if (flags & PF_DECODE_CTC_BEAM) {
     PF_CHECK(mc_.kind_id() == 1 && !mc_.seaco, PF_ERR_UNSUPPORTED, "PF_DECODE_CTC_BEAM: only a SenseVoice model has a CTC head");
     flags |= PF_DECODE_TOPK;
@@ -1851,6 +1855,32 @@ void Engine::set_decode(int flags) {
   // the SeACo bias merge replaces rows of the result after the arg-max; their scores would need a path of their own
   PF_CHECK(flags == 0 || !mc_.seaco, PF_ERR_UNSUPPORTED, "PF_DECODE_SCORES: not available for a SeACo model");
   decode_flags_ = flags;
+  if (!(flags & PF_DECODE_ALIGN)) { align_B_ = 0; align_tgt_.clear(); align_len_.clear(); }
+}
+
+void Engine::set_align_targets(const int64_t* ids, const int32_t* len, int B, int cap) {
+  PF_CHECK(decode_flags_ & PF_DECODE_ALIGN, PF_ERR_INVALID_ARG, "set_align_targets: PF_DECODE_ALIGN is not set");
+  PF_CHECK(B >= 0 && cap >= 0 && (B == 0 || len), PF_ERR_INVALID_ARG, "set_align_targets: bad B / cap / len");
+  int mx = 0;
+  for (int b = 0; b < B; ++b) {
+    PF_CHECK(len[b] >= -1, PF_ERR_INVALID_ARG, "set_align_targets: len[b] is -1 (no target) or a length");
+    PF_CHECK(len[b] <= PF_ALIGN_MAX_TOKENS && len[b] <= cap, PF_ERR_CAPACITY,
+             "set_align_targets: a target of " + std::to_string(len[b]) + " tokens > min(cap, PF_ALIGN_MAX_TOKENS)");
+    mx = std::max(mx, len[b]);
+  }
+  PF_CHECK(mx == 0 || ids, PF_ERR_INVALID_ARG, "set_align_targets: null ids");
+  for (int b = 0; b < B; ++b)
+    for (int p = 0; p < len[b]; ++p) {
+      const int64_t c = ids[(size_t)b * cap + p];
+      PF_CHECK(c >= 1 && c < mc_.vocab, PF_ERR_INVALID_ARG, "set_align_targets: an id outside [1, V)");
+    }
+  const int c1 = std::max(mx, 1);
+  align_tgt_.assign((size_t)B * c1, -1);
+  align_len_.assign(len, len + B);
+  for (int b = 0; b < B; ++b)
+    for (int p = 0; p < len[b]; ++p) align_tgt_[(size_t)b * c1 + p] = (int32_t)ids[(size_t)b * cap + p];
+  align_B_ = B;
+  align_cap_ = c1;
 }
 
 void Engine::set_topk(int k) {
@@ -1878,7 +1908,7 @@ void Engine::queue_decode_results(int B, int L) {
   const float* sc = (const float*)ws_score_.p;
   last_.scores.resize((size_t)B * L);
   PF_HIP(hipMemcpyAsync(last_.scores.data(), sc, (size_t)B * L * 4, hipMemcpyDeviceToHost, stream_));
-  if (decode_flags_ & (PF_DECODE_CTC | PF_DECODE_CTC_BEAM)) {
+  if (decode_flags_ & (PF_DECODE_CTC | PF_DECODE_CTC_BEAM | PF_DECODE_ALIGN)) {
     if ((int)len.size() != B) len.assign(B, L);
     for (int b = 0; b < B; ++b) len[b] = std::min(std::max(len[b], 0), L);
   }
@@ -1921,6 +1951,57 @@ void Engine::queue_decode_results(int B, int L) {
       PF_HIP(hipMemcpyAsync(last_.beam.data(), ws_beam_.p, bwords * 8, hipMemcpyDeviceToHost, stream_));
     }
   }
+  if (decode_flags_ & PF_DECODE_ALIGN) {
+    // jobs per utterance: the caller's target (when set for this forward), then the hypotheses the search above left in ws_beam_
+    const bool tg = align_B_ == B;
+    const int Nb = (decode_flags_ & PF_DECODE_CTC_BEAM) ? last_.beam_n : 0, b_cap = last_.beam_cap;
+    const int H = (tg ? 1 : 0) + Nb;
+    align_tgt_q_.clear(); align_len_q_.clear();
+    align_tgt_q_.swap(align_tgt_);                  // consumed, like the lengths
+    align_len_q_.swap(align_len_);
+    const int c_cap = align_cap_;
+    align_B_ = 0;
+    if (H > 0) {
+      const int cap = std::max(1, std::max(tg ? c_cap : 0, Nb ? std::min(L, (int)PF_ALIGN_MAX_TOKENS) : 0));
+      const size_t jobs = (size_t)B * H, awords = HostBatchOut::align_words(B, H, cap);
+      const size_t bp_stride = ctc_align_bp_words(L, cap);
+      const size_t tail4 = jobs * cap + (size_t)B + (tg ? (size_t)B * c_cap + (size_t)B : 0) + jobs * bp_stride;
+      ensure(ws_align_, awords * 8 + tail4 * 4);
+      last_.align.resize(awords);
+      last_.align_h = H;
+      last_.align_cap = cap;
+      double* ll_o = (double*)ws_align_.p;
+      float* ps_o = (float*)(ll_o + jobs);
+      int32_t* ok_o = (int32_t*)(ps_o + jobs);
+      int32_t* tlen_d = ok_o + jobs;
+      int32_t* first_o = tlen_d + jobs;
+      int32_t* last_o = first_o + jobs * cap;
+      float* tok_o = (float*)(last_o + jobs * cap);
+      int32_t* tgt_d = (int32_t*)((char*)ws_align_.p + awords * 8);
+      int32_t* len_d = tgt_d + jobs * cap;
+      int32_t* ctgt_d = len_d + B;
+      int32_t* clen_d = ctgt_d + (tg ? (size_t)B * c_cap : 0);
+      uint32_t* bp_d = (uint32_t*)(clen_d + (tg ? B : 0));
+      PF_HIP(hipMemcpyAsync(len_d, len.data(), (size_t)B * 4, hipMemcpyHostToDevice, stream_));
+      if (tg) {
+        PF_HIP(hipMemcpyAsync(ctgt_d, align_tgt_q_.data(), (size_t)B * c_cap * 4, hipMemcpyHostToDevice, stream_));
+        PF_HIP(hipMemcpyAsync(clen_d, align_len_q_.data(), (size_t)B * 4, hipMemcpyHostToDevice, stream_));
+      }
+      const int32_t* bids_d = nullptr, *blen_d = nullptr, *bnh_d = nullptr;
+      if (Nb) {
+        bids_d = (const int32_t*)((const double*)ws_beam_.p + (size_t)B * Nb);
+        blen_d = bids_d + (size_t)B * Nb * b_cap;
+        bnh_d = blen_d + (size_t)B * Nb;
+      }
+      prof_begin("ctc_align", 0);
+      launch_ctc_align_jobs(stream_, tg ? ctgt_d : nullptr, tg ? clen_d : nullptr, c_cap, bids_d, blen_d, bnh_d, Nb, b_cap, B, H, cap,
+                            tgt_d, tlen_d);
+      launch_ctc_align(stream_, logits_, logits_ld_, last_.V, tgt_d, tlen_d, len_d, B, L, H, cap, bp_d, (int64_t)bp_stride, ps_o, ll_o,
+                       ok_o, first_o, last_o, tok_o);
+      prof_end("ctc_align");
+      PF_HIP(hipMemcpyAsync(last_.align.data(), ws_align_.p, awords * 8, hipMemcpyDeviceToHost, stream_));
+    }
+  }
   if (!(decode_flags_ & PF_DECODE_CTC)) return;
   const int cap = L;
   const size_t words = HostBatchOut::ctc_words(B, cap);
@@ -1948,6 +2029,12 @@ void Engine::forward_device(const float* speech_dev, int B, int T, bool want_log
   last_.scores.clear(); last_.ctc.clear(); last_.ctc_cap = 0;
   last_.topk.clear(); last_.topk_k = 0;
   last_.beam.clear(); last_.beam_n = 0; last_.beam_cap = 0;
+  last_.align.clear(); last_.align_h = 0; last_.align_cap = 0;
+  if (align_B_ != 0 && align_B_ != B) {             // before anything is launched; the targets are dropped
+    const int want = align_B_;
+    align_B_ = 0; align_tgt_.clear(); align_len_.clear();
+    PF_CHECK(false, PF_ERR_INVALID_ARG, "forward: align targets were set for a batch of " + std::to_string(want) + ", not " + std::to_string(B));
+  }
   if (fp32_mode_) { forward_fp32(speech_dev, B, T, want_logits); return; }
   if (int8_mode_) { forward_int8(speech_dev, B, T, want_logits); return; }
   encoder(speech_dev, B, T);
@@ -2130,6 +2217,35 @@ void Engine::fetch_ctc_beam(int64_t* ids, int32_t* len, double* score, int32_t c
     const int k = std::min(cap, r.beam_cap);
     for (int p = 0; p < k; ++p) dst[p] = src[p];
     std::fill(dst + k, dst + cap, (int64_t)-1);
+  }
+}
+
+void Engine::fetch_align(float* path_score, double* loglik, int32_t* ok, int32_t* len, int32_t* first, int32_t* last, float* tok_score,
+                         int32_t cap, int32_t* H_out, int32_t* len_max) {
+  PF_HIP(hipStreamSynchronize(stream_));
+  check_async_errors();
+  auto it = t_slots_find(uid_);
+  const HostBatchOut& r = it ? *it : last_;
+  PF_CHECK(r.decode_flags & PF_DECODE_ALIGN, PF_ERR_INVALID_ARG, "fetch_align: PF_DECODE_ALIGN was not set for the last forward");
+  const int B = r.B, H = r.align.empty() ? 0 : r.align_h;
+  const size_t jobs = (size_t)B * H;
+  int mx = 0;
+  for (size_t x = 0; x < jobs; ++x) mx = std::max(mx, r.align_len()[x]);
+  if (H_out) *H_out = H;
+  if (len_max) *len_max = mx;
+  if (jobs == 0) return;
+  if (path_score) std::memcpy(path_score, r.align_path(), jobs * 4);
+  if (loglik) std::memcpy(loglik, r.align_loglik(), jobs * 8);
+  if (ok) std::memcpy(ok, r.align_ok(), jobs * 4);
+  if (len) std::memcpy(len, r.align_len(), jobs * 4);
+  if (!first && !last && !tok_score) return;
+  PF_CHECK(cap >= mx, PF_ERR_CAPACITY, "align capacity " + std::to_string(cap) + " < len_max = " + std::to_string(mx));
+  const size_t k = (size_t)std::min(cap, r.align_cap);
+  for (size_t x = 0; x < jobs; ++x) {
+    const size_t src = x * r.align_cap, dst = x * cap;
+    if (first) { std::memcpy(first + dst, r.align_first() + src, k * 4); std::fill(first + dst + k, first + dst + cap, -1); }
+    if (last) { std::memcpy(last + dst, r.align_last() + src, k * 4); std::fill(last + dst + k, last + dst + cap, -1); }
+    if (tok_score) { std::memcpy(tok_score + dst, r.align_tok() + src, k * 4); std::fill(tok_score + dst + k, tok_score + dst + cap, 0.f); }
   }
 }
 

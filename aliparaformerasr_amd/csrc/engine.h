@@ -178,6 +178,13 @@ class Engine {
   void fetch_ctc_beam(int64_t* ids, int32_t* len, double* score, int32_t cap, int32_t* n_hyp, int32_t* len_max, int32_t* N_out);
   void op_ctc_beam(const float* blank_lp, const int64_t* ids, const float* val, const int32_t* n, const int32_t* lens, int B, int T,
                    int K, int blank, int W, int N, int64_t* out_ids, int32_t* out_len, double* out_score, int cap, int32_t* n_hyp);
+  // ALIGN (SenseVoice; implies SCORES): behind the other decode launches one kernel (k_ctcalign.hip) aligns the caller's
+  // targets of this forward (set_align_targets; consumed) and, with CTC_BEAM, the beam's hypotheses to the log-prob rows
+  void set_align_targets(const int64_t* ids, const int32_t* len, int B, int cap);
+  void fetch_align(float* path_score, double* loglik, int32_t* ok, int32_t* len, int32_t* first, int32_t* last, float* tok_score,
+                   int32_t cap, int32_t* H_out, int32_t* len_max);
+  void op_ctc_align(const float* lp, int B, int T, int V, int ld, const int32_t* tgt, const int32_t* tlen, const int32_t* lens, int H,
+                    int cap, float* path_score, double* loglik, int32_t* ok, int32_t* first, int32_t* last, float* tok_score);
   void op_pcm_convert(const void* data, int64_t n_values, const pf_pcm_desc& desc, float* out, int64_t cap, int64_t* n_out);
   void op_ctc_collapse(const int64_t* ids, const float* scores, const int32_t* lens, int B, int T, int blank, int64_t* ids_out,
                        int32_t* first_out, int32_t* last_out, float* score_out, int cap, int32_t* n_out);
@@ -442,7 +449,12 @@ class Engine {
   // the arg-max form of a pipeline head: the top-k kernel reads the log-probs the arg-max leaves in place
   int beam_w_ = 16, beam_n_ = 16;    // W / N of PF_DECODE_CTC_BEAM
   DevBuf ws_beam_;                   // the beam result block (HostBatchOut::beam) | len [B] | prefix nodes; allocated with the flag only
-  int argmax_mode(bool want_logits) const { return (want_logits || (decode_flags_ & PF_DECODE_TOPK)) ? 2 : 1; }
+  // PF_DECODE_ALIGN: the targets of the next forward (int32, [B, align_cap_]; align_B_ = 0: none) and those of the forward
+  // being queued (alive until the next forward: the host-to-device copies may read them after the call returns)
+  std::vector<int32_t> align_tgt_, align_len_, align_tgt_q_, align_len_q_;
+  int align_B_ = 0, align_cap_ = 0;
+  DevBuf ws_align_;                  // the result block (HostBatchOut::align) | jobs | len [B] | targets | back-pointers; with the flag only
+  int argmax_mode(bool want_logits) const { return (want_logits || (decode_flags_ & (PF_DECODE_TOPK | PF_DECODE_ALIGN))) ? 2 : 1; }
   void queue_decode_results(int B, int L);   // behind the ids copy: the scores' copy, the collapse and its copy
   uint64_t uid_ = 0;                 // key of this engine in the per-thread result store
   static uint64_t register_uid();

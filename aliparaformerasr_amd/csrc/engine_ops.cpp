@@ -124,6 +124,41 @@ void Engine::op_ctc_beam(const float* blank_lp, const int64_t* ids, const float*
   for (size_t x = 0; x < hyp * cap; ++x) out_ids[x] = h_ids[x];
 }
 
+void Engine::op_ctc_align(const float* lp, int B, int T, int V, int ld, const int32_t* tgt, const int32_t* tlen, const int32_t* lens,
+                          int H, int cap, float* path_score, double* loglik, int32_t* ok, int32_t* first, int32_t* last,
+                          float* tok_score) {
+  PF_HIP(hipSetDevice(device_));
+  if (B == 0 || H == 0) return;
+  const size_t rows = (size_t)B * T, jobs = (size_t)B * H, bp_stride = ctc_align_bp_words(T, cap);
+  // the 8-byte item first, then the 4-byte ones
+  const size_t words4 = jobs * 2 + jobs * cap * 3 + jobs * cap + jobs + (size_t)B + rows * ld + jobs * bp_stride;
+  ensure(ws_tmp_, jobs * 8 + words4 * 4);
+  double* d_ll = (double*)ws_tmp_.p;
+  float* d_ps = (float*)(d_ll + jobs);
+  int32_t* d_ok = (int32_t*)(d_ps + jobs);
+  int32_t* d_first = d_ok + jobs;
+  int32_t* d_last = d_first + jobs * cap;
+  float* d_tok = (float*)(d_last + jobs * cap);
+  int32_t* d_tgt = (int32_t*)(d_tok + jobs * cap);
+  int32_t* d_tlen = d_tgt + jobs * cap;
+  int32_t* d_len = d_tlen + jobs;
+  float* d_lp = (float*)(d_len + B);
+  uint32_t* d_bp = (uint32_t*)(d_lp + rows * ld);
+  if (rows > 0) PF_HIP(hipMemcpyAsync(d_lp, lp, rows * ld * 4, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipMemcpyAsync(d_tgt, tgt, jobs * cap * 4, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipMemcpyAsync(d_tlen, tlen, jobs * 4, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipMemcpyAsync(d_len, lens, (size_t)B * 4, hipMemcpyHostToDevice, stream_));
+  launch_ctc_align(stream_, d_lp, ld, V, d_tgt, d_tlen, d_len, B, T, H, cap, d_bp, (int64_t)bp_stride, d_ps, d_ll, d_ok, d_first, d_last,
+                   d_tok);
+  PF_HIP(hipMemcpyAsync(path_score, d_ps, jobs * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipMemcpyAsync(loglik, d_ll, jobs * 8, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipMemcpyAsync(ok, d_ok, jobs * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipMemcpyAsync(first, d_first, jobs * cap * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipMemcpyAsync(last, d_last, jobs * cap * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipMemcpyAsync(tok_score, d_tok, jobs * cap * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipStreamSynchronize(stream_));
+}
+
 void Engine::op_ctc_collapse(const int64_t* ids, const float* scores, const int32_t* lens, int B, int T, int blank,
                              int64_t* ids_out, int32_t* first_out, int32_t* last_out, float* score_out, int cap, int32_t* n_out) {
   PF_HIP(hipSetDevice(device_));

@@ -172,8 +172,10 @@ void Group::recognize(const float* const* samples, const int64_t* n, int B, cons
   merged_ = HostBatchOut();
   merged_logits_ = want_logits;
   // the gather carries ids / token counts / log-probs only: the per-position alternatives have no merged form here
-  for (auto& e : eng_)
+  for (auto& e : eng_) {
     PF_CHECK(!(e->decode_flags() & PF_DECODE_TOPK), PF_ERR_UNSUPPORTED, "pf_group: PF_DECODE_TOPK is not available for a group forward");
+    PF_CHECK(!(e->decode_flags() & PF_DECODE_ALIGN), PF_ERR_UNSUPPORTED, "pf_group: PF_DECODE_ALIGN is not available for a group forward");
+  }
   if (B == 0) return;
   int Tg = 0;                                         // the reference pads to the BATCH maximum (PadHelper.cs:25)
   for (int b = 0; b < B; ++b) {

@@ -628,4 +628,64 @@ int host_ctc_beam(const float* blank_lp, int64_t blank_stride, const int64_t* id
   return nh;
 }
 
+// ------------------------------------------------------------------ CTC forced alignment ---------------
+int host_ctc_align(const float* lp, int64_t ld, int T, int V, const int64_t* y, int U, float* path_score, double* loglik,
+                   int32_t* first, int32_t* last, float* tok_score) {
+  if (!path_score || !loglik || (U > 0 && (!y || !first || !last || !tok_score)) || (T > 0 && !lp))
+    throw Error(PF_ERR_INVALID_ARG, "ctc_align: null argument");
+  if (T < 0 || U < 0 || V < 1 || ld < V) throw Error(PF_ERR_INVALID_ARG, "ctc_align: bad T / U / V / ld");
+  if (U > PF_ALIGN_MAX_TOKENS) throw Error(PF_ERR_CAPACITY, "ctc_align: a target of " + std::to_string(U) + " tokens > PF_ALIGN_MAX_TOKENS");
+  for (int u = 0; u < U; ++u)
+    if (y[u] < 1 || y[u] >= V) throw Error(PF_ERR_INVALID_ARG, "ctc_align: a target id outside [1, V)");
+  const float kNegF = -INFINITY;
+  for (int u = 0; u < U; ++u) { first[u] = -1; last[u] = -1; tok_score[u] = 0.f; }
+  if (T == 0) {
+    *path_score = U == 0 ? 0.f : kNegF;
+    *loglik = U == 0 ? 0.0 : kNegInf;
+    return U == 0;
+  }
+  const int S = 2 * U + 1, nW = (S + 15) / 16;
+  auto lab = [&](int s) { return (s & 1) ? (int)y[s >> 1] : 0; };
+  std::vector<float> a((size_t)S, kNegF), na((size_t)S);
+  std::vector<double> d((size_t)S, kNegInf), nd((size_t)S);
+  std::vector<uint32_t> bp((size_t)T * nW, 0u);         // 2 bits per cell, 16 states per word, as the kernel packs them
+  a[0] = lp[0]; d[0] = (double)lp[0];
+  if (S > 1) { a[1] = lp[lab(1)]; d[1] = (double)a[1]; }
+  for (int t = 1; t < T; ++t) {
+    const float* row = lp + (size_t)t * ld;
+    for (int s = 0; s < S; ++s) {
+      const bool skip = (s & 1) && s >= 3 && lab(s) != lab(s - 2);
+      float best = a[(size_t)s];
+      uint32_t m = 0;
+      if (s >= 1 && a[(size_t)s - 1] > best) { best = a[(size_t)s - 1]; m = 1; }
+      if (skip && a[(size_t)s - 2] > best) { best = a[(size_t)s - 2]; m = 2; }
+      const float v = row[lab(s)];
+      na[(size_t)s] = best + v;
+      bp[(size_t)t * nW + (s >> 4)] |= m << (2 * (s & 15));
+      double acc = d[(size_t)s];
+      if (s >= 1) acc = beam_lse(acc, d[(size_t)s - 1]);
+      if (skip) acc = beam_lse(acc, d[(size_t)s - 2]);
+      nd[(size_t)s] = acc + (double)v;
+    }
+    a.swap(na);
+    d.swap(nd);
+  }
+  int s = S - 1;
+  if (S > 1 && a[(size_t)S - 2] > a[(size_t)S - 1]) s = S - 2;
+  *path_score = a[(size_t)s];
+  *loglik = S > 1 ? beam_lse(d[(size_t)S - 1], d[(size_t)S - 2]) : d[0];
+  if (!(*path_score > kNegF)) return 0;
+  for (int t = T - 1; t >= 0; --t) {
+    if (s & 1) {
+      const int u = s >> 1;
+      const float v = lp[(size_t)t * ld + y[u]];
+      if (last[u] < 0) { last[u] = t; tok_score[u] = v; }
+      else tok_score[u] = fmaxf(tok_score[u], v);
+      first[u] = t;
+    }
+    s -= (int)((bp[(size_t)t * nW + (s >> 4)] >> (2 * (s & 15))) & 3u);
+  }
+  return 1;
+}
+
 }  // namespace pf

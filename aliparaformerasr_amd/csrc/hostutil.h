@@ -81,6 +81,13 @@ int host_nbest(const float* val, const int32_t* n, int L, int K, int n_free, int
 int host_ctc_beam(const float* blank_lp, int64_t blank_stride, const int64_t* ids, const float* val, const int32_t* n, int T, int K,
                   int blank, int W, int N, int64_t* out_ids, int32_t* out_len, double* out_score, int cap);
 
+// ---- CTC forced alignment of one utterance and one target (paraformer_hip.h "CTC forced alignment"; tests/ctcalign_ref.py) ----
+// The host twin of k_ctcalign.hip: lp [T, ld] log-prob rows (V read per row), y [U] ids in [1, V) (PF_ERR_INVALID_ARG
+// otherwise; U > PF_ALIGN_MAX_TOKENS is PF_ERR_CAPACITY).  *path_score: the float32 Viterbi score, *loglik: the float64 log of
+// the summed alignments; first / last / tok_score [U] (-1 / -1 / 0 when not ok).  Returns ok = path_score > -inf.
+int host_ctc_align(const float* lp, int64_t ld, int T, int V, const int64_t* y, int U, float* path_score, double* loglik,
+                   int32_t* first, int32_t* last, float* tok_score);
+
 // UTF-8 <-> code points
 std::vector<uint32_t> utf8_decode(const std::string& s);
 std::string utf8_encode(uint32_t cp);

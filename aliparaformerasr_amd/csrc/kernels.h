@@ -366,6 +366,23 @@ void launch_topk(hipStream_t s, const float* x, int64_t rows, int V, int ldx, in
 void launch_ctc_beam(hipStream_t s, const float* blank_lp, int64_t blank_stride, const int64_t* ids, const float* val,
                      const int32_t* n, const int32_t* len, int B, int T, int K, int blank, int W, int N, int cap, int32_t* node_par,
                      int32_t* node_tok, int32_t* out_ids, int32_t* out_len, double* out_score, int32_t* n_hyp);
+// ------------------------------------------------------------------ CTC forced alignment -------
+// Per job (b, h) the best CTC alignment of the target tgt[b, h, 0 .. tlen[b, h]) to the log-prob rows lp[(b * T + t) * ld + v],
+// t < min(max(len[b], 0), T), v < V, and the float64 log of the sum over all of its alignments (k_ctcalign.hip; the definition
+// is tests/ctcalign_ref.py).  tlen = -1 skips the job; tlen above cap or PF_ALIGN_MAX_TOKENS and an id outside [0, V) make it
+// not ok.  bp: workspace of B * H * bp_stride words, bp_stride >= ctc_align_bp_words(T, cap).  path_score / loglik / ok [B, H],
+// first / last / tok_score [B, H, cap]: every slot is written (-inf / -inf / 0 and -1 / -1 / 0 for a skipped job).  Nothing at
+// or beyond len[b], V or tlen is read.  B <= 65535.
+size_t ctc_align_bp_words(int T, int cap);
+void launch_ctc_align(hipStream_t s, const float* lp, int64_t ld, int V, const int32_t* tgt, const int32_t* tlen, const int32_t* len,
+                      int B, int T, int H, int cap, uint32_t* bp, int64_t bp_stride, float* path_score, double* loglik, int32_t* ok,
+                      int32_t* first, int32_t* last, float* tok_score);
+// The jobs of a forward, assembled on the device: job 0 from the caller's targets c_tgt [B, c_cap] / c_len [B] (when c_len is
+// given), then N jobs from the beam search's result block (b_ids [B, N, b_cap], b_len [B, N], b_nhyp [B]; hypotheses past
+// b_nhyp[b] get tlen -1).  H = (c_len ? 1 : 0) + N.  tgt [B, H, cap] (-1 past a target), tlen [B, H]: every slot is written.
+void launch_ctc_align_jobs(hipStream_t s, const int32_t* c_tgt, const int32_t* c_len, int c_cap, const int32_t* b_ids,
+                           const int32_t* b_len, const int32_t* b_nhyp, int N, int b_cap, int B, int H, int cap, int32_t* tgt,
+                           int32_t* tlen);
 
 // ---------------------------------------------------------------- PCM intake (k_pcm.hip) ------
 // One utterance of a pcm_to_samples launch: n raw values of `format` (pf_pcm_format) at raw + in_off (bytes, 16-byte aligned)

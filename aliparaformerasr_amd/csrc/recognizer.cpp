@@ -514,8 +514,24 @@ std::shared_ptr<Engine> Recognizer::make_engine() {
 }
 
 void Recognizer::SetDecode(int flags) {
-  set_decode_all(flags | (nbest_n_ > 0 ? PF_DECODE_TOPK : 0) | (beam_on_ ? PF_DECODE_CTC_BEAM : 0), topk_k_);
+  set_decode_all(flags | extra_flags(), topk_k_);
   user_flags_ = flags;
+}
+
+void Recognizer::SetAlign(bool on) {
+  if (!on) {
+    align_on_ = false;
+    set_decode_all(user_flags_ | extra_flags(), topk_k_);
+    return;
+  }
+  if (engine_kind_ != "sensevoicesmall") throw Error(PF_ERR_UNSUPPORTED, "SetAlign: only a SenseVoice model has a CTC head");
+  align_on_ = true;
+  try {
+    set_decode_all(user_flags_ | extra_flags(), topk_k_);
+  } catch (...) {
+    align_on_ = false;
+    throw;
+  }
 }
 
 void Recognizer::SetCtcBeam(int N, int W, int K) {
@@ -523,7 +539,7 @@ void Recognizer::SetCtcBeam(int N, int W, int K) {
     throw Error(PF_ERR_INVALID_ARG, "SetCtcBeam: N is 0 .. 64, W is 0 or N .. 64, K is 0 .. 8");
   if (N == 0) {
     beam_on_ = false;
-    set_decode_all(user_flags_ | (nbest_n_ > 0 ? PF_DECODE_TOPK : 0), topk_k_);
+    set_decode_all(user_flags_ | extra_flags(), topk_k_);
     return;
   }
   if (engine_kind_ != "sensevoicesmall") throw Error(PF_ERR_UNSUPPORTED, "SetCtcBeam: only a SenseVoice model has a CTC head");
@@ -531,7 +547,7 @@ void Recognizer::SetCtcBeam(int N, int W, int K) {
   beam_n_ = N;
   beam_on_ = true;
   try {
-    set_decode_all(user_flags_ | (nbest_n_ > 0 ? PF_DECODE_TOPK : 0) | PF_DECODE_CTC_BEAM, K == 0 ? 4 : K);
+    set_decode_all(user_flags_ | extra_flags(), K == 0 ? 4 : K);
   } catch (...) {
     beam_on_ = false;
     throw;
@@ -541,14 +557,14 @@ void Recognizer::SetCtcBeam(int N, int W, int K) {
 void Recognizer::SetNBest(int N, int K) {
   if (N < 0 || N > PF_NBEST_MAX || K < 0 || K > PF_TOPK_MAX) throw Error(PF_ERR_INVALID_ARG, "SetNBest: N is 0 .. 64, K is 0 .. 8");
   if (N == 0) {
-    set_decode_all((user_flags_ & ~PF_DECODE_TOPK) | (beam_on_ ? PF_DECODE_CTC_BEAM : 0), topk_k_);
+    set_decode_all((user_flags_ & ~PF_DECODE_TOPK) | (extra_flags() & ~PF_DECODE_TOPK), topk_k_);
     user_flags_ = user_flags_ & ~PF_DECODE_TOPK;
     nbest_n_ = 0;
     return;
   }
   // frames of a CTC model are not independent tokens: a sum over frame ranks is no hypothesis score
   if (N > 1 && engine_kind_ == "sensevoicesmall") throw Error(PF_ERR_UNSUPPORTED, "SetNBest: N > 1 needs a paraformer model (SenseVoice offers K alone)");
-  set_decode_all(user_flags_ | PF_DECODE_TOPK | (beam_on_ ? PF_DECODE_CTC_BEAM : 0), K == 0 ? 4 : K);
+  set_decode_all(user_flags_ | PF_DECODE_TOPK | extra_flags(), K == 0 ? 4 : K);
   nbest_n_ = N;
 }
 
@@ -971,6 +987,21 @@ void Recognizer::Forward(const std::vector<Stream*>& streams) {
       e->set_hotwords(pad.data(), (int)hw.size());
     }
     e->drop_thread_result();              // this call's result is read back under the same lease, not from a slot
+    bool any_target = false;
+    if (dflags & PF_DECODE_ALIGN) {
+      // the streams' targets of this batch (SetAlign): a stream without one gets len = -1
+      size_t cap = 1;
+      for (Stream* s : streams) { any_target = any_target || s->has_align; if (s->has_align) cap = std::max(cap, s->AlignIds.size()); }
+      std::vector<int64_t> t_ids((size_t)B * cap, 0);
+      std::vector<int32_t> t_len((size_t)B, -1);
+      for (int b = 0; b < B && any_target; ++b)
+        if (streams[b]->has_align) {
+          t_len[b] = (int32_t)streams[b]->AlignIds.size();
+          std::copy(streams[b]->AlignIds.begin(), streams[b]->AlignIds.end(), t_ids.begin() + (size_t)b * cap);
+        }
+      if (any_target) e->set_align_targets(t_ids.data(), t_len.data(), B, (int)cap);
+      else e->set_align_targets(nullptr, nullptr, 0, 0);
+    }
     if (all_dev) {
       // the batched front-end over the samples where they are (fbank -> LFR + CMVN + PadSequence [+ the SenseVoice query
       // rows]) and the model, one stream of launches: WavFrontend.cs:31-111 + Utils/PadHelper.cs:25 + ModelProj
@@ -1052,11 +1083,28 @@ void Recognizer::Forward(const std::vector<Stream*>& streams) {
       b_ids.resize((size_t)B * Nb * b_cap); b_len.resize((size_t)B * Nb); b_score.resize((size_t)B * Nb);
       e->fetch_ctc_beam(b_ids.data(), b_len.data(), b_score.data(), b_cap, nullptr, nullptr, nullptr);
     }
+    // forced alignments (SetAlign): job 0 is the stream's own target when any stream of the batch has one, then the hypotheses
+    std::vector<float> a_path, a_tok; std::vector<double> a_ll; std::vector<int32_t> a_ok, a_len, a_first, a_last;
+    int Ha = 0, a_cap = 1;
+    if (dflags & PF_DECODE_ALIGN) {
+      int32_t hh = 0, len_max = 0;
+      e->fetch_align(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, &hh, &len_max);
+      Ha = hh;
+      a_cap = std::max(len_max, 1);
+      const size_t jobs = (size_t)B * Ha;
+      a_path.resize(jobs); a_ll.resize(jobs); a_ok.resize(jobs); a_len.resize(jobs);
+      a_first.resize(jobs * a_cap); a_last.resize(jobs * a_cap); a_tok.resize(jobs * a_cap);
+      if (Ha > 0)
+        e->fetch_align(a_path.data(), a_ll.data(), a_ok.data(), a_len.data(), a_first.data(), a_last.data(), a_tok.data(), a_cap, nullptr,
+                       nullptr);
+    }
+    const int a_hc = (Ha > 0 && any_target) ? 1 : 0;
     const int nbest = nbest_n_;
-    const int extras = PF_DECODE_TOPK | PF_DECODE_CTC_BEAM;      // neither changes what Scores holds
+    const int extras = PF_DECODE_TOPK | PF_DECODE_CTC_BEAM | PF_DECODE_ALIGN;      // none changes what Scores holds
     const bool want_scores = (dflags & ~extras) == PF_DECODE_SCORES && (!(dflags & extras) || (user_flags_ & PF_DECODE_SCORES));
     fc.lap(5);
     lease.release();                      // the device work of this call is over: the text stage below needs no engine
+    const int ms_frame = conf_.lfr_n * 10;          // a frame = lfr_n x 10 ms; the four prompt rows carry no audio
     for (int b = 0; b < B; ++b) {
       Stream* s = streams[b];
       s->Tokens.assign(ids.begin() + (size_t)b * out.l_cap, ids.begin() + (size_t)b * out.l_cap + L);   // :187
@@ -1118,7 +1166,26 @@ void Recognizer::Forward(const std::vector<Stream*>& streams) {
         a.score = b_score[x];
         a.ctc = true;
         a.ids.assign(b_ids.begin() + x * b_cap, b_ids.begin() + x * b_cap + b_len[x]);
+        if (Ha >= a_hc + Nb) {
+          const size_t j = (size_t)b * Ha + a_hc + i;
+          a.loglik = a_ll[j];
+          if (a_ok[j] && a_len[j] == b_len[x])
+            for (int k = 0; k < a_len[j]; ++k) {
+              a.ts.push_back(ms_frame * std::max(a_first[j * a_cap + k] - 4, 0));
+              a.ts.push_back(ms_frame * std::max(a_last[j * a_cap + k] + 1 - 4, 0));
+            }
+        }
         s->Alternatives.push_back(std::move(a));
+      }
+      s->AlignTs.clear(); s->AlignTok.clear(); s->AlignPath = 0.f; s->AlignLoglik = 0.0; s->AlignOk = 0; s->AlignN = -1;
+      if (a_hc && a_len[(size_t)b * Ha] >= 0) {
+        const size_t j = (size_t)b * Ha;
+        s->AlignN = a_len[j]; s->AlignOk = a_ok[j]; s->AlignPath = a_path[j]; s->AlignLoglik = a_ll[j];
+        for (int k = 0; k < a_len[j] && a_ok[j]; ++k) {
+          s->AlignTs.push_back(ms_frame * std::max(a_first[j * a_cap + k] - 4, 0));
+          s->AlignTs.push_back(ms_frame * std::max(a_last[j * a_cap + k] + 1 - 4, 0));
+          s->AlignTok.push_back(a_tok[j * a_cap + k]);
+        }
       }
       if (all_dev && sv && s->Tokens.size() <= 2) {
         // quirk Q8 on the device form: the reference has prepended the query rows to Speech IN PLACE, and a stream whose
@@ -1155,8 +1222,12 @@ void Recognizer::GetResults(const std::vector<Stream*>& streams) {
   std::vector<ResultEntity> out;
   for (Stream* s : streams) out.push_back(decode_multi_one(token_table_, s->Tokens, s->Timestamps));
   for (Stream* s : streams)                                   // the n-best list goes through the same DecodeMulti
-    for (Alternative& a : s->Alternatives)                    // (a beam hypothesis has no per-token times: {0, 0} each)
-      a.res = decode_multi_one(token_table_, a.ids, a.ctc ? TsList(a.ids.size(), TsVec{0, 0}) : s->Timestamps);
+    for (Alternative& a : s->Alternatives) {                  // (a beam hypothesis has no per-token times without SetAlign:
+      TsList own(a.ctc ? a.ids.size() : 0, TsVec{0, 0});      //  {0, 0} each; with it, those of its own forced alignment)
+      if (a.ctc && a.ts.size() == 2 * a.ids.size())
+        for (size_t k = 0; k < a.ids.size(); ++k) own[k] = TsVec{a.ts[2 * k], a.ts[2 * k + 1]};
+      a.res = decode_multi_one(token_table_, a.ids, a.ctc ? own : s->Timestamps);
+    }
   fc.lap(7);
   fwd_report();
   {

@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <deque>
 #include <functional>
@@ -79,6 +80,10 @@ struct Alternative {
   std::vector<int64_t> ids;
   double score = 0;
   bool ctc = false;            // a labeling of the CTC beam search (SetCtcBeam): its own length, score = log of the summed alignments
+  // with SetAlign beside SetCtcBeam: the labeling's own forced alignment — [begin, end] ms per id (flat, 2 per id; empty without
+  // it or when the alignment is not ok) and the log of the sum over ALL of its alignments (NaN without it)
+  std::vector<int32_t> ts;
+  double loglik = std::nan("");
   ResultEntity res;
 };
 // time_stamp_lfr6_onnx (OfflineRecognizer.cs:200-302); throws PF_ERR_RECOGNITION where the C#
@@ -144,6 +149,12 @@ class Stream {
   std::vector<float> AltVal;
   int AltK = 0;
   std::vector<Alternative> Alternatives;
+  // CTC forced alignment (Recognizer::SetAlign).  AlignIds: the stream's target (token ids), kept until cleared.  Of the last
+  // GetResults: [begin, end] ms per target id (flat), the token scores, the Viterbi score, the log-likelihood, ok; AlignN = -1
+  // when that GetResults aligned nothing for this stream
+  std::vector<int64_t> AlignIds; bool has_align = false;
+  std::vector<int32_t> AlignTs; std::vector<float> AlignTok;
+  float AlignPath = 0.f; double AlignLoglik = 0.0; int AlignOk = 0, AlignN = -1;
   void RemoveChunk();                                         // OfflineStream.cs:69-79
   bool disposed = false;
   std::shared_ptr<Recognizer> owner;
@@ -172,6 +183,9 @@ class Recognizer : public std::enable_shared_from_this<Recognizer> {
   // SenseVoice only (paraformer_hip.h "CTC beam search"): N = 0 off; N >= 1: PF_DECODE_CTC_BEAM with beam width W (0 = max(16, N))
   // and top-k K (0 = 4) on every engine — Alternatives holds up to N labelings by descending CTC score
   void SetCtcBeam(int N, int W, int K);
+  // SenseVoice only (paraformer_hip.h "CTC forced alignment"): PF_DECODE_ALIGN on every engine — a stream's target (AlignIds)
+  // is aligned to its audio, and with SetCtcBeam every Alternative gets its own times and log-likelihood
+  void SetAlign(bool on);
   bool disposed() const { return disposed_.load(); }
   // engine 0 (nullptr once disposed): what pf_recognizer_engine hands out; callers lock engine->mutex() themselves
   std::shared_ptr<Engine> engine() { std::lock_guard<std::mutex> lk(mu_); return engines_.empty() ? nullptr : engines_[0]; }
@@ -272,6 +286,8 @@ class Recognizer : public std::enable_shared_from_this<Recognizer> {
   std::atomic<int> topk_k_{4};
   std::atomic<int> beam_w_{16}, beam_n_{16};
   std::atomic<bool> beam_on_{false};
+  std::atomic<bool> align_on_{false};
+  int extra_flags() const { return (nbest_n_ > 0 ? PF_DECODE_TOPK : 0) | (beam_on_ ? PF_DECODE_CTC_BEAM : 0) | (align_on_ ? PF_DECODE_ALIGN : 0); }
   void set_decode_all(int flags, int k);
   friend class Stream;
 };

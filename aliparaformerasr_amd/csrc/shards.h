@@ -60,6 +60,18 @@ struct HostBatchOut { // results of a forward, host side
   const int32_t* beam_ids() const { return (const int32_t*)(beam.data() + (size_t)B * beam_n); }
   const int32_t* beam_len() const { return beam_ids() + (size_t)B * beam_n * beam_cap; }
   const int32_t* beam_nhyp() const { return beam_len() + (size_t)B * beam_n; }
+  // CTC forced alignment as the kernel leaves it, one block (the float64 item first, for its alignment):
+  // loglik [B, H] float64 | path_score [B, H] fp32 | ok [B, H] | len [B, H] | first [B, H, cap] | last | tok_score fp32
+  std::vector<int64_t> align;
+  int align_h = 0, align_cap = 0;
+  static size_t align_words(int B, int H, int cap) { return (size_t)B * H + ((size_t)B * H * 12 + (size_t)B * H * cap * 12 + 7) / 8; }
+  const double* align_loglik() const { return (const double*)align.data(); }
+  const float* align_path() const { return (const float*)(align.data() + (size_t)B * align_h); }
+  const int32_t* align_ok() const { return (const int32_t*)(align_path() + (size_t)B * align_h); }
+  const int32_t* align_len() const { return align_ok() + (size_t)B * align_h; }
+  const int32_t* align_first() const { return align_len() + (size_t)B * align_h; }
+  const int32_t* align_last() const { return align_first() + (size_t)B * align_h * align_cap; }
+  const float* align_tok() const { return (const float*)(align_last() + (size_t)B * align_h * align_cap); }
 };
 
 // rendezvous of the G worker threads with a max-reduction; abort() releases every waiter with an Error

@@ -99,8 +99,37 @@ def host_ctc_beam(blank_lp, ids, val, n, W, n_best=None, blank=0, cap=None, blan
     return CtcBeamResult(nh, oi, ol, sc)
 
 
+class AlignResult:
+    """CTC forced alignments (PF_DECODE_ALIGN), H jobs per utterance: path_score [B, H] float32 (the Viterbi score), loglik
+    [B, H] float64 (the log of the summed alignments), ok [B, H], len [B, H] (the target's length; -1: a skipped job), first /
+    last [B, H, cap] int32 frame indices (-1 past len and when not ok), tok_score [B, H, cap] float32."""
+
+    def __init__(self, path_score, loglik, ok, len_, first, last, tok_score):
+        self.path_score, self.loglik, self.ok, self.len = path_score, loglik, ok, len_
+        self.first, self.last, self.tok_score = first, last, tok_score
+        self.H = ok.shape[-1]
+
+
+def host_ctc_align(lp, y, V=None) -> AlignResult:
+    """The alignment of ONE utterance and ONE target in host code (pf_host_ctc_align, the twin of the device kernel):
+    lp [T, ld] log-prob rows (V <= ld entries read per row), y [U] ids in [1, V) -> AlignResult with B = H = 1."""
+    x = _f32(lp)
+    T, ld = x.shape
+    yy = np.ascontiguousarray(y, dtype=np.int64).reshape(-1)
+    U = yy.shape[0]
+    ps, ll, ok = C.c_float(), C.c_double(), C.c_int32()
+    cap = max(U, 1)
+    first, last, tok = np.zeros((1, 1, cap), np.int32), np.zeros((1, 1, cap), np.int32), np.zeros((1, 1, cap), np.float32)
+    N.check(N.load().pf_host_ctc_align(_fp(x), ld, T, int(ld if V is None else V), _i64p(yy), U, ps, ll, ok, _i32p(first), _i32p(last),
+                                       _fp(tok)))
+    return AlignResult(np.array([[ps.value]], np.float32), np.array([[ll.value]], np.float64), np.array([[ok.value]], np.int32),
+                       np.array([[U]], np.int32), first[:, :, :U], last[:, :, :U], tok[:, :, :U])
+
+
 class BatchResult:
-    def __init__(self, token_ids, token_num, L, V, logits=None, cif_peak=None, scores=None, ctc=None, topk=None, beam=None):
+    def __init__(self, token_ids, token_num, L, V, logits=None, cif_peak=None, scores=None, ctc=None, topk=None, beam=None,
+                 align=None):
+        self.align = align              # AlignResult (Engine.set_decode(PF_DECODE_ALIGN) with targets or CTC_BEAM) or None
         self.token_ids = token_ids      # [B, L] int64
         self.token_num = token_num      # [B] int32
         self.L = L
@@ -199,6 +228,18 @@ def _fetch_ctc_beam(lib, h, B, n_best):
     return CtcBeamResult(nh, ids, ln, sc)
 
 
+def _fetch_align(lib, h, B):
+    hh, mx = C.c_int32(), C.c_int32()
+    N.check(lib.pf_fetch_align(h, None, None, None, None, None, None, None, 0, hh, mx))
+    H, cap = hh.value, max(mx.value, 1)
+    ps, ll = np.zeros((B, H), np.float32), np.zeros((B, H), np.float64)
+    ok, ln = np.zeros((B, H), np.int32), np.zeros((B, H), np.int32)
+    first, last, tok = np.zeros((B, H, cap), np.int32), np.zeros((B, H, cap), np.int32), np.zeros((B, H, cap), np.float32)
+    if H:
+        N.check(lib.pf_fetch_align(h, _fp(ps), _dp(ll), _i32p(ok), _i32p(ln), _i32p(first), _i32p(last), _fp(tok), cap, None, None))
+    return AlignResult(ps, ll, ok, ln, first, last, tok)
+
+
 def _collect_result(lib, fetch_fn, call, B, want_logits, decode=None):
     """The learn-L-then-fetch protocol shared by pf_engine and pf_group handles.  decode = (engine handle, flags):
     also the decoding extras of an engine with Engine.set_decode flags."""
@@ -230,8 +271,11 @@ def _collect_result(lib, fetch_fn, call, B, want_logits, decode=None):
     beam = None
     if decode is not None and decode[1] & N.PF_DECODE_CTC_BEAM:
         beam = _fetch_ctc_beam(lib, decode[0], B, decode[2])
+    align = None
+    if decode is not None and decode[1] & N.PF_DECODE_ALIGN:
+        align = _fetch_align(lib, decode[0], B)
     N.check(fetch_fn(C.byref(out)))
-    return BatchResult(ids[:, :L].copy(), tn, L, V, logits, peak, scores, ctc, topk, beam)
+    return BatchResult(ids[:, :L].copy(), tn, L, V, logits, peak, scores, ctc, topk, beam, align)
 
 
 class Engine:
@@ -298,7 +342,38 @@ class Engine:
         behaviour): BatchResult.scores, and for a SenseVoice model BatchResult.ctc."""
         N.check(self._lib.pf_engine_set_decode(self._h, int(flags)))
         f = int(flags) | (N.PF_DECODE_TOPK if int(flags) & N.PF_DECODE_CTC_BEAM else 0)
-        self._decode = f | (N.PF_DECODE_SCORES if f & (N.PF_DECODE_CTC | N.PF_DECODE_TOPK) else 0)
+        self._decode = f | (N.PF_DECODE_SCORES if f & (N.PF_DECODE_CTC | N.PF_DECODE_TOPK | N.PF_DECODE_ALIGN) else 0)
+
+    def set_align_targets(self, targets):
+        """Targets of the NEXT forward under PF_DECODE_ALIGN (consumed by it): one sequence of token ids per utterance, None
+        for "no target for this row"; an empty list clears pending targets.  Ids, not text: the tokenizer is the caller's."""
+        B = len(targets)
+        ln = np.array([-1 if t is None else len(t) for t in targets], np.int32).reshape(B)
+        cap = max(int(ln.max()) if B else 0, 1)
+        ids = np.zeros((B, cap), np.int64)
+        for b, t in enumerate(targets):
+            if t is not None:
+                ids[b, : len(t)] = np.asarray(t, dtype=np.int64)
+        N.check(self._lib.pf_engine_set_align_targets(self._h, _i64p(ids), _i32p(ln), B, cap))
+
+    host_ctc_align = staticmethod(host_ctc_align)
+
+    def op_ctc_align(self, lp, tgt, tlen, lens, V=None, out=None) -> AlignResult:
+        """The pipeline's alignment kernel on caller data: lp [B, T, ld] (V <= ld entries read per row), tgt [B, H, cap] int32,
+        tlen [B, H] (-1 skips a job), lens [B].  out = (path_score, loglik, ok, first, last, tok_score): write into these."""
+        x = _f32(lp)
+        B, T, ld = x.shape
+        y = np.ascontiguousarray(tgt, dtype=np.int32)
+        tl = np.ascontiguousarray(tlen, dtype=np.int32)
+        ln = np.ascontiguousarray(lens, dtype=np.int32)
+        _, H, cap = y.shape
+        if out is None:
+            out = (np.zeros((B, H), np.float32), np.zeros((B, H), np.float64), np.zeros((B, H), np.int32),
+                   np.zeros((B, H, cap), np.int32), np.zeros((B, H, cap), np.int32), np.zeros((B, H, cap), np.float32))
+        ps, ll, ok, first, last, tok = out
+        N.check(self._lib.pf_op_ctc_align(self._h, _fp(x), B, T, int(ld if V is None else V), ld, _i32p(y), _i32p(tl), _i32p(ln), H,
+                                          cap, _fp(ps), _dp(ll), _i32p(ok), _i32p(first), _i32p(last), _fp(tok)))
+        return AlignResult(ps, ll, ok, tl.copy(), first, last, tok)
 
     def set_ctc_beam(self, W: int = 16, n_best: int = 16):
         """Beam width W and list length n_best (1 <= n_best <= W <= 64, default 16 / 16) of PF_DECODE_CTC_BEAM for the

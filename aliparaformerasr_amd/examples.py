@@ -1,7 +1,7 @@
 """Command-line harness mirroring AliParaformerAsr.Examples (`-type offline` and `-type online`).
 
     python -m aliparaformerasr_amd.examples -type offline -method batch -base <dir> -model <name> \
-        [-accuracy int8] [-threads 2] [-decode ctc|frames] [-intake host|device] [-nbest N [-topk K] [-beam W]] -files a.wav b.wav
+        [-accuracy int8] [-threads 2] [-decode ctc|frames] [-intake host|device] [-nbest N [-topk K] [-beam W]] [-align FILE|beam] -files a.wav b.wav
     python -m aliparaformerasr_amd.examples -type online -method one -base <dir> -model <name> -files a.wav
 
 Mirrors (file:line in /root/reference/AliParaformerAsr.Examples):
@@ -27,7 +27,13 @@ OfflineStream.AddPcm raw: decode, down-mix and resample run on the device and gi
 `-nbest N [-topk K]` (offline, paraformer models; OfflineRecognizer.SetNBest) prints under each result line the N best
 hypotheses, one `nbest[i] score:<sum of log-probs> text:<text>` line each, best first; line 0 is the result itself.
 `-nbest N -beam W` (offline, SenseVoice models; OfflineRecognizer.SetCtcBeam) prints the N best labelings of a CTC prefix
-beam search of width W in the same form; the score is the log of the summed alignments."""
+beam search of width W in the same form; the score is the log of the summed alignments.
+`-align FILE` (offline, SenseVoice models; OfflineRecognizer.SetAlign) aligns a known text to each input file: FILE holds one
+line of space-separated token ids per file of `-files`, in their order (an empty line: no target; ids, not text — the
+tokenizer is not part of this package), and under each result line goes
+`align ok:<0|1> path:<best alignment's log-prob> loglik:<log P(ids | audio)> pairs:[begin,end],...` in milliseconds.
+`-align beam` (with `-nbest N -beam W`) aligns the beam search's labelings instead: under each `nbest[i]` line goes
+`align[i] loglik:<...> pairs:[begin,end],...`."""
 from __future__ import annotations
 
 import ctypes as C
@@ -128,13 +134,41 @@ def _result_line(r) -> str:
     return '{"text": "%s","tokens":[%s],"timestamps":[%s]}' % (r.Text, toks, ts)
 
 
-def _nbest_lines(stream) -> list:
-    return ['nbest[%d] score:%.6f text:%s' % (i, a.Score, a.Text) for i, a in enumerate(stream.Alternatives)]
+def _pairs(ts) -> str:
+    return ",".join("[%d,%d]" % (t[0], t[-1]) for t in ts)
+
+
+def _nbest_lines(stream, align=False) -> list:
+    out = []
+    for i, a in enumerate(stream.Alternatives):
+        out.append('nbest[%d] score:%.6f text:%s' % (i, a.Score, a.Text))
+        if align and a.LogLik is not None:
+            out.append('align[%d] loglik:%.6f pairs:%s' % (i, a.LogLik, _pairs(a.Timestamps)))
+    return out
+
+
+def _align_lines(stream) -> list:
+    a = stream.Alignment
+    if a is None:
+        return []
+    return ['align ok:%d path:%.6f loglik:%.6f pairs:%s' % (a.Ok, a.PathScore, a.LogLik, _pairs(a.Timestamps))]
+
+
+def read_align_file(path: str) -> list:
+    """one line of space-separated token ids per input file; an empty line means no target for that file"""
+    out = []
+    with open(path, encoding="utf-8") as f:
+        for ln in f.read().splitlines():
+            try:
+                out.append([int(x) for x in ln.split()] if ln.strip() else None)
+            except ValueError:
+                raise ValueError("The align file holds token ids (integers), one line per input file: %r" % ln)
+    return out
 
 
 def offline_recognizer(method="one", model="paraformer-seaco-large-zh-timestamp-onnx-offline", accuracy="int8",
                        threads=2, files=None, base=None, out=sys.stdout, decode="frames", intake="host", nbest=0, topk=4,
-                       beam=0):
+                       beam=0, align=None):
     from .offline_recognizer import OfflineRecognizer
     base = base or os.getcwd()
     sel = select_model_files(base, model, accuracy)
@@ -149,6 +183,11 @@ def offline_recognizer(method="one", model="paraformer-seaco-large-zh-timestamp-
         rec.SetCtcBeam(nbest, beam, topk)
     elif nbest:
         rec.SetNBest(nbest, topk)
+    targets = None
+    if align:
+        rec.SetAlign(True)
+        if align != "beam":
+            targets = dict(zip(files or [], read_align_file(align)))
     print("init_models_elapsed_milliseconds:%s" % ((time.perf_counter() - t0) * 1e3), file=out)
     if not files:
         files = []
@@ -177,28 +216,35 @@ def offline_recognizer(method="one", model="paraformer-seaco-large-zh-timestamp-
             st.AddPcm(s[0], s[1], s[2], s[3])
         else:
             st.AddSamples(s)
+
+    def extra_lines(st):
+        return (_nbest_lines(st, align == "beam") if nbest else []) + (_align_lines(st) if targets is not None else [])
     print("Recognition results:\r\n", file=out)
     try:
         if method == "one":
             for p, s in zip(paths, samples):
                 st = rec.CreateOfflineStream()
                 add(st, s)
+                if targets is not None and targets.get(p) is not None:
+                    st.SetAlignIds(targets[p])
                 r = rec.GetResult(st)
                 results.append(r)
                 print(p, file=out); print(_result_line(r), file=out)
-                for ln in _nbest_lines(st) if nbest else ():
+                for ln in extra_lines(st):
                     print(ln, file=out)
                 print("", file=out)
         elif method == "batch":
             streams = []
-            for s in samples:
+            for p, s in zip(paths, samples):
                 st = rec.CreateOfflineStream()
                 add(st, s)
+                if targets is not None and targets.get(p) is not None:
+                    st.SetAlignIds(targets[p])
                 streams.append(st)
             results = rec.GetResults(streams)
             for p, r, st in zip(paths, results, streams):
                 print(p, file=out); print(_result_line(r), file=out)
-                for ln in _nbest_lines(st) if nbest else ():
+                for ln in extra_lines(st):
                     print(ln, file=out)
                 print("", file=out)
     except Exception as ex:          # the reference prints the message and carries on to the timing lines
@@ -341,6 +387,11 @@ def parse_args(argv, env=None):
             if not lo <= v <= hi:
                 raise ValueError("The %s value must be an integer from %d to %d" % (a[1:], lo, hi))
             cfg[a[1:]] = v
+        elif a == "-align":
+            i += 1
+            if i >= len(argv) or argv[i].startswith("-"):
+                raise ValueError("-align takes a file of token ids, or `beam`")
+            cfg["align"] = argv[i]
         elif a == "-threads":
             try:
                 i += 1
@@ -366,6 +417,10 @@ def parse_args(argv, env=None):
         raise ValueError("The beam value must not be smaller than the nbest value")
     if "nbest" in cfg and cfg["recognizerType"] != "offline":
         raise ValueError("-nbest is an offline option")
+    if "align" in cfg and cfg["recognizerType"] != "offline":
+        raise ValueError("-align is an offline option")
+    if cfg.get("align") == "beam" and "beam" not in cfg:
+        raise ValueError("-align beam needs -nbest N -beam W")
     return cfg
 
 
@@ -383,7 +438,7 @@ def main(argv=None):
     elif cfg["recognizerType"] == "offline":
         offline_recognizer(cfg["methodType"], cfg["modelName"], cfg["modelAccuracy"], cfg["threads"], cfg["files"],
                            cfg["modelBasePath"] or None, decode=cfg.get("decode", "frames"), intake=cfg.get("intake", "host"),
-                           nbest=cfg.get("nbest", 0), topk=cfg.get("topk", 4), beam=cfg.get("beam", 0))
+                           nbest=cfg.get("nbest", 0), topk=cfg.get("topk", 4), beam=cfg.get("beam", 0), align=cfg.get("align"))
     else:
         print("the recognizer type must be online or offline")
         return 2

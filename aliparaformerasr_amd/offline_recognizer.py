@@ -72,6 +72,21 @@ class Alternative:
     Score: float = 0.0
     Text: str = ""
     Tokens: List[str] = field(default_factory=list)
+    # OfflineRecognizer.SetAlign beside SetCtcBeam: one [begin, end] pair in ms per id from the labeling's own forced alignment
+    # (empty without), and the log of the sum over ALL of its alignments (None without)
+    Timestamps: List[List[int]] = field(default_factory=list)
+    LogLik: Optional[float] = None
+
+
+@dataclass
+class Alignment:
+    """OfflineStream.Alignment: the forced alignment of the stream's target ids (OfflineStream.SetAlignIds) to its audio.
+    Ok = 0: the target does not fit the audio (more ids than frames); Timestamps / Scores are then empty."""
+    Ok: int = 0
+    PathScore: float = 0.0                 # float32 log-prob of the best alignment
+    LogLik: float = 0.0                    # float64 log P(target | audio): the sum over all alignments
+    Timestamps: List[List[int]] = field(default_factory=list)   # [begin, end] ms per id
+    Scores: List[float] = field(default_factory=list)           # per id: the largest log-prob of its run
 
 
 @dataclass
@@ -209,9 +224,34 @@ class OfflineStream:
                 t = C.c_char_p()
                 _ck(self._lib.pf_stream_alternative_token(self._h, i, j, C.byref(t)))
                 toks.append((t.value or b"").decode("utf-8"))
+            pt, nts, ll = C.POINTER(C.c_int32)(), C.c_int32(), C.c_double()
+            _ck(self._lib.pf_stream_alternative_timestamps(self._h, i, C.byref(pt), nts, C.byref(ll)))
             out.append(Alternative(Ids=[p[m] for m in range(k.value)], Score=sc.value,
-                                   Text=(txt.value or b"").decode("utf-8"), Tokens=toks))
+                                   Text=(txt.value or b"").decode("utf-8"), Tokens=toks,
+                                   Timestamps=[[pt[2 * j], pt[2 * j + 1]] for j in range(nts.value)],
+                                   LogLik=None if ll.value != ll.value else ll.value))
         return out
+
+    def SetAlignIds(self, ids: Optional[List[int]]) -> None:
+        """The stream's target for forced alignment (OfflineRecognizer.SetAlign): token IDS — text to ids needs the model's
+        tokenizer and is the caller's.  Kept until cleared with None."""
+        if ids is None:
+            _ck(self._lib.pf_stream_set_align_ids(self._h, None, -1))
+            return
+        a = (C.c_int64 * max(len(ids), 1))(*[int(v) for v in ids])
+        _ck(self._lib.pf_stream_set_align_ids(self._h, a, len(ids)))
+
+    @property
+    def Alignment(self) -> Optional["Alignment"]:
+        """The alignment of the target of the last GetResults (None when nothing was aligned for this stream)."""
+        pt, ps = C.POINTER(C.c_int32)(), C.POINTER(C.c_float)()
+        n, ok, path, ll = C.c_int32(), C.c_int32(), C.c_float(), C.c_double()
+        _ck(self._lib.pf_stream_alignment(self._h, C.byref(pt), C.byref(ps), n, path, C.byref(ll), ok))
+        if n.value < 0:
+            return None
+        k = n.value if ok.value else 0
+        return Alignment(Ok=ok.value, PathScore=path.value, LogLik=ll.value,
+                         Timestamps=[[pt[2 * j], pt[2 * j + 1]] for j in range(k)], Scores=[ps[j] for j in range(k)])
 
     @property
     def Timestamps(self) -> List[List[int]]:
@@ -321,6 +361,13 @@ class OfflineRecognizer:
         (1 .. 8) best ids per frame.  Tokens, Timestamps, Scores and the result text stay as they are; entry 0 is the
         search's best, which need not be the result."""
         _ck(self._lib.pf_recognizer_set_ctc_beam(self._h, int(N), int(W), int(K)))
+
+    def SetAlign(self, on: bool = True) -> None:
+        """SenseVoice models: CTC forced alignment on the device for every GetResults that follows (off by default).  A
+        stream with a target (OfflineStream.SetAlignIds) gets OfflineStream.Alignment — where each id of the known text lies
+        in the audio, and log P(text | audio); with SetCtcBeam every Alternative gets Timestamps of its own and LogLik.
+        Tokens, Timestamps, Scores, the result text and the alternatives' order and scores stay as they are."""
+        _ck(self._lib.pf_recognizer_set_align(self._h, 1 if on else 0))
 
     def GetResult(self, stream: OfflineStream) -> OfflineRecognizerResultEntity:
         return self.GetResults([stream])[0]

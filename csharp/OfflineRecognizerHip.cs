@@ -180,9 +180,38 @@ namespace AliParaformerAsr.Hip
                         ParaformerHip.Check(ParaformerHip.pf_stream_alternative_token(Handle, i, j, out IntPtr t));
                         a.Tokens.Add(Marshal.PtrToStringUTF8(t) ?? "");
                     }
+                    ParaformerHip.Check(ParaformerHip.pf_stream_alternative_timestamps(Handle, i, out IntPtr pt, out int nts, out double ll));
+                    var flat = new int[2 * nts];
+                    if (nts > 0) Marshal.Copy(pt, flat, 0, 2 * nts);
+                    for (int j = 0; j < nts; j++) a.Timestamps.Add(new[] { flat[2 * j], flat[2 * j + 1] });
+                    a.LogLik = ll;
                     r.Add(a);
                 }
                 return r;
+            }
+        }
+
+        /// <summary>Not in the reference: the stream's target for forced alignment (OfflineRecognizer.SetAlign) as token IDS — text
+        /// to ids needs the model's tokenizer and is the caller's.  Kept until cleared with null.</summary>
+        public void SetAlignIds(long[]? ids)
+            => ParaformerHip.Check(ParaformerHip.pf_stream_set_align_ids(Handle, ids, ids == null ? -1 : ids.Length));
+
+        /// <summary>Not in the reference: the forced alignment of the target of the last GetResults; null when nothing was aligned
+        /// for this stream.</summary>
+        public Alignment? Alignment
+        {
+            get
+            {
+                ParaformerHip.Check(ParaformerHip.pf_stream_alignment(Handle, out IntPtr pt, out IntPtr ps, out int n, out float path,
+                                                                      out double ll, out int ok));
+                if (n < 0) return null;
+                var a = new Alignment { Ok = ok != 0, PathScore = path, LogLik = ll };
+                int k = ok != 0 ? n : 0;
+                var flat = new int[2 * k]; var sc = new float[k];
+                if (k > 0) { Marshal.Copy(pt, flat, 0, 2 * k); Marshal.Copy(ps, sc, 0, k); }
+                for (int j = 0; j < k; j++) a.Timestamps.Add(new[] { flat[2 * j], flat[2 * j + 1] });
+                a.Scores.AddRange(sc);
+                return a;
             }
         }
 
@@ -225,6 +254,21 @@ namespace AliParaformerAsr.Hip
         public double Score;
         public string Text = "";
         public List<string> Tokens = new List<string>();
+        /// <summary>SetAlign beside SetCtcBeam: one [begin, end] pair in ms per id from the labeling's own forced alignment (empty
+        /// without) and the log of the sum over all of its alignments (NaN without).</summary>
+        public List<int[]> Timestamps = new List<int[]>();
+        public double LogLik = double.NaN;
+    }
+
+    /// <summary>OfflineStream.Alignment: where each id of a known text lies in the audio.  Ok = false: the target does not fit the
+    /// audio; Timestamps / Scores are then empty.</summary>
+    public sealed class Alignment
+    {
+        public bool Ok;
+        public float PathScore;
+        public double LogLik;
+        public List<int[]> Timestamps = new List<int[]>();
+        public List<float> Scores = new List<float>();
     }
 
     public sealed class OfflineRecognizer : IDisposable
@@ -262,6 +306,11 @@ namespace AliParaformerAsr.Hip
         /// descending Score (the log of the summed alignments), found with beam width W (0 = max(16, N)) over the K (1 .. 8) best
         /// ids per frame.  Tokens, Timestamps, Scores and the result text stay as they are.</summary>
         public void SetCtcBeam(int N, int W = 0, int K = 4) => ParaformerHip.Check(ParaformerHip.pf_recognizer_set_ctc_beam(_r, N, W, K));
+
+        /// <summary>Not in the reference: SenseVoice models only.  CTC forced alignment on the device for every GetResults that
+        /// follows (off by default): a stream with a target (OfflineStream.SetAlignIds) gets OfflineStream.Alignment, and with
+        /// SetCtcBeam every Alternative gets Timestamps of its own and LogLik.  Everything else stays as it is.</summary>
+        public void SetAlign(bool on = true) => ParaformerHip.Check(ParaformerHip.pf_recognizer_set_align(_r, on ? 1 : 0));
 
         public OfflineStream CreateOfflineStream()
         {

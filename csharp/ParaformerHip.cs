@@ -102,6 +102,17 @@ namespace AliParaformerAsr.Native
         [DllImport(Lib)] internal static extern int pf_host_ctc_beam(float[] blankLp, long blankStride, long[] ids, float[] val, int[] n, int T, int K,
                                                                     int blank, int W, int N, [Out] long[] outIds, [Out] int[] outLen,
                                                                     [Out] double[] outScore, int cap, out int nHyp);
+        // CTC forced alignment (additions to ABI 6): PF_DECODE_ALIGN (SenseVoice; implies SCORES) aligns the targets set for the next
+        // forward, and with PF_DECODE_CTC_BEAM the beam's hypotheses, to the log-prob rows: Viterbi path and log-likelihood per job
+        internal const int PF_DECODE_ALIGN = 32;
+        internal const int PF_ALIGN_MAX_TOKENS = 1023;
+        [DllImport(Lib)] internal static extern int pf_engine_set_align_targets(IntPtr e, long[]? ids, int[]? len, int B, int cap);
+        [DllImport(Lib)] internal static extern int pf_fetch_align(IntPtr e, [Out] float[]? pathScore, [Out] double[]? loglik, [Out] int[]? ok,
+                                                                  [Out] int[]? len, [Out] int[]? first, [Out] int[]? last,
+                                                                  [Out] float[]? tokScore, int cap, out int H, out int lenMax);
+        [DllImport(Lib)] internal static extern int pf_host_ctc_align(float[] lp, long ld, int T, int V, long[] y, int U, out float pathScore,
+                                                                     out double loglik, out int ok, [Out] int[] first, [Out] int[] last,
+                                                                     [Out] float[] tokScore);
         [DllImport(Lib)] internal static extern int pf_host_nbest(long[]? ids, float[] val, int[] n, int L, int K, int nFree, int N,
                                                                  [Out] int[] outRanks, [Out] double[] outScores, out int nOut);
 
@@ -154,6 +165,11 @@ namespace AliParaformerAsr.Native
         [DllImport(Lib)] internal static extern int pf_stream_scores(IntPtr s, out IntPtr scores, out int n);
         [DllImport(Lib)] internal static extern int pf_recognizer_set_nbest(IntPtr r, int N, int K);
         [DllImport(Lib)] internal static extern int pf_recognizer_set_ctc_beam(IntPtr r, int N, int W, int K);
+        [DllImport(Lib)] internal static extern int pf_recognizer_set_align(IntPtr r, int on);
+        [DllImport(Lib)] internal static extern int pf_stream_set_align_ids(IntPtr s, long[]? ids, int n);
+        [DllImport(Lib)] internal static extern int pf_stream_alignment(IntPtr s, out IntPtr beginEnd, out IntPtr tokScore, out int n, out float pathScore,
+                                                                       out double loglik, out int ok);
+        [DllImport(Lib)] internal static extern int pf_stream_alternative_timestamps(IntPtr s, int i, out IntPtr beginEnd, out int n, out double loglik);
         [DllImport(Lib)] internal static extern int pf_stream_token_alternatives(IntPtr s, out IntPtr ids, out IntPtr val, out int nTokens, out int K);
         [DllImport(Lib)] internal static extern int pf_stream_num_alternatives(IntPtr s, out int n);
         [DllImport(Lib)] internal static extern int pf_stream_alternative(IntPtr s, int i, out IntPtr ids, out int nIds, out double score,

@@ -283,6 +283,50 @@ int pf_host_ctc_beam(const float* blank_lp, int64_t blank_stride, const int64_t*
                      int32_t K, int32_t blank, int32_t W, int32_t N, int64_t* out_ids, int32_t* out_len, double* out_score,
                      int32_t cap, int32_t* n_hyp);
 
+/* ---- CTC forced alignment (additions to ABI 6; nothing is launched or allocated without the flag) ----------------------
+   PF_DECODE_ALIGN (pf_engine_set_decode; SenseVoice only, every math_mode; implies SCORES, not TOPK; independent of
+   PF_DECODE_CTC; PF_ERR_UNSUPPORTED for a paraformer or SeACo model and for a pf_group forward): where the text is already
+   known — a caller's target, or the hypotheses PF_DECODE_CTC_BEAM keeps — one kernel (csrc/k_ctcalign.hip) behind the other
+   decode launches finds the best CTC alignment (Viterbi) of that labeling and the sum over all of its alignments.
+   The API takes token IDS: text to ids needs the model's sentencepiece tokenizer and is the caller's business.
+   INPUTS per job: the log-prob rows lp[t, :] of the frames t < n_b (the arg-max's in-place rows, prompt rows included, n_b
+   as for PF_DECODE_CTC) and a target y[0 .. U) of ids in [1, V); the blank is id 0.  States s in [0, 2U + 1): lab(s) is the
+   blank for even s and y[s / 2] for odd s.
+   BEST PATH, float32: a[0][0] = lp[0][0], a[0][1] = lp[0][y[0]], else -inf; a[t][s] = best + lp[t][lab(s)] with best among
+   the predecessors s, s-1 and (s odd, lab(s) != lab(s-2)) s-2, tried in that order with a strict >: of equal values the
+   larger state wins.  The end state is 2U unless a[T-1][2U-1] > a[T-1][2U].  One float add per cell in frame order.
+   Per token u: first[u] / last[u] = first / last frame of the path in state 2u+1 (indices in the row, as pf_fetch_ctc),
+   tok_score[u] = the largest lp[t][y[u]] of that run.
+   LOG-LIKELIHOOD, float64: the same recursion with lse(a, b) = max + log1p(exp(-|a - b|)) (-inf passed through) in place of
+   max, ((stay + s-1) + s-2) + lp, ended by lse(a[2U], a[2U-1]): log of the sum over all alignments, which the beam search's
+   scores bound from below.
+   ok = path_score > -inf.  Not ok (U > n_b, too few frames for repeated ids, n_b = 0 with U > 0, NaN rows; a beam hypothesis
+   longer than PF_ALIGN_MAX_TOKENS): first / last hold -1, tok_score 0, path_score / loglik -inf or NaN.  U = 0 is the
+   all-blank path; n_b = 0 with U = 0 is ok with score 0.  The definition in numpy is tests/ctcalign_ref.py.
+   JOBS of a forward: H = (targets set ? 1 : 0) + (PF_DECODE_CTC_BEAM ? N : 0) per utterance, the caller's target first, then
+   the beam's hypotheses in their order (assembled on the device); H = 0 launches nothing.  token_ids, pf_fetch_scores,
+   pf_fetch_ctc, pf_fetch_topk and pf_fetch_ctc_beam are what they are without the flag.
+   The flag is bit 32; bits 4 and 64 stay unassigned (PF_ERR_INVALID_ARG). */
+#define PF_DECODE_ALIGN 32
+#define PF_ALIGN_MAX_TOKENS 1023
+/* Targets of the NEXT forward on this engine (consumed by it, like the decode lengths): ids [B, cap] int64, len [B] with
+   len[b] = -1 for "no target for this row" (its job is skipped).  PF_ERR_INVALID_ARG: PF_DECODE_ALIGN not set, an id outside
+   [1, V); PF_ERR_CAPACITY: a len above PF_ALIGN_MAX_TOKENS or cap.  A forward whose batch is not B answers
+   PF_ERR_INVALID_ARG before it launches anything (the targets are dropped).  B = 0 clears pending targets. */
+int pf_engine_set_align_targets(pf_engine* e, const int64_t* ids, const int32_t* len, int32_t B, int32_t cap);
+/* path_score [B, H] fp32, loglik [B, H] float64, ok [B, H], len [B, H] (the job's target length; -1: skipped job, its other
+   slots hold -inf / -inf / 0), first / last [B, H, cap] (-1 past len and when not ok), tok_score [B, H, cap] (0 likewise), each
+   optional.  *H = jobs per utterance, *len_max = the longest target of the batch.  first / last / tok_score with
+   cap < *len_max -> PF_ERR_CAPACITY (H and len_max filled in first).  PF_ERR_INVALID_ARG when that forward ran without the
+   flag.  Call it BEFORE the pf_fetch that receives token_ids (it releases the thread's slot). */
+int pf_fetch_align(pf_engine* e, float* path_score, double* loglik, int32_t* ok, int32_t* len, int32_t* first, int32_t* last,
+                   float* tok_score, int32_t cap, int32_t* H, int32_t* len_max);
+/* The same alignment for ONE utterance and ONE target in plain host code (the twin of the kernel): lp [T, ld] (V read per
+   row), y [U]; first / last / tok_score [U].  PF_ERR_INVALID_ARG for an id outside [1, V), PF_ERR_CAPACITY for
+   U > PF_ALIGN_MAX_TOKENS. */
+int pf_host_ctc_align(const float* lp, int64_t ld, int32_t T, int32_t V, const int64_t* y, int32_t U, float* path_score,
+                      double* loglik, int32_t* ok, int32_t* first, int32_t* last, float* tok_score);
+
 /* ---- PCM intake (additions to ABI 6) --------------------------------------------------------------------------------
    The audio in the form callers hold it — a wav payload, PCM off a socket — uploaded RAW and turned into the engine's
    float32 mono samples at `fs` by one kernel (csrc/k_pcm.hip) in front of the unchanged fbank.  The result is bit for bit
@@ -397,6 +441,13 @@ int pf_op_topk(pf_engine* e, const float* x, int64_t rows, int32_t V, int32_t ld
 int pf_op_ctc_beam(pf_engine* e, const float* blank_lp, const int64_t* ids, const float* val, const int32_t* n, const int32_t* lens,
                    int32_t B, int32_t T, int32_t K, int32_t blank, int32_t W, int32_t N, int64_t* out_ids, int32_t* out_len,
                    double* out_score, int32_t cap, int32_t* n_hyp);
+/* exactly the pipeline's alignment kernel (k_ctcalign.hip) on caller arrays: lp [B * T, ld] (V read per row), tgt [B, H, cap]
+   int32, tlen [B, H] (-1: skip the job; above cap or PF_ALIGN_MAX_TOKENS: ok = 0), lens [B] (clamped to 0 .. T; nothing at or
+   beyond lens[b] is read, nor a target slot at or beyond tlen; an id outside [0, V) makes the job not ok).  Outputs as
+   pf_fetch_align, every slot written. */
+int pf_op_ctc_align(pf_engine* e, const float* lp, int32_t B, int32_t T, int32_t V, int32_t ld, const int32_t* tgt,
+                    const int32_t* tlen, const int32_t* lens, int32_t H, int32_t cap, float* path_score, double* loglik,
+                    int32_t* ok, int32_t* first, int32_t* last, float* tok_score);
 /* C = A[M,K] * W[N,K]^T + bias, f16 operands / f32 accumulate; epilogue 0 none, 1 relu,
    2 = f16 result store (the path the pipeline uses), returned widened to fp32. */
 /* One dynamically quantised Linear, the building block of math_mode 2 (the reference's default model.int8.onnx:
@@ -656,6 +707,22 @@ int pf_recognizer_set_nbest(pf_recognizer* r, int32_t N, int32_t K);
    result); TokenAlternatives is filled as with pf_recognizer_set_nbest(1, K).  Tokens, Timestamps, Scores and the result
    text are what they are without it; alternative 0 is the search's best, not necessarily the result. */
 int pf_recognizer_set_ctc_beam(pf_recognizer* r, int32_t N, int32_t W, int32_t K);
+/* SenseVoice only (see "CTC forced alignment"; PF_ERR_UNSUPPORTED otherwise).  on != 0: PF_DECODE_ALIGN on every engine of
+   the pool, present and future, beside the other flags.  A stream's target is set with pf_stream_set_align_ids (token IDS — text
+   to ids is the caller's; kept until cleared with n < 0; PF_ERR_INVALID_ARG for an id outside [1, V), PF_ERR_CAPACITY above
+   PF_ALIGN_MAX_TOKENS); in a batch a stream without a target is skipped.  After GetResults pf_stream_alignment gives the
+   target's [begin, end] pairs in ms (begin = ms * max(first - 4, 0), end = ms * max(last + 1 - 4, 0), ms = lfr_n * 10, as for
+   PF_DECODE_CTC), the token scores, the Viterbi score, the log-likelihood and ok; *n = -1 when nothing was aligned for the
+   stream, and with ok = 0 the arrays are empty.  With pf_recognizer_set_ctc_beam beside it each Alternative carries the times
+   of its own alignment — in its decoded timestamps in place of {0, 0}, and raw ([*n, 2], *n = 0 without) through
+   pf_stream_alternative_timestamps — and *loglik, the log of the sum over ALL of its alignments (NaN without).  Tokens,
+   Timestamps, Scores, the result text and the alternatives' order and scores are what they are without it.  The pointers stay
+   valid until the stream's next GetResults. */
+int pf_recognizer_set_align(pf_recognizer* r, int32_t on);
+int pf_stream_set_align_ids(pf_stream* s, const int64_t* ids, int32_t n);
+int pf_stream_alignment(pf_stream* s, const int32_t** begin_end, const float** tok_score, int32_t* n, float* path_score,
+                        double* loglik, int32_t* ok);
+int pf_stream_alternative_timestamps(pf_stream* s, int32_t i, const int32_t** begin_end, int32_t* n, double* loglik);
 /* ids / val: [*n_tokens, *K], parallel to pf_stream_tokens; slots past a position's n hold -1 / -inf.  *n_tokens = 0
    without pf_recognizer_set_nbest.  The pointers stay valid until the stream's next GetResults. */
 int pf_stream_token_alternatives(pf_stream* s, const int64_t** ids, const float** val, int32_t* n_tokens, int32_t* K);
