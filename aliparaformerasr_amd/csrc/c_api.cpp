@@ -840,6 +840,28 @@ int pf_op_fsmn_dec(pf_engine* h, const float* tn, const float* w, const int32_t*
   return PF_OK;
   PF_CATCH
 }
+int pf_op_lstm(pf_engine* h, const float* xg, const float* whh, int32_t B, int32_t T3, int32_t D, int32_t ndir, int32_t form,
+               float* hout) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  NEED(xg); NEED(whh); NEED(hout);
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->op_lstm(xg, whh, B, T3, D, ndir, form, hout);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_op_us_peak(pf_engine* h, const float* hout, const float* w, const float* b0, float smooth, float noise, const int32_t* token_num,
+                  float thr, int32_t B, int32_t T3, int32_t W, float* alphas_raw, float* alphas, float* peak) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  NEED(hout); NEED(w); NEED(b0); NEED(token_num); NEED(alphas_raw); NEED(alphas); NEED(peak);
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->op_us_peak(hout, w, b0, smooth, noise, token_num, thr, B, T3, W, alphas_raw, alphas, peak);
+  return PF_OK;
+  PF_CATCH
+}
 int pf_op_logsoftmax_argmax(pf_engine* h, const float* x, int64_t rows, int32_t V, float* y, int64_t* ids) {
   PF_TRY
   std::shared_ptr<Engine> eh_ = E(h);

@@ -1696,11 +1696,10 @@ void Engine::seaco_head(int B, int L, const float* e0, const float* hid32, bool 
   for (size_t l = 0; l < seaco_lstm_.size(); ++l) {
     gemm("gemm_seaco", seaco_lstm_[l].ih, in16, D, NJ, xg, 4 * D, nullptr, 0, nullptr, 0, nullptr, 0, false, 0, 1.f);
     prof_begin("seaco_embed", 0);
-    PF_HIP(hipMemsetAsync(hs, 0, (size_t)2 * N * D * 2, stream_));
-    PF_HIP(hipMemsetAsync(cs, 0, (size_t)N * D * 4, stream_));
     LstmArgs a{};
     a.whh = seaco_lstm_[l].whh; a.xg = xg; a.hstate = hs; a.cstate = cs; a.hout = hout; a.B = N; a.T3 = J; a.D = D; a.ndir = 1;
-    for (int st = 0; st < J; ++st) { a.step = st; launch_lstm_step(stream_, a); }
+    lstm_clear16(a);
+    lstm_steps16(a);
     launch_f32_to_f16(stream_, hout, NJ, D, D, in16, D);
     prof_end("seaco_embed");
   }
@@ -1750,6 +1749,42 @@ void Engine::seaco_head(int B, int L, const float* e0, const float* hid32, bool 
   prof_end("seaco_merge");
 }
 
+// The recurrence of the f16 timestamp head (k_bicif.hip): ONE persistent launch (W_hh resident in registers, h exchanged through
+// a ring of write-through stores) when every workgroup fits on the device at once; otherwise (B > 64) the T3 dependent launches,
+// captured once per (shape, buffers) into a hipGraph and replayed.
+void Engine::lstm_clear16(const LstmArgs& a) {
+  PF_HIP(hipMemsetAsync(a.hstate, 0, (size_t)a.ndir * 2 * a.B * a.D * 2, stream_));
+  PF_HIP(hipMemsetAsync(a.cstate, 0, (size_t)a.ndir * a.B * a.D * 4, stream_));
+}
+
+void Engine::lstm_steps16(LstmArgs a) {
+  for (int s = 0; s < a.T3; ++s) { a.step = s; launch_lstm_step(stream_, a); }
+}
+
+bool Engine::lstm_recurrence16(LstmArgs a, unsigned* sw, bool ring_only) {
+  lstm_clear16(a);
+  if (launch_lstm_persistent(stream_, a, sw)) {
+    lstm_err_ = sw + 63;
+    return true;
+  }
+  PF_CHECK(!ring_only, PF_ERR_UNSUPPORTED, "lstm: the persistent recurrence does not fit on the device at this shape");
+  auto& k = lstm_graph_key_;
+  const void* rest[4] = {a.whh, a.hstate, a.cstate, a.hout};
+  if (!lstm_graph_exec_ || k.xg != a.xg || k.B != a.B || k.T3 != a.T3 || k.ndir != a.ndir || std::memcmp(k.rest, rest, sizeof(rest)) != 0) {
+    if (lstm_graph_exec_) { hipGraphExecDestroy(lstm_graph_exec_); lstm_graph_exec_ = nullptr; }
+    hipGraph_t g = nullptr;
+    PF_HIP(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal));
+    lstm_steps16(a);
+    PF_HIP(hipStreamEndCapture(stream_, &g));
+    PF_HIP(hipGraphInstantiate(&lstm_graph_exec_, g, nullptr, nullptr, 0));
+    hipGraphDestroy(g);
+    k.xg = a.xg; k.B = a.B; k.T3 = a.T3; k.ndir = a.ndir;
+    std::memcpy(k.rest, rest, sizeof(rest));
+  }
+  PF_HIP(hipGraphLaunch(lstm_graph_exec_, stream_));
+  return false;
+}
+
 // BiCIF timestamp head (k_bicif.hip): us_cif_peak [B, 3T]; needs token_num (device) only.
 void Engine::timestamp_head(int B, int T) {
   const int D = mc_.d_model, up = mc_.upsample;
@@ -1774,30 +1809,9 @@ void Engine::timestamp_head(int B, int T) {
   gemm("gemm_ts", ts_up_, H16_, D, M, nullptr, 0, up16, up * D, nullptr, 0, nullptr, 0, false, 0, 1.f);
   gemm("gemm_ts", ts_ih_, up16, D, (int)M3, xg, 8 * D, nullptr, 0, nullptr, 0, nullptr, 0, false, 0, 1.f);
   prof_begin("lstm", 2.0 * 2 * M3 * 4.0 * D * D);
-  PF_HIP(hipMemsetAsync(hs, 0, (size_t)4 * B * D * 2, stream_));
-  PF_HIP(hipMemsetAsync(cs, 0, (size_t)2 * B * D * 4, stream_));
   LstmArgs a{};
   a.whh = ts_whh_; a.xg = xg; a.hstate = hs; a.cstate = cs; a.hout = hout; a.B = B; a.T3 = T3; a.D = D; a.ndir = 2;
-  // the recurrence: ONE persistent launch (W_hh resident in registers, h exchanged through a ring of write-through
-  // stores, k_bicif.hip) when every workgroup fits on the device at once; otherwise (B > 64) the 3T dependent launches,
-  // captured once per (shape, workspace) into a hipGraph and replayed
-  unsigned* sw = (unsigned*)(base + o_sw);
-  const bool persistent = launch_lstm_persistent(stream_, a, sw);
-  if (persistent) {
-    lstm_err_ = sw + 63;
-  } else {
-    if (!lstm_graph_exec_ || lstm_graph_key_.xg != xg || lstm_graph_key_.B != B || lstm_graph_key_.T3 != T3) {
-      if (lstm_graph_exec_) { hipGraphExecDestroy(lstm_graph_exec_); lstm_graph_exec_ = nullptr; }
-      hipGraph_t g = nullptr;
-      PF_HIP(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal));
-      for (int s = 0; s < T3; ++s) { a.step = s; launch_lstm_step(stream_, a); }
-      PF_HIP(hipStreamEndCapture(stream_, &g));
-      PF_HIP(hipGraphInstantiate(&lstm_graph_exec_, g, nullptr, nullptr, 0));
-      hipGraphDestroy(g);
-      lstm_graph_key_.xg = xg; lstm_graph_key_.B = B; lstm_graph_key_.T3 = T3;
-    }
-    PF_HIP(hipGraphLaunch(lstm_graph_exec_, stream_));
-  }
+  lstm_recurrence16(a, (unsigned*)(base + o_sw));
   prof_end("lstm");
   if (ts_defer_copy_) PF_HIP(hipStreamWaitEvent(stream_, ev_scan_, 0));   // on the side stream: token_num comes from the CIF scan
   prof_begin("ts_misc", 0);

@@ -214,6 +214,12 @@ class Engine {
               int M, int D, int F, float* y);
   void op_fsmn_enc(const float* v, const float* w, int B, int T, int D, int k, float* y);
   void op_fsmn_dec(const float* tn, const float* w, const int32_t* token_num, int B, int L, int D, int k, float* x);
+  // the (Bi)LSTM recurrence through the functions the heads call; form: 0 = as timestamp_head chooses (ring, else the cached graph of
+  // step launches), 1 = plain step launches (seaco_head), 2 = f16 ring, 3 = pair-operand ring, 4 = fp32 GEMM + cell per step
+  void op_lstm(const float* xg, const float* whh, int B, int T3, int D, int ndir, int form, float* hout);
+  // launch_us_alpha + launch_us_peak as the timestamp heads run them
+  void op_us_peak(const float* hout, const float* w, const float* b0, float smooth, float noise, const int32_t* token_num, float thr,
+                  int B, int T3, int W, float* alphas_raw, float* alphas, float* peak);
   void op_logsoftmax_argmax(const float* x, int64_t rows, int V, float* y, int64_t* ids);
   void op_layernorm(const float* x, const float* g, const float* b, int64_t rows, int D, float* y);
   void op_attention(const float* q, const float* k, const float* v, int B, int Lq, int Lk, int H, float* o);
@@ -296,6 +302,16 @@ class Engine {
   // fp32 LSTM over rows [Bn * Tn] of x (row b * Tn + t): hout[(b * Tn + t) * ldh + col0 .. + D); reverse = time runs backwards
   void lstm_fp32(const float* x, int Bn, int Tn, const float* w_ih, const float* w_hh, const float* bias, bool reverse,
                  float* xg, float* gates, float* hbuf, float* cbuf, float* hout, int ldh, int col0);
+  // the recurrence of lstm_fp32 on prepared gate inputs xg [Bn * Tn, 4D]: one fp32 GEMM + one cell kernel per time step
+  void lstm_fp32_steps(const float* xg, int Bn, int Tn, const float* w_hh, bool reverse, float* gates, float* hbuf, float* cbuf,
+                       float* hout, int ldh, int col0);
+  // the f16-operand recurrences on prepared LstmArgs (k_bicif.hip); the heads and op_lstm run the same functions
+  void lstm_clear16(const LstmArgs& a);              // h_{-1} = c_{-1} = 0 of the per-step form: hstate [ndir][2][B][D], cstate [ndir][B][D]
+  void lstm_steps16(LstmArgs a);                     // T3 launches of lstm_step_kernel
+  // clears the state, then the ring (sw: 64 sync words) when every workgroup fits on the device, otherwise the T3 step launches as a
+  // cached hipGraph; returns whether the ring ran.  ring_only: PF_ERR_UNSUPPORTED instead of the step launches
+  bool lstm_recurrence16(LstmArgs a, unsigned* sw, bool ring_only = false);
+  bool lstm_ring_x3(const LstmArgs& a, unsigned* sw);   // the pair-operand ring (math_mode 3); false = does not fit, nothing was launched
   void enc_layer_fp32(const EncLayer& L, bool first, const float* speech_dev, int B, int T, float** bufs);
   void timestamp_head(int B, int T);
   void start_timestamp_head(int B, int T);
@@ -430,7 +446,7 @@ class Engine {
   float* fsm_ = nullptr; half_t* h16_ = nullptr; float* H32_ = nullptr; half_t* H16_ = nullptr;
   float* alphas_ = nullptr; CifPlan plan_{};
   float* us_peak_ = nullptr;
-  struct { const float* xg = nullptr; int B = 0, T3 = 0; } lstm_graph_key_;
+  struct { const float* xg = nullptr; int B = 0, T3 = 0; const void* rest[4] = {nullptr, nullptr, nullptr, nullptr}; int ndir = 0; } lstm_graph_key_;
   hipGraphExec_t lstm_graph_exec_ = nullptr;
   // decoder views
   float* logits_ = nullptr; int64_t* ids_dev_ = nullptr; int logits_ld_ = 0;

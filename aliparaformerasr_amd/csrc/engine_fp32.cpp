@@ -368,6 +368,12 @@ void Engine::lstm_fp32(const float* x, int Bn, int Tn, const float* w_ih, const 
   const int D = mc_.d_model;
   // input half of the gates for every row at once: xg[b * Tn + t, 0:4D] = x W_ih^T + (b_ih + b_hh)
   gemm32(x, D, w_ih, D, bias, Bn * Tn, 4 * D, D, xg, 4 * D, nullptr, 0, false, 0, 1.f);
+  lstm_fp32_steps(xg, Bn, Tn, w_hh, reverse, gates, hbuf, cbuf, hout, ldh, col0);
+}
+
+void Engine::lstm_fp32_steps(const float* xg, int Bn, int Tn, const float* w_hh, bool reverse, float* gates, float* hbuf, float* cbuf,
+                             float* hout, int ldh, int col0) {
+  const int D = mc_.d_model;
   PF_HIP(hipMemsetAsync(hbuf, 0, (size_t)Bn * D * 4, stream_));
   PF_HIP(hipMemsetAsync(cbuf, 0, (size_t)Bn * D * 4, stream_));
   for (int st = 0; st < Tn; ++st) {
@@ -376,6 +382,12 @@ void Engine::lstm_fp32(const float* x, int Bn, int Tn, const float* w_ih, const 
     launch_gemm_f32(stream_, hbuf, D, w_hh, D, nullptr, Bn, 4 * D, D, gates, 4 * D, xg + (size_t)t * 4 * D, Tn * 4 * D, false, 0, 1.f);
     launch_lstm_cell_f32(stream_, gates, 4 * D, cbuf, hbuf, hout + (size_t)t * ldh + col0, (int64_t)Tn * ldh, Bn, D);
   }
+}
+
+bool Engine::lstm_ring_x3(const LstmArgs& a, unsigned* sw) {
+  const bool done = launch_lstm_persistent_x3(stream_, a, sw);
+  if (done) lstm_err_ = sw + 63;
+  return done;
 }
 
 void Engine::timestamp_head_fp32(int B, int T) {
@@ -414,9 +426,7 @@ void Engine::timestamp_head_fp32(int B, int T) {
              xg2 + (size_t)d * 4 * D, 8 * D, nullptr, 0, false, 0, 1.f, d == 1 ? kX3SameInput : 0);
     LstmArgs a{};
     a.whh = ts_whh_x3_; a.xg = xg2; a.hstate = (half_t*)(base + o_hs); a.cstate = nullptr; a.hout = hout; a.B = B; a.T3 = T3; a.D = D; a.ndir = 2;
-    unsigned* sw = (unsigned*)(base + o_sw);
-    done = launch_lstm_persistent_x3(stream_, a, sw);
-    if (done) lstm_err_ = sw + 63;
+    done = lstm_ring_x3(a, (unsigned*)(base + o_sw));
   }
   if (!done)
   for (int d = 0; d < 2; ++d)

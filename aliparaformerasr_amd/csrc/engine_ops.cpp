@@ -726,6 +726,83 @@ void Engine::op_fsmn_dec(const float* tn, const float* w, const int32_t* token_n
   PF_HIP(hipStreamSynchronize(stream_));
 }
 
+// The (Bi)LSTM recurrence through the functions the heads call (lstm_recurrence16 / lstm_steps16 / lstm_ring_x3 / lstm_fp32_steps):
+// xg [B, T3, ndir * 4D] fp32 gate inputs with the biases added, whh [ndir, 4D, D] fp32 (converted here as load_weights /
+// timestamp_head_fp32 convert it), hout [B, T3, ndir * D].  hout is NaN-filled first: an element no form wrote stays visible.
+void Engine::op_lstm(const float* xg, const float* whh, int B, int T3, int D, int ndir, int form, float* hout) {
+  PF_CHECK(D == 512 && D == mc_.d_model, PF_ERR_UNSUPPORTED, "lstm: hidden size must be 512 and the engine's d_model");
+  PF_CHECK(B > 0 && T3 > 0 && (ndir == 1 || ndir == 2), PF_ERR_INVALID_ARG, "lstm: bad shape");
+  PF_CHECK(form >= 0 && form <= 4, PF_ERR_INVALID_ARG, "lstm: form must be 0..4");
+  PF_HIP(hipSetDevice(device_));
+  const size_t rows = (size_t)B * T3, nw = (size_t)ndir * 4 * D * D;
+  size_t off = 0;
+  auto carve = [&](size_t bytes) { size_t o = off; off += round_up((int64_t)bytes, (int64_t)kAlign); return o; };
+  const size_t o_xg = carve(rows * ndir * 4 * D * 4), o_w32 = carve(nw * 4), o_w16 = carve(nw * 2 * 2);
+  const size_t o_hs = carve((size_t)ndir * 4 * B * 2 * D * 2), o_cs = carve((size_t)ndir * B * D * 4), o_ho = carve(rows * ndir * D * 4);
+  const size_t o_sw = carve(256), o_xd = carve(rows * 4 * D * 4), o_g = carve((size_t)B * 4 * D * 4), o_h = carve((size_t)B * D * 4);
+  const size_t o_c = carve((size_t)B * D * 4);
+  ensure(ws_tmp_, off);
+  char* base = (char*)ws_tmp_.p;
+  float* xgd = (float*)(base + o_xg); float* w32 = (float*)(base + o_w32); half_t* w16 = (half_t*)(base + o_w16);
+  float* ho = (float*)(base + o_ho);
+  unsigned* sw = (unsigned*)(base + o_sw);
+  PF_HIP(hipMemcpyAsync(xgd, xg, rows * ndir * 4 * D * 4, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipMemcpyAsync(w32, whh, nw * 4, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipMemsetAsync(ho, 0xFF, rows * ndir * D * 4, stream_));
+  LstmArgs a{};
+  a.whh = w16; a.xg = xgd; a.hstate = (half_t*)(base + o_hs); a.cstate = (float*)(base + o_cs); a.hout = ho;
+  a.B = B; a.T3 = T3; a.D = D; a.ndir = ndir;
+  if (form <= 2) {
+    launch_f32_to_f16(stream_, w32, (int64_t)ndir * 4 * D, D, D, w16, D);
+    if (form == 1) { lstm_clear16(a); lstm_steps16(a); }
+    else lstm_recurrence16(a, sw, form == 2);
+  } else if (form == 3) {
+    for (int d = 0; d < ndir; ++d)
+      launch_split_x3(stream_, w32 + (size_t)d * 4 * D * D, 4 * D, D, D, w16 + (size_t)d * 4 * D * 2 * D, 2 * D, D, 0);
+    a.cstate = nullptr;
+    PF_CHECK(lstm_ring_x3(a, sw), PF_ERR_UNSUPPORTED, "lstm: the persistent recurrence does not fit on the device at this shape");
+  } else {
+    float* xd = (float*)(base + o_xd);
+    for (int d = 0; d < ndir; ++d) {                  // lstm_fp32's gate inputs are one direction's [B * T3, 4D]
+      PF_HIP(hipMemcpy2DAsync(xd, (size_t)4 * D * 4, xgd + (size_t)d * 4 * D, (size_t)ndir * 4 * D * 4, (size_t)4 * D * 4, rows,
+                              hipMemcpyDeviceToDevice, stream_));
+      lstm_fp32_steps(xd, B, T3, w32 + (size_t)d * 4 * D * D, d == 1, (float*)(base + o_g), (float*)(base + o_h), (float*)(base + o_c), ho,
+                      ndir * D, d * D);
+    }
+  }
+  PF_HIP(hipMemcpyAsync(hout, ho, rows * ndir * D * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipStreamSynchronize(stream_));
+  check_async_errors();
+}
+
+// The tail of the timestamp heads: alphas_raw = relu(sigmoid(hout w + b0) * smooth - noise) (launch_us_alpha), then alphas =
+// alphas_raw * token_num / sum and the running integral peak (launch_us_peak, in place as the heads run it).
+void Engine::op_us_peak(const float* hout, const float* w, const float* b0, float smooth, float noise, const int32_t* token_num, float thr,
+                        int B, int T3, int W, float* alphas_raw, float* alphas, float* peak) {
+  PF_CHECK(B > 0 && T3 > 0 && W > 0 && W % 4 == 0, PF_ERR_INVALID_ARG, "us_peak: bad shape");
+  PF_HIP(hipSetDevice(device_));
+  const size_t rows = (size_t)B * T3;
+  size_t off = 0;
+  auto carve = [&](size_t bytes) { size_t o = off; off += round_up((int64_t)bytes, (int64_t)kAlign); return o; };
+  const size_t o_h = carve(rows * W * 4), o_w = carve((size_t)W * 4), o_b = carve(4), o_n = carve((size_t)B * 4), o_al = carve(rows * 4),
+               o_pk = carve(rows * 4);
+  ensure(ws_tmp_, off);
+  char* base = (char*)ws_tmp_.p;
+  float* al = (float*)(base + o_al); float* pk = (float*)(base + o_pk);
+  PF_HIP(hipMemcpyAsync(base + o_h, hout, rows * W * 4, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipMemcpyAsync(base + o_w, w, (size_t)W * 4, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipMemcpyAsync(base + o_b, b0, 4, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipMemcpyAsync(base + o_n, token_num, (size_t)B * 4, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipMemsetAsync(al, 0xFF, rows * 4, stream_));
+  PF_HIP(hipMemsetAsync(pk, 0xFF, rows * 4, stream_));
+  launch_us_alpha(stream_, (const float*)(base + o_h), (int64_t)rows, W, (const float*)(base + o_w), (const float*)(base + o_b), smooth, noise, al);
+  PF_HIP(hipMemcpyAsync(alphas_raw, al, rows * 4, hipMemcpyDeviceToHost, stream_));
+  launch_us_peak(stream_, al, (const int32_t*)(base + o_n), B, T3, thr, pk);
+  PF_HIP(hipMemcpyAsync(alphas, al, rows * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipMemcpyAsync(peak, pk, rows * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipStreamSynchronize(stream_));
+}
+
 // The pipeline's vocabulary tail: log-probs y = (x - max) - log(sum exp(x - max)) and the reference's last-index
 // arg-max over y (OfflineRecognizer.cs:139-152 scans the graph OUTPUT).  y == nullptr: ids only (mode 1).
 void Engine::op_logsoftmax_argmax(const float* x, int64_t rows, int V, float* y, int64_t* ids) {

@@ -822,6 +822,30 @@ class Engine:
                                          w.shape[1], _fp(x)))
         return x
 
+    def op_lstm(self, xg, whh, ndir, form) -> np.ndarray:
+        """The heads' LSTM recurrence on gate inputs xg [B, T3, ndir * 4D], whh [ndir, 4D, D] (pf_op_lstm): form 0 = as the f16
+        timestamp head chooses, 1 = per-step launches, 2 = f16 ring, 3 = pair-operand ring, 4 = fp32 per step."""
+        xg, whh = _f32(xg), _f32(whh)
+        B, T3, G = xg.shape
+        D = whh.shape[2]
+        assert whh.shape == (ndir, 4 * D, D) and G == ndir * 4 * D, (xg.shape, whh.shape, ndir)
+        hout = np.zeros((B, T3, ndir * D), np.float32)
+        N.check(self._lib.pf_op_lstm(self._h, _fp(xg), _fp(whh), B, T3, D, ndir, form, _fp(hout)))
+        return hout
+
+    def op_us_peak(self, hout, w, b0, smooth, noise, token_num, thr):
+        """launch_us_alpha + launch_us_peak as the timestamp heads run them (pf_op_us_peak): (alphas_raw, alphas, peak) [B, T3]."""
+        hout, w = _f32(hout), _f32(w).reshape(-1)
+        B, T3, Wd = hout.shape
+        assert w.size == Wd
+        b = np.asarray([b0], np.float32).reshape(1)
+        t = np.ascontiguousarray(token_num, dtype=np.int32)
+        assert t.shape == (B,)
+        outs = [np.zeros((B, T3), np.float32) for _ in range(3)]
+        N.check(self._lib.pf_op_us_peak(self._h, _fp(hout), _fp(w), _fp(b), float(smooth), float(noise),
+                                        t.ctypes.data_as(C.POINTER(C.c_int32)), float(thr), B, T3, Wd, *[_fp(o) for o in outs]))
+        return tuple(outs)
+
     def op_logsoftmax_argmax(self, x, store=True):
         a = _f32(x)
         V = a.shape[-1]

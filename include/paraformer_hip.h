@@ -570,6 +570,22 @@ int pf_op_fsmn_enc(pf_engine* e, const float* v, const float* w, int32_t B, int3
 /* Decoder FSMN kernel: x += (dwconv_k(tn*m) + tn*m)*m, m = (l < token_num[b]); x in/out [B,L,D]. */
 int pf_op_fsmn_dec(pf_engine* e, const float* tn, const float* w, const int32_t* token_num, int32_t B, int32_t L,
                    int32_t D, int32_t k, float* x);
+/* The (Bi)LSTM recurrence of the heads on prepared gate inputs, through the functions the heads call:
+     xg [B,T3,ndir*4D] = x W_ih^T + b_ih + b_hh (gate order i, f, g, o; directions side by side), whh [ndir,4D,D] fp32,
+     hout [B,T3,ndir*D]; D = 512 (and the engine's d_model).
+   form 0 = as the f16 timestamp head chooses: the persistent ring when it fits on the device, otherwise the step launches captured
+            into a hipGraph that is cached and replayed like the head's;
+        1 = plain per-step launches (the hot-word embedder's form);  2 = the f16 ring;  3 = the ring with (hi, lo') pair operands
+            (math_mode 3);  4 = one fp32 GEMM + one cell kernel per step (math_mode 1).
+   Forms 2 and 3 return PF_ERR_UNSUPPORTED where the ring does not fit (B > 64 at ndir = 2 on 256 compute units); a ring
+   time-out is PF_ERR_DEVICE. */
+int pf_op_lstm(pf_engine* e, const float* xg, const float* whh, int32_t B, int32_t T3, int32_t D, int32_t ndir, int32_t form,
+               float* hout);
+/* The tail of the timestamp heads: alphas_raw = relu(sigmoid(hout w + b0) * smooth - noise), alphas = alphas_raw * token_num / sum,
+   peak = the running integral with threshold thr (recorded before the reset).  hout [B,T3,W] with W a multiple of 4, w [W],
+   b0 [1], token_num [B]; the three outputs [B,T3]. */
+int pf_op_us_peak(pf_engine* e, const float* hout, const float* w, const float* b0, float smooth, float noise, const int32_t* token_num,
+                  float thr, int32_t B, int32_t T3, int32_t W, float* alphas_raw, float* alphas, float* peak);
 /* The pipeline's vocabulary tail: y = log_softmax(x) (two-step form, see k_misc.hip) and the last-index arg-max
    over y — what OfflineRecognizer.cs:139-152 scans.  y_out may be NULL (ids-only variant of the kernel). */
 int pf_op_logsoftmax_argmax(pf_engine* e, const float* x, int64_t rows, int32_t V, float* y_out, int64_t* ids_out);

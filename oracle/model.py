@@ -365,7 +365,12 @@ class Oracle:
         hcat = torch.cat(outs, dim=-1)                              # [B, 3T, 2D]
         z = torch.matmul(hcat, self.w["predictor.out2.weight"].t()).squeeze(-1) + self.w["predictor.out2.bias"]
         a2 = torch.relu(torch.sigmoid(z) * c.cif_smooth2 - c.cif_noise2)
-        a2 = a2.numpy().astype(F32)
+        return self.us_renorm_peak(a2.numpy().astype(F32), token_num)
+
+    def us_renorm_peak(self, a2, token_num):
+        """The last two stages of us_alphas_peak on the alphas before renormalisation, a2 [B, 3T] float32."""
+        c = self.cfg
+        B = a2.shape[0]
         tn = np.asarray(token_num, dtype=F32)
         ssum = a2.sum(axis=1, dtype=F32)
         a2 = (a2 * (tn / ssum)[:, None].astype(F32)).astype(F32)
