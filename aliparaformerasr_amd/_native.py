@@ -28,6 +28,9 @@ PF_DECODE_SCORES = 1
 PF_DECODE_CTC = 2
 PF_DECODE_TOPK = 8
 PF_DECODE_CTC_BEAM = 16
+PF_HOTWORD_STATES_MAX = 4096
+PF_HOTWORD_LEN_MAX = 64
+PF_HOTWORD_TABLE_BYTES_MAX = 16 * 1024 * 1024
 PF_DECODE_ALIGN = 32
 PF_ALIGN_MAX_TOKENS = 1023
 PF_TOPK_MAX = 8
@@ -174,6 +177,16 @@ SIGNATURES = {
     "pf_op_ctc_beam": (C.c_int, [_vp, _f, _i64, _f, _i32, _i32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                  _i64, _i32, _P(C.c_double), C.c_int32, _i32]),
     "pf_recognizer_set_ctc_beam": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32]),
+    "pf_host_hotword_graph": (C.c_int, [_i32, _i32, C.c_int32, C.c_int32, _i32, _i32, _i32, _i32, C.c_int64, _i32, C.c_int32]),
+    "pf_engine_set_ctc_hotwords": (C.c_int, [_vp, _i32, _i32, C.c_int32, C.c_float]),
+    "pf_fetch_ctc_beam_hot": (C.c_int, [_vp, _i32, _P(C.c_double)]),
+    "pf_host_ctc_beam_hot": (C.c_int, [_f, C.c_int64, _i64, _f, _i32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _i64, _i32,
+                                       _P(C.c_double), C.c_int32, _i32, _i32, _i32, C.c_int32, C.c_float, _i32, _P(C.c_double)]),
+    "pf_op_ctc_beam_hot": (C.c_int, [_vp, _f, _i64, _f, _i32, _i32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                     _i64, _i32, _P(C.c_double), C.c_int32, _i32, _i32, _i32, C.c_int32, C.c_float, _i32,
+                                     _P(C.c_double)]),
+    "pf_recognizer_set_hotword_boost": (C.c_int, [_vp, C.c_float]),
+    "pf_stream_alternative_hot": (C.c_int, [_vp, C.c_int32, _i32, _P(C.c_double)]),
     "pf_engine_set_align_targets": (C.c_int, [_vp, _i64, _i32, C.c_int32, C.c_int32]),
     "pf_fetch_align": (C.c_int, [_vp, _f, _P(C.c_double), _i32, _i32, _i32, _i32, _f, C.c_int32, _i32, _i32]),
     "pf_host_ctc_align": (C.c_int, [_f, C.c_int64, C.c_int32, C.c_int32, _i64, C.c_int32, _f, _P(C.c_double), _i32, _i32, _i32, _f]),

@@ -421,6 +421,55 @@ int pf_host_ctc_beam(const float* blank_lp, int64_t blank_stride, const int64_t*
   PF_CATCH
 }
 
+int pf_host_hotword_graph(const int32_t* ids, const int32_t* lens, int32_t n_hotwords, int32_t V, int32_t* n_states, int32_t* n_cols,
+                          int32_t* tok_col, int32_t* table, int64_t table_cap, int32_t* depth, int32_t depth_cap) {
+  PF_TRY
+  NEED(n_states); NEED(n_cols);
+  HotwordGraph g;
+  build_hotword_graph(ids, lens, n_hotwords, V, g);
+  *n_states = g.S;
+  *n_cols = g.A;
+  PF_CHECK(!table || table_cap >= (int64_t)g.table.size(), PF_ERR_CAPACITY, "hotword_graph: table_cap < n_states * n_cols");
+  PF_CHECK(!depth || depth_cap >= g.S, PF_ERR_CAPACITY, "hotword_graph: depth_cap < n_states");
+  if (tok_col) std::copy(g.tok_col.begin(), g.tok_col.end(), tok_col);
+  if (table) std::copy(g.table.begin(), g.table.end(), table);
+  if (depth) std::copy(g.depth.begin(), g.depth.end(), depth);
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_engine_set_ctc_hotwords(pf_engine* h, const int32_t* ids, const int32_t* lens, int32_t n_hotwords, float boost) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->set_ctc_hotwords(ids, lens, n_hotwords, boost);
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_fetch_ctc_beam_hot(pf_engine* h, int32_t* matched, double* loglik_sum) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->fetch_ctc_beam_hot(matched, loglik_sum);
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_host_ctc_beam_hot(const float* blank_lp, int64_t blank_stride, const int64_t* ids, const float* val, const int32_t* n, int32_t T,
+                         int32_t K, int32_t blank, int32_t W, int32_t N, int64_t* out_ids, int32_t* out_len, double* out_score,
+                         int32_t cap, int32_t* n_hyp, const int32_t* hw_ids, const int32_t* hw_lens, int32_t n_hotwords, float boost,
+                         int32_t* out_matched, double* out_loglik) {
+  PF_TRY
+  NEED(n_hyp);
+  *n_hyp = host_ctc_beam_hot(blank_lp, blank_stride, ids, val, n, T, K, blank, W, N, hw_ids, hw_lens, n_hotwords, boost, out_ids,
+                             out_len, out_score, out_matched, out_loglik, cap);
+  return PF_OK;
+  PF_CATCH
+}
+
 int pf_engine_set_align_targets(pf_engine* h, const int64_t* ids, const int32_t* len, int32_t B, int32_t cap) {
   PF_TRY
   std::shared_ptr<Engine> eh_ = E(h);
@@ -655,6 +704,24 @@ int pf_op_ctc_beam(pf_engine* h, const float* blank_lp, const int64_t* ids, cons
   if ((int64_t)B * T > 0) { NEED(blank_lp); NEED(ids); NEED(val); NEED(n); }
   std::lock_guard<std::mutex> lk(e->mutex());
   e->op_ctc_beam(blank_lp, ids, val, n, lens, B, T, K, blank, W, N, out_ids, out_len, out_score, cap, n_hyp);
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_op_ctc_beam_hot(pf_engine* h, const float* blank_lp, const int64_t* ids, const float* val, const int32_t* n, const int32_t* lens,
+                       int32_t B, int32_t T, int32_t K, int32_t blank, int32_t W, int32_t N, int64_t* out_ids, int32_t* out_len,
+                       double* out_score, int32_t cap, int32_t* n_hyp, const int32_t* hw_ids, const int32_t* hw_lens,
+                       int32_t n_hotwords, float boost, int32_t* out_matched, double* out_loglik) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  NEED(lens); NEED(out_ids); NEED(out_len); NEED(out_score); NEED(n_hyp); NEED(out_matched); NEED(out_loglik);
+  PF_CHECK(B >= 0 && T >= 0 && cap >= 1 && K >= 1 && K <= PF_TOPK_MAX && N >= 1 && N <= W && W <= PF_NBEST_MAX, PF_ERR_INVALID_ARG,
+           "ctc_beam: bad shape (1 <= N <= W <= 64, 1 <= K <= 8, cap >= 1)");
+  if ((int64_t)B * T > 0) { NEED(blank_lp); NEED(ids); NEED(val); NEED(n); }
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->op_ctc_beam_hot(blank_lp, ids, val, n, lens, B, T, K, blank, W, N, hw_ids, hw_lens, n_hotwords, boost, out_ids, out_len, out_score,
+                     out_matched, out_loglik, cap, n_hyp);
   return PF_OK;
   PF_CATCH
 }
@@ -1230,6 +1297,26 @@ int pf_recognizer_set_align(pf_recognizer* h, int32_t on) {
   std::shared_ptr<Recognizer> r = R(h);
   PF_CHECK(!r->disposed(), PF_ERR_DISPOSED, "OfflineRecognizer");
   r->SetAlign(on != 0);
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_recognizer_set_hotword_boost(pf_recognizer* h, float boost) {
+  PF_TRY
+  std::shared_ptr<Recognizer> r = R(h);
+  PF_CHECK(!r->disposed(), PF_ERR_DISPOSED, "OfflineRecognizer");
+  r->SetHotwordBoost(boost);
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_stream_alternative_hot(pf_stream* h, int32_t i, int32_t* hotword_tokens, double* loglik_sum) {
+  PF_TRY
+  Stream* s = S(h);
+  PF_CHECK(i >= 0 && i < (int32_t)s->Alternatives.size(), PF_ERR_INVALID_ARG, "alternative index out of range");
+  const Alternative& a = s->Alternatives[(size_t)i];
+  if (hotword_tokens) *hotword_tokens = a.hot_tokens;
+  if (loglik_sum) *loglik_sum = a.loglik_sum;
   return PF_OK;
   PF_CATCH
 }

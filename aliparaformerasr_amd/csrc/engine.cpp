@@ -1908,6 +1908,36 @@ void Engine::set_ctc_beam(int W, int N) {
   beam_n_ = N;
 }
 
+void Engine::set_ctc_hotwords(const int32_t* ids, const int32_t* lens, int n, float boost) {
+  PF_CHECK(mc_.kind_id() == 1 && !mc_.seaco, PF_ERR_UNSUPPORTED, "set_ctc_hotwords: only a SenseVoice model has a CTC head");
+  PF_CHECK(boost >= 0.f && boost <= 3.4028234e38f, PF_ERR_INVALID_ARG, "set_ctc_hotwords: the boost is finite and >= 0");
+  PF_CHECK(n >= 0, PF_ERR_INVALID_ARG, "set_ctc_hotwords: negative n_hotwords");
+  PF_CHECK(n == 0 || lens, PF_ERR_INVALID_ARG, "set_ctc_hotwords: null lens");
+  if (n == 0 || boost == 0.f) { hot_boost_ = 0.f; hot_A_ = 0; hot_ids_.clear(); hot_lens_.clear(); return; }
+  size_t total = 0;
+  for (int i = 0; i < n; ++i) { PF_CHECK(lens[i] >= 0, PF_ERR_INVALID_ARG, "set_ctc_hotwords: negative hot-word length"); total += (size_t)lens[i]; }
+  PF_CHECK(total == 0 || ids, PF_ERR_INVALID_ARG, "set_ctc_hotwords: null ids");
+  // the automaton is kept while the set is the same (by content): only the boost may have changed
+  if (hot_boost_ > 0.f && hot_lens_.size() == (size_t)n && hot_ids_.size() == total && std::equal(lens, lens + n, hot_lens_.begin()) &&
+      std::equal(ids, ids + total, hot_ids_.begin())) {
+    hot_boost_ = boost;
+    return;
+  }
+  HotwordGraph g;
+  build_hotword_graph(ids, lens, n, mc_.vocab, g);   // throws before anything changes
+  if (g.empty()) { hot_boost_ = 0.f; hot_A_ = 0; hot_ids_.clear(); hot_lens_.clear(); return; }
+  hot_ids_.assign(ids, ids + total);
+  hot_lens_.assign(lens, lens + n);
+  PF_HIP(hipSetDevice(device_));
+  PF_HIP(hipStreamSynchronize(stream_));            // a queued search may still read the table about to be replaced
+  const size_t V = g.tok_col.size(), words = V + g.table.size();
+  ensure(ws_hot_, words * 4);
+  PF_HIP(hipMemcpy(ws_hot_.p, g.tok_col.data(), V * 4, hipMemcpyHostToDevice));
+  PF_HIP(hipMemcpy((int32_t*)ws_hot_.p + V, g.table.data(), g.table.size() * 4, hipMemcpyHostToDevice));
+  hot_boost_ = boost;
+  hot_A_ = g.A;
+}
+
 float* Engine::score_buf(int64_t rows) {
   if (!decode_flags_) return nullptr;
   ensure(ws_score_, (size_t)std::max<int64_t>(rows, 1) * 4);
@@ -1946,7 +1976,10 @@ void Engine::queue_decode_results(int B, int L) {
       const int W = beam_w_, Nh = beam_n_, cap = L;
       const size_t bwords = HostBatchOut::beam_words(B, Nh, cap);
       const size_t nodes = (size_t)B * ((size_t)L * W + 1);
-      ensure(ws_beam_, bwords * 8 + (size_t)B * 4 + nodes * 8);
+      const bool hot = hot_boost_ > 0.f;
+      const size_t hwords = hot ? HostBatchOut::beam_hot_words(B, Nh) : 0;
+      const size_t tail4 = ((size_t)B + 2 * nodes + 1) / 2 * 2;              // len | nodes, kept a multiple of 8 bytes
+      ensure(ws_beam_, hot ? bwords * 8 + tail4 * 4 + hwords * 8 : bwords * 8 + (size_t)B * 4 + nodes * 8);
       last_.beam.resize(bwords);
       last_.beam_n = Nh;
       last_.beam_cap = cap;
@@ -1959,10 +1992,22 @@ void Engine::queue_decode_results(int B, int L) {
       int32_t* node_tok = node_par + nodes;
       PF_HIP(hipMemcpyAsync(len_d, len.data(), (size_t)B * 4, hipMemcpyHostToDevice, stream_));
       prof_begin("ctc_beam", 0);
-      launch_ctc_beam(stream_, logits_, logits_ld_, ids_o, val_o, n_o, len_d, B, L, K, 0, W, Nh, cap, node_par, node_tok, bids_o,
-                      blen_o, score_o, nhyp_o);
+      if (hot) {
+        // the biased form: the same outputs in the biased order, and loglik_sum | matched behind the node workspace
+        double* ll_o = (double*)((char*)ws_beam_.p + bwords * 8 + tail4 * 4);
+        int32_t* m_o = (int32_t*)(ll_o + (size_t)B * Nh);
+        const int32_t* tok_col = (const int32_t*)ws_hot_.p;
+        last_.beam_hot.resize(hwords);
+        launch_ctc_beam_hot(stream_, logits_, logits_ld_, ids_o, val_o, n_o, len_d, B, L, K, 0, W, Nh, cap, node_par, node_tok, tok_col,
+                            mc_.vocab, tok_col + mc_.vocab, hot_A_, hot_boost_, bids_o, blen_o, score_o, m_o, ll_o, nhyp_o);
+      } else {
+        launch_ctc_beam(stream_, logits_, logits_ld_, ids_o, val_o, n_o, len_d, B, L, K, 0, W, Nh, cap, node_par, node_tok, bids_o,
+                        blen_o, score_o, nhyp_o);
+      }
       prof_end("ctc_beam");
       PF_HIP(hipMemcpyAsync(last_.beam.data(), ws_beam_.p, bwords * 8, hipMemcpyDeviceToHost, stream_));
+      if (hot)
+        PF_HIP(hipMemcpyAsync(last_.beam_hot.data(), (char*)ws_beam_.p + bwords * 8 + tail4 * 4, hwords * 8, hipMemcpyDeviceToHost, stream_));
     }
   }
   if (decode_flags_ & PF_DECODE_ALIGN) {
@@ -2042,7 +2087,7 @@ void Engine::forward_device(const float* speech_dev, int B, int T, bool want_log
   last_.decode_flags = decode_flags_;
   last_.scores.clear(); last_.ctc.clear(); last_.ctc_cap = 0;
   last_.topk.clear(); last_.topk_k = 0;
-  last_.beam.clear(); last_.beam_n = 0; last_.beam_cap = 0;
+  last_.beam.clear(); last_.beam_n = 0; last_.beam_cap = 0; last_.beam_hot.clear();
   last_.align.clear(); last_.align_h = 0; last_.align_cap = 0;
   if (align_B_ != 0 && align_B_ != B) {             // before anything is launched; the targets are dropped
     const int want = align_B_;
@@ -2232,6 +2277,18 @@ void Engine::fetch_ctc_beam(int64_t* ids, int32_t* len, double* score, int32_t c
     for (int p = 0; p < k; ++p) dst[p] = src[p];
     std::fill(dst + k, dst + cap, (int64_t)-1);
   }
+}
+
+void Engine::fetch_ctc_beam_hot(int32_t* matched, double* loglik) {
+  PF_HIP(hipStreamSynchronize(stream_));
+  check_async_errors();
+  auto it = t_slots_find(uid_);
+  const HostBatchOut& r = it ? *it : last_;
+  PF_CHECK((r.decode_flags & PF_DECODE_CTC_BEAM) && !r.beam_hot.empty(), PF_ERR_INVALID_ARG,
+           "fetch_ctc_beam_hot: the last forward ran no biased beam search (PF_DECODE_CTC_BEAM with pf_engine_set_ctc_hotwords)");
+  const size_t hyp = (size_t)r.B * r.beam_n;
+  if (matched) std::memcpy(matched, r.beam_matched(), hyp * 4);
+  if (loglik) std::memcpy(loglik, r.beam_loglik(), hyp * 8);
 }
 
 void Engine::fetch_align(float* path_score, double* loglik, int32_t* ok, int32_t* len, int32_t* first, int32_t* last, float* tok_score,

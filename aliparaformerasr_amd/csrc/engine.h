@@ -178,6 +178,16 @@ class Engine {
   void fetch_ctc_beam(int64_t* ids, int32_t* len, double* score, int32_t cap, int32_t* n_hyp, int32_t* len_max, int32_t* N_out);
   void op_ctc_beam(const float* blank_lp, const int64_t* ids, const float* val, const int32_t* n, const int32_t* lens, int B, int T,
                    int K, int blank, int W, int N, int64_t* out_ids, int32_t* out_len, double* out_score, int cap, int32_t* n_hyp);
+  // hot words inside the search (paraformer_hip.h "CTC hot words"): the set of the forwards that follow, compiled into the
+  // automaton's table and uploaded here; n == 0 or boost == 0 clears it.  With a set installed CTC_BEAM launches the biased
+  // form of the kernel and fetch_ctc_beam_hot gives matched / loglik_sum beside fetch_ctc_beam's (biased) scores.
+  void set_ctc_hotwords(const int32_t* ids, const int32_t* lens, int n, float boost);
+  bool ctc_hotwords_on() const { return hot_boost_ > 0.f; }
+  void fetch_ctc_beam_hot(int32_t* matched, double* loglik);
+  void op_ctc_beam_hot(const float* blank_lp, const int64_t* ids, const float* val, const int32_t* n, const int32_t* lens, int B, int T,
+                       int K, int blank, int W, int N, const int32_t* hw_ids, const int32_t* hw_lens, int n_hw, float boost,
+                       int64_t* out_ids, int32_t* out_len, double* out_score, int32_t* out_matched, double* out_loglik, int cap,
+                       int32_t* n_hyp);
   // ALIGN (SenseVoice; implies SCORES): behind the other decode launches one kernel (k_ctcalign.hip) aligns the caller's
   // targets of this forward (set_align_targets; consumed) and, with CTC_BEAM, the beam's hypotheses to the log-prob rows
   void set_align_targets(const int64_t* ids, const int32_t* len, int B, int cap);
@@ -465,6 +475,10 @@ class Engine {
   // the arg-max form of a pipeline head: the top-k kernel reads the log-probs the arg-max leaves in place
   int beam_w_ = 16, beam_n_ = 16;    // W / N of PF_DECODE_CTC_BEAM
   DevBuf ws_beam_;                   // the beam result block (HostBatchOut::beam) | len [B] | prefix nodes; allocated with the flag only
+  float hot_boost_ = 0.f;            // > 0: a hot-word set is installed (set_ctc_hotwords); its table lives in ws_hot_
+  int hot_A_ = 0;                    // columns of the table
+  std::vector<int32_t> hot_ids_, hot_lens_;   // the installed set as given: a call with the same content keeps the table
+  DevBuf ws_hot_;                    // tok_col [V] | table [S, A]; allocated by set_ctc_hotwords only
   // PF_DECODE_ALIGN: the targets of the next forward (int32, [B, align_cap_]; align_B_ = 0: none) and those of the forward
   // being queued (alive until the next forward: the host-to-device copies may read them after the call returns)
   std::vector<int32_t> align_tgt_, align_len_, align_tgt_q_, align_len_q_;

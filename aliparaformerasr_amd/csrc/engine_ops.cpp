@@ -124,6 +124,63 @@ void Engine::op_ctc_beam(const float* blank_lp, const int64_t* ids, const float*
   for (size_t x = 0; x < hyp * cap; ++x) out_ids[x] = h_ids[x];
 }
 
+void Engine::op_ctc_beam_hot(const float* blank_lp, const int64_t* ids, const float* val, const int32_t* n, const int32_t* lens, int B,
+                             int T, int K, int blank, int W, int N, const int32_t* hw_ids, const int32_t* hw_lens, int n_hw, float boost,
+                             int64_t* out_ids, int32_t* out_len, double* out_score, int32_t* out_matched, double* out_loglik, int cap,
+                             int32_t* n_hyp) {
+  PF_CHECK(boost >= 0.f && boost <= 3.4028234e38f, PF_ERR_INVALID_ARG, "ctc_beam_hot: the boost is finite and >= 0");
+  HotwordGraph g;
+  build_hotword_graph(hw_ids, hw_lens, n_hw, hotword_vocab_bound(hw_ids, hw_lens, n_hw), g);
+  const size_t hyp = (size_t)B * N;
+  if (boost == 0.f || g.empty()) {                  // no bias: the launch of op_ctc_beam itself
+    op_ctc_beam(blank_lp, ids, val, n, lens, B, T, K, blank, W, N, out_ids, out_len, out_score, cap, n_hyp);
+    for (size_t x = 0; x < hyp; ++x) { out_matched[x] = 0; out_loglik[x] = out_score[x]; }
+    return;
+  }
+  PF_HIP(hipSetDevice(device_));
+  if (B == 0) return;
+  const size_t rows = (size_t)B * T, nodes = (size_t)B * ((size_t)T * W + 1);
+  const size_t Vh = g.tok_col.size(), tab = g.table.size();
+  // 8-byte items first: score | loglik | ids in; then the 4-byte ones
+  const size_t words4 = rows * K + rows + rows + (size_t)B + hyp * cap + hyp + hyp + (size_t)B + 2 * nodes + Vh + tab;
+  ensure(ws_tmp_, (2 * hyp + rows * K) * 8 + words4 * 4);
+  double* d_score = (double*)ws_tmp_.p;
+  double* d_ll = d_score + hyp;
+  int64_t* d_ids = (int64_t*)(d_ll + hyp);
+  float* d_val = (float*)(d_ids + rows * K);
+  float* d_lb = d_val + rows * K;
+  int32_t* d_n = (int32_t*)(d_lb + rows);
+  int32_t* d_len = d_n + rows;
+  int32_t* d_oids = d_len + B;
+  int32_t* d_olen = d_oids + hyp * cap;
+  int32_t* d_m = d_olen + hyp;
+  int32_t* d_nhyp = d_m + hyp;
+  int32_t* d_par = d_nhyp + B;
+  int32_t* d_tok = d_par + nodes;
+  int32_t* d_col = d_tok + nodes;
+  int32_t* d_tab = d_col + Vh;
+  if (rows > 0) {
+    PF_HIP(hipMemcpyAsync(d_ids, ids, rows * K * 8, hipMemcpyHostToDevice, stream_));
+    PF_HIP(hipMemcpyAsync(d_val, val, rows * K * 4, hipMemcpyHostToDevice, stream_));
+    PF_HIP(hipMemcpyAsync(d_lb, blank_lp, rows * 4, hipMemcpyHostToDevice, stream_));
+    PF_HIP(hipMemcpyAsync(d_n, n, rows * 4, hipMemcpyHostToDevice, stream_));
+  }
+  PF_HIP(hipMemcpyAsync(d_len, lens, (size_t)B * 4, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipMemcpyAsync(d_col, g.tok_col.data(), Vh * 4, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipMemcpyAsync(d_tab, g.table.data(), tab * 4, hipMemcpyHostToDevice, stream_));
+  launch_ctc_beam_hot(stream_, d_lb, 1, d_ids, d_val, d_n, d_len, B, T, K, blank, W, N, cap, d_par, d_tok, d_col, (int)Vh, d_tab, g.A,
+                      boost, d_oids, d_olen, d_score, d_m, d_ll, d_nhyp);
+  std::vector<int32_t> h_ids(hyp * cap);
+  if (hyp * cap > 0) PF_HIP(hipMemcpyAsync(h_ids.data(), d_oids, hyp * cap * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipMemcpyAsync(out_len, d_olen, hyp * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipMemcpyAsync(out_score, d_score, hyp * 8, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipMemcpyAsync(out_loglik, d_ll, hyp * 8, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipMemcpyAsync(out_matched, d_m, hyp * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipMemcpyAsync(n_hyp, d_nhyp, (size_t)B * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipStreamSynchronize(stream_));            // g's host arrays are read by the copies queued above until here
+  for (size_t x = 0; x < hyp * cap; ++x) out_ids[x] = h_ids[x];
+}
+
 void Engine::op_ctc_align(const float* lp, int B, int T, int V, int ld, const int32_t* tgt, const int32_t* tlen, const int32_t* lens,
                           int H, int cap, float* path_score, double* loglik, int32_t* ok, int32_t* first, int32_t* last,
                           float* tok_score) {

@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <map>
 #include <queue>
 #include <sstream>
 
@@ -522,20 +523,26 @@ struct BeamEntry {
   double pb, pnb;
   uint64_t hash;
   int node, par, tok, len;
+  int st, m;                 // hot words: automaton state and matched tokens of the prefix (0 / 0 without a set)
 };
 struct BeamCand {
-  double tot, pb, pnb;
-  int idx;
+  double tot, key, pb, pnb;  // key = tot + bias(prefix): what select orders by (tot itself without a set)
+  int idx, st, m;
 };
-}  // namespace
 
-int host_ctc_beam(const float* blank_lp, int64_t blank_stride, const int64_t* ids, const float* val, const int32_t* n, int T, int K,
-                  int blank, int W, int N, int64_t* out_ids, int32_t* out_len, double* out_score, int cap) {
+// the search of the definition; g == nullptr: the unbiased one (tests/ctcbeam_ref.py), else tests/ctcbeam_bias_ref.py
+int ctc_beam_impl(const float* blank_lp, int64_t blank_stride, const int64_t* ids, const float* val, const int32_t* n, int T, int K,
+                  int blank, int W, int N, const HotwordGraph* g, double boost, int64_t* out_ids, int32_t* out_len, double* out_score,
+                  int32_t* out_matched, double* out_loglik, int cap) {
   if (!out_ids || !out_len || !out_score || (T > 0 && (!blank_lp || !ids || !val || !n)))
     throw Error(PF_ERR_INVALID_ARG, "ctc_beam: null argument");
   if (T < 0 || K < 1 || K > PF_TOPK_MAX || N < 1 || N > W || W > PF_NBEST_MAX || cap < 0 || blank_stride < 1)
     throw Error(PF_ERR_INVALID_ARG, "ctc_beam: bad T / K / W / N / cap");
-  for (int h = 0; h < N; ++h) { out_len[h] = 0; out_score[h] = kNegInf; }
+  for (int h = 0; h < N; ++h) {
+    out_len[h] = 0; out_score[h] = kNegInf;
+    if (out_matched) out_matched[h] = 0;
+    if (out_loglik) out_loglik[h] = kNegInf;
+  }
   std::fill(out_ids, out_ids + (size_t)N * cap, (int64_t)-1);
   for (int t = 0; t < T; ++t) {
     if (n[t] < 0 || n[t] > K) throw Error(PF_ERR_INVALID_ARG, "ctc_beam: n[t] outside 0 .. K");
@@ -553,7 +560,8 @@ int host_ctc_beam(const float* blank_lp, int64_t blank_stride, const int64_t* id
     }
     return true;
   };
-  std::vector<BeamEntry> beam(1, BeamEntry{0.0, kNegInf, 0x243F6A8885A308D3ull, 0, -1, -1, 0}), next;
+  const int Vg = g ? (int)g->tok_col.size() : 0;
+  std::vector<BeamEntry> beam(1, BeamEntry{0.0, kNegInf, 0x243F6A8885A308D3ull, 0, -1, -1, 0, 0, 0}), next;
   std::vector<BeamCand> cand;
   std::vector<double> merged;
   const int K1 = K + 1;
@@ -563,13 +571,14 @@ int host_ctc_beam(const float* blank_lp, int64_t blank_stride, const int64_t* id
     const int nt = n[t];
     const double lb = (double)blank_lp[(size_t)t * blank_stride];
     const int nbeam = (int)beam.size();
-    cand.assign((size_t)nbeam * K1, BeamCand{kNegInf, kNegInf, kNegInf, 0});
+    cand.assign((size_t)nbeam * K1, BeamCand{kNegInf, kNegInf, kNegInf, kNegInf, 0, 0, 0});
     merged.assign((size_t)nbeam, kNegInf);
     for (int i = 0; i < nbeam; ++i) {
       const BeamEntry& p = beam[(size_t)i];
       const double tot = beam_lse(p.pb, p.pnb);
       BeamCand& st = cand[(size_t)i * K1];
       st.pb = tot + lb;
+      st.st = p.st; st.m = p.m;
       for (int r = 0; r < nt; ++r) {
         const int c = (int)id[r];
         if (c == blank || c < 0) continue;
@@ -583,8 +592,15 @@ int host_ctc_beam(const float* blank_lp, int64_t blank_stride, const int64_t* id
           const BeamEntry& e = beam[(size_t)q];
           if (e.len == p.len + 1 && e.tok == c && e.hash == h && same_prefix(e.par, p.node)) hit = q;
         }
-        if (hit >= 0) merged[(size_t)hit] = value;               // at most one extension meets one entry
-        else cand[(size_t)i * K1 + 1 + r].pnb = value;
+        if (hit >= 0) { merged[(size_t)hit] = value; continue; }   // at most one extension meets one entry
+        BeamCand& x = cand[(size_t)i * K1 + 1 + r];
+        x.pnb = value;
+        if (g) {
+          const int col = c < Vg ? g->tok_col[(size_t)c] : -1;
+          const int e = col >= 0 ? g->table[(size_t)p.st * g->A + col] : 0;
+          x.st = e & 0xFFFF;
+          x.m = p.m + ((e >> 16) & 0xFF);
+        }
       }
     }
     std::vector<int> live;
@@ -593,10 +609,11 @@ int host_ctc_beam(const float* blank_lp, int64_t blank_stride, const int64_t* id
       c.idx = j;
       if (j % K1 == 0) c.pnb = beam_lse(c.pnb, merged[(size_t)(j / K1)]);
       c.tot = beam_lse(c.pb, c.pnb);
+      c.key = g ? c.tot + boost * (double)(c.m + g->depth[(size_t)c.st]) : c.tot;
       if (c.tot > kNegInf) live.push_back(j);
     }
     std::sort(live.begin(), live.end(), [&](int a, int b) {
-      const double x = cand[(size_t)a].tot, y = cand[(size_t)b].tot;
+      const double x = cand[(size_t)a].key, y = cand[(size_t)b].key;
       return x != y ? x > y : a < b;
     });
     if ((int)live.size() > W) live.resize((size_t)W);
@@ -605,26 +622,156 @@ int host_ctc_beam(const float* blank_lp, int64_t blank_stride, const int64_t* id
       const BeamCand& c = cand[(size_t)j];
       const BeamEntry& p = beam[(size_t)(j / K1)];
       if (j % K1 == 0) {
-        next.push_back(BeamEntry{c.pb, c.pnb, p.hash, p.node, p.par, p.tok, p.len});
+        next.push_back(BeamEntry{c.pb, c.pnb, p.hash, p.node, p.par, p.tok, p.len, c.st, c.m});
       } else {
         const int tok = (int)id[j % K1 - 1];
         npar.push_back(p.node);
         ntok.push_back(tok);
-        next.push_back(BeamEntry{c.pb, c.pnb, beam_hash(p.hash, tok), (int)npar.size() - 1, p.node, tok, p.len + 1});
+        next.push_back(BeamEntry{c.pb, c.pnb, beam_hash(p.hash, tok), (int)npar.size() - 1, p.node, tok, p.len + 1, c.st, c.m});
       }
     }
     beam.swap(next);
   }
-  const int nh = std::min(N, (int)beam.size());
+  // finish: the pending part of the bias is revoked, the completed part stays; (score, beam rank) orders the output
+  const int nb = (int)beam.size();
+  std::vector<double> ll((size_t)nb), score((size_t)nb);
+  std::vector<int> order((size_t)nb);
+  for (int h = 0; h < nb; ++h) {
+    ll[(size_t)h] = beam_lse(beam[(size_t)h].pb, beam[(size_t)h].pnb);
+    score[(size_t)h] = g ? ll[(size_t)h] + boost * (double)beam[(size_t)h].m : ll[(size_t)h];
+    order[(size_t)h] = h;
+  }
+  if (g)
+    std::sort(order.begin(), order.end(), [&](int a, int b) {
+      return score[(size_t)a] != score[(size_t)b] ? score[(size_t)a] > score[(size_t)b] : a < b;
+    });
+  const int nh = std::min(N, nb);
   for (int h = 0; h < nh; ++h)
-    if (beam[(size_t)h].len > cap) throw Error(PF_ERR_CAPACITY, "ctc_beam: a hypothesis of " + std::to_string(beam[(size_t)h].len) + " tokens > cap");
+    if (beam[(size_t)order[(size_t)h]].len > cap)
+      throw Error(PF_ERR_CAPACITY, "ctc_beam: a hypothesis of " + std::to_string(beam[(size_t)order[(size_t)h]].len) + " tokens > cap");
   for (int h = 0; h < nh; ++h) {
-    const BeamEntry& e = beam[(size_t)h];
+    const int src = order[(size_t)h];
+    const BeamEntry& e = beam[(size_t)src];
     int node = e.node;
     for (int p = e.len - 1; p >= 0; --p) { out_ids[(size_t)h * cap + p] = ntok[(size_t)node]; node = npar[(size_t)node]; }
     out_len[h] = e.len;
-    out_score[h] = beam_lse(e.pb, e.pnb);
+    out_score[h] = score[(size_t)src];
+    if (out_matched) out_matched[h] = e.m;
+    if (out_loglik) out_loglik[h] = ll[(size_t)src];
   }
+  return nh;
+}
+}  // namespace
+
+int host_ctc_beam(const float* blank_lp, int64_t blank_stride, const int64_t* ids, const float* val, const int32_t* n, int T, int K,
+                  int blank, int W, int N, int64_t* out_ids, int32_t* out_len, double* out_score, int cap) {
+  return ctc_beam_impl(blank_lp, blank_stride, ids, val, n, T, K, blank, W, N, nullptr, 0.0, out_ids, out_len, out_score, nullptr,
+                       nullptr, cap);
+}
+
+// ------------------------------------------------------------------ hot words: context graph ---------------
+void build_hotword_graph(const int32_t* ids, const int32_t* lens, int n, int V, HotwordGraph& g) {
+  if (n < 0 || V < 1 || (n > 0 && !lens)) throw Error(PF_ERR_INVALID_ARG, "hotword_graph: bad n / V / lens");
+  size_t total = 0;
+  for (int i = 0; i < n; ++i) {
+    if (lens[i] < 0) throw Error(PF_ERR_INVALID_ARG, "hotword_graph: negative hot-word length");
+    total += (size_t)lens[i];
+  }
+  if (total > 0 && !ids) throw Error(PF_ERR_INVALID_ARG, "hotword_graph: null ids");
+  for (size_t x = 0; x < total; ++x)
+    if (ids[x] <= 0 || ids[x] >= V) throw Error(PF_ERR_INVALID_ARG, "hotword_graph: an id outside [1, V)");
+  for (int i = 0; i < n; ++i)
+    if (lens[i] > PF_HOTWORD_LEN_MAX)
+      throw Error(PF_ERR_CAPACITY, "hotword_graph: a hot word of " + std::to_string(lens[i]) + " ids > PF_HOTWORD_LEN_MAX");
+  g = HotwordGraph();
+  g.tok_col.assign((size_t)V, -1);
+  std::vector<int32_t> toks(ids, ids + total);
+  std::sort(toks.begin(), toks.end());
+  toks.erase(std::unique(toks.begin(), toks.end()), toks.end());
+  const int A = (int)toks.size();
+  for (int a = 0; a < A; ++a) g.tok_col[(size_t)toks[(size_t)a]] = a;
+  // the trie: children as (node, column) -> node; is_end marks a node that spells a whole hot word
+  std::map<std::pair<int, int>, int> child;
+  std::vector<int> depth(1, 0), parent(1, -1), pcol(1, -1);
+  std::vector<char> is_end(1, 0);
+  size_t off = 0;
+  for (int i = 0; i < n; ++i) {
+    int u = 0;
+    for (int p = 0; p < lens[i]; ++p) {
+      const int col = g.tok_col[(size_t)ids[off + p]];
+      auto it = child.find({u, col});
+      if (it == child.end()) {
+        if ((int)depth.size() >= PF_HOTWORD_STATES_MAX)
+          throw Error(PF_ERR_CAPACITY, "hotword_graph: more than PF_HOTWORD_STATES_MAX states");
+        const int v = (int)depth.size();
+        child[{u, col}] = v;
+        depth.push_back(depth[(size_t)u] + 1);
+        parent.push_back(u);
+        pcol.push_back(col);
+        is_end.push_back(0);
+        u = v;
+      } else {
+        u = it->second;
+      }
+    }
+    if (lens[i] > 0) is_end[(size_t)u] = 1;
+    off += (size_t)lens[i];
+  }
+  const int S = (int)depth.size();
+  if ((size_t)S * (size_t)A * 4 > (size_t)PF_HOTWORD_TABLE_BYTES_MAX)
+    throw Error(PF_ERR_CAPACITY, "hotword_graph: a table of " + std::to_string(S) + " x " + std::to_string(A) + " entries > PF_HOTWORD_TABLE_BYTES_MAX");
+  g.S = S;
+  g.A = A;
+  g.depth.assign(depth.begin(), depth.end());
+  // the full Aho-Corasick transition delta(u, a) = the longest suffix of path(u) + a that is a trie path, breadth first
+  // (nodes were numbered along the words, not by depth, so the order is made here); endlen(v): the longest hot word that
+  // is a suffix of path(v), i.e. that ends v or a node on v's failure chain
+  std::vector<int32_t> delta((size_t)S * A, 0);
+  std::vector<int> fail((size_t)S, 0), endlen((size_t)S, 0), bfs;
+  bfs.reserve((size_t)S);
+  bfs.push_back(0);
+  for (auto& kv : child)
+    if (kv.first.first == 0) delta[(size_t)kv.first.second] = kv.second;
+  std::vector<std::vector<std::pair<int, int>>> kids((size_t)S);
+  for (auto& kv : child) kids[(size_t)kv.first.first].push_back({kv.first.second, kv.second});
+  for (size_t head = 0; head < bfs.size(); ++head) {
+    const int u = bfs[head];
+    if (u != 0) {
+      const int f = parent[(size_t)u] == 0 ? 0 : delta[(size_t)fail[(size_t)parent[(size_t)u]] * A + pcol[(size_t)u]];
+      fail[(size_t)u] = f;
+      endlen[(size_t)u] = is_end[(size_t)u] ? depth[(size_t)u] : endlen[(size_t)f];
+      for (int a = 0; a < A; ++a) delta[(size_t)u * A + a] = delta[(size_t)f * A + a];
+      for (auto& k : kids[(size_t)u]) delta[(size_t)u * A + k.first] = k.second;
+    }
+    for (auto& k : kids[(size_t)u]) bfs.push_back(k.second);
+  }
+  g.table.assign((size_t)S * A, 0);
+  for (size_t x = 0; x < (size_t)S * A; ++x) {
+    const int v = delta[x];
+    g.table[x] = endlen[(size_t)v] > 0 ? (endlen[(size_t)v] << 16) : (v | (depth[(size_t)v] << 24));
+  }
+}
+
+// one past the largest id of a set given without a vocabulary size (ids below 1 are left to the builder's refusal)
+int hotword_vocab_bound(const int32_t* ids, const int32_t* lens, int n) {
+  int64_t total = 0;
+  for (int i = 0; i < n && lens; ++i) total += std::max(lens[i], 0);
+  int mx = 0;
+  for (int64_t x = 0; x < total && ids; ++x) mx = std::max(mx, ids[x]);
+  if (mx >= (1 << 24)) throw Error(PF_ERR_INVALID_ARG, "ctc_beam_hot: a hot-word id outside [1, 2^24)");
+  return mx + 1;
+}
+
+int host_ctc_beam_hot(const float* blank_lp, int64_t blank_stride, const int64_t* ids, const float* val, const int32_t* n, int T, int K,
+                      int blank, int W, int N, const int32_t* hw_ids, const int32_t* hw_lens, int n_hw, float boost, int64_t* out_ids,
+                      int32_t* out_len, double* out_score, int32_t* out_matched, double* out_loglik, int cap) {
+  if (!out_matched || !out_loglik) throw Error(PF_ERR_INVALID_ARG, "ctc_beam_hot: null argument");
+  if (!(boost >= 0.f) || std::isinf(boost)) throw Error(PF_ERR_INVALID_ARG, "ctc_beam_hot: the boost is finite and >= 0");
+  HotwordGraph g;
+  build_hotword_graph(hw_ids, hw_lens, n_hw, hotword_vocab_bound(hw_ids, hw_lens, n_hw), g);
+  const bool on = boost > 0.f && !g.empty();
+  const int nh = ctc_beam_impl(blank_lp, blank_stride, ids, val, n, T, K, blank, W, N, on ? &g : nullptr, (double)boost, out_ids, out_len,
+                               out_score, out_matched, out_loglik, cap);
   return nh;
 }
 

@@ -81,6 +81,30 @@ int host_nbest(const float* val, const int32_t* n, int L, int K, int n_free, int
 int host_ctc_beam(const float* blank_lp, int64_t blank_stride, const int64_t* ids, const float* val, const int32_t* n, int T, int K,
                   int blank, int W, int N, int64_t* out_ids, int32_t* out_len, double* out_score, int cap);
 
+// ---- hot-word boosting inside the beam search (paraformer_hip.h "CTC hot words"; the definition is tests/ctcbeam_bias_ref.py) ----
+// The context graph of a hot-word set, compiled into a deterministic table: a trie over the set with Aho-Corasick failure
+// links folded in.  State 0 is the root.  From state u on token c: col = tok_col[c] (-1: not a hot-word token: root, nothing
+// completes), e = table[u * A + col]: e & 0xFFFF the next state, (e >> 16) & 0xFF the length of the hot word that completes
+// (then the next state is the root), e >> 24 the depth of the next state.  depth[u] is the length of the pending partial match in u.
+// n words, word i = lens[i] ids at ids[sum of lens before i]; an empty word is dropped, a duplicate harmless.
+// PF_ERR_INVALID_ARG for an id outside [1, V); PF_ERR_CAPACITY for a word longer than PF_HOTWORD_LEN_MAX, more than
+// PF_HOTWORD_STATES_MAX states or a table over PF_HOTWORD_TABLE_BYTES_MAX.
+struct HotwordGraph {
+  int S = 0, A = 0;                 // states (trie nodes, root included), distinct hot-word tokens
+  std::vector<int32_t> tok_col;     // [V]
+  std::vector<int32_t> table;       // [S, A]
+  std::vector<int32_t> depth;       // [S]
+  bool empty() const { return A == 0; }
+};
+void build_hotword_graph(const int32_t* ids, const int32_t* lens, int n, int V, HotwordGraph& g);
+// host_ctc_beam with the biased select and finish of the definition: out_score = lse(pb, pnb) + boost * matched in the
+// re-ordered list, out_matched [N] (0), out_loglik [N] (-inf) next to it.  boost is widened to float64; with boost == 0 or a
+// set without a non-empty word this IS host_ctc_beam (matched 0, loglik = score).
+int hotword_vocab_bound(const int32_t* ids, const int32_t* lens, int n);   // one past the largest id; ids are below 2^24
+int host_ctc_beam_hot(const float* blank_lp, int64_t blank_stride, const int64_t* ids, const float* val, const int32_t* n, int T, int K,
+                      int blank, int W, int N, const int32_t* hw_ids, const int32_t* hw_lens, int n_hw, float boost,
+                      int64_t* out_ids, int32_t* out_len, double* out_score, int32_t* out_matched, double* out_loglik, int cap);
+
 // ---- CTC forced alignment of one utterance and one target (paraformer_hip.h "CTC forced alignment"; tests/ctcalign_ref.py) ----
 // The host twin of k_ctcalign.hip: lp [T, ld] log-prob rows (V read per row), y [U] ids in [1, V) (PF_ERR_INVALID_ARG
 // otherwise; U > PF_ALIGN_MAX_TOKENS is PF_ERR_CAPACITY).  *path_score: the float32 Viterbi score, *loglik: the float64 log of

@@ -18,6 +18,15 @@
 // the beam and was made again hangs off a new node while a descendant of the old one may still be in the beam.  The
 // merge test therefore compares token sequences: a 64-bit hash of the sequence is the filter, then both chains are
 // walked until they meet in one node (the usual case: at once; chains of different length never meet).
+//
+// Hot words (kBias; the definition is tests/ctcbeam_bias_ref.py): a beam entry also carries its state in the
+// hot-word automaton and the tokens m its prefix has matched.  An extension looks its (state, token) up in the table the host
+// compiled (hostutil.cpp build_hotword_graph) — one read, issued before the merge scan and independent of it; a stay
+// candidate inherits.  The select orders by key = total + boost * (m + pending depth) while pb / pnb stay unbiased, and after
+// the last frame one more rank-by-count over (total + boost * m, beam rank) gives the output order.  The kBias = false form
+// is the kernel as it was: every addition sits behind `if constexpr (kBias)`.
+#include <type_traits>
+
 #include "kernels.h"
 
 namespace pf {
@@ -60,17 +69,32 @@ __device__ inline bool beam_same_prefix(const int32_t* npar, const int32_t* ntok
 
 }  // namespace
 
-template <int kBeamThreads>
+// what the biased form reads and writes beyond the unbiased one; an empty argument in the kBias = false form
+struct BeamHotArgs {
+  const int32_t* tok_col;   // [V]: column of a hot-word token, -1 elsewhere
+  const int32_t* table;     // [S, A]: next state | completed length << 16 | depth of the next state << 24
+  int V, A;
+  double boost;
+  int32_t* out_matched;     // [B, N]
+  double* out_loglik;       // [B, N]
+};
+struct BeamNoArgs {};
+
+template <int kBeamThreads, bool kBias>
 __global__ __launch_bounds__(kBeamThreads) void ctc_beam_kernel(const float* blank_lp, int64_t blank_stride, const int64_t* ids,
                                                                 const float* val, const int32_t* n, const int32_t* len, int T,
                                                                 int K, int blank, int W, int N, int cap, int32_t* node_par,
                                                                 int32_t* node_tok, int32_t* out_ids, int32_t* out_len,
-                                                                double* out_score, int32_t* n_hyp) {
+                                                                double* out_score, int32_t* n_hyp,
+                                                                std::conditional_t<kBias, BeamHotArgs, BeamNoArgs> hot) {
   __shared__ BeamBuf bm[2];
   __shared__ double c_tot[kBeamCand];
   __shared__ double m_val[kBeamW];                 // what the frame's merged extensions add to entry q's stay candidate
   __shared__ double f_val[2][PF_TOPK_MAX], f_lb[2];
   __shared__ int f_id[2][PF_TOPK_MAX], f_n[2];
+  // kBias: per beam entry the automaton state (with its depth in the top byte, as the table packs it) and the matched tokens,
+  // double-buffered like the beam; the output order of the final pass
+  __shared__ int h_st[kBias ? 2 : 1][kBias ? kBeamW : 1], h_m[kBias ? 2 : 1][kBias ? kBeamW : 1], h_ord[kBias ? kBeamW : 1];
 
   const int b = blockIdx.x, tid = threadIdx.x;
   const int nb = min(max(len[b], 0), T);
@@ -83,6 +107,7 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_kernel(const float* bla
     bm[0].pb[0] = 0.0; bm[0].pnb[0] = kNegInf; bm[0].hash[0] = 0x243F6A8885A308D3ull;
     bm[0].node[0] = 0; bm[0].par[0] = -1; bm[0].tok[0] = -1; bm[0].len[0] = 0;
     npar[0] = -1; ntok[0] = -1;
+    if constexpr (kBias) { h_st[0][0] = 0; h_m[0][0] = 0; }
   }
   if (tid < kBeamW) m_val[tid] = kNegInf;
   int n_nx = 0;                                    // n of frame t + 1, known one frame ahead so that its list can be prefetched
@@ -118,12 +143,14 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_kernel(const float* bla
     const int i = j / K1, s = j - i * K1;
     // 1. the candidate; an extension that meets a beam entry leaves its value in m_val
     double pb1 = kNegInf, pnb1 = kNegInf;
+    int st1 = 0, m1 = 0;                           // kBias: the candidate's automaton state and matched tokens
     if (j < NC) {
       const double pb = B0.pb[i], pnb = B0.pnb[i];
       const double tot = beam_lse(pb, pnb);
       const int e = B0.tok[i], li = B0.len[i];
       if (s == 0) {
         pb1 = tot + lb;
+        if constexpr (kBias) { st1 = h_st[cur][i]; m1 = h_m[cur][i]; }
         if (li > 0)
           for (int r = 0; r < nt; ++r)
             if (f_id[cur][r] == e) pnb1 = pnb + f_val[cur][r];
@@ -132,6 +159,12 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_kernel(const float* bla
         if (c != blank && c >= 0) {
           const double base = (li > 0 && c == e) ? pb : tot;
           if (base != kNegInf) {
+            if constexpr (kBias) {                 // issued ahead of the scan below, which does not depend on it
+              const int col = c < hot.V ? hot.tok_col[c] : -1;
+              const int e = col >= 0 ? hot.table[(h_st[cur][i] & 0xFFFF) * hot.A + col] : 0;
+              st1 = e & (int)0xFF00FFFF;
+              m1 = h_m[cur][i] + ((e >> 16) & 0xFF);
+            }
             const double value = base + f_val[cur][s - 1];
             const unsigned long long h = beam_hash(B0.hash[i], c);
             const int me = B0.node[i];
@@ -158,11 +191,13 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_kernel(const float* bla
     }
     __syncthreads();
     // 2. totals
-    double my = kNegInf;
+    double my = kNegInf, key = kNegInf;            // the unbiased total decides who lives, the key who ranks where
     if (j < NC) {
       if (s == 0) pnb1 = beam_lse(pnb1, m_val[i]);
       my = beam_lse(pb1, pnb1);
-      c_tot[j] = my;
+      if constexpr (kBias) key = my + hot.boost * (double)(m1 + (int)((unsigned)st1 >> 24));
+      else key = my;
+      c_tot[j] = key;
     }
     __syncthreads();
     // 3. the slot of a candidate is the number of candidates ordered before it
@@ -172,11 +207,12 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_kernel(const float* bla
     for (int k = 0; k < NC; ++k) {
       const double tk = c_tot[k];
       nlive += tk > kNegInf;
-      rank += (tk > my) || (tk == my && k < j);
+      rank += (tk > key) || (tk == key && k < j);
     }
     if (j < NC && my > kNegInf && rank < W) {
       const int r = rank;
       B1.pb[r] = pb1; B1.pnb[r] = pnb1;
+      if constexpr (kBias) { h_st[nxt][r] = st1; h_m[nxt][r] = m1; }
       if (s == 0) {
         B1.hash[r] = B0.hash[i]; B1.node[r] = B0.node[i]; B1.par[r] = B0.par[i]; B1.tok[r] = B0.tok[i]; B1.len[r] = B0.len[i];
       } else {
@@ -198,25 +234,57 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_kernel(const float* bla
   // the first N entries, ids by walking the chain back; every slot is written
   const BeamBuf& F = bm[nb & 1];
   const int nh = bad ? 0 : min(N, nbeam);
+  int src = tid;                                   // the beam entry that output slot tid shows
+  if constexpr (kBias) {
+    // finish: score = total + boost * m (the pending part is revoked); a slot is again a count, over (score, beam rank)
+    const int fb = nb & 1;
+    double sc = kNegInf;
+    if (tid < nbeam && !bad) sc = beam_lse(F.pb[tid], F.pnb[tid]) + hot.boost * (double)h_m[fb][tid];
+    if (tid < kBeamW) c_tot[tid] = sc;
+    __syncthreads();
+    if (tid < nbeam && !bad) {
+      int rank = 0;
+      for (int q = 0; q < nbeam; ++q) {
+        const double tq = c_tot[q];
+        rank += (tq > sc) || (tq == sc && q < tid);
+      }
+      h_ord[rank] = tid;
+    }
+    __syncthreads();
+    if (tid < nh) src = h_ord[tid];
+  }
   if (tid < N) {
     const int64_t o = (int64_t)b * N + tid;
     if (tid < nh) {
-      const int L = F.len[tid];
-      int node = F.node[tid];
+      const int L = F.len[src];
+      int node = F.node[src];
       for (int p = L - 1; p >= 0; --p) {
         if (p < cap) out_ids[o * cap + p] = ntok[node];
         node = npar[node];
       }
       out_len[o] = L;
-      out_score[o] = beam_lse(F.pb[tid], F.pnb[tid]);
+      const double ll = beam_lse(F.pb[src], F.pnb[src]);
+      if constexpr (kBias) {
+        const int m = h_m[nb & 1][src];
+        out_score[o] = ll + hot.boost * (double)m;
+        hot.out_matched[o] = m;
+        hot.out_loglik[o] = ll;
+      } else {
+        out_score[o] = ll;
+      }
     } else {
       out_len[o] = 0;
       out_score[o] = kNegInf;
+      if constexpr (kBias) { hot.out_matched[o] = 0; hot.out_loglik[o] = kNegInf; }
     }
   }
   for (int x = tid; x < N * cap; x += kBeamThreads) {
     const int h = x / cap, p = x - h * cap;
-    const int L = h < nh ? F.len[h] : 0;
+    int L = 0;
+    if (h < nh) {
+      if constexpr (kBias) L = F.len[h_ord[h]];
+      else L = F.len[h];
+    }
     if (p >= L) out_ids[(int64_t)b * N * cap + x] = -1;
   }
   if (tid == 0) n_hyp[b] = nh;
@@ -229,11 +297,31 @@ void launch_ctc_beam(hipStream_t s, const float* blank_lp, int64_t blank_stride,
            PF_ERR_INVALID_ARG, "ctc_beam: 1 <= N <= W <= 64, 1 <= K <= 8");
   if (B == 0) return;
   if (W * (K + 1) <= 256)
-    hipLaunchKernelGGL(ctc_beam_kernel<256>, dim3((unsigned)B), dim3(256), 0, s, blank_lp, blank_stride, ids, val, n, len, T, K,
-                       blank, W, N, cap, node_par, node_tok, out_ids, out_len, out_score, n_hyp);
+    hipLaunchKernelGGL((ctc_beam_kernel<256, false>), dim3((unsigned)B), dim3(256), 0, s, blank_lp, blank_stride, ids, val, n, len, T,
+                       K, blank, W, N, cap, node_par, node_tok, out_ids, out_len, out_score, n_hyp, BeamNoArgs{});
   else
-    hipLaunchKernelGGL(ctc_beam_kernel<1024>, dim3((unsigned)B), dim3(1024), 0, s, blank_lp, blank_stride, ids, val, n, len, T, K,
-                       blank, W, N, cap, node_par, node_tok, out_ids, out_len, out_score, n_hyp);
+    hipLaunchKernelGGL((ctc_beam_kernel<1024, false>), dim3((unsigned)B), dim3(1024), 0, s, blank_lp, blank_stride, ids, val, n, len,
+                       T, K, blank, W, N, cap, node_par, node_tok, out_ids, out_len, out_score, n_hyp, BeamNoArgs{});
+  PF_HIP(hipGetLastError());
+}
+
+void launch_ctc_beam_hot(hipStream_t s, const float* blank_lp, int64_t blank_stride, const int64_t* ids, const float* val,
+                         const int32_t* n, const int32_t* len, int B, int T, int K, int blank, int W, int N, int cap,
+                         int32_t* node_par, int32_t* node_tok, const int32_t* tok_col, int V, const int32_t* table, int A, float boost,
+                         int32_t* out_ids, int32_t* out_len, double* out_score, int32_t* out_matched, double* out_loglik,
+                         int32_t* n_hyp) {
+  PF_CHECK(N >= 1 && N <= W && W <= kBeamW && K >= 1 && K <= PF_TOPK_MAX && T >= 0 && cap >= 0 && blank_stride >= 1,
+           PF_ERR_INVALID_ARG, "ctc_beam: 1 <= N <= W <= 64, 1 <= K <= 8");
+  PF_CHECK(tok_col && table && V >= 1 && A >= 1 && boost > 0.f && boost <= 3.4028234e38f, PF_ERR_INVALID_ARG,
+           "ctc_beam_hot: a compiled hot-word table and a finite boost > 0");
+  if (B == 0) return;
+  const BeamHotArgs hot{tok_col, table, V, A, (double)boost, out_matched, out_loglik};
+  if (W * (K + 1) <= 256)
+    hipLaunchKernelGGL((ctc_beam_kernel<256, true>), dim3((unsigned)B), dim3(256), 0, s, blank_lp, blank_stride, ids, val, n, len, T,
+                       K, blank, W, N, cap, node_par, node_tok, out_ids, out_len, out_score, n_hyp, hot);
+  else
+    hipLaunchKernelGGL((ctc_beam_kernel<1024, true>), dim3((unsigned)B), dim3(1024), 0, s, blank_lp, blank_stride, ids, val, n, len,
+                       T, K, blank, W, N, cap, node_par, node_tok, out_ids, out_len, out_score, n_hyp, hot);
   PF_HIP(hipGetLastError());
 }
 

@@ -366,6 +366,14 @@ void launch_topk(hipStream_t s, const float* x, int64_t rows, int V, int ldx, in
 void launch_ctc_beam(hipStream_t s, const float* blank_lp, int64_t blank_stride, const int64_t* ids, const float* val,
                      const int32_t* n, const int32_t* len, int B, int T, int K, int blank, int W, int N, int cap, int32_t* node_par,
                      int32_t* node_tok, int32_t* out_ids, int32_t* out_len, double* out_score, int32_t* n_hyp);
+// The biased form (hot words; the definition is tests/ctcbeam_bias_ref.py): tok_col [V] / table [S, A] as build_hotword_graph
+// leaves them (device copies), boost finite and > 0.  The hypotheses come in the biased order with score = total + boost *
+// matched; out_matched [B, N] (0) and out_loglik [B, N] float64 (-inf) hold m and the unbiased total: every slot is written.
+void launch_ctc_beam_hot(hipStream_t s, const float* blank_lp, int64_t blank_stride, const int64_t* ids, const float* val,
+                         const int32_t* n, const int32_t* len, int B, int T, int K, int blank, int W, int N, int cap,
+                         int32_t* node_par, int32_t* node_tok, const int32_t* tok_col, int V, const int32_t* table, int A, float boost,
+                         int32_t* out_ids, int32_t* out_len, double* out_score, int32_t* out_matched, double* out_loglik,
+                         int32_t* n_hyp);
 // ------------------------------------------------------------------ CTC forced alignment -------
 // Per job (b, h) the best CTC alignment of the target tgt[b, h, 0 .. tlen[b, h]) to the log-prob rows lp[(b * T + t) * ld + v],
 // t < min(max(len[b], 0), T), v < V, and the float64 log of the sum over all of its alignments (k_ctcalign.hip; the definition

@@ -554,6 +554,13 @@ void Recognizer::SetCtcBeam(int N, int W, int K) {
   }
 }
 
+void Recognizer::SetHotwordBoost(float boost) {
+  if (!(boost >= 0.f) || boost > 3.4028234e38f) throw Error(PF_ERR_INVALID_ARG, "SetHotwordBoost: the boost is finite and >= 0");
+  if (engine_kind_ != "sensevoicesmall" && boost > 0.f)
+    throw Error(PF_ERR_UNSUPPORTED, "SetHotwordBoost: only a SenseVoice model has a CTC head (SeACo biases through its own decoder)");
+  hot_boost_ = boost;
+}
+
 void Recognizer::SetNBest(int N, int K) {
   if (N < 0 || N > PF_NBEST_MAX || K < 0 || K > PF_TOPK_MAX) throw Error(PF_ERR_INVALID_ARG, "SetNBest: N is 0 .. 64, K is 0 .. 8");
   if (N == 0) {
@@ -986,6 +993,29 @@ void Recognizer::Forward(const std::vector<Stream*>& streams) {
         for (int j = 0; j < 10; ++j) pad.push_back(j < (int)w.size() ? w[j] : 0);
       e->set_hotwords(pad.data(), (int)hw.size());
     }
+    if (sv && !mc.seaco) {
+      // hot words inside the beam search (SetHotwordBoost beside SetCtcBeam): the SeACo rule above for where they come from,
+      // without the [sos_eos_id] terminator entry GetHotwords appends; the engine keeps its automaton while the set is the same
+      const float boost = hot_boost_;
+      if (boost > 0.f && (dflags & PF_DECODE_CTC_BEAM)) {
+        std::vector<std::vector<int32_t>> hw;
+        for (Stream* s : streams) {
+          if (s->hotwords_null) throw Error(PF_ERR_RECOGNITION, "Value cannot be null (Hotwords)");
+          for (auto& w : s->Hotwords) hw.push_back(w);
+        }
+        if (hw.empty()) hw = hotwords_;
+        std::vector<int32_t> flat, lens;
+        for (auto& w : hw) {
+          if (w.size() == 1 && w[0] == 1) continue;
+          flat.insert(flat.end(), w.begin(), w.end());
+          lens.push_back((int32_t)w.size());
+        }
+        e->set_ctc_hotwords(flat.data(), lens.data(), (int)lens.size(), boost);
+      } else if (e->ctc_hotwords_on()) {
+        e->set_ctc_hotwords(nullptr, nullptr, 0, 0.f);
+      }
+    }
+    const bool hot_on = sv && !mc.seaco && (dflags & PF_DECODE_CTC_BEAM) && e->ctc_hotwords_on();
     e->drop_thread_result();              // this call's result is read back under the same lease, not from a slot
     bool any_target = false;
     if (dflags & PF_DECODE_ALIGN) {
@@ -1073,6 +1103,7 @@ void Recognizer::Forward(const std::vector<Stream*>& streams) {
     }
     // the beam search's hypotheses (SetCtcBeam): ids [B, Nb, b_cap], lengths, float64 totals
     std::vector<int64_t> b_ids; std::vector<int32_t> b_len, b_nhyp; std::vector<double> b_score;
+    std::vector<int32_t> b_hot; std::vector<double> b_llsum;      // with hot words: matched tokens, the unbiased totals
     int Nb = 0, b_cap = 0;
     if (dflags & PF_DECODE_CTC_BEAM) {
       int32_t len_max = 0, nb = 0;
@@ -1082,6 +1113,10 @@ void Recognizer::Forward(const std::vector<Stream*>& streams) {
       b_cap = std::max(len_max, 1);
       b_ids.resize((size_t)B * Nb * b_cap); b_len.resize((size_t)B * Nb); b_score.resize((size_t)B * Nb);
       e->fetch_ctc_beam(b_ids.data(), b_len.data(), b_score.data(), b_cap, nullptr, nullptr, nullptr);
+      if (hot_on) {
+        b_hot.resize((size_t)B * Nb); b_llsum.resize((size_t)B * Nb);
+        e->fetch_ctc_beam_hot(b_hot.data(), b_llsum.data());
+      }
     }
     // forced alignments (SetAlign): job 0 is the stream's own target when any stream of the batch has one, then the hypotheses
     std::vector<float> a_path, a_tok; std::vector<double> a_ll; std::vector<int32_t> a_ok, a_len, a_first, a_last;
@@ -1165,6 +1200,7 @@ void Recognizer::Forward(const std::vector<Stream*>& streams) {
         Alternative a;
         a.score = b_score[x];
         a.ctc = true;
+        if (!b_hot.empty()) { a.hot_tokens = b_hot[x]; a.loglik_sum = b_llsum[x]; }
         a.ids.assign(b_ids.begin() + x * b_cap, b_ids.begin() + x * b_cap + b_len[x]);
         if (Ha >= a_hc + Nb) {
           const size_t j = (size_t)b * Ha + a_hc + i;

@@ -84,6 +84,10 @@ struct Alternative {
   // it or when the alignment is not ok) and the log of the sum over ALL of its alignments (NaN without it)
   std::vector<int32_t> ts;
   double loglik = std::nan("");
+  // with SetHotwordBoost beside SetCtcBeam: the hot-word tokens the labeling completed (score = loglik_sum + boost * these) and
+  // the unbiased log of the alignments the search summed (0 / NaN without it)
+  int hot_tokens = 0;
+  double loglik_sum = std::nan("");
   ResultEntity res;
 };
 // time_stamp_lfr6_onnx (OfflineRecognizer.cs:200-302); throws PF_ERR_RECOGNITION where the C#
@@ -186,6 +190,9 @@ class Recognizer : public std::enable_shared_from_this<Recognizer> {
   // SenseVoice only (paraformer_hip.h "CTC forced alignment"): PF_DECODE_ALIGN on every engine — a stream's target (AlignIds)
   // is aligned to its audio, and with SetCtcBeam every Alternative gets its own times and log-likelihood
   void SetAlign(bool on);
+  // SenseVoice only (paraformer_hip.h "CTC hot words"): boost per matched hot-word token inside the beam search of SetCtcBeam
+  // (inert without it); 0 = off.  The hot words of a batch: the union of its streams' Hotwords, else the hot-word file's.
+  void SetHotwordBoost(float s);
   bool disposed() const { return disposed_.load(); }
   // engine 0 (nullptr once disposed): what pf_recognizer_engine hands out; callers lock engine->mutex() themselves
   std::shared_ptr<Engine> engine() { std::lock_guard<std::mutex> lk(mu_); return engines_.empty() ? nullptr : engines_[0]; }
@@ -285,6 +292,7 @@ class Recognizer : public std::enable_shared_from_this<Recognizer> {
   std::atomic<int> nbest_n_{0};
   std::atomic<int> topk_k_{4};
   std::atomic<int> beam_w_{16}, beam_n_{16};
+  std::atomic<float> hot_boost_{0.f};   // SetHotwordBoost
   std::atomic<bool> beam_on_{false};
   std::atomic<bool> align_on_{false};
   int extra_flags() const { return (nbest_n_ > 0 ? PF_DECODE_TOPK : 0) | (beam_on_ ? PF_DECODE_CTC_BEAM : 0) | (align_on_ ? PF_DECODE_ALIGN : 0); }

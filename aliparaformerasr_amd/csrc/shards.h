@@ -60,6 +60,11 @@ struct HostBatchOut { // results of a forward, host side
   const int32_t* beam_ids() const { return (const int32_t*)(beam.data() + (size_t)B * beam_n); }
   const int32_t* beam_len() const { return beam_ids() + (size_t)B * beam_n * beam_cap; }
   const int32_t* beam_nhyp() const { return beam_len() + (size_t)B * beam_n; }
+  // the biased search's extras, one block: loglik_sum [B, N] float64 | matched [B, N] int32; empty when the search ran unbiased
+  std::vector<int64_t> beam_hot;
+  static size_t beam_hot_words(int B, int N) { return (size_t)B * N + ((size_t)B * N * 4 + 7) / 8; }
+  const double* beam_loglik() const { return (const double*)beam_hot.data(); }
+  const int32_t* beam_matched() const { return (const int32_t*)(beam_hot.data() + (size_t)B * beam_n); }
   // CTC forced alignment as the kernel leaves it, one block (the float64 item first, for its alignment):
   // loglik [B, H] float64 | path_score [B, H] fp32 | ok [B, H] | len [B, H] | first [B, H, cap] | last | tok_score fp32
   std::vector<int64_t> align;

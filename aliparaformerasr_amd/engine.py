@@ -63,9 +63,12 @@ class CtcBeamResult:
     """The labelings a CTC prefix beam search kept (PF_DECODE_CTC_BEAM): n_hyp [B]; ids [B, N, cap] int64 (-1 past a
     hypothesis' length), len [B, N], score [B, N] float64 (the log of the summed alignments; -inf past n_hyp[b])."""
 
-    def __init__(self, n_hyp, ids, len_, score):
+    def __init__(self, n_hyp, ids, len_, score, matched=None, loglik_sum=None):
         self.n_hyp, self.ids, self.len, self.score = n_hyp, ids, len_, score
         self.N = score.shape[-1]
+        # hot words (Engine.set_ctc_hotwords / host_ctc_beam_hot / op_ctc_beam_hot), else None: matched [B, N] int32, the
+        # hot-word tokens a labeling completed; loglik_sum [B, N] float64 = score - boost * matched, the unbiased log of the sum
+        self.matched, self.loglik_sum = matched, loglik_sum
 
     def hyps(self, b=0):
         """[(ids tuple, score)] of utterance b, best first."""
@@ -97,6 +100,60 @@ def host_ctc_beam(blank_lp, ids, val, n, W, n_best=None, blank=0, cap=None, blan
     N.check(N.load().pf_host_ctc_beam(_fp(lb), int(blank_stride), _i64p(y), _fp(v), _i32p(nn), T, K, int(blank), int(W), int(n_best),
                                       _i64p(oi), _i32p(ol), _dp(sc), cap, _i32p(nh)))
     return CtcBeamResult(nh, oi, ol, sc)
+
+
+def _hot_arrays(hotwords):
+    """A hot-word set (sequences of ids) as the C entry points take it: flat int32 ids, int32 lengths."""
+    ids = np.ascontiguousarray([c for w in hotwords for c in w], dtype=np.int32).reshape(-1)
+    lens = np.ascontiguousarray([len(w) for w in hotwords], dtype=np.int32).reshape(-1)
+    return ids, lens
+
+
+class HotwordGraph:
+    """The automaton of a hot-word set (pf_host_hotword_graph): S states, A columns, tok_col [V], table [S, A], depth [S]."""
+
+    def __init__(self, hotwords, V):
+        ids, lens = _hot_arrays(hotwords)
+        lib = N.load()
+        s, a = C.c_int32(), C.c_int32()
+        N.check(lib.pf_host_hotword_graph(_i32p(ids), _i32p(lens), len(lens), int(V), s, a, None, None, 0, None, 0))
+        self.S, self.A = s.value, a.value
+        self.tok_col = np.zeros(int(V), np.int32)
+        self.table = np.zeros((self.S, self.A), np.int32)
+        self.depth = np.zeros(self.S, np.int32)
+        N.check(lib.pf_host_hotword_graph(_i32p(ids), _i32p(lens), len(lens), int(V), s, a, _i32p(self.tok_col), _i32p(self.table),
+                                          self.table.size, _i32p(self.depth), self.S))
+
+    def step(self, state, token):
+        """(next state, completed length) from `state` on `token`."""
+        col = int(self.tok_col[token]) if 0 <= token < self.tok_col.shape[0] else -1
+        if col < 0:
+            return 0, 0
+        e = int(self.table[state, col])
+        return e & 0xFFFF, (e >> 16) & 0xFF
+
+
+def host_ctc_beam_hot(blank_lp, ids, val, n, W, hotwords, boost, n_best=None, blank=0, cap=None, blank_stride=1) -> CtcBeamResult:
+    """host_ctc_beam with a hot-word set (sequences of ids in [1, V)) and a boost >= 0 (pf_host_ctc_beam_hot): the biased
+    search of ONE utterance in host code -> CtcBeamResult with B = 1, matched and loglik_sum filled."""
+    y = np.ascontiguousarray(ids, dtype=np.int64)
+    v = _f32(val)
+    nn = np.ascontiguousarray(n, dtype=np.int32)
+    lb = _f32(blank_lp).reshape(-1)
+    T, K = y.shape
+    n_best = W if n_best is None else n_best
+    cap = max(T, 1) if cap is None else cap
+    hi, hl = _hot_arrays(hotwords)
+    oi = np.zeros((1, max(n_best, 0), cap), np.int64)
+    ol = np.zeros((1, max(n_best, 0)), np.int32)
+    sc = np.zeros((1, max(n_best, 0)), np.float64)
+    om = np.zeros((1, max(n_best, 0)), np.int32)
+    oll = np.zeros((1, max(n_best, 0)), np.float64)
+    nh = np.zeros(1, np.int32)
+    N.check(N.load().pf_host_ctc_beam_hot(_fp(lb), int(blank_stride), _i64p(y), _fp(v), _i32p(nn), T, K, int(blank), int(W), int(n_best),
+                                          _i64p(oi), _i32p(ol), _dp(sc), cap, _i32p(nh), _i32p(hi), _i32p(hl), len(hl), float(boost),
+                                          _i32p(om), _dp(oll)))
+    return CtcBeamResult(nh, oi, ol, sc, om, oll)
 
 
 class AlignResult:
@@ -216,7 +273,7 @@ def _fetch_topk(lib, h, B, L):
     return TopkResult(ids, val, n)
 
 
-def _fetch_ctc_beam(lib, h, B, n_best):
+def _fetch_ctc_beam(lib, h, B, n_best, hot=False):
     nh = np.zeros(B, np.int32)
     mx = C.c_int32()
     N.check(lib.pf_fetch_ctc_beam(h, None, None, None, 0, _i32p(nh), mx))
@@ -225,7 +282,12 @@ def _fetch_ctc_beam(lib, h, B, n_best):
     ln = np.zeros((B, n_best), np.int32)
     sc = np.zeros((B, n_best), np.float64)
     N.check(lib.pf_fetch_ctc_beam(h, _i64p(ids), _i32p(ln), _dp(sc), cap, None, None))
-    return CtcBeamResult(nh, ids, ln, sc)
+    if not hot:
+        return CtcBeamResult(nh, ids, ln, sc)
+    m = np.zeros((B, n_best), np.int32)
+    ll = np.zeros((B, n_best), np.float64)
+    N.check(lib.pf_fetch_ctc_beam_hot(h, _i32p(m), _dp(ll)))
+    return CtcBeamResult(nh, ids, ln, sc, m, ll)
 
 
 def _fetch_align(lib, h, B):
@@ -270,7 +332,7 @@ def _collect_result(lib, fetch_fn, call, B, want_logits, decode=None):
         topk = _fetch_topk(lib, decode[0], B, L)
     beam = None
     if decode is not None and decode[1] & N.PF_DECODE_CTC_BEAM:
-        beam = _fetch_ctc_beam(lib, decode[0], B, decode[2])
+        beam = _fetch_ctc_beam(lib, decode[0], B, decode[2], len(decode) > 3 and decode[3])
     align = None
     if decode is not None and decode[1] & N.PF_DECODE_ALIGN:
         align = _fetch_align(lib, decode[0], B)
@@ -297,6 +359,7 @@ class Engine:
         self.kind, self.vocab, self.feat_dim = kind.value, vocab.value, feat.value
         self._decode = 0
         self._beam_n = 16
+        self._hot = False
 
     def close(self):
         if getattr(self, "_h", None):
@@ -335,7 +398,7 @@ class Engine:
     # ---- forward ------------------------------------------------------------
     def _collect(self, call, B, want_logits):
         return _collect_result(self._lib, lambda o: self._lib.pf_fetch(self._h, o), call, B, want_logits,
-                               (self._h, self._decode, self._beam_n))
+                               (self._h, self._decode, self._beam_n, self._hot))
 
     def set_decode(self, flags: int):
         """Decoding extras of the forwards that follow (_native.PF_DECODE_SCORES | PF_DECODE_CTC; 0 = off, the reference
@@ -382,6 +445,37 @@ class Engine:
         self._beam_n = int(n_best)
 
     host_ctc_beam = staticmethod(host_ctc_beam)
+    host_ctc_beam_hot = staticmethod(host_ctc_beam_hot)
+
+    def set_ctc_hotwords(self, hotwords, boost: float):
+        """The hot-word set (sequences of token ids in [1, V)) and the boost per matched token (>= 0) of the forwards that
+        follow (pf_engine_set_ctc_hotwords; SenseVoice only).  An empty set or boost 0 clears it.  With a set installed
+        PF_DECODE_CTC_BEAM runs the biased search: BatchResult.beam comes in the biased order with matched and loglik_sum."""
+        hi, hl = _hot_arrays(hotwords)
+        N.check(self._lib.pf_engine_set_ctc_hotwords(self._h, _i32p(hi), _i32p(hl), len(hl), float(boost)))
+        self._hot = float(np.float32(boost)) > 0 and any(len(w) > 0 for w in hotwords)
+
+    def op_ctc_beam_hot(self, blank_lp, ids, val, n, lens, W, hotwords, boost, n_best=None, blank=0, cap=None, out=None) -> CtcBeamResult:
+        """op_ctc_beam with a hot-word set and a boost: the biased form of the kernel on caller data.  out = (ids, len, score,
+        n_hyp, matched [B, N] int32, loglik_sum [B, N] float64): write into these arrays."""
+        y = np.ascontiguousarray(ids, dtype=np.int64)
+        v = _f32(val)
+        nn = np.ascontiguousarray(n, dtype=np.int32)
+        lb = _f32(blank_lp)
+        ln = np.ascontiguousarray(lens, dtype=np.int32)
+        B, T, K = y.shape
+        n_best = W if n_best is None else n_best
+        cap = max(T, 1) if cap is None else cap
+        hi, hl = _hot_arrays(hotwords)
+        if out is None:
+            out = (np.zeros((B, max(n_best, 0), cap), np.int64), np.zeros((B, max(n_best, 0)), np.int32),
+                   np.zeros((B, max(n_best, 0)), np.float64), np.zeros(B, np.int32), np.zeros((B, max(n_best, 0)), np.int32),
+                   np.zeros((B, max(n_best, 0)), np.float64))
+        oi, ol, sc, nh, om, oll = out
+        N.check(self._lib.pf_op_ctc_beam_hot(self._h, _fp(lb), _i64p(y), _fp(v), _i32p(nn), _i32p(ln), B, T, K, int(blank), int(W),
+                                             int(n_best), _i64p(oi), _i32p(ol), _dp(sc), cap, _i32p(nh), _i32p(hi), _i32p(hl),
+                                             len(hl), float(boost), _i32p(om), _dp(oll)))
+        return CtcBeamResult(nh, oi, ol, sc, om, oll)
 
     def op_ctc_beam(self, blank_lp, ids, val, n, lens, W, n_best=None, blank=0, cap=None, out=None) -> CtcBeamResult:
         """The pipeline's beam search kernel on caller data: blank_lp [B, T], ids / val [B, T, K], n [B, T], lens [B].

@@ -1,7 +1,7 @@
 """Command-line harness mirroring AliParaformerAsr.Examples (`-type offline` and `-type online`).
 
     python -m aliparaformerasr_amd.examples -type offline -method batch -base <dir> -model <name> \
-        [-accuracy int8] [-threads 2] [-decode ctc|frames] [-intake host|device] [-nbest N [-topk K] [-beam W]] [-align FILE|beam] -files a.wav b.wav
+        [-accuracy int8] [-threads 2] [-decode ctc|frames] [-intake host|device] [-nbest N [-topk K] [-beam W [-hotboost S]]] [-align FILE|beam] -files a.wav b.wav
     python -m aliparaformerasr_amd.examples -type online -method one -base <dir> -model <name> -files a.wav
 
 Mirrors (file:line in /root/reference/AliParaformerAsr.Examples):
@@ -28,6 +28,8 @@ OfflineStream.AddPcm raw: decode, down-mix and resample run on the device and gi
 hypotheses, one `nbest[i] score:<sum of log-probs> text:<text>` line each, best first; line 0 is the result itself.
 `-nbest N -beam W` (offline, SenseVoice models; OfflineRecognizer.SetCtcBeam) prints the N best labelings of a CTC prefix
 beam search of width W in the same form; the score is the log of the summed alignments.
+`-hotboost S` (with `-nbest N -beam W`; OfflineRecognizer.SetHotwordBoost) biases that search towards the model directory's
+`hotword*.txt` by S per matched token; each `nbest[i]` line then ends in ` hot:<matched tokens> loglik_sum:<unbiased score>`.
 `-align FILE` (offline, SenseVoice models; OfflineRecognizer.SetAlign) aligns a known text to each input file: FILE holds one
 line of space-separated token ids per file of `-files`, in their order (an empty line: no target; ids, not text — the
 tokenizer is not part of this package), and under each result line goes
@@ -141,7 +143,8 @@ def _pairs(ts) -> str:
 def _nbest_lines(stream, align=False) -> list:
     out = []
     for i, a in enumerate(stream.Alternatives):
-        out.append('nbest[%d] score:%.6f text:%s' % (i, a.Score, a.Text))
+        hot = '' if a.LogLikSum is None else ' hot:%d loglik_sum:%.6f' % (a.HotwordTokens, a.LogLikSum)
+        out.append('nbest[%d] score:%.6f text:%s%s' % (i, a.Score, a.Text, hot))
         if align and a.LogLik is not None:
             out.append('align[%d] loglik:%.6f pairs:%s' % (i, a.LogLik, _pairs(a.Timestamps)))
     return out
@@ -168,7 +171,7 @@ def read_align_file(path: str) -> list:
 
 def offline_recognizer(method="one", model="paraformer-seaco-large-zh-timestamp-onnx-offline", accuracy="int8",
                        threads=2, files=None, base=None, out=sys.stdout, decode="frames", intake="host", nbest=0, topk=4,
-                       beam=0, align=None):
+                       beam=0, align=None, hotboost=0.0):
     from .offline_recognizer import OfflineRecognizer
     base = base or os.getcwd()
     sel = select_model_files(base, model, accuracy)
@@ -181,6 +184,8 @@ def offline_recognizer(method="one", model="paraformer-seaco-large-zh-timestamp-
         rec.SetDecode(ctc=True)
     if nbest and beam:
         rec.SetCtcBeam(nbest, beam, topk)
+        if hotboost:
+            rec.SetHotwordBoost(hotboost)
     elif nbest:
         rec.SetNBest(nbest, topk)
     targets = None
@@ -387,6 +392,15 @@ def parse_args(argv, env=None):
             if not lo <= v <= hi:
                 raise ValueError("The %s value must be an integer from %d to %d" % (a[1:], lo, hi))
             cfg[a[1:]] = v
+        elif a == "-hotboost":
+            try:
+                i += 1
+                v = float(argv[i])
+            except (IndexError, ValueError):
+                v = -1.0
+            if not (0.0 <= v < float("inf")):
+                raise ValueError("The hotboost value must be a finite number >= 0")
+            cfg["hotboost"] = v
         elif a == "-align":
             i += 1
             if i >= len(argv) or argv[i].startswith("-"):
@@ -415,6 +429,8 @@ def parse_args(argv, env=None):
         raise ValueError("-beam goes with -nbest")
     if "beam" in cfg and cfg["beam"] < cfg["nbest"]:
         raise ValueError("The beam value must not be smaller than the nbest value")
+    if "hotboost" in cfg and "beam" not in cfg:
+        raise ValueError("-hotboost needs -nbest N -beam W")
     if "nbest" in cfg and cfg["recognizerType"] != "offline":
         raise ValueError("-nbest is an offline option")
     if "align" in cfg and cfg["recognizerType"] != "offline":
@@ -438,7 +454,8 @@ def main(argv=None):
     elif cfg["recognizerType"] == "offline":
         offline_recognizer(cfg["methodType"], cfg["modelName"], cfg["modelAccuracy"], cfg["threads"], cfg["files"],
                            cfg["modelBasePath"] or None, decode=cfg.get("decode", "frames"), intake=cfg.get("intake", "host"),
-                           nbest=cfg.get("nbest", 0), topk=cfg.get("topk", 4), beam=cfg.get("beam", 0), align=cfg.get("align"))
+                           nbest=cfg.get("nbest", 0), topk=cfg.get("topk", 4), beam=cfg.get("beam", 0), align=cfg.get("align"),
+                           hotboost=cfg.get("hotboost", 0.0))
     else:
         print("the recognizer type must be online or offline")
         return 2

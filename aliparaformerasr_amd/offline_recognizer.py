@@ -76,6 +76,10 @@ class Alternative:
     # (empty without), and the log of the sum over ALL of its alignments (None without)
     Timestamps: List[List[int]] = field(default_factory=list)
     LogLik: Optional[float] = None
+    # OfflineRecognizer.SetHotwordBoost beside SetCtcBeam: the hot-word tokens the labeling completed (Score = LogLikSum + boost *
+    # HotwordTokens) and the unbiased log of the alignments the search summed (0 / None when the search ran unbiased)
+    HotwordTokens: int = 0
+    LogLikSum: Optional[float] = None
 
 
 @dataclass
@@ -226,7 +230,10 @@ class OfflineStream:
                 toks.append((t.value or b"").decode("utf-8"))
             pt, nts, ll = C.POINTER(C.c_int32)(), C.c_int32(), C.c_double()
             _ck(self._lib.pf_stream_alternative_timestamps(self._h, i, C.byref(pt), nts, C.byref(ll)))
-            out.append(Alternative(Ids=[p[m] for m in range(k.value)], Score=sc.value,
+            hm, hs = C.c_int32(), C.c_double()
+            _ck(self._lib.pf_stream_alternative_hot(self._h, i, hm, hs))
+            out.append(Alternative(Ids=[p[m] for m in range(k.value)], Score=sc.value, HotwordTokens=hm.value,
+                                   LogLikSum=None if hs.value != hs.value else hs.value,
                                    Text=(txt.value or b"").decode("utf-8"), Tokens=toks,
                                    Timestamps=[[pt[2 * j], pt[2 * j + 1]] for j in range(nts.value)],
                                    LogLik=None if ll.value != ll.value else ll.value))
@@ -361,6 +368,15 @@ class OfflineRecognizer:
         (1 .. 8) best ids per frame.  Tokens, Timestamps, Scores and the result text stay as they are; entry 0 is the
         search's best, which need not be the result."""
         _ck(self._lib.pf_recognizer_set_ctc_beam(self._h, int(N), int(W), int(K)))
+
+    def SetHotwordBoost(self, s: float) -> None:
+        """SenseVoice models: hot-word boosting inside the beam search of SetCtcBeam (inert without it; 0 turns it off).  A
+        labeling earns s per token while it spells a hot word, keeps it when the word completes and loses it when the match
+        breaks.  The hot words of a GetResults call are the union of its streams' Hotwords (token ids), else the recognizer's
+        hot-word file, tokenised per character as the reference does — set stream.Hotwords ids where sentencepiece pieces are
+        needed.  Alternatives then come in the biased order, each with Score, HotwordTokens and LogLikSum; Text and Tokens stay
+        as they are."""
+        _ck(self._lib.pf_recognizer_set_hotword_boost(self._h, float(s)))
 
     def SetAlign(self, on: bool = True) -> None:
         """SenseVoice models: CTC forced alignment on the device for every GetResults that follows (off by default).  A

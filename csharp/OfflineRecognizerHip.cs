@@ -185,6 +185,9 @@ namespace AliParaformerAsr.Hip
                     if (nts > 0) Marshal.Copy(pt, flat, 0, 2 * nts);
                     for (int j = 0; j < nts; j++) a.Timestamps.Add(new[] { flat[2 * j], flat[2 * j + 1] });
                     a.LogLik = ll;
+                    ParaformerHip.Check(ParaformerHip.pf_stream_alternative_hot(Handle, i, out int hot, out double llSum));
+                    a.HotwordTokens = hot;
+                    a.LogLikSum = llSum;
                     r.Add(a);
                 }
                 return r;
@@ -258,6 +261,10 @@ namespace AliParaformerAsr.Hip
         /// without) and the log of the sum over all of its alignments (NaN without).</summary>
         public List<int[]> Timestamps = new List<int[]>();
         public double LogLik = double.NaN;
+        /// <summary>SetHotwordBoost beside SetCtcBeam: the hot-word tokens the labeling completed (Score = LogLikSum + boost *
+        /// HotwordTokens) and the unbiased log of the alignments the search summed (0 / NaN when the search ran unbiased).</summary>
+        public int HotwordTokens;
+        public double LogLikSum = double.NaN;
     }
 
     /// <summary>OfflineStream.Alignment: where each id of a known text lies in the audio.  Ok = false: the target does not fit the
@@ -306,6 +313,14 @@ namespace AliParaformerAsr.Hip
         /// descending Score (the log of the summed alignments), found with beam width W (0 = max(16, N)) over the K (1 .. 8) best
         /// ids per frame.  Tokens, Timestamps, Scores and the result text stay as they are.</summary>
         public void SetCtcBeam(int N, int W = 0, int K = 4) => ParaformerHip.Check(ParaformerHip.pf_recognizer_set_ctc_beam(_r, N, W, K));
+
+        /// <summary>Not in the reference: SenseVoice models only (SeACo biases through its own decoder).  Hot-word boosting inside
+        /// the beam search of SetCtcBeam (inert without it; 0 turns it off): a labeling earns s per token while it spells a hot word,
+        /// keeps it when the word completes and loses it when the match breaks.  The hot words of a GetResults call are the union of
+        /// its streams' Hotwords (token ids), else the hot-word file's, tokenised per character as the reference does — set
+        /// stream.Hotwords ids where sentencepiece pieces are needed.  Alternatives then come in the biased order, each with Score,
+        /// HotwordTokens and LogLikSum; Text and Tokens stay as they are.</summary>
+        public void SetHotwordBoost(float s) => ParaformerHip.Check(ParaformerHip.pf_recognizer_set_hotword_boost(_r, s));
 
         /// <summary>Not in the reference: SenseVoice models only.  CTC forced alignment on the device for every GetResults that
         /// follows (off by default): a stream with a target (OfflineStream.SetAlignIds) gets OfflineStream.Alignment, and with

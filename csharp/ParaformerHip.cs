@@ -102,6 +102,22 @@ namespace AliParaformerAsr.Native
         [DllImport(Lib)] internal static extern int pf_host_ctc_beam(float[] blankLp, long blankStride, long[] ids, float[] val, int[] n, int T, int K,
                                                                     int blank, int W, int N, [Out] long[] outIds, [Out] int[] outLen,
                                                                     [Out] double[] outScore, int cap, out int nHyp);
+        // CTC hot words (additions to ABI 6): a hot-word set and a boost per matched token inside the beam search (SenseVoice); with a
+        // set installed PF_DECODE_CTC_BEAM runs the biased search: score = loglik_sum + boost * matched, in the biased order
+        internal const int PF_HOTWORD_STATES_MAX = 4096, PF_HOTWORD_LEN_MAX = 64, PF_HOTWORD_TABLE_BYTES_MAX = 16 * 1024 * 1024;
+        [DllImport(Lib)] internal static extern int pf_host_hotword_graph(int[]? ids, int[]? lens, int nHotwords, int V, out int nStates, out int nCols,
+                                                                         [Out] int[]? tokCol, [Out] int[]? table, long tableCap,
+                                                                         [Out] int[]? depth, int depthCap);
+        [DllImport(Lib)] internal static extern int pf_engine_set_ctc_hotwords(IntPtr e, int[]? ids, int[]? lens, int nHotwords, float boost);
+        [DllImport(Lib)] internal static extern int pf_fetch_ctc_beam_hot(IntPtr e, [Out] int[]? matched, [Out] double[]? loglikSum);
+        [DllImport(Lib)] internal static extern int pf_host_ctc_beam_hot(float[] blankLp, long blankStride, long[] ids, float[] val, int[] n, int T, int K,
+                                                                        int blank, int W, int N, [Out] long[] outIds, [Out] int[] outLen,
+                                                                        [Out] double[] outScore, int cap, out int nHyp, int[]? hwIds, int[]? hwLens,
+                                                                        int nHotwords, float boost, [Out] int[] outMatched, [Out] double[] outLoglik);
+        [DllImport(Lib)] internal static extern int pf_op_ctc_beam_hot(IntPtr e, float[] blankLp, long[] ids, float[] val, int[] n, int[] lens, int B,
+                                                                      int T, int K, int blank, int W, int N, [Out] long[] outIds, [Out] int[] outLen,
+                                                                      [Out] double[] outScore, int cap, [Out] int[] nHyp, int[]? hwIds, int[]? hwLens,
+                                                                      int nHotwords, float boost, [Out] int[] outMatched, [Out] double[] outLoglik);
         // CTC forced alignment (additions to ABI 6): PF_DECODE_ALIGN (SenseVoice; implies SCORES) aligns the targets set for the next
         // forward, and with PF_DECODE_CTC_BEAM the beam's hypotheses, to the log-prob rows: Viterbi path and log-likelihood per job
         internal const int PF_DECODE_ALIGN = 32;
@@ -170,6 +186,8 @@ namespace AliParaformerAsr.Native
         [DllImport(Lib)] internal static extern int pf_stream_alignment(IntPtr s, out IntPtr beginEnd, out IntPtr tokScore, out int n, out float pathScore,
                                                                        out double loglik, out int ok);
         [DllImport(Lib)] internal static extern int pf_stream_alternative_timestamps(IntPtr s, int i, out IntPtr beginEnd, out int n, out double loglik);
+        [DllImport(Lib)] internal static extern int pf_recognizer_set_hotword_boost(IntPtr r, float boost);
+        [DllImport(Lib)] internal static extern int pf_stream_alternative_hot(IntPtr s, int i, out int hotwordTokens, out double loglikSum);
         [DllImport(Lib)] internal static extern int pf_stream_token_alternatives(IntPtr s, out IntPtr ids, out IntPtr val, out int nTokens, out int K);
         [DllImport(Lib)] internal static extern int pf_stream_num_alternatives(IntPtr s, out int n);
         [DllImport(Lib)] internal static extern int pf_stream_alternative(IntPtr s, int i, out IntPtr ids, out int nIds, out double score,

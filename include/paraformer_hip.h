@@ -283,6 +283,58 @@ int pf_host_ctc_beam(const float* blank_lp, int64_t blank_stride, const int64_t*
                      int32_t K, int32_t blank, int32_t W, int32_t N, int64_t* out_ids, int32_t* out_len, double* out_score,
                      int32_t cap, int32_t* n_hyp);
 
+/* ---- CTC hot words (additions to ABI 6; nothing is launched or allocated without an installed set) ----------------------
+   Shallow fusion of a hot-word set into the CTC beam search above: a hypothesis earns a bonus per token while it spells a
+   hot word, keeps it when the word completes and loses it when the match breaks.  SenseVoice only; SeACo has its bias decoder.
+   INPUTS: everything the beam search takes, a set of H hot words (sequences of ids in [1, V); blank is id 0) and a boost s
+   (float32, finite, s >= 0, widened to float64).
+   MATCHED TOKENS of a label sequence y: walk y left to right keeping the SEGMENT read since the last completion (empty at the
+   start, m = 0).  After each token, if one or more hot words are a suffix of the segment, the longest one completes:
+   m += its length and the segment is emptied.  At the end d(y) is the length of the longest suffix of the segment that is a
+   PROPER prefix of some hot word (the pending partial match; 0 when there is none).  Matches do not overlap: of the hot
+   words `ab` and `abc` only `ab` can ever complete, so a hot-word set should be prefix-free (nothing is special-cased).
+     bias(y) = double(s) * (m(y) + d(y))       bonus(y) = double(s) * m(y)
+   each ONE float64 product of the widened boost by an integer.
+   SEARCH: the beam search above with exactly two changes.
+     select   a candidate's key is total + bias(its prefix); a candidate whose total is -inf is still discarded; the W best
+              by key stay, ties to the smaller candidate index; the stored pb / pnb remain unbiased (equal prefixes have equal
+              bias, so folding a merged extension into the stay candidate stays valid).
+     finish   after the last frame each entry gets score = lse(pb, pnb) + bonus(prefix) (the pending part is revoked); the
+              entries are re-ordered by descending score, ties to the smaller beam rank; the first N are the hypotheses:
+              ids, length, score, matched = m(prefix), loglik_sum = lse(pb, pnb) = the unbiased log of the summed alignments.
+   s = 0 or an empty set IS the unbiased search, bit for bit.  Only ids in a frame's top-k list can be boosted (the
+   candidates are the K <= 8 listed ids).  The definition in Python is tests/ctcbeam_bias_ref.py.
+   AUTOMATON (pf_host_hotword_graph): a trie over the set with Aho-Corasick failure links, compiled into a deterministic
+   table.  State 0 is the root.  From state u on token c: col = tok_col[c]; col < 0 (not a hot-word token): root, nothing
+   completes; else e = table[u * A + col]: next state e & 0xFFFF, completed length (e >> 16) & 0xFF (then the next state is the root), e >> 24 = depth[next state].
+   depth[u] = d of a sequence that ends in u.  *n_states = S (trie nodes, root included), *n_cols = A (distinct hot-word
+   tokens); tok_col [V], table [S * A] (table_cap entries), depth [S] (depth_cap entries) are optional: call with NULL to size.
+   An empty hot word is dropped, a duplicate is harmless.  PF_ERR_INVALID_ARG: an id <= 0 or >= V.  PF_ERR_CAPACITY: more than
+   PF_HOTWORD_STATES_MAX states, a hot word longer than PF_HOTWORD_LEN_MAX ids, a table over PF_HOTWORD_TABLE_BYTES_MAX, or
+   table_cap / depth_cap too small (sizes filled in). */
+#define PF_HOTWORD_STATES_MAX 4096
+#define PF_HOTWORD_LEN_MAX 64
+#define PF_HOTWORD_TABLE_BYTES_MAX (16 * 1024 * 1024)
+int pf_host_hotword_graph(const int32_t* ids, const int32_t* lens, int32_t n_hotwords, int32_t V, int32_t* n_states, int32_t* n_cols,
+                          int32_t* tok_col, int32_t* table, int64_t table_cap, int32_t* depth, int32_t depth_cap);
+/* The set of the forwards that FOLLOW on this engine: n_hotwords words, word i = lens[i] ids at ids[sum of the lens before].
+   SenseVoice only (PF_ERR_UNSUPPORTED otherwise).  n_hotwords == 0 or boost == 0 (or only empty words) clears it.  The table
+   is built and uploaded once here.  With a set installed a forward with PF_DECODE_CTC_BEAM runs the biased search (there is no
+   decode bit of its own); pf_fetch_ctc_beam then returns the biased order and score, PF_DECODE_ALIGN aligns those hypotheses;
+   token_ids, pf_fetch_scores, pf_fetch_ctc and pf_fetch_topk are what they are without the set.  PF_ERR_INVALID_ARG: a
+   negative, infinite or NaN boost, an id outside [1, V); PF_ERR_CAPACITY as pf_host_hotword_graph (the installed set stays). */
+int pf_engine_set_ctc_hotwords(pf_engine* e, const int32_t* ids, const int32_t* lens, int32_t n_hotwords, float boost);
+/* matched [B, N] int32 (0 past n_hyp) and loglik_sum [B, N] float64 (-inf past n_hyp) of the last forward's hypotheses, each
+   optional, in pf_fetch_ctc_beam's order: score - boost * matched == loglik_sum bit for bit.  Slot rules as pf_fetch_ctc_beam
+   (call it before the pf_fetch that takes the ids).  PF_ERR_INVALID_ARG when that forward ran unbiased. */
+int pf_fetch_ctc_beam_hot(pf_engine* e, int32_t* matched, double* loglik_sum);
+/* pf_host_ctc_beam with a hot-word set and a boost: the biased search for ONE utterance in plain host code.  out_matched [N],
+   out_loglik [N] next to out_score.  Hot-word ids are in [1, 2^24) here (there is no vocabulary to bound them). */
+int pf_host_ctc_beam_hot(const float* blank_lp, int64_t blank_stride, const int64_t* ids, const float* val, const int32_t* n, int32_t T,
+                         int32_t K, int32_t blank, int32_t W, int32_t N, int64_t* out_ids, int32_t* out_len, double* out_score,
+                         int32_t cap, int32_t* n_hyp, const int32_t* hw_ids, const int32_t* hw_lens, int32_t n_hotwords, float boost,
+                         int32_t* out_matched, double* out_loglik);
+
 /* ---- CTC forced alignment (additions to ABI 6; nothing is launched or allocated without the flag) ----------------------
    PF_DECODE_ALIGN (pf_engine_set_decode; SenseVoice only, every math_mode; implies SCORES, not TOPK; independent of
    PF_DECODE_CTC; PF_ERR_UNSUPPORTED for a paraformer or SeACo model and for a pf_group forward): where the text is already
@@ -441,6 +493,13 @@ int pf_op_topk(pf_engine* e, const float* x, int64_t rows, int32_t V, int32_t ld
 int pf_op_ctc_beam(pf_engine* e, const float* blank_lp, const int64_t* ids, const float* val, const int32_t* n, const int32_t* lens,
                    int32_t B, int32_t T, int32_t K, int32_t blank, int32_t W, int32_t N, int64_t* out_ids, int32_t* out_len,
                    double* out_score, int32_t cap, int32_t* n_hyp);
+/* the biased form of the same kernel (see "CTC hot words"): pf_op_ctc_beam plus the set, the boost and the two outputs
+   [B, N] next to out_score.  boost == 0 or a set without a non-empty word launches exactly what pf_op_ctc_beam launches
+   (matched 0, loglik = score). */
+int pf_op_ctc_beam_hot(pf_engine* e, const float* blank_lp, const int64_t* ids, const float* val, const int32_t* n, const int32_t* lens,
+                       int32_t B, int32_t T, int32_t K, int32_t blank, int32_t W, int32_t N, int64_t* out_ids, int32_t* out_len,
+                       double* out_score, int32_t cap, int32_t* n_hyp, const int32_t* hw_ids, const int32_t* hw_lens,
+                       int32_t n_hotwords, float boost, int32_t* out_matched, double* out_loglik);
 /* exactly the pipeline's alignment kernel (k_ctcalign.hip) on caller arrays: lp [B * T, ld] (V read per row), tgt [B, H, cap]
    int32, tlen [B, H] (-1: skip the job; above cap or PF_ALIGN_MAX_TOKENS: ok = 0), lens [B] (clamped to 0 .. T; nothing at or
    beyond lens[b] is read, nor a target slot at or beyond tlen; an id outside [0, V) makes the job not ok).  Outputs as
@@ -735,6 +794,18 @@ int pf_recognizer_set_ctc_beam(pf_recognizer* r, int32_t N, int32_t W, int32_t K
    Timestamps, Scores, the result text and the alternatives' order and scores are what they are without it.  The pointers stay
    valid until the stream's next GetResults. */
 int pf_recognizer_set_align(pf_recognizer* r, int32_t on);
+/* SenseVoice only (see "CTC hot words"; PF_ERR_UNSUPPORTED otherwise).  boost > 0: the beam search of
+   pf_recognizer_set_ctc_beam is biased towards the batch's hot words by `boost` per matched token; 0 = off; inert until
+   pf_recognizer_set_ctc_beam is set.  The hot words of a GetResults call follow the SeACo rule: the union of the batch's
+   stream.Hotwords (pf_stream_set_hotwords; a null list fails the call as it does there), and if that is empty the recognizer's
+   hot-word file, tokenised as the reference does (per character IndexOf, unknown characters dropped) — a SenseVoice caller who
+   needs sentencepiece pieces sets stream.Hotwords ids.  The [1] terminator entry GetHotwords appends is dropped wherever it
+   appears.  An engine keeps its automaton while the union is the same.  Alternatives then come in the biased order, each with
+   score (biased), hotword_tokens (= matched) and loglik_sum through pf_stream_alternative_hot (0 / NaN when the call ran
+   unbiased); Text and Tokens stay what they are.  A hot word that breaks the automaton's limits or holds an id outside
+   [1, V) fails GetResults (PF_ERR_RECOGNITION). */
+int pf_recognizer_set_hotword_boost(pf_recognizer* r, float boost);
+int pf_stream_alternative_hot(pf_stream* s, int32_t i, int32_t* hotword_tokens, double* loglik_sum);
 int pf_stream_set_align_ids(pf_stream* s, const int64_t* ids, int32_t n);
 int pf_stream_alignment(pf_stream* s, const int32_t** begin_end, const float** tok_score, int32_t* n, float* path_score,
                         double* loglik, int32_t* ok);
