@@ -16,8 +16,6 @@
 
 namespace pf {
 
-static const size_t kAlign = 256;
-
 // live engines' main streams and the streams parked by the hardware-queue probe (Engine::own_hardware_queue below)
 static std::mutex g_main_mu;
 static std::vector<std::pair<int, hipStream_t>> g_main_streams;      // (device, main stream) of the live engines
@@ -1234,7 +1232,7 @@ void Engine::encoder(const float* speech_dev, int B, int T, bool pre_encoded) {
   const int k0 = enc_.empty() ? D : enc_[0].qkv.Kpad;
   // carve the encoder arena
   size_t off = 0;
-  auto carve = [&](size_t bytes) { size_t o = off; off += round_up((int64_t)bytes, (int64_t)kAlign); return o; };
+  const Carve carve{off};
   const size_t o_x = carve(Mp * D * 4), o_xn = carve(Mp * std::max(k0, D) * 2), o_qkv = carve(Mp * 3 * D * 2);
   const size_t o_ctx = carve(Mp * D * 2), o_fsm = carve(Mp * D * 4), o_h = carve(Mp * std::max(F, 3 * D) * 2);
   const size_t o_H32 = carve(Mp * D * 4), o_H16 = carve(Mp * D * 2), o_al = carve((size_t)B * (T + 1) * 4);
@@ -1664,7 +1662,7 @@ void Engine::seaco_head(int B, int L, const float* e0, const float* hid32, bool 
   // once per call: it is a function of the weights and the list alone (the reference re-runs model_eb every call,
   // OfflineProjOfSeacoParaformer.cs:83-111, with the same result)
   size_t hoff = 0;
-  auto hcarve = [&](size_t bytes) { size_t o = hoff; hoff += round_up((int64_t)bytes, (int64_t)kAlign); return o; };
+  const Carve hcarve{hoff};
   const size_t o_ids = hcarve((size_t)NJ * 4), o_e32 = hcarve((size_t)NJp * D * 4), o_in16 = hcarve((size_t)NJp * D * 2);
   const size_t o_xg = hcarve((size_t)NJp * 4 * D * 4), o_ho = hcarve((size_t)NJp * D * 4), o_hs = hcarve((size_t)2 * N * D * 2);
   const size_t o_cs = hcarve((size_t)N * D * 4), o_kv = hcarve((size_t)NJp * std::max(ns, 1) * 2 * D * 2);
@@ -1792,7 +1790,7 @@ void Engine::timestamp_head(int B, int T) {
   const int64_t M3 = (int64_t)B * T3;
   const int64_t Mp = round_up(M, 128) + 128, M3p = round_up(M3, 128) + 128;
   size_t off = 0;
-  auto carve = [&](size_t bytes) { size_t o = off; off += round_up((int64_t)bytes, (int64_t)kAlign); return o; };
+  const Carve carve{off};
   const size_t o_up = carve((size_t)std::max<int64_t>(Mp * up, M3p) * D * 2), o_xg = carve((size_t)M3p * 8 * D * 4);
   const size_t o_ho = carve((size_t)M3 * 2 * D * 4), o_hs = carve((size_t)8 * B * D * 2), o_cs = carve((size_t)2 * B * D * 4);
   const size_t o_al = carve((size_t)M3 * 4), o_pk = carve((size_t)M3 * 4), o_sw = carve(256);
@@ -1831,7 +1829,7 @@ void Engine::sensevoice_head(int B, int T, bool want_logits) {
   const int M = B * T;
   const int64_t Mp = round_up(M, 128) + 128;
   size_t off = 0;
-  auto carve = [&](size_t bytes) { size_t o = off; off += round_up((int64_t)bytes, (int64_t)kAlign); return o; };
+  const Carve carve{off};
   const size_t o_lg = carve((size_t)Mp * round_up(V, 4) * 4), o_ids = carve((size_t)M * 8);
   ensure(ws_dec_, off);
   logits_ = (float*)((char*)ws_dec_.p + o_lg);
@@ -1945,7 +1943,7 @@ float* Engine::score_buf(int64_t rows) {
 }
 
 void Engine::queue_decode_results(int B, int L) {
-  std::vector<int32_t>& len = ctc_len_;              // (a member: the host-to-device copy below may read it after this call returns)
+  std::vector<int32_t>& len = ctc_len_;              // (a member: the host-to-device copies below may read it after this call returns)
   len.clear();
   len.swap(dec_len_);                                // consumed: a later forward without lengths decodes every row
   if (!decode_flags_ || B * L == 0) return;
@@ -1956,128 +1954,116 @@ void Engine::queue_decode_results(int B, int L) {
     if ((int)len.size() != B) len.assign(B, L);
     for (int b = 0; b < B; ++b) len[b] = std::min(std::max(len[b], 0), L);
   }
-  if (decode_flags_ & PF_DECODE_TOPK) {
-    // the arg-max ran in its store-in-place form (argmax_mode): logits_ holds the log-probs it scanned
-    const int64_t rows = (int64_t)B * L;
-    const int K = topk_k_;
-    const size_t words = HostBatchOut::topk_words(rows, K);
-    ensure(ws_topk_, words * 8);
-    last_.topk.resize(words);
-    last_.topk_k = K;
-    int64_t* ids_o = (int64_t*)ws_topk_.p;
-    float* val_o = (float*)(ids_o + (size_t)rows * K);
-    int32_t* n_o = (int32_t*)(val_o + (size_t)rows * K);
-    prof_begin("topk", 0);
-    launch_topk(stream_, logits_, rows, last_.V, logits_ld_, K, ids_o, val_o, n_o);
-    prof_end("topk");
-    PF_HIP(hipMemcpyAsync(last_.topk.data(), ws_topk_.p, ((size_t)rows * K * 12 + (size_t)rows * 4), hipMemcpyDeviceToHost, stream_));
-    if (decode_flags_ & PF_DECODE_CTC_BEAM) {
-      // the search reads the lists just made and the blank column (id 0) of the in-place log-prob rows
-      const int W = beam_w_, Nh = beam_n_, cap = L;
-      const size_t bwords = HostBatchOut::beam_words(B, Nh, cap);
-      const size_t nodes = (size_t)B * ((size_t)L * W + 1);
-      const bool hot = hot_boost_ > 0.f;
-      const size_t hwords = hot ? HostBatchOut::beam_hot_words(B, Nh) : 0;
-      const size_t tail4 = ((size_t)B + 2 * nodes + 1) / 2 * 2;              // len | nodes, kept a multiple of 8 bytes
-      ensure(ws_beam_, hot ? bwords * 8 + tail4 * 4 + hwords * 8 : bwords * 8 + (size_t)B * 4 + nodes * 8);
-      last_.beam.resize(bwords);
-      last_.beam_n = Nh;
-      last_.beam_cap = cap;
-      double* score_o = (double*)ws_beam_.p;
-      int32_t* bids_o = (int32_t*)(score_o + (size_t)B * Nh);
-      int32_t* blen_o = bids_o + (size_t)B * Nh * cap;
-      int32_t* nhyp_o = blen_o + (size_t)B * Nh;
-      int32_t* len_d = (int32_t*)((char*)ws_beam_.p + bwords * 8);
-      int32_t* node_par = len_d + B;
-      int32_t* node_tok = node_par + nodes;
-      PF_HIP(hipMemcpyAsync(len_d, len.data(), (size_t)B * 4, hipMemcpyHostToDevice, stream_));
-      prof_begin("ctc_beam", 0);
-      if (hot) {
-        // the biased form: the same outputs in the biased order, and loglik_sum | matched behind the node workspace
-        double* ll_o = (double*)((char*)ws_beam_.p + bwords * 8 + tail4 * 4);
-        int32_t* m_o = (int32_t*)(ll_o + (size_t)B * Nh);
-        const int32_t* tok_col = (const int32_t*)ws_hot_.p;
-        last_.beam_hot.resize(hwords);
-        launch_ctc_beam_hot(stream_, logits_, logits_ld_, ids_o, val_o, n_o, len_d, B, L, K, 0, W, Nh, cap, node_par, node_tok, tok_col,
-                            mc_.vocab, tok_col + mc_.vocab, hot_A_, hot_boost_, bids_o, blen_o, score_o, m_o, ll_o, nhyp_o);
-      } else {
-        launch_ctc_beam(stream_, logits_, logits_ld_, ids_o, val_o, n_o, len_d, B, L, K, 0, W, Nh, cap, node_par, node_tok, bids_o,
-                        blen_o, score_o, nhyp_o);
-      }
-      prof_end("ctc_beam");
-      PF_HIP(hipMemcpyAsync(last_.beam.data(), ws_beam_.p, bwords * 8, hipMemcpyDeviceToHost, stream_));
-      if (hot)
-        PF_HIP(hipMemcpyAsync(last_.beam_hot.data(), (char*)ws_beam_.p + bwords * 8 + tail4 * 4, hwords * 8, hipMemcpyDeviceToHost, stream_));
-    }
+  if (decode_flags_ & PF_DECODE_TOPK) queue_topk(B, L);
+  if (decode_flags_ & PF_DECODE_CTC_BEAM) queue_ctc_beam(B, L);      // (set_decode: implies TOPK)
+  if (decode_flags_ & PF_DECODE_ALIGN) queue_align(B, L);
+  if (decode_flags_ & PF_DECODE_CTC) queue_ctc_collapse(B, L);
+}
+
+void Engine::queue_topk(int B, int L) {
+  // the arg-max ran in its store-in-place form (argmax_mode): logits_ holds the log-probs it scanned
+  const int64_t rows = (int64_t)B * L;
+  const int K = topk_k_;
+  Cursor c;
+  const TopkBlock k(c, rows, K);
+  ensure(ws_topk_, c.off);
+  last_.topk.resize(k.words());
+  last_.topk_k = K;
+  void* ws = ws_topk_.p;
+  prof_begin("topk", 0);
+  launch_topk(stream_, logits_, rows, last_.V, logits_ld_, K, k.ids(ws), k.val(ws), k.n(ws));
+  prof_end("topk");
+  PF_HIP(hipMemcpyAsync(last_.topk.data(), ws, k.bytes(), hipMemcpyDeviceToHost, stream_));
+}
+
+void Engine::queue_ctc_beam(int B, int L) {
+  // the search reads the lists queue_topk just made and the blank column (id 0) of the in-place log-prob rows
+  const int W = beam_w_, Nh = beam_n_, cap = L, K = topk_k_;
+  const bool hot = hot_boost_ > 0.f;
+  const size_t nodes = (size_t)B * ((size_t)L * W + 1);
+  const TopkBlock tk = block_at_zero<TopkBlock>((size_t)B * L, K);
+  Cursor c;
+  const BeamBlock k(c, B, Nh, cap);
+  const Field<int32_t> len_d = c.take<int32_t>(B), node_par = c.take<int32_t>(nodes), node_tok = c.take<int32_t>(nodes);
+  Cursor ch = c;
+  const BeamHotBlock h(ch, B, Nh);                   // the biased form only: loglik_sum | matched behind the node workspace
+  ensure(ws_beam_, hot ? ch.off : c.off);
+  last_.beam.resize(k.words());
+  last_.beam_n = Nh;
+  last_.beam_cap = cap;
+  void* ws = ws_beam_.p;
+  const void* wt = ws_topk_.p;
+  PF_HIP(hipMemcpyAsync(len_d(ws), ctc_len_.data(), ctc_len_.size() * 4, hipMemcpyHostToDevice, stream_));
+  prof_begin("ctc_beam", 0);
+  if (hot) {
+    const int32_t* tok_col = (const int32_t*)ws_hot_.p;
+    last_.beam_hot.resize(h.words());
+    launch_ctc_beam_hot(stream_, logits_, logits_ld_, tk.ids(wt), tk.val(wt), tk.n(wt), len_d(ws), B, L, K, 0, W, Nh, cap, node_par(ws),
+                        node_tok(ws), tok_col, mc_.vocab, tok_col + mc_.vocab, hot_A_, hot_boost_, k.ids(ws), k.len(ws), k.score(ws),
+                        h.matched(ws), h.loglik(ws), k.n_hyp(ws));
+  } else {
+    launch_ctc_beam(stream_, logits_, logits_ld_, tk.ids(wt), tk.val(wt), tk.n(wt), len_d(ws), B, L, K, 0, W, Nh, cap, node_par(ws),
+                    node_tok(ws), k.ids(ws), k.len(ws), k.score(ws), k.n_hyp(ws));
   }
-  if (decode_flags_ & PF_DECODE_ALIGN) {
-    // jobs per utterance: the caller's target (when set for this forward), then the hypotheses the search above left in ws_beam_
-    const bool tg = align_B_ == B;
-    const int Nb = (decode_flags_ & PF_DECODE_CTC_BEAM) ? last_.beam_n : 0, b_cap = last_.beam_cap;
-    const int H = (tg ? 1 : 0) + Nb;
-    align_tgt_q_.clear(); align_len_q_.clear();
-    align_tgt_q_.swap(align_tgt_);                  // consumed, like the lengths
-    align_len_q_.swap(align_len_);
-    const int c_cap = align_cap_;
-    align_B_ = 0;
-    if (H > 0) {
-      const int cap = std::max(1, std::max(tg ? c_cap : 0, Nb ? std::min(L, (int)PF_ALIGN_MAX_TOKENS) : 0));
-      const size_t jobs = (size_t)B * H, awords = HostBatchOut::align_words(B, H, cap);
-      const size_t bp_stride = ctc_align_bp_words(L, cap);
-      const size_t tail4 = jobs * cap + (size_t)B + (tg ? (size_t)B * c_cap + (size_t)B : 0) + jobs * bp_stride;
-      ensure(ws_align_, awords * 8 + tail4 * 4);
-      last_.align.resize(awords);
-      last_.align_h = H;
-      last_.align_cap = cap;
-      double* ll_o = (double*)ws_align_.p;
-      float* ps_o = (float*)(ll_o + jobs);
-      int32_t* ok_o = (int32_t*)(ps_o + jobs);
-      int32_t* tlen_d = ok_o + jobs;
-      int32_t* first_o = tlen_d + jobs;
-      int32_t* last_o = first_o + jobs * cap;
-      float* tok_o = (float*)(last_o + jobs * cap);
-      int32_t* tgt_d = (int32_t*)((char*)ws_align_.p + awords * 8);
-      int32_t* len_d = tgt_d + jobs * cap;
-      int32_t* ctgt_d = len_d + B;
-      int32_t* clen_d = ctgt_d + (tg ? (size_t)B * c_cap : 0);
-      uint32_t* bp_d = (uint32_t*)(clen_d + (tg ? B : 0));
-      PF_HIP(hipMemcpyAsync(len_d, len.data(), (size_t)B * 4, hipMemcpyHostToDevice, stream_));
-      if (tg) {
-        PF_HIP(hipMemcpyAsync(ctgt_d, align_tgt_q_.data(), (size_t)B * c_cap * 4, hipMemcpyHostToDevice, stream_));
-        PF_HIP(hipMemcpyAsync(clen_d, align_len_q_.data(), (size_t)B * 4, hipMemcpyHostToDevice, stream_));
-      }
-      const int32_t* bids_d = nullptr, *blen_d = nullptr, *bnh_d = nullptr;
-      if (Nb) {
-        bids_d = (const int32_t*)((const double*)ws_beam_.p + (size_t)B * Nb);
-        blen_d = bids_d + (size_t)B * Nb * b_cap;
-        bnh_d = blen_d + (size_t)B * Nb;
-      }
-      prof_begin("ctc_align", 0);
-      launch_ctc_align_jobs(stream_, tg ? ctgt_d : nullptr, tg ? clen_d : nullptr, c_cap, bids_d, blen_d, bnh_d, Nb, b_cap, B, H, cap,
-                            tgt_d, tlen_d);
-      launch_ctc_align(stream_, logits_, logits_ld_, last_.V, tgt_d, tlen_d, len_d, B, L, H, cap, bp_d, (int64_t)bp_stride, ps_o, ll_o,
-                       ok_o, first_o, last_o, tok_o);
-      prof_end("ctc_align");
-      PF_HIP(hipMemcpyAsync(last_.align.data(), ws_align_.p, awords * 8, hipMemcpyDeviceToHost, stream_));
-    }
+  prof_end("ctc_beam");
+  PF_HIP(hipMemcpyAsync(last_.beam.data(), ws, k.words() * 8, hipMemcpyDeviceToHost, stream_));
+  if (hot) PF_HIP(hipMemcpyAsync(last_.beam_hot.data(), (char*)ws + h.begin, h.words() * 8, hipMemcpyDeviceToHost, stream_));
+}
+
+void Engine::queue_align(int B, int L) {
+  // jobs per utterance: the caller's target (when set for this forward), then the hypotheses queue_ctc_beam left in ws_beam_
+  const bool tg = align_B_ == B;
+  const int Nb = (decode_flags_ & PF_DECODE_CTC_BEAM) ? last_.beam_n : 0, b_cap = last_.beam_cap;
+  const int H = (tg ? 1 : 0) + Nb;
+  align_tgt_q_.clear(); align_len_q_.clear();
+  align_tgt_q_.swap(align_tgt_);                    // consumed, like the lengths
+  align_len_q_.swap(align_len_);
+  const int c_cap = align_cap_;
+  align_B_ = 0;
+  if (H == 0) return;
+  const int cap = std::max(1, std::max(tg ? c_cap : 0, Nb ? std::min(L, (int)PF_ALIGN_MAX_TOKENS) : 0));
+  const size_t bp_stride = ctc_align_bp_words(L, cap);
+  Cursor c;
+  const AlignBlock k(c, B, H, cap);
+  const Field<int32_t> tgt_d = c.take<int32_t>(k.first.count), len_d = c.take<int32_t>(B);
+  const Field<int32_t> ctgt_d = c.take<int32_t>(tg ? align_tgt_q_.size() : 0), clen_d = c.take<int32_t>(tg ? align_len_q_.size() : 0);
+  const Field<uint32_t> bp_d = c.take<uint32_t>(k.ok.count * bp_stride);
+  ensure(ws_align_, c.off);
+  last_.align.resize(k.words());
+  last_.align_h = H;
+  last_.align_cap = cap;
+  void* ws = ws_align_.p;
+  PF_HIP(hipMemcpyAsync(len_d(ws), ctc_len_.data(), ctc_len_.size() * 4, hipMemcpyHostToDevice, stream_));
+  if (tg) {
+    PF_HIP(hipMemcpyAsync(ctgt_d(ws), align_tgt_q_.data(), align_tgt_q_.size() * 4, hipMemcpyHostToDevice, stream_));
+    PF_HIP(hipMemcpyAsync(clen_d(ws), align_len_q_.data(), align_len_q_.size() * 4, hipMemcpyHostToDevice, stream_));
   }
-  if (!(decode_flags_ & PF_DECODE_CTC)) return;
+  const BeamBlock bm = block_at_zero<BeamBlock>(B, Nb, b_cap);
+  const void* wb = ws_beam_.p;
+  prof_begin("ctc_align", 0);
+  launch_ctc_align_jobs(stream_, tg ? ctgt_d(ws) : nullptr, tg ? clen_d(ws) : nullptr, c_cap, Nb ? bm.ids(wb) : nullptr,
+                        Nb ? bm.len(wb) : nullptr, Nb ? bm.n_hyp(wb) : nullptr, Nb, b_cap, B, H, cap, tgt_d(ws), k.len(ws));
+  launch_ctc_align(stream_, logits_, logits_ld_, last_.V, tgt_d(ws), k.len(ws), len_d(ws), B, L, H, cap, bp_d(ws), (int64_t)bp_stride,
+                   k.path(ws), k.loglik(ws), k.ok(ws), k.first(ws), k.last(ws), k.tok(ws));
+  prof_end("ctc_align");
+  PF_HIP(hipMemcpyAsync(last_.align.data(), ws, k.words() * 8, hipMemcpyDeviceToHost, stream_));
+}
+
+void Engine::queue_ctc_collapse(int B, int L) {
   const int cap = L;
-  const size_t words = HostBatchOut::ctc_words(B, cap);
-  ensure(ws_ctc_, words * 8 + (size_t)B * 4);
-  last_.ctc.resize(words);
+  Cursor c;
+  const CtcBlock k(c, B, cap);
+  const Field<int32_t> len_d = c.take<int32_t>(B);
+  ensure(ws_ctc_, c.off);
+  last_.ctc.resize(k.words());
   last_.ctc_cap = cap;
-  int64_t* ids_o = (int64_t*)ws_ctc_.p;
-  int32_t* first_o = (int32_t*)(ids_o + (size_t)B * cap);
-  int32_t* last_o = first_o + (size_t)B * cap;
-  float* score_o = (float*)(last_o + (size_t)B * cap);
-  int32_t* n_o = last_o + 2 * (size_t)B * cap;
-  int32_t* len_d = (int32_t*)((char*)ws_ctc_.p + words * 8);
-  PF_HIP(hipMemcpyAsync(len_d, len.data(), (size_t)B * 4, hipMemcpyHostToDevice, stream_));
+  void* ws = ws_ctc_.p;
+  PF_HIP(hipMemcpyAsync(len_d(ws), ctc_len_.data(), ctc_len_.size() * 4, hipMemcpyHostToDevice, stream_));
   prof_begin("ctc_collapse", 0);
-  launch_ctc_collapse(stream_, ids_dev_, sc, len_d, B, L, 0, cap, n_o, ids_o, first_o, last_o, score_o);
+  launch_ctc_collapse(stream_, ids_dev_, (const float*)ws_score_.p, len_d(ws), B, L, 0, cap, k.n(ws), k.ids(ws), k.first(ws), k.last(ws),
+                      k.score(ws));
   prof_end("ctc_collapse");
-  PF_HIP(hipMemcpyAsync(last_.ctc.data(), ws_ctc_.p, words * 8, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipMemcpyAsync(last_.ctc.data(), ws, k.words() * 8, hipMemcpyDeviceToHost, stream_));
 }
 
 void Engine::forward_device(const float* speech_dev, int B, int T, bool want_logits) {
@@ -2134,12 +2120,6 @@ void Engine::unregister_uid(uint64_t id) {
   g_live.erase(id);
 }
 
-// the calling thread's slot of engine `uid` (null: none published, or already released)
-static const HostBatchOut* t_slots_find(uint64_t uid) {
-  auto it = t_slots.find(uid);
-  return it == t_slots.end() ? nullptr : &it->second;
-}
-
 void Engine::publish_thread_result() {
   PF_HIP(hipStreamSynchronize(stream_));
   check_async_errors();
@@ -2185,13 +2165,19 @@ void Engine::fetch_ids_device(int64_t* ids_dev, int l_cap, int32_t* L_out) {
   sync();
 }
 
-void Engine::fetch(pf_batch_out* out) {
-  PF_CHECK(out, PF_ERR_INVALID_ARG, "fetch: null out");
+const HostBatchOut& Engine::fetch_result(int flags, const char* refusal) {
   PF_HIP(hipStreamSynchronize(stream_));
   check_async_errors();
   auto it = t_slots.find(uid_);
-  const bool slot = it != t_slots.end();
-  const HostBatchOut& r = slot ? it->second : last_;
+  const HostBatchOut& r = it != t_slots.end() ? it->second : last_;
+  PF_CHECK((r.decode_flags & flags) == flags, PF_ERR_INVALID_ARG, refusal);
+  return r;
+}
+
+void Engine::fetch(pf_batch_out* out) {
+  PF_CHECK(out, PF_ERR_INVALID_ARG, "fetch: null out");
+  const HostBatchOut& r = fetch_result(0, "");   // no decode flag is needed for the ids
+  const bool slot = &r != &last_;
   const int B = r.B, L = r.L, V = r.V;
   out->L = L; out->V = V; out->cif_peak_len = r.peak_len;
   if (out->cif_peak && out->cif_peak_cap > 0 && r.peak_len > 0) {
@@ -2218,15 +2204,11 @@ void Engine::fetch(pf_batch_out* out) {
   }
   // the call that receives the ids completes the learn-L-then-fetch protocol: release the slot (a B*L*V host
   // copy of the log-probs may hang off it)
-  if (slot && out->token_ids) t_slots.erase(it);
+  if (slot && out->token_ids) t_slots.erase(uid_);
 }
 
 void Engine::fetch_scores(float* scores, int64_t cap, int32_t* L_out) {
-  PF_HIP(hipStreamSynchronize(stream_));
-  check_async_errors();
-  auto it = t_slots_find(uid_);
-  const HostBatchOut& r = it ? *it : last_;
-  PF_CHECK(r.decode_flags & PF_DECODE_SCORES, PF_ERR_INVALID_ARG, "fetch_scores: PF_DECODE_SCORES was not set for the last forward");
+  const HostBatchOut& r = fetch_result(PF_DECODE_SCORES, "fetch_scores: PF_DECODE_SCORES was not set for the last forward");
   if (L_out) *L_out = r.L;
   const int64_t need = (int64_t)r.B * r.L;
   if (!scores) return;
@@ -2235,113 +2217,89 @@ void Engine::fetch_scores(float* scores, int64_t cap, int32_t* L_out) {
 }
 
 void Engine::fetch_topk(int64_t* ids, float* val, int32_t* n, int64_t cap_rows, int32_t* L_out, int32_t* K_out) {
-  PF_HIP(hipStreamSynchronize(stream_));
-  check_async_errors();
-  auto it = t_slots_find(uid_);
-  const HostBatchOut& r = it ? *it : last_;
-  PF_CHECK(r.decode_flags & PF_DECODE_TOPK, PF_ERR_INVALID_ARG, "fetch_topk: PF_DECODE_TOPK was not set for the last forward");
+  const HostBatchOut& r = fetch_result(PF_DECODE_TOPK, "fetch_topk: PF_DECODE_TOPK was not set for the last forward");
   if (L_out) *L_out = r.L;
   if (K_out) *K_out = r.topk_k;
   if (!ids && !val && !n) return;
   const int64_t rows = (int64_t)r.B * r.L;
   PF_CHECK(cap_rows >= rows, PF_ERR_CAPACITY, "topk capacity < B*L = " + std::to_string(rows));
   if (rows == 0 || r.topk.empty()) return;
-  const size_t K = (size_t)r.topk_k;
-  if (ids) std::memcpy(ids, r.topk_ids(), (size_t)rows * K * 8);
-  if (val) std::memcpy(val, r.topk_val(), (size_t)rows * K * 4);
-  if (n) std::memcpy(n, r.topk_n(), (size_t)rows * 4);
+  const TopkBlock k = r.topk_block();
+  const void* p = r.topk.data();
+  if (ids) std::memcpy(ids, k.ids(p), k.ids.count * 8);
+  if (val) std::memcpy(val, k.val(p), k.val.count * 4);
+  if (n) std::memcpy(n, k.n(p), k.n.count * 4);
 }
 
 void Engine::fetch_ctc_beam(int64_t* ids, int32_t* len, double* score, int32_t cap, int32_t* n_hyp, int32_t* len_max, int32_t* N_out) {
-  PF_HIP(hipStreamSynchronize(stream_));
-  check_async_errors();
-  auto it = t_slots_find(uid_);
-  const HostBatchOut& r = it ? *it : last_;
-  PF_CHECK(r.decode_flags & PF_DECODE_CTC_BEAM, PF_ERR_INVALID_ARG, "fetch_ctc_beam: PF_DECODE_CTC_BEAM was not set for the last forward");
+  const HostBatchOut& r = fetch_result(PF_DECODE_CTC_BEAM, "fetch_ctc_beam: PF_DECODE_CTC_BEAM was not set for the last forward");
   const int B = r.B, Nh = r.beam_n;
   const bool have = !r.beam.empty();
+  const BeamBlock k = r.beam_block();
+  const void* p = r.beam.data();
   int mx = 0;
-  for (int x = 0; x < B * Nh && have; ++x) mx = std::max(mx, r.beam_len()[x]);
+  for (int x = 0; x < B * Nh && have; ++x) mx = std::max(mx, k.len(p)[x]);
   if (len_max) *len_max = mx;
   if (N_out) *N_out = Nh;
-  if (n_hyp) for (int b = 0; b < B; ++b) n_hyp[b] = have ? r.beam_nhyp()[b] : 0;
+  if (n_hyp) for (int b = 0; b < B; ++b) n_hyp[b] = have ? k.n_hyp(p)[b] : 0;
   if (!have) return;
-  if (len) std::memcpy(len, r.beam_len(), (size_t)B * Nh * 4);
-  if (score) std::memcpy(score, r.beam_score(), (size_t)B * Nh * 8);
+  if (len) std::memcpy(len, k.len(p), k.len.count * 4);
+  if (score) std::memcpy(score, k.score(p), k.score.count * 8);
   if (!ids) return;
   PF_CHECK(cap >= mx, PF_ERR_CAPACITY, "ctc_beam capacity " + std::to_string(cap) + " < len_max = " + std::to_string(mx));
-  for (int x = 0; x < B * Nh; ++x) {
-    const int32_t* src = r.beam_ids() + (size_t)x * r.beam_cap;
-    int64_t* dst = ids + (size_t)x * cap;
-    const int k = std::min(cap, r.beam_cap);
-    for (int p = 0; p < k; ++p) dst[p] = src[p];
-    std::fill(dst + k, dst + cap, (int64_t)-1);
-  }
+  copy_rows_padded(ids, cap, k.ids(p), r.beam_cap, k.len.count, (int64_t)-1);
 }
 
 void Engine::fetch_ctc_beam_hot(int32_t* matched, double* loglik) {
-  PF_HIP(hipStreamSynchronize(stream_));
-  check_async_errors();
-  auto it = t_slots_find(uid_);
-  const HostBatchOut& r = it ? *it : last_;
-  PF_CHECK((r.decode_flags & PF_DECODE_CTC_BEAM) && !r.beam_hot.empty(), PF_ERR_INVALID_ARG,
-           "fetch_ctc_beam_hot: the last forward ran no biased beam search (PF_DECODE_CTC_BEAM with pf_engine_set_ctc_hotwords)");
-  const size_t hyp = (size_t)r.B * r.beam_n;
-  if (matched) std::memcpy(matched, r.beam_matched(), hyp * 4);
-  if (loglik) std::memcpy(loglik, r.beam_loglik(), hyp * 8);
+  const char* refusal = "fetch_ctc_beam_hot: the last forward ran no biased beam search (PF_DECODE_CTC_BEAM with pf_engine_set_ctc_hotwords)";
+  const HostBatchOut& r = fetch_result(PF_DECODE_CTC_BEAM, refusal);
+  PF_CHECK(!r.beam_hot.empty(), PF_ERR_INVALID_ARG, refusal);
+  const BeamHotBlock k = r.beam_hot_block();
+  const void* p = r.beam_hot.data();
+  if (matched) std::memcpy(matched, k.matched(p), k.matched.count * 4);
+  if (loglik) std::memcpy(loglik, k.loglik(p), k.loglik.count * 8);
 }
 
 void Engine::fetch_align(float* path_score, double* loglik, int32_t* ok, int32_t* len, int32_t* first, int32_t* last, float* tok_score,
                          int32_t cap, int32_t* H_out, int32_t* len_max) {
-  PF_HIP(hipStreamSynchronize(stream_));
-  check_async_errors();
-  auto it = t_slots_find(uid_);
-  const HostBatchOut& r = it ? *it : last_;
-  PF_CHECK(r.decode_flags & PF_DECODE_ALIGN, PF_ERR_INVALID_ARG, "fetch_align: PF_DECODE_ALIGN was not set for the last forward");
-  const int B = r.B, H = r.align.empty() ? 0 : r.align_h;
-  const size_t jobs = (size_t)B * H;
+  const HostBatchOut& r = fetch_result(PF_DECODE_ALIGN, "fetch_align: PF_DECODE_ALIGN was not set for the last forward");
+  const int H = r.align.empty() ? 0 : r.align_h;
+  const AlignBlock k = r.align_block();
+  const void* p = r.align.data();
+  const size_t jobs = H ? k.len.count : 0;
   int mx = 0;
-  for (size_t x = 0; x < jobs; ++x) mx = std::max(mx, r.align_len()[x]);
+  for (size_t x = 0; x < jobs; ++x) mx = std::max(mx, k.len(p)[x]);
   if (H_out) *H_out = H;
   if (len_max) *len_max = mx;
   if (jobs == 0) return;
-  if (path_score) std::memcpy(path_score, r.align_path(), jobs * 4);
-  if (loglik) std::memcpy(loglik, r.align_loglik(), jobs * 8);
-  if (ok) std::memcpy(ok, r.align_ok(), jobs * 4);
-  if (len) std::memcpy(len, r.align_len(), jobs * 4);
+  if (path_score) std::memcpy(path_score, k.path(p), k.path.count * 4);
+  if (loglik) std::memcpy(loglik, k.loglik(p), k.loglik.count * 8);
+  if (ok) std::memcpy(ok, k.ok(p), k.ok.count * 4);
+  if (len) std::memcpy(len, k.len(p), k.len.count * 4);
   if (!first && !last && !tok_score) return;
   PF_CHECK(cap >= mx, PF_ERR_CAPACITY, "align capacity " + std::to_string(cap) + " < len_max = " + std::to_string(mx));
-  const size_t k = (size_t)std::min(cap, r.align_cap);
-  for (size_t x = 0; x < jobs; ++x) {
-    const size_t src = x * r.align_cap, dst = x * cap;
-    if (first) { std::memcpy(first + dst, r.align_first() + src, k * 4); std::fill(first + dst + k, first + dst + cap, -1); }
-    if (last) { std::memcpy(last + dst, r.align_last() + src, k * 4); std::fill(last + dst + k, last + dst + cap, -1); }
-    if (tok_score) { std::memcpy(tok_score + dst, r.align_tok() + src, k * 4); std::fill(tok_score + dst + k, tok_score + dst + cap, 0.f); }
-  }
+  copy_rows_padded(first, cap, k.first(p), r.align_cap, jobs, -1);
+  copy_rows_padded(last, cap, k.last(p), r.align_cap, jobs, -1);
+  copy_rows_padded(tok_score, cap, k.tok(p), r.align_cap, jobs, 0.f);
 }
 
 void Engine::fetch_ctc(int64_t* ids, int32_t* first, int32_t* last, float* score, int32_t cap, int32_t* n, int32_t* n_max) {
-  PF_HIP(hipStreamSynchronize(stream_));
-  check_async_errors();
-  auto it = t_slots_find(uid_);
-  const HostBatchOut& r = it ? *it : last_;
-  PF_CHECK(r.decode_flags & PF_DECODE_CTC, PF_ERR_INVALID_ARG, "fetch_ctc: PF_DECODE_CTC was not set for the last forward");
+  const HostBatchOut& r = fetch_result(PF_DECODE_CTC, "fetch_ctc: PF_DECODE_CTC was not set for the last forward");
   const int B = r.B;
   const bool have = !r.ctc.empty();
+  const CtcBlock k = r.ctc_block();
+  const void* p = r.ctc.data();
   int mx = 0;
-  for (int b = 0; b < B && have; ++b) mx = std::max(mx, r.ctc_n()[b]);
+  for (int b = 0; b < B && have; ++b) mx = std::max(mx, k.n(p)[b]);
   if (n_max) *n_max = mx;
-  if (n) for (int b = 0; b < B; ++b) n[b] = have ? r.ctc_n()[b] : 0;
+  if (n) for (int b = 0; b < B; ++b) n[b] = have ? k.n(p)[b] : 0;
   if (!ids && !first && !last && !score) return;
   PF_CHECK(cap >= mx, PF_ERR_CAPACITY, "ctc capacity " + std::to_string(cap) + " < n_max = " + std::to_string(mx));
-  for (int b = 0; b < B && have; ++b) {
-    const size_t src = (size_t)b * r.ctc_cap, dst = (size_t)b * cap;
-    const size_t k = (size_t)std::min(cap, r.ctc_cap);
-    if (ids) { std::memcpy(ids + dst, r.ctc_ids() + src, k * 8); std::fill(ids + dst + k, ids + dst + cap, (int64_t)-1); }
-    if (first) { std::memcpy(first + dst, r.ctc_first() + src, k * 4); std::fill(first + dst + k, first + dst + cap, -1); }
-    if (last) { std::memcpy(last + dst, r.ctc_last() + src, k * 4); std::fill(last + dst + k, last + dst + cap, -1); }
-    if (score) { std::memcpy(score + dst, r.ctc_score() + src, k * 4); std::fill(score + dst + k, score + dst + cap, 0.f); }
-  }
+  if (!have) return;
+  copy_rows_padded(ids, cap, k.ids(p), r.ctc_cap, B, (int64_t)-1);
+  copy_rows_padded(first, cap, k.first(p), r.ctc_cap, B, -1);
+  copy_rows_padded(last, cap, k.last(p), r.ctc_cap, B, -1);
+  copy_rows_padded(score, cap, k.score(p), r.ctc_cap, B, 0.f);
 }
 
 }  // namespace pf

@@ -98,10 +98,17 @@ struct DecRun {
   bool operand_only = false;               // fp32: norm1 / norm3 / the context feed gemm32 alone (layernorm32, attention32 only_operand)
   const float* cache_in = nullptr; float* cache_out = nullptr;   // f16 plain walk: the streaming FSMN with its caches [layers, B, D, k - 1]
 };
+static const size_t kAlign = 256;   // of every buffer carved out of a workspace
 // carves aligned buffers out of one allocation; with base == nullptr it only measures (Engine::carve_into)
 struct Arena {
-  char* base = nullptr; size_t align = 256; size_t off = 0;
+  char* base = nullptr; size_t align = kAlign; size_t off = 0;
   template <class T> T* take(size_t bytes) { const size_t o = off; off += (bytes + align - 1) / align * align; return base ? (T*)(base + o) : nullptr; }
+};
+
+// the same rounding as offsets: carve(bytes) gives where the buffer starts and moves the caller's `off` past it
+struct Carve {
+  size_t& off; size_t align = kAlign;
+  size_t operator()(size_t bytes) const { const size_t o = off; off += (bytes + align - 1) / align * align; return o; }
 };
 
 struct DevBuf {       // grow-only device allocation
@@ -485,7 +492,16 @@ class Engine {
   int align_B_ = 0, align_cap_ = 0;
   DevBuf ws_align_;                  // the result block (HostBatchOut::align) | jobs | len [B] | targets | back-pointers; with the flag only
   int argmax_mode(bool want_logits) const { return (want_logits || (decode_flags_ & (PF_DECODE_TOPK | PF_DECODE_ALIGN))) ? 2 : 1; }
-  void queue_decode_results(int B, int L);   // behind the ids copy: the scores' copy, the collapse and its copy
+  // Behind the ids copy: the scores' copy, then one step per decoder flag.  A step lays out its ws_* buffer with the block
+  // type of decode_blocks.h (the result block, its scratch behind it), launches, and queues the one copy of the block.
+  void queue_decode_results(int B, int L);
+  void queue_topk(int B, int L);
+  void queue_ctc_beam(int B, int L);
+  void queue_align(int B, int L);
+  void queue_ctc_collapse(int B, int L);
+  // What every fetch starts with: waits for the forward, raises what its kernels reported, and returns the calling thread's
+  // published result (else the engine's last one) after checking that it was made with all of `flags` (else `refusal`)
+  const HostBatchOut& fetch_result(int flags, const char* refusal);
   uint64_t uid_ = 0;                 // key of this engine in the per-thread result store
   static uint64_t register_uid();
   static void unregister_uid(uint64_t id);

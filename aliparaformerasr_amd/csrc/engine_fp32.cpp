@@ -14,8 +14,6 @@
 
 namespace pf {
 
-static const size_t kAlign = 256;
-
 // ------------------------------------------------------------------ fp32 parity mode -------
 // math_mode = 1: the same graph with fp32 activations and fp32 weights on the fp32 matrix path (k_fp32.hip).  Supported
 // for the paraformer and SenseVoice graphs (no BiCIF head, no SeACo branch); one launch per graph node, no fusion.
@@ -259,7 +257,7 @@ void Engine::forward_fp32(const float* speech_dev, int B, int T, bool want_logit
   const int taps = mc_.cif_l_order + mc_.cif_r_order + 1;
   build_pe(T);
   size_t off = 0;
-  auto carve = [&](size_t bytes) { size_t o = off; off += round_up((int64_t)bytes, (int64_t)kAlign); return o; };
+  const Carve carve{off};
   const size_t W = (size_t)std::max(std::max(Fd, D), taps * D);
   size_t o_f[F_COUNT];
   o_f[F_X] = carve((size_t)M * D * 4); o_f[F_XN] = carve((size_t)M * W * 4); o_f[F_Q] = carve((size_t)M * D * 4);
@@ -290,7 +288,7 @@ void Engine::forward_fp32(const float* speech_dev, int B, int T, bool want_logit
   last_.cif_peak.clear();
   if (mc_.kind == "sensevoicesmall") {
     size_t o2 = 0;
-    auto c2 = [&](size_t bytes) { size_t o = o2; o2 += round_up((int64_t)bytes, (int64_t)kAlign); return o; };
+    const Carve c2{o2};
     const size_t o_lg = c2((size_t)M * ldV * 4), o_ids = c2((size_t)M * 8);
     ensure(ws_dec_, o2);
     logits_ = (float*)((char*)ws_dec_.p + o_lg); ids_dev_ = (int64_t*)((char*)ws_dec_.p + o_ids); logits_ld_ = ldV;
@@ -396,7 +394,7 @@ void Engine::timestamp_head_fp32(int B, int T) {
   const int64_t M3 = (int64_t)B * T3;
   PF_CHECK(ts_up_w32_, PF_ERR_UNSUPPORTED, "fp32 timestamp head: operands were not prepared (engine not created in math_mode 1)");
   size_t off = 0;
-  auto carve = [&](size_t bytes) { size_t o = off; off += round_up((int64_t)bytes, (int64_t)kAlign); return o; };
+  const Carve carve{off};
   const size_t o_up = carve((size_t)M3 * D * 4), o_xg = carve((size_t)M3 * 4 * D * 4), o_ho = carve((size_t)M3 * 2 * D * 4);
   const size_t o_g = carve((size_t)B * 4 * D * 4), o_h = carve((size_t)B * D * 4), o_c = carve((size_t)B * D * 4);
   const size_t o_al = carve((size_t)M3 * 4), o_pk = carve((size_t)M3 * 4);

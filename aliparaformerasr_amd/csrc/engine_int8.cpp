@@ -179,7 +179,7 @@ void Engine::forward_int8(const float* speech_dev, int B, int T, bool want_logit
   const float qscale = 1.0f / std::sqrt((float)(D / mc_.heads));
   build_pe(T);
   size_t off = 0;
-  auto carve = [&](size_t bytes) { size_t o = off; off += round_up((int64_t)bytes, (int64_t)kAlignQ); return o; };
+  const Carve carve{off, kAlignQ};
   const size_t o_x = carve(Mp * D * 4), o_t = carve(Mp * std::max(Fd, D) * 4);
   const size_t o_qkv = carve(Mp * 3 * D * 2), o_ctx = carve(Mp * D * 2), o_fsm = carve(Mp * D * 4);
   const size_t o_h = carve(Mp * std::max(F, taps * D) * 2), o_H32 = carve(Mp * D * 4), o_H16 = carve(Mp * D * 2);
@@ -240,7 +240,7 @@ void Engine::forward_int8(const float* speech_dev, int B, int T, bool want_logit
   last_flops_ = 0;
   if (mc_.kind == "sensevoicesmall") {
     size_t o2 = 0;
-    auto c2 = [&](size_t bytes) { size_t o = o2; o2 += round_up((int64_t)bytes, (int64_t)kAlignQ); return o; };
+    const Carve c2{o2, kAlignQ};
     const size_t o_lg = c2((size_t)Mp * ldV * 4), o_ids = c2((size_t)M * 8);
     ensure(ws_dec_, o2);
     logits_ = (float*)((char*)ws_dec_.p + o_lg); ids_dev_ = (int64_t*)((char*)ws_dec_.p + o_ids); logits_ld_ = ldV;
@@ -413,7 +413,7 @@ void Engine::op_qlinear(const float* x, const float* W, const float* bias, int M
   const int Kp = (int)round_up(K, 128), ldy = (int)round_up(N, 4);
   const int64_t Mp = round_up(M, 256) + 256, Np = round_up(N, 128);
   size_t off = 0;
-  auto carve = [&](size_t bytes) { size_t o = off; off += round_up((int64_t)bytes, (int64_t)kAlignQ); return o; };
+  const Carve carve{off, kAlignQ};
   const size_t ox = carve((size_t)M * K * 4), ox16 = carve((size_t)M * K * 2), oW = carve((size_t)N * K * 4), ob = carve((size_t)(N + 8) * 4);
   const size_t oa = carve((size_t)Mp * Kp), ors = carve((size_t)Mp * 4), opar = carve(64), osc = carve(quant_scratch_bytes());
   const size_t ow = carve((size_t)Np * Kp), ocs = carve((size_t)(N + 8) * 4), ozp = carve((size_t)(N + 8) * 4), ows = carve((size_t)(N + 8) * 4);

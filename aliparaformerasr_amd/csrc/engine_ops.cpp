@@ -13,8 +13,6 @@
 
 namespace pf {
 
-static const size_t kAlign = 256;
-
 // ------------------------------------------------------------------ stand-alone ops -------
 void Engine::op_lfr_cmvn_pad(const float* const* fbank, const int32_t* t80, int B, int sentinel, float* out,
                              int64_t cap, int32_t* tmax_out) {
@@ -69,116 +67,81 @@ void Engine::op_pcm_convert(const void* data, int64_t n_values, const pf_pcm_des
   PF_HIP(hipStreamSynchronize(stream_));
 }
 
+// the five decoders on caller data; ws_tmp_: the result block of decode_blocks.h, then the uploaded inputs and the scratch
 void Engine::op_topk(const float* x, int64_t rows, int V, int ld, int K, int64_t* ids, float* val, int32_t* n) {
   PF_HIP(hipSetDevice(device_));
   if (rows == 0) return;
-  const size_t in = (size_t)rows * ld, out = (size_t)rows * K;
-  // ids (int64), then val | n | x (4-byte)
-  ensure(ws_tmp_, out * 8 + (out + (size_t)rows + in) * 4);
-  int64_t* d_ids = (int64_t*)ws_tmp_.p;
-  float* d_val = (float*)(d_ids + out);
-  int32_t* d_n = (int32_t*)(d_val + out);
-  float* d_x = (float*)(d_n + rows);
-  PF_HIP(hipMemcpyAsync(d_x, x, in * 4, hipMemcpyHostToDevice, stream_));
-  launch_topk(stream_, d_x, rows, V, ld, K, d_ids, d_val, d_n);
-  PF_HIP(hipMemcpyAsync(ids, d_ids, out * 8, hipMemcpyDeviceToHost, stream_));
-  PF_HIP(hipMemcpyAsync(val, d_val, out * 4, hipMemcpyDeviceToHost, stream_));
-  PF_HIP(hipMemcpyAsync(n, d_n, (size_t)rows * 4, hipMemcpyDeviceToHost, stream_));
+  Cursor c;
+  const TopkBlock k(c, rows, K);
+  const Field<float> d_x = c.take<float>((size_t)rows * ld);
+  ensure(ws_tmp_, c.off);
+  void* ws = ws_tmp_.p;
+  PF_HIP(hipMemcpyAsync(d_x(ws), x, d_x.count * 4, hipMemcpyHostToDevice, stream_));
+  launch_topk(stream_, d_x(ws), rows, V, ld, K, k.ids(ws), k.val(ws), k.n(ws));
+  PF_HIP(hipMemcpyAsync(ids, k.ids(ws), k.ids.count * 8, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipMemcpyAsync(val, k.val(ws), k.val.count * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipMemcpyAsync(n, k.n(ws), k.n.count * 4, hipMemcpyDeviceToHost, stream_));
   PF_HIP(hipStreamSynchronize(stream_));
 }
 
 void Engine::op_ctc_beam(const float* blank_lp, const int64_t* ids, const float* val, const int32_t* n, const int32_t* lens, int B,
                          int T, int K, int blank, int W, int N, int64_t* out_ids, int32_t* out_len, double* out_score, int cap,
                          int32_t* n_hyp) {
-  PF_HIP(hipSetDevice(device_));
-  if (B == 0) return;
-  const size_t rows = (size_t)B * T, hyp = (size_t)B * N, nodes = (size_t)B * ((size_t)T * W + 1);
-  // 8-byte items first: score | ids in; then the 4-byte ones
-  const size_t words4 = rows * K + rows + rows + (size_t)B + hyp * cap + hyp + (size_t)B + 2 * nodes;
-  ensure(ws_tmp_, (hyp + rows * K) * 8 + words4 * 4);
-  double* d_score = (double*)ws_tmp_.p;
-  int64_t* d_ids = (int64_t*)(d_score + hyp);
-  float* d_val = (float*)(d_ids + rows * K);
-  float* d_lb = d_val + rows * K;
-  int32_t* d_n = (int32_t*)(d_lb + rows);
-  int32_t* d_len = d_n + rows;
-  int32_t* d_oids = d_len + B;
-  int32_t* d_olen = d_oids + hyp * cap;
-  int32_t* d_nhyp = d_olen + hyp;
-  int32_t* d_par = d_nhyp + B;
-  int32_t* d_tok = d_par + nodes;
-  if (rows > 0) {
-    PF_HIP(hipMemcpyAsync(d_ids, ids, rows * K * 8, hipMemcpyHostToDevice, stream_));
-    PF_HIP(hipMemcpyAsync(d_val, val, rows * K * 4, hipMemcpyHostToDevice, stream_));
-    PF_HIP(hipMemcpyAsync(d_lb, blank_lp, rows * 4, hipMemcpyHostToDevice, stream_));
-    PF_HIP(hipMemcpyAsync(d_n, n, rows * 4, hipMemcpyHostToDevice, stream_));
-  }
-  PF_HIP(hipMemcpyAsync(d_len, lens, (size_t)B * 4, hipMemcpyHostToDevice, stream_));
-  launch_ctc_beam(stream_, d_lb, 1, d_ids, d_val, d_n, d_len, B, T, K, blank, W, N, cap, d_par, d_tok, d_oids, d_olen, d_score, d_nhyp);
-  std::vector<int32_t> h_ids(hyp * cap);
-  if (hyp * cap > 0) PF_HIP(hipMemcpyAsync(h_ids.data(), d_oids, hyp * cap * 4, hipMemcpyDeviceToHost, stream_));
-  PF_HIP(hipMemcpyAsync(out_len, d_olen, hyp * 4, hipMemcpyDeviceToHost, stream_));
-  PF_HIP(hipMemcpyAsync(out_score, d_score, hyp * 8, hipMemcpyDeviceToHost, stream_));
-  PF_HIP(hipMemcpyAsync(n_hyp, d_nhyp, (size_t)B * 4, hipMemcpyDeviceToHost, stream_));
-  PF_HIP(hipStreamSynchronize(stream_));
-  for (size_t x = 0; x < hyp * cap; ++x) out_ids[x] = h_ids[x];
+  op_ctc_beam_hot(blank_lp, ids, val, n, lens, B, T, K, blank, W, N, nullptr, nullptr, 0, 0.f, out_ids, out_len, out_score, nullptr, nullptr,
+                  cap, n_hyp);
 }
 
+// the one body of both: a hot-word set that biases (its tables, the boost, the two extra outputs) is the optional part
 void Engine::op_ctc_beam_hot(const float* blank_lp, const int64_t* ids, const float* val, const int32_t* n, const int32_t* lens, int B,
                              int T, int K, int blank, int W, int N, const int32_t* hw_ids, const int32_t* hw_lens, int n_hw, float boost,
                              int64_t* out_ids, int32_t* out_len, double* out_score, int32_t* out_matched, double* out_loglik, int cap,
                              int32_t* n_hyp) {
   PF_CHECK(boost >= 0.f && boost <= 3.4028234e38f, PF_ERR_INVALID_ARG, "ctc_beam_hot: the boost is finite and >= 0");
-  HotwordGraph g;
-  build_hotword_graph(hw_ids, hw_lens, n_hw, hotword_vocab_bound(hw_ids, hw_lens, n_hw), g);
-  const size_t hyp = (size_t)B * N;
-  if (boost == 0.f || g.empty()) {                  // no bias: the launch of op_ctc_beam itself
-    op_ctc_beam(blank_lp, ids, val, n, lens, B, T, K, blank, W, N, out_ids, out_len, out_score, cap, n_hyp);
-    for (size_t x = 0; x < hyp; ++x) { out_matched[x] = 0; out_loglik[x] = out_score[x]; }
-    return;
-  }
+  HotwordGraph graph;                               // (op_ctc_beam gives no set: nothing is built for it)
+  if (n_hw != 0) build_hotword_graph(hw_ids, hw_lens, n_hw, hotword_vocab_bound(hw_ids, hw_lens, n_hw), graph);
+  const HotwordGraph* g = boost == 0.f || graph.empty() ? nullptr : &graph;
   PF_HIP(hipSetDevice(device_));
   if (B == 0) return;
   const size_t rows = (size_t)B * T, nodes = (size_t)B * ((size_t)T * W + 1);
-  const size_t Vh = g.tok_col.size(), tab = g.table.size();
-  // 8-byte items first: score | loglik | ids in; then the 4-byte ones
-  const size_t words4 = rows * K + rows + rows + (size_t)B + hyp * cap + hyp + hyp + (size_t)B + 2 * nodes + Vh + tab;
-  ensure(ws_tmp_, (2 * hyp + rows * K) * 8 + words4 * 4);
-  double* d_score = (double*)ws_tmp_.p;
-  double* d_ll = d_score + hyp;
-  int64_t* d_ids = (int64_t*)(d_ll + hyp);
-  float* d_val = (float*)(d_ids + rows * K);
-  float* d_lb = d_val + rows * K;
-  int32_t* d_n = (int32_t*)(d_lb + rows);
-  int32_t* d_len = d_n + rows;
-  int32_t* d_oids = d_len + B;
-  int32_t* d_olen = d_oids + hyp * cap;
-  int32_t* d_m = d_olen + hyp;
-  int32_t* d_nhyp = d_m + hyp;
-  int32_t* d_par = d_nhyp + B;
-  int32_t* d_tok = d_par + nodes;
-  int32_t* d_col = d_tok + nodes;
-  int32_t* d_tab = d_col + Vh;
+  Cursor c;
+  const BeamBlock k(c, B, N, cap);
+  const BeamHotBlock h(c, g ? B : 0, N);
+  const TopkBlock in(c, rows, K);                   // the lists as op_topk gives them
+  const Field<float> d_lb = c.take<float>(rows);
+  const Field<int32_t> d_len = c.take<int32_t>(B), d_par = c.take<int32_t>(nodes), d_tok = c.take<int32_t>(nodes);
+  const Field<int32_t> d_col = c.take<int32_t>(g ? g->tok_col.size() : 0), d_tab = c.take<int32_t>(g ? g->table.size() : 0);
+  ensure(ws_tmp_, c.off);
+  void* ws = ws_tmp_.p;
   if (rows > 0) {
-    PF_HIP(hipMemcpyAsync(d_ids, ids, rows * K * 8, hipMemcpyHostToDevice, stream_));
-    PF_HIP(hipMemcpyAsync(d_val, val, rows * K * 4, hipMemcpyHostToDevice, stream_));
-    PF_HIP(hipMemcpyAsync(d_lb, blank_lp, rows * 4, hipMemcpyHostToDevice, stream_));
-    PF_HIP(hipMemcpyAsync(d_n, n, rows * 4, hipMemcpyHostToDevice, stream_));
+    PF_HIP(hipMemcpyAsync(in.ids(ws), ids, in.ids.count * 8, hipMemcpyHostToDevice, stream_));
+    PF_HIP(hipMemcpyAsync(in.val(ws), val, in.val.count * 4, hipMemcpyHostToDevice, stream_));
+    PF_HIP(hipMemcpyAsync(d_lb(ws), blank_lp, rows * 4, hipMemcpyHostToDevice, stream_));
+    PF_HIP(hipMemcpyAsync(in.n(ws), n, rows * 4, hipMemcpyHostToDevice, stream_));
   }
-  PF_HIP(hipMemcpyAsync(d_len, lens, (size_t)B * 4, hipMemcpyHostToDevice, stream_));
-  PF_HIP(hipMemcpyAsync(d_col, g.tok_col.data(), Vh * 4, hipMemcpyHostToDevice, stream_));
-  PF_HIP(hipMemcpyAsync(d_tab, g.table.data(), tab * 4, hipMemcpyHostToDevice, stream_));
-  launch_ctc_beam_hot(stream_, d_lb, 1, d_ids, d_val, d_n, d_len, B, T, K, blank, W, N, cap, d_par, d_tok, d_col, (int)Vh, d_tab, g.A,
-                      boost, d_oids, d_olen, d_score, d_m, d_ll, d_nhyp);
-  std::vector<int32_t> h_ids(hyp * cap);
-  if (hyp * cap > 0) PF_HIP(hipMemcpyAsync(h_ids.data(), d_oids, hyp * cap * 4, hipMemcpyDeviceToHost, stream_));
-  PF_HIP(hipMemcpyAsync(out_len, d_olen, hyp * 4, hipMemcpyDeviceToHost, stream_));
-  PF_HIP(hipMemcpyAsync(out_score, d_score, hyp * 8, hipMemcpyDeviceToHost, stream_));
-  PF_HIP(hipMemcpyAsync(out_loglik, d_ll, hyp * 8, hipMemcpyDeviceToHost, stream_));
-  PF_HIP(hipMemcpyAsync(out_matched, d_m, hyp * 4, hipMemcpyDeviceToHost, stream_));
-  PF_HIP(hipMemcpyAsync(n_hyp, d_nhyp, (size_t)B * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipMemcpyAsync(d_len(ws), lens, d_len.count * 4, hipMemcpyHostToDevice, stream_));
+  if (g) {
+    PF_HIP(hipMemcpyAsync(d_col(ws), g->tok_col.data(), d_col.count * 4, hipMemcpyHostToDevice, stream_));
+    PF_HIP(hipMemcpyAsync(d_tab(ws), g->table.data(), d_tab.count * 4, hipMemcpyHostToDevice, stream_));
+    launch_ctc_beam_hot(stream_, d_lb(ws), 1, in.ids(ws), in.val(ws), in.n(ws), d_len(ws), B, T, K, blank, W, N, cap, d_par(ws), d_tok(ws),
+                        d_col(ws), (int)d_col.count, d_tab(ws), g->A, boost, k.ids(ws), k.len(ws), k.score(ws), h.matched(ws), h.loglik(ws),
+                        k.n_hyp(ws));
+  } else {
+    launch_ctc_beam(stream_, d_lb(ws), 1, in.ids(ws), in.val(ws), in.n(ws), d_len(ws), B, T, K, blank, W, N, cap, d_par(ws), d_tok(ws),
+                    k.ids(ws), k.len(ws), k.score(ws), k.n_hyp(ws));
+  }
+  std::vector<int32_t> h_ids(k.ids.count);
+  if (!h_ids.empty()) PF_HIP(hipMemcpyAsync(h_ids.data(), k.ids(ws), h_ids.size() * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipMemcpyAsync(out_len, k.len(ws), k.len.count * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipMemcpyAsync(out_score, k.score(ws), k.score.count * 8, hipMemcpyDeviceToHost, stream_));
+  if (g) {
+    PF_HIP(hipMemcpyAsync(out_loglik, h.loglik(ws), h.loglik.count * 8, hipMemcpyDeviceToHost, stream_));
+    PF_HIP(hipMemcpyAsync(out_matched, h.matched(ws), h.matched.count * 4, hipMemcpyDeviceToHost, stream_));
+  }
+  PF_HIP(hipMemcpyAsync(n_hyp, k.n_hyp(ws), k.n_hyp.count * 4, hipMemcpyDeviceToHost, stream_));
   PF_HIP(hipStreamSynchronize(stream_));            // g's host arrays are read by the copies queued above until here
-  for (size_t x = 0; x < hyp * cap; ++x) out_ids[x] = h_ids[x];
+  std::copy(h_ids.begin(), h_ids.end(), out_ids);
+  if (!g && out_matched)                            // a set that does not bias: op_ctc_beam's launch ran
+    for (size_t x = 0; x < k.score.count; ++x) { out_matched[x] = 0; out_loglik[x] = out_score[x]; }
 }
 
 void Engine::op_ctc_align(const float* lp, int B, int T, int V, int ld, const int32_t* tgt, const int32_t* tlen, const int32_t* lens,
@@ -186,33 +149,26 @@ void Engine::op_ctc_align(const float* lp, int B, int T, int V, int ld, const in
                           float* tok_score) {
   PF_HIP(hipSetDevice(device_));
   if (B == 0 || H == 0) return;
-  const size_t rows = (size_t)B * T, jobs = (size_t)B * H, bp_stride = ctc_align_bp_words(T, cap);
-  // the 8-byte item first, then the 4-byte ones
-  const size_t words4 = jobs * 2 + jobs * cap * 3 + jobs * cap + jobs + (size_t)B + rows * ld + jobs * bp_stride;
-  ensure(ws_tmp_, jobs * 8 + words4 * 4);
-  double* d_ll = (double*)ws_tmp_.p;
-  float* d_ps = (float*)(d_ll + jobs);
-  int32_t* d_ok = (int32_t*)(d_ps + jobs);
-  int32_t* d_first = d_ok + jobs;
-  int32_t* d_last = d_first + jobs * cap;
-  float* d_tok = (float*)(d_last + jobs * cap);
-  int32_t* d_tgt = (int32_t*)(d_tok + jobs * cap);
-  int32_t* d_tlen = d_tgt + jobs * cap;
-  int32_t* d_len = d_tlen + jobs;
-  float* d_lp = (float*)(d_len + B);
-  uint32_t* d_bp = (uint32_t*)(d_lp + rows * ld);
-  if (rows > 0) PF_HIP(hipMemcpyAsync(d_lp, lp, rows * ld * 4, hipMemcpyHostToDevice, stream_));
-  PF_HIP(hipMemcpyAsync(d_tgt, tgt, jobs * cap * 4, hipMemcpyHostToDevice, stream_));
-  PF_HIP(hipMemcpyAsync(d_tlen, tlen, jobs * 4, hipMemcpyHostToDevice, stream_));
-  PF_HIP(hipMemcpyAsync(d_len, lens, (size_t)B * 4, hipMemcpyHostToDevice, stream_));
-  launch_ctc_align(stream_, d_lp, ld, V, d_tgt, d_tlen, d_len, B, T, H, cap, d_bp, (int64_t)bp_stride, d_ps, d_ll, d_ok, d_first, d_last,
-                   d_tok);
-  PF_HIP(hipMemcpyAsync(path_score, d_ps, jobs * 4, hipMemcpyDeviceToHost, stream_));
-  PF_HIP(hipMemcpyAsync(loglik, d_ll, jobs * 8, hipMemcpyDeviceToHost, stream_));
-  PF_HIP(hipMemcpyAsync(ok, d_ok, jobs * 4, hipMemcpyDeviceToHost, stream_));
-  PF_HIP(hipMemcpyAsync(first, d_first, jobs * cap * 4, hipMemcpyDeviceToHost, stream_));
-  PF_HIP(hipMemcpyAsync(last, d_last, jobs * cap * 4, hipMemcpyDeviceToHost, stream_));
-  PF_HIP(hipMemcpyAsync(tok_score, d_tok, jobs * cap * 4, hipMemcpyDeviceToHost, stream_));
+  const size_t rows = (size_t)B * T, bp_stride = ctc_align_bp_words(T, cap);
+  Cursor c;
+  const AlignBlock k(c, B, H, cap);                 // len: the targets' lengths, uploaded
+  const Field<int32_t> d_tgt = c.take<int32_t>(k.first.count), d_len = c.take<int32_t>(B);   // a target slot per token slot
+  const Field<float> d_lp = c.take<float>(rows * ld);
+  const Field<uint32_t> d_bp = c.take<uint32_t>(k.ok.count * bp_stride);          // per job
+  ensure(ws_tmp_, c.off);
+  void* ws = ws_tmp_.p;
+  if (rows > 0) PF_HIP(hipMemcpyAsync(d_lp(ws), lp, d_lp.count * 4, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipMemcpyAsync(d_tgt(ws), tgt, d_tgt.count * 4, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipMemcpyAsync(k.len(ws), tlen, k.len.count * 4, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipMemcpyAsync(d_len(ws), lens, d_len.count * 4, hipMemcpyHostToDevice, stream_));
+  launch_ctc_align(stream_, d_lp(ws), ld, V, d_tgt(ws), k.len(ws), d_len(ws), B, T, H, cap, d_bp(ws), (int64_t)bp_stride, k.path(ws),
+                   k.loglik(ws), k.ok(ws), k.first(ws), k.last(ws), k.tok(ws));
+  PF_HIP(hipMemcpyAsync(path_score, k.path(ws), k.path.count * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipMemcpyAsync(loglik, k.loglik(ws), k.loglik.count * 8, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipMemcpyAsync(ok, k.ok(ws), k.ok.count * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipMemcpyAsync(first, k.first(ws), k.first.count * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipMemcpyAsync(last, k.last(ws), k.last.count * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipMemcpyAsync(tok_score, k.tok(ws), k.tok.count * 4, hipMemcpyDeviceToHost, stream_));
   PF_HIP(hipStreamSynchronize(stream_));
 }
 
@@ -220,26 +176,23 @@ void Engine::op_ctc_collapse(const int64_t* ids, const float* scores, const int3
                              int64_t* ids_out, int32_t* first_out, int32_t* last_out, float* score_out, int cap, int32_t* n_out) {
   PF_HIP(hipSetDevice(device_));
   if (B == 0) return;
-  const size_t in = (size_t)B * T, out = (size_t)B * cap;
-  // ids | ids_out (int64), then scores | score_out | first | last | lens | n (4-byte)
-  ensure(ws_tmp_, (in + out) * 8 + (in + 3 * out + 2 * (size_t)B) * 4);
-  int64_t* d_ids = (int64_t*)ws_tmp_.p;
-  int64_t* d_io = d_ids + in;
-  float* d_sc = (float*)(d_io + out);
-  float* d_so = d_sc + in;
-  int32_t* d_fo = (int32_t*)(d_so + out);
-  int32_t* d_lo = d_fo + out;
-  int32_t* d_len = d_lo + out;
-  int32_t* d_n = d_len + B;
-  PF_HIP(hipMemcpyAsync(d_ids, ids, in * 8, hipMemcpyHostToDevice, stream_));
-  PF_HIP(hipMemcpyAsync(d_sc, scores, in * 4, hipMemcpyHostToDevice, stream_));
-  PF_HIP(hipMemcpyAsync(d_len, lens, (size_t)B * 4, hipMemcpyHostToDevice, stream_));
-  launch_ctc_collapse(stream_, d_ids, d_sc, d_len, B, T, blank, cap, d_n, d_io, d_fo, d_lo, d_so);
-  PF_HIP(hipMemcpyAsync(ids_out, d_io, out * 8, hipMemcpyDeviceToHost, stream_));
-  PF_HIP(hipMemcpyAsync(first_out, d_fo, out * 4, hipMemcpyDeviceToHost, stream_));
-  PF_HIP(hipMemcpyAsync(last_out, d_lo, out * 4, hipMemcpyDeviceToHost, stream_));
-  PF_HIP(hipMemcpyAsync(score_out, d_so, out * 4, hipMemcpyDeviceToHost, stream_));
-  PF_HIP(hipMemcpyAsync(n_out, d_n, (size_t)B * 4, hipMemcpyDeviceToHost, stream_));
+  const size_t in = (size_t)B * T;
+  Cursor c;
+  const CtcBlock k(c, B, cap);
+  const Field<int64_t> d_ids = c.take<int64_t>(in);
+  const Field<float> d_sc = c.take<float>(in);
+  const Field<int32_t> d_len = c.take<int32_t>(B);
+  ensure(ws_tmp_, c.off);
+  void* ws = ws_tmp_.p;
+  PF_HIP(hipMemcpyAsync(d_ids(ws), ids, in * 8, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipMemcpyAsync(d_sc(ws), scores, in * 4, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipMemcpyAsync(d_len(ws), lens, d_len.count * 4, hipMemcpyHostToDevice, stream_));
+  launch_ctc_collapse(stream_, d_ids(ws), d_sc(ws), d_len(ws), B, T, blank, cap, k.n(ws), k.ids(ws), k.first(ws), k.last(ws), k.score(ws));
+  PF_HIP(hipMemcpyAsync(ids_out, k.ids(ws), k.ids.count * 8, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipMemcpyAsync(first_out, k.first(ws), k.first.count * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipMemcpyAsync(last_out, k.last(ws), k.last.count * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipMemcpyAsync(score_out, k.score(ws), k.score.count * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipMemcpyAsync(n_out, k.n(ws), k.n.count * 4, hipMemcpyDeviceToHost, stream_));
   PF_HIP(hipStreamSynchronize(stream_));
   for (int b = 0; b < B; ++b)
     PF_CHECK(n_out[b] <= cap, PF_ERR_CAPACITY, "ctc_collapse: capacity " + std::to_string(cap) + " < " + std::to_string(n_out[b]) + " tokens");
@@ -251,7 +204,7 @@ void Engine::op_gemm(const float* A, const float* W, const float* bias, int M, i
   const int Kp = (int)round_up(K, 64);
   const int64_t Mp = round_up(M, 256), Np = round_up(N, 256);
   size_t off = 0;
-  auto carve = [&](size_t bytes) { size_t o = off; off += round_up((int64_t)bytes, (int64_t)kAlign); return o; };
+  const Carve carve{off};
   const size_t oA = carve((size_t)M * K * 4), oW = carve((size_t)N * K * 4), ob = carve((size_t)N * 4);
   const size_t oA16 = carve((size_t)Mp * Kp * 2), oW16 = carve((size_t)Np * Kp * 2), oC = carve((size_t)Mp * N * 4);
   ensure(ws_tmp_, off);
@@ -307,7 +260,7 @@ void Engine::op_linear32(const float* x, const float* W, const float* bias, cons
   const int ldc = (int)round_up(N, 4);
   const int64_t Mp = round_up(M, 256) + 128, Np = round_up(N, 256);
   size_t off = 0;
-  auto carve = [&](size_t bytes) { size_t o = off; off += round_up((int64_t)bytes, (int64_t)kAlign); return o; };
+  const Carve carve{off};
   const size_t ox = carve((size_t)Mp * K * 4), oW = carve((size_t)Np * K * 4), ob = carve((size_t)Np * 4), orr = carve((size_t)Mp * ldc * 4),
                oy = carve((size_t)Mp * ldc * 4);
   ensure(ws_tmp_, off);
@@ -331,7 +284,7 @@ void Engine::op_ffn32(const float* x, const float* W1, const float* b1, const fl
   PF_HIP(hipSetDevice(device_));
   const int64_t Mp = round_up(M, 256) + 128, Dp = round_up(D, 256), Fp = round_up(F, 256);
   size_t off = 0;
-  auto carve = [&](size_t bytes) { size_t o = off; off += round_up((int64_t)bytes, (int64_t)kAlign); return o; };
+  const Carve carve{off};
   const size_t ox = carve((size_t)Mp * D * 4), o1 = carve((size_t)Fp * D * 4), ob1 = carve((size_t)Fp * 4), o2 = carve((size_t)Dp * F * 4),
                ob2 = carve((size_t)Dp * 4), oh = carve((size_t)Mp * F * 4), oy = carve((size_t)Mp * D * 4);
   ensure(ws_tmp_, off);
@@ -370,7 +323,7 @@ void Engine::op_gemm_ex(const pf_gemm_desc& ds, const float* A, const float* W, 
   const int64_t Mp = round_up(M, 256) + 128, Np = round_up(N, 256);
   const int ld32 = (int)round_up(N, 4), ld16 = (int)round_up(N, 8);
   size_t off = 0;
-  auto carve = [&](size_t bytes) { size_t o = off; off += round_up((int64_t)bytes, (int64_t)kAlign); return o; };
+  const Carve carve{off};
   const size_t oA = carve((size_t)M * K * 4), oW = carve((size_t)N * K * 4), ob = carve((size_t)N * 4);
   const size_t oA16 = carve((size_t)Mp * Kp * 2), oW16 = carve((size_t)Np * Kp * 2);
   const size_t oR = carve((size_t)Mp * ld32 * 4), oD = carve((size_t)Mp * ld32 * 4), oC = carve((size_t)Mp * std::max(ld32, ld16) * 4);
@@ -449,7 +402,7 @@ void Engine::op_gemm_rc(const pf_gemm_rc_desc& ds, const float* A, const float* 
   const int64_t Mp = round_up(M, 256) + 128;
   const int k = ds.fsmn_k;
   size_t off = 0;
-  auto carve = [&](size_t bytes) { size_t o = off; off += round_up((int64_t)bytes, (int64_t)kAlign); return o; };
+  const Carve carve{off};
   const size_t o32 = carve((size_t)std::max<int64_t>((int64_t)M * std::max(K, N), (int64_t)N * K) * 4);
   const size_t oA16 = carve((size_t)Mp * K * 2), oW16 = carve((size_t)N * K * 2), ob = carve((size_t)N * 4);
   const size_t oR = carve((size_t)Mp * N * 4), oV = carve((size_t)(Mp + 128) * 3 * N * 2), owT = carve((size_t)std::max(k, 1) * N * 4);
@@ -541,7 +494,7 @@ void Engine::op_ffn(const float* x, const float* w1, const float* b1, const floa
   PF_CHECK(M > 0 && D % 64 == 0 && F % 64 == 0, PF_ERR_INVALID_ARG, "ffn: D and F must be multiples of 64");
   const int64_t Mp = round_up(M, 256) + 128, Fp = round_up(F, 256), Dp = round_up(D, 256);
   size_t off = 0;
-  auto carve = [&](size_t bytes) { size_t o = off; off += round_up((int64_t)bytes, (int64_t)kAlign); return o; };
+  const Carve carve{off};
   const size_t o32 = carve((size_t)std::max<int64_t>((int64_t)M * D, (int64_t)F * D) * 4);
   const size_t ox16 = carve((size_t)Mp * D * 2), ow1 = carve((size_t)Fp * D * 2), ow2 = carve((size_t)Dp * F * 2);
   const size_t ob1 = carve((size_t)F * 4), ob2 = carve((size_t)D * 4), oh = carve((size_t)Mp * F * 2);
@@ -581,7 +534,7 @@ void Engine::op_dec_ffn_fused(const pf_dec_ffn_desc& ds, float* t_out, float* n_
   const bool op = ds.ctx != nullptr;
   const int64_t Mp = round_up(M, 256) + 128;
   size_t off = 0;
-  auto carve = [&](size_t bytes) { size_t o = off; off += round_up((int64_t)bytes, (int64_t)kAlign); return o; };
+  const Carve carve{off};
   const size_t o32 = carve((size_t)std::max<int64_t>((int64_t)M * D, (int64_t)F * D) * 4);
   const size_t ox16 = carve((size_t)Mp * D * 2), ow1 = carve((size_t)F * D * 2), ow2 = carve((size_t)D * F * 4);
   const size_t oimg = carve(ffn_dec_image_bytes()), ows = carve(ffn_dec_workspace_bytes(M, splits));
@@ -640,7 +593,7 @@ void Engine::op_ffn_fused(const float* x, const float* w1, const float* b1, cons
   PF_CHECK(op || x, PF_ERR_INVALID_ARG, "ffn_fused: missing operand");
   const int64_t Mp = round_up(M, 256) + 128;
   size_t off = 0;
-  auto carve = [&](size_t bytes) { size_t o = off; off += round_up((int64_t)bytes, (int64_t)kAlign); return o; };
+  const Carve carve{off};
   const size_t o32 = carve((size_t)std::max<int64_t>((int64_t)M * D, (int64_t)F * D) * 4);
   const size_t ox16 = carve((size_t)Mp * D * 2), ow1 = carve((size_t)F * D * 2), ow2 = carve((size_t)D * F * 2);
   const size_t owt = carve(ffn_fused_weight_bytes());
@@ -746,7 +699,7 @@ void Engine::op_fsmn_enc(const float* v, const float* w, int B, int T, int D, in
   for (int c = 0; c < D; ++c)
     for (int j = 0; j < k; ++j) wT[(size_t)j * D + c] = w[(size_t)c * k + j];
   size_t off = 0;
-  auto carve = [&](size_t bytes) { size_t o2 = off; off += round_up((int64_t)bytes, (int64_t)kAlign); return o2; };
+  const Carve carve{off};
   const size_t ov = carve(n * 4), oq = carve(((size_t)B * T + 128) * 3 * D * 2), ow = carve(wT.size() * 4), oy = carve(n * 4);
   ensure(ws_tmp_, off);
   char* base = (char*)ws_tmp_.p;
@@ -769,7 +722,7 @@ void Engine::op_fsmn_dec(const float* tn, const float* w, const int32_t* token_n
   for (int c = 0; c < D; ++c)
     for (int j = 0; j < k; ++j) wT[(size_t)j * D + c] = w[(size_t)c * k + j];
   size_t off = 0;
-  auto carve = [&](size_t bytes) { size_t o2 = off; off += round_up((int64_t)bytes, (int64_t)kAlign); return o2; };
+  const Carve carve{off};
   const size_t ot = carve(n * 4), ox = carve(n * 4), ow = carve(wT.size() * 4), on = carve((size_t)B * 4);
   ensure(ws_tmp_, off);
   char* base = (char*)ws_tmp_.p;
@@ -793,7 +746,7 @@ void Engine::op_lstm(const float* xg, const float* whh, int B, int T3, int D, in
   PF_HIP(hipSetDevice(device_));
   const size_t rows = (size_t)B * T3, nw = (size_t)ndir * 4 * D * D;
   size_t off = 0;
-  auto carve = [&](size_t bytes) { size_t o = off; off += round_up((int64_t)bytes, (int64_t)kAlign); return o; };
+  const Carve carve{off};
   const size_t o_xg = carve(rows * ndir * 4 * D * 4), o_w32 = carve(nw * 4), o_w16 = carve(nw * 2 * 2);
   const size_t o_hs = carve((size_t)ndir * 4 * B * 2 * D * 2), o_cs = carve((size_t)ndir * B * D * 4), o_ho = carve(rows * ndir * D * 4);
   const size_t o_sw = carve(256), o_xd = carve(rows * 4 * D * 4), o_g = carve((size_t)B * 4 * D * 4), o_h = carve((size_t)B * D * 4);
@@ -840,7 +793,7 @@ void Engine::op_us_peak(const float* hout, const float* w, const float* b0, floa
   PF_HIP(hipSetDevice(device_));
   const size_t rows = (size_t)B * T3;
   size_t off = 0;
-  auto carve = [&](size_t bytes) { size_t o = off; off += round_up((int64_t)bytes, (int64_t)kAlign); return o; };
+  const Carve carve{off};
   const size_t o_h = carve(rows * W * 4), o_w = carve((size_t)W * 4), o_b = carve(4), o_n = carve((size_t)B * 4), o_al = carve(rows * 4),
                o_pk = carve(rows * 4);
   ensure(ws_tmp_, off);
@@ -880,7 +833,7 @@ void Engine::op_layernorm(const float* x, const float* g, const float* b, int64_
   PF_HIP(hipSetDevice(device_));
   if (rows == 0) return;
   size_t off = 0;
-  auto carve = [&](size_t bytes) { size_t o = off; off += round_up((int64_t)bytes, (int64_t)kAlign); return o; };
+  const Carve carve{off};
   const size_t ox = carve((size_t)rows * D * 4), og = carve((size_t)D * 4), obb = carve((size_t)D * 4), oy = carve((size_t)rows * D * 4);
   ensure(ws_tmp_, off);
   char* base = (char*)ws_tmp_.p;
@@ -898,7 +851,7 @@ void Engine::op_attention(const float* q, const float* k, const float* v, int B,
   const int Dm = H * 128;
   const int64_t nq = (int64_t)B * Lq, nk = (int64_t)B * Lk;
   size_t off = 0;
-  auto carve = [&](size_t bytes) { size_t o2 = off; off += round_up((int64_t)bytes, (int64_t)kAlign); return o2; };
+  const Carve carve{off};
   const size_t oin = carve((size_t)std::max(nq, nk) * Dm * 4);
   const size_t oq = carve((size_t)(nq + 128) * Dm * 2), ok = carve((size_t)(nk + 128) * Dm * 2);
   const size_t ov = carve((size_t)(nk + 128) * Dm * 2), oo = carve((size_t)(nq + 128) * Dm * 2), oo32 = carve((size_t)nq * Dm * 4);
@@ -966,7 +919,7 @@ void Engine::op_attention_ex(const float* q, const float* k, const float* v, int
   const size_t obytes = (size_t)(nq + kSlack) * orow * oes;
   PF_CHECK(raw_bytes == (int64_t)obytes, PF_ERR_INVALID_ARG, "attention_ex: raw_bytes must be " + std::to_string(obytes));
   size_t off = 0;
-  auto carve = [&](size_t bytes) { size_t o2 = off; off += round_up((int64_t)bytes, (int64_t)kAlign); return o2; };
+  const Carve carve{off};
   size_t om[3];
   for (int m = 0; m < 3; ++m) om[m] = carve((size_t)rows[m] * ld[m] * es);
   const size_t oo = carve(obytes), org = carve(quant_scratch_bytes());
@@ -1067,7 +1020,7 @@ void Engine::op_qkv_attention(const float* x, const float* w, const float* bias,
   PF_CHECK(gemm_qkvp_applicable(M, Kpad, Kpad, Kpad, D), PF_ERR_INVALID_ARG, "qkv_attention: shape not covered by the 256 x 192 kernel");
   const int64_t Mp = round_up(M, 256) + 128;
   size_t off = 0;
-  auto carve = [&](size_t bytes) { size_t o2 = off; off += round_up((int64_t)bytes, (int64_t)kAlign); return o2; };
+  const Carve carve{off};
   const size_t o32 = carve((size_t)std::max<int64_t>((int64_t)M * K, (int64_t)N * K) * 4), oA = carve((size_t)Mp * Kpad * 2);
   const size_t oW = carve((size_t)N * Kpad * 2), oWp = carve((size_t)N * Kpad * 2), ob = carve((size_t)N * 4), obp = carve((size_t)N * 4);
   const size_t oqk = carve((size_t)Mp * 2 * D * 2), ov = carve((size_t)Mp * D * 2), oc = carve((size_t)Mp * D * 2);
@@ -1124,7 +1077,7 @@ void Engine::op_fsmn(const float* v, const float* w, const float* mask, int B, i
   for (int c = 0; c < D; ++c)
     for (int j = 0; j < k; ++j) wT[(size_t)j * D + c] = w[(size_t)c * k + j];
   size_t off = 0;
-  auto carve = [&](size_t bytes) { size_t o2 = off; off += round_up((int64_t)bytes, (int64_t)kAlign); return o2; };
+  const Carve carve{off};
   const size_t ov = carve(n * 4), ow = carve(wT.size() * 4), om = carve((size_t)B * T * 4), oy = carve(n * 4);
   ensure(ws_tmp_, off);
   char* base = (char*)ws_tmp_.p;
@@ -1143,7 +1096,7 @@ void Engine::op_cif(const float* H, const float* alphas, int B, int T, int D, fl
   PF_CHECK(D % 4 == 0 && B > 0 && T > 0, PF_ERR_INVALID_ARG, "cif: bad shape");
   const int T1 = T + 1;
   size_t off = 0;
-  auto carve = [&](size_t bytes) { size_t o2 = off; off += round_up((int64_t)bytes, (int64_t)kAlign); return o2; };
+  const Carve carve{off};
   const size_t oH = carve((size_t)B * T * D * 4), oa = carve((size_t)B * T1 * 4), ofc = carve((size_t)B * 4), otn = carve((size_t)B * 4);
   const size_t off_ = carve((size_t)B * T1 * 4), owc = carve((size_t)B * T1 * 4), owr = carve((size_t)B * T1 * 4), omx = carve(256);
   const size_t oE = carve((size_t)B * std::max(Lcap, 1) * D * 4);

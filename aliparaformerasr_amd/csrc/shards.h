@@ -20,64 +20,10 @@
 #include <vector>
 
 #include "common.h"
+// HostBatchOut (what a shard run fills and the merge reads) is defined beside the layouts of the blocks it carries
+#include "decode_blocks.h"
 
 namespace pf {
-
-struct HostBatchOut { // results of a forward, host side
-  int B = 0, L = 0, V = 0, T = 0;
-  std::vector<int64_t> ids;        // [B, L]
-  std::vector<int32_t> token_num;  // [B]
-  std::vector<int32_t> fire_count; // [B]
-  std::vector<float> cif_peak;     // [B, peak_len] us_cif_peak (timestamp models), else empty
-  int peak_len = 0;
-  std::vector<float> logits;       // [B, L, V] host copy (per-thread result slots only)
-  bool has_logits = false;
-  // decoding extras (Engine::set_decode); empty without the flag
-  int decode_flags = 0;
-  std::vector<float> scores;       // [B, L] log-prob of ids[b, l]
-  // CTC collapse as the kernel leaves it, one block: ids [B, cap] int64 | first [B, cap] | last [B, cap] int32 |
-  // score [B, cap] fp32 | n [B] int32
-  std::vector<int64_t> ctc;
-  int ctc_cap = 0;
-  static size_t ctc_words(int B, int cap) { return (size_t)B * cap + ((size_t)B * cap * 12 + (size_t)B * 4 + 7) / 8; }
-  const int64_t* ctc_ids() const { return ctc.data(); }
-  const int32_t* ctc_first() const { return (const int32_t*)(ctc.data() + (size_t)B * ctc_cap); }
-  const int32_t* ctc_last() const { return ctc_first() + (size_t)B * ctc_cap; }
-  const float* ctc_score() const { return (const float*)(ctc_last() + (size_t)B * ctc_cap); }
-  const int32_t* ctc_n() const { return ctc_last() + 2 * (size_t)B * ctc_cap; }
-  // top-k alternatives as the kernel leaves them, one block: ids [B * L, K] int64 | val [B * L, K] fp32 | n [B * L] int32
-  std::vector<int64_t> topk;
-  int topk_k = 0;
-  static size_t topk_words(int64_t rows, int K) { return (size_t)rows * K + ((size_t)rows * K * 4 + (size_t)rows * 4 + 7) / 8; }
-  const int64_t* topk_ids() const { return topk.data(); }
-  const float* topk_val() const { return (const float*)(topk.data() + (size_t)B * L * topk_k); }
-  const int32_t* topk_n() const { return (const int32_t*)(topk_val() + (size_t)B * L * topk_k); }
-  // CTC beam search as the kernel leaves it, one block: score [B, N] float64 | ids [B, N, cap] int32 | len [B, N] | n_hyp [B]
-  std::vector<int64_t> beam;
-  int beam_n = 0, beam_cap = 0;
-  static size_t beam_words(int B, int N, int cap) { return (size_t)B * N + ((size_t)B * N * cap * 4 + (size_t)B * N * 4 + (size_t)B * 4 + 7) / 8; }
-  const double* beam_score() const { return (const double*)beam.data(); }
-  const int32_t* beam_ids() const { return (const int32_t*)(beam.data() + (size_t)B * beam_n); }
-  const int32_t* beam_len() const { return beam_ids() + (size_t)B * beam_n * beam_cap; }
-  const int32_t* beam_nhyp() const { return beam_len() + (size_t)B * beam_n; }
-  // the biased search's extras, one block: loglik_sum [B, N] float64 | matched [B, N] int32; empty when the search ran unbiased
-  std::vector<int64_t> beam_hot;
-  static size_t beam_hot_words(int B, int N) { return (size_t)B * N + ((size_t)B * N * 4 + 7) / 8; }
-  const double* beam_loglik() const { return (const double*)beam_hot.data(); }
-  const int32_t* beam_matched() const { return (const int32_t*)(beam_hot.data() + (size_t)B * beam_n); }
-  // CTC forced alignment as the kernel leaves it, one block (the float64 item first, for its alignment):
-  // loglik [B, H] float64 | path_score [B, H] fp32 | ok [B, H] | len [B, H] | first [B, H, cap] | last | tok_score fp32
-  std::vector<int64_t> align;
-  int align_h = 0, align_cap = 0;
-  static size_t align_words(int B, int H, int cap) { return (size_t)B * H + ((size_t)B * H * 12 + (size_t)B * H * cap * 12 + 7) / 8; }
-  const double* align_loglik() const { return (const double*)align.data(); }
-  const float* align_path() const { return (const float*)(align.data() + (size_t)B * align_h); }
-  const int32_t* align_ok() const { return (const int32_t*)(align_path() + (size_t)B * align_h); }
-  const int32_t* align_len() const { return align_ok() + (size_t)B * align_h; }
-  const int32_t* align_first() const { return align_len() + (size_t)B * align_h; }
-  const int32_t* align_last() const { return align_first() + (size_t)B * align_h * align_cap; }
-  const float* align_tok() const { return (const float*)(align_last() + (size_t)B * align_h * align_cap); }
-};
 
 // rendezvous of the G worker threads with a max-reduction; abort() releases every waiter with an Error
 class MaxBarrier {

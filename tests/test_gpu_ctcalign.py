@@ -542,3 +542,78 @@ def test_cli_prints_the_pairs(tmp_path, sv_embed):
     out = io.StringIO()
     ex.offline_recognizer(method="one", model="m", base=str(tmp_path), files=[str(d / "a.wav")], out=out, nbest=3, topk=4, beam=8)
     assert "align" not in out.getvalue()                                          # without -align nothing changes
+
+
+# ---- 4: the decoders share one forward: together they leave what each leaves alone --------------------------------------------
+def _bits64(a):
+    return np.ascontiguousarray(a, np.float64).view(np.uint64)
+
+
+def _same_beam(r1, r0, hot):
+    for name in ("n_hyp", "ids", "len"):
+        np.testing.assert_array_equal(getattr(r1.beam, name), getattr(r0.beam, name), err_msg=name)
+    np.testing.assert_array_equal(_bits64(r1.beam.score), _bits64(r0.beam.score))
+    if hot:
+        np.testing.assert_array_equal(r1.beam.matched, r0.beam.matched)
+        np.testing.assert_array_equal(_bits64(r1.beam.loglik_sum), _bits64(r0.beam.loglik_sum))
+    else:
+        assert r1.beam.matched is None and r0.beam.matched is None and r1.beam.loglik_sum is None and r0.beam.loglik_sum is None
+
+
+def _same_align(r1, r0):
+    a1, a0 = r1.align, r0.align
+    assert a1.H == a0.H
+    for name in ("ok", "len", "first", "last"):
+        np.testing.assert_array_equal(getattr(a1, name), getattr(a0, name), err_msg=name)
+    np.testing.assert_array_equal(_bits(a1.path_score), _bits(a0.path_score))
+    np.testing.assert_array_equal(_bits(a1.tok_score), _bits(a0.tok_score))
+    np.testing.assert_array_equal(_bits64(a1.loglik), _bits64(a0.loglik))
+
+
+def test_every_flag_at_once_equals_each_flag_alone(sv_embed):
+    """One engine with CTC | TOPK | CTC_BEAM | ALIGN (W = 8, N = 4, targets of lengths [-1, n, 0]) against engines that have
+    only the flags a field needs: ids, scores, the collapse, the top-k lists, the beam (plain, then with a hot-word set:
+    matched / loglik_sum too) and every alignment field, bit for bit."""
+    from aliparaformerasr_amd.engine import Engine
+    cfg, w = _sv_model(sv_embed)
+    blob, cmvn, audio = W.pack_pfw(cfg, w), W.synth_cmvn(), _audio()
+    Wd, NB, K = 8, 4, 4
+
+    def run(flags, targets=None, hot=None):
+        e = Engine(weights=blob, cmvn=cmvn, device=0)
+        e.set_decode(flags)
+        e.set_topk(K)
+        e.set_ctc_beam(Wd, NB)
+        if hot is not None:
+            e.set_ctc_hotwords(hot, 1.5)
+        if targets is not None:
+            e.set_align_targets(targets)
+        r = e.recognize(audio)
+        e.close()
+        return r
+    r_plain, r_sc, r_ctc, r_topk = run(0), run(SCORES), run(CTC), run(TOPK)
+    n = int(r_ctc.ctc.n[1])
+    assert n >= 1
+    targets = [None, [int(v) for v in r_ctc.ctc.ids[1, :n]], []]
+    r_beam = run(BEAM)
+    hyps = r_beam.beam.hyps(0)
+    assert len(hyps) >= 2 and len(hyps[1][0]) >= 1
+    hotset = [list(hyps[1][0][:3]), list(r_beam.beam.hyps(1)[0][0][:2]) or [5]]
+    for hot in (None, hotset):
+        if hot is not None:
+            r_beam = run(BEAM, hot=hot)
+            assert int(r_beam.beam.matched.max()) >= 1                            # the set does bias this search
+        r_al = run(BEAM | ALIGN, targets, hot)
+        r_all = run(CTC | TOPK | BEAM | ALIGN, targets, hot)
+        np.testing.assert_array_equal(r_all.token_ids, r_plain.token_ids)
+        np.testing.assert_array_equal(_bits(r_all.scores), _bits(r_sc.scores))
+        for name in ("n", "ids", "first", "last"):
+            np.testing.assert_array_equal(getattr(r_all.ctc, name), getattr(r_ctc.ctc, name), err_msg=name)
+        np.testing.assert_array_equal(_bits(r_all.ctc.score), _bits(r_ctc.ctc.score))
+        np.testing.assert_array_equal(r_all.topk.ids, r_topk.topk.ids)
+        np.testing.assert_array_equal(_bits(r_all.topk.val), _bits(r_topk.topk.val))
+        np.testing.assert_array_equal(r_all.topk.n, r_topk.topk.n)
+        _same_beam(r_all, r_beam, hot is not None)
+        _same_beam(r_al, r_beam, hot is not None)
+        assert r_all.align.H == 1 + NB and r_all.align.len[:, 0].tolist() == [-1, n, 0]
+        _same_align(r_all, r_al)

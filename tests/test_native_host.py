@@ -215,6 +215,37 @@ def test_copy_helpers_under_sanitizers(san, tmp_path):
     assert r.stdout.startswith("ok ")
 
 
+@pytest.mark.timeout(300)
+def test_decode_block_layouts_under_sanitizers(tmp_path):
+    """csrc/decode_blocks.h (the packed result blocks of the decoding extras, one definition for the device pointers and the host
+    accessors) under AddressSanitizer + UBSan (tests/native/decode_blocks_sanitize.cpp): words() equals the hand-written formulas
+    the layouts replaced, every field is aligned to its element size, a pattern written through every field of a buffer of
+    exactly bytes() reads back, copy_rows_padded pads, truncates and widens; no report."""
+    import shutil
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("no hipcc")
+    exe = str(tmp_path / "decode_blocks_sanitize")
+    cs = os.path.join(root, "aliparaformerasr_amd", "csrc")
+    flags = [hipcc, "-x", "hip", "--offload-arch=gfx950", "-g", "-O1", "-fsanitize=address,undefined", "-fno-gpu-sanitize",
+             "-fno-omit-frame-pointer", "-std=c++17", "-I" + cs]
+    probe = tmp_path / "probe.cpp"
+    probe.write_text("int main() { return 0; }\n")
+    b = subprocess.run(flags + [str(probe), "-o", str(tmp_path / "probe")], capture_output=True, text=True)
+    if b.returncode != 0:                              # only a missing sanitizer runtime skips; the program itself must compile
+        pytest.skip("sanitizer runtime not available: " + b.stderr[-300:])
+    b = subprocess.run(flags + [os.path.join(root, "tests", "native", "decode_blocks_sanitize.cpp"), "-o", exe],
+                       capture_output=True, text=True)
+    assert b.returncode == 0, b.stderr[-3000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=240,
+                       env=dict(os.environ, UBSAN_OPTIONS="halt_on_error=1", ASAN_OPTIONS="detect_leaks=1"))
+    assert r.returncode == 0, (r.stdout[-500:], r.stderr[-3000:])
+    assert "runtime error" not in r.stderr and "Sanitizer" not in r.stderr, r.stderr[-3000:]
+    assert r.stdout.startswith("ok ")
+
+
 @pytest.mark.skipif(not os.environ.get("PF_SANITIZE_FULL"), reason="set PF_SANITIZE_FULL=1: rebuilds the whole library with ASan + UBSan (minutes)")
 @pytest.mark.timeout(3000)
 def test_every_host_entry_point_under_sanitizers(tmp_path):
