@@ -658,6 +658,18 @@ int pf_op_lfr_cmvn_pad(pf_engine* h, const float* const* fbank, const int32_t* t
   return PF_OK;
   PF_CATCH
 }
+int pf_op_fbank_batch(pf_engine* h, const float* const* samples, const int64_t* n, int32_t B, float* out, int64_t cap,
+                      int32_t* t80) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  PF_CHECK(B >= 0, PF_ERR_INVALID_ARG, "negative batch");
+  if (B > 0) { NEED(samples); NEED(n); NEED(t80); }
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->op_fbank_batch(samples, n, B, out, cap, t80);
+  return PF_OK;
+  PF_CATCH
+}
 int pf_op_argmax(pf_engine* h, const float* x, int64_t rows, int32_t V, int64_t* ids) {
   PF_TRY
   std::shared_ptr<Engine> eh_ = E(h);

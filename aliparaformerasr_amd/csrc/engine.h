@@ -214,6 +214,8 @@ class Engine {
   // ---- stand-alone ops (parity tests) -------------------------------------
   void op_lfr_cmvn_pad(const float* const* fbank, const int32_t* t80, int B, int sentinel, float* out,
                        int64_t cap, int32_t* tmax);
+  // stage_audio + the ONE launch_fbank over all B utterances that run_staged makes; rows [sum t80, n_mels] and t80 [B] back
+  void op_fbank_batch(const float* const* samples, const int64_t* n, int B, float* out, int64_t cap, int32_t* t80);
   void op_argmax(const float* x, int64_t rows, int V, int64_t* ids);
   void op_gemm(const float* A, const float* W, const float* bias, int M, int N, int K, int epi, float* C);
   void op_gemm_ex(const pf_gemm_desc& d, const float* A, const float* W, float* C);

@@ -41,6 +41,21 @@ void Engine::op_lfr_cmvn_pad(const float* const* fbank, const int32_t* t80, int 
   PF_HIP(hipStreamSynchronize(stream_));
 }
 
+void Engine::op_fbank_batch(const float* const* samples, const int64_t* n, int B, float* out, int64_t cap, int32_t* t80) {
+  stage_audio(samples, n, B);
+  for (int b = 0; b < B; ++b) t80[b] = st_t80_[b];
+  const int64_t need = st_total_frames_ * fc_.n_mels;
+  PF_CHECK(cap >= need, PF_ERR_CAPACITY, "fbank_batch: out capacity < " + std::to_string(need));
+  if (need == 0) return;
+  PF_CHECK(out != nullptr, PF_ERR_INVALID_ARG, "fbank_batch: null out");
+  const int64_t* meta = (const int64_t*)ws_meta_.p;
+  ensure(ws_fbank_, (size_t)need * 4);
+  launch_fbank(stream_, fb_, (const float*)ws_audio_.p, meta, meta + (B + 1), meta + 2 * (B + 1), B, st_total_frames_,
+               fc_.snip_edges ? 1 : 0, (float*)ws_fbank_.p, fc_.dither, next_dither_seed());
+  PF_HIP(hipMemcpyAsync(out, ws_fbank_.p, (size_t)need * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipStreamSynchronize(stream_));
+}
+
 void Engine::op_argmax(const float* x, int64_t rows, int V, int64_t* ids) {
   PF_HIP(hipSetDevice(device_));
   if (rows == 0) return;

@@ -357,6 +357,9 @@ class Engine:
         kind, vocab, feat, ts = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
         N.check(self._lib.pf_engine_info(self._h, kind, vocab, feat, ts))
         self.kind, self.vocab, self.feat_dim = kind.value, vocab.value, feat.value
+        # the front-end geometry the library settled on (a value <= 0 selects its default)
+        self.n_mels, self.lfr_m, self.lfr_n = (n_mels if n_mels > 0 else 80, lfr_m if lfr_m > 0 else 7,
+                                               lfr_n if lfr_n > 0 else 6)
         self._decode = 0
         self._beam_n = 16
         self._hot = False
@@ -380,11 +383,12 @@ class Engine:
 
     def fbank(self, samples) -> np.ndarray:
         x = _f32(samples)
-        cap = (x.shape[0] // 160 + 2) * 128
+        m = self.n_mels
+        cap = (x.shape[0] // 160 + 2) * m
         out = np.zeros(cap, np.float32)
         t = C.c_int32()
         N.check(self._lib.pf_fbank(self._h, _fp(x), x.shape[0], _fp(out), cap, t))
-        return out[: t.value * 80].reshape(t.value, 80).copy()
+        return out[: t.value * m].reshape(t.value, m).copy()
 
     def frontend(self, samples) -> np.ndarray:
         x = _f32(samples)
@@ -697,15 +701,30 @@ class Engine:
 
     # ---- stand-alone ops ------------------------------------------------------
     def op_lfr_cmvn_pad(self, fbanks, sentinel=True) -> np.ndarray:
-        arrs = [_f32(f).reshape(-1, 80) for f in fbanks]
+        arrs = [_f32(f).reshape(-1, self.n_mels) for f in fbanks]
         B = len(arrs)
         ptrs = (C.POINTER(C.c_float) * B)(*[_fp(a) for a in arrs])
         t80 = (C.c_int32 * B)(*[a.shape[0] for a in arrs])
-        tmax = max([a.shape[0] // 6 for a in arrs] + [0])
-        out = np.zeros((B, tmax, self.feat_dim), np.float32)
+        tmax = max([a.shape[0] // self.lfr_n for a in arrs] + [0])
+        out = np.zeros((B, tmax, self.lfr_m * self.n_mels), np.float32)
         tm = C.c_int32()
         N.check(self._lib.pf_op_lfr_cmvn_pad(self._h, ptrs, t80, B, 1 if sentinel else 0, _fp(out), out.size, tm))
+        assert tm.value == tmax, (tm.value, tmax)
         return out
+
+    def op_fbank_batch(self, samples_list) -> list:
+        """The batched fbank as run_staged launches it (pf_op_fbank_batch): one launch over all the utterances;
+        returns each utterance's rows [t, n_mels]."""
+        arrs = [_f32(s) for s in samples_list]
+        B, m = len(arrs), self.n_mels
+        ptrs = (C.POINTER(C.c_float) * B)(*[_fp(a) for a in arrs])
+        ns = (C.c_int64 * B)(*[a.shape[0] for a in arrs])
+        cap = sum(a.shape[0] // 160 + 2 for a in arrs) * m
+        out = np.zeros(max(cap, 1), np.float32)
+        t80 = np.zeros(max(B, 1), np.int32)
+        N.check(self._lib.pf_op_fbank_batch(self._h, ptrs, ns, B, _fp(out), cap, _i32p(t80)))
+        offs = np.concatenate([[0], np.cumsum(t80[:B], dtype=np.int64)])
+        return [out[offs[b] * m: offs[b + 1] * m].reshape(int(t80[b]), m).copy() for b in range(B)]
 
     def op_qlinear(self, x, W, bias=None, relu=False, x_is_f16=False, details=False, f16_result=False):
         """One dynamically quantised Linear on the int8 MFMA (pf_op_qlinear).  details=True also returns the uint8

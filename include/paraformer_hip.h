@@ -464,14 +464,19 @@ int pf_last_flops(pf_engine* e, double* flops);
 /* 5. Stand-alone device ops exposed for parity tests (tests/ call these through
  *    the C ABI).  pf_op_gemm_ex / pf_op_gemm_rc / pf_op_ffn / pf_op_fsmn_enc / pf_op_fsmn_dec /
  *    pf_op_logsoftmax_argmax / pf_op_attention / pf_op_attention_ex / pf_op_layernorm / pf_op_cif /
- *    pf_op_lfr_cmvn_pad launch exactly the kernels (and kernel variants) the
+ *    pf_op_lfr_cmvn_pad / pf_op_fbank_batch launch exactly the kernels (and kernel variants) the
  *    pipeline launches; pf_op_gemm chooses its variant by shape like the
  *    pipeline does; pf_op_fsmn is a generic fp32 FSMN (arbitrary mask) that the
  *    pipeline itself does not launch; pf_op_argmax scans the values as given. */
 /* ------------------------------------------------------------------------ */
-/* LFR + CMVN + right-pad + sentinel: fbank rows of B utterances -> [B, Tmax, lfr_m*80]. */
+/* LFR + CMVN + right-pad + sentinel: fbank rows [t80[b], n_mels] of B utterances -> [B, Tmax, lfr_m*n_mels]. */
 int pf_op_lfr_cmvn_pad(pf_engine* e, const float* const* fbank, const int32_t* t80, int32_t B,
                        int32_t apply_sentinel, float* out, int64_t out_cap, int32_t* tmax_out);
+/* the batched fbank exactly as pf_run_staged launches it: pf_stage_audio, then ONE fbank launch over all B utterances.
+   out = the rows [sum t80, n_mels] of the utterances one after another, t80_out [B] = frames per utterance (filled in
+   before PF_ERR_CAPACITY is reported when out_cap floats do not hold the rows). */
+int pf_op_fbank_batch(pf_engine* e, const float* const* samples, const int64_t* n_samples, int32_t B, float* out,
+                      int64_t out_cap, int32_t* t80_out);
 /* last-index arg-max over the trailing dim: x [rows, V] -> ids [rows]. */
 int pf_op_argmax(pf_engine* e, const float* x, int64_t rows, int32_t V, int64_t* ids_out);
 /* exactly the pipeline's CTC collapse kernel (k_ctc.hip) on caller data: ids / scores [B, T], lens [B] (clamped to

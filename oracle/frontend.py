@@ -85,22 +85,32 @@ def window_function(window_type: str = "hamming") -> np.ndarray:
     return w.astype(F32)
 
 
-def mel_scale(f):
+def mel_scale(f, libm_log: bool = False):
+    """MelScale: 1127.0f * logf(1.0f + f / 700.0f).
+
+    Default: numpy's float32 log, as every committed golden file was written with.  That log is a SIMD approximation, up
+    to 2 ulp away from a libm logf (and dependent on the CPU numpy dispatches for); through the filter edges it moves 69
+    of the 501 weights of the 80-bin bank by up to 1.4e-5.  libm_log=True takes the logarithm in double and rounds once
+    — a correctly rounded logf, what kaldi's float code gets from libm but for a rare last-bit case — for comparisons
+    that resolve float32 rounding (tests/fbank_ref.py)."""
+    if libm_log:
+        x = (F32(1.0) + np.asarray(f, dtype=F32) / F32(700.0)).astype(F32)
+        return (F32(1127.0) * np.log(x.astype(np.float64)).astype(F32)).astype(F32)
     return F32(1127.0) * np.log(F32(1.0) + np.asarray(f, dtype=F32) / F32(700.0)).astype(F32)
 
 
-def mel_banks(num_bins: int = 80, sample_rate: int = 16000) -> np.ndarray:
+def mel_banks(num_bins: int = 80, sample_rate: int = 16000, libm_log: bool = False) -> np.ndarray:
     """MelBanks::MelBanks — dense [num_bins, NFFT/2] float32 weight matrix
-    (FFT bin NFFT/2 is never used by kaldi)."""
+    (FFT bin NFFT/2 is never used by kaldi).  libm_log: see mel_scale."""
     nyquist = 0.5 * sample_rate
     high_freq = nyquist
     fft_bin_width = F32(sample_rate / NFFT)
-    mel_low = mel_scale(LOW_FREQ)
-    mel_high = mel_scale(high_freq)
+    mel_low = mel_scale(LOW_FREQ, libm_log)
+    mel_high = mel_scale(high_freq, libm_log)
     delta = F32((mel_high - mel_low) / F32(num_bins + 1))
     nb = NFFT // 2
     w = np.zeros((num_bins, nb), dtype=F32)
-    mel = mel_scale(fft_bin_width * np.arange(nb, dtype=F32))
+    mel = mel_scale(fft_bin_width * np.arange(nb, dtype=F32), libm_log)
     for b in range(num_bins):
         left = F32(mel_low + F32(b) * delta)
         center = F32(mel_low + F32(b + 1) * delta)
@@ -139,13 +149,14 @@ def extract_frames(wave: np.ndarray, snip_edges: bool) -> np.ndarray:
 
 
 def kaldi_fbank(samples: np.ndarray, conf: FrontendConf | None = None,
-                scale_to_int16: bool = True, dither_rng=None) -> np.ndarray:
+                scale_to_int16: bool = True, dither_rng=None, libm_log: bool = False) -> np.ndarray:
     """GetFbank (WavFrontend.cs:31-37): x*32768, then kaldi fbank -> [T80, n_mels] f32.
 
     dither != 0 (the reference default is 1.0, Model/FrontendConfEntity.cs:12): kaldi's ProcessWindow adds
     `dither * N(0,1)` to every sample of every extracted frame window (overlapping frames draw independently)
     BEFORE the DC removal; the reference is itself non-deterministic there (quirk Q11), so parity with it can
     only be statistical.  `dither_rng` seeds the draw (numpy Generator); bit-parity work runs with dither = 0.
+    `libm_log`: the mel weights of mel_banks(..., libm_log=True).
     """
     conf = conf or FrontendConf(dither=0.0)
     if samples is None:
@@ -174,7 +185,7 @@ def kaldi_fbank(samples: np.ndarray, conf: FrontendConf | None = None,
     padded[:, :FRAME_LEN] = pre
     spec = np.fft.rfft(padded.astype(np.float64), axis=1)    # double FFT, rounded below
     power = (spec.real ** 2 + spec.imag ** 2).astype(F32)[:, : NFFT // 2]
-    mel = power.astype(F32) @ mel_banks(conf.n_mels, conf.fs).T.astype(F32)
+    mel = power.astype(F32) @ mel_banks(conf.n_mels, conf.fs, libm_log).T.astype(F32)
     mel = np.maximum(mel.astype(F32), FLT_EPSILON)
     return np.log(mel).astype(F32)
 
@@ -182,35 +193,36 @@ def kaldi_fbank(samples: np.ndarray, conf: FrontendConf | None = None,
 # ----------------------------------------------------------------------------
 # LFR / CMVN / pad — reference's own C#
 # ----------------------------------------------------------------------------
-def apply_lfr(fbank: np.ndarray, lfr_m: int = 7, lfr_n: int = 6) -> np.ndarray:
+def apply_lfr(fbank: np.ndarray, lfr_m: int = 7, lfr_n: int = 6, n_mels: int = 80) -> np.ndarray:
     """ApplyLfr (WavFrontend.cs:73-111), quirks preserved:
-    - feature width 80 hard-coded (:75);
+    - feature width 80 hard-coded (:75) — `n_mels` here, 80 unless a caller states another bin count;
     - t_lfr = floor(T80 / lfr_n) with integer division (:76);
     - the intended first-frame replication is overwritten: the loop :82-85 writes
       input_0 at offset tile_x*80 and :86 then copies the input over the same
       offset, so the (lfr_m-1)/2 left-context frames stay ZERO;
     - tail branch :96-108 replicates the last frame when fewer than lfr_m remain.
     """
+    w = n_mels
     flat = np.asarray(fbank, dtype=F32).reshape(-1)
-    t = flat.shape[0] // 80
+    t = flat.shape[0] // w
     t_lfr = t // lfr_n
     tile_x = (lfr_m - 1) // 2
     t = t + tile_x
-    temp = np.zeros(t * 80, dtype=F32)
-    temp[tile_x * 80: tile_x * 80 + flat.shape[0]] = flat
-    out = np.zeros(t_lfr * lfr_m * 80, dtype=F32)
+    temp = np.zeros(t * w, dtype=F32)
+    temp[tile_x * w: tile_x * w + flat.shape[0]] = flat
+    out = np.zeros(t_lfr * lfr_m * w, dtype=F32)
     for i in range(t_lfr):
         if lfr_m <= t - i * lfr_n:
-            out[i * lfr_m * 80:(i + 1) * lfr_m * 80] = temp[i * lfr_n * 80: i * lfr_n * 80 + lfr_m * 80]
+            out[i * lfr_m * w:(i + 1) * lfr_m * w] = temp[i * lfr_n * w: i * lfr_n * w + lfr_m * w]
         else:
             num_padding = lfr_m - (t - i * lfr_n)
-            frame = np.zeros(lfr_m * 80, dtype=F32)
-            have = (t - i * lfr_n) * 80
-            frame[:have] = temp[i * lfr_n * 80: i * lfr_n * 80 + have]
+            frame = np.zeros(lfr_m * w, dtype=F32)
+            have = (t - i * lfr_n) * w
+            frame[:have] = temp[i * lfr_n * w: i * lfr_n * w + have]
             for j in range(num_padding):
-                frame[(lfr_m - num_padding + j) * 80:(lfr_m - num_padding + j + 1) * 80] = temp[(t - 1) * 80: t * 80]
-            out[i * lfr_m * 80:(i + 1) * lfr_m * 80] = frame
-    return out.reshape(t_lfr, lfr_m * 80)
+                frame[(lfr_m - num_padding + j) * w:(lfr_m - num_padding + j + 1) * w] = temp[(t - 1) * w: t * w]
+            out[i * lfr_m * w:(i + 1) * lfr_m * w] = frame
+    return out.reshape(t_lfr, lfr_m * w)
 
 
 def apply_cmvn(feats: np.ndarray, shift: np.ndarray, scale: np.ndarray) -> np.ndarray:
