@@ -1018,6 +1018,16 @@ int pf_op_cif(pf_engine* h, const float* H, const float* alphas, int32_t B, int3
   return PF_OK;
   PF_CATCH
 }
+int pf_op_cif_alphas(pf_engine* h, const float* H, int32_t B, int32_t T, float* alphas) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  NEED(H); NEED(alphas);
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->op_cif_alphas(H, B, T, alphas);
+  return PF_OK;
+  PF_CATCH
+}
 int pf_op_encoder(pf_engine* h, const float* speech, int32_t B, int32_t T, float* Hout) {
   PF_TRY
   std::shared_ptr<Engine> eh_ = E(h);

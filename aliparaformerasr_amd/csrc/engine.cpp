@@ -1344,25 +1344,31 @@ void Engine::decoder16(const DecStack& S, const DecRun& r) {
   ffn_dec(S.final_norm1, S.final_w1, S.final_ffn_norm, S.final_w2);
 }
 
-void Engine::predictor_and_decoder(int B, int T, bool want_logits) {
-  const int D = mc_.d_model, F = mc_.ffn, V = mc_.vocab;
-  const int M = B * T, T1 = T + 1;
-  const int taps = mc_.cif_l_order + mc_.cif_r_order + 1;
-  if (ev_enc_) PF_HIP(hipEventRecord(ev_enc_, stream_));     // the encoder output exists: all the timestamp head's GEMMs and its recurrence need
-  // conv1d(k=3) as im2col GEMM; reuse the FFN hidden buffer for the [M, 3D] operand and the
-  // FSMN buffer for the fp32 conv output.
-  half_t* col16 = h16_;
-  float* conv32 = fsm_;
+// The predictor's alpha stage, one body for the pipeline, the streaming seam and pf_op_cif_alphas: conv1d(k = l + r + 1) as an
+// im2col GEMM with ReLU, then alpha = relu(sigmoid(y . w + b0) * smooth - noise) and the tail weight.  H16 [B*T, D]; col16 holds
+// [B*T, taps*D] and conv32 [B*T, D], both in padded rows (round_up(B*T, 128) + 128).  scan: the plan the fire scan fills
+// behind it, inside the same profile bracket as the pipeline has always had it, or nullptr for the alphas alone.
+void Engine::cif_alpha_stage(const half_t* H16, int B, int T, half_t* col16, float* conv32, float* alphas, const CifPlan* scan) {
+  const int D = mc_.d_model, M = B * T, taps = mc_.cif_l_order + mc_.cif_r_order + 1;
   prof_begin("cif_misc", 0);
-  launch_cif_im2col(stream_, H16_, B, T, D, mc_.cif_l_order, mc_.cif_r_order, col16);
+  launch_cif_im2col(stream_, H16, B, T, D, mc_.cif_l_order, mc_.cif_r_order, col16);
   prof_end("cif_misc");
   gemm("gemm_cif", cif_conv_, col16, taps * D, M, conv32, D, nullptr, 0, nullptr, 0, nullptr, 0, true, 0, 1.f);
   prof_begin("cif_misc", 0);
-  launch_cif_alpha(stream_, conv32, B, T, D, cif_out_w_, cif_out_b_, mc_.cif_smooth, mc_.cif_noise, mc_.cif_tail,
-                   alphas_);
-  if (mc_.cif_cumsum) launch_cif_scan_cumsum(stream_, alphas_, B, T1, plan_);
-  else launch_cif_scan(stream_, alphas_, B, T1, mc_.cif_threshold, plan_);
+  launch_cif_alpha(stream_, conv32, B, T, D, cif_out_w_, cif_out_b_, mc_.cif_smooth, mc_.cif_noise, mc_.cif_tail, alphas);
+  if (scan) {
+    if (mc_.cif_cumsum) launch_cif_scan_cumsum(stream_, alphas, B, T + 1, *scan);
+    else launch_cif_scan(stream_, alphas, B, T + 1, mc_.cif_threshold, *scan);
+  }
   prof_end("cif_misc");
+}
+
+void Engine::predictor_and_decoder(int B, int T, bool want_logits) {
+  const int D = mc_.d_model, F = mc_.ffn, V = mc_.vocab;
+  const int M = B * T, T1 = T + 1;
+  if (ev_enc_) PF_HIP(hipEventRecord(ev_enc_, stream_));     // the encoder output exists: all the timestamp head's GEMMs and its recurrence need
+  // reuse the FFN hidden buffer for the [M, 3D] operand and the FSMN buffer for the fp32 conv output
+  cif_alpha_stage(H16_, B, T, h16_, fsm_, alphas_, &plan_);
   export_plan(B);
   last_.peak_len = 0;
   last_.cif_peak.clear();
@@ -1588,10 +1594,7 @@ void Engine::online_encoder(const float* speech, int B, int Tc, float* enc_out, 
   ensure(ws_speech_, n * 4);
   PF_HIP(hipMemcpyAsync(ws_speech_.p, speech, n * 4, hipMemcpyHostToDevice, stream_));
   encoder((const float*)ws_speech_.p, B, Tc, true);
-  const int taps = mc_.cif_l_order + mc_.cif_r_order + 1;
-  launch_cif_im2col(stream_, H16_, B, Tc, D, mc_.cif_l_order, mc_.cif_r_order, h16_);
-  gemm("gemm_cif", cif_conv_, h16_, taps * D, M, fsm_, D, nullptr, 0, nullptr, 0, nullptr, 0, true, 0, 1.f);
-  launch_cif_alpha(stream_, fsm_, B, Tc, D, cif_out_w_, cif_out_b_, mc_.cif_smooth, mc_.cif_noise, mc_.cif_tail, alphas_);
+  cif_alpha_stage(H16_, B, Tc, h16_, fsm_, alphas_, nullptr);
   PF_HIP(hipMemcpyAsync(enc_out, H32_, (size_t)M * D * 4, hipMemcpyDeviceToHost, stream_));
   PF_HIP(hipMemcpy2DAsync(alphas_out, (size_t)Tc * 4, alphas_, (size_t)(Tc + 1) * 4, (size_t)Tc * 4, B, hipMemcpyDeviceToHost, stream_));
   PF_HIP(hipStreamSynchronize(stream_));

@@ -249,6 +249,9 @@ class Engine {
   void op_fsmn(const float* v, const float* w, const float* mask, int B, int T, int D, int k, float* y);
   void op_cif(const float* H, const float* alphas, int B, int T, int D, float thr, int Lcap, float* E,
               int32_t* fire_count, int32_t* token_num, int32_t* L_out);
+  // the predictor's alpha stage on caller data with the loaded predictor weights: cif_alpha_stage (math_mode 0) or
+  // cif_alpha_stage32 (math_mode 1 / 3), the bodies the pipelines run; alphas [B, T+1] incl. the tail weight
+  void op_cif_alphas(const float* H, int B, int T, float* alphas);
   void op_encoder(const float* speech, int B, int T, float* H);
 
   // ---- profiling -----------------------------------------------------------
@@ -294,6 +297,9 @@ class Engine {
   int v_pp_ = 0;                     // which of the two V buffers the current layer reads (the fused launch writes the other)
   // first: 0 = not the first layer, 1 = first (x sqrt(d) + position encoding fused into norm1), 2 = first, input already encoded
   void enc_layer(const EncLayer& L, int first, const float* speech_dev, int B, int T, const EncNext& nx);
+  // im2col -> conv GEMM with ReLU -> launch_cif_alpha (scan: then the fire scan into *scan, as the offline pipeline has it)
+  void cif_alpha_stage(const half_t* H16, int B, int T, half_t* col16, float* conv32, float* alphas, const CifPlan* scan);
+  void cif_alpha_stage32(const float* H32, int B, int T, float* col32, float* conv32, float* alphas);
   void predictor_and_decoder(int B, int T, bool want_logits);
   void sensevoice_head(int B, int T, bool want_logits);
   void forward_fp32(const float* speech_dev, int B, int T, bool want_logits);   // math_mode 1 (k_fp32.hip)

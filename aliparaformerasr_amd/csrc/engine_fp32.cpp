@@ -252,6 +252,16 @@ void Engine::decoder32(const DecStack& S, const DecRun& r) {
   ffn_dec(S.final_norm1, S.final_w1, S.final_ffn_norm, S.final_w2);
 }
 
+// The predictor's alpha stage of the fp32 graph, one body for forward_fp32 and pf_op_cif_alphas: fp32 im2col, the conv as a
+// gemm32 with ReLU, then launch_cif_alpha.  H32 [B*T, D], col32 [B*T, taps*D], conv32 [B*T, D].
+void Engine::cif_alpha_stage32(const float* H32, int B, int T, float* col32, float* conv32, float* alphas) {
+  const int D = mc_.d_model, M = B * T, taps = mc_.cif_l_order + mc_.cif_r_order + 1;
+  launch_im2col_f32(stream_, H32, B, T, D, mc_.cif_l_order, mc_.cif_r_order, col32);
+  cls32_ = "gemm32_cif";
+  gemm32(col32, taps * D, cif_conv_w32_, taps * D, cif_conv_.bias, M, D, taps * D, conv32, D, nullptr, 0, true, 0, 1.f);
+  launch_cif_alpha(stream_, conv32, B, T, D, cif_out_w_, cif_out_b_, mc_.cif_smooth, mc_.cif_noise, mc_.cif_tail, alphas);
+}
+
 void Engine::forward_fp32(const float* speech_dev, int B, int T, bool want_logits) {
   const int D = mc_.d_model, F = mc_.ffn, V = mc_.vocab, Fd = mc_.feat_dim, M = B * T, T1 = T + 1;
   const int taps = mc_.cif_l_order + mc_.cif_r_order + 1;
@@ -304,10 +314,7 @@ void Engine::forward_fp32(const float* speech_dev, int B, int T, bool want_logit
     return;
   }
   // ---- CIF predictor
-  launch_im2col_f32(stream_, H32_, B, T, D, mc_.cif_l_order, mc_.cif_r_order, f[F_T]);
-  cls32_ = "gemm32_cif";
-  gemm32(f[F_T], taps * D, cif_conv_w32_, taps * D, cif_conv_.bias, M, D, taps * D, f[F_FS], D, nullptr, 0, true, 0, 1.f);
-  launch_cif_alpha(stream_, f[F_FS], B, T, D, cif_out_w_, cif_out_b_, mc_.cif_smooth, mc_.cif_noise, mc_.cif_tail, alphas_);
+  cif_alpha_stage32(H32_, B, T, f[F_T], f[F_FS], alphas_);
   if (mc_.cif_cumsum) launch_cif_scan_cumsum(stream_, alphas_, B, T1, plan_);
   else launch_cif_scan(stream_, alphas_, B, T1, mc_.cif_threshold, plan_);
   export_plan(B);

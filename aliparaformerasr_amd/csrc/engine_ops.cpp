@@ -1138,6 +1138,33 @@ void Engine::op_cif(const float* H, const float* alphas, int B, int T, int D, fl
   PF_HIP(hipStreamSynchronize(stream_));
 }
 
+void Engine::op_cif_alphas(const float* H, int B, int T, float* alphas) {
+  PF_CHECK(H && alphas && B > 0 && T > 0, PF_ERR_INVALID_ARG, "cif_alphas: bad arguments");
+  PF_CHECK(mc_.kind != "sensevoicesmall", PF_ERR_UNSUPPORTED, "cif_alphas: paraformer models only");
+  PF_CHECK(!int8_mode_, PF_ERR_UNSUPPORTED, "cif_alphas: math_mode 0, 1 and 3 only (the int8 pipeline has its own predictor tail)");
+  PF_HIP(hipSetDevice(device_));
+  const int D = mc_.d_model, taps = mc_.cif_l_order + mc_.cif_r_order + 1;
+  const int64_t M = (int64_t)B * T, Mp = round_up(M, 128) + 128;     // the pipeline's row padding (Engine::gemm: out_padded)
+  PF_CHECK(M < (1ll << 31) / (taps * D), PF_ERR_INVALID_ARG, "cif_alphas: batch too large for 32-bit row indexing");
+  size_t off = 0;
+  const Carve carve{off};
+  const size_t oH = carve((size_t)M * D * 4), oa = carve((size_t)B * (T + 1) * 4), oH16 = carve((size_t)Mp * D * 2);
+  const size_t ocol = carve((size_t)Mp * taps * D * 4), oconv = carve((size_t)Mp * D * 4);
+  ensure(ws_tmp_, off);
+  char* base = (char*)ws_tmp_.p;
+  PF_HIP(hipMemcpyAsync(base + oH, H, (size_t)M * D * 4, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipMemsetAsync(base + oa, 0xFF, (size_t)B * (T + 1) * 4, stream_));          // NaN: an alpha nobody wrote shows
+  if (fp32_mode_) {
+    cif_alpha_stage32((const float*)(base + oH), B, T, (float*)(base + ocol), (float*)(base + oconv), (float*)(base + oa));
+    x3a_src_ = nullptr;                                                                // (the operand lives in ws_tmp_)
+  } else {
+    launch_f32_to_f16(stream_, (const float*)(base + oH), M, D, D, (half_t*)(base + oH16), D);
+    cif_alpha_stage((const half_t*)(base + oH16), B, T, (half_t*)(base + ocol), (float*)(base + oconv), (float*)(base + oa), nullptr);
+  }
+  PF_HIP(hipMemcpyAsync(alphas, base + oa, (size_t)B * (T + 1) * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipStreamSynchronize(stream_));
+}
+
 void Engine::op_encoder(const float* speech, int B, int T, float* H) {
   PF_HIP(hipSetDevice(device_));
   PF_CHECK(speech && H && B > 0 && T > 0, PF_ERR_INVALID_ARG, "encoder: bad arguments");

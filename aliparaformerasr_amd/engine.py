@@ -1048,6 +1048,15 @@ class Engine:
                                     fc.ctypes.data_as(C.POINTER(C.c_int32)), tn.ctypes.data_as(C.POINTER(C.c_int32)), L))
         return E[:, : L.value].copy(), fc, tn
 
+    def op_cif_alphas(self, H) -> np.ndarray:
+        """The predictor's alpha stage as the pipeline runs it, on the loaded predictor weights (pf_op_cif_alphas):
+        H [B, T, d_model] -> alphas [B, T+1], the tail weight last."""
+        H = _f32(H)
+        B, T, _ = H.shape
+        a = np.zeros((B, T + 1), np.float32)
+        N.check(self._lib.pf_op_cif_alphas(self._h, _fp(H), B, T, _fp(a)))
+        return a
+
     def op_encoder(self, speech) -> np.ndarray:
         sp = _f32(speech)
         B, T, _ = sp.shape

@@ -463,7 +463,7 @@ int pf_last_flops(pf_engine* e, double* flops);
 /* ------------------------------------------------------------------------ */
 /* 5. Stand-alone device ops exposed for parity tests (tests/ call these through
  *    the C ABI).  pf_op_gemm_ex / pf_op_gemm_rc / pf_op_ffn / pf_op_fsmn_enc / pf_op_fsmn_dec /
- *    pf_op_logsoftmax_argmax / pf_op_attention / pf_op_attention_ex / pf_op_layernorm / pf_op_cif /
+ *    pf_op_logsoftmax_argmax / pf_op_attention / pf_op_attention_ex / pf_op_layernorm / pf_op_cif / pf_op_cif_alphas /
  *    pf_op_lfr_cmvn_pad / pf_op_fbank_batch launch exactly the kernels (and kernel variants) the
  *    pipeline launches; pf_op_gemm chooses its variant by shape like the
  *    pipeline does; pf_op_fsmn is a generic fp32 FSMN (arbitrary mask) that the
@@ -690,10 +690,17 @@ int pf_op_qkv_attention(pf_engine* e, const float* x, const float* w, const floa
 int pf_op_fsmn(pf_engine* e, const float* v, const float* w, const float* mask,
                int32_t B, int32_t T, int32_t D, int32_t k, float* y);
 /* CIF integrate-and-fire: H [B,T,D], alphas [B,T+1] -> embeds [B,Lcap,D] (zero padded),
-   fire_count [B], token_num [B]; returns L = max fire_count in *L_out. */
+   fire_count [B], token_num [B]; returns L = max fire_count in *L_out.  The counts and *L_out are written before the
+   capacity is checked: with Lcap < L the call returns PF_ERR_CAPACITY, leaves embeds untouched and the counts valid
+   (Lcap = 0 asks for the counts only; embeds may then be NULL). */
 int pf_op_cif(pf_engine* e, const float* H, const float* alphas, int32_t B, int32_t T, int32_t D,
               float threshold, int32_t Lcap, float* embeds, int32_t* fire_count,
               int32_t* token_num, int32_t* L_out);
+/* The CIF predictor's alpha stage with the engine's loaded predictor weights, through the function the pipeline runs:
+   H [B,T,d_model] (an encoder output) -> conv1d over time (zero padded) + ReLU -> alpha = relu(sigmoid(y . w + b) * smooth - noise);
+   alphas [B,T+1], alphas[b,T] = the tail weight.  math_mode 0 rounds H to f16 as the pipeline holds it, math_mode 1 / 3 run the
+   fp32 graph; PF_ERR_UNSUPPORTED for math_mode 2 and for SenseVoice models. */
+int pf_op_cif_alphas(pf_engine* e, const float* H, int32_t B, int32_t T, float* alphas);
 /* Encoder only: speech [B,T,feat] -> H [B,T,512] fp32. */
 int pf_op_encoder(pf_engine* e, const float* speech, int32_t B, int32_t T, float* H);
 
