@@ -4,6 +4,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstdio>
+#include <mutex>
 #include <stdexcept>
 #include <string>
 
@@ -43,6 +44,30 @@ inline int env_int(const char* name, int dflt) { const char* e = getenv(name); r
 inline int cu_limit(int cus) {
   static const int cap = [] { const char* e = getenv("PF_CU_CAP"); return e ? atoi(e) : 0; }();   // thread-safe initialiser
   return cap > 0 && cap < cus ? cap : cus;
+}
+
+// ---- per-device start-up of a launcher.  Engines on different devices launch from different host threads (one engine
+// per GPU, include/paraformer_hip.h pf_group_*), so what a launcher does once per device is done under a lock.
+// compute units of the current device, looked up once per device (k_gemm.hip): all of them, and as PF_CU_CAP limits them
+int device_cu_count();
+int device_cus();
+// `static DeviceOnce once; once.run([] { set_max_lds(kernel, bytes); ... });` runs the callable on the first launch
+// from that launcher on the current device (kernel attributes are per device, and are set lazily, not at library load)
+struct DeviceOnce {
+  template <class F>
+  void run(F&& f) {
+    int dev = 0;
+    PF_HIP(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lk(mu);
+    if (!done[dev & 63]) { f(); done[dev & 63] = true; }
+  }
+ private:
+  std::mutex mu;
+  bool done[64] = {false};
+};
+// a kernel that asks for more than 64 KiB of dynamic LDS must be allowed to
+inline void set_max_lds(const void* kernel, int bytes) {
+  PF_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
 }
 
 }  // namespace pf

@@ -20,16 +20,12 @@
 //   K: 16-byte chunk ^= (key & 15)          -> conflict-free ds_read_b128 of 32 keys
 //   V: 16-byte chunk ^= ((key & 3) << 2)    -> the 4 key rows of a tr-read hit 4 bank quarters
 #include "kernels.h"
+#include "kdev.h"
 
 #include <cstdlib>
-#include <mutex>
 
 namespace pf {
-
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 typedef __fp16 fp4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
-typedef float f16x __attribute__((ext_vector_type(16)));
 
 #define ATT_DK 128
 // compile-time ablation bits for tools/attn_abl.sh (timing experiments only; 0 in every shipped build):
@@ -71,11 +67,6 @@ struct AttnDev {
 typedef float f2 __attribute__((ext_vector_type(2)));
 template <int V>
 struct att_ic { static constexpr int value = V; };
-
-__device__ __forceinline__ void att_glds16(const void* g, void* l) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-}
 
 // Per wave and tile kt: S(kt) = K(kt) Q^T, softmax arithmetic, O^T += V(kt)^T P(kt)^T.  K and V tiles live in a ring of
 // NS stages with NS - 1 tiles in flight (round 4: with two stages the only tile in flight had exactly one tile's compute
@@ -157,13 +148,13 @@ __global__ __launch_bounds__(64 * NW, (NS > 2 || NW == 8) ? NW / 4 : 2) void att
     char* kl = smem + slot * ATT_STAGE_BYTES;
     if (p.blk) {
 #pragma unroll
-      for (int i = 0; i < PPW; ++i) att_glds16(blk_k_addr(i, kt), kl + (wave * PPW + i) * 1024);
+      for (int i = 0; i < PPW; ++i) glds16(blk_k_addr(i, kt), kl + (wave * PPW + i) * 1024);
       return;
     }
     const char* kg = reinterpret_cast<const char*>(kb_ + (int64_t)kt * ATT_BK * p.k_rs);
     if ((kt + 1) * ATT_BK <= p.Lk) {
 #pragma unroll
-      for (int i = 0; i < PPW; ++i) att_glds16(kg + k_src[i], kl + (wave * PPW + i) * 1024);
+      for (int i = 0; i < PPW; ++i) glds16(kg + k_src[i], kl + (wave * PPW + i) * 1024);
     } else {
       // tail tile: rows >= Lk are re-reads of row Lk-1.  They are masked out of the softmax anyway, but
       // what lies behind the last key in memory is not ours (another utterance, or stale workspace bytes
@@ -171,7 +162,7 @@ __global__ __launch_bounds__(64 * NW, (NS > 2 || NW == 8) ? NW / 4 : 2) void att
 #pragma unroll
       for (int i = 0; i < PPW; ++i) {
         const int over = kt * ATT_BK + (wave * PPW + i) * 4 + srow - (p.Lk - 1);     // rows to step back
-        att_glds16(kg + (k_src[i] - (unsigned)((over > 0 ? over : 0) * p.k_rs * 2)), kl + (wave * PPW + i) * 1024);
+        glds16(kg + (k_src[i] - (unsigned)((over > 0 ? over : 0) * p.k_rs * 2)), kl + (wave * PPW + i) * 1024);
       }
     }
   };
@@ -180,12 +171,12 @@ __global__ __launch_bounds__(64 * NW, (NS > 2 || NW == 8) ? NW / 4 : 2) void att
     const char* vg = reinterpret_cast<const char*>(vb + (int64_t)kt * ATT_BK * p.v_rs);
     if ((kt + 1) * ATT_BK <= p.Lk) {
 #pragma unroll
-      for (int i = 0; i < PPW; ++i) att_glds16(vg + v_src[i], vl + (wave * PPW + i) * 1024);
+      for (int i = 0; i < PPW; ++i) glds16(vg + v_src[i], vl + (wave * PPW + i) * 1024);
     } else {
 #pragma unroll
       for (int i = 0; i < PPW; ++i) {
         const int over = kt * ATT_BK + (wave * PPW + i) * 4 + srow - (p.Lk - 1);
-        att_glds16(vg + (v_src[i] - (unsigned)((over > 0 ? over : 0) * p.v_rs * 2)), vl + (wave * PPW + i) * 1024);
+        glds16(vg + (v_src[i] - (unsigned)((over > 0 ? over : 0) * p.v_rs * 2)), vl + (wave * PPW + i) * 1024);
       }
     }
   };
@@ -422,8 +413,6 @@ __global__ __launch_bounds__(64 * NW, (NS > 2 || NW == 8) ? NW / 4 : 2) void att
   if (wide) {
     const float inv = qrow < p.Lq ? 1.0f / l_tot : 0.f;
     half_t* op = ob + (int64_t)qrow * p.o_rs + 8 * lh;
-    typedef float f2v __attribute__((ext_vector_type(2)));
-    typedef _Float16 h2v __attribute__((ext_vector_type(2)));
 #pragma unroll
     for (int db = 0; db < 4; ++db)
 #pragma unroll
@@ -447,9 +436,8 @@ __global__ __launch_bounds__(64 * NW, (NS > 2 || NW == 8) ? NW / 4 : 2) void att
         for (int e = 0; e < 2; ++e) asm volatile("v_permlane32_swap_b32 %0, %1" : "+v"(x[e]), "+v"(y[e]));
         const h4 lo_ = __builtin_bit_cast(h4, (unsigned long long)x[0] | ((unsigned long long)x[1] << 32));
         const h4 hi_ = __builtin_bit_cast(h4, (unsigned long long)y[0] | ((unsigned long long)y[1] << 32));
-        typedef _Float16 h8o __attribute__((ext_vector_type(8)));
-        const h8o hv = __builtin_shufflevector(lo_, hi_, 0, 1, 2, 3, 4, 5, 6, 7);
-        if (qrow < p.Lq) *reinterpret_cast<h8o*>(op + db * 32 + 16 * gp) = hv;
+        const h8 hv = __builtin_shufflevector(lo_, hi_, 0, 1, 2, 3, 4, 5, 6, 7);
+        if (qrow < p.Lq) *reinterpret_cast<h8*>(op + db * 32 + 16 * gp) = hv;
       }
   } else if (qrow < p.Lq) {
     const float inv = 1.0f / l_tot;
@@ -510,23 +498,10 @@ static int attention_grid(const AttnArgs& a, int cus, bool& nw8) {
   nw8 = a.force_nw ? a.force_nw == 8 : wg8 >= cus;
   return nw8 ? wg8 : ((a.Lq + ATT_BQ - 1) / ATT_BQ) * a.B * a.H;
 }
-static int attention_cus() {
-  static std::mutex mu;
-  static int cus[64] = {0};
-  int dev = 0;
-  PF_HIP(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lk(mu);
-  if (!cus[dev & 63]) {
-    hipDeviceProp_t prop;
-    PF_HIP(hipGetDeviceProperties(&prop, dev));
-    cus[dev & 63] = cu_limit(prop.multiProcessorCount);
-  }
-  return cus[dev & 63];
-}
 bool attention_reports_range(const AttnArgs& a) {
   if (a.B == 0 || a.Lq == 0 || a.Lk == 0) return false;
   bool nw8;
-  return attention_grid(a, attention_cus(), nw8) <= 256;
+  return attention_grid(a, device_cus(), nw8) <= 256;
 }
 
 void launch_attention(hipStream_t s, const AttnArgs& a) {
@@ -544,25 +519,14 @@ void launch_attention(hipStream_t s, const AttnArgs& a) {
   PF_CHECK(!a.range || attention_reports_range(a), PF_ERR_INVALID_ARG, "attention: a range output needs a grid of at most 256 workgroups");
   PF_CHECK(a.q_rstride % 8 == 0 && a.k_rstride % 8 == 0 && a.v_rstride % 8 == 0 && a.o_rstride % 4 == 0,
            PF_ERR_INVALID_ARG, "attention: row strides must keep 16-byte alignment");
-  static std::mutex init_mu;                         // engines on different devices launch from different threads
-  static bool attr_set[64] = {false};
-  static int cus[64] = {0};
-  int dev = 0;
-  PF_HIP(hipGetDevice(&dev));
-  {
-    std::lock_guard<std::mutex> lk(init_mu);
-    if (!attr_set[dev & 63]) {
-      PF_HIP(hipFuncSetAttribute((const void*)attn_kernel<4, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * ATT_STAGE_BYTES));
-      PF_HIP(hipFuncSetAttribute((const void*)attn_kernel<8, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * ATT_STAGE_BYTES));
-      hipDeviceProp_t prop;
-      PF_HIP(hipGetDeviceProperties(&prop, dev));
-      cus[dev & 63] = cu_limit(prop.multiProcessorCount);
-      attr_set[dev & 63] = true;
-    }
-  }
+  static DeviceOnce once;
+  once.run([] {
+    set_max_lds((const void*)attn_kernel<4, 2>, 2 * ATT_STAGE_BYTES);
+    set_max_lds((const void*)attn_kernel<8, 2>, 2 * ATT_STAGE_BYTES);
+  });
   // 256-query workgroups when they still cover the chip (self-attention at T = 500: 2 x 128 workgroups); two ring stages
   bool nw8;
-  (void)attention_grid(a, cus[dev & 63], nw8);
+  (void)attention_grid(a, device_cus(), nw8);
   if (nw8) {
     dim3 grid((a.Lq + 255) / 256, a.B * a.H);
     hipLaunchKernelGGL((attn_kernel<8, 2>), grid, dim3(512), 2 * ATT_STAGE_BYTES, s, d);

@@ -17,11 +17,9 @@
 
 #include "exact.h"
 #include "kernels.h"
+#include "kdev.h"
 
 namespace pf {
-
-typedef _Float16 h8v __attribute__((ext_vector_type(8)));
-typedef float f16v __attribute__((ext_vector_type(16)));
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + __expf(-x)); }
 
@@ -49,15 +47,15 @@ __global__ __launch_bounds__(256) void lstm_step_kernel(LstmArgs a) {
   const float xi = xgp[0], xf = xgp[D], xc = xgp[2 * D], xo = xgp[3 * D], cprev = *cp;
 
   const int kspan = D / 4;               // K slice of this wave
-  f16v acc;
+  f16x acc;
 #pragma unroll
   for (int i = 0; i < 16; ++i) acc[i] = 0.f;
   for (int k0 = wave * kspan; k0 < (wave + 1) * kspan; k0 += 128) {
-    h8v av[8], bv[8];
+    h8 av[8], bv[8];
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
-      av[s] = *reinterpret_cast<const h8v*>(wrow + k0 + s * 16 + kg * 8);
-      bv[s] = *reinterpret_cast<const h8v*>(hrow + k0 + s * 16 + kg * 8);
+      av[s] = *reinterpret_cast<const h8*>(wrow + k0 + s * 16 + kg * 8);
+      bv[s] = *reinterpret_cast<const h8*>(hrow + k0 + s * 16 + kg * 8);
     }
 #pragma unroll
     for (int s = 0; s < 8; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(av[s], bv[s], acc, 0, 0, 0);
@@ -93,7 +91,7 @@ __global__ __launch_bounds__(256) void lstm_step_kernel(LstmArgs a) {
 // is bounded: on time-out the kernel raises *err and every workgroup leaves.
 // eight 16-byte sc1 loads (offsets 0, 32, .., 224 bytes) issued back to back, ONE wait: the loads and their wait live
 // in one asm statement, so the compiler never sees a destination before the data has landed (CDNA guide §5.7 item 1)
-__device__ __forceinline__ void ld8x16_sc1(const half_t* p, h8v (&v)[8]) {
+__device__ __forceinline__ void ld8x16_sc1(const half_t* p, h8 (&v)[8]) {
   asm volatile(
       "global_load_dwordx4 %0, %8, off sc1\n\t"
       "global_load_dwordx4 %1, %8, off offset:32 sc1\n\t"
@@ -107,9 +105,6 @@ __device__ __forceinline__ void ld8x16_sc1(const half_t* p, h8v (&v)[8]) {
       : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3]), "=&v"(v[4]), "=&v"(v[5]), "=&v"(v[6]), "=&v"(v[7])
       : "v"(p)
       : "memory");
-}
-__device__ __forceinline__ void st16_sc1(half_t* p, h8v v) {
-  asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
 }
 
 // ---- ring form of the persistent recurrence: the h exchange carries its own arrival information.
@@ -150,18 +145,18 @@ __global__ __launch_bounds__(320) void lstm_ring_kernel(LstmArgs a, unsigned* __
   const int cw = storer ? 0 : wave;                          // K slice index of a compute wave
   const half_t* wrow = a.whh + ((size_t)dir * 4 * D + (size_t)(r & 3) * D + ub * 8 + (r >> 2)) * RS;
   const int kspan = D / 4;
-  h8v av[8], avl[X3 ? 8 : 1];
+  h8 av[8], avl[X3 ? 8 : 1];
 #pragma unroll
   for (int s = 0; s < 8; ++s) {
-    av[s] = *reinterpret_cast<const h8v*>(wrow + cw * kspan + s * 16 + kg * 8);
-    if constexpr (X3) avl[s] = *reinterpret_cast<const h8v*>(wrow + D + cw * kspan + s * 16 + kg * 8);
+    av[s] = *reinterpret_cast<const h8*>(wrow + cw * kspan + s * 16 + kg * 8);
+    if constexpr (X3) avl[s] = *reinterpret_cast<const h8*>(wrow + D + cw * kspan + s * 16 + kg * 8);
   }
   const int bb = min(bt * 32 + r, a.B - 1);
   const int uq = ub * 8 + 2 * cw + kg;
   float c = 0.f;
   if (threadIdx.x == 0) s_abort = 0;
   __syncthreads();
-  h8v poison;
+  h8 poison;
 #pragma unroll
   for (int e = 0; e < 8; ++e) poison[e] = __builtin_bit_cast(_Float16, (unsigned short)0xFFFFu);
   half_t* const slots = a.hstate + (size_t)dir * 4 * a.B * RS;
@@ -181,8 +176,8 @@ __global__ __launch_bounds__(320) void lstm_ring_kernel(LstmArgs a, unsigned* __
       if constexpr (X3) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
       else asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
       if (lane < 32 && bt * 32 + lane < a.B) {
-        st16_sc1(slots + ((size_t)so * a.B + bt * 32 + lane) * RS + ub * 8, *reinterpret_cast<const h8v*>(&hx[lane][0]));
-        if constexpr (X3) st16_sc1(slots + ((size_t)so * a.B + bt * 32 + lane) * RS + D + ub * 8, *reinterpret_cast<const h8v*>(&hxl[lane][0]));
+        st16_sc1(slots + ((size_t)so * a.B + bt * 32 + lane) * RS + ub * 8, *reinterpret_cast<const h8*>(&hx[lane][0]));
+        if constexpr (X3) st16_sc1(slots + ((size_t)so * a.B + bt * 32 + lane) * RS + D + ub * 8, *reinterpret_cast<const h8*>(&hxl[lane][0]));
       }
       const int ob = bt * 32 + (lane >> 1);
       if (ob < a.B)
@@ -193,7 +188,7 @@ __global__ __launch_bounds__(320) void lstm_ring_kernel(LstmArgs a, unsigned* __
     const float* xgp = a.xg + ((size_t)bb * a.T3 + t) * (size_t)(a.ndir * 4 * D) + (size_t)dir * 4 * D + uq;
     const float xi = xgp[0], xf = xgp[D], xc = xgp[2 * D], xo = xgp[3 * D];
     const half_t* hrow = slots + ((size_t)si * a.B + bb) * RS + wave * kspan + kg * 8;
-    h8v bv[8], bvl[X3 ? 8 : 1];
+    h8 bv[8], bvl[X3 ? 8 : 1];
     unsigned spins = 0;
     // cheap poll first: lane j < 16 watches the first word of producer (wave * 16 + j)'s granule for the tile's first
     // utterance (64 bytes per wave and poll; polling with the eight full loads — 8 KB per wave — kept 4 MB per round in
@@ -232,7 +227,7 @@ __global__ __launch_bounds__(320) void lstm_ring_kernel(LstmArgs a, unsigned* __
         break;
       }
     }
-    f16v acc;
+    f16x acc;
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = 0.f;
     if constexpr (X3) {

@@ -23,16 +23,10 @@
 //      straight from a fragment-ordered image (launch_ffn_retile_out, the encoder tail's), 8 in flight; bias in the accumulators
 //      from the start, scale, f16, 16-byte row-major stores after a v_permlane32_swap (k_ffn.hip's V pass).
 #include "kernels.h"
+#include "kdev.h"
 #include "exact.h"
 
-#include <mutex>
-
 namespace pf {
-
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef float f16x __attribute__((ext_vector_type(16)));
-typedef float4 __attribute__((may_alias)) float4a;
 
 constexpr int DM_R = 32, DM_D = 512, DM_F = 2048;
 constexpr int DM_ROWB = DM_D * 4;                         // an fp32 row in LDS
@@ -54,18 +48,6 @@ struct DecMidDev {
   const float* n3_g; const float* n3_b;
   const half_t* Wqt; const float* bq; float qscale; half_t* q16; int ldq;
 };
-
-__device__ __forceinline__ float dm_wave_sum(float v) {
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, false));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, false));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, false));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, false));
-  const float a = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 0));
-  const float b = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 16));
-  const float c = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 32));
-  const float d = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 48));
-  return (a + b) + (c + d);
-}
 
 template <int K>
 __global__ __launch_bounds__(512, 1) void dec_mid_kernel(DecMidDev p) {
@@ -162,9 +144,9 @@ __global__ __launch_bounds__(512, 1) void dec_mid_kernel(DecMidDev p) {
         const float4 x0 = a0[i], x1 = a1[i];
         float4 y0 = make_float4(rs * (x0.x - mu * cc0.x) + dd0.x, rs * (x0.y - mu * cc0.y) + dd0.y, rs * (x0.z - mu * cc0.z) + dd0.z, rs * (x0.w - mu * cc0.w) + dd0.w);
         float4 y1 = make_float4(rs * (x1.x - mu * cc1.x) + dd1.x, rs * (x1.y - mu * cc1.y) + dd1.y, rs * (x1.z - mu * cc1.z) + dd1.z, rs * (x1.w - mu * cc1.w) + dd1.w);
-        const float mean = dm_wave_sum(((y0.x + y0.y) + (y0.z + y0.w)) + ((y1.x + y1.y) + (y1.z + y1.w))) * (1.0f / DM_D);
+        const float mean = wave_sum(((y0.x + y0.y) + (y0.z + y0.w)) + ((y1.x + y1.y) + (y1.z + y1.w))) * (1.0f / DM_D);
         y0.x -= mean; y0.y -= mean; y0.z -= mean; y0.w -= mean; y1.x -= mean; y1.y -= mean; y1.z -= mean; y1.w -= mean;
-        const float k = 1.0f / sqrtf(dm_wave_sum(((y0.x * y0.x + y0.y * y0.y) + (y0.z * y0.z + y0.w * y0.w)) +
+        const float k = 1.0f / sqrtf(wave_sum(((y0.x * y0.x + y0.y * y0.y) + (y0.z * y0.z + y0.w * y0.w)) +
                                                  ((y1.x * y1.x + y1.y * y1.y) + (y1.z * y1.z + y1.w * y1.w))) * (1.0f / DM_D) + p.eps2);
         z0 = make_float4(y0.x * k * g0.x + e0.x, y0.y * k * g0.y + e0.y, y0.z * k * g0.z + e0.z, y0.w * k * g0.w + e0.w);
         z1 = make_float4(y1.x * k * g1.x + e1.x, y1.y * k * g1.y + e1.y, y1.z * k * g1.z + e1.z, y1.w * k * g1.w + e1.w);
@@ -225,9 +207,9 @@ __global__ __launch_bounds__(512, 1) void dec_mid_kernel(DecMidDev p) {
         const float x0 = __shfl(a.x, 0, 64);
         a.x = sub_rn(a.x, x0); a.y = sub_rn(a.y, x0); a.z = sub_rn(a.z, x0); a.w = sub_rn(a.w, x0);
         c.x = sub_rn(c.x, x0); c.y = sub_rn(c.y, x0); c.z = sub_rn(c.z, x0); c.w = sub_rn(c.w, x0);
-        const float mean = dm_wave_sum(((a.x + a.y) + (a.z + a.w)) + ((c.x + c.y) + (c.z + c.w))) / (float)DM_D;
+        const float mean = wave_sum(((a.x + a.y) + (a.z + a.w)) + ((c.x + c.y) + (c.z + c.w))) / (float)DM_D;
         a.x -= mean; a.y -= mean; a.z -= mean; a.w -= mean; c.x -= mean; c.y -= mean; c.z -= mean; c.w -= mean;
-        const float var = dm_wave_sum(((a.x * a.x + a.y * a.y) + (a.z * a.z + a.w * a.w)) + ((c.x * c.x + c.y * c.y) + (c.z * c.z + c.w * c.w))) / (float)DM_D;
+        const float var = wave_sum(((a.x * a.x + a.y * a.y) + (a.z * a.z + a.w * a.w)) + ((c.x * c.x + c.y * c.y) + (c.z * c.z + c.w * c.w))) / (float)DM_D;
         const float rstd = 1.0f / sqrtf(var + 1e-12f);
         y0 = h4{(half_t)(a.x * rstd * g0.x + e0.x), (half_t)(a.y * rstd * g0.y + e0.y), (half_t)(a.z * rstd * g0.z + e0.z), (half_t)(a.w * rstd * g0.w + e0.w)};
         y1 = h4{(half_t)(c.x * rstd * g1.x + e1.x), (half_t)(c.y * rstd * g1.y + e1.y), (half_t)(c.z * rstd * g1.z + e1.z), (half_t)(c.w * rstd * g1.w + e1.w)};
@@ -284,8 +266,6 @@ __global__ __launch_bounds__(512, 1) void dec_mid_kernel(DecMidDev p) {
   DM_TS(4)
   // rows l0 + l31: lanes l / l + 32 hold columns 8 g + 0..3 / 8 g + 4..7; after v_permlane32_swap lane l holds the 8 columns of
   // group 2 gp, lane l + 32 those of group 2 gp + 1: 16-byte row-major stores
-  typedef float f2v __attribute__((ext_vector_type(2)));
-  typedef _Float16 h2v __attribute__((ext_vector_type(2)));
   const int lrow = l0 + l31;
   half_t* qrow = p.q16 + ((size_t)b * p.L + lrow) * p.ldq + wave * 64;
 #pragma unroll
@@ -336,17 +316,10 @@ bool launch_dec_mid(hipStream_t s, const DecMidArgs& a) {
   d.n2_g = a.n2_g; d.n2_b = a.n2_b; d.eps2 = a.eps2;
   d.wT = a.fsmn_wT; d.token_num = a.token_num; d.B = a.B; d.L = a.L; d.x = a.x;
   d.n3_g = a.n3_g; d.n3_b = a.n3_b; d.Wqt = a.Wqt; d.bq = a.bq; d.qscale = a.qscale; d.q16 = a.q16; d.ldq = a.ldq;
-  static std::mutex init_mu;
-  static bool attr_set[64] = {false};
-  int dev = 0;
-  PF_HIP(hipGetDevice(&dev));
-  {
-    std::lock_guard<std::mutex> lk(init_mu);
-    if (!attr_set[dev & 63]) {
-      PF_HIP(hipFuncSetAttribute((const void*)dec_mid_kernel<11>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dec_mid_lds_bytes(11)));
-      attr_set[dev & 63] = true;
-    }
-  }
+  static DeviceOnce once;
+  once.run([] {
+    set_max_lds((const void*)dec_mid_kernel<11>, (int)dec_mid_lds_bytes(11));
+  });
   const dim3 grid((unsigned)(a.B * cdiv(a.L, DM_R)));
   hipLaunchKernelGGL(dec_mid_kernel<11>, grid, dim3(512), dec_mid_lds_bytes(11), s, d);
   PF_HIP(hipGetLastError());

@@ -33,16 +33,9 @@
 // Epilogue = k_gemm_rc.hip's: the 64 x 512 fp32 tile goes through LDS, every wave owns 8 complete rows: bias + residual
 // -> x, LayerNorm (two-pass statistics on DPP wave sums) -> f16 / fp32.
 #include "kernels.h"
-
-#include <mutex>
+#include "kdev.h"
 
 namespace pf {
-
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-typedef float f16x __attribute__((ext_vector_type(16)));
-typedef float4 __attribute__((may_alias)) float4a;
 
 struct FfnDev {
   const half_t* A; const half_t* W1t; const half_t* W2t; const float* b1; const float* b2;
@@ -98,21 +91,6 @@ constexpr int FF_B_OFF = FF_BM * FF_XROW;                  // b1 (8 KiB) behind 
 constexpr int FF_LDS = FF_B_OFF + FF_F * 4;                // 140 288 B
 static_assert(FF_A_BYTES + 2 * FF_H_BYTES <= FF_B_OFF, "tile + hidden buffers must end before the bias copy");
 
-__device__ __forceinline__ void ff_glds16(const void* g, void* l) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-}
-__device__ __forceinline__ float ff_wave_sum(float v) {
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, false));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, false));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, false));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, false));
-  const float a = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 0));
-  const float b = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 16));
-  const float c = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 32));
-  const float d = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 48));
-  return (a + b) + (c + d);
-}
 // LDS traffic between waves: writes retired before the barrier, nothing moved across it (local address space only: the
 // weight loads in flight must NOT be drained)
 __device__ __forceinline__ void ff_lds_barrier() {
@@ -218,11 +196,11 @@ __global__ __launch_bounds__(512, 1) void ffn_fused_kernel(FfnDev p) {
     const char* src = OP ? reinterpret_cast<const char*>(p.ctx + (size_t)(m0 + row) * p.lda_c) + ((schunk ^ swz(row)) << 4)
                          : reinterpret_cast<const char*>(p.A + (size_t)(m0 + row) * p.lda) + ((schunk ^ swz(row)) << 4);
 #pragma unroll
-    for (int kb = 0; kb < 8; ++kb) ff_glds16(src + kb * 128, smem + kb * 8192 + wave * 1024);
+    for (int kb = 0; kb < 8; ++kb) glds16(src + kb * 128, smem + kb * 8192 + wave * 1024);
     // b1 (2048 floats) as it is: read back per chunk with ds_read — a global load used right behind its issue would make
     // the compiler wait for vmcnt(0), i.e. drain the weight stream
-    if (!OP) ff_glds16(reinterpret_cast<const char*>(p.b1) + wave * 1024 + lane * 16, smem + FF_B_OFF + wave * 1024);
-    if (SP && !OP && wave == 0) ff_glds16(reinterpret_cast<const char*>(p.b1) + 8192 + lane * 16, smem + FF_B_OFF + 8192);   // the zero chunk's bias
+    if (!OP) glds16(reinterpret_cast<const char*>(p.b1) + wave * 1024 + lane * 16, smem + FF_B_OFF + wave * 1024);
+    if (SP && !OP && wave == 0) glds16(reinterpret_cast<const char*>(p.b1) + 8192 + lane * 16, smem + FF_B_OFF + 8192);   // the zero chunk's bias
   }
   // fragment read offsets of the xn tile: row half i, 16-byte k-group (2 ss + lh) of a k-block
   unsigned xo[2][4];
@@ -380,7 +358,7 @@ __global__ __launch_bounds__(512, 1) void ffn_fused_kernel(FfnDev p) {
 #pragma unroll
     for (int r = 0; r < 8; ++r) {
       const float sm = ((xv[0][r].x + xv[0][r].y) + (xv[0][r].z + xv[0][r].w)) + ((xv[1][r].x + xv[1][r].y) + (xv[1][r].z + xv[1][r].w));
-      mean[r] = ff_wave_sum(sm) * (1.0f / FF_D);
+      mean[r] = wave_sum(sm) * (1.0f / FF_D);
     }
 #pragma unroll
     for (int r = 0; r < 8; ++r) {
@@ -389,7 +367,7 @@ __global__ __launch_bounds__(512, 1) void ffn_fused_kernel(FfnDev p) {
       xv[1][r].x -= m; xv[1][r].y -= m; xv[1][r].z -= m; xv[1][r].w -= m;
       const float q = ((xv[0][r].x * xv[0][r].x + xv[0][r].y * xv[0][r].y) + (xv[0][r].z * xv[0][r].z + xv[0][r].w * xv[0][r].w)) +
                       ((xv[1][r].x * xv[1][r].x + xv[1][r].y * xv[1][r].y) + (xv[1][r].z * xv[1][r].z + xv[1][r].w * xv[1][r].w));
-      rstd[r] = 1.0f / sqrtf(ff_wave_sum(q) * (1.0f / FF_D) + p.eps);
+      rstd[r] = 1.0f / sqrtf(wave_sum(q) * (1.0f / FF_D) + p.eps);
     }
     ff_lds_barrier();                                              // every wave has read its fragments of x_mid back
 #pragma unroll
@@ -407,8 +385,8 @@ __global__ __launch_bounds__(512, 1) void ffn_fused_kernel(FfnDev p) {
     }
     // b1 -> LDS now (its place was inside the fp32 tile's footprint? no: behind it — but the DMA is cheapest here, off the
     // critical path), then the block's first weight fragments
-    ff_glds16(reinterpret_cast<const char*>(p.b1) + wave * 1024 + lane * 16, smem + FF_B_OFF + wave * 1024);
-    if (SP && wave == 0) ff_glds16(reinterpret_cast<const char*>(p.b1) + 8192 + lane * 16, smem + FF_B_OFF + 8192);
+    glds16(reinterpret_cast<const char*>(p.b1) + wave * 1024 + lane * 16, smem + FF_B_OFF + wave * 1024);
+    if (SP && wave == 0) glds16(reinterpret_cast<const char*>(p.b1) + 8192 + lane * 16, smem + FF_B_OFF + 8192);
 #pragma unroll
     for (int i = 0; i < PF; ++i) ring[i] = wload(i);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -617,7 +595,7 @@ __global__ __launch_bounds__(512, 1) void ffn_fused_kernel(FfnDev p) {
 #pragma unroll
   for (int r = 0; r < 8; ++r) {
     const float s = ((xv[0][r].x + xv[0][r].y) + (xv[0][r].z + xv[0][r].w)) + ((xv[1][r].x + xv[1][r].y) + (xv[1][r].z + xv[1][r].w));
-    mean[r] = ff_wave_sum(s) * (1.0f / FF_D);
+    mean[r] = wave_sum(s) * (1.0f / FF_D);
   }
 #pragma unroll
   for (int r = 0; r < 8; ++r) {
@@ -626,7 +604,7 @@ __global__ __launch_bounds__(512, 1) void ffn_fused_kernel(FfnDev p) {
     xv[1][r].x -= m; xv[1][r].y -= m; xv[1][r].z -= m; xv[1][r].w -= m;
     const float q = ((xv[0][r].x * xv[0][r].x + xv[0][r].y * xv[0][r].y) + (xv[0][r].z * xv[0][r].z + xv[0][r].w * xv[0][r].w)) +
                     ((xv[1][r].x * xv[1][r].x + xv[1][r].y * xv[1][r].y) + (xv[1][r].z * xv[1][r].z + xv[1][r].w * xv[1][r].w));
-    rstd[r] = 1.0f / sqrtf(ff_wave_sum(q) * (1.0f / FF_D) + p.eps);
+    rstd[r] = 1.0f / sqrtf(wave_sum(q) * (1.0f / FF_D) + p.eps);
   }
   h4 yh[QK ? 2 : 1][QK ? 8 : 1];
 #pragma unroll
@@ -678,7 +656,7 @@ __global__ __launch_bounds__(512, 1) void ffn_fused_kernel(FfnDev p) {
       }
     const unsigned lane16e = (unsigned)lane_e * 16u;
     // bq (1536 floats) -> the LDS place of b1 (dead by now): a global load used right behind its issue would drain the stream
-    if (wave < 6) ff_glds16(reinterpret_cast<const char*>(p.bq) + wave * 1024 + lane_e * 16, smem + FF_B_OFF + wave * 1024);
+    if (wave < 6) glds16(reinterpret_cast<const char*>(p.bq) + wave * 1024 + lane_e * 16, smem + FF_B_OFF + wave * 1024);
     // ONE weight stream over the three passes (192 fragments of this wave), PF ahead across the pass ends
     const half_t* wqu = p.Wqt + (size_t)wave * (64 * 512);
     // The workgroups of an XCD walk Q, K, V in three different orders (round 6).  Every layer's Wq image is COLD in the XCD's L2
@@ -701,8 +679,6 @@ __global__ __launch_bounds__(512, 1) void ffn_fused_kernel(FfnDev p) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     ff_lds_barrier();                                      // the operand tile and the bias are complete
     FF_TS(7)
-    typedef float f2v __attribute__((ext_vector_type(2)));
-    typedef _Float16 h2v __attribute__((ext_vector_type(2)));
 #pragma unroll
     for (int pass = 0; pass < 3; ++pass) {
       int pr = pass + prot;                               // which of Q | K | V this pass computes
@@ -866,7 +842,6 @@ __global__ void ffn_retile_out_kernel(const half_t* __restrict__ Wo, int ldw, ha
   *reinterpret_cast<h8*>(Wot + (size_t)pc * 8) = v;
 }
 
-
 // ---- decoder form (SP > 0) -----------------------------------------------------------------------------------------
 // The decoder's position-wise block is  t = LN_F(relu(xn W1^T + b1)) W2^T  (LayerNorm over the 2048 hidden columns between the
 // products, W2 without bias: the w_1 / norm / w_2 nodes of the decoder graph behind AliParaformerAsr/OfflineProjOfParaformer.cs:68).
@@ -974,9 +949,9 @@ __global__ __launch_bounds__(256) void ffn_dec_finish_kernel(const float* __rest
     *reinterpret_cast<float4*>(t32 + (size_t)m * ldt + 256 + 4 * lane) = y1;
   }
   if (!g) return;
-  const float mean = ff_wave_sum(((y0.x + y0.y) + (y0.z + y0.w)) + ((y1.x + y1.y) + (y1.z + y1.w))) * (1.0f / FF_D);
+  const float mean = wave_sum(((y0.x + y0.y) + (y0.z + y0.w)) + ((y1.x + y1.y) + (y1.z + y1.w))) * (1.0f / FF_D);
   y0.x -= mean; y0.y -= mean; y0.z -= mean; y0.w -= mean; y1.x -= mean; y1.y -= mean; y1.z -= mean; y1.w -= mean;
-  const float k = 1.0f / sqrtf(ff_wave_sum(((y0.x * y0.x + y0.y * y0.y) + (y0.z * y0.z + y0.w * y0.w)) +
+  const float k = 1.0f / sqrtf(wave_sum(((y0.x * y0.x + y0.y * y0.y) + (y0.z * y0.z + y0.w * y0.w)) +
                                             ((y1.x * y1.x + y1.y * y1.y) + (y1.z * y1.z + y1.w * y1.w))) * (1.0f / FF_D) + eps);
   const float4 g0 = *reinterpret_cast<const float4*>(g + 4 * lane), g1 = *reinterpret_cast<const float4*>(g + 256 + 4 * lane);
   const float4 b0 = *reinterpret_cast<const float4*>(b + 4 * lane), b1 = *reinterpret_cast<const float4*>(b + 256 + 4 * lane);
@@ -1033,27 +1008,20 @@ void launch_ffn_dec(hipStream_t s, const FfnDecArgs& a) {
   d.part = reinterpret_cast<float*>(a.ws); d.stats = d.part + (size_t)S * Mp * FF_D;
   d.ctx = a.ctx; d.lda_c = a.lda_c; d.Wot = a.Wot; d.bo = a.bo; d.resid = a.resid; d.ldr = a.ldr; d.out_x = a.out_x; d.ldx = a.ldx;
   d.ln2_g = a.ln1_g; d.ln2_b = a.ln1_b; d.eps = a.eps1;
-  static std::mutex init_mu;
-  static bool attr_set[64] = {false};
-  int dev = 0;
-  PF_HIP(hipGetDevice(&dev));
   constexpr int LDSB = FF_LDS + 1024;
-  {
-    std::lock_guard<std::mutex> lk(init_mu);
-    if (!attr_set[dev & 63]) {
-      PF_HIP(hipFuncSetAttribute((const void*)ffn_fused_kernel<8, 0, 2, 0, 0, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, LDSB));
-      PF_HIP(hipFuncSetAttribute((const void*)ffn_fused_kernel<8, 0, 2, 0, 0, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, LDSB));
-      PF_HIP(hipFuncSetAttribute((const void*)ffn_fused_kernel<8, 0, 2, 0, 0, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, LDSB));
-      PF_HIP(hipFuncSetAttribute((const void*)ffn_fused_kernel<8, 0, 2, 0, 0, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, LDSB));
-      PF_HIP(hipFuncSetAttribute((const void*)ffn_fused_kernel<8, 0, 2, 0, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDSB));
-      PF_HIP(hipFuncSetAttribute((const void*)ffn_fused_kernel<8, 0, 2, 2, 0, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, LDSB));
-      PF_HIP(hipFuncSetAttribute((const void*)ffn_fused_kernel<8, 0, 2, 2, 0, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, LDSB));
-      PF_HIP(hipFuncSetAttribute((const void*)ffn_fused_kernel<8, 0, 2, 2, 0, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, LDSB));
-      PF_HIP(hipFuncSetAttribute((const void*)ffn_fused_kernel<8, 0, 2, 2, 0, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, LDSB));
-      PF_HIP(hipFuncSetAttribute((const void*)ffn_fused_kernel<8, 0, 2, 2, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDSB));
-      attr_set[dev & 63] = true;
-    }
-  }
+  static DeviceOnce once;
+  once.run([] {
+    set_max_lds((const void*)ffn_fused_kernel<8, 0, 2, 0, 0, 8>, LDSB);
+    set_max_lds((const void*)ffn_fused_kernel<8, 0, 2, 0, 0, 4>, LDSB);
+    set_max_lds((const void*)ffn_fused_kernel<8, 0, 2, 0, 0, 3>, LDSB);
+    set_max_lds((const void*)ffn_fused_kernel<8, 0, 2, 0, 0, 2>, LDSB);
+    set_max_lds((const void*)ffn_fused_kernel<8, 0, 2, 0, 0, 1>, LDSB);
+    set_max_lds((const void*)ffn_fused_kernel<8, 0, 2, 2, 0, 8>, LDSB);
+    set_max_lds((const void*)ffn_fused_kernel<8, 0, 2, 2, 0, 4>, LDSB);
+    set_max_lds((const void*)ffn_fused_kernel<8, 0, 2, 2, 0, 3>, LDSB);
+    set_max_lds((const void*)ffn_fused_kernel<8, 0, 2, 2, 0, 2>, LDSB);
+    set_max_lds((const void*)ffn_fused_kernel<8, 0, 2, 2, 0, 1>, LDSB);
+  });
   const dim3 grid((unsigned)(cdiv(a.M, FF_BM) * S));
 #ifdef PF_FFN_ABLATIONS
   if (const char* e = getenv("PF_DEC_ABL")) {              // tools/dec_ffn_abl.sh: garbage results, only the times matter (S = 3 forms)
@@ -1144,21 +1112,14 @@ void launch_ffn_fused(hipStream_t s, const FfnFusedArgs& a) {
   PF_CHECK(!op || (a.Wot && a.bo && a.fsmn_v && a.fsmn_wT && a.ln2_g && a.ln2_b && a.lda_c % 8 == 0 && a.ldv % 4 == 0 && d.T >= 8),
            PF_ERR_INVALID_ARG, "ffn_fused: the out-projection form needs ctx, Wo, bias, the V slice, FSMN taps and norm2");
   PF_CHECK(op || a.A, PF_ERR_INVALID_ARG, "ffn_fused: missing operand");
-  static std::mutex init_mu;
-  static bool attr_set[64] = {false};
   static int abl = 0;
-  int dev = 0;
-  PF_HIP(hipGetDevice(&dev));
-  {
-    std::lock_guard<std::mutex> lk(init_mu);
-    if (!attr_set[dev & 63]) {
-      PF_HIP(hipFuncSetAttribute((const void*)ffn_fused_kernel<8, 0, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, FF_LDS));
-      PF_HIP(hipFuncSetAttribute((const void*)ffn_fused_kernel<8, 0, 2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, FF_LDS));
-      PF_HIP(hipFuncSetAttribute((const void*)ffn_fused_kernel<8, 0, 2, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, FF_LDS));
-      if (const char* e = getenv("PF_FFN_ABL")) abl = atoi(e);
-      attr_set[dev & 63] = true;
-    }
-  }
+  static DeviceOnce once;
+  once.run([] {
+    set_max_lds((const void*)ffn_fused_kernel<8, 0, 2>, FF_LDS);
+    set_max_lds((const void*)ffn_fused_kernel<8, 0, 2, 1>, FF_LDS);
+    set_max_lds((const void*)ffn_fused_kernel<8, 0, 2, 1, 1>, FF_LDS);
+    if (const char* e = getenv("PF_FFN_ABL")) abl = atoi(e);
+  });
   d.rot_mask = 7;                                       // chunk-order rotation period - 1
   const dim3 grid((unsigned)cdiv(a.M, FF_BM));
 #ifdef PF_FFN_ABLATIONS

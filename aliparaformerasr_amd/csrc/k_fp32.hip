@@ -5,11 +5,10 @@
 // accumulation order.  1/16 of the f16 MFMA rate by construction and deliberately simple (LDS-staged 64 x 64 tiles, no
 // software pipelining): this mode exists to check token identity against fp32 references, not to be benchmarked.
 #include "kernels.h"
+#include "kdev.h"
 #include "exact.h"
 
 namespace pf {
-
-typedef float f16x __attribute__((ext_vector_type(16)));
 
 struct G32Dev {
   const float* A; const float* W; const float* bias; const float* resid; float* out;
@@ -195,7 +194,6 @@ __global__ __launch_bounds__(256) void attn_f32_mfma_kernel(const float* __restr
     // fma(oacc, inv, -hi), the difference would be taken from the unrounded product, lo' would carry bits below the fp32
     // value's last place and the pair would differ from split_x3_kernel's of the fp32 result (the fallback's).
 #pragma clang fp contract(off)
-    typedef _Float16 h4 __attribute__((ext_vector_type(4)));
     half_t* pp = opair + (size_t)b * o_bs + (size_t)(q0 + l31) * o_rs + h * 128;
 #pragma unroll
     for (int d = 0; d < 4; ++d)
@@ -263,7 +261,6 @@ __global__ __launch_bounds__(256) void split_x3_kernel(const float* __restrict__
   if (i >= rows * kq) return;
   const int64_t r = i / kq;
   const int c = (int)(i - r * kq) * 4;
-  typedef _Float16 h4 __attribute__((ext_vector_type(4)));
   h4 hi, lo;
 #pragma unroll
   for (int e = 0; e < 4; ++e) {

@@ -364,14 +364,7 @@ void launch_fbank(hipStream_t s, const FbankTables* tb, const float* audio, cons
   p.window = tb->window; p.tw512 = tb->tw512; p.mel_w = tb->mel_w; p.mel_chunk = tb->mel_chunk; p.mel_chunk_off = tb->mel_chunk_off;
   p.n_chunks = tb->n_chunks; p.n_weights = tb->n_weights;
   p.dither = dither; p.dither_seed = dither_seed; p.out = fbank;
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    PF_HIP(hipGetDevice(&dev));
-    PF_HIP(hipGetDeviceProperties(&prop, dev));
-    cus = prop.multiProcessorCount;
-  }
+  const int cus = device_cu_count();                     // all of them: PF_CU_CAP limits the persistent GEMM grids only (common.h)
   const int64_t blocks = (total_frames + 3) / 4;
   // the persistent grid = exactly the workgroups that are resident at once (the occupancy the registers and the LDS
   // allow: 4 per CU at 114 VGPRs); a grid of 5 per CU ran its fifth workgroups as a second round: 156 vs 131 us

@@ -41,6 +41,7 @@
 //    residual loads and stores are whole row segments (lds_epilogue32); edge tiles use direct 16-byte I/O.
 //  * Two kernel kinds (f16-only / fp32) x two tile heights (256 / 128 rows, MI = 2 / 1) are instantiated.
 #include "kernels.h"
+#include "kdev.h"
 #include "exact.h"
 
 #include <cstdlib>
@@ -48,15 +49,6 @@
 #include <type_traits>
 
 namespace pf {
-
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef float f16x __attribute__((ext_vector_type(16)));
-// LDS scratch is written with one vector width and read back with another: these accesses must
-// not be reordered by type-based alias analysis
-typedef h8 __attribute__((may_alias)) h8a;
-typedef h4 __attribute__((may_alias)) h4a;
-typedef float4 __attribute__((may_alias)) float4a;
 template <int V>
 using ic = std::integral_constant<int, V>;
 
@@ -85,52 +77,13 @@ struct GemmDev {
   float* q_part;             // null, or QMM_G {min, max} pairs: the result's range for the quantiser that consumes it (k_quant.hip)
 };
 
-__device__ __forceinline__ void glds16(const void* g, void* l) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-}
-__device__ __forceinline__ void glds4(const void* g, void* l) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)l, 4, 0, 0);
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  // gfx9 s_waitcnt simm16: vmcnt[3:0] | expcnt[6:4] | lgkmcnt[11:8] | vmcnt[5:4] << 14
-  __builtin_amdgcn_s_waitcnt((N & 15) | (7 << 4) | (15 << 8) | ((N >> 4) << 14));
-}
-
 // compile-time ablation bits for tools/gemm_abl.sh (timing experiments only; 0 in every shipped build):
 // 1 no steady-state DMA, 2 no fragment reads, 4 no MFMA, 8 no f16 output stores, 16 no direct (fp32) epilogue, 32 no transpose passes
 #ifndef PF_ABL
 #define PF_ABL 0
 #endif
 constexpr int ABL = PF_ABL;
-// cache policy of the deferred f16 result stores: 0 plain, 1 nt, 2 sc1 (write-through, line dropped from the
-// XCD's L2).  66 MB of results per launch otherwise churn the 8 x 4 MB L2s that hold the A panels and W tiles.
-// A/B in one session (tools/gemm_st.sh): plain 14.88-14.96 ms/step, nt 14.96-14.99 (the consumers then miss),
-// sc1 14.81 (QKV -5 %, FFN-up -3 %, attention / FSMN / FFN-down unchanged).
-#ifndef PF_GEMM_ST
-#define PF_GEMM_ST 2
-#endif
-__device__ __forceinline__ void st16(void* p, h8 v) {
-#if PF_GEMM_ST == 1
-  asm volatile("global_store_dwordx4 %0, %1, off nt" ::"v"(p), "v"(v) : "memory");
-#elif PF_GEMM_ST == 2
-  asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(p), "v"(v) : "memory");
-#else
-  *reinterpret_cast<h8*>(p) = v;
-#endif
-}
-__device__ __forceinline__ void st8(void* p, h4 v) {
-#if PF_GEMM_ST == 1
-  asm volatile("global_store_dwordx2 %0, %1, off nt" ::"v"(p), "v"(v) : "memory");
-#elif PF_GEMM_ST == 2
-  asm volatile("global_store_dwordx2 %0, %1, off sc1" ::"v"(p), "v"(v) : "memory");
-#else
-  *reinterpret_cast<h4*>(p) = v;
-#endif
-}
+// (the deferred f16 result stores st16 / st8 and their cache policy PF_GEMM_ST: kdev.h)
 constexpr int GEMM_BN = 128, GEMM_BK = 64, GEMM_S = 3;   // tile rows: 128 * MI (MI = 32-row MFMA blocks per wave)
 constexpr int GEMM_SCRATCH = 8 * 2048;                                   // 2 KiB per wave
 constexpr int gemm_lds_bytes(int mi) { return GEMM_S * (128 * mi + GEMM_BN) * GEMM_BK * 2 + GEMM_SCRATCH; }   // MI=2: 160 KiB
@@ -801,6 +754,21 @@ static thread_local const char* g_last_gemm_kernel = "";
 const char* last_gemm_kernel() { return g_last_gemm_kernel; }
 void note_gemm_kernel(const char* name) { g_last_gemm_kernel = name; }
 
+int device_cu_count() {
+  static std::mutex mu;
+  static int cus[64] = {0};
+  int dev = 0;
+  PF_HIP(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> lk(mu);
+  if (!cus[dev & 63]) {
+    hipDeviceProp_t prop;
+    PF_HIP(hipGetDeviceProperties(&prop, dev));
+    cus[dev & 63] = prop.multiProcessorCount;
+  }
+  return cus[dev & 63];
+}
+int device_cus() { return cu_limit(device_cu_count()); }
+
 void launch_gemm(hipStream_t s, const GemmArgs& a) {
   PF_CHECK(a.K % 64 == 0 && a.K > 0, PF_ERR_INVALID_ARG, "gemm: K must be a multiple of 64");
   PF_CHECK(a.lda % 8 == 0 && a.ldw % 8 == 0, PF_ERR_INVALID_ARG, "gemm: lda/ldw must be multiples of 8");
@@ -840,29 +808,18 @@ void launch_gemm(hipStream_t s, const GemmArgs& a) {
   // A/B in one session: x = 0.9 -> 14.85 ms/step, x = 0 -> 15.15, x >= 1.5 (also the encoder N = 512 GEMMs) -> 15.9.
   // Round 3: x = 0.6 — between 0.6 and 0.9 of the CUs in 256-row tiles, the 128-row form needs a second round (SenseVoice's
   // FFN-down at M = 10 880: 172 tiles -> 340 = 2 rounds x 0.58): 3.6 -> 2.87 ms per step there, 13.55 -> 12.8 ms for configs[2]
-  int dev = 0;
-  PF_HIP(hipGetDevice(&dev));
-  dev &= 63;
-  // per-device launch facts, initialised once per device under a lock: engines on different devices launch
-  // from different host threads (one engine per GPU, include/paraformer_hip.h pf_group_*)
-  static std::mutex init_mu;
-  static int cus[64] = {0};
   // PF_GEMM_MI_X: tuning knob for tools/ (tiles < x * CUs -> 128-row tiles)
   static const float mi_x = [] { const char* e = getenv("PF_GEMM_MI_X"); return e ? (float)atof(e) : 0.6f; }();
-  {
-    std::lock_guard<std::mutex> lk(init_mu);
-    if (!cus[dev]) {
-      hipDeviceProp_t prop;
-      PF_HIP(hipGetDeviceProperties(&prop, dev));
-      PF_HIP(hipFuncSetAttribute((const void*)gemm_f16_pp3<1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, gemm_lds_bytes(2)));
-      PF_HIP(hipFuncSetAttribute((const void*)gemm_f16_pp3<2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, gemm_lds_bytes(2)));
-      PF_HIP(hipFuncSetAttribute((const void*)gemm_f16_pp3<1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, gemm_lds_bytes(1)));
-      PF_HIP(hipFuncSetAttribute((const void*)gemm_f16_pp3<2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, gemm_lds_bytes(1)));
-      PF_HIP(hipFuncSetAttribute((const void*)gemm_f16_pp3<3, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, gemm_lds_bytes(2)));
-      PF_HIP(hipFuncSetAttribute((const void*)gemm_f16_pp3<3, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, gemm_lds_bytes(1)));
-      cus[dev] = cu_limit(prop.multiProcessorCount);
-    }
-  }
+  static DeviceOnce once;
+  once.run([] {
+    set_max_lds((const void*)gemm_f16_pp3<1, 2>, gemm_lds_bytes(2));
+    set_max_lds((const void*)gemm_f16_pp3<2, 2>, gemm_lds_bytes(2));
+    set_max_lds((const void*)gemm_f16_pp3<1, 1>, gemm_lds_bytes(1));
+    set_max_lds((const void*)gemm_f16_pp3<2, 1>, gemm_lds_bytes(1));
+    set_max_lds((const void*)gemm_f16_pp3<3, 2>, gemm_lds_bytes(2));
+    set_max_lds((const void*)gemm_f16_pp3<3, 1>, gemm_lds_bytes(1));
+  });
+  const int cus = device_cus();
   {
     // blocked-layout results (FFN-up): the persistent 256 x 256-tile kernel (k_gemm_big.hip)
     const bool can = gemm_bigp_applicable(a);
@@ -870,9 +827,9 @@ void launch_gemm(hipStream_t s, const GemmArgs& a) {
     // by rounds: a 256 x 256 tile costs ~1.9 tiles of this file's kernel; whichever schedule has less idle tail wins
     // (M = 16000: 504 tiles = 2 rounds vs 1008 = 4 -> persistent; SenseVoice M = 10944: 344 = 2 rounds vs 688 = 3 -> this kernel)
     const int t_big = cdiv(a.M, 256) * (a.N / 256), t_pp3 = cdiv(a.M, 256) * cdiv(a.N, GEMM_BN);
-    const bool fewer_rounds = t_big >= cus[dev] && 1.9 * cdiv(t_big, cus[dev]) <= (double)cdiv(t_pp3, cus[dev]);
+    const bool fewer_rounds = t_big >= cus && 1.9 * cdiv(t_big, cus) <= (double)cdiv(t_pp3, cus);
     if (can && (a.force_mi == 5 || (a.force_mi == 0 && fewer_rounds))) {
-      launch_gemm_bigp(s, a, cus[dev]);
+      launch_gemm_bigp(s, a, cus);
       return;
     }
   }
@@ -880,15 +837,15 @@ void launch_gemm(hipStream_t s, const GemmArgs& a) {
   // bytes); whichever schedule has the shorter last round wins (decoder FFN-up, M = 5344: 336 tiles = 2 rounds vs
   // 672 = 3 x 0.58).
   const int t2 = cdiv(d.M, 256) * cdiv(d.N, GEMM_BN), t1 = cdiv(d.M, 128) * cdiv(d.N, GEMM_BN);
-  const bool few = (float)t2 < mi_x * cus[dev];
-  const bool rounds1 = 0.58 * cdiv(t1, cus[dev]) < (double)cdiv(t2, cus[dev]);
+  const bool few = (float)t2 < mi_x * cus;
+  const bool rounds1 = 0.58 * cdiv(t1, cus) < (double)cdiv(t2, cus);
   const int mi = a.force_mi ? (a.force_mi == 1 ? 1 : 2) : ((few || rounds1) ? 1 : 2);
   PF_CHECK(a.force_mi != 6, PF_ERR_UNSUPPORTED, "gemm: the k-step-32 kernel was removed in round 5 (numbers: profiles/round4_k32_microbench.txt)");
   d.tiles_m = cdiv(d.M, 128 * mi);
   d.tiles_n = cdiv(d.N, GEMM_BN);
   const int total = d.tiles_m * d.tiles_n;
   if (total == 0) return;
-  int grid = cus[dev];
+  int grid = cus;
   if (grid > total) grid = total;
   const bool f16_only = a.out_f16 && !a.out_f32 && !a.resid && !a.add2 && a.out_padded && ((a.ldc16 & 7) == 0 || a.out_blocked) &&
                         a.f16_lo_off == 0 && a.k_wrap == 0;     // (pair output and the K-loop wrap live in the fp32-kind kernel)
@@ -924,32 +881,23 @@ void launch_gemm_i8(hipStream_t s, const GemmI8Args& a) {
   d.relu = a.relu; d.scale_cols = a.scale_cols; d.scale = a.scale_cols > 0 ? a.scale : 1.f;
   d.out_padded = 0; d.out_blocked = 0; d.a_blocked = 0;
   d.q_rowsum = a.rowsum; d.q_colsum = a.colsum; d.q_wzp = a.wzp; d.q_wscale = a.wscale; d.q_aparams = a.aparams; d.q_k = a.K;
-  int dev = 0;
-  PF_HIP(hipGetDevice(&dev));
-  dev &= 63;
-  static std::mutex init_mu;
-  static int cus[64] = {0};
-  {
-    std::lock_guard<std::mutex> lk(init_mu);
-    if (!cus[dev]) {
-      hipDeviceProp_t prop;
-      PF_HIP(hipGetDeviceProperties(&prop, dev));
-      PF_HIP(hipFuncSetAttribute((const void*)gemm_i8_pp3<2>, hipFuncAttributeMaxDynamicSharedMemorySize, gemm_lds_bytes(2)));
-      PF_HIP(hipFuncSetAttribute((const void*)gemm_i8_pp3<1>, hipFuncAttributeMaxDynamicSharedMemorySize, gemm_lds_bytes(1)));
-      PF_HIP(hipFuncSetAttribute((const void*)gemm_i8f_pp3<2>, hipFuncAttributeMaxDynamicSharedMemorySize, gemm_lds_bytes(2)));
-      PF_HIP(hipFuncSetAttribute((const void*)gemm_i8f_pp3<1>, hipFuncAttributeMaxDynamicSharedMemorySize, gemm_lds_bytes(1)));
-      cus[dev] = cu_limit(prop.multiProcessorCount);
-    }
-  }
+  static DeviceOnce once;
+  once.run([] {
+    set_max_lds((const void*)gemm_i8_pp3<2>, gemm_lds_bytes(2));
+    set_max_lds((const void*)gemm_i8_pp3<1>, gemm_lds_bytes(1));
+    set_max_lds((const void*)gemm_i8f_pp3<2>, gemm_lds_bytes(2));
+    set_max_lds((const void*)gemm_i8f_pp3<1>, gemm_lds_bytes(1));
+  });
+  const int cus = device_cus();
   const int t2 = cdiv(d.M, 256) * cdiv(d.N, GEMM_BN), t1 = cdiv(d.M, 128) * cdiv(d.N, GEMM_BN);
-  const bool few = (float)t2 < 0.9f * cus[dev];       // (int8: 0.9 measured better than the f16 kernels' 0.6 — SenseVoice 16.9 vs 17.5 ms)
-  const bool rounds1 = 0.58 * cdiv(t1, cus[dev]) < (double)cdiv(t2, cus[dev]);
+  const bool few = (float)t2 < 0.9f * cus;       // (int8: 0.9 measured better than the f16 kernels' 0.6 — SenseVoice 16.9 vs 17.5 ms)
+  const bool rounds1 = 0.58 * cdiv(t1, cus) < (double)cdiv(t2, cus);
   const int mi = (few || rounds1) ? 1 : 2;
   d.tiles_m = cdiv(d.M, 128 * mi);
   d.tiles_n = cdiv(d.N, GEMM_BN);
   const int total = d.tiles_m * d.tiles_n;
   if (total == 0) return;
-  const int grid = std::min(cus[dev], total);
+  const int grid = std::min(cus, total);
   PF_CHECK(!a.range_out || grid <= 256, PF_ERR_UNSUPPORTED, "gemm_i8: range output needs a grid of at most 256 workgroups");
   d.q_dz = a.dz; d.q_part = a.range_out;
   // f16-only results into a padded buffer: the deferred packed epilogue (gemm_i8f_pp3), as the f16 path's KIND 1

@@ -20,18 +20,12 @@
 // epilogue; it measured equal to gemm_f16_pp3 on every shape — its per-tile prologue / epilogue is not overlapped at
 // K = 512 — and was removed in round 3: profiles/round2_gemm_big_ablation.txt keeps the numbers.)
 #include "kernels.h"
+#include "kdev.h"
 
 #include <algorithm>
 #include <cstdlib>
-#include <mutex>
 
 namespace pf {
-
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef float f16x __attribute__((ext_vector_type(16)));
-typedef h4 __attribute__((may_alias)) h4a;
-typedef h8 __attribute__((may_alias)) h8a;
 
 struct BigDev {
   const half_t* A; const half_t* W; const float* bias; half_t* out;
@@ -53,21 +47,6 @@ constexpr int bg_stage(int nj) { return (BG_BM + 64 * nj) * BG_ROWB; }          
 constexpr int bg_xrow(int nj) { return 64 * nj * 2 + 16; }                       // f16 epilogue row + 16-byte skew
 constexpr int bg_lds(int nj) { return BG_S * bg_stage(nj) > BG_BM * bg_xrow(nj) ? BG_S * bg_stage(nj) : BG_BM * bg_xrow(nj); }
 
-__device__ __forceinline__ void bg_glds16(const void* g, void* l) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-}
-template <int N>
-__device__ __forceinline__ void bg_wait_vmcnt() {
-  __builtin_amdgcn_s_waitcnt((N & 15) | (7 << 4) | (15 << 8) | ((N >> 4) << 14));
-}
-// result stores are write-through and dropped from the XCD's L2 (sc1): 66 MB of results per launch would otherwise
-// evict the W panel and the A panels the other tiles of this XCD are re-reading (k_gemm.hip measured the same)
-__device__ __forceinline__ void bg_store16(void* p, h8 v) {
-  asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
-}
-__device__ __forceinline__ void bg_wait_lgkm0() { __builtin_amdgcn_s_waitcnt(0xC07F); }
-
 // ---------------------------------------------------------------------------------------------------------------
 // Persistent form for the blocked-layout result (FFN-up: [M x 512] x [512 x 2048] + bias + ReLU -> the blocked f16
 // hidden): one workgroup per CU walks tiles slot, slot + G, .. with the (tile, k-step) sequence as ONE flat pipeline,
@@ -77,13 +56,6 @@ __device__ __forceinline__ void bg_wait_lgkm0() { __builtin_amdgcn_s_waitcnt(0xC
 // ReLU + cvt, then 32 fire-and-forget 512-byte stores per wave straight from the accumulators, which are zeroed and
 // reused at once.  Those stores enter the vmcnt immediates exactly (vmcnt retires in order): the two waits that follow
 // a tile end allow 32 more operations in flight.
-__device__ __forceinline__ void bg_store8(void* p, h4 v) {
-  asm volatile("global_store_dwordx2 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
-}
-__device__ __forceinline__ void bg_glds4(const void* g, void* l) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)l, 4, 0, 0);
-}
 constexpr int BGP_NJ = 4, BGP_BN = 64 * BGP_NJ, BGP_STAGE = bg_stage(BGP_NJ), BGP_RING = BG_S * BGP_STAGE;
 constexpr int BGP_LDS = BGP_RING + 2 * BGP_BN * 4;            // ring + two bias lines
 
@@ -131,8 +103,8 @@ __global__ __launch_bounds__(512, 1) void gemm_bigp_kernel(BigDev p) {
   auto issue_piece = [&](int q) __attribute__((always_inline)) {
     if (BG_ABL & 1) return;
     char* st = smem + (is_slot & (BG_S - 1)) * STAGE + wave * 1024;
-    if (q < 2) bg_glds16(is_a + a_vo[q & 1], st + (q & 1) * 8192);
-    else bg_glds16(is_w + w_vo[q & 1], st + A_BYTES + (q & 1) * 8192);
+    if (q < 2) glds16(is_a + a_vo[q & 1], st + (q & 1) * 8192);
+    else glds16(is_w + w_vo[q & 1], st + A_BYTES + (q & 1) * 8192);
   };
   // The loop body is BRANCH-FREE (a conditional DMA or wait splits the block, and the compiler then puts a full
   // lgkmcnt(0) in front of the first MFMA: the fragment reads issued just before it would no longer run under the
@@ -142,7 +114,7 @@ __global__ __launch_bounds__(512, 1) void gemm_bigp_kernel(BigDev p) {
   // slot nobody reads again), which makes every vmcnt immediate a compile-time constant.
   auto issue_bias = [&]() __attribute__((always_inline)) {
     if (BG_ABL & 1) return;
-    bg_glds4(p.bias + is_n0 + (wave & 3) * 64 + lane, bias_line + (is_round & 1) * BN + (wave & 3) * 64);
+    glds4(p.bias + is_n0 + (wave & 3) * 64 + lane, bias_line + (is_round & 1) * BN + (wave & 3) * 64);
   };
   auto issue_advance = [&]() __attribute__((always_inline)) {
     if (is_t + 1 < T) {
@@ -155,7 +127,7 @@ __global__ __launch_bounds__(512, 1) void gemm_bigp_kernel(BigDev p) {
   // stage t + 1 of this wave has landed: the 2 x 5 operations of stages t + 2, t + 3 (and, for two steps after a tile
   // end, its 32 stores) may still be in flight
   auto wait_landed = [&](bool burst) __attribute__((always_inline)) {
-    if (burst) bg_wait_vmcnt<42>(); else bg_wait_vmcnt<10>();
+    if (burst) wait_vmcnt<42>(); else wait_vmcnt<10>();
   };
 
   unsigned fa[2][2], fb[2][NJ];
@@ -226,7 +198,6 @@ __global__ __launch_bounds__(512, 1) void gemm_bigp_kernel(BigDev p) {
   // ---- tile end: bias + scale + ReLU + cvt, 2 * NJ * 4 = 32 blocked-layout stores per wave, accumulators reused at once
   // accumulators START as the bias of their tile (a 16-byte LDS read per register quad), so the tile end is only
   // [scale] -> cvt -> packed ReLU -> store, and the next tile's bias is loaded in place of the zeroing
-  typedef float f4v __attribute__((ext_vector_type(4)));
   auto acc_init = [&](int rnd) __attribute__((always_inline)) {
     const unsigned bl = lds0 + BGP_RING + ((rnd & 1) * BN + wn * (32 * NJ) + 4 * lh) * 4;
     f4v b4[NJ][4];
@@ -246,8 +217,6 @@ __global__ __launch_bounds__(512, 1) void gemm_bigp_kernel(BigDev p) {
           acc[i][j][4 * g + 0] = b4[j][g][0]; acc[i][j][4 * g + 1] = b4[j][g][1]; acc[i][j][4 * g + 2] = b4[j][g][2]; acc[i][j][4 * g + 3] = b4[j][g][3];
         }
   };
-  typedef float f2v __attribute__((ext_vector_type(2)));
-  typedef _Float16 h2v __attribute__((ext_vector_type(2)));
   auto tile_end = [&]() __attribute__((always_inline)) {
     const int tm = tile / p.tiles_n, tn = tile - tm * p.tiles_n;
     const int m0 = tm * BG_BM, n0 = tn * BN;
@@ -268,7 +237,7 @@ __global__ __launch_bounds__(512, 1) void gemm_bigp_kernel(BigDev p) {
           h2v l = __builtin_convertvector(lo2, h2v), h = __builtin_convertvector(hi2, h2v);
           if (p.relu) { l = __builtin_elementwise_max(l, zero2); h = __builtin_elementwise_max(h, zero2); }
           const h4 hv = {l[0], l[1], h[0], h[1]};
-          if (!(BG_ABL & 4)) bg_store8(ob + i * rb_stride + (size_t)(j * 4 + g) * 512, hv);
+          if (!(BG_ABL & 4)) store8_sc1(ob + i * rb_stride + (size_t)(j * 4 + g) * 512, hv);
         }
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -301,7 +270,7 @@ __global__ __launch_bounds__(512, 1) void gemm_bigp_kernel(BigDev p) {
     ++since_burst;
     if (++k == nk) tile_end();
   }
-  bg_wait_vmcnt<0>();                                          // the clamped DMA of the last steps must not outlive the workgroup's LDS
+  wait_vmcnt<0>();                                          // the clamped DMA of the last steps must not outlive the workgroup's LDS
 }
 
 bool gemm_bigp_applicable(const GemmArgs& a) {
@@ -319,29 +288,21 @@ void launch_gemm_bigp(hipStream_t s, const GemmArgs& a, int cus) {
   d.relu = a.relu; d.scale_cols = a.scale_cols; d.scale = a.scale_cols > 0 ? a.scale : 1.f;
   d.blocked = 1;
   if (!d.bias) {                                             // the kernel always loads a bias line: zeros when there is none
-    static std::mutex zmu;
+    static DeviceOnce zonce;
     static float* zeros[64] = {nullptr};
     int zd = 0;
     PF_HIP(hipGetDevice(&zd));
-    std::lock_guard<std::mutex> lk(zmu);
-    if (!zeros[zd & 63]) {
+    zonce.run([zd] {
       PF_HIP(hipMalloc(&zeros[zd & 63], 65536 * 4));
       PF_HIP(hipMemset(zeros[zd & 63], 0, 65536 * 4));
       PF_HIP(hipDeviceSynchronize());                       // the fill runs on the null stream; the caller's stream does not wait for it
-    }
+    });
     d.bias = zeros[zd & 63];
   }
-  static std::mutex init_mu;
-  static bool attr_set[64] = {false};
-  int dev = 0;
-  PF_HIP(hipGetDevice(&dev));
-  {
-    std::lock_guard<std::mutex> lk(init_mu);
-    if (!attr_set[dev & 63]) {
-      PF_HIP(hipFuncSetAttribute((const void*)gemm_bigp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, BGP_LDS));
-      attr_set[dev & 63] = true;
-    }
-  }
+  static DeviceOnce once;
+  once.run([] {
+    set_max_lds((const void*)gemm_bigp_kernel, BGP_LDS);
+  });
   const int total = d.tiles_m * d.tiles_n;
   if (total == 0) return;
   note_gemm_kernel("gemm_bigp_kernel");

@@ -24,15 +24,11 @@
 // the tile's bias).  Same accumulation order as gemm_f16_pp3 (k ascending in 16-wide MFMA steps from the bias), so
 // the results are bit-identical to the row-major kernel's.
 #include "kernels.h"
+#include "kdev.h"
 
 #include <algorithm>
-#include <mutex>
 
 namespace pf {
-
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef float f16x __attribute__((ext_vector_type(16)));
 
 struct QkvDev {
   const half_t* A; const half_t* W; const float* bias;       // W, bias: tile-permuted (qkv_tile_row)
@@ -64,28 +60,6 @@ __global__ void qkv_permute_kernel(const half_t* __restrict__ w, int ldw, const 
 void launch_qkv_permute(hipStream_t s, const half_t* w, int ldw, const float* bias, half_t* wp, float* bp) {
   hipLaunchKernelGGL(qkv_permute_kernel, dim3(1536), dim3(128), 0, s, w, ldw, bias, wp, bp, ldw);
   PF_HIP(hipGetLastError());
-}
-
-__device__ __forceinline__ void qv_glds16(const void* g, void* l) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-}
-__device__ __forceinline__ void qv_glds4(const void* g, void* l) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)l, 4, 0, 0);
-}
-template <int N>
-__device__ __forceinline__ void qv_wait_vmcnt() {
-  __builtin_amdgcn_s_waitcnt((N & 15) | (7 << 4) | (15 << 8) | ((N >> 4) << 14));
-}
-// Q | K blocks: write-through and dropped from the XCD's L2 (they are read by the attention kernel, after this
-// launch; the L2 is needed for the A panels and W tiles — k_gemm_big.hip measured the same)
-__device__ __forceinline__ void qv_store8_sc1(void* p, h4 v) {
-  asm volatile("global_store_dwordx2 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
-}
-// V pieces: 16 bytes of a 64-byte row segment; write-back, so that the L2 merges the four pieces of a line
-__device__ __forceinline__ void qv_store16(void* p, h8 v) {
-  asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
 }
 
 __global__ __launch_bounds__(512, 1) void gemm_qkvp_kernel(QkvDev p) {
@@ -135,12 +109,12 @@ __global__ __launch_bounds__(512, 1) void gemm_qkvp_kernel(QkvDev p) {
   set_issue_tile();
   auto issue_piece = [&](int q) __attribute__((always_inline)) {
     char* st = smem + (is_slot & (QV_S - 1)) * STAGE;
-    if (q < 2) qv_glds16(is_a + a_vo[q & 1], st + (wave + 8 * (q & 1)) * 1024);
-    else qv_glds16(is_w + w_vo[q & 1], st + w_dst[q & 1]);
+    if (q < 2) glds16(is_a + a_vo[q & 1], st + (wave + 8 * (q & 1)) * 1024);
+    else glds16(is_w + w_vo[q & 1], st + w_dst[q & 1]);
   };
   const int bw = wave % 3;
   auto issue_bias = [&]() __attribute__((always_inline)) {
-    qv_glds4(p.bias + is_n0 + bw * 64 + lane, bias_line + (is_round & 1) * BN + bw * 64);
+    glds4(p.bias + is_n0 + bw * 64 + lane, bias_line + (is_round & 1) * BN + bw * 64);
   };
   auto issue_advance = [&]() __attribute__((always_inline)) {
     if (is_t + 1 < T) {
@@ -151,7 +125,7 @@ __global__ __launch_bounds__(512, 1) void gemm_qkvp_kernel(QkvDev p) {
     ++is_slot;
   };
   auto wait_landed = [&](bool burst) __attribute__((always_inline)) {
-    if (burst) qv_wait_vmcnt<10 + QV_STORES>(); else qv_wait_vmcnt<10>();
+    if (burst) wait_vmcnt<10 + QV_STORES>(); else wait_vmcnt<10>();
   };
 
   unsigned fa[2][2], fb[2][NJ];
@@ -213,7 +187,6 @@ __global__ __launch_bounds__(512, 1) void gemm_qkvp_kernel(QkvDev p) {
   load(lds0, 0, a0, b0);
 
   int tile = slot, k = 0, round = 0, since_burst = 3;
-  typedef float f4v __attribute__((ext_vector_type(4)));
   auto acc_init = [&](int rnd) __attribute__((always_inline)) {
     const unsigned bl = lds0 + QV_RING + ((rnd & 1) * BN + wn * (32 * NJ) + 4 * lh) * 4;
     f4v b4[NJ][4];
@@ -233,8 +206,6 @@ __global__ __launch_bounds__(512, 1) void gemm_qkvp_kernel(QkvDev p) {
           acc[i][j][4 * g + 0] = b4[j][g][0]; acc[i][j][4 * g + 1] = b4[j][g][1]; acc[i][j][4 * g + 2] = b4[j][g][2]; acc[i][j][4 * g + 3] = b4[j][g][3];
         }
   };
-  typedef float f2v __attribute__((ext_vector_type(2)));
-  typedef _Float16 h2v __attribute__((ext_vector_type(2)));
   auto tile_end = [&]() __attribute__((always_inline)) {
     const int tm = tile / QV_TN, tn = tile - tm * QV_TN;
     const int m0 = tm * QV_BM;
@@ -253,7 +224,7 @@ __global__ __launch_bounds__(512, 1) void gemm_qkvp_kernel(QkvDev p) {
           if (scaled) { lo2 *= p.scale; hi2 *= p.scale; }
           const h2v l = __builtin_convertvector(lo2, h2v), h = __builtin_convertvector(hi2, h2v);
           const h4 hv = {l[0], l[1], h[0], h[1]};
-          qv_store8_sc1(ob + i * rb_stride + (size_t)(j * 4 + g) * 512, hv);
+          store8_sc1(ob + i * rb_stride + (size_t)(j * 4 + g) * 512, hv);
         }
     // ---- V: row-major [M, ldv]; lanes l / l + 32 hold columns 8g + 0..3 / 8g + 4..7 of row l: after the swap lane l
     // holds the 8 columns of group g, lane l + 32 those of group g + 1
@@ -279,7 +250,7 @@ __global__ __launch_bounds__(512, 1) void gemm_qkvp_kernel(QkvDev p) {
           const h4 lo_ = __builtin_bit_cast(h4, (unsigned long long)x[0] | ((unsigned long long)x[1] << 32));
           const h4 hi_ = __builtin_bit_cast(h4, (unsigned long long)y[0] | ((unsigned long long)y[1] << 32));
           const h8 hv = __builtin_shufflevector(lo_, hi_, 0, 1, 2, 3, 4, 5, 6, 7);
-          qv_store16(vrow + 16 * gp + 8 * lh, hv);
+          store16_wb(vrow + 16 * gp + 8 * lh, hv);
         }
       }
     }
@@ -313,7 +284,7 @@ __global__ __launch_bounds__(512, 1) void gemm_qkvp_kernel(QkvDev p) {
     ++since_burst;
     if (++k == nk) tile_end();
   }
-  qv_wait_vmcnt<0>();
+  wait_vmcnt<0>();
 }
 
 bool gemm_qkvp_applicable(int M, int K, int lda, int ldw, int ldv) {
@@ -326,24 +297,11 @@ void launch_gemm_qkvp(hipStream_t s, const half_t* A, int lda, const half_t* Wp,
   QkvDev d{};
   d.A = A; d.W = Wp; d.bias = bias_p; d.out_qk = out_qk; d.out_v = out_v;
   d.lda = lda; d.ldw = ldw; d.ldv = ldv; d.M = M; d.K = K; d.tiles_m = cdiv(M, QV_BM); d.scale = qscale;
-  static std::mutex init_mu;
-  static bool attr_set[64] = {false};
-  static int cus[64] = {0};
-  int dev = 0;
-  PF_HIP(hipGetDevice(&dev));
-  {
-    std::lock_guard<std::mutex> lk(init_mu);
-    if (!attr_set[dev & 63]) {
-      PF_HIP(hipFuncSetAttribute((const void*)gemm_qkvp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, QV_LDS));
-      hipDeviceProp_t prop;
-      PF_HIP(hipGetDeviceProperties(&prop, dev));
-      cus[dev & 63] = cu_limit(prop.multiProcessorCount);
-      attr_set[dev & 63] = true;
-    }
-  }
+  static DeviceOnce once;
+  once.run([] { set_max_lds((const void*)gemm_qkvp_kernel, QV_LDS); });
   const int total = d.tiles_m * QV_TN;
   note_gemm_kernel("gemm_qkvp_kernel");
-  hipLaunchKernelGGL(gemm_qkvp_kernel, dim3((unsigned)std::min(total, cus[dev & 63])), dim3(512), QV_LDS, s, d);
+  hipLaunchKernelGGL(gemm_qkvp_kernel, dim3((unsigned)std::min(total, device_cus())), dim3(512), QV_LDS, s, d);
   PF_HIP(hipGetLastError());
 }
 

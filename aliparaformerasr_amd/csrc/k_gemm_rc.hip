@@ -23,15 +23,9 @@
 // x stores and the f16 stores are whole 1-2 KB row segments, the LayerNorm statistics are two wave reductions
 // (two-pass: mean, then sum of squared deviations), no cross-workgroup traffic of any kind.
 #include "kernels.h"
-
-#include <mutex>
+#include "kdev.h"
 
 namespace pf {
-
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef float f16x __attribute__((ext_vector_type(16)));
-typedef float4 __attribute__((may_alias)) float4a;
 
 struct RcDev {
   const half_t* A; const half_t* W; const float* bias;
@@ -50,30 +44,6 @@ constexpr int RC_W_BYTES = RC_BN * RC_ROWB;              // 64 KiB
 constexpr int RC_STAGE = RC_A_BYTES + RC_W_BYTES;        // 72 KiB
 constexpr int RC_XROW = RC_BN * 4 + 16;                  // epilogue tile: 16-byte skew per row (conflict-free dump)
 constexpr int RC_LDS = 2 * RC_STAGE > RC_BM * RC_XROW ? 2 * RC_STAGE : RC_BM * RC_XROW;   // 144 KiB
-
-__device__ __forceinline__ void rc_glds16(const void* g, void* l) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-}
-template <int N>
-__device__ __forceinline__ void rc_wait_vmcnt() {
-  __builtin_amdgcn_s_waitcnt((N & 15) | (7 << 4) | (15 << 8) | ((N >> 4) << 14));
-}
-__device__ __forceinline__ void rc_wait_lgkm0() { __builtin_amdgcn_s_waitcnt(0xC07F); }   // vmcnt 63, expcnt 7, lgkmcnt 0
-
-// wave-wide sum, broadcast to every lane: four DPP steps give every lane its 16-lane row total (VALU only, no LDS
-// crossbar as ds_bpermute-based shuffles use), the four row totals are read through SGPRs
-__device__ __forceinline__ float rc_wave_sum(float v) {
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, false));   // quad_perm [1,0,3,2]
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, false));   // quad_perm [2,3,0,1]
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, false));  // row_half_mirror
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, false));  // row_mirror
-  const float a = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 0));
-  const float b = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 16));
-  const float c = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 32));
-  const float d = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 48));
-  return (a + b) + (c + d);
-}
 
 // FSMN accumulation for 8 consecutive output rows x 4 columns of one lane.  MASKED: rows near an utterance edge
 // (or the end of the buffer) — taps reaching outside the utterance contribute nothing (zero padding of the
@@ -162,9 +132,9 @@ __global__ __launch_bounds__(512, 1) void gemm_rc_kernel(RcDev p) {
   constexpr int NOPS = PFD > 0 ? 10 : 9;                   // vector-memory operations per wave and k-step
   auto issue = [&](int k, int buf) __attribute__((always_inline)) {
     char* st = smem + buf * RC_STAGE + wave * 1024;
-    rc_glds16(a_base + (size_t)k * a_step + a_vo, st);
+    glds16(a_base + (size_t)k * a_step + a_vo, st);
 #pragma unroll
-    for (int i = 0; i < 8; ++i) rc_glds16(w_base + (size_t)k * (RC_BK * 2) + w_vo[i], st + RC_A_BYTES + i * 8192);
+    for (int i = 0; i < 8; ++i) glds16(w_base + (size_t)k * (RC_BK * 2) + w_vo[i], st + RC_A_BYTES + i * 8192);
   };
 
   // ---- fragment read offsets inside a stage (bytes)
@@ -199,7 +169,7 @@ __global__ __launch_bounds__(512, 1) void gemm_rc_kernel(RcDev p) {
   if (PFD > 0) touch(kk(PFD < nk ? PFD : nk - 1));
   if (nk > 1) issue(kk(1), 1);
   for (int k = 0; k < nk; ++k) {
-    if (k + 1 < nk) rc_wait_vmcnt<NOPS>(); else rc_wait_vmcnt<0>();   // this wave's 9 pieces of stage k have landed
+    if (k + 1 < nk) wait_vmcnt<NOPS>(); else wait_vmcnt<0>();   // this wave's 9 pieces of stage k have landed
     __builtin_amdgcn_s_barrier();                                      // ... and everybody else's
     const char* rd = smem + (k & 1) * RC_STAGE;
     h8 af[4][2], bf[4][2];
@@ -210,7 +180,7 @@ __global__ __launch_bounds__(512, 1) void gemm_rc_kernel(RcDev p) {
         af[s][i] = *(const h8*)(rd + fa[s][i]);
         bf[s][i] = *(const h8*)(rd + fb[s][i]);
       }
-    rc_wait_lgkm0();                                                   // fragments are in registers
+    wait_lgkm0();                                                   // fragments are in registers
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();                                      // nobody reads this stage any more
     const bool more = k + 2 < nk;
@@ -233,8 +203,8 @@ __global__ __launch_bounds__(512, 1) void gemm_rc_kernel(RcDev p) {
         for (int pp = 0; pp < (s == 0 && i == 0 ? 2 : 1); ++pp) {
           __builtin_amdgcn_sched_barrier(0);
           if (more) {
-            if (piece == 0) rc_glds16(an, st);
-            else rc_glds16(wn_ + w_vo[piece > 0 ? piece - 1 : 0], st + RC_A_BYTES + (piece - 1) * 8192);
+            if (piece == 0) glds16(an, st);
+            else glds16(wn_ + w_vo[piece > 0 ? piece - 1 : 0], st + RC_A_BYTES + (piece - 1) * 8192);
           }
           ++piece;
           __builtin_amdgcn_sched_barrier(0);
@@ -321,7 +291,7 @@ __global__ __launch_bounds__(512, 1) void gemm_rc_kernel(RcDev p) {
 #pragma unroll
   for (int r = 0; r < 8; ++r) {
     const float s = ((xv[0][r].x + xv[0][r].y) + (xv[0][r].z + xv[0][r].w)) + ((xv[1][r].x + xv[1][r].y) + (xv[1][r].z + xv[1][r].w));
-    mean[r] = rc_wave_sum(s) * (1.0f / RC_BN);
+    mean[r] = wave_sum(s) * (1.0f / RC_BN);
   }
 #pragma unroll
   for (int r = 0; r < 8; ++r) {
@@ -330,7 +300,7 @@ __global__ __launch_bounds__(512, 1) void gemm_rc_kernel(RcDev p) {
     xv[1][r].x -= m; xv[1][r].y -= m; xv[1][r].z -= m; xv[1][r].w -= m;
     const float q = ((xv[0][r].x * xv[0][r].x + xv[0][r].y * xv[0][r].y) + (xv[0][r].z * xv[0][r].z + xv[0][r].w * xv[0][r].w)) +
                     ((xv[1][r].x * xv[1][r].x + xv[1][r].y * xv[1][r].y) + (xv[1][r].z * xv[1][r].z + xv[1][r].w * xv[1][r].w));
-    rstd[r] = 1.0f / sqrtf(rc_wave_sum(q) * (1.0f / RC_BN) + p.eps);
+    rstd[r] = 1.0f / sqrtf(wave_sum(q) * (1.0f / RC_BN) + p.eps);
   }
 #pragma unroll
   for (int r = 0; r < 8; ++r) {
@@ -374,18 +344,11 @@ void launch_gemm_rc(hipStream_t s, const GemmRcArgs& a) {
   d.lda = a.lda; d.ldw = a.ldw; d.ldr = a.ldr; d.ldx = a.ldx; d.ldv = a.ldv; d.ldn16 = a.ldn16; d.ldn32 = a.ldn32;
   d.M = a.M; d.K = a.K; d.T = a.T > 0 ? a.T : a.M; d.a_blocked = a.a_blocked;
   d.eps = a.eps;
-  static std::mutex init_mu;                         // engines on different devices launch from different threads
-  static bool attr_set[64] = {false};
-  int dev = 0;
-  PF_HIP(hipGetDevice(&dev));
-  {
-    std::lock_guard<std::mutex> lk(init_mu);
-    if (!attr_set[dev & 63]) {
-      PF_HIP(hipFuncSetAttribute((const void*)gemm_rc_kernel<0, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, RC_LDS));
-      PF_HIP(hipFuncSetAttribute((const void*)gemm_rc_kernel<11, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, RC_LDS));
-      attr_set[dev & 63] = true;
-    }
-  }
+  static DeviceOnce once;
+  once.run([] {
+    set_max_lds((const void*)gemm_rc_kernel<0, 0>, RC_LDS);
+    set_max_lds((const void*)gemm_rc_kernel<11, 0>, RC_LDS);
+  });
   const dim3 grid((unsigned)cdiv(a.M, RC_BM));
   if (a.fsmn_v) {                                    // (the names are the ones the rocprofv3 kernel trace shows)
     note_gemm_kernel("gemm_rc_kernel<11, 0>");

@@ -28,15 +28,11 @@
 //   * The encoder's FSMN memory (11 taps over V, channel-local) is an epilogue term of the attention out-projection:
 //     a lane adds sum_j w_j[n] * V[t + j - 5, n] + V[t, n] for its own row and 16 columns.
 #include "kernels.h"
+#include "kdev.h"
 
 #include <cstdlib>
-#include <mutex>
 
 namespace pf {
-
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef float f16x __attribute__((ext_vector_type(16)));
 
 struct SmallDev {
   const half_t* A; int lda;
@@ -56,20 +52,6 @@ constexpr int SM_BM = 128, SM_BN = 32, SM_PART_LD = 512;
 template <int CPR>
 __device__ __forceinline__ int sm_swz(int row, int c) {
   return (CPR & 15) ? (c ^ ((row >> 1) & 7)) : (c ^ (row & 15));
-}
-
-// wave-wide sum broadcast to every lane: four DPP steps + four SGPR reads (VALU only; ds_bpermute-based shuffles cost
-// ~120 cycles each and a LayerNorm is a chain of 12 of them — 15 us for the 24 rows a wave normalises on load)
-__device__ __forceinline__ float sm_wave_sum(float v) {
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, false));   // quad_perm [1,0,3,2]
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, false));   // quad_perm [2,3,0,1]
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, false));  // row_half_mirror
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, false));  // row_mirror
-  const float a = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 0));
-  const float b = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 16));
-  const float c = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 32));
-  const float d = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 48));
-  return (a + b) + (c + d);
 }
 
 // CPR: 16-byte chunks per brick row (KC = 8 * CPR)
@@ -288,9 +270,9 @@ __global__ __launch_bounds__(256) void small_reduce_kernel(ReduceDev p) {
   if (!p.ln_g) return;
   const float x0 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, a.x)));
   a.x -= x0; a.y -= x0; a.z -= x0; a.w -= x0; c.x -= x0; c.y -= x0; c.z -= x0; c.w -= x0;
-  const float mean = sm_wave_sum(((a.x + a.y) + (a.z + a.w)) + ((c.x + c.y) + (c.z + c.w))) * (1.0f / 512.0f);
+  const float mean = wave_sum(((a.x + a.y) + (a.z + a.w)) + ((c.x + c.y) + (c.z + c.w))) * (1.0f / 512.0f);
   a.x -= mean; a.y -= mean; a.z -= mean; a.w -= mean; c.x -= mean; c.y -= mean; c.z -= mean; c.w -= mean;
-  const float var = sm_wave_sum(((a.x * a.x + a.y * a.y) + (a.z * a.z + a.w * a.w)) + ((c.x * c.x + c.y * c.y) + (c.z * c.z + c.w * c.w))) * (1.0f / 512.0f);
+  const float var = wave_sum(((a.x * a.x + a.y * a.y) + (a.z * a.z + a.w * a.w)) + ((c.x * c.x + c.y * c.y) + (c.z * c.z + c.w * c.w))) * (1.0f / 512.0f);
   const float rstd = 1.0f / sqrtf(var + 1e-12f);
   const float4 g0 = *reinterpret_cast<const float4*>(p.ln_g + c0), g1 = *reinterpret_cast<const float4*>(p.ln_g + c1);
   const float4 e0 = *reinterpret_cast<const float4*>(p.ln_b + c0), e1 = *reinterpret_cast<const float4*>(p.ln_b + c1);
@@ -337,17 +319,10 @@ bool gemm_small_applicable(const GemmSmallArgs& a) {
 
 template <int CPR>
 static void small_launch(hipStream_t s, const SmallDev& d, int rows_alloc) {
-  static std::mutex mu;
-  static bool attr[64] = {false};
-  int dev = 0;
-  PF_HIP(hipGetDevice(&dev));
-  {
-    std::lock_guard<std::mutex> lk(mu);
-    if (!attr[dev & 63]) {
-      PF_HIP(hipFuncSetAttribute((const void*)gemm_small_kernel<CPR>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      attr[dev & 63] = true;
-    }
-  }
+  static DeviceOnce once;
+  once.run([] {
+    set_max_lds((const void*)gemm_small_kernel<CPR>, 160 * 1024);
+  });
   const int lds = (rows_alloc + SM_BN) * CPR * 16;
   note_gemm_kernel("gemm_small_kernel");
   hipLaunchKernelGGL((gemm_small_kernel<CPR>), dim3((unsigned)(d.tiles_n * d.tiles_m * d.S)), dim3(256), lds, s, d);

@@ -11,11 +11,10 @@
 //   * FSMN: external ONNX graph (FunASR MultiHeadedAttentionSANM.forward_fsmn and
 //     MultiHeadedAttentionSANMDecoder); kernel_size 11 from EncoderConfEntity.cs:23.
 #include "kernels.h"
+#include "kdev.h"
 #include "exact.h"
 
 namespace pf {
-
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 
 // ------------------------------------------------------------------ encoder FSMN ----------
 // f[b,t,c] = sum_j wT[j][c] * v[b,t+j-left,c] + v[b,t,c]   (zero outside the utterance)
@@ -92,7 +91,6 @@ __global__ __launch_bounds__(256) void fsmn_enc_kernel(const half_t* __restrict_
       float4* o = reinterpret_cast<float4*>(f + ((int64_t)b * T + t0 + q) * D + c0);
 #pragma unroll
       for (int e = 0; e < C; e += 4) {
-        typedef float f4v __attribute__((ext_vector_type(4)));
         const f4v v4 = {acc[q][e], acc[q][e + 1], acc[q][e + 2], acc[q][e + 3]};
 #if FS_ST == 2
         asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(o + e / 4), "v"(v4) : "memory");
@@ -689,7 +687,6 @@ __global__ __launch_bounds__(256) void embed_gather_kernel(const float* __restri
   id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
   const float4 v = *reinterpret_cast<const float4*>(table + (int64_t)id * D + c4);
   *reinterpret_cast<float4*>(out32 + (int64_t)r * D + c4) = v;
-  typedef _Float16 h4 __attribute__((ext_vector_type(4)));
   if (out16) *reinterpret_cast<h4*>(out16 + (int64_t)r * D + c4) = h4{(half_t)v.x, (half_t)v.y, (half_t)v.z, (half_t)v.w};
 }
 
@@ -707,7 +704,6 @@ __global__ __launch_bounds__(256) void add_to_f16_kernel(const float* __restrict
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n4) return;
   const float4 x = reinterpret_cast<const float4*>(a)[i], y = reinterpret_cast<const float4*>(b)[i];
-  typedef _Float16 h4 __attribute__((ext_vector_type(4)));
   reinterpret_cast<h4*>(out16)[i] = h4{(half_t)(x.x + y.x), (half_t)(x.y + y.y), (half_t)(x.z + y.z), (half_t)(x.w + y.w)};
 }
 

@@ -10,6 +10,7 @@
 // into the first layer's norm1; the multiply and the add are kept as two separately
 // rounded fp32 operations (no FMA contraction) to match a Mul node followed by an Add node.
 #include "kernels.h"
+#include "kdev.h"
 
 #include <cstdlib>
 #include "exact.h"
@@ -17,20 +18,6 @@
 namespace pf {
 
 #define LN_EPS 1e-12f
-
-// wave-wide sum broadcast to every lane: four DPP steps + four SGPR reads (VALU only; a ds_bpermute-based butterfly is a
-// chain of six LDS-crossbar round trips, which is most of a small launch's run time)
-__device__ __forceinline__ float wave_sum(float v) {
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, false));   // quad_perm [1,0,3,2]
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, false));   // quad_perm [2,3,0,1]
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, false));  // row_half_mirror
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, false));  // row_mirror
-  const float a = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 0));
-  const float b = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 16));
-  const float c = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 32));
-  const float d = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 48));
-  return (a + b) + (c + d);
-}
 
 // NV = float4 slots per lane; row width D (multiple of 4, D/4 <= 64*NV)
 template <int NV, bool POSENC>
@@ -105,7 +92,6 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
       y.w = (v[i].w - mean) * rstd * g.w + b.w;
       if (out32) reinterpret_cast<float4*>(out32 + row * (int64_t)ld32)[qd] = y;
       if (out16) {
-        typedef _Float16 h4 __attribute__((ext_vector_type(4)));
         h4 h = {(half_t)y.x, (half_t)y.y, (half_t)y.z, (half_t)y.w};
         reinterpret_cast<h4*>(out16 + row * (int64_t)ld16)[qd] = h;
       }
@@ -179,7 +165,6 @@ __global__ __launch_bounds__(256) void layernorm512_kernel(const float* __restri
       reinterpret_cast<float4*>(out32 + row * (int64_t)ld32)[lane + 64] = yb;
     }
     if (out16) {
-      typedef _Float16 h4 __attribute__((ext_vector_type(4)));
       const h4 ha = h4{(half_t)ya.x, (half_t)ya.y, (half_t)ya.z, (half_t)ya.w}, hb = h4{(half_t)yb.x, (half_t)yb.y, (half_t)yb.z, (half_t)yb.w};
       reinterpret_cast<h4*>(out16 + row * (int64_t)ld16)[lane] = ha;
       reinterpret_cast<h4*>(out16 + row * (int64_t)ld16)[lane + 64] = hb;
@@ -247,7 +232,6 @@ template <int NV>
 __global__ __launch_bounds__(256) void layernorm_f16_kernel(const half_t* __restrict__ x, int64_t rows, int D,
                                                             const float* __restrict__ gamma, const float* __restrict__ beta,
                                                             half_t* __restrict__ out) {
-  typedef _Float16 h8 __attribute__((ext_vector_type(8)));
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
@@ -388,7 +372,6 @@ __global__ __launch_bounds__(256) void fsmn_dec_ln_kernel(const float* __restric
     a.x -= mean; a.y -= mean; a.z -= mean; a.w -= mean; c.x -= mean; c.y -= mean; c.z -= mean; c.w -= mean;
     const float var = wave_sum(((a.x * a.x + a.y * a.y) + (a.z * a.z + a.w * a.w)) + ((c.x * c.x + c.y * c.y) + (c.z * c.z + c.w * c.w))) / (float)D;
     const float rstd = 1.0f / sqrtf(var + LN_EPS);
-    typedef _Float16 h4 __attribute__((ext_vector_type(4)));
     half_t* orow = out16 + ((int64_t)b * L + l) * D;
     *reinterpret_cast<h4*>(orow + c0) = h4{(half_t)(a.x * rstd * g0.x + e0.x), (half_t)(a.y * rstd * g0.y + e0.y),
                                            (half_t)(a.z * rstd * g0.z + e0.z), (half_t)(a.w * rstd * g0.w + e0.w)};

@@ -17,6 +17,7 @@
 // The matrix cores multiply SIGNED bytes, so both sides are stored minus 128 (a' = q - 128) together with the row /
 // column sums that restore the exact integer sum (k_gemm.hip gemm_i8_pp3).
 #include "kernels.h"
+#include "kdev.h"
 #include "exact.h"
 
 namespace pf {
@@ -84,7 +85,6 @@ __global__ __launch_bounds__(QMM_T) void minmax_kernel(const void* __restrict__ 
     const int64_t r = i / cq;
     const int c = (int)(i - r * cq) * 4;
     if constexpr (F16) {
-      typedef _Float16 h4 __attribute__((ext_vector_type(4)));
       const h4 h = *reinterpret_cast<const h4*>(reinterpret_cast<const half_t*>(xv) + r * ldx + c);
       return make_float4((float)h[0], (float)h[1], (float)h[2], (float)h[3]);
     } else {
@@ -138,7 +138,6 @@ __global__ __launch_bounds__(256) void quantize_rows_kernel(const void* __restri
     if (c < cols) {
       float v[4];
       if constexpr (F16) {
-        typedef _Float16 h4 __attribute__((ext_vector_type(4)));
         const h4 h = *reinterpret_cast<const h4*>(reinterpret_cast<const half_t*>(xv) + r * ldx + c);
         v[0] = (float)h[0]; v[1] = (float)h[1]; v[2] = (float)h[2]; v[3] = (float)h[3];
       } else {
