@@ -13,6 +13,68 @@
 
 namespace pf {
 
+// ---- hostile hosts: the stand-alone GEMM ops hand their kernels what the pipeline may hand them, not what is convenient.
+// Operand rows the contract only calls "readable" (A rows [M, Mp), W rows [N, Np), V rows outside [0, M)) hold a large
+// finite f16 pattern instead of zeros (the K pad columns stay zero: that IS the contract), and every output buffer is
+// pre-filled with a NaN-payload sentinel: after the launch every cell of [M, N] must have been written, nothing may have
+// changed in columns [N, ld) or in rows at or beyond round_up(M, 256) (the 128 spare rows the ops carve are the guard).
+namespace {
+constexpr uint32_t kSentinel32 = 0x7FC5A5A5u;
+constexpr uint16_t kSentinel16 = 0x7E5Au;
+constexpr int kVLead = 64;                                    // rows in front of the V slice of the FSMN ops
+
+inline half_t hostile16(size_t i) {                           // +-32768 .. +-65504, never the same in neighbouring cells
+  const uint16_t bits = (uint16_t)(0x7800u | (uint16_t)((i * 37u) & 0x3FFu) | (uint16_t)((i & 1u) << 15));
+  half_t h;
+  std::memcpy(&h, &bits, 2);
+  return h;
+}
+
+// rows [row0, row1) of a row-major f16 matrix: columns [0, cols) hostile, [cols, ld) zero
+void fill_hostile_rows(hipStream_t s, half_t* base, int ld, int64_t row0, int64_t row1, int cols) {
+  if (row1 <= row0) return;
+  std::vector<half_t> h((size_t)(row1 - row0) * ld, (half_t)0.f);
+  for (int64_t r = 0; r < row1 - row0; ++r)
+    for (int c = 0; c < cols; ++c) h[(size_t)r * ld + c] = hostile16((size_t)(row0 + r) * 131 + c);
+  PF_HIP(hipMemcpyAsync(base + (size_t)row0 * ld, h.data(), h.size() * 2, hipMemcpyHostToDevice, s));
+  PF_HIP(hipStreamSynchronize(s));
+}
+// the same rows of a host image in the blocked activation layout (Kp columns, the first K of them hostile)
+void fill_hostile_blocked(std::vector<half_t>& img, int64_t row0, int64_t row1, int K, int Kp) {
+  for (int64_t m = row0; m < row1; ++m)
+    for (int k = 0; k < K; ++k)
+      img[(((size_t)(m >> 5) * (Kp >> 3) + (k >> 3)) * 32 + (m & 31)) * 8 + (k & 7)] = hostile16((size_t)m * 131 + k);
+}
+void fill_sentinel32(hipStream_t s, void* p, size_t count) { PF_HIP(hipMemsetD32Async((hipDeviceptr_t)p, (int)kSentinel32, count, s)); }
+void fill_sentinel16(hipStream_t s, void* p, size_t count) { PF_HIP(hipMemsetD16Async((hipDeviceptr_t)p, kSentinel16, count, s)); }
+
+// U = uint32_t (fp32 buffers) / uint16_t (f16): rows x ld cells of a buffer that was sentinel-filled before the launch.
+// blocked: the blocked activation layout (ld == N).  written = false: the buffer was not sentinel-filled inside [M, N]
+// (a result that aliases its residual), only the guard rows and columns are checked.
+template <class U>
+void check_guard(hipStream_t s, const char* op, const char* what, const void* dev, U sentinel, int64_t rows, int M, int N, int ld,
+                 bool blocked, bool written = true) {
+  std::vector<U> h((size_t)rows * ld);
+  PF_HIP(hipMemcpyAsync(h.data(), dev, h.size() * sizeof(U), hipMemcpyDeviceToHost, s));
+  PF_HIP(hipStreamSynchronize(s));
+  const int64_t guard = round_up(M, 256);
+  auto at = [&](int64_t m, int n) -> U {
+    return blocked ? h[(((size_t)(m >> 5) * (N >> 3) + (n >> 3)) * 32 + (m & 31)) * 8 + (n & 7)] : h[(size_t)m * ld + n];
+  };
+  auto fail = [&](const char* why, int64_t m, int n) {
+    throw Error(PF_ERR_DEVICE, std::string(op) + ": " + what + " (" + std::to_string(M) + " x " + std::to_string(N) + ", ld " + std::to_string(ld) +
+                                   "): cell (" + std::to_string(m) + ", " + std::to_string(n) + ") " + why);
+  };
+  for (int64_t m = 0; m < rows; ++m)
+    for (int n = 0; n < ld; ++n) {
+      const bool is_sent = at(m, n) == sentinel;
+      if (m < M && n < N) { if (written && is_sent) fail("was not written", m, n); }
+      else if (n >= N) { if (!is_sent) fail("was written: a column beyond N", m, n); }
+      else if (m >= guard && !is_sent) fail("was written: a row at or beyond round_up(M, 256)", m, n);
+    }
+}
+}  // namespace
+
 // ------------------------------------------------------------------ stand-alone ops -------
 void Engine::op_lfr_cmvn_pad(const float* const* fbank, const int32_t* t80, int B, int sentinel, float* out,
                              int64_t cap, int32_t* tmax_out) {
@@ -354,11 +416,16 @@ void Engine::op_gemm_ex(const pf_gemm_desc& ds, const float* A, const float* W, 
     for (int m = 0; m < M; ++m)
       for (int k = 0; k < K; ++k)
         ablk[(((size_t)(m >> 5) * (Kp >> 3) + (k >> 3)) * 32 + (m & 31)) * 8 + (k & 7)] = (half_t)A[(size_t)m * K + k];
+    fill_hostile_blocked(ablk, M, Mp, K, Kp);
     PF_HIP(hipMemcpyAsync(base + oA16, ablk.data(), ablk.size() * 2, hipMemcpyHostToDevice, stream_));
   } else {
+    fill_hostile_rows(stream_, (half_t*)(base + oA16), Kp, M, Mp, K);
     PF_HIP(hipMemcpyAsync(base + oA, A, (size_t)M * K * 4, hipMemcpyHostToDevice, stream_));
     launch_f32_to_f16(stream_, (const float*)(base + oA), M, K, K, (half_t*)(base + oA16), Kp);
   }
+  fill_hostile_rows(stream_, (half_t*)(base + oW16), Kp, N, Np, K);
+  if (ds.out_kind == 0) fill_sentinel32(stream_, base + oC, (size_t)Mp * ld32);
+  else fill_sentinel16(stream_, base + oC, (size_t)Mp * (ds.out_kind == 2 ? N : ld16));
   PF_HIP(hipMemcpyAsync(base + oW, W, (size_t)N * K * 4, hipMemcpyHostToDevice, stream_));
   launch_f32_to_f16(stream_, (const float*)(base + oW), N, K, K, (half_t*)(base + oW16), Kp);
   if (ds.bias) PF_HIP(hipMemcpyAsync(base + ob, ds.bias, (size_t)N * 4, hipMemcpyHostToDevice, stream_));
@@ -389,6 +456,8 @@ void Engine::op_gemm_ex(const pf_gemm_desc& ds, const float* A, const float* W, 
     launch_gemm(stream_, g);
     prof_end(r == 0 ? "gemm_op" : "gemm_op_warm");
   }
+  if (ds.out_kind == 0) check_guard<uint32_t>(stream_, "gemm_ex", "the fp32 result", base + oC, kSentinel32, Mp, M, N, ld32, false);
+  else check_guard<uint16_t>(stream_, "gemm_ex", "the f16 result", base + oC, kSentinel16, Mp, M, N, ds.out_kind == 2 ? N : ld16, ds.out_kind == 2);
   if (ds.out_kind == 0) {
     PF_HIP(hipMemcpy2DAsync(C, (size_t)N * 4, base + oC, (size_t)ld32 * 4, (size_t)N * 4, M, hipMemcpyDeviceToHost, stream_));
     PF_HIP(hipStreamSynchronize(stream_));
@@ -432,8 +501,10 @@ void Engine::op_gemm_rc(const pf_gemm_rc_desc& ds, const float* A, const float* 
     for (int m = 0; m < M; ++m)
       for (int kk = 0; kk < K; ++kk)
         ablk[(((size_t)(m >> 5) * (K >> 3) + (kk >> 3)) * 32 + (m & 31)) * 8 + (kk & 7)] = (half_t)A[(size_t)m * K + kk];
+    fill_hostile_blocked(ablk, M, Mp, K, K);
     PF_HIP(hipMemcpyAsync(base + oA16, ablk.data(), ablk.size() * 2, hipMemcpyHostToDevice, stream_));
   } else {
+    fill_hostile_rows(stream_, (half_t*)(base + oA16), K, M, Mp, K);
     PF_HIP(hipMemcpyAsync(base + o32, A, (size_t)M * K * 4, hipMemcpyHostToDevice, stream_));
     launch_f32_to_f16(stream_, (const float*)(base + o32), M, K, K, (half_t*)(base + oA16), K);
     PF_HIP(hipStreamSynchronize(stream_));
@@ -448,17 +519,22 @@ void Engine::op_gemm_rc(const pf_gemm_rc_desc& ds, const float* A, const float* 
   if (ds.resid) { PF_HIP(hipMemcpyAsync(base + oR, ds.resid, (size_t)M * N * 4, hipMemcpyHostToDevice, stream_)); g.resid = (const float*)(base + oR); g.ldr = N; }
   std::vector<float> wT;
   if (ds.fsmn_v) {
-    // the V slice of a [M, 3*512] QKV buffer, as in the pipeline (row stride 1536 halves)
-    PF_HIP(hipMemsetAsync(base + oV, 0, (size_t)(Mp + 128) * 3 * N * 2, stream_));
+    // the V slice of a [M, 3*512] QKV buffer, as in the pipeline (row stride 1536 halves); the rows in front of it and
+    // behind it, and the Q | K columns, are hostile
+    fill_hostile_rows(stream_, (half_t*)(base + oV), 3 * N, 0, Mp + 128, 3 * N);
+    half_t* vs = (half_t*)(base + oV) + (size_t)kVLead * 3 * N + 2 * N;
     PF_HIP(hipMemcpyAsync(base + o32, ds.fsmn_v, (size_t)M * N * 4, hipMemcpyHostToDevice, stream_));
-    launch_f32_to_f16(stream_, (const float*)(base + o32), M, N, N, (half_t*)(base + oV) + 2 * N, 3 * N);
+    launch_f32_to_f16(stream_, (const float*)(base + o32), M, N, N, vs, 3 * N);
     wT.resize((size_t)k * N);
     for (int c = 0; c < N; ++c)
       for (int j = 0; j < k; ++j) wT[(size_t)j * N + c] = ds.fsmn_w[(size_t)c * k + j];
     PF_HIP(hipMemcpyAsync(base + owT, wT.data(), wT.size() * 4, hipMemcpyHostToDevice, stream_));
-    g.fsmn_v = (half_t*)(base + oV) + 2 * N; g.ldv = 3 * N; g.fsmn_wT = (const float*)(base + owT); g.fsmn_k = k;
+    g.fsmn_v = vs; g.ldv = 3 * N; g.fsmn_wT = (const float*)(base + owT); g.fsmn_k = k;
   }
   g.T = ds.T > 0 ? ds.T : M;
+  fill_sentinel32(stream_, base + oX, (size_t)Mp * N);
+  fill_sentinel16(stream_, base + oN16, (size_t)Mp * N);
+  fill_sentinel32(stream_, base + oN32, (size_t)Mp * N);
   if (ds.ln_gamma) {
     PF_HIP(hipMemcpyAsync(base + og, ds.ln_gamma, (size_t)N * 4, hipMemcpyHostToDevice, stream_));
     PF_HIP(hipMemcpyAsync(base + obe, ds.ln_beta, (size_t)N * 4, hipMemcpyHostToDevice, stream_));
@@ -478,18 +554,26 @@ void Engine::op_gemm_rc(const pf_gemm_rc_desc& ds, const float* A, const float* 
     if (need_x) { q.out_f32 = (float*)(base + oX); q.ldc32 = N; }
     if (K <= 576) {
       q.fsmn_v = g.fsmn_v; q.ldv = g.ldv; q.fsmn_wT = g.fsmn_wT; q.fsmn_k = g.fsmn_k; q.T = g.T;
+      prof_begin("gemm_op", 2.0 * M * (double)N * K);
       launch_gemm_small(stream_, q);
+      prof_end("gemm_op");
       if (g.ln_g) launch_layernorm(stream_, q.out_f32, M, N, g.ln_g, g.ln_b, g.out_n16, N, g.out_n32, N);
     } else {
       PF_CHECK(!g.fsmn_v, PF_ERR_INVALID_ARG, "gemm_rc: the split short-input form has no FSMN term");
       q.post_ln_g = g.ln_g; q.post_ln_b = g.ln_b; q.post_n16 = g.out_n16; q.ldn16 = N; q.post_n32 = g.out_n32; q.ldn32 = N;
+      prof_begin("gemm_op", 2.0 * M * (double)N * K);
       launch_gemm_small(stream_, q);
+      prof_end("gemm_op");
     }
+    if (q.out_f32) check_guard<uint32_t>(stream_, "gemm_rc", "x", base + oX, kSentinel32, Mp, M, N, N, false);
   } else {
     prof_begin("gemm_op", 2.0 * M * (double)N * K);
     launch_gemm_rc(stream_, g);
     prof_end("gemm_op");
+    if (g.out_x) check_guard<uint32_t>(stream_, "gemm_rc", "x", base + oX, kSentinel32, Mp, M, N, N, false);
   }
+  if (g.out_n16) check_guard<uint16_t>(stream_, "gemm_rc", "the f16 LayerNorm result", base + oN16, kSentinel16, Mp, M, N, N, false);
+  if (g.out_n32) check_guard<uint32_t>(stream_, "gemm_rc", "the fp32 LayerNorm result", base + oN32, kSentinel32, Mp, M, N, N, false);
   if (x_out) PF_HIP(hipMemcpyAsync(x_out, base + oX, (size_t)M * N * 4, hipMemcpyDeviceToHost, stream_));
   if (g.out_n32) PF_HIP(hipMemcpyAsync(n32_out, base + oN32, (size_t)M * N * 4, hipMemcpyDeviceToHost, stream_));
   std::vector<half_t> tmp;
@@ -522,6 +606,11 @@ void Engine::op_ffn(const float* x, const float* w1, const float* b1, const floa
     launch_f32_to_f16(stream_, (const float*)(base + o32), rows, cols, cols, (half_t*)(base + dst), cols);
     PF_HIP(hipStreamSynchronize(stream_));
   };
+  fill_hostile_rows(stream_, (half_t*)(base + ox16), D, M, Mp, D);
+  fill_hostile_rows(stream_, (half_t*)(base + ow1), D, F, Fp, D);
+  fill_hostile_rows(stream_, (half_t*)(base + ow2), F, D, Dp, F);
+  fill_sentinel16(stream_, base + oh, (size_t)Mp * F);
+  fill_sentinel32(stream_, base + oxr, (size_t)Mp * D);
   up16(x, M, D, ox16); up16(w1, F, D, ow1); up16(w2, D, F, ow2);
   PF_HIP(hipMemcpyAsync(base + ob1, b1, (size_t)F * 4, hipMemcpyHostToDevice, stream_));
   PF_HIP(hipMemcpyAsync(base + ob2, b2, (size_t)D * 4, hipMemcpyHostToDevice, stream_));
@@ -532,6 +621,8 @@ void Engine::op_ffn(const float* x, const float* w1, const float* b1, const floa
   float* xr = (float*)(base + oxr);
   gemm("gemm_ffn1", L1, (half_t*)(base + ox16), D, M, nullptr, 0, (half_t*)(base + oh), F, nullptr, 0, nullptr, 0, true, 0, 1.f, true, 1);
   gemm("gemm_ffn2", L2, (half_t*)(base + oh), F, M, xr, D, nullptr, 0, xr, D, nullptr, 0, false, 0, 1.f, true, 2);
+  check_guard<uint16_t>(stream_, "ffn", "the blocked hidden", base + oh, kSentinel16, Mp, M, F, F, true);
+  check_guard<uint32_t>(stream_, "ffn", "the result (in place on the residual)", xr, kSentinel32, Mp, M, D, D, false, false);
   PF_HIP(hipMemcpyAsync(y, xr, (size_t)M * D * 4, hipMemcpyDeviceToHost, stream_));
   PF_HIP(hipStreamSynchronize(stream_));
 }
@@ -629,6 +720,9 @@ void Engine::op_ffn_fused(const float* x, const float* w1, const float* b1, cons
     launch_f32_to_f16(stream_, (const float*)(base + o32), rows, cols, cols, (half_t*)(base + dst), ldo);
     PF_HIP(hipStreamSynchronize(stream_));
   };
+  fill_hostile_rows(stream_, (half_t*)(base + ox16), D, M, Mp, D);
+  fill_sentinel32(stream_, base + oxo, (size_t)Mp * D);
+  fill_sentinel16(stream_, base + on16, (size_t)Mp * D);
   up16(op ? op->ctx : x, M, D, ox16, D); up16(w1, F, D, ow1, D); up16(w2, D, F, ow2, F);
   PF_HIP(hipMemcpyAsync(base + ob1, b1, (size_t)F * 4, hipMemcpyHostToDevice, stream_));
   PF_HIP(hipMemcpyAsync(base + ob2, b2, (size_t)D * 4, hipMemcpyHostToDevice, stream_));
@@ -641,9 +735,10 @@ void Engine::op_ffn_fused(const float* x, const float* w1, const float* b1, cons
   if (op) {
     up16(op->wo, D, D, owo, D);
     launch_ffn_retile_out(stream_, (half_t*)(base + owo), D, (half_t*)(base + owot));
-    PF_HIP(hipMemsetAsync(base + ov, 0, (size_t)(Mp + 128) * 3 * D * 2, stream_));
+    fill_hostile_rows(stream_, (half_t*)(base + ov), 3 * D, 0, Mp + 128, 3 * D);      // as op_gemm_rc: hostile around the V slice
+    half_t* vs = (half_t*)(base + ov) + (size_t)kVLead * 3 * D + 2 * D;
     PF_HIP(hipMemcpyAsync(base + o32, op->v, (size_t)M * D * 4, hipMemcpyHostToDevice, stream_));
-    launch_f32_to_f16(stream_, (const float*)(base + o32), M, D, D, (half_t*)(base + ov) + 2 * D, 3 * D);
+    launch_f32_to_f16(stream_, (const float*)(base + o32), M, D, D, vs, 3 * D);
     PF_HIP(hipStreamSynchronize(stream_));
     wT.resize((size_t)11 * D);
     for (int c = 0; c < D; ++c)
@@ -653,7 +748,7 @@ void Engine::op_ffn_fused(const float* x, const float* w1, const float* b1, cons
     PF_HIP(hipMemcpyAsync(base + og2, op->ln2_gamma, (size_t)D * 4, hipMemcpyHostToDevice, stream_));
     PF_HIP(hipMemcpyAsync(base + obe2, op->ln2_beta, (size_t)D * 4, hipMemcpyHostToDevice, stream_));
     f.ctx = (half_t*)(base + ox16); f.lda_c = D; f.Wot = (half_t*)(base + owot); f.bo = (const float*)(base + obo);
-    f.fsmn_v = (half_t*)(base + ov) + 2 * D; f.ldv = 3 * D; f.fsmn_wT = (const float*)(base + owT); f.T = op->T > 0 ? op->T : M;
+    f.fsmn_v = vs; f.ldv = 3 * D; f.fsmn_wT = (const float*)(base + owT); f.T = op->T > 0 ? op->T : M;
     f.ln2_g = (const float*)(base + og2); f.ln2_b = (const float*)(base + obe2);
     f.A = nullptr;
   }
@@ -681,6 +776,8 @@ void Engine::op_ffn_fused(const float* x, const float* w1, const float* b1, cons
     launch_ffn_fused(stream_, f);
     prof_end(r == 0 ? "gemm_op" : "gemm_op_warm");
   }
+  if (f.out_x) check_guard<uint32_t>(stream_, "ffn_fused", "x", base + oxo, kSentinel32, Mp, M, D, D, false);
+  if (f.out_n16) check_guard<uint16_t>(stream_, "ffn_fused", "the f16 LayerNorm result", base + on16, kSentinel16, Mp, M, D, D, false);
   if (x_out) PF_HIP(hipMemcpyAsync(x_out, base + oxo, (size_t)M * D * 4, hipMemcpyDeviceToHost, stream_));
   std::vector<half_t> n16;
   if (f.out_n16) {
@@ -1043,6 +1140,9 @@ void Engine::op_qkv_attention(const float* x, const float* w, const float* bias,
   char* base = (char*)ws_tmp_.p;
   PF_HIP(hipMemsetAsync(base + oA, 0, (size_t)Mp * Kpad * 2, stream_));
   PF_HIP(hipMemsetAsync(base + oW, 0, (size_t)N * Kpad * 2, stream_));
+  fill_hostile_rows(stream_, (half_t*)(base + oA), Kpad, M, Mp, K);
+  fill_sentinel16(stream_, base + oqk, (size_t)Mp * 2 * D);
+  fill_sentinel16(stream_, base + ov, (size_t)Mp * D);
   PF_HIP(hipMemcpyAsync(base + o32, x, (size_t)M * K * 4, hipMemcpyHostToDevice, stream_));
   launch_f32_to_f16(stream_, (const float*)(base + o32), M, K, K, (half_t*)(base + oA), Kpad);
   PF_HIP(hipStreamSynchronize(stream_));
@@ -1056,6 +1156,8 @@ void Engine::op_qkv_attention(const float* x, const float* w, const float* bias,
   prof_begin("gemm_op", 2.0 * M * (double)N * K);
   launch_gemm_qkvp(stream_, (half_t*)(base + oA), Kpad, (half_t*)(base + oWp), Kpad, (const float*)(base + obp), M, Kpad, qscale, qk, vb, D);
   prof_end("gemm_op");
+  check_guard<uint16_t>(stream_, "qkv_attention", "the blocked Q | K", qk, kSentinel16, Mp, M, 2 * D, 2 * D, true);
+  check_guard<uint16_t>(stream_, "qkv_attention", "V", vb, kSentinel16, Mp, M, D, D, false);
   AttnArgs a{};
   a.q = qk; a.k = qk; a.qk_blocked = 1; a.blk_groups = 2 * D / 8; a.blk_brows = T; a.blk_kgrp = D / 8;
   a.v = vb; a.v_bstride = (int64_t)T * D; a.v_rstride = D;

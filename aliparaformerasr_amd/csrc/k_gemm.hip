@@ -512,6 +512,12 @@ __device__ __forceinline__ void gemm_pp3_impl(const GemmDev& p) {
   int ep_tile = slot;
   auto tile_end = [&]() __attribute__((always_inline)) {
     flush();                                          // only non-empty when nk < 8
+    // The bias line (int8: the three column lines) read below was requested by LDS-DMA at the previous tile end.  The counted
+    // waits of the k-steps in between retire that request only from the third step on (group B's wait of the first step
+    // sits in front of the step's own pieces, and in the second step the store term still counts stores older than the
+    // request), so with one or two k-steps per tile nothing but latency would order its arrival against the read: drain.
+    // Uniform per launch and never taken at the pipeline's depths (three k-steps or more).
+    if (fast0 && nk < 3) wait_vmcnt<0>();
     const int tile = ep_tile;
     ep_tile += G;
     const int tm = tile / p.tiles_n, tn = tile - tm * p.tiles_n;

@@ -27,6 +27,7 @@
 //     the fp32 rows double the brick's bytes and the 48 row reductions sit in front of the first MFMA.  Removed.)
 //   * The encoder's FSMN memory (11 taps over V, channel-local) is an epilogue term of the attention out-projection:
 //     a lane adds sum_j w_j[n] * V[t + j - 5, n] + V[t, n] for its own row and 16 columns.
+#include <cstdio>
 #include "kernels.h"
 #include "kdev.h"
 
@@ -324,7 +325,11 @@ static void small_launch(hipStream_t s, const SmallDev& d, int rows_alloc) {
     set_max_lds((const void*)gemm_small_kernel<CPR>, 160 * 1024);
   });
   const int lds = (rows_alloc + SM_BN) * CPR * 16;
-  note_gemm_kernel("gemm_small_kernel");
+  // the instance and the form: "gemm_small_kernel<CPR>, 128-row bricks" | "..., 96-row bricks" | "..., split S + small_reduce_kernel"
+  static thread_local char name[96];
+  if (d.S > 1) snprintf(name, sizeof(name), "gemm_small_kernel<%d>, split %d + small_reduce_kernel", CPR, d.S);
+  else snprintf(name, sizeof(name), "gemm_small_kernel<%d>, %d-row bricks", CPR, d.bm);
+  note_gemm_kernel(name);
   hipLaunchKernelGGL((gemm_small_kernel<CPR>), dim3((unsigned)(d.tiles_n * d.tiles_m * d.S)), dim3(256), lds, s, d);
   PF_HIP(hipGetLastError());
 }
