@@ -50,6 +50,16 @@ class PfPcmDesc(C.Structure):
                 ("flags", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
+class PfVadConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("struct_size", "floor_pct", "margin_q", "abs_level", "window", "on_count", "off_count",
+                                         "pad_begin", "pad_end", "min_speech", "max_len", "split_search")] + \
+               [("reserved", C.c_int32 * 4)]
+
+
+PF_VAD_MAX_SEGMENTS = 65536
+PF_VAD_MAX_FRAMES = 1 << 22
+
+
 class PfAttnDesc(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("kind", C.c_int32), ("layout", C.c_int32), ("shared_kv", C.c_int32),
                 ("o_ld", C.c_int32), ("form", C.c_int32), ("ldkv", C.c_int32), ("kv_off", C.c_int32)]
@@ -144,6 +154,13 @@ SIGNATURES = {
     "pf_stage_pcm": (C.c_int, [_vp, _P(_vp), _i64, _P(PfPcmDesc), C.c_int32, C.c_int32]),
     "pf_recognize_pcm": (C.c_int, [_vp, _P(_vp), _i64, _P(PfPcmDesc), C.c_int32, C.c_int32, _i32, C.c_int32, _P(PfBatchOut)]),
     "pf_op_pcm_convert": (C.c_int, [_vp, _vp, C.c_int64, _P(PfPcmDesc), _f, C.c_int64, _i64]),
+    "pf_vad_default": (C.c_int, [_P(PfVadConfig)]),
+    "pf_vad_segment": (C.c_int, [_vp, _P(_f), _i64, C.c_int32, _P(PfVadConfig), _i32, C.c_int32, _i32]),
+    "pf_host_vad_levels": (C.c_int, [_f, C.c_int64, C.c_int32, _i32]),
+    "pf_host_vad_segments": (C.c_int, [_i32, C.c_int32, C.c_int32, C.c_int32, _P(PfVadConfig), _i32, C.c_int32, _i32]),
+    "pf_host_long_plan": (C.c_int, [_i32, C.c_int32, C.c_int32, C.c_int64, _i32, _i32, _i32]),
+    "pf_op_vad_levels": (C.c_int, [_vp, _f, C.c_int64, C.c_int32, _i32]),
+    "pf_op_vad_segments": (C.c_int, [_vp, _i32, _i32, C.c_int32, C.c_int32, C.c_int32, _P(PfVadConfig), _i32, C.c_int32, _i32]),
     "pf_stream_add_pcm": (C.c_int, [_vp, _vp, C.c_int64, _P(PfPcmDesc)]),
     "pf_host_wav_info": (C.c_int, [C.c_char_p, _P(PfPcmDesc), _i64, _i64, C.POINTER(C.c_double)]),
     "pf_engine_set_hotwords": (C.c_int, [_vp, C.POINTER(C.c_int32), C.c_int32]),
@@ -185,6 +202,9 @@ SIGNATURES = {
     "pf_op_ctc_beam_hot": (C.c_int, [_vp, _f, _i64, _f, _i32, _i32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                      _i64, _i32, _P(C.c_double), C.c_int32, _i32, _i32, _i32, C.c_int32, C.c_float, _i32,
                                      _P(C.c_double)]),
+    "pf_recognizer_set_vad": (C.c_int, [_vp, _P(PfVadConfig), C.c_int32, C.c_int64, C.c_char_p]),
+    "pf_stream_num_segments": (C.c_int, [_vp, _i32]),
+    "pf_stream_segment": (C.c_int, [_vp, C.c_int32, _i32, _i32, _i32, _i32, _i32, _i32, _cpp]),
     "pf_recognizer_set_hotword_boost": (C.c_int, [_vp, C.c_float]),
     "pf_stream_alternative_hot": (C.c_int, [_vp, C.c_int32, _i32, _P(C.c_double)]),
     "pf_engine_set_align_targets": (C.c_int, [_vp, _i64, _i32, C.c_int32, C.c_int32]),

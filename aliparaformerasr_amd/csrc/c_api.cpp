@@ -692,6 +692,83 @@ int pf_op_pcm_convert(pf_engine* h, const void* data, int64_t n_values, const pf
   PF_CATCH
 }
 
+// ---- voice-activity segmentation ----
+int pf_vad_default(pf_vad_config* cfg) {
+  PF_TRY
+  NEED(cfg);
+  *cfg = vad_default();
+  return PF_OK;
+  PF_CATCH
+}
+int pf_host_vad_levels(const float* rows, int64_t T, int32_t n_mels, int32_t* out) {
+  PF_TRY
+  PF_CHECK(T >= 0 && n_mels >= 1 && n_mels <= 1024, PF_ERR_INVALID_ARG, "vad_levels: bad shape (n_mels 1 .. 1024)");
+  if (T > 0) { NEED(rows); NEED(out); }
+  host_vad_levels(rows, T, n_mels, out);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_host_vad_segments(const int32_t* levels, int32_t T, int32_t n_mels, int32_t lfr_n, const pf_vad_config* cfg, int32_t* seg,
+                         int32_t cap, int32_t* n) {
+  PF_TRY
+  NEED(n);
+  PF_CHECK(T >= 0 && n_mels >= 1 && n_mels <= 1024 && cap >= 0 && lfr_n >= 1, PF_ERR_INVALID_ARG, "vad_segments: bad shape");
+  if (T > 0) NEED(levels);
+  const pf_vad_config c = vad_check(cfg, lfr_n);
+  const std::vector<int32_t> s = host_vad_segments(levels, T, n_mels, c);
+  *n = (int32_t)(s.size() / 2);
+  PF_CHECK(*n <= cap, PF_ERR_CAPACITY, "vad: capacity " + std::to_string(cap) + " < " + std::to_string(*n) + " segments");
+  if (*n > 0) { NEED(seg); std::memcpy(seg, s.data(), s.size() * 4); }
+  return PF_OK;
+  PF_CATCH
+}
+int pf_host_long_plan(const int32_t* len, int32_t n, int32_t batch_max, int64_t frame_budget, int32_t* batch, int32_t* row,
+                      int32_t* n_batches) {
+  PF_TRY
+  PF_CHECK(n >= 0, PF_ERR_INVALID_ARG, "long_plan: negative count");
+  if (n > 0) { NEED(len); NEED(batch); NEED(row); }
+  for (int i = 0; i < n; ++i) PF_CHECK(len[i] >= 0, PF_ERR_INVALID_ARG, "long_plan: negative length");
+  const int nb = host_long_plan(len, n, batch_max, frame_budget, batch, row);
+  if (n_batches) *n_batches = nb;
+  return PF_OK;
+  PF_CATCH
+}
+int pf_vad_segment(pf_engine* h, const float* const* samples, const int64_t* n_samples, int32_t B, const pf_vad_config* cfg,
+                   int32_t* seg, int32_t cap, int32_t* n_seg) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  PF_CHECK(B >= 0 && cap >= 0, PF_ERR_INVALID_ARG, "vad_segment: negative batch or capacity");
+  if (B > 0) { NEED(samples); NEED(n_samples); NEED(n_seg); if (cap > 0) NEED(seg); }
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->vad_segment(samples, n_samples, B, cfg, seg, cap, n_seg);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_op_vad_levels(pf_engine* h, const float* rows, int64_t T, int32_t n_mels, int32_t* out) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  PF_CHECK(T >= 0 && n_mels >= 1 && n_mels <= 1024, PF_ERR_INVALID_ARG, "vad_levels: bad shape (n_mels 1 .. 1024)");
+  if (T > 0) { NEED(rows); NEED(out); }
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->op_vad_levels(rows, T, n_mels, out);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_op_vad_segments(pf_engine* h, const int32_t* levels, const int32_t* T, int32_t B, int32_t ld, int32_t n_mels,
+                       const pf_vad_config* cfg, int32_t* seg, int32_t cap, int32_t* n) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  PF_CHECK(B >= 0 && ld >= 0 && cap >= 0 && n_mels >= 1 && n_mels <= 1024, PF_ERR_INVALID_ARG, "vad_segments: bad shape");
+  if (B > 0) { NEED(T); NEED(n); if (ld > 0) NEED(levels); if (cap > 0) NEED(seg); }
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->op_vad_segments(levels, T, B, ld, n_mels, cfg, seg, cap, n);
+  return PF_OK;
+  PF_CATCH
+}
+
 int pf_op_topk(pf_engine* h, const float* x, int64_t rows, int32_t V, int32_t ld, int32_t K, int64_t* ids, float* val,
                int32_t* n) {
   PF_TRY
@@ -1319,6 +1396,39 @@ int pf_recognizer_set_align(pf_recognizer* h, int32_t on) {
   std::shared_ptr<Recognizer> r = R(h);
   PF_CHECK(!r->disposed(), PF_ERR_DISPOSED, "OfflineRecognizer");
   r->SetAlign(on != 0);
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_recognizer_set_vad(pf_recognizer* h, const pf_vad_config* cfg, int32_t batch_max, int64_t frame_budget, const char* sep_utf8) {
+  PF_TRY
+  std::shared_ptr<Recognizer> r = R(h);
+  PF_CHECK(!r->disposed(), PF_ERR_DISPOSED, "OfflineRecognizer");
+  r->SetVad(cfg, batch_max, frame_budget, sep_utf8);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_stream_num_segments(pf_stream* h, int32_t* n) {
+  PF_TRY
+  Stream* s = S(h);
+  NEED(n);
+  *n = (int32_t)s->Segments.size();
+  return PF_OK;
+  PF_CATCH
+}
+int pf_stream_segment(pf_stream* h, int32_t i, int32_t* begin_ms, int32_t* end_ms, int32_t* batch, int32_t* row, int32_t* tok_begin,
+                      int32_t* tok_end, const char** text_utf8) {
+  PF_TRY
+  Stream* s = S(h);
+  PF_CHECK(i >= 0 && (size_t)i < s->Segments.size(), PF_ERR_INVALID_ARG, "segment index out of range");
+  const Stream::Segment& g = s->Segments[(size_t)i];
+  if (begin_ms) *begin_ms = g.begin_ms;
+  if (end_ms) *end_ms = g.end_ms;
+  if (batch) *batch = g.batch;
+  if (row) *row = g.row;
+  if (tok_begin) *tok_begin = g.tok_begin;
+  if (tok_end) *tok_end = g.tok_end;
+  if (text_utf8) *text_utf8 = g.text.c_str();
   return PF_OK;
   PF_CATCH
 }

@@ -203,6 +203,16 @@ class Engine {
   void op_ctc_align(const float* lp, int B, int T, int V, int ld, const int32_t* tgt, const int32_t* tlen, const int32_t* lens, int H,
                     int cap, float* path_score, double* loglik, int32_t* ok, int32_t* first, int32_t* last, float* tok_score);
   void op_pcm_convert(const void* data, int64_t n_values, const pf_pcm_desc& desc, float* out, int64_t cap, int64_t* n_out);
+  // voice-activity segmentation (k_vad.hip): stage_audio, run_staged's one fbank launch, then the two detector launches (profile
+  // class "vad") over all B utterances; only n [B] and the segment lists come back.  seg [B, cap, 2].
+  void vad_segment(const float* const* samples, const int64_t* n, int B, const pf_vad_config* cfg, int32_t* seg, int cap, int32_t* n_seg);
+  // the same over audio that is already on the device (stage_device_audio: the recognizer's resident streams)
+  void vad_segment_device(const float* const* samples_dev, const int64_t* n, int B, const pf_vad_config* cfg, int32_t* seg, int cap,
+                          int32_t* n_seg);
+  void vad_staged(const pf_vad_config* cfg, int32_t* seg, int cap, int32_t* n_seg);
+  void op_vad_levels(const float* rows, int64_t T, int n_mels, int32_t* out);
+  void op_vad_segments(const int32_t* levels, const int32_t* T, int B, int ld, int n_mels, const pf_vad_config* cfg, int32_t* seg,
+                       int cap, int32_t* n);
   void op_ctc_collapse(const int64_t* ids, const float* scores, const int32_t* lens, int B, int T, int blank, int64_t* ids_out,
                        int32_t* first_out, int32_t* last_out, float* score_out, int cap, int32_t* n_out);
   // ---- streaming seams (OnlineRecognizer.cs EncoderProj / DecoderProj) ------

@@ -144,6 +144,120 @@ void Engine::op_pcm_convert(const void* data, int64_t n_values, const pf_pcm_des
   PF_HIP(hipStreamSynchronize(stream_));
 }
 
+// ---- voice-activity segmentation (k_vad.hip).  ws_tmp_: levels | seg [B, cap, 2] | n [B] | T [B] | off [B]
+namespace {
+VadParams vad_params(const pf_vad_config& c, int n_mels) {
+  // a run is never longer than PF_VAD_MAX_FRAMES: a larger max_len means the same and keeps b + max_len inside int32
+  return VadParams{c.floor_pct, c.margin_q, c.abs_level, c.window, c.on_count, c.off_count, c.pad_begin, c.pad_end, c.min_speech,
+                   std::min(c.max_len, 2 * PF_VAD_MAX_FRAMES), c.split_search, n_mels};
+}
+struct VadLayout {
+  Field<int32_t> lev, seg, n, T; Field<int64_t> off;
+  size_t bytes;
+  VadLayout(size_t frames, size_t B, size_t cap) {
+    Cursor c;
+    lev = c.take<int32_t>(frames); seg = c.take<int32_t>(B * cap * 2); n = c.take<int32_t>(B); T = c.take<int32_t>(B);
+    off = c.take<int64_t>(B);
+    bytes = c.off;
+  }
+};
+// n [B] first, then the lists of the rows that have one: min(n[b], cap) pairs each
+void vad_read_back(hipStream_t s, const void* ws, const VadLayout& L, int B, int cap, int dev_cap, int32_t* seg, int32_t* n) {
+  PF_HIP(hipMemcpyAsync(n, L.n(ws), (size_t)B * 4, hipMemcpyDeviceToHost, s));
+  PF_HIP(hipStreamSynchronize(s));
+  int worst = 0;
+  for (int b = 0; b < B; ++b) {
+    const int k = std::min(n[b], std::min(cap, dev_cap));
+    if (k > 0) PF_HIP(hipMemcpyAsync(seg + (size_t)b * cap * 2, L.seg(ws) + (size_t)b * dev_cap * 2, (size_t)k * 8, hipMemcpyDeviceToHost, s));
+    worst = std::max(worst, n[b]);
+  }
+  PF_HIP(hipStreamSynchronize(s));
+  PF_CHECK(worst <= PF_VAD_MAX_SEGMENTS, PF_ERR_CAPACITY, "vad: more than PF_VAD_MAX_SEGMENTS segments");
+  PF_CHECK(worst <= cap, PF_ERR_CAPACITY, "vad: capacity " + std::to_string(cap) + " < " + std::to_string(worst) + " segments");
+}
+}  // namespace
+
+void Engine::op_vad_levels(const float* rows, int64_t T, int n_mels, int32_t* out) {
+  PF_HIP(hipSetDevice(device_));
+  if (T == 0) return;
+  Cursor c;
+  const Field<float> d_x = c.take<float>((size_t)T * n_mels + 4);
+  c.off = (size_t)round_up((int64_t)c.off, 16);
+  const Field<int32_t> d_e = c.take<int32_t>((size_t)T);
+  ensure(ws_tmp_, c.off);
+  void* ws = ws_tmp_.p;
+  PF_HIP(hipMemcpyAsync(d_x(ws), rows, (size_t)T * n_mels * 4, hipMemcpyHostToDevice, stream_));
+  launch_vad_levels(stream_, d_x(ws), T, n_mels, d_e(ws));
+  PF_HIP(hipMemcpyAsync(out, d_e(ws), (size_t)T * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipStreamSynchronize(stream_));
+}
+
+void Engine::op_vad_segments(const int32_t* levels, const int32_t* T, int B, int ld, int n_mels, const pf_vad_config* cfg, int32_t* seg,
+                             int cap, int32_t* n) {
+  const pf_vad_config c = vad_check(cfg, fc_.lfr_n);
+  for (int b = 0; b < B; ++b) {
+    PF_CHECK(T[b] >= 0 && T[b] <= ld, PF_ERR_INVALID_ARG, "vad_segments: T[b] outside 0 .. ld");
+    PF_CHECK(T[b] <= PF_VAD_MAX_FRAMES, PF_ERR_CAPACITY, "vad: more than PF_VAD_MAX_FRAMES frames");
+  }
+  PF_HIP(hipSetDevice(device_));
+  if (B == 0) return;
+  const int dev_cap = std::max(std::min(cap, PF_VAD_MAX_SEGMENTS), 1);
+  const VadLayout L((size_t)B * ld, B, dev_cap);
+  ensure(ws_tmp_, L.bytes);
+  void* ws = ws_tmp_.p;
+  std::vector<int64_t> off((size_t)B);
+  for (int b = 0; b < B; ++b) off[b] = (int64_t)b * ld;
+  if ((int64_t)B * ld > 0) PF_HIP(hipMemcpyAsync(L.lev(ws), levels, (size_t)B * ld * 4, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipMemcpyAsync(L.T(ws), T, (size_t)B * 4, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipMemcpyAsync(L.off(ws), off.data(), (size_t)B * 8, hipMemcpyHostToDevice, stream_));
+  launch_vad_segments(stream_, L.lev(ws), L.off(ws), L.T(ws), B, vad_params(c, n_mels), L.seg(ws), dev_cap, L.n(ws));
+  vad_read_back(stream_, ws, L, B, cap, dev_cap, seg, n);         // (waits for the stream: `off` is read by its copy until then)
+}
+
+void Engine::vad_segment(const float* const* samples, const int64_t* n, int B, const pf_vad_config* cfg, int32_t* seg, int cap,
+                         int32_t* n_seg) {
+  vad_check(cfg, fc_.lfr_n);
+  PF_CHECK(!fc_.snip_edges, PF_ERR_UNSUPPORTED, "vad: snip_edges = true is not supported");
+  stage_audio(samples, n, B);
+  vad_staged(cfg, seg, cap, n_seg);
+}
+
+void Engine::vad_segment_device(const float* const* samples_dev, const int64_t* n, int B, const pf_vad_config* cfg, int32_t* seg, int cap,
+                                int32_t* n_seg) {
+  vad_check(cfg, fc_.lfr_n);
+  PF_CHECK(!fc_.snip_edges, PF_ERR_UNSUPPORTED, "vad: snip_edges = true is not supported");
+  stage_device_audio(samples_dev, n, B);
+  vad_staged(cfg, seg, cap, n_seg);
+}
+
+// the staged utterances (host or device audio): run_staged's fbank launch, the detector, the lists back
+void Engine::vad_staged(const pf_vad_config* cfg, int32_t* seg, int cap, int32_t* n_seg) {
+  const pf_vad_config c = vad_check(cfg, fc_.lfr_n);
+  const int B = st_B_;
+  if (B == 0) return;
+  for (int b = 0; b < B; ++b) PF_CHECK(st_t80_[b] <= PF_VAD_MAX_FRAMES, PF_ERR_CAPACITY, "vad: more than PF_VAD_MAX_FRAMES frames");
+  const int64_t* meta = (const int64_t*)ws_meta_.p;
+  const int32_t* t80d = (const int32_t*)((const char*)ws_meta_.p + 3 * (size_t)(B + 1) * 8);
+  const int dev_cap = std::max(std::min(cap, PF_VAD_MAX_SEGMENTS), 1);
+  const VadLayout L((size_t)st_total_frames_, B, dev_cap);
+  ensure(ws_tmp_, L.bytes);
+  void* ws = ws_tmp_.p;
+  if (st_total_frames_ > 0) {
+    ensure(ws_fbank_, (size_t)st_total_frames_ * fc_.n_mels * 4);
+    prof_begin("fbank", 0);
+    launch_fbank(stream_, fb_, st_audio_ext_ ? st_audio_ext_ : (const float*)ws_audio_.p, meta, meta + (B + 1), meta + 2 * (B + 1), B,
+                 st_total_frames_, 0, (float*)ws_fbank_.p, fc_.dither, next_dither_seed());
+    prof_end("fbank");
+  }
+  prof_begin("vad", 0);
+  launch_vad_levels(stream_, (const float*)ws_fbank_.p, st_total_frames_, fc_.n_mels, L.lev(ws));
+  prof_end("vad");
+  prof_begin("vad", 0);
+  launch_vad_segments(stream_, L.lev(ws), meta + 2 * (B + 1), t80d, B, vad_params(c, fc_.n_mels), L.seg(ws), dev_cap, L.n(ws));
+  prof_end("vad");
+  vad_read_back(stream_, ws, L, B, cap, dev_cap, seg, n_seg);
+}
+
 // the five decoders on caller data; ws_tmp_: the result block of decode_blocks.h, then the uploaded inputs and the scratch
 void Engine::op_topk(const float* x, int64_t rows, int V, int ld, int K, int64_t* ids, float* val, int32_t* n) {
   PF_HIP(hipSetDevice(device_));

@@ -835,4 +835,117 @@ int host_ctc_align(const float* lp, int64_t ld, int T, int V, const int64_t* y, 
   return 1;
 }
 
+
+// ---- voice-activity segmentation (paraformer_hip.h "Voice-activity segmentation"; tests/vad_ref.py) --------------------------
+pf_vad_config vad_default() {
+  pf_vad_config c{};
+  c.struct_size = (int32_t)sizeof(pf_vad_config);
+  c.floor_pct = 10; c.margin_q = 96; c.abs_level = INT32_MIN;
+  c.window = 20; c.on_count = 15; c.off_count = 15;
+  c.pad_begin = 30; c.pad_end = 5;
+  c.min_speech = 50; c.max_len = 3000; c.split_search = 500;
+  return c;
+}
+
+pf_vad_config vad_check(const pf_vad_config* cfg, int lfr_n) {
+  if (!cfg) return vad_default();
+  const pf_vad_config c = *cfg;
+  PF_CHECK(c.struct_size == (int32_t)sizeof(pf_vad_config), PF_ERR_INVALID_ARG, "pf_vad_config.struct_size mismatch");
+  PF_CHECK(c.floor_pct >= -1 && c.floor_pct <= 100, PF_ERR_INVALID_ARG, "vad: floor_pct outside -1 .. 100");
+  PF_CHECK(c.window >= 1 && c.window <= 256, PF_ERR_INVALID_ARG, "vad: window outside 1 .. 256");
+  PF_CHECK(c.on_count >= 1 && c.on_count <= c.window && c.off_count >= 1 && c.off_count <= c.window, PF_ERR_INVALID_ARG,
+           "vad: on_count / off_count outside 1 .. window");
+  PF_CHECK(c.on_count + c.off_count > c.window, PF_ERR_INVALID_ARG, "vad: on_count + off_count must exceed window");
+  PF_CHECK(c.pad_begin >= 0 && c.pad_begin <= 1024 && c.pad_end >= 0 && c.pad_end <= 1024, PF_ERR_INVALID_ARG,
+           "vad: pad_begin / pad_end outside 0 .. 1024");
+  PF_CHECK((int64_t)c.min_speech >= 2 * (int64_t)std::max(lfr_n, 1), PF_ERR_INVALID_ARG, "vad: min_speech below 2 * lfr_n");
+  PF_CHECK(c.split_search >= 0 && c.split_search <= 1024, PF_ERR_INVALID_ARG, "vad: split_search outside 0 .. 1024");
+  PF_CHECK(2 * (int64_t)c.min_speech + c.split_search <= (int64_t)c.max_len, PF_ERR_INVALID_ARG,
+           "vad: 2 * min_speech + split_search must not exceed max_len");
+  return c;
+}
+
+void host_vad_levels(const float* rows, int64_t T, int n_mels, int32_t* out) {
+  for (int64_t t = 0; t < T; ++t) {
+    int32_t e = 0;
+    for (int m = 0; m < n_mels; ++m) {
+      float v = rows[t * n_mels + m];
+      if (!(v > -64.f)) v = -64.f;
+      if (v > 64.f) v = 64.f;
+      e += (int32_t)rintf(v * 64.f);
+    }
+    out[t] = e;
+  }
+}
+
+std::vector<int32_t> host_vad_segments(const int32_t* lev, int T, int n_mels, const pf_vad_config& c) {
+  std::vector<int32_t> seg;
+  PF_CHECK(T >= 0, PF_ERR_INVALID_ARG, "vad: negative frame count");
+  PF_CHECK(T <= PF_VAD_MAX_FRAMES, PF_ERR_CAPACITY, "vad: more than PF_VAD_MAX_FRAMES frames");
+  if (T == 0) return seg;
+  // 2 threshold
+  int64_t thr = c.abs_level;
+  if (c.floor_pct >= 0) {
+    const int64_t k = std::min<int64_t>(T - 1, (int64_t)T * c.floor_pct / 100);
+    std::vector<int32_t> s(lev, lev + T);
+    std::nth_element(s.begin(), s.begin() + k, s.end());
+    thr = std::max<int64_t>((int64_t)s[(size_t)k] + (int64_t)c.margin_q * n_mels, c.abs_level);
+  }
+  // 3 window and hysteresis, 4 padding: d[t] through a difference array over the padded frames of every state-1 frame
+  std::vector<int32_t> pre((size_t)T + 1, 0), cover((size_t)T + 1, 0);
+  for (int t = 0; t < T; ++t) pre[t + 1] = pre[t] + ((int64_t)lev[t] > thr ? 1 : 0);
+  int state = 0;
+  for (int t = 0; t < T; ++t) {
+    const int w = std::min(c.window, t + 1), cnt = pre[t + 1] - pre[t + 1 - w];
+    if (cnt >= c.on_count) state = 1;
+    else if (w - cnt >= c.off_count) state = 0;
+    if (state) { ++cover[std::max(t - c.pad_begin, 0)]; --cover[std::min(t + c.pad_end + 1, T)]; }
+  }
+  const int64_t max_len = c.max_len;
+  auto emit = [&](int64_t b, int64_t e) {
+    PF_CHECK(seg.size() / 2 < (size_t)PF_VAD_MAX_SEGMENTS, PF_ERR_CAPACITY, "vad: more than PF_VAD_MAX_SEGMENTS segments");
+    seg.push_back((int32_t)b); seg.push_back((int32_t)e);
+  };
+  int depth = 0, b0 = -1;
+  for (int t = 0; t <= T; ++t) {
+    depth += t < T ? cover[t] : 0;
+    const bool d = t < T && depth > 0;
+    if (d && b0 < 0) b0 = t;
+    if (!d && b0 >= 0) {
+      int64_t b = b0, e = t;
+      b0 = -1;
+      if (e - b < c.min_speech) continue;
+      // 5 split
+      while (e - b > max_len) {
+        const int64_t hi = std::min(b + max_len, e - c.min_speech), lo = hi - c.split_search;
+        int64_t cut = lo;
+        for (int64_t x = lo; x <= hi; ++x) if (lev[x] <= lev[cut]) cut = x;
+        emit(b, cut);
+        b = cut;
+      }
+      emit(b, e);
+    }
+  }
+  return seg;
+}
+
+int host_long_plan(const int32_t* len, int n, int batch_max, int64_t frame_budget, int32_t* batch, int32_t* row) {
+  if (batch_max <= 0) batch_max = 32;
+  if (frame_budget <= 0) frame_budget = 96000;
+  std::vector<int32_t> order((size_t)n);
+  for (int i = 0; i < n; ++i) order[i] = i;
+  std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return len[a] > len[b]; });
+  int nb = 0;
+  for (int i = 0; i < n;) {
+    const int64_t L = len[order[i]];
+    int rows = 0;
+    do {
+      batch[order[i]] = nb; row[order[i]] = rows;
+      ++rows; ++i;
+    } while (i < n && rows < batch_max && (int64_t)(rows + 1) * L <= frame_budget);
+    ++nb;
+  }
+  return nb;
+}
+
 }  // namespace pf

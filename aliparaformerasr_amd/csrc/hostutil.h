@@ -112,6 +112,17 @@ int host_ctc_beam_hot(const float* blank_lp, int64_t blank_stride, const int64_t
 int host_ctc_align(const float* lp, int64_t ld, int T, int V, const int64_t* y, int U, float* path_score, double* loglik,
                    int32_t* first, int32_t* last, float* tok_score);
 
+// ---- voice-activity segmentation (paraformer_hip.h "Voice-activity segmentation"; the definition is tests/vad_ref.py) ----
+// The host twins of k_vad.hip.  vad_default: the stated defaults.  vad_check: cfg (null = the defaults) validated against the
+// constraints of the header (PF_ERR_INVALID_ARG), returned by value.
+pf_vad_config vad_default();
+pf_vad_config vad_check(const pf_vad_config* cfg, int lfr_n);
+void host_vad_levels(const float* rows, int64_t T, int n_mels, int32_t* out);
+// steps 2-6 over ONE utterance's levels: all segments in order (PF_ERR_CAPACITY above PF_VAD_MAX_FRAMES / PF_VAD_MAX_SEGMENTS)
+std::vector<int32_t> host_vad_segments(const int32_t* levels, int T, int n_mels, const pf_vad_config& c);
+// the batch plan of long-audio recognition: batch / row per segment; returns the number of batches
+int host_long_plan(const int32_t* len, int n, int batch_max, int64_t frame_budget, int32_t* batch, int32_t* row);
+
 // UTF-8 <-> code points
 std::vector<uint32_t> utf8_decode(const std::string& s);
 std::string utf8_encode(uint32_t cp);

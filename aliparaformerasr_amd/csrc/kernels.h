@@ -401,4 +401,15 @@ void launch_pcm_to_samples(hipStream_t s, const PcmJob* jobs_dev, int B, int64_t
 // the same kernel for ONE utterance, its job passed in the kernel arguments (no table in device memory)
 void launch_pcm_to_samples_one(hipStream_t s, const PcmJob& job, const void* raw, float* samples);
 
+// ---------------------------------------------------------------- voice-activity segmentation (k_vad.hip) ------
+// The detector of paraformer_hip.h "Voice-activity segmentation"; the definition in numpy is tests/vad_ref.py.
+// Step 1: rows [T, n_mels] fp32 (row stride n_mels) -> levels [T] int32.
+void launch_vad_levels(hipStream_t s, const float* rows, int64_t T, int n_mels, int32_t* levels);
+// Steps 2-6 for B utterances in one launch: utterance b = T[b] levels at levels + off[b].  seg [B, cap, 2] frame pairs (only
+// the first min(n[b], cap) rows are written), n [B] = the segments that exist.  cfg: validated by vad_check (hostutil.h).
+struct VadParams { int32_t floor_pct, margin_q, abs_level, window, on_count, off_count, pad_begin, pad_end, min_speech, max_len,
+                   split_search, n_mels; };
+void launch_vad_segments(hipStream_t s, const int32_t* levels, const int64_t* off, const int32_t* T, int B, const VadParams& p,
+                         int32_t* seg, int cap, int32_t* n);
+
 }  // namespace pf

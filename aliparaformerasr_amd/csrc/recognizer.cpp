@@ -289,7 +289,7 @@ void Stream::wait_device_audio() {
 
 void Stream::drop_device_audio() {
   wait_device_audio();                                  // the buffer goes back to the cache: no DMA may still be writing it
-  if (dev_audio && owner) owner->audio_free(dev_audio, dev_bytes);
+  if (dev_audio && owner && !borrowed) owner->audio_free(dev_audio, dev_bytes);
   dev_audio = nullptr; dev_bytes = 0; dev_n = 0;
   device_form = false;
 }
@@ -524,6 +524,7 @@ void Recognizer::SetAlign(bool on) {
     set_decode_all(user_flags_ | extra_flags(), topk_k_);
     return;
   }
+  { std::lock_guard<std::mutex> lk(vad_mu_); if (vad_on_) throw Error(PF_ERR_UNSUPPORTED, "SetAlign: not available beside SetVad (long-audio recognition)"); }
   if (engine_kind_ != "sensevoicesmall") throw Error(PF_ERR_UNSUPPORTED, "SetAlign: only a SenseVoice model has a CTC head");
   align_on_ = true;
   try {
@@ -542,6 +543,7 @@ void Recognizer::SetCtcBeam(int N, int W, int K) {
     set_decode_all(user_flags_ | extra_flags(), topk_k_);
     return;
   }
+  { std::lock_guard<std::mutex> lk(vad_mu_); if (vad_on_) throw Error(PF_ERR_UNSUPPORTED, "SetCtcBeam: not available beside SetVad (long-audio recognition)"); }
   if (engine_kind_ != "sensevoicesmall") throw Error(PF_ERR_UNSUPPORTED, "SetCtcBeam: only a SenseVoice model has a CTC head");
   beam_w_ = W == 0 ? std::max(16, N) : W;
   beam_n_ = N;
@@ -569,10 +571,144 @@ void Recognizer::SetNBest(int N, int K) {
     nbest_n_ = 0;
     return;
   }
+  { std::lock_guard<std::mutex> lk(vad_mu_); if (vad_on_) throw Error(PF_ERR_UNSUPPORTED, "SetNBest: not available beside SetVad (long-audio recognition)"); }
   // frames of a CTC model are not independent tokens: a sum over frame ranks is no hypothesis score
   if (N > 1 && engine_kind_ == "sensevoicesmall") throw Error(PF_ERR_UNSUPPORTED, "SetNBest: N > 1 needs a paraformer model (SenseVoice offers K alone)");
   set_decode_all(user_flags_ | PF_DECODE_TOPK | extra_flags(), K == 0 ? 4 : K);
   nbest_n_ = N;
+}
+
+void Recognizer::SetVad(const pf_vad_config* cfg, int batch_max, int64_t frame_budget, const char* sep) {
+  if (disposed_) throw Error(PF_ERR_DISPOSED, "OfflineRecognizer");
+  if (!cfg) {
+    std::lock_guard<std::mutex> lk(vad_mu_);
+    vad_on_ = false;
+    return;
+  }
+  const pf_vad_config c = vad_check(cfg, (conf_.lfr_m == 1 && conf_.lfr_n == 1) ? 1 : conf_.lfr_n);
+  if (conf_.snip_edges) throw Error(PF_ERR_UNSUPPORTED, "SetVad: snip_edges = true is not supported");
+  if (batch_max < 0 || frame_budget < 0) throw Error(PF_ERR_INVALID_ARG, "SetVad: negative batch_max or frame_budget");
+  if (nbest_n_ > 0 || beam_on_ || align_on_)
+    throw Error(PF_ERR_UNSUPPORTED, "SetVad: not available beside SetNBest, SetCtcBeam or SetAlign");
+  std::lock_guard<std::mutex> lk(vad_mu_);
+  vad_on_ = true; vad_cfg_ = c;
+  vad_batch_max_ = batch_max == 0 ? 32 : batch_max;
+  vad_budget_ = frame_budget == 0 ? 96000 : frame_budget;
+  vad_sep_ = sep ? sep : "";
+}
+
+// GetResults with SetVad: segment every stream where its audio lies, plan batches over the pooled pieces, run Forward on each
+// batch through PIECE streams (plain device-form streams whose dev_audio points into the parent's buffer, so a piece's ids,
+// text and times are what a plain stream holding that sample range gives in that batch position), stitch per stream.
+void Recognizer::ForwardLong(const std::vector<Stream*>& streams, std::vector<ResultEntity>& out) {
+  out.assign(streams.size(), ResultEntity());
+  if (streams.empty()) return;
+  pf_vad_config cfg; int batch_max; int64_t budget; std::string sep;
+  { std::lock_guard<std::mutex> lk(vad_mu_); cfg = vad_cfg_; batch_max = vad_batch_max_; budget = vad_budget_; sep = vad_sep_; }
+  struct Piece { int stream, b, e; };
+  std::vector<Piece> pieces;
+  try {
+    if (disposed_) throw Error(PF_ERR_DISPOSED, "OfflineRecognizer");
+    const int B = (int)streams.size();
+    for (Stream* s : streams) {
+      adopt(s);
+      // the cut is made in the samples: a stream that holds features only (a second AddSamples, pf_stream_set_speech, the host
+      // form) has none left
+      if (!s->has_speech) throw Error(PF_ERR_RECOGNITION, "Object reference not set (Speech is null)");
+      if (!s->device_form) throw Error(PF_ERR_UNSUPPORTED, "SetVad: the stream holds features, not samples (long-audio recognition cuts the audio)");
+      s->wait_device_audio();
+    }
+    // 1. the speech of every stream, one batched launch set
+    std::vector<const float*> ptrs; std::vector<int64_t> ns;
+    int cap = 1;
+    for (Stream* s : streams) {
+      ptrs.push_back(s->dev_audio); ns.push_back(s->dev_n);
+      cap = std::max<int64_t>(cap, s->dev_n / 160 / std::max(cfg.min_speech, 1) + 2);
+    }
+    std::vector<int32_t> seg((size_t)B * cap * 2), nseg((size_t)B);
+    {
+      Lease lease = acquire();
+      lease->vad_segment_device(ptrs.data(), ns.data(), B, &cfg, seg.data(), cap, nseg.data());
+    }
+    // 2. the plan over the pooled pieces
+    std::vector<int32_t> lens;
+    for (int i = 0; i < B; ++i)
+      for (int k = 0; k < nseg[i]; ++k) {
+        const Piece p{i, seg[((size_t)i * cap + k) * 2], seg[((size_t)i * cap + k) * 2 + 1]};
+        pieces.push_back(p); lens.push_back(p.e - p.b);
+      }
+    std::vector<int32_t> batch(pieces.size()), row(pieces.size());
+    const int nb = host_long_plan(lens.data(), (int)lens.size(), batch_max, budget, batch.data(), row.data());
+    // SeACo: the call's hot words go to every batch (Forward takes the union over the batch's streams)
+    std::vector<std::vector<int32_t>> hw_all; bool hw_null = false;
+    for (Stream* s : streams) { hw_null = hw_null || s->hotwords_null; for (auto& w : s->Hotwords) hw_all.push_back(w); }
+    // 3. batch by batch
+    std::vector<std::unique_ptr<Stream>> views(pieces.size());
+    std::shared_ptr<Recognizer> self = shared_from_this();
+    for (int k = 0; k < nb; ++k) {
+      std::vector<Stream*> rows;
+      for (size_t j = 0; j < pieces.size(); ++j) if (batch[j] == k) { if ((size_t)row[j] >= rows.size()) rows.resize(row[j] + 1, nullptr); }
+      for (size_t j = 0; j < pieces.size(); ++j) {
+        if (batch[j] != k) continue;
+        Stream* parent = streams[pieces[j].stream];
+        const int64_t s0 = (int64_t)160 * pieces[j].b, s1 = std::min<int64_t>(parent->dev_n, (int64_t)160 * pieces[j].e);
+        views[j].reset(new Stream(self));
+        Stream* v = views[j].get();
+        v->borrowed = true; v->device_form = true; v->has_speech = true;
+        v->dev_audio = parent->dev_audio + s0; v->dev_n = s1 - s0; v->dev_bytes = 0;
+        v->SpeechLength = feature_floats(v->dev_n);
+        v->Tokens.clear();
+        v->hotwords_null = hw_null;
+        if (row[j] == 0) v->Hotwords = hw_all;
+        rows[row[j]] = v;
+      }
+      Forward(rows);
+    }
+    // 4. one result per stream, pieces in time order
+    std::vector<std::vector<int64_t>> ids(B); std::vector<TsList> ts(B); std::vector<std::vector<float>> sc(B);
+    for (Stream* s : streams) s->Segments.clear();
+    for (size_t j = 0; j < pieces.size(); ++j) {
+      const int i = pieces[j].stream, off_ms = 10 * pieces[j].b;
+      Stream* v = views[j].get();
+      auto shifted = [off_ms](const TsList& in) {               // every int of every entry onto the stream's clock
+        TsList o;
+        o.reserve(in.size());
+        for (const TsVec& t : in) {
+          std::vector<int32_t> x(t.begin(), t.end());
+          for (int32_t& y : x) y += off_ms;
+          o.emplace_back(x.data(), x.data() + x.size());
+        }
+        return o;
+      };
+      const TsList vt = shifted(v->Timestamps);
+      ResultEntity r = decode_multi_one(token_table_, v->Tokens, v->Timestamps);
+      Stream::Segment g;
+      g.begin_ms = off_ms; g.end_ms = 10 * pieces[j].e; g.batch = batch[j]; g.row = row[j];
+      g.tok_begin = (int)ids[i].size(); g.tok_end = g.tok_begin + (int)v->Tokens.size();
+      g.text = r.Text;
+      ResultEntity& o = out[i];
+      if (!streams[i]->Segments.empty()) o.Text += sep;
+      o.Text += r.Text;
+      o.Tokens.insert(o.Tokens.end(), r.Tokens.begin(), r.Tokens.end());
+      for (TsVec& t : shifted(r.Timestamps)) o.Timestamps.push_back(std::move(t));
+      ids[i].insert(ids[i].end(), v->Tokens.begin(), v->Tokens.end());
+      ts[i].insert(ts[i].end(), vt.begin(), vt.end());
+      sc[i].insert(sc[i].end(), v->Scores.begin(), v->Scores.end());
+      streams[i]->Segments.push_back(std::move(g));
+      v->dev_audio = nullptr; v->device_form = false;           // (the piece never owned it)
+    }
+    for (int i = 0; i < B; ++i) {
+      Stream* s = streams[i];
+      out[i].TextLen = utf16_length(out[i].Text);
+      s->Tokens.swap(ids[i]); s->Timestamps.swap(ts[i]); s->Scores.swap(sc[i]);
+      s->AltIds.clear(); s->AltVal.clear(); s->AltK = 0; s->Alternatives.clear();
+      s->AlignTs.clear(); s->AlignTok.clear(); s->AlignN = -1;
+      s->RemoveChunk();                                          // as Forward: a stream that produced a result gives up its audio
+    }
+  } catch (const Error& ex) {
+    if (ex.code == PF_ERR_RECOGNITION) throw;
+    throw Error(PF_ERR_RECOGNITION, std::string("Offline recognition failed: ") + ex.what());           // :194-197
+  }
 }
 
 void Recognizer::set_decode_all(int flags, int k) {
@@ -1253,10 +1389,17 @@ Recognizer::~Recognizer() {
 }
 
 void Recognizer::GetResults(const std::vector<Stream*>& streams) {
-  Forward(streams);
-  FwdClock fc;
+  bool vad;
+  { std::lock_guard<std::mutex> lk(vad_mu_); vad = vad_on_; }
   std::vector<ResultEntity> out;
-  for (Stream* s : streams) out.push_back(decode_multi_one(token_table_, s->Tokens, s->Timestamps));
+  if (vad) ForwardLong(streams, out);
+  else Forward(streams);
+  FwdClock fc;
+  for (Stream* s : streams) {
+    if (vad) break;
+    s->Segments.clear();
+    out.push_back(decode_multi_one(token_table_, s->Tokens, s->Timestamps));
+  }
   for (Stream* s : streams)                                   // the n-best list goes through the same DecodeMulti
     for (Alternative& a : s->Alternatives) {                  // (a beam hypothesis has no per-token times without SetAlign:
       TsList own(a.ctc ? a.ids.size() : 0, TsVec{0, 0});      //  {0, 0} each; with it, those of its own forced alignment)

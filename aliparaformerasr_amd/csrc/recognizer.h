@@ -159,6 +159,12 @@ class Stream {
   std::vector<int64_t> AlignIds; bool has_align = false;
   std::vector<int32_t> AlignTs; std::vector<float> AlignTok;
   float AlignPath = 0.f; double AlignLoglik = 0.0; int AlignOk = 0, AlignN = -1;
+  // long-audio recognition (Recognizer::SetVad): the pieces the stream was cut into by the last GetResults, in time order —
+  // [begin_ms, end_ms) on the stream's clock, where the piece ran (batch, row of the plan), its share [tok_begin, tok_end) of
+  // Tokens / Scores / Timestamps, and its own text.  Empty without SetVad.
+  struct Segment { int begin_ms = 0, end_ms = 0, batch = 0, row = 0, tok_begin = 0, tok_end = 0; std::string text; };
+  std::vector<Segment> Segments;
+  bool borrowed = false;                                      // dev_audio points INTO another stream's buffer (a piece): never freed here
   void RemoveChunk();                                         // OfflineStream.cs:69-79
   bool disposed = false;
   std::shared_ptr<Recognizer> owner;
@@ -193,6 +199,11 @@ class Recognizer : public std::enable_shared_from_this<Recognizer> {
   // SenseVoice only (paraformer_hip.h "CTC hot words"): boost per matched hot-word token inside the beam search of SetCtcBeam
   // (inert without it); 0 = off.  The hot words of a batch: the union of its streams' Hotwords, else the hot-word file's.
   void SetHotwordBoost(float s);
+  // Long-audio recognition (paraformer_hip.h "Voice-activity segmentation"): cfg != null: every GetResults that follows cuts
+  // its streams into speech pieces on the device (Engine::vad_segment_device over the resident audio), plans batches of similar
+  // length (host_long_plan), forwards each batch over pointers into the streams' audio and stitches one result per stream.
+  // cfg == null: off.  PF_ERR_UNSUPPORTED beside SetNBest / SetCtcBeam / SetAlign (either order).
+  void SetVad(const pf_vad_config* cfg, int batch_max, int64_t frame_budget, const char* sep);
   bool disposed() const { return disposed_.load(); }
   // engine 0 (nullptr once disposed): what pf_recognizer_engine hands out; callers lock engine->mutex() themselves
   std::shared_ptr<Engine> engine() { std::lock_guard<std::mutex> lk(mu_); return engines_.empty() ? nullptr : engines_[0]; }
@@ -232,6 +243,9 @@ class Recognizer : public std::enable_shared_from_this<Recognizer> {
 
  private:
   void Forward(const std::vector<Stream*>& streams);          // :118-198
+  void ForwardLong(const std::vector<Stream*>& streams, std::vector<ResultEntity>& out);   // GetResults with SetVad
+  std::mutex vad_mu_;                                         // guards the four below
+  bool vad_on_ = false; pf_vad_config vad_cfg_{}; int vad_batch_max_ = 32; int64_t vad_budget_ = 96000; std::string vad_sep_;
   std::shared_ptr<Engine> make_engine();
   std::mutex mu_;                                             // guards engines_, busy_, the audio cache
   std::condition_variable cv_;

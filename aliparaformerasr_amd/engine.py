@@ -183,6 +183,54 @@ def host_ctc_align(lp, y, V=None) -> AlignResult:
                        np.array([[U]], np.int32), first[:, :, :U], last[:, :, :U], tok[:, :, :U])
 
 
+def vad_config(**kw) -> "N.PfVadConfig":
+    """pf_vad_config with the stated defaults (pf_vad_default), fields overridden by keyword."""
+    c = N.PfVadConfig()
+    N.check(N.load().pf_vad_default(C.byref(c)))
+    for k, v in kw.items():
+        assert hasattr(c, k) and k not in ("struct_size", "reserved"), k
+        setattr(c, k, int(v))
+    return c
+
+
+def _vad_cfg_ptr(cfg):
+    if cfg is None:
+        return None
+    return C.byref(cfg if isinstance(cfg, N.PfVadConfig) else vad_config(**cfg))
+
+
+def host_vad_levels(rows) -> np.ndarray:
+    """Step 1 of the voice-activity segmentation in host code (pf_host_vad_levels): rows [T, n_mels] -> levels [T] int32."""
+    x = _f32(rows)
+    T, m = x.shape
+    out = np.zeros(T, np.int32)
+    N.check(N.load().pf_host_vad_levels(_fp(x), T, m, _i32p(out)))
+    return out
+
+
+def host_vad_segments(levels, n_mels=80, cfg=None, lfr_n=6, cap=None) -> np.ndarray:
+    """Steps 2-6 for ONE utterance in host code (pf_host_vad_segments): levels [T] int32 -> segments [n, 2] frame pairs.
+    cfg: None (the defaults), a PfVadConfig or a dict of its fields."""
+    e = np.ascontiguousarray(levels, dtype=np.int32).reshape(-1)
+    lib, n = N.load(), C.c_int32()
+    if cap is None:
+        rc = lib.pf_host_vad_segments(_i32p(e), e.size, int(n_mels), int(lfr_n), _vad_cfg_ptr(cfg), None, 0, n)
+        if rc != N.PF_ERR_CAPACITY:
+            N.check(rc)
+        cap = n.value
+    seg = np.zeros((max(cap, 1), 2), np.int32)
+    N.check(lib.pf_host_vad_segments(_i32p(e), e.size, int(n_mels), int(lfr_n), _vad_cfg_ptr(cfg), _i32p(seg), int(cap), n))
+    return seg[: n.value].copy()
+
+
+def host_long_plan(lens, batch_max=0, frame_budget=0):
+    """The batch plan of long-audio recognition (pf_host_long_plan): ([(batch, row)] per segment, number of batches)."""
+    ln = np.ascontiguousarray(lens, dtype=np.int32).reshape(-1)
+    b, r, nb = np.zeros(max(ln.size, 1), np.int32), np.zeros(max(ln.size, 1), np.int32), C.c_int32()
+    N.check(N.load().pf_host_long_plan(_i32p(ln), ln.size, int(batch_max), int(frame_budget), _i32p(b), _i32p(r), nb))
+    return list(zip(b[: ln.size].tolist(), r[: ln.size].tolist())), nb.value
+
+
 class BatchResult:
     def __init__(self, token_ids, token_num, L, V, logits=None, cif_peak=None, scores=None, ctc=None, topk=None, beam=None,
                  align=None):
@@ -711,6 +759,50 @@ class Engine:
         N.check(self._lib.pf_op_lfr_cmvn_pad(self._h, ptrs, t80, B, 1 if sentinel else 0, _fp(out), out.size, tm))
         assert tm.value == tmax, (tm.value, tmax)
         return out
+
+    def op_vad_levels(self, rows) -> np.ndarray:
+        """The detector's level kernel on caller rows [T, n_mels] (pf_op_vad_levels) -> [T] int32."""
+        x = _f32(rows)
+        T, m = x.shape
+        out = np.zeros(T, np.int32)
+        N.check(self._lib.pf_op_vad_levels(self._h, _fp(x), T, m, _i32p(out)))
+        return out
+
+    def op_vad_segments(self, levels_list, n_mels=80, cfg=None, cap=None, ld=None):
+        """The detector's segment kernel on caller levels (pf_op_vad_segments): ONE launch over all the utterances of
+        levels_list (int32 arrays of any lengths, laid out as [B, ld]); returns each utterance's segments [n, 2].  cap: the
+        capacity handed over (default: what always suffices); too small raises PfError(PF_ERR_CAPACITY) whose .n is n [B]."""
+        arrs = [np.ascontiguousarray(a, dtype=np.int32).reshape(-1) for a in levels_list]
+        B = len(arrs)
+        ld = max([a.size for a in arrs] + [1]) if ld is None else ld
+        lev = np.full((max(B, 1), ld), 0x7FFFFFFF, np.int32)      # past T[b]: values that would change every answer if read
+        for b, a in enumerate(arrs):
+            lev[b, : a.size] = a
+        T = np.ascontiguousarray([a.size for a in arrs] + [0] * (B == 0), dtype=np.int32)
+        cap = ld // 2 + 1 if cap is None else cap
+        seg = np.full((max(B, 1), max(cap, 1), 2), -7, np.int32)
+        n = np.zeros(max(B, 1), np.int32)
+        rc = self._lib.pf_op_vad_segments(self._h, _i32p(lev), _i32p(T), B, ld, int(n_mels), _vad_cfg_ptr(cfg), _i32p(seg), int(cap), _i32p(n))
+        if rc < 0:
+            try:
+                N.check(rc)
+            except N.PfError as ex:
+                ex.n, ex.seg = n[:B].copy(), seg[:B].copy()
+                raise
+        return [seg[b, : n[b]].copy() for b in range(B)]
+
+    def vad_segment(self, samples_list, cfg=None, cap=None):
+        """Voice-activity segmentation of whole streams on the device (pf_vad_segment): upload, the one batched fbank
+        launch, the detector; returns each utterance's segments [n, 2] (10 ms frame pairs)."""
+        arrs = [_f32(s) for s in samples_list]
+        B = len(arrs)
+        ptrs = (C.POINTER(C.c_float) * max(B, 1))(*[_fp(a) for a in arrs])
+        ns = (C.c_int64 * max(B, 1))(*[a.shape[0] for a in arrs])
+        cap = max([a.shape[0] // 320 + 2 for a in arrs] + [1]) if cap is None else cap
+        seg = np.zeros((max(B, 1), max(cap, 1), 2), np.int32)
+        n = np.zeros(max(B, 1), np.int32)
+        N.check(self._lib.pf_vad_segment(self._h, ptrs, ns, B, _vad_cfg_ptr(cfg), _i32p(seg), int(cap), _i32p(n)))
+        return [seg[b, : n[b]].copy() for b in range(B)]
 
     def op_fbank_batch(self, samples_list) -> list:
         """The batched fbank as run_staged launches it (pf_op_fbank_batch): one launch over all the utterances;

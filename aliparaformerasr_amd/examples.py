@@ -1,7 +1,7 @@
 """Command-line harness mirroring AliParaformerAsr.Examples (`-type offline` and `-type online`).
 
     python -m aliparaformerasr_amd.examples -type offline -method batch -base <dir> -model <name> \
-        [-accuracy int8] [-threads 2] [-decode ctc|frames] [-intake host|device] [-nbest N [-topk K] [-beam W [-hotboost S]]] [-align FILE|beam] -files a.wav b.wav
+        [-accuracy int8] [-threads 2] [-decode ctc|frames] [-intake host|device] [-nbest N [-topk K] [-beam W [-hotboost S]]] [-align FILE|beam] [-vad [key=value,...]] -files a.wav b.wav
     python -m aliparaformerasr_amd.examples -type online -method one -base <dir> -model <name> -files a.wav
 
 Mirrors (file:line in /root/reference/AliParaformerAsr.Examples):
@@ -34,6 +34,11 @@ beam search of width W in the same form; the score is the log of the summed alig
 line of space-separated token ids per file of `-files`, in their order (an empty line: no target; ids, not text — the
 tokenizer is not part of this package), and under each result line goes
 `align ok:<0|1> path:<best alignment's log-prob> loglik:<log P(ids | audio)> pairs:[begin,end],...` in milliseconds.
+`-vad [key=value,...]` (offline; OfflineRecognizer.SetVad) is for long recordings: each file is cut into speech segments on
+the device, the segments are recognised in batches of similar length and stitched into one result per file; under each result
+line goes one `[begin-end ms] text` line per segment.  Keys: the pf_vad_config fields (floor_pct, margin_q, abs_level, window,
+on_count, off_count, pad_begin, pad_end, min_speech, max_len, split_search), batch_max, frame_budget and sep.  The default
+thresholds are unvalidated on real speech.  Not beside -nbest / -align.
 `-align beam` (with `-nbest N -beam W`) aligns the beam search's labelings instead: under each `nbest[i]` line goes
 `align[i] loglik:<...> pairs:[begin,end],...`."""
 from __future__ import annotations
@@ -157,6 +162,38 @@ def _align_lines(stream) -> list:
     return ['align ok:%d path:%.6f loglik:%.6f pairs:%s' % (a.Ok, a.PathScore, a.LogLik, _pairs(a.Timestamps))]
 
 
+VAD_KEYS = ("floor_pct", "margin_q", "abs_level", "window", "on_count", "off_count", "pad_begin", "pad_end", "min_speech", "max_len",
+            "split_search")
+
+
+def parse_vad_option(text: str) -> dict:
+    """`key=value,...` of -vad -> {"cfg": {pf_vad_config fields}, "batch_max", "frame_budget", "sep"}"""
+    out = {"cfg": {}, "batch_max": 0, "frame_budget": 0, "sep": ""}
+    for item in [x for x in text.split(",") if x]:
+        k, eq, v = item.partition("=")
+        k = k.strip()
+        if not eq:
+            raise ValueError("-vad takes key=value pairs: %r" % item)
+        if k == "sep":
+            out["sep"] = v
+            continue
+        try:
+            iv = int(v)
+        except ValueError:
+            raise ValueError("The -vad value of %s must be an integer" % k)
+        if k in VAD_KEYS:
+            out["cfg"][k] = iv
+        elif k in ("batch_max", "frame_budget"):
+            out[k] = iv
+        else:
+            raise ValueError("Unknown -vad key: %s" % k)
+    return out
+
+
+def _segment_lines(stream) -> list:
+    return ["[%d-%d ms] %s" % (g.BeginMs, g.EndMs, g.Text) for g in stream.Segments]
+
+
 def read_align_file(path: str) -> list:
     """one line of space-separated token ids per input file; an empty line means no target for that file"""
     out = []
@@ -171,7 +208,7 @@ def read_align_file(path: str) -> list:
 
 def offline_recognizer(method="one", model="paraformer-seaco-large-zh-timestamp-onnx-offline", accuracy="int8",
                        threads=2, files=None, base=None, out=sys.stdout, decode="frames", intake="host", nbest=0, topk=4,
-                       beam=0, align=None, hotboost=0.0):
+                       beam=0, align=None, hotboost=0.0, vad=None):
     from .offline_recognizer import OfflineRecognizer
     base = base or os.getcwd()
     sel = select_model_files(base, model, accuracy)
@@ -188,6 +225,8 @@ def offline_recognizer(method="one", model="paraformer-seaco-large-zh-timestamp-
             rec.SetHotwordBoost(hotboost)
     elif nbest:
         rec.SetNBest(nbest, topk)
+    if vad is not None:
+        rec.SetVad(vad["cfg"] or True, vad["batch_max"], vad["frame_budget"], vad["sep"])
     targets = None
     if align:
         rec.SetAlign(True)
@@ -223,7 +262,8 @@ def offline_recognizer(method="one", model="paraformer-seaco-large-zh-timestamp-
             st.AddSamples(s)
 
     def extra_lines(st):
-        return (_nbest_lines(st, align == "beam") if nbest else []) + (_align_lines(st) if targets is not None else [])
+        return (_nbest_lines(st, align == "beam") if nbest else []) + (_align_lines(st) if targets is not None else []) + \
+            (_segment_lines(st) if vad is not None else [])
     print("Recognition results:\r\n", file=out)
     try:
         if method == "one":
@@ -406,6 +446,12 @@ def parse_args(argv, env=None):
             if i >= len(argv) or argv[i].startswith("-"):
                 raise ValueError("-align takes a file of token ids, or `beam`")
             cfg["align"] = argv[i]
+        elif a == "-vad":
+            text = ""
+            if i + 1 < len(argv) and not argv[i + 1].startswith("-") and "=" in argv[i + 1]:
+                i += 1
+                text = argv[i]
+            cfg["vad"] = parse_vad_option(text)
         elif a == "-threads":
             try:
                 i += 1
@@ -435,6 +481,10 @@ def parse_args(argv, env=None):
         raise ValueError("-nbest is an offline option")
     if "align" in cfg and cfg["recognizerType"] != "offline":
         raise ValueError("-align is an offline option")
+    if "vad" in cfg and cfg["recognizerType"] != "offline":
+        raise ValueError("-vad is an offline option")
+    if "vad" in cfg and ("nbest" in cfg or "align" in cfg):
+        raise ValueError("-vad does not go with -nbest or -align")
     if cfg.get("align") == "beam" and "beam" not in cfg:
         raise ValueError("-align beam needs -nbest N -beam W")
     return cfg
@@ -455,7 +505,7 @@ def main(argv=None):
         offline_recognizer(cfg["methodType"], cfg["modelName"], cfg["modelAccuracy"], cfg["threads"], cfg["files"],
                            cfg["modelBasePath"] or None, decode=cfg.get("decode", "frames"), intake=cfg.get("intake", "host"),
                            nbest=cfg.get("nbest", 0), topk=cfg.get("topk", 4), beam=cfg.get("beam", 0), align=cfg.get("align"),
-                           hotboost=cfg.get("hotboost", 0.0))
+                           hotboost=cfg.get("hotboost", 0.0), vad=cfg.get("vad"))
     else:
         print("the recognizer type must be online or offline")
         return 2

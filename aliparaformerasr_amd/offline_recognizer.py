@@ -94,6 +94,20 @@ class Alignment:
 
 
 @dataclass
+class Segment:
+    """OfflineStream.Segments: one speech piece of a long stream (OfflineRecognizer.SetVad).  [BeginMs, EndMs) on the stream's
+    clock; Batch / Row: where the piece ran in the call's batch plan; [TokBegin, TokEnd): its share of the stream's Tokens,
+    Scores and Timestamps; Text: its own text."""
+    BeginMs: int = 0
+    EndMs: int = 0
+    Batch: int = 0
+    Row: int = 0
+    TokBegin: int = 0
+    TokEnd: int = 0
+    Text: str = ""
+
+
+@dataclass
 class FrontendConfEntity:
     """Model/FrontendConfEntity.cs:6-28 (defaults included)."""
     fs: int = 16000
@@ -237,6 +251,19 @@ class OfflineStream:
                                    Text=(txt.value or b"").decode("utf-8"), Tokens=toks,
                                    Timestamps=[[pt[2 * j], pt[2 * j + 1]] for j in range(nts.value)],
                                    LogLik=None if ll.value != ll.value else ll.value))
+        return out
+
+    @property
+    def Segments(self) -> List["Segment"]:
+        """The pieces the last GetResults cut this stream into, in time order (OfflineRecognizer.SetVad; empty without it)."""
+        n = C.c_int32()
+        _ck(self._lib.pf_stream_num_segments(self._h, n))
+        out = []
+        for i in range(n.value):
+            v = [C.c_int32() for _ in range(6)]
+            txt = C.c_char_p()
+            _ck(self._lib.pf_stream_segment(self._h, i, *v, C.byref(txt)))
+            out.append(Segment(*[x.value for x in v], Text=(txt.value or b"").decode("utf-8")))
         return out
 
     def SetAlignIds(self, ids: Optional[List[int]]) -> None:
@@ -384,6 +411,20 @@ class OfflineRecognizer:
         in the audio, and log P(text | audio); with SetCtcBeam every Alternative gets Timestamps of its own and LogLik.
         Tokens, Timestamps, Scores, the result text and the alternatives' order and scores stay as they are."""
         _ck(self._lib.pf_recognizer_set_align(self._h, 1 if on else 0))
+
+    def SetVad(self, cfg=True, batch_max: int = 0, frame_budget: int = 0, sep: str = "") -> None:
+        """Long-audio recognition for every GetResults that follows (off by default; SetVad(None) turns it off again): each
+        stream is cut into speech segments on the device, the segments of the call are batched by length, forwarded where
+        they lie and stitched into one result per stream — Text joined by sep, Tokens / Scores concatenated, Timestamps on
+        the stream's clock; stream.Segments lists the pieces.  cfg: True (the stated defaults, which nobody has validated
+        on real speech), a dict of pf_vad_config fields, or a PfVadConfig.  batch_max / frame_budget: 0 = 32 rows /
+        96000 frames per batch.  Not available beside SetNBest, SetCtcBeam or SetAlign."""
+        if cfg is None or cfg is False:
+            _ck(self._lib.pf_recognizer_set_vad(self._h, None, 0, 0, None))
+            return
+        from .engine import vad_config
+        c = cfg if isinstance(cfg, N.PfVadConfig) else vad_config(**({} if cfg is True else cfg))
+        _ck(self._lib.pf_recognizer_set_vad(self._h, C.byref(c), int(batch_max), int(frame_budget), sep.encode("utf-8")))
 
     def GetResult(self, stream: OfflineStream) -> OfflineRecognizerResultEntity:
         return self.GetResults([stream])[0]

@@ -194,6 +194,34 @@ namespace AliParaformerAsr.Hip
             }
         }
 
+        /// <summary>Not in the reference: one speech piece of a long stream (OfflineRecognizer.SetVad): [BeginMs, EndMs) on the
+        /// stream's clock, where it ran in the call's batch plan, its share [TokBegin, TokEnd) of Tokens / Scores / Timestamps and
+        /// its own text.</summary>
+        public sealed class Segment
+        {
+            public int BeginMs, EndMs, Batch, Row, TokBegin, TokEnd;
+            public string Text = "";
+        }
+
+        /// <summary>Not in the reference: the pieces the last GetResults cut this stream into, in time order (empty without
+        /// OfflineRecognizer.SetVad).</summary>
+        public List<Segment> Segments
+        {
+            get
+            {
+                var r = new List<Segment>();
+                ParaformerHip.Check(ParaformerHip.pf_stream_num_segments(Handle, out int n));
+                for (int i = 0; i < n; i++)
+                {
+                    ParaformerHip.Check(ParaformerHip.pf_stream_segment(Handle, i, out int b, out int e, out int batch, out int row, out int t0,
+                                                                       out int t1, out IntPtr txt));
+                    r.Add(new Segment { BeginMs = b, EndMs = e, Batch = batch, Row = row, TokBegin = t0, TokEnd = t1,
+                                        Text = Marshal.PtrToStringUTF8(txt) ?? "" });
+                }
+                return r;
+            }
+        }
+
         /// <summary>Not in the reference: the stream's target for forced alignment (OfflineRecognizer.SetAlign) as token IDS — text
         /// to ids needs the model's tokenizer and is the caller's.  Kept until cleared with null.</summary>
         public void SetAlignIds(long[]? ids)
@@ -326,6 +354,23 @@ namespace AliParaformerAsr.Hip
         /// follows (off by default): a stream with a target (OfflineStream.SetAlignIds) gets OfflineStream.Alignment, and with
         /// SetCtcBeam every Alternative gets Timestamps of its own and LogLik.  Everything else stays as it is.</summary>
         public void SetAlign(bool on = true) => ParaformerHip.Check(ParaformerHip.pf_recognizer_set_align(_r, on ? 1 : 0));
+
+        /// <summary>Not in the reference: long-audio recognition for every GetResults that follows (off by default; null turns it
+        /// off again).  Each stream is cut into speech segments on the device, the call's segments are batched by length, forwarded
+        /// where they lie and stitched into one result per stream: Text joined by sep, Tokens / Scores concatenated, Timestamps on
+        /// the stream's clock; OfflineStream.Segments lists the pieces.  batchMax / frameBudget: 0 = 32 rows / 96000 frames per
+        /// batch.  Not available beside SetNBest, SetCtcBeam or SetAlign.  The default thresholds are unvalidated on real speech.</summary>
+        public void SetVad(PfVadConfig? cfg, int batchMax = 0, long frameBudget = 0, string sep = "")
+        {
+            ParaformerHip.Check(ParaformerHip.pf_recognizer_set_vad(_r, cfg == null ? null : new[] { cfg.Value }, batchMax, frameBudget, sep));
+        }
+
+        /// <summary>The stated defaults of the detector (pf_vad_default).</summary>
+        public static PfVadConfig DefaultVad()
+        {
+            ParaformerHip.Check(ParaformerHip.pf_vad_default(out PfVadConfig c));
+            return c;
+        }
 
         public OfflineStream CreateOfflineStream()
         {

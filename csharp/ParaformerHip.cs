@@ -43,6 +43,15 @@ namespace AliParaformerAsr.Native
         };
     }
 
+    /// <summary>pf_vad_config: the voice-activity detector's configuration (paraformer_hip.h "Voice-activity segmentation");
+    /// pf_vad_default fills in the stated defaults, which nobody has validated on real speech.</summary>
+    [StructLayout(LayoutKind.Sequential)]
+    public struct PfVadConfig
+    {
+        public int struct_size, floor_pct, margin_q, abs_level, window, on_count, off_count, pad_begin, pad_end, min_speech, max_len,
+                   split_search, reserved0, reserved1, reserved2, reserved3;
+    }
+
     /// <summary>pf_batch_out: capacities in, L / V / cif_peak_len and the filled buffers out.</summary>
     [StructLayout(LayoutKind.Sequential)]
     internal struct PfBatchOut
@@ -186,6 +195,16 @@ namespace AliParaformerAsr.Native
         [DllImport(Lib)] internal static extern int pf_stream_alignment(IntPtr s, out IntPtr beginEnd, out IntPtr tokScore, out int n, out float pathScore,
                                                                        out double loglik, out int ok);
         [DllImport(Lib)] internal static extern int pf_stream_alternative_timestamps(IntPtr s, int i, out IntPtr beginEnd, out int n, out double loglik);
+        // long-audio recognition: voice-activity segmentation on the device, batches of similar length, one result per stream
+        [DllImport(Lib)] internal static extern int pf_vad_default(out PfVadConfig cfg);
+        [DllImport(Lib)] internal static extern int pf_vad_segment(IntPtr e, IntPtr[] samples, long[] nSamples, int B, ref PfVadConfig cfg,
+                                                                  [Out] int[] seg, int cap, [Out] int[] nSeg);
+        // cfg: an array of one element, or null (= off)
+        [DllImport(Lib)] internal static extern int pf_recognizer_set_vad(IntPtr r, PfVadConfig[]? cfg, int batchMax, long frameBudget,
+                                                                         [MarshalAs(UnmanagedType.LPUTF8Str)] string? sepUtf8);
+        [DllImport(Lib)] internal static extern int pf_stream_num_segments(IntPtr s, out int n);
+        [DllImport(Lib)] internal static extern int pf_stream_segment(IntPtr s, int i, out int beginMs, out int endMs, out int batch, out int row,
+                                                                     out int tokBegin, out int tokEnd, out IntPtr textUtf8);
         [DllImport(Lib)] internal static extern int pf_recognizer_set_hotword_boost(IntPtr r, float boost);
         [DllImport(Lib)] internal static extern int pf_stream_alternative_hot(IntPtr s, int i, out int hotwordTokens, out double loglikSum);
         [DllImport(Lib)] internal static extern int pf_stream_token_alternatives(IntPtr s, out IntPtr ids, out IntPtr val, out int nTokens, out int K);

@@ -410,6 +410,67 @@ int pf_stage_pcm(pf_engine* e, const void* const* data, const int64_t* n_values,
 int pf_recognize_pcm(pf_engine* e, const void* const* data, const int64_t* n_values, const pf_pcm_desc* descs,
                      int32_t n_descs, int32_t B, const int32_t* hotwords, int32_t n_hotwords, pf_batch_out* out);
 
+/* ---- Voice-activity segmentation (additions to ABI 6; nothing is launched or allocated unless one of these is called) ----
+   Long audio is cut into utterance-sized pieces on the device: a deterministic, all-integer detector over the 10 ms fbank
+   rows the engine already computes (csrc/k_vad.hip).  The per-frame SCORE (step 1) is separate from the state machine
+   (steps 2-5), so a learned score can replace the energy level without touching the rest.  Every value below is an integer:
+   the device form, the host form (pf_host_vad_*) and the definition in numpy (tests/vad_ref.py) agree exactly.
+   THE DEFAULT THRESHOLDS ARE STATED, NOT TUNED: nobody has measured them on real speech.
+   Frames t = 0 .. T-1 of the whole stream, T = the fbank frame count of n samples; snip_edges = false only
+   (PF_ERR_UNSUPPORTED otherwise).
+   1 level      per row x[t, 0 .. n_mels) in fp32: v = x; !(v > -64) -> -64 (NaN, -inf); v > 64 -> 64;
+                q = (int)rintf(v * 64.f) (half to even); e[t] = sum of q (int32)
+   2 threshold  k = min(T - 1, (int64)T * floor_pct / 100); F = the k-th smallest e (0-based);
+                thr = max(F + margin_q * n_mels, abs_level) in int64; floor_pct = -1: thr = abs_level; raw[t] = e[t] > thr
+   3 hysteresis w = min(window, t + 1), c[t] = raw frames in [t - w + 1, t]; c[t] >= on_count: state[t] = 1; else
+                w - c[t] >= off_count: state[t] = 0; else state[t] = state[t - 1] (state[-1] = 0)
+   4 padding    d[t] = 1 iff some u in [t - pad_end, t + pad_begin] within [0, T) has state[u] = 1; runs = the maximal [b, e)
+                of d; runs with e - b < min_speech are dropped
+   5 split      while e - b > max_len: hi = min(b + max_len, e - min_speech), lo = hi - split_search, cut = the t in [lo, hi]
+                with the smallest e[t] (ties: the largest t); emit [b, cut), b = cut.  Then emit [b, e).
+                Every piece has min_speech <= length <= max_len.
+   6 output     [n, 2] int32 frame pairs, ascending.  Segment [b, e) covers the samples [160 b, min(n_samples, 160 e)).
+   PF_ERR_INVALID_ARG unless  -1 <= floor_pct <= 100,  1 <= window <= 256,  1 <= on_count, off_count <= window,
+   on_count + off_count > window,  0 <= pad_begin, pad_end <= 1024,  min_speech >= 2 * lfr_n (every segment yields an LFR
+   frame),  0 <= split_search <= 1024,  2 * min_speech + split_search <= max_len.
+   PF_ERR_CAPACITY: T above PF_VAD_MAX_FRAMES, more than PF_VAD_MAX_SEGMENTS segments, or more than the caller's cap
+   (the counts are filled in first). */
+#define PF_VAD_MAX_SEGMENTS 65536
+#define PF_VAD_MAX_FRAMES (1 << 22)
+typedef struct pf_vad_config {
+  int32_t struct_size;        /* = sizeof(pf_vad_config)                                                   */
+  int32_t floor_pct;          /* 10: percentile of the levels taken as the noise floor; -1 = none          */
+  int32_t margin_q;           /* 96: speech is this far above the floor, in 1/64 log units per mel bin     */
+  int32_t abs_level;          /* INT32_MIN: a lower bound of the threshold                                 */
+  int32_t window;             /* 20 frames                                                                 */
+  int32_t on_count;           /* 15                                                                        */
+  int32_t off_count;          /* 15                                                                        */
+  int32_t pad_begin;          /* 30 frames kept in front of speech                                         */
+  int32_t pad_end;            /* 5 frames kept behind it                                                   */
+  int32_t min_speech;         /* 50                                                                        */
+  int32_t max_len;            /* 3000                                                                      */
+  int32_t split_search;       /* 500                                                                       */
+  int32_t reserved[4];
+} pf_vad_config;
+/* fills in struct_size and the defaults above */
+int pf_vad_default(pf_vad_config* cfg);
+/* pf_stage_audio, the ONE batched fbank launch pf_run_staged makes, then the detector's launches over all B utterances;
+   only the segment lists are read back.  seg [B, cap, 2] frame pairs, n_seg [B].  cfg == NULL: the defaults. */
+int pf_vad_segment(pf_engine* e, const float* const* samples, const int64_t* n_samples, int32_t B, const pf_vad_config* cfg,
+                   int32_t* seg, int32_t cap, int32_t* n_seg);
+/* The host forms (plain C++, no device): step 1 over rows [T, n_mels]; steps 2-6 over the levels of ONE utterance, lfr_n as
+   the engine's front-end has it (seg may be NULL with cap 0 to learn *n). */
+int pf_host_vad_levels(const float* rows, int64_t T, int32_t n_mels, int32_t* out);
+int pf_host_vad_segments(const int32_t* levels, int32_t T, int32_t n_mels, int32_t lfr_n, const pf_vad_config* cfg, int32_t* seg,
+                         int32_t cap, int32_t* n);
+/* The batch plan of long-audio recognition (pure host code; part of the definition, because quirk Q2 makes a result depend
+   on its batch mates).  len [n]: segment lengths in frames, pooled over the streams of one call.  Order: length descending,
+   ties by index ascending.  A batch opens with the longest segment left (length L) and takes the following ones while
+   rows < batch_max and (rows + 1) * L <= frame_budget; it always takes at least one.  batch_max <= 0: 32;
+   frame_budget <= 0: 96000.  batch [n] / row [n]: where each segment goes; *n_batches (optional). */
+int pf_host_long_plan(const int32_t* len, int32_t n, int32_t batch_max, int64_t frame_budget, int32_t* batch, int32_t* row,
+                      int32_t* n_batches);
+
 /* ------------------------------------------------------------------------ */
 /* 4b. Multi-GPU inside one process: one engine, one host thread and one HIP stream per listed
  *     device.  The reference builds a single ORT session (OfflineRecognizer.cs:23); what shards is the utterance
@@ -488,6 +549,14 @@ int pf_op_ctc_collapse(pf_engine* e, const int64_t* ids, const float* scores, co
    out == NULL: only learn *n_out.  PF_ERR_CAPACITY (n_out filled in) when cap < n_out. */
 int pf_op_pcm_convert(pf_engine* e, const void* data, int64_t n_values, const pf_pcm_desc* desc, float* out, int64_t cap,
                       int64_t* n_out);
+/* exactly the detector's level kernel (k_vad.hip, step 1 of "Voice-activity segmentation") on caller rows [T, n_mels] fp32:
+   out [T] int32.  n_mels: 1 .. 1024. */
+int pf_op_vad_levels(pf_engine* e, const float* rows, int64_t T, int32_t n_mels, int32_t* out);
+/* exactly the detector's segment kernel (steps 2-6) on caller levels: levels [B, ld] int32 (any values), T [B] frames per
+   utterance (0 <= T[b] <= ld), cfg (NULL: the defaults; min_speech is checked against the engine's lfr_n); seg [B, cap, 2],
+   n [B].  PF_ERR_CAPACITY (n filled in, the first cap segments of each row stored) when a row has more than cap segments. */
+int pf_op_vad_segments(pf_engine* e, const int32_t* levels, const int32_t* T, int32_t B, int32_t ld, int32_t n_mels,
+                       const pf_vad_config* cfg, int32_t* seg, int32_t cap, int32_t* n);
 /* exactly the pipeline's top-k kernel (k_topk.hip) on the values as given: x [rows, ld] (ld >= V; nothing at or beyond V is
    read in a row), K: 1 .. PF_TOPK_MAX; ids [rows, K], val [rows, K], n [rows] as pf_fetch_topk. */
 int pf_op_topk(pf_engine* e, const float* x, int64_t rows, int32_t V, int32_t ld, int32_t K, int64_t* ids, float* val,
@@ -816,6 +885,31 @@ int pf_recognizer_set_align(pf_recognizer* r, int32_t on);
    score (biased), hotword_tokens (= matched) and loglik_sum through pf_stream_alternative_hot (0 / NaN when the call ran
    unbiased); Text and Tokens stay what they are.  A hot word that breaks the automaton's limits or holds an id outside
    [1, V) fails GetResults (PF_ERR_RECOGNITION). */
+/* Long-audio recognition (see "Voice-activity segmentation"; additions to ABI 6).  cfg != NULL: every GetResults that follows, on
+   every engine of the pool, present and future,
+     - segments all of the call's streams on the device, where their audio lies (one batched launch set);
+     - pools the segments and plans batches of similar length (pf_host_long_plan with batch_max / frame_budget; 0 = 32 / 96000);
+     - forwards batch after batch over device pointers into the streams' resident audio, no copy: a segment's ids, text,
+       times and scores are exactly what a plain stream holding its sample range gives in that batch position;
+     - stitches one result per stream in time order: Text = the segment texts joined by sep_utf8 (NULL = ""), Tokens and the
+       raw ids concatenated, every int of every timestamp entry + 10 * b ms (b = the segment's first frame), Scores
+       concatenated when a decode flag is set.  A stream with no segment gets empty Text, Tokens and Timestamps and takes
+       part in no forward.
+   cfg == NULL: off — nothing of this is launched or allocated and every result is bit for bit what it is without it.
+   The cut is made in the SAMPLES: a stream must hold its audio on the device (one pf_stream_add_samples / pf_stream_add_pcm
+   call); a stream that holds features only (a second AddSamples call, pf_stream_set_speech, PF_RECOGNIZER_DEVICE_STREAMS=0)
+   fails the call as PF_ERR_UNSUPPORTED inside Forward's try block ("Offline recognition failed: ...", PF_ERR_RECOGNITION).
+   Allowed beside it: PF_DECODE_SCORES, PF_DECODE_CTC, timestamp models, SeACo hot words (the union of the call's
+   stream.Hotwords goes to every batch).  PF_ERR_UNSUPPORTED beside it, whichever is set second: pf_recognizer_set_nbest,
+   pf_recognizer_set_ctc_beam, pf_recognizer_set_align.  pf_group_* and the streaming classes have no such switch.
+   PF_ERR_INVALID_ARG as for pf_vad_config; PF_ERR_UNSUPPORTED for a snip_edges = true front-end. */
+int pf_recognizer_set_vad(pf_recognizer* r, const pf_vad_config* cfg, int32_t batch_max, int64_t frame_budget, const char* sep_utf8);
+/* The segments of the stream's last GetResults in time order (0 without pf_recognizer_set_vad): [begin_ms, end_ms) on the
+   stream's clock, where it ran (batch, row of the plan), its share [tok_begin, tok_end) of pf_stream_tokens / pf_stream_scores
+   / pf_stream_timestamp, and its own text; each output optional.  Valid until the stream's next GetResults. */
+int pf_stream_num_segments(pf_stream* s, int32_t* n);
+int pf_stream_segment(pf_stream* s, int32_t i, int32_t* begin_ms, int32_t* end_ms, int32_t* batch, int32_t* row, int32_t* tok_begin,
+                      int32_t* tok_end, const char** text_utf8);
 int pf_recognizer_set_hotword_boost(pf_recognizer* r, float boost);
 int pf_stream_alternative_hot(pf_stream* s, int32_t i, int32_t* hotword_tokens, double* loglik_sum);
 int pf_stream_set_align_ids(pf_stream* s, const int64_t* ids, int32_t n);
