@@ -31,6 +31,9 @@ PF_DECODE_CTC_BEAM = 16
 PF_HOTWORD_STATES_MAX = 4096
 PF_HOTWORD_LEN_MAX = 64
 PF_HOTWORD_TABLE_BYTES_MAX = 16 * 1024 * 1024
+PF_LM_ORDER_MAX = 8
+PF_LM_IMAGE_BYTES_MAX = 1024 * 1024 * 1024
+PF_LM_EOS = 1
 PF_DECODE_ALIGN = 32
 PF_ALIGN_MAX_TOKENS = 1023
 PF_TOPK_MAX = 8
@@ -202,11 +205,28 @@ SIGNATURES = {
     "pf_op_ctc_beam_hot": (C.c_int, [_vp, _f, _i64, _f, _i32, _i32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                      _i64, _i32, _P(C.c_double), C.c_int32, _i32, _i32, _i32, C.c_int32, C.c_float, _i32,
                                      _P(C.c_double)]),
+    "pf_host_lm_build": (C.c_int, [C.c_int32, _i64, _i32, _f, _f, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, _i32, C.c_int32,
+                                   _P(_vp)]),
+    "pf_host_lm_from_arpa": (C.c_int, [C.c_char_p, _cpp, C.c_int32, C.c_float, _i64, _P(_vp)]),
+    "pf_host_lm_info": (C.c_int, [_vp, _i32, _i64, _i64, _i64]),
+    "pf_host_lm_score": (C.c_int, [_vp, _i32, C.c_int32, C.c_float, C.c_float, C.c_int32, _P(C.c_double), _i32, _P(C.c_double), _i32]),
+    "pf_lm_free": (None, [_vp]),
+    "pf_engine_set_ctc_lm": (C.c_int, [_vp, _vp, C.c_float, C.c_float, C.c_int32]),
+    "pf_fetch_ctc_beam_lm": (C.c_int, [_vp, _P(C.c_double), _P(C.c_double)]),
+    "pf_host_ctc_beam_lm": (C.c_int, [_f, C.c_int64, _i64, _f, _i32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _i64, _i32,
+                                      _P(C.c_double), C.c_int32, _i32, _i32, _i32, C.c_int32, C.c_float, _i32, _P(C.c_double), _vp,
+                                      C.c_float, C.c_float, C.c_int32, _P(C.c_double)]),
+    "pf_op_ctc_beam_lm": (C.c_int, [_vp, _f, _i64, _f, _i32, _i32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                    _i64, _i32, _P(C.c_double), C.c_int32, _i32, _i32, _i32, C.c_int32, C.c_float, _i32,
+                                    _P(C.c_double), _vp, C.c_float, C.c_float, C.c_int32, _P(C.c_double)]),
+    "pf_op_lm_score": (C.c_int, [_vp, _vp, _i32, _i32, C.c_int32, C.c_int32, C.c_float, C.c_float, _P(C.c_double), _i32]),
     "pf_recognizer_set_vad": (C.c_int, [_vp, _P(PfVadConfig), C.c_int32, C.c_int64, C.c_char_p]),
     "pf_stream_num_segments": (C.c_int, [_vp, _i32]),
     "pf_stream_segment": (C.c_int, [_vp, C.c_int32, _i32, _i32, _i32, _i32, _i32, _i32, _cpp]),
     "pf_recognizer_set_hotword_boost": (C.c_int, [_vp, C.c_float]),
     "pf_stream_alternative_hot": (C.c_int, [_vp, C.c_int32, _i32, _P(C.c_double)]),
+    "pf_recognizer_set_lm": (C.c_int, [_vp, C.c_char_p, C.c_float, C.c_float, C.c_int32]),
+    "pf_stream_alternative_lm": (C.c_int, [_vp, C.c_int32, _P(C.c_double), _P(C.c_double)]),
     "pf_engine_set_align_targets": (C.c_int, [_vp, _i64, _i32, C.c_int32, C.c_int32]),
     "pf_fetch_align": (C.c_int, [_vp, _f, _P(C.c_double), _i32, _i32, _i32, _i32, _f, C.c_int32, _i32, _i32]),
     "pf_host_ctc_align": (C.c_int, [_f, C.c_int64, C.c_int32, C.c_int32, _i64, C.c_int32, _f, _P(C.c_double), _i32, _i32, _i32, _f]),

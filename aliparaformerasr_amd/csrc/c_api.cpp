@@ -470,6 +470,81 @@ int pf_host_ctc_beam_hot(const float* blank_lp, int64_t blank_stride, const int6
   PF_CATCH
 }
 
+int pf_host_lm_build(int32_t order, const int64_t* n_ngrams, const int32_t* ids, const float* logp, const float* backoff, int32_t V,
+                     int32_t bos, int32_t eos, int32_t unk, float oov, const int32_t* transparent, int32_t n_transparent, pf_lm** lm) {
+  PF_TRY
+  NEED(lm);
+  *lm = nullptr;
+  std::shared_ptr<const LmImage> p = lm_build(order, n_ngrams, ids, logp, backoff, V, bos, eos, unk, oov, transparent, n_transparent);
+  *lm = new pf_lm{std::move(p)};
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_host_lm_from_arpa(const char* path, const char* const* tokens, int32_t n_tokens, float oov, int64_t* n_dropped, pf_lm** lm) {
+  PF_TRY
+  NEED(lm); NEED(path);
+  *lm = nullptr;
+  std::shared_ptr<const LmImage> p = lm_from_arpa(path, tokens, n_tokens, oov, n_dropped);
+  *lm = new pf_lm{std::move(p)};
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_host_lm_info(const pf_lm* lm, int32_t* order, int64_t* n_states, int64_t* n_arcs, int64_t* image_bytes) {
+  PF_TRY
+  NEED(lm);
+  if (order) *order = lm->p->order;
+  if (n_states) *n_states = lm->p->states;
+  if (n_arcs) *n_arcs = lm->p->arcs;
+  if (image_bytes) *image_bytes = (int64_t)lm->p->bytes();
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_host_lm_score(const pf_lm* lm, const int32_t* ids, int32_t n, float alpha, float beta, int32_t flags, double* g, int32_t* state,
+                     double* g_pos, int32_t* state_pos) {
+  PF_TRY
+  NEED(lm);
+  lm_score(*lm->p, ids, n, alpha, beta, flags, g, state, g_pos, state_pos);
+  return PF_OK;
+  PF_CATCH
+}
+
+void pf_lm_free(pf_lm* lm) { delete lm; }
+
+int pf_engine_set_ctc_lm(pf_engine* h, const pf_lm* lm, float alpha, float beta, int32_t flags) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->set_ctc_lm(lm ? lm->p : nullptr, alpha, beta, flags);
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_fetch_ctc_beam_lm(pf_engine* h, double* lm_sum, double* loglik_sum) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->fetch_ctc_beam_lm(lm_sum, loglik_sum);
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_host_ctc_beam_lm(const float* blank_lp, int64_t blank_stride, const int64_t* ids, const float* val, const int32_t* n, int32_t T,
+                        int32_t K, int32_t blank, int32_t W, int32_t N, int64_t* out_ids, int32_t* out_len, double* out_score,
+                        int32_t cap, int32_t* n_hyp, const int32_t* hw_ids, const int32_t* hw_lens, int32_t n_hotwords, float boost,
+                        int32_t* out_matched, double* out_loglik, const pf_lm* lm, float alpha, float beta, int32_t flags, double* out_lm) {
+  PF_TRY
+  NEED(n_hyp); NEED(lm);
+  *n_hyp = host_ctc_beam_lm(blank_lp, blank_stride, ids, val, n, T, K, blank, W, N, hw_ids, hw_lens, n_hotwords, boost, out_ids, out_len,
+                            out_score, out_matched, out_loglik, cap, *lm->p, alpha, beta, flags, out_lm);
+  return PF_OK;
+  PF_CATCH
+}
+
 int pf_engine_set_align_targets(pf_engine* h, const int64_t* ids, const int32_t* len, int32_t B, int32_t cap) {
   PF_TRY
   std::shared_ptr<Engine> eh_ = E(h);
@@ -811,6 +886,39 @@ int pf_op_ctc_beam_hot(pf_engine* h, const float* blank_lp, const int64_t* ids, 
   std::lock_guard<std::mutex> lk(e->mutex());
   e->op_ctc_beam_hot(blank_lp, ids, val, n, lens, B, T, K, blank, W, N, hw_ids, hw_lens, n_hotwords, boost, out_ids, out_len, out_score,
                      out_matched, out_loglik, cap, n_hyp);
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_op_ctc_beam_lm(pf_engine* h, const float* blank_lp, const int64_t* ids, const float* val, const int32_t* n, const int32_t* lens,
+                      int32_t B, int32_t T, int32_t K, int32_t blank, int32_t W, int32_t N, int64_t* out_ids, int32_t* out_len,
+                      double* out_score, int32_t cap, int32_t* n_hyp, const int32_t* hw_ids, const int32_t* hw_lens,
+                      int32_t n_hotwords, float boost, int32_t* out_matched, double* out_loglik, const pf_lm* lm, float alpha,
+                      float beta, int32_t flags, double* out_lm) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  NEED(lens); NEED(out_ids); NEED(out_len); NEED(out_score); NEED(n_hyp); NEED(out_matched); NEED(out_loglik); NEED(lm); NEED(out_lm);
+  PF_CHECK(B >= 0 && T >= 0 && cap >= 1 && K >= 1 && K <= PF_TOPK_MAX && N >= 1 && N <= W && W <= PF_NBEST_MAX, PF_ERR_INVALID_ARG,
+           "ctc_beam: bad shape (1 <= N <= W <= 64, 1 <= K <= 8, cap >= 1)");
+  if ((int64_t)B * T > 0) { NEED(blank_lp); NEED(ids); NEED(val); NEED(n); }
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->op_ctc_beam_lm(blank_lp, ids, val, n, lens, B, T, K, blank, W, N, hw_ids, hw_lens, n_hotwords, boost, out_ids, out_len, out_score,
+                    out_matched, out_loglik, cap, n_hyp, lm->p, alpha, beta, flags, out_lm);
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_op_lm_score(pf_engine* h, const pf_lm* lm, const int32_t* ids, const int32_t* lens, int32_t B, int32_t L, float alpha, float beta,
+                   double* g, int32_t* state) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  NEED(lm);
+  PF_CHECK(B >= 0 && L >= 0, PF_ERR_INVALID_ARG, "lm_score: bad shape");
+  if ((int64_t)B * L > 0) { NEED(ids); NEED(lens); NEED(g); NEED(state); }
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->op_lm_score(lm->p, ids, lens, B, L, alpha, beta, g, state);
   return PF_OK;
   PF_CATCH
 }
@@ -1448,6 +1556,26 @@ int pf_stream_alternative_hot(pf_stream* h, int32_t i, int32_t* hotword_tokens, 
   PF_CHECK(i >= 0 && i < (int32_t)s->Alternatives.size(), PF_ERR_INVALID_ARG, "alternative index out of range");
   const Alternative& a = s->Alternatives[(size_t)i];
   if (hotword_tokens) *hotword_tokens = a.hot_tokens;
+  if (loglik_sum) *loglik_sum = a.loglik_sum;
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_recognizer_set_lm(pf_recognizer* h, const char* arpa_path, float alpha, float beta, int32_t flags) {
+  PF_TRY
+  std::shared_ptr<Recognizer> r = R(h);
+  PF_CHECK(!r->disposed(), PF_ERR_DISPOSED, "OfflineRecognizer");
+  r->SetLm(arpa_path ? arpa_path : "", alpha, beta, flags);
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_stream_alternative_lm(pf_stream* h, int32_t i, double* lm_sum, double* loglik_sum) {
+  PF_TRY
+  Stream* s = S(h);
+  PF_CHECK(i >= 0 && i < (int32_t)s->Alternatives.size(), PF_ERR_INVALID_ARG, "alternative index out of range");
+  const Alternative& a = s->Alternatives[(size_t)i];
+  if (lm_sum) *lm_sum = a.lm_sum;
   if (loglik_sum) *loglik_sum = a.loglik_sum;
   return PF_OK;
   PF_CATCH

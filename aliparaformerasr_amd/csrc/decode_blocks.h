@@ -65,6 +65,12 @@ struct BeamHotBlock : Block {
   BeamHotBlock(Cursor& c, size_t B, size_t N) : Block(c) { lay(c, loglik, B * N, matched, B * N); }
 };
 
+// the fused search's extra (language model): lm_sum [B, N] float64; loglik_sum travels in BeamHotBlock (matched 0 without a set)
+struct BeamLmBlock : Block {
+  Field<double> lm_sum;
+  BeamLmBlock(Cursor& c, size_t B, size_t N) : Block(c) { lay(c, lm_sum, B * N); }
+};
+
 // CTC forced alignment (k_ctcalign.hip): loglik [B, H] float64 | path_score [B, H] fp32 | ok [B, H] | len [B, H] int32 |
 // first [B, H, cap] | last [B, H, cap] int32 | tok_score [B, H, cap] fp32
 struct AlignBlock : Block {
@@ -103,12 +109,15 @@ struct HostBatchOut { // results of a forward, host side
   // decoding extras (Engine::set_decode), empty without the flag: one block each, as the kernel leaves it; *_block() lays it out
   int decode_flags = 0;
   std::vector<float> scores;       // [B, L] log-prob of ids[b, l]
-  std::vector<int64_t> ctc, topk, beam, beam_hot, align;   // beam_hot: empty when the search ran unbiased
+  std::vector<int64_t> ctc, topk, beam, beam_hot, align;   // beam_hot: empty when the search ran unbiased and unfused
+  std::vector<int64_t> beam_lm;    // empty when the search ran without a language model; loglik_sum then sits in beam_hot
+  bool beam_biased = false;        // a hot-word set biased the search: beam_hot's matched means something
   int ctc_cap = 0, topk_k = 0, beam_n = 0, beam_cap = 0, align_h = 0, align_cap = 0;
   CtcBlock ctc_block() const { return block_at_zero<CtcBlock>(B, ctc_cap); }
   TopkBlock topk_block() const { return block_at_zero<TopkBlock>((size_t)B * L, topk_k); }
   BeamBlock beam_block() const { return block_at_zero<BeamBlock>(B, beam_n, beam_cap); }
   BeamHotBlock beam_hot_block() const { return block_at_zero<BeamHotBlock>(B, beam_n); }
+  BeamLmBlock beam_lm_block() const { return block_at_zero<BeamLmBlock>(B, beam_n); }
   AlignBlock align_block() const { return block_at_zero<AlignBlock>(B, align_h, align_cap); }
 };
 

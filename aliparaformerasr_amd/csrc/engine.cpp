@@ -119,7 +119,8 @@ void Engine::release() {
   for (void* p : owned_) hipFree(p);
   owned_.clear();
   DevBuf* bufs[] = {&ws_f32_, &ws_pcm_, &ws_audio_, &ws_meta_, &ws_fbank_, &ws_speech_, &ws_enc_, &ws_dec_, &ws_kv_, &ws_pe_, &ws_tmp_,
-                    &ws_ts_, &ws_seaco_, &ws_seaco_in_, &ws_seaco_hw_, &ws_q_, &ws_qf_, &ws_seaco_q_, &ws_x3a_, &ws_x3t_, &ws_x3h_};
+                    &ws_ts_, &ws_seaco_, &ws_seaco_in_, &ws_seaco_hw_, &ws_q_, &ws_qf_, &ws_seaco_q_, &ws_x3a_, &ws_x3t_, &ws_x3h_, &lm_inst_.buf, &lm_op_.buf};
+  lm_inst_.src.reset(); lm_op_.src.reset(); lm_.reset();
   x3_pair_live_ = false; x3a_src_ = nullptr; x3a_pair_only_ = false;
   x3w_.clear();
   ts_whh_x3_ = nullptr;
@@ -1939,6 +1940,17 @@ void Engine::set_ctc_hotwords(const int32_t* ids, const int32_t* lens, int n, fl
   hot_A_ = g.A;
 }
 
+void Engine::set_ctc_lm(const std::shared_ptr<const LmImage>& lm, float alpha, float beta, int flags) {
+  PF_CHECK(mc_.kind_id() == 1 && !mc_.seaco, PF_ERR_UNSUPPORTED, "set_ctc_lm: only a SenseVoice model has a CTC head");
+  if (!lm) { lm_.reset(); return; }                 // (the image stays where it is: the same model again costs no upload)
+  lm_check_weights(alpha, beta, flags);
+  PF_HIP(hipSetDevice(device_));
+  if (lm_inst_.src != lm) PF_HIP(hipStreamSynchronize(stream_));   // a queued search may still read the image about to be replaced
+  lm_device_image(lm_inst_, lm);
+  lm_ = lm;
+  lm_alpha_ = alpha; lm_beta_ = beta; lm_flags_ = flags;
+}
+
 float* Engine::score_buf(int64_t rows) {
   if (!decode_flags_) return nullptr;
   ensure(ws_score_, (size_t)std::max<int64_t>(rows, 1) * 4);
@@ -1982,7 +1994,7 @@ void Engine::queue_topk(int B, int L) {
 void Engine::queue_ctc_beam(int B, int L) {
   // the search reads the lists queue_topk just made and the blank column (id 0) of the in-place log-prob rows
   const int W = beam_w_, Nh = beam_n_, cap = L, K = topk_k_;
-  const bool hot = hot_boost_ > 0.f;
+  const bool hot = hot_boost_ > 0.f, lm = (bool)lm_;
   const size_t nodes = (size_t)B * ((size_t)L * W + 1);
   const TopkBlock tk = block_at_zero<TopkBlock>((size_t)B * L, K);
   Cursor c;
@@ -1990,7 +2002,9 @@ void Engine::queue_ctc_beam(int B, int L) {
   const Field<int32_t> len_d = c.take<int32_t>(B), node_par = c.take<int32_t>(nodes), node_tok = c.take<int32_t>(nodes);
   Cursor ch = c;
   const BeamHotBlock h(ch, B, Nh);                   // the biased form only: loglik_sum | matched behind the node workspace
-  ensure(ws_beam_, hot ? ch.off : c.off);
+  const size_t hot_end = ch.off;
+  const BeamLmBlock l(ch, B, Nh);                    // the fused forms only: lm_sum behind that (loglik_sum is the biased form's)
+  ensure(ws_beam_, lm ? ch.off : hot ? hot_end : c.off);
   last_.beam.resize(k.words());
   last_.beam_n = Nh;
   last_.beam_cap = cap;
@@ -1998,7 +2012,17 @@ void Engine::queue_ctc_beam(int B, int L) {
   const void* wt = ws_topk_.p;
   PF_HIP(hipMemcpyAsync(len_d(ws), ctc_len_.data(), ctc_len_.size() * 4, hipMemcpyHostToDevice, stream_));
   prof_begin("ctc_beam", 0);
-  if (hot) {
+  last_.beam_biased = hot;
+  if (lm) {
+    const int32_t* tok_col = hot ? (const int32_t*)ws_hot_.p : nullptr;
+    last_.beam_hot.resize(h.words());
+    last_.beam_lm.resize(l.words());
+    if (!hot) PF_HIP(hipMemsetAsync(h.matched(ws), 0, h.matched.count * 4, stream_));   // no set: nothing matched
+    launch_ctc_beam_lm(stream_, logits_, logits_ld_, tk.ids(wt), tk.val(wt), tk.n(wt), len_d(ws), B, L, K, 0, W, Nh, cap, node_par(ws),
+                       node_tok(ws), tok_col, mc_.vocab, hot ? tok_col + mc_.vocab : nullptr, hot_A_, hot_boost_,
+                       (const int32_t*)lm_inst_.buf.p, lm_alpha_, lm_beta_, lm_flags_, k.ids(ws), k.len(ws), k.score(ws), h.matched(ws),
+                       h.loglik(ws), l.lm_sum(ws), k.n_hyp(ws));
+  } else if (hot) {
     const int32_t* tok_col = (const int32_t*)ws_hot_.p;
     last_.beam_hot.resize(h.words());
     launch_ctc_beam_hot(stream_, logits_, logits_ld_, tk.ids(wt), tk.val(wt), tk.n(wt), len_d(ws), B, L, K, 0, W, Nh, cap, node_par(ws),
@@ -2010,7 +2034,8 @@ void Engine::queue_ctc_beam(int B, int L) {
   }
   prof_end("ctc_beam");
   PF_HIP(hipMemcpyAsync(last_.beam.data(), ws, k.words() * 8, hipMemcpyDeviceToHost, stream_));
-  if (hot) PF_HIP(hipMemcpyAsync(last_.beam_hot.data(), (char*)ws + h.begin, h.words() * 8, hipMemcpyDeviceToHost, stream_));
+  if (hot || lm) PF_HIP(hipMemcpyAsync(last_.beam_hot.data(), (char*)ws + h.begin, h.words() * 8, hipMemcpyDeviceToHost, stream_));
+  if (lm) PF_HIP(hipMemcpyAsync(last_.beam_lm.data(), (char*)ws + l.begin, l.words() * 8, hipMemcpyDeviceToHost, stream_));
 }
 
 void Engine::queue_align(int B, int L) {
@@ -2076,7 +2101,7 @@ void Engine::forward_device(const float* speech_dev, int B, int T, bool want_log
   last_.decode_flags = decode_flags_;
   last_.scores.clear(); last_.ctc.clear(); last_.ctc_cap = 0;
   last_.topk.clear(); last_.topk_k = 0;
-  last_.beam.clear(); last_.beam_n = 0; last_.beam_cap = 0; last_.beam_hot.clear();
+  last_.beam.clear(); last_.beam_n = 0; last_.beam_cap = 0; last_.beam_hot.clear(); last_.beam_lm.clear(); last_.beam_biased = false;
   last_.align.clear(); last_.align_h = 0; last_.align_cap = 0;
   if (align_B_ != 0 && align_B_ != B) {             // before anything is launched; the targets are dropped
     const int want = align_B_;
@@ -2256,11 +2281,21 @@ void Engine::fetch_ctc_beam(int64_t* ids, int32_t* len, double* score, int32_t c
 void Engine::fetch_ctc_beam_hot(int32_t* matched, double* loglik) {
   const char* refusal = "fetch_ctc_beam_hot: the last forward ran no biased beam search (PF_DECODE_CTC_BEAM with pf_engine_set_ctc_hotwords)";
   const HostBatchOut& r = fetch_result(PF_DECODE_CTC_BEAM, refusal);
-  PF_CHECK(!r.beam_hot.empty(), PF_ERR_INVALID_ARG, refusal);
+  PF_CHECK(!r.beam_hot.empty() && r.beam_biased, PF_ERR_INVALID_ARG, refusal);
   const BeamHotBlock k = r.beam_hot_block();
   const void* p = r.beam_hot.data();
   if (matched) std::memcpy(matched, k.matched(p), k.matched.count * 4);
   if (loglik) std::memcpy(loglik, k.loglik(p), k.loglik.count * 8);
+}
+
+void Engine::fetch_ctc_beam_lm(double* lm_sum, double* loglik) {
+  const char* refusal = "fetch_ctc_beam_lm: the last forward ran no fused beam search (PF_DECODE_CTC_BEAM with pf_engine_set_ctc_lm)";
+  const HostBatchOut& r = fetch_result(PF_DECODE_CTC_BEAM, refusal);
+  PF_CHECK(!r.beam_lm.empty() && !r.beam_hot.empty(), PF_ERR_INVALID_ARG, refusal);
+  const BeamLmBlock k = r.beam_lm_block();
+  const BeamHotBlock h = r.beam_hot_block();
+  if (lm_sum) std::memcpy(lm_sum, k.lm_sum(r.beam_lm.data()), k.lm_sum.count * 8);
+  if (loglik) std::memcpy(loglik, h.loglik(r.beam_hot.data()), h.loglik.count * 8);
 }
 
 void Engine::fetch_align(float* path_score, double* loglik, int32_t* ok, int32_t* len, int32_t* first, int32_t* last, float* tok_score,

@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 
+#include "lm.h"
 #include "json.h"
 #include "kernels.h"
 #include "shards.h"
@@ -190,11 +191,24 @@ class Engine {
   // form of the kernel and fetch_ctc_beam_hot gives matched / loglik_sum beside fetch_ctc_beam's (biased) scores.
   void set_ctc_hotwords(const int32_t* ids, const int32_t* lens, int n, float boost);
   bool ctc_hotwords_on() const { return hot_boost_ > 0.f; }
+  // Language model (SenseVoice; the definition is tests/ctcbeam_lm_ref.py): with a model installed a forward with CTC_BEAM runs
+  // a fused form of the kernel and fetch_ctc_beam_lm gives lm_sum / loglik_sum beside fetch_ctc_beam's (fused) scores.  nullptr
+  // clears; the image is uploaded once, the same model again only takes the new weights.
+  void set_ctc_lm(const std::shared_ptr<const LmImage>& lm, float alpha, float beta, int flags);
+  bool ctc_lm_on() const { return (bool)lm_; }
+  void fetch_ctc_beam_lm(double* lm_sum, double* loglik);
   void fetch_ctc_beam_hot(int32_t* matched, double* loglik);
   void op_ctc_beam_hot(const float* blank_lp, const int64_t* ids, const float* val, const int32_t* n, const int32_t* lens, int B, int T,
                        int K, int blank, int W, int N, const int32_t* hw_ids, const int32_t* hw_lens, int n_hw, float boost,
                        int64_t* out_ids, int32_t* out_len, double* out_score, int32_t* out_matched, double* out_loglik, int cap,
                        int32_t* n_hyp);
+  // the fused forms on caller data (language model, with or without a hot-word set), and the model's walk on its own
+  void op_ctc_beam_lm(const float* blank_lp, const int64_t* ids, const float* val, const int32_t* n, const int32_t* lens, int B, int T,
+                      int K, int blank, int W, int N, const int32_t* hw_ids, const int32_t* hw_lens, int n_hw, float boost,
+                      int64_t* out_ids, int32_t* out_len, double* out_score, int32_t* out_matched, double* out_loglik, int cap,
+                      int32_t* n_hyp, const std::shared_ptr<const LmImage>& lm, float alpha, float beta, int lm_flags, double* out_lm);
+  void op_lm_score(const std::shared_ptr<const LmImage>& lm, const int32_t* ids, const int32_t* lens, int B, int L, float alpha,
+                   float beta, double* g, int32_t* state);
   // ALIGN (SenseVoice; implies SCORES): behind the other decode launches one kernel (k_ctcalign.hip) aligns the caller's
   // targets of this forward (set_align_targets; consumed) and, with CTC_BEAM, the beam's hypotheses to the log-prob rows
   void set_align_targets(const int64_t* ids, const int32_t* len, int B, int cap);
@@ -504,6 +518,14 @@ class Engine {
   int hot_A_ = 0;                    // columns of the table
   std::vector<int32_t> hot_ids_, hot_lens_;   // the installed set as given: a call with the same content keeps the table
   DevBuf ws_hot_;                    // tok_col [V] | table [S, A]; allocated by set_ctc_hotwords only
+  // the language model's image in a buffer of its own: uploaded when a model is first used, kept (with a reference to the
+  // model) while the same one is given
+  struct LmDev { DevBuf buf; std::shared_ptr<const LmImage> src; };
+  LmDev lm_inst_, lm_op_;            // the installed model's image (set_ctc_lm), and the one pf_op_* last used
+  const int32_t* lm_device_image(LmDev& d, const std::shared_ptr<const LmImage>& lm);
+  std::shared_ptr<const LmImage> lm_;   // the installed model (nullptr: none), its weights and flags
+  float lm_alpha_ = 0.f, lm_beta_ = 0.f;
+  int lm_flags_ = 0;
   // PF_DECODE_ALIGN: the targets of the next forward (int32, [B, align_cap_]; align_B_ = 0: none) and those of the forward
   // being queued (alive until the next forward: the host-to-device copies may read them after the call returns)
   std::vector<int32_t> align_tgt_, align_len_, align_tgt_q_, align_len_q_;

@@ -278,25 +278,73 @@ void Engine::op_topk(const float* x, int64_t rows, int V, int ld, int K, int64_t
 void Engine::op_ctc_beam(const float* blank_lp, const int64_t* ids, const float* val, const int32_t* n, const int32_t* lens, int B,
                          int T, int K, int blank, int W, int N, int64_t* out_ids, int32_t* out_len, double* out_score, int cap,
                          int32_t* n_hyp) {
-  op_ctc_beam_hot(blank_lp, ids, val, n, lens, B, T, K, blank, W, N, nullptr, nullptr, 0, 0.f, out_ids, out_len, out_score, nullptr, nullptr,
-                  cap, n_hyp);
+  op_ctc_beam_lm(blank_lp, ids, val, n, lens, B, T, K, blank, W, N, nullptr, nullptr, 0, 0.f, out_ids, out_len, out_score, nullptr, nullptr,
+                 cap, n_hyp, nullptr, 0.f, 0.f, 0, nullptr);
 }
 
-// the one body of both: a hot-word set that biases (its tables, the boost, the two extra outputs) is the optional part
 void Engine::op_ctc_beam_hot(const float* blank_lp, const int64_t* ids, const float* val, const int32_t* n, const int32_t* lens, int B,
                              int T, int K, int blank, int W, int N, const int32_t* hw_ids, const int32_t* hw_lens, int n_hw, float boost,
                              int64_t* out_ids, int32_t* out_len, double* out_score, int32_t* out_matched, double* out_loglik, int cap,
                              int32_t* n_hyp) {
+  op_ctc_beam_lm(blank_lp, ids, val, n, lens, B, T, K, blank, W, N, hw_ids, hw_lens, n_hw, boost, out_ids, out_len, out_score, out_matched,
+                 out_loglik, cap, n_hyp, nullptr, 0.f, 0.f, 0, nullptr);
+}
+
+// the model's image on this engine's device: one upload per model
+const int32_t* Engine::lm_device_image(LmDev& d, const std::shared_ptr<const LmImage>& lm) {
+  if (d.src != lm) {
+    d.src.reset();
+    ensure(d.buf, lm->bytes());
+    PF_HIP(hipMemcpyAsync(d.buf.p, lm->words.data(), lm->bytes(), hipMemcpyHostToDevice, stream_));
+    PF_HIP(hipStreamSynchronize(stream_));
+    d.src = lm;
+  }
+  return (const int32_t*)d.buf.p;
+}
+
+void Engine::op_lm_score(const std::shared_ptr<const LmImage>& lm, const int32_t* ids, const int32_t* lens, int B, int L, float alpha,
+                         float beta, double* g, int32_t* state) {
+  lm_check_weights(alpha, beta, 0);
+  PF_HIP(hipSetDevice(device_));
+  if (B == 0 || L == 0) return;
+  const int32_t* image = lm_device_image(lm_inst_.src == lm ? lm_inst_ : lm_op_, lm);
+  const size_t rows = (size_t)B * L;
+  Cursor c;
+  const Field<double> d_g = c.take<double>(rows);
+  const Field<int32_t> d_st = c.take<int32_t>(rows), d_ids = c.take<int32_t>(rows), d_len = c.take<int32_t>(B);
+  ensure(ws_tmp_, c.off);
+  void* ws = ws_tmp_.p;
+  // the caller's outputs go up first: the positions the kernel does not write come back as they were
+  PF_HIP(hipMemcpyAsync(d_g(ws), g, rows * 8, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipMemcpyAsync(d_st(ws), state, rows * 4, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipMemcpyAsync(d_ids(ws), ids, rows * 4, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipMemcpyAsync(d_len(ws), lens, (size_t)B * 4, hipMemcpyHostToDevice, stream_));
+  launch_lm_walk(stream_, image, d_ids(ws), d_len(ws), B, L, alpha, beta, d_g(ws), d_st(ws));
+  PF_HIP(hipMemcpyAsync(g, d_g(ws), rows * 8, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipMemcpyAsync(state, d_st(ws), rows * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipStreamSynchronize(stream_));
+}
+
+// the one body of all three: a hot-word set that biases (its tables, the boost, the two extra outputs) and a language model
+// (its image, the weights, out_lm) are the optional parts
+void Engine::op_ctc_beam_lm(const float* blank_lp, const int64_t* ids, const float* val, const int32_t* n, const int32_t* lens, int B,
+                            int T, int K, int blank, int W, int N, const int32_t* hw_ids, const int32_t* hw_lens, int n_hw, float boost,
+                            int64_t* out_ids, int32_t* out_len, double* out_score, int32_t* out_matched, double* out_loglik, int cap,
+                            int32_t* n_hyp, const std::shared_ptr<const LmImage>& lm, float alpha, float beta, int lm_flags,
+                            double* out_lm) {
   PF_CHECK(boost >= 0.f && boost <= 3.4028234e38f, PF_ERR_INVALID_ARG, "ctc_beam_hot: the boost is finite and >= 0");
+  if (lm) lm_check_weights(alpha, beta, lm_flags);
   HotwordGraph graph;                               // (op_ctc_beam gives no set: nothing is built for it)
   if (n_hw != 0) build_hotword_graph(hw_ids, hw_lens, n_hw, hotword_vocab_bound(hw_ids, hw_lens, n_hw), graph);
   const HotwordGraph* g = boost == 0.f || graph.empty() ? nullptr : &graph;
   PF_HIP(hipSetDevice(device_));
   if (B == 0) return;
+  const int32_t* lm_image = lm ? lm_device_image(lm_inst_.src == lm ? lm_inst_ : lm_op_, lm) : nullptr;
   const size_t rows = (size_t)B * T, nodes = (size_t)B * ((size_t)T * W + 1);
   Cursor c;
   const BeamBlock k(c, B, N, cap);
-  const BeamHotBlock h(c, g ? B : 0, N);
+  const BeamHotBlock h(c, g || lm ? B : 0, N);
+  const BeamLmBlock l(c, lm ? B : 0, N);
   const TopkBlock in(c, rows, K);                   // the lists as op_topk gives them
   const Field<float> d_lb = c.take<float>(rows);
   const Field<int32_t> d_len = c.take<int32_t>(B), d_par = c.take<int32_t>(nodes), d_tok = c.take<int32_t>(nodes);
@@ -313,6 +361,12 @@ void Engine::op_ctc_beam_hot(const float* blank_lp, const int64_t* ids, const fl
   if (g) {
     PF_HIP(hipMemcpyAsync(d_col(ws), g->tok_col.data(), d_col.count * 4, hipMemcpyHostToDevice, stream_));
     PF_HIP(hipMemcpyAsync(d_tab(ws), g->table.data(), d_tab.count * 4, hipMemcpyHostToDevice, stream_));
+  }
+  if (lm) {
+    launch_ctc_beam_lm(stream_, d_lb(ws), 1, in.ids(ws), in.val(ws), in.n(ws), d_len(ws), B, T, K, blank, W, N, cap, d_par(ws), d_tok(ws),
+                       g ? d_col(ws) : nullptr, (int)d_col.count, d_tab(ws), g ? g->A : 0, boost, lm_image, alpha, beta, lm_flags, k.ids(ws),
+                       k.len(ws), k.score(ws), h.matched(ws), h.loglik(ws), l.lm_sum(ws), k.n_hyp(ws));
+  } else if (g) {
     launch_ctc_beam_hot(stream_, d_lb(ws), 1, in.ids(ws), in.val(ws), in.n(ws), d_len(ws), B, T, K, blank, W, N, cap, d_par(ws), d_tok(ws),
                         d_col(ws), (int)d_col.count, d_tab(ws), g->A, boost, k.ids(ws), k.len(ws), k.score(ws), h.matched(ws), h.loglik(ws),
                         k.n_hyp(ws));
@@ -324,15 +378,17 @@ void Engine::op_ctc_beam_hot(const float* blank_lp, const int64_t* ids, const fl
   if (!h_ids.empty()) PF_HIP(hipMemcpyAsync(h_ids.data(), k.ids(ws), h_ids.size() * 4, hipMemcpyDeviceToHost, stream_));
   PF_HIP(hipMemcpyAsync(out_len, k.len(ws), k.len.count * 4, hipMemcpyDeviceToHost, stream_));
   PF_HIP(hipMemcpyAsync(out_score, k.score(ws), k.score.count * 8, hipMemcpyDeviceToHost, stream_));
-  if (g) {
-    PF_HIP(hipMemcpyAsync(out_loglik, h.loglik(ws), h.loglik.count * 8, hipMemcpyDeviceToHost, stream_));
-    PF_HIP(hipMemcpyAsync(out_matched, h.matched(ws), h.matched.count * 4, hipMemcpyDeviceToHost, stream_));
-  }
+  if (g || lm) PF_HIP(hipMemcpyAsync(out_loglik, h.loglik(ws), h.loglik.count * 8, hipMemcpyDeviceToHost, stream_));
+  if (g) PF_HIP(hipMemcpyAsync(out_matched, h.matched(ws), h.matched.count * 4, hipMemcpyDeviceToHost, stream_));
+  if (lm) PF_HIP(hipMemcpyAsync(out_lm, l.lm_sum(ws), l.lm_sum.count * 8, hipMemcpyDeviceToHost, stream_));
   PF_HIP(hipMemcpyAsync(n_hyp, k.n_hyp(ws), k.n_hyp.count * 4, hipMemcpyDeviceToHost, stream_));
   PF_HIP(hipStreamSynchronize(stream_));            // g's host arrays are read by the copies queued above until here
   std::copy(h_ids.begin(), h_ids.end(), out_ids);
-  if (!g && out_matched)                            // a set that does not bias: op_ctc_beam's launch ran
-    for (size_t x = 0; x < k.score.count; ++x) { out_matched[x] = 0; out_loglik[x] = out_score[x]; }
+  if (!g && out_matched)                            // a set that does not bias: no hot-word term was added
+    for (size_t x = 0; x < k.score.count; ++x) {
+      out_matched[x] = 0;
+      if (!lm) out_loglik[x] = out_score[x];
+    }
 }
 
 void Engine::op_ctc_align(const float* lp, int B, int T, int V, int ld, const int32_t* tgt, const int32_t* tlen, const int32_t* lens,

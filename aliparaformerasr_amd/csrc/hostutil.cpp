@@ -1,5 +1,7 @@
 // hostutil.cpp — see hostutil.h
 #include "hostutil.h"
+#include "lm.h"
+#include "lm_dev.h"
 
 #include <cerrno>
 #include <climits>
@@ -524,16 +526,22 @@ struct BeamEntry {
   uint64_t hash;
   int node, par, tok, len;
   int st, m;                 // hot words: automaton state and matched tokens of the prefix (0 / 0 without a set)
+  int ls;                    // language model: its state and g of the prefix (0 / 0 without a model)
+  double g;
 };
 struct BeamCand {
-  double tot, key, pb, pnb;  // key = tot + bias(prefix): what select orders by (tot itself without a set)
+  double tot, key, pb, pnb;  // key = tot + bias(prefix) + g(prefix): what select orders by (tot itself without a set or a model)
   int idx, st, m;
+  int ls;
+  double g;
 };
 
-// the search of the definition; g == nullptr: the unbiased one (tests/ctcbeam_ref.py), else tests/ctcbeam_bias_ref.py
+// the search of the definition; g == nullptr: the unbiased one (tests/ctcbeam_ref.py), else tests/ctcbeam_bias_ref.py; lm: the
+// fused one (tests/ctcbeam_lm_ref.py), whose step is lm_dev.h's, the text the kernel runs
 int ctc_beam_impl(const float* blank_lp, int64_t blank_stride, const int64_t* ids, const float* val, const int32_t* n, int T, int K,
                   int blank, int W, int N, const HotwordGraph* g, double boost, int64_t* out_ids, int32_t* out_len, double* out_score,
-                  int32_t* out_matched, double* out_loglik, int cap) {
+                  int32_t* out_matched, double* out_loglik, int cap, const LmImage* lm = nullptr, double alpha = 0.0, double beta = 0.0,
+                  int lm_flags = 0, double* out_lm = nullptr) {
   if (!out_ids || !out_len || !out_score || (T > 0 && (!blank_lp || !ids || !val || !n)))
     throw Error(PF_ERR_INVALID_ARG, "ctc_beam: null argument");
   if (T < 0 || K < 1 || K > PF_TOPK_MAX || N < 1 || N > W || W > PF_NBEST_MAX || cap < 0 || blank_stride < 1)
@@ -542,7 +550,10 @@ int ctc_beam_impl(const float* blank_lp, int64_t blank_stride, const int64_t* id
     out_len[h] = 0; out_score[h] = kNegInf;
     if (out_matched) out_matched[h] = 0;
     if (out_loglik) out_loglik[h] = kNegInf;
+    if (out_lm) out_lm[h] = 0.0;
   }
+  LmView lv{};
+  if (lm) lv = lm_view(lm->words.data());
   std::fill(out_ids, out_ids + (size_t)N * cap, (int64_t)-1);
   for (int t = 0; t < T; ++t) {
     if (n[t] < 0 || n[t] > K) throw Error(PF_ERR_INVALID_ARG, "ctc_beam: n[t] outside 0 .. K");
@@ -561,7 +572,7 @@ int ctc_beam_impl(const float* blank_lp, int64_t blank_stride, const int64_t* id
     return true;
   };
   const int Vg = g ? (int)g->tok_col.size() : 0;
-  std::vector<BeamEntry> beam(1, BeamEntry{0.0, kNegInf, 0x243F6A8885A308D3ull, 0, -1, -1, 0, 0, 0}), next;
+  std::vector<BeamEntry> beam(1, BeamEntry{0.0, kNegInf, 0x243F6A8885A308D3ull, 0, -1, -1, 0, 0, 0, lv.start, 0.0}), next;
   std::vector<BeamCand> cand;
   std::vector<double> merged;
   const int K1 = K + 1;
@@ -571,7 +582,7 @@ int ctc_beam_impl(const float* blank_lp, int64_t blank_stride, const int64_t* id
     const int nt = n[t];
     const double lb = (double)blank_lp[(size_t)t * blank_stride];
     const int nbeam = (int)beam.size();
-    cand.assign((size_t)nbeam * K1, BeamCand{kNegInf, kNegInf, kNegInf, kNegInf, 0, 0, 0});
+    cand.assign((size_t)nbeam * K1, BeamCand{kNegInf, kNegInf, kNegInf, kNegInf, 0, 0, 0, 0, 0.0});
     merged.assign((size_t)nbeam, kNegInf);
     for (int i = 0; i < nbeam; ++i) {
       const BeamEntry& p = beam[(size_t)i];
@@ -579,6 +590,7 @@ int ctc_beam_impl(const float* blank_lp, int64_t blank_stride, const int64_t* id
       BeamCand& st = cand[(size_t)i * K1];
       st.pb = tot + lb;
       st.st = p.st; st.m = p.m;
+      st.ls = p.ls; st.g = p.g;
       for (int r = 0; r < nt; ++r) {
         const int c = (int)id[r];
         if (c == blank || c < 0) continue;
@@ -601,6 +613,10 @@ int ctc_beam_impl(const float* blank_lp, int64_t blank_stride, const int64_t* id
           x.st = e & 0xFFFF;
           x.m = p.m + ((e >> 16) & 0xFF);
         }
+        if (lm) {
+          x.g = p.g;
+          x.ls = lm_step(lv, p.ls, c, alpha, beta, true, x.g);
+        }
       }
     }
     std::vector<int> live;
@@ -610,6 +626,7 @@ int ctc_beam_impl(const float* blank_lp, int64_t blank_stride, const int64_t* id
       if (j % K1 == 0) c.pnb = beam_lse(c.pnb, merged[(size_t)(j / K1)]);
       c.tot = beam_lse(c.pb, c.pnb);
       c.key = g ? c.tot + boost * (double)(c.m + g->depth[(size_t)c.st]) : c.tot;
+      if (lm) c.key = c.key + c.g;
       if (c.tot > kNegInf) live.push_back(j);
     }
     std::sort(live.begin(), live.end(), [&](int a, int b) {
@@ -622,12 +639,12 @@ int ctc_beam_impl(const float* blank_lp, int64_t blank_stride, const int64_t* id
       const BeamCand& c = cand[(size_t)j];
       const BeamEntry& p = beam[(size_t)(j / K1)];
       if (j % K1 == 0) {
-        next.push_back(BeamEntry{c.pb, c.pnb, p.hash, p.node, p.par, p.tok, p.len, c.st, c.m});
+        next.push_back(BeamEntry{c.pb, c.pnb, p.hash, p.node, p.par, p.tok, p.len, c.st, c.m, c.ls, c.g});
       } else {
         const int tok = (int)id[j % K1 - 1];
         npar.push_back(p.node);
         ntok.push_back(tok);
-        next.push_back(BeamEntry{c.pb, c.pnb, beam_hash(p.hash, tok), (int)npar.size() - 1, p.node, tok, p.len + 1, c.st, c.m});
+        next.push_back(BeamEntry{c.pb, c.pnb, beam_hash(p.hash, tok), (int)npar.size() - 1, p.node, tok, p.len + 1, c.st, c.m, c.ls, c.g});
       }
     }
     beam.swap(next);
@@ -639,9 +656,14 @@ int ctc_beam_impl(const float* blank_lp, int64_t blank_stride, const int64_t* id
   for (int h = 0; h < nb; ++h) {
     ll[(size_t)h] = beam_lse(beam[(size_t)h].pb, beam[(size_t)h].pnb);
     score[(size_t)h] = g ? ll[(size_t)h] + boost * (double)beam[(size_t)h].m : ll[(size_t)h];
+    if (lm) {                                        // g_final: the end-of-sentence step where asked for
+      BeamEntry& e = beam[(size_t)h];
+      if ((lm_flags & PF_LM_EOS) && lv.eos >= 0) lm_step(lv, e.ls, lv.eos, alpha, beta, false, e.g);
+      score[(size_t)h] = score[(size_t)h] + e.g;
+    }
     order[(size_t)h] = h;
   }
-  if (g)
+  if (g || lm)
     std::sort(order.begin(), order.end(), [&](int a, int b) {
       return score[(size_t)a] != score[(size_t)b] ? score[(size_t)a] > score[(size_t)b] : a < b;
     });
@@ -658,6 +680,7 @@ int ctc_beam_impl(const float* blank_lp, int64_t blank_stride, const int64_t* id
     out_score[h] = score[(size_t)src];
     if (out_matched) out_matched[h] = e.m;
     if (out_loglik) out_loglik[h] = ll[(size_t)src];
+    if (out_lm) out_lm[h] = e.g;
   }
   return nh;
 }
@@ -773,6 +796,21 @@ int host_ctc_beam_hot(const float* blank_lp, int64_t blank_stride, const int64_t
   const int nh = ctc_beam_impl(blank_lp, blank_stride, ids, val, n, T, K, blank, W, N, on ? &g : nullptr, (double)boost, out_ids, out_len,
                                out_score, out_matched, out_loglik, cap);
   return nh;
+}
+
+int host_ctc_beam_lm(const float* blank_lp, int64_t blank_stride, const int64_t* ids, const float* val, const int32_t* n, int T, int K,
+                     int blank, int W, int N, const int32_t* hw_ids, const int32_t* hw_lens, int n_hw, float boost, int64_t* out_ids,
+                     int32_t* out_len, double* out_score, int32_t* out_matched, double* out_loglik, int cap, const LmImage& lm, float alpha,
+                     float beta, int lm_flags, double* out_lm) {
+  if (!out_matched || !out_loglik || !out_lm) throw Error(PF_ERR_INVALID_ARG, "ctc_beam_lm: null argument");
+  if (!(boost >= 0.f) || std::isinf(boost)) throw Error(PF_ERR_INVALID_ARG, "ctc_beam_hot: the boost is finite and >= 0");
+  if (!(alpha >= 0.f) || std::isinf(alpha) || !std::isfinite(beta) || (lm_flags & ~PF_LM_EOS))
+    throw Error(PF_ERR_INVALID_ARG, "lm: alpha is finite and >= 0, beta finite, flags known");
+  HotwordGraph g;
+  build_hotword_graph(hw_ids, hw_lens, n_hw, hotword_vocab_bound(hw_ids, hw_lens, n_hw), g);
+  const bool on = boost > 0.f && !g.empty();
+  return ctc_beam_impl(blank_lp, blank_stride, ids, val, n, T, K, blank, W, N, on ? &g : nullptr, (double)boost, out_ids, out_len, out_score,
+                       out_matched, out_loglik, cap, &lm, (double)alpha, (double)beta, lm_flags, out_lm);
 }
 
 // ------------------------------------------------------------------ CTC forced alignment ---------------

@@ -105,6 +105,15 @@ int host_ctc_beam_hot(const float* blank_lp, int64_t blank_stride, const int64_t
                       int blank, int W, int N, const int32_t* hw_ids, const int32_t* hw_lens, int n_hw, float boost,
                       int64_t* out_ids, int32_t* out_len, double* out_score, int32_t* out_matched, double* out_loglik, int cap);
 
+// host_ctc_beam_hot with a language model fused in (paraformer_hip.h "CTC language model"; the definition is
+// tests/ctcbeam_lm_ref.py): score = (lse(pb, pnb) + boost * matched) + lm_sum in the re-ordered list, out_lm [N] (0) next to
+// out_loglik.  A set that does not bias (boost == 0, no non-empty word) is allowed: matched 0.
+struct LmImage;
+int host_ctc_beam_lm(const float* blank_lp, int64_t blank_stride, const int64_t* ids, const float* val, const int32_t* n, int T, int K,
+                     int blank, int W, int N, const int32_t* hw_ids, const int32_t* hw_lens, int n_hw, float boost, int64_t* out_ids,
+                     int32_t* out_len, double* out_score, int32_t* out_matched, double* out_loglik, int cap, const LmImage& lm, float alpha,
+                     float beta, int lm_flags, double* out_lm);
+
 // ---- CTC forced alignment of one utterance and one target (paraformer_hip.h "CTC forced alignment"; tests/ctcalign_ref.py) ----
 // The host twin of k_ctcalign.hip: lp [T, ld] log-prob rows (V read per row), y [U] ids in [1, V) (PF_ERR_INVALID_ARG
 // otherwise; U > PF_ALIGN_MAX_TOKENS is PF_ERR_CAPACITY).  *path_score: the float32 Viterbi score, *loglik: the float64 log of

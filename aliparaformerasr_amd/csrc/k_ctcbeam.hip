@@ -25,9 +25,16 @@
 // candidate inherits.  The select orders by key = total + boost * (m + pending depth) while pb / pnb stay unbiased, and after
 // the last frame one more rank-by-count over (total + boost * m, beam rank) gives the output order.  The kBias = false form
 // is the kernel as it was: every addition sits behind `if constexpr (kBias)`.
+//
+// Language model (kLm; the definition is tests/ctcbeam_lm_ref.py): a beam entry also carries its state in the
+// back-off automaton lm.cpp compiled and g, the weighted LM score of its prefix.  An extension takes one step of lm_dev.h — a
+// back-off walk with one bounded search of a sorted arc list per level — issued, like the hot-word read, before the merge scan;
+// a stay candidate inherits.  g is one more term of the select key and of the final score, pb / pnb stay unfused, and the
+// finish shares the biased form's rank-by-count pass.  The kLm = false forms are the kernel as it was.
 #include <type_traits>
 
 #include "kernels.h"
+#include "lm_dev.h"
 
 namespace pf {
 
@@ -79,14 +86,29 @@ struct BeamHotArgs {
   double* out_loglik;       // [B, N]
 };
 struct BeamNoArgs {};
+// the same for the language model: the image, the weights widened, whether finish takes the end-of-sentence step
+struct BeamLmArgs {
+  const int32_t* image;
+  double alpha, beta;
+  int eos;
+  double* out_lm;           // [B, N]
+  double* out_loglik;       // [B, N] (the biased form's own pointer when both are on)
+};
+struct BeamLmOnlyArgs { BeamLmArgs lm; };
+struct BeamHotLmArgs : BeamHotArgs { BeamLmArgs lm; };
+// what a candidate carries for the language model (its LM state and g), and the kernel's view of the image; empty without one
+template <bool kLm> struct BeamLmCand { int ls = 0; double g = 0.0; };
+template <> struct BeamLmCand<false> {};
+template <bool kBias, bool kLm>
+using BeamExtraArgs = std::conditional_t<kLm, std::conditional_t<kBias, BeamHotLmArgs, BeamLmOnlyArgs>, std::conditional_t<kBias, BeamHotArgs, BeamNoArgs>>;
 
-template <int kBeamThreads, bool kBias>
+template <int kBeamThreads, bool kBias, bool kLm>
 __global__ __launch_bounds__(kBeamThreads) void ctc_beam_kernel(const float* blank_lp, int64_t blank_stride, const int64_t* ids,
                                                                 const float* val, const int32_t* n, const int32_t* len, int T,
                                                                 int K, int blank, int W, int N, int cap, int32_t* node_par,
                                                                 int32_t* node_tok, int32_t* out_ids, int32_t* out_len,
                                                                 double* out_score, int32_t* n_hyp,
-                                                                std::conditional_t<kBias, BeamHotArgs, BeamNoArgs> hot) {
+                                                                BeamExtraArgs<kBias, kLm> hot) {
   __shared__ BeamBuf bm[2];
   __shared__ double c_tot[kBeamCand];
   __shared__ double m_val[kBeamW];                 // what the frame's merged extensions add to entry q's stay candidate
@@ -94,7 +116,10 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_kernel(const float* bla
   __shared__ int f_id[2][PF_TOPK_MAX], f_n[2];
   // kBias: per beam entry the automaton state (with its depth in the top byte, as the table packs it) and the matched tokens,
   // double-buffered like the beam; the output order of the final pass
-  __shared__ int h_st[kBias ? 2 : 1][kBias ? kBeamW : 1], h_m[kBias ? 2 : 1][kBias ? kBeamW : 1], h_ord[kBias ? kBeamW : 1];
+  __shared__ int h_st[kBias ? 2 : 1][kBias ? kBeamW : 1], h_m[kBias ? 2 : 1][kBias ? kBeamW : 1], h_ord[kBias || kLm ? kBeamW : 1];
+  // kLm: per beam entry the LM state and g of its prefix, double-buffered alike
+  __shared__ int l_st[kLm ? 2 : 1][kLm ? kBeamW : 1];
+  __shared__ double l_g[kLm ? 2 : 1][kLm ? kBeamW : 1];
 
   const int b = blockIdx.x, tid = threadIdx.x;
   const int nb = min(max(len[b], 0), T);
@@ -102,12 +127,15 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_kernel(const float* bla
   const int K1 = K + 1;
   int32_t* npar = node_par + (int64_t)b * ((int64_t)T * W + 1);
   int32_t* ntok = node_tok + (int64_t)b * ((int64_t)T * W + 1);
+  [[maybe_unused]] std::conditional_t<kLm, LmView, BeamNoArgs> lv{};
+  if constexpr (kLm) lv = lm_view(hot.lm.image);
 
   if (tid == 0) {
     bm[0].pb[0] = 0.0; bm[0].pnb[0] = kNegInf; bm[0].hash[0] = 0x243F6A8885A308D3ull;
     bm[0].node[0] = 0; bm[0].par[0] = -1; bm[0].tok[0] = -1; bm[0].len[0] = 0;
     npar[0] = -1; ntok[0] = -1;
     if constexpr (kBias) { h_st[0][0] = 0; h_m[0][0] = 0; }
+    if constexpr (kLm) { l_st[0][0] = lv.start; l_g[0][0] = 0.0; }
   }
   if (tid < kBeamW) m_val[tid] = kNegInf;
   int n_nx = 0;                                    // n of frame t + 1, known one frame ahead so that its list can be prefetched
@@ -144,6 +172,7 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_kernel(const float* bla
     // 1. the candidate; an extension that meets a beam entry leaves its value in m_val
     double pb1 = kNegInf, pnb1 = kNegInf;
     int st1 = 0, m1 = 0;                           // kBias: the candidate's automaton state and matched tokens
+    [[maybe_unused]] BeamLmCand<kLm> lc;           // kLm: its LM state and g
     if (j < NC) {
       const double pb = B0.pb[i], pnb = B0.pnb[i];
       const double tot = beam_lse(pb, pnb);
@@ -151,6 +180,7 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_kernel(const float* bla
       if (s == 0) {
         pb1 = tot + lb;
         if constexpr (kBias) { st1 = h_st[cur][i]; m1 = h_m[cur][i]; }
+        if constexpr (kLm) { lc.ls = l_st[cur][i]; lc.g = l_g[cur][i]; }
         if (li > 0)
           for (int r = 0; r < nt; ++r)
             if (f_id[cur][r] == e) pnb1 = pnb + f_val[cur][r];
@@ -164,6 +194,10 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_kernel(const float* bla
               const int e = col >= 0 ? hot.table[(h_st[cur][i] & 0xFFFF) * hot.A + col] : 0;
               st1 = e & (int)0xFF00FFFF;
               m1 = h_m[cur][i] + ((e >> 16) & 0xFF);
+            }
+            if constexpr (kLm) {                   // the back-off walk, likewise independent of the scan
+              lc.g = l_g[cur][i];
+              lc.ls = lm_step(lv, l_st[cur][i], c, hot.lm.alpha, hot.lm.beta, true, lc.g);
             }
             const double value = base + f_val[cur][s - 1];
             const unsigned long long h = beam_hash(B0.hash[i], c);
@@ -197,6 +231,7 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_kernel(const float* bla
       my = beam_lse(pb1, pnb1);
       if constexpr (kBias) key = my + hot.boost * (double)(m1 + (int)((unsigned)st1 >> 24));
       else key = my;
+      if constexpr (kLm) key = key + lc.g;
       c_tot[j] = key;
     }
     __syncthreads();
@@ -213,6 +248,7 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_kernel(const float* bla
       const int r = rank;
       B1.pb[r] = pb1; B1.pnb[r] = pnb1;
       if constexpr (kBias) { h_st[nxt][r] = st1; h_m[nxt][r] = m1; }
+      if constexpr (kLm) { l_st[nxt][r] = lc.ls; l_g[nxt][r] = lc.g; }
       if (s == 0) {
         B1.hash[r] = B0.hash[i]; B1.node[r] = B0.node[i]; B1.par[r] = B0.par[i]; B1.tok[r] = B0.tok[i]; B1.len[r] = B0.len[i];
       } else {
@@ -235,11 +271,20 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_kernel(const float* bla
   const BeamBuf& F = bm[nb & 1];
   const int nh = bad ? 0 : min(N, nbeam);
   int src = tid;                                   // the beam entry that output slot tid shows
-  if constexpr (kBias) {
+  if constexpr (kBias || kLm) {
     // finish: score = total + boost * m (the pending part is revoked); a slot is again a count, over (score, beam rank)
     const int fb = nb & 1;
     double sc = kNegInf;
-    if (tid < nbeam && !bad) sc = beam_lse(F.pb[tid], F.pnb[tid]) + hot.boost * (double)h_m[fb][tid];
+    if constexpr (!kLm) {
+      if (tid < nbeam && !bad) sc = beam_lse(F.pb[tid], F.pnb[tid]) + hot.boost * (double)h_m[fb][tid];
+    } else if (tid < nbeam && !bad) {              // + g_final: the end-of-sentence step where asked for; kept for the output
+      sc = beam_lse(F.pb[tid], F.pnb[tid]);
+      if constexpr (kBias) sc = sc + hot.boost * (double)h_m[fb][tid];
+      double gf = l_g[fb][tid];
+      if (hot.lm.eos && lv.eos >= 0) lm_step(lv, l_st[fb][tid], lv.eos, hot.lm.alpha, hot.lm.beta, false, gf);
+      l_g[fb][tid] = gf;
+      sc = sc + gf;
+    }
     if (tid < kBeamW) c_tot[tid] = sc;
     __syncthreads();
     if (tid < nbeam && !bad) {
@@ -264,7 +309,18 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_kernel(const float* bla
       }
       out_len[o] = L;
       const double ll = beam_lse(F.pb[src], F.pnb[src]);
-      if constexpr (kBias) {
+      if constexpr (kLm) {                          // score = (ll + boost * m) + g_final, as finish ranked it
+        double sc = ll;
+        if constexpr (kBias) {
+          const int m = h_m[nb & 1][src];
+          sc = ll + hot.boost * (double)m;
+          hot.out_matched[o] = m;
+        }
+        const double gf = l_g[nb & 1][src];
+        out_score[o] = sc + gf;
+        hot.lm.out_lm[o] = gf;
+        hot.lm.out_loglik[o] = ll;
+      } else if constexpr (kBias) {
         const int m = h_m[nb & 1][src];
         out_score[o] = ll + hot.boost * (double)m;
         hot.out_matched[o] = m;
@@ -275,14 +331,18 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_kernel(const float* bla
     } else {
       out_len[o] = 0;
       out_score[o] = kNegInf;
-      if constexpr (kBias) { hot.out_matched[o] = 0; hot.out_loglik[o] = kNegInf; }
+      if constexpr (kLm) {
+        if constexpr (kBias) hot.out_matched[o] = 0;
+        hot.lm.out_lm[o] = 0.0;
+        hot.lm.out_loglik[o] = kNegInf;
+      } else if constexpr (kBias) { hot.out_matched[o] = 0; hot.out_loglik[o] = kNegInf; }
     }
   }
   for (int x = tid; x < N * cap; x += kBeamThreads) {
     const int h = x / cap, p = x - h * cap;
     int L = 0;
     if (h < nh) {
-      if constexpr (kBias) L = F.len[h_ord[h]];
+      if constexpr (kBias || kLm) L = F.len[h_ord[h]];
       else L = F.len[h];
     }
     if (p >= L) out_ids[(int64_t)b * N * cap + x] = -1;
@@ -297,10 +357,10 @@ void launch_ctc_beam(hipStream_t s, const float* blank_lp, int64_t blank_stride,
            PF_ERR_INVALID_ARG, "ctc_beam: 1 <= N <= W <= 64, 1 <= K <= 8");
   if (B == 0) return;
   if (W * (K + 1) <= 256)
-    hipLaunchKernelGGL((ctc_beam_kernel<256, false>), dim3((unsigned)B), dim3(256), 0, s, blank_lp, blank_stride, ids, val, n, len, T,
+    hipLaunchKernelGGL((ctc_beam_kernel<256, false, false>), dim3((unsigned)B), dim3(256), 0, s, blank_lp, blank_stride, ids, val, n, len, T,
                        K, blank, W, N, cap, node_par, node_tok, out_ids, out_len, out_score, n_hyp, BeamNoArgs{});
   else
-    hipLaunchKernelGGL((ctc_beam_kernel<1024, false>), dim3((unsigned)B), dim3(1024), 0, s, blank_lp, blank_stride, ids, val, n, len,
+    hipLaunchKernelGGL((ctc_beam_kernel<1024, false, false>), dim3((unsigned)B), dim3(1024), 0, s, blank_lp, blank_stride, ids, val, n, len,
                        T, K, blank, W, N, cap, node_par, node_tok, out_ids, out_len, out_score, n_hyp, BeamNoArgs{});
   PF_HIP(hipGetLastError());
 }
@@ -317,11 +377,48 @@ void launch_ctc_beam_hot(hipStream_t s, const float* blank_lp, int64_t blank_str
   if (B == 0) return;
   const BeamHotArgs hot{tok_col, table, V, A, (double)boost, out_matched, out_loglik};
   if (W * (K + 1) <= 256)
-    hipLaunchKernelGGL((ctc_beam_kernel<256, true>), dim3((unsigned)B), dim3(256), 0, s, blank_lp, blank_stride, ids, val, n, len, T,
+    hipLaunchKernelGGL((ctc_beam_kernel<256, true, false>), dim3((unsigned)B), dim3(256), 0, s, blank_lp, blank_stride, ids, val, n, len, T,
                        K, blank, W, N, cap, node_par, node_tok, out_ids, out_len, out_score, n_hyp, hot);
   else
-    hipLaunchKernelGGL((ctc_beam_kernel<1024, true>), dim3((unsigned)B), dim3(1024), 0, s, blank_lp, blank_stride, ids, val, n, len,
+    hipLaunchKernelGGL((ctc_beam_kernel<1024, true, false>), dim3((unsigned)B), dim3(1024), 0, s, blank_lp, blank_stride, ids, val, n, len,
                        T, K, blank, W, N, cap, node_par, node_tok, out_ids, out_len, out_score, n_hyp, hot);
+  PF_HIP(hipGetLastError());
+}
+
+// the fused forms: the language model alone (tok_col == nullptr) or together with a hot-word set
+void launch_ctc_beam_lm(hipStream_t s, const float* blank_lp, int64_t blank_stride, const int64_t* ids, const float* val,
+                        const int32_t* n, const int32_t* len, int B, int T, int K, int blank, int W, int N, int cap, int32_t* node_par,
+                        int32_t* node_tok, const int32_t* tok_col, int V, const int32_t* table, int A, float boost,
+                        const int32_t* lm_image, float alpha, float beta, int lm_flags, int32_t* out_ids, int32_t* out_len,
+                        double* out_score, int32_t* out_matched, double* out_loglik, double* out_lm, int32_t* n_hyp) {
+  PF_CHECK(N >= 1 && N <= W && W <= kBeamW && K >= 1 && K <= PF_TOPK_MAX && T >= 0 && cap >= 0 && blank_stride >= 1,
+           PF_ERR_INVALID_ARG, "ctc_beam: 1 <= N <= W <= 64, 1 <= K <= 8");
+  PF_CHECK(lm_image && out_lm && out_loglik && alpha >= 0.f && alpha <= 3.4028234e38f && beta >= -3.4028234e38f && beta <= 3.4028234e38f,
+           PF_ERR_INVALID_ARG, "ctc_beam_lm: a compiled model, alpha finite and >= 0, beta finite");
+  if (B == 0) return;
+  const BeamLmArgs lm{lm_image, (double)alpha, (double)beta, (lm_flags & PF_LM_EOS) != 0, out_lm, out_loglik};
+  const bool big = W * (K + 1) > 256;
+  if (tok_col) {
+    PF_CHECK(table && out_matched && V >= 1 && A >= 1 && boost > 0.f && boost <= 3.4028234e38f, PF_ERR_INVALID_ARG,
+             "ctc_beam_hot: a compiled hot-word table and a finite boost > 0");
+    BeamHotLmArgs x;
+    (BeamHotArgs&)x = BeamHotArgs{tok_col, table, V, A, (double)boost, out_matched, out_loglik};
+    x.lm = lm;
+    if (!big)
+      hipLaunchKernelGGL((ctc_beam_kernel<256, true, true>), dim3((unsigned)B), dim3(256), 0, s, blank_lp, blank_stride, ids, val, n, len,
+                         T, K, blank, W, N, cap, node_par, node_tok, out_ids, out_len, out_score, n_hyp, x);
+    else
+      hipLaunchKernelGGL((ctc_beam_kernel<1024, true, true>), dim3((unsigned)B), dim3(1024), 0, s, blank_lp, blank_stride, ids, val, n,
+                         len, T, K, blank, W, N, cap, node_par, node_tok, out_ids, out_len, out_score, n_hyp, x);
+  } else {
+    const BeamLmOnlyArgs x{lm};
+    if (!big)
+      hipLaunchKernelGGL((ctc_beam_kernel<256, false, true>), dim3((unsigned)B), dim3(256), 0, s, blank_lp, blank_stride, ids, val, n, len,
+                         T, K, blank, W, N, cap, node_par, node_tok, out_ids, out_len, out_score, n_hyp, x);
+    else
+      hipLaunchKernelGGL((ctc_beam_kernel<1024, false, true>), dim3((unsigned)B), dim3(1024), 0, s, blank_lp, blank_stride, ids, val, n,
+                         len, T, K, blank, W, N, cap, node_par, node_tok, out_ids, out_len, out_score, n_hyp, x);
+  }
   PF_HIP(hipGetLastError());
 }
 

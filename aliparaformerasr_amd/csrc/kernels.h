@@ -374,6 +374,19 @@ void launch_ctc_beam_hot(hipStream_t s, const float* blank_lp, int64_t blank_str
                          int32_t* node_par, int32_t* node_tok, const int32_t* tok_col, int V, const int32_t* table, int A, float boost,
                          int32_t* out_ids, int32_t* out_len, double* out_score, int32_t* out_matched, double* out_loglik,
                          int32_t* n_hyp);
+// The fused forms (language model; the definition is tests/ctcbeam_lm_ref.py): lm_image as lm_build leaves it (a device copy),
+// alpha finite and >= 0, beta finite, lm_flags PF_LM_EOS or 0.  tok_col == nullptr: the model alone (table / boost / out_matched
+// unused), else together with the hot-word set.  score = (total + boost * matched) + lm_sum in the re-ordered list; out_loglik
+// [B, N] (-inf) the unfused total, out_lm [B, N] (0) the weighted LM score of the hypothesis: every slot is written.
+void launch_ctc_beam_lm(hipStream_t s, const float* blank_lp, int64_t blank_stride, const int64_t* ids, const float* val,
+                        const int32_t* n, const int32_t* len, int B, int T, int K, int blank, int W, int N, int cap, int32_t* node_par,
+                        int32_t* node_tok, const int32_t* tok_col, int V, const int32_t* table, int A, float boost,
+                        const int32_t* lm_image, float alpha, float beta, int lm_flags, int32_t* out_ids, int32_t* out_len,
+                        double* out_score, int32_t* out_matched, double* out_loglik, double* out_lm, int32_t* n_hyp);
+// the model's walk on its own (k_lm.hip): ids [B, L], lens [B] -> g [B, L] float64 and state [B, L] after every token
+// p < lens[b] from the start state; later positions are not written
+void launch_lm_walk(hipStream_t s, const int32_t* image, const int32_t* ids, const int32_t* lens, int B, int L, float alpha, float beta,
+                    double* g, int32_t* state);
 // ------------------------------------------------------------------ CTC forced alignment -------
 // Per job (b, h) the best CTC alignment of the target tgt[b, h, 0 .. tlen[b, h]) to the log-prob rows lp[(b * T + t) * ld + v],
 // t < min(max(len[b], 0), T), v < V, and the float64 log of the sum over all of its alignments (k_ctcalign.hip; the definition

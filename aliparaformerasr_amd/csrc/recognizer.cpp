@@ -563,6 +563,23 @@ void Recognizer::SetHotwordBoost(float boost) {
   hot_boost_ = boost;
 }
 
+void Recognizer::SetLm(const std::string& arpa_path, float alpha, float beta, int flags) {
+  if (arpa_path.empty()) {
+    std::lock_guard<std::mutex> lk(lm_mu_);
+    lm_.reset();
+    return;
+  }
+  if (engine_kind_ != "sensevoicesmall")
+    throw Error(PF_ERR_UNSUPPORTED, "SetLm: only a SenseVoice model has a CTC head (paraformer / SeACo decoding is not a CTC search)");
+  lm_check_weights(alpha, beta, flags);
+  std::vector<const char*> toks;
+  for (auto& t : tokens_) toks.push_back(t.c_str());
+  std::shared_ptr<const LmImage> lm = lm_from_arpa(arpa_path, toks.data(), (int)toks.size(), -10.f, nullptr);   // throws before anything changes
+  std::lock_guard<std::mutex> lk(lm_mu_);
+  lm_ = std::move(lm);
+  lm_alpha_ = alpha; lm_beta_ = beta; lm_flags_ = flags;
+}
+
 void Recognizer::SetNBest(int N, int K) {
   if (N < 0 || N > PF_NBEST_MAX || K < 0 || K > PF_TOPK_MAX) throw Error(PF_ERR_INVALID_ARG, "SetNBest: N is 0 .. 64, K is 0 .. 8");
   if (N == 0) {
@@ -1151,7 +1168,17 @@ void Recognizer::Forward(const std::vector<Stream*>& streams) {
         e->set_ctc_hotwords(nullptr, nullptr, 0, 0.f);
       }
     }
+    if (sv && !mc.seaco) {
+      // the language model inside the beam search (SetLm beside SetCtcBeam): this engine uploads the image on first use
+      std::shared_ptr<const LmImage> lm;
+      float la = 0.f, lb = 0.f;
+      int lf = 0;
+      { std::lock_guard<std::mutex> lk(lm_mu_); lm = lm_; la = lm_alpha_; lb = lm_beta_; lf = lm_flags_; }
+      if (lm && (dflags & PF_DECODE_CTC_BEAM)) e->set_ctc_lm(lm, la, lb, lf);
+      else if (e->ctc_lm_on()) e->set_ctc_lm(nullptr, 0.f, 0.f, 0);
+    }
     const bool hot_on = sv && !mc.seaco && (dflags & PF_DECODE_CTC_BEAM) && e->ctc_hotwords_on();
+    const bool lm_on = sv && !mc.seaco && (dflags & PF_DECODE_CTC_BEAM) && e->ctc_lm_on();
     e->drop_thread_result();              // this call's result is read back under the same lease, not from a slot
     bool any_target = false;
     if (dflags & PF_DECODE_ALIGN) {
@@ -1240,6 +1267,7 @@ void Recognizer::Forward(const std::vector<Stream*>& streams) {
     // the beam search's hypotheses (SetCtcBeam): ids [B, Nb, b_cap], lengths, float64 totals
     std::vector<int64_t> b_ids; std::vector<int32_t> b_len, b_nhyp; std::vector<double> b_score;
     std::vector<int32_t> b_hot; std::vector<double> b_llsum;      // with hot words: matched tokens, the unbiased totals
+    std::vector<double> b_lm;                                     // with a language model: lm_sum (and the unfused totals above)
     int Nb = 0, b_cap = 0;
     if (dflags & PF_DECODE_CTC_BEAM) {
       int32_t len_max = 0, nb = 0;
@@ -1252,6 +1280,10 @@ void Recognizer::Forward(const std::vector<Stream*>& streams) {
       if (hot_on) {
         b_hot.resize((size_t)B * Nb); b_llsum.resize((size_t)B * Nb);
         e->fetch_ctc_beam_hot(b_hot.data(), b_llsum.data());
+      }
+      if (lm_on) {
+        b_lm.resize((size_t)B * Nb); b_llsum.resize((size_t)B * Nb);
+        e->fetch_ctc_beam_lm(b_lm.data(), b_llsum.data());
       }
     }
     // forced alignments (SetAlign): job 0 is the stream's own target when any stream of the batch has one, then the hypotheses
@@ -1337,6 +1369,7 @@ void Recognizer::Forward(const std::vector<Stream*>& streams) {
         a.score = b_score[x];
         a.ctc = true;
         if (!b_hot.empty()) { a.hot_tokens = b_hot[x]; a.loglik_sum = b_llsum[x]; }
+        if (!b_lm.empty()) { a.lm_sum = b_lm[x]; a.loglik_sum = b_llsum[x]; }
         a.ids.assign(b_ids.begin() + x * b_cap, b_ids.begin() + x * b_cap + b_len[x]);
         if (Ha >= a_hc + Nb) {
           const size_t j = (size_t)b * Ha + a_hc + i;

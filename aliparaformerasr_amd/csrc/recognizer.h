@@ -19,6 +19,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "lm.h"
 #include "copycrew.h"
 #include "engine.h"
 #include "hostutil.h"
@@ -88,6 +89,9 @@ struct Alternative {
   // the unbiased log of the alignments the search summed (0 / NaN without it)
   int hot_tokens = 0;
   double loglik_sum = std::nan("");
+  // with SetLm beside SetCtcBeam: the weighted LM score of the labeling, score = (loglik_sum + boost * hot_tokens) + lm_sum (NaN
+  // without it; loglik_sum is then filled with or without hot words)
+  double lm_sum = std::nan("");
   ResultEntity res;
 };
 // time_stamp_lfr6_onnx (OfflineRecognizer.cs:200-302); throws PF_ERR_RECOGNITION where the C#
@@ -199,6 +203,9 @@ class Recognizer : public std::enable_shared_from_this<Recognizer> {
   // SenseVoice only (paraformer_hip.h "CTC hot words"): boost per matched hot-word token inside the beam search of SetCtcBeam
   // (inert without it); 0 = off.  The hot words of a batch: the union of its streams' Hotwords, else the hot-word file's.
   void SetHotwordBoost(float s);
+  // SenseVoice: an ARPA n-gram LM fused into the beam search of SetCtcBeam (inert without it).  Loaded once against the token
+  // table; every engine of the pool uploads it on first use.  An empty path clears it.
+  void SetLm(const std::string& arpa_path, float alpha, float beta, int flags);
   // Long-audio recognition (paraformer_hip.h "Voice-activity segmentation"): cfg != null: every GetResults that follows cuts
   // its streams into speech pieces on the device (Engine::vad_segment_device over the resident audio), plans batches of similar
   // length (host_long_plan), forwards each batch over pointers into the streams' audio and stitches one result per stream.
@@ -307,6 +314,10 @@ class Recognizer : public std::enable_shared_from_this<Recognizer> {
   std::atomic<int> topk_k_{4};
   std::atomic<int> beam_w_{16}, beam_n_{16};
   std::atomic<float> hot_boost_{0.f};   // SetHotwordBoost
+  std::mutex lm_mu_;                    // SetLm: the model and its weights, read by every GetResults call
+  std::shared_ptr<const LmImage> lm_;
+  float lm_alpha_ = 0.f, lm_beta_ = 0.f;
+  int lm_flags_ = 0;
   std::atomic<bool> beam_on_{false};
   std::atomic<bool> align_on_{false};
   int extra_flags() const { return (nbest_n_ > 0 ? PF_DECODE_TOPK : 0) | (beam_on_ ? PF_DECODE_CTC_BEAM : 0) | (align_on_ ? PF_DECODE_ALIGN : 0); }

@@ -63,8 +63,11 @@ class CtcBeamResult:
     """The labelings a CTC prefix beam search kept (PF_DECODE_CTC_BEAM): n_hyp [B]; ids [B, N, cap] int64 (-1 past a
     hypothesis' length), len [B, N], score [B, N] float64 (the log of the summed alignments; -inf past n_hyp[b])."""
 
-    def __init__(self, n_hyp, ids, len_, score, matched=None, loglik_sum=None):
+    def __init__(self, n_hyp, ids, len_, score, matched=None, loglik_sum=None, lm_sum=None):
         self.n_hyp, self.ids, self.len, self.score = n_hyp, ids, len_, score
+        # language model (host_ctc_beam_lm / op_ctc_beam_lm), else None: lm_sum [B, N] float64, the weighted LM score of a
+        # labeling; score == (loglik_sum + boost * matched) + lm_sum
+        self.lm_sum = lm_sum
         self.N = score.shape[-1]
         # hot words (Engine.set_ctc_hotwords / host_ctc_beam_hot / op_ctc_beam_hot), else None: matched [B, N] int32, the
         # hot-word tokens a labeling completed; loglik_sum [B, N] float64 = score - boost * matched, the unbiased log of the sum
@@ -154,6 +157,98 @@ def host_ctc_beam_hot(blank_lp, ids, val, n, W, hotwords, boost, n_best=None, bl
                                           _i64p(oi), _i32p(ol), _dp(sc), cap, _i32p(nh), _i32p(hi), _i32p(hl), len(hl), float(boost),
                                           _i32p(om), _dp(oll)))
     return CtcBeamResult(nh, oi, ol, sc, om, oll)
+
+
+class LanguageModel:
+    """A back-off n-gram language model compiled into the flat image the beam search walks (pf_host_lm_build /
+    pf_host_lm_from_arpa; see "CTC language model" in the header).  ngrams: {tuple of ids: (logp, backoff or None)} with
+    natural-log float32 weights; or LanguageModel.from_arrays / from_arpa.  Release with close() (an engine that uploaded it
+    keeps its own reference)."""
+
+    def __init__(self, order, ngrams, V, bos=-1, eos=-1, unk=-1, oov=-10.0, transparent=(), _handle=None):
+        self._lib = N.load()
+        self.dropped = 0
+        self._h = _handle
+        if _handle is None:
+            by_k = [[w for w in ngrams if len(w) == k] for k in range(1, int(order) + 1)]
+            if sum(len(x) for x in by_k) != len(ngrams):
+                raise ValueError("an n-gram of order 0 or above the model's order")
+            flat = [w for x in by_k for w in x]
+            self._h = self._build(order, [len(x) for x in by_k], [c for w in flat for c in w], [ngrams[w][0] for w in flat],
+                                  [np.nan if ngrams[w][1] is None else ngrams[w][1] for w in flat], V, bos, eos, unk, oov, transparent)
+        o, s, a, b = C.c_int32(), C.c_int64(), C.c_int64(), C.c_int64()
+        N.check(self._lib.pf_host_lm_info(self._h, o, s, a, b))
+        self.order, self.states, self.arcs, self.image_bytes = o.value, s.value, a.value, b.value
+
+    @staticmethod
+    def _build(order, counts, ids, logp, backoff, V, bos, eos, unk, oov, transparent):
+        counts = np.ascontiguousarray(counts, dtype=np.int64).reshape(-1)
+        ids = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        logp = np.ascontiguousarray(logp, dtype=np.float32).reshape(-1)
+        bo = np.ascontiguousarray(backoff, dtype=np.float32).reshape(-1)
+        tr = np.ascontiguousarray(list(transparent), dtype=np.int32).reshape(-1)
+        h = C.c_void_p()
+        N.check(N.load().pf_host_lm_build(int(order), _i64p(counts), _i32p(ids), _fp(logp), _fp(bo), int(V), int(bos), int(eos), int(unk),
+                                          float(oov), _i32p(tr), len(tr), C.byref(h)))
+        return h
+
+    @classmethod
+    def from_arrays(cls, order, counts, ids, logp, backoff, V, bos=-1, eos=-1, unk=-1, oov=-10.0, transparent=()):
+        """The builder's own argument form: counts [order], then per listed n-gram (all 1-grams first) its ids flattened, logp
+        and backoff (NaN: none)."""
+        return cls(0, {}, 0, _handle=cls._build(order, counts, ids, logp, backoff, V, bos, eos, unk, oov, transparent))
+
+    @classmethod
+    def from_arpa(cls, path, tokens, oov=-10.0):
+        """ARPA text against a token table (list of str): words map to ids by exact equality; .dropped counts the n-grams left
+        out because a word is not in the table."""
+        arr = (C.c_char_p * len(tokens))(*[t.encode("utf-8") for t in tokens])
+        h, d = C.c_void_p(), C.c_int64()
+        N.check(N.load().pf_host_lm_from_arpa(str(path).encode("utf-8"), arr, len(tokens), float(oov), d, C.byref(h)))
+        lm = cls(0, {}, 0, _handle=h)
+        lm.dropped = d.value
+        return lm
+
+    def score(self, ids, alpha=1.0, beta=0.0, flags=0):
+        """The plain walk over ids (pf_host_lm_score): (g, state, g_pos [n] float64, state_pos [n] int32)."""
+        y = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        g, st = C.c_double(), C.c_int32()
+        gp, sp = np.zeros(len(y), np.float64), np.zeros(len(y), np.int32)
+        N.check(self._lib.pf_host_lm_score(self._h, _i32p(y), len(y), float(alpha), float(beta), int(flags), g, st, _dp(gp), _i32p(sp)))
+        return g.value, st.value, gp, sp
+
+    def close(self):
+        if self._h is not None:
+            self._lib.pf_lm_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def host_ctc_beam_lm(blank_lp, ids, val, n, W, lm, alpha, beta, flags=0, hotwords=(), boost=0.0, n_best=None, blank=0, cap=None,
+                     blank_stride=1) -> CtcBeamResult:
+    """host_ctc_beam_hot with a LanguageModel fused in (pf_host_ctc_beam_lm): ONE utterance in host code -> CtcBeamResult with
+    B = 1, matched, loglik_sum and lm_sum filled.  An empty hot-word set is allowed."""
+    y = np.ascontiguousarray(ids, dtype=np.int64)
+    v = _f32(val)
+    nn = np.ascontiguousarray(n, dtype=np.int32)
+    lb = _f32(blank_lp).reshape(-1)
+    T, K = y.shape
+    n_best = W if n_best is None else n_best
+    cap = max(T, 1) if cap is None else cap
+    hi, hl = _hot_arrays(hotwords)
+    nb = max(n_best, 0)
+    oi, ol, sc = np.zeros((1, nb, cap), np.int64), np.zeros((1, nb), np.int32), np.zeros((1, nb), np.float64)
+    om, oll, olm = np.zeros((1, nb), np.int32), np.zeros((1, nb), np.float64), np.zeros((1, nb), np.float64)
+    nh = np.zeros(1, np.int32)
+    N.check(N.load().pf_host_ctc_beam_lm(_fp(lb), int(blank_stride), _i64p(y), _fp(v), _i32p(nn), T, K, int(blank), int(W), int(n_best),
+                                         _i64p(oi), _i32p(ol), _dp(sc), cap, _i32p(nh), _i32p(hi), _i32p(hl), len(hl), float(boost),
+                                         _i32p(om), _dp(oll), lm._h, float(alpha), float(beta), int(flags), _dp(olm)))
+    return CtcBeamResult(nh, oi, ol, sc, om, oll, olm)
 
 
 class AlignResult:
@@ -321,7 +416,7 @@ def _fetch_topk(lib, h, B, L):
     return TopkResult(ids, val, n)
 
 
-def _fetch_ctc_beam(lib, h, B, n_best, hot=False):
+def _fetch_ctc_beam(lib, h, B, n_best, hot=False, lm=False):
     nh = np.zeros(B, np.int32)
     mx = C.c_int32()
     N.check(lib.pf_fetch_ctc_beam(h, None, None, None, 0, _i32p(nh), mx))
@@ -330,12 +425,15 @@ def _fetch_ctc_beam(lib, h, B, n_best, hot=False):
     ln = np.zeros((B, n_best), np.int32)
     sc = np.zeros((B, n_best), np.float64)
     N.check(lib.pf_fetch_ctc_beam(h, _i64p(ids), _i32p(ln), _dp(sc), cap, None, None))
-    if not hot:
+    if not hot and not lm:
         return CtcBeamResult(nh, ids, ln, sc)
-    m = np.zeros((B, n_best), np.int32)
-    ll = np.zeros((B, n_best), np.float64)
-    N.check(lib.pf_fetch_ctc_beam_hot(h, _i32p(m), _dp(ll)))
-    return CtcBeamResult(nh, ids, ln, sc, m, ll)
+    m, ll, g = np.zeros((B, n_best), np.int32), np.zeros((B, n_best), np.float64), None
+    if hot:
+        N.check(lib.pf_fetch_ctc_beam_hot(h, _i32p(m), _dp(ll)))
+    if lm:
+        g = np.zeros((B, n_best), np.float64)
+        N.check(lib.pf_fetch_ctc_beam_lm(h, _dp(g), _dp(ll)))
+    return CtcBeamResult(nh, ids, ln, sc, m, ll, g)
 
 
 def _fetch_align(lib, h, B):
@@ -380,7 +478,7 @@ def _collect_result(lib, fetch_fn, call, B, want_logits, decode=None):
         topk = _fetch_topk(lib, decode[0], B, L)
     beam = None
     if decode is not None and decode[1] & N.PF_DECODE_CTC_BEAM:
-        beam = _fetch_ctc_beam(lib, decode[0], B, decode[2], len(decode) > 3 and decode[3])
+        beam = _fetch_ctc_beam(lib, decode[0], B, decode[2], len(decode) > 3 and decode[3], len(decode) > 4 and decode[4])
     align = None
     if decode is not None and decode[1] & N.PF_DECODE_ALIGN:
         align = _fetch_align(lib, decode[0], B)
@@ -411,6 +509,7 @@ class Engine:
         self._decode = 0
         self._beam_n = 16
         self._hot = False
+        self._lm = None
 
     def close(self):
         if getattr(self, "_h", None):
@@ -450,7 +549,7 @@ class Engine:
     # ---- forward ------------------------------------------------------------
     def _collect(self, call, B, want_logits):
         return _collect_result(self._lib, lambda o: self._lib.pf_fetch(self._h, o), call, B, want_logits,
-                               (self._h, self._decode, self._beam_n, self._hot))
+                               (self._h, self._decode, self._beam_n, self._hot, self._lm is not None))
 
     def set_decode(self, flags: int):
         """Decoding extras of the forwards that follow (_native.PF_DECODE_SCORES | PF_DECODE_CTC; 0 = off, the reference
@@ -498,6 +597,7 @@ class Engine:
 
     host_ctc_beam = staticmethod(host_ctc_beam)
     host_ctc_beam_hot = staticmethod(host_ctc_beam_hot)
+    host_ctc_beam_lm = staticmethod(host_ctc_beam_lm)
 
     def set_ctc_hotwords(self, hotwords, boost: float):
         """The hot-word set (sequences of token ids in [1, V)) and the boost per matched token (>= 0) of the forwards that
@@ -506,6 +606,13 @@ class Engine:
         hi, hl = _hot_arrays(hotwords)
         N.check(self._lib.pf_engine_set_ctc_hotwords(self._h, _i32p(hi), _i32p(hl), len(hl), float(boost)))
         self._hot = float(np.float32(boost)) > 0 and any(len(w) > 0 for w in hotwords)
+
+    def set_ctc_lm(self, lm, alpha: float = 0.5, beta: float = 0.0, flags: int = 0):
+        """The LanguageModel of the forwards that follow with its weight alpha >= 0, the per-token bonus beta and flags
+        (_native.PF_LM_EOS) (pf_engine_set_ctc_lm; SenseVoice only); None clears it.  With a model installed PF_DECODE_CTC_BEAM
+        runs the fused search: BatchResult.beam comes in the fused order with lm_sum and loglik_sum (matched 0 without hot words)."""
+        N.check(self._lib.pf_engine_set_ctc_lm(self._h, None if lm is None else lm._h, float(alpha), float(beta), int(flags)))
+        self._lm = lm
 
     def op_ctc_beam_hot(self, blank_lp, ids, val, n, lens, W, hotwords, boost, n_best=None, blank=0, cap=None, out=None) -> CtcBeamResult:
         """op_ctc_beam with a hot-word set and a boost: the biased form of the kernel on caller data.  out = (ids, len, score,
@@ -528,6 +635,41 @@ class Engine:
                                              int(n_best), _i64p(oi), _i32p(ol), _dp(sc), cap, _i32p(nh), _i32p(hi), _i32p(hl),
                                              len(hl), float(boost), _i32p(om), _dp(oll)))
         return CtcBeamResult(nh, oi, ol, sc, om, oll)
+
+    def op_ctc_beam_lm(self, blank_lp, ids, val, n, lens, W, lm, alpha, beta, flags=0, hotwords=(), boost=0.0, n_best=None, blank=0,
+                       cap=None, out=None) -> CtcBeamResult:
+        """op_ctc_beam_hot with a LanguageModel fused in: the kLm forms of the kernel on caller data.  out = (ids, len, score,
+        n_hyp, matched [B, N] int32, loglik_sum [B, N] float64, lm_sum [B, N] float64): write into these arrays."""
+        y = np.ascontiguousarray(ids, dtype=np.int64)
+        v = _f32(val)
+        nn = np.ascontiguousarray(n, dtype=np.int32)
+        lb = _f32(blank_lp)
+        ln = np.ascontiguousarray(lens, dtype=np.int32)
+        B, T, K = y.shape
+        n_best = W if n_best is None else n_best
+        cap = max(T, 1) if cap is None else cap
+        hi, hl = _hot_arrays(hotwords)
+        nb = max(n_best, 0)
+        if out is None:
+            out = (np.zeros((B, nb, cap), np.int64), np.zeros((B, nb), np.int32), np.zeros((B, nb), np.float64), np.zeros(B, np.int32),
+                   np.zeros((B, nb), np.int32), np.zeros((B, nb), np.float64), np.zeros((B, nb), np.float64))
+        oi, ol, sc, nh, om, oll, olm = out
+        N.check(self._lib.pf_op_ctc_beam_lm(self._h, _fp(lb), _i64p(y), _fp(v), _i32p(nn), _i32p(ln), B, T, K, int(blank), int(W),
+                                            int(n_best), _i64p(oi), _i32p(ol), _dp(sc), cap, _i32p(nh), _i32p(hi), _i32p(hl), len(hl),
+                                            float(boost), _i32p(om), _dp(oll), lm._h, float(alpha), float(beta), int(flags), _dp(olm)))
+        return CtcBeamResult(nh, oi, ol, sc, om, oll, olm)
+
+    def op_lm_score(self, lm, ids, lens, alpha=1.0, beta=0.0, out=None):
+        """lm_walk_kernel on caller data (pf_op_lm_score): ids [B, L] int32, lens [B] -> (g [B, L] float64, state [B, L] int32)
+        after every token p < lens[b]; positions past a length keep what `out` = (g, state) held."""
+        y = np.ascontiguousarray(ids, dtype=np.int32)
+        ln = np.ascontiguousarray(lens, dtype=np.int32)
+        B, L = y.shape
+        if out is None:
+            out = (np.zeros((B, L), np.float64), np.zeros((B, L), np.int32))
+        g, st = out
+        N.check(self._lib.pf_op_lm_score(self._h, lm._h, _i32p(y), _i32p(ln), B, L, float(alpha), float(beta), _dp(g), _i32p(st)))
+        return g, st
 
     def op_ctc_beam(self, blank_lp, ids, val, n, lens, W, n_best=None, blank=0, cap=None, out=None) -> CtcBeamResult:
         """The pipeline's beam search kernel on caller data: blank_lp [B, T], ids / val [B, T, K], n [B, T], lens [B].

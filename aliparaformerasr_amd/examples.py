@@ -1,7 +1,7 @@
 """Command-line harness mirroring AliParaformerAsr.Examples (`-type offline` and `-type online`).
 
     python -m aliparaformerasr_amd.examples -type offline -method batch -base <dir> -model <name> \
-        [-accuracy int8] [-threads 2] [-decode ctc|frames] [-intake host|device] [-nbest N [-topk K] [-beam W [-hotboost S]]] [-align FILE|beam] [-vad [key=value,...]] -files a.wav b.wav
+        [-accuracy int8] [-threads 2] [-decode ctc|frames] [-intake host|device] [-nbest N [-topk K] [-beam W [-hotboost S] [-lm FILE [-lmweight A] [-lmbonus B] [-lmeos]]]] [-align FILE|beam] [-vad [key=value,...]] -files a.wav b.wav
     python -m aliparaformerasr_amd.examples -type online -method one -base <dir> -model <name> -files a.wav
 
 Mirrors (file:line in /root/reference/AliParaformerAsr.Examples):
@@ -30,6 +30,9 @@ hypotheses, one `nbest[i] score:<sum of log-probs> text:<text>` line each, best 
 beam search of width W in the same form; the score is the log of the summed alignments.
 `-hotboost S` (with `-nbest N -beam W`; OfflineRecognizer.SetHotwordBoost) biases that search towards the model directory's
 `hotword*.txt` by S per matched token; each `nbest[i]` line then ends in ` hot:<matched tokens> loglik_sum:<unbiased score>`.
+`-lm FILE [-lmweight A] [-lmbonus B] [-lmeos]` (with `-nbest N -beam W`; OfflineRecognizer.SetLm) fuses the ARPA n-gram language
+model FILE into that search with weight A (default 0.5), per-token bonus B (default 0) and, with `-lmeos`, the end-of-sentence
+step; each `nbest[i]` line then ends in ` hot:<matched tokens> lm:<lm_sum> loglik_sum:<unfused score>`.
 `-align FILE` (offline, SenseVoice models; OfflineRecognizer.SetAlign) aligns a known text to each input file: FILE holds one
 line of space-separated token ids per file of `-files`, in their order (an empty line: no target; ids, not text — the
 tokenizer is not part of this package), and under each result line goes
@@ -148,7 +151,10 @@ def _pairs(ts) -> str:
 def _nbest_lines(stream, align=False) -> list:
     out = []
     for i, a in enumerate(stream.Alternatives):
-        hot = '' if a.LogLikSum is None else ' hot:%d loglik_sum:%.6f' % (a.HotwordTokens, a.LogLikSum)
+        if a.LmSum is not None:
+            hot = ' hot:%d lm:%.6f loglik_sum:%.6f' % (a.HotwordTokens, a.LmSum, a.LogLikSum)
+        else:
+            hot = '' if a.LogLikSum is None else ' hot:%d loglik_sum:%.6f' % (a.HotwordTokens, a.LogLikSum)
         out.append('nbest[%d] score:%.6f text:%s%s' % (i, a.Score, a.Text, hot))
         if align and a.LogLik is not None:
             out.append('align[%d] loglik:%.6f pairs:%s' % (i, a.LogLik, _pairs(a.Timestamps)))
@@ -208,7 +214,7 @@ def read_align_file(path: str) -> list:
 
 def offline_recognizer(method="one", model="paraformer-seaco-large-zh-timestamp-onnx-offline", accuracy="int8",
                        threads=2, files=None, base=None, out=sys.stdout, decode="frames", intake="host", nbest=0, topk=4,
-                       beam=0, align=None, hotboost=0.0, vad=None):
+                       beam=0, align=None, hotboost=0.0, vad=None, lm=None, lmweight=0.5, lmbonus=0.0, lmeos=False):
     from .offline_recognizer import OfflineRecognizer
     base = base or os.getcwd()
     sel = select_model_files(base, model, accuracy)
@@ -223,6 +229,8 @@ def offline_recognizer(method="one", model="paraformer-seaco-large-zh-timestamp-
         rec.SetCtcBeam(nbest, beam, topk)
         if hotboost:
             rec.SetHotwordBoost(hotboost)
+        if lm:
+            rec.SetLm(lm, lmweight, lmbonus, 1 if lmeos else 0)
     elif nbest:
         rec.SetNBest(nbest, topk)
     if vad is not None:
@@ -441,6 +449,22 @@ def parse_args(argv, env=None):
             if not (0.0 <= v < float("inf")):
                 raise ValueError("The hotboost value must be a finite number >= 0")
             cfg["hotboost"] = v
+        elif a == "-lm":
+            i += 1
+            if i >= len(argv) or argv[i].startswith("-"):
+                raise ValueError("-lm takes an ARPA file")
+            cfg["lm"] = argv[i]
+        elif a in ("-lmweight", "-lmbonus"):
+            try:
+                i += 1
+                v = float(argv[i])
+            except (IndexError, ValueError):
+                v = float("nan")
+            if not (abs(v) < float("inf")) or (a == "-lmweight" and v < 0):
+                raise ValueError("The %s value must be a finite number%s" % (a[1:], " >= 0" if a == "-lmweight" else ""))
+            cfg[a[1:]] = v
+        elif a == "-lmeos":
+            cfg["lmeos"] = True
         elif a == "-align":
             i += 1
             if i >= len(argv) or argv[i].startswith("-"):
@@ -477,6 +501,10 @@ def parse_args(argv, env=None):
         raise ValueError("The beam value must not be smaller than the nbest value")
     if "hotboost" in cfg and "beam" not in cfg:
         raise ValueError("-hotboost needs -nbest N -beam W")
+    if "lm" in cfg and "beam" not in cfg:
+        raise ValueError("-lm needs -nbest N -beam W")
+    if any(k in cfg for k in ("lmweight", "lmbonus", "lmeos")) and "lm" not in cfg:
+        raise ValueError("-lmweight, -lmbonus and -lmeos go with -lm FILE")
     if "nbest" in cfg and cfg["recognizerType"] != "offline":
         raise ValueError("-nbest is an offline option")
     if "align" in cfg and cfg["recognizerType"] != "offline":
@@ -505,7 +533,8 @@ def main(argv=None):
         offline_recognizer(cfg["methodType"], cfg["modelName"], cfg["modelAccuracy"], cfg["threads"], cfg["files"],
                            cfg["modelBasePath"] or None, decode=cfg.get("decode", "frames"), intake=cfg.get("intake", "host"),
                            nbest=cfg.get("nbest", 0), topk=cfg.get("topk", 4), beam=cfg.get("beam", 0), align=cfg.get("align"),
-                           hotboost=cfg.get("hotboost", 0.0), vad=cfg.get("vad"))
+                           hotboost=cfg.get("hotboost", 0.0), vad=cfg.get("vad"), lm=cfg.get("lm"), lmweight=cfg.get("lmweight", 0.5),
+                           lmbonus=cfg.get("lmbonus", 0.0), lmeos=cfg.get("lmeos", False))
     else:
         print("the recognizer type must be online or offline")
         return 2

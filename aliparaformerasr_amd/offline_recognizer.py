@@ -80,6 +80,9 @@ class Alternative:
     # HotwordTokens) and the unbiased log of the alignments the search summed (0 / None when the search ran unbiased)
     HotwordTokens: int = 0
     LogLikSum: Optional[float] = None
+    # OfflineRecognizer.SetLm beside SetCtcBeam: the weighted language-model score of the labeling, Score = (LogLikSum + boost *
+    # HotwordTokens) + LmSum (None when the search ran without a model; LogLikSum is then filled with or without hot words)
+    LmSum: Optional[float] = None
 
 
 @dataclass
@@ -246,8 +249,11 @@ class OfflineStream:
             _ck(self._lib.pf_stream_alternative_timestamps(self._h, i, C.byref(pt), nts, C.byref(ll)))
             hm, hs = C.c_int32(), C.c_double()
             _ck(self._lib.pf_stream_alternative_hot(self._h, i, hm, hs))
+            lm = C.c_double()
+            _ck(self._lib.pf_stream_alternative_lm(self._h, i, lm, None))
             out.append(Alternative(Ids=[p[m] for m in range(k.value)], Score=sc.value, HotwordTokens=hm.value,
                                    LogLikSum=None if hs.value != hs.value else hs.value,
+                                   LmSum=None if lm.value != lm.value else lm.value,
                                    Text=(txt.value or b"").decode("utf-8"), Tokens=toks,
                                    Timestamps=[[pt[2 * j], pt[2 * j + 1]] for j in range(nts.value)],
                                    LogLik=None if ll.value != ll.value else ll.value))
@@ -404,6 +410,14 @@ class OfflineRecognizer:
         needed.  Alternatives then come in the biased order, each with Score, HotwordTokens and LogLikSum; Text and Tokens stay
         as they are."""
         _ck(self._lib.pf_recognizer_set_hotword_boost(self._h, float(s)))
+
+    def SetLm(self, arpaPath, alpha: float = 0.5, beta: float = 0.0, flags: int = 0) -> None:
+        """SenseVoice models: an ARPA n-gram language model fused into the beam search of SetCtcBeam (inert without it; None
+        or "" clears it) with weight alpha >= 0, per-token bonus beta and flags (_native.PF_LM_EOS: add the end-of-sentence
+        step).  The file is read once against the token table; each engine of the pool uploads it on first use.
+        Alternatives then come in the fused order, each with Score, LmSum and LogLikSum; Text and Tokens stay as they are."""
+        path = None if not arpaPath else str(arpaPath).encode("utf-8")
+        _ck(self._lib.pf_recognizer_set_lm(self._h, path, float(alpha), float(beta), int(flags)))
 
     def SetAlign(self, on: bool = True) -> None:
         """SenseVoice models: CTC forced alignment on the device for every GetResults that follows (off by default).  A

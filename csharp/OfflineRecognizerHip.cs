@@ -188,6 +188,8 @@ namespace AliParaformerAsr.Hip
                     ParaformerHip.Check(ParaformerHip.pf_stream_alternative_hot(Handle, i, out int hot, out double llSum));
                     a.HotwordTokens = hot;
                     a.LogLikSum = llSum;
+                    ParaformerHip.Check(ParaformerHip.pf_stream_alternative_lm(Handle, i, out double lmSum, out double _));
+                    a.LmSum = lmSum;
                     r.Add(a);
                 }
                 return r;
@@ -293,6 +295,9 @@ namespace AliParaformerAsr.Hip
         /// HotwordTokens) and the unbiased log of the alignments the search summed (0 / NaN when the search ran unbiased).</summary>
         public int HotwordTokens;
         public double LogLikSum = double.NaN;
+        /// <summary>SetLm beside SetCtcBeam: the weighted language-model score of the labeling, Score = (LogLikSum + boost *
+        /// HotwordTokens) + LmSum (NaN when the search ran without a model; LogLikSum is then filled with or without hot words).</summary>
+        public double LmSum = double.NaN;
     }
 
     /// <summary>OfflineStream.Alignment: where each id of a known text lies in the audio.  Ok = false: the target does not fit the
@@ -349,6 +354,13 @@ namespace AliParaformerAsr.Hip
         /// stream.Hotwords ids where sentencepiece pieces are needed.  Alternatives then come in the biased order, each with Score,
         /// HotwordTokens and LogLikSum; Text and Tokens stay as they are.</summary>
         public void SetHotwordBoost(float s) => ParaformerHip.Check(ParaformerHip.pf_recognizer_set_hotword_boost(_r, s));
+
+        /// <summary>Not in the reference: SenseVoice models only.  An ARPA n-gram language model fused into the beam search of
+        /// SetCtcBeam (inert without it; null or "" clears it) with weight alpha, per-token bonus beta and flags (1 = add the
+        /// end-of-sentence step).  The file is read once against the token table; each engine of the pool uploads it on first use.
+        /// Alternatives then come in the fused order, each with Score, LmSum and LogLikSum; Text and Tokens stay as they are.</summary>
+        public void SetLm(string? arpaPath, float alpha = 0.5f, float beta = 0f, int flags = 0) =>
+            ParaformerHip.Check(ParaformerHip.pf_recognizer_set_lm(_r, arpaPath, alpha, beta, flags));
 
         /// <summary>Not in the reference: SenseVoice models only.  CTC forced alignment on the device for every GetResults that
         /// follows (off by default): a stream with a target (OfflineStream.SetAlignIds) gets OfflineStream.Alignment, and with

@@ -127,6 +127,31 @@ namespace AliParaformerAsr.Native
                                                                       int T, int K, int blank, int W, int N, [Out] long[] outIds, [Out] int[] outLen,
                                                                       [Out] double[] outScore, int cap, [Out] int[] nHyp, int[]? hwIds, int[]? hwLens,
                                                                       int nHotwords, float boost, [Out] int[] outMatched, [Out] double[] outLoglik);
+        // CTC language model (additions to ABI 6): a back-off n-gram LM compiled on the host (pf_lm handle), its plain walk, and
+        // the fused forms of the beam search
+        internal const int PF_LM_ORDER_MAX = 8, PF_LM_IMAGE_BYTES_MAX = 1024 * 1024 * 1024, PF_LM_EOS = 1;
+        [DllImport(Lib)] internal static extern int pf_host_lm_build(int order, long[] nNgrams, int[]? ids, float[]? logp, float[]? backoff, int V, int bos,
+                                                                    int eos, int unk, float oov, int[]? transparent, int nTransparent, out IntPtr lm);
+        [DllImport(Lib)] internal static extern int pf_host_lm_from_arpa([MarshalAs(UnmanagedType.LPUTF8Str)] string path, IntPtr[] tokens, int nTokens,
+                                                                        float oov, out long nDropped, out IntPtr lm);
+        [DllImport(Lib)] internal static extern int pf_host_lm_info(IntPtr lm, out int order, out long nStates, out long nArcs, out long imageBytes);
+        [DllImport(Lib)] internal static extern int pf_host_lm_score(IntPtr lm, int[]? ids, int n, float alpha, float beta, int flags, out double g,
+                                                                    out int state, [Out] double[]? gPos, [Out] int[]? statePos);
+        [DllImport(Lib)] internal static extern void pf_lm_free(IntPtr lm);
+        [DllImport(Lib)] internal static extern int pf_engine_set_ctc_lm(IntPtr e, IntPtr lm, float alpha, float beta, int flags);
+        [DllImport(Lib)] internal static extern int pf_fetch_ctc_beam_lm(IntPtr e, [Out] double[]? lmSum, [Out] double[]? loglikSum);
+        [DllImport(Lib)] internal static extern int pf_host_ctc_beam_lm(float[] blankLp, long blankStride, long[] ids, float[] val, int[] n, int T, int K,
+                                                                       int blank, int W, int N, [Out] long[] outIds, [Out] int[] outLen,
+                                                                       [Out] double[] outScore, int cap, out int nHyp, int[]? hwIds, int[]? hwLens,
+                                                                       int nHotwords, float boost, [Out] int[] outMatched, [Out] double[] outLoglik,
+                                                                       IntPtr lm, float alpha, float beta, int flags, [Out] double[] outLm);
+        [DllImport(Lib)] internal static extern int pf_op_ctc_beam_lm(IntPtr e, float[] blankLp, long[] ids, float[] val, int[] n, int[] lens, int B,
+                                                                     int T, int K, int blank, int W, int N, [Out] long[] outIds, [Out] int[] outLen,
+                                                                     [Out] double[] outScore, int cap, [Out] int[] nHyp, int[]? hwIds, int[]? hwLens,
+                                                                     int nHotwords, float boost, [Out] int[] outMatched, [Out] double[] outLoglik,
+                                                                     IntPtr lm, float alpha, float beta, int flags, [Out] double[] outLm);
+        [DllImport(Lib)] internal static extern int pf_op_lm_score(IntPtr e, IntPtr lm, int[] ids, int[] lens, int B, int L, float alpha, float beta,
+                                                                  [Out] double[] g, [Out] int[] state);
         // CTC forced alignment (additions to ABI 6): PF_DECODE_ALIGN (SenseVoice; implies SCORES) aligns the targets set for the next
         // forward, and with PF_DECODE_CTC_BEAM the beam's hypotheses, to the log-prob rows: Viterbi path and log-likelihood per job
         internal const int PF_DECODE_ALIGN = 32;
@@ -207,6 +232,9 @@ namespace AliParaformerAsr.Native
                                                                      out int tokBegin, out int tokEnd, out IntPtr textUtf8);
         [DllImport(Lib)] internal static extern int pf_recognizer_set_hotword_boost(IntPtr r, float boost);
         [DllImport(Lib)] internal static extern int pf_stream_alternative_hot(IntPtr s, int i, out int hotwordTokens, out double loglikSum);
+        [DllImport(Lib)] internal static extern int pf_recognizer_set_lm(IntPtr r, [MarshalAs(UnmanagedType.LPUTF8Str)] string? arpaPath, float alpha,
+                                                                        float beta, int flags);
+        [DllImport(Lib)] internal static extern int pf_stream_alternative_lm(IntPtr s, int i, out double lmSum, out double loglikSum);
         [DllImport(Lib)] internal static extern int pf_stream_token_alternatives(IntPtr s, out IntPtr ids, out IntPtr val, out int nTokens, out int K);
         [DllImport(Lib)] internal static extern int pf_stream_num_alternatives(IntPtr s, out int n);
         [DllImport(Lib)] internal static extern int pf_stream_alternative(IntPtr s, int i, out IntPtr ids, out int nIds, out double score,

@@ -335,6 +335,81 @@ int pf_host_ctc_beam_hot(const float* blank_lp, int64_t blank_stride, const int6
                          int32_t cap, int32_t* n_hyp, const int32_t* hw_ids, const int32_t* hw_lens, int32_t n_hotwords, float boost,
                          int32_t* out_matched, double* out_loglik);
 
+/* ---- CTC language model (additions to ABI 6; nothing is launched, allocated or uploaded without a model) ----------------
+   Shallow fusion of a back-off n-gram language model into the CTC beam search above: the weighted LM score of a prefix is one
+   more term of the key the search selects by, so the model decides which prefixes survive a frame.  Opt-in, absent from the
+   reference.  The definition in Python is tests/ctcbeam_lm_ref.py.
+   THE MODEL: a back-off n-gram LM of order O (1 <= O <= PF_LM_ORDER_MAX) over token ids in [1, V).  Each listed n-gram has a
+   float32 natural-log probability, each listed n-gram of order < O may have a float32 natural-log back-off weight; the model
+   carries optional bos / eos / unk ids (-1: none; an unk must be a listed unigram), a float32 oov log-probability used when
+   there is no unk, and a set of TRANSPARENT ids.  All weights are finite.  n-grams whose prefix context is not listed are legal.
+   ONE STEP: g and the context h are functions of the label sequence alone.  Start: g = +0.0, h = (bos) with a bos, else ().
+   For each token c in order:
+     c transparent: nothing changes (no weight, no bonus, same h).
+     c no listed unigram: with an unk, c is replaced by unk for scoring and for the context; else g = (g + alpha * oov) + beta
+       and h = ().
+     otherwise take h' = the last min(|h|, O - 1) tokens of h and repeat: if h' . c is listed, g = g + alpha * logp(h' . c) and
+       stop; else, if h' is listed with a back-off, g = g + alpha * bo(h'); drop the first token of h' (the empty context ends
+       the walk at the unigram).  Then g = g + beta.  The new h is the longest suffix of h . c that is a listed n-gram of
+       order < O.
+   alpha >= 0 and beta are finite float32; every operand is widened to float64; alpha * x is the (exact) product of two widened
+   floats and every + one rounded float64 addition in exactly this order.  The definition, the host scorer and the kernels
+   give bit-equal g.  END OF SENTENCE: with PF_LM_EOS and an eos id one more step for eos, without beta, ends a hypothesis.
+   SEARCH: the beam search above (with the hot-word changes when a set is given) and one more term.
+     select   key = (total + boost * (m + d)) + g(prefix), the hot-word term only with a set; a candidate whose total is -inf
+              is still discarded; the W best by key stay, ties to the smaller candidate index; pb / pnb stay unfused.
+     finish   score = (lse(pb, pnb) + boost * m) + g_final; re-ordered by descending score, ties to the smaller beam rank;
+              per hypothesis ids, length, score, loglik_sum = lse(pb, pnb), lm_sum = g_final (and matched with hot words):
+              score == (loglik_sum + boost * matched) + lm_sum bit for bit.
+   alpha = beta = 0 gives the unfused lists and scores bit for bit.  Only ids in a frame's top-k list are candidates.
+   THE IMAGE: pf_host_lm_build compiles the model into one flat image of a back-off automaton: state 0 is the empty context
+   with a dense [V] lookup, every other state has an arc list sorted by token, a back-off state and weight, and next states
+   are precomputed.  Its layout is private (csrc/lm_dev.h).
+   OUT OF SCOPE: paraformer / SeACo (their decoder needs a position-synchronous search of its own; pf_host_lm_score /
+   pf_op_lm_score are the building block for re-ranking their n-best), pf_group forwards, neural LMs, binary LM formats. */
+#define PF_LM_ORDER_MAX 8
+#define PF_LM_IMAGE_BYTES_MAX (1024 * 1024 * 1024)
+#define PF_LM_EOS 1
+typedef struct pf_lm pf_lm;
+/* n_ngrams [order]; then per listed n-gram, all 1-grams first, then all 2-grams, ...: its k ids in `ids` (flattened), logp and
+   backoff (NaN: listed without a back-off weight; not read at the highest order); transparent: n_transparent ids in [0, V).
+   PF_ERR_INVALID_ARG: a duplicate n-gram, an id outside [1, V), a non-finite weight, an unk that is no listed unigram;
+   PF_ERR_CAPACITY: an image over PF_LM_IMAGE_BYTES_MAX.  *lm is released with pf_lm_free. */
+int pf_host_lm_build(int32_t order, const int64_t* n_ngrams, const int32_t* ids, const float* logp, const float* backoff, int32_t V,
+                     int32_t bos, int32_t eos, int32_t unk, float oov, const int32_t* transparent, int32_t n_transparent, pf_lm** lm);
+/* ARPA text against a token table (V = n_tokens).  Section counts are checked; each value is float32(strtod(text) * ln 10);
+   words map to ids by exact equality with the table (the first spelling wins); <s>, </s> and <unk> are recognised by spelling;
+   an n-gram with a word that is not in the table (or is id 0) is dropped and counted in *n_dropped (optional); every token
+   spelled <|...|> is transparent.  PF_ERR_INVALID_ARG with path:line for a malformed or truncated file, PF_ERR_IO when it
+   cannot be opened. */
+int pf_host_lm_from_arpa(const char* path, const char* const* tokens, int32_t n_tokens, float oov, int64_t* n_dropped, pf_lm** lm);
+/* each optional */
+int pf_host_lm_info(const pf_lm* lm, int32_t* order, int64_t* n_states, int64_t* n_arcs, int64_t* image_bytes);
+/* The plain walk: *g and *state after ids[0 .. n) from the start (PF_LM_EOS in flags: and the end-of-sentence step);
+   g_pos / state_pos [n]: after every token.  All four optional. */
+int pf_host_lm_score(const pf_lm* lm, const int32_t* ids, int32_t n, float alpha, float beta, int32_t flags, double* g, int32_t* state,
+                     double* g_pos, int32_t* state_pos);
+void pf_lm_free(pf_lm* lm);
+/* The model of the forwards that FOLLOW on this engine.  SenseVoice only (PF_ERR_UNSUPPORTED otherwise).  lm = NULL clears.  The
+   engine takes a reference of its own (pf_lm_free may follow at once) and uploads the image once, into a buffer of its own; a
+   call with the same model only updates alpha / beta / flags.  With a model installed a forward with PF_DECODE_CTC_BEAM runs
+   the fused search (there is no decode bit of its own), together with the hot-word set when one is installed;
+   pf_fetch_ctc_beam then returns the fused order and score, PF_DECODE_ALIGN aligns those hypotheses; token_ids, pf_fetch_scores,
+   pf_fetch_ctc and pf_fetch_topk are what they are without the model.  PF_ERR_INVALID_ARG: alpha negative or not finite, beta
+   not finite, an unknown flag (the installed model stays). */
+int pf_engine_set_ctc_lm(pf_engine* e, const pf_lm* lm, float alpha, float beta, int32_t flags);
+/* lm_sum [B, N] float64 (0 past n_hyp) and loglik_sum [B, N] float64 (-inf past n_hyp) of the last forward's hypotheses, each
+   optional, in pf_fetch_ctc_beam's order: score == (loglik_sum + boost * matched) + lm_sum bit for bit (matched: with a
+   hot-word set, pf_fetch_ctc_beam_hot).  Slot rules as pf_fetch_ctc_beam (call it before the pf_fetch that takes the ids).
+   PF_ERR_INVALID_ARG when that forward ran without a model. */
+int pf_fetch_ctc_beam_lm(pf_engine* e, double* lm_sum, double* loglik_sum);
+/* pf_host_ctc_beam_hot plus the model, alpha, beta and flags: the fused search for ONE utterance in plain host code.  An empty
+   hot-word set (n_hotwords == 0 or boost == 0) is allowed: out_matched is then 0.  out_lm [N] (0 past n_hyp) next to out_loglik. */
+int pf_host_ctc_beam_lm(const float* blank_lp, int64_t blank_stride, const int64_t* ids, const float* val, const int32_t* n, int32_t T,
+                        int32_t K, int32_t blank, int32_t W, int32_t N, int64_t* out_ids, int32_t* out_len, double* out_score,
+                        int32_t cap, int32_t* n_hyp, const int32_t* hw_ids, const int32_t* hw_lens, int32_t n_hotwords, float boost,
+                        int32_t* out_matched, double* out_loglik, const pf_lm* lm, float alpha, float beta, int32_t flags, double* out_lm);
+
 /* ---- CTC forced alignment (additions to ABI 6; nothing is launched or allocated without the flag) ----------------------
    PF_DECODE_ALIGN (pf_engine_set_decode; SenseVoice only, every math_mode; implies SCORES, not TOPK; independent of
    PF_DECODE_CTC; PF_ERR_UNSUPPORTED for a paraformer or SeACo model and for a pf_group forward): where the text is already
@@ -574,6 +649,17 @@ int pf_op_ctc_beam_hot(pf_engine* e, const float* blank_lp, const int64_t* ids, 
                        int32_t B, int32_t T, int32_t K, int32_t blank, int32_t W, int32_t N, int64_t* out_ids, int32_t* out_len,
                        double* out_score, int32_t cap, int32_t* n_hyp, const int32_t* hw_ids, const int32_t* hw_lens,
                        int32_t n_hotwords, float boost, int32_t* out_matched, double* out_loglik);
+/* the fused forms of the same kernel (see "CTC language model"): pf_op_ctc_beam_hot plus the model, alpha, beta, flags and
+   out_lm [B, N].  The image is uploaded into a buffer of its own on first use and kept while the same model is given. */
+int pf_op_ctc_beam_lm(pf_engine* e, const float* blank_lp, const int64_t* ids, const float* val, const int32_t* n, const int32_t* lens,
+                      int32_t B, int32_t T, int32_t K, int32_t blank, int32_t W, int32_t N, int64_t* out_ids, int32_t* out_len,
+                      double* out_score, int32_t cap, int32_t* n_hyp, const int32_t* hw_ids, const int32_t* hw_lens,
+                      int32_t n_hotwords, float boost, int32_t* out_matched, double* out_loglik, const pf_lm* lm, float alpha,
+                      float beta, int32_t flags, double* out_lm);
+/* lm_walk_kernel (csrc/k_lm.hip), the device twin of pf_host_lm_score: ids [B, L], lens [B] -> g [B, L] float64 and state
+   [B, L] after every token p < lens[b]; positions past a length are not written. */
+int pf_op_lm_score(pf_engine* e, const pf_lm* lm, const int32_t* ids, const int32_t* lens, int32_t B, int32_t L, float alpha, float beta,
+                   double* g, int32_t* state);
 /* exactly the pipeline's alignment kernel (k_ctcalign.hip) on caller arrays: lp [B * T, ld] (V read per row), tgt [B, H, cap]
    int32, tlen [B, H] (-1: skip the job; above cap or PF_ALIGN_MAX_TOKENS: ok = 0), lens [B] (clamped to 0 .. T; nothing at or
    beyond lens[b] is read, nor a target slot at or beyond tlen; an id outside [0, V) makes the job not ok).  Outputs as
@@ -912,6 +998,15 @@ int pf_stream_segment(pf_stream* s, int32_t i, int32_t* begin_ms, int32_t* end_m
                       int32_t* tok_end, const char** text_utf8);
 int pf_recognizer_set_hotword_boost(pf_recognizer* r, float boost);
 int pf_stream_alternative_hot(pf_stream* s, int32_t i, int32_t* hotword_tokens, double* loglik_sum);
+/* SenseVoice only (see "CTC language model"; PF_ERR_UNSUPPORTED otherwise).  An ARPA n-gram LM fused into the beam search of
+   pf_recognizer_set_ctc_beam with weight alpha, per-token bonus beta and flags (PF_LM_EOS); inert until
+   pf_recognizer_set_ctc_beam is set; arpa_path NULL or "" clears it.  The file is read once, against the recognizer's token
+   table (pf_host_lm_from_arpa with oov = -10); each engine of the pool uploads the image on first use.  Alternatives then come
+   in the fused order, each with its score (fused), lm_sum and loglik_sum through pf_stream_alternative_lm (NaN when the call
+   ran without a model); beside pf_recognizer_set_hotword_boost both terms enter one search.  Text and Tokens of the result
+   stay the greedy ones.  Errors as pf_host_lm_from_arpa and pf_engine_set_ctc_lm (the installed model stays). */
+int pf_recognizer_set_lm(pf_recognizer* r, const char* arpa_path, float alpha, float beta, int32_t flags);
+int pf_stream_alternative_lm(pf_stream* s, int32_t i, double* lm_sum, double* loglik_sum);
 int pf_stream_set_align_ids(pf_stream* s, const int64_t* ids, int32_t n);
 int pf_stream_alignment(pf_stream* s, const int32_t** begin_end, const float** tok_score, int32_t* n, float* path_score,
                         double* loglik, int32_t* ok);

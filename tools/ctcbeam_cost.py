@@ -3,7 +3,7 @@ flight), in ONE process: a step with PF_DECODE_TOPK alone and with the beam sear
 the device time of the `ctc_beam` class; and the host twin (pf_host_ctc_beam, one thread) over the same fetched lists and
 blank column, compared hypothesis by hypothesis with what the device kept.
 
-    python tools/ctcbeam_cost.py [--settings 16:4,64:8] [--steps 20] [--blocks 3] [--nbest 0] [--class-samples 1] [--hotwords]
+    python tools/ctcbeam_cost.py [--settings 16:4,64:8] [--steps 20] [--blocks 3] [--nbest 0] [--class-samples 1] [--hotwords] [--lm]
 
 `--settings` lists W:K pairs (N = W unless --nbest is given).  `--settings none` never touches the beam API and times the
 TOPK-alone legs only, so the same file also runs on a build that predates the flag (the parent's step time).
@@ -11,7 +11,12 @@ TOPK-alone legs only, so the same file also runs on a build that predates the fl
 `--hotwords` adds per setting a leg with a hot-word set installed (Engine.set_ctc_hotwords: 100 hot words of 2 .. 6 ids drawn
 from the unbiased hypotheses of the batch, boost 2): the biased step and `ctc_beam` class beside the unbiased ones in the same
 alternation, and the biased host twin (pf_host_ctc_beam_hot) over the same lists (profiles/ctcbeam_hot_cost.json, DESIGN
-§4.6f).  Without it nothing of the hot-word API is touched, so the file also runs on a build that predates it."""
+§4.6f).  Without it nothing of the hot-word API is touched, so the file also runs on a build that predates it.
+`--lm` adds per setting two legs with a language model installed (Engine.set_ctc_lm, alpha 0.5, beta 0.5, PF_LM_EOS): two
+synthetic 3-gram models made from the unbiased hypotheses of the batch and padded with random n-grams, `lm_small` whose image
+fits in the L2 and `lm_large` of at least --lm-large-mb (256) MB; the fused step and `ctc_beam` class beside the unfused ones in
+the same alternation, and the fused host twin (pf_host_ctc_beam_lm) over the same lists (profiles/ctcbeam_lm_cost.json, DESIGN
+§4.6i).  Without it nothing of the LM API is touched."""
 import argparse
 import json
 import os
@@ -37,6 +42,8 @@ ap.add_argument("--seconds", type=int, default=10)
 ap.add_argument("--class-samples", type=int, default=1)
 ap.add_argument("--hotwords", action="store_true")
 ap.add_argument("--boost", type=float, default=2.0)
+ap.add_argument("--lm", action="store_true")
+ap.add_argument("--lm-large-mb", type=int, default=256)
 args = ap.parse_args()
 settings = [] if args.settings == "none" else [tuple(int(x) for x in s.split(":")) for s in args.settings.split(",")]
 B = args.batch
@@ -70,6 +77,37 @@ if args.hotwords:
         hot_sets[(w, k)] = words
 
 
+lms = {}
+if args.lm:
+    from aliparaformerasr_amd.engine import LanguageModel         # noqa: E402
+    legs += [(name, w, k) for w, k in settings for name in ("lm_small", "lm_large")]
+    V = cfg["vocab"]
+    eng.set_decode(N.PF_DECODE_CTC_BEAM)
+    eng.set_topk(settings[0][1])
+    eng.set_ctc_beam(settings[0][0], args.nbest or settings[0][0])
+    r = eng.recognize(audio)
+    hyp = [h[0] for b in range(B) for h in r.beam.hyps(b)]
+
+    def synth_lm(n_random, seed):
+        """every id a unigram; the 2- and 3-grams of the batch's unbiased hypotheses; n_random random 3-grams whose contexts are
+        drawn from the first 2048 ids (and the 2-grams that are those contexts)"""
+        rng = np.random.default_rng(seed)
+        uni = np.arange(1, V, dtype=np.int64)
+        bi = {(y[p], y[p + 1]) for y in hyp for p in range(len(y) - 1)}
+        tri = {(y[p], y[p + 1], y[p + 2]) for y in hyp for p in range(len(y) - 2)}
+        ctx_hi = min(2048, V)
+        rnd = np.unique(rng.integers(1, ctx_hi, n_random) * V * V + rng.integers(1, ctx_hi, n_random) * V + rng.integers(1, V, n_random))
+        t3 = np.unique(np.concatenate([rnd, np.asarray([a * V * V + b * V + c for a, b, c in tri], np.int64)]))
+        t2 = np.unique(np.concatenate([t3 // V, np.asarray([a * V + b for a, b in bi], np.int64)]))
+        ids = np.concatenate([uni, np.stack([t2 // V, t2 % V], -1).ravel(), np.stack([t3 // (V * V), t3 // V % V, t3 % V], -1).ravel()])
+        n = len(uni) + len(t2) + len(t3)
+        logp = rng.uniform(-6.0, -0.2, n).astype(np.float32)
+        bo = rng.uniform(-1.0, 0.0, n).astype(np.float32)
+        return LanguageModel.from_arrays(3, [len(uni), len(t2), len(t3)], ids, logp, bo, V, bos=1, eos=2)
+    lms["lm_small"] = synth_lm(40000, 1)                                        # about 2.4 MB: inside one XCD's 4 MB of L2
+    lms["lm_large"] = synth_lm(int(args.lm_large_mb * 1024 * 1024 / 13.0), 2)      # 12 bytes an arc and 16 per context: ends above the mark
+
+
 def set_leg(leg):
     if leg[0] == "topk":
         eng.set_decode(N.PF_DECODE_TOPK)
@@ -80,6 +118,8 @@ def set_leg(leg):
         eng.set_ctc_beam(leg[1], args.nbest or leg[1])
         if args.hotwords:                           # the table is built and uploaded here, outside every timed step
             eng.set_ctc_hotwords(hot_sets[leg[1:]] if leg[0] == "hot" else [], args.boost if leg[0] == "hot" else 0.0)
+        if args.lm:                                 # the image is uploaded once per model (one buffer: a change of model uploads again,
+            eng.set_ctc_lm(lms.get(leg[0]), 0.5, 0.5, N.PF_LM_EOS)      # here, outside every timed step)
 
 
 def leg_name(leg):
@@ -144,6 +184,8 @@ for w, k in settings:
     eng.set_ctc_beam(w, nb)
     if args.hotwords:
         eng.set_ctc_hotwords([], 0.0)
+    if args.lm:
+        eng.set_ctc_lm(None)
     r = eng.recognize(audio, want_logits=True)
     rows = [4 + eng.frontend(a).shape[0] for a in audio]
     lb = np.ascontiguousarray(r.logits[:, :, 0])
@@ -161,6 +203,24 @@ for w, k in settings:
         "host_twin_ms_per_batch": round(host_ms, 3), "L": r.L, "utterances_with_identical_lists": int(same_ids),
         "worst_score_difference_in_tolerances": round(worst, 4), "hypotheses": int(r.beam.n_hyp.sum()),
         "longest_hypothesis": int(r.beam.len.max())})
+    for name, lm in lms.items():                    # the fused twin over the same lists, against what the device kept with the model
+        eng.set_ctc_lm(lm, 0.5, 0.5, N.PF_LM_EOS)
+        rl = eng.recognize(audio)
+        t0 = time.perf_counter()
+        host = [eng.host_ctc_beam_lm(lb[b, :rows[b]], r.topk.ids[b, :rows[b]], r.topk.val[b, :rows[b]], r.topk.n[b, :rows[b]], w, lm, 0.5,
+                                     0.5, N.PF_LM_EOS, n_best=nb) for b in range(B)]
+        host_ms = (time.perf_counter() - t0) * 1e3
+        same = changed = 0
+        for b in range(B):
+            dev = rl.beam.hyps(b)
+            same += [h[0] for h in host[b].hyps(0)] == [h[0] for h in dev] and \
+                (host[b].lm_sum[0].view(np.uint64) == rl.beam.lm_sum[b].view(np.uint64)).all()
+            changed += [h[0] for h in dev] != [h[0] for h in r.beam.hyps(b)]
+        out["legs"]["%s_w%d_k%d" % (name, w, k)].update({
+            "alpha": 0.5, "beta": 0.5, "eos": True, "order": lm.order, "states": lm.states, "arcs": lm.arcs, "image_bytes": lm.image_bytes,
+            "host_twin_ms_per_batch": round(host_ms, 3), "utterances_with_identical_lists_and_lm_sum": int(same),
+            "utterances_whose_list_changed": int(changed)})
+        eng.set_ctc_lm(None)
     if not args.hotwords:
         continue
     # the biased twin over the same lists, against what the device kept with the set installed
