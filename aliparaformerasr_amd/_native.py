@@ -219,6 +219,16 @@ SIGNATURES = {
     "pf_op_ctc_beam_lm": (C.c_int, [_vp, _f, _i64, _f, _i32, _i32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                     _i64, _i32, _P(C.c_double), C.c_int32, _i32, _i32, _i32, C.c_int32, C.c_float, _i32,
                                     _P(C.c_double), _vp, C.c_float, C.c_float, C.c_int32, _P(C.c_double)]),
+    "pf_engine_set_nbest_search": (C.c_int, [_vp, C.c_int32, C.c_int32]),
+    "pf_engine_set_nbest_lm": (C.c_int, [_vp, _vp, C.c_float, C.c_float, C.c_int32]),
+    "pf_engine_set_nbest_hotwords": (C.c_int, [_vp, _i32, _i32, C.c_int32, C.c_float]),
+    "pf_fetch_nbest_search": (C.c_int, [_vp, _i32, _P(C.c_double), _P(C.c_double), _P(C.c_double), _i32, _i32, _i32, _i32]),
+    "pf_host_nbest_search": (C.c_int, [_i64, _f, _i32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _i32, _i32, C.c_int32,
+                                       C.c_float, _vp, C.c_float, C.c_float, C.c_int32, _i32, _P(C.c_double), _P(C.c_double),
+                                       _P(C.c_double), _i32, _i32]),
+    "pf_op_nbest_search": (C.c_int, [_vp, _i64, _f, _i32, _i32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _i32, _i32,
+                                     C.c_int32, C.c_float, _vp, C.c_float, C.c_float, C.c_int32, _i32, _P(C.c_double), _P(C.c_double),
+                                     _P(C.c_double), _i32, _i32]),
     "pf_op_lm_score": (C.c_int, [_vp, _vp, _i32, _i32, C.c_int32, C.c_int32, C.c_float, C.c_float, _P(C.c_double), _i32]),
     "pf_recognizer_set_vad": (C.c_int, [_vp, _P(PfVadConfig), C.c_int32, C.c_int64, C.c_char_p]),
     "pf_stream_num_segments": (C.c_int, [_vp, _i32]),
@@ -227,6 +237,9 @@ SIGNATURES = {
     "pf_stream_alternative_hot": (C.c_int, [_vp, C.c_int32, _i32, _P(C.c_double)]),
     "pf_recognizer_set_lm": (C.c_int, [_vp, C.c_char_p, C.c_float, C.c_float, C.c_int32]),
     "pf_stream_alternative_lm": (C.c_int, [_vp, C.c_int32, _P(C.c_double), _P(C.c_double)]),
+    "pf_recognizer_set_nbest_search": (C.c_int, [_vp, C.c_int32]),
+    "pf_recognizer_set_nbest_lm": (C.c_int, [_vp, C.c_char_p, C.c_float, C.c_float, C.c_int32]),
+    "pf_recognizer_set_nbest_hotword_boost": (C.c_int, [_vp, C.c_float]),
     "pf_engine_set_align_targets": (C.c_int, [_vp, _i64, _i32, C.c_int32, C.c_int32]),
     "pf_fetch_align": (C.c_int, [_vp, _f, _P(C.c_double), _i32, _i32, _i32, _i32, _f, C.c_int32, _i32, _i32]),
     "pf_host_ctc_align": (C.c_int, [_f, C.c_int64, C.c_int32, C.c_int32, _i64, C.c_int32, _f, _P(C.c_double), _i32, _i32, _i32, _f]),

@@ -545,6 +545,59 @@ int pf_host_ctc_beam_lm(const float* blank_lp, int64_t blank_stride, const int64
   PF_CATCH
 }
 
+int pf_engine_set_nbest_search(pf_engine* h, int32_t W, int32_t N) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->set_nbest_search(W, N);
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_engine_set_nbest_lm(pf_engine* h, const pf_lm* lm, float alpha, float beta, int32_t flags) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->set_nbest_lm(lm ? lm->p : nullptr, alpha, beta, flags);
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_engine_set_nbest_hotwords(pf_engine* h, const int32_t* ids, const int32_t* lens, int32_t n_hotwords, float boost) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->set_nbest_hotwords(ids, lens, n_hotwords, boost);
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_fetch_nbest_search(pf_engine* h, int32_t* ranks, double* score, double* loglik_sum, double* lm_sum, int32_t* matched,
+                          int32_t* n_hyp, int32_t* L_out, int32_t* N_out) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->fetch_nbest_search(ranks, score, loglik_sum, lm_sum, matched, n_hyp, L_out, N_out);
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_host_nbest_search(const int64_t* ids, const float* val, const int32_t* n, int32_t L, int32_t K, int32_t token_num, int32_t W,
+                         int32_t N, const int32_t* hw_ids, const int32_t* hw_lens, int32_t n_hotwords, float boost, const pf_lm* lm,
+                         float alpha, float beta, int32_t flags, int32_t* out_ranks, double* out_score, double* out_loglik,
+                         double* out_lm, int32_t* out_matched, int32_t* n_hyp) {
+  PF_TRY
+  NEED(n_hyp);
+  *n_hyp = host_nbest_search(ids, val, n, L, K, token_num, W, N, hw_ids, hw_lens, n_hotwords, boost, lm ? lm->p.get() : nullptr, alpha, beta,
+                             flags, out_ranks, out_score, out_loglik, out_lm, out_matched);
+  return PF_OK;
+  PF_CATCH
+}
+
 int pf_engine_set_align_targets(pf_engine* h, const int64_t* ids, const int32_t* len, int32_t B, int32_t cap) {
   PF_TRY
   std::shared_ptr<Engine> eh_ = E(h);
@@ -886,6 +939,20 @@ int pf_op_ctc_beam_hot(pf_engine* h, const float* blank_lp, const int64_t* ids, 
   std::lock_guard<std::mutex> lk(e->mutex());
   e->op_ctc_beam_hot(blank_lp, ids, val, n, lens, B, T, K, blank, W, N, hw_ids, hw_lens, n_hotwords, boost, out_ids, out_len, out_score,
                      out_matched, out_loglik, cap, n_hyp);
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_op_nbest_search(pf_engine* h, const int64_t* ids, const float* val, const int32_t* n, const int32_t* token_num, int32_t B,
+                       int32_t L, int32_t K, int32_t W, int32_t N, const int32_t* hw_ids, const int32_t* hw_lens, int32_t n_hotwords,
+                       float boost, const pf_lm* lm, float alpha, float beta, int32_t flags, int32_t* out_ranks, double* out_score,
+                       double* out_loglik, double* out_lm, int32_t* out_matched, int32_t* n_hyp) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->op_nbest_search(ids, val, n, token_num, B, L, K, W, N, hw_ids, hw_lens, n_hotwords, boost, lm ? lm->p : nullptr, alpha, beta, flags,
+                     out_ranks, out_score, out_loglik, out_lm, out_matched, n_hyp);
   return PF_OK;
   PF_CATCH
 }
@@ -1577,6 +1644,33 @@ int pf_stream_alternative_lm(pf_stream* h, int32_t i, double* lm_sum, double* lo
   const Alternative& a = s->Alternatives[(size_t)i];
   if (lm_sum) *lm_sum = a.lm_sum;
   if (loglik_sum) *loglik_sum = a.loglik_sum;
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_recognizer_set_nbest_search(pf_recognizer* h, int32_t W) {
+  PF_TRY
+  std::shared_ptr<Recognizer> r = R(h);
+  PF_CHECK(!r->disposed(), PF_ERR_DISPOSED, "OfflineRecognizer");
+  r->SetNBestSearch(W);
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_recognizer_set_nbest_lm(pf_recognizer* h, const char* arpa_path, float alpha, float beta, int32_t flags) {
+  PF_TRY
+  std::shared_ptr<Recognizer> r = R(h);
+  PF_CHECK(!r->disposed(), PF_ERR_DISPOSED, "OfflineRecognizer");
+  r->SetNBestLm(arpa_path ? arpa_path : "", alpha, beta, flags);
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_recognizer_set_nbest_hotword_boost(pf_recognizer* h, float boost) {
+  PF_TRY
+  std::shared_ptr<Recognizer> r = R(h);
+  PF_CHECK(!r->disposed(), PF_ERR_DISPOSED, "OfflineRecognizer");
+  r->SetNBestHotwordBoost(boost);
   return PF_OK;
   PF_CATCH
 }

@@ -71,6 +71,15 @@ struct BeamLmBlock : Block {
   BeamLmBlock(Cursor& c, size_t B, size_t N) : Block(c) { lay(c, lm_sum, B * N); }
 };
 
+// n-best search over paraformer's top-k lists (k_nbestsearch.hip): score [B, N] | loglik_sum [B, N] | lm_sum [B, N] float64 |
+// ranks [B, N, L] | matched [B, N] | n_hyp [B] int32
+struct NbestSearchBlock : Block {
+  Field<double> score, loglik, lm_sum; Field<int32_t> ranks, matched, n_hyp;
+  NbestSearchBlock(Cursor& c, size_t B, size_t N, size_t L) : Block(c) {
+    lay(c, score, B * N, loglik, B * N, lm_sum, B * N, ranks, B * N * L, matched, B * N, n_hyp, B);
+  }
+};
+
 // CTC forced alignment (k_ctcalign.hip): loglik [B, H] float64 | path_score [B, H] fp32 | ok [B, H] | len [B, H] int32 |
 // first [B, H, cap] | last [B, H, cap] int32 | tok_score [B, H, cap] fp32
 struct AlignBlock : Block {
@@ -112,12 +121,14 @@ struct HostBatchOut { // results of a forward, host side
   std::vector<int64_t> ctc, topk, beam, beam_hot, align;   // beam_hot: empty when the search ran unbiased and unfused
   std::vector<int64_t> beam_lm;    // empty when the search ran without a language model; loglik_sum then sits in beam_hot
   bool beam_biased = false;        // a hot-word set biased the search: beam_hot's matched means something
-  int ctc_cap = 0, topk_k = 0, beam_n = 0, beam_cap = 0, align_h = 0, align_cap = 0;
+  std::vector<int64_t> nbs;        // empty when the forward ran no n-best search (Engine::set_nbest_search)
+  int ctc_cap = 0, topk_k = 0, beam_n = 0, beam_cap = 0, align_h = 0, align_cap = 0, nbs_n = 0;
   CtcBlock ctc_block() const { return block_at_zero<CtcBlock>(B, ctc_cap); }
   TopkBlock topk_block() const { return block_at_zero<TopkBlock>((size_t)B * L, topk_k); }
   BeamBlock beam_block() const { return block_at_zero<BeamBlock>(B, beam_n, beam_cap); }
   BeamHotBlock beam_hot_block() const { return block_at_zero<BeamHotBlock>(B, beam_n); }
   BeamLmBlock beam_lm_block() const { return block_at_zero<BeamLmBlock>(B, beam_n); }
+  NbestSearchBlock nbs_block() const { return block_at_zero<NbestSearchBlock>(B, nbs_n, L); }
   AlignBlock align_block() const { return block_at_zero<AlignBlock>(B, align_h, align_cap); }
 };
 

@@ -119,8 +119,8 @@ void Engine::release() {
   for (void* p : owned_) hipFree(p);
   owned_.clear();
   DevBuf* bufs[] = {&ws_f32_, &ws_pcm_, &ws_audio_, &ws_meta_, &ws_fbank_, &ws_speech_, &ws_enc_, &ws_dec_, &ws_kv_, &ws_pe_, &ws_tmp_,
-                    &ws_ts_, &ws_seaco_, &ws_seaco_in_, &ws_seaco_hw_, &ws_q_, &ws_qf_, &ws_seaco_q_, &ws_x3a_, &ws_x3t_, &ws_x3h_, &lm_inst_.buf, &lm_op_.buf};
-  lm_inst_.src.reset(); lm_op_.src.reset(); lm_.reset();
+                    &ws_ts_, &ws_seaco_, &ws_seaco_in_, &ws_seaco_hw_, &ws_q_, &ws_qf_, &ws_seaco_q_, &ws_x3a_, &ws_x3t_, &ws_x3h_, &lm_inst_.buf, &lm_op_.buf, &nbs_hot_.buf, &ws_nbs_};
+  lm_inst_.src.reset(); lm_op_.src.reset(); lm_.reset(); nbs_lm_.reset();
   x3_pair_live_ = false; x3a_src_ = nullptr; x3a_pair_only_ = false;
   x3w_.clear();
   ts_whh_x3_ = nullptr;
@@ -1912,32 +1912,38 @@ void Engine::set_ctc_beam(int W, int N) {
 
 void Engine::set_ctc_hotwords(const int32_t* ids, const int32_t* lens, int n, float boost) {
   PF_CHECK(mc_.kind_id() == 1 && !mc_.seaco, PF_ERR_UNSUPPORTED, "set_ctc_hotwords: only a SenseVoice model has a CTC head");
-  PF_CHECK(boost >= 0.f && boost <= 3.4028234e38f, PF_ERR_INVALID_ARG, "set_ctc_hotwords: the boost is finite and >= 0");
-  PF_CHECK(n >= 0, PF_ERR_INVALID_ARG, "set_ctc_hotwords: negative n_hotwords");
-  PF_CHECK(n == 0 || lens, PF_ERR_INVALID_ARG, "set_ctc_hotwords: null lens");
-  if (n == 0 || boost == 0.f) { hot_boost_ = 0.f; hot_A_ = 0; hot_ids_.clear(); hot_lens_.clear(); return; }
+  install_hotwords(hot_, "set_ctc_hotwords", ids, lens, n, boost);
+}
+
+// the argument rules, the content test and the one upload of both hot-word setters
+void Engine::install_hotwords(HotDev& d, const char* who_, const int32_t* ids, const int32_t* lens, int n, float boost) {
+  const std::string who = who_;
+  PF_CHECK(boost >= 0.f && boost <= 3.4028234e38f, PF_ERR_INVALID_ARG, who + ": the boost is finite and >= 0");
+  PF_CHECK(n >= 0, PF_ERR_INVALID_ARG, who + ": negative n_hotwords");
+  PF_CHECK(n == 0 || lens, PF_ERR_INVALID_ARG, who + ": null lens");
+  if (n == 0 || boost == 0.f) { d.clear(); return; }
   size_t total = 0;
-  for (int i = 0; i < n; ++i) { PF_CHECK(lens[i] >= 0, PF_ERR_INVALID_ARG, "set_ctc_hotwords: negative hot-word length"); total += (size_t)lens[i]; }
-  PF_CHECK(total == 0 || ids, PF_ERR_INVALID_ARG, "set_ctc_hotwords: null ids");
+  for (int i = 0; i < n; ++i) { PF_CHECK(lens[i] >= 0, PF_ERR_INVALID_ARG, who + ": negative hot-word length"); total += (size_t)lens[i]; }
+  PF_CHECK(total == 0 || ids, PF_ERR_INVALID_ARG, who + ": null ids");
   // the automaton is kept while the set is the same (by content): only the boost may have changed
-  if (hot_boost_ > 0.f && hot_lens_.size() == (size_t)n && hot_ids_.size() == total && std::equal(lens, lens + n, hot_lens_.begin()) &&
-      std::equal(ids, ids + total, hot_ids_.begin())) {
-    hot_boost_ = boost;
+  if (d.boost > 0.f && d.lens.size() == (size_t)n && d.ids.size() == total && std::equal(lens, lens + n, d.lens.begin()) &&
+      std::equal(ids, ids + total, d.ids.begin())) {
+    d.boost = boost;
     return;
   }
   HotwordGraph g;
   build_hotword_graph(ids, lens, n, mc_.vocab, g);   // throws before anything changes
-  if (g.empty()) { hot_boost_ = 0.f; hot_A_ = 0; hot_ids_.clear(); hot_lens_.clear(); return; }
-  hot_ids_.assign(ids, ids + total);
-  hot_lens_.assign(lens, lens + n);
+  if (g.empty()) { d.clear(); return; }
+  d.ids.assign(ids, ids + total);
+  d.lens.assign(lens, lens + n);
   PF_HIP(hipSetDevice(device_));
   PF_HIP(hipStreamSynchronize(stream_));            // a queued search may still read the table about to be replaced
   const size_t V = g.tok_col.size(), words = V + g.table.size();
-  ensure(ws_hot_, words * 4);
-  PF_HIP(hipMemcpy(ws_hot_.p, g.tok_col.data(), V * 4, hipMemcpyHostToDevice));
-  PF_HIP(hipMemcpy((int32_t*)ws_hot_.p + V, g.table.data(), g.table.size() * 4, hipMemcpyHostToDevice));
-  hot_boost_ = boost;
-  hot_A_ = g.A;
+  ensure(d.buf, words * 4);
+  PF_HIP(hipMemcpy(d.buf.p, g.tok_col.data(), V * 4, hipMemcpyHostToDevice));
+  PF_HIP(hipMemcpy((int32_t*)d.buf.p + V, g.table.data(), g.table.size() * 4, hipMemcpyHostToDevice));
+  d.boost = boost;
+  d.A = g.A;
 }
 
 void Engine::set_ctc_lm(const std::shared_ptr<const LmImage>& lm, float alpha, float beta, int flags) {
@@ -1949,6 +1955,30 @@ void Engine::set_ctc_lm(const std::shared_ptr<const LmImage>& lm, float alpha, f
   lm_device_image(lm_inst_, lm);
   lm_ = lm;
   lm_alpha_ = alpha; lm_beta_ = beta; lm_flags_ = flags;
+}
+
+void Engine::set_nbest_search(int W, int N) {
+  PF_CHECK(mc_.kind_id() == 0 && !mc_.seaco, PF_ERR_UNSUPPORTED, "set_nbest_search: only a paraformer model (not SeACo, not SenseVoice) has this search");
+  if (W == 0) { nbs_w_ = 0; nbs_n_ = 0; return; }
+  PF_CHECK(N >= 1 && N <= W && W <= PF_NBEST_MAX, PF_ERR_INVALID_ARG, "set_nbest_search: W == 0 or 1 <= N <= W <= " + std::to_string(PF_NBEST_MAX));
+  nbs_w_ = W;
+  nbs_n_ = N;
+}
+
+void Engine::set_nbest_lm(const std::shared_ptr<const LmImage>& lm, float alpha, float beta, int flags) {
+  PF_CHECK(mc_.kind_id() == 0 && !mc_.seaco, PF_ERR_UNSUPPORTED, "set_nbest_lm: only a paraformer model (not SeACo, not SenseVoice) has this search");
+  if (!lm) { nbs_lm_.reset(); return; }             // (the image stays where it is: the same model again costs no upload)
+  lm_check_weights(alpha, beta, flags);
+  PF_HIP(hipSetDevice(device_));
+  if (lm_inst_.src != lm) PF_HIP(hipStreamSynchronize(stream_));   // a queued search may still read the image about to be replaced
+  lm_device_image(lm_inst_, lm);
+  nbs_lm_ = lm;
+  nbs_alpha_ = alpha; nbs_beta_ = beta; nbs_flags_ = flags;
+}
+
+void Engine::set_nbest_hotwords(const int32_t* ids, const int32_t* lens, int n, float boost) {
+  PF_CHECK(mc_.kind_id() == 0 && !mc_.seaco, PF_ERR_UNSUPPORTED, "set_nbest_hotwords: only a paraformer model (not SeACo, not SenseVoice) has this search");
+  install_hotwords(nbs_hot_, "set_nbest_hotwords", ids, lens, n, boost);
 }
 
 float* Engine::score_buf(int64_t rows) {
@@ -1970,6 +2000,7 @@ void Engine::queue_decode_results(int B, int L) {
     for (int b = 0; b < B; ++b) len[b] = std::min(std::max(len[b], 0), L);
   }
   if (decode_flags_ & PF_DECODE_TOPK) queue_topk(B, L);
+  if ((decode_flags_ & PF_DECODE_TOPK) && nbs_w_ > 0) queue_nbest_search(B, L);
   if (decode_flags_ & PF_DECODE_CTC_BEAM) queue_ctc_beam(B, L);      // (set_decode: implies TOPK)
   if (decode_flags_ & PF_DECODE_ALIGN) queue_align(B, L);
   if (decode_flags_ & PF_DECODE_CTC) queue_ctc_collapse(B, L);
@@ -1991,10 +2022,39 @@ void Engine::queue_topk(int B, int L) {
   PF_HIP(hipMemcpyAsync(last_.topk.data(), ws, k.bytes(), hipMemcpyDeviceToHost, stream_));
 }
 
+void Engine::queue_nbest_search(int B, int L) {
+  // the search reads the lists queue_topk just made and the CIF plan's token counts where the decoder read them
+  const int W = nbs_w_, Nh = nbs_n_, K = topk_k_;
+  const bool hot = nbs_hot_.boost > 0.f, lm = (bool)nbs_lm_;
+  const TopkBlock tk = block_at_zero<TopkBlock>((size_t)B * L, K);
+  Cursor c;
+  const NbestSearchBlock k(c, B, Nh, L);
+  const Field<int32_t> bp = c.take<int32_t>((size_t)B * L * W);
+  ensure(ws_nbs_, c.off);
+  last_.nbs.resize(k.words());
+  last_.nbs_n = Nh;
+  void* ws = ws_nbs_.p;
+  const void* wt = ws_topk_.p;
+  const int32_t* tok_col = hot ? (const int32_t*)nbs_hot_.buf.p : nullptr;
+  NbestSearchArgs a{};
+  a.ids = tk.ids(wt); a.val = tk.val(wt); a.n = tk.n(wt); a.token_num = plan_.token_num;
+  a.L = L; a.K = K; a.W = W; a.N = Nh;
+  a.bp = bp(ws);
+  a.tok_col = tok_col; a.table = hot ? tok_col + mc_.vocab : nullptr; a.V = mc_.vocab; a.A = nbs_hot_.A; a.boost = (double)nbs_hot_.boost;
+  a.lm_image = lm ? (const int32_t*)lm_inst_.buf.p : nullptr; a.alpha = (double)nbs_alpha_; a.beta = (double)nbs_beta_;
+  a.lm_eos = (nbs_flags_ & PF_LM_EOS) != 0;
+  a.out_ranks = k.ranks(ws); a.out_score = k.score(ws); a.out_loglik = k.loglik(ws); a.out_lm = k.lm_sum(ws);
+  a.out_matched = k.matched(ws); a.n_hyp = k.n_hyp(ws);
+  prof_begin("nbest_search", 0);
+  launch_nbest_search(stream_, a, B);
+  prof_end("nbest_search");
+  PF_HIP(hipMemcpyAsync(last_.nbs.data(), ws, k.words() * 8, hipMemcpyDeviceToHost, stream_));
+}
+
 void Engine::queue_ctc_beam(int B, int L) {
   // the search reads the lists queue_topk just made and the blank column (id 0) of the in-place log-prob rows
   const int W = beam_w_, Nh = beam_n_, cap = L, K = topk_k_;
-  const bool hot = hot_boost_ > 0.f, lm = (bool)lm_;
+  const bool hot = hot_.boost > 0.f, lm = (bool)lm_;
   const size_t nodes = (size_t)B * ((size_t)L * W + 1);
   const TopkBlock tk = block_at_zero<TopkBlock>((size_t)B * L, K);
   Cursor c;
@@ -2014,19 +2074,19 @@ void Engine::queue_ctc_beam(int B, int L) {
   prof_begin("ctc_beam", 0);
   last_.beam_biased = hot;
   if (lm) {
-    const int32_t* tok_col = hot ? (const int32_t*)ws_hot_.p : nullptr;
+    const int32_t* tok_col = hot ? (const int32_t*)hot_.buf.p : nullptr;
     last_.beam_hot.resize(h.words());
     last_.beam_lm.resize(l.words());
     if (!hot) PF_HIP(hipMemsetAsync(h.matched(ws), 0, h.matched.count * 4, stream_));   // no set: nothing matched
     launch_ctc_beam_lm(stream_, logits_, logits_ld_, tk.ids(wt), tk.val(wt), tk.n(wt), len_d(ws), B, L, K, 0, W, Nh, cap, node_par(ws),
-                       node_tok(ws), tok_col, mc_.vocab, hot ? tok_col + mc_.vocab : nullptr, hot_A_, hot_boost_,
+                       node_tok(ws), tok_col, mc_.vocab, hot ? tok_col + mc_.vocab : nullptr, hot_.A, hot_.boost,
                        (const int32_t*)lm_inst_.buf.p, lm_alpha_, lm_beta_, lm_flags_, k.ids(ws), k.len(ws), k.score(ws), h.matched(ws),
                        h.loglik(ws), l.lm_sum(ws), k.n_hyp(ws));
   } else if (hot) {
-    const int32_t* tok_col = (const int32_t*)ws_hot_.p;
+    const int32_t* tok_col = (const int32_t*)hot_.buf.p;
     last_.beam_hot.resize(h.words());
     launch_ctc_beam_hot(stream_, logits_, logits_ld_, tk.ids(wt), tk.val(wt), tk.n(wt), len_d(ws), B, L, K, 0, W, Nh, cap, node_par(ws),
-                        node_tok(ws), tok_col, mc_.vocab, tok_col + mc_.vocab, hot_A_, hot_boost_, k.ids(ws), k.len(ws), k.score(ws),
+                        node_tok(ws), tok_col, mc_.vocab, tok_col + mc_.vocab, hot_.A, hot_.boost, k.ids(ws), k.len(ws), k.score(ws),
                         h.matched(ws), h.loglik(ws), k.n_hyp(ws));
   } else {
     launch_ctc_beam(stream_, logits_, logits_ld_, tk.ids(wt), tk.val(wt), tk.n(wt), len_d(ws), B, L, K, 0, W, Nh, cap, node_par(ws),
@@ -2103,6 +2163,7 @@ void Engine::forward_device(const float* speech_dev, int B, int T, bool want_log
   last_.topk.clear(); last_.topk_k = 0;
   last_.beam.clear(); last_.beam_n = 0; last_.beam_cap = 0; last_.beam_hot.clear(); last_.beam_lm.clear(); last_.beam_biased = false;
   last_.align.clear(); last_.align_h = 0; last_.align_cap = 0;
+  last_.nbs.clear(); last_.nbs_n = 0;
   if (align_B_ != 0 && align_B_ != B) {             // before anything is launched; the targets are dropped
     const int want = align_B_;
     align_B_ = 0; align_tgt_.clear(); align_len_.clear();
@@ -2296,6 +2357,23 @@ void Engine::fetch_ctc_beam_lm(double* lm_sum, double* loglik) {
   const BeamHotBlock h = r.beam_hot_block();
   if (lm_sum) std::memcpy(lm_sum, k.lm_sum(r.beam_lm.data()), k.lm_sum.count * 8);
   if (loglik) std::memcpy(loglik, h.loglik(r.beam_hot.data()), h.loglik.count * 8);
+}
+
+void Engine::fetch_nbest_search(int32_t* ranks, double* score, double* loglik, double* lm_sum, int32_t* matched, int32_t* n_hyp,
+                                int32_t* L_out, int32_t* N_out) {
+  const char* refusal = "fetch_nbest_search: the last forward ran no n-best search (PF_DECODE_TOPK with pf_engine_set_nbest_search)";
+  const HostBatchOut& r = fetch_result(PF_DECODE_TOPK, refusal);
+  PF_CHECK(r.nbs_n > 0, PF_ERR_INVALID_ARG, refusal);
+  if (L_out) *L_out = r.L;
+  if (N_out) *N_out = r.nbs_n;
+  const NbestSearchBlock k = r.nbs_block();
+  const void* p = r.nbs.data();
+  if (ranks) std::memcpy(ranks, k.ranks(p), k.ranks.count * 4);
+  if (score) std::memcpy(score, k.score(p), k.score.count * 8);
+  if (loglik) std::memcpy(loglik, k.loglik(p), k.loglik.count * 8);
+  if (lm_sum) std::memcpy(lm_sum, k.lm_sum(p), k.lm_sum.count * 8);
+  if (matched) std::memcpy(matched, k.matched(p), k.matched.count * 4);
+  if (n_hyp) std::memcpy(n_hyp, k.n_hyp(p), k.n_hyp.count * 4);
 }
 
 void Engine::fetch_align(float* path_score, double* loglik, int32_t* ok, int32_t* len, int32_t* first, int32_t* last, float* tok_score,

@@ -190,7 +190,7 @@ class Engine {
   // automaton's table and uploaded here; n == 0 or boost == 0 clears it.  With a set installed CTC_BEAM launches the biased
   // form of the kernel and fetch_ctc_beam_hot gives matched / loglik_sum beside fetch_ctc_beam's (biased) scores.
   void set_ctc_hotwords(const int32_t* ids, const int32_t* lens, int n, float boost);
-  bool ctc_hotwords_on() const { return hot_boost_ > 0.f; }
+  bool ctc_hotwords_on() const { return hot_.boost > 0.f; }
   // Language model (SenseVoice; the definition is tests/ctcbeam_lm_ref.py): with a model installed a forward with CTC_BEAM runs
   // a fused form of the kernel and fetch_ctc_beam_lm gives lm_sum / loglik_sum beside fetch_ctc_beam's (fused) scores.  nullptr
   // clears; the image is uploaded once, the same model again only takes the new weights.
@@ -209,6 +209,22 @@ class Engine {
                       int32_t* n_hyp, const std::shared_ptr<const LmImage>& lm, float alpha, float beta, int lm_flags, double* out_lm);
   void op_lm_score(const std::shared_ptr<const LmImage>& lm, const int32_t* ids, const int32_t* lens, int B, int L, float alpha,
                    float beta, double* g, int32_t* state);
+  // N-best search (paraformer, not SeACo; the definition is tests/nbest_search_ref.py): with W > 0 installed a forward with TOPK
+  // runs, behind the top-k launch, one kernel (k_nbestsearch.hip) that searches every utterance's lists with a beam of width W
+  // and keeps the N best rank vectors; W == 0 turns it off (nothing is launched, allocated or uploaded).  A model and a hot-word
+  // set of its own may be fused in; both are inert until a search is installed, and share rules and one-time upload with their
+  // set_ctc_* siblings.
+  void set_nbest_search(int W, int N);
+  int nbest_search_w() const { return nbs_w_; }
+  void set_nbest_lm(const std::shared_ptr<const LmImage>& lm, float alpha, float beta, int flags);
+  void set_nbest_hotwords(const int32_t* ids, const int32_t* lens, int n, float boost);
+  void fetch_nbest_search(int32_t* ranks, double* score, double* loglik, double* lm_sum, int32_t* matched, int32_t* n_hyp, int32_t* L_out,
+                          int32_t* N_out);
+  // the kernel alone on caller-supplied lists [B, L, K] with token_num [B]
+  void op_nbest_search(const int64_t* ids, const float* val, const int32_t* n, const int32_t* token_num, int B, int L, int K, int W, int N,
+                       const int32_t* hw_ids, const int32_t* hw_lens, int n_hw, float boost, const std::shared_ptr<const LmImage>& lm,
+                       float alpha, float beta, int lm_flags, int32_t* out_ranks, double* out_score, double* out_loglik, double* out_lm,
+                       int32_t* out_matched, int32_t* n_hyp);
   // ALIGN (SenseVoice; implies SCORES): behind the other decode launches one kernel (k_ctcalign.hip) aligns the caller's
   // targets of this forward (set_align_targets; consumed) and, with CTC_BEAM, the beam's hypotheses to the log-prob rows
   void set_align_targets(const int64_t* ids, const int32_t* len, int B, int cap);
@@ -514,18 +530,32 @@ class Engine {
   // the arg-max form of a pipeline head: the top-k kernel reads the log-probs the arg-max leaves in place
   int beam_w_ = 16, beam_n_ = 16;    // W / N of PF_DECODE_CTC_BEAM
   DevBuf ws_beam_;                   // the beam result block (HostBatchOut::beam) | len [B] | prefix nodes; allocated with the flag only
-  float hot_boost_ = 0.f;            // > 0: a hot-word set is installed (set_ctc_hotwords); its table lives in ws_hot_
-  int hot_A_ = 0;                    // columns of the table
-  std::vector<int32_t> hot_ids_, hot_lens_;   // the installed set as given: a call with the same content keeps the table
-  DevBuf ws_hot_;                    // tok_col [V] | table [S, A]; allocated by set_ctc_hotwords only
+  // an installed hot-word set (set_ctc_hotwords for the CTC search, set_nbest_hotwords for the n-best search)
+  struct HotDev {
+    float boost = 0.f;               // > 0: a set is installed; its table lives in buf
+    int A = 0;                       // columns of the table
+    std::vector<int32_t> ids, lens;  // the installed set as given: a call with the same content keeps the table
+    DevBuf buf;                      // tok_col [V] | table [S, A]; allocated by the setter only
+    void clear() { boost = 0.f; A = 0; ids.clear(); lens.clear(); }
+  };
+  HotDev hot_, nbs_hot_;
+  void install_hotwords(HotDev& d, const char* who, const int32_t* ids, const int32_t* lens, int n, float boost);
   // the language model's image in a buffer of its own: uploaded when a model is first used, kept (with a reference to the
   // model) while the same one is given
   struct LmDev { DevBuf buf; std::shared_ptr<const LmImage> src; };
-  LmDev lm_inst_, lm_op_;            // the installed model's image (set_ctc_lm), and the one pf_op_* last used
+  LmDev lm_inst_, lm_op_;            // the installed model's image (set_ctc_lm / set_nbest_lm: an engine is of one kind), and
+                                     // the one pf_op_* last used
   const int32_t* lm_device_image(LmDev& d, const std::shared_ptr<const LmImage>& lm);
   std::shared_ptr<const LmImage> lm_;   // the installed model (nullptr: none), its weights and flags
   float lm_alpha_ = 0.f, lm_beta_ = 0.f;
   int lm_flags_ = 0;
+  // the n-best search (set_nbest_search; 0: off), its model with weights and flags (set_nbest_lm), its workspace
+  int nbs_w_ = 0, nbs_n_ = 0;
+  std::shared_ptr<const LmImage> nbs_lm_;
+  float nbs_alpha_ = 0.f, nbs_beta_ = 0.f;
+  int nbs_flags_ = 0;
+  DevBuf ws_nbs_;                    // the result block (HostBatchOut::nbs) | back-pointers [B, L, W]; allocated by a search only
+  void queue_nbest_search(int B, int L);
   // PF_DECODE_ALIGN: the targets of the next forward (int32, [B, align_cap_]; align_B_ = 0: none) and those of the forward
   // being queued (alive until the next forward: the host-to-device copies may read them after the call returns)
   std::vector<int32_t> align_tgt_, align_len_, align_tgt_q_, align_len_q_;

@@ -391,6 +391,79 @@ void Engine::op_ctc_beam_lm(const float* blank_lp, const int64_t* ids, const flo
     }
 }
 
+// the n-best search kernel alone on caller lists; the result block is sentinel-filled and every cell must come back written
+void Engine::op_nbest_search(const int64_t* ids, const float* val, const int32_t* n, const int32_t* token_num, int B, int L, int K, int W,
+                             int N, const int32_t* hw_ids, const int32_t* hw_lens, int n_hw, float boost,
+                             const std::shared_ptr<const LmImage>& lm, float alpha, float beta, int lm_flags, int32_t* out_ranks,
+                             double* out_score, double* out_loglik, double* out_lm, int32_t* out_matched, int32_t* n_hyp) {
+  PF_CHECK(B >= 0 && L >= 0 && K >= 1 && K <= PF_TOPK_MAX && N >= 1 && N <= W && W <= PF_NBEST_MAX, PF_ERR_INVALID_ARG,
+           "nbest_search: bad B / L / K / W / N");
+  PF_CHECK(boost >= 0.f && boost <= 3.4028234e38f, PF_ERR_INVALID_ARG, "nbest_search: the boost is finite and >= 0");
+  if (lm) lm_check_weights(alpha, beta, lm_flags);
+  const size_t rows = (size_t)B * L;
+  PF_CHECK(B == 0 || (token_num && n_hyp && out_score && out_loglik && out_lm && out_matched), PF_ERR_INVALID_ARG, "nbest_search: null argument");
+  PF_CHECK(rows == 0 || (ids && val && n && out_ranks), PF_ERR_INVALID_ARG, "nbest_search: null argument");
+  for (size_t x = 0; x < rows; ++x) PF_CHECK(n[x] >= 0 && n[x] <= K, PF_ERR_INVALID_ARG, "nbest_search: n[l] outside 0 .. K");
+  HotwordGraph graph;
+  if (n_hw != 0) build_hotword_graph(hw_ids, hw_lens, n_hw, hotword_vocab_bound(hw_ids, hw_lens, n_hw), graph);
+  const HotwordGraph* g = boost == 0.f || graph.empty() ? nullptr : &graph;
+  PF_HIP(hipSetDevice(device_));
+  if (B == 0) return;
+  const int32_t* lm_image = lm ? lm_device_image(lm_inst_.src == lm ? lm_inst_ : lm_op_, lm) : nullptr;
+  Cursor c;
+  const NbestSearchBlock k(c, B, N, L);
+  const TopkBlock in(c, rows, K);
+  const Field<int32_t> d_tn = c.take<int32_t>(B), d_bp = c.take<int32_t>(rows * W);
+  const Field<int32_t> d_col = c.take<int32_t>(g ? g->tok_col.size() : 0), d_tab = c.take<int32_t>(g ? g->table.size() : 0);
+  ensure(ws_tmp_, c.off);
+  void* ws = ws_tmp_.p;
+  fill_sentinel32(stream_, (char*)ws + k.begin, k.words() * 2);
+  if (rows > 0) {
+    PF_HIP(hipMemcpyAsync(in.ids(ws), ids, in.ids.count * 8, hipMemcpyHostToDevice, stream_));
+    PF_HIP(hipMemcpyAsync(in.val(ws), val, in.val.count * 4, hipMemcpyHostToDevice, stream_));
+    PF_HIP(hipMemcpyAsync(in.n(ws), n, rows * 4, hipMemcpyHostToDevice, stream_));
+  }
+  PF_HIP(hipMemcpyAsync(d_tn(ws), token_num, d_tn.count * 4, hipMemcpyHostToDevice, stream_));
+  if (g) {
+    PF_HIP(hipMemcpyAsync(d_col(ws), g->tok_col.data(), d_col.count * 4, hipMemcpyHostToDevice, stream_));
+    PF_HIP(hipMemcpyAsync(d_tab(ws), g->table.data(), d_tab.count * 4, hipMemcpyHostToDevice, stream_));
+  }
+  NbestSearchArgs a{};
+  a.ids = in.ids(ws); a.val = in.val(ws); a.n = in.n(ws); a.token_num = d_tn(ws);
+  a.L = L; a.K = K; a.W = W; a.N = N;
+  a.bp = d_bp(ws);
+  a.tok_col = g ? d_col(ws) : nullptr; a.table = g ? d_tab(ws) : nullptr; a.V = (int)d_col.count; a.A = g ? g->A : 0; a.boost = (double)boost;
+  a.lm_image = lm_image; a.alpha = (double)alpha; a.beta = (double)beta; a.lm_eos = (lm_flags & PF_LM_EOS) != 0;
+  a.out_ranks = k.ranks(ws); a.out_score = k.score(ws); a.out_loglik = k.loglik(ws); a.out_lm = k.lm_sum(ws);
+  a.out_matched = k.matched(ws); a.n_hyp = k.n_hyp(ws);
+  launch_nbest_search(stream_, a, B);
+  std::vector<int64_t> h(k.words());
+  PF_HIP(hipMemcpyAsync(h.data(), (char*)ws + k.begin, h.size() * 8, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipStreamSynchronize(stream_));            // g's host arrays are read by the copies queued above until here
+  const NbestSearchBlock hk = block_at_zero<NbestSearchBlock>(B, N, L);
+  const void* p = h.data();
+  const uint64_t sent64 = ((uint64_t)kSentinel32 << 32) | kSentinel32;
+  auto written32 = [&](const Field<int32_t>& f, const char* what) {
+    for (size_t x = 0; x < f.count; ++x)
+      PF_CHECK((uint32_t)f(p)[x] != kSentinel32, PF_ERR_DEVICE, std::string("nbest_search: ") + what + " cell " + std::to_string(x) + " was not written");
+  };
+  auto written64 = [&](const Field<double>& f, const char* what) {
+    for (size_t x = 0; x < f.count; ++x) {
+      uint64_t u;
+      std::memcpy(&u, f(p) + x, 8);
+      PF_CHECK(u != sent64, PF_ERR_DEVICE, std::string("nbest_search: ") + what + " cell " + std::to_string(x) + " was not written");
+    }
+  };
+  written32(hk.ranks, "ranks"); written32(hk.matched, "matched"); written32(hk.n_hyp, "n_hyp");
+  written64(hk.score, "score"); written64(hk.loglik, "loglik_sum"); written64(hk.lm_sum, "lm_sum");
+  if (hk.ranks.count) std::memcpy(out_ranks, hk.ranks(p), hk.ranks.count * 4);
+  std::memcpy(out_score, hk.score(p), hk.score.count * 8);
+  std::memcpy(out_loglik, hk.loglik(p), hk.loglik.count * 8);
+  std::memcpy(out_lm, hk.lm_sum(p), hk.lm_sum.count * 8);
+  std::memcpy(out_matched, hk.matched(p), hk.matched.count * 4);
+  std::memcpy(n_hyp, hk.n_hyp(p), hk.n_hyp.count * 4);
+}
+
 void Engine::op_ctc_align(const float* lp, int B, int T, int V, int ld, const int32_t* tgt, const int32_t* tlen, const int32_t* lens,
                           int H, int cap, float* path_score, double* loglik, int32_t* ok, int32_t* first, int32_t* last,
                           float* tok_score) {

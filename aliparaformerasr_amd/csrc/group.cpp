@@ -175,6 +175,7 @@ void Group::recognize(const float* const* samples, const int64_t* n, int B, cons
   for (auto& e : eng_) {
     PF_CHECK(!(e->decode_flags() & PF_DECODE_TOPK), PF_ERR_UNSUPPORTED, "pf_group: PF_DECODE_TOPK is not available for a group forward");
     PF_CHECK(!(e->decode_flags() & PF_DECODE_ALIGN), PF_ERR_UNSUPPORTED, "pf_group: PF_DECODE_ALIGN is not available for a group forward");
+    PF_CHECK(e->nbest_search_w() == 0, PF_ERR_UNSUPPORTED, "pf_group: the n-best search is not available for a group forward");
   }
   if (B == 0) return;
   int Tg = 0;                                         // the reference pads to the BATCH maximum (PadHelper.cs:25)

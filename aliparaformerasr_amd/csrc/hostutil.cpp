@@ -813,6 +813,121 @@ int host_ctc_beam_lm(const float* blank_lp, int64_t blank_stride, const int64_t*
                        out_matched, out_loglik, cap, &lm, (double)alpha, (double)beta, lm_flags, out_lm);
 }
 
+// ------------------------------------------------------------------ n-best search (paraformer) ---------------
+int host_nbest_search(const int64_t* ids, const float* val, const int32_t* n, int L, int K, int token_num, int W, int N,
+                      const int32_t* hw_ids, const int32_t* hw_lens, int n_hw, float boost, const LmImage* lm, float alpha, float beta,
+                      int lm_flags, int32_t* out_ranks, double* out_score, double* out_loglik, double* out_lm, int32_t* out_matched) {
+  if (L < 0 || K < 1 || K > PF_TOPK_MAX || N < 1 || N > W || W > PF_NBEST_MAX)
+    throw Error(PF_ERR_INVALID_ARG, "nbest_search: bad L / K / W / N");
+  if (L > 0 && (!ids || !val || !n || !out_ranks)) throw Error(PF_ERR_INVALID_ARG, "nbest_search: null argument");
+  if (!(boost >= 0.f) || std::isinf(boost)) throw Error(PF_ERR_INVALID_ARG, "nbest_search: the boost is finite and >= 0");
+  // (stated here as in host_ctc_beam_lm: this file links without lm.cpp)
+  if (lm && (!(alpha >= 0.f) || std::isinf(alpha) || !std::isfinite(beta) || (lm_flags & ~PF_LM_EOS)))
+    throw Error(PF_ERR_INVALID_ARG, "lm: alpha is finite and >= 0, beta finite, flags known");
+  HotwordGraph graph;
+  if (n_hw != 0) build_hotword_graph(hw_ids, hw_lens, n_hw, hotword_vocab_bound(hw_ids, hw_lens, n_hw), graph);
+  const HotwordGraph* g = boost > 0.f && !graph.empty() ? &graph : nullptr;
+  const double s = (double)boost, al = (double)alpha, be = (double)beta;
+  for (int h = 0; h < N; ++h) {
+    if (out_score) out_score[h] = kNegInf;
+    if (out_loglik) out_loglik[h] = kNegInf;
+    if (out_lm) out_lm[h] = 0.0;
+    if (out_matched) out_matched[h] = 0;
+  }
+  if (L > 0) std::fill(out_ranks, out_ranks + (size_t)N * L, -1);
+  bool ok = L > 0;
+  for (int l = 0; l < L; ++l) {
+    if (n[l] < 0 || n[l] > K) throw Error(PF_ERR_INVALID_ARG, "nbest_search: n[l] outside 0 .. K");
+    if (n[l] == 0) ok = false;
+    for (int r = 0; r < n[l]; ++r) {
+      const float v = val[(size_t)l * K + r];
+      if (v != v || v == INFINITY) ok = false;
+    }
+  }
+  if (!ok) return 0;
+  const int n_free = std::min(L, std::max(token_num, 0));
+  LmView lv{};
+  if (lm) lv = lm_view(lm->words.data());
+  const int Vg = g ? (int)g->tok_col.size() : 0;
+  struct Entry { double a, g; int ls, st, m; };
+  struct Cand { double key; Entry e; int parent, r; };
+  std::vector<Entry> beam(1, Entry{0.0, 0.0, lv.start, 0, 0}), next;
+  std::vector<Cand> cand;
+  std::vector<int> order;
+  std::vector<int32_t> bp((size_t)n_free * W, 0);    // (parent slot << 8) | r per (l, slot), as the kernel keeps them
+  for (int l = 0; l < n_free; ++l) {
+    cand.clear();
+    for (int i = 0; i < (int)beam.size(); ++i)
+      for (int r = 0; r < n[l]; ++r) {
+        const Entry& p = beam[(size_t)i];
+        const int c = (int)ids[(size_t)l * K + r];
+        Cand x{0.0, p, i, r};
+        x.e.a = p.a + (double)val[(size_t)l * K + r];
+        x.key = x.e.a;
+        if (g) {
+          const int col = c >= 0 && c < Vg ? g->tok_col[(size_t)c] : -1;
+          const int e = col >= 0 ? g->table[(size_t)p.st * g->A + col] : 0;
+          x.e.st = e & 0xFFFF;
+          x.e.m = p.m + ((e >> 16) & 0xFF);
+          x.key = x.key + s * (double)(x.e.m + g->depth[(size_t)x.e.st]);
+        }
+        if (lm) {
+          x.e.ls = lm_step(lv, p.ls, c, al, be, true, x.e.g);
+          x.key = x.key + x.e.g;
+        }
+        cand.push_back(x);
+      }
+    order.resize(cand.size());
+    for (size_t j = 0; j < cand.size(); ++j) order[j] = (int)j;
+    std::sort(order.begin(), order.end(), [&](int x, int y) {   // (the candidate index i * K + r orders as the place in `cand` does)
+      return cand[(size_t)x].key != cand[(size_t)y].key ? cand[(size_t)x].key > cand[(size_t)y].key : x < y;
+    });
+    if ((int)order.size() > W) order.resize((size_t)W);
+    next.clear();
+    for (size_t slot = 0; slot < order.size(); ++slot) {
+      const Cand& x = cand[(size_t)order[slot]];
+      next.push_back(x.e);
+      bp[(size_t)l * W + slot] = (x.parent << 8) | x.r;
+    }
+    beam.swap(next);
+  }
+  const int nb = (int)beam.size();
+  std::vector<double> score((size_t)nb);
+  order.resize((size_t)nb);
+  for (int h = 0; h < nb; ++h) {
+    Entry& e = beam[(size_t)h];
+    for (int l = n_free; l < L; ++l) e.a = e.a + (double)val[(size_t)l * K];
+    double sc = e.a;
+    if (g) sc = sc + s * (double)e.m;
+    if (lm) {
+      if ((lm_flags & PF_LM_EOS) && lv.eos >= 0) lm_step(lv, e.ls, lv.eos, al, be, false, e.g);
+      sc = sc + e.g;
+    }
+    score[(size_t)h] = sc;
+    order[(size_t)h] = h;
+  }
+  std::sort(order.begin(), order.end(), [&](int x, int y) {
+    return score[(size_t)x] != score[(size_t)y] ? score[(size_t)x] > score[(size_t)y] : x < y;
+  });
+  const int nh = std::min(N, nb);
+  for (int h = 0; h < nh; ++h) {
+    int slot = order[(size_t)h];
+    const Entry& e = beam[(size_t)slot];
+    if (out_score) out_score[h] = score[(size_t)slot];
+    if (out_loglik) out_loglik[h] = e.a;
+    if (out_lm) out_lm[h] = e.g;
+    if (out_matched) out_matched[h] = e.m;
+    int32_t* rk = out_ranks + (size_t)h * L;
+    for (int l = n_free; l < L; ++l) rk[l] = 0;
+    for (int l = n_free - 1; l >= 0; --l) {
+      const int v = bp[(size_t)l * W + slot];
+      rk[l] = v & 0xFF;
+      slot = v >> 8;
+    }
+  }
+  return nh;
+}
+
 // ------------------------------------------------------------------ CTC forced alignment ---------------
 int host_ctc_align(const float* lp, int64_t ld, int T, int V, const int64_t* y, int U, float* path_score, double* loglik,
                    int32_t* first, int32_t* last, float* tok_score) {

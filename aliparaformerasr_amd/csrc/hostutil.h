@@ -114,6 +114,16 @@ int host_ctc_beam_lm(const float* blank_lp, int64_t blank_stride, const int64_t*
                      int32_t* out_len, double* out_score, int32_t* out_matched, double* out_loglik, int cap, const LmImage& lm, float alpha,
                      float beta, int lm_flags, double* out_lm);
 
+// ---- n-best search of one paraformer utterance (paraformer_hip.h "N-best search"; the definition is tests/nbest_search_ref.py) ----
+// The host twin of k_nbestsearch.hip: the top-k block ids / val [L, K], n [L] and token_num -> the N best of a position-synchronous
+// beam of width W (1 <= N <= W <= 64), optionally biased by a hot-word set (boost > 0 and a non-empty word) and fused with a
+// model (lm != nullptr).  out_ranks [N, L] (-1), out_score / out_loglik [N] (-inf), out_lm [N] (0), out_matched [N] (0): every
+// slot is written; all but out_ranks are optional.  Returns the number of hypotheses: 0 when L == 0, some n[l] == 0 or a listed
+// value is NaN or +inf (no throw).  Bit-equal to the definition and the kernel: it runs lm_step and the same table.
+int host_nbest_search(const int64_t* ids, const float* val, const int32_t* n, int L, int K, int token_num, int W, int N,
+                      const int32_t* hw_ids, const int32_t* hw_lens, int n_hw, float boost, const LmImage* lm, float alpha, float beta,
+                      int lm_flags, int32_t* out_ranks, double* out_score, double* out_loglik, double* out_lm, int32_t* out_matched);
+
 // ---- CTC forced alignment of one utterance and one target (paraformer_hip.h "CTC forced alignment"; tests/ctcalign_ref.py) ----
 // The host twin of k_ctcalign.hip: lp [T, ld] log-prob rows (V read per row), y [U] ids in [1, V) (PF_ERR_INVALID_ARG
 // otherwise; U > PF_ALIGN_MAX_TOKENS is PF_ERR_CAPACITY).  *path_score: the float32 Viterbi score, *loglik: the float64 log of

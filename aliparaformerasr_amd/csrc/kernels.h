@@ -387,6 +387,24 @@ void launch_ctc_beam_lm(hipStream_t s, const float* blank_lp, int64_t blank_stri
 // p < lens[b] from the start state; later positions are not written
 void launch_lm_walk(hipStream_t s, const int32_t* image, const int32_t* ids, const int32_t* lens, int B, int L, float alpha, float beta,
                     double* g, int32_t* state);
+// ------------------------------------------------------------------ n-best search (paraformer) ------
+// Per utterance b the N best rank vectors of a position-synchronous beam search of width W over the top-k lists ids / val
+// [B * L, K], n [B * L] (as launch_topk leaves them), free positions l < min(L, max(token_num[b], 0)), rank 0 behind them
+// (k_nbestsearch.hip; the definition is tests/nbest_search_ref.py).  1 <= N <= W <= 64, 1 <= K <= PF_TOPK_MAX.  tok_col != nullptr:
+// a hot-word set biases (tok_col [V] / table [S, A] as build_hotword_graph leaves them, boost finite and > 0); lm_image !=
+// nullptr: a language model is fused (alpha finite and >= 0, beta finite, lm_eos: the end-of-sentence step at finish).  All
+// device pointers.  bp: workspace of B * L * W int32.  out_ranks [B, N, L] (-1), out_score / out_loglik [B, N] float64 (-inf),
+// out_lm [B, N] float64 (0), out_matched [B, N] (0), n_hyp [B]: every slot is written in every form.  Nothing at or beyond
+// n[row] is read.
+struct NbestSearchArgs {
+  const int64_t* ids; const float* val; const int32_t* n; const int32_t* token_num;
+  int L, K, W, N;
+  int32_t* bp;
+  const int32_t* tok_col; const int32_t* table; int V, A; double boost;
+  const int32_t* lm_image; double alpha, beta; int lm_eos;
+  int32_t* out_ranks; double* out_score; double* out_loglik; double* out_lm; int32_t* out_matched; int32_t* n_hyp;
+};
+void launch_nbest_search(hipStream_t s, const NbestSearchArgs& a, int B);
 // ------------------------------------------------------------------ CTC forced alignment -------
 // Per job (b, h) the best CTC alignment of the target tgt[b, h, 0 .. tlen[b, h]) to the log-prob rows lp[(b * T + t) * ld + v],
 // t < min(max(len[b], 0), T), v < V, and the float64 log of the sum over all of its alignments (k_ctcalign.hip; the definition

@@ -498,6 +498,7 @@ Recognizer::Recognizer(const std::string& model, const std::string& config, cons
   engines_.push_back(make_engine());
   busy_.push_back(0);
   engine_kind_ = engines_[0]->model().kind;
+  plain_paraformer_ = engines_[0]->model().kind_id() == 0 && !engines_[0]->model().seaco;
   sv_device_prompt_ = engines_[0]->has_device_prompt();
   if (engine_kind_ == "sensevoicesmall") { sv_embed_ = engines_[0]->embed_table(); sv_use_itn_ = engines_[0]->model().use_itn; }
   feat_m_ = (conf_.lfr_m != 1 || conf_.lfr_n != 1) ? conf_.lfr_m : 1;
@@ -580,6 +581,37 @@ void Recognizer::SetLm(const std::string& arpa_path, float alpha, float beta, in
   lm_alpha_ = alpha; lm_beta_ = beta; lm_flags_ = flags;
 }
 
+void Recognizer::SetNBestSearch(int W) {
+  if (W < 0 || W > PF_NBEST_MAX) throw Error(PF_ERR_INVALID_ARG, "SetNBestSearch: W is 0 .. 64");
+  if (W > 0) { std::lock_guard<std::mutex> lk(vad_mu_); if (vad_on_) throw Error(PF_ERR_UNSUPPORTED, "SetNBestSearch: not available beside SetVad (long-audio recognition)"); }
+  if (W > 0 && !plain_paraformer_)
+    throw Error(PF_ERR_UNSUPPORTED, "SetNBestSearch: only a paraformer model has this search (SenseVoice: SetCtcBeam; SeACo: its bias decoder)");
+  search_w_ = W;
+}
+
+void Recognizer::SetNBestHotwordBoost(float boost) {
+  if (!(boost >= 0.f) || boost > 3.4028234e38f) throw Error(PF_ERR_INVALID_ARG, "SetNBestHotwordBoost: the boost is finite and >= 0");
+  if (boost > 0.f && !plain_paraformer_)
+    throw Error(PF_ERR_UNSUPPORTED, "SetNBestHotwordBoost: only a paraformer model has this search");
+  search_boost_ = boost;
+}
+
+void Recognizer::SetNBestLm(const std::string& arpa_path, float alpha, float beta, int flags) {
+  if (arpa_path.empty()) {
+    std::lock_guard<std::mutex> lk(lm_mu_);
+    search_lm_.reset();
+    return;
+  }
+  if (!plain_paraformer_) throw Error(PF_ERR_UNSUPPORTED, "SetNBestLm: only a paraformer model has this search");
+  lm_check_weights(alpha, beta, flags);
+  std::vector<const char*> toks;
+  for (auto& t : tokens_) toks.push_back(t.c_str());
+  std::shared_ptr<const LmImage> lm = lm_from_arpa(arpa_path, toks.data(), (int)toks.size(), -10.f, nullptr);   // throws before anything changes
+  std::lock_guard<std::mutex> lk(lm_mu_);
+  search_lm_ = std::move(lm);
+  search_alpha_ = alpha; search_beta_ = beta; search_flags_ = flags;
+}
+
 void Recognizer::SetNBest(int N, int K) {
   if (N < 0 || N > PF_NBEST_MAX || K < 0 || K > PF_TOPK_MAX) throw Error(PF_ERR_INVALID_ARG, "SetNBest: N is 0 .. 64, K is 0 .. 8");
   if (N == 0) {
@@ -607,6 +639,7 @@ void Recognizer::SetVad(const pf_vad_config* cfg, int batch_max, int64_t frame_b
   if (batch_max < 0 || frame_budget < 0) throw Error(PF_ERR_INVALID_ARG, "SetVad: negative batch_max or frame_budget");
   if (nbest_n_ > 0 || beam_on_ || align_on_)
     throw Error(PF_ERR_UNSUPPORTED, "SetVad: not available beside SetNBest, SetCtcBeam or SetAlign");
+  if (search_w_ > 0) throw Error(PF_ERR_UNSUPPORTED, "SetVad: not available beside SetNBestSearch");
   std::lock_guard<std::mutex> lk(vad_mu_);
   vad_on_ = true; vad_cfg_ = c;
   vad_batch_max_ = batch_max == 0 ? 32 : batch_max;
@@ -1177,6 +1210,36 @@ void Recognizer::Forward(const std::vector<Stream*>& streams) {
       if (lm && (dflags & PF_DECODE_CTC_BEAM)) e->set_ctc_lm(lm, la, lb, lf);
       else if (e->ctc_lm_on()) e->set_ctc_lm(nullptr, 0.f, 0.f, 0);
     }
+    // the n-best search (SetNBestSearch beside SetNBest(N > 1)): width, hot words and model of THIS call on this engine; the
+    // engine keeps its automaton while the set is the same and uploads the model on first use
+    const bool search_on = plain_paraformer_ && search_w_ > 0 && nbest_n_ > 1 && (dflags & PF_DECODE_TOPK);
+    if (search_on) {
+      const int n = nbest_n_;
+      e->set_nbest_search(std::max<int>(search_w_, n), n);
+      const float boost = search_boost_;
+      if (boost > 0.f) {
+        std::vector<std::vector<int32_t>> hw;
+        for (Stream* s : streams)
+          for (auto& w : s->Hotwords) hw.push_back(w);
+        if (hw.empty()) hw = hotwords_;
+        std::vector<int32_t> flat, lens;
+        for (auto& w : hw) {
+          if (w.size() == 1 && w[0] == 1) continue;   // the [sos_eos_id] terminator entry GetHotwords appends
+          flat.insert(flat.end(), w.begin(), w.end());
+          lens.push_back((int32_t)w.size());
+        }
+        e->set_nbest_hotwords(flat.data(), lens.data(), (int)lens.size(), boost);
+      } else {
+        e->set_nbest_hotwords(nullptr, nullptr, 0, 0.f);
+      }
+      std::shared_ptr<const LmImage> lm;
+      float la = 0.f, lb = 0.f;
+      int lf = 0;
+      { std::lock_guard<std::mutex> lk(lm_mu_); lm = search_lm_; la = search_alpha_; lb = search_beta_; lf = search_flags_; }
+      e->set_nbest_lm(lm, la, lb, lf);
+    } else if (e->nbest_search_w() != 0) {
+      e->set_nbest_search(0, 0);
+    }
     const bool hot_on = sv && !mc.seaco && (dflags & PF_DECODE_CTC_BEAM) && e->ctc_hotwords_on();
     const bool lm_on = sv && !mc.seaco && (dflags & PF_DECODE_CTC_BEAM) && e->ctc_lm_on();
     e->drop_thread_result();              // this call's result is read back under the same lease, not from a slot
@@ -1286,6 +1349,17 @@ void Recognizer::Forward(const std::vector<Stream*>& streams) {
         e->fetch_ctc_beam_lm(b_lm.data(), b_llsum.data());
       }
     }
+    // the n-best search's hypotheses: ranks [B, Ns, L], float64 score / loglik_sum / lm_sum, matched
+    std::vector<int32_t> s_ranks, s_hot, s_nhyp; std::vector<double> s_score, s_ll, s_lm;
+    int Ns = 0;
+    if (search_on && L > 0) {
+      int32_t nn = 0;
+      e->fetch_nbest_search(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &nn);
+      Ns = nn;
+      const size_t cells = (size_t)B * Ns;
+      s_ranks.resize(cells * L); s_hot.resize(cells); s_nhyp.resize(B); s_score.resize(cells); s_ll.resize(cells); s_lm.resize(cells);
+      e->fetch_nbest_search(s_ranks.data(), s_score.data(), s_ll.data(), s_lm.data(), s_hot.data(), s_nhyp.data(), nullptr, nullptr);
+    }
     // forced alignments (SetAlign): job 0 is the stream's own target when any stream of the batch has one, then the hypotheses
     std::vector<float> a_path, a_tok; std::vector<double> a_ll; std::vector<int32_t> a_ok, a_len, a_first, a_last;
     int Ha = 0, a_cap = 1;
@@ -1349,7 +1423,18 @@ void Recognizer::Forward(const std::vector<Stream*>& streams) {
           s->AltIds.assign(k_ids.begin() + r0 * K, k_ids.begin() + (r0 + L) * K);
           s->AltVal.assign(k_val.begin() + r0 * K, k_val.begin() + (r0 + L) * K);
         }
-        if (nbest > 1 && !sv) {
+        if (nbest > 1 && !sv && Ns > 0) {
+          // the fused order of the device search; each alternative is decoded like the host enumeration's below
+          const int got = s_nhyp[b];
+          s->Alternatives.resize((size_t)got);
+          for (int i = 0; i < got; ++i) {
+            const size_t x = (size_t)b * Ns + i;
+            Alternative& a = s->Alternatives[(size_t)i];
+            a.score = s_score[x]; a.loglik_sum = s_ll[x]; a.lm_sum = s_lm[x]; a.hot_tokens = s_hot[x];
+            a.ids.resize((size_t)L);
+            for (int l = 0; l < L; ++l) a.ids[(size_t)l] = k_ids[(r0 + l) * K + s_ranks[x * L + l]];
+          }
+        } else if (nbest > 1 && !sv) {
           std::vector<int32_t> ranks((size_t)nbest * L);
           std::vector<double> sc((size_t)nbest);
           const int n_free = std::min(L, std::max(tnum[b], 0));

@@ -206,6 +206,15 @@ class Recognizer : public std::enable_shared_from_this<Recognizer> {
   // SenseVoice: an ARPA n-gram LM fused into the beam search of SetCtcBeam (inert without it).  Loaded once against the token
   // table; every engine of the pool uploads it on first use.  An empty path clears it.
   void SetLm(const std::string& arpa_path, float alpha, float beta, int flags);
+  // Paraformer only (paraformer_hip.h "N-best search"): W = 0 off (always accepted); W in 1 .. 64: with SetNBest(N > 1, K) the
+  // n-best list comes from the beam search on the device (width max(W, N)) instead of the host enumeration, in the fused order,
+  // with score, loglik_sum, lm_sum and hot_tokens per Alternative.  Inert until SetNBest(N > 1, K).
+  void SetNBestSearch(int W);
+  // the model and the hot-word boost of that search (inert without it).  The ARPA file is read once against the token table,
+  // every engine of the pool uploads it on first use; an empty path clears it.  The hot words come from where SetHotwordBoost
+  // reads them: the union of the batch's streams' Hotwords, else the hot-word file's.  "Off" is always accepted.
+  void SetNBestLm(const std::string& arpa_path, float alpha, float beta, int flags);
+  void SetNBestHotwordBoost(float s);
   // Long-audio recognition (paraformer_hip.h "Voice-activity segmentation"): cfg != null: every GetResults that follows cuts
   // its streams into speech pieces on the device (Engine::vad_segment_device over the resident audio), plans batches of similar
   // length (host_long_plan), forwards each batch over pointers into the streams' audio and stitches one result per stream.
@@ -266,6 +275,7 @@ class Recognizer : public std::enable_shared_from_this<Recognizer> {
   bool device_streams_ = true;                                // PF_RECOGNIZER_DEVICE_STREAMS=0: always the host form
   int feat_m_ = 1;
   std::string engine_kind_; bool sv_device_prompt_ = false;
+  bool plain_paraformer_ = false;                             // a paraformer without the SeACo bias decoder: what the n-best search serves
   int creating_ = 0;                                          // engines being built outside the lock
   int device_ = 0;
   pf_engine_config ec_{};                                     // template for further engines (strings owned below)
@@ -318,6 +328,11 @@ class Recognizer : public std::enable_shared_from_this<Recognizer> {
   std::shared_ptr<const LmImage> lm_;
   float lm_alpha_ = 0.f, lm_beta_ = 0.f;
   int lm_flags_ = 0;
+  std::atomic<int> search_w_{0};        // SetNBestSearch
+  std::atomic<float> search_boost_{0.f};   // SetNBestHotwordBoost
+  std::shared_ptr<const LmImage> search_lm_;   // SetNBestLm (under lm_mu_), its weights and flags
+  float search_alpha_ = 0.f, search_beta_ = 0.f;
+  int search_flags_ = 0;
   std::atomic<bool> beam_on_{false};
   std::atomic<bool> align_on_{false};
   int extra_flags() const { return (nbest_n_ > 0 ? PF_DECODE_TOPK : 0) | (beam_on_ ? PF_DECODE_CTC_BEAM : 0) | (align_on_ ? PF_DECODE_ALIGN : 0); }

@@ -251,6 +251,46 @@ def host_ctc_beam_lm(blank_lp, ids, val, n, W, lm, alpha, beta, flags=0, hotword
     return CtcBeamResult(nh, oi, ol, sc, om, oll, olm)
 
 
+class NbestSearchResult:
+    """The hypotheses the n-best search over a paraformer's top-k lists kept (Engine.set_nbest_search / host_nbest_search /
+    op_nbest_search): n_hyp [B]; ranks [B, N, L] int32 (-1 past n_hyp[b]); score, loglik_sum [B, N] float64 (-inf), lm_sum
+    [B, N] float64 (0), matched [B, N] int32 (0): score == (loglik_sum + boost * matched) + lm_sum bit for bit."""
+
+    def __init__(self, n_hyp, ranks, score, loglik_sum, lm_sum, matched):
+        self.n_hyp, self.ranks, self.score, self.loglik_sum, self.lm_sum, self.matched = n_hyp, ranks, score, loglik_sum, lm_sum, matched
+        self.N = score.shape[-1]
+
+    def hyps(self, b=0):
+        """[(ranks tuple, score, loglik_sum, lm_sum, matched)] of utterance b, best first."""
+        return [(tuple(self.ranks[b, i].tolist()), float(self.score[b, i]), float(self.loglik_sum[b, i]), float(self.lm_sum[b, i]),
+                 int(self.matched[b, i])) for i in range(int(self.n_hyp[b]))]
+
+
+def _nbest_search_out(B, n_best, L, out):
+    if out is not None:
+        return out
+    nb = max(n_best, 0)
+    return (np.zeros((B, nb, L), np.int32), np.zeros((B, nb), np.float64), np.zeros((B, nb), np.float64), np.zeros((B, nb), np.float64),
+            np.zeros((B, nb), np.int32), np.zeros(B, np.int32))
+
+
+def host_nbest_search(ids, val, n, token_num, W, n_best=None, lm=None, alpha=0.0, beta=0.0, flags=0, hotwords=(), boost=0.0,
+                      out=None) -> NbestSearchResult:
+    """The n-best search of ONE utterance in host code (pf_host_nbest_search, the twin of the device kernel): ids / val [L, K],
+    n [L], token_num -> NbestSearchResult with B = 1.  lm: a LanguageModel or None; hotwords: sequences of ids."""
+    y = np.ascontiguousarray(ids, dtype=np.int64)
+    v = _f32(val)
+    nn = np.ascontiguousarray(n, dtype=np.int32).reshape(-1)
+    L, K = y.shape
+    n_best = W if n_best is None else n_best
+    hi, hl = _hot_arrays(hotwords)
+    rk, sc, ll, g, m, nh = _nbest_search_out(1, n_best, L, out)
+    N.check(N.load().pf_host_nbest_search(_i64p(y), _fp(v), _i32p(nn), L, K, int(token_num), int(W), int(n_best), _i32p(hi), _i32p(hl),
+                                          len(hl), float(boost), None if lm is None else lm._h, float(alpha), float(beta), int(flags),
+                                          _i32p(rk), _dp(sc), _dp(ll), _dp(g), _i32p(m), _i32p(nh)))
+    return NbestSearchResult(nh, rk, sc, ll, g, m)
+
+
 class AlignResult:
     """CTC forced alignments (PF_DECODE_ALIGN), H jobs per utterance: path_score [B, H] float32 (the Viterbi score), loglik
     [B, H] float64 (the log of the summed alignments), ok [B, H], len [B, H] (the target's length; -1: a skipped job), first /
@@ -328,7 +368,8 @@ def host_long_plan(lens, batch_max=0, frame_budget=0):
 
 class BatchResult:
     def __init__(self, token_ids, token_num, L, V, logits=None, cif_peak=None, scores=None, ctc=None, topk=None, beam=None,
-                 align=None):
+                 align=None, search=None):
+        self.search = search            # NbestSearchResult (PF_DECODE_TOPK with Engine.set_nbest_search) or None
         self.align = align              # AlignResult (Engine.set_decode(PF_DECODE_ALIGN) with targets or CTC_BEAM) or None
         self.token_ids = token_ids      # [B, L] int64
         self.token_num = token_num      # [B] int32
@@ -436,6 +477,14 @@ def _fetch_ctc_beam(lib, h, B, n_best, hot=False, lm=False):
     return CtcBeamResult(nh, ids, ln, sc, m, ll, g)
 
 
+def _fetch_nbest_search(lib, h, B):
+    ll, nn = C.c_int32(), C.c_int32()
+    N.check(lib.pf_fetch_nbest_search(h, None, None, None, None, None, None, ll, nn))
+    rk, sc, lg, g, m, nh = _nbest_search_out(B, nn.value, ll.value, None)
+    N.check(lib.pf_fetch_nbest_search(h, _i32p(rk), _dp(sc), _dp(lg), _dp(g), _i32p(m), _i32p(nh), None, None))
+    return NbestSearchResult(nh, rk, sc, lg, g, m)
+
+
 def _fetch_align(lib, h, B):
     hh, mx = C.c_int32(), C.c_int32()
     N.check(lib.pf_fetch_align(h, None, None, None, None, None, None, None, 0, hh, mx))
@@ -482,8 +531,11 @@ def _collect_result(lib, fetch_fn, call, B, want_logits, decode=None):
     align = None
     if decode is not None and decode[1] & N.PF_DECODE_ALIGN:
         align = _fetch_align(lib, decode[0], B)
+    search = None
+    if decode is not None and decode[1] & N.PF_DECODE_TOPK and len(decode) > 5 and decode[5]:
+        search = _fetch_nbest_search(lib, decode[0], B)
     N.check(fetch_fn(C.byref(out)))
-    return BatchResult(ids[:, :L].copy(), tn, L, V, logits, peak, scores, ctc, topk, beam, align)
+    return BatchResult(ids[:, :L].copy(), tn, L, V, logits, peak, scores, ctc, topk, beam, align, search)
 
 
 class Engine:
@@ -510,6 +562,7 @@ class Engine:
         self._beam_n = 16
         self._hot = False
         self._lm = None
+        self._search_w = 0
 
     def close(self):
         if getattr(self, "_h", None):
@@ -549,7 +602,7 @@ class Engine:
     # ---- forward ------------------------------------------------------------
     def _collect(self, call, B, want_logits):
         return _collect_result(self._lib, lambda o: self._lib.pf_fetch(self._h, o), call, B, want_logits,
-                               (self._h, self._decode, self._beam_n, self._hot, self._lm is not None))
+                               (self._h, self._decode, self._beam_n, self._hot, self._lm is not None, self._search_w > 0))
 
     def set_decode(self, flags: int):
         """Decoding extras of the forwards that follow (_native.PF_DECODE_SCORES | PF_DECODE_CTC; 0 = off, the reference
@@ -613,6 +666,44 @@ class Engine:
         runs the fused search: BatchResult.beam comes in the fused order with lm_sum and loglik_sum (matched 0 without hot words)."""
         N.check(self._lib.pf_engine_set_ctc_lm(self._h, None if lm is None else lm._h, float(alpha), float(beta), int(flags)))
         self._lm = lm
+
+    host_nbest_search = staticmethod(host_nbest_search)
+
+    def set_nbest_search(self, W: int = 16, n_best: int = None):
+        """The n-best search of the forwards that follow (pf_engine_set_nbest_search; paraformer only): beam width W and list
+        length n_best (1 <= n_best <= W <= 64; n_best None: W); W = 0 turns it off.  With it installed a forward with
+        PF_DECODE_TOPK runs the search behind the top-k launch: BatchResult.search."""
+        N.check(self._lib.pf_engine_set_nbest_search(self._h, int(W), int(W if n_best is None else n_best)))
+        self._search_w = int(W)
+
+    def set_nbest_lm(self, lm, alpha: float = 0.5, beta: float = 0.0, flags: int = 0):
+        """The LanguageModel of the n-best search with its weight alpha >= 0, the per-token bonus beta and flags
+        (pf_engine_set_nbest_lm; paraformer only); None clears it.  Inert until a search is installed."""
+        N.check(self._lib.pf_engine_set_nbest_lm(self._h, None if lm is None else lm._h, float(alpha), float(beta), int(flags)))
+        self._nbest_lm = lm                      # (keeps the handle alive while installed)
+
+    def set_nbest_hotwords(self, hotwords, boost: float):
+        """The hot-word set (sequences of token ids in [1, V)) and the boost per matched token (>= 0) of the n-best search
+        (pf_engine_set_nbest_hotwords; paraformer only).  An empty set or boost 0 clears it.  Inert until a search is installed."""
+        hi, hl = _hot_arrays(hotwords)
+        N.check(self._lib.pf_engine_set_nbest_hotwords(self._h, _i32p(hi), _i32p(hl), len(hl), float(boost)))
+
+    def op_nbest_search(self, ids, val, n, token_num, W, n_best=None, lm=None, alpha=0.0, beta=0.0, flags=0, hotwords=(), boost=0.0,
+                        out=None) -> NbestSearchResult:
+        """The search kernel alone on caller lists: ids / val [B, L, K], n [B, L], token_num [B].  out = (ranks [B, N, L] int32,
+        score, loglik_sum, lm_sum [B, N] float64, matched [B, N] int32, n_hyp [B] int32): write into these arrays."""
+        y = np.ascontiguousarray(ids, dtype=np.int64)
+        v = _f32(val)
+        nn = np.ascontiguousarray(n, dtype=np.int32)
+        tn = np.ascontiguousarray(token_num, dtype=np.int32).reshape(-1)
+        B, L, K = y.shape
+        n_best = W if n_best is None else n_best
+        hi, hl = _hot_arrays(hotwords)
+        rk, sc, ll, g, m, nh = _nbest_search_out(B, n_best, L, out)
+        N.check(self._lib.pf_op_nbest_search(self._h, _i64p(y), _fp(v), _i32p(nn), _i32p(tn), B, L, K, int(W), int(n_best), _i32p(hi),
+                                             _i32p(hl), len(hl), float(boost), None if lm is None else lm._h, float(alpha), float(beta),
+                                             int(flags), _i32p(rk), _dp(sc), _dp(ll), _dp(g), _i32p(m), _i32p(nh)))
+        return NbestSearchResult(nh, rk, sc, ll, g, m)
 
     def op_ctc_beam_hot(self, blank_lp, ids, val, n, lens, W, hotwords, boost, n_best=None, blank=0, cap=None, out=None) -> CtcBeamResult:
         """op_ctc_beam with a hot-word set and a boost: the biased form of the kernel on caller data.  out = (ids, len, score,

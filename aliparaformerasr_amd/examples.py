@@ -1,7 +1,7 @@
 """Command-line harness mirroring AliParaformerAsr.Examples (`-type offline` and `-type online`).
 
     python -m aliparaformerasr_amd.examples -type offline -method batch -base <dir> -model <name> \
-        [-accuracy int8] [-threads 2] [-decode ctc|frames] [-intake host|device] [-nbest N [-topk K] [-beam W [-hotboost S] [-lm FILE [-lmweight A] [-lmbonus B] [-lmeos]]]] [-align FILE|beam] [-vad [key=value,...]] -files a.wav b.wav
+        [-accuracy int8] [-threads 2] [-decode ctc|frames] [-intake host|device] [-nbest N [-topk K] [-beam W | -search W] [-hotboost S] [-lm FILE [-lmweight A] [-lmbonus B] [-lmeos]]] [-align FILE|beam] [-vad [key=value,...]] -files a.wav b.wav
     python -m aliparaformerasr_amd.examples -type online -method one -base <dir> -model <name> -files a.wav
 
 Mirrors (file:line in /root/reference/AliParaformerAsr.Examples):
@@ -30,6 +30,10 @@ hypotheses, one `nbest[i] score:<sum of log-probs> text:<text>` line each, best 
 beam search of width W in the same form; the score is the log of the summed alignments.
 `-hotboost S` (with `-nbest N -beam W`; OfflineRecognizer.SetHotwordBoost) biases that search towards the model directory's
 `hotword*.txt` by S per matched token; each `nbest[i]` line then ends in ` hot:<matched tokens> loglik_sum:<unbiased score>`.
+`-search W` (with `-nbest N`, offline, paraformer models; OfflineRecognizer.SetNBestSearch) takes the N best from a beam search
+of width W over the per-token alternatives on the device instead of the exact enumeration; `-hotboost`, `-lm`, `-lmweight`,
+`-lmbonus` and `-lmeos` then go to that search (SetNBestHotwordBoost, SetNBestLm) and decide which prefixes survive a position;
+each `nbest[i]` line ends in ` hot:<matched tokens> lm:<lm_sum> loglik_sum:<sum of log-probs>`.
 `-lm FILE [-lmweight A] [-lmbonus B] [-lmeos]` (with `-nbest N -beam W`; OfflineRecognizer.SetLm) fuses the ARPA n-gram language
 model FILE into that search with weight A (default 0.5), per-token bonus B (default 0) and, with `-lmeos`, the end-of-sentence
 step; each `nbest[i]` line then ends in ` hot:<matched tokens> lm:<lm_sum> loglik_sum:<unfused score>`.
@@ -214,7 +218,7 @@ def read_align_file(path: str) -> list:
 
 def offline_recognizer(method="one", model="paraformer-seaco-large-zh-timestamp-onnx-offline", accuracy="int8",
                        threads=2, files=None, base=None, out=sys.stdout, decode="frames", intake="host", nbest=0, topk=4,
-                       beam=0, align=None, hotboost=0.0, vad=None, lm=None, lmweight=0.5, lmbonus=0.0, lmeos=False):
+                       beam=0, align=None, hotboost=0.0, vad=None, lm=None, lmweight=0.5, lmbonus=0.0, lmeos=False, search=0):
     from .offline_recognizer import OfflineRecognizer
     base = base or os.getcwd()
     sel = select_model_files(base, model, accuracy)
@@ -233,6 +237,12 @@ def offline_recognizer(method="one", model="paraformer-seaco-large-zh-timestamp-
             rec.SetLm(lm, lmweight, lmbonus, 1 if lmeos else 0)
     elif nbest:
         rec.SetNBest(nbest, topk)
+        if search:
+            rec.SetNBestSearch(search)
+            if hotboost:
+                rec.SetNBestHotwordBoost(hotboost)
+            if lm:
+                rec.SetNBestLm(lm, lmweight, lmbonus, 1 if lmeos else 0)
     if vad is not None:
         rec.SetVad(vad["cfg"] or True, vad["batch_max"], vad["frame_budget"], vad["sep"])
     targets = None
@@ -430,7 +440,7 @@ def parse_args(argv, env=None):
             if i >= len(argv) or argv[i].lower() not in ("host", "device"):
                 raise ValueError("The intake type must be host or device")
             cfg["intake"] = argv[i].lower()
-        elif a in ("-nbest", "-topk", "-beam"):
+        elif a in ("-nbest", "-topk", "-beam", "-search"):
             lo, hi = (1, N.PF_TOPK_MAX) if a == "-topk" else (1, N.PF_NBEST_MAX)
             try:
                 i += 1
@@ -499,9 +509,13 @@ def parse_args(argv, env=None):
         raise ValueError("-beam goes with -nbest")
     if "beam" in cfg and cfg["beam"] < cfg["nbest"]:
         raise ValueError("The beam value must not be smaller than the nbest value")
-    if "hotboost" in cfg and "beam" not in cfg:
+    if "search" in cfg and "nbest" not in cfg:
+        raise ValueError("-search goes with -nbest")
+    if "search" in cfg and "beam" in cfg:
+        raise ValueError("-search (paraformer) and -beam (SenseVoice) do not go together")
+    if "hotboost" in cfg and "beam" not in cfg and "search" not in cfg:
         raise ValueError("-hotboost needs -nbest N -beam W")
-    if "lm" in cfg and "beam" not in cfg:
+    if "lm" in cfg and "beam" not in cfg and "search" not in cfg:
         raise ValueError("-lm needs -nbest N -beam W")
     if any(k in cfg for k in ("lmweight", "lmbonus", "lmeos")) and "lm" not in cfg:
         raise ValueError("-lmweight, -lmbonus and -lmeos go with -lm FILE")
@@ -534,7 +548,7 @@ def main(argv=None):
                            cfg["modelBasePath"] or None, decode=cfg.get("decode", "frames"), intake=cfg.get("intake", "host"),
                            nbest=cfg.get("nbest", 0), topk=cfg.get("topk", 4), beam=cfg.get("beam", 0), align=cfg.get("align"),
                            hotboost=cfg.get("hotboost", 0.0), vad=cfg.get("vad"), lm=cfg.get("lm"), lmweight=cfg.get("lmweight", 0.5),
-                           lmbonus=cfg.get("lmbonus", 0.0), lmeos=cfg.get("lmeos", False))
+                           lmbonus=cfg.get("lmbonus", 0.0), lmeos=cfg.get("lmeos", False), search=cfg.get("search", 0))
     else:
         print("the recognizer type must be online or offline")
         return 2

@@ -419,6 +419,27 @@ class OfflineRecognizer:
         path = None if not arpaPath else str(arpaPath).encode("utf-8")
         _ck(self._lib.pf_recognizer_set_lm(self._h, path, float(alpha), float(beta), int(flags)))
 
+    def SetNBestSearch(self, W: int) -> None:
+        """Paraformer models: the n-best list of SetNBest(N > 1, K) from a beam search of width max(W, N) over the per-token
+        alternatives on the device (inert until SetNBest; 0 turns it off, which any model accepts).  On its own it lists what
+        SetNBest lists; its purpose is SetNBestLm and SetNBestHotwordBoost, whose scores decide which prefixes survive a
+        position.  Alternatives then come in the fused order, each with Score, LogLikSum, LmSum and HotwordTokens:
+        Score == (LogLikSum + boost * HotwordTokens) + LmSum.  Text, Tokens, Timestamps, Scores and TokenAlternatives stay."""
+        _ck(self._lib.pf_recognizer_set_nbest_search(self._h, int(W)))
+
+    def SetNBestLm(self, arpaPath, alpha: float = 0.5, beta: float = 0.0, flags: int = 0) -> None:
+        """Paraformer models: an ARPA n-gram language model fused into the search of SetNBestSearch (inert without it; None or
+        "" clears it) with weight alpha >= 0, per-token bonus beta and flags.  A paraformer emits its own </s> as the last
+        token, which the model already scores as the end of the sentence: leave _native.PF_LM_EOS clear."""
+        path = None if not arpaPath else str(arpaPath).encode("utf-8")
+        _ck(self._lib.pf_recognizer_set_nbest_lm(self._h, path, float(alpha), float(beta), int(flags)))
+
+    def SetNBestHotwordBoost(self, s: float) -> None:
+        """Paraformer models: hot-word boosting inside the search of SetNBestSearch (inert without it; 0 turns it off): s per
+        token while a hypothesis spells a hot word, kept when the word completes.  The hot words are read where
+        SetHotwordBoost reads them: the streams' Hotwords (token ids), else the recognizer's hot-word file."""
+        _ck(self._lib.pf_recognizer_set_nbest_hotword_boost(self._h, float(s)))
+
     def SetAlign(self, on: bool = True) -> None:
         """SenseVoice models: CTC forced alignment on the device for every GetResults that follows (off by default).  A
         stream with a target (OfflineStream.SetAlignIds) gets OfflineStream.Alignment — where each id of the known text lies

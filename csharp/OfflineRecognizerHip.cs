@@ -362,6 +362,23 @@ namespace AliParaformerAsr.Hip
         public void SetLm(string? arpaPath, float alpha = 0.5f, float beta = 0f, int flags = 0) =>
             ParaformerHip.Check(ParaformerHip.pf_recognizer_set_lm(_r, arpaPath, alpha, beta, flags));
 
+        /// <summary>Not in the reference: paraformer models only (0 = off, which any model accepts).  The n-best list of
+        /// SetNBest(N &gt; 1, K) from a beam search of width max(W, N) over the per-token alternatives on the device (inert until
+        /// SetNBest).  Its purpose is SetNBestLm and SetNBestHotwordBoost, whose scores decide which prefixes survive a position.
+        /// Alternatives then come in the fused order, each with Score, LogLikSum, LmSum and HotwordTokens; Text, Tokens, Timestamps,
+        /// Scores and TokenAlternatives stay as they are.  Not available beside SetVad.</summary>
+        public void SetNBestSearch(int W) => ParaformerHip.Check(ParaformerHip.pf_recognizer_set_nbest_search(_r, W));
+
+        /// <summary>Not in the reference: paraformer models only.  An ARPA n-gram language model fused into the search of
+        /// SetNBestSearch (inert without it; null or "" clears it) with weight alpha, per-token bonus beta and flags.  A paraformer
+        /// emits its own end-of-sentence token, which the model already scores: leave flag 1 clear.</summary>
+        public void SetNBestLm(string? arpaPath, float alpha = 0.5f, float beta = 0f, int flags = 0) =>
+            ParaformerHip.Check(ParaformerHip.pf_recognizer_set_nbest_lm(_r, arpaPath, alpha, beta, flags));
+
+        /// <summary>Not in the reference: paraformer models only.  Hot-word boosting inside the search of SetNBestSearch (inert
+        /// without it; 0 turns it off); the hot words are read where SetHotwordBoost reads them.</summary>
+        public void SetNBestHotwordBoost(float s) => ParaformerHip.Check(ParaformerHip.pf_recognizer_set_nbest_hotword_boost(_r, s));
+
         /// <summary>Not in the reference: SenseVoice models only.  CTC forced alignment on the device for every GetResults that
         /// follows (off by default): a stream with a target (OfflineStream.SetAlignIds) gets OfflineStream.Alignment, and with
         /// SetCtcBeam every Alternative gets Timestamps of its own and LogLik.  Everything else stays as it is.</summary>

@@ -145,6 +145,23 @@ namespace AliParaformerAsr.Native
                                                                        [Out] double[] outScore, int cap, out int nHyp, int[]? hwIds, int[]? hwLens,
                                                                        int nHotwords, float boost, [Out] int[] outMatched, [Out] double[] outLoglik,
                                                                        IntPtr lm, float alpha, float beta, int flags, [Out] double[] outLm);
+        // N-best search (additions to ABI 6): a paraformer's position-synchronous beam search over its top-k lists on the device,
+        // optionally fused with a hot-word set and the n-gram LM above; with a search installed a forward with PF_DECODE_TOPK runs it
+        [DllImport(Lib)] internal static extern int pf_engine_set_nbest_search(IntPtr e, int W, int N);
+        [DllImport(Lib)] internal static extern int pf_engine_set_nbest_lm(IntPtr e, IntPtr lm, float alpha, float beta, int flags);
+        [DllImport(Lib)] internal static extern int pf_engine_set_nbest_hotwords(IntPtr e, int[]? ids, int[]? lens, int nHotwords, float boost);
+        [DllImport(Lib)] internal static extern int pf_fetch_nbest_search(IntPtr e, [Out] int[]? ranks, [Out] double[]? score, [Out] double[]? loglikSum,
+                                                                         [Out] double[]? lmSum, [Out] int[]? matched, [Out] int[]? nHyp, out int L,
+                                                                         out int N);
+        [DllImport(Lib)] internal static extern int pf_host_nbest_search(long[] ids, float[] val, int[] n, int L, int K, int tokenNum, int W, int N,
+                                                                        int[]? hwIds, int[]? hwLens, int nHotwords, float boost, IntPtr lm,
+                                                                        float alpha, float beta, int flags, [Out] int[] outRanks,
+                                                                        [Out] double[]? outScore, [Out] double[]? outLoglik, [Out] double[]? outLm,
+                                                                        [Out] int[]? outMatched, out int nHyp);
+        [DllImport(Lib)] internal static extern int pf_recognizer_set_nbest_search(IntPtr r, int W);
+        [DllImport(Lib)] internal static extern int pf_recognizer_set_nbest_lm(IntPtr r, [MarshalAs(UnmanagedType.LPUTF8Str)] string? arpaPath, float alpha,
+                                                                              float beta, int flags);
+        [DllImport(Lib)] internal static extern int pf_recognizer_set_nbest_hotword_boost(IntPtr r, float boost);
         [DllImport(Lib)] internal static extern int pf_op_ctc_beam_lm(IntPtr e, float[] blankLp, long[] ids, float[] val, int[] n, int[] lens, int B,
                                                                      int T, int K, int blank, int W, int N, [Out] long[] outIds, [Out] int[] outLen,
                                                                      [Out] double[] outScore, int cap, [Out] int[] nHyp, int[]? hwIds, int[]? hwLens,

@@ -365,8 +365,8 @@ int pf_host_ctc_beam_hot(const float* blank_lp, int64_t blank_stride, const int6
    THE IMAGE: pf_host_lm_build compiles the model into one flat image of a back-off automaton: state 0 is the empty context
    with a dense [V] lookup, every other state has an arc list sorted by token, a back-off state and weight, and next states
    are precomputed.  Its layout is private (csrc/lm_dev.h).
-   OUT OF SCOPE: paraformer / SeACo (their decoder needs a position-synchronous search of its own; pf_host_lm_score /
-   pf_op_lm_score are the building block for re-ranking their n-best), pf_group forwards, neural LMs, binary LM formats. */
+   OUT OF SCOPE HERE: a paraformer has a position-synchronous search of its own that takes the same model (see "N-best
+   search"; pf_engine_set_ctc_lm keeps refusing it); SeACo, pf_group forwards, neural LMs, binary LM formats. */
 #define PF_LM_ORDER_MAX 8
 #define PF_LM_IMAGE_BYTES_MAX (1024 * 1024 * 1024)
 #define PF_LM_EOS 1
@@ -409,6 +409,68 @@ int pf_host_ctc_beam_lm(const float* blank_lp, int64_t blank_stride, const int64
                         int32_t K, int32_t blank, int32_t W, int32_t N, int64_t* out_ids, int32_t* out_len, double* out_score,
                         int32_t cap, int32_t* n_hyp, const int32_t* hw_ids, const int32_t* hw_lens, int32_t n_hotwords, float boost,
                         int32_t* out_matched, double* out_loglik, const pf_lm* lm, float alpha, float beta, int32_t flags, double* out_lm);
+
+/* ---- N-best search (additions to ABI 6; nothing is launched, allocated or uploaded without pf_engine_set_nbest_search) ----
+   A position-synchronous beam search over a paraformer's per-position top-k lists, on the device (csrc/k_nbestsearch.hip), one
+   launch per batch, with optional hot-word and n-gram LM shallow fusion.  pf_host_nbest above is exact only because positions
+   are independent; a language model couples them, so the fused n-best is no re-ranking of the acoustic one: the model decides
+   which prefixes survive a position.  Opt-in, absent from the reference.  The definition in Python is tests/nbest_search_ref.py.
+   INPUTS per utterance: the top-k block exactly as pf_fetch_topk returns it (ids [L, K], val [L, K] float32, n [L]);
+   n_free = min(L, max(token_num, 0)); 1 <= N <= W <= PF_NBEST_MAX, K <= PF_TOPK_MAX; optionally a hot-word set with a boost s
+   (automaton, m, d, bias and bonus as in "CTC hot words", read over an id sequence) and a model with alpha, beta and flags (g,
+   the context, PF_LM_EOS, transparent ids, unk and oov as in "CTC language model").  fp32 inputs are widened; all scores are
+   float64; alpha * x and s * integer are exact products and every + is ONE rounded addition in the order written; nothing
+   transcendental is evaluated.  So the definition, the host twin and the kernel agree BIT FOR BIT on every input, ties
+   included: no decision-gap condition is needed.
+   BEAM: an ordered list of at most W entries (rank prefix, a, LM state, g, hot-word state, m), at first
+   [((), +0.0, start, +0.0, root, 0)].
+   POSITION l < n_free: beam entry i in rank order and list rank r < n[l] make candidate index i * K + r with c = ids[l, r]:
+     a' = a + val[l, r]; one LM step on c gives g'; one automaton step on c gives m', d';
+     key = (a' + s * (m' + d')) + g'       (the hot-word term only with a set that biases, the g term only with a model)
+   No candidate is discarded; -inf orders like any other value.  The W best by key stay, ties to the smaller candidate index;
+   that order is the new beam's order.  There is no merging: the ids of a list are distinct, so distinct candidates spell
+   distinct sequences.
+   POSITIONS n_free <= l < L: every entry takes rank 0, a = a + val[l, 0], in order; the LM and the hot words do not see these
+   ids (as pf_host_nbest keeps them at the 1-best id).
+   FINISH: with PF_LM_EOS and an eos id one eos step without beta; score = (a + s * m) + g_final (the pending part d is
+   revoked); re-ordered by descending score, ties to the smaller beam rank; the first N entries are the hypotheses, each with
+   ranks [L], score, loglik_sum = a, lm_sum = g_final, matched = m:
+     score == (loglik_sum + s * matched) + lm_sum bit for bit.
+   NO HYPOTHESES: n_hyp = 0 when L = 0, when some n[l] == 0 for l < L, or when a listed value is NaN or +inf — in the kernel and
+   in the twin alike (the twin does not throw here).
+   CONSEQUENCES: with no set and alpha = beta = 0 every score is the pf_host_nbest score of that rank vector bit for bit; with
+   W >= N the list is pf_host_nbest's list whenever no two hypotheses tie (only the tie rules differ); with W >= K ^ n_free
+   nothing is pruned and the list is the brute-force enumeration sorted by score.
+   THE MODEL'S OWN </s>: a paraformer emits its </s> id as the last free position and an ARPA file maps </s> to the eos id, so
+   that position is already scored as P(</s> | h).  PF_LM_EOS would add a second one: the flag is allowed, leaving it clear is
+   recommended.
+   OUT OF SCOPE: SeACo (its bias decoder stays the hot-word route), SenseVoice (it has the CTC search), the streaming path,
+   pf_group forwards, neural LMs and binary LM formats, merging hypotheses by text. */
+/* W = 0 turns the search off; else 1 <= N <= W <= PF_NBEST_MAX (PF_ERR_INVALID_ARG).  Paraformer only: PF_ERR_UNSUPPORTED for
+   a SenseVoice or SeACo model.  There is no decode bit of its own (bits 4 and 64 stay invalid): with a search installed a
+   forward with PF_DECODE_TOPK runs it right behind the top-k launch, K being pf_engine_set_topk's.  token_ids,
+   pf_fetch_scores, pf_fetch_topk and pf_host_nbest are what they are without it.  A pf_group forward over an engine with a
+   search installed answers PF_ERR_UNSUPPORTED; the streaming path does not run it. */
+int pf_engine_set_nbest_search(pf_engine* e, int32_t W, int32_t N);
+/* The model and the hot-word set of the search: argument rules, refusals, the one-time upload and "NULL / 0 clears" are those of
+   pf_engine_set_ctc_lm / pf_engine_set_ctc_hotwords, for a paraformer instead of a SenseVoice model.  Inert until a search is
+   installed.  (pf_engine_set_ctc_lm, pf_engine_set_ctc_hotwords and PF_DECODE_CTC_BEAM keep refusing a paraformer.) */
+int pf_engine_set_nbest_lm(pf_engine* e, const pf_lm* lm, float alpha, float beta, int32_t flags);
+int pf_engine_set_nbest_hotwords(pf_engine* e, const int32_t* ids, const int32_t* lens, int32_t n_hotwords, float boost);
+/* ranks [B, N, L] int32 (-1 past n_hyp), score / loglik_sum [B, N] float64 (-inf past n_hyp), lm_sum [B, N] float64 (0),
+   matched [B, N] int32 (0), n_hyp [B] of the calling thread's last forward, each optional; *L_out and *N_out (optional): the
+   L of that forward and the N in force at it.  Slot rules as pf_fetch_ctc_beam (call it BEFORE the pf_fetch that receives
+   token_ids).  PF_ERR_INVALID_ARG when that forward ran without a search. */
+int pf_fetch_nbest_search(pf_engine* e, int32_t* ranks, double* score, double* loglik_sum, double* lm_sum, int32_t* matched,
+                          int32_t* n_hyp, int32_t* L_out, int32_t* N_out);
+/* The same search for ONE utterance in plain host code (the twin of the kernel: it runs the same LM step and the same
+   automaton table).  hw_* / boost: a hot-word set (n_hotwords == 0 or boost == 0: none; ids in [1, 2^24)); lm (NULL: none)
+   with alpha, beta, flags.  out_ranks [N, L], out_score / out_loglik / out_lm [N], out_matched [N] filled as above (all but
+   out_ranks optional), *n_hyp.  PF_ERR_INVALID_ARG: bad K / W / N, n[l] outside 0 .. K, a bad boost or weight. */
+int pf_host_nbest_search(const int64_t* ids, const float* val, const int32_t* n, int32_t L, int32_t K, int32_t token_num, int32_t W,
+                         int32_t N, const int32_t* hw_ids, const int32_t* hw_lens, int32_t n_hotwords, float boost, const pf_lm* lm,
+                         float alpha, float beta, int32_t flags, int32_t* out_ranks, double* out_score, double* out_loglik,
+                         double* out_lm, int32_t* out_matched, int32_t* n_hyp);
 
 /* ---- CTC forced alignment (additions to ABI 6; nothing is launched or allocated without the flag) ----------------------
    PF_DECODE_ALIGN (pf_engine_set_decode; SenseVoice only, every math_mode; implies SCORES, not TOPK; independent of
@@ -656,6 +718,13 @@ int pf_op_ctc_beam_lm(pf_engine* e, const float* blank_lp, const int64_t* ids, c
                       double* out_score, int32_t cap, int32_t* n_hyp, const int32_t* hw_ids, const int32_t* hw_lens,
                       int32_t n_hotwords, float boost, int32_t* out_matched, double* out_loglik, const pf_lm* lm, float alpha,
                       float beta, int32_t flags, double* out_lm);
+/* The n-best search kernel alone on caller-supplied lists for a batch: ids / val [B, L, K], n [B, L], token_num [B]; the
+   outputs [B, ...] as pf_fetch_nbest_search fills them (none optional).  The device outputs are sentinel-filled before the
+   launch: PF_ERR_DEVICE when a cell comes back unwritten. */
+int pf_op_nbest_search(pf_engine* e, const int64_t* ids, const float* val, const int32_t* n, const int32_t* token_num, int32_t B,
+                       int32_t L, int32_t K, int32_t W, int32_t N, const int32_t* hw_ids, const int32_t* hw_lens, int32_t n_hotwords,
+                       float boost, const pf_lm* lm, float alpha, float beta, int32_t flags, int32_t* out_ranks, double* out_score,
+                       double* out_loglik, double* out_lm, int32_t* out_matched, int32_t* n_hyp);
 /* lm_walk_kernel (csrc/k_lm.hip), the device twin of pf_host_lm_score: ids [B, L], lens [B] -> g [B, L] float64 and state
    [B, L] after every token p < lens[b]; positions past a length are not written. */
 int pf_op_lm_score(pf_engine* e, const pf_lm* lm, const int32_t* ids, const int32_t* lens, int32_t B, int32_t L, float alpha, float beta,
@@ -1007,6 +1076,22 @@ int pf_stream_alternative_hot(pf_stream* s, int32_t i, int32_t* hotword_tokens, 
    stay the greedy ones.  Errors as pf_host_lm_from_arpa and pf_engine_set_ctc_lm (the installed model stays). */
 int pf_recognizer_set_lm(pf_recognizer* r, const char* arpa_path, float alpha, float beta, int32_t flags);
 int pf_stream_alternative_lm(pf_stream* s, int32_t i, double* lm_sum, double* loglik_sum);
+/* Paraformer only (see "N-best search"; PF_ERR_UNSUPPORTED for a SenseVoice or SeACo model; "off" — W = 0, boost = 0, a NULL or
+   empty path — is always accepted).  pf_recognizer_set_nbest_search: W = 0 off, else 1 .. PF_NBEST_MAX: with
+   pf_recognizer_set_nbest(N > 1, K) in force (inert until then) every engine of the pool, present and future, runs the beam
+   search of width max(W, N) on the device and Alternatives come from its result block in the FUSED order — the host
+   enumeration (pf_host_nbest) is skipped — each decoded by the same DecodeMulti, with its score, and hotword_tokens /
+   loglik_sum / lm_sum through pf_stream_alternative_hot / pf_stream_alternative_lm: score == (loglik_sum + boost *
+   hotword_tokens) + lm_sum bit for bit (lm_sum 0 without a model).  Text, Tokens, Timestamps, Scores and TokenAlternatives are
+   untouched.  PF_ERR_UNSUPPORTED beside pf_recognizer_set_vad, whichever is set second.
+   pf_recognizer_set_nbest_lm: an ARPA file read once against the recognizer's token table (as pf_recognizer_set_lm; each engine
+   uploads it on first use), alpha, beta, flags as pf_engine_set_nbest_lm.  pf_recognizer_set_nbest_hotword_boost: boost per
+   matched token of a hot word (finite, >= 0); the hot words of a GetResults call come from where pf_recognizer_set_hotword_boost
+   reads them: the union of its streams' Hotwords, else the hot-word file's.  pf_recognizer_set_lm,
+   pf_recognizer_set_hotword_boost and pf_recognizer_set_ctc_beam keep refusing a paraformer. */
+int pf_recognizer_set_nbest_search(pf_recognizer* r, int32_t W);
+int pf_recognizer_set_nbest_lm(pf_recognizer* r, const char* arpa_path, float alpha, float beta, int32_t flags);
+int pf_recognizer_set_nbest_hotword_boost(pf_recognizer* r, float boost);
 int pf_stream_set_align_ids(pf_stream* s, const int64_t* ids, int32_t n);
 int pf_stream_alignment(pf_stream* s, const int32_t** begin_end, const float** tok_score, int32_t* n, float* path_score,
                         double* loglik, int32_t* ok);
