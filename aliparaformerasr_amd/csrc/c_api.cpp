@@ -1055,6 +1055,17 @@ int pf_op_gemm_ex(pf_engine* h, const pf_gemm_desc* d, const float* A, const flo
   return PF_OK;
   PF_CATCH
 }
+int pf_op_gemm_panel(pf_engine* h, int32_t M, int32_t N, int32_t out_kind, int32_t form, int32_t padded, const float* bias, const float* A,
+                     const float* W, float* C) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  NEED(A); NEED(W); NEED(C);
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->op_gemm_panel(M, N, out_kind, form, padded, bias, A, W, C);
+  return PF_OK;
+  PF_CATCH
+}
 int pf_op_gemm_rc(pf_engine* h, const pf_gemm_rc_desc* d, const float* A, const float* W, float* x_out, float* n16_out,
                   float* n32_out) {
   PF_TRY

@@ -59,6 +59,7 @@ Engine::Engine(const pf_engine_config& cfg) {
   { const char* e = getenv("PF_QKV_FILL"); if (e && e[0]) qkv_split_min_fill_ = atoi(e); }
   { const char* e = getenv("PF_FFN_MIN"); if (e && e[0]) ffn_fused_min_rows_ = atoi(e); }
   { const char* e = getenv("PF_DEC_MID"); if (e && e[0]) dec_mid_ = e[0] != '0'; }     // the decoder's middle as the launches it replaces (tests compare both forms)
+  { const char* e = getenv("PF_GEMM_PANEL"); if (e && e[0]) gemm_panel_ = e[0] != '0'; }   // the panel-resident K = 512 GEMM (tests compare both forms)
 
   // host-only validation BEFORE anything is uploaded (a bad am.mvn must not cost a 0.9 GB upload per retry)
   std::vector<float> shift, scale;
@@ -603,6 +604,14 @@ void Engine::load_weights(const pf_engine_config& cfg) {
   PF_CHECK(dec_.out.N == mc_.vocab && dec_.out.K == D && dec_.final_w1.K == D && dec_.final_w1.N == mc_.ffn &&
                dec_.final_w2.N == D && dec_.final_w2.K == dec_.final_w1.N,
            PF_ERR_FORMAT, "weights: decoder.final / decoder.output shapes");
+  // the K | V projection of all layers and the vocabulary layer in the fragment order of the panel-resident kernel
+  // (k_gemm_panel.hip; f16 mode only — the row-major weights stay: the tiled and short-input kernels read them)
+  if (gemm_panel_ && !fp32_mode_ && !int8_mode_)
+    for (Lin* l : {&dec_.kv_all, &dec_.out})
+      if (l->w && l->N > 0 && l->K == 512 && l->Kpad == 512) {
+        l->w_panel = (half_t*)dalloc(gemm_panel_image_bytes(l->N));
+        launch_gemm_panel_retile(stream_, l->w, l->Kpad, l->N, l->w_panel);
+      }
   // SeACo: hotword embedder (Embedding + LSTM stack) and the bias decoder
   if (mc_.seaco) {
     const Tensor& ew = tensor("seaco.embed.weight");
@@ -810,6 +819,7 @@ void Engine::gemm(const char* cls, const Lin& w, const half_t* A, int lda, int M
   g.out_padded = 1;   // every pipeline buffer is carved with round_up(rows,128)+128 rows
   g.out_blocked = blocked == 1; g.a_blocked = blocked == 2;
   g.small_ws = small_ws_;
+  g.W_panel = gemm_panel_ ? w.w_panel : nullptr;
   prof_begin(cls, 2.0 * M * (double)w.N * w.K);
   launch_gemm(stream_, g);
   prof_end(cls);

@@ -43,6 +43,7 @@ struct Lin {          // y = x W^T + b ; W stored f16 [Npad][Kpad]
   const float* bias = nullptr;
   int N = 0, K = 0, Kpad = 0;
   const float* w32 = nullptr;         // the fp32 tensor [N][K] as stored in the container (fp32 parity mode)
+  half_t* w_panel = nullptr;          // the weight in the fragment order of gemm_panel_kernel (k_gemm_panel.hip; null: not built)
 };
 struct LNp { const float* g = nullptr; const float* b = nullptr; int D = 0; };
 // a Linear as onnxruntime's quantize_dynamic stores it (math_mode 2): w' = w_q - 128 as signed bytes [Npad][Kpad], K-contiguous
@@ -259,6 +260,7 @@ class Engine {
   void op_argmax(const float* x, int64_t rows, int V, int64_t* ids);
   void op_gemm(const float* A, const float* W, const float* bias, int M, int N, int K, int epi, float* C);
   void op_gemm_ex(const pf_gemm_desc& d, const float* A, const float* W, float* C);
+  void op_gemm_panel(int M, int N, int out_kind, int form, int padded, const float* bias, const float* A, const float* W, float* C);
   void op_linear32(const float* x, const float* W, const float* bias, const float* resid, int M, int N, int K, bool relu, float* y);
   void op_ffn32(const float* x, const float* W1, const float* b1, const float* W2, const float* b2, int M, int D, int F, float* y);
   void op_gemm_rc(const pf_gemm_rc_desc& d, const float* A, const float* W, float* x_out, float* n16_out, float* n32_out);
@@ -424,6 +426,7 @@ class Engine {
   void own_hardware_queue_ts();
   void own_hardware_queue();         // round 6: the main stream must not share a hardware queue with another live engine's (see engine.cpp)
   bool dec_mid_ = true;              // PF_DEC_MID: finishing pass + norm2 + FSMN + residual + norm3 + q-projection in one launch (k_decmid.hip)
+  bool gemm_panel_ = true;           // PF_GEMM_PANEL: the K | V and vocabulary products on the panel-resident kernel where its rule admits them (0: gemm_f16_pp3)
   int ffn_fused_min_rows_ = 1200;    // PF_FFN_MIN: below, 64-row tiles leave most CUs idle and the persistent kernels tie or win (tools/mid_rows.py)
   int qkv_split_min_tiles_ = 256;    // PF_QKV_MIN: least number of 256 x 192 tiles for which the split form is chosen
   int qkv_split_min_fill_ = 60;      // PF_QKV_FILL: ... and least fill (percent) of its rounds of tiles (85 was the break-even with ONE step in

@@ -719,6 +719,76 @@ void Engine::op_gemm_ex(const pf_gemm_desc& ds, const float* A, const float* W, 
   }
 }
 
+// The K = 512 product  C = A W^T + bias  on the panel-resident kernel (form 7) or, for comparison, on gemm_f16_pp3 (form 1 / 2 =
+// 128- / 256-row tiles) or by launch_gemm's rule (form 0), with the hosts at their most hostile: the A rows behind M - 1 and
+// the W rows behind N - 1 hold NaNs, the result (out_kind 0: fp32, ld = round_up(N, 4); 1: f16, ld = N + 64) sits in a
+// sentinel-filled buffer in which nothing but [M, N] may change — unless `padded` declares the rows up to round_up(M, 256)
+// writable, as the pipeline's buffers are.
+void Engine::op_gemm_panel(int M, int N, int out_kind, int form, int padded, const float* bias, const float* A, const float* W, float* C) {
+  PF_HIP(hipSetDevice(device_));
+  constexpr int K = 512;
+  PF_CHECK(M > 0 && N > 0, PF_ERR_INVALID_ARG, "gemm_panel: empty problem");
+  PF_CHECK(out_kind == 0 || out_kind == 1, PF_ERR_INVALID_ARG, "gemm_panel: out_kind must be 0 (fp32) or 1 (f16)");
+  PF_CHECK(form == 0 || form == 1 || form == 2 || form == 7, PF_ERR_INVALID_ARG, "gemm_panel: form must be 0, 1, 2 or 7");
+  const int64_t Mp = round_up(M, 256) + 128, Np = round_up(N, 256);
+  const int ld = out_kind == 1 ? N + 64 : (int)round_up(N, 4);
+  PF_CHECK(ld % 4 == 0, PF_ERR_INVALID_ARG, "gemm_panel: the f16 form needs N % 4 == 0");
+  const size_t esz = out_kind == 1 ? 2 : 4;
+  size_t off = 0;
+  const Carve carve{off};
+  const size_t oA = carve((size_t)M * K * 4), oW = carve((size_t)N * K * 4), ob = carve((size_t)N * 4);
+  const size_t oA16 = carve((size_t)Mp * K * 2), oW16 = carve((size_t)Np * K * 2), oI = carve(gemm_panel_image_bytes(N));
+  const size_t oC = carve((size_t)Mp * ld * esz);
+  ensure(ws_tmp_, off);
+  char* base = (char*)ws_tmp_.p;
+  PF_HIP(hipMemsetD16Async((hipDeviceptr_t)(base + oA16), 0x7E00, (size_t)Mp * K, stream_));     // NaN behind the operands
+  PF_HIP(hipMemsetD16Async((hipDeviceptr_t)(base + oW16), 0x7E00, (size_t)Np * K, stream_));
+  PF_HIP(hipMemcpyAsync(base + oA, A, (size_t)M * K * 4, hipMemcpyHostToDevice, stream_));
+  launch_f32_to_f16(stream_, (const float*)(base + oA), M, K, K, (half_t*)(base + oA16), K);
+  PF_HIP(hipMemcpyAsync(base + oW, W, (size_t)N * K * 4, hipMemcpyHostToDevice, stream_));
+  launch_f32_to_f16(stream_, (const float*)(base + oW), N, K, K, (half_t*)(base + oW16), K);
+  launch_gemm_panel_retile(stream_, (const half_t*)(base + oW16), K, N, (half_t*)(base + oI));
+  if (bias) PF_HIP(hipMemcpyAsync(base + ob, bias, (size_t)N * 4, hipMemcpyHostToDevice, stream_));
+  if (out_kind == 0) fill_sentinel32(stream_, base + oC, (size_t)Mp * ld);
+  else fill_sentinel16(stream_, base + oC, (size_t)Mp * ld);
+  GemmArgs g{};
+  g.A = (half_t*)(base + oA16); g.lda = K; g.W = (half_t*)(base + oW16); g.ldw = K; g.W_panel = (half_t*)(base + oI);
+  g.bias = bias ? (const float*)(base + ob) : nullptr;
+  g.M = M; g.N = N; g.K = K;
+  g.out_padded = padded ? 1 : 0;
+  g.force_mi = form;
+  if (out_kind == 0) { g.out_f32 = (float*)(base + oC); g.ldc32 = ld; }
+  else { g.out_f16 = (half_t*)(base + oC); g.ldc16 = ld; }
+  static const int reps = [] { const char* e = getenv("PF_OP_REPEAT"); return e ? std::max(1, atoi(e)) : 1; }();   // tools/: warm-cache timing
+  for (int r = 0; r < reps; ++r) {
+    prof_begin(r == 0 ? "gemm_op" : "gemm_op_warm", 2.0 * M * (double)N * K);
+    launch_gemm(stream_, g);
+    prof_end(r == 0 ? "gemm_op" : "gemm_op_warm");
+  }
+  std::vector<char> h((size_t)Mp * ld * esz);
+  PF_HIP(hipMemcpyAsync(h.data(), base + oC, h.size(), hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipStreamSynchronize(stream_));
+  const int64_t guard = padded ? round_up(M, 256) : M;
+  for (int64_t m = 0; m < Mp; ++m)
+    for (int n = 0; n < ld; ++n) {
+      const size_t i = (size_t)m * ld + n;
+      const bool is_sent = out_kind == 1 ? reinterpret_cast<const uint16_t*>(h.data())[i] == kSentinel16
+                                         : reinterpret_cast<const uint32_t*>(h.data())[i] == kSentinel32;
+      const char* why = nullptr;
+      if (m < M && n < N) { if (is_sent) why = "was not written"; }
+      else if (n >= N) { if (!is_sent) why = "was written: a column beyond N"; }
+      else if (m >= guard && !is_sent) why = "was written: a row the destination does not declare writable";
+      if (why)
+        throw Error(PF_ERR_DEVICE, "gemm_panel (" + std::to_string(M) + " x " + std::to_string(N) + ", ld " + std::to_string(ld) + "): cell (" +
+                                       std::to_string(m) + ", " + std::to_string(n) + ") " + why);
+    }
+  for (int m = 0; m < M; ++m)
+    for (int n = 0; n < N; ++n) {
+      const size_t i = (size_t)m * ld + n;
+      C[(size_t)m * N + n] = out_kind == 1 ? (float)reinterpret_cast<const half_t*>(h.data())[i] : reinterpret_cast<const float*>(h.data())[i];
+    }
+}
+
 void Engine::op_gemm_rc(const pf_gemm_rc_desc& ds, const float* A, const float* W, float* x_out, float* n16_out,
                         float* n32_out) {
   PF_HIP(hipSetDevice(device_));

@@ -799,6 +799,16 @@ void launch_gemm(hipStream_t s, const GemmArgs& a) {
   PF_CHECK(!a.out_blocked || (a.out_f16 && !a.out_f32 && !a.resid && !a.add2 && a.out_padded && a.N % 64 == 0),
            PF_ERR_INVALID_ARG, "gemm: blocked output needs an f16-only padded result with N % 64 == 0");
   PF_CHECK(!a.a_blocked || a.K % 64 == 0, PF_ERR_INVALID_ARG, "gemm: blocked A operand needs K % 64 == 0");
+  {
+    // K = 512 with a fragment-ordered weight image: the panel-resident kernel (k_gemm_panel.hip); short inputs stay below
+    const bool can = gemm_panel_applicable(a);
+    PF_CHECK(a.force_mi != 7 || can, PF_ERR_INVALID_ARG, "gemm: the panel-resident kernel does not apply to this problem");
+    const int min_rows = std::max(gemm_panel_min_rows(), a.small_ws ? gemm_small_max_rows() : 0);
+    if (can && (a.force_mi == 7 || (a.force_mi == 0 && a.M > min_rows))) {
+      launch_gemm_panel(s, a, device_cus());
+      return;
+    }
+  }
   if (a.force_mi == 4 || (a.force_mi == 0 && a.small_ws && a.M <= gemm_small_max_rows() && !a.out_blocked && !a.a_blocked)) {
     // short inputs: one-shot bricks over the whole device instead of a handful of tiles walking K (k_gemm_small.hip)
     GemmSmallArgs g{};

@@ -40,8 +40,19 @@ struct GemmArgs {
   int k_wrap, a_wrap, w_wrap; float wrap_scale;
   int force_mi;                  // 0 = choose by shape; 1 / 2 = 128- / 256-row tiles of gemm_f16_pp3, 4 = the short-input kernel, 5 = the persistent 256 x 256 kernel (blocked result)
                                  // (stand-alone op tests; 4 / 5 fail when that kernel does not apply)
+                                 // 7 = the panel-resident kernel (k_gemm_panel.hip; fails where gemm_panel_applicable is false)
+  const half_t* W_panel;         // optional: launch_gemm_panel_retile image of W (K = 512): the panel-resident kernel may take the problem
 };
 void launch_gemm(hipStream_t s, const GemmArgs& a);
+// panel-resident kernel for K = 512 (k_gemm_panel.hip): a workgroup keeps 128 rows of A in LDS and streams the weights of its
+// share of N from a fragment-ordered image; bias + f16 (ldc16) or fp32 (ldc32) row-major result, rows >= M and columns >= N
+// are never written; results bit-identical to gemm_f16_pp3's for the same arguments
+size_t gemm_panel_image_bytes(int N);
+void launch_gemm_panel_retile(hipStream_t s, const half_t* W, int ldw, int N, half_t* img);   // W [N, ldw >= 512]; pad rows of the image are zeros
+bool gemm_panel_applicable(const GemmArgs& a);
+int gemm_panel_min_rows();                       // rows above which launch_gemm chooses it (PF_PANEL_M)
+int gemm_panel_shares(int panels, int N, int cus);
+void launch_gemm_panel(hipStream_t s, const GemmArgs& a, int cus);
 // name of the kernel the calling thread's most recent GEMM launcher chose (bench.py prints it next to the class it
 // reports as `roofline`; the same name appears in the rocprofv3 kernel trace)
 const char* last_gemm_kernel();

@@ -1108,6 +1108,18 @@ class Engine:
         N.check(self._lib.pf_op_gemm_ex(self._h, C.byref(d), _fp(A), _fp(W), _fp(out)))
         return out
 
+    def op_gemm_panel(self, A, W, bias=None, f16_out=False, form=7, padded=False) -> np.ndarray:
+        """A [M,512] W [N,512]^T + bias on the panel-resident kernel (form 7), gemm_f16_pp3 (1 / 2) or by the rule (0)."""
+        A, W = _f32(A), _f32(W)
+        M, K = A.shape
+        Nn = W.shape[0]
+        assert K == 512 and W.shape[1] == 512
+        b = _f32(bias) if bias is not None else None
+        out = np.zeros((M, Nn), np.float32)
+        N.check(self._lib.pf_op_gemm_panel(self._h, M, Nn, int(f16_out), form, int(padded), _fp(b) if b is not None else None,
+                                           _fp(A), _fp(W), _fp(out)))
+        return out
+
     def op_gemm_rc(self, A, W, bias=None, resid=None, fsmn_v=None, fsmn_w=None, T=0, ln=None, a_blocked=False,
                    want_x=True, want_n16=True, want_n32=True, short_input=False):
         """Row-complete GEMM (N = 512) + fused epilogue; returns (x, n16, n32) (n* = None without `ln`).

@@ -774,6 +774,14 @@ typedef struct pf_gemm_desc {
 } pf_gemm_desc;
 /* C [M,N] fp32 (f16 results widened, blocked results de-blocked on the host). */
 int pf_op_gemm_ex(pf_engine* e, const pf_gemm_desc* d, const float* A, const float* W, float* C);
+/* The K = 512 product C [M,N] = A [M,512] W [N,512]^T + bias (bias may be NULL) as the decoder's K | V projection and the
+   vocabulary layer launch it.  form: 7 = the panel-resident kernel, 1 / 2 = gemm_f16_pp3 with 128- / 256-row tiles, 0 = by the
+   pipeline's rule.  out_kind: 0 = fp32 result (row stride round_up(N, 4)), 1 = f16 result (row stride N + 64; N % 4 == 0),
+   widened into C.  padded != 0 declares the result rows up to round_up(M, 256) writable, as the pipeline's buffers are.  The
+   operand rows behind M - 1 / N - 1 hold NaNs and the result buffer is guarded: PF_ERR_DEVICE when a cell of [M, N] was
+   not written or any other cell was.                                                                                 */
+int pf_op_gemm_panel(pf_engine* e, int32_t M, int32_t N, int32_t out_kind, int32_t form, int32_t padded, const float* bias,
+                     const float* A, const float* W, float* C);
 /* Row-complete GEMM (N = 512) with its fused epilogue, as the encoder launches it for the attention output
    projection and the FFN down-projection: x = resid + A W^T + bias + FSMN_k(v) ; n = LayerNorm(x). */
 typedef struct pf_gemm_rc_desc {
