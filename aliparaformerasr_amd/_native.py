@@ -275,6 +275,8 @@ SIGNATURES = {
     "pf_op_ffn_fused": (C.c_int, [_vp, _f, _f, _f, _f, _f, _f, _f, _f, C.c_int32, _f, _f]),
     "pf_op_dec_ffn_fused": (C.c_int, [_vp, C.c_void_p, _f, _f, _f]),
     "pf_op_attn_ffn_fused": (C.c_int, [_vp, _vp, _f, _f]),
+    "pf_op_dec_mid": (C.c_int, [_vp, C.c_void_p, _f, _f, _f, _f, _i32]),
+    "pf_op_fsmn_dec_ln": (C.c_int, [_vp, _f, _f, _i32, C.c_int32, C.c_int32, C.c_int32, _f, _f, _f, _f, _f]),
     "pf_op_fsmn_enc": (C.c_int, [_vp, _f, _f, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f]),
     "pf_op_linear32": (C.c_int, [_vp, _f, _f, _f, _f, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f]),
     "pf_op_ffn32": (C.c_int, [_vp, _f, _f, _f, _f, _f, C.c_int32, C.c_int32, C.c_int32, _f]),
@@ -389,6 +391,13 @@ class PfDecFfnDesc(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("M", C.c_int32), ("splits", C.c_int32), ("reserved", C.c_int32)] + \
                [(n, C.POINTER(C.c_float)) for n in ("x", "w1", "b1", "gamma_f", "beta_f", "w2", "ln_gamma", "ln_beta",
                                                     "ctx", "wo", "bo", "resid", "ln1_gamma", "ln1_beta")]
+
+
+class PfDecMidDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("struct_size", "B", "L", "splits", "form", "reserved")] + \
+               [(n, C.POINTER(C.c_int32) if n == "token_num" else C.POINTER(C.c_float))
+                for n in ("a", "w1", "b1", "gamma_f", "beta_f", "w2", "n2_gamma", "n2_beta", "taps", "token_num", "x",
+                          "n3_gamma", "n3_beta", "wq", "bq")]
 
 
 class PfError(RuntimeError):

@@ -1121,6 +1121,32 @@ int pf_op_dec_ffn_fused(pf_engine* h, const pf_dec_ffn_desc* d, float* t_out, fl
   return PF_OK;
   PF_CATCH
 }
+int pf_op_dec_mid(pf_engine* h, const pf_dec_mid_desc* d, float* x_out, float* q_out, float* tn_out, float* xn16_out, int32_t* ran) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  NEED(d);
+  PF_CHECK(d->struct_size == (int32_t)sizeof(pf_dec_mid_desc), PF_ERR_INVALID_ARG, "pf_dec_mid_desc.struct_size mismatch");
+  PF_CHECK(d->reserved == 0, PF_ERR_INVALID_ARG, "pf_dec_mid_desc.reserved must be 0");
+  NEED(d->a); NEED(d->w1); NEED(d->b1); NEED(d->gamma_f); NEED(d->beta_f); NEED(d->w2); NEED(d->n2_gamma); NEED(d->n2_beta);
+  NEED(d->taps); NEED(d->token_num); NEED(d->x); NEED(d->n3_gamma); NEED(d->n3_beta); NEED(d->wq); NEED(d->bq);
+  NEED(x_out); NEED(q_out); NEED(ran);
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->op_dec_mid(*d, x_out, q_out, tn_out, xn16_out, ran);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_op_fsmn_dec_ln(pf_engine* h, const float* tn, const float* taps, const int32_t* token_num, int32_t B, int32_t L, int32_t k,
+                      const float* x, const float* gamma, const float* beta, float* x_out, float* xn16_out) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  NEED(tn); NEED(taps); NEED(token_num); NEED(x); NEED(gamma); NEED(beta); NEED(x_out);
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->op_fsmn_dec_ln(tn, taps, token_num, B, L, k, x, gamma, beta, x_out, xn16_out);
+  return PF_OK;
+  PF_CATCH
+}
 int pf_op_attn_ffn_fused(pf_engine* h, const pf_attn_ffn_desc* d, float* x_out, float* n16_out) {
   PF_TRY
   std::shared_ptr<Engine> eh_ = E(h);

@@ -269,6 +269,9 @@ class Engine {
   void op_qlinear(const float* x, const float* W, const float* bias, int M, int N, int K, int relu, int x_is_f16, float* y,
                   uint8_t* xq_out, float* aparams_out, uint8_t* wq_out, float* wscale_out, int32_t* wzp_out);
   void op_dec_ffn_fused(const pf_dec_ffn_desc& ds, float* t_out, float* n_out, float* x_out);
+  void op_dec_mid(const pf_dec_mid_desc& ds, float* x_out, float* q_out, float* tn_out, float* xn16_out, int32_t* ran);
+  void op_fsmn_dec_ln(const float* tn, const float* taps, const int32_t* token_num, int B, int L, int k, const float* x, const float* gamma,
+                      const float* beta, float* x_out, float* xn16_out);
   void op_ffn_fused(const float* x, const float* w1, const float* b1, const float* w2, const float* b2, const float* resid,
                     const float* g, const float* be, int M, float* x_out, float* n16_out, const pf_attn_ffn_desc* op = nullptr);
   void op_ffn(const float* x, const float* w1, const float* b1, const float* w2, const float* b2, const float* resid,

@@ -18,6 +18,9 @@ namespace pf {
 // finite f16 pattern instead of zeros (the K pad columns stay zero: that IS the contract), and every output buffer is
 // pre-filled with a NaN-payload sentinel: after the launch every cell of [M, N] must have been written, nothing may have
 // changed in columns [N, ld) or in rows at or beyond round_up(M, 256) (the 128 spare rows the ops carve are the guard).
+// The layer ops (dec_ffn_fused, ffn_fused / attn_ffn_fused, dec_mid, fsmn_dec_ln) check the tighter contracts kernels.h states
+// for their kernels: no store at or beyond row M (round_up(M, 64) for the blocked Q | K and V of the encoder tail), the fp32
+// residual's rows behind M - 1 hostile as well, sentinel bytes behind the split form's workspace.
 namespace {
 constexpr uint32_t kSentinel32 = 0x7FC5A5A5u;
 constexpr uint16_t kSentinel16 = 0x7E5Au;
@@ -50,14 +53,15 @@ void fill_sentinel16(hipStream_t s, void* p, size_t count) { PF_HIP(hipMemsetD16
 
 // U = uint32_t (fp32 buffers) / uint16_t (f16): rows x ld cells of a buffer that was sentinel-filled before the launch.
 // blocked: the blocked activation layout (ld == N).  written = false: the buffer was not sentinel-filled inside [M, N]
-// (a result that aliases its residual), only the guard rows and columns are checked.
+// (a result that aliases its residual), only the guard rows and columns are checked.  guard_row: the first row that must not
+// have been written (-1: round_up(M, 256), the padding the GEMM kernels declare; the layer kernels declare M or round_up(M, 64)).
 template <class U>
 void check_guard(hipStream_t s, const char* op, const char* what, const void* dev, U sentinel, int64_t rows, int M, int N, int ld,
-                 bool blocked, bool written = true) {
+                 bool blocked, bool written = true, int64_t guard_row = -1) {
   std::vector<U> h((size_t)rows * ld);
   PF_HIP(hipMemcpyAsync(h.data(), dev, h.size() * sizeof(U), hipMemcpyDeviceToHost, s));
   PF_HIP(hipStreamSynchronize(s));
-  const int64_t guard = round_up(M, 256);
+  const int64_t guard = guard_row >= 0 ? guard_row : round_up(M, 256);
   auto at = [&](int64_t m, int n) -> U {
     return blocked ? h[(((size_t)(m >> 5) * (N >> 3) + (n >> 3)) * 32 + (m & 31)) * 8 + (n & 7)] : h[(size_t)m * ld + n];
   };
@@ -70,9 +74,27 @@ void check_guard(hipStream_t s, const char* op, const char* what, const void* de
       const bool is_sent = at(m, n) == sentinel;
       if (m < M && n < N) { if (written && is_sent) fail("was not written", m, n); }
       else if (n >= N) { if (!is_sent) fail("was written: a column beyond N", m, n); }
-      else if (m >= guard && !is_sent) fail("was written: a row at or beyond round_up(M, 256)", m, n);
+      else if (m >= guard && !is_sent) fail(guard_row >= 0 ? "was written: a row the kernel's contract (kernels.h) calls never written"
+                                                           : "was written: a row at or beyond round_up(M, 256)", m, n);
     }
 }
+// rows [row0, row1) of a row-major fp32 matrix [*, ld]: a large finite pattern (+-2^100 .. 2^101), as fill_hostile_rows
+void fill_hostile_rows32(hipStream_t s, float* base, int ld, int64_t row0, int64_t row1) {
+  if (row1 <= row0) return;
+  std::vector<float> h((size_t)(row1 - row0) * ld);
+  for (size_t i = 0; i < h.size(); ++i) h[i] = std::ldexp(1.0f + (float)((i * 37u) & 0x3FFu) / 1024.0f, 100) * ((i & 1u) ? -1.0f : 1.0f);
+  PF_HIP(hipMemcpyAsync(base + (size_t)row0 * ld, h.data(), h.size() * 4, hipMemcpyHostToDevice, s));
+  PF_HIP(hipStreamSynchronize(s));
+}
+// a sentinel-filled fp32 buffer (bytes % 4 == 0) that nothing may have touched
+void check_untouched32(hipStream_t s, const char* op, const char* what, const void* dev, size_t bytes) {
+  std::vector<uint32_t> h(bytes / 4);
+  PF_HIP(hipMemcpyAsync(h.data(), dev, h.size() * 4, hipMemcpyDeviceToHost, s));
+  PF_HIP(hipStreamSynchronize(s));
+  for (size_t i = 0; i < h.size(); ++i)
+    if (h[i] != kSentinel32) throw Error(PF_ERR_DEVICE, std::string(op) + ": " + what + ": word " + std::to_string(i) + " was written");
+}
+constexpr size_t kWsGuard = 4096;                             // sentinel bytes behind a kernel's workspace
 }  // namespace
 
 // ------------------------------------------------------------------ stand-alone ops -------
@@ -956,14 +978,21 @@ void Engine::op_dec_ffn_fused(const pf_dec_ffn_desc& ds, float* t_out, float* n_
   const Carve carve{off};
   const size_t o32 = carve((size_t)std::max<int64_t>((int64_t)M * D, (int64_t)F * D) * 4);
   const size_t ox16 = carve((size_t)Mp * D * 2), ow1 = carve((size_t)F * D * 2), ow2 = carve((size_t)D * F * 4);
-  const size_t oimg = carve(ffn_dec_image_bytes()), ows = carve(ffn_dec_workspace_bytes(M, splits));
+  const size_t wsb = ffn_dec_workspace_bytes(M, splits);
+  const size_t oimg = carve(ffn_dec_image_bytes()), ows = carve(wsb + kWsGuard);
   const size_t ob1 = carve((size_t)F * 4), ogf = carve((size_t)F * 4), obf = carve((size_t)F * 4), og = carve((size_t)D * 4), obe = carve((size_t)D * 4);
-  const size_t ot = carve((size_t)M * D * 4), on = carve((size_t)M * D * 4);
+  const size_t ot = carve((size_t)Mp * D * 4), on = carve((size_t)Mp * D * 4);
   const size_t owo = carve((size_t)D * D * 2), owot = carve(ffn_outproj_weight_bytes()), obo = carve((size_t)D * 4);
   const size_t og1 = carve((size_t)D * 4), obe1 = carve((size_t)D * 4), oxr = carve((size_t)Mp * D * 4), oxo = carve((size_t)Mp * D * 4);
   ensure(ws_tmp_, off);
   char* base = (char*)ws_tmp_.p;
-  PF_HIP(hipMemsetAsync(base + ox16, 0, (size_t)Mp * D * 2, stream_));
+  // a hostile host (see the top of the file): the operand rows behind M - 1 hold the large finite pattern, the residual's too,
+  // every output and the bytes behind the workspace are sentinel-filled and checked against kernels.h's contract
+  fill_hostile_rows(stream_, (half_t*)(base + ox16), D, M, Mp, D);
+  fill_sentinel32(stream_, base + ot, (size_t)Mp * D);
+  fill_sentinel32(stream_, base + on, (size_t)Mp * D);
+  fill_sentinel32(stream_, base + oxo, (size_t)Mp * D);
+  fill_sentinel32(stream_, base + ows + wsb, kWsGuard / 4);
   auto up16 = [&](const float* src, int rows, int cols, size_t dst, int ldo) {
     PF_HIP(hipMemcpyAsync(base + o32, src, (size_t)rows * cols * 4, hipMemcpyHostToDevice, stream_));
     launch_f32_to_f16(stream_, (const float*)(base + o32), rows, cols, cols, (half_t*)(base + dst), ldo);
@@ -982,7 +1011,7 @@ void Engine::op_dec_ffn_fused(const pf_dec_ffn_desc& ds, float* t_out, float* n_
     up16(ds.wo, D, D, owo, D);
     launch_ffn_retile_out(stream_, (const half_t*)(base + owo), D, (half_t*)(base + owot));
     up(ds.bo, D, obo); up(ds.ln1_gamma, D, og1); up(ds.ln1_beta, D, obe1);
-    PF_HIP(hipMemsetAsync(base + oxr, 0, (size_t)Mp * D * 4, stream_));
+    fill_hostile_rows32(stream_, (float*)(base + oxr), D, M, Mp);
     up(ds.resid, (size_t)M * D, oxr);
     f.A = nullptr; f.ctx = (const half_t*)(base + ox16); f.lda_c = D; f.Wot = (const half_t*)(base + owot); f.bo = (const float*)(base + obo);
     f.resid = (const float*)(base + oxr); f.ldr = D; f.out_x = (float*)(base + oxo); f.ldx = D;
@@ -998,6 +1027,10 @@ void Engine::op_dec_ffn_fused(const pf_dec_ffn_desc& ds, float* t_out, float* n_
     launch_ffn_dec(stream_, f);
     prof_end(r == 0 ? "gemm_op" : "gemm_op_warm");
   }
+  if (f.t32) check_guard<uint32_t>(stream_, "dec_ffn_fused", "t", base + ot, kSentinel32, Mp, M, D, D, false, true, M);
+  if (f.n32) check_guard<uint32_t>(stream_, "dec_ffn_fused", "the LayerNorm result", base + on, kSentinel32, Mp, M, D, D, false, true, M);
+  if (op) check_guard<uint32_t>(stream_, "dec_ffn_fused", "x_out", base + oxo, kSentinel32, Mp, M, D, D, false, true, M);
+  check_untouched32(stream_, "dec_ffn_fused", "the bytes behind ffn_dec_workspace_bytes", base + ows + wsb, kWsGuard);
   if (t_out) PF_HIP(hipMemcpyAsync(t_out, base + ot, (size_t)M * D * 4, hipMemcpyDeviceToHost, stream_));
   if (n_out) PF_HIP(hipMemcpyAsync(n_out, base + on, (size_t)M * D * 4, hipMemcpyDeviceToHost, stream_));
   if (x_out && op) PF_HIP(hipMemcpyAsync(x_out, base + oxo, (size_t)M * D * 4, hipMemcpyDeviceToHost, stream_));
@@ -1028,6 +1061,8 @@ void Engine::op_ffn_fused(const float* x, const float* w1, const float* b1, cons
   char* base = (char*)ws_tmp_.p;
   PF_HIP(hipMemsetAsync(base + ox16, 0, (size_t)Mp * D * 2, stream_));
   PF_HIP(hipMemsetAsync(base + oxr, 0, (size_t)Mp * D * 4, stream_));
+  fill_hostile_rows32(stream_, (float*)(base + oxr), D, M, Mp);       // the residual rows behind M - 1 are never read (kernels.h)
+  if (tail) { fill_sentinel16(stream_, base + oqk, (size_t)Mp * 2 * D); fill_sentinel16(stream_, base + ovo, (size_t)Mp * D); }
   auto up16 = [&](const float* src, int rows, int cols, size_t dst, int ldo) {
     PF_HIP(hipMemcpyAsync(base + o32, src, (size_t)rows * cols * 4, hipMemcpyHostToDevice, stream_));
     launch_f32_to_f16(stream_, (const float*)(base + o32), rows, cols, cols, (half_t*)(base + dst), ldo);
@@ -1089,8 +1124,12 @@ void Engine::op_ffn_fused(const float* x, const float* w1, const float* b1, cons
     launch_ffn_fused(stream_, f);
     prof_end(r == 0 ? "gemm_op" : "gemm_op_warm");
   }
-  if (f.out_x) check_guard<uint32_t>(stream_, "ffn_fused", "x", base + oxo, kSentinel32, Mp, M, D, D, false);
-  if (f.out_n16) check_guard<uint16_t>(stream_, "ffn_fused", "the f16 LayerNorm result", base + on16, kSentinel16, Mp, M, D, D, false);
+  if (f.out_x) check_guard<uint32_t>(stream_, "ffn_fused", "x", base + oxo, kSentinel32, Mp, M, D, D, false, true, M);
+  if (f.out_n16) check_guard<uint16_t>(stream_, "ffn_fused", "the f16 LayerNorm result", base + on16, kSentinel16, Mp, M, D, D, false, true, M);
+  if (tail) {
+    check_guard<uint16_t>(stream_, "attn_ffn_fused", "the blocked Q | K", base + oqk, kSentinel16, Mp, M, 2 * D, 2 * D, true, true, round_up(M, 64));
+    check_guard<uint16_t>(stream_, "attn_ffn_fused", "V", base + ovo, kSentinel16, Mp, M, D, D, false, true, round_up(M, 64));
+  }
   if (x_out) PF_HIP(hipMemcpyAsync(x_out, base + oxo, (size_t)M * D * 4, hipMemcpyDeviceToHost, stream_));
   std::vector<half_t> n16;
   if (f.out_n16) {
@@ -1159,6 +1198,184 @@ void Engine::op_fsmn_dec(const float* tn, const float* w, const int32_t* token_n
                   (float*)(base + ox));
   PF_HIP(hipMemcpyAsync(x, base + ox, n * 4, hipMemcpyDeviceToHost, stream_));
   PF_HIP(hipStreamSynchronize(stream_));
+}
+
+// The fused decoder FSMN + norm3 kernel (k_norm.hip fsmn_dec_ln_kernel<11 | 21>) alone, on a hostile host: the rows of tn at
+// l >= token_num[b] hold a large finite pattern (the kernel must mask them, not multiply them by zero), x and xn16 sit in
+// sentinel-guarded buffers, and a row of x at l >= token_num[b] must come back with the bits it went in with.
+void Engine::op_fsmn_dec_ln(const float* tn, const float* taps, const int32_t* token_num, int B, int L, int k, const float* x, const float* gamma,
+                            const float* beta, float* x_out, float* xn16_out) {
+  PF_HIP(hipSetDevice(device_));
+  constexpr int D = 512;
+  PF_CHECK(B > 0 && L > 0 && (k == 11 || k == 21), PF_ERR_INVALID_ARG, "fsmn_dec_ln: B, L > 0 and k = 11 | 21");
+  const int M = B * L;
+  const int64_t Mp = (int64_t)M + 64;
+  size_t off = 0;
+  const Carve carve{off};
+  const size_t ot = carve((size_t)Mp * D * 4), ox = carve((size_t)Mp * D * 4), on16 = carve((size_t)Mp * D * 2), ow = carve((size_t)k * D * 4);
+  const size_t og = carve((size_t)D * 4), ob = carve((size_t)D * 4), onum = carve((size_t)B * 4);
+  ensure(ws_tmp_, off);
+  char* base = (char*)ws_tmp_.p;
+  fill_hostile_rows32(stream_, (float*)(base + ot), D, 0, Mp);
+  for (int b = 0; b < B; ++b) {
+    const int nv = std::min(std::max(token_num[b], 0), L);
+    if (nv) PF_HIP(hipMemcpyAsync(base + ot + (size_t)b * L * D * 4, tn + (size_t)b * L * D, (size_t)nv * D * 4, hipMemcpyHostToDevice, stream_));
+  }
+  fill_sentinel32(stream_, base + ox, (size_t)Mp * D);
+  fill_sentinel16(stream_, base + on16, (size_t)Mp * D);
+  PF_HIP(hipMemcpyAsync(base + ox, x, (size_t)M * D * 4, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipMemcpyAsync(base + ow, taps, (size_t)k * D * 4, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipMemcpyAsync(base + og, gamma, (size_t)D * 4, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipMemcpyAsync(base + ob, beta, (size_t)D * 4, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipMemcpyAsync(base + onum, token_num, (size_t)B * 4, hipMemcpyHostToDevice, stream_));
+  prof_begin("gemm_op", 0);                       // ("gemm_" classes record the kernel the launcher notes)
+  const bool ran = launch_fsmn_dec_ln(stream_, (const float*)(base + ot), (const float*)(base + ow), (const int32_t*)(base + onum), B, L, D, k,
+                                      (float*)(base + ox), (const float*)(base + og), (const float*)(base + ob), (half_t*)(base + on16));
+  prof_end("gemm_op");
+  PF_CHECK(ran, PF_ERR_UNSUPPORTED, "fsmn_dec_ln: the launcher declined the geometry");
+  check_guard<uint32_t>(stream_, "fsmn_dec_ln", "x", base + ox, kSentinel32, Mp, M, D, D, false, false, M);
+  check_guard<uint16_t>(stream_, "fsmn_dec_ln", "the f16 LayerNorm result", base + on16, kSentinel16, Mp, M, D, D, false, true, M);
+  std::vector<half_t> n16((size_t)M * D);
+  PF_HIP(hipMemcpyAsync(x_out, base + ox, (size_t)M * D * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipMemcpyAsync(n16.data(), base + on16, n16.size() * 2, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipStreamSynchronize(stream_));
+  for (int b = 0; b < B; ++b)
+    for (int l = std::max(token_num[b], 0); l < L; ++l)
+      PF_CHECK(std::memcmp(x_out + ((size_t)b * L + l) * D, x + ((size_t)b * L + l) * D, (size_t)D * 4) == 0, PF_ERR_DEVICE,
+               "fsmn_dec_ln: x changed at utterance " + std::to_string(b) + ", position " + std::to_string(l) + " >= token_num");
+  if (xn16_out)
+    for (size_t i = 0; i < n16.size(); ++i) xn16_out[i] = (float)n16[i];
+}
+
+// The middle of a decoder layer in the three forms the engine can run it (include/paraformer_hip.h pf_op_dec_mid), on a
+// hostile host: operand rows behind M - 1 hold the large finite pattern, x / q / tn / xn16 sit in sentinel-guarded buffers
+// (q with a row stride of 520 halves), the bytes behind the split form's workspace are guarded, and a row of x at
+// l >= token_num[b] must come back with the bits it went in with.
+void Engine::op_dec_mid(const pf_dec_mid_desc& ds, float* x_out, float* q_out, float* tn_out, float* xn16_out, int32_t* ran_out) {
+  PF_HIP(hipSetDevice(device_));
+  constexpr int D = 512, F = 2048, K = 11, LDQ = 520;
+  const int B = ds.B, L = ds.L, splits = ds.splits, form = ds.form;
+  PF_CHECK(B > 0 && L > 0, PF_ERR_INVALID_ARG, "dec_mid: B and L must be positive");
+  PF_CHECK(splits == 0 || splits == 1 || splits == 2 || splits == 3 || splits == 4 || splits == 8, PF_ERR_INVALID_ARG,
+           "dec_mid: splits must be 0 (automatic) | 1 | 2 | 3 | 4 | 8");
+  PF_CHECK(form == 0 || form == 1 || form == 2, PF_ERR_INVALID_ARG, "dec_mid: form must be 0, 1 or 2");
+  const int M = B * L;
+  const int64_t Mp = round_up(M, 256) + 128;
+  const size_t wsb = ffn_dec_workspace_bytes(M, splits);
+  size_t off = 0;
+  const Carve carve{off};
+  const size_t o32 = carve((size_t)std::max<int64_t>((int64_t)M * D, (int64_t)F * D) * 4);
+  const size_t oa16 = carve((size_t)Mp * D * 2), ow1 = carve((size_t)F * D * 2), ow2 = carve((size_t)D * F * 4);
+  const size_t oimg = carve(ffn_dec_image_bytes()), ows = carve(wsb + kWsGuard);
+  const size_t ob1 = carve((size_t)F * 4), ogf = carve((size_t)F * 4), obf = carve((size_t)F * 4);
+  const size_t og2 = carve((size_t)D * 4), ob2 = carve((size_t)D * 4), og3 = carve((size_t)D * 4), ob3 = carve((size_t)D * 4);
+  const size_t otap = carve((size_t)K * D * 4), onum = carve((size_t)B * 4), ox = carve((size_t)Mp * D * 4);
+  const size_t owq = carve((size_t)D * D * 2), owqt = carve(ffn_outproj_weight_bytes()), obq = carve((size_t)D * 4);
+  const size_t oq = carve((size_t)Mp * LDQ * 2), otn = carve((size_t)Mp * D * 4), oxn = carve((size_t)Mp * D * 2);
+  ensure(ws_tmp_, off);
+  char* base = (char*)ws_tmp_.p;
+  auto up16 = [&](const float* src, int rows, int cols, size_t dst) {
+    PF_HIP(hipMemcpyAsync(base + o32, src, (size_t)rows * cols * 4, hipMemcpyHostToDevice, stream_));
+    launch_f32_to_f16(stream_, (const float*)(base + o32), rows, cols, cols, (half_t*)(base + dst), cols);
+    PF_HIP(hipStreamSynchronize(stream_));
+  };
+  auto up = [&](const void* src, size_t n, size_t dst) { PF_HIP(hipMemcpyAsync(base + dst, src, n * 4, hipMemcpyHostToDevice, stream_)); };
+  fill_hostile_rows(stream_, (half_t*)(base + oa16), D, M, Mp, D);
+  fill_sentinel32(stream_, base + ows + wsb, kWsGuard / 4);
+  fill_sentinel32(stream_, base + ox, (size_t)Mp * D);
+  fill_sentinel16(stream_, base + oq, (size_t)Mp * LDQ);
+  fill_sentinel32(stream_, base + otn, (size_t)Mp * D);
+  fill_sentinel16(stream_, base + oxn, (size_t)Mp * D);
+  up16(ds.a, M, D, oa16); up16(ds.w1, F, D, ow1); up16(ds.wq, D, D, owq);
+  up(ds.w2, (size_t)D * F, ow2); up(ds.b1, F, ob1); up(ds.gamma_f, F, ogf); up(ds.beta_f, F, obf);
+  up(ds.n2_gamma, D, og2); up(ds.n2_beta, D, ob2); up(ds.n3_gamma, D, og3); up(ds.n3_beta, D, ob3);
+  up(ds.taps, (size_t)K * D, otap); up(ds.token_num, B, onum); up(ds.x, (size_t)M * D, ox); up(ds.bq, D, obq);
+  launch_ffn_dec_retile(stream_, (const half_t*)(base + ow1), D, (const float*)(base + ow2), (const float*)(base + ogf),
+                        (const float*)(base + obf), (const float*)(base + ob1), (half_t*)(base + oimg));
+  launch_ffn_retile_out(stream_, (const half_t*)(base + owq), D, (half_t*)(base + owqt));
+  const float qscale = 1.0f / std::sqrt(128.0f);
+  FfnDecArgs f{};
+  f.A = (const half_t*)(base + oa16); f.lda = D; f.img = (const half_t*)(base + oimg); f.ws = base + ows; f.M = M; f.splits = splits;
+  f.eps_hidden = 1e-12f; f.eps = 1e-12f;
+  const int32_t* num = (const int32_t*)(base + onum);
+  float* xd = (float*)(base + ox);
+  float* tn = (float*)(base + otn);
+  half_t* xn = (half_t*)(base + oxn);
+  half_t* q16 = (half_t*)(base + oq);
+  bool ran = true;
+  if (form == 0) {
+    f.no_finish = true;
+    prof_begin("gemm_op", 4.0 * M * (double)D * F);
+    launch_ffn_dec(stream_, f);
+    prof_end("gemm_op");
+    // what launch_dec_mid must not use (kernels.h): of every share the partial rows and statistics of the masked positions and of
+    // the rows behind M - 1 — overwritten with the hostile pattern between the two launches
+    {
+      const int S = splits > 0 ? splits : ffn_dec_splits(M);
+      const int64_t Mq = round_up(M, 64);
+      float* part = (float*)(base + ows);
+      float* stats = part + (size_t)S * Mq * D;
+      for (int sh = 0; sh < S; ++sh) {
+        for (int b = 0; b <= B; ++b) {
+          const int64_t r0 = b < B ? (int64_t)b * L + std::min(std::max(ds.token_num[b], 0), L) : M, r1 = b < B ? (int64_t)(b + 1) * L : Mq;
+          fill_hostile_rows32(stream_, part + (size_t)sh * Mq * D, D, r0, r1);
+          fill_hostile_rows32(stream_, stats + (size_t)sh * Mq * 2, 2, r0, r1);
+        }
+      }
+    }
+    DecMidArgs m{};
+    m.ws = base + ows; m.img = f.img; m.splits = splits; m.eps_hidden = 1e-12f;
+    m.n2_g = (const float*)(base + og2); m.n2_b = (const float*)(base + ob2); m.eps2 = 1e-12f;
+    m.fsmn_wT = (const float*)(base + otap); m.k = K; m.token_num = num; m.B = B; m.L = L; m.x = xd;
+    m.n3_g = (const float*)(base + og3); m.n3_b = (const float*)(base + ob3);
+    m.Wqt = (const half_t*)(base + owqt); m.bq = (const float*)(base + obq); m.qscale = qscale; m.q16 = q16; m.ldq = LDQ;
+    prof_begin("gemm_op_mid", 2.0 * M * (double)D * D);
+    ran = launch_dec_mid(stream_, m);
+    prof_end("gemm_op_mid");
+  } else {
+    f.ln_g = (const float*)(base + og2); f.ln_b = (const float*)(base + ob2); f.n32 = tn; f.ldn32 = D;
+    prof_begin("gemm_op", 4.0 * M * (double)D * F);
+    launch_ffn_dec(stream_, f);
+    prof_end("gemm_op");
+    check_guard<uint32_t>(stream_, "dec_mid", "tn", base + otn, kSentinel32, Mp, M, D, D, false, true, M);
+    if (form == 1) {
+      prof_begin("gemm_op_mid", 0);
+      const bool fused = launch_fsmn_dec_ln(stream_, tn, (const float*)(base + otap), num, B, L, D, K, xd, (const float*)(base + og3),
+                                            (const float*)(base + ob3), xn);
+      prof_end("gemm_op_mid");
+      PF_CHECK(fused, PF_ERR_UNSUPPORTED, "dec_mid: the fused FSMN + LayerNorm launch declined the geometry");
+    } else {
+      launch_fsmn_dec(stream_, tn, (const float*)(base + otap), num, B, L, D, K, xd);
+      launch_layernorm(stream_, xd, M, D, (const float*)(base + og3), (const float*)(base + ob3), xn, D, nullptr, 0);
+    }
+    check_guard<uint16_t>(stream_, "dec_mid", "xn16", base + oxn, kSentinel16, Mp, M, D, D, false, true, M);
+    Lin Lq;
+    Lq.w = (half_t*)(base + owq); Lq.bias = (const float*)(base + obq); Lq.N = D; Lq.K = D; Lq.Kpad = D;
+    gemm("gemm_dec_q", Lq, xn, D, M, nullptr, 0, q16, LDQ, nullptr, 0, nullptr, 0, false, D, qscale);
+  }
+  if (ran_out) *ran_out = ran ? 1 : 0;
+  if (!ran) return;
+  check_guard<uint32_t>(stream_, "dec_mid", "x", base + ox, kSentinel32, Mp, M, D, D, false, false, M);
+  // (the q GEMM of forms 1 and 2 declares its destination padded to round_up(M, 256) rows, the fused kernel declares nothing)
+  check_guard<uint16_t>(stream_, "dec_mid", "q", base + oq, kSentinel16, Mp, M, D, LDQ, false, true, form == 0 ? (int64_t)M : -1);
+  check_untouched32(stream_, "dec_mid", "the bytes behind ffn_dec_workspace_bytes", base + ows + wsb, kWsGuard);
+  std::vector<half_t> h16((size_t)M * LDQ);
+  PF_HIP(hipMemcpyAsync(x_out, base + ox, (size_t)M * D * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipMemcpyAsync(h16.data(), base + oq, h16.size() * 2, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipStreamSynchronize(stream_));
+  for (int m = 0; m < M; ++m)
+    for (int n = 0; n < D; ++n) q_out[(size_t)m * D + n] = (float)h16[(size_t)m * LDQ + n];
+  for (int b = 0; b < B; ++b)
+    for (int l = std::max(ds.token_num[b], 0); l < L; ++l)
+      PF_CHECK(std::memcmp(x_out + ((size_t)b * L + l) * D, ds.x + ((size_t)b * L + l) * D, (size_t)D * 4) == 0, PF_ERR_DEVICE,
+               "dec_mid: x changed at utterance " + std::to_string(b) + ", position " + std::to_string(l) + " >= token_num");
+  if (form != 0) {
+    if (tn_out) PF_HIP(hipMemcpy(tn_out, base + otn, (size_t)M * D * 4, hipMemcpyDeviceToHost));
+    if (xn16_out) {
+      PF_HIP(hipMemcpy(h16.data(), base + oxn, (size_t)M * D * 2, hipMemcpyDeviceToHost));
+      for (size_t i = 0; i < (size_t)M * D; ++i) xn16_out[i] = (float)h16[i];
+    }
+  }
 }
 
 // The (Bi)LSTM recurrence through the functions the heads call (lstm_recurrence16 / lstm_steps16 / lstm_ring_x3 / lstm_fp32_steps):

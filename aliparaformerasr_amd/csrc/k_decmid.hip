@@ -321,6 +321,7 @@ bool launch_dec_mid(hipStream_t s, const DecMidArgs& a) {
     set_max_lds((const void*)dec_mid_kernel<11>, (int)dec_mid_lds_bytes(11));
   });
   const dim3 grid((unsigned)(a.B * cdiv(a.L, DM_R)));
+  note_gemm_kernel("dec_mid_kernel<11>");
   hipLaunchKernelGGL(dec_mid_kernel<11>, grid, dim3(512), dec_mid_lds_bytes(11), s, d);
   PF_HIP(hipGetLastError());
   return true;

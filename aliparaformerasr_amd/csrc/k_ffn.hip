@@ -1109,8 +1109,9 @@ void launch_ffn_fused(hipStream_t s, const FfnFusedArgs& a) {
   const bool op = a.ctx != nullptr;
   PF_CHECK(!a.Wqt || (op && a.bq && a.out_qk && a.out_v && a.ldvo % 8 == 0 && a.ln_g), PF_ERR_INVALID_ARG,
            "ffn_fused: the Q | K | V tail needs the out-projection form, the next LayerNorm, bias and both outputs");
-  PF_CHECK(!op || (a.Wot && a.bo && a.fsmn_v && a.fsmn_wT && a.ln2_g && a.ln2_b && a.lda_c % 8 == 0 && a.ldv % 4 == 0 && d.T >= 8),
+  PF_CHECK(!op || (a.Wot && a.bo && a.fsmn_v && a.fsmn_wT && a.ln2_g && a.ln2_b && a.lda_c % 8 == 0 && a.ldv % 4 == 0),
            PF_ERR_INVALID_ARG, "ffn_fused: the out-projection form needs ctx, Wo, bias, the V slice, FSMN taps and norm2");
+  PF_CHECK(!op || d.T >= 8, PF_ERR_INVALID_ARG, "ffn_fused: the fused FSMN memory needs utterances of T >= 8 rows");
   PF_CHECK(op || a.A, PF_ERR_INVALID_ARG, "ffn_fused: missing operand");
   static int abl = 0;
   static DeviceOnce once;

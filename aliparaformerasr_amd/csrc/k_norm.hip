@@ -386,6 +386,7 @@ bool launch_fsmn_dec_ln(hipStream_t s, const float* tn, const float* wT, const i
   const int64_t waves = (int64_t)B * ((L + FDL_ROWS - 1) / FDL_ROWS);
   if (waves == 0) return true;
   const dim3 grid((unsigned)((waves + 3) / 4)), block(256);
+  note_gemm_kernel(k == 11 ? "fsmn_dec_ln_kernel<11>" : "fsmn_dec_ln_kernel<21>");
   if (k == 11) hipLaunchKernelGGL(fsmn_dec_ln_kernel<11>, grid, block, 0, s, tn, wT, token_num, B, L, x, gamma, beta, out16);
   else hipLaunchKernelGGL(fsmn_dec_ln_kernel<21>, grid, block, 0, s, tn, wT, token_num, B, L, x, gamma, beta, out16);
   PF_HIP(hipGetLastError());

@@ -151,6 +151,13 @@ void launch_gemm_rc(hipStream_t s, const GemmRcArgs& a);
 // The encoder's whole feed-forward block in one launch (k_ffn.hip): x = resid + relu(A W1^T + b1) W2^T + b2;
 // n = LayerNorm(x).  d_model 512, hidden 2048; 64-row tiles, the hidden stays in LDS, W1 / W2 are streamed from their
 // fragment-ordered images (launch_ffn_retile, once per layer at load) straight into registers.
+// Rows read and written (tiles are 64 rows, Mpad = round_up(M, 64)):
+//   read     A and ctx rows [0, Mpad) (the rows behind M - 1 may hold anything finite or not: nothing of them reaches a row < M);
+//            resid rows [0, M) only; fsmn_v rows [0, M) only (the window is clamped to them and masked at the edges of each run
+//            of T rows);
+//   written  out_x, out_n16, out_n32: rows [0, M), columns [0, 512), nothing else;  with the tail out_qk (blocked, 1024 columns)
+//            and out_v (columns [0, 512) of row stride ldvo): rows [0, Mpad) — the rows behind M - 1 hold the projection of the
+//            pad rows, i.e. garbage — never a row at or beyond Mpad.
 struct FfnFusedArgs {
   const half_t* A; int lda;                      // [M,512] f16 (LayerNorm norm2 of the residual stream), rows readable up to round_up(M,64)
   const half_t* Wt;                              // ffn_fused_weight_bytes(): W1t | W2t
@@ -182,6 +189,12 @@ void launch_ffn_fused(hipStream_t s, const FfnFusedArgs& a);
 // The decoder's position-wise block  t = LN_F(relu(A W1^T + b1)) W2^T  [, n = LayerNorm(t; ln_g, ln_b)]  (k_ffn.hip, split form):
 // the same chunked kernel, the hidden range of a 64-row tile shared by 1 | 2 | 3 | 4 | 8 workgroups (ffn_dec_splits: the decoder
 // has few rows), LN_F applied afterwards from row statistics collected on the way.  D = 512, F = 2048 only.
+// Rows read and written (tiles are 64 rows, Mpad = round_up(M, 64)):
+//   read     A / ctx rows [0, Mpad) (what the rows behind M - 1 hold reaches no row < M); resid rows [0, M) only;
+//   written  out_x, t32, n32, n16: rows [0, M), columns [0, 512), nothing else;
+//            ws: share s owns the rows [s Mpad, (s + 1) Mpad) of the partial-row block [S Mpad, 512] and of the statistics block
+//            [S Mpad, 2] behind it (ffn_dec_workspace_bytes); of these the rows [0, M) of every share are written, the others
+//            are the launch's to use; nothing at or beyond ffn_dec_workspace_bytes(M, splits).
 struct FfnDecArgs {
   const half_t* A; int lda;                      // norm1(x) as f16 [M,512] (ignored when ctx != null)
   // ctx != null: the PREVIOUS layer's cross-attention out-projection in front of the block, same launch:
@@ -203,6 +216,12 @@ const float* ffn_dec_image_cd(const half_t* img);  // the (c | d) vectors of the
 
 // the middle of a decoder layer in one launch (k_decmid.hip, round 6): finishing pass of the split FFN + norm2 + FSMN memory +
 // residual + norm3 + q-projection, on the workspace a launch_ffn_dec(no_finish) left behind
+// Rows read and written (M = B L):
+//   read     ws: of every share the partial rows and statistics of the positions l < min(token_num[b], L) only (a masked
+//            position is a zero row of norm2's result, whatever the workspace holds there); x rows [0, M);
+//   written  x: the rows with l < token_num[b], in place; every other cell keeps its bits;  q16: rows [0, M), columns [0, 512) —
+//            all of them, masked positions too (norm3 and the projection run on every row) — never a column in [512, ldq) or a
+//            row at or beyond M.
 struct DecMidArgs {
   const void* ws; const half_t* img; int splits; float eps_hidden;   // as the FfnDecArgs of the split launch in front
   const float* n2_g; const float* n2_b; float eps2;                   // norm2
@@ -291,6 +310,8 @@ void launch_fsmn_dec(hipStream_t s, const float* tn, const float* w, const int32
 // LayerNorm of f16 rows -> f16 (may run in place); D % 8 == 0, D <= 2048
 void launch_layernorm_f16(hipStream_t s, const half_t* x, int64_t rows, int D, const float* gamma, const float* beta, half_t* out);
 // the same followed by LayerNorm(x) -> f16 (norm3): one launch; false = geometry not covered (D != 512 or k not 11/21)
+// read: tn rows with l < min(token_num[b], L) only (a masked row may hold anything), x rows [0, B L);  written: x rows with
+// l < token_num[b] (every other cell keeps its bits), out16 rows [0, B L) x [0, 512), all of them; nothing behind row B L - 1
 bool launch_fsmn_dec_ln(hipStream_t s, const float* tn, const float* w, const int32_t* token_num, int B, int L, int D, int k,
                         float* x, const float* gamma, const float* beta, half_t* out16);
 // streaming decoder FSMN (FunASR MultiHeadedAttentionSANMDecoder export with a cache): xc = cat(cache_in [B,D,K-1],

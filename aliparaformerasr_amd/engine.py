@@ -1272,6 +1272,47 @@ class Engine:
                                          w.shape[1], _fp(x)))
         return x
 
+    def op_fsmn_dec_ln(self, tn, taps, token_num, x, ln):
+        """The fused decoder FSMN + LayerNorm kernel alone (pf_op_fsmn_dec_ln): tn, x [B, L, 512], taps [k, 512] (k = 11 | 21),
+        ln = (gamma, beta); returns (x_out, xn16)."""
+        tn, taps, x, g, b = _f32(tn), _f32(taps), _f32(x), _f32(ln[0]), _f32(ln[1])
+        B, L, D = tn.shape
+        assert D == 512 and x.shape == tn.shape and taps.shape[1] == 512
+        t = np.ascontiguousarray(token_num, dtype=np.int32)
+        assert t.shape == (B,)
+        xo, xn = np.zeros_like(x), np.zeros_like(x)
+        N.check(self._lib.pf_op_fsmn_dec_ln(self._h, _fp(tn), _fp(taps), t.ctypes.data_as(C.POINTER(C.c_int32)), B, L, taps.shape[0],
+                                            _fp(x), _fp(g), _fp(b), _fp(xo), _fp(xn)))
+        return xo, xn
+
+    def op_dec_mid(self, a, w1, b1, ln_hidden, w2, n2, taps, token_num, x, n3, wq, bq, splits=0, form=0):
+        """The middle of a decoder layer (pf_op_dec_mid): form 0 = the split block without its finishing pass + the fused
+        middle kernel (k_decmid.hip), 1 = finishing pass with norm2 | fused FSMN + norm3 | q GEMM, 2 = the same with the FSMN
+        and the LayerNorm as two launches.  a [B L, 512], x [B, L, 512], taps [11, 512], n2 / n3 / ln_hidden = (gamma, beta).
+        Returns dict(x, q, tn, xn16, ran): tn / xn16 are None in form 0; ran False = form 0 declined (x, q are None)."""
+        x = _f32(x)
+        B, L, D = x.shape
+        arrs = dict(a=_f32(a), w1=_f32(w1), b1=_f32(b1), gamma_f=_f32(ln_hidden[0]), beta_f=_f32(ln_hidden[1]), w2=_f32(w2),
+                    n2_gamma=_f32(n2[0]), n2_beta=_f32(n2[1]), taps=_f32(taps), x=x, n3_gamma=_f32(n3[0]), n3_beta=_f32(n3[1]),
+                    wq=_f32(wq), bq=_f32(bq))
+        assert arrs["a"].shape == (B * L, 512) and arrs["taps"].shape == (11, 512) and arrs["wq"].shape == (512, 512)
+        t = np.ascontiguousarray(token_num, dtype=np.int32)
+        assert t.shape == (B,)
+        d = N.PfDecMidDesc()
+        d.struct_size, d.B, d.L, d.splits, d.form = C.sizeof(N.PfDecMidDesc), B, L, int(splits), int(form)
+        for k, v in arrs.items():
+            setattr(d, k, _fp(v))
+        d.token_num = t.ctypes.data_as(C.POINTER(C.c_int32))
+        xo, q = np.zeros((B * L, 512), np.float32), np.zeros((B * L, 512), np.float32)
+        tn = np.zeros((B * L, 512), np.float32) if form else None
+        xn = np.zeros((B * L, 512), np.float32) if form else None
+        ran = C.c_int32(0)
+        N.check(self._lib.pf_op_dec_mid(self._h, C.byref(d), _fp(xo), _fp(q), _fp(tn) if form else None, _fp(xn) if form else None,
+                                        C.byref(ran)))
+        if not ran.value:
+            return dict(x=None, q=None, tn=None, xn16=None, ran=False)
+        return dict(x=xo, q=q, tn=tn, xn16=xn, ran=True)
+
     def op_lstm(self, xg, whh, ndir, form) -> np.ndarray:
         """The heads' LSTM recurrence on gate inputs xg [B, T3, ndir * 4D], whh [ndir, 4D, D] (pf_op_lstm): form 0 = as the f16
         timestamp head chooses, 1 = per-step launches, 2 = f16 ring, 3 = pair-operand ring, 4 = fp32 per step."""

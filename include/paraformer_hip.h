@@ -834,6 +834,40 @@ typedef struct pf_dec_ffn_desc {
 } pf_dec_ffn_desc;
 /* t_out / n_out / x_out [M,512] fp32, each may be NULL (n_out needs ln_gamma / ln_beta, x_out needs ctx). */
 int pf_op_dec_ffn_fused(pf_engine* e, const pf_dec_ffn_desc* d, float* t_out, float* n_out, float* x_out);
+/* The middle of a decoder layer on caller data, in the three forms the engine can run it (d_model 512, hidden 2048, M = B L):
+     t  = LayerNorm_F(relu(a w1^T + b1); gamma_f, beta_f) w2^T          the position-wise block of pf_op_dec_ffn_fused, split form
+     tn = LayerNorm(t; n2), a zero row at the positions l >= token_num[b]
+     x += sum_j taps[j] tn[l + j - 5] + tn[l]      for l < token_num[b]   (11 taps [11][512]; a masked row of x keeps its bits)
+     xn = f16 LayerNorm(x; n3)                     on every row
+     q  = f16((xn wq^T + bq) / sqrt(128))
+   form 0: the split launch without its finishing pass + ONE launch of the fused kernel (k_decmid.hip);
+   form 1: the split launch with its finishing pass and norm2, the fused FSMN + norm3 kernel, the q GEMM;
+   form 2: the same with the FSMN kernel and the LayerNorm kernel as two launches.
+   x_out [M,512] fp32, q_out [M,512] (the stored f16 widened to fp32); tn_out (fp32) and xn16_out (f16 widened) exist in forms
+   1 and 2 only and may be NULL.  *ran = 1 when the form ran as asked, 0 when form 0 declined the geometry (nothing is returned
+   then).  In form 0 the workspace rows of the masked positions are overwritten with a large finite pattern between the two
+   launches.  q is stored with a row stride of 520 halves; the 8 columns behind it, the rows of x and q behind M - 1 and, in
+   form 0, the bits of every masked row of x are checked after the launch (PF_ERR_DEVICE names the cell). */
+typedef struct pf_dec_mid_desc {
+  int32_t struct_size;           /* sizeof(pf_dec_mid_desc) */
+  int32_t B, L, splits, form, reserved;   /* splits as pf_dec_ffn_desc; reserved = 0 */
+  const float* a;                /* [M,512] the block's normalised input */
+  const float* w1; const float* b1;            /* [2048,512], [2048] */
+  const float* gamma_f; const float* beta_f;   /* [2048] */
+  const float* w2;                             /* [512,2048] */
+  const float* n2_gamma; const float* n2_beta; /* [512] */
+  const float* taps;                           /* [11][512] */
+  const int32_t* token_num;                    /* [B], 0 <= token_num[b]; values above L count as L */
+  const float* x;                              /* [M,512] the residual stream */
+  const float* n3_gamma; const float* n3_beta; /* [512] */
+  const float* wq; const float* bq;            /* [512,512], [512] */
+} pf_dec_mid_desc;
+int pf_op_dec_mid(pf_engine* e, const pf_dec_mid_desc* d, float* x_out, float* q_out, float* tn_out, float* xn16_out, int32_t* ran);
+/* The fused decoder FSMN + LayerNorm kernel (k_norm.hip) alone: x_out = x + (sum_j taps[j] tn[l + j - (k - 1) / 2] + tn[l]) for
+   l < token_num[b] (taps [k][512], k = 11 | 21; tn, x [B L,512]), xn16_out = f16 LayerNorm(x_out; gamma, beta) of every row.  The
+   rows of tn at l >= token_num[b] are replaced by a large finite pattern on the device: they must not reach any result. */
+int pf_op_fsmn_dec_ln(pf_engine* e, const float* tn, const float* taps, const int32_t* token_num, int32_t B, int32_t L, int32_t k,
+                      const float* x, const float* gamma, const float* beta, float* x_out, float* xn16_out);
 /* The same launch with the attention out-projection in front of the block, as the pipeline runs two thirds of an encoder
    layer since round 5: x_mid = resid + ctx wo^T + bo + FSMN(v) (11 taps, utterances = runs of T rows);
    x_out = x_mid + W2 relu(W1 LayerNorm(x_mid; ln2) + b1) + b2; n16_out = f16 LayerNorm(x_out; ln_gamma, ln_beta).

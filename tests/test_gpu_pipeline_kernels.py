@@ -645,8 +645,9 @@ def test_decoder_middle_in_one_launch(monkeypatch):
     """Round 6: finishing pass of the split FFN + norm2 + FSMN memory + residual + norm3 + q-projection as ONE launch
     (k_decmid.hip, `PF_DEC_MID`) against the three launches it replaces, on the same engine inputs: ragged utterances (token_num
     below L, L not a multiple of the kernel's 32-row blocks, an utterance shorter than the FSMN half-window), log-probs equal up to
-    the f16 rounding of q (measured: bit-identical — both forms accumulate the q product over K in the same order and round at the same
-    points), token_num / L / ids identical; and against the oracle with the engine's rounding points."""
+    the f16 rounding of q (bit-identical on these inputs; not in general: tests/test_gpu_layer_conformance.py compares the two forms
+    on the kernel's own inputs and finds x identical and q within the derived bound only), token_num / L / ids identical; and against
+    the oracle with the engine's rounding points."""
     from aliparaformerasr_amd.engine import Engine
     from oracle import frontend as fe, model as om
     cfg = W.paraformer_large_config(enc_layers=2, dec_layers=3, vocab=300)
