@@ -113,6 +113,16 @@ class PfGemmDesc(C.Structure):
     ]
 
 
+class PfQgemmDesc(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32), ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32),
+        ("relu", C.c_int32), ("out_kind", C.c_int32), ("tile_rows", C.c_int32), ("want_range", C.c_int32),
+        ("scale_cols", C.c_int32), ("scale", C.c_float), ("a_scale", C.c_float), ("a_zp", C.c_int32),
+        ("w_zp", C.POINTER(C.c_int32)), ("w_scale", C.POINTER(C.c_float)),
+        ("bias", C.POINTER(C.c_float)), ("resid", C.POINTER(C.c_float)), ("add2", C.POINTER(C.c_float)),
+    ]
+
+
 class PfGemmRcDesc(C.Structure):
     _fields_ = [
         ("struct_size", C.c_int32), ("M", C.c_int32), ("K", C.c_int32), ("a_blocked", C.c_int32), ("T", C.c_int32),
@@ -266,6 +276,11 @@ SIGNATURES = {
     "pf_op_fbank_batch": (C.c_int, [_vp, _P(_f), _i64, C.c_int32, _f, C.c_int64, _i32]),
     "pf_op_qlinear": (C.c_int, [_vp, _f, _f, _f, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f, _P(C.c_uint8), _f,
                                 _P(C.c_uint8), _f, _i32]),
+    "pf_op_quantize": (C.c_int, [_vp, _f, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f, _f, _P(C.c_int8), _i32, _f]),
+    "pf_op_quantize_weight": (C.c_int, [_vp, _f, C.c_int32, C.c_int32, C.c_int32, _P(C.c_int8), _i32, _i32, _f, _i32]),
+    "pf_op_import_weight": (C.c_int, [_vp, _P(C.c_uint8), _P(C.c_uint8), _f, C.c_int32, C.c_int32, C.c_int32, _P(C.c_int8), _i32, _i32,
+                                      _f, _i32]),
+    "pf_op_qgemm_ex": (C.c_int, [_vp, _P(PfQgemmDesc), _P(C.c_uint8), _P(C.c_uint8), _f, _f, _f]),
     "pf_op_argmax": (C.c_int, [_vp, _f, C.c_int64, C.c_int32, _i64]),
     "pf_op_gemm": (C.c_int, [_vp, _f, _f, _f, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f]),
     "pf_op_gemm_ex": (C.c_int, [_vp, _P(PfGemmDesc), _f, _f, _f]),

@@ -1044,6 +1044,50 @@ int pf_op_qlinear(pf_engine* h, const float* x, const float* W, const float* bia
   return PF_OK;
   PF_CATCH
 }
+int pf_op_quantize(pf_engine* h, const float* x, int32_t rows, int32_t cols, int32_t ldx, int32_t x_is_f16, int32_t ld, const float* gamma,
+                   const float* beta, int8_t* codes_out, int32_t* rowsum_out, float* params_out) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  NEED(x); NEED(codes_out); NEED(rowsum_out); NEED(params_out);
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->op_quantize(x, rows, cols, ldx, x_is_f16, ld, gamma, beta, codes_out, rowsum_out, params_out);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_op_quantize_weight(pf_engine* h, const float* W, int32_t N, int32_t K, int32_t ld, int8_t* w_out, int32_t* colsum_out, int32_t* wzp_out,
+                          float* wscale_out, int32_t* dz_out) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  NEED(W); NEED(w_out); NEED(colsum_out); NEED(wzp_out); NEED(wscale_out); NEED(dz_out);
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->op_weight(W, nullptr, nullptr, nullptr, N, K, ld, w_out, colsum_out, wzp_out, wscale_out, dz_out);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_op_import_weight(pf_engine* h, const uint8_t* Q, const uint8_t* zp, const float* scale, int32_t N, int32_t K, int32_t ld, int8_t* w_out,
+                        int32_t* colsum_out, int32_t* wzp_out, float* wscale_out, int32_t* dz_out) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  NEED(Q); NEED(zp); NEED(scale); NEED(w_out); NEED(colsum_out); NEED(wzp_out); NEED(wscale_out); NEED(dz_out);
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->op_weight(nullptr, Q, zp, scale, N, K, ld, w_out, colsum_out, wzp_out, wscale_out, dz_out);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_op_qgemm_ex(pf_engine* h, const pf_qgemm_desc* d, const uint8_t* a_codes, const uint8_t* w_codes, float* y32, float* y16, float* range_out) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  NEED(d); NEED(a_codes); NEED(w_codes);
+  PF_CHECK(d->struct_size == (int32_t)sizeof(pf_qgemm_desc), PF_ERR_INVALID_ARG, "pf_qgemm_desc.struct_size mismatch");
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->op_qgemm_ex(*d, a_codes, w_codes, y32, y16, range_out);
+  return PF_OK;
+  PF_CATCH
+}
 int pf_op_gemm_ex(pf_engine* h, const pf_gemm_desc* d, const float* A, const float* W, float* C) {
   PF_TRY
   std::shared_ptr<Engine> eh_ = E(h);

@@ -268,6 +268,13 @@ class Engine {
   // activations [M, K], {a_scale, a_zp}, the uint8 weights [N, K] and their per-channel scale / zero point
   void op_qlinear(const float* x, const float* W, const float* bias, int M, int N, int K, int relu, int x_is_f16, float* y,
                   uint8_t* xq_out, float* aparams_out, uint8_t* wq_out, float* wscale_out, int32_t* wzp_out);
+  // the parts of the int8 path one at a time, each on a hostile host that enforces kernels.h's contracts (engine_int8.cpp)
+  void op_quantize(const float* x, int rows, int cols, int ldx, int x_is_f16, int ld, const float* gamma, const float* beta,
+                   int8_t* codes_out, int32_t* rowsum_out, float* params_out);
+  // Q == null: quantize_weight_kernel on W; else import_weight_kernel on the stored bytes
+  void op_weight(const float* W, const uint8_t* Q, const uint8_t* zp, const float* scale, int N, int K, int ld, int8_t* w_out,
+                 int32_t* colsum_out, int32_t* wzp_out, float* wscale_out, int32_t* dz_out);
+  void op_qgemm_ex(const pf_qgemm_desc& d, const uint8_t* a_codes, const uint8_t* w_codes, float* y32, float* y16, float* range_out);
   void op_dec_ffn_fused(const pf_dec_ffn_desc& ds, float* t_out, float* n_out, float* x_out);
   void op_dec_mid(const pf_dec_mid_desc& ds, float* x_out, float* q_out, float* tn_out, float* xn16_out, int32_t* ran);
   void op_fsmn_dec_ln(const float* tn, const float* taps, const int32_t* token_num, int B, int L, int k, const float* x, const float* gamma,

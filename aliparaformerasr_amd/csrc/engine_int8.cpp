@@ -11,8 +11,10 @@
 // Weights: a container converted from an int8 export carries the stored bytes (`<linear>.weight_q` u8, `.weight_zp` u8,
 // `.weight_scale` f32, aliparaformerasr_amd/convert.py) and those are what is multiplied; a container with fp32 tensors
 // only (the synthetic models) is quantised at first use on the device with quantize_dynamic's per-channel algorithm.
+#include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <string>
 
 #include "engine.h"
 
@@ -492,6 +494,314 @@ void Engine::op_qlinear(const float* x, const float* W, const float* bias, int M
       for (int k = 0; k < K; ++k) wq_out[(size_t)n * K + k] = (uint8_t)((int)wq[(size_t)n * Kp + k] + 128);
   if (wzp_out)
     for (int n = 0; n < N; ++n) wzp_out[n] = zp[(size_t)n] + 128;
+}
+
+// ---- hostile hosts of the int8 path (as engine_ops.cpp's for the f16 kernels): whatever kernels.h only calls readable holds a
+// pattern that shows in the result when it is used — large finite floats in pad rows, pad columns and behind a tensor, NaN
+// behind the float vectors, large magnitudes behind the integer vectors, the codes +127 / -128 in the operand pad rows — and
+// every output sits in a sentinel-filled buffer: a result cell must come back written, every other cell with its sentinel.
+// A byte has no value a code cannot take, so the byte outputs run twice, on two sentinels: an unwritten cell holds both.
+namespace {
+constexpr uint32_t kSent32 = 0x7FC5A5A5u;                     // a NaN payload as a float; as an int32 no row / column sum or dz word
+constexpr uint16_t kSent16 = 0x7E5Au;
+constexpr uint8_t kSent8[2] = {0x5A, 0xA5};
+constexpr int kTail = 136;                                    // hostile cells behind a vector (more than one wave tile of columns)
+
+inline float hostile32(size_t i) { return std::ldexp(1.0f + (float)((i * 37u) & 0x3FFu) / 1024.0f, 100) * ((i & 1u) ? -1.0f : 1.0f); }
+inline half_t hostile16(size_t i) {                           // +-32768 .. +-65504
+  const uint16_t bits = (uint16_t)(0x7800u | (uint16_t)((i * 37u) & 0x3FFu) | (uint16_t)((i & 1u) << 15));
+  half_t h;
+  std::memcpy(&h, &bits, 2);
+  return h;
+}
+inline int32_t hostile_i32(size_t i) { return ((i & 1u) ? -1 : 1) * ((1 << 30) + (int32_t)((i * 37u) & 0xFFFFu)); }
+inline float quiet_nan() { return std::nanf(""); }
+
+template <class U>
+void upload(hipStream_t s, void* dev, const std::vector<U>& h) {
+  PF_HIP(hipMemcpyAsync(dev, h.data(), h.size() * sizeof(U), hipMemcpyHostToDevice, s));
+  PF_HIP(hipStreamSynchronize(s));
+}
+// A [rows, ld] buffer that held `before` at the launch, downloaded into `after`: outside [0, guard) x [0, N) every cell keeps its
+// bits; inside [0, M) x [0, N) (must_write) no cell holds the sentinel any more.  Vectors: ld = 1, N = 1.
+template <class U>
+void check_region(hipStream_t s, const std::string& what, const void* dev, const std::vector<U>& before, std::vector<U>& after, U sentinel,
+                  int64_t rows, int64_t ld, int64_t M, int64_t N, int64_t guard, bool must_write) {
+  after.resize(before.size());
+  PF_HIP(hipMemcpyAsync(after.data(), dev, after.size() * sizeof(U), hipMemcpyDeviceToHost, s));
+  PF_HIP(hipStreamSynchronize(s));
+  for (int64_t m = 0; m < rows; ++m)
+    for (int64_t n = 0; n < ld; ++n) {
+      const size_t i = (size_t)(m * ld + n);
+      const char* why = nullptr;
+      if (m < M && n < N) { if (must_write && after[i] == sentinel) why = "was not written"; }
+      else if ((n >= N || m >= guard) && after[i] != before[i]) why = n >= N ? "was written: a column the contract (kernels.h) calls never written"
+                                                                            : "was written: a row the contract (kernels.h) calls never written";
+      if (why)
+        throw Error(PF_ERR_DEVICE, what + " (" + std::to_string(M) + " x " + std::to_string(N) + ", ld " + std::to_string(ld) + "): cell (" +
+                                       std::to_string(m) + ", " + std::to_string(n) + ") " + why);
+    }
+}
+// the two runs of a byte output: a cell of [0, M) x [0, N) that holds its sentinel after both was written by neither
+void check_bytes_written(const std::string& what, const std::vector<uint8_t>& a0, const std::vector<uint8_t>& a1, int64_t ld, int64_t M, int64_t N) {
+  for (int64_t m = 0; m < M; ++m)
+    for (int64_t n = 0; n < N; ++n) {
+      const size_t i = (size_t)(m * ld + n);
+      if (a0[i] == kSent8[0] && a1[i] == kSent8[1])
+        throw Error(PF_ERR_DEVICE, what + ": cell (" + std::to_string(m) + ", " + std::to_string(n) + ") was not written");
+      if (a0[i] != a1[i]) throw Error(PF_ERR_DEVICE, what + ": cell (" + std::to_string(m) + ", " + std::to_string(n) + ") differs between two runs");
+    }
+}
+}  // namespace
+
+void Engine::op_quantize(const float* x, int rows, int cols, int ldx, int x_is_f16, int ld, const float* gamma, const float* beta,
+                         int8_t* codes_out, int32_t* rowsum_out, float* params_out) {
+  PF_HIP(hipSetDevice(device_));
+  const bool ln = gamma || beta;
+  PF_CHECK(x && codes_out && rowsum_out && params_out && rows > 0 && cols > 0 && cols % 4 == 0 && ldx % 4 == 0 && ldx >= cols && ld % 4 == 0 && ld >= cols,
+           PF_ERR_INVALID_ARG, "op_quantize: cols, ldx and ld must be multiples of 4, ldx and ld at least cols");
+  PF_CHECK(!ln || (gamma && beta && !x_is_f16 && ldx == cols), PF_ERR_INVALID_ARG, "op_quantize: LayerNorm rows are dense fp32 and need gamma and beta");
+  const int64_t xr = rows + 8, orows = rows + 8;               // hostile rows behind x, guard rows behind the outputs
+  const size_t esz = x_is_f16 ? 2 : 4, part_words = quant_scratch_bytes() / 4;
+  size_t off = 0;
+  const Carve carve{off, kAlignQ};
+  const size_t ox = carve((size_t)xr * ldx * esz), og = carve((size_t)(cols + kTail) * 4), ob = carve((size_t)(cols + kTail) * 4);
+  const size_t oo = carve((size_t)orows * ld), ors = carve((size_t)orows * 4), opar = carve(64), opart = carve((part_words + 64) * 4);
+  ensure(ws_tmp_, off);
+  char* base = (char*)ws_tmp_.p;
+  // x: the tensor inside [rows, cols], the large finite pattern in the pad columns and in the rows behind it
+  if (x_is_f16) {
+    std::vector<half_t> h((size_t)xr * ldx);
+    for (int64_t r = 0; r < xr; ++r)
+      for (int c = 0; c < ldx; ++c) h[(size_t)r * ldx + c] = r < rows && c < cols ? (half_t)x[(size_t)r * cols + c] : hostile16((size_t)r * 131 + c);
+    upload(stream_, base + ox, h);
+  } else {
+    std::vector<float> h((size_t)xr * ldx);
+    for (int64_t r = 0; r < xr; ++r)
+      for (int c = 0; c < ldx; ++c) h[(size_t)r * ldx + c] = r < rows && c < cols ? x[(size_t)r * cols + c] : hostile32((size_t)r * 131 + c);
+    upload(stream_, base + ox, h);
+  }
+  if (ln) {
+    std::vector<float> g((size_t)cols + kTail, quiet_nan()), b((size_t)cols + kTail, quiet_nan());
+    std::copy(gamma, gamma + cols, g.begin());
+    std::copy(beta, beta + cols, b.begin());
+    upload(stream_, base + og, g);
+    upload(stream_, base + ob, b);
+  }
+  const std::vector<uint32_t> rs0((size_t)orows, kSent32), par0(16, kSent32), part0(part_words + 64, kSent32);
+  std::vector<uint32_t> rs1, par1, part1;
+  std::vector<uint8_t> out1[2];
+  for (int run = 0; run < 2; ++run) {
+    const std::vector<uint8_t> out0((size_t)orows * ld, kSent8[run]);
+    upload(stream_, base + oo, out0);
+    upload(stream_, base + ors, rs0);
+    upload(stream_, base + opar, par0);
+    upload(stream_, base + opart, part0);
+    float* part = (float*)(base + opart);
+    if (ln) {
+      launch_ln_minmax(stream_, (const float*)(base + ox), rows, cols, (const float*)(base + og), (const float*)(base + ob), part);
+      launch_ln_quantize(stream_, (const float*)(base + ox), rows, cols, (const float*)(base + og), (const float*)(base + ob), (int8_t*)(base + oo), ld,
+                         (int32_t*)(base + ors), (float*)(base + opar), part);
+    } else {
+      const float* x32 = x_is_f16 ? nullptr : (const float*)(base + ox);
+      const half_t* x16 = x_is_f16 ? (const half_t*)(base + ox) : nullptr;
+      launch_minmax(stream_, x32, x16, rows, cols, ldx, part);
+      launch_quantize(stream_, x32, x16, rows, cols, ldx, (int8_t*)(base + oo), ld, (int32_t*)(base + ors), (float*)(base + opar), part);
+    }
+    check_region<uint8_t>(stream_, "op_quantize: the codes", base + oo, out0, out1[run], kSent8[run], orows, ld, rows, ld, rows, false);
+    check_region<uint32_t>(stream_, "op_quantize: rowsum", base + ors, rs0, rs1, kSent32, orows, 1, rows, 1, rows, true);
+    check_region<uint32_t>(stream_, "op_quantize: params", base + opar, par0, par1, kSent32, 16, 1, 2, 1, 2, true);
+    check_region<uint32_t>(stream_, "op_quantize: the {min, max} pairs", base + opart, part0, part1, kSent32, (int64_t)part_words + 64, 1,
+                           (int64_t)part_words, 1, (int64_t)part_words, true);
+  }
+  check_bytes_written("op_quantize: the codes", out1[0], out1[1], ld, rows, ld);
+  std::memcpy(codes_out, out1[1].data(), (size_t)rows * ld);
+  std::memcpy(rowsum_out, rs1.data(), (size_t)rows * 4);
+  std::memcpy(params_out, par1.data(), 8);
+}
+
+void Engine::op_weight(const float* W, const uint8_t* Q, const uint8_t* zp, const float* scale, int N, int K, int ld, int8_t* w_out,
+                       int32_t* colsum_out, int32_t* wzp_out, float* wscale_out, int32_t* dz_out) {
+  PF_HIP(hipSetDevice(device_));
+  PF_CHECK((W || (Q && zp && scale)) && w_out && colsum_out && wzp_out && wscale_out && dz_out && N > 0 && K > 0 && ld >= K, PF_ERR_INVALID_ARG,
+           "op_quantize_weight / op_import_weight: bad arguments (ld >= K)");
+  const char* op = Q ? "op_import_weight" : "op_quantize_weight";
+  const int64_t wr = N + 4, orows = N + 4, vn = N + kTail;
+  size_t off = 0;
+  const Carve carve{off, kAlignQ};
+  const size_t oW = carve((size_t)wr * K * 4), oQ = carve((size_t)wr * K), ozq = carve((size_t)vn), osq = carve((size_t)vn * 4);
+  const size_t oo = carve((size_t)orows * ld), ocs = carve((size_t)vn * 4), ozp = carve((size_t)vn * 4), ows = carve((size_t)vn * 4), odz = carve((size_t)vn * 4);
+  ensure(ws_tmp_, off);
+  char* base = (char*)ws_tmp_.p;
+  if (Q) {                                                     // the rows and vector cells behind N: the largest bytes, NaN scales
+    std::vector<uint8_t> q((size_t)wr * K, 255), z((size_t)vn, 255);
+    std::vector<float> sc((size_t)vn, quiet_nan());
+    std::copy(Q, Q + (size_t)N * K, q.begin());
+    std::copy(zp, zp + N, z.begin());
+    std::copy(scale, scale + N, sc.begin());
+    upload(stream_, base + oQ, q);
+    upload(stream_, base + ozq, z);
+    upload(stream_, base + osq, sc);
+  } else {
+    std::vector<float> w((size_t)wr * K);
+    for (size_t i = 0; i < w.size(); ++i) w[i] = i < (size_t)N * K ? W[i] : hostile32(i);
+    upload(stream_, base + oW, w);
+  }
+  const std::vector<uint32_t> v0((size_t)vn, kSent32);
+  std::vector<uint32_t> cs1, zp1, ws1, dz1;
+  std::vector<uint8_t> out1[2];
+  for (int run = 0; run < 2; ++run) {
+    const std::vector<uint8_t> out0((size_t)orows * ld, kSent8[run]);
+    upload(stream_, base + oo, out0);
+    for (size_t o : {ocs, ozp, ows, odz}) upload(stream_, base + o, v0);
+    if (Q)
+      launch_import_weight(stream_, (const uint8_t*)(base + oQ), (const uint8_t*)(base + ozq), (const float*)(base + osq), N, K, (int8_t*)(base + oo), ld,
+                           (int32_t*)(base + ocs), (int32_t*)(base + ozp), (float*)(base + ows));
+    else
+      launch_quantize_weight(stream_, (const float*)(base + oW), N, K, (int8_t*)(base + oo), ld, (int32_t*)(base + ocs), (int32_t*)(base + ozp),
+                             (float*)(base + ows));
+    launch_pack_dz(stream_, (const int32_t*)(base + ocs), (const int32_t*)(base + ozp), N, K, (int32_t*)(base + odz));
+    check_region<uint8_t>(stream_, std::string(op) + ": w'", base + oo, out0, out1[run], kSent8[run], orows, ld, N, ld, N, false);
+    check_region<uint32_t>(stream_, std::string(op) + ": colsum", base + ocs, v0, cs1, kSent32, vn, 1, N, 1, N, true);
+    check_region<uint32_t>(stream_, std::string(op) + ": wzp", base + ozp, v0, zp1, kSent32, vn, 1, N, 1, N, true);
+    check_region<uint32_t>(stream_, std::string(op) + ": wscale", base + ows, v0, ws1, kSent32, vn, 1, N, 1, N, true);
+    check_region<uint32_t>(stream_, std::string(op) + ": dz", base + odz, v0, dz1, kSent32, vn, 1, N, 1, N, true);
+  }
+  check_bytes_written(std::string(op) + ": w'", out1[0], out1[1], ld, N, ld);
+  std::memcpy(w_out, out1[1].data(), (size_t)N * ld);
+  std::memcpy(colsum_out, cs1.data(), (size_t)N * 4);
+  std::memcpy(wzp_out, zp1.data(), (size_t)N * 4);
+  std::memcpy(wscale_out, ws1.data(), (size_t)N * 4);
+  std::memcpy(dz_out, dz1.data(), (size_t)N * 4);
+}
+
+void Engine::op_qgemm_ex(const pf_qgemm_desc& ds, const uint8_t* a_codes, const uint8_t* w_codes, float* y32, float* y16, float* range_out) {
+  PF_HIP(hipSetDevice(device_));
+  const int M = ds.M, N = ds.N, K = ds.K, kind = ds.out_kind;
+  PF_CHECK(M > 0 && N > 0 && K > 0 && a_codes && w_codes && ds.w_zp && ds.w_scale, PF_ERR_INVALID_ARG, "qgemm_ex: empty problem");
+  PF_CHECK(kind >= 0 && kind <= 3, PF_ERR_INVALID_ARG, "qgemm_ex: out_kind must be 0 .. 3");
+  PF_CHECK(ds.tile_rows == 0 || ds.tile_rows == 128 || ds.tile_rows == 256, PF_ERR_INVALID_ARG, "qgemm_ex: tile_rows must be 0, 128 or 256");
+  PF_CHECK(kind != 1 || (!ds.resid && !ds.add2), PF_ERR_INVALID_ARG, "qgemm_ex: the f16-result kernel takes no residual / addend");
+  PF_CHECK(ds.a_zp >= 0 && ds.a_zp <= 255, PF_ERR_INVALID_ARG, "qgemm_ex: a_zp must be in 0 .. 255");
+  const bool has32 = kind == 0 || kind == 3, has16 = kind != 0;
+  PF_CHECK((!has32 || y32) && (!has16 || y16) && (!ds.want_range || range_out), PF_ERR_INVALID_ARG, "qgemm_ex: missing output");
+  const int Kp = (int)round_up(K, 128);
+  const int64_t Mp = round_up(M, 256), Np = round_up(N, 128), Mo = Mp + 128, vn = N + kTail;
+  const int ld32 = (int)round_up(N, 4) + 4, ld16 = kind == 1 ? (int)round_up(N, 8) + 8 : (int)round_up(N, 4) + 4;
+  const size_t part_words = quant_scratch_bytes() / 4;
+  size_t off = 0;
+  const Carve carve{off, kAlignQ};
+  const size_t oa = carve((size_t)Mp * Kp), ow = carve((size_t)Np * Kp), ors = carve((size_t)Mp * 4), opar = carve(64);
+  const size_t ocs = carve((size_t)vn * 4), ozp = carve((size_t)vn * 4), odz = carve((size_t)vn * 4), ows = carve((size_t)vn * 4), ob = carve((size_t)vn * 4);
+  const size_t o32 = carve((size_t)Mo * ld32 * 4), o16 = carve((size_t)Mo * ld16 * 2), oR = carve((size_t)Mo * ld32 * 4), oD = carve((size_t)Mo * ld32 * 4);
+  const size_t opart = carve((part_words + 64) * 4);
+  ensure(ws_tmp_, off);
+  char* base = (char*)ws_tmp_.p;
+  // a', w' with their sums and dz, on the host; pad columns 0 (the contract), pad rows the largest codes of both signs
+  std::vector<int8_t> a((size_t)Mp * Kp, 0), w((size_t)Np * Kp, 0);
+  std::vector<int32_t> rs((size_t)Mp), cs((size_t)vn), wz((size_t)vn), dz((size_t)vn);
+  std::vector<float> wsc((size_t)vn, quiet_nan()), bias((size_t)vn, quiet_nan());
+  for (int64_t m = 0; m < Mp; ++m) {
+    int sum = 0;
+    for (int k = 0; k < K; ++k) {
+      const int v = m < M ? (int)a_codes[(size_t)m * K + k] - 128 : (((m + k) & 1) ? 127 : -128);
+      a[(size_t)m * Kp + k] = (int8_t)v;
+      sum += v;
+    }
+    rs[(size_t)m] = m < M ? sum : hostile_i32((size_t)m);
+  }
+  for (int64_t n = 0; n < Np; ++n)
+    for (int k = 0; k < K; ++k)
+      w[(size_t)n * Kp + k] = (int8_t)(n < N ? (int)w_codes[(size_t)n * K + k] - 128 : (((n + k) & 1) ? -128 : 127));
+  for (int64_t n = 0; n < vn; ++n) {
+    if (n >= N) { cs[(size_t)n] = hostile_i32((size_t)n); wz[(size_t)n] = hostile_i32((size_t)n + 1); dz[(size_t)n] = hostile_i32((size_t)n + 2); continue; }
+    PF_CHECK(ds.w_zp[n] >= 0 && ds.w_zp[n] <= 255, PF_ERR_INVALID_ARG, "qgemm_ex: w_zp must be in 0 .. 255");
+    int sum = 0;
+    for (int k = 0; k < K; ++k) sum += w[(size_t)n * Kp + k];
+    cs[(size_t)n] = sum;
+    wz[(size_t)n] = ds.w_zp[n] - 128;
+    dz[(size_t)n] = (int32_t)((uint32_t)(sum - K * wz[(size_t)n]) * 256u + (uint32_t)(wz[(size_t)n] & 255));
+    wsc[(size_t)n] = ds.w_scale[n];
+    if (ds.bias) bias[(size_t)n] = ds.bias[n];
+  }
+  PF_CHECK(kind != 1 || K <= 16384, PF_ERR_UNSUPPORTED, "qgemm_ex: K too large for the packed column word");
+  const float par[16] = {ds.a_scale, (float)ds.a_zp, quiet_nan(), quiet_nan()};
+  upload(stream_, base + oa, a);
+  upload(stream_, base + ow, w);
+  upload(stream_, base + ors, rs);
+  upload(stream_, base + ocs, cs);
+  upload(stream_, base + ozp, wz);
+  upload(stream_, base + odz, dz);
+  upload(stream_, base + ows, wsc);
+  upload(stream_, base + ob, bias);
+  PF_HIP(hipMemcpyAsync(base + opar, par, sizeof(par), hipMemcpyHostToDevice, stream_));
+  // results: sentinels; a residual aliases the fp32 result where there is one (its cells of [M, N] hold the residual)
+  std::vector<uint32_t> c32((size_t)Mo * ld32, kSent32), after32;
+  std::vector<uint16_t> c16((size_t)Mo * ld16, kSent16), after16;
+  const std::vector<uint32_t> part0(part_words + 64, kSent32);
+  std::vector<uint32_t> part1;
+  auto pad32 = [&](const float* src, size_t dst_off, bool hostile) {       // [M, N] into [Mo, ld32]
+    std::vector<float> h((size_t)Mo * ld32);
+    for (int64_t m = 0; m < Mo; ++m)
+      for (int n = 0; n < ld32; ++n) h[(size_t)m * ld32 + n] = m < M && n < N ? src[(size_t)m * N + n] : (hostile ? hostile32((size_t)m * 131 + n) : 0.f);
+    upload(stream_, base + dst_off, h);
+  };
+  const bool alias = has32 && ds.resid;
+  if (alias)
+    for (int m = 0; m < M; ++m) std::memcpy(&c32[(size_t)m * ld32], ds.resid + (size_t)m * N, (size_t)N * 4);
+  else if (ds.resid) pad32(ds.resid, oR, true);
+  if (ds.add2) pad32(ds.add2, oD, true);
+  if (has32) upload(stream_, base + o32, c32);
+  if (has16) upload(stream_, base + o16, c16);
+  upload(stream_, base + opart, part0);
+  GemmI8Args g{};
+  g.A = (int8_t*)(base + oa); g.lda = Kp; g.W = (int8_t*)(base + ow); g.ldw = Kp;
+  g.rowsum = (int32_t*)(base + ors); g.colsum = (int32_t*)(base + ocs); g.wzp = (int32_t*)(base + ozp); g.wscale = (float*)(base + ows);
+  g.aparams = (float*)(base + opar); g.bias = ds.bias ? (const float*)(base + ob) : nullptr;
+  g.M = M; g.N = N; g.K = K; g.Kpad = Kp;
+  g.relu = ds.relu ? 1 : 0; g.scale_cols = ds.scale_cols; g.scale = ds.scale;
+  if (has32) { g.out_f32 = (float*)(base + o32); g.ldc32 = ld32; }
+  if (has16) { g.out_f16 = (half_t*)(base + o16); g.ldc16 = ld16; }
+  if (ds.resid) { g.resid = alias ? (const float*)(base + o32) : (const float*)(base + oR); g.ldr = ld32; }
+  if (ds.add2) { g.add2 = (const float*)(base + oD); g.ld2 = ld32; }
+  if (kind == 1) { g.dz = (int32_t*)(base + odz); g.out_padded = 1; }
+  if (ds.want_range) g.range_out = (float*)(base + opart);
+  g.force_mi = ds.tile_rows == 128 ? 1 : (ds.tile_rows == 256 ? 2 : 0);
+  prof_begin("gemm_op", 2.0 * M * (double)N * K);
+  try {
+    launch_gemm_i8(stream_, g);
+  } catch (...) {                                              // a refusal of the launcher: close the profile's event pair
+    prof_end("gemm_op");
+    throw;
+  }
+  prof_end("gemm_op");
+  PF_CHECK(std::strncmp(last_gemm_kernel(), kind == 1 ? "gemm_i8f_pp3" : "gemm_i8_pp3", kind == 1 ? 12 : 11) == 0, PF_ERR_DEVICE,
+           "qgemm_ex: the result kind ran on another kernel than kernels.h names for it");
+  const std::string tag = std::string("qgemm_ex [") + last_gemm_kernel() + "]: ";
+  if (has32) check_region<uint32_t>(stream_, tag + "the fp32 result", base + o32, c32, after32, kSent32, Mo, ld32, M, N, M, !alias);
+  if (has16) check_region<uint16_t>(stream_, tag + "the f16 result", base + o16, c16, after16, kSent16, Mo, ld16, M, N, kind == 1 ? Mp : M, true);
+  check_region<uint32_t>(stream_, tag + "the {min, max} pairs", base + opart, part0, part1, kSent32, (int64_t)part_words + 64, 1,
+                         ds.want_range ? (int64_t)part_words : 0, 1, ds.want_range ? (int64_t)part_words : 0, true);
+  if (has32)
+    for (int m = 0; m < M; ++m) std::memcpy(y32 + (size_t)m * N, &after32[(size_t)m * ld32], (size_t)N * 4);
+  if (has16)
+    for (int m = 0; m < M; ++m)
+      for (int n = 0; n < N; ++n) {
+        half_t h;
+        std::memcpy(&h, &after16[(size_t)m * ld16 + n], 2);
+        y16[(size_t)m * N + n] = (float)h;
+      }
+  if (ds.want_range) {                                         // the consumer's fold of the 256 pairs (k_quant.hip fold_minmax)
+    float lo = 0.f, hi = 0.f;
+    for (size_t i = 0; i < part_words / 2; ++i) {
+      float l, h;
+      std::memcpy(&l, &part1[2 * i], 4);
+      std::memcpy(&h, &part1[2 * i + 1], 4);
+      lo = std::fmin(lo, l);
+      hi = std::fmax(hi, h);
+    }
+    range_out[0] = lo; range_out[1] = hi;
+  }
 }
 
 }  // namespace pf

@@ -908,13 +908,17 @@ void launch_gemm_i8(hipStream_t s, const GemmI8Args& a) {
   const int t2 = cdiv(d.M, 256) * cdiv(d.N, GEMM_BN), t1 = cdiv(d.M, 128) * cdiv(d.N, GEMM_BN);
   const bool few = (float)t2 < 0.9f * cus;       // (int8: 0.9 measured better than the f16 kernels' 0.6 — SenseVoice 16.9 vs 17.5 ms)
   const bool rounds1 = 0.58 * cdiv(t1, cus) < (double)cdiv(t2, cus);
-  const int mi = (few || rounds1) ? 1 : 2;
+  PF_CHECK(a.force_mi == 0 || a.force_mi == 1 || a.force_mi == 2, PF_ERR_INVALID_ARG, "gemm_i8: force_mi must be 0, 1 or 2");
+  const int mi = a.force_mi ? a.force_mi : ((few || rounds1) ? 1 : 2);
   d.tiles_m = cdiv(d.M, 128 * mi);
   d.tiles_n = cdiv(d.N, GEMM_BN);
   const int total = d.tiles_m * d.tiles_n;
   if (total == 0) return;
   const int grid = std::min(cus, total);
   PF_CHECK(!a.range_out || grid <= 256, PF_ERR_UNSUPPORTED, "gemm_i8: range output needs a grid of at most 256 workgroups");
+  // the pair is rounded to f16, "as the consumer will read it": with an fp32 result the consumer reads other values, and no
+  // caller asks for both (kRangeOut is set on the encoder's FFN-up alone, an f16 result)
+  PF_CHECK(!a.range_out || !a.out_f32, PF_ERR_UNSUPPORTED, "gemm_i8: range output is the range of an f16 result (no out_f32 beside it)");
   d.q_dz = a.dz; d.q_part = a.range_out;
   // f16-only results into a padded buffer: the deferred packed epilogue (gemm_i8f_pp3), as the f16 path's KIND 1
   const bool f16_only = a.out_f16 && !a.out_f32 && !a.resid && !a.add2 && a.out_padded && (a.ldc16 & 7) == 0 && a.dz;

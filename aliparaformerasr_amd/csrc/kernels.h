@@ -72,6 +72,20 @@ void launch_gemm_bigp(hipStream_t s, const GemmArgs& a, int cus);
 //   y[m,n] = float( sum_k (a_q[m,k] - a_zp)(w_q[n,k] - w_zp[n]) ) * (a_scale * w_scale[n]) + bias[n]  [+ add2 + resid] [ReLU]
 // The device keeps SIGNED bytes a' = a_q - 128, w' = w_q - 128 (the matrix cores multiply signed int8) plus the row /
 // column sums that turn sum a' w' back into the exact integer above.
+// Epilogue order: dequantise, + bias, x scale (columns n < scale_cols), + add2, + resid, ReLU, f16 round-to-nearest-even.
+// Rows and columns read and written (tiles are 128 or 256 rows by 128 columns, Mpad = round_up(M, 256), Npad = round_up(N, 128)):
+//   read     A rows [0, Mpad) and W rows [0, Npad), columns [0, Kpad) of both: the rows behind M - 1 / N - 1 may hold any bytes
+//            (their products reach no cell of [M, N] and not the range); the columns [K, Kpad) of both hold 0;
+//            aparams [0, 2); wscale, bias, colsum, wzp, dz: elements [0, N) only; resid, add2: rows [0, M), columns [0, N) only;
+//            rowsum: rows [0, M) only — except the f16-result kernel (below), which reads rows [0, Mpad): what the rows behind
+//            M - 1 hold reaches no cell of [M, N] and not the range;
+//   written  fp32 result (out_f32, with or without out_f16 beside it) and an f16 result without dz or with out_padded = 0
+//            (gemm_i8_pp3): rows [0, M), columns [0, N) of each result, nothing else;
+//            f16-only result with dz and out_padded = 1 (gemm_i8f_pp3, needs ldc16 % 8 == 0, no resid / add2): rows [0, Mpad),
+//            columns [0, N) — the rows behind M - 1 hold the products of the pad rows, i.e. garbage — never a column in
+//            [N, ldc16) or a row at or beyond Mpad;
+//            range_out (f16 results only; refused together with out_f32): all 256 {min, max} pairs, each including 0, over the
+//            f16 values of rows [0, M), columns [0, N); nothing behind quant_scratch_bytes().
 struct GemmI8Args {
   const int8_t* A; int lda;            // [M, Kpad] a', rows readable up to round_up(M, 256); lda (bytes) % 16 == 0
   const int8_t* W; int ldw;            // [round_up(N,128), Kpad] w', K-contiguous; pad columns of A and W hold 0
@@ -89,13 +103,14 @@ struct GemmI8Args {
   // packed epilogue when dz is given: dz[n] = (colsum[n] - K wzp[n]) * 256 + (wzp[n] & 255)  (launch_pack_dz)
   const int32_t* dz; int out_padded;
   float* range_out;                    // null, or quant_scratch_bytes(): {min, max} of the results per workgroup (pass 1 of the consumer's quantiser)
+  int force_mi;                        // 0 = choose the tile height by shape; 1 / 2 = 128- / 256-row tiles (stand-alone op tests)
 };
 void launch_pack_dz(hipStream_t s, const int32_t* colsum, const int32_t* wzp, int N, int K, int32_t* dz);
 void launch_gemm_i8(hipStream_t s, const GemmI8Args& a);
 // DynamicQuantizeLinear over the WHOLE tensor x [rows, cols] (fp32, or f16 when x16 is given): min / max (including 0)
 // -> a_scale = (max - min) / 255, a_zp = rne(clamp(-min / a_scale, 0, 255)); q = clamp(rne(x / a_scale) + a_zp, 0, 255);
 // writes a' = q - 128 into out [rows, ld] (pad columns 0), the row sums of a', and {a_scale, a_zp} into params[2].
-// scratch: >= 16 bytes of device memory (min / max accumulators).
+// scratch: quant_scratch_bytes() of device memory (one {min, max} pair per workgroup of the min / max pass).
 void launch_quantize_rows(hipStream_t s, const float* x32, const half_t* x16, int64_t rows, int cols, int ldx, int8_t* out, int ld,
                           int32_t* rowsum, float* params, unsigned* scratch);
 // the two passes as separate launches; part: quant_scratch_bytes() of scratch ({min, max} per workgroup of pass 1)

@@ -1073,6 +1073,71 @@ class Engine:
                                         wq.ctypes.data_as(u8), _fp(ws), wz.ctypes.data_as(C.POINTER(C.c_int32))))
         return (y, xq, (float(ap[0]), int(ap[1])), wq, ws, wz) if details else y
 
+    def op_quantize(self, x, x_is_f16=False, ldx=None, ld=None, ln=None):
+        """DynamicQuantizeLinear of x [rows, cols] (pf_op_quantize: the min / max pass and the quantise pass; ln = (gamma,
+        beta): of LayerNorm(x), never stored) on a hostile host.  ldx: row stride of x on the device, ld: of the result.
+        Returns (a' int8 [rows, ld] = code - 128 with the pad columns, which must be 0; rowsum int32 [rows]; (scale, zp))."""
+        x = _f32(x)
+        rows, cols = x.shape
+        ldx, ld = ldx or cols, ld or cols
+        g, b = (_f32(ln[0]), _f32(ln[1])) if ln is not None else (None, None)
+        aq = np.zeros((rows, ld), np.int8)
+        rs = np.zeros(rows, np.int32)
+        par = np.zeros(2, np.float32)
+        N.check(self._lib.pf_op_quantize(self._h, _fp(x), rows, cols, ldx, int(x_is_f16), ld, _fp(g) if g is not None else None,
+                                         _fp(b) if b is not None else None, aq.ctypes.data_as(C.POINTER(C.c_int8)), _i32p(rs), _fp(par)))
+        return aq, rs, (par[0], par[1])
+
+    def _op_weight_out(self, rows, ld):
+        return np.zeros((rows, ld), np.int8), np.zeros(rows, np.int32), np.zeros(rows, np.int32), np.zeros(rows, np.float32), np.zeros(rows, np.int32)
+
+    def op_quantize_weight(self, W, ld=None):
+        """quantize_weight_kernel + pack_dz on W [N, K] (pf_op_quantize_weight, hostile host).  Returns (w' int8 [N, ld] =
+        code - 128, colsum, wzp = zp - 128, wscale, dz)."""
+        W = _f32(W)
+        rows, depth = W.shape
+        w, cs, wz, ws, dz = self._op_weight_out(rows, ld or depth)
+        N.check(self._lib.pf_op_quantize_weight(self._h, _fp(W), rows, depth, ld or depth, w.ctypes.data_as(C.POINTER(C.c_int8)), _i32p(cs),
+                                                _i32p(wz), _fp(ws), _i32p(dz)))
+        return w, cs, wz, ws, dz
+
+    def op_import_weight(self, Q, zp, scale, ld=None):
+        """import_weight_kernel + pack_dz on the stored bytes of an int8 export (pf_op_import_weight); returns as op_quantize_weight."""
+        Q, zp, scale = np.ascontiguousarray(Q, np.uint8), np.ascontiguousarray(zp, np.uint8), _f32(scale)
+        rows, depth = Q.shape
+        w, cs, wz, ws, dz = self._op_weight_out(rows, ld or depth)
+        u8 = C.POINTER(C.c_uint8)
+        N.check(self._lib.pf_op_import_weight(self._h, Q.ctypes.data_as(u8), zp.ctypes.data_as(u8), _fp(scale), rows, depth, ld or depth,
+                                              w.ctypes.data_as(C.POINTER(C.c_int8)), _i32p(cs), _i32p(wz), _fp(ws), _i32p(dz)))
+        return w, cs, wz, ws, dz
+
+    def op_qgemm_ex(self, a_codes, a_scale, a_zp, w_codes, w_zp, w_scale, bias=None, resid=None, add2=None, relu=False, scale_cols=0,
+                    scale=1.0, out_kind=0, tile_rows=0, want_range=False, K_true=None):
+        """The integer GEMM on codes and parameters as given (pf_op_qgemm_ex, hostile host).  out_kind 0 fp32 (resid aliases
+        the result), 1 f16 through gemm_i8f_pp3, 2 f16 through gemm_i8_pp3's direct epilogue, 3 fp32 and f16 together.
+        Returns (y32 or None, y16 widened or None, (min, max) or None)."""
+        a, w = np.ascontiguousarray(a_codes, np.uint8), np.ascontiguousarray(w_codes, np.uint8)
+        M, K = a.shape
+        Nn = w.shape[0]
+        assert w.shape[1] == K and (K_true is None or K_true == K)
+        d = N.PfQgemmDesc()
+        d.struct_size = C.sizeof(N.PfQgemmDesc)
+        d.M, d.N, d.K = M, Nn, K
+        d.relu, d.out_kind, d.tile_rows, d.want_range = int(relu), out_kind, tile_rows, int(want_range)
+        d.scale_cols, d.scale, d.a_scale, d.a_zp = scale_cols, scale, float(a_scale), int(a_zp)
+        wz, ws = np.ascontiguousarray(w_zp, np.int32), _f32(w_scale)
+        assert wz.shape == (Nn,) and ws.shape == (Nn,)
+        d.w_zp, d.w_scale = _i32p(wz), _fp(ws)
+        keep = [_f32(t) if t is not None else None for t in (bias, resid, add2)]
+        d.bias, d.resid, d.add2 = [_fp(t) if t is not None else None for t in keep]
+        y32 = np.zeros((M, Nn), np.float32) if out_kind in (0, 3) else None
+        y16 = np.zeros((M, Nn), np.float32) if out_kind != 0 else None
+        rng = np.zeros(2, np.float32) if want_range else None
+        u8 = C.POINTER(C.c_uint8)
+        N.check(self._lib.pf_op_qgemm_ex(self._h, C.byref(d), a.ctypes.data_as(u8), w.ctypes.data_as(u8), _fp(y32) if y32 is not None else None,
+                                         _fp(y16) if y16 is not None else None, _fp(rng) if rng is not None else None))
+        return y32, y16, (float(rng[0]), float(rng[1])) if want_range else None
+
     def op_argmax(self, x) -> np.ndarray:
         a = _f32(x)
         V = a.shape[-1]

@@ -169,6 +169,26 @@ namespace AliParaformerAsr.Native
                                                                      IntPtr lm, float alpha, float beta, int flags, [Out] double[] outLm);
         [DllImport(Lib)] internal static extern int pf_op_lm_score(IntPtr e, IntPtr lm, int[] ids, int[] lens, int B, int L, float alpha, float beta,
                                                                   [Out] double[] g, [Out] int[] state);
+        // The int8 path (math_mode 2) one kernel at a time, for parity tests: the activation quantiser (optionally behind a
+        // LayerNorm that is never stored), the weight quantiser, the import of an export's stored bytes, and the integer GEMM on
+        // codes and parameters as given.  Hostile hosts: PF_ERR_DEVICE when a result cell comes back unwritten or a kernel stored
+        // outside what its contract allows.  codes / w: signed bytes (code - 128), pad columns included.
+        [StructLayout(LayoutKind.Sequential)]
+        internal struct PfQgemmDesc
+        {
+            public int struct_size, M, N, K, relu, out_kind, tile_rows, want_range, scale_cols;
+            public float scale, a_scale;
+            public int a_zp;
+            public IntPtr w_zp, w_scale, bias, resid, add2;
+        }
+        [DllImport(Lib)] internal static extern int pf_op_quantize(IntPtr e, float[] x, int rows, int cols, int ldx, int xIsF16, int ld, float[]? gamma,
+                                                                  float[]? beta, [Out] sbyte[] codes, [Out] int[] rowsum, [Out] float[] scaleZp);
+        [DllImport(Lib)] internal static extern int pf_op_quantize_weight(IntPtr e, float[] W, int N, int K, int ld, [Out] sbyte[] w, [Out] int[] colsum,
+                                                                         [Out] int[] wzp, [Out] float[] wscale, [Out] int[] dz);
+        [DllImport(Lib)] internal static extern int pf_op_import_weight(IntPtr e, byte[] Q, byte[] zp, float[] scale, int N, int K, int ld, [Out] sbyte[] w,
+                                                                       [Out] int[] colsum, [Out] int[] wzp, [Out] float[] wscale, [Out] int[] dz);
+        [DllImport(Lib)] internal static extern int pf_op_qgemm_ex(IntPtr e, ref PfQgemmDesc d, byte[] aCodes, byte[] wCodes, [Out] float[]? y32,
+                                                                  [Out] float[]? y16, [Out] float[]? range);
         // CTC forced alignment (additions to ABI 6): PF_DECODE_ALIGN (SenseVoice; implies SCORES) aligns the targets set for the next
         // forward, and with PF_DECODE_CTC_BEAM the beam's hypotheses, to the log-prob rows: Viterbi path and log-likelihood per job
         internal const int PF_DECODE_ALIGN = 32;

@@ -750,6 +750,47 @@ int pf_op_ctc_align(pf_engine* e, const float* lp, int32_t B, int32_t T, int32_t
 int pf_op_qlinear(pf_engine* e, const float* x, const float* W, const float* bias, int32_t M, int32_t N, int32_t K,
                   int32_t relu, int32_t x_is_f16, float* y, uint8_t* xq_out, float* aparams_out, uint8_t* wq_out,
                   float* wscale_out, int32_t* wzp_out);
+/* The parts of the same Linear one at a time, each on a hostile host: whatever the kernels' contracts (csrc/kernels.h) only
+   call readable holds a large finite pattern (float vectors behind their last element NaN, the operand pad rows of the GEMM
+   the codes +127 / -128, rowsum behind M large magnitudes), every output is sentinel-filled, and PF_ERR_DEVICE is returned
+   when a result cell comes back unwritten or anything outside the region the contract allows was stored to.
+   pf_op_quantize: DynamicQuantizeLinear of x [rows, cols] fp32 (x_is_f16: handed to the kernels as f16), placed with the row
+   stride ldx >= cols on the device, or — gamma / beta [cols] given (ldx == cols, fp32) — of LayerNorm(x) without storing it.
+   codes_out [rows, ld]: the signed bytes a' = q - 128 the matrix cores read, pad columns (0) included; rowsum_out [rows] =
+   sum_k a'; params_out [2] = {scale, zero point}. */
+int pf_op_quantize(pf_engine* e, const float* x, int32_t rows, int32_t cols, int32_t ldx, int32_t x_is_f16, int32_t ld,
+                   const float* gamma, const float* beta, int8_t* codes_out, int32_t* rowsum_out, float* params_out);
+/* The weight side: W [N, K] fp32 quantised per output channel (pf_op_quantize_weight), or the stored bytes of an int8 export
+   Q [N, K] u8, zp [N] u8, scale [N] (pf_op_import_weight) -> w_out [N, ld] signed bytes w' = q - 128 (pad columns 0),
+   colsum_out [N] = sum_k w', wzp_out [N] = zp - 128, wscale_out [N], dz_out [N] the packed column word of the f16-result
+   kernel (PF_ERR_UNSUPPORTED when K > 16384: the word does not hold it). */
+int pf_op_quantize_weight(pf_engine* e, const float* W, int32_t N, int32_t K, int32_t ld, int8_t* w_out, int32_t* colsum_out,
+                          int32_t* wzp_out, float* wscale_out, int32_t* dz_out);
+int pf_op_import_weight(pf_engine* e, const uint8_t* Q, const uint8_t* zp, const float* scale, int32_t N, int32_t K, int32_t ld,
+                        int8_t* w_out, int32_t* colsum_out, int32_t* wzp_out, float* wscale_out, int32_t* dz_out);
+/* The integer GEMM alone, on codes and parameters as given (no quantiser runs): the operands a', w', the row / column sums
+   and dz are built on the host. */
+typedef struct pf_qgemm_desc {
+  int32_t struct_size;
+  int32_t M, N, K;            /* K = the true depth (the operands are padded to a multiple of 128 with zeros)            */
+  int32_t relu;
+  int32_t out_kind;           /* 0 fp32 (resid, when given, aliases the result), 1 f16 into a padded buffer with dz
+                                 (gemm_i8f_pp3), 2 f16 unpadded (gemm_i8_pp3's direct epilogue), 3 fp32 and f16 together  */
+  int32_t tile_rows;          /* 0 = by shape, 128 / 256 = the tile height                                              */
+  int32_t want_range;         /* != 0: the launch reports the {min, max} of its results (range_out)                     */
+  int32_t scale_cols;         /* columns n < scale_cols are multiplied by scale after the bias                          */
+  float scale;
+  float a_scale; int32_t a_zp;   /* the activation tensor's parameters, zero point in 0 .. 255                         */
+  const int32_t* w_zp;        /* [N], 0 .. 255                                                                          */
+  const float* w_scale;       /* [N]                                                                                    */
+  const float* bias;          /* [N] or NULL                                                                            */
+  const float* resid;         /* [M,N] fp32 or NULL (out_kind 0, 2, 3)                                                  */
+  const float* add2;          /* [M,N] fp32 or NULL (out_kind 0, 2, 3)                                                  */
+} pf_qgemm_desc;
+/* a_codes [M, K], w_codes [N, K] uint8; y32 [M, N] (out_kind 0, 3), y16 [M, N] widened to fp32 (out_kind 1, 2, 3),
+   range_out [2] (want_range); the kernel's name is left under the profile class "gemm_op" (pf_profile_kernel). */
+int pf_op_qgemm_ex(pf_engine* e, const pf_qgemm_desc* d, const uint8_t* a_codes, const uint8_t* w_codes, float* y32, float* y16,
+                   float* range_out);
 int pf_op_gemm(pf_engine* e, const float* A, const float* W, const float* bias,
                int32_t M, int32_t N, int32_t K, int32_t epilogue, float* C);
 /* The GEMM as the pipeline launches it, every variant selectable. */
