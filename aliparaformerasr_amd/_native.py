@@ -173,6 +173,18 @@ SIGNATURES = {
     "pf_host_vad_segments": (C.c_int, [_i32, C.c_int32, C.c_int32, C.c_int32, _P(PfVadConfig), _i32, C.c_int32, _i32]),
     "pf_host_long_plan": (C.c_int, [_i32, C.c_int32, C.c_int32, C.c_int64, _i32, _i32, _i32]),
     "pf_op_vad_levels": (C.c_int, [_vp, _f, C.c_int64, C.c_int32, _i32]),
+    "pf_vad_model_load": (C.c_int, [C.c_char_p, _P(_vp)]),
+    "pf_vad_model_from_memory": (C.c_int, [_vp, C.c_int64, _P(_vp)]),
+    "pf_vad_model_info": (C.c_int, [_vp, _i32, _i32, _i64]),
+    "pf_vad_model_sil_ids": (C.c_int, [_vp, _i32, C.c_int32, _i32]),
+    "pf_vad_model_tensor": (C.c_int, [_vp, C.c_char_p, _f, C.c_int64, _i64]),
+    "pf_vad_model_config": (C.c_int, [_P(PfVadConfig)]),
+    "pf_vad_model_free": (None, [_vp]),
+    "pf_host_vad_model_logits": (C.c_int, [_vp, _f, C.c_int64, C.c_int32, _P(C.c_double)]),
+    "pf_host_vad_model_levels": (C.c_int, [_vp, _f, C.c_int64, C.c_int32, _i32]),
+    "pf_engine_set_vad_model": (C.c_int, [_vp, _vp]),
+    "pf_op_vad_model_logits": (C.c_int, [_vp, _f, _i32, C.c_int32, C.c_int32, _f]),
+    "pf_op_vad_model_levels": (C.c_int, [_vp, _f, _i32, C.c_int32, C.c_int32, _i32]),
     "pf_op_vad_segments": (C.c_int, [_vp, _i32, _i32, C.c_int32, C.c_int32, C.c_int32, _P(PfVadConfig), _i32, C.c_int32, _i32]),
     "pf_stream_add_pcm": (C.c_int, [_vp, _vp, C.c_int64, _P(PfPcmDesc)]),
     "pf_host_wav_info": (C.c_int, [C.c_char_p, _P(PfPcmDesc), _i64, _i64, C.POINTER(C.c_double)]),
@@ -241,6 +253,7 @@ SIGNATURES = {
                                      _P(C.c_double), _i32, _i32]),
     "pf_op_lm_score": (C.c_int, [_vp, _vp, _i32, _i32, C.c_int32, C.c_int32, C.c_float, C.c_float, _P(C.c_double), _i32]),
     "pf_recognizer_set_vad": (C.c_int, [_vp, _P(PfVadConfig), C.c_int32, C.c_int64, C.c_char_p]),
+    "pf_recognizer_set_vad_model": (C.c_int, [_vp, C.c_char_p]),
     "pf_stream_num_segments": (C.c_int, [_vp, _i32]),
     "pf_stream_segment": (C.c_int, [_vp, C.c_int32, _i32, _i32, _i32, _i32, _i32, _i32, _cpp]),
     "pf_recognizer_set_hotword_boost": (C.c_int, [_vp, C.c_float]),

@@ -15,6 +15,10 @@ mismatch with a real file fails loudly instead of producing a silently wrong mod
                                                            [--timestamp]
     python -m aliparaformerasr_amd.convert model.int8.onnx out.pfw [--eb model_eb.int8.onnx] [--kind ...]
         (ONNX graph walk, see onnx_to_state_dict; an int8 file's stored bytes are carried beside their float image)
+    python -m aliparaformerasr_amd.convert vad.onnx|vad.pt out.pfw --kind fsmnvad --mvn vad.mvn [--sil 0,...] [--lfr-m 5]
+        (FunASR's FSMN-VAD, the model score of the voice-activity segmentation: vad_state_dict_to_pfw / vad_onnx_to_state_dict.
+         NO REAL FSMN-VAD FILE HAS BEEN THROUGH THIS ROUTE: the names are restated from the public FunASR sources and
+         exercised on tests/fsmn_vad_like.py)
 """
 from __future__ import annotations
 
@@ -291,6 +295,138 @@ def onnx_to_pfw(model_path, eb_path=None, kind="paraformer", timestamp=None):
     return cfg, wts
 
 
+# ------------------------------------------------------------------ FSMN-VAD ---------
+def parse_mvn_text(text: str):
+    """(shift, scale) float32 of an am.mvn / vad.mvn in the kaldi-nnet text layout (weights.format_mvn_text): the vectors
+    between '[' and ']' on the <LearnRateCoef> lines that follow <AddShift> and <Rescale>."""
+    out = {}
+    lines = text.splitlines()
+    for i, ln in enumerate(lines):
+        tag = ln.split()[0] if ln.split() else ""
+        if tag in ("<AddShift>", "<Rescale>"):
+            for nxt in lines[i + 1: i + 3]:
+                if nxt.lstrip().startswith("<LearnRateCoef>") and "[" in nxt and "]" in nxt:
+                    out[tag] = np.asarray([float(x) for x in nxt[nxt.index("[") + 1: nxt.rindex("]")].split()], np.float32)
+                    break
+    if "<AddShift>" not in out or "<Rescale>" not in out or out["<AddShift>"].shape != out["<Rescale>"].shape:
+        raise ValueError("mvn: no <AddShift> / <Rescale> vectors of one length")
+    return out["<AddShift>"], out["<Rescale>"]
+
+
+def vad_name_map(n_layers: int) -> dict:
+    """PFW tensor name -> FunASR FSMN-VAD state_dict key (funasr.models.fsmn_vad_streaming.encoder.FSMN under `encoder.`)."""
+    m = {}
+    for a in ("in1", "in2", "out1", "out2"):
+        f = {"in1": "in_linear1", "in2": "in_linear2", "out1": "out_linear1", "out2": "out_linear2"}[a]
+        m[a + ".weight"], m[a + ".bias"] = "encoder.%s.linear.weight" % f, "encoder.%s.linear.bias" % f
+    for l in range(n_layers):
+        m["fsmn.%d.linear.weight" % l] = "encoder.fsmn.%d.linear.linear.weight" % l
+        m["fsmn.%d.taps" % l] = "encoder.fsmn.%d.fsmn_block.conv_left.weight" % l
+        m["fsmn.%d.affine.weight" % l] = "encoder.fsmn.%d.affine.linear.weight" % l
+        m["fsmn.%d.affine.bias" % l] = "encoder.fsmn.%d.affine.linear.bias" % l
+    return m
+
+
+def vad_state_dict_to_pfw(sd: dict, shift, scale, sil_ids=(0,), lfr_m: int = 5, lstride: int = 1):
+    """FunASR FSMN-VAD state dict (+ the vad.mvn vectors) -> (cfg, PFW weights) of kind "fsmnvad".  The depthwise
+    conv_left.weight [proj, 1, lorder, 1] becomes taps [lorder, proj]; lstride is the conv's dilation, which a state dict does
+    not carry (the ONNX route reads it from the graph).  KeyError lists missing keys; ValueError on a shape clash or a
+    right-context block (conv_right: rorder > 0 is not supported)."""
+    sd = {k: np.asarray(v, np.float32) for k, v in sd.items()}
+    if any(".conv_right." in k for k in sd):
+        raise ValueError("fsmnvad: the checkpoint has conv_right tensors (rorder > 0), which is not supported")
+    ids = {int(m.group(1)) for k in sd for m in [re.match(r"encoder\.fsmn\.(\d+)\.", k)] if m}
+    n_layers = max(ids) + 1 if ids else 0
+    nm = vad_name_map(n_layers)
+    missing = [v for v in nm.values() if v not in sd]
+    if missing or not n_layers:
+        raise KeyError("checkpoint lacks %d expected tensors, e.g. %s" % (len(missing), missing[:5]))
+    conv = sd[nm["fsmn.0.taps"]]
+    if conv.ndim != 4 or conv.shape[1] != 1 or conv.shape[3] != 1:
+        raise ValueError("fsmnvad: conv_left.weight has shape %s, expected [proj, 1, lorder, 1]" % (list(conv.shape),))
+    shift, scale = np.asarray(shift, np.float32).reshape(-1), np.asarray(scale, np.float32).reshape(-1)
+    I = int(sd[nm["in1.weight"]].shape[1])
+    if I % lfr_m:
+        raise ValueError("fsmnvad: input width %d is no multiple of lfr_m %d" % (I, lfr_m))
+    cfg = W.fsmn_vad_config(n_mels=I // lfr_m, lfr_m=lfr_m, affine_dim=int(sd[nm["in1.weight"]].shape[0]),
+                            linear_dim=int(sd[nm["in2.weight"]].shape[0]), proj_dim=int(conv.shape[0]),
+                            output_dim=int(sd[nm["out2.weight"]].shape[0]), n_layers=n_layers, lorder=int(conv.shape[2]),
+                            lstride=int(lstride), sil_ids=tuple(int(i) for i in sil_ids))
+    out = {"cmvn.shift": shift, "cmvn.scale": scale}
+    for k, v in nm.items():
+        a = sd[v]
+        out[k] = np.ascontiguousarray(a[:, 0, :, 0].T if k.endswith(".taps") else a)
+    for k, want in W.vad_tensor_shapes(cfg).items():
+        if tuple(out[k].shape) != tuple(want):
+            raise ValueError("%s: shape %s, expected %s" % (k, list(out[k].shape), list(want)))
+    if any(not 0 <= i < cfg["output_dim"] for i in cfg["sil_ids"]):
+        raise ValueError("fsmnvad: a silence id is outside [0, output_dim)")
+    return cfg, out
+
+
+def vad_onnx_to_state_dict(graph):
+    """A FunASR FSMN-VAD ONNX export -> ({FunASR parameter name: float32 array}, lstride).  The exporter anonymises the MatMul
+    weights, so the graph is walked from `speech` in node order: MatMul nodes whose second operand is a 2-D initialiser and
+    Conv nodes with a 4-D initialiser, in the order in_linear1, in_linear2, (linear, conv_left, affine) per block, out_linear1,
+    out_linear2; a bias is the 1-D initialiser of the Add that consumes the MatMul.  The in_cache* / out_cache* inputs and
+    outputs and the trailing Softmax carry no parameters and are passed over.  ValueError when the sequence does not have
+    that shape."""
+    ini = graph.initializers
+    if "speech" not in graph.inputs:
+        raise ValueError("fsmnvad: the graph has no input named speech")
+    seq = []
+    for node in graph.nodes:
+        if node.op_type == "MatMul" and len(node.inputs) == 2 and node.inputs[1] in ini and ini[node.inputs[1]].ndim == 2:
+            bias = None
+            for c in graph.consumers(node.outputs[0]):
+                if c.op_type == "Add":
+                    for i in c.inputs:
+                        if i in ini and ini[i].ndim == 1 and ini[i].shape[0] == ini[node.inputs[1]].shape[1]:
+                            bias = np.asarray(ini[i], np.float32)
+            seq.append(("mm", np.ascontiguousarray(np.asarray(ini[node.inputs[1]], np.float32).T), bias))
+        elif node.op_type == "Conv" and len(node.inputs) >= 2 and node.inputs[1] in ini and ini[node.inputs[1]].ndim == 4:
+            dil = node.attrs.get("dilations") or [1, 1]
+            seq.append(("conv", np.asarray(ini[node.inputs[1]], np.float32), int(dil[0])))
+    kinds = "".join("c" if s[0] == "conv" else ("B" if s[2] is not None else "m") for s in seq)
+    mt = re.fullmatch(r"BB((?:mcB)+)BB", kinds)
+    if not mt:
+        raise ValueError("fsmnvad: the graph's MatMul / Conv sequence %r is not in_linear1, in_linear2, (linear, conv_left, affine)*, "
+                         "out_linear1, out_linear2" % kinds)
+    n_layers = len(mt.group(1)) // 3
+    sd = {}
+
+    def put(prefix, s):
+        sd[prefix + ".weight"] = s[1]
+        if s[2] is not None:
+            sd[prefix + ".bias"] = s[2]
+    put("encoder.in_linear1.linear", seq[0]); put("encoder.in_linear2.linear", seq[1])
+    strides = set()
+    for l in range(n_layers):
+        lin, conv, aff = seq[2 + 3 * l: 5 + 3 * l]
+        put("encoder.fsmn.%d.linear.linear" % l, lin)
+        sd["encoder.fsmn.%d.fsmn_block.conv_left.weight" % l] = conv[1]
+        strides.add(conv[2])
+        put("encoder.fsmn.%d.affine.linear" % l, aff)
+    put("encoder.out_linear1.linear", seq[-2]); put("encoder.out_linear2.linear", seq[-1])
+    if len(strides) != 1:
+        raise ValueError("fsmnvad: the blocks have different dilations %s" % sorted(strides))
+    return sd, strides.pop()
+
+
+def vad_to_pfw(model_path, mvn_path, sil_ids=(0,), lfr_m=5, lstride=1):
+    with open(mvn_path, "r") as f:
+        shift, scale = parse_mvn_text(f.read())
+    if str(model_path).endswith(".onnx"):
+        from . import onnx_reader as R
+        sd, lstride = vad_onnx_to_state_dict(R.load(model_path))
+    else:
+        import torch
+        sd = torch.load(model_path, map_location="cpu")
+        sd = sd.get("state_dict", sd.get("model", sd)) if isinstance(sd, dict) else sd
+        sd = {k: v.float().numpy() for k, v in sd.items() if hasattr(v, "numpy")}
+    return vad_state_dict_to_pfw(sd, shift, scale, sil_ids, lfr_m, lstride)
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     if len(argv) < 2:
@@ -299,6 +435,17 @@ def main(argv=None):
     kind, ts = "paraformer", None
     if "--kind" in argv:
         kind = argv[argv.index("--kind") + 1]
+    if kind == "fsmnvad":
+        if "--mvn" not in argv:
+            print("--kind fsmnvad needs --mvn vad.mvn (the model's own CMVN)")
+            return 2
+        sil = tuple(int(x) for x in argv[argv.index("--sil") + 1].split(",")) if "--sil" in argv else (0,)
+        lfr_m = int(argv[argv.index("--lfr-m") + 1]) if "--lfr-m" in argv else 5
+        lstride = int(argv[argv.index("--lstride") + 1]) if "--lstride" in argv else 1
+        cfg, wts = vad_to_pfw(argv[0], argv[argv.index("--mvn") + 1], sil, lfr_m, lstride)
+        W.save_pfw(argv[1], cfg, wts)
+        print("wrote %s (%s, %d tensors)" % (argv[1], cfg["kind"], len(wts)))
+        return 0
     if "--timestamp" in argv:
         ts = True
     if argv[0].endswith(".onnx"):

@@ -897,6 +897,116 @@ int pf_op_vad_segments(pf_engine* h, const int32_t* levels, const int32_t* T, in
   PF_CATCH
 }
 
+// ---- voice-activity segmentation, model score ----
+int pf_vad_model_load(const char* path, pf_vad_model** m) {
+  PF_TRY
+  NEED(m); NEED(path);
+  *m = nullptr;
+  std::shared_ptr<const VadModel> p = vad_model_load(path);
+  *m = new pf_vad_model{std::move(p)};
+  return PF_OK;
+  PF_CATCH
+}
+int pf_vad_model_from_memory(const void* data, int64_t nbytes, pf_vad_model** m) {
+  PF_TRY
+  NEED(m); NEED(data);
+  *m = nullptr;
+  std::shared_ptr<const VadModel> p = vad_model_from_memory(data, nbytes);
+  *m = new pf_vad_model{std::move(p)};
+  return PF_OK;
+  PF_CATCH
+}
+int pf_vad_model_info(const pf_vad_model* m, int32_t* dims, int32_t* n_sil, int64_t* image_bytes) {
+  PF_TRY
+  NEED(m);
+  const VadModel& v = *m->p;
+  if (dims) {
+    const int32_t d[9] = {v.input_dim, v.affine_dim, v.linear_dim, v.proj_dim, v.output_dim, v.n_layers, v.lorder, v.lstride, v.lfr_m};
+    std::memcpy(dims, d, sizeof(d));
+  }
+  if (n_sil) *n_sil = (int32_t)v.sil_ids.size();
+  if (image_bytes) *image_bytes = (int64_t)v.image.size();
+  return PF_OK;
+  PF_CATCH
+}
+int pf_vad_model_sil_ids(const pf_vad_model* m, int32_t* sil, int32_t cap, int32_t* n) {
+  PF_TRY
+  NEED(m); NEED(n);
+  *n = (int32_t)m->p->sil_ids.size();
+  PF_CHECK(cap >= *n, PF_ERR_CAPACITY, "vad model: capacity below the number of silence ids");
+  if (*n > 0) { NEED(sil); std::memcpy(sil, m->p->sil_ids.data(), (size_t)*n * 4); }
+  return PF_OK;
+  PF_CATCH
+}
+int pf_vad_model_tensor(const pf_vad_model* m, const char* name, float* out, int64_t cap, int64_t* n) {
+  PF_TRY
+  NEED(m); NEED(name); NEED(n);
+  const std::vector<float>* t = m->p->tensor(name);
+  PF_CHECK(t != nullptr, PF_ERR_INVALID_ARG, std::string("vad model: no tensor named '") + name + "'");
+  *n = (int64_t)t->size();
+  if (!out && cap == 0) return PF_OK;
+  PF_CHECK(cap >= *n, PF_ERR_CAPACITY, "vad model: capacity below the tensor's size");
+  NEED(out);
+  std::memcpy(out, t->data(), t->size() * 4);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_vad_model_config(pf_vad_config* cfg) {
+  PF_TRY
+  NEED(cfg);
+  *cfg = vad_model_default();
+  return PF_OK;
+  PF_CATCH
+}
+void pf_vad_model_free(pf_vad_model* m) { delete m; }
+int pf_host_vad_model_logits(const pf_vad_model* m, const float* rows, int64_t T, int32_t n_mels, double* out) {
+  PF_TRY
+  NEED(m);
+  PF_CHECK(T >= 0 && n_mels >= 1 && n_mels <= 1024, PF_ERR_INVALID_ARG, "vad_model_logits: bad shape (n_mels 1 .. 1024)");
+  if (T > 0) { NEED(rows); NEED(out); }
+  host_vad_model_logits(*m->p, rows, T, n_mels, out);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_host_vad_model_levels(const pf_vad_model* m, const float* rows, int64_t T, int32_t n_mels, int32_t* out) {
+  PF_TRY
+  NEED(m);
+  PF_CHECK(T >= 0 && n_mels >= 1 && n_mels <= 1024, PF_ERR_INVALID_ARG, "vad_model_levels: bad shape (n_mels 1 .. 1024)");
+  if (T > 0) { NEED(rows); NEED(out); }
+  host_vad_model_levels(*m->p, rows, T, n_mels, out);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_engine_set_vad_model(pf_engine* h, const pf_vad_model* m) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->set_vad_model(m ? m->p : nullptr);
+  return PF_OK;
+  PF_CATCH
+}
+static int op_vad_model(pf_engine* h, const float* rows, const int32_t* T, int32_t B, int32_t n_mels, float* logits, int32_t* levels) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  PF_CHECK(B >= 0 && n_mels >= 1 && n_mels <= 1024, PF_ERR_INVALID_ARG, "vad_model: bad shape (n_mels 1 .. 1024)");
+  if (B > 0) NEED(T);
+  int64_t total = 0;
+  for (int b = 0; b < B; ++b) total += std::max(T[b], 0);
+  if (total > 0) { NEED(rows); PF_CHECK(logits || levels, PF_ERR_INVALID_ARG, "null argument: out"); }
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->op_vad_model(rows, T, B, n_mels, logits, levels);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_op_vad_model_logits(pf_engine* h, const float* rows, const int32_t* T, int32_t B, int32_t n_mels, float* out) {
+  return op_vad_model(h, rows, T, B, n_mels, out, nullptr);
+}
+int pf_op_vad_model_levels(pf_engine* h, const float* rows, const int32_t* T, int32_t B, int32_t n_mels, int32_t* out) {
+  return op_vad_model(h, rows, T, B, n_mels, nullptr, out);
+}
+
 int pf_op_topk(pf_engine* h, const float* x, int64_t rows, int32_t V, int32_t ld, int32_t K, int64_t* ids, float* val,
                int32_t* n) {
   PF_TRY
@@ -1661,6 +1771,14 @@ int pf_recognizer_set_vad(pf_recognizer* h, const pf_vad_config* cfg, int32_t ba
   std::shared_ptr<Recognizer> r = R(h);
   PF_CHECK(!r->disposed(), PF_ERR_DISPOSED, "OfflineRecognizer");
   r->SetVad(cfg, batch_max, frame_budget, sep_utf8);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_recognizer_set_vad_model(pf_recognizer* h, const char* pfw_path) {
+  PF_TRY
+  std::shared_ptr<Recognizer> r = R(h);
+  PF_CHECK(!r->disposed(), PF_ERR_DISPOSED, "OfflineRecognizer");
+  r->SetVadModel(pfw_path ? pfw_path : "");
   return PF_OK;
   PF_CATCH
 }

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "lm.h"
+#include "vadnet.h"
 #include "json.h"
 #include "kernels.h"
 #include "shards.h"
@@ -242,6 +243,17 @@ class Engine {
                           int32_t* n_seg);
   void vad_staged(const pf_vad_config* cfg, int32_t* seg, int cap, int32_t* n_seg);
   void op_vad_levels(const float* rows, int64_t T, int n_mels, int32_t* out);
+  // The FSMN-VAD model score (k_vadnet.hip, vadnet.h): with a model attached vad_staged computes the levels with the network
+  // (profile class "vadnet", 1 + n_layers launches) where it otherwise launches the energy level; everything behind the levels
+  // is unchanged.  nullptr detaches and frees the image and the p rows (nothing of it is launched or allocated then; attaching the
+  // same model to an engine that still has it costs no upload).  The engine keeps a reference and uploads the
+  // image once.  PF_ERR_INVALID_ARG unless n_mels * lfr_m equals the model's input width; PF_ERR_UNSUPPORTED with snip_edges.
+  void set_vad_model(const std::shared_ptr<const VadModel>& m);
+  bool vad_model_on() const { return (bool)vadnet_; }
+  const std::shared_ptr<const VadModel>& vad_model() const { return vadnet_; }
+  // the network on caller rows: rows = the concatenated frames of B utterances of T[b] frames; logits [sum T, output_dim]
+  // and / or levels [sum T] (either may be null).  Uses the attached model.
+  void op_vad_model(const float* rows, const int32_t* T, int B, int n_mels, float* logits, int32_t* levels);
   void op_vad_segments(const int32_t* levels, const int32_t* T, int B, int ld, int n_mels, const pf_vad_config* cfg, int32_t* seg,
                        int cap, int32_t* n);
   void op_ctc_collapse(const int64_t* ids, const float* scores, const int32_t* lens, int B, int T, int blank, int64_t* ids_out,
@@ -560,6 +572,12 @@ class Engine {
                                      // the one pf_op_* last used
   const int32_t* lm_device_image(LmDev& d, const std::shared_ptr<const LmImage>& lm);
   std::shared_ptr<const LmImage> lm_;   // the installed model (nullptr: none), its weights and flags
+  // the FSMN-VAD model (set_vad_model): the attached model, its image on the device and the two p buffers the launches alternate
+  // between; allocated by an attach / a run only, freed by a detach
+  std::shared_ptr<const VadModel> vadnet_;
+  struct VadNetDev { DevBuf buf; std::shared_ptr<const VadModel> src; } vadnet_dev_;
+  DevBuf ws_vadnet_;
+  void run_vadnet(const float* rows_dev, const int64_t* off_dev, int B, int64_t total, int n_mels, float* logits_dev, int32_t* levels_dev);
   float lm_alpha_ = 0.f, lm_beta_ = 0.f;
   int lm_flags_ = 0;
   // the n-best search (set_nbest_search; 0: off), its model with weights and flags (set_nbest_lm), its workspace

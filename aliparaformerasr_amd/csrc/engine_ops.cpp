@@ -271,13 +271,111 @@ void Engine::vad_staged(const pf_vad_config* cfg, int32_t* seg, int cap, int32_t
                  st_total_frames_, 0, (float*)ws_fbank_.p, fc_.dither, next_dither_seed());
     prof_end("fbank");
   }
-  prof_begin("vad", 0);
-  launch_vad_levels(stream_, (const float*)ws_fbank_.p, st_total_frames_, fc_.n_mels, L.lev(ws));
-  prof_end("vad");
+  if (vadnet_) {
+    run_vadnet((const float*)ws_fbank_.p, meta + 2 * (B + 1), B, st_total_frames_, fc_.n_mels, nullptr, L.lev(ws));
+  } else {
+    prof_begin("vad", 0);
+    launch_vad_levels(stream_, (const float*)ws_fbank_.p, st_total_frames_, fc_.n_mels, L.lev(ws));
+    prof_end("vad");
+  }
   prof_begin("vad", 0);
   launch_vad_segments(stream_, L.lev(ws), meta + 2 * (B + 1), t80d, B, vad_params(c, fc_.n_mels), L.seg(ws), dev_cap, L.n(ws));
   prof_end("vad");
   vad_read_back(stream_, ws, L, B, cap, dev_cap, seg, n_seg);
+}
+
+// ---- the FSMN-VAD model score (k_vadnet.hip; the launch plan is at the head of that file)
+void Engine::set_vad_model(const std::shared_ptr<const VadModel>& m) {
+  if (!m) {                                         // detached: nothing of the network stays allocated
+    vadnet_.reset();
+    vadnet_dev_.src.reset();
+    if (vadnet_dev_.buf.p || ws_vadnet_.p) {
+      PF_HIP(hipSetDevice(device_));
+      PF_HIP(hipStreamSynchronize(stream_));        // a queued launch may still read the image or the p rows
+      for (DevBuf* b : {&vadnet_dev_.buf, &ws_vadnet_})
+        if (b->p) { PF_HIP(hipFree(b->p)); b->p = nullptr; b->bytes = 0; }
+    }
+    return;
+  }
+  PF_CHECK((int64_t)fc_.n_mels * m->lfr_m == m->input_dim, PF_ERR_INVALID_ARG,
+           "set_vad_model: n_mels * lfr_m does not equal the model's input width");
+  PF_CHECK(!fc_.snip_edges, PF_ERR_UNSUPPORTED, "set_vad_model: snip_edges = true is not supported");
+  PF_HIP(hipSetDevice(device_));
+  if (vadnet_dev_.src != m) {
+    PF_HIP(hipStreamSynchronize(stream_));          // a queued launch may still read the image about to be replaced
+    vadnet_dev_.src.reset();
+    ensure(vadnet_dev_.buf, m->image.size());
+    PF_HIP(hipMemcpyAsync(vadnet_dev_.buf.p, m->image.data(), m->image.size(), hipMemcpyHostToDevice, stream_));
+    PF_HIP(hipStreamSynchronize(stream_));
+    vadnet_dev_.src = m;
+  }
+  vadnet_ = m;
+}
+
+void Engine::run_vadnet(const float* rows_dev, const int64_t* off_dev, int B, int64_t total, int n_mels, float* logits_dev,
+                        int32_t* levels_dev) {
+  const VadModel& m = *vadnet_;
+  PF_CHECK((int64_t)n_mels * m.lfr_m == m.input_dim, PF_ERR_INVALID_ARG, "vad model: n_mels * lfr_m does not equal the model's input width");
+  if (total <= 0 || B <= 0) return;
+  const size_t pbytes = (size_t)round_up((int64_t)total * m.ldp * 4, 256);
+  ensure(ws_vadnet_, 2 * pbytes);
+  float* p[2] = {(float*)ws_vadnet_.p, (float*)((char*)ws_vadnet_.p + pbytes)};
+  for (int l = 0; l <= m.n_layers; ++l) {
+    VadNetLaunch a{};
+    a.img = (const char*)vadnet_dev_.buf.p; a.off = off_dev; a.B = B; a.total = total; a.ld = m.lds_ld;
+    a.ldp = m.ldp; a.lorder = m.lorder; a.lstride = m.lstride;
+    double flops = 0;
+    auto mid = [&](const VadGemm& g, bool relu) { a.mid[a.n_mid] = g; a.mid_relu[a.n_mid] = relu ? 1 : 0; ++a.n_mid; flops += 2.0 * g.Npad * g.Kpad; };
+    if (l == 0) {
+      a.head = 0; a.head_w = m.g_in1.Kpad;
+      a.x = rows_dev; a.n_mels = n_mels; a.lfr_m = m.lfr_m; a.in_dim = m.input_dim; a.shift_off = m.shift_off; a.scale_off = m.scale_off;
+      mid(m.g_in1, false); mid(m.g_in2, true);
+    } else {
+      a.head = 1; a.head_w = m.g_aff[l - 1].Kpad;
+      a.p_in = p[(l - 1) & 1]; a.taps_off = m.taps_off[l - 1];
+      mid(m.g_aff[l - 1], true);
+    }
+    if (l < m.n_layers) {
+      a.tail = 0; a.last = m.g_lin[l]; a.p_out = p[l & 1];
+    } else {
+      mid(m.g_out1, false);
+      a.tail = 1; a.last = m.g_out2; a.sil_off = m.sil_off; a.out_dim = m.output_dim; a.logits = logits_dev; a.levels = levels_dev;
+    }
+    flops += 2.0 * a.last.Npad * a.last.Kpad;
+    prof_begin("vadnet", flops * (double)total);
+    launch_vadnet(stream_, a);
+    prof_end("vadnet");
+  }
+}
+
+void Engine::op_vad_model(const float* rows, const int32_t* T, int B, int n_mels, float* logits, int32_t* levels) {
+  PF_CHECK(vadnet_ != nullptr, PF_ERR_INVALID_ARG, "op_vad_model: no model is attached (pf_engine_set_vad_model)");
+  PF_CHECK((int64_t)n_mels * vadnet_->lfr_m == vadnet_->input_dim, PF_ERR_INVALID_ARG,
+           "op_vad_model: n_mels * lfr_m does not equal the model's input width");
+  std::vector<int64_t> off((size_t)B + 1, 0);
+  for (int b = 0; b < B; ++b) {
+    PF_CHECK(T[b] >= 0, PF_ERR_INVALID_ARG, "op_vad_model: negative frame count");
+    PF_CHECK(T[b] <= PF_VAD_MAX_FRAMES, PF_ERR_CAPACITY, "vad: more than PF_VAD_MAX_FRAMES frames");
+    off[b + 1] = off[b] + T[b];
+  }
+  PF_HIP(hipSetDevice(device_));
+  const int64_t total = off[(size_t)B];
+  if (total == 0) return;
+  const int O = vadnet_->output_dim;
+  Cursor c;
+  const Field<float> d_x = c.take<float>((size_t)total * n_mels + 4);
+  const Field<int64_t> d_off = c.take<int64_t>((size_t)B + 1);
+  const Field<int32_t> d_e = c.take<int32_t>((size_t)total);
+  c.off = (size_t)round_up((int64_t)c.off, 16);
+  const Field<float> d_z = c.take<float>(logits ? (size_t)total * O : 0);
+  ensure(ws_tmp_, c.off);
+  void* ws = ws_tmp_.p;
+  PF_HIP(hipMemcpyAsync(d_x(ws), rows, (size_t)total * n_mels * 4, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipMemcpyAsync(d_off(ws), off.data(), off.size() * 8, hipMemcpyHostToDevice, stream_));
+  run_vadnet(d_x(ws), d_off(ws), B, total, n_mels, logits ? d_z(ws) : nullptr, d_e(ws));
+  if (logits) PF_HIP(hipMemcpyAsync(logits, d_z(ws), (size_t)total * O * 4, hipMemcpyDeviceToHost, stream_));
+  if (levels) PF_HIP(hipMemcpyAsync(levels, d_e(ws), (size_t)total * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipStreamSynchronize(stream_));                          // (`off` is read by its copy until then)
 }
 
 // the five decoders on caller data; ws_tmp_: the result block of decode_blocks.h, then the uploaded inputs and the scratch

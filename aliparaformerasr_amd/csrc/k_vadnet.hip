@@ -1,0 +1,277 @@
+// k_vadnet.hip — the FSMN-VAD model score on the device (paraformer_hip.h "Voice-activity segmentation, model score",
+// DESIGN.md §4.6k).  The definition in numpy float64 is tests/vadnet_ref.py, the host twin host_vad_model_* (vadnet.cpp).
+//
+// Rows are the concatenated 10 ms fbank frames of all B utterances (frame offsets off [B + 1]); a workgroup of four waves
+// owns a tile of 64 consecutive rows, which may straddle utterance boundaries: every row looks up its own utterance, and the
+// LFR clamp and the zero history of the FSMN taps are per utterance.  1 + n_layers launches of ONE kernel:
+//   launch 0            LFR + CMVN -> in_linear1 -> in_linear2 + ReLU -> linear_0                       -> p_0
+//   launch l = 1 .. n-1 FSMN taps over p_{l-1} (global memory, left halo) -> affine_{l-1} + ReLU -> linear_l -> p_l
+//   launch n            FSMN taps over p_{n-1} -> affine_{n-1} + ReLU -> out_linear1 -> out_linear2 -> softmax -> level
+// The only dependence between tiles is the tap halo, which a launch boundary covers: no grid barrier, nothing persistent.
+//
+// A product is Y^T [N, 64] = W [N, K] X^T [K, 64] on v_mfma_f32_32x32x16_f16: W as the A operand (fragments tiled once at
+// attach time, vadnet.h VadGemm, streamed from L2 16 bytes per lane), the activation tile X [64, K] f16 row-major in LDS as
+// the B operand (row stride ld = the widest operand + 8 halves: an odd number of 16-byte chunks, so the rows of a read do not
+// all start on one bank; it is not conflict-free: at the released size ld = 408 is 204 dwords = 12 mod 64, and rows r and
+// r + 16 of a read share a bank.  The cost of that was not measured).  A wave
+// takes the 32-row blocks nt = wave, wave + 4, ... of W and both 32-row halves of the tile; the accumulator starts as the
+// bias.  Lane (r, h) then holds row 32 i + r of the tile and the 16 channels 32 nt + 8 g + 4 h + (0 .. 3), g = 0 .. 3.
+//
+// Rounding points (everything else is fp32): R0 the weights, once, at attach time; R1 the LFR + CMVN input; R2 in_linear1's
+// output; R3 in_linear2's after ReLU; R4 the FSMN sum m; R5 affine's output after ReLU; R6 out_linear1's output.  p is stored
+// as fp32 [rows, ldp] (proj padded to 32; the padding columns hold zeros), the logits are fp32 and go to memory only when asked
+// for.  Padded rows and columns of W are zeros, padded columns of X are written as zeros, so padding never changes a sum;
+// columns at or beyond output_dim never enter the softmax.
+//
+// The softmax runs on the accumulators: every lane keeps (max, sum, silence sum) over its channels on line, the two lane
+// halves are merged with one shuffle, the four waves through 3 KB of LDS; e = rint((1 - 2 s) * 16384), -16384 when that is
+// not finite.  ReLU is x < 0 ? 0 : x, which keeps a NaN (fmaxf would drop it).
+// Nothing at or beyond an utterance's T is read; rows at or beyond the total are computed as zeros and never stored.
+#include "kdev.h"
+#include "kernels.h"
+
+namespace pf {
+
+namespace {
+
+constexpr int VN_ROWS = 64;
+
+struct VnRowInfo {            // per tile row: the first row of its utterance and that utterance's length; T = 0: no such row
+  long long start[VN_ROWS];
+  int T[VN_ROWS];
+};
+
+// X [64, g.Kpad] (LDS, row stride ld halves) times W^T: epi(nt, i, acc) per 32-row block nt of W and tile half i
+template <class Epi>
+__device__ __forceinline__ void vn_product(const char* __restrict__ img, const VadGemm& g, const half_t* __restrict__ x, int ld, int wave,
+                                           int lane, Epi&& epi) {
+  const int r = lane & 31, h = lane >> 5, KS = g.Kpad >> 4;
+  const h8* __restrict__ wt = reinterpret_cast<const h8*>(img + g.w_off);
+  const float* __restrict__ bias = reinterpret_cast<const float*>(img + g.b_off);
+  const half_t* x0 = x + r * ld + 8 * h;
+  const half_t* x1 = x0 + 32 * ld;
+  for (int nt = wave; nt < (g.Npad >> 5); nt += 4) {
+    f16x acc[2];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const float4 b4 = *reinterpret_cast<const float4*>(bias + 32 * nt + 8 * q + 4 * h);
+      acc[0][4 * q + 0] = b4.x; acc[0][4 * q + 1] = b4.y; acc[0][4 * q + 2] = b4.z; acc[0][4 * q + 3] = b4.w;
+    }
+    acc[1] = acc[0];
+    const h8* wp = wt + ((size_t)nt * KS) * 64 + lane;
+    h8 wn = wp[0];
+    for (int ks = 0; ks < KS; ++ks) {
+      const h8 wf = wn;
+      if (ks + 1 < KS) wn = wp[(size_t)(ks + 1) * 64];
+      const h8 b0 = *reinterpret_cast<const h8a*>(x0 + 16 * ks);
+      const h8 b1 = *reinterpret_cast<const h8a*>(x1 + 16 * ks);
+      acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf, b0, acc[0], 0, 0, 0);
+      acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf, b1, acc[1], 0, 0, 0);
+    }
+    epi(nt, 0, acc[0]);
+    epi(nt, 1, acc[1]);
+  }
+}
+
+// the f16 tile of the next product: Y [64, g.Npad], optional ReLU
+__device__ __forceinline__ void vn_stage(const char* __restrict__ img, const VadGemm& g, bool relu, const half_t* x, half_t* y, int ld,
+                                         int wave, int lane) {
+  const int r = lane & 31, h = lane >> 5;
+  vn_product(img, g, x, ld, wave, lane, [&](int nt, int i, const f16x& acc) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      h4 v;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float f = acc[4 * q + e];
+        if (relu) f = f < 0.f ? 0.f : f;
+        v[e] = (half_t)f;
+      }
+      *reinterpret_cast<h4a*>(y + (32 * i + r) * ld + 32 * nt + 8 * q + 4 * h) = v;
+    }
+  });
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(256) void vadnet_kernel(VadNetLaunch a) {
+  extern __shared__ __attribute__((aligned(16))) char vn_lds[];
+  __shared__ VnRowInfo info;
+  __shared__ float red[4][VN_ROWS][3];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int ld = a.ld;
+  half_t* buf0 = reinterpret_cast<half_t*>(vn_lds);
+  half_t* buf1 = buf0 + (size_t)VN_ROWS * ld;
+  const long long g0 = (long long)blockIdx.x * VN_ROWS;
+
+  // ---- every row's utterance: the last b with off[b] <= row (utterances of no frame share their offset with the next one and
+  // are stepped over, because the search looks for the LAST such b below B)
+  if (tid < VN_ROWS) {
+    const long long g = g0 + tid;
+    long long start = 0;
+    int T = 0;
+    if (g < a.total) {
+      int lo = 0, hi = a.B - 1;                          // off[0] = 0 <= g < off[B] = total
+      while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (a.off[mid] <= g) lo = mid; else hi = mid - 1;
+      }
+      start = a.off[lo];
+      T = (int)(a.off[lo + 1] - start);
+    }
+    info.start[tid] = start;
+    info.T[tid] = T;
+  }
+  __syncthreads();
+
+  // ---- the head: the first f16 tile in buf0, width a.head_w (a multiple of 16), zeros in its padding columns and in rows
+  // at or beyond the total
+  if (a.head == 0) {
+    // LFR + CMVN: column c = j * n_mels + m of row t is (x[clamp(t - left + j, 0, T - 1)][m] + shift[c]) * scale[c]     (R1)
+    const float* __restrict__ shift = reinterpret_cast<const float*>(a.img + a.shift_off);
+    const float* __restrict__ scale = reinterpret_cast<const float*>(a.img + a.scale_off);
+    const int left = (a.lfr_m - 1) >> 1;
+    for (int row = wave; row < VN_ROWS; row += 4) {
+      const int T = info.T[row];
+      const long long start = info.start[row], t = g0 + row - start;
+      for (int c = lane; c < a.head_w; c += 64) {
+        float v = 0.f;
+        if (T > 0 && c < a.in_dim) {
+          const int j = c / a.n_mels, m = c - j * a.n_mels;
+          long long src = t - left + j;
+          src = src < 0 ? 0 : (src > T - 1 ? T - 1 : src);
+          v = (a.x[(start + src) * a.n_mels + m] + shift[c]) * scale[c];
+        }
+        buf0[row * ld + c] = (half_t)v;
+      }
+    }
+  } else {
+    // the FSMN sum over p (fp32, row stride ldp): m[t] = p[t] + sum_k taps[k] * p[t - (lorder - 1 - k) * lstride]   (R4)
+    const float* __restrict__ taps = reinterpret_cast<const float*>(a.img + a.taps_off);
+    for (int row = wave; row < VN_ROWS; row += 4) {
+      const int T = info.T[row];
+      const long long g = g0 + row, t = g - info.start[row];
+      for (int c = lane; c < a.head_w; c += 64) {
+        float v = 0.f;
+        if (T > 0 && c < a.ldp) {
+          v = a.p_in[g * a.ldp + c];
+          for (int k = 0; k < a.lorder; ++k) {
+            const long long d = (long long)(a.lorder - 1 - k) * a.lstride;
+            if (d <= t) v += taps[k * a.ldp + c] * a.p_in[(g - d) * a.ldp + c];
+          }
+        }
+        buf0[row * ld + c] = (half_t)v;
+      }
+    }
+  }
+  __syncthreads();
+
+  // ---- the products that stay in LDS
+  half_t* cur = buf0;
+  half_t* nxt = buf1;
+  for (int s = 0; s < a.n_mid; ++s) {
+    vn_stage(a.img, a.mid[s], a.mid_relu[s] != 0, cur, nxt, ld, wave, lane);
+    __syncthreads();
+    half_t* t = cur; cur = nxt; nxt = t;
+  }
+
+  const int r = lane & 31, h = lane >> 5;
+  if (a.tail == 0) {
+    // ---- linear_l: p rows to memory, fp32, all ldp columns (the padding ones are exact zeros)
+    vn_product(a.img, a.last, cur, ld, wave, lane, [&](int nt, int i, const f16x& acc) {
+      const long long g = g0 + 32 * i + r;
+      if (g < a.total) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          *reinterpret_cast<float4*>(a.p_out + g * a.ldp + 32 * nt + 8 * q + 4 * h) =
+              make_float4(acc[4 * q + 0], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]);
+      }
+    });
+    return;
+  }
+
+  // ---- out_linear2, the softmax and the level
+  const float* __restrict__ silf = reinterpret_cast<const float*>(a.img + a.sil_off);
+  float mx[2] = {-INFINITY, -INFINITY}, sum[2] = {0.f, 0.f}, sil[2] = {0.f, 0.f};
+  bool poisoned[2] = {false, false};
+  vn_product(a.img, a.last, cur, ld, wave, lane, [&](int nt, int i, const f16x& acc) {
+    const long long g = g0 + 32 * i + r;
+    float tm = -INFINITY;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int n = 32 * nt + 8 * q + 4 * h;
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (n + e < a.out_dim) {
+          const float v = acc[4 * q + e];
+          if (v != v) poisoned[i] = true;
+          tm = fmaxf(tm, v);
+          if (a.logits && g < a.total) a.logits[g * a.out_dim + n + e] = v;
+        }
+    }
+    if (tm == -INFINITY) return;                         // no valid column in this block for this lane half, or all -inf
+    const float nm = fmaxf(mx[i], tm);
+    const float sc = mx[i] == -INFINITY ? 0.f : expf(mx[i] - nm);
+    float s1 = sum[i] * sc, s2 = sil[i] * sc;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int n = 32 * nt + 8 * q + 4 * h;
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (n + e < a.out_dim) {
+          const float ex = expf(acc[4 * q + e] - nm);
+          s1 += ex;
+          s2 += ex * silf[n + e];
+        }
+    }
+    mx[i] = nm; sum[i] = s1; sil[i] = s2;
+  });
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    // the other lane half holds the other channels of the same row
+    const float om = __shfl_xor(mx[i], 32, 64), os = __shfl_xor(sum[i], 32, 64), oq = __shfl_xor(sil[i], 32, 64);
+    const bool op = __shfl_xor((int)poisoned[i], 32, 64) != 0;
+    const float nm = fmaxf(mx[i], om);
+    const float ca = mx[i] == -INFINITY ? 0.f : expf(mx[i] - nm), cb = om == -INFINITY ? 0.f : expf(om - nm);
+    float s1 = sum[i] * ca + os * cb, s2 = sil[i] * ca + oq * cb;
+    if (poisoned[i] || op) s1 = NAN;
+    if (h == 0) { red[wave][32 * i + r][0] = nm; red[wave][32 * i + r][1] = s1; red[wave][32 * i + r][2] = s2; }
+  }
+  __syncthreads();
+  if (tid < VN_ROWS) {
+    const long long g = g0 + tid;
+    if (g < a.total && a.levels) {
+      float nm = -INFINITY;
+#pragma unroll
+      for (int w = 0; w < 4; ++w) nm = fmaxf(nm, red[w][tid][0]);
+      float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+      for (int w = 0; w < 4; ++w) {
+        const float m = red[w][tid][0];
+        const float c = m == -INFINITY ? 0.f : expf(m - nm);
+        s1 += red[w][tid][1] * c;
+        s2 += red[w][tid][2] * c;
+      }
+      const float v = (1.f - 2.f * (s2 / s1)) * 16384.f;
+      a.levels[g] = (v >= -16384.f && v <= 16384.f) ? (int)rintf(v) : -16384;
+    }
+  }
+}
+
+size_t vadnet_lds_bytes(int ld) { return (size_t)2 * VN_ROWS * ld * sizeof(half_t); }
+
+void launch_vadnet(hipStream_t s, const VadNetLaunch& a) {
+  if (a.total <= 0 || a.B <= 0) return;
+  PF_CHECK(a.img && a.off && a.ld >= 24 && a.ld % 8 == 0 && a.head_w % 16 == 0 && a.head_w <= a.ld - 8 && a.n_mid >= 0 && a.n_mid <= 2 &&
+               a.ldp % 32 == 0 && (a.head == 0 ? (a.x != nullptr && a.n_mels >= 1) : (a.p_in != nullptr)) &&
+               (a.tail == 0 ? a.p_out != nullptr : (a.levels != nullptr || a.logits != nullptr)),
+           PF_ERR_INVALID_ARG, "vadnet: missing operand");
+  const size_t lds = vadnet_lds_bytes(a.ld);
+  PF_CHECK(lds <= 150 * 1024, PF_ERR_UNSUPPORTED, "vadnet: the model's widest operand does not fit the LDS");
+  static DeviceOnce once;
+  once.run([] { set_max_lds((const void*)vadnet_kernel, 150 * 1024); });
+  hipLaunchKernelGGL(vadnet_kernel, dim3((unsigned)((a.total + VN_ROWS - 1) / VN_ROWS)), dim3(256), lds, s, a);
+  PF_HIP(hipGetLastError());
+}
+
+}  // namespace pf

@@ -1,6 +1,7 @@
 // kernels.h — launchers of the gfx950 kernels (implemented in k_*.hip)
 #pragma once
 #include "common.h"
+#include "vadnet.h"
 
 namespace pf {
 
@@ -489,5 +490,23 @@ struct VadParams { int32_t floor_pct, margin_q, abs_level, window, on_count, off
                    split_search, n_mels; };
 void launch_vad_segments(hipStream_t s, const int32_t* levels, const int64_t* off, const int32_t* T, int B, const VadParams& p,
                          int32_t* seg, int cap, int32_t* n);
+
+// ---------------------------------------------------------------- the FSMN-VAD model score (k_vadnet.hip) ------
+// The second form of step 1 of the voice-activity segmentation; the definition in numpy is tests/vadnet_ref.py.  One launch
+// of the 1 + n_layers that make a forward (the plan is at the head of k_vadnet.hip; Engine::run_vadnet fills these in).
+// img: the model's device image (vadnet.h); every *_off is a byte offset into it.
+struct VadNetLaunch {
+  const char* img; const int64_t* off; int B; int64_t total;    // rows: `total` frames, utterance b at rows [off[b], off[b + 1])
+  int ld;                                                       // LDS row stride in halves (VadModel::lds_ld)
+  int head, head_w;                                             // head 0: LFR + CMVN over x; 1: the FSMN taps over p_in.  head_w: the tile's width
+  const float* x; int n_mels, lfr_m, in_dim; int64_t shift_off, scale_off;
+  const float* p_in; int64_t taps_off; int lorder, lstride, ldp;
+  int n_mid; VadGemm mid[2]; int mid_relu[2];                   // the products whose result stays in LDS as f16
+  int tail; VadGemm last;                                       // tail 0: `last` = linear_l -> p_out fp32 [total, ldp]; 1: out_linear2 -> softmax
+  float* p_out;
+  int64_t sil_off; int out_dim; float* logits; int32_t* levels; // logits [total, out_dim] / levels [total]: either may be null
+};
+size_t vadnet_lds_bytes(int ld);
+void launch_vadnet(hipStream_t s, const VadNetLaunch& a);
 
 }  // namespace pf

@@ -511,6 +511,9 @@ std::shared_ptr<Engine> Recognizer::make_engine() {
   std::shared_ptr<void> img = image_;                // the engine points into the image: it must outlive the engine
   std::shared_ptr<Engine> e(new Engine(ec_), [img](Engine* p) { delete p; });
   if (decode_flags_) { e->set_topk(topk_k_); e->set_ctc_beam(beam_w_, std::min<int>(beam_n_, beam_w_)); e->set_decode(decode_flags_); }
+  std::shared_ptr<const VadModel> vm;
+  { std::lock_guard<std::mutex> lk(vad_mu_); vm = vad_model_; }
+  if (vm) e->set_vad_model(vm);
   return e;
 }
 
@@ -647,6 +650,28 @@ void Recognizer::SetVad(const pf_vad_config* cfg, int batch_max, int64_t frame_b
   vad_sep_ = sep ? sep : "";
 }
 
+void Recognizer::SetVadModel(const std::string& pfw_path) {
+  if (disposed_) throw Error(PF_ERR_DISPOSED, "OfflineRecognizer");
+  std::shared_ptr<const VadModel> vm;
+  if (!pfw_path.empty()) {
+    vm = vad_model_load(pfw_path);                                           // throws before anything changes
+    if ((int64_t)conf_.n_mels * vm->lfr_m != vm->input_dim)
+      throw Error(PF_ERR_INVALID_ARG, "SetVadModel: n_mels * lfr_m does not equal the model's input width");
+    if (conf_.snip_edges) throw Error(PF_ERR_UNSUPPORTED, "SetVadModel: snip_edges = true is not supported");
+  }
+  std::vector<std::shared_ptr<Engine>> es;
+  {
+    std::lock_guard<std::mutex> lk(mu_);
+    if (disposed_ || engines_.empty()) throw Error(PF_ERR_DISPOSED, "OfflineRecognizer");
+    es = engines_;
+  }
+  { std::lock_guard<std::mutex> lk(vad_mu_); vad_model_ = vm; }              // engines made from here on attach it themselves
+  for (auto& e : es) {                                                       // (ForwardLong also applies it under its lease, which
+    std::lock_guard<std::mutex> lk(e->mutex());                              //  covers an engine that joined the pool meanwhile)
+    e->set_vad_model(vm);
+  }
+}
+
 // GetResults with SetVad: segment every stream where its audio lies, plan batches over the pooled pieces, run Forward on each
 // batch through PIECE streams (plain device-form streams whose dev_audio points into the parent's buffer, so a piece's ids,
 // text and times are what a plain stream holding that sample range gives in that batch position), stitch per stream.
@@ -678,6 +703,9 @@ void Recognizer::ForwardLong(const std::vector<Stream*>& streams, std::vector<Re
     std::vector<int32_t> seg((size_t)B * cap * 2), nseg((size_t)B);
     {
       Lease lease = acquire();
+      std::shared_ptr<const VadModel> vm;
+      { std::lock_guard<std::mutex> lk(vad_mu_); vm = vad_model_; }
+      if (lease->vad_model() != vm) lease->set_vad_model(vm);
       lease->vad_segment_device(ptrs.data(), ns.data(), B, &cfg, seg.data(), cap, nseg.data());
     }
     // 2. the plan over the pooled pieces

@@ -220,6 +220,9 @@ class Recognizer : public std::enable_shared_from_this<Recognizer> {
   // length (host_long_plan), forwards each batch over pointers into the streams' audio and stitches one result per stream.
   // cfg == null: off.  PF_ERR_UNSUPPORTED beside SetNBest / SetCtcBeam / SetAlign (either order).
   void SetVad(const pf_vad_config* cfg, int batch_max, int64_t frame_budget, const char* sep);
+  // The FSMN-VAD model score for SetVad's segmentation (paraformer_hip.h "Voice-activity segmentation, model score"): a `.pfw`
+  // of kind "fsmnvad", loaded once and attached to every engine of the pool, present and future; "" clears.  Inert until SetVad.
+  void SetVadModel(const std::string& pfw_path);
   bool disposed() const { return disposed_.load(); }
   // engine 0 (nullptr once disposed): what pf_recognizer_engine hands out; callers lock engine->mutex() themselves
   std::shared_ptr<Engine> engine() { std::lock_guard<std::mutex> lk(mu_); return engines_.empty() ? nullptr : engines_[0]; }
@@ -260,7 +263,8 @@ class Recognizer : public std::enable_shared_from_this<Recognizer> {
  private:
   void Forward(const std::vector<Stream*>& streams);          // :118-198
   void ForwardLong(const std::vector<Stream*>& streams, std::vector<ResultEntity>& out);   // GetResults with SetVad
-  std::mutex vad_mu_;                                         // guards the four below
+  std::mutex vad_mu_;                                         // guards the five below
+  std::shared_ptr<const VadModel> vad_model_;
   bool vad_on_ = false; pf_vad_config vad_cfg_{}; int vad_batch_max_ = 32; int64_t vad_budget_ = 96000; std::string vad_sep_;
   std::shared_ptr<Engine> make_engine();
   std::mutex mu_;                                             // guards engines_, busy_, the audio cache

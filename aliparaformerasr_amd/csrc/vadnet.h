@@ -1,0 +1,53 @@
+// vadnet.h — the FSMN-VAD model score of the voice-activity segmentation (paraformer_hip.h "Voice-activity segmentation, model
+// score"; the definition is tests/vadnet_ref.py): the loader of a `.pfw` of kind "fsmnvad", the float64 host twins and the
+// builder of the weight image k_vadnet.hip reads.  Host-only: no HIP header beyond common.h.
+#pragma once
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "common.h"
+
+namespace pf {
+
+// limits of the loader (PF_ERR_UNSUPPORTED beyond them): two [64, widest + 8] f16 tiles must fit the 160 KB of LDS
+constexpr int kVadMaxWidth = 512, kVadMaxProj = 256, kVadMaxLayers = 8, kVadMaxReach = 256, kVadMaxLfr = 16;
+
+// one matrix product of the device image: W [N, K] fp32 as f16 fragments of the 32x32x16 MFMA, rows padded to Npad (a
+// multiple of 32) and columns to Kpad (a multiple of 16) with zeros: halves [Npad / 32][Kpad / 16][64 lanes][8], lane
+// (r = lane & 31, h = lane >> 5) holding W[32 nt + r][16 ks + 8 h + j]; bias fp32 [Npad] (zeros where the product has none)
+struct VadGemm { int64_t w_off = 0, b_off = 0; int N = 0, K = 0, Npad = 0, Kpad = 0; };
+
+struct VadModel {
+  int input_dim = 0, affine_dim = 0, linear_dim = 0, proj_dim = 0, output_dim = 0, n_layers = 0, lorder = 0, lstride = 0, lfr_m = 0;
+  std::vector<int32_t> sil_ids;
+  std::vector<float> shift, scale, in1_w, in1_b, in2_w, in2_b, out1_w, out1_b, out2_w, out2_b;
+  struct Layer { std::vector<float> lin_w, taps, aff_w, aff_b; };      // taps [lorder, proj]
+  std::vector<Layer> layers;
+  // the device image: what an engine uploads, byte for byte (offsets in bytes, each 256-aligned)
+  std::vector<char> image;
+  VadGemm g_in1, g_in2, g_out1, g_out2;
+  std::vector<VadGemm> g_lin, g_aff;
+  std::vector<int64_t> taps_off;        // fp32 [lorder, ldp] per layer
+  int64_t shift_off = 0, scale_off = 0, sil_off = 0;   // fp32 [input_dim] each; fp32 [g_out2.Npad]: 1 on a silence id, else 0
+  int ldp = 0;                          // row stride of the p rows: proj_dim padded to 32
+  int lds_ld = 0;                       // row stride (halves) of the kernel's LDS tiles: the widest operand + 8
+  const std::vector<float>* tensor(const std::string& name) const;     // by its container name; nullptr: no such tensor
+};
+
+// PF_ERR_INVALID_ARG: not a PFW1 container of kind "fsmnvad", truncated, an extent outside the file, a missing tensor, a
+// wrong shape, a non-finite value, a silence id outside [0, output_dim).  PF_ERR_UNSUPPORTED: rorder > 0, lfr_n != 1, a
+// dimension beyond the limits above.
+std::shared_ptr<const VadModel> vad_model_from_memory(const void* data, int64_t nbytes);
+std::shared_ptr<const VadModel> vad_model_load(const std::string& path);
+// the CPU twins for ONE utterance, float64 from the fp32 weights.  rows [T, n_mels]; logits [T, output_dim]
+void host_vad_model_logits(const VadModel& m, const float* rows, int64_t T, int n_mels, double* logits);
+void host_vad_model_levels(const VadModel& m, const float* rows, int64_t T, int n_mels, int32_t* levels);
+pf_vad_config vad_model_default();      // vad_default() with floor_pct = -1, abs_level = 9830
+
+}  // namespace pf
+
+// the C handle: a reference to an immutable model (an engine that attaches it takes a reference of its own)
+struct pf_vad_model {
+  std::shared_ptr<const pf::VadModel> p;
+};

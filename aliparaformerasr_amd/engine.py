@@ -358,6 +358,85 @@ def host_vad_segments(levels, n_mels=80, cfg=None, lfr_n=6, cap=None) -> np.ndar
     return seg[: n.value].copy()
 
 
+def vad_model_config(**kw) -> "N.PfVadConfig":
+    """pf_vad_config with the defaults that go with the model score (pf_vad_model_config: floor_pct = -1, abs_level = 9830,
+    stated and not tuned), fields overridden by keyword."""
+    c = N.PfVadConfig()
+    N.check(N.load().pf_vad_model_config(C.byref(c)))
+    for k, v in kw.items():
+        assert hasattr(c, k) and k not in ("struct_size", "reserved"), k
+        setattr(c, k, int(v))
+    return c
+
+
+VAD_MODEL_DIMS = ("input_dim", "affine_dim", "linear_dim", "proj_dim", "output_dim", "n_layers", "lorder", "lstride", "lfr_m")
+
+
+class VadModel:
+    """An FSMN-VAD model: a `.pfw` of kind "fsmnvad" loaded and validated on the host (pf_vad_model_load /
+    pf_vad_model_from_memory; see "Voice-activity segmentation, model score" in the header).  Release with close() (an engine
+    that attached it keeps its own reference)."""
+
+    def __init__(self, handle):
+        self._lib = N.load()
+        self._h = handle
+        d, ns, ib = np.zeros(9, np.int32), C.c_int32(), C.c_int64()
+        N.check(self._lib.pf_vad_model_info(self._h, _i32p(d), ns, ib))
+        self.dims = dict(zip(VAD_MODEL_DIMS, d.tolist()))
+        self.image_bytes = ib.value
+        sil, n = np.zeros(max(ns.value, 1), np.int32), C.c_int32()
+        N.check(self._lib.pf_vad_model_sil_ids(self._h, _i32p(sil), ns.value, n))
+        self.sil_ids = sil[: n.value].tolist()
+
+    def tensor(self, name: str) -> np.ndarray:
+        """A tensor as loaded, flat float32 (pf_vad_model_tensor)."""
+        n = C.c_int64()
+        N.check(self._lib.pf_vad_model_tensor(self._h, name.encode("utf-8"), None, 0, n))
+        out = np.zeros(max(n.value, 1), np.float32)
+        N.check(self._lib.pf_vad_model_tensor(self._h, name.encode("utf-8"), _fp(out), n.value, n))
+        return out[: n.value]
+
+    def close(self):
+        if self._h is not None:
+            self._lib.pf_vad_model_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def load_vad_model(source) -> VadModel:
+    """A `.pfw` of kind "fsmnvad" from a path or from bytes -> VadModel."""
+    h = C.c_void_p()
+    if isinstance(source, (bytes, bytearray, memoryview)):
+        buf = bytes(source)
+        N.check(N.load().pf_vad_model_from_memory(C.cast(C.c_char_p(buf), C.c_void_p), len(buf), C.byref(h)))
+    else:
+        N.check(N.load().pf_vad_model_load(str(source).encode("utf-8"), C.byref(h)))
+    return VadModel(h)
+
+
+def host_vad_model_logits(model: VadModel, rows) -> np.ndarray:
+    """The network for ONE utterance in host code, float64 (pf_host_vad_model_logits): rows [T, n_mels] -> [T, output_dim]."""
+    x = _f32(rows)
+    T, m = x.shape
+    out = np.zeros((T, model.dims["output_dim"]), np.float64)
+    N.check(N.load().pf_host_vad_model_logits(model._h, _fp(x), T, m, _dp(out)))
+    return out
+
+
+def host_vad_model_levels(model: VadModel, rows) -> np.ndarray:
+    """The model score of ONE utterance in host code (pf_host_vad_model_levels): rows [T, n_mels] -> levels [T] int32."""
+    x = _f32(rows)
+    T, m = x.shape
+    out = np.zeros(T, np.int32)
+    N.check(N.load().pf_host_vad_model_levels(model._h, _fp(x), T, m, _i32p(out)))
+    return out
+
+
 def host_long_plan(lens, batch_max=0, frame_budget=0):
     """The batch plan of long-audio recognition (pf_host_long_plan): ([(batch, row)] per segment, number of batches)."""
     ln = np.ascontiguousarray(lens, dtype=np.int32).reshape(-1)
@@ -562,6 +641,7 @@ class Engine:
         self._beam_n = 16
         self._hot = False
         self._lm = None
+        self._vad_model = None
         self._search_w = 0
 
     def close(self):
@@ -1000,6 +1080,39 @@ class Engine:
         out = np.zeros(T, np.int32)
         N.check(self._lib.pf_op_vad_levels(self._h, _fp(x), T, m, _i32p(out)))
         return out
+
+    def set_vad_model(self, model):
+        """Attaches a VadModel (pf_engine_set_vad_model): vad_segment and everything built on it then score frames with the
+        network instead of the energy level; None detaches."""
+        N.check(self._lib.pf_engine_set_vad_model(self._h, None if model is None else model._h))
+        self._vad_model = model
+
+    def _op_vad_model(self, rows_list, want_logits):
+        arrs = [_f32(r) for r in rows_list]
+        B = len(arrs)
+        m = arrs[0].shape[1] if B else 1
+        assert all(a.ndim == 2 and a.shape[1] == m for a in arrs)
+        T = np.ascontiguousarray([a.shape[0] for a in arrs] + [0] * (B == 0), dtype=np.int32)
+        total = int(T.sum())
+        x = np.ascontiguousarray(np.concatenate(arrs, axis=0) if B else np.zeros((0, m), np.float32))
+        O = self._vad_model.dims["output_dim"] if self._vad_model is not None else 1     # (without a model the call is refused)
+        if want_logits:
+            out = np.zeros((max(total, 1), O), np.float32)
+            N.check(self._lib.pf_op_vad_model_logits(self._h, _fp(x), _i32p(T), B, m, _fp(out)))
+        else:
+            out = np.zeros(max(total, 1), np.int32)
+            N.check(self._lib.pf_op_vad_model_levels(self._h, _fp(x), _i32p(T), B, m, _i32p(out)))
+        off = np.concatenate([[0], np.cumsum(T[:B])]).astype(np.int64)
+        return [out[off[b]: off[b + 1]].copy() for b in range(B)]
+
+    def op_vad_model_logits(self, rows_list) -> list:
+        """The attached model's launches on caller rows (pf_op_vad_model_logits): ONE call over all the utterances of rows_list
+        ([T_b, n_mels] each); returns each utterance's logits [T_b, output_dim] float32."""
+        return self._op_vad_model(rows_list, True)
+
+    def op_vad_model_levels(self, rows_list) -> list:
+        """As op_vad_model_logits, the levels [T_b] int32 (pf_op_vad_model_levels)."""
+        return self._op_vad_model(rows_list, False)
 
     def op_vad_segments(self, levels_list, n_mels=80, cfg=None, cap=None, ld=None):
         """The detector's segment kernel on caller levels (pf_op_vad_segments): ONE launch over all the utterances of

@@ -1,7 +1,7 @@
 """Command-line harness mirroring AliParaformerAsr.Examples (`-type offline` and `-type online`).
 
     python -m aliparaformerasr_amd.examples -type offline -method batch -base <dir> -model <name> \
-        [-accuracy int8] [-threads 2] [-decode ctc|frames] [-intake host|device] [-nbest N [-topk K] [-beam W | -search W] [-hotboost S] [-lm FILE [-lmweight A] [-lmbonus B] [-lmeos]]] [-align FILE|beam] [-vad [key=value,...]] -files a.wav b.wav
+        [-accuracy int8] [-threads 2] [-decode ctc|frames] [-intake host|device] [-nbest N [-topk K] [-beam W | -search W] [-hotboost S] [-lm FILE [-lmweight A] [-lmbonus B] [-lmeos]]] [-align FILE|beam] [-vad [key=value,...] [-vadmodel FILE]] -files a.wav b.wav
     python -m aliparaformerasr_amd.examples -type online -method one -base <dir> -model <name> -files a.wav
 
 Mirrors (file:line in /root/reference/AliParaformerAsr.Examples):
@@ -46,6 +46,9 @@ the device, the segments are recognised in batches of similar length and stitche
 line goes one `[begin-end ms] text` line per segment.  Keys: the pf_vad_config fields (floor_pct, margin_q, abs_level, window,
 on_count, off_count, pad_begin, pad_end, min_speech, max_len, split_search), batch_max, frame_budget and sep.  The default
 thresholds are unvalidated on real speech.  Not beside -nbest / -align.
+`-vadmodel FILE` (with `-vad`; OfflineRecognizer.SetVadModel) scores the frames with an FSMN-VAD network instead of the
+log-mel energy: FILE is a `.pfw` of kind fsmnvad (`python -m aliparaformerasr_amd.convert vad.onnx out.pfw --kind fsmnvad
+--mvn vad.mvn`); the model's default thresholds (floor_pct=-1, abs_level=9830; unvalidated too) apply unless keys are given.
 `-align beam` (with `-nbest N -beam W`) aligns the beam search's labelings instead: under each `nbest[i]` line goes
 `align[i] loglik:<...> pairs:[begin,end],...`."""
 from __future__ import annotations
@@ -218,7 +221,7 @@ def read_align_file(path: str) -> list:
 
 def offline_recognizer(method="one", model="paraformer-seaco-large-zh-timestamp-onnx-offline", accuracy="int8",
                        threads=2, files=None, base=None, out=sys.stdout, decode="frames", intake="host", nbest=0, topk=4,
-                       beam=0, align=None, hotboost=0.0, vad=None, lm=None, lmweight=0.5, lmbonus=0.0, lmeos=False, search=0):
+                       beam=0, align=None, hotboost=0.0, vad=None, lm=None, lmweight=0.5, lmbonus=0.0, lmeos=False, search=0, vadmodel=None):
     from .offline_recognizer import OfflineRecognizer
     base = base or os.getcwd()
     sel = select_model_files(base, model, accuracy)
@@ -244,7 +247,12 @@ def offline_recognizer(method="one", model="paraformer-seaco-large-zh-timestamp-
             if lm:
                 rec.SetNBestLm(lm, lmweight, lmbonus, 1 if lmeos else 0)
     if vad is not None:
-        rec.SetVad(vad["cfg"] or True, vad["batch_max"], vad["frame_budget"], vad["sep"])
+        vcfg = vad["cfg"] or True
+        if vadmodel:                                       # the model's default thresholds unless keys are given
+            from .engine import vad_model_config
+            rec.SetVadModel(vadmodel)
+            vcfg = vad_model_config(**vad["cfg"])
+        rec.SetVad(vcfg, vad["batch_max"], vad["frame_budget"], vad["sep"])
     targets = None
     if align:
         rec.SetAlign(True)
@@ -486,6 +494,11 @@ def parse_args(argv, env=None):
                 i += 1
                 text = argv[i]
             cfg["vad"] = parse_vad_option(text)
+        elif a == "-vadmodel":
+            i += 1
+            if i >= len(argv) or argv[i].startswith("-"):
+                raise ValueError("-vadmodel takes a .pfw file of kind fsmnvad")
+            cfg["vadmodel"] = argv[i]
         elif a == "-threads":
             try:
                 i += 1
@@ -527,6 +540,8 @@ def parse_args(argv, env=None):
         raise ValueError("-vad is an offline option")
     if "vad" in cfg and ("nbest" in cfg or "align" in cfg):
         raise ValueError("-vad does not go with -nbest or -align")
+    if "vadmodel" in cfg and "vad" not in cfg:
+        raise ValueError("-vadmodel goes with -vad")
     if cfg.get("align") == "beam" and "beam" not in cfg:
         raise ValueError("-align beam needs -nbest N -beam W")
     return cfg
@@ -548,7 +563,8 @@ def main(argv=None):
                            cfg["modelBasePath"] or None, decode=cfg.get("decode", "frames"), intake=cfg.get("intake", "host"),
                            nbest=cfg.get("nbest", 0), topk=cfg.get("topk", 4), beam=cfg.get("beam", 0), align=cfg.get("align"),
                            hotboost=cfg.get("hotboost", 0.0), vad=cfg.get("vad"), lm=cfg.get("lm"), lmweight=cfg.get("lmweight", 0.5),
-                           lmbonus=cfg.get("lmbonus", 0.0), lmeos=cfg.get("lmeos", False), search=cfg.get("search", 0))
+                           lmbonus=cfg.get("lmbonus", 0.0), lmeos=cfg.get("lmeos", False), search=cfg.get("search", 0),
+                           vadmodel=cfg.get("vadmodel"))
     else:
         print("the recognizer type must be online or offline")
         return 2

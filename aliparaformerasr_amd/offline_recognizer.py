@@ -461,6 +461,13 @@ class OfflineRecognizer:
         c = cfg if isinstance(cfg, N.PfVadConfig) else vad_config(**({} if cfg is True else cfg))
         _ck(self._lib.pf_recognizer_set_vad(self._h, C.byref(c), int(batch_max), int(frame_budget), sep.encode("utf-8")))
 
+    def SetVadModel(self, pfwPath) -> None:
+        """The FSMN-VAD model score for SetVad's segmentation: a `.pfw` of kind "fsmnvad" (python -m aliparaformerasr_amd.convert
+        ... --kind fsmnvad), loaded once and attached to every engine of the pool, present and future; None clears.  Inert
+        until SetVad, and may be set before or after it; pass engine.vad_model_config() to SetVad for the thresholds that go
+        with it (stated, not tuned: nobody has validated them on real speech)."""
+        _ck(self._lib.pf_recognizer_set_vad_model(self._h, None if pfwPath is None else str(pfwPath).encode("utf-8")))
+
     def GetResult(self, stream: OfflineStream) -> OfflineRecognizerResultEntity:
         return self.GetResults([stream])[0]
 

@@ -25,6 +25,11 @@ as they are, ``<linear>.weight`` beside them is their de-quantised float32 image
 
 Tensor inventory follows SURVEY.md §8a ("Tensor inventory for the
 synthetic-weight generator").
+
+A container of kind "fsmnvad" holds a voice-activity model instead of a
+recogniser (fsmn_vad_config / vad_tensor_shapes / synth_vad_weights below;
+the definition is tests/vadnet_ref.py): it is loaded with
+engine.load_vad_model, never handed to an Engine as its weights.
 """
 from __future__ import annotations
 
@@ -198,6 +203,61 @@ def synth_weights(cfg: dict, seed: int = 42) -> dict:
         w.update(_linear(rng, D, Fs, bias=False, prefix=p + ".ffn.w2"))
         w.update(_ln(rng, D, "seaco.decoder.after_norm"))
         w.update(_linear(rng, V, D, prefix="seaco.output"))
+    return w
+
+
+FSMN_VAD_CONFIG = dict(
+    kind="fsmnvad", n_mels=80, lfr_m=5, lfr_n=1, input_dim=400, affine_dim=140, linear_dim=250, proj_dim=128, output_dim=248,
+    n_layers=4, lorder=20, lstride=1, rorder=0, sil_ids=(0,),
+)
+
+
+def fsmn_vad_config(**kw) -> dict:
+    """The config of a `.pfw` of kind "fsmnvad" (the FSMN-VAD model score of the voice-activity segmentation; the definition is
+    tests/vadnet_ref.py).  The defaults are the dimensions of FunASR's released model; input_dim follows n_mels * lfr_m unless
+    given."""
+    cfg = dict(FSMN_VAD_CONFIG)
+    for k, v in kw.items():
+        if k not in cfg:
+            raise KeyError(k)
+        cfg[k] = v
+    if "input_dim" not in kw:
+        cfg["input_dim"] = int(cfg["n_mels"]) * int(cfg["lfr_m"])
+    cfg["sil_ids"] = [int(i) for i in cfg["sil_ids"]]
+    return cfg
+
+
+def vad_tensor_shapes(cfg: dict) -> dict:
+    """name -> shape of every tensor of an "fsmnvad" container.  Linear weights are [out, in]; the FSMN taps are [lorder, proj]
+    (taps[k] weighs the frame (lorder - 1 - k) * lstride back)."""
+    I, A, L, P, O = (int(cfg[k]) for k in ("input_dim", "affine_dim", "linear_dim", "proj_dim", "output_dim"))
+    sh = {"cmvn.shift": (I,), "cmvn.scale": (I,), "in1.weight": (A, I), "in1.bias": (A,), "in2.weight": (L, A), "in2.bias": (L,)}
+    for l in range(int(cfg["n_layers"])):
+        sh["fsmn.%d.linear.weight" % l] = (P, L)
+        sh["fsmn.%d.taps" % l] = (int(cfg["lorder"]), P)
+        sh["fsmn.%d.affine.weight" % l] = (L, P)
+        sh["fsmn.%d.affine.bias" % l] = (L,)
+    sh.update({"out1.weight": (A, L), "out1.bias": (A,), "out2.weight": (O, A), "out2.bias": (O,)})
+    return sh
+
+
+def synth_vad_weights(cfg: dict, seed: int = 42) -> dict:
+    """Seeded synthetic FSMN-VAD weights: Linear N(0, 1 / sqrt(fan_in)), biases N(0, 0.1), taps N(0, 0.1), a CMVN that
+    brings fbank-like rows (about N(-4, 3)) near N(0, 1)."""
+    rng = np.random.default_rng(seed)
+    w = {}
+    for name, shape in vad_tensor_shapes(cfg).items():
+        if name == "cmvn.shift":
+            a = 4.0 + 0.5 * rng.standard_normal(shape)
+        elif name == "cmvn.scale":
+            a = rng.uniform(0.25, 0.4, shape)
+        elif name.endswith(".taps"):
+            a = 0.1 * rng.standard_normal(shape)
+        elif name.endswith(".bias"):
+            a = 0.1 * rng.standard_normal(shape)
+        else:
+            a = rng.standard_normal(shape) / np.sqrt(shape[1])
+        w[name] = a.astype(np.float32)
     return w
 
 

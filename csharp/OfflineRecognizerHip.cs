@@ -394,6 +394,18 @@ namespace AliParaformerAsr.Hip
             ParaformerHip.Check(ParaformerHip.pf_recognizer_set_vad(_r, cfg == null ? null : new[] { cfg.Value }, batchMax, frameBudget, sep));
         }
 
+        /// <summary>Not in the reference: the FSMN-VAD model score for SetVad's segmentation: a .pfw of kind "fsmnvad", loaded once and
+        /// attached to every engine of the pool, present and future; null clears.  Inert until SetVad, and may be set before or after
+        /// it; pass DefaultVadModel() to SetVad for the thresholds that go with it (stated, not tuned).</summary>
+        public void SetVadModel(string? pfwPath) => ParaformerHip.Check(ParaformerHip.pf_recognizer_set_vad_model(_r, pfwPath));
+
+        /// <summary>The stated defaults that go with the model score (pf_vad_model_config: floor_pct = -1, abs_level = 9830).</summary>
+        public static PfVadConfig DefaultVadModel()
+        {
+            ParaformerHip.Check(ParaformerHip.pf_vad_model_config(out PfVadConfig c));
+            return c;
+        }
+
         /// <summary>The stated defaults of the detector (pf_vad_default).</summary>
         public static PfVadConfig DefaultVad()
         {

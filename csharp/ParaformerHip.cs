@@ -259,6 +259,17 @@ namespace AliParaformerAsr.Native
         [DllImport(Lib)] internal static extern int pf_stream_alternative_timestamps(IntPtr s, int i, out IntPtr beginEnd, out int n, out double loglik);
         // long-audio recognition: voice-activity segmentation on the device, batches of similar length, one result per stream
         [DllImport(Lib)] internal static extern int pf_vad_default(out PfVadConfig cfg);
+        // the FSMN-VAD model score (a .pfw of kind "fsmnvad"): the loader, what it read, the defaults that go with it, the attach calls
+        [DllImport(Lib)] internal static extern int pf_vad_model_load([MarshalAs(UnmanagedType.LPUTF8Str)] string path, out IntPtr m);
+        [DllImport(Lib)] internal static extern int pf_vad_model_from_memory(byte[] data, long nbytes, out IntPtr m);
+        [DllImport(Lib)] internal static extern int pf_vad_model_info(IntPtr m, [Out] int[]? dims, out int nSil, out long imageBytes);
+        [DllImport(Lib)] internal static extern int pf_vad_model_sil_ids(IntPtr m, [Out] int[]? sil, int cap, out int n);
+        [DllImport(Lib)] internal static extern int pf_vad_model_tensor(IntPtr m, [MarshalAs(UnmanagedType.LPUTF8Str)] string name, [Out] float[]? data,
+                                                                       long cap, out long n);
+        [DllImport(Lib)] internal static extern int pf_vad_model_config(out PfVadConfig cfg);
+        [DllImport(Lib)] internal static extern void pf_vad_model_free(IntPtr m);
+        [DllImport(Lib)] internal static extern int pf_engine_set_vad_model(IntPtr e, IntPtr m);
+        [DllImport(Lib)] internal static extern int pf_recognizer_set_vad_model(IntPtr r, [MarshalAs(UnmanagedType.LPUTF8Str)] string? pfwPath);
         [DllImport(Lib)] internal static extern int pf_vad_segment(IntPtr e, IntPtr[] samples, long[] nSamples, int B, ref PfVadConfig cfg,
                                                                   [Out] int[] seg, int cap, [Out] int[] nSeg);
         // cfg: an array of one element, or null (= off)

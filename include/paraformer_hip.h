@@ -550,7 +550,7 @@ int pf_recognize_pcm(pf_engine* e, const void* const* data, const int64_t* n_val
 /* ---- Voice-activity segmentation (additions to ABI 6; nothing is launched or allocated unless one of these is called) ----
    Long audio is cut into utterance-sized pieces on the device: a deterministic, all-integer detector over the 10 ms fbank
    rows the engine already computes (csrc/k_vad.hip).  The per-frame SCORE (step 1) is separate from the state machine
-   (steps 2-5), so a learned score can replace the energy level without touching the rest.  Every value below is an integer:
+   (steps 2-5): "Voice-activity segmentation, model score" below is its second, learned form.  Every value below is an integer:
    the device form, the host form (pf_host_vad_*) and the definition in numpy (tests/vad_ref.py) agree exactly.
    THE DEFAULT THRESHOLDS ARE STATED, NOT TUNED: nobody has measured them on real speech.
    Frames t = 0 .. T-1 of the whole stream, T = the fbank frame count of n samples; snip_edges = false only
@@ -607,6 +607,53 @@ int pf_host_vad_segments(const int32_t* levels, int32_t T, int32_t n_mels, int32
    frame_budget <= 0: 96000.  batch [n] / row [n]: where each segment goes; *n_batches (optional). */
 int pf_host_long_plan(const int32_t* len, int32_t n, int32_t batch_max, int64_t frame_budget, int32_t* batch, int32_t* row,
                       int32_t* n_batches);
+
+/* ---- Voice-activity segmentation, model score (additions to ABI 6; opt-in: with no model attached nothing of this is launched
+   or allocated and every result is bit for bit what it is without it) ----
+   A second form of step 1: the level of a frame comes from an FSMN-VAD network (the detector FunASR pairs with paraformer and
+   SenseVoice) instead of the log-mel energy.  Steps 2-6 are untouched.  The definition in numpy float64 is
+   tests/vadnet_ref.py; DESIGN.md 4.6k has the launch plan and the rounding points of the device form (csrc/k_vadnet.hip).
+   The model is a `.pfw` of kind "fsmnvad" (python -m aliparaformerasr_amd.convert ... --kind fsmnvad): the dimensions
+   input_dim, affine_dim, linear_dim, proj_dim, output_dim, n_layers, lorder, lstride, lfr_m, the silence ids sil_ids and the
+   tensors cmvn.shift / cmvn.scale [input], in1 / in2 / out1 / out2 .weight [out, in] and .bias, and per layer l
+   fsmn.l.linear.weight [proj, linear], fsmn.l.taps [lorder, proj], fsmn.l.affine.weight [linear, proj] and .bias.
+   For frame t of an utterance of T fbank rows x (fp32, n_mels wide; n_mels * lfr_m = input_dim):
+     u[t] = concat_j x[clamp(t - (lfr_m - 1) / 2 + j, 0, T - 1)], j = 0 .. lfr_m - 1, then (u + shift) * scale
+     a    = ReLU(in2(in1(u)))
+     per layer: p = linear(a) (no bias); m[t] = p[t] + sum_k taps[k] * p[t - (lorder - 1 - k) * lstride], rows before the
+            utterance's first frame being zeros; a = ReLU(affine(m))
+     z    = out2(out1(a));  s = the sum of softmax(z) over sil_ids
+     e[t] = rint((1 - 2 s) * 16384), half to even, an int32 in [-16384, 16384]; -16384 where that value is not finite
+   The device form multiplies f16 operands with fp32 accumulation (bias, ReLU, the FSMN sum, the softmax and the level in fp32),
+   so its levels are close to, not equal to, the host form's; the segments it returns ARE exactly steps 2-6 over its own levels.
+   The exact and fp32 math modes of an engine use the same f16 kernel for this network.
+   pf_vad_model_config: pf_vad_default with floor_pct = -1 and abs_level = 9830, which is FunASR's rule p_speech >= p_sil + 0.6.
+   THESE VALUES ARE AGAIN STATED, NOT TUNED: no threshold has been validated on real speech, and no real FSMN-VAD file has been
+   through the converter.
+   Loading validates everything.  PF_ERR_INVALID_ARG: not such a container, truncated, a tensor extent outside the file, a
+   missing tensor, a wrong shape, a value that is not finite, a silence id outside [0, output_dim).  PF_ERR_UNSUPPORTED:
+   rorder > 0, lfr_n != 1, or input / affine / linear / output > 512, proj > 256, n_layers > 8, lfr_m > 16,
+   (lorder - 1) * lstride > 256.  PF_ERR_IO: the file cannot be read. */
+typedef struct pf_vad_model pf_vad_model;
+int pf_vad_model_load(const char* path, pf_vad_model** m);
+int pf_vad_model_from_memory(const void* data, int64_t nbytes, pf_vad_model** m);
+/* dims [9]: input_dim, affine_dim, linear_dim, proj_dim, output_dim, n_layers, lorder, lstride, lfr_m; each output optional */
+int pf_vad_model_info(const pf_vad_model* m, int32_t* dims, int32_t* n_sil, int64_t* image_bytes);
+/* sil [cap] (NULL with cap 0 to learn *n); PF_ERR_CAPACITY when cap < *n */
+int pf_vad_model_sil_ids(const pf_vad_model* m, int32_t* sil, int32_t cap, int32_t* n);
+/* a tensor as loaded, by its container name: out [cap] fp32 (NULL with cap 0 to learn *n); PF_ERR_INVALID_ARG: no such name */
+int pf_vad_model_tensor(const pf_vad_model* m, const char* name, float* out, int64_t cap, int64_t* n);
+int pf_vad_model_config(pf_vad_config* cfg);
+void pf_vad_model_free(pf_vad_model* m);
+/* The CPU twins for ONE utterance (plain C++, float64 from the fp32 weights): rows [T, n_mels]; out [T, output_dim] / [T]. */
+int pf_host_vad_model_logits(const pf_vad_model* m, const float* rows, int64_t T, int32_t n_mels, double* out);
+int pf_host_vad_model_levels(const pf_vad_model* m, const float* rows, int64_t T, int32_t n_mels, int32_t* out);
+/* Attaches the model to the engine (NULL detaches and frees what the attach and its runs allocated): pf_vad_segment and everything built on it then compute step 1 with the
+   network (profile class "vadnet", 1 + n_layers launches) instead of the energy level (one launch of class "vad").  The engine
+   takes a reference of its own (pf_vad_model_free may follow at once) and uploads the weight image once.
+   PF_ERR_INVALID_ARG unless n_mels * lfr_m equals the model's input width; PF_ERR_UNSUPPORTED for a snip_edges = true
+   front-end.  A pf_group forward is unaffected. */
+int pf_engine_set_vad_model(pf_engine* e, const pf_vad_model* m);
 
 /* ------------------------------------------------------------------------ */
 /* 4b. Multi-GPU inside one process: one engine, one host thread and one HIP stream per listed
@@ -694,6 +741,11 @@ int pf_op_vad_levels(pf_engine* e, const float* rows, int64_t T, int32_t n_mels,
    n [B].  PF_ERR_CAPACITY (n filled in, the first cap segments of each row stored) when a row has more than cap segments. */
 int pf_op_vad_segments(pf_engine* e, const int32_t* levels, const int32_t* T, int32_t B, int32_t ld, int32_t n_mels,
                        const pf_vad_config* cfg, int32_t* seg, int32_t cap, int32_t* n);
+/* exactly the attached model's launches (k_vadnet.hip; PF_ERR_INVALID_ARG without pf_engine_set_vad_model) on caller rows: the
+   concatenated frames of B utterances, T [B] frames each, rows [sum T, n_mels] fp32; out [sum T, output_dim] fp32 logits /
+   out [sum T] int32 levels.  An utterance's result does not depend on its batch mates. */
+int pf_op_vad_model_logits(pf_engine* e, const float* rows, const int32_t* T, int32_t B, int32_t n_mels, float* out);
+int pf_op_vad_model_levels(pf_engine* e, const float* rows, const int32_t* T, int32_t B, int32_t n_mels, int32_t* out);
 /* exactly the pipeline's top-k kernel (k_topk.hip) on the values as given: x [rows, ld] (ld >= V; nothing at or beyond V is
    read in a row), K: 1 .. PF_TOPK_MAX; ids [rows, K], val [rows, K], n [rows] as pf_fetch_topk. */
 int pf_op_topk(pf_engine* e, const float* x, int64_t rows, int32_t V, int32_t ld, int32_t K, int64_t* ids, float* val,
@@ -1142,6 +1194,11 @@ int pf_recognizer_set_align(pf_recognizer* r, int32_t on);
    pf_recognizer_set_ctc_beam, pf_recognizer_set_align.  pf_group_* and the streaming classes have no such switch.
    PF_ERR_INVALID_ARG as for pf_vad_config; PF_ERR_UNSUPPORTED for a snip_edges = true front-end. */
 int pf_recognizer_set_vad(pf_recognizer* r, const pf_vad_config* cfg, int32_t batch_max, int64_t frame_budget, const char* sep_utf8);
+/* The FSMN-VAD model score for long-audio recognition (see "Voice-activity segmentation, model score"): pfw_path = a `.pfw` of
+   kind "fsmnvad", loaded once and attached to every engine of the pool, present and future; NULL clears.  Inert until
+   pf_recognizer_set_vad, and may be set before or after it.  The thresholds of pf_vad_model_config are the caller's to pass to
+   pf_recognizer_set_vad.  Errors as pf_vad_model_load and pf_engine_set_vad_model. */
+int pf_recognizer_set_vad_model(pf_recognizer* r, const char* pfw_path);
 /* The segments of the stream's last GetResults in time order (0 without pf_recognizer_set_vad): [begin_ms, end_ms) on the
    stream's clock, where it ran (batch, row of the plan), its share [tok_begin, tok_end) of pf_stream_tokens / pf_stream_scores
    / pf_stream_timestamp, and its own text; each output optional.  Valid until the stream's next GetResults. */
