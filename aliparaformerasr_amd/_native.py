@@ -185,6 +185,20 @@ SIGNATURES = {
     "pf_engine_set_vad_model": (C.c_int, [_vp, _vp]),
     "pf_op_vad_model_logits": (C.c_int, [_vp, _f, _i32, C.c_int32, C.c_int32, _f]),
     "pf_op_vad_model_levels": (C.c_int, [_vp, _f, _i32, C.c_int32, C.c_int32, _i32]),
+    "pf_punc_model_load": (C.c_int, [C.c_char_p, _P(_vp)]),
+    "pf_punc_model_from_memory": (C.c_int, [_vp, C.c_int64, _P(_vp)]),
+    "pf_punc_model_info": (C.c_int, [_vp, _i32, _i64]),
+    "pf_punc_model_free": (None, [_vp]),
+    "pf_host_punc_words": (C.c_int, [_vp, C.c_char_p, _i32, _i32, _i32, C.c_int32, _i32]),
+    "pf_host_punc_logits": (C.c_int, [_vp, _i32, C.c_int32, _P(C.c_double)]),
+    "pf_host_punc_cut": (C.c_int, [_vp, _i32, C.c_int32, C.c_int32, _i32]),
+    "pf_host_punc_ids": (C.c_int, [_vp, _i32, C.c_int64, _i32, _i32, _i32, C.c_int32, _i32]),
+    "pf_host_punc_assemble": (C.c_int, [_vp, C.c_char_p, _i32, C.c_int32, C.c_char_p, C.c_int64, _i64, _i32, C.c_int32, _i32]),
+    "pf_host_punc_text": (C.c_int, [_vp, C.c_char_p, C.c_char_p, C.c_int64, _i64, _i32, C.c_int32, _i32]),
+    "pf_engine_set_punc_model": (C.c_int, [_vp, _vp]),
+    "pf_engine_punctuate": (C.c_int, [_vp, _i32, _i32, C.c_int32, _i32, _i32]),
+    "pf_op_punc_logits": (C.c_int, [_vp, _i32, _i32, C.c_int32, _f, _f]),
+    "pf_op_punc_window": (C.c_int, [_vp, _i32, _i32, _i32, C.c_int32, _i32, _i32, _f]),
     "pf_op_vad_segments": (C.c_int, [_vp, _i32, _i32, C.c_int32, C.c_int32, C.c_int32, _P(PfVadConfig), _i32, C.c_int32, _i32]),
     "pf_stream_add_pcm": (C.c_int, [_vp, _vp, C.c_int64, _P(PfPcmDesc)]),
     "pf_host_wav_info": (C.c_int, [C.c_char_p, _P(PfPcmDesc), _i64, _i64, C.POINTER(C.c_double)]),
@@ -254,6 +268,10 @@ SIGNATURES = {
     "pf_op_lm_score": (C.c_int, [_vp, _vp, _i32, _i32, C.c_int32, C.c_int32, C.c_float, C.c_float, _P(C.c_double), _i32]),
     "pf_recognizer_set_vad": (C.c_int, [_vp, _P(PfVadConfig), C.c_int32, C.c_int64, C.c_char_p]),
     "pf_recognizer_set_vad_model": (C.c_int, [_vp, C.c_char_p]),
+    "pf_recognizer_set_punc_model": (C.c_int, [_vp, C.c_char_p]),
+    "pf_stream_punctuated": (C.c_int, [_vp, _cpp, _P(_i32), _i32]),
+    "pf_stream_num_sentences": (C.c_int, [_vp, _i32]),
+    "pf_stream_sentence": (C.c_int, [_vp, C.c_int32, _i32, _i32, _i32, _i32, _i32, _cpp]),
     "pf_stream_num_segments": (C.c_int, [_vp, _i32]),
     "pf_stream_segment": (C.c_int, [_vp, C.c_int32, _i32, _i32, _i32, _i32, _i32, _i32, _cpp]),
     "pf_recognizer_set_hotword_boost": (C.c_int, [_vp, C.c_float]),

@@ -16,6 +16,7 @@ mismatch with a real file fails loudly instead of producing a silently wrong mod
     python -m aliparaformerasr_amd.convert model.int8.onnx out.pfw [--eb model_eb.int8.onnx] [--kind ...]
         (ONNX graph walk, see onnx_to_state_dict; an int8 file's stored bytes are carried beside their float image)
     python -m aliparaformerasr_amd.convert vad.onnx|vad.pt out.pfw --kind fsmnvad --mvn vad.mvn [--sil 0,...] [--lfr-m 5]
+    python -m aliparaformerasr_amd.convert punc.pt|punc.onnx out.pfw --kind cttransformer --tokens tokens.json [--heads 8]
         (FunASR's FSMN-VAD, the model score of the voice-activity segmentation: vad_state_dict_to_pfw / vad_onnx_to_state_dict.
          NO REAL FSMN-VAD FILE HAS BEEN THROUGH THIS ROUTE: the names are restated from the public FunASR sources and
          exercised on tests/fsmn_vad_like.py)
@@ -427,6 +428,111 @@ def vad_to_pfw(model_path, mvn_path, sil_ids=(0,), lfr_m=5, lstride=1):
     return vad_state_dict_to_pfw(sd, shift, scale, sil_ids, lfr_m, lstride)
 
 
+def punc_state_dict_to_pfw(sd: dict, tokens, punc_list=None, sentence_end_id=None, heads: int = 8):
+    """FunASR CT-Transformer state dict (+ the vocabulary) -> (cfg, PFW weights) of kind "cttransformer".  FunASR's names:
+    embed.weight (or embed.0.weight), encoder.encoders0.0.* for the first block and encoder.encoders.N.* for block N + 1, each
+    with norm1, self_attn.linear_q_k_v, self_attn.fsmn_block.weight [d_model, 1, kernel], self_attn.linear_out, norm2,
+    feed_forward.w_1 / w_2; encoder.after_norm; decoder.  Refuses anything else: no silent defaults for a missing tensor."""
+    sd = {k: np.asarray(v, dtype=np.float32) for k, v in sd.items()}
+    emb = sd.get("embed.weight", sd.get("embed.0.weight"))
+    if emb is None or emb.ndim != 2:
+        raise ValueError("cttransformer: the checkpoint has no embed.weight [vocab, d_model]")
+    tokens = [str(t) for t in tokens]
+    if len(tokens) != emb.shape[0]:
+        raise ValueError("cttransformer: %d tokens for an embedding of %d rows" % (len(tokens), emb.shape[0]))
+    blocks = ["encoder.encoders0.0."] if any(k.startswith("encoder.encoders0.0.") for k in sd) else []
+    n = 0
+    while any(k.startswith("encoder.encoders.%d." % n) for k in sd):
+        blocks.append("encoder.encoders.%d." % n)
+        n += 1
+    if not blocks:
+        raise ValueError("cttransformer: the checkpoint has no encoder.encoders0.0.* / encoder.encoders.N.* blocks")
+    punc_list = list(punc_list or W.CT_TRANSFORMER_CONFIG["punc_list"])
+
+    def get(name):
+        if name not in sd:
+            raise ValueError("cttransformer: the checkpoint lacks " + name)
+        return sd[name]
+    w = {"embed.weight": emb}
+    for l, b in enumerate(blocks):
+        p = "layers.%d." % l
+        for src, dst in (("norm1", "norm1"), ("self_attn.linear_q_k_v", "attn.qkv"), ("self_attn.linear_out", "attn.out"), ("norm2", "norm2"),
+                         ("feed_forward.w_1", "ffn.w1"), ("feed_forward.w_2", "ffn.w2")):
+            w[p + dst + ".weight"] = get(b + src + ".weight")
+            w[p + dst + ".bias"] = get(b + src + ".bias")
+        f = get(b + "self_attn.fsmn_block.weight")
+        if f.ndim != 3 or f.shape[1] != 1:
+            raise ValueError("cttransformer: fsmn_block.weight has shape %s, expected [d_model, 1, kernel]" % (list(f.shape),))
+        w[p + "attn.fsmn.weight"] = f[:, 0, :]
+    for src, dst in (("encoder.after_norm", "after_norm"), ("decoder", "decoder")):
+        w[dst + ".weight"] = get(src + ".weight")
+        w[dst + ".bias"] = get(src + ".bias")
+    if w["decoder.weight"].shape[0] != len(punc_list):
+        raise ValueError("cttransformer: the decoder has %d classes, punc_list %d" % (w["decoder.weight"].shape[0], len(punc_list)))
+    if sentence_end_id is None:
+        sentence_end_id = punc_list.index("\u3002") if "\u3002" in punc_list else -1
+    cfg = W.ct_transformer_config(vocab=int(emb.shape[0]), d_model=int(emb.shape[1]), heads=int(heads), ffn=int(w["layers.0.ffn.w1.weight"].shape[0]),
+                                  kernel=int(w["layers.0.attn.fsmn.weight"].shape[1]), n_layers=len(blocks), punc_list=punc_list,
+                                  sentence_end_id=int(sentence_end_id))
+    for name, shape in W.punc_tensor_shapes(cfg).items():
+        if tuple(w[name].shape) != tuple(shape):
+            raise ValueError("cttransformer: %s has shape %s, expected %s" % (name, list(w[name].shape), list(shape)))
+    w = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in w.items()}
+    w["vocab"] = np.frombuffer("\n".join(tokens).encode("utf-8"), dtype=np.uint8).copy()
+    return cfg, w
+
+
+def punc_onnx_to_state_dict(graph) -> dict:
+    """A FunASR CT-Transformer ONNX export -> {FunASR parameter name: float32 array}, through the walk the Paraformer encoder's
+    export goes through (onnx_to_state_dict: the anonymous MatMul weights are named after the bias their Add carries).  Refuses
+    (ValueError) a graph that is not an embedding Gather followed by SAN-M blocks and one more Linear: per block one Softmax, one
+    depthwise Conv whose weight is [d_model, 1, kernel] and four MatMuls against 2-D initialisers, plus the decoder's."""
+    blocks = ["encoder.encoders0.0."] + ["encoder.encoders.%d." % n for n in range(64)]
+    parts = ("norm1", "self_attn.linear_q_k_v", "self_attn.linear_out", "norm2", "feed_forward.w_1", "feed_forward.w_2")
+    expected = {"embed.weight", "encoder.after_norm.weight", "encoder.after_norm.bias", "decoder.weight", "decoder.bias"}
+    for b in blocks:
+        expected |= {b + q + sfx for q in parts for sfx in (".weight", ".bias")} | {b + "self_attn.fsmn_block.weight"}
+    sd = {k: v for k, v in onnx_to_state_dict(graph, expected).items() if not k.endswith(_Q_SUFFIXES)}
+    ini = graph.initializers
+    n_blocks = len({k.split("self_attn.fsmn_block.weight")[0] for k in sd if k.endswith("self_attn.fsmn_block.weight")})
+    gathers = [n for n in graph.nodes if n.op_type == "Gather" and n.inputs and n.inputs[0] in ini and np.asarray(ini[n.inputs[0]]).ndim == 2]
+    softmax = sum(1 for n in graph.nodes if n.op_type == "Softmax")
+    convs = [n for n in graph.nodes if n.op_type == "Conv"]
+    mms = sum(1 for n in graph.nodes if n.op_type == "MatMul" and len(n.inputs) == 2 and n.inputs[1] in ini and np.asarray(ini[n.inputs[1]]).ndim == 2)
+    if "embed.weight" not in sd or len(gathers) != 1 or n_blocks < 1 or softmax != n_blocks or len(convs) != n_blocks or mms != 4 * n_blocks + 1:
+        raise ValueError("cttransformer: the graph is not an embedding followed by SAN-M blocks and a decoder (%d embedding Gather, %d "
+                         "fsmn_block weights, %d Softmax, %d Conv, %d MatMul against a matrix)" % (len(gathers), n_blocks, softmax, len(convs), mms))
+    d = sd["embed.weight"].shape[1]
+    for n in convs:
+        wt = np.asarray(ini.get(n.inputs[1], np.zeros(0))) if len(n.inputs) > 1 else np.zeros(0)
+        if wt.ndim != 3 or wt.shape[0] != d or wt.shape[1] != 1 or int(n.attrs.get("group", 1)) != d:
+            raise ValueError("cttransformer: a Conv of the graph is not a depthwise FSMN block over d_model channels")
+    return sd
+
+
+def punc_to_pfw(model_path, tokens_path, heads=8):
+    """model.pt | model.onnx + tokens -> (cfg, PFW weights) of kind "cttransformer"."""
+    if str(model_path).endswith(".onnx"):
+        from . import onnx_reader as R
+        sd = punc_onnx_to_state_dict(R.load(model_path))
+    else:
+        import torch
+        sd = torch.load(model_path, map_location="cpu")
+        sd = sd.get("state_dict", sd.get("model", sd)) if isinstance(sd, dict) else sd
+        sd = {k: v.float().numpy() for k, v in sd.items() if hasattr(v, "numpy")}
+    return punc_state_dict_to_pfw(sd, read_punc_tokens(tokens_path), heads=heads)
+
+
+def read_punc_tokens(path):
+    """tokens.json (a JSON list of strings) or a text file with one token per line."""
+    import json
+    with open(path, "r", encoding="utf-8") as f:
+        text = f.read()
+    if text.lstrip().startswith("["):
+        return [str(t) for t in json.loads(text)]
+    return [ln for ln in text.split("\n") if ln != ""]
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     if len(argv) < 2:
@@ -443,6 +549,15 @@ def main(argv=None):
         lfr_m = int(argv[argv.index("--lfr-m") + 1]) if "--lfr-m" in argv else 5
         lstride = int(argv[argv.index("--lstride") + 1]) if "--lstride" in argv else 1
         cfg, wts = vad_to_pfw(argv[0], argv[argv.index("--mvn") + 1], sil, lfr_m, lstride)
+        W.save_pfw(argv[1], cfg, wts)
+        print("wrote %s (%s, %d tensors)" % (argv[1], cfg["kind"], len(wts)))
+        return 0
+    if kind == "cttransformer":
+        if "--tokens" not in argv:
+            print("--kind cttransformer needs --tokens tokens.json (or a file with one token per line)")
+            return 2
+        heads = int(argv[argv.index("--heads") + 1]) if "--heads" in argv else 8
+        cfg, wts = punc_to_pfw(argv[0], argv[argv.index("--tokens") + 1], heads)
         W.save_pfw(argv[1], cfg, wts)
         print("wrote %s (%s, %d tensors)" % (argv[1], cfg["kind"], len(wts)))
         return 0

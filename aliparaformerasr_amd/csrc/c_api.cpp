@@ -1007,6 +1007,189 @@ int pf_op_vad_model_levels(pf_engine* h, const float* rows, const int32_t* T, in
   return op_vad_model(h, rows, T, B, n_mels, nullptr, out);
 }
 
+// ---- punctuation ----
+int pf_punc_model_load(const char* path, pf_punc_model** m) {
+  PF_TRY
+  NEED(m); NEED(path);
+  *m = nullptr;
+  std::shared_ptr<const PuncModel> p = punc_model_load(path);
+  *m = new pf_punc_model{std::move(p)};
+  return PF_OK;
+  PF_CATCH
+}
+int pf_punc_model_from_memory(const void* data, int64_t nbytes, pf_punc_model** m) {
+  PF_TRY
+  NEED(m); NEED(data);
+  *m = nullptr;
+  std::shared_ptr<const PuncModel> p = punc_model_from_memory(data, nbytes);
+  *m = new pf_punc_model{std::move(p)};
+  return PF_OK;
+  PF_CATCH
+}
+int pf_punc_model_info(const pf_punc_model* m, int32_t* dims, int64_t* image_bytes) {
+  PF_TRY
+  NEED(m);
+  const PuncModel& v = *m->p;
+  if (dims) {
+    const int32_t d[16] = {v.vocab, v.d_model, v.heads, v.ffn, v.kernel, v.n_layers, v.n_punc, v.sentence_end_id, v.unk_word,
+                           v.id_unk, v.id_none, v.id_comma, v.id_period, v.id_question, v.id_pause, 0};
+    std::memcpy(dims, d, sizeof(d));
+  }
+  if (image_bytes) *image_bytes = (int64_t)v.image.size();
+  return PF_OK;
+  PF_CATCH
+}
+void pf_punc_model_free(pf_punc_model* m) { delete m; }
+int pf_host_punc_words(const pf_punc_model* m, const char* text, int32_t* ids, int32_t* begin, int32_t* end, int32_t cap, int32_t* n) {
+  PF_TRY
+  NEED(m); NEED(text); NEED(n);
+  const std::vector<PuncWord> w = host_punc_words(*m->p, text);
+  *n = (int32_t)w.size();
+  if (cap == 0 && !ids && !begin && !end) return PF_OK;
+  PF_CHECK(cap >= *n, PF_ERR_CAPACITY, "punc_words: capacity below the number of words");
+  for (size_t i = 0; i < w.size(); ++i) {
+    if (ids) ids[i] = w[i].id;
+    if (begin) begin[i] = w[i].begin;
+    if (end) end[i] = w[i].end;
+  }
+  return PF_OK;
+  PF_CATCH
+}
+int pf_host_punc_logits(const pf_punc_model* m, const int32_t* ids, int32_t T, double* out) {
+  PF_TRY
+  NEED(m);
+  PF_CHECK(T >= 0 && T <= PF_PUNC_MAX_WINDOW, PF_ERR_INVALID_ARG, "punc_logits: a window holds 0 .. PF_PUNC_MAX_WINDOW ids");
+  if (T > 0) { NEED(ids); NEED(out); }
+  host_punc_logits(*m->p, ids, T, out);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_host_punc_cut(const pf_punc_model* m, int32_t* p, int32_t n, int32_t last, int32_t* cut) {
+  PF_TRY
+  NEED(m); NEED(cut);
+  PF_CHECK(n >= 0, PF_ERR_INVALID_ARG, "punc_cut: negative length");
+  if (n > 0) NEED(p);
+  *cut = host_punc_cut(*m->p, p, n, last != 0);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_host_punc_ids(const pf_punc_model* m, const int32_t* ids, int64_t n, int32_t* punc_ids, int32_t* win_len, int32_t* win_cut,
+                     int32_t win_cap, int32_t* n_win) {
+  PF_TRY
+  NEED(m);
+  PF_CHECK(n >= 0, PF_ERR_INVALID_ARG, "punc_ids: negative length");
+  if (n > 0) { NEED(ids); NEED(punc_ids); }
+  std::vector<std::pair<int32_t, int32_t>> wins;
+  host_punc_ids(*m->p, ids, n, punc_ids, &wins);
+  if (n_win) *n_win = (int32_t)wins.size();
+  if (win_len || win_cut) {
+    PF_CHECK(win_cap >= (int32_t)wins.size(), PF_ERR_CAPACITY, "punc_ids: capacity below the number of windows");
+    for (size_t i = 0; i < wins.size(); ++i) {
+      if (win_len) win_len[i] = wins[i].first;
+      if (win_cut) win_cut[i] = wins[i].second;
+    }
+  }
+  return PF_OK;
+  PF_CATCH
+}
+static int punc_assemble(const PuncModel& m, const std::string& text, const std::vector<PuncWord>& w, const int32_t* punc_ids, char* out,
+                         int64_t cap, int64_t* out_len, int32_t* sent_end, int32_t sent_cap, int32_t* n_sent) {
+  std::vector<int32_t> se;
+  const std::string s = host_punc_assemble(m, text, w, punc_ids, &se);
+  if (out_len) *out_len = (int64_t)s.size();
+  if (n_sent) *n_sent = (int32_t)se.size();
+  if (out || cap > 0) {
+    PF_CHECK(cap >= (int64_t)s.size() && (out || s.empty()), PF_ERR_CAPACITY, "punc: capacity below the length of the text");
+    if (!s.empty()) std::memcpy(out, s.data(), s.size());
+  }
+  if (sent_end) {
+    PF_CHECK(sent_cap >= (int32_t)se.size(), PF_ERR_CAPACITY, "punc: capacity below the number of sentences");
+    if (!se.empty()) std::memcpy(sent_end, se.data(), se.size() * 4);
+  }
+  return PF_OK;
+}
+int pf_host_punc_assemble(const pf_punc_model* m, const char* text, const int32_t* punc_ids, int32_t n, char* out, int64_t cap,
+                          int64_t* out_len, int32_t* sent_end, int32_t sent_cap, int32_t* n_sent) {
+  PF_TRY
+  NEED(m); NEED(text);
+  const std::string t(text);
+  const std::vector<PuncWord> w = host_punc_words(*m->p, t);
+  PF_CHECK(n == (int32_t)w.size(), PF_ERR_INVALID_ARG, "punc_assemble: n is not the number of words of the text");
+  if (n > 0) NEED(punc_ids);
+  return punc_assemble(*m->p, t, w, punc_ids, out, cap, out_len, sent_end, sent_cap, n_sent);
+  PF_CATCH
+}
+int pf_host_punc_text(const pf_punc_model* m, const char* text, char* out, int64_t cap, int64_t* out_len, int32_t* punc_ids,
+                      int32_t ids_cap, int32_t* n_words) {
+  PF_TRY
+  NEED(m); NEED(text);
+  const std::string t(text);
+  const std::vector<PuncWord> w = host_punc_words(*m->p, t);
+  if (n_words) *n_words = (int32_t)w.size();
+  std::vector<int32_t> ids(w.size()), p(w.size());
+  for (size_t i = 0; i < w.size(); ++i) ids[i] = w[i].id;
+  host_punc_ids(*m->p, ids.data(), (int64_t)ids.size(), p.data(), nullptr);
+  if (punc_ids) {
+    PF_CHECK(ids_cap >= (int32_t)w.size(), PF_ERR_CAPACITY, "punc_text: capacity below the number of words");
+    if (!p.empty()) std::memcpy(punc_ids, p.data(), p.size() * 4);
+  }
+  return punc_assemble(*m->p, t, w, p.data(), out, cap, out_len, nullptr, 0, nullptr);
+  PF_CATCH
+}
+int pf_engine_set_punc_model(pf_engine* h, const pf_punc_model* m) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->set_punc_model(m ? m->p : nullptr);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_engine_punctuate(pf_engine* h, const int32_t* ids, const int32_t* lens, int32_t B, int32_t* punc_ids, int32_t* rounds) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  PF_CHECK(B >= 0, PF_ERR_INVALID_ARG, "punctuate: negative B");
+  int64_t total = 0;
+  if (B > 0) NEED(lens);
+  for (int b = 0; b < B; ++b) total += std::max(lens[b], 0);
+  if (total > 0) { NEED(ids); NEED(punc_ids); }
+  std::lock_guard<std::mutex> lk(e->mutex());
+  const int r = e->punctuate(ids, lens, B, punc_ids);
+  if (rounds) *rounds = r;
+  return PF_OK;
+  PF_CATCH
+}
+int pf_op_punc_logits(pf_engine* h, const int32_t* ids, const int32_t* T, int32_t B, float* logits, float* x0) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  PF_CHECK(B >= 0, PF_ERR_INVALID_ARG, "punc_logits: negative B");
+  int64_t total = 0;
+  if (B > 0) NEED(T);
+  for (int b = 0; b < B; ++b) total += std::max(T[b], 0);
+  if (total > 0) { NEED(ids); NEED(logits); }
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->op_punc(ids, T, nullptr, B, logits, x0, nullptr, nullptr);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_op_punc_window(pf_engine* h, const int32_t* ids, const int32_t* T, const int32_t* last, int32_t B, int32_t* p, int32_t* cut,
+                      float* logits) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  PF_CHECK(B >= 0, PF_ERR_INVALID_ARG, "punc_window: negative B");
+  int64_t total = 0;
+  if (B > 0) { NEED(T); NEED(last); NEED(cut); }
+  for (int b = 0; b < B; ++b) total += std::max(T[b], 0);
+  if (total > 0) { NEED(ids); NEED(p); }
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->op_punc(ids, T, last, B, logits, nullptr, p, cut);
+  return PF_OK;
+  PF_CATCH
+}
+
 int pf_op_topk(pf_engine* h, const float* x, int64_t rows, int32_t V, int32_t ld, int32_t K, int64_t* ids, float* val,
                int32_t* n) {
   PF_TRY
@@ -1779,6 +1962,46 @@ int pf_recognizer_set_vad_model(pf_recognizer* h, const char* pfw_path) {
   std::shared_ptr<Recognizer> r = R(h);
   PF_CHECK(!r->disposed(), PF_ERR_DISPOSED, "OfflineRecognizer");
   r->SetVadModel(pfw_path ? pfw_path : "");
+  return PF_OK;
+  PF_CATCH
+}
+int pf_recognizer_set_punc_model(pf_recognizer* h, const char* pfw_path) {
+  PF_TRY
+  std::shared_ptr<Recognizer> r = R(h);
+  PF_CHECK(!r->disposed(), PF_ERR_DISPOSED, "OfflineRecognizer");
+  r->SetPuncModel(pfw_path ? pfw_path : "");
+  return PF_OK;
+  PF_CATCH
+}
+int pf_stream_punctuated(pf_stream* h, const char** text_utf8, const int32_t** punc_ids, int32_t* n_words) {
+  PF_TRY
+  Stream* s = S(h);
+  if (text_utf8) *text_utf8 = s->Punctuated.c_str();
+  if (punc_ids) *punc_ids = s->PuncIds.data();
+  if (n_words) *n_words = (int32_t)s->PuncIds.size();
+  return PF_OK;
+  PF_CATCH
+}
+int pf_stream_num_sentences(pf_stream* h, int32_t* n) {
+  PF_TRY
+  Stream* s = S(h);
+  NEED(n);
+  *n = (int32_t)s->Sentences.size();
+  return PF_OK;
+  PF_CATCH
+}
+int pf_stream_sentence(pf_stream* h, int32_t i, int32_t* word_begin, int32_t* word_end, int32_t* has_time, int32_t* begin_ms,
+                       int32_t* end_ms, const char** text_utf8) {
+  PF_TRY
+  Stream* s = S(h);
+  PF_CHECK(i >= 0 && (size_t)i < s->Sentences.size(), PF_ERR_INVALID_ARG, "sentence index out of range");
+  const Stream::Sentence& g = s->Sentences[(size_t)i];
+  if (word_begin) *word_begin = g.word_begin;
+  if (word_end) *word_end = g.word_end;
+  if (has_time) *has_time = g.has_time ? 1 : 0;
+  if (begin_ms) *begin_ms = g.begin_ms;
+  if (end_ms) *end_ms = g.end_ms;
+  if (text_utf8) *text_utf8 = g.text.c_str();
   return PF_OK;
   PF_CATCH
 }

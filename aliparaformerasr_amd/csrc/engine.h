@@ -11,6 +11,7 @@
 
 #include "lm.h"
 #include "vadnet.h"
+#include "punc.h"
 #include "json.h"
 #include "kernels.h"
 #include "shards.h"
@@ -254,6 +255,16 @@ class Engine {
   // the network on caller rows: rows = the concatenated frames of B utterances of T[b] frames; logits [sum T, output_dim]
   // and / or levels [sum T] (either may be null).  Uses the attached model.
   void op_vad_model(const float* rows, const int32_t* T, int B, int n_mels, float* logits, int32_t* levels);
+  // The CT-Transformer punctuation model (k_punc.hip, punc.h).  nullptr detaches and frees the image and the workspace (nothing
+  // of it is launched or allocated then; attaching the model an engine still has costs no upload).  The engine keeps a
+  // reference and uploads the image once.  A forward is profile class "punc": 1 + 2 n_layers launches, one more with the cut.
+  void set_punc_model(const std::shared_ptr<const PuncModel>& m);
+  const std::shared_ptr<const PuncModel>& punc_model() const { return punc_; }
+  // the text loop over B texts given as ids (punc.h host_punc_ids is its host form): punc_ids [sum lens]; returns the rounds
+  int punctuate(const int32_t* ids, const int32_t* lens, int B, int32_t* punc_ids);
+  // the forward on caller windows: logits [sum T, n_punc], x0 [sum T, d_model] (layer 0's input), p [sum T] and cut [B] (the
+  // cut launch runs when cut is asked for; it needs last [B]); every output may be null
+  void op_punc(const int32_t* ids, const int32_t* T, const int32_t* last, int B, float* logits, float* x0, int32_t* p, int32_t* cut);
   void op_vad_segments(const int32_t* levels, const int32_t* T, int B, int ld, int n_mels, const pf_vad_config* cfg, int32_t* seg,
                        int cap, int32_t* n);
   void op_ctc_collapse(const int64_t* ids, const float* scores, const int32_t* lens, int B, int T, int blank, int64_t* ids_out,
@@ -577,6 +588,11 @@ class Engine {
   std::shared_ptr<const VadModel> vadnet_;
   struct VadNetDev { DevBuf buf; std::shared_ptr<const VadModel> src; } vadnet_dev_;
   DevBuf ws_vadnet_;
+  // the punctuation model (set_punc_model): as above; ws_punc_ holds ids, offsets, x, the two q | k | v buffers, ctx, logits, p, cut
+  std::shared_ptr<const PuncModel> punc_;
+  struct PuncDev { DevBuf buf; std::shared_ptr<const PuncModel> src; } punc_dev_;
+  DevBuf ws_punc_;
+  void run_punc(const int32_t* ids, const int64_t* off, const int32_t* last, int B, float* logits, float* x0, int32_t* p, int32_t* cut);
   void run_vadnet(const float* rows_dev, const int64_t* off_dev, int B, int64_t total, int n_mels, float* logits_dev, int32_t* levels_dev);
   float lm_alpha_ = 0.f, lm_beta_ = 0.f;
   int lm_flags_ = 0;

@@ -378,6 +378,166 @@ void Engine::op_vad_model(const float* rows, const int32_t* T, int B, int n_mels
   PF_HIP(hipStreamSynchronize(stream_));                          // (`off` is read by its copy until then)
 }
 
+// ---- the CT-Transformer punctuation model (k_punc.hip; the launch plan is at the head of that file)
+void Engine::set_punc_model(const std::shared_ptr<const PuncModel>& m) {
+  if (!m) {                                         // detached: nothing of the network stays allocated
+    punc_.reset();
+    punc_dev_.src.reset();
+    if (punc_dev_.buf.p || ws_punc_.p) {
+      PF_HIP(hipSetDevice(device_));
+      PF_HIP(hipStreamSynchronize(stream_));        // a queued launch may still read the image or the workspace
+      for (DevBuf* b : {&punc_dev_.buf, &ws_punc_})
+        if (b->p) { PF_HIP(hipFree(b->p)); b->p = nullptr; b->bytes = 0; }
+    }
+    return;
+  }
+  PF_HIP(hipSetDevice(device_));
+  if (punc_dev_.src != m) {
+    PF_HIP(hipStreamSynchronize(stream_));          // a queued launch may still read the image about to be replaced
+    punc_dev_.src.reset();
+    ensure(punc_dev_.buf, m->image.size());
+    PF_HIP(hipMemcpyAsync(punc_dev_.buf.p, m->image.data(), m->image.size(), hipMemcpyHostToDevice, stream_));
+    PF_HIP(hipStreamSynchronize(stream_));
+    punc_dev_.src = m;
+  }
+  punc_ = m;
+}
+
+// one forward over B windows (host arrays in, host arrays out; returns after the results have arrived)
+void Engine::run_punc(const int32_t* ids, const int64_t* off, const int32_t* last, int B, float* logits, float* x0, int32_t* p,
+                      int32_t* cut) {
+  const PuncModel& m = *punc_;
+  const int64_t total = off[B];
+  for (int b = 0; b < B; ++b)
+    PF_CHECK(off[b + 1] >= off[b] && off[b + 1] - off[b] <= PF_PUNC_MAX_WINDOW, PF_ERR_CAPACITY, "punc: a window above PF_PUNC_MAX_WINDOW ids");
+  if (total == 0) {                                 // nothing to launch: every window is empty
+    if (cut) std::fill(cut, cut + B, -1);
+    return;
+  }
+  const int D = m.d_model, P = m.n_punc, NL = m.n_layers;
+  Cursor c;
+  const Field<int64_t> d_off = c.take<int64_t>((size_t)B + 1);
+  const Field<int32_t> d_ids = c.take<int32_t>((size_t)total), d_last = c.take<int32_t>((size_t)B), d_cut = c.take<int32_t>((size_t)B),
+                       d_p = c.take<int32_t>((size_t)total);
+  c.off = (size_t)round_up((int64_t)c.off, 256);
+  const Field<float> d_x = c.take<float>((size_t)total * D), d_z = c.take<float>((size_t)total * P);
+  c.off = (size_t)round_up((int64_t)c.off, 256);
+  const Field<half_t> d_q0 = c.take<half_t>((size_t)total * 3 * D), d_q1 = c.take<half_t>((size_t)total * 3 * D),
+                      d_ctx = c.take<half_t>((size_t)total * D);
+  ensure(ws_punc_, c.off);
+  void* ws = ws_punc_.p;
+  PF_HIP(hipMemcpyAsync(d_off(ws), off, ((size_t)B + 1) * 8, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipMemcpyAsync(d_ids(ws), ids, (size_t)total * 4, hipMemcpyHostToDevice, stream_));
+  if (cut) PF_HIP(hipMemcpyAsync(d_last(ws), last, (size_t)B * 4, hipMemcpyHostToDevice, stream_));
+  half_t* qkv[2] = {d_q0(ws), d_q1(ws)};
+  const double rows = (double)round_up(total, 64);
+  const double f_qkv = 2.0 * 3 * D * D, f_layer = 2.0 * D * D + 4.0 * D * m.ffn;
+  auto tail = [&](PuncRowsLaunch& a, int l) {       // what follows layer l - 1 (l = 0: the embedding)
+    if (l < NL) {
+      a.tail = 0; a.n_g = m.limg[(size_t)l].n1_g; a.n_b = m.limg[(size_t)l].n1_b; a.last = m.limg[(size_t)l].qkv; a.qkv_out = qkv[l & 1];
+    } else {
+      a.tail = 1; a.n_g = m.after_g_off; a.n_b = m.after_b_off; a.last = m.dec; a.n_punc = P; a.logits = d_z(ws); a.p = d_p(ws);
+    }
+  };
+  PuncRowsLaunch a{};
+  a.img = (const char*)punc_dev_.buf.p; a.off = d_off(ws); a.B = B; a.total = total; a.x = d_x(ws);
+  a.head = 0; a.ids = d_ids(ws); a.pe_off = m.pe_off; a.embed_off = m.embed_off;
+  tail(a, 0);
+  prof_begin("punc", f_qkv * rows);
+  launch_punc_rows(stream_, a);
+  prof_end("punc");
+  if (x0) PF_HIP(hipMemcpyAsync(x0, d_x(ws), (size_t)total * D * 4, hipMemcpyDeviceToHost, stream_));   // before layer 0 rewrites x
+  for (int l = 0; l < NL; ++l) {
+    const PuncModel::LayerImg& g = m.limg[(size_t)l];
+    prof_begin("punc", 0);                          // (4 T^2 d_model per window: not counted, T varies per window)
+    launch_punc_attn(stream_, PuncAttnLaunch{qkv[l & 1], d_off(ws), B, d_ctx(ws)});
+    prof_end("punc");
+    PuncRowsLaunch r{};
+    r.img = a.img; r.off = a.off; r.B = B; r.total = total; r.x = a.x;
+    r.head = 1; r.ctx = d_ctx(ws); r.qkv_in = qkv[l & 1]; r.taps_off = g.taps; r.kernel = m.kernel; r.out = g.out;
+    r.n2_g = g.n2_g; r.n2_b = g.n2_b; r.w1 = g.w1; r.w2 = g.w2;
+    tail(r, l + 1);
+    prof_begin("punc", (f_layer + (l + 1 < NL ? f_qkv : 2.0 * 32 * D)) * rows);
+    launch_punc_rows(stream_, r);
+    prof_end("punc");
+  }
+  if (cut) {
+    PuncCutLaunch k{d_p(ws), d_off(ws), d_last(ws), B, d_cut(ws), m.id_none, m.id_comma, m.id_period, m.id_question, m.id_pause,
+                    m.sentence_end_id, kPuncCommaWindow, kPuncHardWindow};
+    prof_begin("punc", 0);
+    launch_punc_cut(stream_, k);
+    prof_end("punc");
+    PF_HIP(hipMemcpyAsync(cut, d_cut(ws), (size_t)B * 4, hipMemcpyDeviceToHost, stream_));
+  }
+  if (logits) PF_HIP(hipMemcpyAsync(logits, d_z(ws), (size_t)total * P * 4, hipMemcpyDeviceToHost, stream_));
+  if (p) PF_HIP(hipMemcpyAsync(p, d_p(ws), (size_t)total * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipStreamSynchronize(stream_));
+}
+
+void Engine::op_punc(const int32_t* ids, const int32_t* T, const int32_t* last, int B, float* logits, float* x0, int32_t* p, int32_t* cut) {
+  PF_CHECK(punc_ != nullptr, PF_ERR_INVALID_ARG, "op_punc: no model is attached (pf_engine_set_punc_model)");
+  PF_CHECK(B >= 0 && B <= PF_PUNC_MAX_BATCH, PF_ERR_INVALID_ARG, "op_punc: B outside 0 .. PF_PUNC_MAX_BATCH");
+  std::vector<int64_t> off((size_t)B + 1, 0);
+  for (int b = 0; b < B; ++b) {
+    PF_CHECK(T[b] >= 0 && T[b] <= PF_PUNC_MAX_WINDOW, PF_ERR_INVALID_ARG, "op_punc: a window holds 0 .. PF_PUNC_MAX_WINDOW ids");
+    off[(size_t)b + 1] = off[(size_t)b] + T[b];
+  }
+  for (int64_t i = 0; i < off[(size_t)B]; ++i)
+    PF_CHECK(ids[i] >= 0 && ids[i] < punc_->vocab, PF_ERR_INVALID_ARG, "op_punc: a word id is outside the vocabulary");
+  if (B == 0) return;
+  PF_HIP(hipSetDevice(device_));
+  run_punc(ids, off.data(), last, B, logits, x0, p, cut);
+}
+
+int Engine::punctuate(const int32_t* ids, const int32_t* lens, int B, int32_t* punc_ids) {
+  PF_CHECK(punc_ != nullptr, PF_ERR_INVALID_ARG, "punctuate: no model is attached (pf_engine_set_punc_model)");
+  PF_CHECK(B >= 0 && B <= PF_PUNC_MAX_BATCH, PF_ERR_INVALID_ARG, "punctuate: B outside 0 .. PF_PUNC_MAX_BATCH");
+  struct Text { int64_t begin = 0, n = 0, n_mini = 0, mini = 0, done = 0; std::vector<int32_t> win; };
+  std::vector<Text> tx((size_t)B);
+  int64_t at = 0, most = 0;
+  for (int b = 0; b < B; ++b) {
+    PF_CHECK(lens[b] >= 0, PF_ERR_INVALID_ARG, "punctuate: a negative length");
+    tx[(size_t)b].begin = at; tx[(size_t)b].n = lens[b]; tx[(size_t)b].n_mini = (lens[b] + kPuncMini - 1) / kPuncMini;
+    most = std::max(most, tx[(size_t)b].n_mini);
+    at += lens[b];
+  }
+  for (int64_t i = 0; i < at; ++i)
+    PF_CHECK(ids[i] >= 0 && ids[i] < punc_->vocab, PF_ERR_INVALID_ARG, "punctuate: a word id is outside the vocabulary");
+  PF_HIP(hipSetDevice(device_));
+  std::vector<int> who;
+  std::vector<int32_t> w_ids, w_last, w_cut, w_p;
+  std::vector<int64_t> w_off;
+  int rounds = 0;
+  for (; rounds < most; ++rounds) {                 // round r: mini-sentence r of every text that has one
+    who.clear(); w_ids.clear(); w_last.clear(); w_off.assign(1, 0);
+    for (int b = 0; b < B; ++b) {
+      Text& t = tx[(size_t)b];
+      if (t.mini >= t.n_mini) continue;
+      const int64_t lo = t.mini * kPuncMini, hi = std::min(t.n, lo + kPuncMini);
+      t.win.insert(t.win.end(), ids + t.begin + lo, ids + t.begin + hi);
+      // the cut rule keeps a carried tail at or below kPuncHardWindow; the kernels' LDS and the pe table end at PF_PUNC_MAX_WINDOW
+      PF_CHECK(t.win.size() <= (size_t)PF_PUNC_MAX_WINDOW, PF_ERR_CAPACITY, "punctuate: a window above PF_PUNC_MAX_WINDOW words");
+      who.push_back(b);
+      w_ids.insert(w_ids.end(), t.win.begin(), t.win.end());
+      w_last.push_back(t.mini == t.n_mini - 1 ? 1 : 0);
+      w_off.push_back((int64_t)w_ids.size());
+    }
+    const int W = (int)who.size();
+    w_cut.assign((size_t)W, -1);
+    w_p.assign(w_ids.size(), 0);
+    run_punc(w_ids.data(), w_off.data(), w_last.data(), W, nullptr, nullptr, w_p.data(), w_cut.data());
+    for (int w = 0; w < W; ++w) {
+      Text& t = tx[(size_t)who[(size_t)w]];
+      const int cut = w_cut[(size_t)w];
+      PF_CHECK(cut >= -1 && cut < (int)t.win.size(), PF_ERR_DEVICE, "punctuate: a cut outside its window");
+      for (int i = 0; i <= cut; ++i) punc_ids[t.begin + t.done++] = w_p[(size_t)w_off[(size_t)w] + (size_t)i];
+      t.win.erase(t.win.begin(), t.win.begin() + (cut + 1));
+      ++t.mini;
+    }
+  }
+  return rounds;
+}
+
 // the five decoders on caller data; ws_tmp_: the result block of decode_blocks.h, then the uploaded inputs and the scratch
 void Engine::op_topk(const float* x, int64_t rows, int V, int ld, int K, int64_t* ids, float* val, int32_t* n) {
   PF_HIP(hipSetDevice(device_));

@@ -509,4 +509,29 @@ struct VadNetLaunch {
 size_t vadnet_lds_bytes(int ld);
 void launch_vadnet(hipStream_t s, const VadNetLaunch& a);
 
+// ---------------------------------------------------------------- the CT-Transformer punctuation model (k_punc.hip) ------
+// The definition in numpy is tests/punc_ref.py; the launch plan (2 + 2 n_layers launches per forward) is at the head of
+// k_punc.hip and Engine::run_punc fills these in.  img: the model's device image (punc.h); every *_off and VadGemm offset is a
+// byte offset into it.  Rows: `total` ids, window b at rows [off[b], off[b + 1]), at most PF_PUNC_MAX_WINDOW each.
+struct PuncRowsLaunch {
+  const char* img; const int64_t* off; int B; int64_t total;
+  int head;                                                     // 0: embedding * 16 + pe -> x; 1: the layer behind its attention
+  int tail;                                                     // 0: LayerNorm (n_g, n_b) + `last` = qkv -> qkv_out; 1: + `last` = decoder -> logits / p
+  float* x;                                                     // the residual stream fp32 [total, 256], updated in place
+  const int32_t* ids; int64_t pe_off, embed_off;                // head 0
+  const half_t* ctx; const half_t* qkv_in; int64_t taps_off; int kernel; VadGemm out; int64_t n2_g, n2_b; VadGemm w1, w2;   // head 1
+  int64_t n_g, n_b; VadGemm last;
+  half_t* qkv_out;                                              // tail 0: f16 [total, 768], q pre-scaled by dh^-0.5
+  int n_punc; float* logits; int32_t* p;                        // tail 1: logits [total, n_punc] / p [total]: either may be null
+};
+void launch_punc_rows(hipStream_t s, const PuncRowsLaunch& a);
+struct PuncAttnLaunch { const half_t* qkv; const int64_t* off; int B; half_t* ctx; };      // ctx f16 [total, 256]
+void launch_punc_attn(hipStream_t s, const PuncAttnLaunch& a);
+// the cut rule of the text loop on p (edited in place): last [B] != 0 marks a text's last window; cut [B]
+struct PuncCutLaunch {
+  int32_t* p; const int64_t* off; const int32_t* last; int B; int32_t* cut;
+  int id_none, id_comma, id_period, id_question, id_pause, sentence_end_id, comma_window, hard_window;
+};
+void launch_punc_cut(hipStream_t s, const PuncCutLaunch& a);
+
 }  // namespace pf

@@ -1,0 +1,397 @@
+// punc.cpp — the CT-Transformer punctuation model on the host (punc.h): the container loader, the float64 twins of
+// k_punc.hip and of the text loop, and the builder of the kernel's weight image.  Uses no device.
+#include "punc.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <map>
+
+#include "hostutil.h"
+#include "json.h"
+
+namespace pf {
+
+namespace {
+
+constexpr int64_t kAlignBytes = 256;
+constexpr double kLnEps = 1e-12;                       // FunASR's LayerNorm(nout, eps = 1e-12)
+
+struct RawTensor { const char* p; std::vector<int64_t> shape; int64_t numel; bool u8; };
+
+void bad(const std::string& m) { throw Error(PF_ERR_INVALID_ARG, "punc model: " + m); }
+
+std::vector<float> take(const std::map<std::string, RawTensor>& ts, const std::string& name, std::vector<int64_t> shape) {
+  auto it = ts.find(name);
+  if (it == ts.end()) bad("tensor '" + name + "' is missing");
+  if (it->second.u8) bad("tensor '" + name + "' is not f32");
+  if (it->second.shape != shape) bad("tensor '" + name + "' has the wrong shape");
+  std::vector<float> v((size_t)it->second.numel);
+  std::memcpy(v.data(), it->second.p, v.size() * 4);                 // (the file's data section need not be 4-aligned in memory)
+  for (float x : v)
+    if (!std::isfinite(x)) bad("tensor '" + name + "' holds a value that is not finite");
+  return v;
+}
+
+// oracle/model.py sinusoidal_pe in its own float32 steps: positions 1 .. T, [sin || cos].  exp, sin and cos are taken in
+// double and rounded once (tests/punc_ref.py does the same): numpy's float32 forms of them are not one function on every host.
+void sinusoidal_pe(int T, int D, std::vector<float>& pe) {
+  const int half = D / 2;
+  const float inc = (float)(std::log(10000.0) / (double)(half - 1));
+  std::vector<float> inv((size_t)half);
+  for (int i = 0; i < half; ++i) inv[(size_t)i] = (float)std::exp((double)((float)i * (-inc)));
+  pe.assign((size_t)T * D, 0.f);
+  for (int t = 0; t < T; ++t)
+    for (int i = 0; i < half; ++i) {
+      const float st = (float)(t + 1) * inv[(size_t)i];
+      pe[(size_t)t * D + i] = (float)std::sin((double)st);
+      pe[(size_t)t * D + half + i] = (float)std::cos((double)st);
+    }
+}
+
+void build_image(PuncModel& m) {
+  std::vector<char>& img = m.image;
+  img.clear();
+  const int D = m.d_model;
+  std::vector<float> pe;
+  sinusoidal_pe(PF_PUNC_MAX_WINDOW, D, pe);
+  m.pe_off = add_floats(img, pe.data(), PF_PUNC_MAX_WINDOW, D, D);
+  m.embed_off = round_up((int64_t)img.size(), kAlignBytes);
+  img.resize((size_t)(m.embed_off + (int64_t)m.vocab * D * 2), 0);
+  {
+    half_t* e = reinterpret_cast<half_t*>(img.data() + m.embed_off);
+    for (size_t i = 0; i < m.embed.size(); ++i) e[i] = (half_t)m.embed[i];           // rounding point R0e
+  }
+  std::vector<float> taps((size_t)m.kernel * D);
+  for (const PuncModel::Layer& L : m.layers) {
+    PuncModel::LayerImg g;
+    g.n1_g = add_floats(img, L.n1_g.data(), 1, D, D);
+    g.n1_b = add_floats(img, L.n1_b.data(), 1, D, D);
+    g.qkv = add_gemm(img, L.qkv_w, &L.qkv_b, 3 * D, D);
+    for (int c = 0; c < D; ++c)
+      for (int j = 0; j < m.kernel; ++j) taps[(size_t)j * D + c] = L.fsmn[(size_t)c * m.kernel + j];
+    g.taps = add_floats(img, taps.data(), m.kernel, D, D);
+    g.out = add_gemm(img, L.out_w, &L.out_b, D, D);
+    g.n2_g = add_floats(img, L.n2_g.data(), 1, D, D);
+    g.n2_b = add_floats(img, L.n2_b.data(), 1, D, D);
+    g.w1 = add_gemm(img, L.w1_w, &L.w1_b, m.ffn, D);
+    g.w2 = add_gemm(img, L.w2_w, &L.w2_b, D, m.ffn);
+    m.limg.push_back(g);
+  }
+  m.after_g_off = add_floats(img, m.after_g.data(), 1, D, D);
+  m.after_b_off = add_floats(img, m.after_b.data(), 1, D, D);
+  m.dec = add_gemm(img, m.dec_w, &m.dec_b, m.n_punc, D);
+}
+
+std::shared_ptr<const PuncModel> parse(const char* data, int64_t nbytes) {
+  if (!data || nbytes < 16) bad("image too small");
+  if (std::memcmp(data, "PFW1", 4) != 0) bad("bad magic (expected a PFW1 container)");
+  uint64_t hlen = 0;
+  std::memcpy(&hlen, data + 8, 8);
+  if (hlen > (uint64_t)nbytes - 16u) bad("truncated header");
+  Json j = JsonParser(data + 16, (size_t)hlen).parse();
+  const Json* jc = j.get("config");
+  const Json* jt = j.get("tensors");
+  if (!jc || jc->type != Json::Obj || !jt || jt->type != Json::Arr) bad("the header lacks config / tensors");
+  if (jc->str_or("kind", "") != "cttransformer") bad("the container's kind is not \"cttransformer\"");
+  auto dim = [&](const char* k) { return jc->int_or(k, -1, INT32_MIN, INT32_MAX); };
+  auto m = std::make_shared<PuncModel>();
+  const int64_t V = dim("vocab"), D = dim("d_model"), H = dim("heads"), F = dim("ffn"), K = dim("kernel"), NL = dim("n_layers");
+  if (V < 1 || D < 1 || H < 1 || F < 1 || K < 1 || NL < 1) bad("a dimension is missing or not positive");
+  if (V > ((int64_t)1 << 24)) bad("the vocabulary is larger than 2^24 words");
+  const Json* jp = jc->get("punc_list");
+  if (!jp || jp->type != Json::Arr) bad("punc_list is missing");
+  for (const Json& s : jp->arr) {
+    if (s.type != Json::Str || s.str.empty()) bad("punc_list holds an entry that is no non-empty string");
+    if (std::find(m->punc_list.begin(), m->punc_list.end(), s.str) != m->punc_list.end()) bad("punc_list names a mark twice");
+    m->punc_list.push_back(s.str);
+  }
+  const int64_t P = (int64_t)m->punc_list.size();
+  PF_CHECK(D == kPuncDModel && H == kPuncHeads && F % 256 == 0 && F <= kPuncMaxFfn && K % 2 == 1 && K <= kPuncMaxKernel &&
+               NL <= kPuncMaxLayers && P >= 2 && P <= kPuncMaxClasses,
+           PF_ERR_UNSUPPORTED,
+           "punc model: a dimension is beyond what the kernels are built for (d_model 256, heads 8, ffn a multiple of 256 up to "
+           "4096, kernel odd up to 31, layers 1 .. 8, classes 2 .. 32)");
+  auto find = [&](const char* s) {
+    auto it = std::find(m->punc_list.begin(), m->punc_list.end(), std::string(s));
+    return it == m->punc_list.end() ? -1 : (int)(it - m->punc_list.begin());
+  };
+  m->id_unk = find("<unk>"); m->id_none = find("_"); m->id_comma = find("\xEF\xBC\x8C"); m->id_period = find("\xE3\x80\x82");
+  m->id_question = find("\xEF\xBC\x9F"); m->id_pause = find("\xE3\x80\x81");
+  if (m->id_unk < 0 || m->id_none < 0) bad("punc_list lacks \"<unk>\" or \"_\"");
+  const int64_t se = dim("sentence_end_id");
+  if (se < 0 || se >= P) bad("sentence_end_id is outside punc_list");
+  m->vocab = (int)V; m->d_model = (int)D; m->heads = (int)H; m->ffn = (int)F; m->kernel = (int)K; m->n_layers = (int)NL;
+  m->n_punc = (int)P; m->sentence_end_id = (int)se;
+
+  const int64_t data_off = round_up((int64_t)(16 + hlen), kAlignBytes);
+  const int64_t data_bytes = nbytes - data_off;
+  if (data_bytes < 0) bad("truncated data section");
+  std::map<std::string, RawTensor> ts;
+  for (const Json& t : jt->arr) {
+    if (t.type != Json::Obj) bad("a tensor entry is no object");
+    const std::string name = t.str_or("name", "");
+    const std::string dt = t.str_or("dtype", "f32");
+    if (dt != "f32" && dt != "u8") bad("tensor '" + name + "' is neither f32 nor u8");
+    const int64_t off = t.int_or("offset", -1), nb = t.int_or("nbytes", -1);
+    if (off < 0 || nb < 0 || off > data_bytes || nb > data_bytes - off) bad("the extent of tensor '" + name + "' lies outside the file");
+    RawTensor r{data + data_off + off, {}, 1, dt == "u8"};
+    const Json* sh = t.get("shape");
+    if (!sh || sh->type != Json::Arr) bad("tensor '" + name + "' has no shape");
+    for (const Json& d : sh->arr) {
+      if (d.type != Json::Num || !(d.num >= 1.0 && d.num <= 1073741824.0) || d.num != (double)(int64_t)d.num) bad("bad dimension in the shape of '" + name + "'");
+      r.shape.push_back((int64_t)d.num);
+      if (r.numel > ((int64_t)1 << 31) / (int64_t)d.num) bad("the shape of '" + name + "' overflows");
+      r.numel *= (int64_t)d.num;
+    }
+    if (r.numel * (r.u8 ? 1 : 4) != nb) bad("shape / nbytes mismatch for '" + name + "'");
+    ts[name] = r;
+  }
+  {
+    auto it = ts.find("vocab");
+    if (it == ts.end() || !it->second.u8 || it->second.shape.size() != 1) bad("the u8 tensor 'vocab' is missing");
+    const std::string all(it->second.p, (size_t)it->second.numel);
+    size_t pos = 0;
+    while (pos <= all.size()) {
+      size_t e = all.find('\n', pos);
+      if (e == std::string::npos) e = all.size();
+      m->words.push_back(all.substr(pos, e - pos));
+      pos = e + 1;
+    }
+    if ((int64_t)m->words.size() != V) bad("'vocab' does not hold `vocab` words");
+    m->word_id.reserve(m->words.size() * 2);
+    for (size_t i = 0; i < m->words.size(); ++i) {
+      if (m->words[i].empty()) bad("'vocab' holds an empty word");
+      if (!m->word_id.emplace(m->words[i], (int32_t)i).second) bad("'vocab' holds a word twice");
+    }
+    auto u = m->word_id.find("<unk>");
+    if (u == m->word_id.end()) bad("'vocab' lacks \"<unk>\"");
+    m->unk_word = u->second;
+  }
+  m->embed = take(ts, "embed.weight", {V, D});
+  for (int l = 0; l < (int)NL; ++l) {
+    const std::string p = "layers." + std::to_string(l) + ".";
+    PuncModel::Layer y;
+    y.n1_g = take(ts, p + "norm1.weight", {D}); y.n1_b = take(ts, p + "norm1.bias", {D});
+    y.qkv_w = take(ts, p + "attn.qkv.weight", {3 * D, D}); y.qkv_b = take(ts, p + "attn.qkv.bias", {3 * D});
+    y.fsmn = take(ts, p + "attn.fsmn.weight", {D, K});
+    y.out_w = take(ts, p + "attn.out.weight", {D, D}); y.out_b = take(ts, p + "attn.out.bias", {D});
+    y.n2_g = take(ts, p + "norm2.weight", {D}); y.n2_b = take(ts, p + "norm2.bias", {D});
+    y.w1_w = take(ts, p + "ffn.w1.weight", {F, D}); y.w1_b = take(ts, p + "ffn.w1.bias", {F});
+    y.w2_w = take(ts, p + "ffn.w2.weight", {D, F}); y.w2_b = take(ts, p + "ffn.w2.bias", {D});
+    m->layers.push_back(std::move(y));
+  }
+  m->after_g = take(ts, "after_norm.weight", {D}); m->after_b = take(ts, "after_norm.bias", {D});
+  m->dec_w = take(ts, "decoder.weight", {P, D}); m->dec_b = take(ts, "decoder.bias", {P});
+  build_image(*m);
+  return m;
+}
+
+// y [T, N] = x [T, K] W^T + b in float64
+void affine64(const std::vector<double>& x, int T, int K, const std::vector<float>& w, const std::vector<float>& b, int N, bool relu,
+              std::vector<double>& y) {
+  y.assign((size_t)T * N, 0.0);
+  for (int t = 0; t < T; ++t)
+    for (int n = 0; n < N; ++n) {
+      double acc = 0.0;
+      const float* wr = w.data() + (size_t)n * K;
+      const double* xr = x.data() + (size_t)t * K;
+      for (int k = 0; k < K; ++k) acc += xr[k] * (double)wr[k];
+      acc += (double)b[(size_t)n];
+      y[(size_t)t * N + n] = (relu && acc < 0.0) ? 0.0 : acc;
+    }
+}
+
+void norm64(const std::vector<double>& x, int T, int D, const std::vector<float>& g, const std::vector<float>& b, std::vector<double>& y) {
+  y.assign((size_t)T * D, 0.0);
+  for (int t = 0; t < T; ++t) {
+    const double* r = x.data() + (size_t)t * D;
+    double mu = 0.0, var = 0.0;
+    for (int c = 0; c < D; ++c) mu += r[c];
+    mu /= D;
+    for (int c = 0; c < D; ++c) var += (r[c] - mu) * (r[c] - mu);
+    var /= D;
+    const double inv = 1.0 / std::sqrt(var + kLnEps);
+    for (int c = 0; c < D; ++c) y[(size_t)t * D + c] = (r[c] - mu) * inv * (double)g[(size_t)c] + (double)b[(size_t)c];
+  }
+}
+
+bool one_byte(const std::string& text, const PuncWord& w) { return ((unsigned char)text[(size_t)w.begin] & 0x80) == 0; }
+
+}  // namespace
+
+std::shared_ptr<const PuncModel> punc_model_from_memory(const void* data, int64_t nbytes) {
+  try {
+    return parse(static_cast<const char*>(data), nbytes);
+  } catch (const Error& e) {
+    if (e.code == PF_ERR_INVALID_ARG || e.code == PF_ERR_UNSUPPORTED) throw;
+    throw Error(PF_ERR_INVALID_ARG, std::string("punc model: ") + e.what());      // a header that is no JSON, a number out of range
+  }
+}
+
+std::shared_ptr<const PuncModel> punc_model_load(const std::string& path) {
+  std::vector<char> file;
+  read_binary_file(path, file);
+  return punc_model_from_memory(file.data(), (int64_t)file.size());
+}
+
+std::vector<PuncWord> host_punc_words(const PuncModel& m, const std::string& text) {
+  std::vector<PuncWord> out;
+  const size_t n = text.size();
+  PF_CHECK(n < ((size_t)1 << 31), PF_ERR_CAPACITY, "punc: the text is longer than 2^31 bytes");
+  auto emit = [&](size_t b, size_t e) {
+    auto it = m.word_id.find(text.substr(b, e - b));
+    out.push_back(PuncWord{it == m.word_id.end() ? m.unk_word : it->second, (int32_t)b, (int32_t)e});
+  };
+  size_t i = 0;
+  while (i < n) {
+    const unsigned char c = (unsigned char)text[i];
+    if (c == 0x20 || (c >= 0x09 && c <= 0x0D)) { ++i; continue; }
+    size_t e = i + 1;
+    if (c < 0x80) {                                          // a maximal run of one-byte characters that are no whitespace
+      while (e < n) {
+        const unsigned char d = (unsigned char)text[e];
+        if (d >= 0x80 || d == 0x20 || (d >= 0x09 && d <= 0x0D)) break;
+        ++e;
+      }
+    } else {                                                 // one character: its lead byte and the continuation bytes behind it
+      while (e < n && ((unsigned char)text[e] & 0xC0) == 0x80) ++e;
+    }
+    emit(i, e);
+    i = e;
+  }
+  return out;
+}
+
+void host_punc_logits(const PuncModel& m, const int32_t* ids, int T, double* logits) {
+  PF_CHECK(T >= 0 && T <= PF_PUNC_MAX_WINDOW, PF_ERR_INVALID_ARG, "punc: a window holds 0 .. PF_PUNC_MAX_WINDOW ids");
+  if (T == 0) return;
+  const int D = m.d_model, H = m.heads, dh = D / H, K = m.kernel, left = (K - 1) / 2;
+  std::vector<float> pe;
+  sinusoidal_pe(T, D, pe);
+  std::vector<double> x((size_t)T * D), xn, qkv, att, h, y;
+  const float scale = (float)std::sqrt((double)D);
+  for (int t = 0; t < T; ++t) {
+    PF_CHECK(ids[t] >= 0 && ids[t] < m.vocab, PF_ERR_INVALID_ARG, "punc: a word id is outside the vocabulary");
+    for (int c = 0; c < D; ++c) {
+      const float a = m.embed[(size_t)ids[t] * D + c] * scale;          // Mul, then Add: separate float32 roundings
+      x[(size_t)t * D + c] = (double)(float)(a + pe[(size_t)t * D + c]);
+    }
+  }
+  const double qs = 1.0 / std::sqrt((double)dh);
+  std::vector<double> ctx((size_t)T * D), s((size_t)T);
+  for (const PuncModel::Layer& L : m.layers) {
+    norm64(x, T, D, L.n1_g, L.n1_b, xn);
+    affine64(xn, T, D, L.qkv_w, L.qkv_b, 3 * D, false, qkv);
+    for (int hd = 0; hd < H; ++hd)
+      for (int t = 0; t < T; ++t) {
+        double mx = -INFINITY;
+        bool nan = false;
+        for (int u = 0; u < T; ++u) {
+          double a = 0.0;
+          for (int c = 0; c < dh; ++c) a += qkv[(size_t)t * 3 * D + hd * dh + c] * qs * qkv[(size_t)u * 3 * D + D + hd * dh + c];
+          s[(size_t)u] = a;
+          if (a != a) nan = true;
+          mx = std::max(mx, a);
+        }
+        double sum = 0.0;
+        for (int u = 0; u < T; ++u) { s[(size_t)u] = nan ? NAN : std::exp(s[(size_t)u] - mx); sum += s[(size_t)u]; }
+        for (int c = 0; c < dh; ++c) {
+          double a = 0.0;
+          for (int u = 0; u < T; ++u) a += s[(size_t)u] * qkv[(size_t)u * 3 * D + 2 * D + hd * dh + c];
+          ctx[(size_t)t * D + hd * dh + c] = a / sum;
+        }
+      }
+    affine64(ctx, T, D, L.out_w, L.out_b, D, false, att);
+    for (int t = 0; t < T; ++t)
+      for (int c = 0; c < D; ++c) {
+        double f = qkv[(size_t)t * 3 * D + 2 * D + c];
+        for (int j = 0; j < K; ++j) {
+          const int u = t + j - left;
+          if (u >= 0 && u < T) f += (double)L.fsmn[(size_t)c * K + j] * qkv[(size_t)u * 3 * D + 2 * D + c];
+        }
+        x[(size_t)t * D + c] += att[(size_t)t * D + c] + f;
+      }
+    norm64(x, T, D, L.n2_g, L.n2_b, xn);
+    affine64(xn, T, D, L.w1_w, L.w1_b, m.ffn, true, h);
+    affine64(h, T, m.ffn, L.w2_w, L.w2_b, D, false, y);
+    for (size_t i = 0; i < x.size(); ++i) x[i] += y[i];
+  }
+  norm64(x, T, D, m.after_g, m.after_b, xn);
+  affine64(xn, T, D, m.dec_w, m.dec_b, m.n_punc, false, y);
+  std::memcpy(logits, y.data(), y.size() * 8);
+}
+
+void host_punc_argmax(const PuncModel& m, const double* logits, int T, int32_t* p) {
+  for (int t = 0; t < T; ++t) {
+    double best = -INFINITY;
+    int at = 0;
+    for (int i = 0; i < m.n_punc; ++i)
+      if (logits[(size_t)t * m.n_punc + i] >= best) { best = logits[(size_t)t * m.n_punc + i]; at = i; }
+    p[t] = at;
+  }
+}
+
+int host_punc_cut(const PuncModel& m, int32_t* p, int n, bool last) {
+  if (n <= 0) return -1;
+  if (last) {
+    if (p[n - 1] == m.id_none || (m.id_comma >= 0 && p[n - 1] == m.id_comma) || (m.id_pause >= 0 && p[n - 1] == m.id_pause))
+      p[n - 1] = m.sentence_end_id;
+    return n - 1;
+  }
+  int cut = -1, comma = -1;
+  for (int i = n - 2; i >= 2; --i) {
+    if ((m.id_period >= 0 && p[i] == m.id_period) || (m.id_question >= 0 && p[i] == m.id_question)) { cut = i; break; }
+    if (comma < 0 && m.id_comma >= 0 && p[i] == m.id_comma) comma = i;
+  }
+  const bool by_comma = cut < 0 && n > kPuncCommaWindow && comma >= 0;
+  if (by_comma) cut = comma;
+  // the hard cut: no cut, or a tail behind it that with the next mini-sentence would pass PF_PUNC_MAX_WINDOW
+  if (n > kPuncHardWindow && (cut < 0 || n - 1 - cut > kPuncHardWindow)) return n - 1;
+  if (by_comma) p[cut] = m.sentence_end_id;
+  return cut;
+}
+
+void host_punc_ids(const PuncModel& m, const int32_t* ids, int64_t n, int32_t* punc_ids, std::vector<std::pair<int32_t, int32_t>>* windows) {
+  std::vector<int32_t> win, p;
+  std::vector<double> z;
+  int64_t done = 0;
+  const int64_t n_mini = (n + kPuncMini - 1) / kPuncMini;
+  for (int64_t mi = 0; mi < n_mini; ++mi) {
+    const int64_t b = mi * kPuncMini, e = std::min<int64_t>(n, b + kPuncMini);
+    win.insert(win.end(), ids + b, ids + e);
+    const int T = (int)win.size();
+    z.assign((size_t)T * m.n_punc, 0.0);
+    p.assign((size_t)T, 0);
+    host_punc_logits(m, win.data(), T, z.data());
+    host_punc_argmax(m, z.data(), T, p.data());
+    const int cut = host_punc_cut(m, p.data(), T, mi == n_mini - 1);
+    if (windows) windows->push_back({(int32_t)T, (int32_t)cut});
+    for (int i = 0; i <= cut; ++i) punc_ids[done++] = p[(size_t)i];
+    win.erase(win.begin(), win.begin() + (cut + 1));
+  }
+}
+
+std::string host_punc_assemble(const PuncModel& m, const std::string& text, const std::vector<PuncWord>& words, const int32_t* punc_ids,
+                               std::vector<int32_t>* sent_end) {
+  std::string out;
+  if (sent_end) sent_end->clear();
+  for (size_t i = 0; i < words.size(); ++i) {
+    const bool ascii = one_byte(text, words[i]);
+    if (i > 0 && ascii && one_byte(text, words[i - 1])) out += ' ';
+    out.append(text, (size_t)words[i].begin, (size_t)(words[i].end - words[i].begin));
+    const int p = punc_ids[i];
+    PF_CHECK(p >= 0 && p < m.n_punc, PF_ERR_INVALID_ARG, "punc: a punctuation id is outside punc_list");
+    if (p != m.id_none && p != m.id_unk) {
+      if (ascii && (p == m.id_comma || p == m.id_pause)) out += ',';
+      else if (ascii && p == m.id_period) out += '.';
+      else if (ascii && p == m.id_question) out += '?';
+      else out += m.punc_list[(size_t)p];
+    }
+    const bool end = (m.id_period >= 0 && p == m.id_period) || (m.id_question >= 0 && p == m.id_question);
+    if (sent_end && (end || i + 1 == words.size())) sent_end->push_back((int32_t)i + 1);
+  }
+  return out;
+}
+
+}  // namespace pf

@@ -1534,6 +1534,74 @@ Recognizer::~Recognizer() {
   g_live.erase(uid_);
 }
 
+void Recognizer::SetPuncModel(const std::string& pfw_path) {
+  if (disposed_) throw Error(PF_ERR_DISPOSED, "OfflineRecognizer");
+  std::shared_ptr<const PuncModel> pm;
+  if (!pfw_path.empty()) pm = punc_model_load(pfw_path);                     // throws before anything changes
+  std::vector<std::shared_ptr<Engine>> es;
+  {
+    std::lock_guard<std::mutex> lk(mu_);
+    if (disposed_ || engines_.empty()) throw Error(PF_ERR_DISPOSED, "OfflineRecognizer");
+    es = engines_;
+  }
+  { std::lock_guard<std::mutex> lk(punc_mu_); punc_model_ = pm; }            // (Punctuate applies it under its lease, which covers
+  for (auto& e : es) {                                                       //  an engine that joins the pool later)
+    std::lock_guard<std::mutex> lk(e->mutex());
+    e->set_punc_model(pm);
+  }
+}
+
+// every stream's final text through the punctuation model: words on the host, ONE pf_engine_punctuate over all streams of the
+// call, the assembly on the host
+void Recognizer::Punctuate(const std::vector<Stream*>& streams, const std::vector<ResultEntity>& out) {
+  std::shared_ptr<const PuncModel> pm;
+  { std::lock_guard<std::mutex> lk(punc_mu_); pm = punc_model_; }
+  for (Stream* s : streams) { s->Punctuated.clear(); s->PuncIds.clear(); s->Sentences.clear(); }
+  if (!pm || out.size() != streams.size()) return;
+  std::vector<std::vector<PuncWord>> words(streams.size());
+  std::vector<int32_t> ids, lens;
+  for (size_t i = 0; i < streams.size(); ++i) {
+    words[i] = host_punc_words(*pm, out[i].Text);
+    for (const PuncWord& w : words[i]) ids.push_back(w.id);
+    lens.push_back((int32_t)words[i].size());
+  }
+  std::vector<int32_t> p(ids.size());
+  for (size_t at = 0; at < streams.size(); at += PF_PUNC_MAX_BATCH) {        // (a call of more streams than a batch holds: in turns)
+    const size_t n = std::min<size_t>(PF_PUNC_MAX_BATCH, streams.size() - at);
+    size_t first = 0;
+    for (size_t i = 0; i < at; ++i) first += (size_t)lens[i];
+    Lease lease = acquire();
+    if (lease->punc_model() != pm) lease->set_punc_model(pm);
+    lease->punctuate(ids.data() + first, lens.data() + at, (int)n, p.data() + first);
+  }
+  size_t first = 0;
+  for (size_t i = 0; i < streams.size(); ++i) {
+    Stream* s = streams[i];
+    const size_t n = words[i].size();
+    s->PuncIds.assign(p.begin() + (std::ptrdiff_t)first, p.begin() + (std::ptrdiff_t)(first + n));
+    std::vector<int32_t> ends;
+    s->Punctuated = host_punc_assemble(*pm, out[i].Text, words[i], s->PuncIds.data(), &ends);
+    const TsList& ts = out[i].Timestamps;
+    bool timed = ts.size() == n, any = false;                // one entry per word, and not the {0, 0} placeholders a model
+    for (size_t k = 0; timed && k < n; ++k) {                // without timestamps fills in (OfflineRecognizer.cs:151,188)
+      timed = ts[k].size() >= 2;
+      any = any || (timed && (ts[k][0] != 0 || ts[k][1] != 0));
+    }
+    timed = timed && any;
+    int begin = 0;
+    for (int32_t e : ends) {
+      Stream::Sentence z;
+      z.word_begin = begin; z.word_end = e; z.has_time = timed;
+      if (timed) { z.begin_ms = ts[(size_t)begin][0]; z.end_ms = ts[(size_t)e - 1][1]; }
+      const std::vector<PuncWord> part(words[i].begin() + begin, words[i].begin() + e);
+      z.text = host_punc_assemble(*pm, out[i].Text, part, s->PuncIds.data() + begin, nullptr);
+      s->Sentences.push_back(std::move(z));
+      begin = e;
+    }
+    first += n;
+  }
+}
+
 void Recognizer::GetResults(const std::vector<Stream*>& streams) {
   bool vad;
   { std::lock_guard<std::mutex> lk(vad_mu_); vad = vad_on_; }
@@ -1560,7 +1628,16 @@ void Recognizer::GetResults(const std::vector<Stream*>& streams) {
     for (auto it = t_results.begin(); it != t_results.end();)
       it = g_live.count(it->first) ? std::next(it) : t_results.erase(it);
   }
-  t_results[uid_] = std::move(out);
+  std::vector<ResultEntity>& kept = t_results[uid_];
+  kept = std::move(out);
+  // punctuation comes last and outside the forward's clock: the recognition results are stored, so an error in this opt-in
+  // step reaches the caller without taking them away (the streams then carry no punctuated text)
+  try {
+    Punctuate(streams, kept);
+  } catch (...) {
+    for (Stream* s : streams) { s->Punctuated.clear(); s->PuncIds.clear(); s->Sentences.clear(); }
+    throw;
+  }
 }
 
 const std::vector<ResultEntity>& Recognizer::results_of_this_thread() {

@@ -168,6 +168,13 @@ class Stream {
   // Tokens / Scores / Timestamps, and its own text.  Empty without SetVad.
   struct Segment { int begin_ms = 0, end_ms = 0, batch = 0, row = 0, tok_begin = 0, tok_end = 0; std::string text; };
   std::vector<Segment> Segments;
+  // punctuation (Recognizer::SetPuncModel): of the last GetResults, the punctuated form of its Text, the mark of every word and
+  // the sentences: words [word_begin, word_end), their text, and [begin_ms, end_ms] when the result has exactly one Timestamps
+  // entry per word (has_time).  Empty without a model.
+  struct Sentence { int word_begin = 0, word_end = 0, begin_ms = 0, end_ms = 0; bool has_time = false; std::string text; };
+  std::string Punctuated;
+  std::vector<int32_t> PuncIds;
+  std::vector<Sentence> Sentences;
   bool borrowed = false;                                      // dev_audio points INTO another stream's buffer (a piece): never freed here
   void RemoveChunk();                                         // OfflineStream.cs:69-79
   bool disposed = false;
@@ -223,6 +230,10 @@ class Recognizer : public std::enable_shared_from_this<Recognizer> {
   // The FSMN-VAD model score for SetVad's segmentation (paraformer_hip.h "Voice-activity segmentation, model score"): a `.pfw`
   // of kind "fsmnvad", loaded once and attached to every engine of the pool, present and future; "" clears.  Inert until SetVad.
   void SetVadModel(const std::string& pfw_path);
+  // Punctuation of every GetResults that follows (paraformer_hip.h "Punctuation"): a `.pfw` of kind "cttransformer", loaded
+  // once; "" clears.  GetResults then punctuates each stream's final Text (with SetVad: the stitched text), all streams of the
+  // call in one pf_engine_punctuate on a leased engine, and keeps the result on the stream; Text / Tokens / Timestamps stay.
+  void SetPuncModel(const std::string& pfw_path);
   bool disposed() const { return disposed_.load(); }
   // engine 0 (nullptr once disposed): what pf_recognizer_engine hands out; callers lock engine->mutex() themselves
   std::shared_ptr<Engine> engine() { std::lock_guard<std::mutex> lk(mu_); return engines_.empty() ? nullptr : engines_[0]; }
@@ -263,6 +274,9 @@ class Recognizer : public std::enable_shared_from_this<Recognizer> {
  private:
   void Forward(const std::vector<Stream*>& streams);          // :118-198
   void ForwardLong(const std::vector<Stream*>& streams, std::vector<ResultEntity>& out);   // GetResults with SetVad
+  void Punctuate(const std::vector<Stream*>& streams, const std::vector<ResultEntity>& out);
+  std::mutex punc_mu_;                                        // guards punc_model_
+  std::shared_ptr<const PuncModel> punc_model_;
   std::mutex vad_mu_;                                         // guards the five below
   std::shared_ptr<const VadModel> vad_model_;
   bool vad_on_ = false; pf_vad_config vad_cfg_{}; int vad_batch_max_ = 32; int64_t vad_budget_ = 96000; std::string vad_sep_;

@@ -31,6 +31,8 @@ std::vector<float> take(const std::map<std::string, RawTensor>& ts, const std::s
   return v;
 }
 
+}  // namespace
+
 // W [N, K] -> the MFMA fragments of vadnet.h, bias [N] (or none) -> fp32 [Npad]
 VadGemm add_gemm(std::vector<char>& img, const std::vector<float>& w, const std::vector<float>* bias, int N, int K) {
   VadGemm g;
@@ -62,6 +64,8 @@ int64_t add_floats(std::vector<char>& img, const float* src, int64_t rows, int64
     for (int64_t c = 0; c < cols; ++c) d[r * ld + c] = src[r * cols + c];
   return off;
 }
+
+namespace {
 
 void build_image(VadModel& m) {
   std::vector<char>& img = m.image;

@@ -18,6 +18,10 @@ constexpr int kVadMaxWidth = 512, kVadMaxProj = 256, kVadMaxLayers = 8, kVadMaxR
 // (r = lane & 31, h = lane >> 5) holding W[32 nt + r][16 ks + 8 h + j]; bias fp32 [Npad] (zeros where the product has none)
 struct VadGemm { int64_t w_off = 0, b_off = 0; int N = 0, K = 0, Npad = 0, Kpad = 0; };
 
+// the builders of such an image (also used by punc.cpp): both append at the next 256-byte boundary and return the offset(s)
+VadGemm add_gemm(std::vector<char>& img, const std::vector<float>& w, const std::vector<float>* bias, int N, int K);
+int64_t add_floats(std::vector<char>& img, const float* src, int64_t rows, int64_t cols, int64_t ld);
+
 struct VadModel {
   int input_dim = 0, affine_dim = 0, linear_dim = 0, proj_dim = 0, output_dim = 0, n_layers = 0, lorder = 0, lstride = 0, lfr_m = 0;
   std::vector<int32_t> sil_ids;

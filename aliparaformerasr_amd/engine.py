@@ -437,6 +437,103 @@ def host_vad_model_levels(model: VadModel, rows) -> np.ndarray:
     return out
 
 
+PUNC_MODEL_DIMS = ("vocab", "d_model", "heads", "ffn", "kernel", "n_layers", "n_punc", "sentence_end_id", "unk_word",
+                   "id_unk", "id_none", "id_comma", "id_period", "id_question", "id_pause")
+
+
+class PuncModel:
+    """A CT-Transformer punctuation model: a `.pfw` of kind "cttransformer" loaded and validated on the host
+    (pf_punc_model_load / pf_punc_model_from_memory; see "Punctuation" in the header).  Release with close() (an engine that
+    attached it keeps its own reference)."""
+
+    def __init__(self, handle):
+        self._lib = N.load()
+        self._h = handle
+        d, ib = np.zeros(16, np.int32), C.c_int64()
+        N.check(self._lib.pf_punc_model_info(self._h, _i32p(d), ib))
+        self.dims = dict(zip(PUNC_MODEL_DIMS, d.tolist()))
+        self.image_bytes = ib.value
+
+    def close(self):
+        if self._h is not None:
+            self._lib.pf_punc_model_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def load_punc_model(source) -> PuncModel:
+    """A `.pfw` of kind "cttransformer" from a path or from bytes -> PuncModel."""
+    h = C.c_void_p()
+    if isinstance(source, (bytes, bytearray, memoryview)):
+        buf = bytes(source)
+        N.check(N.load().pf_punc_model_from_memory(C.cast(C.c_char_p(buf), C.c_void_p), len(buf), C.byref(h)))
+    else:
+        N.check(N.load().pf_punc_model_load(str(source).encode("utf-8"), C.byref(h)))
+    return PuncModel(h)
+
+
+def host_punc_words(model: PuncModel, text: str):
+    """The words of a text (pf_host_punc_words): (ids int32 [n], the words as strings)."""
+    raw = text.encode("utf-8")
+    n = C.c_int32()
+    N.check(N.load().pf_host_punc_words(model._h, raw, None, None, None, 0, n))
+    ids, b, e = (np.zeros(max(n.value, 1), np.int32) for _ in range(3))
+    N.check(N.load().pf_host_punc_words(model._h, raw, _i32p(ids), _i32p(b), _i32p(e), n.value, n))
+    return ids[: n.value].copy(), [raw[b[i]: e[i]].decode("utf-8") for i in range(n.value)]
+
+
+def host_punc_logits(model: PuncModel, ids) -> np.ndarray:
+    """The network on ONE window in host code, float64 (pf_host_punc_logits): ids [T] -> [T, n_punc]."""
+    a = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+    out = np.zeros((a.size, model.dims["n_punc"]), np.float64)
+    N.check(N.load().pf_host_punc_logits(model._h, _i32p(a), a.size, _dp(out)))
+    return out
+
+
+def host_punc_cut(model: PuncModel, p, last: bool):
+    """The cut rule and the last-window edits on one window's p (pf_host_punc_cut): (cut, the edited p)."""
+    a = np.array(p, dtype=np.int32).reshape(-1)
+    cut = C.c_int32()
+    N.check(N.load().pf_host_punc_cut(model._h, _i32p(a), a.size, 1 if last else 0, cut))
+    return cut.value, a
+
+
+def host_punc_ids(model: PuncModel, ids):
+    """The text loop over the ids of one text in host code (pf_host_punc_ids): (punc_ids [n], [(window length, cut)])."""
+    a = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+    out = np.zeros(max(a.size, 1), np.int32)
+    cap = a.size // 20 + 2
+    wl, wc, nw = np.zeros(cap, np.int32), np.zeros(cap, np.int32), C.c_int32()
+    N.check(N.load().pf_host_punc_ids(model._h, _i32p(a), a.size, _i32p(out), _i32p(wl), _i32p(wc), cap, nw))
+    return out[: a.size].copy(), list(zip(wl[: nw.value].tolist(), wc[: nw.value].tolist()))
+
+
+def host_punc_assemble(model: PuncModel, text: str, punc_ids):
+    """The output text and its sentences (pf_host_punc_assemble): (text, [one past the last word of each sentence])."""
+    raw = text.encode("utf-8")
+    p = np.ascontiguousarray(punc_ids, dtype=np.int32).reshape(-1)
+    cap = len(raw) + 17 * p.size + 16
+    buf, ln, ns = C.create_string_buffer(cap), C.c_int64(), C.c_int32()
+    se = np.zeros(max(p.size, 1), np.int32)
+    N.check(N.load().pf_host_punc_assemble(model._h, raw, _i32p(p), p.size, buf, cap, ln, _i32p(se), se.size, ns))
+    return buf.raw[: ln.value].decode("utf-8"), se[: ns.value].tolist()
+
+
+def host_punc_text(model: PuncModel, text: str):
+    """Words, loop and assembly on the host (pf_host_punc_text): (the punctuated text, punc_ids [n_words])."""
+    raw = text.encode("utf-8")
+    cap = 18 * len(raw) + 16
+    buf, ln, nw = C.create_string_buffer(cap), C.c_int64(), C.c_int32()
+    p = np.zeros(len(raw) + 1, np.int32)
+    N.check(N.load().pf_host_punc_text(model._h, raw, buf, cap, ln, _i32p(p), p.size, nw))
+    return buf.raw[: ln.value].decode("utf-8"), p[: nw.value].copy()
+
+
 def host_long_plan(lens, batch_max=0, frame_budget=0):
     """The batch plan of long-audio recognition (pf_host_long_plan): ([(batch, row)] per segment, number of batches)."""
     ln = np.ascontiguousarray(lens, dtype=np.int32).reshape(-1)
@@ -642,6 +739,7 @@ class Engine:
         self._hot = False
         self._lm = None
         self._vad_model = None
+        self._punc_model = None
         self._search_w = 0
 
     def close(self):
@@ -1113,6 +1211,68 @@ class Engine:
     def op_vad_model_levels(self, rows_list) -> list:
         """As op_vad_model_logits, the levels [T_b] int32 (pf_op_vad_model_levels)."""
         return self._op_vad_model(rows_list, False)
+
+    def set_punc_model(self, model):
+        """Attaches a PuncModel (pf_engine_set_punc_model); None detaches and frees what the attach and its runs allocated."""
+        N.check(self._lib.pf_engine_set_punc_model(self._h, None if model is None else model._h))
+        self._punc_model = model
+
+    @staticmethod
+    def _punc_batch(ids_list):
+        arrs = [np.ascontiguousarray(a, dtype=np.int32).reshape(-1) for a in ids_list]
+        T = np.ascontiguousarray([a.size for a in arrs] + [0] * (len(arrs) == 0), dtype=np.int32)
+        ids = np.ascontiguousarray(np.concatenate(arrs + [np.zeros(1, np.int32)]))       # (never empty: a valid pointer)
+        off = np.concatenate([[0], np.cumsum(T[: len(arrs)])]).astype(np.int64)
+        return arrs, T, ids, off
+
+    def punctuate(self, ids_list):
+        """The text loop on the device for the texts of ids_list, given as word ids (pf_engine_punctuate): ONE call, a forward per
+        round.  Returns (each text's punc_ids int32, the number of rounds)."""
+        arrs, T, ids, off = self._punc_batch(ids_list)
+        out, rounds = np.zeros(ids.size, np.int32), C.c_int32()
+        N.check(self._lib.pf_engine_punctuate(self._h, _i32p(ids), _i32p(T), len(arrs), _i32p(out), rounds))
+        return [out[off[b]: off[b + 1]].copy() for b in range(len(arrs))], rounds.value
+
+    def punctuate_text(self, texts):
+        """Words on the host, the loop on the device, the assembly on the host: for every text (punctuated text, punc_ids,
+        sentences as [one past the last word])."""
+        m = self._punc_model
+        ids = [host_punc_words(m, t)[0] for t in texts]
+        p, _ = self.punctuate(ids)
+        return [host_punc_assemble(m, t, p[i]) + (p[i],) for i, t in enumerate(texts)]
+
+    def op_punc_logits(self, ids_list, want_x0=False, out=None):
+        """The attached model's launches on caller windows (pf_op_punc_logits): ONE call over all windows of ids_list; returns
+        each window's logits [T_b, n_punc] float32 (and layer 0's input [T_b, d_model] with want_x0).  out: a float32 buffer of
+        at least sum T * n_punc values to store into (tests look at what lies beyond)."""
+        arrs, T, ids, off = self._punc_batch(ids_list)
+        dims = self._punc_model.dims if self._punc_model is not None else {}       # (without a model the call is refused)
+        P, D = dims.get("n_punc", 1), dims.get("d_model", 1)
+        total = int(off[-1])
+        z = np.zeros(max(total, 1) * P, np.float32) if out is None else out
+        x0 = np.zeros((max(total, 1), D), np.float32) if want_x0 else None
+        N.check(self._lib.pf_op_punc_logits(self._h, _i32p(ids), _i32p(T), len(arrs), _fp(z), None if x0 is None else _fp(x0)))
+        zs = [z[off[b] * P: off[b + 1] * P].reshape(-1, P).copy() for b in range(len(arrs))]
+        if want_x0:
+            return zs, [x0[off[b]: off[b + 1]].copy() for b in range(len(arrs))]
+        return zs
+
+    def op_punc_window(self, ids_list, last, want_logits=False):
+        """As op_punc_logits with the cut launch behind it (pf_op_punc_window): last[b] marks a text's last window; returns
+        (each window's p int32 after the edits, cut int32 [B]) and the logits with want_logits."""
+        arrs, T, ids, off = self._punc_batch(ids_list)
+        P = self._punc_model.dims["n_punc"] if self._punc_model is not None else 1      # (without a model the call is refused)
+        total = int(off[-1])
+        lst = np.ascontiguousarray([1 if x else 0 for x in last] + [0] * (len(arrs) == 0), dtype=np.int32)
+        assert len(last) == len(arrs)
+        p, cut = np.zeros(max(total, 1), np.int32), np.zeros(max(len(arrs), 1), np.int32)
+        z = np.zeros((max(total, 1), P), np.float32) if want_logits else None
+        N.check(self._lib.pf_op_punc_window(self._h, _i32p(ids), _i32p(T), _i32p(lst), len(arrs), _i32p(p), _i32p(cut),
+                                            None if z is None else _fp(z)))
+        ps = [p[off[b]: off[b + 1]].copy() for b in range(len(arrs))]
+        if want_logits:
+            return ps, cut[: len(arrs)].copy(), [z[off[b]: off[b + 1]].copy() for b in range(len(arrs))]
+        return ps, cut[: len(arrs)].copy()
 
     def op_vad_segments(self, levels_list, n_mels=80, cfg=None, cap=None, ld=None):
         """The detector's segment kernel on caller levels (pf_op_vad_segments): ONE launch over all the utterances of

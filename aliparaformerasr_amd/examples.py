@@ -1,7 +1,7 @@
 """Command-line harness mirroring AliParaformerAsr.Examples (`-type offline` and `-type online`).
 
     python -m aliparaformerasr_amd.examples -type offline -method batch -base <dir> -model <name> \
-        [-accuracy int8] [-threads 2] [-decode ctc|frames] [-intake host|device] [-nbest N [-topk K] [-beam W | -search W] [-hotboost S] [-lm FILE [-lmweight A] [-lmbonus B] [-lmeos]]] [-align FILE|beam] [-vad [key=value,...] [-vadmodel FILE]] -files a.wav b.wav
+        [-accuracy int8] [-threads 2] [-decode ctc|frames] [-intake host|device] [-nbest N [-topk K] [-beam W | -search W] [-hotboost S] [-lm FILE [-lmweight A] [-lmbonus B] [-lmeos]]] [-align FILE|beam] [-vad [key=value,...] [-vadmodel FILE]] [-punc FILE] -files a.wav b.wav
     python -m aliparaformerasr_amd.examples -type online -method one -base <dir> -model <name> -files a.wav
 
 Mirrors (file:line in /root/reference/AliParaformerAsr.Examples):
@@ -49,6 +49,9 @@ thresholds are unvalidated on real speech.  Not beside -nbest / -align.
 `-vadmodel FILE` (with `-vad`; OfflineRecognizer.SetVadModel) scores the frames with an FSMN-VAD network instead of the
 log-mel energy: FILE is a `.pfw` of kind fsmnvad (`python -m aliparaformerasr_amd.convert vad.onnx out.pfw --kind fsmnvad
 --mvn vad.mvn`); the model's default thresholds (floor_pct=-1, abs_level=9830; unvalidated too) apply unless keys are given.
+`-punc FILE` (OfflineRecognizer.SetPuncModel) punctuates every result on the GPU with a CT-Transformer: FILE is a `.pfw` of kind
+cttransformer; under each result goes a `punctuated: ...` line and one `  [begin-end ms] sentence` line per sentence (without the
+times when the result has no timestamp per word).  Rules and dimensions are stated, not validated on a real model.
 `-align beam` (with `-nbest N -beam W`) aligns the beam search's labelings instead: under each `nbest[i]` line goes
 `align[i] loglik:<...> pairs:[begin,end],...`."""
 from __future__ import annotations
@@ -219,9 +222,17 @@ def read_align_file(path: str) -> list:
     return out
 
 
+def _punc_lines(st):
+    """-punc: the punctuated line, then one line per sentence (with its times where the result has one timestamp per word)"""
+    out = ["punctuated: " + st.Punctuated]
+    for z in st.Sentences:
+        out.append(("  [%d-%d ms] " % tuple(z.Times) if z.Times else "  ") + z.Text)
+    return out
+
+
 def offline_recognizer(method="one", model="paraformer-seaco-large-zh-timestamp-onnx-offline", accuracy="int8",
                        threads=2, files=None, base=None, out=sys.stdout, decode="frames", intake="host", nbest=0, topk=4,
-                       beam=0, align=None, hotboost=0.0, vad=None, lm=None, lmweight=0.5, lmbonus=0.0, lmeos=False, search=0, vadmodel=None):
+                       beam=0, align=None, hotboost=0.0, vad=None, lm=None, lmweight=0.5, lmbonus=0.0, lmeos=False, search=0, vadmodel=None, punc=None):
     from .offline_recognizer import OfflineRecognizer
     base = base or os.getcwd()
     sel = select_model_files(base, model, accuracy)
@@ -253,6 +264,8 @@ def offline_recognizer(method="one", model="paraformer-seaco-large-zh-timestamp-
             rec.SetVadModel(vadmodel)
             vcfg = vad_model_config(**vad["cfg"])
         rec.SetVad(vcfg, vad["batch_max"], vad["frame_budget"], vad["sep"])
+    if punc:
+        rec.SetPuncModel(punc)
     targets = None
     if align:
         rec.SetAlign(True)
@@ -289,7 +302,7 @@ def offline_recognizer(method="one", model="paraformer-seaco-large-zh-timestamp-
 
     def extra_lines(st):
         return (_nbest_lines(st, align == "beam") if nbest else []) + (_align_lines(st) if targets is not None else []) + \
-            (_segment_lines(st) if vad is not None else [])
+            (_segment_lines(st) if vad is not None else []) + (_punc_lines(st) if punc else [])
     print("Recognition results:\r\n", file=out)
     try:
         if method == "one":
@@ -499,6 +512,11 @@ def parse_args(argv, env=None):
             if i >= len(argv) or argv[i].startswith("-"):
                 raise ValueError("-vadmodel takes a .pfw file of kind fsmnvad")
             cfg["vadmodel"] = argv[i]
+        elif a == "-punc":
+            i += 1
+            if i >= len(argv) or argv[i].startswith("-"):
+                raise ValueError("-punc takes a .pfw file of kind cttransformer")
+            cfg["punc"] = argv[i]
         elif a == "-threads":
             try:
                 i += 1
@@ -540,6 +558,8 @@ def parse_args(argv, env=None):
         raise ValueError("-vad is an offline option")
     if "vad" in cfg and ("nbest" in cfg or "align" in cfg):
         raise ValueError("-vad does not go with -nbest or -align")
+    if "punc" in cfg and cfg["recognizerType"] != "offline":
+        raise ValueError("-punc is an offline option")
     if "vadmodel" in cfg and "vad" not in cfg:
         raise ValueError("-vadmodel goes with -vad")
     if cfg.get("align") == "beam" and "beam" not in cfg:
@@ -564,7 +584,7 @@ def main(argv=None):
                            nbest=cfg.get("nbest", 0), topk=cfg.get("topk", 4), beam=cfg.get("beam", 0), align=cfg.get("align"),
                            hotboost=cfg.get("hotboost", 0.0), vad=cfg.get("vad"), lm=cfg.get("lm"), lmweight=cfg.get("lmweight", 0.5),
                            lmbonus=cfg.get("lmbonus", 0.0), lmeos=cfg.get("lmeos", False), search=cfg.get("search", 0),
-                           vadmodel=cfg.get("vadmodel"))
+                           vadmodel=cfg.get("vadmodel"), punc=cfg.get("punc"))
     else:
         print("the recognizer type must be online or offline")
         return 2

@@ -97,6 +97,17 @@ class Alignment:
 
 
 @dataclass
+class Sentence:
+    """OfflineStream.Sentences: one sentence of the punctuated text (OfflineRecognizer.SetPuncModel): the words [WordBegin,
+    WordEnd), its text, and Times = [begin of its first word, end of its last] in ms when the result has exactly one
+    Timestamps entry per word, else []."""
+    WordBegin: int = 0
+    WordEnd: int = 0
+    Times: List[int] = field(default_factory=list)
+    Text: str = ""
+
+
+@dataclass
 class Segment:
     """OfflineStream.Segments: one speech piece of a long stream (OfflineRecognizer.SetVad).  [BeginMs, EndMs) on the stream's
     clock; Batch / Row: where the piece ran in the call's batch plan; [TokBegin, TokEnd): its share of the stream's Tokens,
@@ -270,6 +281,35 @@ class OfflineStream:
             txt = C.c_char_p()
             _ck(self._lib.pf_stream_segment(self._h, i, *v, C.byref(txt)))
             out.append(Segment(*[x.value for x in v], Text=(txt.value or b"").decode("utf-8")))
+        return out
+
+    def _punctuated(self):
+        txt, ids, n = C.c_char_p(), C.POINTER(C.c_int32)(), C.c_int32()
+        _ck(self._lib.pf_stream_punctuated(self._h, C.byref(txt), C.byref(ids), n))
+        return (txt.value or b"").decode("utf-8"), [ids[i] for i in range(n.value)]
+
+    @property
+    def Punctuated(self) -> str:
+        """The punctuated form of the last GetResults' Text (OfflineRecognizer.SetPuncModel; "" without it)."""
+        return self._punctuated()[0]
+
+    @property
+    def PuncIds(self) -> List[int]:
+        """The mark of every word of that text, as an index into the model's punc_list."""
+        return self._punctuated()[1]
+
+    @property
+    def Sentences(self) -> List["Sentence"]:
+        """The sentences of the punctuated text; with times when the result has one Timestamps entry per word."""
+        n = C.c_int32()
+        _ck(self._lib.pf_stream_num_sentences(self._h, n))
+        out = []
+        for i in range(n.value):
+            v = [C.c_int32() for _ in range(5)]
+            txt = C.c_char_p()
+            _ck(self._lib.pf_stream_sentence(self._h, i, *v, C.byref(txt)))
+            wb, we, ht, b, e = (x.value for x in v)
+            out.append(Sentence(WordBegin=wb, WordEnd=we, Times=[b, e] if ht else [], Text=(txt.value or b"").decode("utf-8")))
         return out
 
     def SetAlignIds(self, ids: Optional[List[int]]) -> None:
@@ -460,6 +500,13 @@ class OfflineRecognizer:
         from .engine import vad_config
         c = cfg if isinstance(cfg, N.PfVadConfig) else vad_config(**({} if cfg is True else cfg))
         _ck(self._lib.pf_recognizer_set_vad(self._h, C.byref(c), int(batch_max), int(frame_budget), sep.encode("utf-8")))
+
+    def SetPuncModel(self, pfwPath) -> None:
+        """Punctuation for every GetResults that follows: a `.pfw` of kind "cttransformer", loaded once and attached to every
+        engine of the pool; None clears.  Each stream's final Text (with SetVad: the stitched text) is punctuated on the device,
+        all streams of a call in one batch: stream.Punctuated, .PuncIds, .Sentences.  Text, Tokens and Timestamps of the result
+        stay what they are.  No real model file has been through this path: the rules and dimensions are stated, not validated."""
+        _ck(self._lib.pf_recognizer_set_punc_model(self._h, None if pfwPath is None else str(pfwPath).encode("utf-8")))
 
     def SetVadModel(self, pfwPath) -> None:
         """The FSMN-VAD model score for SetVad's segmentation: a `.pfw` of kind "fsmnvad" (python -m aliparaformerasr_amd.convert

@@ -29,7 +29,10 @@ synthetic-weight generator").
 A container of kind "fsmnvad" holds a voice-activity model instead of a
 recogniser (fsmn_vad_config / vad_tensor_shapes / synth_vad_weights below;
 the definition is tests/vadnet_ref.py): it is loaded with
-engine.load_vad_model, never handed to an Engine as its weights.
+engine.load_vad_model, never handed to an Engine as its weights.  The same
+holds for kind "cttransformer", the punctuation model (ct_transformer_config
+/ punc_tensor_shapes / synth_punc_weights; tests/punc_ref.py;
+engine.load_punc_model): its vocabulary travels as the u8 tensor "vocab".
 """
 from __future__ import annotations
 
@@ -258,6 +261,76 @@ def synth_vad_weights(cfg: dict, seed: int = 42) -> dict:
         else:
             a = rng.standard_normal(shape) / np.sqrt(shape[1])
         w[name] = a.astype(np.float32)
+    return w
+
+
+CT_TRANSFORMER_CONFIG = dict(
+    kind="cttransformer", vocab=272727, d_model=256, heads=8, ffn=1024, kernel=11, n_layers=4,
+    punc_list=("<unk>", "_", "，", "。", "？", "、"), sentence_end_id=3,
+)
+
+
+def ct_transformer_config(**kw) -> dict:
+    """The config of a `.pfw` of kind "cttransformer" (the punctuation model; the definition is tests/punc_ref.py).  The
+    defaults are the dimensions of FunASR's released punc_ct-transformer_zh-cn-common-vocab272727 as remembered, not read from
+    a file."""
+    cfg = dict(CT_TRANSFORMER_CONFIG)
+    for k, v in kw.items():
+        if k not in cfg:
+            raise KeyError(k)
+        cfg[k] = v
+    cfg["punc_list"] = [str(s) for s in cfg["punc_list"]]
+    cfg["n_punc"] = len(cfg["punc_list"])
+    return cfg
+
+
+def punc_tensor_shapes(cfg: dict) -> dict:
+    """name -> shape of every float tensor of a "cttransformer" container (the vocabulary strings travel beside them as the
+    u8 tensor "vocab": the UTF-8 words joined by newlines)."""
+    D, F, K, P = (int(cfg[k]) for k in ("d_model", "ffn", "kernel", "n_punc"))
+    sh = {"embed.weight": (int(cfg["vocab"]), D)}
+    for l in range(int(cfg["n_layers"])):
+        p = "layers.%d." % l
+        sh.update({p + "norm1.weight": (D,), p + "norm1.bias": (D,), p + "attn.qkv.weight": (3 * D, D), p + "attn.qkv.bias": (3 * D,),
+                   p + "attn.fsmn.weight": (D, K), p + "attn.out.weight": (D, D), p + "attn.out.bias": (D,),
+                   p + "norm2.weight": (D,), p + "norm2.bias": (D,), p + "ffn.w1.weight": (F, D), p + "ffn.w1.bias": (F,),
+                   p + "ffn.w2.weight": (D, F), p + "ffn.w2.bias": (D,)})
+    sh.update({"after_norm.weight": (D,), "after_norm.bias": (D,), "decoder.weight": (P, D), "decoder.bias": (P,)})
+    return sh
+
+
+def synth_punc_vocab(n: int) -> list:
+    """n distinct words: "<unk>" first, then CJK characters from U+4E00, every fifth entry a lower-case ASCII word."""
+    out = ["<unk>"]
+    for i in range(1, n):
+        if i % 5 == 0:
+            s, k = "", i // 5
+            while True:
+                s += chr(ord("a") + k % 26)
+                k //= 26
+                if k == 0:
+                    break
+            out.append("w" + s)
+        else:
+            out.append(chr(0x4E00 + i + (0x800 if 0x4E00 + i >= 0xD800 else 0)))      # (stepping over the surrogate range)
+    return out
+
+
+def synth_punc_weights(cfg: dict, seed: int = 42, decoder_scale: float = 1.0) -> dict:
+    """Seeded synthetic CT-Transformer weights: the encoder layers as synth_weights draws them, the embedding N(0, 1 / 16)
+    (so that embed * sqrt(d_model) is about N(0, 1)), the decoder N(0, decoder_scale / sqrt(d_model)) and "vocab":
+    synth_punc_vocab.  decoder_scale scales the float64 top-2 margin and the f16 error of the logits alike, so it does not
+    change the share of positions whose margin clears the error; at 1 that share is above 95 % (tests/test_punc_cpu.py)."""
+    rng = np.random.default_rng(seed)
+    D = int(cfg["d_model"])
+    w = {"embed.weight": (rng.standard_normal((int(cfg["vocab"]), D), dtype=np.float32) / np.float32(16.0)).astype(np.float32)}
+    for l in range(int(cfg["n_layers"])):
+        w.update(_enc_layer(rng, cfg, "layers.%d" % l, D))
+    w.update(_ln(rng, D, "after_norm"))
+    dec = _linear(rng, int(cfg["n_punc"]), D, prefix="decoder")
+    dec["decoder.weight"] = (dec["decoder.weight"] * np.float32(decoder_scale)).astype(np.float32)
+    w.update(dec)
+    w["vocab"] = np.frombuffer("\n".join(synth_punc_vocab(int(cfg["vocab"]))).encode("utf-8"), dtype=np.uint8).copy()
     return w
 
 

@@ -224,6 +224,55 @@ namespace AliParaformerAsr.Hip
             }
         }
 
+        /// <summary>Not in the reference: one sentence of the punctuated text: the words [WordBegin, WordEnd), its text, and
+        /// [BeginMs, EndMs] when the result has exactly one Timestamps entry per word (HasTime).</summary>
+        public sealed class Sentence
+        {
+            public int WordBegin, WordEnd, BeginMs, EndMs;
+            public bool HasTime;
+            public string Text = "";
+        }
+
+        /// <summary>Not in the reference: the punctuated form of the last GetResults' Text (OfflineRecognizer.SetPuncModel; "" without it).</summary>
+        public string Punctuated
+        {
+            get
+            {
+                ParaformerHip.Check(ParaformerHip.pf_stream_punctuated(Handle, out IntPtr txt, out _, out _));
+                return Marshal.PtrToStringUTF8(txt) ?? "";
+            }
+        }
+
+        /// <summary>Not in the reference: the mark of every word of that text, as an index into the model's punc_list.</summary>
+        public int[] PuncIds
+        {
+            get
+            {
+                ParaformerHip.Check(ParaformerHip.pf_stream_punctuated(Handle, out _, out IntPtr ids, out int n));
+                var r = new int[n];
+                if (n > 0) Marshal.Copy(ids, r, 0, n);
+                return r;
+            }
+        }
+
+        /// <summary>Not in the reference: the sentences of the punctuated text.</summary>
+        public List<Sentence> Sentences
+        {
+            get
+            {
+                var r = new List<Sentence>();
+                ParaformerHip.Check(ParaformerHip.pf_stream_num_sentences(Handle, out int n));
+                for (int i = 0; i < n; i++)
+                {
+                    ParaformerHip.Check(ParaformerHip.pf_stream_sentence(Handle, i, out int wb, out int we, out int ht, out int b, out int e,
+                                                                        out IntPtr txt));
+                    r.Add(new Sentence { WordBegin = wb, WordEnd = we, HasTime = ht != 0, BeginMs = b, EndMs = e,
+                                         Text = Marshal.PtrToStringUTF8(txt) ?? "" });
+                }
+                return r;
+            }
+        }
+
         /// <summary>Not in the reference: the stream's target for forced alignment (OfflineRecognizer.SetAlign) as token IDS — text
         /// to ids needs the model's tokenizer and is the caller's.  Kept until cleared with null.</summary>
         public void SetAlignIds(long[]? ids)
@@ -398,6 +447,12 @@ namespace AliParaformerAsr.Hip
         /// attached to every engine of the pool, present and future; null clears.  Inert until SetVad, and may be set before or after
         /// it; pass DefaultVadModel() to SetVad for the thresholds that go with it (stated, not tuned).</summary>
         public void SetVadModel(string? pfwPath) => ParaformerHip.Check(ParaformerHip.pf_recognizer_set_vad_model(_r, pfwPath));
+
+        /// <summary>Not in the reference: punctuation for every GetResults that follows: a .pfw of kind "cttransformer", loaded once and
+        /// attached to every engine of the pool; null clears.  Each stream's final Text is punctuated on the device, all streams of a
+        /// call in one batch (OfflineStream.Punctuated, PuncIds, Sentences); Text, Tokens and Timestamps stay what they are.  The rules
+        /// and dimensions are stated, not validated on a real model.</summary>
+        public void SetPuncModel(string? pfwPath) => ParaformerHip.Check(ParaformerHip.pf_recognizer_set_punc_model(_r, pfwPath));
 
         /// <summary>The stated defaults that go with the model score (pf_vad_model_config: floor_pct = -1, abs_level = 9830).</summary>
         public static PfVadConfig DefaultVadModel()

@@ -275,6 +275,18 @@ namespace AliParaformerAsr.Native
         // cfg: an array of one element, or null (= off)
         [DllImport(Lib)] internal static extern int pf_recognizer_set_vad(IntPtr r, PfVadConfig[]? cfg, int batchMax, long frameBudget,
                                                                          [MarshalAs(UnmanagedType.LPUTF8Str)] string? sepUtf8);
+        // punctuation (a .pfw of kind "cttransformer"): the loader, what it read, the attach calls, the loop on ids, a stream's result
+        [DllImport(Lib)] internal static extern int pf_punc_model_load([MarshalAs(UnmanagedType.LPUTF8Str)] string path, out IntPtr m);
+        [DllImport(Lib)] internal static extern int pf_punc_model_from_memory(byte[] data, long nbytes, out IntPtr m);
+        [DllImport(Lib)] internal static extern int pf_punc_model_info(IntPtr m, [Out] int[]? dims, out long imageBytes);
+        [DllImport(Lib)] internal static extern void pf_punc_model_free(IntPtr m);
+        [DllImport(Lib)] internal static extern int pf_engine_set_punc_model(IntPtr e, IntPtr m);
+        [DllImport(Lib)] internal static extern int pf_engine_punctuate(IntPtr e, int[] ids, int[] lens, int B, [Out] int[] puncIds, out int rounds);
+        [DllImport(Lib)] internal static extern int pf_recognizer_set_punc_model(IntPtr r, [MarshalAs(UnmanagedType.LPUTF8Str)] string? pfwPath);
+        [DllImport(Lib)] internal static extern int pf_stream_punctuated(IntPtr s, out IntPtr textUtf8, out IntPtr puncIds, out int nWords);
+        [DllImport(Lib)] internal static extern int pf_stream_num_sentences(IntPtr s, out int n);
+        [DllImport(Lib)] internal static extern int pf_stream_sentence(IntPtr s, int i, out int wordBegin, out int wordEnd, out int hasTime,
+                                                                      out int beginMs, out int endMs, out IntPtr textUtf8);
         [DllImport(Lib)] internal static extern int pf_stream_num_segments(IntPtr s, out int n);
         [DllImport(Lib)] internal static extern int pf_stream_segment(IntPtr s, int i, out int beginMs, out int endMs, out int batch, out int row,
                                                                      out int tokBegin, out int tokEnd, out IntPtr textUtf8);

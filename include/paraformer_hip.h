@@ -655,6 +655,80 @@ int pf_host_vad_model_levels(const pf_vad_model* m, const float* rows, int64_t T
    front-end.  A pf_group forward is unaffected. */
 int pf_engine_set_vad_model(pf_engine* e, const pf_vad_model* m);
 
+/* ---- Punctuation (additions to ABI 6; opt-in: with no model attached nothing of this is launched or allocated and every
+   result is bit for bit what it is without it) ----
+   A CT-Transformer (the punctuation model FunASR pairs with paraformer: VAD -> ASR -> punctuation) marks every word of a text
+   with one of the model's punctuation classes.  The definition in numpy float64 is tests/punc_ref.py; DESIGN.md 4.6l has the
+   launch plan and the rounding points of the device form (csrc/k_punc.hip).  The text rules are THIS PROJECT'S definition,
+   restated from FunASR's CTTransformer.inference from memory; the default dimensions are those of FunASR's released
+   punc_ct-transformer_zh-cn-common-vocab272727 as remembered.  NO REAL MODEL FILE HAS BEEN LOADED AND NOTHING HERE IS VALIDATED ON ONE.
+   The model is a `.pfw` of kind "cttransformer": vocab, d_model, heads, ffn, kernel, n_layers, punc_list (strings),
+   sentence_end_id, the u8 tensor "vocab" (the words joined by newlines) and the fp32 tensors embed.weight [vocab, d_model],
+   per layer l layers.l.norm1 / attn.qkv / attn.out / norm2 / ffn.w1 / ffn.w2 (.weight [out, in] and .bias),
+   layers.l.attn.fsmn.weight [d_model, kernel], after_norm, decoder [n_punc, d_model].
+   WORDS: the text is split at ASCII whitespace; inside a piece every character longer than one byte is a word and every
+   maximal run of one-byte characters is a word; a word's id is its index in the vocabulary, else that of "<unk>".
+   NETWORK, for a window of T <= PF_PUNC_MAX_WINDOW ids: x = fp32(embed[id]) * sqrt(d_model) + pe (positions 1 .. T, [sin || cos]);
+   n_layers SAN-M layers (norm1, fused qkv, FSMN over v with `kernel` centred taps inside the window plus identity, softmax
+   attention over the window's keys with q scaled by dh^-0.5, out(ctx) + fsmn, residual, norm2, w2(relu(w1)), residual);
+   after_norm; decoder; arg-max per row, ties to the larger index.
+   TEXT LOOP: the ids are cut into mini-sentences of 20; window m = the carried tail + mini-sentence m.  On the last one the
+   whole window is kept and a final "，", "、" or "_" becomes sentence_end_id.  Otherwise the cut is the largest i in
+   [2, n - 2] whose mark is "。" or "？"; failing that, when n > 200, the largest i in that range marked "，", which becomes
+   sentence_end_id; failing that nothing is emitted (cut = -1).  THE HARD CUT overrules these: when n > 492 and there is no
+   cut, or the cut found would leave more than 492 words behind it (n - 1 - cut > 492), the cut is n - 1 and p stays
+   unchanged (the comma is then not rewritten).  This is this project's own rule: a carried tail is at most 492 words, so a
+   window never passes PF_PUNC_MAX_WINDOW = 492 + 20; FunASR lets it grow.  Words 0 .. cut are emitted, the rest is carried.
+   ASSEMBLY: a word is preceded by one space when it and its predecessor both begin with a one-byte character; after such a
+   word "，" "。" "？" "、" are written , . ? , and otherwise as listed; "_" and "<unk>" write nothing; no capitalisation.  A
+   sentence is a run of words ending at a "。" or "？" (or at the end of the text).
+   The device form multiplies f16 operands with fp32 accumulation, so its logits are close to, not equal to, the host form's;
+   the loop it runs IS exactly the loop above over its own arg-max.  A window's bits do not depend on its batch mates.
+   Loading validates everything.  PF_ERR_INVALID_ARG: not such a container, truncated, a tensor extent outside the file, a
+   missing tensor, a wrong shape, a value that is not finite, a vocabulary that is not `vocab` distinct non-empty words or lacks
+   "<unk>", a punc_list without "<unk>" / "_", a sentence_end_id outside the list.  PF_ERR_UNSUPPORTED: d_model != 256,
+   heads != 8, ffn no multiple of 256 or above 4096, kernel even or above 31, n_layers > 8, fewer than 2 or more than 32
+   classes.  PF_ERR_IO: the file cannot be read. */
+#define PF_PUNC_MAX_WINDOW 512
+#define PF_PUNC_MAX_BATCH 4096
+typedef struct pf_punc_model pf_punc_model;
+int pf_punc_model_load(const char* path, pf_punc_model** m);
+int pf_punc_model_from_memory(const void* data, int64_t nbytes, pf_punc_model** m);
+/* dims [16]: vocab, d_model, heads, ffn, kernel, n_layers, n_punc, sentence_end_id, the vocabulary id of "<unk>", then the ids
+   of "<unk>" "_" "，" "。" "？" "、" in punc_list (-1: not listed), 0; each output optional */
+int pf_punc_model_info(const pf_punc_model* m, int32_t* dims, int64_t* image_bytes);
+void pf_punc_model_free(pf_punc_model* m);
+/* The CPU twins (plain C++, float64 from the fp32 weights).
+   pf_host_punc_words: the words of a text: ids / begin / end [cap] (byte spans in text_utf8; NULL with cap 0 to learn *n);
+   PF_ERR_CAPACITY when cap < *n.
+   pf_host_punc_logits: ONE window of T ids -> out [T, n_punc].
+   pf_host_punc_cut: the cut rule and the last-window edits on one window's p [n] (edited in place) -> *cut.
+   pf_host_punc_ids: the text loop over n ids -> punc_ids [n]; win_len / win_cut [win_cap] and *n_win (optional): every
+   forward's window length and cut.
+   pf_host_punc_assemble: the output text of `text_utf8` (n words, as pf_host_punc_words counts them) under punc_ids [n]: out
+   [cap] bytes (no terminator; *out_len is the length needed, PF_ERR_CAPACITY when cap is below it), sent_end [sent_cap] one
+   past the last word of each sentence, *n_sent.
+   pf_host_punc_text: words, loop and assembly in one call; punc_ids [ids_cap] optional. */
+int pf_host_punc_words(const pf_punc_model* m, const char* text_utf8, int32_t* ids, int32_t* begin, int32_t* end, int32_t cap, int32_t* n);
+int pf_host_punc_logits(const pf_punc_model* m, const int32_t* ids, int32_t T, double* out);
+int pf_host_punc_cut(const pf_punc_model* m, int32_t* p, int32_t n, int32_t last, int32_t* cut);
+int pf_host_punc_ids(const pf_punc_model* m, const int32_t* ids, int64_t n, int32_t* punc_ids, int32_t* win_len, int32_t* win_cut,
+                     int32_t win_cap, int32_t* n_win);
+int pf_host_punc_assemble(const pf_punc_model* m, const char* text_utf8, const int32_t* punc_ids, int32_t n, char* out, int64_t cap,
+                          int64_t* out_len, int32_t* sent_end, int32_t sent_cap, int32_t* n_sent);
+int pf_host_punc_text(const pf_punc_model* m, const char* text_utf8, char* out, int64_t cap, int64_t* out_len, int32_t* punc_ids,
+                      int32_t ids_cap, int32_t* n_words);
+/* Attaches the model to the engine (NULL detaches and frees what the attach and its runs allocated).  The engine takes a
+   reference of its own (pf_punc_model_free may follow at once) and uploads the weight image once.  Nothing else the engine
+   computes changes; a pf_group forward is unaffected. */
+int pf_engine_set_punc_model(pf_engine* e, const pf_punc_model* m);
+/* The text loop on the device for B texts given as word ids (B <= PF_PUNC_MAX_BATCH): ids = the concatenated ids, lens [B]
+   -> punc_ids [sum lens], aligned with ids.  The loop runs in rounds; a round is ONE forward (profile class "punc",
+   2 + 2 n_layers launches) over the next window of every text that still has a mini-sentence, and the host only assembles the
+   next windows from the cuts.  *rounds (optional): how many rounds ran = the longest text's number of mini-sentences.
+   PF_ERR_INVALID_ARG without an attached model or for an id outside the vocabulary. */
+int pf_engine_punctuate(pf_engine* e, const int32_t* ids, const int32_t* lens, int32_t B, int32_t* punc_ids, int32_t* rounds);
+
 /* ------------------------------------------------------------------------ */
 /* 4b. Multi-GPU inside one process: one engine, one host thread and one HIP stream per listed
  *     device.  The reference builds a single ORT session (OfflineRecognizer.cs:23); what shards is the utterance
@@ -746,6 +820,14 @@ int pf_op_vad_segments(pf_engine* e, const int32_t* levels, const int32_t* T, in
    out [sum T] int32 levels.  An utterance's result does not depend on its batch mates. */
 int pf_op_vad_model_logits(pf_engine* e, const float* rows, const int32_t* T, int32_t B, int32_t n_mels, float* out);
 int pf_op_vad_model_levels(pf_engine* e, const float* rows, const int32_t* T, int32_t B, int32_t n_mels, int32_t* out);
+/* exactly the attached punctuation model's launches (k_punc.hip; PF_ERR_INVALID_ARG without pf_engine_set_punc_model) on
+   caller windows: the concatenated ids of B windows, T [B] ids each (0 .. PF_PUNC_MAX_WINDOW).
+   pf_op_punc_logits: logits [sum T, n_punc] fp32 and, optionally, x0 [sum T, d_model] fp32, the input of layer 0 (1 + 2 n_layers
+   launches).  pf_op_punc_window: with the cut launch behind them (2 + 2 n_layers): last [B] != 0 marks a text's last window;
+   p [sum T] after the edits, cut [B]; logits optional.  A window's result does not depend on its batch mates. */
+int pf_op_punc_logits(pf_engine* e, const int32_t* ids, const int32_t* T, int32_t B, float* logits, float* x0);
+int pf_op_punc_window(pf_engine* e, const int32_t* ids, const int32_t* T, const int32_t* last, int32_t B, int32_t* p, int32_t* cut,
+                      float* logits);
 /* exactly the pipeline's top-k kernel (k_topk.hip) on the values as given: x [rows, ld] (ld >= V; nothing at or beyond V is
    read in a row), K: 1 .. PF_TOPK_MAX; ids [rows, K], val [rows, K], n [rows] as pf_fetch_topk. */
 int pf_op_topk(pf_engine* e, const float* x, int64_t rows, int32_t V, int32_t ld, int32_t K, int64_t* ids, float* val,
@@ -1199,6 +1281,21 @@ int pf_recognizer_set_vad(pf_recognizer* r, const pf_vad_config* cfg, int32_t ba
    pf_recognizer_set_vad, and may be set before or after it.  The thresholds of pf_vad_model_config are the caller's to pass to
    pf_recognizer_set_vad.  Errors as pf_vad_model_load and pf_engine_set_vad_model. */
 int pf_recognizer_set_vad_model(pf_recognizer* r, const char* pfw_path);
+/* Punctuation of every GetResults that follows (see "Punctuation"): pfw_path = a `.pfw` of kind "cttransformer", loaded once
+   and attached to every engine of the pool; NULL clears.  GetResults then punctuates each stream's final text (with
+   pf_recognizer_set_vad: the stitched text), all streams of the call in one pf_engine_punctuate, and keeps the result on the
+   stream; Text, Tokens and Timestamps of the result are what they are without it.  Alternatives are not punctuated; pf_group_*
+   and the streaming classes have no such switch.  Errors as pf_punc_model_load.
+   pf_stream_punctuated: the punctuated text, the mark of every word (punc_list index) and the word count of the stream's last
+   GetResults ("" / 0 without a model); each output optional; valid until the stream's next GetResults.
+   pf_stream_sentence: sentence i: its words [word_begin, word_end), its punctuated text and, when the result has exactly one
+   Timestamps entry per word and they are not all the {0, 0} placeholders of a model without timestamps (*has_time), [begin of
+   its first word, end of its last] in ms. */
+int pf_recognizer_set_punc_model(pf_recognizer* r, const char* pfw_path);
+int pf_stream_punctuated(pf_stream* s, const char** text_utf8, const int32_t** punc_ids, int32_t* n_words);
+int pf_stream_num_sentences(pf_stream* s, int32_t* n);
+int pf_stream_sentence(pf_stream* s, int32_t i, int32_t* word_begin, int32_t* word_end, int32_t* has_time, int32_t* begin_ms,
+                       int32_t* end_ms, const char** text_utf8);
 /* The segments of the stream's last GetResults in time order (0 without pf_recognizer_set_vad): [begin_ms, end_ms) on the
    stream's clock, where it ran (batch, row of the plan), its share [tok_begin, tok_end) of pf_stream_tokens / pf_stream_scores
    / pf_stream_timestamp, and its own text; each output optional.  Valid until the stream's next GetResults. */
