@@ -92,6 +92,18 @@ static ShellPool<pf_online_stream>& online_stream_shells() { static ShellPool<pf
 
 #define NEED(p) PF_CHECK((p) != nullptr, PF_ERR_INVALID_ARG, "null argument: " #p)
 
+// a new handle on an immutable model (pf_vad_model, pf_punc_model) from a path or from memory; *m is null on a failure
+template <class H, class Make>
+static int new_model_handle(H** m, const void* arg, const char* arg_name, Make&& make) {
+  PF_TRY
+  NEED(m);
+  PF_CHECK(arg != nullptr, PF_ERR_INVALID_ARG, std::string("null argument: ") + arg_name);
+  *m = nullptr;
+  *m = new H{make()};
+  return PF_OK;
+  PF_CATCH
+}
+
 extern "C" {
 
 int pf_version(void) { return PF_ABI_VERSION; }
@@ -899,22 +911,10 @@ int pf_op_vad_segments(pf_engine* h, const int32_t* levels, const int32_t* T, in
 
 // ---- voice-activity segmentation, model score ----
 int pf_vad_model_load(const char* path, pf_vad_model** m) {
-  PF_TRY
-  NEED(m); NEED(path);
-  *m = nullptr;
-  std::shared_ptr<const VadModel> p = vad_model_load(path);
-  *m = new pf_vad_model{std::move(p)};
-  return PF_OK;
-  PF_CATCH
+  return new_model_handle(m, path, "path", [&] { return vad_model_load(path); });
 }
 int pf_vad_model_from_memory(const void* data, int64_t nbytes, pf_vad_model** m) {
-  PF_TRY
-  NEED(m); NEED(data);
-  *m = nullptr;
-  std::shared_ptr<const VadModel> p = vad_model_from_memory(data, nbytes);
-  *m = new pf_vad_model{std::move(p)};
-  return PF_OK;
-  PF_CATCH
+  return new_model_handle(m, data, "data", [&] { return vad_model_from_memory(data, nbytes); });
 }
 int pf_vad_model_info(const pf_vad_model* m, int32_t* dims, int32_t* n_sil, int64_t* image_bytes) {
   PF_TRY
@@ -1009,22 +1009,10 @@ int pf_op_vad_model_levels(pf_engine* h, const float* rows, const int32_t* T, in
 
 // ---- punctuation ----
 int pf_punc_model_load(const char* path, pf_punc_model** m) {
-  PF_TRY
-  NEED(m); NEED(path);
-  *m = nullptr;
-  std::shared_ptr<const PuncModel> p = punc_model_load(path);
-  *m = new pf_punc_model{std::move(p)};
-  return PF_OK;
-  PF_CATCH
+  return new_model_handle(m, path, "path", [&] { return punc_model_load(path); });
 }
 int pf_punc_model_from_memory(const void* data, int64_t nbytes, pf_punc_model** m) {
-  PF_TRY
-  NEED(m); NEED(data);
-  *m = nullptr;
-  std::shared_ptr<const PuncModel> p = punc_model_from_memory(data, nbytes);
-  *m = new pf_punc_model{std::move(p)};
-  return PF_OK;
-  PF_CATCH
+  return new_model_handle(m, data, "data", [&] { return punc_model_from_memory(data, nbytes); });
 }
 int pf_punc_model_info(const pf_punc_model* m, int32_t* dims, int64_t* image_bytes) {
   PF_TRY

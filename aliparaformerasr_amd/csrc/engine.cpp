@@ -13,6 +13,7 @@
 #include <set>
 
 #include "hostutil.h"
+#include "pfw.h"
 
 namespace pf {
 
@@ -341,28 +342,21 @@ void Engine::load_weights(const pf_engine_config& cfg) {
   } else if (cfg.weights_device) {
     dev_image = (const char*)cfg.weights_device;
     nbytes = cfg.weights_bytes;
-    PF_CHECK(nbytes >= 16, PF_ERR_FORMAT, "weights: image too small");
+    if (nbytes < 16) pfw_bad(kPfwWeights, "image too small");
     head.resize(16);
     PF_HIP(hipMemcpy(head.data(), dev_image, 16, hipMemcpyDeviceToHost));
   } else {
     throw Error(PF_ERR_INVALID_ARG, "weights: no source given (weights_path / weights_host / weights_device)");
   }
-  PF_CHECK(nbytes >= 16, PF_ERR_FORMAT, "weights: image too small");
-  const char* h16 = host ? host : head.data();
-  PF_CHECK(std::memcmp(h16, "PFW1", 4) == 0, PF_ERR_FORMAT, "weights: bad magic (expected PFW1 container)");
-  uint64_t hlen = 0;
-  std::memcpy(&hlen, h16 + 8, 8);
-  PF_CHECK(hlen <= (uint64_t)nbytes - 16u, PF_ERR_FORMAT, "weights: truncated header");   // unsigned: a huge hlen cannot wrap
+  const PfwFrame fr = pfw_frame(host ? host : head.data(), nbytes, kPfwWeights);
   std::string hdr;
-  if (host) hdr.assign(host + 16, hlen);
+  if (host) hdr.assign(host + 16, (size_t)fr.header_len);
   else {
-    hdr.resize(hlen);
-    PF_HIP(hipMemcpy(&hdr[0], dev_image + 16, hlen, hipMemcpyDeviceToHost));
+    hdr.resize((size_t)fr.header_len);
+    PF_HIP(hipMemcpy(&hdr[0], dev_image + 16, hdr.size(), hipMemcpyDeviceToHost));
   }
-  Json j = JsonParser(hdr.data(), hdr.size()).parse();
-  const Json* jc = j.get("config");
-  const Json* jt = j.get("tensors");
-  PF_CHECK(jc && jt && jt->type == Json::Arr, PF_ERR_FORMAT, "weights: header lacks config/tensors");
+  const PfwIndex ix = pfw_index(hdr.data(), fr.header_len, fr.data_bytes, kPfwWeights);
+  const Json* jc = &ix.config;
   mc_.kind = jc->str_or("kind", mc_.kind);
   PF_CHECK(mc_.kind != "fsmnvad", PF_ERR_INVALID_ARG,
            "weights: a container of kind \"fsmnvad\" is a voice-activity model (pf_vad_model_load), not a recogniser");
@@ -409,41 +403,17 @@ void Engine::load_weights(const pf_engine_config& cfg) {
            "seaco: unsupported dimensions");
   PF_CHECK(!mc_.timestamp_head || mc_.upsample == 3, PF_ERR_UNSUPPORTED, "timestamp head: only upsample = 3");
 
-  const int64_t data_off = round_up((int64_t)(16 + hlen), (int64_t)kAlign);
-  const int64_t data_bytes = nbytes - data_off;
-  PF_CHECK(data_bytes >= 0, PF_ERR_FORMAT, "weights: truncated data section");
   const char* data_dev = nullptr;
   if (host) {
-    PF_HIP(hipMalloc(&blob_dev_, std::max<int64_t>(data_bytes, 256)));
+    PF_HIP(hipMalloc(&blob_dev_, std::max<int64_t>(fr.data_bytes, 256)));
     blob_owned_ = true;
-    PF_HIP(hipMemcpy(blob_dev_, host + data_off, data_bytes, hipMemcpyHostToDevice));
+    PF_HIP(hipMemcpy(blob_dev_, host + fr.data_off, fr.data_bytes, hipMemcpyHostToDevice));
     data_dev = (const char*)blob_dev_;
   } else {
-    data_dev = dev_image + data_off;
+    data_dev = dev_image + fr.data_off;
   }
-  for (const Json& t : jt->arr) {
-    Tensor tt;
-    const std::string name = t.str_or("name", "");
-    const std::string dt = t.str_or("dtype", "f32");
-    PF_CHECK(dt == "f32" || dt == "u8", PF_ERR_FORMAT, "weights: tensor '" + name + "' has dtype '" + dt + "' (f32 and u8 are supported)");
-    tt.u8 = dt == "u8";
-    const int64_t off = t.int_or("offset", -1), nb = t.int_or("nbytes", -1);
-    PF_CHECK(off >= 0 && nb >= 0 && off + nb <= data_bytes && off % 16 == 0, PF_ERR_FORMAT,
-             "weights: bad tensor extent for '" + name + "'");
-    tt.dev = (const float*)(data_dev + off);
-    tt.numel = 1;
-    if (const Json* sh = t.get("shape"))
-      for (const Json& d : sh->arr) {
-        const double dv = d.type == Json::Num ? d.num : -1.0;
-        PF_CHECK(dv >= 1.0 && dv <= 2147483647.0 && dv == (double)(int64_t)dv, PF_ERR_FORMAT,
-                 "weights: bad dimension in the shape of '" + name + "'");
-        PF_CHECK(tt.numel <= (int64_t)1 << 40, PF_ERR_FORMAT, "weights: shape of '" + name + "' overflows");
-        tt.shape.push_back((int64_t)dv);
-        tt.numel *= (int64_t)dv;
-      }
-    PF_CHECK(tt.numel * (tt.u8 ? 1 : 4) == nb, PF_ERR_FORMAT, "weights: shape/nbytes mismatch for '" + name + "'");
-    tensors_[name] = tt;
-  }
+  for (const auto& kv : ix.tensors)
+    tensors_[kv.first] = Tensor{(const float*)(data_dev + kv.second.offset), kv.second.shape, kv.second.numel, kv.second.u8};
   if (const Json* ex = jc->get("int8_exclude"))
     if (ex->type == Json::Arr)
       for (const Json& e : ex->arr)
@@ -1957,8 +1927,11 @@ void Engine::install_hotwords(HotDev& d, const char* who_, const int32_t* ids, c
   PF_HIP(hipStreamSynchronize(stream_));            // a queued search may still read the table about to be replaced
   const size_t V = g.tok_col.size(), words = V + g.table.size();
   ensure(d.buf, words * 4);
-  PF_HIP(hipMemcpy(d.buf.p, g.tok_col.data(), V * 4, hipMemcpyHostToDevice));
-  PF_HIP(hipMemcpy((int32_t*)d.buf.p + V, g.table.data(), g.table.size() * 4, hipMemcpyHostToDevice));
+  // on stream_, behind the zero fill that ensure() queues there when it allocates: the stream is non-blocking, so a copy on
+  // the null stream is not ordered against that fill and could be overwritten by it (a fresh engine's first table)
+  PF_HIP(hipMemcpyAsync(d.buf.p, g.tok_col.data(), V * 4, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipMemcpyAsync((int32_t*)d.buf.p + V, g.table.data(), g.table.size() * 4, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipStreamSynchronize(stream_));              // (g goes with this scope)
   d.boost = boost;
   d.A = g.A;
 }

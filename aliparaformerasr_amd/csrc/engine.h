@@ -583,14 +583,17 @@ class Engine {
                                      // the one pf_op_* last used
   const int32_t* lm_device_image(LmDev& d, const std::shared_ptr<const LmImage>& lm);
   std::shared_ptr<const LmImage> lm_;   // the installed model (nullptr: none), its weights and flags
-  // the FSMN-VAD model (set_vad_model): the attached model, its image on the device and the two p buffers the launches alternate
-  // between; allocated by an attach / a run only, freed by a detach
+  // an auxiliary network: the attached model, its image on the device (with the model it was uploaded from) and a workspace;
+  // allocated by an attach / a run only, freed by a detach (attach_model with nullptr)
+  template <class M> struct ModelDev { DevBuf buf; std::shared_ptr<const M> src; };
+  template <class M> void attach_model(std::shared_ptr<const M>& on, ModelDev<M>& dev, DevBuf& ws, const std::shared_ptr<const M>& m);
+  // the FSMN-VAD model (set_vad_model): ws_vadnet_ holds the two p buffers the launches alternate between
   std::shared_ptr<const VadModel> vadnet_;
-  struct VadNetDev { DevBuf buf; std::shared_ptr<const VadModel> src; } vadnet_dev_;
+  ModelDev<VadModel> vadnet_dev_;
   DevBuf ws_vadnet_;
   // the punctuation model (set_punc_model): as above; ws_punc_ holds ids, offsets, x, the two q | k | v buffers, ctx, logits, p, cut
   std::shared_ptr<const PuncModel> punc_;
-  struct PuncDev { DevBuf buf; std::shared_ptr<const PuncModel> src; } punc_dev_;
+  ModelDev<PuncModel> punc_dev_;
   DevBuf ws_punc_;
   void run_punc(const int32_t* ids, const int64_t* off, const int32_t* last, int B, float* logits, float* x0, int32_t* p, int32_t* cut);
   void run_vadnet(const float* rows_dev, const int64_t* off_dev, int B, int64_t total, int n_mels, float* logits_dev, int32_t* levels_dev);

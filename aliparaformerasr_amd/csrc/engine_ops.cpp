@@ -284,32 +284,43 @@ void Engine::vad_staged(const pf_vad_config* cfg, int32_t* seg, int cap, int32_t
   vad_read_back(stream_, ws, L, B, cap, dev_cap, seg, n_seg);
 }
 
-// ---- the FSMN-VAD model score (k_vadnet.hip; the launch plan is at the head of that file)
-void Engine::set_vad_model(const std::shared_ptr<const VadModel>& m) {
-  if (!m) {                                         // detached: nothing of the network stays allocated
-    vadnet_.reset();
-    vadnet_dev_.src.reset();
-    if (vadnet_dev_.buf.p || ws_vadnet_.p) {
+// ---- attach / detach of an auxiliary network (the FSMN-VAD model, the punctuation model): `on` is the attached model, `dev`
+// its image on the device with the model it was uploaded from, `ws` the workspace its runs grow.  nullptr detaches: nothing
+// of the network stays allocated.  The stream is synchronised before an image is replaced and before anything is freed: a
+// queued launch may still read the image or the workspace.
+template <class M>
+void Engine::attach_model(std::shared_ptr<const M>& on, ModelDev<M>& dev, DevBuf& ws, const std::shared_ptr<const M>& m) {
+  if (!m) {
+    on.reset();
+    dev.src.reset();
+    if (dev.buf.p || ws.p) {
       PF_HIP(hipSetDevice(device_));
-      PF_HIP(hipStreamSynchronize(stream_));        // a queued launch may still read the image or the p rows
-      for (DevBuf* b : {&vadnet_dev_.buf, &ws_vadnet_})
+      PF_HIP(hipStreamSynchronize(stream_));
+      for (DevBuf* b : {&dev.buf, &ws})
         if (b->p) { PF_HIP(hipFree(b->p)); b->p = nullptr; b->bytes = 0; }
     }
     return;
   }
-  PF_CHECK((int64_t)fc_.n_mels * m->lfr_m == m->input_dim, PF_ERR_INVALID_ARG,
-           "set_vad_model: n_mels * lfr_m does not equal the model's input width");
-  PF_CHECK(!fc_.snip_edges, PF_ERR_UNSUPPORTED, "set_vad_model: snip_edges = true is not supported");
   PF_HIP(hipSetDevice(device_));
-  if (vadnet_dev_.src != m) {
-    PF_HIP(hipStreamSynchronize(stream_));          // a queued launch may still read the image about to be replaced
-    vadnet_dev_.src.reset();
-    ensure(vadnet_dev_.buf, m->image.size());
-    PF_HIP(hipMemcpyAsync(vadnet_dev_.buf.p, m->image.data(), m->image.size(), hipMemcpyHostToDevice, stream_));
+  if (dev.src != m) {
     PF_HIP(hipStreamSynchronize(stream_));
-    vadnet_dev_.src = m;
+    dev.src.reset();
+    ensure(dev.buf, m->image.size());
+    PF_HIP(hipMemcpyAsync(dev.buf.p, m->image.data(), m->image.size(), hipMemcpyHostToDevice, stream_));
+    PF_HIP(hipStreamSynchronize(stream_));
+    dev.src = m;
   }
-  vadnet_ = m;
+  on = m;
+}
+
+// ---- the FSMN-VAD model score (k_vadnet.hip; the launch plan is at the head of that file)
+void Engine::set_vad_model(const std::shared_ptr<const VadModel>& m) {
+  if (m) {
+    PF_CHECK((int64_t)fc_.n_mels * m->lfr_m == m->input_dim, PF_ERR_INVALID_ARG,
+             "set_vad_model: n_mels * lfr_m does not equal the model's input width");
+    PF_CHECK(!fc_.snip_edges, PF_ERR_UNSUPPORTED, "set_vad_model: snip_edges = true is not supported");
+  }
+  attach_model(vadnet_, vadnet_dev_, ws_vadnet_, m);
 }
 
 void Engine::run_vadnet(const float* rows_dev, const int64_t* off_dev, int B, int64_t total, int n_mels, float* logits_dev,
@@ -325,7 +336,7 @@ void Engine::run_vadnet(const float* rows_dev, const int64_t* off_dev, int B, in
     a.img = (const char*)vadnet_dev_.buf.p; a.off = off_dev; a.B = B; a.total = total; a.ld = m.lds_ld;
     a.ldp = m.ldp; a.lorder = m.lorder; a.lstride = m.lstride;
     double flops = 0;
-    auto mid = [&](const VadGemm& g, bool relu) { a.mid[a.n_mid] = g; a.mid_relu[a.n_mid] = relu ? 1 : 0; ++a.n_mid; flops += 2.0 * g.Npad * g.Kpad; };
+    auto mid = [&](const TileGemm& g, bool relu) { a.mid[a.n_mid] = g; a.mid_relu[a.n_mid] = relu ? 1 : 0; ++a.n_mid; flops += 2.0 * g.Npad * g.Kpad; };
     if (l == 0) {
       a.head = 0; a.head_w = m.g_in1.Kpad;
       a.x = rows_dev; a.n_mels = n_mels; a.lfr_m = m.lfr_m; a.in_dim = m.input_dim; a.shift_off = m.shift_off; a.scale_off = m.scale_off;
@@ -379,29 +390,7 @@ void Engine::op_vad_model(const float* rows, const int32_t* T, int B, int n_mels
 }
 
 // ---- the CT-Transformer punctuation model (k_punc.hip; the launch plan is at the head of that file)
-void Engine::set_punc_model(const std::shared_ptr<const PuncModel>& m) {
-  if (!m) {                                         // detached: nothing of the network stays allocated
-    punc_.reset();
-    punc_dev_.src.reset();
-    if (punc_dev_.buf.p || ws_punc_.p) {
-      PF_HIP(hipSetDevice(device_));
-      PF_HIP(hipStreamSynchronize(stream_));        // a queued launch may still read the image or the workspace
-      for (DevBuf* b : {&punc_dev_.buf, &ws_punc_})
-        if (b->p) { PF_HIP(hipFree(b->p)); b->p = nullptr; b->bytes = 0; }
-    }
-    return;
-  }
-  PF_HIP(hipSetDevice(device_));
-  if (punc_dev_.src != m) {
-    PF_HIP(hipStreamSynchronize(stream_));          // a queued launch may still read the image about to be replaced
-    punc_dev_.src.reset();
-    ensure(punc_dev_.buf, m->image.size());
-    PF_HIP(hipMemcpyAsync(punc_dev_.buf.p, m->image.data(), m->image.size(), hipMemcpyHostToDevice, stream_));
-    PF_HIP(hipStreamSynchronize(stream_));
-    punc_dev_.src = m;
-  }
-  punc_ = m;
-}
+void Engine::set_punc_model(const std::shared_ptr<const PuncModel>& m) { attach_model(punc_, punc_dev_, ws_punc_, m); }
 
 // one forward over B windows (host arrays in, host arrays out; returns after the results have arrived)
 void Engine::run_punc(const int32_t* ids, const int64_t* off, const int32_t* last, int B, float* logits, float* x0, int32_t* p,

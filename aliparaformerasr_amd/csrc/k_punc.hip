@@ -13,10 +13,9 @@
 // the FSMN sum stay in LDS and registers.
 //
 // punc_rows: a workgroup of four waves owns 64 consecutive rows, which may straddle windows (every row looks up its own
-// window).  A product is Y^T [N, 64] = W [N, K] X^T [K, 64] on v_mfma_f32_32x32x16_f16 exactly as in k_vadnet.hip: W is the A
-// operand (fragments tiled at attach time, vadnet.h VadGemm), the activation tile X [64, 256] f16 in LDS (row stride 264
-// halves) the B operand, so a tile row is an output COLUMN: its result depends on that row of X and on W alone, in a fixed
-// k order, whatever the other 63 rows hold.  LayerNorm is one wave per row in a fixed reduction order.  That, and an
+// window).  A product is the one of tile_rows.h, on an activation tile X [64, 256] f16 in LDS with a row stride of 264
+// halves: a tile row's result depends on that row of X and on W alone, whatever the other 63 rows hold.  LayerNorm is one
+// wave per row in a fixed reduction order.  That, and an
 // attention launch that sees one window per workgroup, is why a window's bits do not depend on its batch mates or on where
 // its rows start.  The FFN hidden is walked in slices of 256 channels (w1 slice -> ReLU -> f16 tile -> w2 partial sums in
 // registers), which is what lets a 64-row tile fit: x fp32 [64, 260] + two f16 [64, 264] tiles = 132 KB of LDS.
@@ -31,54 +30,15 @@
 // from the fp32 values); R4 ctx; R5 the FFN hidden after ReLU.  ReLU is x < 0 ? 0 : x, which keeps a NaN.
 #include "kdev.h"
 #include "kernels.h"
+#include "tile_rows.h"
 
 namespace pf {
 
 namespace {
 
-constexpr int PR_ROWS = 64, PR_D = 256, PR_XLD = 260, PR_LD = 264;
+constexpr int PR_ROWS = TR_ROWS, PR_D = 256, PR_XLD = 260, PR_LD = 264;
 constexpr size_t PR_X_BYTES = (size_t)PR_ROWS * PR_XLD * 4, PR_BUF_BYTES = (size_t)PR_ROWS * PR_LD * 2;
 constexpr size_t PR_LDS_BYTES = PR_X_BYTES + 2 * PR_BUF_BYTES + PR_ROWS * 8 + PR_ROWS * 4;
-
-__device__ __forceinline__ void pr_bias(const float* __restrict__ bias, int nt, int h, f16x& acc) {
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const float4 b4 = *reinterpret_cast<const float4*>(bias + 32 * nt + 8 * q + 4 * h);
-    acc[4 * q + 0] = b4.x; acc[4 * q + 1] = b4.y; acc[4 * q + 2] = b4.z; acc[4 * q + 3] = b4.w;
-  }
-}
-
-// nks k-steps of one 32-row block of W (wp: the block's first fragment of the range, already offset by the lane) times the
-// two 32-row halves of the tile (x0 / x1: the lane's row, already offset by the range's first column and the lane half)
-__device__ __forceinline__ void pr_mma(const h8* __restrict__ wp, int nks, const half_t* x0, const half_t* x1, f16x& c0, f16x& c1) {
-  h8 wn = wp[0];
-  for (int ks = 0; ks < nks; ++ks) {
-    const h8 wf = wn;
-    if (ks + 1 < nks) wn = wp[(size_t)(ks + 1) * 64];
-    const h8 b0 = *reinterpret_cast<const h8a*>(x0 + 16 * ks);
-    const h8 b1 = *reinterpret_cast<const h8a*>(x1 + 16 * ks);
-    c0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf, b0, c0, 0, 0, 0);
-    c1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf, b1, c1, 0, 0, 0);
-  }
-}
-
-// X [64, 256] (LDS, row stride PR_LD) times W^T over the whole K = 256: epi(nt, i, acc) per 32-row block nt of W and tile half i
-template <class Epi>
-__device__ __forceinline__ void pr_product(const char* __restrict__ img, const VadGemm& g, const half_t* __restrict__ x, int wave, int lane,
-                                           Epi&& epi) {
-  const int r = lane & 31, h = lane >> 5, KS = g.Kpad >> 4;
-  const h8* __restrict__ wt = reinterpret_cast<const h8*>(img + g.w_off);
-  const float* __restrict__ bias = reinterpret_cast<const float*>(img + g.b_off);
-  const half_t* x0 = x + r * PR_LD + 8 * h;
-  for (int nt = wave; nt < (g.Npad >> 5); nt += 4) {
-    f16x acc[2];
-    pr_bias(bias, nt, h, acc[0]);
-    acc[1] = acc[0];
-    pr_mma(wt + ((size_t)nt * KS) * 64 + lane, KS, x0, x0 + 32 * PR_LD, acc[0], acc[1]);
-    epi(nt, 0, acc[0]);
-    epi(nt, 1, acc[1]);
-  }
-}
 
 // LayerNorm of the fp32 tile into an f16 tile: one wave per row, four channels per lane                          (R1)
 __device__ __forceinline__ void pr_norm(const float* __restrict__ xs, const float* __restrict__ gam, const float* __restrict__ bet,
@@ -109,24 +69,7 @@ __global__ __launch_bounds__(256) void punc_rows_kernel(PuncRowsLaunch a) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5;
   const long long g0 = (long long)blockIdx.x * PR_ROWS;
 
-  // ---- every row's window: the last b with off[b] <= row (empty windows share their offset with the next one and are
-  // stepped over)
-  if (tid < PR_ROWS) {
-    const long long g = g0 + tid;
-    long long start = 0;
-    int T = 0;
-    if (g < a.total) {
-      int lo = 0, hi = a.B - 1;                          // off[0] = 0 <= g < off[B] = total
-      while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (a.off[mid] <= g) lo = mid; else hi = mid - 1;
-      }
-      start = a.off[lo];
-      T = (int)(a.off[lo + 1] - start);
-    }
-    row_start[tid] = start;
-    row_T[tid] = T;
-  }
+  tr_row_info(a.off, a.B, a.total, g0, tid, row_start, row_T);         // every row's window
   __syncthreads();
 
   if (a.head == 0) {
@@ -177,7 +120,7 @@ __global__ __launch_bounds__(256) void punc_rows_kernel(PuncRowsLaunch a) {
     }
     __syncthreads();
     // ---- x + (out(ctx) + fsmn) -> xs
-    pr_product(a.img, a.out, bufA, wave, lane, [&](int nt, int i, const f16x& acc) {
+    tr_product(a.img, a.out, bufA, PR_LD, wave, lane, [&](int nt, int i, const f16x& acc) {
       const int row = 32 * i + r;
       const long long g = g0 + row;
       const bool valid = row_T[row] > 0;
@@ -203,7 +146,7 @@ __global__ __launch_bounds__(256) void punc_rows_kernel(PuncRowsLaunch a) {
     f16x y[2][2];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      pr_bias(reinterpret_cast<const float*>(a.img + a.w2.b_off), wave + 4 * j, h, y[j][0]);
+      tr_bias(reinterpret_cast<const float*>(a.img + a.w2.b_off), wave + 4 * j, h, y[j][0]);
       y[j][1] = y[j][0];
     }
     const half_t* xa = bufA + r * PR_LD + 8 * h;
@@ -213,26 +156,16 @@ __global__ __launch_bounds__(256) void punc_rows_kernel(PuncRowsLaunch a) {
       for (int j = 0; j < 2; ++j) {
         const int nb = wave + 4 * j, nt = 8 * c + nb;
         f16x acc[2];
-        pr_bias(b1, nt, h, acc[0]);
+        tr_bias(b1, nt, h, acc[0]);
         acc[1] = acc[0];
-        pr_mma(w1t + ((size_t)nt * KS1) * 64 + lane, KS1, xa, xa + 32 * PR_LD, acc[0], acc[1]);
+        tr_mma(w1t + ((size_t)nt * KS1) * 64 + lane, KS1, xa, xa + 32 * PR_LD, acc[0], acc[1]);
 #pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            h4 v;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              const float f = acc[i][4 * q + e];
-              v[e] = (half_t)(f < 0.f ? 0.f : f);
-            }
-            *reinterpret_cast<h4a*>(bufB + (32 * i + r) * PR_LD + 32 * nb + 8 * q + 4 * h) = v;
-          }
+        for (int i = 0; i < 2; ++i) tr_put_f16(acc[i], true, bufB, PR_LD, i, nb, r, h);                  // R5
       }
       __syncthreads();
 #pragma unroll
       for (int j = 0; j < 2; ++j)
-        pr_mma(w2t + ((size_t)(wave + 4 * j) * KS2 + 16 * c) * 64 + lane, 16, xb, xb + 32 * PR_LD, y[j][0], y[j][1]);
+        tr_mma(w2t + ((size_t)(wave + 4 * j) * KS2 + 16 * c) * 64 + lane, 16, xb, xb + 32 * PR_LD, y[j][0], y[j][1]);
       __syncthreads();
     }
     // ---- x + ffn -> xs, and to memory where a later launch reads it
@@ -259,7 +192,7 @@ __global__ __launch_bounds__(256) void punc_rows_kernel(PuncRowsLaunch a) {
   __syncthreads();
   if (a.tail == 0) {
     // q * dh^-0.5 | k | v of the next layer, f16                                                            (R2)
-    pr_product(a.img, a.last, bufA, wave, lane, [&](int nt, int i, const f16x& acc) {
+    tr_product(a.img, a.last, bufA, PR_LD, wave, lane, [&](int nt, int i, const f16x& acc) {
       const int row = 32 * i + r;
       if (row_T[row] <= 0) return;
       const float sc = nt < (PR_D >> 5) ? 0.17677669529663687f : 1.f;
@@ -275,7 +208,7 @@ __global__ __launch_bounds__(256) void punc_rows_kernel(PuncRowsLaunch a) {
     return;
   }
   // the decoder (one 32-row block of W: wave 0), the logits and the arg-max, ties to the larger index
-  pr_product(a.img, a.last, bufA, wave, lane, [&](int nt, int i, const f16x& acc) {
+  tr_product(a.img, a.last, bufA, PR_LD, wave, lane, [&](int nt, int i, const f16x& acc) {
     const int row = 32 * i + r;
     const long long g = g0 + row;
     const bool valid = row_T[row] > 0;

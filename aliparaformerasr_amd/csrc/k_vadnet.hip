@@ -9,13 +9,10 @@
 //   launch n            FSMN taps over p_{n-1} -> affine_{n-1} + ReLU -> out_linear1 -> out_linear2 -> softmax -> level
 // The only dependence between tiles is the tap halo, which a launch boundary covers: no grid barrier, nothing persistent.
 //
-// A product is Y^T [N, 64] = W [N, K] X^T [K, 64] on v_mfma_f32_32x32x16_f16: W as the A operand (fragments tiled once at
-// attach time, vadnet.h VadGemm, streamed from L2 16 bytes per lane), the activation tile X [64, K] f16 row-major in LDS as
-// the B operand (row stride ld = the widest operand + 8 halves: an odd number of 16-byte chunks, so the rows of a read do not
-// all start on one bank; it is not conflict-free: at the released size ld = 408 is 204 dwords = 12 mod 64, and rows r and
-// r + 16 of a read share a bank.  The cost of that was not measured).  A wave
-// takes the 32-row blocks nt = wave, wave + 4, ... of W and both 32-row halves of the tile; the accumulator starts as the
-// bias.  Lane (r, h) then holds row 32 i + r of the tile and the 16 channels 32 nt + 8 g + 4 h + (0 .. 3), g = 0 .. 3.
+// A product is the one of tile_rows.h: W fragments from the image as the A operand, the activation tile X [64, K] f16 in LDS as
+// the B operand.  The tile's row stride is ld = the widest operand + 8 halves: an odd number of 16-byte chunks, so the rows of
+// a read do not all start on one bank; it is not conflict-free: at the released size ld = 408 is 204 dwords = 12 mod 64, and
+// rows r and r + 16 of a read share a bank.  The cost of that was not measured.
 //
 // Rounding points (everything else is fp32): R0 the weights, once, at attach time; R1 the LFR + CMVN input; R2 in_linear1's
 // output; R3 in_linear2's after ReLU; R4 the FSMN sum m; R5 affine's output after ReLU; R6 out_linear1's output.  p is stored
@@ -29,67 +26,24 @@
 // Nothing at or beyond an utterance's T is read; rows at or beyond the total are computed as zeros and never stored.
 #include "kdev.h"
 #include "kernels.h"
+#include "tile_rows.h"
 
 namespace pf {
 
 namespace {
 
-constexpr int VN_ROWS = 64;
+constexpr int VN_ROWS = TR_ROWS;
 
 struct VnRowInfo {            // per tile row: the first row of its utterance and that utterance's length; T = 0: no such row
   long long start[VN_ROWS];
   int T[VN_ROWS];
 };
 
-// X [64, g.Kpad] (LDS, row stride ld halves) times W^T: epi(nt, i, acc) per 32-row block nt of W and tile half i
-template <class Epi>
-__device__ __forceinline__ void vn_product(const char* __restrict__ img, const VadGemm& g, const half_t* __restrict__ x, int ld, int wave,
-                                           int lane, Epi&& epi) {
-  const int r = lane & 31, h = lane >> 5, KS = g.Kpad >> 4;
-  const h8* __restrict__ wt = reinterpret_cast<const h8*>(img + g.w_off);
-  const float* __restrict__ bias = reinterpret_cast<const float*>(img + g.b_off);
-  const half_t* x0 = x + r * ld + 8 * h;
-  const half_t* x1 = x0 + 32 * ld;
-  for (int nt = wave; nt < (g.Npad >> 5); nt += 4) {
-    f16x acc[2];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const float4 b4 = *reinterpret_cast<const float4*>(bias + 32 * nt + 8 * q + 4 * h);
-      acc[0][4 * q + 0] = b4.x; acc[0][4 * q + 1] = b4.y; acc[0][4 * q + 2] = b4.z; acc[0][4 * q + 3] = b4.w;
-    }
-    acc[1] = acc[0];
-    const h8* wp = wt + ((size_t)nt * KS) * 64 + lane;
-    h8 wn = wp[0];
-    for (int ks = 0; ks < KS; ++ks) {
-      const h8 wf = wn;
-      if (ks + 1 < KS) wn = wp[(size_t)(ks + 1) * 64];
-      const h8 b0 = *reinterpret_cast<const h8a*>(x0 + 16 * ks);
-      const h8 b1 = *reinterpret_cast<const h8a*>(x1 + 16 * ks);
-      acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf, b0, acc[0], 0, 0, 0);
-      acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf, b1, acc[1], 0, 0, 0);
-    }
-    epi(nt, 0, acc[0]);
-    epi(nt, 1, acc[1]);
-  }
-}
-
 // the f16 tile of the next product: Y [64, g.Npad], optional ReLU
-__device__ __forceinline__ void vn_stage(const char* __restrict__ img, const VadGemm& g, bool relu, const half_t* x, half_t* y, int ld,
+__device__ __forceinline__ void vn_stage(const char* __restrict__ img, const TileGemm& g, bool relu, const half_t* x, half_t* y, int ld,
                                          int wave, int lane) {
   const int r = lane & 31, h = lane >> 5;
-  vn_product(img, g, x, ld, wave, lane, [&](int nt, int i, const f16x& acc) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      h4 v;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float f = acc[4 * q + e];
-        if (relu) f = f < 0.f ? 0.f : f;
-        v[e] = (half_t)f;
-      }
-      *reinterpret_cast<h4a*>(y + (32 * i + r) * ld + 32 * nt + 8 * q + 4 * h) = v;
-    }
-  });
+  tr_product(img, g, x, ld, wave, lane, [&](int nt, int i, const f16x& acc) { tr_put_f16(acc, relu, y, ld, i, nt, r, h); });
 }
 
 }  // namespace
@@ -104,24 +58,7 @@ __global__ __launch_bounds__(256) void vadnet_kernel(VadNetLaunch a) {
   half_t* buf1 = buf0 + (size_t)VN_ROWS * ld;
   const long long g0 = (long long)blockIdx.x * VN_ROWS;
 
-  // ---- every row's utterance: the last b with off[b] <= row (utterances of no frame share their offset with the next one and
-  // are stepped over, because the search looks for the LAST such b below B)
-  if (tid < VN_ROWS) {
-    const long long g = g0 + tid;
-    long long start = 0;
-    int T = 0;
-    if (g < a.total) {
-      int lo = 0, hi = a.B - 1;                          // off[0] = 0 <= g < off[B] = total
-      while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (a.off[mid] <= g) lo = mid; else hi = mid - 1;
-      }
-      start = a.off[lo];
-      T = (int)(a.off[lo + 1] - start);
-    }
-    info.start[tid] = start;
-    info.T[tid] = T;
-  }
+  tr_row_info(a.off, a.B, a.total, g0, tid, info.start, info.T);       // every row's utterance
   __syncthreads();
 
   // ---- the head: the first f16 tile in buf0, width a.head_w (a multiple of 16), zeros in its padding columns and in rows
@@ -178,7 +115,7 @@ __global__ __launch_bounds__(256) void vadnet_kernel(VadNetLaunch a) {
   const int r = lane & 31, h = lane >> 5;
   if (a.tail == 0) {
     // ---- linear_l: p rows to memory, fp32, all ldp columns (the padding ones are exact zeros)
-    vn_product(a.img, a.last, cur, ld, wave, lane, [&](int nt, int i, const f16x& acc) {
+    tr_product(a.img, a.last, cur, ld, wave, lane, [&](int nt, int i, const f16x& acc) {
       const long long g = g0 + 32 * i + r;
       if (g < a.total) {
 #pragma unroll
@@ -194,7 +131,7 @@ __global__ __launch_bounds__(256) void vadnet_kernel(VadNetLaunch a) {
   const float* __restrict__ silf = reinterpret_cast<const float*>(a.img + a.sil_off);
   float mx[2] = {-INFINITY, -INFINITY}, sum[2] = {0.f, 0.f}, sil[2] = {0.f, 0.f};
   bool poisoned[2] = {false, false};
-  vn_product(a.img, a.last, cur, ld, wave, lane, [&](int nt, int i, const f16x& acc) {
+  tr_product(a.img, a.last, cur, ld, wave, lane, [&](int nt, int i, const f16x& acc) {
     const long long g = g0 + 32 * i + r;
     float tm = -INFINITY;
 #pragma unroll

@@ -1,7 +1,7 @@
 // kernels.h — launchers of the gfx950 kernels (implemented in k_*.hip)
 #pragma once
 #include "common.h"
-#include "vadnet.h"
+#include "tile_image.h"
 
 namespace pf {
 
@@ -501,8 +501,8 @@ struct VadNetLaunch {
   int head, head_w;                                             // head 0: LFR + CMVN over x; 1: the FSMN taps over p_in.  head_w: the tile's width
   const float* x; int n_mels, lfr_m, in_dim; int64_t shift_off, scale_off;
   const float* p_in; int64_t taps_off; int lorder, lstride, ldp;
-  int n_mid; VadGemm mid[2]; int mid_relu[2];                   // the products whose result stays in LDS as f16
-  int tail; VadGemm last;                                       // tail 0: `last` = linear_l -> p_out fp32 [total, ldp]; 1: out_linear2 -> softmax
+  int n_mid; TileGemm mid[2]; int mid_relu[2];                   // the products whose result stays in LDS as f16
+  int tail; TileGemm last;                                       // tail 0: `last` = linear_l -> p_out fp32 [total, ldp]; 1: out_linear2 -> softmax
   float* p_out;
   int64_t sil_off; int out_dim; float* logits; int32_t* levels; // logits [total, out_dim] / levels [total]: either may be null
 };
@@ -511,7 +511,7 @@ void launch_vadnet(hipStream_t s, const VadNetLaunch& a);
 
 // ---------------------------------------------------------------- the CT-Transformer punctuation model (k_punc.hip) ------
 // The definition in numpy is tests/punc_ref.py; the launch plan (2 + 2 n_layers launches per forward) is at the head of
-// k_punc.hip and Engine::run_punc fills these in.  img: the model's device image (punc.h); every *_off and VadGemm offset is a
+// k_punc.hip and Engine::run_punc fills these in.  img: the model's device image (punc.h); every *_off and TileGemm offset is a
 // byte offset into it.  Rows: `total` ids, window b at rows [off[b], off[b + 1]), at most PF_PUNC_MAX_WINDOW each.
 struct PuncRowsLaunch {
   const char* img; const int64_t* off; int B; int64_t total;
@@ -519,8 +519,8 @@ struct PuncRowsLaunch {
   int tail;                                                     // 0: LayerNorm (n_g, n_b) + `last` = qkv -> qkv_out; 1: + `last` = decoder -> logits / p
   float* x;                                                     // the residual stream fp32 [total, 256], updated in place
   const int32_t* ids; int64_t pe_off, embed_off;                // head 0
-  const half_t* ctx; const half_t* qkv_in; int64_t taps_off; int kernel; VadGemm out; int64_t n2_g, n2_b; VadGemm w1, w2;   // head 1
-  int64_t n_g, n_b; VadGemm last;
+  const half_t* ctx; const half_t* qkv_in; int64_t taps_off; int kernel; TileGemm out; int64_t n2_g, n2_b; TileGemm w1, w2;   // head 1
+  int64_t n_g, n_b; TileGemm last;
   half_t* qkv_out;                                              // tail 0: f16 [total, 768], q pre-scaled by dh^-0.5
   int n_punc; float* logits; int32_t* p;                        // tail 1: logits [total, n_punc] / p [total]: either may be null
 };

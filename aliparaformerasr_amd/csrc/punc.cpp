@@ -1,37 +1,21 @@
-// punc.cpp — the CT-Transformer punctuation model on the host (punc.h): the container loader, the float64 twins of
+// punc.cpp — the CT-Transformer punctuation model on the host (punc.h): the loader (on pfw.h's reader), the float64 twins of
 // k_punc.hip and of the text loop, and the builder of the kernel's weight image.  Uses no device.
 #include "punc.h"
 
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <map>
 
 #include "hostutil.h"
-#include "json.h"
+#include "pfw.h"
 
 namespace pf {
 
 namespace {
 
-constexpr int64_t kAlignBytes = 256;
 constexpr double kLnEps = 1e-12;                       // FunASR's LayerNorm(nout, eps = 1e-12)
 
-struct RawTensor { const char* p; std::vector<int64_t> shape; int64_t numel; bool u8; };
-
-void bad(const std::string& m) { throw Error(PF_ERR_INVALID_ARG, "punc model: " + m); }
-
-std::vector<float> take(const std::map<std::string, RawTensor>& ts, const std::string& name, std::vector<int64_t> shape) {
-  auto it = ts.find(name);
-  if (it == ts.end()) bad("tensor '" + name + "' is missing");
-  if (it->second.u8) bad("tensor '" + name + "' is not f32");
-  if (it->second.shape != shape) bad("tensor '" + name + "' has the wrong shape");
-  std::vector<float> v((size_t)it->second.numel);
-  std::memcpy(v.data(), it->second.p, v.size() * 4);                 // (the file's data section need not be 4-aligned in memory)
-  for (float x : v)
-    if (!std::isfinite(x)) bad("tensor '" + name + "' holds a value that is not finite");
-  return v;
-}
+void bad(const std::string& m) { pfw_bad(kPfwPuncModel, m); }
 
 // oracle/model.py sinusoidal_pe in its own float32 steps: positions 1 .. T, [sin || cos].  exp, sin and cos are taken in
 // double and rounded once (tests/punc_ref.py does the same): numpy's float32 forms of them are not one function on every host.
@@ -56,7 +40,7 @@ void build_image(PuncModel& m) {
   std::vector<float> pe;
   sinusoidal_pe(PF_PUNC_MAX_WINDOW, D, pe);
   m.pe_off = add_floats(img, pe.data(), PF_PUNC_MAX_WINDOW, D, D);
-  m.embed_off = round_up((int64_t)img.size(), kAlignBytes);
+  m.embed_off = round_up((int64_t)img.size(), 256);
   img.resize((size_t)(m.embed_off + (int64_t)m.vocab * D * 2), 0);
   {
     half_t* e = reinterpret_cast<half_t*>(img.data() + m.embed_off);
@@ -84,15 +68,9 @@ void build_image(PuncModel& m) {
 }
 
 std::shared_ptr<const PuncModel> parse(const char* data, int64_t nbytes) {
-  if (!data || nbytes < 16) bad("image too small");
-  if (std::memcmp(data, "PFW1", 4) != 0) bad("bad magic (expected a PFW1 container)");
-  uint64_t hlen = 0;
-  std::memcpy(&hlen, data + 8, 8);
-  if (hlen > (uint64_t)nbytes - 16u) bad("truncated header");
-  Json j = JsonParser(data + 16, (size_t)hlen).parse();
-  const Json* jc = j.get("config");
-  const Json* jt = j.get("tensors");
-  if (!jc || jc->type != Json::Obj || !jt || jt->type != Json::Arr) bad("the header lacks config / tensors");
+  const PfwFrame fr = pfw_frame(data, nbytes, kPfwPuncModel);
+  const PfwIndex ix = pfw_index(data + 16, fr.header_len, fr.data_bytes, kPfwPuncModel);
+  const Json* jc = &ix.config;
   if (jc->str_or("kind", "") != "cttransformer") bad("the container's kind is not \"cttransformer\"");
   auto dim = [&](const char* k) { return jc->int_or(k, -1, INT32_MIN, INT32_MAX); };
   auto m = std::make_shared<PuncModel>();
@@ -124,33 +102,12 @@ std::shared_ptr<const PuncModel> parse(const char* data, int64_t nbytes) {
   m->vocab = (int)V; m->d_model = (int)D; m->heads = (int)H; m->ffn = (int)F; m->kernel = (int)K; m->n_layers = (int)NL;
   m->n_punc = (int)P; m->sentence_end_id = (int)se;
 
-  const int64_t data_off = round_up((int64_t)(16 + hlen), kAlignBytes);
-  const int64_t data_bytes = nbytes - data_off;
-  if (data_bytes < 0) bad("truncated data section");
-  std::map<std::string, RawTensor> ts;
-  for (const Json& t : jt->arr) {
-    if (t.type != Json::Obj) bad("a tensor entry is no object");
-    const std::string name = t.str_or("name", "");
-    const std::string dt = t.str_or("dtype", "f32");
-    if (dt != "f32" && dt != "u8") bad("tensor '" + name + "' is neither f32 nor u8");
-    const int64_t off = t.int_or("offset", -1), nb = t.int_or("nbytes", -1);
-    if (off < 0 || nb < 0 || off > data_bytes || nb > data_bytes - off) bad("the extent of tensor '" + name + "' lies outside the file");
-    RawTensor r{data + data_off + off, {}, 1, dt == "u8"};
-    const Json* sh = t.get("shape");
-    if (!sh || sh->type != Json::Arr) bad("tensor '" + name + "' has no shape");
-    for (const Json& d : sh->arr) {
-      if (d.type != Json::Num || !(d.num >= 1.0 && d.num <= 1073741824.0) || d.num != (double)(int64_t)d.num) bad("bad dimension in the shape of '" + name + "'");
-      r.shape.push_back((int64_t)d.num);
-      if (r.numel > ((int64_t)1 << 31) / (int64_t)d.num) bad("the shape of '" + name + "' overflows");
-      r.numel *= (int64_t)d.num;
-    }
-    if (r.numel * (r.u8 ? 1 : 4) != nb) bad("shape / nbytes mismatch for '" + name + "'");
-    ts[name] = r;
-  }
+  const char* sec = data + fr.data_off;
+  auto take = [&](const std::string& name, std::vector<int64_t> shape) { return pfw_take(ix, sec, name, shape, kPfwPuncModel); };
   {
-    auto it = ts.find("vocab");
-    if (it == ts.end() || !it->second.u8 || it->second.shape.size() != 1) bad("the u8 tensor 'vocab' is missing");
-    const std::string all(it->second.p, (size_t)it->second.numel);
+    auto it = ix.tensors.find("vocab");
+    if (it == ix.tensors.end() || !it->second.u8 || it->second.shape.size() != 1) bad("the u8 tensor 'vocab' is missing");
+    const std::string all(sec + it->second.offset, (size_t)it->second.numel);
     size_t pos = 0;
     while (pos <= all.size()) {
       size_t e = all.find('\n', pos);
@@ -168,38 +125,23 @@ std::shared_ptr<const PuncModel> parse(const char* data, int64_t nbytes) {
     if (u == m->word_id.end()) bad("'vocab' lacks \"<unk>\"");
     m->unk_word = u->second;
   }
-  m->embed = take(ts, "embed.weight", {V, D});
+  m->embed = take("embed.weight", {V, D});
   for (int l = 0; l < (int)NL; ++l) {
     const std::string p = "layers." + std::to_string(l) + ".";
     PuncModel::Layer y;
-    y.n1_g = take(ts, p + "norm1.weight", {D}); y.n1_b = take(ts, p + "norm1.bias", {D});
-    y.qkv_w = take(ts, p + "attn.qkv.weight", {3 * D, D}); y.qkv_b = take(ts, p + "attn.qkv.bias", {3 * D});
-    y.fsmn = take(ts, p + "attn.fsmn.weight", {D, K});
-    y.out_w = take(ts, p + "attn.out.weight", {D, D}); y.out_b = take(ts, p + "attn.out.bias", {D});
-    y.n2_g = take(ts, p + "norm2.weight", {D}); y.n2_b = take(ts, p + "norm2.bias", {D});
-    y.w1_w = take(ts, p + "ffn.w1.weight", {F, D}); y.w1_b = take(ts, p + "ffn.w1.bias", {F});
-    y.w2_w = take(ts, p + "ffn.w2.weight", {D, F}); y.w2_b = take(ts, p + "ffn.w2.bias", {D});
+    y.n1_g = take(p + "norm1.weight", {D}); y.n1_b = take(p + "norm1.bias", {D});
+    y.qkv_w = take(p + "attn.qkv.weight", {3 * D, D}); y.qkv_b = take(p + "attn.qkv.bias", {3 * D});
+    y.fsmn = take(p + "attn.fsmn.weight", {D, K});
+    y.out_w = take(p + "attn.out.weight", {D, D}); y.out_b = take(p + "attn.out.bias", {D});
+    y.n2_g = take(p + "norm2.weight", {D}); y.n2_b = take(p + "norm2.bias", {D});
+    y.w1_w = take(p + "ffn.w1.weight", {F, D}); y.w1_b = take(p + "ffn.w1.bias", {F});
+    y.w2_w = take(p + "ffn.w2.weight", {D, F}); y.w2_b = take(p + "ffn.w2.bias", {D});
     m->layers.push_back(std::move(y));
   }
-  m->after_g = take(ts, "after_norm.weight", {D}); m->after_b = take(ts, "after_norm.bias", {D});
-  m->dec_w = take(ts, "decoder.weight", {P, D}); m->dec_b = take(ts, "decoder.bias", {P});
+  m->after_g = take("after_norm.weight", {D}); m->after_b = take("after_norm.bias", {D});
+  m->dec_w = take("decoder.weight", {P, D}); m->dec_b = take("decoder.bias", {P});
   build_image(*m);
   return m;
-}
-
-// y [T, N] = x [T, K] W^T + b in float64
-void affine64(const std::vector<double>& x, int T, int K, const std::vector<float>& w, const std::vector<float>& b, int N, bool relu,
-              std::vector<double>& y) {
-  y.assign((size_t)T * N, 0.0);
-  for (int t = 0; t < T; ++t)
-    for (int n = 0; n < N; ++n) {
-      double acc = 0.0;
-      const float* wr = w.data() + (size_t)n * K;
-      const double* xr = x.data() + (size_t)t * K;
-      for (int k = 0; k < K; ++k) acc += xr[k] * (double)wr[k];
-      acc += (double)b[(size_t)n];
-      y[(size_t)t * N + n] = (relu && acc < 0.0) ? 0.0 : acc;
-    }
 }
 
 void norm64(const std::vector<double>& x, int T, int D, const std::vector<float>& g, const std::vector<float>& b, std::vector<double>& y) {
@@ -224,8 +166,7 @@ std::shared_ptr<const PuncModel> punc_model_from_memory(const void* data, int64_
   try {
     return parse(static_cast<const char*>(data), nbytes);
   } catch (const Error& e) {
-    if (e.code == PF_ERR_INVALID_ARG || e.code == PF_ERR_UNSUPPORTED) throw;
-    throw Error(PF_ERR_INVALID_ARG, std::string("punc model: ") + e.what());      // a header that is no JSON, a number out of range
+    pfw_rethrow(kPfwPuncModel, e);                    // a config field that is no integer in range
   }
 }
 
@@ -282,7 +223,7 @@ void host_punc_logits(const PuncModel& m, const int32_t* ids, int T, double* log
   std::vector<double> ctx((size_t)T * D), s((size_t)T);
   for (const PuncModel::Layer& L : m.layers) {
     norm64(x, T, D, L.n1_g, L.n1_b, xn);
-    affine64(xn, T, D, L.qkv_w, L.qkv_b, 3 * D, false, qkv);
+    affine64(xn, T, D, L.qkv_w, &L.qkv_b, 3 * D, false, qkv);
     for (int hd = 0; hd < H; ++hd)
       for (int t = 0; t < T; ++t) {
         double mx = -INFINITY;
@@ -302,7 +243,7 @@ void host_punc_logits(const PuncModel& m, const int32_t* ids, int T, double* log
           ctx[(size_t)t * D + hd * dh + c] = a / sum;
         }
       }
-    affine64(ctx, T, D, L.out_w, L.out_b, D, false, att);
+    affine64(ctx, T, D, L.out_w, &L.out_b, D, false, att);
     for (int t = 0; t < T; ++t)
       for (int c = 0; c < D; ++c) {
         double f = qkv[(size_t)t * 3 * D + 2 * D + c];
@@ -313,12 +254,12 @@ void host_punc_logits(const PuncModel& m, const int32_t* ids, int T, double* log
         x[(size_t)t * D + c] += att[(size_t)t * D + c] + f;
       }
     norm64(x, T, D, L.n2_g, L.n2_b, xn);
-    affine64(xn, T, D, L.w1_w, L.w1_b, m.ffn, true, h);
-    affine64(h, T, m.ffn, L.w2_w, L.w2_b, D, false, y);
+    affine64(xn, T, D, L.w1_w, &L.w1_b, m.ffn, true, h);
+    affine64(h, T, m.ffn, L.w2_w, &L.w2_b, D, false, y);
     for (size_t i = 0; i < x.size(); ++i) x[i] += y[i];
   }
   norm64(x, T, D, m.after_g, m.after_b, xn);
-  affine64(xn, T, D, m.dec_w, m.dec_b, m.n_punc, false, y);
+  affine64(xn, T, D, m.dec_w, &m.dec_b, m.n_punc, false, y);
   std::memcpy(logits, y.data(), y.size() * 8);
 }
 

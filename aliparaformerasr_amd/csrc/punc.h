@@ -8,7 +8,7 @@
 #include <vector>
 
 #include "common.h"
-#include "vadnet.h"
+#include "tile_image.h"
 
 namespace pf {
 
@@ -31,13 +31,13 @@ struct PuncModel {
   std::vector<char> image;
   int64_t pe_off = 0;                   // fp32 [PF_PUNC_MAX_WINDOW, d_model]: sinusoidal_pe, positions 1 .. 512
   int64_t embed_off = 0;                // f16 [vocab, d_model] (rounding point R0e)
-  struct LayerImg { int64_t n1_g, n1_b, taps, n2_g, n2_b; VadGemm qkv, out, w1, w2; };   // taps fp32 [kernel, d_model]
+  struct LayerImg { int64_t n1_g, n1_b, taps, n2_g, n2_b; TileGemm qkv, out, w1, w2; };   // taps fp32 [kernel, d_model]
   std::vector<LayerImg> limg;
   int64_t after_g_off = 0, after_b_off = 0;
-  VadGemm dec;
+  TileGemm dec;
 };
 
-// PF_ERR_INVALID_ARG: not a PFW1 container of kind "cttransformer", truncated, an extent outside the file, a missing tensor, a
+// PF_ERR_INVALID_ARG: not a PFW1 container (pfw.h) of kind "cttransformer", a missing tensor, a
 // wrong shape, a non-finite value, a vocabulary that is not `vocab` distinct non-empty words or lacks "<unk>", a punc_list
 // without "<unk>" / "_", a sentence_end_id outside the list.  PF_ERR_UNSUPPORTED: d_model != 256, heads != 8, ffn no
 // multiple of 256 or above 4096, an even kernel or one above 31, more than 8 layers, fewer than 2 or more than 32 classes.

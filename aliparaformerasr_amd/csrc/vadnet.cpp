@@ -1,71 +1,19 @@
-// vadnet.cpp — the FSMN-VAD model score on the host (vadnet.h): the container loader, the float64 twins of k_vadnet.hip and
+// vadnet.cpp — the FSMN-VAD model score on the host (vadnet.h): the loader (on pfw.h's reader), the float64 twins of k_vadnet.hip and
 // the builder of the kernel's weight image.  Uses no device.
 #include "vadnet.h"
 
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <map>
 
 #include "hostutil.h"
-#include "json.h"
+#include "pfw.h"
 
 namespace pf {
 
 namespace {
 
-constexpr int64_t kAlignBytes = 256;
-
-struct RawTensor { const float* p; std::vector<int64_t> shape; int64_t numel; };
-
-void bad(const std::string& m) { throw Error(PF_ERR_INVALID_ARG, "vad model: " + m); }
-
-std::vector<float> take(const std::map<std::string, RawTensor>& ts, const std::string& name, std::vector<int64_t> shape) {
-  auto it = ts.find(name);
-  if (it == ts.end()) bad("tensor '" + name + "' is missing");
-  if (it->second.shape != shape) bad("tensor '" + name + "' has the wrong shape");
-  std::vector<float> v((size_t)it->second.numel);
-  std::memcpy(v.data(), it->second.p, v.size() * 4);                 // (the file's data section need not be 4-aligned in memory)
-  for (float x : v)
-    if (!std::isfinite(x)) bad("tensor '" + name + "' holds a value that is not finite");
-  return v;
-}
-
-}  // namespace
-
-// W [N, K] -> the MFMA fragments of vadnet.h, bias [N] (or none) -> fp32 [Npad]
-VadGemm add_gemm(std::vector<char>& img, const std::vector<float>& w, const std::vector<float>* bias, int N, int K) {
-  VadGemm g;
-  g.N = N; g.K = K; g.Npad = (int)round_up(N, 32); g.Kpad = (int)round_up(K, 16);
-  g.w_off = round_up((int64_t)img.size(), kAlignBytes);
-  const int64_t halves = (int64_t)g.Npad * g.Kpad;
-  g.b_off = round_up(g.w_off + halves * 2, kAlignBytes);
-  img.resize((size_t)(g.b_off + (int64_t)g.Npad * 4), 0);
-  half_t* wt = reinterpret_cast<half_t*>(img.data() + g.w_off);
-  const int KS = g.Kpad / 16;
-  for (int nt = 0; nt < g.Npad / 32; ++nt)
-    for (int ks = 0; ks < KS; ++ks)
-      for (int lane = 0; lane < 64; ++lane)
-        for (int j = 0; j < 8; ++j) {
-          const int n = 32 * nt + (lane & 31), k = 16 * ks + 8 * (lane >> 5) + j;
-          const float v = (n < N && k < K) ? w[(size_t)n * K + k] : 0.f;
-          wt[(((int64_t)nt * KS + ks) * 64 + lane) * 8 + j] = (half_t)v;       // rounding point R0
-        }
-  float* b = reinterpret_cast<float*>(img.data() + g.b_off);
-  for (int n = 0; n < g.Npad; ++n) b[n] = (bias && n < N) ? (*bias)[(size_t)n] : 0.f;
-  return g;
-}
-
-int64_t add_floats(std::vector<char>& img, const float* src, int64_t rows, int64_t cols, int64_t ld) {
-  const int64_t off = round_up((int64_t)img.size(), kAlignBytes);
-  img.resize((size_t)(off + rows * ld * 4), 0);
-  float* d = reinterpret_cast<float*>(img.data() + off);
-  for (int64_t r = 0; r < rows; ++r)
-    for (int64_t c = 0; c < cols; ++c) d[r * ld + c] = src[r * cols + c];
-  return off;
-}
-
-namespace {
+void bad(const std::string& m) { pfw_bad(kPfwVadModel, m); }
 
 void build_image(VadModel& m) {
   std::vector<char>& img = m.image;
@@ -86,21 +34,15 @@ void build_image(VadModel& m) {
   for (int32_t i : m.sil_ids) sil[(size_t)i] = 1.f;
   m.sil_off = add_floats(img, sil.data(), 1, m.g_out2.Npad, m.g_out2.Npad);
   int widest = std::max(m.g_in1.Kpad, m.ldp);
-  for (const VadGemm* g : {&m.g_in1, &m.g_in2, &m.g_out1}) widest = std::max(widest, g->Npad);
-  for (const VadGemm& g : m.g_aff) widest = std::max(widest, g.Npad);
+  for (const TileGemm* g : {&m.g_in1, &m.g_in2, &m.g_out1}) widest = std::max(widest, g->Npad);
+  for (const TileGemm& g : m.g_aff) widest = std::max(widest, g.Npad);
   m.lds_ld = widest + 8;
 }
 
 std::shared_ptr<const VadModel> parse(const char* data, int64_t nbytes) {
-  if (!data || nbytes < 16) bad("image too small");
-  if (std::memcmp(data, "PFW1", 4) != 0) bad("bad magic (expected a PFW1 container)");
-  uint64_t hlen = 0;
-  std::memcpy(&hlen, data + 8, 8);
-  if (hlen > (uint64_t)nbytes - 16u) bad("truncated header");
-  Json j = JsonParser(data + 16, (size_t)hlen).parse();
-  const Json* jc = j.get("config");
-  const Json* jt = j.get("tensors");
-  if (!jc || jc->type != Json::Obj || !jt || jt->type != Json::Arr) bad("the header lacks config / tensors");
+  const PfwFrame fr = pfw_frame(data, nbytes, kPfwVadModel);
+  const PfwIndex ix = pfw_index(data + 16, fr.header_len, fr.data_bytes, kPfwVadModel);
+  const Json* jc = &ix.config;
   if (jc->str_or("kind", "") != "fsmnvad") bad("the container's kind is not \"fsmnvad\"");
   auto dim = [&](const char* k) { return jc->int_or(k, -1, INT32_MIN, INT32_MAX); };
   auto m = std::make_shared<VadModel>();
@@ -125,60 +67,24 @@ std::shared_ptr<const VadModel> parse(const char* data, int64_t nbytes) {
     m->sil_ids.push_back((int32_t)s.num);
   }
 
-  const int64_t data_off = round_up((int64_t)(16 + hlen), kAlignBytes);
-  const int64_t data_bytes = nbytes - data_off;
-  if (data_bytes < 0) bad("truncated data section");
-  std::map<std::string, RawTensor> ts;
-  for (const Json& t : jt->arr) {
-    if (t.type != Json::Obj) bad("a tensor entry is no object");
-    const std::string name = t.str_or("name", "");
-    if (t.str_or("dtype", "f32") != "f32") bad("tensor '" + name + "' is not f32");
-    const int64_t off = t.int_or("offset", -1), nb = t.int_or("nbytes", -1);
-    if (off < 0 || nb < 0 || off > data_bytes || nb > data_bytes - off) bad("the extent of tensor '" + name + "' lies outside the file");
-    RawTensor r{reinterpret_cast<const float*>(data + data_off + off), {}, 1};
-    const Json* sh = t.get("shape");
-    if (!sh || sh->type != Json::Arr) bad("tensor '" + name + "' has no shape");
-    for (const Json& d : sh->arr) {
-      if (d.type != Json::Num || !(d.num >= 1.0 && d.num <= 1048576.0) || d.num != (double)(int64_t)d.num) bad("bad dimension in the shape of '" + name + "'");
-      r.shape.push_back((int64_t)d.num);
-      r.numel *= (int64_t)d.num;
-      if (r.numel > ((int64_t)1 << 30)) bad("the shape of '" + name + "' overflows");
-    }
-    if (r.numel * 4 != nb) bad("shape / nbytes mismatch for '" + name + "'");
-    ts[name] = r;
-  }
-  m->shift = take(ts, "cmvn.shift", {I});
-  m->scale = take(ts, "cmvn.scale", {I});
-  m->in1_w = take(ts, "in1.weight", {A, I}); m->in1_b = take(ts, "in1.bias", {A});
-  m->in2_w = take(ts, "in2.weight", {L, A}); m->in2_b = take(ts, "in2.bias", {L});
+  auto take = [&](const std::string& name, std::vector<int64_t> shape) { return pfw_take(ix, data + fr.data_off, name, shape, kPfwVadModel); };
+  m->shift = take("cmvn.shift", {I});
+  m->scale = take("cmvn.scale", {I});
+  m->in1_w = take("in1.weight", {A, I}); m->in1_b = take("in1.bias", {A});
+  m->in2_w = take("in2.weight", {L, A}); m->in2_b = take("in2.bias", {L});
   for (int l = 0; l < (int)NL; ++l) {
     const std::string p = "fsmn." + std::to_string(l) + ".";
     VadModel::Layer y;
-    y.lin_w = take(ts, p + "linear.weight", {P, L});
-    y.taps = take(ts, p + "taps", {lorder, P});
-    y.aff_w = take(ts, p + "affine.weight", {L, P});
-    y.aff_b = take(ts, p + "affine.bias", {L});
+    y.lin_w = take(p + "linear.weight", {P, L});
+    y.taps = take(p + "taps", {lorder, P});
+    y.aff_w = take(p + "affine.weight", {L, P});
+    y.aff_b = take(p + "affine.bias", {L});
     m->layers.push_back(std::move(y));
   }
-  m->out1_w = take(ts, "out1.weight", {A, L}); m->out1_b = take(ts, "out1.bias", {A});
-  m->out2_w = take(ts, "out2.weight", {O, A}); m->out2_b = take(ts, "out2.bias", {O});
+  m->out1_w = take("out1.weight", {A, L}); m->out1_b = take("out1.bias", {A});
+  m->out2_w = take("out2.weight", {O, A}); m->out2_b = take("out2.bias", {O});
   build_image(*m);
   return m;
-}
-
-// y [T, N] = x [T, K] W^T + b in float64
-void affine64(const std::vector<double>& x, int64_t T, int K, const std::vector<float>& w, const std::vector<float>* b, int N, bool relu,
-              std::vector<double>& y) {
-  y.assign((size_t)T * N, 0.0);
-  for (int64_t t = 0; t < T; ++t)
-    for (int n = 0; n < N; ++n) {
-      double acc = 0.0;
-      const float* wr = w.data() + (size_t)n * K;
-      const double* xr = x.data() + (size_t)t * K;
-      for (int k = 0; k < K; ++k) acc += xr[k] * (double)wr[k];
-      if (b) acc += (double)(*b)[(size_t)n];
-      y[(size_t)t * N + n] = (relu && acc < 0.0) ? 0.0 : acc;
-    }
 }
 
 void logits64(const VadModel& m, const float* rows, int64_t T, int n_mels, std::vector<double>& z) {
@@ -239,8 +145,7 @@ std::shared_ptr<const VadModel> vad_model_from_memory(const void* data, int64_t 
   try {
     return parse(static_cast<const char*>(data), nbytes);
   } catch (const Error& e) {
-    if (e.code == PF_ERR_INVALID_ARG || e.code == PF_ERR_UNSUPPORTED) throw;
-    throw Error(PF_ERR_INVALID_ARG, std::string("vad model: ") + e.what());      // a header that is no JSON, a number out of range
+    pfw_rethrow(kPfwVadModel, e);                     // a config field that is no integer in range
   }
 }
 

@@ -7,20 +7,12 @@
 #include <vector>
 
 #include "common.h"
+#include "tile_image.h"
 
 namespace pf {
 
 // limits of the loader (PF_ERR_UNSUPPORTED beyond them): two [64, widest + 8] f16 tiles must fit the 160 KB of LDS
 constexpr int kVadMaxWidth = 512, kVadMaxProj = 256, kVadMaxLayers = 8, kVadMaxReach = 256, kVadMaxLfr = 16;
-
-// one matrix product of the device image: W [N, K] fp32 as f16 fragments of the 32x32x16 MFMA, rows padded to Npad (a
-// multiple of 32) and columns to Kpad (a multiple of 16) with zeros: halves [Npad / 32][Kpad / 16][64 lanes][8], lane
-// (r = lane & 31, h = lane >> 5) holding W[32 nt + r][16 ks + 8 h + j]; bias fp32 [Npad] (zeros where the product has none)
-struct VadGemm { int64_t w_off = 0, b_off = 0; int N = 0, K = 0, Npad = 0, Kpad = 0; };
-
-// the builders of such an image (also used by punc.cpp): both append at the next 256-byte boundary and return the offset(s)
-VadGemm add_gemm(std::vector<char>& img, const std::vector<float>& w, const std::vector<float>* bias, int N, int K);
-int64_t add_floats(std::vector<char>& img, const float* src, int64_t rows, int64_t cols, int64_t ld);
 
 struct VadModel {
   int input_dim = 0, affine_dim = 0, linear_dim = 0, proj_dim = 0, output_dim = 0, n_layers = 0, lorder = 0, lstride = 0, lfr_m = 0;
@@ -30,8 +22,8 @@ struct VadModel {
   std::vector<Layer> layers;
   // the device image: what an engine uploads, byte for byte (offsets in bytes, each 256-aligned)
   std::vector<char> image;
-  VadGemm g_in1, g_in2, g_out1, g_out2;
-  std::vector<VadGemm> g_lin, g_aff;
+  TileGemm g_in1, g_in2, g_out1, g_out2;
+  std::vector<TileGemm> g_lin, g_aff;
   std::vector<int64_t> taps_off;        // fp32 [lorder, ldp] per layer
   int64_t shift_off = 0, scale_off = 0, sil_off = 0;   // fp32 [input_dim] each; fp32 [g_out2.Npad]: 1 on a silence id, else 0
   int ldp = 0;                          // row stride of the p rows: proj_dim padded to 32
@@ -39,7 +31,7 @@ struct VadModel {
   const std::vector<float>* tensor(const std::string& name) const;     // by its container name; nullptr: no such tensor
 };
 
-// PF_ERR_INVALID_ARG: not a PFW1 container of kind "fsmnvad", truncated, an extent outside the file, a missing tensor, a
+// PF_ERR_INVALID_ARG: not a PFW1 container (pfw.h) of kind "fsmnvad", a u8 tensor, a missing tensor, a
 // wrong shape, a non-finite value, a silence id outside [0, output_dim).  PF_ERR_UNSUPPORTED: rorder > 0, lfr_n != 1, a
 // dimension beyond the limits above.
 std::shared_ptr<const VadModel> vad_model_from_memory(const void* data, int64_t nbytes);

@@ -1,4 +1,4 @@
-// Mutation fuzz of the host-side parsers that read files a user hands over (csrc/json.h: PFW header / asr.json;
+// Mutation fuzz of the host-side parsers that read files a user hands over (csrc/json.h, csrc/pfw.cpp: PFW header / asr.json;
 // csrc/hostutil.cpp: asr.yaml, am.mvn, tokens, RIFF/WAVE, resampler, UTF-8), built with AddressSanitizer + UBSan
 // (tests/test_native_host.py builds and runs it).  Every input either parses or throws pf::Error; nothing else.
 //   usage: host_fuzz <iterations> <scratch dir>
@@ -8,6 +8,7 @@
 #include <fstream>
 
 #include "hostutil.h"
+#include "pfw.h"
 
 static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
 static uint32_t rnd() {
@@ -75,6 +76,7 @@ int main(int argc, char** argv) {
       (void)v.num_or("x", 1); (void)v.str_or("kind", ""); (void)v.bool_or("use_itn", false);
       if (const pf::Json* t = v.get("tensors")) for (const pf::Json& e : t->arr) { (void)e.str_or("name", ""); (void)e.num_or("offset", -1); }
     }, ok, err);
+    guarded([&] { (void)pf::pfw_index(j.data(), (int64_t)j.size(), 1 << 21, it & 1 ? pf::kPfwWeights : pf::kPfwPuncModel); }, ok, err);
     guarded([&] { (void)pf::conf_from_json(j); }, ok, err);
     const std::string y = mutate(yaml_seed);
     guarded([&] { (void)pf::conf_from_yaml(y); }, ok, err);

@@ -164,7 +164,7 @@ def test_recognizer_without_device_fails_loudly(tmp_path):
 
 @pytest.mark.timeout(300)
 def test_host_parsers_under_sanitizers(tmp_path):
-    """csrc/json.h + csrc/hostutil.cpp (PFW header / asr.json / asr.yaml / am.mvn / RIFF-WAVE / resampler / UTF-8) built
+    """csrc/json.h + csrc/pfw.cpp + csrc/hostutil.cpp (PFW header / asr.json / asr.yaml / am.mvn / RIFF-WAVE / resampler / UTF-8) built
     with AddressSanitizer + UBSan on the host code and fed mutated files (tests/native/host_fuzz.cpp): every input parses or is
     rejected with a pf::Error, no report.  (Round 3: `"lfr_n": 1e400` used to be cast to int — now PF_ERR_FORMAT.)"""
     import shutil
@@ -178,6 +178,7 @@ def test_host_parsers_under_sanitizers(tmp_path):
     b = subprocess.run([hipcc, "-x", "hip", "--offload-arch=gfx950", "-g", "-O1", "-fsanitize=address,undefined", "-fno-gpu-sanitize",
                         "-fno-omit-frame-pointer",
                         "-std=c++17", "-I" + cs, os.path.join(root, "tests", "native", "host_fuzz.cpp"), os.path.join(cs, "hostutil.cpp"),
+                        os.path.join(cs, "pfw.cpp"),
                         "-o", exe], capture_output=True, text=True)
     if b.returncode != 0:
         pytest.skip("sanitizer runtime not available: " + b.stderr[-300:])

@@ -8,6 +8,7 @@ import struct
 import numpy as np
 import pytest
 
+from pfw_helpers import repack
 import punc_ref as R
 from aliparaformerasr_amd import _native as N
 from aliparaformerasr_amd import engine as E
@@ -251,20 +252,6 @@ def test_assembly_rules(model):
 
 
 # ---- the container -------------------------------------------------------------------------------------------------------
-def _repack(cfg, w, edit_header=None):
-    blob = bytearray(W.pack_pfw(cfg, w))
-    if edit_header:
-        hlen = struct.unpack_from("<Q", blob, 8)[0]
-        hdr = json.loads(bytes(blob[16:16 + hlen]).decode())
-        base = (16 + hlen + 255) // 256 * 256
-        data = bytes(blob[base:])
-        edit_header(hdr)
-        h2 = json.dumps(hdr).encode()
-        pre = 16 + len(h2)
-        blob = bytearray(b"PFW1" + struct.pack("<IQ", 1, len(h2)) + h2 + b"\0" * ((-pre) % 256) + data)
-    return bytes(blob)
-
-
 def _refusals():
     cfg, w = _model(1)
     good = W.pack_pfw(cfg, w)
@@ -281,7 +268,7 @@ def _refusals():
     vocab = R.vocab_of(w)
     enc = lambda words: np.frombuffer("\n".join(words).encode("utf-8"), dtype=np.uint8).copy()
     inv = [("short", good[:40]), ("cut tail", good[: len(good) - 237]), ("half", good[: len(good) // 2]), ("empty", b""),
-           ("offset", _repack(cfg, w, far)), ("nbytes", _repack(cfg, w, big)),
+           ("offset", repack(cfg, w, far)), ("nbytes", repack(cfg, w, big)),
            ("header length", good[:8] + struct.pack("<Q", (1 << 64) - 8) + good[16:]), ("magic", b"XXXX" + good[4:]),
            ("kind", with_(kind="fsmnvad")), ("nan", tensor("decoder.bias", nan)), ("inf", tensor("embed.weight", inf)),
            ("shape", tensor("layers.0.attn.fsmn.weight", lambda a: a[:, :9].copy())),
@@ -340,7 +327,7 @@ def test_loader_under_sanitizers(tmp_path):
     exe = str(tmp_path / "punc_sanitize")
     b = subprocess.run([hipcc, "-x", "hip", "--offload-arch=gfx950", "-g", "-O1", "-fsanitize=address,undefined", "-fno-gpu-sanitize",
                         "-fno-omit-frame-pointer", "-std=c++17", "-I" + cs, os.path.join(root, "tests", "native", "punc_sanitize.cpp"),
-                        os.path.join(cs, "punc.cpp"), os.path.join(cs, "vadnet.cpp"), os.path.join(cs, "hostutil.cpp"), os.path.join(cs, "lm.cpp"),
+                        os.path.join(cs, "punc.cpp"), os.path.join(cs, "pfw.cpp"), os.path.join(cs, "hostutil.cpp"), os.path.join(cs, "lm.cpp"),
                         "-o", exe], capture_output=True, text=True)
     if b.returncode != 0:
         # only a missing sanitizer runtime is a reason to skip; a compile error in the sources under test is a failure

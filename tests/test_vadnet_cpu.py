@@ -9,6 +9,7 @@ import struct
 import numpy as np
 import pytest
 
+from pfw_helpers import repack
 import vad_ref as V
 import vadnet_ref as R
 from aliparaformerasr_amd import _native as N
@@ -124,22 +125,6 @@ def test_container_round_trip(model, tmp_path):
     assert cfg2 == json.loads(json.dumps(cfg)) and set(w2) == set(W.vad_tensor_shapes(cfg))
 
 
-def _repack(cfg, w, edit_header=None, cut=None):
-    blob = bytearray(W.pack_pfw(cfg, w))
-    if edit_header:
-        hlen = struct.unpack_from("<Q", blob, 8)[0]
-        hdr = json.loads(bytes(blob[16:16 + hlen]).decode())
-        base = (16 + hlen + 255) // 256 * 256
-        data = bytes(blob[base:])
-        edit_header(hdr)
-        h2 = json.dumps(hdr).encode()
-        pre = 16 + len(h2)
-        blob = bytearray(b"PFW1" + struct.pack("<IQ", 1, len(h2)) + h2 + b"\0" * ((-pre) % 256) + data)
-    if cut is not None:
-        blob = blob[:cut]
-    return bytes(blob)
-
-
 def _refused(blob, code=N.PF_ERR_INVALID_ARG):
     with pytest.raises(N.PfError) as ei:
         E.load_vad_model(blob)
@@ -162,10 +147,10 @@ def test_malformed_containers_are_refused():
     def neg(h): h["tensors"][0]["offset"] = -256
     def mism(h): h["tensors"][2]["shape"] = [h["tensors"][2]["shape"][0] + 1, h["tensors"][2]["shape"][1]]
     for edit in (far, big, neg, mism):
-        _refused(_repack(cfg, w, edit))
+        _refused(repack(cfg, w, edit))
     # wrong kind, a recogniser's container
     def kind(h): h["config"]["kind"] = "paraformer"
-    _refused(_repack(cfg, w, kind))
+    _refused(repack(cfg, w, kind))
     pcfg = W.paraformer_large_config(enc_layers=1, dec_layers=1, vocab=16)
     _refused(W.pack_pfw(pcfg, {"encoder.after_norm.weight": np.ones(512, np.float32)}))
     # a weight that is not finite, a shape that does not follow the dimensions, a missing tensor, a bad silence id
@@ -351,7 +336,7 @@ def test_loader_under_sanitizers(tmp_path):
     exe = str(tmp_path / "vadnet_sanitize")
     b = subprocess.run([hipcc, "-x", "hip", "--offload-arch=gfx950", "-g", "-O1", "-fsanitize=address,undefined", "-fno-gpu-sanitize",
                         "-fno-omit-frame-pointer", "-std=c++17", "-I" + cs, os.path.join(root, "tests", "native", "vadnet_sanitize.cpp"),
-                        os.path.join(cs, "vadnet.cpp"), os.path.join(cs, "hostutil.cpp"), os.path.join(cs, "lm.cpp"), "-o", exe],
+                        os.path.join(cs, "vadnet.cpp"), os.path.join(cs, "pfw.cpp"), os.path.join(cs, "hostutil.cpp"), os.path.join(cs, "lm.cpp"), "-o", exe],
                        capture_output=True, text=True)
     if b.returncode != 0:
         # only a missing sanitizer runtime is a reason to skip; a compile error in the sources under test is a failure
@@ -365,7 +350,7 @@ def test_loader_under_sanitizers(tmp_path):
 
     def far(h): h["tensors"][3]["offset"] = 1 << 40
     def big(h): h["tensors"][-1]["nbytes"] = h["tensors"][-1]["nbytes"] + 4096
-    blobs = [good, good[:40], good[: len(good) - 237], good[: len(good) // 2], _repack(cfg, w, far), _repack(cfg, w, big),
+    blobs = [good, good[:40], good[: len(good) - 237], good[: len(good) // 2], repack(cfg, w, far), repack(cfg, w, big),
              W.pack_pfw(cfg, w_nan), W.pack_pfw(dict(cfg, kind="paraformer"), w), W.pack_pfw(dict(cfg, rorder=2), w),
              good[:8] + struct.pack("<Q", (1 << 64) - 8) + good[16:], b""]
     paths = []

@@ -29,7 +29,7 @@ for san in thread address; do
   echo "== copy helpers of the staged uploads ($san sanitizer)"
   TSAN_OPTIONS=halt_on_error=1 "$OUT/copycrew_$san" 60
 done
-"$HIPCC" -x hip --offload-arch=gfx950 $SAN -O1 -std=c++17 -I"$CS" "$ROOT/tests/native/host_fuzz.cpp" "$CS/hostutil.cpp" -o "$OUT/host_fuzz" 2>&1 | grep -v "Woption-ignored\|^$" || true
+"$HIPCC" -x hip --offload-arch=gfx950 $SAN -O1 -std=c++17 -I"$CS" "$ROOT/tests/native/host_fuzz.cpp" "$CS/hostutil.cpp" "$CS/pfw.cpp" -o "$OUT/host_fuzz" 2>&1 | grep -v "Woption-ignored\|^$" || true
 mkdir -p "$OUT/scratch"
 echo "== host parsers (ASan + UBSan)"
 UBSAN_OPTIONS=halt_on_error=1 "$OUT/host_fuzz" "$IT" "$OUT/scratch"
