@@ -113,6 +113,15 @@ class PfGemmDesc(C.Structure):
     ]
 
 
+class PfLinear32Desc(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32), ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32),
+        ("lda", C.c_int32), ("ldw", C.c_int32), ("ldc", C.c_int32), ("ldr", C.c_int32),
+        ("resid_aliases_out", C.c_int32), ("relu", C.c_int32), ("scale_cols", C.c_int32), ("scale", C.c_float), ("flags", C.c_int32),
+        ("bias", C.POINTER(C.c_float)), ("resid", C.POINTER(C.c_float)), ("resid2", C.POINTER(C.c_float)),
+    ]
+
+
 class PfQgemmDesc(C.Structure):
     _fields_ = [
         ("struct_size", C.c_int32), ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32),
@@ -326,6 +335,11 @@ SIGNATURES = {
     "pf_op_fsmn_enc": (C.c_int, [_vp, _f, _f, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f]),
     "pf_op_linear32": (C.c_int, [_vp, _f, _f, _f, _f, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f]),
     "pf_op_ffn32": (C.c_int, [_vp, _f, _f, _f, _f, _f, C.c_int32, C.c_int32, C.c_int32, _f]),
+    "pf_op_linear32_ex": (C.c_int, [_vp, _P(PfLinear32Desc), _f, _f, _f]),
+    "pf_op_split_x3": (C.c_int, [_vp, _f, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P(C.c_uint16)]),
+    "pf_op_layernorm32": (C.c_int, [_vp, _f, _f, _f, C.c_int32, C.c_int32, C.c_int32, _f, _P(C.c_uint16), _i32, _f, _f, C.c_int32, _f]),
+    "pf_op_ffn32_ex": (C.c_int, [_vp, _f, _f, _f, _f, _f, C.c_int32, C.c_int32, C.c_int32, C.c_float, _f, _P(C.c_uint16), _i32]),
+    "pf_op_qkv32": (C.c_int, [_vp, _f, _f, _f, C.c_int32, C.c_int32, C.c_int32, C.c_float, _f]),
     "pf_op_fsmn_dec": (C.c_int, [_vp, _f, _f, _i32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f]),
     "pf_op_lstm": (C.c_int, [_vp, _f, _f, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f]),
     "pf_op_us_peak": (C.c_int, [_vp, _f, _f, _f, C.c_float, C.c_float, _i32, C.c_float, C.c_int32, C.c_int32, C.c_int32, _f, _f, _f]),

@@ -1522,6 +1522,64 @@ int pf_op_ffn32(pf_engine* h, const float* x, const float* W1, const float* b1, 
   return PF_OK;
   PF_CATCH
 }
+int pf_op_linear32_ex(pf_engine* h, const pf_linear32_desc* d, const float* A, const float* W, float* C) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  NEED(d); NEED(A); NEED(W); NEED(C);
+  PF_CHECK(d->struct_size == (int32_t)sizeof(pf_linear32_desc), PF_ERR_INVALID_ARG, "linear32_ex: struct_size mismatch");
+  PF_CHECK(d->M > 0 && d->N > 0 && d->K > 0, PF_ERR_INVALID_ARG, "linear32_ex: bad shape");
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->op_linear32_ex(*d, A, W, C);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_op_split_x3(pf_engine* h, const float* x, int32_t rows, int32_t K, int32_t ldx, int32_t ldo, int32_t Kp, int32_t swap, uint16_t* out) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  NEED(x); NEED(out);
+  PF_CHECK(rows > 0 && K > 0 && Kp >= K && Kp % 4 == 0 && ldx >= K && ldo >= 2 * Kp && ldo % 4 == 0, PF_ERR_INVALID_ARG, "split_x3: bad shape");
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->op_split_x3(x, rows, K, ldx, ldo, Kp, swap, out);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_op_layernorm32(pf_engine* h, const float* x, const float* gamma, const float* beta, int32_t M, int32_t D, int32_t direct_pair,
+                      float* out32, uint16_t* pair, int32_t* wrote_pair, const float* W, const float* bias, int32_t N, float* y) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  NEED(x); NEED(gamma); NEED(beta); NEED(out32); NEED(pair); NEED(wrote_pair);
+  PF_CHECK(M > 0 && D > 0 && D % 4 == 0 && (!W || (N > 0 && y)), PF_ERR_INVALID_ARG, "layernorm32: bad shape");
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->op_layernorm32(x, gamma, beta, M, D, direct_pair, out32, pair, wrote_pair, W, bias, N, y);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_op_ffn32_ex(pf_engine* h, const float* x, const float* W1, const float* b1, const float* W2, const float* b2, int32_t M,
+                   int32_t D, int32_t F, float hidden_scale, float* y, uint16_t* hidden_pair, int32_t* pair_written) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  NEED(x); NEED(W1); NEED(b1); NEED(W2); NEED(b2); NEED(y); NEED(hidden_pair); NEED(pair_written);
+  PF_CHECK(M > 0 && D > 0 && F > 0, PF_ERR_INVALID_ARG, "ffn32_ex: bad shape");
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->op_ffn32_ex(x, W1, b1, W2, b2, M, D, F, hidden_scale, y, hidden_pair, pair_written);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_op_qkv32(pf_engine* h, const float* x, const float* W, const float* bias, int32_t M, int32_t D, int32_t K, float qscale, float* out) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  NEED(x); NEED(W); NEED(bias); NEED(out);
+  PF_CHECK(M > 0 && D > 0 && K > 0 && D % 4 == 0, PF_ERR_INVALID_ARG, "qkv32: bad shape");
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->op_qkv32(x, W, bias, M, D, K, qscale, out);
+  return PF_OK;
+  PF_CATCH
+}
 int pf_op_fsmn_dec(pf_engine* h, const float* tn, const float* w, const int32_t* token_num, int32_t B, int32_t L,
                    int32_t D, int32_t k, float* x) {
   PF_TRY

@@ -286,6 +286,14 @@ class Engine {
   void op_gemm_panel(int M, int N, int out_kind, int form, int padded, const float* bias, const float* A, const float* W, float* C);
   void op_linear32(const float* x, const float* W, const float* bias, const float* resid, int M, int N, int K, bool relu, float* y);
   void op_ffn32(const float* x, const float* W1, const float* b1, const float* W2, const float* b2, int M, int D, int F, float* y);
+  // the fp32 graph's Linear, split, LayerNorm, FFN chain and Q, K, V triple on hostile hosts (tests/test_gpu_fp32_conformance.py)
+  void op_linear32_ex(const pf_linear32_desc& d, const float* A, const float* W, float* C);
+  void op_split_x3(const float* x, int rows, int K, int ldx, int ldo, int Kp, int swap, uint16_t* out);
+  void op_layernorm32(const float* x, const float* gamma, const float* beta, int M, int D, int direct_pair, float* out32, uint16_t* pair,
+                      int32_t* wrote_pair, const float* W, const float* bias, int N, float* y);
+  void op_ffn32_ex(const float* x, const float* W1, const float* b1, const float* W2, const float* b2, int M, int D, int F, float hidden_scale,
+                   float* y, uint16_t* hidden_pair, int32_t* pair_written);
+  void op_qkv32(const float* x, const float* W, const float* bias, int M, int D, int K, float qscale, float* out);
   void op_gemm_rc(const pf_gemm_rc_desc& d, const float* A, const float* W, float* x_out, float* n16_out, float* n32_out);
   // DynamicQuantizeLinear(x) + MatMulInteger + rescale (+ bias) (+ ReLU) on the int8 MFMA; optional outputs: the uint8
   // activations [M, K], {a_scale, a_zp}, the uint8 weights [N, K] and their per-channel scale / zero point
@@ -474,6 +482,7 @@ class Engine {
   void layernorm32(const float* x, int M, int D, const LNp& ln, float* xn);
   bool x3a_pair_only_ = false;       // x3a_src_ exists ONLY as the pair in ws_x3a_ (its fp32 form was never written)
   bool x3_mode_ = false;             // math_mode 3: the fp32 graph with every large Linear as three f16 MFMA products of (hi, lo') operand pairs
+  void x3_poison(int M, int N, int K);     // stand-alone ops: the three x3 arenas at the size an [M, K] x [N, K] product needs, filled with a large finite pattern
   void x3_forget(const float* W);          // drops W's cached pair image (stand-alone ops: their weights live in a scratch arena)
   std::map<std::pair<const float*, int>, half_t*> x3w_;   // (fp32 weight, rows N) -> its [lo' | hi] f16 pair image (built on first use; the fused
                                                           // Q | K | V product and the three separate ones name the same first row)

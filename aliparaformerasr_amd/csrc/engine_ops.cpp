@@ -895,6 +895,263 @@ void Engine::op_ffn32(const float* x, const float* W1, const float* b1, const fl
   x3a_src_ = nullptr;
 }
 
+// ---- the fp32 graph's Linear on hostile hosts (tests/test_gpu_fp32_conformance.py): every fp32 matrix is uploaded as an image
+// whose cells outside the matrix hold the large finite pattern (rows behind the last, the columns between the width and the row
+// stride), the three x3 arenas are filled with a large finite pattern before the call (so a pad row or pad column that reached
+// a cell of [M, N] would be seen), every result sits in a sentinel-filled buffer.
+namespace {
+constexpr uint16_t kPoison16 = 0x7A5Au;                       // 52 032 as f16; two of them are 2.8e35 as an fp32 word
+
+inline float hostile32(size_t i) { return std::ldexp(1.0f + (float)((i * 37u) & 0x3FFu) / 1024.0f, 100) * ((i & 1u) ? -1.0f : 1.0f); }
+
+// device image [rows, ld] of the host matrix src [m, n] (dense rows; null: nothing inside), hostile everywhere else
+void upload_hostile32(hipStream_t s, float* dev, int64_t rows, int ld, const float* src, int m, int n) {
+  std::vector<float> h((size_t)rows * ld);
+  for (size_t i = 0; i < h.size(); ++i) h[i] = hostile32(i);
+  if (src)
+    for (int r = 0; r < m; ++r) std::memcpy(&h[(size_t)r * ld], src + (size_t)r * n, (size_t)n * 4);
+  PF_HIP(hipMemcpyAsync(dev, h.data(), h.size() * 4, hipMemcpyHostToDevice, s));
+  PF_HIP(hipStreamSynchronize(s));
+}
+// f16 cells [row0, row1) x [0, ld) of an arena that was filled with kPoison16: nothing may have been stored there
+void check_poison16(hipStream_t s, const char* op, const char* what, const void* dev, int ld, int64_t row0, int64_t row1) {
+  if (row1 <= row0) return;
+  std::vector<uint16_t> h((size_t)(row1 - row0) * ld);
+  PF_HIP(hipMemcpyAsync(h.data(), (const uint16_t*)dev + (size_t)row0 * ld, h.size() * 2, hipMemcpyDeviceToHost, s));
+  PF_HIP(hipStreamSynchronize(s));
+  for (size_t i = 0; i < h.size(); ++i)
+    if (h[i] != kPoison16)
+      throw Error(PF_ERR_DEVICE, std::string(op) + ": " + what + ": cell (" + std::to_string(row0 + (int64_t)(i / ld)) + ", " + std::to_string(i % ld) + ") was written");
+}
+}  // namespace
+
+void Engine::x3_poison(int M, int N, int K) {
+  if (!x3_mode_) return;
+  const int64_t Mp = round_up(M, 256) + 128, Kp = round_up(K, 64);
+  ensure(ws_x3a_, (size_t)Mp * 2 * Kp * 2);
+  ensure(ws_x3t_, (size_t)Mp * round_up(N, 4) * 4);
+  ensure(ws_x3h_, (size_t)Mp * 2 * round_up(N, 64) * 2);
+  for (DevBuf* b : {&ws_x3a_, &ws_x3t_, &ws_x3h_}) PF_HIP(hipMemsetD16Async((hipDeviceptr_t)b->p, kPoison16, b->bytes / 2, stream_));
+}
+
+void Engine::op_linear32_ex(const pf_linear32_desc& ds, const float* A, const float* W, float* C) {
+  PF_CHECK(fp32_mode_, PF_ERR_UNSUPPORTED, "linear32_ex: the engine was not created with math_mode 1 or 3");
+  PF_HIP(hipSetDevice(device_));
+  const int M = ds.M, N = ds.N, K = ds.K;
+  const bool alias = ds.resid_aliases_out != 0;
+  const int lda = ds.lda ? ds.lda : K, ldw = ds.ldw ? ds.ldw : K, ldc = ds.ldc ? ds.ldc : (int)round_up(N, 4);
+  const int ldr = alias ? ldc : (ds.ldr ? ds.ldr : ldc);
+  PF_CHECK(lda >= K && ldw >= K && ldc >= N && ldr >= N, PF_ERR_INVALID_ARG, "linear32_ex: a row stride is narrower than its matrix");
+  PF_CHECK(!alias || ds.resid, PF_ERR_INVALID_ARG, "linear32_ex: resid_aliases_out without a residual");
+  const int64_t Mp = round_up(M, 256) + 128, Np = round_up(N, 256);
+  size_t off = 0;
+  const Carve carve{off};
+  const size_t oA = carve((size_t)Mp * lda * 4), oW = carve((size_t)Np * ldw * 4), ob = carve((size_t)Np * 4), oR = carve((size_t)Mp * ldr * 4),
+               oR2 = carve((size_t)Mp * ldr * 4), oC = carve((size_t)Mp * ldc * 4);
+  ensure(ws_tmp_, off);
+  char* base = (char*)ws_tmp_.p;
+  upload_hostile32(stream_, (float*)(base + oA), Mp, lda, A, M, K);
+  upload_hostile32(stream_, (float*)(base + oW), Np, ldw, W, N, K);
+  upload_hostile32(stream_, (float*)(base + ob), 1, (int)Np, ds.bias, 1, N);
+  if (ds.resid && !alias) upload_hostile32(stream_, (float*)(base + oR), Mp, ldr, ds.resid, M, N);
+  if (ds.resid2) upload_hostile32(stream_, (float*)(base + oR2), Mp, ldr, ds.resid2, M, N);
+  fill_sentinel32(stream_, base + oC, (size_t)Mp * ldc);
+  if (alias) PF_HIP(hipMemcpy2DAsync(base + oC, (size_t)ldc * 4, ds.resid, (size_t)N * 4, (size_t)N * 4, M, hipMemcpyHostToDevice, stream_));
+  x3_poison(M, N, K);
+  const float* Wd = (const float*)(base + oW);
+  float* out = (float*)(base + oC);
+  auto done = [&] { x3_forget(Wd); x3a_src_ = nullptr; x3a_pair_only_ = false; x3_pair_live_ = false; cls32_ = "gemm32_misc"; };
+  try {
+    cls32_ = "gemm32_op";
+    gemm32((const float*)(base + oA), lda, Wd, ldw, ds.bias ? (const float*)(base + ob) : nullptr, M, N, K, out, ldc,
+           ds.resid ? (alias ? out : (const float*)(base + oR)) : nullptr, ldr, ds.relu != 0, ds.scale_cols, ds.scale, ds.flags,
+           ds.resid2 ? (const float*)(base + oR2) : nullptr);
+    check_guard<uint32_t>(stream_, "linear32_ex", "the fp32 result", out, kSentinel32, Mp, M, N, ldc, false, !alias, M);
+  } catch (...) {
+    done();
+    throw;
+  }
+  done();
+  PF_HIP(hipMemcpy2DAsync(C, (size_t)N * 4, out, (size_t)ldc * 4, (size_t)N * 4, M, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipStreamSynchronize(stream_));
+}
+
+void Engine::op_split_x3(const float* x, int rows, int K, int ldx, int ldo, int Kp, int swap, uint16_t* out) {
+  PF_HIP(hipSetDevice(device_));
+  const int64_t Rp = (int64_t)rows + 64;
+  size_t off = 0;
+  const Carve carve{off};
+  const size_t ox = carve((size_t)Rp * ldx * 4), oo = carve((size_t)Rp * ldo * 2);
+  ensure(ws_tmp_, off);
+  char* base = (char*)ws_tmp_.p;
+  upload_hostile32(stream_, (float*)(base + ox), Rp, ldx, x, rows, K);
+  fill_sentinel16(stream_, base + oo, (size_t)Rp * ldo);
+  launch_split_x3(stream_, (const float*)(base + ox), rows, K, ldx, (half_t*)(base + oo), ldo, Kp, swap);
+  check_guard<uint16_t>(stream_, "split_x3", "the pair", base + oo, kSentinel16, Rp, rows, 2 * Kp, ldo, false, true, rows);
+  PF_HIP(hipMemcpyAsync(out, base + oo, (size_t)rows * ldo * 2, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipStreamSynchronize(stream_));
+}
+
+void Engine::op_layernorm32(const float* x, const float* gamma, const float* beta, int M, int D, int direct_pair, float* out32, uint16_t* pair,
+                            int32_t* wrote_pair, const float* W, const float* bias, int N, float* y) {
+  PF_CHECK(fp32_mode_, PF_ERR_UNSUPPORTED, "layernorm32: the engine was not created with math_mode 1 or 3");
+  PF_HIP(hipSetDevice(device_));
+  if (!W) N = 4;
+  const int ldc = (int)round_up(N, 4), ldo = 2 * D + 8;
+  const int64_t Mp = round_up(M, 256) + 128, Np = round_up(N, 256);
+  size_t off = 0;
+  const Carve carve{off};
+  const size_t ox = carve((size_t)Mp * D * 4), og = carve((size_t)D * 4), obt = carve((size_t)D * 4), on = carve((size_t)Mp * D * 4),
+               op = carve((size_t)Mp * ldo * 2), oW = carve((size_t)Np * D * 4), ob = carve((size_t)Np * 4), oy = carve((size_t)Mp * ldc * 4);
+  ensure(ws_tmp_, off);
+  char* base = (char*)ws_tmp_.p;
+  upload_hostile32(stream_, (float*)(base + ox), Mp, D, x, M, D);
+  PF_HIP(hipMemcpyAsync(base + og, gamma, (size_t)D * 4, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipMemcpyAsync(base + obt, beta, (size_t)D * 4, hipMemcpyHostToDevice, stream_));
+  const float* xd = (const float*)(base + ox);
+  float* xn = (float*)(base + on);
+  *wrote_pair = 0;
+  if (direct_pair) {
+    PF_CHECK(D == 512, PF_ERR_INVALID_ARG, "layernorm32: the pair kernel is the D = 512 kernel");
+    fill_sentinel16(stream_, base + op, (size_t)Mp * ldo);
+    launch_layernorm_pair(stream_, xd, M, (const float*)(base + og), (const float*)(base + obt), (half_t*)(base + op), ldo, D);
+    check_guard<uint16_t>(stream_, "layernorm32", "the pair", base + op, kSentinel16, Mp, M, 2 * D, ldo, false, true, M);
+    PF_HIP(hipMemcpy2DAsync(pair, (size_t)2 * D * 2, base + op, (size_t)ldo * 2, (size_t)2 * D * 2, M, hipMemcpyDeviceToHost, stream_));
+    PF_HIP(hipStreamSynchronize(stream_));
+    *wrote_pair = 1;
+    return;
+  }
+  if (W) {
+    upload_hostile32(stream_, (float*)(base + oW), Np, D, W, N, D);
+    upload_hostile32(stream_, (float*)(base + ob), 1, (int)Np, bias, 1, N);
+    fill_sentinel32(stream_, base + oy, (size_t)Mp * ldc);
+  }
+  fill_sentinel32(stream_, xn, (size_t)Mp * D);
+  x3_poison(M, N, D);
+  const float* Wd = (const float*)(base + oW);
+  auto done = [&] { x3_forget(Wd); x3a_src_ = nullptr; x3a_pair_only_ = false; x3_pair_live_ = false; cls32_ = "gemm32_misc"; };
+  try {
+    LNp ln;
+    ln.g = (const float*)(base + og); ln.b = (const float*)(base + obt); ln.D = D;
+    layernorm32(xd, M, D, ln, xn);
+    if (x3a_pair_only_ && x3a_src_ == xn) {
+      *wrote_pair = 1;
+      check_untouched32(stream_, "layernorm32", "the fp32 row buffer beside the pair", xn, (size_t)Mp * D * 4);
+      check_poison16(stream_, "layernorm32", "the pair arena behind row M - 1", ws_x3a_.p, 2 * D, M, Mp);
+      PF_HIP(hipMemcpyAsync(pair, ws_x3a_.p, (size_t)M * 2 * D * 2, hipMemcpyDeviceToHost, stream_));
+    } else {
+      check_guard<uint32_t>(stream_, "layernorm32", "the fp32 rows", xn, kSentinel32, Mp, M, D, D, false, true, M);
+      PF_HIP(hipMemcpyAsync(out32, xn, (size_t)M * D * 4, hipMemcpyDeviceToHost, stream_));
+    }
+    PF_HIP(hipStreamSynchronize(stream_));
+    if (W) {
+      cls32_ = "gemm32_op";
+      gemm32(xn, D, Wd, D, bias ? (const float*)(base + ob) : nullptr, M, N, D, (float*)(base + oy), ldc, nullptr, 0, false, 0, 1.f);
+      check_guard<uint32_t>(stream_, "layernorm32", "the product behind it", base + oy, kSentinel32, Mp, M, N, ldc, false, true, M);
+      PF_HIP(hipMemcpy2DAsync(y, (size_t)N * 4, base + oy, (size_t)ldc * 4, (size_t)N * 4, M, hipMemcpyDeviceToHost, stream_));
+      PF_HIP(hipStreamSynchronize(stream_));
+    }
+  } catch (...) {
+    done();
+    throw;
+  }
+  done();
+}
+
+void Engine::op_ffn32_ex(const float* x, const float* W1, const float* b1, const float* W2, const float* b2, int M, int D, int F, float hidden_scale,
+                         float* y, uint16_t* hidden_pair, int32_t* pair_written) {
+  PF_CHECK(fp32_mode_, PF_ERR_UNSUPPORTED, "ffn32_ex: the engine was not created with math_mode 1 or 3");
+  PF_CHECK(D % 4 == 0 && F % 4 == 0, PF_ERR_INVALID_ARG, "ffn32_ex: D and F must be multiples of 4");
+  PF_HIP(hipSetDevice(device_));
+  const int64_t Mp = round_up(M, 256) + 128, Dp = round_up(D, 256), Fp = round_up(F, 256);
+  size_t off = 0;
+  const Carve carve{off};
+  const size_t ox = carve((size_t)Mp * D * 4), o1 = carve((size_t)Fp * D * 4), ob1 = carve((size_t)Fp * 4), o2 = carve((size_t)Dp * F * 4),
+               ob2 = carve((size_t)Dp * 4), oh = carve((size_t)Mp * F * 4), oy = carve((size_t)Mp * D * 4);
+  ensure(ws_tmp_, off);
+  char* base = (char*)ws_tmp_.p;
+  upload_hostile32(stream_, (float*)(base + ox), Mp, D, x, M, D);
+  upload_hostile32(stream_, (float*)(base + o1), Fp, D, W1, F, D);
+  upload_hostile32(stream_, (float*)(base + ob1), 1, (int)Fp, b1, 1, F);
+  upload_hostile32(stream_, (float*)(base + o2), Dp, F, W2, D, F);
+  upload_hostile32(stream_, (float*)(base + ob2), 1, (int)Dp, b2, 1, D);
+  fill_sentinel32(stream_, base + oh, (size_t)Mp * F);
+  fill_sentinel32(stream_, base + oy, (size_t)Mp * D);
+  x3_poison(M, std::max(D, F), std::max(D, F));
+  const float* xd = (const float*)(base + ox);
+  const float* w1 = (const float*)(base + o1);
+  const float* w2 = (const float*)(base + o2);
+  auto done = [&] { x3_forget(w1); x3_forget(w2); x3a_src_ = nullptr; x3a_pair_only_ = false; x3_pair_live_ = false; cls32_ = "gemm32_misc"; };
+  *pair_written = 0;
+  try {
+    const bool scaled = hidden_scale != 1.0f;
+    cls32_ = "gemm32_ffn1";
+    gemm32(xd, D, w1, D, (const float*)(base + ob1), M, F, D, (float*)(base + oh), F, nullptr, 0, true, scaled ? F : 0, hidden_scale, kX3OutPair);
+    if (x3_pair_live_) {
+      *pair_written = 1;
+      const int ldp = 2 * (int)round_up(F, 64);
+      check_untouched32(stream_, "ffn32_ex", "the fp32 hidden beside its pair", base + oh, (size_t)Mp * F * 4);
+      check_poison16(stream_, "ffn32_ex", "the pair arena at and beyond round_up(M, 256)", ws_x3h_.p, ldp, round_up(M, 256), Mp);
+      PF_HIP(hipMemcpy2DAsync(hidden_pair, (size_t)2 * F * 2, ws_x3h_.p, (size_t)ldp * 2, (size_t)F * 2, M, hipMemcpyDeviceToHost, stream_));
+      PF_HIP(hipMemcpy2DAsync(hidden_pair + F, (size_t)2 * F * 2, (const uint16_t*)ws_x3h_.p + ldp / 2, (size_t)ldp * 2, (size_t)F * 2, M,
+                              hipMemcpyDeviceToHost, stream_));
+      PF_HIP(hipStreamSynchronize(stream_));
+    } else {
+      check_guard<uint32_t>(stream_, "ffn32_ex", "the fp32 hidden", base + oh, kSentinel32, Mp, M, F, F, false, true, M);
+    }
+    cls32_ = "gemm32_ffn2";
+    gemm32((const float*)(base + oh), F, w2, F, (const float*)(base + ob2), M, D, F, (float*)(base + oy), D, xd, D, false, 0, 1.f, kX3InPair);
+    check_guard<uint32_t>(stream_, "ffn32_ex", "the fp32 result", base + oy, kSentinel32, Mp, M, D, D, false, true, M);
+  } catch (...) {
+    done();
+    throw;
+  }
+  done();
+  PF_HIP(hipMemcpyAsync(y, base + oy, (size_t)M * D * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipStreamSynchronize(stream_));
+}
+
+void Engine::op_qkv32(const float* x, const float* W, const float* bias, int M, int D, int K, float qscale, float* out) {
+  PF_CHECK(fp32_mode_, PF_ERR_UNSUPPORTED, "qkv32: the engine was not created with math_mode 1 or 3");
+  PF_HIP(hipSetDevice(device_));
+  const int64_t Mp = round_up(M, 256) + 128, Np = round_up(3 * D, 256);
+  size_t off = 0;
+  const Carve carve{off};
+  const size_t ox = carve((size_t)Mp * K * 4), oW = carve((size_t)Np * K * 4), ob = carve((size_t)Np * 4);
+  size_t oq[3];
+  for (int i = 0; i < 3; ++i) oq[i] = carve((size_t)Mp * D * 4);
+  ensure(ws_tmp_, off);
+  char* base = (char*)ws_tmp_.p;
+  upload_hostile32(stream_, (float*)(base + ox), Mp, K, x, M, K);
+  upload_hostile32(stream_, (float*)(base + oW), Np, K, W, 3 * D, K);
+  upload_hostile32(stream_, (float*)(base + ob), 1, (int)Np, bias, 1, 3 * D);
+  for (int i = 0; i < 3; ++i) fill_sentinel32(stream_, base + oq[i], (size_t)Mp * D);
+  x3_poison(M, D, K);
+  const float* xd = (const float*)(base + ox);
+  const float* Wd = (const float*)(base + oW);
+  const float* bd = (const float*)(base + ob);
+  auto done = [&] {
+    for (int i = 0; i < 3; ++i) x3_forget(Wd + (size_t)i * D * K);
+    x3a_src_ = nullptr; x3a_pair_only_ = false; x3_pair_live_ = false; cls32_ = "gemm32_misc";
+  };
+  static const char* const cls[3] = {"gemm32_op_q", "gemm32_op_k", "gemm32_op_v"};
+  try {
+    for (int i = 0; i < 3; ++i) {                                // as enc_layer_fp32 launches the three
+      cls32_ = cls[i];
+      gemm32(xd, K, Wd + (size_t)i * D * K, K, bd + (size_t)i * D, M, D, K, (float*)(base + oq[i]), D, nullptr, 0, false, i == 0 ? D : 0,
+             i == 0 ? qscale : 1.f, i == 0 ? 0 : kX3SameInput);
+      check_guard<uint32_t>(stream_, "qkv32", cls[i], base + oq[i], kSentinel32, Mp, M, D, D, false, true, M);
+    }
+  } catch (...) {
+    done();
+    throw;
+  }
+  done();
+  for (int i = 0; i < 3; ++i)
+    PF_HIP(hipMemcpy2DAsync(out + (size_t)i * D, (size_t)3 * D * 4, base + oq[i], (size_t)D * 4, (size_t)D * 4, M, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipStreamSynchronize(stream_));
+}
+
 // GEMM exactly as the pipeline launches it: kernel kind (fp32 / f16 row-major / f16 blocked result), tile height,
 // blocked A operand, residual / second addend, column scaling — the stand-alone counterpart of Engine::gemm().
 void Engine::op_gemm_ex(const pf_gemm_desc& ds, const float* A, const float* W, float* C) {

@@ -61,6 +61,7 @@ void launch_gemm_f32(hipStream_t s, const float* A, int lda, const float* W, int
                      float* out, int ldc, const float* resid, int ldr, bool relu, int scale_cols, float scale) {
   if (M <= 0 || N <= 0) return;
   G32Dev d{A, W, bias, resid, out, lda, ldw, ldr, ldc, M, N, K, relu ? 1 : 0, scale_cols, scale_cols > 0 ? scale : 1.f};
+  note_gemm_kernel("gemm_f32_kernel");
   hipLaunchKernelGGL(gemm_f32_kernel, dim3((unsigned)cdiv(N, 64), (unsigned)cdiv(M, 64)), dim3(256), 0, s, d);
   PF_HIP(hipGetLastError());
 }
@@ -251,7 +252,9 @@ void launch_attention_f32(hipStream_t s, const float* q, int64_t q_bs, int q_rs,
 
 // ---- "x3" products (math_mode 3): an fp32 value as TWO f16 numbers, hi = f16(x) and lo' = f16((x - hi) * 2^11) — 22 bits of
 // mantissa, the low part kept in the normal range by the scaling — so that x y = hi_x hi_y + 2^-11 (hi_x lo'_y + lo'_x hi_y)
-// up to 2^-22 relative: three f16 MFMA products (16x the fp32 matrix rate each) with fp32 accumulation.
+// up to 3 * 2^-22 relative (one 2^-22 per operand's pair and one for the dropped lo lo term): three f16 MFMA products (16x the
+// fp32 matrix rate each) with fp32 accumulation.  The 22 bits hold for 2^-14 <= |x| < 65520: below, hi is an f16 subnormal and
+// the scaled low part one as well (|x - (hi + lo'/2^11)| up to 2^-36, absolute); beyond, hi overflows (kernels.h).
 // Row r of x [rows, K] (fp32, row stride ldx) -> out[r, 0:Kp] | out[r, Kp:2 Kp] = hi | lo' (swap = 0) or lo' | hi (swap = 1);
 // columns K..Kp-1 of both halves are zeroed.
 __global__ __launch_bounds__(256) void split_x3_kernel(const float* __restrict__ x, int64_t rows, int K, int ldx, half_t* __restrict__ out,

@@ -255,13 +255,26 @@ void launch_ffn_dec_retile(hipStream_t s, const half_t* W1, int ldw1, const floa
 void launch_ffn_dec(hipStream_t s, const FfnDecArgs& a);
 
 // ---------------------------------------------------------------- fp32 parity mode (k_fp32.hip) ----
+// C[M,N] = A[M,K] W[N,K]^T on v_mfma_f32_32x32x2_f32 (gemm_f32_kernel): fp32 operands, none truncated (a one-term product comes
+// back as fl32(a w), the float64 product rounded once), fp32 accumulation in k order.  Epilogue order: + bias, x scale (columns
+// n < scale_cols, any value: no multiple of 64 needed), + resid, ReLU.  Any M, N, K >= 1 and any lda, ldw >= K, ldc, ldr >= N.
+//   read     A rows [0, M) and W rows [0, N), columns [0, K) of both, nothing else (no pad row, no pad column: rows behind M - 1 / N - 1
+//            and the columns [K, ld) may hold anything); bias elements [0, N); resid rows [0, M), columns [0, N); resid may
+//            alias out (each cell is read and written by the same lane);
+//   written  out rows [0, M), columns [0, N), nothing else.
 void launch_gemm_f32(hipStream_t s, const float* A, int lda, const float* W, int ldw, const float* bias, int M, int N, int K,
                      float* out, int ldc, const float* resid, int ldr, bool relu, int scale_cols, float scale);
 void launch_attention_f32(hipStream_t s, const float* q, int64_t q_bs, int q_rs, const float* k, int64_t k_bs, int k_rs,
                           const float* v, int64_t v_bs, int v_rs, float* o, int64_t o_bs, int o_rs, int B, int H, int Lq, int Lk);
 bool launch_attention_f32_pair(hipStream_t s, const float* q, int64_t q_bs, int q_rs, const float* k, int64_t k_bs, int k_rs,
                                const float* v, int64_t v_bs, int v_rs, half_t* pair, int64_t p_bs, int p_rs, int p_lo, int B, int H, int Lq, int Lk);
-// x [rows, K] fp32 -> out [rows, 2 Kp] f16 = hi | lo' (swap: lo' | hi), lo' = f16((x - hi) * 2^11); Kp % 4 == 0, pad columns zeroed
+// x [rows, K] fp32 -> out [rows, 2 Kp] f16 = hi | lo' (swap: lo' | hi), hi = f16(x) (round to nearest even), lo' = f16((x - hi) * 2^11):
+// x - hi and its 2^11-fold are exact in fp32, so the pair is a function of x alone, bit for bit.  Kp % 4 == 0, Kp >= K, ldo % 4 == 0,
+// ldo >= 2 Kp.  Domain: finite |x| < 65520 (beyond, hi is infinite and lo' a NaN).  hi + lo'/2048 is x up to 2^-22 (1 + 2^-11) |x| for
+// |x| >= 2^-14; below, hi is an f16 subnormal and lo' one as well: up to 2^-36 absolute (fp32 subnormals split into (+-0, +-0)).
+//   read     x rows [0, rows), columns [0, K), nothing else;
+//   written  out rows [0, rows), columns [0, 2 Kp): both halves' pad columns [K, Kp) as zeros; never a column in [2 Kp, ldo) or a row
+//            at or beyond `rows`.
 void launch_split_x3(hipStream_t s, const float* x, int64_t rows, int K, int ldx, half_t* out, int ldo, int Kp, int swap);
 void launch_im2col_f32(hipStream_t s, const float* H, int B, int T, int D, int l_order, int r_order, float* out);
 void launch_add_f32(hipStream_t s, float* x, const float* y, int64_t n);     // x += y
@@ -293,8 +306,13 @@ void launch_pad_sentinel(hipStream_t s, const float* feats, const int64_t* feat_
 void launch_posenc_ln_tab(hipStream_t s, const float* speech, int B, int T, int F, float xscale, const float* pe,
                       const float* gamma, const float* beta, half_t* out, int ldo);
 // LayerNorm rows of width D (512 or 2048, or generic) : fp32 in -> f16 and/or fp32 out
+// D = 512; the result leaves ONLY as the (hi | lo') operand pair of an x3 product: the pair is launch_split_x3's of the fp32
+// value the kernel formed (hi = f16(y), lo' = f16((y - hi) * 2^11)); ldo % 4 == 0, lo_off % 4 == 0, lo_off >= 512.
+//   read     x rows [0, rows), columns [0, 512) (row stride 512); gamma, beta [0, 512);
+//   written  out rows [0, rows), columns [0, 512) and [lo_off, lo_off + 512), nothing else — the columns between the halves and
+//            behind them keep what they held, so a consumer with Kp > 512 pad columns must have zeroed them itself.
 void launch_layernorm_pair(hipStream_t s, const float* x, int64_t rows, const float* gamma, const float* beta, half_t* out, int ldo,
-                           int lo_off);     // D = 512; result as the (hi | lo') operand pair of an x3 product only (k_norm.hip)
+                           int lo_off);
 void launch_layernorm(hipStream_t s, const float* x, int64_t rows, int D, const float* gamma,
                       const float* beta, half_t* out16, int ld16, float* out32, int ld32);
 

@@ -1602,6 +1602,70 @@ class Engine:
         N.check(self._lib.pf_op_ffn32(self._h, _fp(x), _fp(W1), _fp(b1), _fp(W2), _fp(b2), M, D, F, _fp(y)))
         return y
 
+    def op_linear32_ex(self, A, W, bias=None, resid=None, resid2=None, relu=False, scale_cols=0, scale=1.0, lda=0, ldw=0, ldc=0, ldr=0,
+                       resid_aliases_out=False, flags=0) -> np.ndarray:
+        """Engine::gemm32 on a hostile host with every argument selectable (pf_op_linear32_ex)."""
+        A, W = _f32(A), _f32(W)
+        M, K = A.shape
+        Nn = W.shape[0]
+        d = N.PfLinear32Desc()
+        d.struct_size = C.sizeof(N.PfLinear32Desc)
+        d.M, d.N, d.K = M, Nn, K
+        d.lda, d.ldw, d.ldc, d.ldr = lda, ldw, ldc, ldr
+        d.resid_aliases_out, d.relu, d.scale_cols, d.scale, d.flags = int(resid_aliases_out), int(relu), scale_cols, scale, flags
+        keep = [_f32(t) if t is not None else None for t in (bias, resid, resid2)]
+        d.bias, d.resid, d.resid2 = [_fp(t) if t is not None else None for t in keep]
+        out = np.zeros((M, Nn), np.float32)
+        N.check(self._lib.pf_op_linear32_ex(self._h, C.byref(d), _fp(A), _fp(W), _fp(out)))
+        return out
+
+    def op_split_x3(self, x, Kp, ldx=0, ldo=0, swap=0) -> np.ndarray:
+        """split_x3_kernel alone: the [rows, ldo] uint16 image of the pair buffer, pre-filled with 0x7E5A (pf_op_split_x3)."""
+        x = _f32(x)
+        rows, K = x.shape
+        ldx, ldo = ldx or K, ldo or 2 * Kp
+        out = np.zeros((rows, ldo), np.uint16)
+        N.check(self._lib.pf_op_split_x3(self._h, _fp(x), rows, K, ldx, ldo, Kp, swap, out.ctypes.data_as(C.POINTER(C.c_uint16))))
+        return out
+
+    def op_layernorm32(self, x, gamma, beta, direct_pair=False, W=None, bias=None):
+        """Engine::layernorm32 (pf_op_layernorm32): (out32 or None, (hi, lo') float16 or None, y or None)."""
+        x, gamma, beta = _f32(x), _f32(gamma), _f32(beta)
+        M, D = x.shape
+        out32 = np.zeros((M, D), np.float32)
+        pair = np.zeros((M, 2 * D), np.uint16)
+        wrote = C.c_int32(0)
+        Wk = _f32(W) if W is not None else None
+        bk = _f32(bias) if bias is not None else None
+        Nn = Wk.shape[0] if Wk is not None else 0
+        y = np.zeros((M, max(Nn, 1)), np.float32)
+        N.check(self._lib.pf_op_layernorm32(self._h, _fp(x), _fp(gamma), _fp(beta), M, D, int(direct_pair), _fp(out32),
+                                            pair.ctypes.data_as(C.POINTER(C.c_uint16)), C.byref(wrote),
+                                            _fp(Wk) if Wk is not None else None, _fp(bk) if bk is not None else None, Nn, _fp(y)))
+        hl = (pair[:, :D].view(np.float16), pair[:, D:].view(np.float16)) if wrote.value else None
+        return (None if wrote.value else out32), hl, (y if Wk is not None else None)
+
+    def op_ffn32_ex(self, x, W1, b1, W2, b2, hidden_scale=1.0):
+        """pf_op_ffn32 on a hostile host, the hidden optionally scaled (pf_op_ffn32_ex): (y, (hi, lo') of the hidden or None)."""
+        x, W1, b1, W2, b2 = _f32(x), _f32(W1), _f32(b1), _f32(W2), _f32(b2)
+        M, D = x.shape
+        F = W1.shape[0]
+        y = np.zeros((M, D), np.float32)
+        pair = np.zeros((M, 2 * F), np.uint16)
+        wrote = C.c_int32(0)
+        N.check(self._lib.pf_op_ffn32_ex(self._h, _fp(x), _fp(W1), _fp(b1), _fp(W2), _fp(b2), M, D, F, hidden_scale, _fp(y),
+                                         pair.ctypes.data_as(C.POINTER(C.c_uint16)), C.byref(wrote)))
+        return y, ((pair[:, :F].view(np.float16), pair[:, F:].view(np.float16)) if wrote.value else None)
+
+    def op_qkv32(self, x, W, bias, qscale) -> np.ndarray:
+        """Q, K and V of the fp32 graph as three Linears on one operand (pf_op_qkv32): [M, 3 D]."""
+        x, W, bias = _f32(x), _f32(W), _f32(bias)
+        M, K = x.shape
+        D = W.shape[0] // 3
+        out = np.zeros((M, 3 * D), np.float32)
+        N.check(self._lib.pf_op_qkv32(self._h, _fp(x), _fp(W), _fp(bias), M, D, K, qscale, _fp(out)))
+        return out
+
     def op_fsmn_dec(self, tn, w, token_num, x) -> np.ndarray:
         tn, w, x = _f32(tn), _f32(w), _f32(x).copy()
         B, L, D = tn.shape

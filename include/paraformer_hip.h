@@ -1070,6 +1070,45 @@ int pf_op_linear32(pf_engine* e, const float* x, const float* W, const float* bi
    the (hi, lo') operand pair of the second (what the encoder layers do). */
 int pf_op_ffn32(pf_engine* e, const float* x, const float* W1, const float* b1, const float* W2, const float* b2, int32_t M,
                 int32_t D, int32_t F, float* y);
+/* The same Linear on a hostile host, every argument of Engine::gemm32 selectable: A [M,K] and W [N,K] are placed with the row
+   strides lda / ldw (0 = K), the result with ldc (0 = round_up(N, 4)), the residual with ldr (0 = ldc) or, resid_aliases_out != 0,
+   in the result buffer itself (what the layers do with the residual stream); resid2 is gemm32's second addend (row stride
+   ldr).  Whatever lies outside the matrices holds a large finite pattern, the x3 arenas are filled with one before the call,
+   and the result buffer is checked for unwritten cells of [M,N] and for stores outside it.  flags: gemm32's (1 = result as an
+   operand pair, 2 = operand is that pair, 4 = same operand as the previous call).  The kernels that ran are read with
+   pf_profile_kernel: class "gemm32_op" (math_mode 3, two-launch form: the second launch; the first is "gemm32_x3_main"). */
+typedef struct pf_linear32_desc {
+  int32_t struct_size;
+  int32_t M, N, K;
+  int32_t lda, ldw, ldc, ldr;
+  int32_t resid_aliases_out;
+  int32_t relu;
+  int32_t scale_cols;         /* columns n < scale_cols are multiplied by scale (after the bias); 0 = none */
+  float scale;
+  int32_t flags;
+  const float* bias;          /* [N] or NULL   */
+  const float* resid;         /* [M,N] or NULL */
+  const float* resid2;        /* [M,N] or NULL */
+} pf_linear32_desc;
+int pf_op_linear32_ex(pf_engine* e, const pf_linear32_desc* d, const float* A, const float* W, float* C);
+/* split_x3_kernel alone: x [rows,K] (placed with row stride ldx >= K) -> out [rows, ldo] f16 bit patterns, hi at columns
+   [0, Kp), lo' at [Kp, 2 Kp) (swap != 0: the other way round); the buffer is pre-filled with 0x7E5A and checked for stores
+   behind row rows - 1.  Domain: finite |x| < 65520. */
+int pf_op_split_x3(pf_engine* e, const float* x, int32_t rows, int32_t K, int32_t ldx, int32_t ldo, int32_t Kp, int32_t swap, uint16_t* out);
+/* LayerNorm of the fp32 graph (Engine::layernorm32): x [M,D] -> out32 [M,D], or, where math_mode 3 writes the operand pair
+   instead (D = 512, M above the short-input threshold), pair [M, 2 D] = hi | lo' f16 bit patterns and *wrote_pair = 1 (out32 is
+   then left alone).  direct_pair != 0: launch_layernorm_pair itself at any M (D = 512).  W [N,D] != NULL: followed by the
+   consuming gemm32, y [M,N] = LayerNorm(x) W^T + bias — the hand-over through the arena as the encoder layers do it. */
+int pf_op_layernorm32(pf_engine* e, const float* x, const float* gamma, const float* beta, int32_t M, int32_t D, int32_t direct_pair,
+                      float* out32, uint16_t* pair, int32_t* wrote_pair, const float* W, const float* bias, int32_t N, float* y);
+/* pf_op_ffn32 on a hostile host with the hidden scaled by hidden_scale (1 = no scale) before the ReLU:
+   y = x + relu((x W1^T + b1) s) W2^T + b2.  Where the hidden travels as an operand pair, hidden_pair [M, 2 F] receives its
+   hi | lo' bit patterns and *pair_written = 1.  Profile classes "gemm32_ffn1" and "gemm32_ffn2". */
+int pf_op_ffn32_ex(pf_engine* e, const float* x, const float* W1, const float* b1, const float* W2, const float* b2, int32_t M,
+                   int32_t D, int32_t F, float hidden_scale, float* y, uint16_t* hidden_pair, int32_t* pair_written);
+/* Q, K and V of the fp32 graph as three gemm32 calls on ONE operand (the second and third with "same operand"):
+   out [M, 3 D] = x [M,K] W [3 D,K]^T + bias, the first D columns times qscale.  Classes "gemm32_op_q", "gemm32_op_k", "gemm32_op_v". */
+int pf_op_qkv32(pf_engine* e, const float* x, const float* W, const float* bias, int32_t M, int32_t D, int32_t K, float qscale, float* out);
 /* Encoder FSMN kernel (f16 V slice of a [B*T, 3D] buffer in, fp32 out): y = dwconv_k(v) + v. */
 int pf_op_fsmn_enc(pf_engine* e, const float* v, const float* w, int32_t B, int32_t T, int32_t D, int32_t k, float* y);
 /* Decoder FSMN kernel: x += (dwconv_k(tn*m) + tn*m)*m, m = (l < token_num[b]); x in/out [B,L,D]. */
