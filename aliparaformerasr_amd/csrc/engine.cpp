@@ -1223,17 +1223,14 @@ void Engine::encoder(const float* speech_dev, int B, int T, bool pre_encoded) {
   const Carve carve{off};
   const size_t o_x = carve(Mp * D * 4), o_xn = carve(Mp * std::max(k0, D) * 2), o_qkv = carve(Mp * 3 * D * 2);
   const size_t o_ctx = carve(Mp * D * 2), o_fsm = carve(Mp * D * 4), o_h = carve(Mp * std::max(F, 3 * D) * 2);
-  const size_t o_H32 = carve(Mp * D * 4), o_H16 = carve(Mp * D * 2), o_al = carve((size_t)B * (T + 1) * 4);
-  const size_t o_fc = carve((size_t)B * 4), o_tn = carve((size_t)B * 4), o_ff = carve((size_t)B * (T + 1) * 4);
-  const size_t o_wc = carve((size_t)B * (T + 1) * 4), o_wr = carve((size_t)B * (T + 1) * 4), o_mx = carve(256);
+  const size_t o_H32 = carve(Mp * D * 4), o_H16 = carve(Mp * D * 2);
+  const CifCarve o_cif(carve, B, T + 1);
   ensure(ws_enc_, off);
   char* base = (char*)ws_enc_.p;
   x_ = (float*)(base + o_x); xn16_ = (half_t*)(base + o_xn); qkv16_ = (half_t*)(base + o_qkv);
   ctx16_ = (half_t*)(base + o_ctx); fsm_ = (float*)(base + o_fsm); h16_ = (half_t*)(base + o_h);
-  H32_ = (float*)(base + o_H32); H16_ = (half_t*)(base + o_H16); alphas_ = (float*)(base + o_al);
-  plan_.fire_count = (int32_t*)(base + o_fc); plan_.token_num = (int32_t*)(base + o_tn);
-  plan_.fire_frame = (int32_t*)(base + o_ff); plan_.w_cur = (float*)(base + o_wc);
-  plan_.w_rem = (float*)(base + o_wr); plan_.max_count = (int32_t*)(base + o_mx);
+  H32_ = (float*)(base + o_H32); H16_ = (half_t*)(base + o_H16);
+  alphas_ = (float*)(base + o_cif.al); plan_ = o_cif.plan(base);
 
   // the LayerNorm that FOLLOWS layer i's FFN-down is the next layer's norm1, or after_norm behind the last one
   const bool has_tp = !tp_.empty();
@@ -1295,7 +1292,7 @@ DecBufs Engine::carve_dec16(Arena& a, int64_t rows, int F, bool with_h32) {
 
 // The decoder stack in its plain form, 9 launches a layer: norm1 | FFN-up (f16 hidden) | LayerNorm(F) in place | FFN-down | norm2 |
 // FSMN memory + residual | norm3 | q | cross attention | out-projection + residual; then the final block's FFN (-> t32).  The SeACo
-// bias decoder and the streaming seam run it; the ASR decoder's fused and short-input forms are predictor_and_decoder's own walk.
+// bias decoder and the streaming seam run it; the ASR decoder's fused and short-input forms are asr_decoder_f16's own walk.
 void Engine::decoder16(const DecStack& S, const DecRun& r) {
   const int D = mc_.d_model, R = r.B * r.L;
   const DecBufs& b = r.b;
@@ -1351,60 +1348,102 @@ void Engine::cif_alpha_stage(const half_t* H16, int B, int T, half_t* col16, flo
   prof_end("cif_misc");
 }
 
-void Engine::predictor_and_decoder(int B, int T, bool want_logits) {
-  const int D = mc_.d_model, F = mc_.ffn, V = mc_.vocab;
-  const int M = B * T, T1 = T + 1;
+// ---- the stages of forward_device behind the encoder
+// The predictor: alphas, the fire scan into plan_, the counts on their way to the host; then the timestamp head starts.  f16 and
+// int8 run the same stage (the Conv1d is a Conv node, which quantize_dynamic leaves alone, and so are the head's nodes: it is
+// run with op_types_to_quantize = ["MatMul"]) with the head beside the decoder; the fp32 graph runs its own forms in line.
+void Engine::predictor(int B, int T) {
+  if (fp32_mode_) {
+    cif_alpha_stage32(H32_, B, T, col32_, fsm_, alphas_);
+    if (mc_.cif_cumsum) launch_cif_scan_cumsum(stream_, alphas_, B, T + 1, plan_);
+    else launch_cif_scan(stream_, alphas_, B, T + 1, mc_.cif_threshold, plan_);
+    export_plan(B);
+    if (mc_.timestamp_head) timestamp_head_fp32(B, T);
+    return;
+  }
   if (ev_enc_) PF_HIP(hipEventRecord(ev_enc_, stream_));     // the encoder output exists: all the timestamp head's GEMMs and its recurrence need
   // reuse the FFN hidden buffer for the [M, 3D] operand and the FSMN buffer for the fp32 conv output
   cif_alpha_stage(H16_, B, T, h16_, fsm_, alphas_, &plan_);
   export_plan(B);
-  last_.peak_len = 0;
-  last_.cif_peak.clear();
   if (mc_.timestamp_head) start_timestamp_head(B, T);
-  // The cross-attention K/V projections of all decoder layers depend on the encoder output only, not on the decoder
-  // length: they go out BEFORE the length is read back and keep the device busy during the host round trip (and,
-  // in a multi-device group, during the rendez-vous that agrees on the batch-wide length).
-  const int nd = (int)dec_.layers.size();
+}
+
+// The cross-attention K/V projections of all decoder layers depend on the encoder output only, not on the decoder
+// length: they go out BEFORE the length is read back and keep the device busy during the host round trip (and,
+// in a multi-device group, during the rendez-vous that agrees on the batch-wide length).
+void Engine::dec_kv_ahead(int B, int T) {
+  const int D = mc_.d_model, M = B * T, nd = (int)dec_.layers.size();
   const int64_t Mp = round_up(M, 128) + 128;
   const int ldkv = std::max(nd, 1) * 2 * D;
   ensure(ws_kv_, (size_t)Mp * ldkv * 2);
-  half_t* kv16 = (half_t*)ws_kv_.p;
   if (nd > 0)
-    gemm("gemm_dec_kv", dec_.kv_all, H16_, D, M, nullptr, 0, kv16, ldkv, nullptr, 0, nullptr, 0, false, 0, 1.f);
-  // the path's only host sync: the decoder length L is data dependent.  The read-back rides a side stream that waits
-  // for the CIF scan alone.
-  int32_t L = read_back_plan(B);       // (the K / V GEMM above is queued BEHIND the event this waits for: nothing waits for the GEMM)
+    gemm("gemm_dec_kv", dec_.kv_all, H16_, D, M, nullptr, 0, (half_t*)ws_kv_.p, ldkv, nullptr, 0, nullptr, 0, false, 0, 1.f);
+}
+
+// The path's only host sync: the decoder length L is data dependent.  The read-back waits for the CIF scan alone (whatever
+// was queued behind export_plan's event, nothing waits for).
+int Engine::decoder_length(int B, int T) {
+  int32_t L = read_back_plan(B);
+  if (fp32_mode_ && mc_.timestamp_head) PF_HIP(hipStreamSynchronize(stream_));   // (the in-line head's results are read by the caller as before)
   if (l_hook_) L = l_hook_(L);                       // shard of a multi-device batch: the batch-wide maximum
-  last_.B = B; last_.L = L; last_.V = V; last_.T = T;
+  last_.B = B; last_.L = L; last_.V = mc_.vocab; last_.T = T;
   last_.ids.assign((size_t)B * L, 0);
-  if (L == 0) { join_ts(); return; }
+  return L;
+}
 
-  const int Md = B * L;
-  const int64_t Mdp = round_up(Md, 128) + 128;
-  float* xd_alt = nullptr;                             // the residual stream ping-pongs when the out-projection rides in front of the next FFN launch
-  const DecBufs w = carve_into(ws_dec_, kAlign, [&](Arena& a) {
-    const DecBufs d = carve_dec16(a, Mdp, F, false);
-    logits_ = a.take<float>((size_t)Mdp * round_up(V, 4) * 4); ids_dev_ = a.take<int64_t>((size_t)Md * 8);
-    xd_alt = a.take<float>(Mdp * D * 4);
-    return d;
-  });
-  float* xd = w.x; half_t* xdn16 = w.xn16; half_t* hd16 = w.h16; float* t32 = w.t32; float* tn32 = w.tn32;
-  half_t* qd16 = w.q16; half_t* ctxd16 = w.ctx16;
-  const float qscale = 1.0f / std::sqrt((float)(D / mc_.heads));
+// The CIF embeds [B * L, D] into the walk's residual stream; with hot words the SeACo bias decoder starts from them too and
+// they are set aside, with room for the ASR decoder's after_norm hidden behind them.
+void Engine::cif_embeds(DecStage& d, int B, int T, int L, const char* cls) {
+  const int D = mc_.d_model;
+  if (cls) prof_begin(cls, 0);
+  if (mc_.cif_cumsum) launch_cif_gather_cumsum(stream_, H32_, alphas_, B, T, D, T + 1, plan_, L, d.b.x);
+  else launch_cif_gather(stream_, H32_, B, T, D, T + 1, plan_, L, d.b.x);
+  if (cls) prof_end(cls);
+  if (!(mc_.seaco && n_hotwords_ > 0)) return;
+  ensure(ws_seaco_in_, (size_t)2 * d.rows * D * 4);
+  d.e0 = (float*)ws_seaco_in_.p;
+  d.hid = d.e0 + (size_t)d.rows * D;
+  PF_HIP(hipMemcpyAsync(d.e0, d.b.x, (size_t)B * L * D * 4, hipMemcpyDeviceToDevice, stream_));
+}
 
-  prof_begin("cif_misc", 0);
-  if (mc_.cif_cumsum) launch_cif_gather_cumsum(stream_, H32_, alphas_, B, T, D, T1, plan_, L, xd);
-  else launch_cif_gather(stream_, H32_, B, T, D, T1, plan_, L, xd);
-  prof_end("cif_misc");
-  const bool bias_branch = mc_.seaco && n_hotwords_ > 0;
-  float* e0 = nullptr;                                 // SeACo: the bias decoder also starts from the CIF embeds
-  float* hid32 = nullptr;
-  if (bias_branch) {
-    ensure(ws_seaco_in_, (size_t)2 * Mdp * D * 4);
-    e0 = (float*)ws_seaco_in_.p;
-    hid32 = e0 + (size_t)Mdp * D;
-    PF_HIP(hipMemcpyAsync(e0, xd, (size_t)Md * D * 4, hipMemcpyDeviceToDevice, stream_));
+void Engine::finish(int B, int L, bool want_logits, const DecStage* d, const char* cls) {
+  const int64_t rows = (int64_t)B * L;
+  if (cls) prof_begin(cls, 0);
+  launch_argmax(stream_, logits_, rows, mc_.vocab, logits_ld_, argmax_mode(want_logits), ids_dev_, score_buf(rows));
+  if (cls) prof_end(cls);
+  if (d && d->e0) {
+    if (fp32_mode_) seaco_head_fp32(B, L, d->e0, d->hid, want_logits);
+    else seaco_head(B, L, d->e0, d->hid, want_logits);
   }
+  join_ts();
+  PF_HIP(hipMemcpyAsync(last_.ids.data(), ids_dev_, (size_t)rows * 8, hipMemcpyDeviceToHost, stream_));
+  queue_decode_results(B, L);
+}
+
+DecStage Engine::dec_arena_f16(int B, int T, int L) {
+  const int D = mc_.d_model, Md = B * L;
+  DecStage d;
+  d.rows = round_up(Md, 128) + 128;
+  d.kv = ws_kv_.p;
+  d.b = carve_into(ws_dec_, kAlign, [&](Arena& a) {
+    const DecBufs b = carve_dec16(a, d.rows, mc_.ffn, false);
+    logits_ = a.take<float>((size_t)d.rows * round_up(mc_.vocab, 4) * 4); ids_dev_ = a.take<int64_t>((size_t)Md * 8);
+    d.x_alt = a.take<float>(d.rows * D * 4);
+    return b;
+  });
+  return d;
+}
+
+// The f16 ASR decoder in its fused and short-input forms, then the vocabulary product.
+void Engine::asr_decoder_f16(DecStage& d, int B, int T, int L) {
+  const int D = mc_.d_model, F = mc_.ffn, V = mc_.vocab, Md = B * L, nd = (int)dec_.layers.size();
+  const int ldkv = std::max(nd, 1) * 2 * D;
+  const half_t* kv16 = (const half_t*)d.kv;
+  const DecBufs& w = d.b;
+  float* xd = w.x; float* xd_alt = d.x_alt;          // the residual stream ping-pongs when the out-projection rides in front of the next FFN launch
+  half_t* xdn16 = w.xn16; half_t* hd16 = w.h16; float* t32 = w.t32; float* tn32 = w.tn32;
+  half_t* qd16 = w.q16; half_t* ctxd16 = w.ctx16; float* hid32 = d.hid;
+  const float qscale = 1.0f / std::sqrt((float)(D / mc_.heads));
 
   // Generic decoder layer = 9 launches: norm1 | FFN-up (f16 hidden) | LayerNorm(2048) in place | FFN-down | norm2 | FSMN
   // memory + norm3 (one kernel) | q | cross attention | out-projection + residual.
@@ -1519,13 +1558,6 @@ void Engine::predictor_and_decoder(int B, int T, bool want_logits) {
   ffn_dec(dec_.final_norm1, dec_.final_w1, dec_.final_ffn_norm, dec_.final_w2, dec_.final_img, dec_.after, hid32, xdn16);
   logits_ld_ = (int)round_up(V, 4);                 // fp32 rows stay 16-byte aligned for any vocabulary size
   gemm("gemm_vocab", dec_.out, xdn16, D, Md, logits_, logits_ld_, nullptr, 0, nullptr, 0, nullptr, 0, false, 0, 1.f);
-  prof_begin("argmax", 0);
-  launch_argmax(stream_, logits_, Md, V, logits_ld_, argmax_mode(want_logits), ids_dev_, score_buf(Md));
-  prof_end("argmax");
-  if (bias_branch) seaco_head(B, L, e0, hid32, want_logits);
-  join_ts();
-  PF_HIP(hipMemcpyAsync(last_.ids.data(), ids_dev_, (size_t)Md * 8, hipMemcpyDeviceToHost, stream_));
-  queue_decode_results(B, L);
 }
 
 // Starts the BiCIF timestamp head of the current forward: beside the decoder on its own stream (default), or in line.
@@ -1816,26 +1848,19 @@ void Engine::timestamp_head(int B, int T) {
 }
 
 void Engine::sensevoice_head(int B, int T, bool want_logits) {
-  const int D = mc_.d_model, V = mc_.vocab;
-  const int M = B * T;
+  const int D = mc_.d_model, V = mc_.vocab, M = B * T;
   const int64_t Mp = round_up(M, 128) + 128;
-  size_t off = 0;
-  const Carve carve{off};
-  const size_t o_lg = carve((size_t)Mp * round_up(V, 4) * 4), o_ids = carve((size_t)M * 8);
-  ensure(ws_dec_, off);
-  logits_ = (float*)((char*)ws_dec_.p + o_lg);
-  ids_dev_ = (int64_t*)((char*)ws_dec_.p + o_ids);
   logits_ld_ = (int)round_up(V, 4);
-  gemm("gemm_vocab", ctc_, H16_, D, M, logits_, logits_ld_, nullptr, 0, nullptr, 0, nullptr, 0, false, 0, 1.f);
-  prof_begin("argmax", 0);
-  launch_argmax(stream_, logits_, M, V, logits_ld_, argmax_mode(want_logits), ids_dev_, score_buf(M));
-  prof_end("argmax");
+  carve_into(ws_dec_, kAlign, [&](Arena& a) { logits_ = a.take<float>((size_t)Mp * logits_ld_ * 4); ids_dev_ = a.take<int64_t>((size_t)M * 8); });
+  // the vocabulary product is the arithmetic's own (fp32: in the class the encoder left, "gemm32_misc")
+  if (fp32_mode_) gemm32(H32_, D, ctc_.w32, D, ctc_.bias, M, V, D, logits_, logits_ld_, nullptr, 0, false, 0, 1.f);
+  else if (int8_mode_) qgemm("gemm_vocab", ctc_, true, H32_, nullptr, D, M, logits_, logits_ld_, nullptr, 0, nullptr, 0, nullptr, 0, false, 0, 1.f);
+  else gemm("gemm_vocab", ctc_, H16_, D, M, logits_, logits_ld_, nullptr, 0, nullptr, 0, nullptr, 0, false, 0, 1.f);
   last_.B = B; last_.L = T; last_.V = V; last_.T = T;
   last_.ids.assign((size_t)M, 0);
   last_.token_num.assign(B, T);
   last_.fire_count.assign(B, T);
-  PF_HIP(hipMemcpyAsync(last_.ids.data(), ids_dev_, (size_t)M * 8, hipMemcpyDeviceToHost, stream_));
-  queue_decode_results(B, T);
+  finish(B, T, want_logits, nullptr, fp32_mode_ ? nullptr : "argmax");
 }
 
 // ------------------------------------------------------------------ decoding extras ---------
@@ -2159,11 +2184,35 @@ void Engine::forward_device(const float* speech_dev, int B, int T, bool want_log
     align_B_ = 0; align_tgt_.clear(); align_len_.clear();
     PF_CHECK(false, PF_ERR_INVALID_ARG, "forward: align targets were set for a batch of " + std::to_string(want) + ", not " + std::to_string(B));
   }
-  if (fp32_mode_) { forward_fp32(speech_dev, B, T, want_logits); return; }
-  if (int8_mode_) { forward_int8(speech_dev, B, T, want_logits); return; }
-  encoder(speech_dev, B, T);
-  if (mc_.kind == "sensevoicesmall") sensevoice_head(B, T, want_logits);
-  else predictor_and_decoder(B, T, want_logits);
+  last_.peak_len = 0;
+  last_.cif_peak.clear();
+  last_flops_ = 0;
+  // ---- the pipeline.  Of its own an arithmetic has the encoder, the decoder arena, and the walk with its vocabulary product.
+  PF_CHECK((int64_t)B * T < (1ll << 31) / (3 * mc_.d_model), PF_ERR_INVALID_ARG, "batch too large for 32-bit row indexing");
+  build_pe(T);
+  const bool f16 = !fp32_mode_ && !int8_mode_;
+  if (fp32_mode_) encoder_fp32(speech_dev, B, T);
+  else if (int8_mode_) encoder_int8(speech_dev, B, T);
+  else encoder(speech_dev, B, T);                    // (repeats the two lines above for its stand-alone callers)
+  if (mc_.kind == "sensevoicesmall") {
+    sensevoice_head(B, T, want_logits);
+  } else {
+    const char* cif_cls = fp32_mode_ ? nullptr : "cif_misc";   // the fp32 graph brackets its products only
+    predictor(B, T);
+    if (f16) dec_kv_ahead(B, T);
+    const int L = decoder_length(B, T);
+    if (L == 0) {
+      join_ts();
+    } else {
+      DecStage d = fp32_mode_ ? dec_arena_fp32(B, T, L) : int8_mode_ ? dec_arena_int8(B, T, L) : dec_arena_f16(B, T, L);
+      cif_embeds(d, B, T, L, cif_cls);
+      if (fp32_mode_) asr_decoder_fp32(d, B, T, L);
+      else if (int8_mode_) asr_decoder_int8(d, B, T, L);
+      else asr_decoder_f16(d, B, T, L);
+      finish(B, L, want_logits, &d, fp32_mode_ ? nullptr : "argmax");
+    }
+  }
+  if (!f16) return;
   // algorithmic FLOPs
   const double D = mc_.d_model, F = mc_.ffn, Td = T, Ld = last_.L, K = mc_.kernel, V = mc_.vocab;
   double enc = 2 * Td * mc_.feat_dim * 3 * D + (mc_.enc_layers - 1 + mc_.tp_layers) * 2 * Td * D * 3 * D +

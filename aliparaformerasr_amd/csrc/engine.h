@@ -114,6 +114,26 @@ struct Carve {
   size_t& off; size_t align = kAlign;
   size_t operator()(size_t bytes) const { const size_t o = off; off += (bytes + align - 1) / align * align; return o; }
 };
+// the CIF stage's arrays for (B, T1 = T + 1) in the order every arena keeps them: the alphas, then the plan's six
+struct CifCarve {
+  size_t al, fc, tn, ff, wc, wr, mx;
+  CifCarve(const Carve& c, int B, int T1)
+      : al(c((size_t)B * T1 * 4)), fc(c((size_t)B * 4)), tn(c((size_t)B * 4)), ff(c((size_t)B * T1 * 4)), wc(c((size_t)B * T1 * 4)),
+        wr(c((size_t)B * T1 * 4)), mx(c(256)) {}
+  CifPlan plan(char* base) const {
+    return CifPlan{(int32_t*)(base + fc), (int32_t*)(base + tn), (int32_t*)(base + ff), (float*)(base + wc), (float*)(base + wr),
+                   (int32_t*)(base + mx)};
+  }
+};
+// the decoder stage of one forward (Engine::forward_device): the walk's arena, whose x receives the CIF embeds, and what the
+// arithmetic keeps beside it
+struct DecStage {
+  DecBufs b; int64_t rows = 0;                 // rows: the arena's row count (f16 / int8: padded)
+  void* kv = nullptr;                          // f16: every layer's K | V, projected ahead of the length; int8 / fp32: one layer's
+  QAct qH;                                     // int8: the quantised encoder memory
+  float* x_alt = nullptr;                      // f16: the residual stream's second buffer (out-projection chain)
+  float* e0 = nullptr; float* hid = nullptr;   // SeACo with hot words: the CIF embeds set aside, the ASR decoder's after_norm hidden
+};
 
 struct DevBuf {       // grow-only device allocation
   void* p = nullptr;
@@ -383,11 +403,24 @@ class Engine {
   // im2col -> conv GEMM with ReLU -> launch_cif_alpha (scan: then the fire scan into *scan, as the offline pipeline has it)
   void cif_alpha_stage(const half_t* H16, int B, int T, half_t* col16, float* conv32, float* alphas, const CifPlan* scan);
   void cif_alpha_stage32(const float* H32, int B, int T, float* col32, float* conv32, float* alphas);
-  void predictor_and_decoder(int B, int T, bool want_logits);
+  // ---- the stages of forward_device, each written once.  An arithmetic (f16; int8 = math_mode 2, engine_int8.cpp: every Linear as
+  // DynamicQuantizeLinear + MatMulInteger on v_mfma_i32_32x32x32_i8; fp32 = math_mode 1 / 3, engine_fp32.cpp) has of its own:
+  // its encoder (leaves H32_, H16_ except fp32, alphas_ and plan_ bound), its decoder arena, and its walk + vocabulary product
+  void encoder_int8(const float* speech_dev, int B, int T);
+  void encoder_fp32(const float* speech_dev, int B, int T);
   void sensevoice_head(int B, int T, bool want_logits);
-  void forward_fp32(const float* speech_dev, int B, int T, bool want_logits);   // math_mode 1 (k_fp32.hip)
-  // math_mode 2 (engine_int8.cpp): every Linear as DynamicQuantizeLinear + MatMulInteger on v_mfma_i32_32x32x32_i8
-  void forward_int8(const float* speech_dev, int B, int T, bool want_logits);
+  void predictor(int B, int T);                      // alphas, fire scan, plan export; starts the timestamp head
+  void dec_kv_ahead(int B, int T);                   // f16: all layers' K | V projections of the encoder memory -> ws_kv_
+  int decoder_length(int B, int T);                  // the forward's one host round trip: L, and last_'s shape
+  DecStage dec_arena_f16(int B, int T, int L);
+  DecStage dec_arena_int8(int B, int T, int L);
+  DecStage dec_arena_fp32(int B, int T, int L);
+  void cif_embeds(DecStage& d, int B, int T, int L, const char* cls);   // cls: the launches' profile class, or null for no bracket
+  void asr_decoder_f16(DecStage& d, int B, int T, int L);              // the walk, then logits_ = the vocabulary product
+  void asr_decoder_int8(DecStage& d, int B, int T, int L);
+  void asr_decoder_fp32(DecStage& d, int B, int T, int L);
+  // arg-max | SeACo head (d with hot-word inputs) | timestamp join | ids copy | decoding extras, over B * L rows of logits_
+  void finish(int B, int L, bool want_logits, const DecStage* d, const char* cls);
   const QLin& qlin(const Lin& l, bool bias = true);
   const QLin& qlin_raw(const float* w32, const float* bias, int N, int K);
   // y = dequant(quant(x) w_q^T) + bias [* scale on the first scale_cols columns] [+ add2] [+ resid] [ReLU]; x fp32 [M, ldx] or f16
@@ -551,10 +584,11 @@ class Engine {
   DevBuf ws_audio_, ws_meta_, ws_fbank_, ws_speech_, ws_enc_, ws_dec_, ws_decffn_, ws_kv_, ws_pe_, ws_tmp_, ws_ts_, ws_seaco_, ws_seaco_in_, ws_seaco_hw_;
   bool seaco_hw_valid_ = false;     // ws_seaco_hw_ holds the embedder output / K,V rows of the CURRENT hot-word list (f16 path)
   int pe_T_ = 0;
-  // encoder views (valid after encoder())
+  // encoder views (valid after the arithmetic's encoder)
   float* x_ = nullptr; half_t* xn16_ = nullptr; half_t* qkv16_ = nullptr; half_t* ctx16_ = nullptr;
   float* fsm_ = nullptr; half_t* h16_ = nullptr; float* H32_ = nullptr; half_t* H16_ = nullptr;
   float* alphas_ = nullptr; CifPlan plan_{};
+  float* col32_ = nullptr;          // fp32: the predictor's im2col operand (fsm_ takes its conv result)
   float* us_peak_ = nullptr;
   struct { const float* xg = nullptr; int B = 0, T3 = 0; const void* rest[4] = {nullptr, nullptr, nullptr, nullptr}; int ndir = 0; } lstm_graph_key_;
   hipGraphExec_t lstm_graph_exec_ = nullptr;

@@ -254,7 +254,7 @@ void Engine::decoder32(const DecStack& S, const DecRun& r) {
   ffn_dec(S.final_norm1, S.final_w1, S.final_ffn_norm, S.final_w2);
 }
 
-// The predictor's alpha stage of the fp32 graph, one body for forward_fp32 and pf_op_cif_alphas: fp32 im2col, the conv as a
+// The predictor's alpha stage of the fp32 graph, one body for the pipeline (Engine::predictor) and pf_op_cif_alphas: fp32 im2col, the conv as a
 // gemm32 with ReLU, then launch_cif_alpha.  H32 [B*T, D], col32 [B*T, taps*D], conv32 [B*T, D].
 void Engine::cif_alpha_stage32(const float* H32, int B, int T, float* col32, float* conv32, float* alphas) {
   const int D = mc_.d_model, M = B * T, taps = mc_.cif_l_order + mc_.cif_r_order + 1;
@@ -264,10 +264,9 @@ void Engine::cif_alpha_stage32(const float* H32, int B, int T, float* col32, flo
   launch_cif_alpha(stream_, conv32, B, T, D, cif_out_w_, cif_out_b_, mc_.cif_smooth, mc_.cif_noise, mc_.cif_tail, alphas);
 }
 
-void Engine::forward_fp32(const float* speech_dev, int B, int T, bool want_logits) {
-  const int D = mc_.d_model, F = mc_.ffn, V = mc_.vocab, Fd = mc_.feat_dim, M = B * T, T1 = T + 1;
+void Engine::encoder_fp32(const float* speech_dev, int B, int T) {
+  const int D = mc_.d_model, F = mc_.ffn, Fd = mc_.feat_dim, M = B * T;
   const int taps = mc_.cif_l_order + mc_.cif_r_order + 1;
-  build_pe(T);
   size_t off = 0;
   const Carve carve{off};
   const size_t W = (size_t)std::max(std::max(Fd, D), taps * D);
@@ -275,16 +274,15 @@ void Engine::forward_fp32(const float* speech_dev, int B, int T, bool want_logit
   o_f[F_X] = carve((size_t)M * D * 4); o_f[F_XN] = carve((size_t)M * W * 4); o_f[F_Q] = carve((size_t)M * D * 4);
   o_f[F_K] = carve((size_t)M * D * 4); o_f[F_V] = carve((size_t)M * D * 4); o_f[F_CTX] = carve((size_t)M * D * 4);
   o_f[F_FS] = carve((size_t)M * D * 4); o_f[F_H] = carve((size_t)M * F * 4); o_f[F_T] = carve((size_t)M * W * 4);
-  const size_t o_H = carve((size_t)M * D * 4), o_al = carve((size_t)B * T1 * 4), o_fc = carve((size_t)B * 4), o_tn = carve((size_t)B * 4);
-  const size_t o_ff = carve((size_t)B * T1 * 4), o_wc = carve((size_t)B * T1 * 4), o_wr = carve((size_t)B * T1 * 4), o_mx = carve(256);
+  const size_t o_H = carve((size_t)M * D * 4);
+  const CifCarve o_cif(carve, B, T + 1);
   ensure(ws_f32_, off);
   char* base = (char*)ws_f32_.p;
   float* f[F_COUNT];
   for (int i = 0; i < F_COUNT; ++i) f[i] = (float*)(base + o_f[i]);
-  H32_ = (float*)(base + o_H); alphas_ = (float*)(base + o_al);
-  plan_.fire_count = (int32_t*)(base + o_fc); plan_.token_num = (int32_t*)(base + o_tn);
-  plan_.fire_frame = (int32_t*)(base + o_ff); plan_.w_cur = (float*)(base + o_wc);
-  plan_.w_rem = (float*)(base + o_wr); plan_.max_count = (int32_t*)(base + o_mx);
+  H32_ = (float*)(base + o_H);
+  alphas_ = (float*)(base + o_cif.al); plan_ = o_cif.plan(base);
+  col32_ = f[F_T]; fsm_ = f[F_FS];                                        // the predictor's im2col operand and conv result
 
   x3_pair_live_ = false; x3a_src_ = nullptr; x3a_pair_only_ = false;      // (a forward that threw may have left an operand pair announced)
   for (size_t i = 0; i < enc_.size(); ++i) enc_layer_fp32(enc_[i], i == 0, speech_dev, B, T, f);
@@ -295,60 +293,28 @@ void Engine::forward_fp32(const float* speech_dev, int B, int T, bool want_logit
     for (size_t i = 0; i < tp_.size(); ++i) enc_layer_fp32(tp_[i], false, nullptr, B, T, f);
     launch_layernorm(stream_, f[F_X], M, D, tp_norm_.g, tp_norm_.b, nullptr, 0, H32_, D);
   }
-  const int ldV = (int)round_up(V, 4);
-  last_.peak_len = 0;
-  last_.cif_peak.clear();
-  if (mc_.kind == "sensevoicesmall") {
-    size_t o2 = 0;
-    const Carve c2{o2};
-    const size_t o_lg = c2((size_t)M * ldV * 4), o_ids = c2((size_t)M * 8);
-    ensure(ws_dec_, o2);
-    logits_ = (float*)((char*)ws_dec_.p + o_lg); ids_dev_ = (int64_t*)((char*)ws_dec_.p + o_ids); logits_ld_ = ldV;
-    gemm32(H32_, D, ctc_.w32, D, ctc_.bias, M, V, D, logits_, ldV, nullptr, 0, false, 0, 1.f);
-    launch_argmax(stream_, logits_, M, V, ldV, argmax_mode(want_logits), ids_dev_, score_buf(M));
-    last_.B = B; last_.L = T; last_.V = V; last_.T = T;
-    last_.ids.assign((size_t)M, 0);
-    last_.token_num.assign(B, T);
-    last_.fire_count.assign(B, T);
-    PF_HIP(hipMemcpyAsync(last_.ids.data(), ids_dev_, (size_t)M * 8, hipMemcpyDeviceToHost, stream_));
-    queue_decode_results(B, T);
-    last_flops_ = 0;
-    return;
-  }
-  // ---- CIF predictor
-  cif_alpha_stage32(H32_, B, T, f[F_T], f[F_FS], alphas_);
-  if (mc_.cif_cumsum) launch_cif_scan_cumsum(stream_, alphas_, B, T1, plan_);
-  else launch_cif_scan(stream_, alphas_, B, T1, mc_.cif_threshold, plan_);
-  export_plan(B);
-  if (mc_.timestamp_head) timestamp_head_fp32(B, T);
-  int32_t L = read_back_plan(B);
-  if (mc_.timestamp_head) PF_HIP(hipStreamSynchronize(stream_));       // (the in-line head's results are read below as before)
-  if (l_hook_) L = l_hook_(L);
-  last_.B = B; last_.L = L; last_.V = V; last_.T = T;
-  last_.ids.assign((size_t)B * L, 0);
-  last_flops_ = 0;
-  if (L == 0) return;
-  // ---- decoder
-  const int Md = B * L;
-  float* kv = nullptr;
-  DecRun r;
-  r.b = carve_into(ws_dec_, kAlign, [&](Arena& a) {
-    const DecBufs d = carve_dec32(a, Md, F);
-    kv = a.take<float>((size_t)M * 2 * D * 4); logits_ = a.take<float>((size_t)Md * ldV * 4); ids_dev_ = a.take<int64_t>((size_t)Md * 8);
-    return d;
+}
+
+DecStage Engine::dec_arena_fp32(int B, int T, int L) {
+  const int D = mc_.d_model, M = B * T, Md = B * L;
+  DecStage d;
+  d.rows = Md;
+  d.b = carve_into(ws_dec_, kAlign, [&](Arena& a) {
+    const DecBufs b = carve_dec32(a, Md, mc_.ffn);
+    d.kv = a.take<float>((size_t)M * 2 * D * 4); logits_ = a.take<float>((size_t)Md * round_up(mc_.vocab, 4) * 4);
+    ids_dev_ = a.take<int64_t>((size_t)Md * 8);
+    return b;
   });
-  float* xd = r.b.x; float* xn = r.b.xn32; float* t32 = r.b.t32;
-  logits_ld_ = ldV;
-  if (mc_.cif_cumsum) launch_cif_gather_cumsum(stream_, H32_, alphas_, B, T, D, T1, plan_, L, xd);
-  else launch_cif_gather(stream_, H32_, B, T, D, T1, plan_, L, xd);
-  const bool bias_branch = mc_.seaco && n_hotwords_ > 0;
-  float* e0 = nullptr;                                 // SeACo: the bias decoder also starts from the CIF embeds
-  if (bias_branch) {
-    ensure(ws_seaco_in_, (size_t)Md * D * 4);
-    e0 = (float*)ws_seaco_in_.p;
-    PF_HIP(hipMemcpyAsync(e0, xd, (size_t)Md * D * 4, hipMemcpyDeviceToDevice, stream_));
-  }
+  return d;
+}
+
+void Engine::asr_decoder_fp32(DecStage& d, int B, int T, int L) {
+  const int D = mc_.d_model, V = mc_.vocab, M = B * T, Md = B * L;
+  float* kv = (float*)d.kv;
+  logits_ld_ = (int)round_up(V, 4);
   cls32_ = "gemm32_dec";
+  DecRun r;
+  r.b = d.b;
   r.B = B; r.L = L; r.token_num = plan_.token_num;
   r.kv_rs = 2 * D; r.kv_bs = (int64_t)T * 2 * D; r.Lk = T;
   r.kv_layer = [&](int i) -> const void* {                 // layer i's K | V of the encoder memory
@@ -358,14 +324,11 @@ void Engine::forward_fp32(const float* speech_dev, int B, int T, bool want_logit
   };
   r.operand_only = true;
   decoder32(dec_, r);
-  launch_layernorm(stream_, t32, Md, D, dec_.after.g, dec_.after.b, nullptr, 0, xn, D);
+  launch_layernorm(stream_, d.b.t32, Md, D, dec_.after.g, dec_.after.b, nullptr, 0, d.b.xn32, D);
+  if (d.e0) d.hid = d.b.xn32;                              // the bias decoder's second input: the after_norm hidden, where it is
   cls32_ = "gemm32_vocab";
-  gemm32(xn, D, dec_.out.w32, D, dec_.out.bias, Md, V, D, logits_, ldV, nullptr, 0, false, 0, 1.f);
-  launch_argmax(stream_, logits_, Md, V, ldV, argmax_mode(want_logits), ids_dev_, score_buf(Md));
+  gemm32(d.b.xn32, D, dec_.out.w32, D, dec_.out.bias, Md, V, D, logits_, logits_ld_, nullptr, 0, false, 0, 1.f);
   cls32_ = "gemm32_misc";
-  if (bias_branch) seaco_head_fp32(B, L, e0, xn, want_logits);      // xn = the ASR decoder's after_norm hidden
-  PF_HIP(hipMemcpyAsync(last_.ids.data(), ids_dev_, (size_t)Md * 8, hipMemcpyDeviceToHost, stream_));
-  queue_decode_results(B, L);
 }
 
 // ---- fp32 forms of the two heads (math_mode 1): the same graphs as timestamp_head / seaco_head with fp32 weights and

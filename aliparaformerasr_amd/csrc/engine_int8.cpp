@@ -174,28 +174,24 @@ void Engine::qgemm(const char* cls, const Lin& lw, bool use_bias, const float* x
   prof_end(cls);
 }
 
-void Engine::forward_int8(const float* speech_dev, int B, int T, bool want_logits) {
-  const int D = mc_.d_model, F = mc_.ffn, V = mc_.vocab, Fd = mc_.feat_dim, T1 = T + 1;
+void Engine::encoder_int8(const float* speech_dev, int B, int T) {
+  const int D = mc_.d_model, F = mc_.ffn, Fd = mc_.feat_dim;
   const int64_t M = (int64_t)B * T, Mp = round_up(M, 128) + 128;
   const int taps = mc_.cif_l_order + mc_.cif_r_order + 1;
   const float qscale = 1.0f / std::sqrt((float)(D / mc_.heads));
-  build_pe(T);
   size_t off = 0;
   const Carve carve{off, kAlignQ};
   const size_t o_x = carve(Mp * D * 4), o_t = carve(Mp * std::max(Fd, D) * 4);
   const size_t o_qkv = carve(Mp * 3 * D * 2), o_ctx = carve(Mp * D * 2), o_fsm = carve(Mp * D * 4);
   const size_t o_h = carve(Mp * std::max(F, taps * D) * 2), o_H32 = carve(Mp * D * 4), o_H16 = carve(Mp * D * 2);
-  const size_t o_al = carve((size_t)B * T1 * 4), o_fc = carve((size_t)B * 4), o_tn = carve((size_t)B * 4);
-  const size_t o_ff = carve((size_t)B * T1 * 4), o_wc = carve((size_t)B * T1 * 4), o_wr = carve((size_t)B * T1 * 4), o_mx = carve(256);
+  const CifCarve o_cif(carve, B, T + 1);
   ensure(ws_enc_, off);
   char* base = (char*)ws_enc_.p;
   x_ = (float*)(base + o_x);
   float* t32e = (float*)(base + o_t);
   qkv16_ = (half_t*)(base + o_qkv); ctx16_ = (half_t*)(base + o_ctx); fsm_ = (float*)(base + o_fsm); h16_ = (half_t*)(base + o_h);
-  H32_ = (float*)(base + o_H32); H16_ = (half_t*)(base + o_H16); alphas_ = (float*)(base + o_al);
-  plan_.fire_count = (int32_t*)(base + o_fc); plan_.token_num = (int32_t*)(base + o_tn);
-  plan_.fire_frame = (int32_t*)(base + o_ff); plan_.w_cur = (float*)(base + o_wc);
-  plan_.w_rem = (float*)(base + o_wr); plan_.max_count = (int32_t*)(base + o_mx);
+  H32_ = (float*)(base + o_H32); H16_ = (half_t*)(base + o_H16);
+  alphas_ = (float*)(base + o_cif.al); plan_ = o_cif.plan(base);
 
   // ---- encoder: LayerNorm (fp32) -> quantise -> QKV (f16 out, q scaled) -> attention (f16) | FSMN(V) -> quantise(ctx) ->
   //      out-projection (+ FSMN memory + residual, fp32) -> LayerNorm -> quantise -> FFN-up + ReLU (f16) -> quantise -> FFN-down + residual
@@ -238,107 +234,53 @@ void Engine::forward_int8(const float* speech_dev, int B, int T, bool want_logit
     launch_layernorm(stream_, x_, M, D, tp_norm_.g, tp_norm_.b, H16_, D, H32_, D);
     prof_end("layernorm");
   }
-  const int ldV = (int)round_up(V, 4);
-  last_flops_ = 0;
-  if (mc_.kind == "sensevoicesmall") {
-    size_t o2 = 0;
-    const Carve c2{o2, kAlignQ};
-    const size_t o_lg = c2((size_t)Mp * ldV * 4), o_ids = c2((size_t)M * 8);
-    ensure(ws_dec_, o2);
-    logits_ = (float*)((char*)ws_dec_.p + o_lg); ids_dev_ = (int64_t*)((char*)ws_dec_.p + o_ids); logits_ld_ = ldV;
-    qgemm("gemm_vocab", ctc_, true, H32_, nullptr, D, (int)M, logits_, ldV, nullptr, 0, nullptr, 0, nullptr, 0, false, 0, 1.f);
-    prof_begin("argmax", 0);
-    launch_argmax(stream_, logits_, M, V, ldV, argmax_mode(want_logits), ids_dev_, score_buf(M));
-    prof_end("argmax");
-    last_.B = B; last_.L = T; last_.V = V; last_.T = T;
-    last_.ids.assign((size_t)M, 0);
-    last_.token_num.assign(B, T);
-    last_.fire_count.assign(B, T);
-    PF_HIP(hipMemcpyAsync(last_.ids.data(), ids_dev_, (size_t)M * 8, hipMemcpyDeviceToHost, stream_));
-    queue_decode_results(B, T);
-    return;
-  }
-  // ---- CIF predictor: the Conv1d is a Conv node (not quantised by quantize_dynamic): the f16 path's im2col GEMM
-  if (ev_enc_) PF_HIP(hipEventRecord(ev_enc_, stream_));
-  last_.peak_len = 0;
-  last_.cif_peak.clear();
-  {
-    half_t* col16 = h16_;
-    float* conv32 = fsm_;
-    prof_begin("cif_misc", 0);
-    launch_cif_im2col(stream_, H16_, B, T, D, mc_.cif_l_order, mc_.cif_r_order, col16);
-    prof_end("cif_misc");
-    gemm("gemm_cif", cif_conv_, col16, taps * D, (int)M, conv32, D, nullptr, 0, nullptr, 0, nullptr, 0, true, 0, 1.f);
-    prof_begin("cif_misc", 0);
-    launch_cif_alpha(stream_, conv32, B, T, D, cif_out_w_, cif_out_b_, mc_.cif_smooth, mc_.cif_noise, mc_.cif_tail, alphas_);
-    if (mc_.cif_cumsum) launch_cif_scan_cumsum(stream_, alphas_, B, T1, plan_);
-    else launch_cif_scan(stream_, alphas_, B, T1, mc_.cif_threshold, plan_);
-    prof_end("cif_misc");
-    export_plan(B);
-  }
-  // BiCIF timestamp head: ConvTranspose1d, LSTM and the excluded cif_output2 MatMul are float nodes of the int8 export too
-  // (quantize_dynamic is run with op_types_to_quantize = ["MatMul"]): the f16 path's head, beside the decoder
-  if (mc_.timestamp_head) start_timestamp_head(B, T);
-  int32_t L = read_back_plan(B);
-  if (l_hook_) L = l_hook_(L);
-  last_.B = B; last_.L = L; last_.V = V; last_.T = T;
-  last_.ids.assign((size_t)B * L, 0);
-  if (L == 0) { join_ts(); return; }
-  // ---- decoder
-  const int Md = B * L;
-  const int64_t Mdp = round_up(Md, 128) + 128;
-  half_t* kv16 = nullptr;
-  QAct qH;                                             // the quantised encoder memory (below)
-  DecRun r;
-  r.b = carve_into(ws_dec_, kAlignQ, [&](Arena& a) {
-    const DecBufs d = carve_dec8(a, Mdp, F);
-    kv16 = a.take<half_t>((size_t)Mp * 2 * D * 2); logits_ = a.take<float>((size_t)Mdp * ldV * 4); ids_dev_ = a.take<int64_t>((size_t)Md * 8);
-    qH.a = a.take<int8_t>((size_t)(Mp + 256) * round_up(D, 128)); qH.rowsum = a.take<int32_t>((size_t)(Mp + 256) * 4); qH.params = a.take<float>(64);
-    return d;
+}
+
+DecStage Engine::dec_arena_int8(int B, int T, int L) {
+  const int D = mc_.d_model, Md = B * L;
+  const int64_t Mp = round_up((int64_t)B * T, 128) + 128;
+  DecStage d;
+  d.rows = round_up(Md, 128) + 128;
+  d.b = carve_into(ws_dec_, kAlignQ, [&](Arena& a) {
+    const DecBufs b = carve_dec8(a, d.rows, mc_.ffn);
+    d.kv = a.take<half_t>((size_t)Mp * 2 * D * 2); logits_ = a.take<float>((size_t)d.rows * round_up(mc_.vocab, 4) * 4);
+    ids_dev_ = a.take<int64_t>((size_t)Md * 8);
+    d.qH.a = a.take<int8_t>((size_t)(Mp + 256) * round_up(D, 128)); d.qH.rowsum = a.take<int32_t>((size_t)(Mp + 256) * 4);
+    d.qH.params = a.take<float>(64);
+    return b;
   });
-  float* xd = r.b.x; float* t32 = r.b.t32;
-  logits_ld_ = ldV;
-  prof_begin("cif_misc", 0);
-  if (mc_.cif_cumsum) launch_cif_gather_cumsum(stream_, H32_, alphas_, B, T, D, T1, plan_, L, xd);
-  else launch_cif_gather(stream_, H32_, B, T, D, T1, plan_, L, xd);
-  prof_end("cif_misc");
-  const bool bias_branch = mc_.seaco && n_hotwords_ > 0;
-  float* e0 = nullptr;                                 // SeACo: the bias decoder also starts from the CIF embeds
-  float* hid32 = nullptr;
-  if (bias_branch) {
-    ensure(ws_seaco_in_, (size_t)2 * Mdp * D * 4);
-    e0 = (float*)ws_seaco_in_.p;
-    hid32 = e0 + (size_t)Mdp * D;
-    PF_HIP(hipMemcpyAsync(e0, xd, (size_t)Md * D * 4, hipMemcpyDeviceToDevice, stream_));
-  }
+  return d;
+}
+
+void Engine::asr_decoder_int8(DecStage& d, int B, int T, int L) {
+  const int D = mc_.d_model, M = B * T, Md = B * L;
+  half_t* kv16 = (half_t*)d.kv;
+  const QAct& qH = d.qH;
+  float* t32 = d.b.t32;
+  logits_ld_ = (int)round_up(mc_.vocab, 4);
   // K / V of the encoder memory: every layer's MatMul quantises the SAME tensor — one DynamicQuantizeLinear result here
   quantize_act(qH, (int)round_up(D, 128), H32_, nullptr, D, M, D, nullptr);
+  DecRun r;
+  r.b = d.b;
   r.B = B; r.L = L; r.token_num = plan_.token_num;
   r.kv_rs = 2 * D; r.kv_bs = (int64_t)T * 2 * D; r.Lk = T;
   r.kv_layer = [&](int i) -> const void* {
     const Lin& kv = dec_.layers[i].kv32;
     if (lin_quantised(kv))
-      qgemm("gemm_dec_kv", kv, true, nullptr, nullptr, D, (int)M, nullptr, 0, kv16, 2 * D, nullptr, 0, nullptr, 0, false, 0, 1.f, nullptr, &qH);
+      qgemm("gemm_dec_kv", kv, true, nullptr, nullptr, D, M, nullptr, 0, kv16, 2 * D, nullptr, 0, nullptr, 0, false, 0, 1.f, nullptr, &qH);
     else
-      gemm("gemm_dec_kv", kv, H16_, D, (int)M, nullptr, 0, kv16, 2 * D, nullptr, 0, nullptr, 0, false, 0, 1.f);
+      gemm("gemm_dec_kv", kv, H16_, D, M, nullptr, 0, kv16, 2 * D, nullptr, 0, nullptr, 0, false, 0, 1.f);
     return kv16;
   };
   decoder_int8(dec_, r);
-  if (bias_branch) {                                   // the bias decoder's second input: the after_norm hidden itself
+  if (d.hid) {                                         // the bias decoder's second input: the after_norm hidden itself
     prof_begin("layernorm", 0);
-    launch_layernorm(stream_, t32, Md, D, dec_.after.g, dec_.after.b, nullptr, 0, hid32, D);
+    launch_layernorm(stream_, t32, Md, D, dec_.after.g, dec_.after.b, nullptr, 0, d.hid, D);
     prof_end("layernorm");
-    qgemm("gemm_vocab", dec_.out, true, hid32, nullptr, D, Md, logits_, ldV, nullptr, 0, nullptr, 0, nullptr, 0, false, 0, 1.f);
+    qgemm("gemm_vocab", dec_.out, true, d.hid, nullptr, D, Md, logits_, logits_ld_, nullptr, 0, nullptr, 0, nullptr, 0, false, 0, 1.f);
   } else {
-    qgemm("gemm_vocab", dec_.out, true, t32, nullptr, D, Md, logits_, ldV, nullptr, 0, nullptr, 0, nullptr, 0, false, 0, 1.f, &dec_.after);
+    qgemm("gemm_vocab", dec_.out, true, t32, nullptr, D, Md, logits_, logits_ld_, nullptr, 0, nullptr, 0, nullptr, 0, false, 0, 1.f, &dec_.after);
   }
-  prof_begin("argmax", 0);
-  launch_argmax(stream_, logits_, Md, V, ldV, argmax_mode(want_logits), ids_dev_, score_buf(Md));
-  prof_end("argmax");
-  if (bias_branch) seaco_head(B, L, e0, hid32, want_logits);
-  join_ts();
-  PF_HIP(hipMemcpyAsync(last_.ids.data(), ids_dev_, (size_t)Md * 8, hipMemcpyDeviceToHost, stream_));
-  queue_decode_results(B, L);
 }
 
 // ---- SeACo bias branch in math_mode 2 (reference default for the flagship model: model.int8.onnx + model_eb.int8.onnx,

@@ -2248,14 +2248,12 @@ void Engine::op_cif(const float* H, const float* alphas, int B, int T, int D, fl
   const int T1 = T + 1;
   size_t off = 0;
   const Carve carve{off};
-  const size_t oH = carve((size_t)B * T * D * 4), oa = carve((size_t)B * T1 * 4), ofc = carve((size_t)B * 4), otn = carve((size_t)B * 4);
-  const size_t off_ = carve((size_t)B * T1 * 4), owc = carve((size_t)B * T1 * 4), owr = carve((size_t)B * T1 * 4), omx = carve(256);
-  const size_t oE = carve((size_t)B * std::max(Lcap, 1) * D * 4);
+  const size_t oH = carve((size_t)B * T * D * 4);
+  const CifCarve o_cif(carve, B, T1);
+  const size_t oa = o_cif.al, oE = carve((size_t)B * std::max(Lcap, 1) * D * 4);
   ensure(ws_tmp_, off);
   char* base = (char*)ws_tmp_.p;
-  CifPlan p;
-  p.fire_count = (int32_t*)(base + ofc); p.token_num = (int32_t*)(base + otn); p.fire_frame = (int32_t*)(base + off_);
-  p.w_cur = (float*)(base + owc); p.w_rem = (float*)(base + owr); p.max_count = (int32_t*)(base + omx);
+  const CifPlan p = o_cif.plan(base);
   PF_HIP(hipMemcpyAsync(base + oH, H, (size_t)B * T * D * 4, hipMemcpyHostToDevice, stream_));
   PF_HIP(hipMemcpyAsync(base + oa, alphas, (size_t)B * T1 * 4, hipMemcpyHostToDevice, stream_));
   if (mc_.cif_cumsum) launch_cif_scan_cumsum(stream_, (const float*)(base + oa), B, T1, p);
@@ -2277,7 +2275,7 @@ void Engine::op_cif(const float* H, const float* alphas, int B, int T, int D, fl
 void Engine::op_cif_alphas(const float* H, int B, int T, float* alphas) {
   PF_CHECK(H && alphas && B > 0 && T > 0, PF_ERR_INVALID_ARG, "cif_alphas: bad arguments");
   PF_CHECK(mc_.kind != "sensevoicesmall", PF_ERR_UNSUPPORTED, "cif_alphas: paraformer models only");
-  PF_CHECK(!int8_mode_, PF_ERR_UNSUPPORTED, "cif_alphas: math_mode 0, 1 and 3 only (the int8 pipeline has its own predictor tail)");
+  PF_CHECK(!int8_mode_, PF_ERR_UNSUPPORTED, "cif_alphas: math_mode 0, 1 and 3 only (math_mode 2 runs math_mode 0's stage: ask an engine of that mode)");
   PF_HIP(hipSetDevice(device_));
   const int D = mc_.d_model, taps = mc_.cif_l_order + mc_.cif_r_order + 1;
   const int64_t M = (int64_t)B * T, Mp = round_up(M, 128) + 128;     // the pipeline's row padding (Engine::gemm: out_padded)

@@ -6,6 +6,9 @@ Models (synthetic, seeded):
      (the model of test_gpu_pipeline_kernels.py::test_decoder_middle_in_one_launch)
   S  SeACo paraformer with the timestamp head, the model of tests/test_gpu_seaco.py (seed 21, vocab 120, NO-BIAS 111)
   O  the streaming model and decoder-seam inputs of test_gpu_online.py::test_online_encoder_and_decoder_seams
+  V  SenseVoice, 3 encoder + 2 tp layers, vocab 403 (no multiple of 4), seed 9: the model of tests/test_gpu_sensevoice.py.  Its
+     "decoder" rows are those of the CTC head, B * (T + 4)
+  C  paraformer with cif_variant="cumsum", 2 encoder / 1 decoder layers, vocab 128, seed 23
 Audio (W.synth_audio(n, 300 + u)):
   long   18 utterances of [24, 9, 17, 0.25, 30, 13] s x 3: B * L > 512 decoder rows — the persistent / fused forms of the f16
          ASR decoder, live (hi | lo') operand pairs in math_mode 3
@@ -54,6 +57,9 @@ OFFLINE = (
     _case("S", "short", 3, hotwords=True),                  # 9  the two-launch product at or below the threshold
     _case("P", "short", 2), _case("P", "long", 2),          # 10 int8
     _case("S", "short", 2, hotwords=True), _case("S", "long", 2, hotwords=True),
+    _case("V", "short", 0), _case("V", "short", 1), _case("V", "short", 2), _case("V", "short", 3),   # 11 the CTC head per arithmetic
+    _case("V", "long", 0), _case("V", "long", 2),
+    _case("C", "short", 0), _case("C", "short", 1), _case("C", "short", 2),   # 12 the cumsum scan and gather per arithmetic
 )
 BY_NAME = {c.name: c for c in OFFLINE}
 
@@ -70,7 +76,14 @@ def model(which):
         w = W.synth_weights(cfg, 21)
         w["predictor.out.bias"] = np.asarray([0.0], np.float32)
         w["seaco.output.bias"][111] += 2.6
+    elif which == "V":
+        cfg = W.sensevoice_small_config(enc_layers=3, tp_layers=2, vocab=403)
+        w = W.synth_weights(cfg, seed=9)
+    elif which == "C":
+        cfg = W.paraformer_large_config(enc_layers=2, dec_layers=1, vocab=128, cif_variant="cumsum")
+        w = W.synth_weights(cfg, seed=23)
     else:
+        assert which == "O", which
         cfg = W.paraformer_large_config(enc_layers=3, dec_layers=3, vocab=300)
         w = W.synth_weights(cfg, seed=31)
         w["predictor.out.bias"] = np.asarray([0.8], np.float32)

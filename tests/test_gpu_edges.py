@@ -78,17 +78,46 @@ def test_long_utterance_many_key_tiles(small):
     _cmp(res, ref, 3e-2)
 
 
-def test_no_fire_gives_empty_hypotheses():
-    """alphas ~ 0 everywhere: sum = tail threshold 0.45 < 1 -> token_num = 0, L = 0, no decoder launch."""
+@pytest.mark.parametrize("mode,ts", [(0, False), (1, False), (2, False), (3, False), (0, True), (2, True)],
+                         ids=lambda v: {False: "plain", True: "ts"}[v] if isinstance(v, bool) else "m%d" % v)
+def test_no_fire_gives_empty_hypotheses(mode, ts):
+    """alphas ~ 0 everywhere: sum = tail threshold 0.45 < 1 -> token_num = 0, L = 0, no decoder launch.
+    The L == 0 exit is one code path of the pipeline for every arithmetic; with the timestamp head beside the decoder
+    (modes 0 and 2) it must still join the side stream.  The engine that met it stays usable: a second, different batch is
+    empty again and leaves no error.  The predictor bias is a weight, so what fires is a second engine (bias 0): two
+    recognitions in a row are equal bit for bit, cif_peak included."""
     from aliparaformerasr_amd.engine import Engine
-    cfg = W.paraformer_large_config(enc_layers=1, dec_layers=1, vocab=64)
+    cfg = W.paraformer_large_config(enc_layers=1, dec_layers=1, vocab=64, timestamp_head=ts)
     w = W.synth_weights(cfg, seed=8)
-    w["predictor.out.bias"] = np.asarray([-30.0], np.float32)
     cmvn = W.synth_cmvn()
-    eng = Engine(weights=W.pack_pfw(cfg, w), cmvn=cmvn, device=0)
-    res = eng.recognize([W.synth_audio(16000, 1), W.synth_audio(12000, 2)])
-    assert res.L == 0 and res.token_ids.shape == (2, 0) and list(res.token_num) == [0, 0]
-    eng.close()
+    audio = [W.synth_audio(16000, 1), W.synth_audio(12000, 2)]
+    other = [W.synth_audio(20000, 3), W.synth_audio(9000, 4), W.synth_audio(14000, 5)]
+
+    w["predictor.out.bias"] = np.asarray([-30.0], np.float32)
+    eng = Engine(weights=W.pack_pfw(cfg, w), cmvn=cmvn, device=0, math_mode=mode)
+    try:
+        res = eng.recognize(audio, want_logits=True)
+        assert res.L == 0 and res.token_ids.shape == (2, 0) and list(res.token_num) == [0, 0]
+        res = eng.recognize(other)
+        assert res.L == 0 and res.token_ids.shape == (3, 0) and list(res.token_num) == [0, 0, 0]
+        eng.sync()                                    # raises what a forward left pending
+    finally:
+        eng.close()
+
+    w["predictor.out.bias"] = np.asarray([0.0], np.float32)
+    eng = Engine(weights=W.pack_pfw(cfg, w), cmvn=cmvn, device=0, math_mode=mode)
+    try:
+        a = eng.recognize(audio, want_logits=True)
+        b = eng.recognize(audio, want_logits=True)
+        assert a.L > 0 and a.L == b.L
+        np.testing.assert_array_equal(a.token_ids, b.token_ids)
+        np.testing.assert_array_equal(a.token_num, b.token_num)
+        assert a.logits.tobytes() == b.logits.tobytes()
+        assert (a.cif_peak is not None) == ts
+        if ts:
+            assert a.cif_peak.size > 0 and a.cif_peak.tobytes() == b.cif_peak.tobytes()
+    finally:
+        eng.close()
 
 
 def test_timestamp_head_batch_larger_than_one_lstm_tile():

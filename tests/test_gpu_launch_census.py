@@ -1,7 +1,8 @@
 """GPU: which forms the decoder walks select, as launch counts per profile class (tests/decoder_cases.py).
 
 tests/golden/decoder_launch_census.json is a recorded result: tools/decoder_census.py --golden, run on the commit before the
-decoder walks were folded into one per arithmetic.  A refactor of the walks keeps every count: the bias decoder must not
+decoder walks were folded into one per arithmetic (the V and C cases: on the commit before the three forward pipelines were
+folded into one, where the same run reproduced the older entries).  A refactor of the walks keeps every count: the bias decoder must not
 start taking the short-input or fused forms, the ASR decoder must keep its three-launch layer, the int8 bias decoder its
 two passes.  The streaming seam is not in the census: that fold gave its non-GEMM launches the brackets of the bias
 decoder, so its counts changed by design; tools/decoder_census.py reports its bit identity."""
