@@ -332,6 +332,13 @@ SIGNATURES = {
     "pf_op_attn_ffn_fused": (C.c_int, [_vp, _vp, _f, _f]),
     "pf_op_dec_mid": (C.c_int, [_vp, C.c_void_p, _f, _f, _f, _f, _i32]),
     "pf_op_fsmn_dec_ln": (C.c_int, [_vp, _f, _f, _i32, C.c_int32, C.c_int32, C.c_int32, _f, _f, _f, _f, _f]),
+    "pf_op_layernorm_ex": (C.c_int, [_vp, _f, _f, _f, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P(C.c_uint16), _f]),
+    "pf_op_layernorm_f16": (C.c_int, [_vp, _P(C.c_uint16), _f, _f, C.c_int64, C.c_int32, C.c_int32, _P(C.c_uint16)]),
+    "pf_op_fsmn_dec_stream": (C.c_int, [_vp, _f, _f, _i32, _f, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f, _f, _f]),
+    "pf_op_embed_gather": (C.c_int, [_vp, _f, _i32, C.c_int32, C.c_int32, C.c_int32, _f, _P(C.c_uint16)]),
+    "pf_op_add_to_f16": (C.c_int, [_vp, _f, _f, C.c_int64, C.c_int32, _P(C.c_uint16)]),
+    "pf_op_seaco_merge": (C.c_int, [_vp, _f, C.c_int32, _i64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _f, C.c_int32, _i64, _f, _i64]),
+    "pf_op_short_input_max_rows": (C.c_int, [_vp, _i32]),
     "pf_op_fsmn_enc": (C.c_int, [_vp, _f, _f, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f]),
     "pf_op_linear32": (C.c_int, [_vp, _f, _f, _f, _f, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f]),
     "pf_op_ffn32": (C.c_int, [_vp, _f, _f, _f, _f, _f, C.c_int32, C.c_int32, C.c_int32, _f]),

@@ -1472,6 +1472,80 @@ int pf_op_fsmn_dec_ln(pf_engine* h, const float* tn, const float* taps, const in
   return PF_OK;
   PF_CATCH
 }
+int pf_op_layernorm_ex(pf_engine* h, const float* x, const float* gamma, const float* beta, int64_t rows, int32_t D, int32_t ld16, int32_t ld32,
+                       int32_t posenc_T, uint16_t* out16, float* out32) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  NEED(x); NEED(gamma); NEED(beta);
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->op_layernorm_ex(x, gamma, beta, rows, D, ld16, ld32, posenc_T, out16, out32);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_op_layernorm_f16(pf_engine* h, const uint16_t* x, const float* gamma, const float* beta, int64_t rows, int32_t D, int32_t in_place,
+                        uint16_t* out) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  NEED(x); NEED(gamma); NEED(beta); NEED(out);
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->op_layernorm_f16(x, gamma, beta, rows, D, in_place, out);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_op_fsmn_dec_stream(pf_engine* h, const float* tn, const float* taps, const int32_t* len, const float* cache_in, int32_t B, int32_t L,
+                          int32_t D, int32_t k, const float* x, float* x_out, float* cache_out) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  NEED(tn); NEED(taps); NEED(len); NEED(cache_in); NEED(x); NEED(x_out); NEED(cache_out);
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->op_fsmn_dec_stream(tn, taps, len, cache_in, B, L, D, k, x, x_out, cache_out);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_op_embed_gather(pf_engine* h, const float* table, const int32_t* ids, int32_t rows, int32_t D, int32_t vocab, float* out32,
+                       uint16_t* out16) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  NEED(table); NEED(ids); NEED(out32);
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->op_embed_gather(table, ids, rows, D, vocab, out32, out16);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_op_add_to_f16(pf_engine* h, const float* a, const float* b, int64_t rows, int32_t D, uint16_t* out16) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  NEED(a); NEED(b); NEED(out16);
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->op_add_to_f16(a, b, rows, D, out16);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_op_seaco_merge(pf_engine* h, const float* dha, int32_t ld_dha, const int64_t* dha_ids, int64_t rows, int32_t V, int32_t nobias,
+                      int32_t copy_logits, const float* logits_in, int32_t ld_logits, const int64_t* ids_in, float* logits_out,
+                      int64_t* ids_out) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  NEED(dha); NEED(dha_ids); NEED(logits_in); NEED(ids_in); NEED(logits_out); NEED(ids_out);
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->op_seaco_merge(dha, ld_dha, dha_ids, rows, V, nobias, copy_logits, logits_in, ld_logits, ids_in, logits_out, ids_out);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_op_short_input_max_rows(pf_engine* h, int32_t* rows) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  NEED(rows);
+  *rows = eh_->short_input_max_rows();
+  return PF_OK;
+  PF_CATCH
+}
 int pf_op_attn_ffn_fused(pf_engine* h, const pf_attn_ffn_desc* d, float* x_out, float* n16_out) {
   PF_TRY
   std::shared_ptr<Engine> eh_ = E(h);

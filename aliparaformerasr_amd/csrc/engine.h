@@ -330,6 +330,17 @@ class Engine {
   void op_dec_mid(const pf_dec_mid_desc& ds, float* x_out, float* q_out, float* tn_out, float* xn16_out, int32_t* ran);
   void op_fsmn_dec_ln(const float* tn, const float* taps, const int32_t* token_num, int B, int L, int k, const float* x, const float* gamma,
                       const float* beta, float* x_out, float* xn16_out);
+  // the row kernels of k_norm.hip / k_misc.hip alone; every result comes back with its guard rows (include/paraformer_hip.h)
+  void op_layernorm_ex(const float* x, const float* g, const float* b, int64_t rows, int D, int ld16, int ld32, int posenc_T, uint16_t* out16,
+                       float* out32);
+  void op_layernorm_f16(const uint16_t* x, const float* g, const float* b, int64_t rows, int D, int in_place, uint16_t* out);
+  void op_fsmn_dec_stream(const float* tn, const float* taps, const int32_t* len, const float* cache_in, int B, int L, int D, int k,
+                          const float* x, float* x_out, float* cache_out);
+  void op_embed_gather(const float* table, const int32_t* ids, int rows, int D, int vocab, float* out32, uint16_t* out16);
+  void op_add_to_f16(const float* a, const float* b, int64_t rows, int D, uint16_t* out16);
+  void op_seaco_merge(const float* dha, int ld_dha, const int64_t* dha_ids, int64_t rows, int V, int nobias, int copy_logits,
+                      const float* logits_in, int ld_logits, const int64_t* ids_in, float* logits_out, int64_t* ids_out);
+  int short_input_max_rows() const { return small_ws_ ? gemm_small_max_rows() : 0; }   // M up to which enc_layer() takes k_gemm_small.hip
   void op_ffn_fused(const float* x, const float* w1, const float* b1, const float* w2, const float* b2, const float* resid,
                     const float* g, const float* be, int M, float* x_out, float* n16_out, const pf_attn_ffn_desc* op = nullptr);
   void op_ffn(const float* x, const float* w1, const float* b1, const float* w2, const float* b2, const float* resid,

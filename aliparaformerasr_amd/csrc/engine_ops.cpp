@@ -1751,6 +1751,166 @@ void Engine::op_fsmn_dec_ln(const float* tn, const float* taps, const int32_t* t
     for (size_t i = 0; i < n16.size(); ++i) xn16_out[i] = (float)n16[i];
 }
 
+// ---- the row kernels alone (k_norm.hip, the non-CIF half of k_misc.hip): thin wrappers, no arithmetic of their own.  Every result
+// buffer is PF_OP_GUARD_ROWS rows longer at either end than the result (and as wide as the caller's row stride), holds the
+// sentinel before the launch and goes back to the caller WHOLE: what the kernel wrote outside its result is the caller's to see.
+namespace {
+constexpr int kG = PF_OP_GUARD_ROWS;
+}  // namespace
+
+void Engine::op_layernorm_ex(const float* x, const float* g, const float* b, int64_t rows, int D, int ld16, int ld32, int posenc_T,
+                             uint16_t* out16, float* out32) {
+  PF_HIP(hipSetDevice(device_));
+  PF_CHECK(rows > 0 && rows < (1 << 24) && D > 0 && D % 4 == 0 && D <= 2048, PF_ERR_INVALID_ARG, "layernorm_ex: bad shape");
+  PF_CHECK(out16 || out32, PF_ERR_INVALID_ARG, "layernorm_ex: no output requested");
+  PF_CHECK(!out16 || (ld16 >= D && ld16 % 4 == 0), PF_ERR_INVALID_ARG, "layernorm_ex: ld16 must be a multiple of 4, >= D");
+  PF_CHECK(!out32 || (ld32 >= D && ld32 % 4 == 0), PF_ERR_INVALID_ARG, "layernorm_ex: ld32 must be a multiple of 4, >= D");
+  PF_CHECK(posenc_T == 0 || (posenc_T > 0 && rows % posenc_T == 0 && D == mc_.feat_dim && out16 && !out32), PF_ERR_INVALID_ARG,
+           "layernorm_ex: the position-encoding form takes [B, T, feat_dim] and writes f16 only");
+  if (!out16) ld16 = 0;
+  if (!out32) ld32 = 0;
+  if (posenc_T) build_pe(posenc_T);                           // the table the encoder would use, by the call the encoder makes
+  size_t off = 0;
+  const Carve carve{off};
+  const size_t ox = carve((size_t)(rows + 2) * D * 4), og = carve((size_t)D * 4), ob = carve((size_t)D * 4);
+  const size_t o16 = carve((size_t)(rows + 2 * kG) * std::max(ld16, 1) * 2), o32 = carve((size_t)(rows + 2 * kG) * std::max(ld32, 1) * 4);
+  ensure(ws_tmp_, off);
+  char* base = (char*)ws_tmp_.p;
+  fill_hostile_rows32(stream_, (float*)(base + ox), D, rows, rows + 2);          // the rows behind rows - 1 are never read
+  PF_HIP(hipMemcpyAsync(base + ox, x, (size_t)rows * D * 4, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipMemcpyAsync(base + og, g, (size_t)D * 4, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipMemcpyAsync(base + ob, b, (size_t)D * 4, hipMemcpyHostToDevice, stream_));
+  if (out16) fill_sentinel16(stream_, base + o16, (size_t)(rows + 2 * kG) * ld16);
+  if (out32) fill_sentinel32(stream_, base + o32, (size_t)(rows + 2 * kG) * ld32);
+  half_t* d16 = out16 ? (half_t*)(base + o16) + (size_t)kG * ld16 : nullptr;
+  float* d32 = out32 ? (float*)(base + o32) + (size_t)kG * ld32 : nullptr;
+  if (posenc_T)
+    launch_posenc_ln_tab(stream_, (const float*)(base + ox), (int)(rows / posenc_T), posenc_T, D, std::sqrt((float)mc_.d_model),
+                         (const float*)ws_pe_.p, (const float*)(base + og), (const float*)(base + ob), d16, ld16);
+  else
+    launch_layernorm(stream_, (const float*)(base + ox), rows, D, (const float*)(base + og), (const float*)(base + ob), d16, ld16, d32, ld32);
+  if (out16) PF_HIP(hipMemcpyAsync(out16, base + o16, (size_t)(rows + 2 * kG) * ld16 * 2, hipMemcpyDeviceToHost, stream_));
+  if (out32) PF_HIP(hipMemcpyAsync(out32, base + o32, (size_t)(rows + 2 * kG) * ld32 * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipStreamSynchronize(stream_));
+}
+
+void Engine::op_layernorm_f16(const uint16_t* x, const float* g, const float* b, int64_t rows, int D, int in_place, uint16_t* out) {
+  PF_HIP(hipSetDevice(device_));
+  PF_CHECK(rows > 0 && rows < (1 << 24) && D > 0 && D % 8 == 0 && D <= 2048, PF_ERR_INVALID_ARG, "layernorm_f16: bad shape");
+  const size_t cells = (size_t)(rows + 2 * kG) * D;
+  size_t off = 0;
+  const Carve carve{off};
+  const size_t ox = carve((size_t)rows * D * 2), og = carve((size_t)D * 4), ob = carve((size_t)D * 4), oo = carve(cells * 2);
+  ensure(ws_tmp_, off);
+  char* base = (char*)ws_tmp_.p;
+  fill_sentinel16(stream_, base + oo, cells);
+  half_t* dst = (half_t*)(base + oo) + (size_t)kG * D;
+  half_t* src = in_place ? dst : (half_t*)(base + ox);
+  PF_HIP(hipMemcpyAsync(src, x, (size_t)rows * D * 2, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipMemcpyAsync(base + og, g, (size_t)D * 4, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipMemcpyAsync(base + ob, b, (size_t)D * 4, hipMemcpyHostToDevice, stream_));
+  launch_layernorm_f16(stream_, src, rows, D, (const float*)(base + og), (const float*)(base + ob), dst);
+  PF_HIP(hipMemcpyAsync(out, base + oo, cells * 2, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipStreamSynchronize(stream_));
+}
+
+// The rows of tn at l >= len[b] hold a large finite pattern on the device: the kernel must mask them, not multiply them by zero.
+void Engine::op_fsmn_dec_stream(const float* tn, const float* taps, const int32_t* len, const float* cache_in, int B, int L, int D, int k,
+                                const float* x, float* x_out, float* cache_out) {
+  PF_HIP(hipSetDevice(device_));
+  PF_CHECK(B > 0 && L > 0 && D > 0 && k >= 2 && (int64_t)B * L * D < (1 << 28), PF_ERR_INVALID_ARG, "fsmn_dec_stream: bad shape");
+  const int CW = k - 1, M = B * L;
+  size_t off = 0;
+  const Carve carve{off};
+  const size_t ot = carve((size_t)M * D * 4), ow = carve((size_t)k * D * 4), on = carve((size_t)B * 4), oc = carve((size_t)B * D * CW * 4);
+  const size_t ox = carve((size_t)(M + 2 * kG) * D * 4), oco = carve((size_t)((int64_t)B * D + 2 * kG) * CW * 4);
+  ensure(ws_tmp_, off);
+  char* base = (char*)ws_tmp_.p;
+  fill_hostile_rows32(stream_, (float*)(base + ot), D, 0, M);
+  for (int bb = 0; bb < B; ++bb) {
+    const int nv = std::min(std::max(len[bb], 0), L);
+    if (nv) PF_HIP(hipMemcpyAsync(base + ot + (size_t)bb * L * D * 4, tn + (size_t)bb * L * D, (size_t)nv * D * 4, hipMemcpyHostToDevice, stream_));
+  }
+  PF_HIP(hipMemcpyAsync(base + ow, taps, (size_t)k * D * 4, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipMemcpyAsync(base + on, len, (size_t)B * 4, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipMemcpyAsync(base + oc, cache_in, (size_t)B * D * CW * 4, hipMemcpyHostToDevice, stream_));
+  fill_sentinel32(stream_, base + ox, (size_t)(M + 2 * kG) * D);
+  fill_sentinel32(stream_, base + oco, (size_t)((int64_t)B * D + 2 * kG) * CW);
+  float* dx = (float*)(base + ox) + (size_t)kG * D;
+  float* dc = (float*)(base + oco) + (size_t)kG * CW;
+  PF_HIP(hipMemcpyAsync(dx, x, (size_t)M * D * 4, hipMemcpyHostToDevice, stream_));
+  launch_fsmn_dec_stream(stream_, (const float*)(base + ot), (const float*)(base + ow), (const int32_t*)(base + on), (const float*)(base + oc),
+                         B, L, D, k, dx, dc);
+  PF_HIP(hipMemcpyAsync(x_out, base + ox, (size_t)(M + 2 * kG) * D * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipMemcpyAsync(cache_out, base + oco, (size_t)((int64_t)B * D + 2 * kG) * CW * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipStreamSynchronize(stream_));
+}
+
+// The table sits between two rows of the large finite pattern: an id clamped one row off returns them.
+void Engine::op_embed_gather(const float* table, const int32_t* ids, int rows, int D, int vocab, float* out32, uint16_t* out16) {
+  PF_HIP(hipSetDevice(device_));
+  PF_CHECK(rows > 0 && D > 0 && D % 4 == 0 && vocab > 0, PF_ERR_INVALID_ARG, "embed_gather: bad shape");
+  const size_t cells = (size_t)(rows + 2 * kG) * D;
+  size_t off = 0;
+  const Carve carve{off};
+  const size_t ot = carve((size_t)(vocab + 2) * D * 4), oi = carve((size_t)rows * 4), o32 = carve(cells * 4), o16 = carve(cells * 2);
+  ensure(ws_tmp_, off);
+  char* base = (char*)ws_tmp_.p;
+  fill_hostile_rows32(stream_, (float*)(base + ot), D, 0, 1);
+  fill_hostile_rows32(stream_, (float*)(base + ot), D, vocab + 1, vocab + 2);
+  PF_HIP(hipMemcpyAsync(base + ot + (size_t)D * 4, table, (size_t)vocab * D * 4, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipMemcpyAsync(base + oi, ids, (size_t)rows * 4, hipMemcpyHostToDevice, stream_));
+  fill_sentinel32(stream_, base + o32, cells);
+  fill_sentinel16(stream_, base + o16, cells);
+  launch_embed_gather(stream_, (const float*)(base + ot) + D, (const int32_t*)(base + oi), rows, D, vocab, (float*)(base + o32) + (size_t)kG * D,
+                      out16 ? (half_t*)(base + o16) + (size_t)kG * D : nullptr);
+  PF_HIP(hipMemcpyAsync(out32, base + o32, cells * 4, hipMemcpyDeviceToHost, stream_));
+  if (out16) PF_HIP(hipMemcpyAsync(out16, base + o16, cells * 2, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipStreamSynchronize(stream_));
+}
+
+void Engine::op_add_to_f16(const float* a, const float* b, int64_t rows, int D, uint16_t* out16) {
+  PF_HIP(hipSetDevice(device_));
+  PF_CHECK(rows > 0 && rows < (1 << 24) && D > 0 && D % 4 == 0, PF_ERR_INVALID_ARG, "add_to_f16: bad shape");
+  const size_t n = (size_t)rows * D, cells = (size_t)(rows + 2 * kG) * D;
+  size_t off = 0;
+  const Carve carve{off};
+  const size_t oa = carve(n * 4), ob = carve(n * 4), oo = carve(cells * 2);
+  ensure(ws_tmp_, off);
+  char* base = (char*)ws_tmp_.p;
+  PF_HIP(hipMemcpyAsync(base + oa, a, n * 4, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipMemcpyAsync(base + ob, b, n * 4, hipMemcpyHostToDevice, stream_));
+  fill_sentinel16(stream_, base + oo, cells);
+  launch_add_to_f16(stream_, (const float*)(base + oa), (const float*)(base + ob), rows, D, (half_t*)(base + oo) + (size_t)kG * D);
+  PF_HIP(hipMemcpyAsync(out16, base + oo, cells * 2, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipStreamSynchronize(stream_));
+}
+
+// dha goes up with its pad columns [V, ld_dha) as the caller filled them; logits and ids go up as the caller's, between the guards.
+void Engine::op_seaco_merge(const float* dha, int ld_dha, const int64_t* dha_ids, int64_t rows, int V, int nobias, int copy_logits,
+                            const float* logits_in, int ld_logits, const int64_t* ids_in, float* logits_out, int64_t* ids_out) {
+  PF_HIP(hipSetDevice(device_));
+  PF_CHECK(rows > 0 && rows < (1 << 20) && V > 0 && ld_dha >= V && ld_logits >= V, PF_ERR_INVALID_ARG, "seaco_merge: bad shape");
+  size_t off = 0;
+  const Carve carve{off};
+  const size_t od = carve((size_t)rows * ld_dha * 4), odi = carve((size_t)rows * 8);
+  const size_t ol = carve((size_t)(rows + 2 * kG) * ld_logits * 4), oi = carve((size_t)(rows + 2 * kG) * 8);
+  ensure(ws_tmp_, off);
+  char* base = (char*)ws_tmp_.p;
+  PF_HIP(hipMemcpyAsync(base + od, dha, (size_t)rows * ld_dha * 4, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipMemcpyAsync(base + odi, dha_ids, (size_t)rows * 8, hipMemcpyHostToDevice, stream_));
+  fill_sentinel32(stream_, base + ol, (size_t)(rows + 2 * kG) * ld_logits);
+  fill_sentinel32(stream_, base + oi, (size_t)(rows + 2 * kG) * 2);
+  float* dl = (float*)(base + ol) + (size_t)kG * ld_logits;
+  int64_t* di = (int64_t*)(base + oi) + kG;
+  PF_HIP(hipMemcpyAsync(dl, logits_in, (size_t)rows * ld_logits * 4, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipMemcpyAsync(di, ids_in, (size_t)rows * 8, hipMemcpyHostToDevice, stream_));
+  launch_seaco_merge(stream_, (const float*)(base + od), ld_dha, (const int64_t*)(base + odi), rows, V, nobias, copy_logits, dl, ld_logits, di);
+  PF_HIP(hipMemcpyAsync(logits_out, base + ol, (size_t)(rows + 2 * kG) * ld_logits * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipMemcpyAsync(ids_out, base + oi, (size_t)(rows + 2 * kG) * 8, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipStreamSynchronize(stream_));
+}
+
 // The middle of a decoder layer in the three forms the engine can run it (include/paraformer_hip.h pf_op_dec_mid), on a
 // hostile host: operand rows behind M - 1 hold the large finite pattern, x / q / tn / xn16 sit in sentinel-guarded buffers
 // (q with a row stride of 520 halves), the bytes behind the split form's workspace are guarded, and a row of x at

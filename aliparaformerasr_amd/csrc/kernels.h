@@ -350,6 +350,9 @@ bool launch_fsmn_dec_ln(hipStream_t s, const float* tn, const float* w, const in
                         float* x, const float* gamma, const float* beta, half_t* out16);
 // streaming decoder FSMN (FunASR MultiHeadedAttentionSANMDecoder export with a cache): xc = cat(cache_in [B,D,K-1],
 // (tn*m)^T); x[b,l,:] += (sum_j w_j * xc[l+j] + tn[l]*m) * m, m = (l < len[b]); cache_out = last K-1 columns of xc
+// read: tn rows with l < min(len[b], L) only (a masked row may hold anything; it enters xc and cache_out as +0, where the
+// graph's tn * 0 is -0 for a negative tn);  written: x rows with l < len[b] (every other cell keeps its bits), cache_out
+// [B, D, K-1], all of it, a bitwise copy of its source columns; cache_out must not alias cache_in
 void launch_fsmn_dec_stream(hipStream_t s, const float* tn, const float* wT, const int32_t* len, const float* cache_in,
                             int B, int L, int D, int k, float* x, float* cache_out);
 // generic fp32 FSMN for the stand-alone op (mask [B,T] floats or null)

@@ -1687,6 +1687,92 @@ class Engine:
                                             _fp(x), _fp(g), _fp(b), _fp(xo), _fp(xn)))
         return xo, xn
 
+    # ---- the row kernels alone.  Every result is the WHOLE guarded buffer of the C ABI: OP_GUARD_ROWS canary rows, the result,
+    # OP_GUARD_ROWS canary rows, each row as wide as its row stride; f16 results are uint16 bit patterns.
+    OP_GUARD_ROWS = 2
+    OP_CANARY32 = 0x7FC5A5A5
+    OP_CANARY16 = 0x7E5A
+
+    def op_layernorm_ex(self, x, gamma, beta, want16=True, want32=True, ld16=0, ld32=0, posenc_T=0):
+        """launch_layernorm on x [rows, D] (pf_op_layernorm_ex), or with posenc_T launch_posenc_ln_tab on x [B, posenc_T, D];
+        returns (out16 [rows + 4, ld16] uint16 | None, out32 [rows + 4, ld32] float32 | None)."""
+        x, g, b = _f32(x), _f32(gamma), _f32(beta)
+        D = x.shape[-1]
+        rows = x.size // D
+        ld16, ld32 = ld16 or D, ld32 or D
+        G = self.OP_GUARD_ROWS
+        o16 = np.zeros((rows + 2 * G, ld16), np.uint16) if want16 else None
+        o32 = np.zeros((rows + 2 * G, ld32), np.float32) if want32 else None
+        N.check(self._lib.pf_op_layernorm_ex(self._h, _fp(x), _fp(g), _fp(b), rows, D, ld16, ld32, posenc_T,
+                                             o16.ctypes.data_as(C.POINTER(C.c_uint16)) if want16 else None, _fp(o32) if want32 else None))
+        return o16, o32
+
+    def op_layernorm_f16(self, x16, gamma, beta, in_place=True) -> np.ndarray:
+        """launch_layernorm_f16 on x16 [rows, D] float16 (pf_op_layernorm_f16): [rows + 4, D] uint16."""
+        x = np.ascontiguousarray(x16, dtype=np.float16)
+        g, b = _f32(gamma), _f32(beta)
+        rows, D = x.shape
+        out = np.zeros((rows + 2 * self.OP_GUARD_ROWS, D), np.uint16)
+        N.check(self._lib.pf_op_layernorm_f16(self._h, x.view(np.uint16).ctypes.data_as(C.POINTER(C.c_uint16)), _fp(g), _fp(b), rows, D,
+                                              1 if in_place else 0, out.ctypes.data_as(C.POINTER(C.c_uint16))))
+        return out
+
+    def op_fsmn_dec_stream(self, tn, taps, lens, cache_in, x):
+        """launch_fsmn_dec_stream (pf_op_fsmn_dec_stream): tn, x [B, L, D], taps [k, D], cache_in [B, D, k - 1];
+        returns (x [B L + 4, D], cache_out [B D + 4, k - 1])."""
+        tn, taps, cin, x = _f32(tn), _f32(taps), _f32(cache_in), _f32(x)
+        B, L, D = tn.shape
+        k = taps.shape[0]
+        assert x.shape == tn.shape and taps.shape == (k, D) and cin.shape == (B, D, k - 1)
+        t = np.ascontiguousarray(lens, dtype=np.int32)
+        assert t.shape == (B,)
+        G = self.OP_GUARD_ROWS
+        xo, co = np.zeros((B * L + 2 * G, D), np.float32), np.zeros((B * D + 2 * G, k - 1), np.float32)
+        N.check(self._lib.pf_op_fsmn_dec_stream(self._h, _fp(tn), _fp(taps), t.ctypes.data_as(C.POINTER(C.c_int32)), _fp(cin), B, L, D, k,
+                                                _fp(x), _fp(xo), _fp(co)))
+        return xo, co
+
+    def op_embed_gather(self, table, ids, want16=True):
+        """launch_embed_gather (pf_op_embed_gather): (out32 [rows + 4, D], out16 [rows + 4, D] uint16 | None)."""
+        table = _f32(table)
+        vocab, D = table.shape
+        i = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        G = self.OP_GUARD_ROWS
+        o32 = np.zeros((i.size + 2 * G, D), np.float32)
+        o16 = np.zeros((i.size + 2 * G, D), np.uint16) if want16 else None
+        N.check(self._lib.pf_op_embed_gather(self._h, _fp(table), i.ctypes.data_as(C.POINTER(C.c_int32)), i.size, D, vocab, _fp(o32),
+                                             o16.ctypes.data_as(C.POINTER(C.c_uint16)) if want16 else None))
+        return o32, o16
+
+    def op_add_to_f16(self, a, b) -> np.ndarray:
+        """launch_add_to_f16 (pf_op_add_to_f16): [rows + 4, D] uint16."""
+        a, b = _f32(a), _f32(b)
+        rows, D = a.shape
+        assert b.shape == a.shape
+        out = np.zeros((rows + 2 * self.OP_GUARD_ROWS, D), np.uint16)
+        N.check(self._lib.pf_op_add_to_f16(self._h, _fp(a), _fp(b), rows, D, out.ctypes.data_as(C.POINTER(C.c_uint16))))
+        return out
+
+    def op_seaco_merge(self, dha, dha_ids, V, nobias, copy_logits, logits, ids):
+        """launch_seaco_merge (pf_op_seaco_merge): dha [rows, ld_dha], logits [rows, ld_logits] (both wider than V), dha_ids / ids
+        [rows] int64; returns (logits [rows + 4, ld_logits], ids [rows + 4] uint64: the guards hold the canary twice)."""
+        dha, logits = _f32(dha), _f32(logits)
+        rows = dha.shape[0]
+        di, ii = np.ascontiguousarray(dha_ids, dtype=np.int64), np.ascontiguousarray(ids, dtype=np.int64)
+        assert logits.shape[0] == rows and di.shape == (rows,) and ii.shape == (rows,)
+        G = self.OP_GUARD_ROWS
+        lo, io = np.zeros((rows + 2 * G, logits.shape[1]), np.float32), np.zeros(rows + 2 * G, np.int64)
+        p64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
+        N.check(self._lib.pf_op_seaco_merge(self._h, _fp(dha), dha.shape[1], p64(di), rows, V, nobias, 1 if copy_logits else 0, _fp(logits),
+                                            logits.shape[1], p64(ii), _fp(lo), p64(io)))
+        return lo, io.view(np.uint64)
+
+    def short_input_max_rows(self) -> int:
+        """rows up to which the encoder takes its short-input kernels (pf_op_short_input_max_rows)."""
+        v = C.c_int32(0)
+        N.check(self._lib.pf_op_short_input_max_rows(self._h, C.byref(v)))
+        return int(v.value)
+
     def op_dec_mid(self, a, w1, b1, ln_hidden, w2, n2, taps, token_num, x, n3, wq, bq, splits=0, form=0):
         """The middle of a decoder layer (pf_op_dec_mid): form 0 = the split block without its finishing pass + the fused
         middle kernel (k_decmid.hip), 1 = finishing pass with norm2 | fused FSMN + norm3 | q GEMM, 2 = the same with the FSMN

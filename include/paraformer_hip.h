@@ -1043,6 +1043,45 @@ int pf_op_dec_mid(pf_engine* e, const pf_dec_mid_desc* d, float* x_out, float* q
    rows of tn at l >= token_num[b] are replaced by a large finite pattern on the device: they must not reach any result. */
 int pf_op_fsmn_dec_ln(pf_engine* e, const float* tn, const float* taps, const int32_t* token_num, int32_t B, int32_t L, int32_t k,
                       const float* x, const float* gamma, const float* beta, float* x_out, float* xn16_out);
+/* The row kernels of k_norm.hip and of the non-CIF half of k_misc.hip, each launcher alone on caller data (tests/rows_ref.py).
+   Every result buffer below is GUARDED: a result of R rows with row stride ld comes back as (R + 2 PF_OP_GUARD_ROWS) rows of ld
+   cells, the result in rows [PF_OP_GUARD_ROWS, PF_OP_GUARD_ROWS + R).  Before the launch every cell holds the canary
+   (PF_OP_CANARY32 in 32-bit cells, twice in 64-bit cells, PF_OP_CANARY16 in f16 cells); the buffer is returned whole and nothing
+   is checked on the way: what was written outside the result is the caller's to judge.  f16 data travels as bit patterns. */
+#define PF_OP_GUARD_ROWS 2
+#define PF_OP_CANARY32 0x7FC5A5A5u
+#define PF_OP_CANARY16 0x7E5Au
+/* launch_layernorm: x [rows,D] (D % 4 == 0, D <= 2048; two rows of a large finite pattern lie behind it on the device) ->
+   out16 guarded [rows, ld16] f16 and / or out32 guarded [rows, ld32] fp32 (either may be NULL; ld % 4 == 0, ld >= D).
+   posenc_T > 0: launch_posenc_ln_tab instead, x = [rows / posenc_T, posenc_T, D] with D the model's feature width, scaled by
+   sqrt(d_model) and position-encoded from the engine's own table (built as the encoder builds it); f16 result only. */
+int pf_op_layernorm_ex(pf_engine* e, const float* x, const float* gamma, const float* beta, int64_t rows, int32_t D, int32_t ld16,
+                       int32_t ld32, int32_t posenc_T, uint16_t* out16, float* out32);
+/* launch_layernorm_f16: x [rows,D] f16 (D % 8 == 0, D <= 2048) -> out guarded [rows, D] f16; in_place != 0: x is placed in the
+   result buffer itself and normalised there, as the decoder does with its FFN hidden. */
+int pf_op_layernorm_f16(pf_engine* e, const uint16_t* x, const float* gamma, const float* beta, int64_t rows, int32_t D, int32_t in_place,
+                        uint16_t* out);
+/* launch_fsmn_dec_stream: the decoder FSMN of the streaming graph over xc = [cache_in | tn * m], m = (l < len[b]):
+     x[b,l,:] += sum_j taps[j] xc[l + j] + tn[l]   for l < len[b];   cache_out = the last k - 1 columns of xc.
+   tn, x [B,L,D]; taps [k,D]; cache_in [B,D,k-1]; len [B] (a value above L counts as L).  x_out guarded [B L, D], cache_out
+   guarded [B D, k-1].  The rows of tn at l >= len[b] are replaced by a large finite pattern on the device. */
+int pf_op_fsmn_dec_stream(pf_engine* e, const float* tn, const float* taps, const int32_t* len, const float* cache_in, int32_t B, int32_t L,
+                          int32_t D, int32_t k, const float* x, float* x_out, float* cache_out);
+/* launch_embed_gather: out32 guarded [rows, D] = table[clamp(ids[r], 0, vocab - 1)], out16 (may be NULL) its f16 rounding.  On the
+   device the table lies between two rows of a large finite pattern. */
+int pf_op_embed_gather(pf_engine* e, const float* table, const int32_t* ids, int32_t rows, int32_t D, int32_t vocab, float* out32,
+                       uint16_t* out16);
+/* launch_add_to_f16: out16 guarded [rows, D] = f16(a + b), the sum rounded to fp32 first. */
+int pf_op_add_to_f16(pf_engine* e, const float* a, const float* b, int64_t rows, int32_t D, uint16_t* out16);
+/* launch_seaco_merge: row r is REPLACED iff the first-index arg-max of dha[r, :V] is not nobias, or dha[r, nobias] is NaN, or nobias
+   lies outside [0, V): then ids[r] = dha_ids[r] and, with copy_logits, logits[r, :V] = dha[r, :V].  dha [rows, ld_dha] goes up with
+   its pad columns as given; logits_in [rows, ld_logits] and ids_in [rows] are what the buffers hold before the launch;
+   logits_out guarded [rows, ld_logits], ids_out guarded [rows] (int64). */
+int pf_op_seaco_merge(pf_engine* e, const float* dha, int32_t ld_dha, const int64_t* dha_ids, int64_t rows, int32_t V, int32_t nobias,
+                      int32_t copy_logits, const float* logits_in, int32_t ld_logits, const int64_t* ids_in, float* logits_out,
+                      int64_t* ids_out);
+/* *rows = the row count up to which this engine's encoder takes its short-input kernels (k_gemm_small.hip); 0: never. */
+int pf_op_short_input_max_rows(pf_engine* e, int32_t* rows);
 /* The same launch with the attention out-projection in front of the block, as the pipeline runs two thirds of an encoder
    layer since round 5: x_mid = resid + ctx wo^T + bo + FSMN(v) (11 taps, utterances = runs of T rows);
    x_out = x_mid + W2 relu(W1 LayerNorm(x_mid; ln2) + b1) + b2; n16_out = f16 LayerNorm(x_out; ln_gamma, ln_beta).
