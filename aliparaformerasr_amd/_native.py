@@ -59,6 +59,13 @@ class PfVadConfig(C.Structure):
                [("reserved", C.c_int32 * 4)]
 
 
+class PfSpkConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("win", C.c_int32), ("shift", C.c_int32), ("min_frames", C.c_int32), ("threshold", C.c_float),
+                ("num_speakers", C.c_int32), ("min_cluster", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
+PF_SPK_MAX_FRAMES = 512
+PF_SPK_MAX_WINDOWS = 8192
 PF_VAD_MAX_SEGMENTS = 65536
 PF_VAD_MAX_FRAMES = 1 << 22
 
@@ -198,6 +205,18 @@ SIGNATURES = {
     "pf_punc_model_from_memory": (C.c_int, [_vp, C.c_int64, _P(_vp)]),
     "pf_punc_model_info": (C.c_int, [_vp, _i32, _i64]),
     "pf_punc_model_free": (None, [_vp]),
+    "pf_spk_model_load": (C.c_int, [C.c_char_p, _P(_vp)]),
+    "pf_spk_model_from_memory": (C.c_int, [_vp, C.c_int64, _P(_vp)]),
+    "pf_spk_model_info": (C.c_int, [_vp, _i32, _i64]),
+    "pf_spk_model_free": (None, [_vp]),
+    "pf_spk_default": (C.c_int, [_P(PfSpkConfig)]),
+    "pf_engine_set_spk_model": (C.c_int, [_vp, _vp]),
+    "pf_host_spk_windows": (C.c_int, [_i32, C.c_int32, _P(PfSpkConfig), _i32, C.c_int32, _i32, _i32]),
+    "pf_host_spk_cluster": (C.c_int, [_f, C.c_int32, _P(PfSpkConfig), _i32, _i32]),
+    "pf_host_spk_segment_labels": (C.c_int, [_i32, C.c_int32, _i32, _i32, C.c_int32, _i32]),
+    "pf_host_spk_centroids": (C.c_int, [_f, _i32, C.c_int32, C.c_int32, C.c_int32, _f]),
+    "pf_op_spk_embed": (C.c_int, [_vp, _f, _i32, C.c_int32, C.c_int32, _f, _f]),
+    "pf_op_spk_affinity": (C.c_int, [_vp, _f, _i32, C.c_int32, C.c_int32, _f]),
     "pf_host_punc_words": (C.c_int, [_vp, C.c_char_p, _i32, _i32, _i32, C.c_int32, _i32]),
     "pf_host_punc_logits": (C.c_int, [_vp, _i32, C.c_int32, _P(C.c_double)]),
     "pf_host_punc_cut": (C.c_int, [_vp, _i32, C.c_int32, C.c_int32, _i32]),
@@ -278,6 +297,12 @@ SIGNATURES = {
     "pf_recognizer_set_vad": (C.c_int, [_vp, _P(PfVadConfig), C.c_int32, C.c_int64, C.c_char_p]),
     "pf_recognizer_set_vad_model": (C.c_int, [_vp, C.c_char_p]),
     "pf_recognizer_set_punc_model": (C.c_int, [_vp, C.c_char_p]),
+    "pf_recognizer_set_spk_model": (C.c_int, [_vp, C.c_char_p, _P(PfSpkConfig)]),
+    "pf_stream_num_speakers": (C.c_int, [_vp, _i32]),
+    "pf_stream_segment_speaker": (C.c_int, [_vp, C.c_int32, _i32]),
+    "pf_stream_speaker_centroid": (C.c_int, [_vp, C.c_int32, _f, C.c_int32, _i32]),
+    "pf_stream_num_spk_windows": (C.c_int, [_vp, _i32]),
+    "pf_stream_spk_window": (C.c_int, [_vp, C.c_int32, _i32, _i32, _i32]),
     "pf_stream_punctuated": (C.c_int, [_vp, _cpp, _P(_i32), _i32]),
     "pf_stream_num_sentences": (C.c_int, [_vp, _i32]),
     "pf_stream_sentence": (C.c_int, [_vp, C.c_int32, _i32, _i32, _i32, _i32, _i32, _cpp]),

@@ -17,6 +17,7 @@ mismatch with a real file fails loudly instead of producing a silently wrong mod
         (ONNX graph walk, see onnx_to_state_dict; an int8 file's stored bytes are carried beside their float image)
     python -m aliparaformerasr_amd.convert vad.onnx|vad.pt out.pfw --kind fsmnvad --mvn vad.mvn [--sil 0,...] [--lfr-m 5]
     python -m aliparaformerasr_amd.convert punc.pt|punc.onnx out.pfw --kind cttransformer --tokens tokens.json [--heads 8]
+    python -m aliparaformerasr_amd.convert campplus.bin|.pt out.pfw --kind campplus [--seg-len 100] [--dilations 1,2,2]
         (FunASR's FSMN-VAD, the model score of the voice-activity segmentation: vad_state_dict_to_pfw / vad_onnx_to_state_dict.
          NO REAL FSMN-VAD FILE HAS BEEN THROUGH THIS ROUTE: the names are restated from the public FunASR sources and
          exercised on tests/fsmn_vad_like.py)
@@ -533,6 +534,102 @@ def read_punc_tokens(path):
     return [ln for ln in text.split("\n") if ln != ""]
 
 
+def spk_state_dict_to_pfw(sd: dict, seg_len: int = 100, dilations=(1, 2, 2), eps: float = 1e-5):
+    """3D-Speaker CAMPPlus state dict -> (cfg, PFW weights) of kind "campplus" (weights.spk_tensor_shapes).  3D-Speaker's names
+    as remembered: head.conv1 / head.bn1, head.layerL.B.{conv1, bn1, conv2, bn2, shortcut.0 (conv), shortcut.1 (bn)}, head.conv2 /
+    head.bn2; xvector.tdnn.{linear, nonlinear.batchnorm}; xvector.blockK.tdnndN.{nonlinear1.batchnorm, linear1, nonlinear2.batchnorm,
+    cam_layer.linear_local, cam_layer.linear1, cam_layer.linear2}; xvector.transitK.{nonlinear.batchnorm, linear};
+    xvector.out_nonlinear.batchnorm; xvector.dense.{linear, nonlinear.batchnorm (no affine)}.  Every BatchNorm is folded with
+    `eps` (a dict name -> eps overrides it per BatchNorm): into the convolution or Linear in front of it where nothing stands
+    between, else it stays as scale / shift.  seg_len and the dilations are not in a state dict.  Missing or misshapen tensors
+    are refused.  No real file has been through this function."""
+    sd = {k: np.asarray(v, np.float64) for k, v in sd.items()}
+
+    def get(name):
+        if name not in sd:
+            raise ValueError("campplus: the checkpoint lacks " + name)
+        return sd[name]
+
+    def bn(prefix, affine=True):
+        e = eps.get(prefix, 1e-5) if isinstance(eps, dict) else eps
+        var, mean = get(prefix + ".running_var"), get(prefix + ".running_mean")
+        scale = 1.0 / np.sqrt(var + e)
+        if affine:
+            scale = scale * get(prefix + ".weight")
+        shift = (get(prefix + ".bias") if affine else 0.0) - mean * scale
+        return scale, shift
+
+    def fold(conv, norm, out, w, affine=True, squeeze=False):
+        k = get(conv + ".weight")
+        if squeeze:
+            if k.ndim != 3 or k.shape[2] != 1:
+                raise ValueError("campplus: %s.weight has shape %s, expected [out, in, 1]" % (conv, list(k.shape)))
+            k = k[:, :, 0]
+        scale, shift = bn(norm, affine)
+        if scale.shape != (k.shape[0],):
+            raise ValueError("campplus: %s has %d channels, %s.weight %d rows" % (norm, scale.shape[0], conv, k.shape[0]))
+        w[out + ".weight"] = k * scale.reshape((-1,) + (1,) * (k.ndim - 1))
+        w[out + ".bias"] = shift + (get(conv + ".bias") * scale if conv + ".bias" in sd else 0.0)
+
+    import re
+    c1 = get("head.conv1.weight")
+    tw = get("xvector.tdnn.linear.weight")
+    if c1.ndim != 4 or tw.ndim != 3 or tw.shape[1] % c1.shape[0] != 0:
+        raise ValueError("campplus: head.conv1.weight / xvector.tdnn.linear.weight have shapes %s / %s" % (list(c1.shape), list(tw.shape)))
+    blocks = [len({int(m.group(1)) for m in (re.match(r"xvector\.block%d\.tdnnd(\d+)\." % b, k) for k in sd) if m}) for b in (1, 2, 3)]
+    if min(blocks) < 1 or any(re.match(r"xvector\.block4\.", k) for k in sd):
+        raise ValueError("campplus: the checkpoint does not have exactly three dense blocks")
+    l1 = get("xvector.block1.tdnnd1.cam_layer.linear_local.weight")
+    cfg = W.campplus_config(n_mels=8 * (tw.shape[1] // c1.shape[0]), m_channels=c1.shape[0], init_channels=tw.shape[0], growth=l1.shape[0],
+                            bn_channels=l1.shape[1], blocks=blocks, dilations=[int(d) for d in dilations], seg_len=int(seg_len),
+                            embedding=get("xvector.dense.linear.weight").shape[0])
+    w = {}
+    fold("head.conv1", "head.bn1", "head.conv1", w)
+    for layer in (1, 2):
+        for blk in (0, 1):
+            p = "head.layer%d.%d." % (layer, blk)
+            fold(p + "conv1", p + "bn1", p + "conv1", w)
+            fold(p + "conv2", p + "bn2", p + "conv2", w)
+            if blk == 0:
+                fold(p + "shortcut.0", p + "shortcut.1", p + "shortcut", w)
+    fold("head.conv2", "head.bn2", "head.conv2", w)
+    fold("xvector.tdnn.linear", "xvector.tdnn.nonlinear.batchnorm", "tdnn", w)
+    for b in (1, 2, 3):
+        for l in range(blocks[b - 1]):
+            s, o = "xvector.block%d.tdnnd%d." % (b, l + 1), "block%d.%d." % (b, l)
+            w[o + "bn1.scale"], w[o + "bn1.shift"] = bn(s + "nonlinear1.batchnorm")
+            fold(s + "linear1", s + "nonlinear2.batchnorm", o + "linear1", w, squeeze=True)
+            w[o + "local.weight"] = get(s + "cam_layer.linear_local.weight")
+            for src, dst in (("linear1", "cam1"), ("linear2", "cam2")):
+                k = get(s + "cam_layer." + src + ".weight")
+                w[o + dst + ".weight"] = k[:, :, 0] if k.ndim == 3 and k.shape[2] == 1 else k
+                w[o + dst + ".bias"] = get(s + "cam_layer." + src + ".bias")
+        s, o = "xvector.transit%d." % b, "transit%d." % b
+        w[o + "bn.scale"], w[o + "bn.shift"] = bn(s + "nonlinear.batchnorm")
+        k = get(s + "linear.weight")
+        w[o + "weight"] = k[:, :, 0] if k.ndim == 3 and k.shape[2] == 1 else k
+    w["out_bn.scale"], w["out_bn.shift"] = bn("xvector.out_nonlinear.batchnorm")
+    fold("xvector.dense.linear", "xvector.dense.nonlinear.batchnorm", "dense", w, affine=False, squeeze=True)
+    shapes = W.spk_tensor_shapes(cfg)
+    for name, shape in shapes.items():
+        if tuple(np.shape(w[name])) != tuple(shape):
+            raise ValueError("campplus: %s has shape %s, expected %s" % (name, list(np.shape(w[name])), list(shape)))
+        if not np.isfinite(w[name]).all():
+            raise ValueError("campplus: %s holds a value that is not finite" % name)
+    return cfg, {name: np.ascontiguousarray(w[name], dtype=np.float32) for name in shapes}
+
+
+def spk_to_pfw(model_path, seg_len=100, dilations=(1, 2, 2)):
+    """campplus.bin | .pt (a state dict; an ONNX route does not exist) -> (cfg, PFW weights) of kind "campplus"."""
+    if str(model_path).endswith(".onnx"):
+        raise ValueError("campplus: the converter reads a state dict (.bin / .pt), not an ONNX export")
+    import torch
+    sd = torch.load(model_path, map_location="cpu")
+    sd = sd.get("state_dict", sd.get("model", sd)) if isinstance(sd, dict) else sd
+    sd = {k: v.double().numpy() for k, v in sd.items() if hasattr(v, "numpy")}
+    return spk_state_dict_to_pfw(sd, seg_len, dilations)
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     if len(argv) < 2:
@@ -549,6 +646,13 @@ def main(argv=None):
         lfr_m = int(argv[argv.index("--lfr-m") + 1]) if "--lfr-m" in argv else 5
         lstride = int(argv[argv.index("--lstride") + 1]) if "--lstride" in argv else 1
         cfg, wts = vad_to_pfw(argv[0], argv[argv.index("--mvn") + 1], sil, lfr_m, lstride)
+        W.save_pfw(argv[1], cfg, wts)
+        print("wrote %s (%s, %d tensors)" % (argv[1], cfg["kind"], len(wts)))
+        return 0
+    if kind == "campplus":
+        seg_len = int(argv[argv.index("--seg-len") + 1]) if "--seg-len" in argv else 100
+        dil = tuple(int(x) for x in argv[argv.index("--dilations") + 1].split(",")) if "--dilations" in argv else (1, 2, 2)
+        cfg, wts = spk_to_pfw(argv[0], seg_len, dil)
         W.save_pfw(argv[1], cfg, wts)
         print("wrote %s (%s, %d tensors)" % (argv[1], cfg["kind"], len(wts)))
         return 0

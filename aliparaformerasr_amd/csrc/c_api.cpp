@@ -1007,6 +1007,122 @@ int pf_op_vad_model_levels(pf_engine* h, const float* rows, const int32_t* T, in
   return op_vad_model(h, rows, T, B, n_mels, nullptr, out);
 }
 
+// ---- speaker labels ----
+int pf_spk_model_load(const char* path, pf_spk_model** m) {
+  return new_model_handle(m, path, "path", [&] { return spk_model_load(path); });
+}
+int pf_spk_model_from_memory(const void* data, int64_t nbytes, pf_spk_model** m) {
+  return new_model_handle(m, data, "data", [&] { return spk_model_from_memory(data, nbytes); });
+}
+int pf_spk_model_info(const pf_spk_model* m, int32_t* dims, int64_t* image_bytes) {
+  PF_TRY
+  NEED(m);
+  const SpkModel& v = *m->p;
+  if (dims) {
+    const int32_t d[16] = {v.n_mels, v.m, v.init, v.growth, v.bn, v.blocks[0], v.blocks[1], v.blocks[2], v.dilations[0], v.dilations[1],
+                           v.dilations[2], v.seg_len, v.embedding, v.c_out, Engine::kSpkLaunches, 0};
+    std::memcpy(dims, d, sizeof(d));
+  }
+  if (image_bytes) *image_bytes = (int64_t)v.image.size();
+  return PF_OK;
+  PF_CATCH
+}
+void pf_spk_model_free(pf_spk_model* m) { delete m; }
+int pf_spk_default(pf_spk_config* cfg) {
+  PF_TRY
+  NEED(cfg);
+  *cfg = spk_default();
+  return PF_OK;
+  PF_CATCH
+}
+static pf_spk_config spk_cfg_or_default(const pf_spk_config* cfg) {
+  const pf_spk_config c = cfg ? *cfg : spk_default();
+  spk_check_config(c);
+  return c;
+}
+int pf_engine_set_spk_model(pf_engine* h, const pf_spk_model* m) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->set_spk_model(m ? m->p : nullptr);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_host_spk_windows(const int32_t* seg, int32_t n_seg, const pf_spk_config* cfg, int32_t* win, int32_t cap, int32_t* n,
+                        int32_t* shift_used) {
+  PF_TRY
+  NEED(n);
+  PF_CHECK(n_seg >= 0 && cap >= 0, PF_ERR_INVALID_ARG, "spk_windows: negative count");
+  if (n_seg > 0) NEED(seg);
+  for (int32_t i = 0; i < n_seg; ++i)
+    PF_CHECK(seg[2 * i] >= 0 && seg[2 * i + 1] >= seg[2 * i], PF_ERR_INVALID_ARG, "spk_windows: a segment that ends before it begins");
+  const pf_spk_config c = spk_cfg_or_default(cfg);
+  std::vector<int32_t> w;
+  host_spk_windows(seg, n_seg, c, w, shift_used);
+  *n = (int32_t)(w.size() / 3);
+  PF_CHECK(cap >= *n, PF_ERR_CAPACITY, "spk_windows: capacity below the number of windows");
+  if (*n > 0) { NEED(win); std::memcpy(win, w.data(), w.size() * 4); }
+  return PF_OK;
+  PF_CATCH
+}
+int pf_host_spk_cluster(const float* S, int32_t N, const pf_spk_config* cfg, int32_t* labels, int32_t* n_speakers) {
+  PF_TRY
+  PF_CHECK(N >= 0 && N <= PF_SPK_MAX_WINDOWS, PF_ERR_INVALID_ARG, "spk_cluster: N outside 0 .. PF_SPK_MAX_WINDOWS");
+  if (N > 0) { NEED(S); NEED(labels); }
+  const pf_spk_config c = spk_cfg_or_default(cfg);
+  host_spk_cluster(S, N, c, labels, n_speakers);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_host_spk_segment_labels(const int32_t* seg, int32_t n_seg, const int32_t* win_seg, const int32_t* win_label, int32_t N,
+                               int32_t* out) {
+  PF_TRY
+  PF_CHECK(n_seg >= 0 && N >= 0, PF_ERR_INVALID_ARG, "spk_segment_labels: negative count");
+  if (n_seg > 0) { NEED(seg); NEED(out); }
+  if (N > 0) { NEED(win_seg); NEED(win_label); }
+  host_spk_segment_labels(seg, n_seg, win_seg, win_label, N, out);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_host_spk_centroids(const float* emb, const int32_t* labels, int32_t N, int32_t E_, int32_t K, float* out) {
+  PF_TRY
+  PF_CHECK(N >= 0 && E_ >= 1 && K >= 0, PF_ERR_INVALID_ARG, "spk_centroids: bad shape");
+  if (N > 0) { NEED(emb); NEED(labels); }
+  if (K > 0) NEED(out);
+  host_spk_centroids(emb, labels, N, E_, K, out);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_op_spk_embed(pf_engine* h, const float* rows, const int32_t* T, int32_t B, int32_t n_mels, float* emb, float* frames) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  PF_CHECK(B >= 0 && n_mels >= 1 && n_mels <= 1024, PF_ERR_INVALID_ARG, "spk_embed: bad shape (n_mels 1 .. 1024)");
+  if (B > 0) { NEED(T); NEED(emb); }
+  int64_t total = 0;
+  for (int b = 0; b < B; ++b) total += std::max(T[b], 0);
+  if (total > 0) NEED(rows);
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->op_spk_embed(rows, T, B, n_mels, emb, frames);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_op_spk_affinity(pf_engine* h, const float* emb, const int32_t* n, int32_t S, int32_t E_, float* out) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  PF_CHECK(S >= 0 && E_ >= 1 && E_ <= 4096, PF_ERR_INVALID_ARG, "spk_affinity: bad shape (E 1 .. 4096)");
+  if (S > 0) NEED(n);
+  int64_t rows = 0;
+  for (int s = 0; s < S; ++s) rows += std::max(n[s], 0);
+  if (rows > 0) { NEED(emb); NEED(out); }
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->op_spk_affinity(emb, n, S, E_, out);
+  return PF_OK;
+  PF_CATCH
+}
+
 // ---- punctuation ----
 int pf_punc_model_load(const char* path, pf_punc_model** m) {
   return new_model_handle(m, path, "path", [&] { return punc_model_load(path); });
@@ -2090,6 +2206,62 @@ int pf_recognizer_set_punc_model(pf_recognizer* h, const char* pfw_path) {
   std::shared_ptr<Recognizer> r = R(h);
   PF_CHECK(!r->disposed(), PF_ERR_DISPOSED, "OfflineRecognizer");
   r->SetPuncModel(pfw_path ? pfw_path : "");
+  return PF_OK;
+  PF_CATCH
+}
+int pf_recognizer_set_spk_model(pf_recognizer* h, const char* pfw_path, const pf_spk_config* cfg) {
+  PF_TRY
+  std::shared_ptr<Recognizer> r = R(h);
+  PF_CHECK(!r->disposed(), PF_ERR_DISPOSED, "OfflineRecognizer");
+  r->SetSpkModel(pfw_path ? pfw_path : "", cfg);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_stream_num_speakers(pf_stream* h, int32_t* n) {
+  PF_TRY
+  Stream* s = S(h);
+  NEED(n);
+  *n = (int32_t)s->NumSpeakers;
+  return PF_OK;
+  PF_CATCH
+}
+int pf_stream_segment_speaker(pf_stream* h, int32_t i, int32_t* spk) {
+  PF_TRY
+  Stream* s = S(h);
+  NEED(spk);
+  PF_CHECK(i >= 0 && (size_t)i < s->SegSpeakers.size(), PF_ERR_INVALID_ARG, "segment index out of range (or no speaker model was on)");
+  *spk = s->SegSpeakers[(size_t)i];
+  return PF_OK;
+  PF_CATCH
+}
+int pf_stream_speaker_centroid(pf_stream* h, int32_t spk, float* out, int32_t cap, int32_t* E_) {
+  PF_TRY
+  Stream* s = S(h);
+  if (E_) *E_ = (int32_t)s->SpkE;
+  if (!out && cap == 0) return PF_OK;
+  PF_CHECK(spk >= 0 && spk < s->NumSpeakers, PF_ERR_INVALID_ARG, "speaker index out of range");
+  PF_CHECK(cap >= s->SpkE, PF_ERR_CAPACITY, "capacity below the embedding's width");
+  NEED(out);
+  std::memcpy(out, s->SpkCentroids.data() + (size_t)spk * s->SpkE, (size_t)s->SpkE * 4);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_stream_num_spk_windows(pf_stream* h, int32_t* n) {
+  PF_TRY
+  Stream* s = S(h);
+  NEED(n);
+  *n = (int32_t)s->SpkWindows.size();
+  return PF_OK;
+  PF_CATCH
+}
+int pf_stream_spk_window(pf_stream* h, int32_t i, int32_t* begin_ms, int32_t* end_ms, int32_t* label) {
+  PF_TRY
+  Stream* s = S(h);
+  PF_CHECK(i >= 0 && (size_t)i < s->SpkWindows.size(), PF_ERR_INVALID_ARG, "window index out of range");
+  const Stream::SpkWindow& w = s->SpkWindows[(size_t)i];
+  if (begin_ms) *begin_ms = w.begin_ms;
+  if (end_ms) *end_ms = w.end_ms;
+  if (label) *label = w.label;
   return PF_OK;
   PF_CATCH
 }

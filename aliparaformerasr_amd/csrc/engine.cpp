@@ -122,10 +122,11 @@ void Engine::release() {
   owned_.clear();
   DevBuf* bufs[] = {&ws_f32_, &ws_pcm_, &ws_audio_, &ws_meta_, &ws_fbank_, &ws_speech_, &ws_enc_, &ws_dec_, &ws_kv_, &ws_pe_, &ws_tmp_,
                     &ws_ts_, &ws_seaco_, &ws_seaco_in_, &ws_seaco_hw_, &ws_q_, &ws_qf_, &ws_seaco_q_, &ws_x3a_, &ws_x3t_, &ws_x3h_, &lm_inst_.buf, &lm_op_.buf, &nbs_hot_.buf, &ws_nbs_,
-                    &vadnet_dev_.buf, &ws_vadnet_, &punc_dev_.buf, &ws_punc_};
+                    &vadnet_dev_.buf, &ws_vadnet_, &punc_dev_.buf, &ws_punc_, &spk_dev_.buf, &ws_spk_};
   lm_inst_.src.reset(); lm_op_.src.reset(); lm_.reset(); nbs_lm_.reset();
   vadnet_dev_.src.reset(); vadnet_.reset();
   punc_dev_.src.reset(); punc_.reset();
+  spk_dev_.src.reset(); spk_.reset();
   x3_pair_live_ = false; x3a_src_ = nullptr; x3a_pair_only_ = false;
   x3w_.clear();
   ts_whh_x3_ = nullptr;
@@ -362,6 +363,8 @@ void Engine::load_weights(const pf_engine_config& cfg) {
            "weights: a container of kind \"fsmnvad\" is a voice-activity model (pf_vad_model_load), not a recogniser");
   PF_CHECK(mc_.kind != "cttransformer", PF_ERR_INVALID_ARG,
            "weights: a container of kind \"cttransformer\" is a punctuation model (pf_punc_model_load), not a recogniser");
+  PF_CHECK(mc_.kind != "campplus", PF_ERR_INVALID_ARG,
+           "weights: a container of kind \"campplus\" is a speaker model (pf_spk_model_load), not a recogniser");
   mc_.feat_dim = (int)jc->int_or("feat_dim", mc_.feat_dim, INT32_MIN, INT32_MAX);
   mc_.d_model = (int)jc->int_or("d_model", mc_.d_model, INT32_MIN, INT32_MAX);
   mc_.heads = (int)jc->int_or("heads", mc_.heads, INT32_MIN, INT32_MAX);

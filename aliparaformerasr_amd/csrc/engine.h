@@ -11,6 +11,7 @@
 
 #include "lm.h"
 #include "vadnet.h"
+#include "spk.h"
 #include "punc.h"
 #include "json.h"
 #include "kernels.h"
@@ -285,6 +286,25 @@ class Engine {
   // the forward on caller windows: logits [sum T, n_punc], x0 [sum T, d_model] (layer 0's input), p [sum T] and cut [B] (the
   // cut launch runs when cut is asked for; it needs last [B]); every output may be null
   void op_punc(const int32_t* ids, const int32_t* T, const int32_t* last, int B, float* logits, float* x0, int32_t* p, int32_t* cut);
+  // The CAM++ speaker model (k_spk.hip, spk.h).  nullptr detaches and frees the image and the workspace (nothing of it is
+  // launched or allocated then; attaching the model an engine still has costs no upload).  The engine keeps a reference and
+  // uploads the image once.  PF_ERR_INVALID_ARG unless the model's n_mels is the front-end's.  A forward is profile class
+  // "spk": kSpkLaunches launches whatever the windows.
+  static constexpr int kSpkLaunches = 15;
+  void set_spk_model(const std::shared_ptr<const SpkModel>& m);
+  const std::shared_ptr<const SpkModel>& spk_model() const { return spk_; }
+  // the forward on caller windows: rows = the concatenated rows of B windows of T[b] frames (0 .. PF_SPK_MAX_FRAMES);
+  // emb [B, embedding]; frames [sum ceil(T / 2), c_out] or null
+  void op_spk_embed(const float* rows, const int32_t* T, int B, int n_mels, float* emb, float* frames);
+  // The recogniser's form, behind vad_staged on the SAME staged utterances (their fbank rows are still in ws_fbank_): win [N, 3]
+  // = (staged utterance, first frame, end frame), grouped by utterance in order, n_utt [st_B] windows each.  Embeds the windows,
+  // as many per forward as keep the activations within kSpkScratchBudget bytes whatever the windows' length (about 1000 windows of
+  // 150 frames at the released dimensions, 300 of 512), and computes one cosine block per utterance in one launch:
+  // emb [N, embedding], aff = the concatenated [n, n] blocks.
+  static constexpr size_t kSpkScratchBudget = (size_t)2 << 30;
+  void spk_staged(const int32_t* win, int N, const int32_t* n_utt, float* emb, float* aff);
+  // the cosine blocks of S streams of n[s] embeddings (host arrays in and out; one launch of class "spk"; needs no model)
+  void op_spk_affinity(const float* emb, const int32_t* n, int S, int E, float* out);
   void op_vad_segments(const int32_t* levels, const int32_t* T, int B, int ld, int n_mels, const pf_vad_config* cfg, int32_t* seg,
                        int cap, int32_t* n);
   void op_ctc_collapse(const int64_t* ids, const float* scores, const int32_t* lens, int B, int T, int blank, int64_t* ids_out,
@@ -649,6 +669,15 @@ class Engine {
   std::shared_ptr<const PuncModel> punc_;
   ModelDev<PuncModel> punc_dev_;
   DevBuf ws_punc_;
+  // the speaker model (set_spk_model): as above; ws_spk_ holds the window table, the rows, the head's three activation buffers,
+  // the TDNN's frames, the four X buffers, the embeddings and the frames asked for
+  std::shared_ptr<const SpkModel> spk_;
+  ModelDev<SpkModel> spk_dev_;
+  DevBuf ws_spk_;
+  // the 15 launches over rows that are on the device: T / toff / tpoff [B] / [B + 1] / [B + 1] device arrays, scratch from ws
+  void run_spk(const float* rows_dev, const int32_t* T_dev, const int64_t* toff_dev, const int64_t* tpoff_dev, const int64_t* xoff_dev, int B,
+               int Tmax, int64_t total, int64_t totalp, char* scratch, float* emb_dev, float* frames_dev);
+  static size_t spk_scratch_bytes(const SpkModel& m, int64_t total, int64_t totalp);
   void run_punc(const int32_t* ids, const int64_t* off, const int32_t* last, int B, float* logits, float* x0, int32_t* p, int32_t* cut);
   void run_vadnet(const float* rows_dev, const int64_t* off_dev, int B, int64_t total, int n_mels, float* logits_dev, int32_t* levels_dev);
   float lm_alpha_ = 0.f, lm_beta_ = 0.f;

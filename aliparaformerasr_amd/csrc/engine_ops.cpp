@@ -389,6 +389,218 @@ void Engine::op_vad_model(const float* rows, const int32_t* T, int B, int n_mels
   PF_HIP(hipStreamSynchronize(stream_));                          // (`off` is read by its copy until then)
 }
 
+// ---- the CAM++ speaker model (k_spk.hip; the launch plan is at the head of that file)
+void Engine::set_spk_model(const std::shared_ptr<const SpkModel>& m) {
+  if (m) PF_CHECK(fc_.n_mels == m->n_mels, PF_ERR_INVALID_ARG, "set_spk_model: the model's n_mels is not the front-end's");
+  attach_model(spk_, spk_dev_, ws_spk_, m);
+}
+
+namespace {
+struct SpkScratch { size_t act[3], frames, X[4], total; };
+SpkScratch spk_scratch(const SpkModel& m, int64_t total, int64_t totalp) {
+  SpkScratch s{};
+  size_t off = 0;
+  auto take = [&](size_t bytes) { const size_t at = off; off += (size_t)round_up((int64_t)bytes + 16, 256); return at; };   // (+ 16: a vector read may pass the last row's end)
+  for (int i = 0; i < 3; ++i) s.act[i] = take((size_t)total * (i == 0 ? m.n_mels : m.n_mels / 2) * m.m * sizeof(half_t));
+  s.frames = take((size_t)total * m.frame_ld * sizeof(half_t));
+  for (int i = 0; i < 4; ++i) s.X[i] = take((size_t)totalp * m.ldx[i] * sizeof(half_t));
+  s.total = off;
+  return s;
+}
+}  // namespace
+
+size_t Engine::spk_scratch_bytes(const SpkModel& m, int64_t total, int64_t totalp) { return spk_scratch(m, total, totalp).total; }
+
+void Engine::run_spk(const float* rows_dev, const int32_t* T_dev, const int64_t* toff_dev, const int64_t* tpoff_dev, const int64_t* xoff_dev, int B,
+                     int Tmax, int64_t total, int64_t totalp, char* scratch, float* emb_dev, float* frames_dev) {
+  const SpkModel& m = *spk_;
+  if (B <= 0) return;
+  const SpkScratch sc = spk_scratch(m, total, totalp);
+  half_t* act[3] = {(half_t*)(scratch + sc.act[0]), (half_t*)(scratch + sc.act[1]), (half_t*)(scratch + sc.act[2])};
+  half_t* frames = (half_t*)(scratch + sc.frames);
+  half_t* X[4] = {(half_t*)(scratch + sc.X[0]), (half_t*)(scratch + sc.X[1]), (half_t*)(scratch + sc.X[2]), (half_t*)(scratch + sc.X[3])};
+  const SpkWin w{(const char*)spk_dev_.buf.p, T_dev, toff_dev, tpoff_dev, xoff_dev, B, Tmax};
+  // every class "spk" launch is timed even where the call has no frame: the count is the model's, not the call's
+  const double share = m.flops_per_frame * (double)total / kSpkLaunches;
+  int F = m.n_mels;
+  for (int i = 0; i < 10; ++i) {
+    SpkConvLaunch a{};
+    a.w = w; a.d = m.conv[i]; a.m = m.m; a.n_mels = m.n_mels; a.frame_ld = m.frame_ld;
+    a.Fin = F; a.Fout = F / a.d.sf; F = a.Fout;
+    a.x = rows_dev;
+    a.in = a.d.in >= 0 ? act[a.d.in] : nullptr;
+    a.aux = a.d.aux >= 0 ? act[a.d.aux] : nullptr;
+    a.out = a.d.to_frames ? frames : act[a.d.out];
+    prof_begin("spk", share);
+    launch_spk_conv(stream_, a);
+    prof_end("spk");
+  }
+  {
+    SpkTdnnLaunch a{};
+    a.w = w; a.g = m.tdnn; a.frame_w = m.frame_w; a.frame_ld = m.frame_ld; a.N = m.init; a.frames = frames; a.X = X[0]; a.ldx = m.ldx[0];
+    prof_begin("spk", share);
+    launch_spk_tdnn(stream_, a);
+    prof_end("spk");
+  }
+  for (int b = 0; b < 3; ++b) {
+    SpkBlockLaunch a{};
+    a.w = w; a.layers_off = m.layers_off[b]; a.n_layers = m.blocks[b]; a.growth = m.growth; a.bn = m.bn; a.dilation = m.dilations[b];
+    a.seg_len = m.seg_len; a.X = X[b]; a.ldx = m.ldx[b]; a.C1 = m.C1[b]; a.tr_scale_off = m.tr_scale_off[b]; a.tr_shift_off = m.tr_shift_off[b];
+    a.transit = m.transit[b]; a.Xn = X[b + 1]; a.ldxn = m.ldx[b + 1];
+    prof_begin("spk", share);
+    launch_spk_block(stream_, a);
+    prof_end("spk");
+  }
+  {
+    SpkPoolLaunch a{};
+    a.w = w; a.X = X[3]; a.ldx = m.ldx[3]; a.C = m.c_out; a.scale_off = m.out_scale_off; a.shift_off = m.out_shift_off; a.dense = m.dense;
+    a.E = m.embedding; a.emb = emb_dev; a.frames = frames_dev;
+    prof_begin("spk", share);
+    launch_spk_pool(stream_, a);
+    prof_end("spk");
+  }
+}
+
+void Engine::op_spk_embed(const float* rows, const int32_t* T, int B, int n_mels, float* emb, float* frames) {
+  PF_CHECK(spk_ != nullptr, PF_ERR_INVALID_ARG, "op_spk_embed: no model is attached (pf_engine_set_spk_model)");
+  PF_CHECK(n_mels == spk_->n_mels, PF_ERR_INVALID_ARG, "op_spk_embed: n_mels is not the model's");
+  if (B <= 0) return;
+  PF_CHECK(B <= 65535, PF_ERR_CAPACITY, "op_spk_embed: more than 65535 windows in one call");
+  const SpkModel& m = *spk_;
+  std::vector<int64_t> off(2 * ((size_t)B + 1), 0);                 // toff | tpoff
+  int Tmax = 0;
+  for (int b = 0; b < B; ++b) {
+    PF_CHECK(T[b] >= 0 && T[b] <= PF_SPK_MAX_FRAMES, PF_ERR_INVALID_ARG, "op_spk_embed: a window of fewer than 0 or more than PF_SPK_MAX_FRAMES frames");
+    off[(size_t)b + 1] = off[(size_t)b] + T[b];
+    off[(size_t)B + 1 + b + 1] = off[(size_t)B + 1 + b] + (T[b] + 1) / 2;
+    Tmax = std::max(Tmax, (int)T[b]);
+  }
+  const int64_t total = off[(size_t)B], totalp = off[2 * (size_t)B + 1];
+  PF_HIP(hipSetDevice(device_));
+  const int E = m.embedding, C = m.c_out;
+  size_t at = 0;
+  auto take = [&](size_t bytes) { const size_t a0 = at; at += (size_t)round_up((int64_t)bytes + 16, 256); return a0; };
+  const size_t o_off = take(off.size() * 8), o_T = take((size_t)B * 4), o_x = take((size_t)total * n_mels * 4), o_emb = take((size_t)B * E * 4),
+               o_fr = take(frames ? (size_t)totalp * C * 4 : 0), o_scr = take(spk_scratch_bytes(m, total, totalp));
+  ensure(ws_spk_, at);
+  char* ws = (char*)ws_spk_.p;
+  PF_HIP(hipMemcpyAsync(ws + o_off, off.data(), off.size() * 8, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipMemcpyAsync(ws + o_T, T, (size_t)B * 4, hipMemcpyHostToDevice, stream_));
+  if (total > 0) PF_HIP(hipMemcpyAsync(ws + o_x, rows, (size_t)total * n_mels * 4, hipMemcpyHostToDevice, stream_));
+  run_spk((const float*)(ws + o_x), (const int32_t*)(ws + o_T), (const int64_t*)(ws + o_off), (const int64_t*)(ws + o_off) + B + 1,
+          (const int64_t*)(ws + o_off), B, Tmax, total, totalp, ws + o_scr, (float*)(ws + o_emb), frames ? (float*)(ws + o_fr) : nullptr);
+  PF_HIP(hipMemcpyAsync(emb, ws + o_emb, (size_t)B * E * 4, hipMemcpyDeviceToHost, stream_));
+  if (frames && totalp > 0) PF_HIP(hipMemcpyAsync(frames, ws + o_fr, (size_t)totalp * C * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipStreamSynchronize(stream_));                          // (`off` and T are read by their copies until then)
+}
+
+void Engine::spk_staged(const int32_t* win, int N, const int32_t* n_utt, float* emb, float* aff) {
+  PF_CHECK(spk_ != nullptr, PF_ERR_INVALID_ARG, "spk_staged: no model is attached");
+  const SpkModel& m = *spk_;
+  const int B = st_B_, E = m.embedding;
+  if (N <= 0 || B <= 0) return;
+  std::vector<int64_t> first((size_t)B + 1, 0);                     // the first staged frame of every utterance
+  for (int b = 0; b < B; ++b) first[(size_t)b + 1] = first[(size_t)b] + st_t80_[b];
+  int64_t counted = 0;
+  for (int b = 0; b < B; ++b) {
+    PF_CHECK(n_utt[b] >= 0 && n_utt[b] <= PF_SPK_MAX_WINDOWS, PF_ERR_INVALID_ARG, "spk_staged: a stream of more than PF_SPK_MAX_WINDOWS windows");
+    counted += n_utt[b];
+  }
+  PF_CHECK(counted == N, PF_ERR_INVALID_ARG, "spk_staged: the windows per utterance do not add up");
+  PF_HIP(hipSetDevice(device_));
+  // the per-chunk tables and the largest chunk's scratch; a chunk is sized for the call's longest window
+  int longest = 1;
+  for (int i = 0; i < N; ++i) longest = std::max(longest, (int)std::min<int64_t>(std::max(win[3 * (size_t)i + 2] - win[3 * (size_t)i + 1], 0), PF_SPK_MAX_FRAMES));
+  const size_t per_window = spk_scratch_bytes(m, longest, (longest + 1) / 2);
+  const int chunk = (int)std::min<size_t>((size_t)std::min(N, 65535), std::max<size_t>(kSpkScratchBudget / per_window, 1));
+  std::vector<int64_t> off;                                         // per chunk: toff [n + 1] | tpoff [n + 1] | xoff [n + 1]
+  std::vector<int32_t> T((size_t)N);
+  size_t scratch = 0;
+  std::vector<int> tmax;
+  for (int c0 = 0; c0 < N; c0 += chunk) {
+    const int n = std::min(chunk, N - c0);
+    const size_t at = off.size();
+    off.resize(at + 3 * ((size_t)n + 1), 0);
+    int64_t* toff = off.data() + at; int64_t* tpoff = toff + n + 1; int64_t* xoff = tpoff + n + 1;
+    int mx = 0;
+    for (int i = 0; i < n; ++i) {
+      const int32_t* w = win + 3 * (size_t)(c0 + i);
+      PF_CHECK(w[0] >= 0 && w[0] < B && w[1] >= 0 && w[2] >= w[1] && w[2] <= st_t80_[w[0]] && w[2] - w[1] <= PF_SPK_MAX_FRAMES, PF_ERR_INVALID_ARG,
+               "spk_staged: a window outside its utterance or above PF_SPK_MAX_FRAMES frames");
+      const int t = w[2] - w[1];
+      T[(size_t)(c0 + i)] = t;
+      toff[i + 1] = toff[i] + t; tpoff[i + 1] = tpoff[i] + (t + 1) / 2; xoff[i] = first[(size_t)w[0]] + w[1];
+      mx = std::max(mx, t);
+    }
+    tmax.push_back(mx);
+    scratch = std::max(scratch, spk_scratch_bytes(m, toff[n], tpoff[n]));
+  }
+  std::vector<int64_t> aoff(2 * ((size_t)B + 1), 0);                // eoff | ooff
+  int nmax = 0;
+  for (int b = 0; b < B; ++b) {
+    aoff[(size_t)b + 1] = aoff[(size_t)b] + n_utt[b];
+    aoff[(size_t)B + 1 + b + 1] = aoff[(size_t)B + 1 + b] + (int64_t)n_utt[b] * n_utt[b];
+    nmax = std::max(nmax, (int)n_utt[b]);
+  }
+  const int64_t cells = aoff[2 * (size_t)B + 1];
+  size_t at = 0;
+  auto take = [&](size_t bytes) { const size_t a0 = at; at += (size_t)round_up((int64_t)bytes + 16, 256); return a0; };
+  const size_t o_off = take(off.size() * 8), o_T = take((size_t)N * 4), o_aoff = take(aoff.size() * 8), o_emb = take((size_t)N * E * 4),
+               o_aff = take((size_t)cells * 4), o_scr = take(scratch);
+  ensure(ws_spk_, at);
+  char* ws = (char*)ws_spk_.p;
+  PF_HIP(hipMemcpyAsync(ws + o_off, off.data(), off.size() * 8, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipMemcpyAsync(ws + o_T, T.data(), (size_t)N * 4, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipMemcpyAsync(ws + o_aoff, aoff.data(), aoff.size() * 8, hipMemcpyHostToDevice, stream_));
+  size_t tab = 0;
+  for (int c0 = 0, ci = 0; c0 < N; c0 += chunk, ++ci) {
+    const int n = std::min(chunk, N - c0);
+    const int64_t* toff = (const int64_t*)(ws + o_off) + tab;
+    const int64_t* h_toff = off.data() + tab;
+    run_spk((const float*)ws_fbank_.p, (const int32_t*)(ws + o_T) + c0, toff, toff + n + 1, toff + 2 * ((size_t)n + 1), n, tmax[(size_t)ci], h_toff[n],
+            h_toff[2 * (size_t)n + 1], ws + o_scr, (float*)(ws + o_emb) + (size_t)c0 * E, nullptr);
+    tab += 3 * ((size_t)n + 1);
+  }
+  if (cells > 0) {
+    SpkAffinityLaunch a{(const float*)(ws + o_emb), (const int64_t*)(ws + o_aoff), (const int64_t*)(ws + o_aoff) + B + 1, B, E, nmax, (float*)(ws + o_aff)};
+    prof_begin("spk", 6.0 * E * (double)cells);
+    launch_spk_affinity(stream_, a);
+    prof_end("spk");
+    PF_HIP(hipMemcpyAsync(aff, ws + o_aff, (size_t)cells * 4, hipMemcpyDeviceToHost, stream_));
+  }
+  PF_HIP(hipMemcpyAsync(emb, ws + o_emb, (size_t)N * E * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipStreamSynchronize(stream_));                          // (the tables are read by their copies until then)
+}
+
+void Engine::op_spk_affinity(const float* emb, const int32_t* n, int S, int E, float* out) {
+  if (S <= 0) return;
+  std::vector<int64_t> off(2 * ((size_t)S + 1), 0);                 // eoff | ooff
+  int nmax = 0;
+  for (int s = 0; s < S; ++s) {
+    PF_CHECK(n[s] >= 0 && n[s] <= PF_SPK_MAX_WINDOWS, PF_ERR_INVALID_ARG, "op_spk_affinity: a stream of fewer than 0 or more than PF_SPK_MAX_WINDOWS embeddings");
+    off[(size_t)s + 1] = off[(size_t)s] + n[s];
+    off[(size_t)S + 1 + s + 1] = off[(size_t)S + 1 + s] + (int64_t)n[s] * n[s];
+    nmax = std::max(nmax, (int)n[s]);
+  }
+  const int64_t rows = off[(size_t)S], cells = off[2 * (size_t)S + 1];
+  if (cells == 0) return;
+  PF_CHECK(S <= 65535 && E >= 1, PF_ERR_CAPACITY, "op_spk_affinity: more than 65535 streams in one call");
+  PF_HIP(hipSetDevice(device_));
+  size_t at = 0;
+  auto take = [&](size_t bytes) { const size_t a0 = at; at += (size_t)round_up((int64_t)bytes, 256); return a0; };
+  const size_t o_off = take(off.size() * 8), o_e = take((size_t)rows * E * 4), o_s = take((size_t)cells * 4);
+  ensure(ws_tmp_, at);
+  char* ws = (char*)ws_tmp_.p;
+  PF_HIP(hipMemcpyAsync(ws + o_off, off.data(), off.size() * 8, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipMemcpyAsync(ws + o_e, emb, (size_t)rows * E * 4, hipMemcpyHostToDevice, stream_));
+  SpkAffinityLaunch a{(const float*)(ws + o_e), (const int64_t*)(ws + o_off), (const int64_t*)(ws + o_off) + S + 1, S, E, nmax, (float*)(ws + o_s)};
+  prof_begin("spk", 6.0 * E * (double)cells);
+  launch_spk_affinity(stream_, a);
+  prof_end("spk");
+  PF_HIP(hipMemcpyAsync(out, ws + o_s, (size_t)cells * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipStreamSynchronize(stream_));
+}
+
 // ---- the CT-Transformer punctuation model (k_punc.hip; the launch plan is at the head of that file)
 void Engine::set_punc_model(const std::shared_ptr<const PuncModel>& m) { attach_model(punc_, punc_dev_, ws_punc_, m); }
 

@@ -2,6 +2,7 @@
 #pragma once
 #include "common.h"
 #include "tile_image.h"
+#include "spk.h"
 
 namespace pf {
 
@@ -554,5 +555,35 @@ struct PuncCutLaunch {
   int id_none, id_comma, id_period, id_question, id_pause, sentence_end_id, comma_window, hard_window;
 };
 void launch_punc_cut(hipStream_t s, const PuncCutLaunch& a);
+
+// ---------------------------------------------------------------- the CAM++ speaker model (k_spk.hip) ------
+// The definition in numpy is tests/spk_ref.py; the launch plan (15 launches per forward) is at the head of k_spk.hip and
+// Engine::run_spk fills these in.  img: the model's device image (spk.h); every *_off and TileGemm offset is a byte offset into
+// it.  Windows: T [B] rows each (at most PF_SPK_MAX_FRAMES), window w at input rows [toff[w], toff[w + 1]) and at output
+// frames [tpoff[w], tpoff[w + 1]) (ceil(T / 2) each).  A head activation of F frequencies is f16 [(toff[w] F + f T + t) m + c].
+// xoff[w]: the window's first row in the rows conv1 reads (windows may overlap there: the recogniser's windows lie in its staged fbank).
+struct SpkWin { const char* img; const int32_t* T; const int64_t* toff; const int64_t* tpoff; const int64_t* xoff; int B; int Tmax; };
+struct SpkConvLaunch {
+  SpkWin w; SpkConvDesc d; int m, Fin, Fout, n_mels, frame_ld;
+  const float* x;                                                // conv1: the fbank rows [sum T, n_mels]
+  const half_t* in; const half_t* aux; half_t* out;              // aux: the shortcut's input (2 Fout frequencies) or the residual (Fout)
+};
+void launch_spk_conv(hipStream_t s, const SpkConvLaunch& a);
+struct SpkTdnnLaunch { SpkWin w; TileGemm g; int frame_w, frame_ld, N; const half_t* frames; half_t* X; int ldx; };
+void launch_spk_tdnn(hipStream_t s, const SpkTdnnLaunch& a);
+struct SpkBlockLaunch {
+  SpkWin w; int64_t layers_off; int n_layers, growth, bn, dilation, seg_len;
+  half_t* X; int ldx;                                            // the block's concatenated activations f16 [sum T', ldx]
+  int C1; int64_t tr_scale_off, tr_shift_off; TileGemm transit; half_t* Xn; int ldxn;     // the transit behind it -> the next block's X
+};
+void launch_spk_block(hipStream_t s, const SpkBlockLaunch& a);
+struct SpkPoolLaunch {
+  SpkWin w; const half_t* X; int ldx, C; int64_t scale_off, shift_off; TileGemm dense; int E;
+  float* emb; float* frames;                                     // emb [B, E]; frames [sum T', C] or null
+};
+void launch_spk_pool(hipStream_t s, const SpkPoolLaunch& a);
+// the cosine blocks of S streams: stream s holds n[s] = eoff[s + 1] - eoff[s] embeddings, its block starts at out + ooff[s]
+struct SpkAffinityLaunch { const float* emb; const int64_t* eoff; const int64_t* ooff; int S, E, nmax; float* out; };
+void launch_spk_affinity(hipStream_t s, const SpkAffinityLaunch& a);
 
 }  // namespace pf

@@ -1,5 +1,5 @@
 // pfw.h — the one reader of the PFW1 container (`.pfw`: the recogniser's weights, the FSMN-VAD model, the punctuation
-// model; the writer is weights.py pack_pfw).  Host-only: no HIP header beyond common.h, no device call; the caller brings
+// model, the speaker model; the writer is weights.py pack_pfw).  Host-only: no HIP header beyond common.h, no device call; the caller brings
 // the bytes (a file, host memory, or the header copied back from a device-resident image).
 //
 //   bytes 0 .. 3 "PFW1" | 4 .. 7 version | 8 .. 15 header length (u64) | 16 .. the header, JSON {"config": {..}, "tensors": [..]}
@@ -31,6 +31,7 @@ struct PfwPolicy { int code; const char* prefix; bool allow_u8; int64_t offset_a
 constexpr PfwPolicy kPfwWeights{PF_ERR_FORMAT, "weights: ", true, 16};
 constexpr PfwPolicy kPfwVadModel{PF_ERR_INVALID_ARG, "vad model: ", false, 1};
 constexpr PfwPolicy kPfwPuncModel{PF_ERR_INVALID_ARG, "punc model: ", true, 1};
+constexpr PfwPolicy kPfwSpkModel{PF_ERR_INVALID_ARG, "spk model: ", false, 1};
 
 [[noreturn]] void pfw_bad(const PfwPolicy& p, const std::string& m);      // throws Error(p.code, p.prefix + m)
 // an Error on its way out of a loader: p.code and PF_ERR_UNSUPPORTED pass as they are, anything else (a JSON error from

@@ -514,6 +514,9 @@ std::shared_ptr<Engine> Recognizer::make_engine() {
   std::shared_ptr<const VadModel> vm;
   { std::lock_guard<std::mutex> lk(vad_mu_); vm = vad_model_; }
   if (vm) e->set_vad_model(vm);
+  std::shared_ptr<const SpkModel> sm;
+  { std::lock_guard<std::mutex> lk(spk_mu_); sm = spk_model_; }
+  if (sm) e->set_spk_model(sm);
   return e;
 }
 
@@ -707,6 +710,44 @@ void Recognizer::ForwardLong(const std::vector<Stream*>& streams, std::vector<Re
       { std::lock_guard<std::mutex> lk(vad_mu_); vm = vad_model_; }
       if (lease->vad_model() != vm) lease->set_vad_model(vm);
       lease->vad_segment_device(ptrs.data(), ns.data(), B, &cfg, seg.data(), cap, nseg.data());
+      // speaker labels: on the rows that launch staged, under the same lease (the batches below stage their own)
+      std::shared_ptr<const SpkModel> sm; pf_spk_config scfg;
+      { std::lock_guard<std::mutex> lk(spk_mu_); sm = spk_model_; scfg = spk_cfg_; }
+      for (Stream* s : streams) { s->SpkWindows.clear(); s->SegSpeakers.clear(); s->SpkCentroids.clear(); s->NumSpeakers = 0; s->SpkE = 0; }
+      if (sm) {
+        if (lease->spk_model() != sm) lease->set_spk_model(sm);
+        std::vector<int32_t> win, n_utt((size_t)B, 0), one;
+        for (int i = 0; i < B; ++i) {
+          host_spk_windows(seg.data() + (size_t)i * cap * 2, nseg[i], scfg, one, nullptr);
+          n_utt[(size_t)i] = (int32_t)(one.size() / 3);
+          for (size_t k = 0; k < one.size(); k += 3) win.insert(win.end(), {i, one[k + 1], one[k + 2], one[k]});      // + the segment
+        }
+        const int N = (int)(win.size() / 4), E = sm->embedding;
+        std::vector<int32_t> w3((size_t)N * 3);
+        int64_t cells = 0;
+        for (int k = 0; k < N; ++k) { w3[3 * (size_t)k] = win[4 * (size_t)k]; w3[3 * (size_t)k + 1] = win[4 * (size_t)k + 1]; w3[3 * (size_t)k + 2] = win[4 * (size_t)k + 2]; }
+        for (int i = 0; i < B; ++i) cells += (int64_t)n_utt[(size_t)i] * n_utt[(size_t)i];
+        std::vector<float> emb((size_t)N * E), aff((size_t)cells);
+        if (N > 0) lease->spk_staged(w3.data(), N, n_utt.data(), emb.data(), aff.data());
+        size_t w0 = 0, a0 = 0;
+        for (int i = 0; i < B; ++i) {
+          Stream* s = streams[i];
+          const int n = n_utt[(size_t)i];
+          std::vector<int32_t> labels((size_t)n), wseg((size_t)n);
+          int32_t K = 0;
+          host_spk_cluster(aff.data() + a0, n, scfg, labels.data(), &K);
+          for (int k = 0; k < n; ++k) {
+            wseg[(size_t)k] = win[4 * (w0 + (size_t)k) + 3];
+            s->SpkWindows.push_back({10 * win[4 * (w0 + (size_t)k) + 1], 10 * win[4 * (w0 + (size_t)k) + 2], labels[(size_t)k]});
+          }
+          s->SegSpeakers.assign((size_t)nseg[i], -1);
+          host_spk_segment_labels(seg.data() + (size_t)i * cap * 2, nseg[i], wseg.data(), labels.data(), n, s->SegSpeakers.data());
+          s->NumSpeakers = K; s->SpkE = E;
+          s->SpkCentroids.assign((size_t)K * E, 0.f);
+          host_spk_centroids(emb.data() + w0 * E, labels.data(), n, E, K, s->SpkCentroids.data());
+          w0 += (size_t)n; a0 += (size_t)n * n;
+        }
+      }
     }
     // 2. the plan over the pooled pieces
     std::vector<int32_t> lens;
@@ -1532,6 +1573,28 @@ Recognizer::~Recognizer() {
   if (!disposed_.exchange(true)) { engines_.clear(); busy_.clear(); free_device_side(); }
   std::lock_guard<std::mutex> lk(g_live_mu);
   g_live.erase(uid_);
+}
+
+void Recognizer::SetSpkModel(const std::string& pfw_path, const pf_spk_config* cfg) {
+  if (disposed_) throw Error(PF_ERR_DISPOSED, "OfflineRecognizer");
+  std::shared_ptr<const SpkModel> sm;
+  pf_spk_config c = cfg ? *cfg : spk_default();
+  if (!pfw_path.empty()) {
+    spk_check_config(c);
+    sm = spk_model_load(pfw_path);                                           // throws before anything changes
+    if (sm->n_mels != conf_.n_mels) throw Error(PF_ERR_INVALID_ARG, "SetSpkModel: the model's n_mels is not the front-end's");
+  }
+  std::vector<std::shared_ptr<Engine>> es;
+  {
+    std::lock_guard<std::mutex> lk(mu_);
+    if (disposed_ || engines_.empty()) throw Error(PF_ERR_DISPOSED, "OfflineRecognizer");
+    es = engines_;
+  }
+  { std::lock_guard<std::mutex> lk(spk_mu_); spk_model_ = sm; spk_cfg_ = c; }  // engines made from here on attach it themselves
+  for (auto& e : es) {
+    std::lock_guard<std::mutex> lk(e->mutex());
+    e->set_spk_model(sm);
+  }
 }
 
 void Recognizer::SetPuncModel(const std::string& pfw_path) {

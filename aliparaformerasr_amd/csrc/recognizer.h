@@ -172,6 +172,14 @@ class Stream {
   // the sentences: words [word_begin, word_end), their text, and [begin_ms, end_ms] when the result has exactly one Timestamps
   // entry per word (has_time).  Empty without a model.
   struct Sentence { int word_begin = 0, word_end = 0, begin_ms = 0, end_ms = 0; bool has_time = false; std::string text; };
+  // speaker labels (Recognizer::SetSpkModel with SetVad): of the last long-audio GetResults, the windows that were embedded
+  // with their labels, the label of every segment (aligned with Segments; -1: the stream has no window), the number of
+  // speakers and their centroids [NumSpeakers, SpkE]; empty without a model
+  struct SpkWindow { int begin_ms = 0, end_ms = 0, label = -1; };
+  std::vector<SpkWindow> SpkWindows;
+  std::vector<int32_t> SegSpeakers;
+  std::vector<float> SpkCentroids;
+  int NumSpeakers = 0, SpkE = 0;
   std::string Punctuated;
   std::vector<int32_t> PuncIds;
   std::vector<Sentence> Sentences;
@@ -234,6 +242,12 @@ class Recognizer : public std::enable_shared_from_this<Recognizer> {
   // once; "" clears.  GetResults then punctuates each stream's final Text (with SetVad: the stitched text), all streams of the
   // call in one pf_engine_punctuate on a leased engine, and keeps the result on the stream; Text / Tokens / Timestamps stay.
   void SetPuncModel(const std::string& pfw_path);
+  // Speaker labels of every long-audio GetResults that follows (paraformer_hip.h "Speaker labels"): a `.pfw` of kind "campplus",
+  // loaded once and attached to every engine of the pool, present and future; "" clears.  Inert until SetVad, and may be set
+  // before or after it.  Behind the segmentation, on the fbank rows it staged, under the same lease: the windows of all of the
+  // call's streams are planned, embedded and turned into one cosine block per stream on the device, each stream is clustered on
+  // the host.  Text / Tokens / Timestamps / Scores / Segments / Punctuated / Sentences stay what they are without it.
+  void SetSpkModel(const std::string& pfw_path, const pf_spk_config* cfg);
   bool disposed() const { return disposed_.load(); }
   // engine 0 (nullptr once disposed): what pf_recognizer_engine hands out; callers lock engine->mutex() themselves
   std::shared_ptr<Engine> engine() { std::lock_guard<std::mutex> lk(mu_); return engines_.empty() ? nullptr : engines_[0]; }
@@ -275,6 +289,9 @@ class Recognizer : public std::enable_shared_from_this<Recognizer> {
   void Forward(const std::vector<Stream*>& streams);          // :118-198
   void ForwardLong(const std::vector<Stream*>& streams, std::vector<ResultEntity>& out);   // GetResults with SetVad
   void Punctuate(const std::vector<Stream*>& streams, const std::vector<ResultEntity>& out);
+  std::mutex spk_mu_;                                         // guards spk_model_ and spk_cfg_
+  std::shared_ptr<const SpkModel> spk_model_;
+  pf_spk_config spk_cfg_{};
   std::mutex punc_mu_;                                        // guards punc_model_
   std::shared_ptr<const PuncModel> punc_model_;
   std::mutex vad_mu_;                                         // guards the five below

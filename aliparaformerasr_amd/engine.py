@@ -437,6 +437,104 @@ def host_vad_model_levels(model: VadModel, rows) -> np.ndarray:
     return out
 
 
+SPK_MODEL_DIMS = ("n_mels", "m_channels", "init_channels", "growth", "bn_channels", "blocks0", "blocks1", "blocks2", "dilation0",
+                  "dilation1", "dilation2", "seg_len", "embedding", "frame_width", "launches")
+
+
+def spk_config(**kw) -> "N.PfSpkConfig":
+    """pf_spk_config with the defaults (pf_spk_default), fields overridden by keyword."""
+    c = N.PfSpkConfig()
+    N.check(N.load().pf_spk_default(C.byref(c)))
+    for k, v in kw.items():
+        assert hasattr(c, k) and k not in ("struct_size", "reserved"), k
+        setattr(c, k, float(v) if k == "threshold" else int(v))
+    return c
+
+
+def _spk_cfg_ptr(cfg):
+    if cfg is None:
+        return None
+    return C.byref(cfg if isinstance(cfg, N.PfSpkConfig) else spk_config(**cfg))
+
+
+class SpkModel:
+    """A CAM++ speaker model: a `.pfw` of kind "campplus" loaded and validated on the host (pf_spk_model_load /
+    pf_spk_model_from_memory; see "Speaker labels" in the header).  Release with close() (an engine that attached it keeps its
+    own reference)."""
+
+    def __init__(self, handle):
+        self._lib = N.load()
+        self._h = handle
+        d, ib = np.zeros(16, np.int32), C.c_int64()
+        N.check(self._lib.pf_spk_model_info(self._h, _i32p(d), ib))
+        self.dims = dict(zip(SPK_MODEL_DIMS, d.tolist()))
+        self.image_bytes = ib.value
+
+    def close(self):
+        if self._h is not None:
+            self._lib.pf_spk_model_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def load_spk_model(source) -> SpkModel:
+    """A `.pfw` of kind "campplus" from a path or from bytes -> SpkModel."""
+    h = C.c_void_p()
+    if isinstance(source, (bytes, bytearray, memoryview)):
+        buf = bytes(source)
+        N.check(N.load().pf_spk_model_from_memory(C.cast(C.c_char_p(buf), C.c_void_p), len(buf), C.byref(h)))
+    else:
+        N.check(N.load().pf_spk_model_load(str(source).encode("utf-8"), C.byref(h)))
+    return SpkModel(h)
+
+
+def host_spk_windows(segs, cfg=None):
+    """The window plan of ONE stream (pf_host_spk_windows): segs [n, 2] frame pairs -> (windows [N, 3] int32 of (segment,
+    begin, end), the shift used)."""
+    s = np.ascontiguousarray(segs, dtype=np.int32).reshape(-1, 2)
+    lib, n, sh = N.load(), C.c_int32(), C.c_int32()
+    rc = lib.pf_host_spk_windows(_i32p(s), s.shape[0], _spk_cfg_ptr(cfg), None, 0, n, sh)
+    if rc != N.PF_ERR_CAPACITY:
+        N.check(rc)
+    win = np.zeros((max(n.value, 1), 3), np.int32)
+    N.check(lib.pf_host_spk_windows(_i32p(s), s.shape[0], _spk_cfg_ptr(cfg), _i32p(win), n.value, n, sh))
+    return win[: n.value].copy(), sh.value
+
+
+def host_spk_cluster(S, cfg=None):
+    """Average-linkage clustering of ONE stream's cosines (pf_host_spk_cluster): S [N, N] fp32 -> (labels [N] int32, speakers)."""
+    a = _f32(S)
+    a = a.reshape(a.shape[0], a.shape[0]) if a.size else a.reshape(0, 0)
+    labels, k = np.zeros(max(a.shape[0], 1), np.int32), C.c_int32()
+    N.check(N.load().pf_host_spk_cluster(_fp(a), a.shape[0], _spk_cfg_ptr(cfg), _i32p(labels), k))
+    return labels[: a.shape[0]].copy(), k.value
+
+
+def host_spk_segment_labels(segs, win_seg, win_label) -> np.ndarray:
+    """The label of every segment from its windows' (pf_host_spk_segment_labels)."""
+    s = np.ascontiguousarray(segs, dtype=np.int32).reshape(-1, 2)
+    ws, wl = np.ascontiguousarray(win_seg, dtype=np.int32).reshape(-1), np.ascontiguousarray(win_label, dtype=np.int32).reshape(-1)
+    assert ws.size == wl.size
+    out = np.zeros(max(s.shape[0], 1), np.int32)
+    N.check(N.load().pf_host_spk_segment_labels(_i32p(s), s.shape[0], _i32p(ws), _i32p(wl), ws.size, _i32p(out)))
+    return out[: s.shape[0]].copy()
+
+
+def host_spk_centroids(emb, labels, K) -> np.ndarray:
+    """Each speaker's centroid [K, E] (pf_host_spk_centroids)."""
+    e = _f32(emb)
+    l = np.ascontiguousarray(labels, dtype=np.int32).reshape(-1)
+    assert e.ndim == 2 and e.shape[0] == l.size
+    out = np.zeros((max(int(K), 1), e.shape[1]), np.float32)
+    N.check(N.load().pf_host_spk_centroids(_fp(e), _i32p(l), l.size, e.shape[1], int(K), _fp(out)))
+    return out[: int(K)].copy()
+
+
 PUNC_MODEL_DIMS = ("vocab", "d_model", "heads", "ffn", "kernel", "n_layers", "n_punc", "sentence_end_id", "unk_word",
                    "id_unk", "id_none", "id_comma", "id_period", "id_question", "id_pause")
 
@@ -740,6 +838,7 @@ class Engine:
         self._lm = None
         self._vad_model = None
         self._punc_model = None
+        self._spk_model = None
         self._search_w = 0
 
     def close(self):
@@ -1211,6 +1310,44 @@ class Engine:
     def op_vad_model_levels(self, rows_list) -> list:
         """As op_vad_model_logits, the levels [T_b] int32 (pf_op_vad_model_levels)."""
         return self._op_vad_model(rows_list, False)
+
+    def set_spk_model(self, model):
+        """Attaches a SpkModel (pf_engine_set_spk_model); None detaches and frees what the attach and its runs allocated."""
+        N.check(self._lib.pf_engine_set_spk_model(self._h, None if model is None else model._h))
+        self._spk_model = model
+
+    def op_spk_embed(self, rows_list, want_frames=False):
+        """The attached speaker model's launches on caller windows (pf_op_spk_embed): ONE call over all the windows of
+        rows_list ([T_b, n_mels] each) -> embeddings [B, E] float32, and with want_frames also the list of the frames
+        [ceil(T_b / 2), C] in front of the pooling."""
+        arrs = [_f32(r).reshape(-1, np.shape(r)[1]) for r in rows_list]
+        B = len(arrs)
+        m = arrs[0].shape[1] if B else 1
+        assert all(a.shape[1] == m for a in arrs)
+        T = np.ascontiguousarray([a.shape[0] for a in arrs] + [0] * (B == 0), dtype=np.int32)
+        x = np.ascontiguousarray(np.concatenate(arrs, axis=0)) if B and int(T.sum()) else np.zeros((1, m), np.float32)
+        d = self._spk_model.dims if self._spk_model is not None else {"embedding": 1, "frame_width": 1}   # (without a model the call is refused)
+        emb = np.zeros((max(B, 1), d["embedding"]), np.float32)
+        Tp = (T[:B] + 1) // 2
+        fr = np.zeros((max(int(Tp.sum()), 1), d["frame_width"]), np.float32) if want_frames else None
+        N.check(self._lib.pf_op_spk_embed(self._h, _fp(x), _i32p(T), B, m, _fp(emb), _fp(fr) if want_frames else None))
+        if not want_frames:
+            return emb[:B].copy()
+        off = np.concatenate([[0], np.cumsum(Tp)]).astype(np.int64)
+        return emb[:B].copy(), [fr[off[b]: off[b + 1]].copy() for b in range(B)]
+
+    def op_spk_affinity(self, emb_list) -> list:
+        """The cosine block of every stream of emb_list ([n_s, E] each) in ONE launch (pf_op_spk_affinity) -> [n_s, n_s] float32."""
+        arrs = [_f32(e).reshape(-1, np.shape(e)[1]) for e in emb_list]
+        S = len(arrs)
+        E_ = arrs[0].shape[1] if S else 1
+        n = np.ascontiguousarray([a.shape[0] for a in arrs] + [0] * (S == 0), dtype=np.int32)
+        x = np.ascontiguousarray(np.concatenate(arrs, axis=0)) if S and int(n.sum()) else np.zeros((1, E_), np.float32)
+        cells = [int(k) * int(k) for k in n[:S]]
+        out = np.zeros(max(sum(cells), 1), np.float32)
+        N.check(self._lib.pf_op_spk_affinity(self._h, _fp(x), _i32p(n), S, E_, _fp(out)))
+        off = np.concatenate([[0], np.cumsum(cells)]).astype(np.int64)
+        return [out[off[s]: off[s + 1]].reshape(int(n[s]), int(n[s])).copy() for s in range(S)]
 
     def set_punc_model(self, model):
         """Attaches a PuncModel (pf_engine_set_punc_model); None detaches and frees what the attach and its runs allocated."""

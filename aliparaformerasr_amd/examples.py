@@ -1,7 +1,7 @@
 """Command-line harness mirroring AliParaformerAsr.Examples (`-type offline` and `-type online`).
 
     python -m aliparaformerasr_amd.examples -type offline -method batch -base <dir> -model <name> \
-        [-accuracy int8] [-threads 2] [-decode ctc|frames] [-intake host|device] [-nbest N [-topk K] [-beam W | -search W] [-hotboost S] [-lm FILE [-lmweight A] [-lmbonus B] [-lmeos]]] [-align FILE|beam] [-vad [key=value,...] [-vadmodel FILE]] [-punc FILE] -files a.wav b.wav
+        [-accuracy int8] [-threads 2] [-decode ctc|frames] [-intake host|device] [-nbest N [-topk K] [-beam W | -search W] [-hotboost S] [-lm FILE [-lmweight A] [-lmbonus B] [-lmeos]]] [-align FILE|beam] [-vad [key=value,...] [-vadmodel FILE] [-spk FILE [key=value,...]]] [-punc FILE] -files a.wav b.wav
     python -m aliparaformerasr_amd.examples -type online -method one -base <dir> -model <name> -files a.wav
 
 Mirrors (file:line in /root/reference/AliParaformerAsr.Examples):
@@ -49,6 +49,10 @@ thresholds are unvalidated on real speech.  Not beside -nbest / -align.
 `-vadmodel FILE` (with `-vad`; OfflineRecognizer.SetVadModel) scores the frames with an FSMN-VAD network instead of the
 log-mel energy: FILE is a `.pfw` of kind fsmnvad (`python -m aliparaformerasr_amd.convert vad.onnx out.pfw --kind fsmnvad
 --mvn vad.mvn`); the model's default thresholds (floor_pct=-1, abs_level=9830; unvalidated too) apply unless keys are given.
+`-spk FILE [key=value,...]` (with `-vad`; OfflineRecognizer.SetSpeakerModel) says who speaks in each segment: FILE is a `.pfw` of
+kind campplus (`python -m aliparaformerasr_amd.convert campplus.bin out.pfw --kind campplus`); each segment line becomes
+`[begin-end ms] spkN text`.  Keys: the pf_spk_config fields (win, shift, min_frames, threshold, num_speakers, min_cluster).  The
+network and the thresholds are stated, not validated on a real model.
 `-punc FILE` (OfflineRecognizer.SetPuncModel) punctuates every result on the GPU with a CT-Transformer: FILE is a `.pfw` of kind
 cttransformer; under each result goes a `punctuated: ...` line and one `  [begin-end ms] sentence` line per sentence (without the
 times when the result has no timestamp per word).  Rules and dimensions are stated, not validated on a real model.
@@ -206,8 +210,32 @@ def parse_vad_option(text: str) -> dict:
     return out
 
 
-def _segment_lines(stream) -> list:
-    return ["[%d-%d ms] %s" % (g.BeginMs, g.EndMs, g.Text) for g in stream.Segments]
+SPK_KEYS = ("win", "shift", "min_frames", "threshold", "num_speakers", "min_cluster")
+
+
+def parse_spk_option(text: str) -> dict:
+    """`key=value,...` of -spk -> {pf_spk_config fields}"""
+    out = {}
+    for item in [x for x in text.split(",") if x]:
+        k, eq, v = item.partition("=")
+        k = k.strip()
+        if not eq:
+            raise ValueError("-spk takes key=value pairs: %r" % item)
+        if k not in SPK_KEYS:
+            raise ValueError("Unknown -spk key: %s" % k)
+        try:
+            out[k] = float(v) if k == "threshold" else int(v)
+        except ValueError:
+            raise ValueError("The -spk value of %s must be %s" % (k, "a number" if k == "threshold" else "an integer"))
+        if out[k] != out[k]:
+            raise ValueError("The -spk value of %s must be a number" % k)
+    return out
+
+
+def _segment_lines(stream, speakers=False) -> list:
+    spk = stream.SegmentSpeakers if speakers else []
+    return ["[%d-%d ms] %s%s" % (g.BeginMs, g.EndMs, ("spk%d " % spk[i]) if i < len(spk) and spk[i] >= 0 else "", g.Text)
+            for i, g in enumerate(stream.Segments)]
 
 
 def read_align_file(path: str) -> list:
@@ -232,7 +260,7 @@ def _punc_lines(st):
 
 def offline_recognizer(method="one", model="paraformer-seaco-large-zh-timestamp-onnx-offline", accuracy="int8",
                        threads=2, files=None, base=None, out=sys.stdout, decode="frames", intake="host", nbest=0, topk=4,
-                       beam=0, align=None, hotboost=0.0, vad=None, lm=None, lmweight=0.5, lmbonus=0.0, lmeos=False, search=0, vadmodel=None, punc=None):
+                       beam=0, align=None, hotboost=0.0, vad=None, lm=None, lmweight=0.5, lmbonus=0.0, lmeos=False, search=0, vadmodel=None, punc=None, spk=None):
     from .offline_recognizer import OfflineRecognizer
     base = base or os.getcwd()
     sel = select_model_files(base, model, accuracy)
@@ -264,6 +292,8 @@ def offline_recognizer(method="one", model="paraformer-seaco-large-zh-timestamp-
             rec.SetVadModel(vadmodel)
             vcfg = vad_model_config(**vad["cfg"])
         rec.SetVad(vcfg, vad["batch_max"], vad["frame_budget"], vad["sep"])
+    if spk:
+        rec.SetSpeakerModel(spk["file"], spk["cfg"] or None)
     if punc:
         rec.SetPuncModel(punc)
     targets = None
@@ -302,7 +332,7 @@ def offline_recognizer(method="one", model="paraformer-seaco-large-zh-timestamp-
 
     def extra_lines(st):
         return (_nbest_lines(st, align == "beam") if nbest else []) + (_align_lines(st) if targets is not None else []) + \
-            (_segment_lines(st) if vad is not None else []) + (_punc_lines(st) if punc else [])
+            (_segment_lines(st, bool(spk)) if vad is not None else []) + (_punc_lines(st) if punc else [])
     print("Recognition results:\r\n", file=out)
     try:
         if method == "one":
@@ -512,6 +542,14 @@ def parse_args(argv, env=None):
             if i >= len(argv) or argv[i].startswith("-"):
                 raise ValueError("-vadmodel takes a .pfw file of kind fsmnvad")
             cfg["vadmodel"] = argv[i]
+        elif a == "-spk":
+            i += 1
+            if i >= len(argv) or argv[i].startswith("-"):
+                raise ValueError("-spk takes a .pfw file of kind campplus")
+            cfg["spk"] = {"file": argv[i], "cfg": {}}
+            if i + 1 < len(argv) and not argv[i + 1].startswith("-") and "=" in argv[i + 1]:
+                i += 1
+                cfg["spk"]["cfg"] = parse_spk_option(argv[i])
         elif a == "-punc":
             i += 1
             if i >= len(argv) or argv[i].startswith("-"):
@@ -560,6 +598,8 @@ def parse_args(argv, env=None):
         raise ValueError("-vad does not go with -nbest or -align")
     if "punc" in cfg and cfg["recognizerType"] != "offline":
         raise ValueError("-punc is an offline option")
+    if "spk" in cfg and "vad" not in cfg:
+        raise ValueError("-spk goes with -vad")
     if "vadmodel" in cfg and "vad" not in cfg:
         raise ValueError("-vadmodel goes with -vad")
     if cfg.get("align") == "beam" and "beam" not in cfg:
@@ -584,7 +624,7 @@ def main(argv=None):
                            nbest=cfg.get("nbest", 0), topk=cfg.get("topk", 4), beam=cfg.get("beam", 0), align=cfg.get("align"),
                            hotboost=cfg.get("hotboost", 0.0), vad=cfg.get("vad"), lm=cfg.get("lm"), lmweight=cfg.get("lmweight", 0.5),
                            lmbonus=cfg.get("lmbonus", 0.0), lmeos=cfg.get("lmeos", False), search=cfg.get("search", 0),
-                           vadmodel=cfg.get("vadmodel"), punc=cfg.get("punc"))
+                           vadmodel=cfg.get("vadmodel"), punc=cfg.get("punc"), spk=cfg.get("spk"))
     else:
         print("the recognizer type must be online or offline")
         return 2

@@ -283,6 +283,45 @@ class OfflineStream:
             out.append(Segment(*[x.value for x in v], Text=(txt.value or b"").decode("utf-8")))
         return out
 
+    @property
+    def SegmentSpeakers(self) -> List[int]:
+        """The speaker label of every entry of Segments (OfflineRecognizer.SetSpeakerModel with SetVad; empty without it): 0, 1, ..
+        in the order of each speaker's first window, -1 when the stream has no window at all."""
+        n, v = C.c_int32(), C.c_int32()
+        _ck(self._lib.pf_stream_num_segments(self._h, n))
+        out = []
+        for i in range(n.value):
+            if self._lib.pf_stream_segment_speaker(self._h, i, v) != 0:      # no speaker model was on
+                return []
+            out.append(v.value)
+        return out
+
+    @property
+    def SpeakerCentroids(self) -> np.ndarray:
+        """[speakers, E] float32: each speaker's centroid, the L2-normalised mean of its windows' L2-normalised embeddings (for
+        matching against enrolled voices); [0, 0] without speaker labels."""
+        k, e = C.c_int32(), C.c_int32()
+        _ck(self._lib.pf_stream_num_speakers(self._h, k))
+        _ck(self._lib.pf_stream_speaker_centroid(self._h, 0, None, 0, e))
+        out = np.zeros((k.value, e.value), np.float32)
+        for s in range(k.value):
+            row = np.zeros(max(e.value, 1), np.float32)
+            _ck(self._lib.pf_stream_speaker_centroid(self._h, s, row.ctypes.data_as(C.POINTER(C.c_float)), e.value, e))
+            out[s] = row[: e.value]
+        return out
+
+    @property
+    def SpeakerWindows(self) -> List[tuple]:
+        """(begin ms, end ms, label) of every window that was embedded, in time order."""
+        n = C.c_int32()
+        _ck(self._lib.pf_stream_num_spk_windows(self._h, n))
+        out = []
+        for i in range(n.value):
+            v = [C.c_int32() for _ in range(3)]
+            _ck(self._lib.pf_stream_spk_window(self._h, i, *v))
+            out.append(tuple(x.value for x in v))
+        return out
+
     def _punctuated(self):
         txt, ids, n = C.c_char_p(), C.POINTER(C.c_int32)(), C.c_int32()
         _ck(self._lib.pf_stream_punctuated(self._h, C.byref(txt), C.byref(ids), n))
@@ -507,6 +546,16 @@ class OfflineRecognizer:
         all streams of a call in one batch: stream.Punctuated, .PuncIds, .Sentences.  Text, Tokens and Timestamps of the result
         stay what they are.  No real model file has been through this path: the rules and dimensions are stated, not validated."""
         _ck(self._lib.pf_recognizer_set_punc_model(self._h, None if pfwPath is None else str(pfwPath).encode("utf-8")))
+
+    def SetSpeakerModel(self, pfwPath, cfg=None) -> None:
+        """Speaker labels for every long-audio GetResults that follows: a `.pfw` of kind "campplus" (python -m
+        aliparaformerasr_amd.convert ... --kind campplus), loaded once and attached to every engine of the pool, present and
+        future; None clears.  cfg: None (the defaults), an engine.spk_config(...) or a dict of its fields.  Inert until SetVad,
+        and may be set before or after it.  stream.SegmentSpeakers, .SpeakerCentroids, .SpeakerWindows; everything else of the
+        result stays what it is.  No real model file has been through this path: the network, the windows and the thresholds are
+        stated, not validated."""
+        from .engine import _spk_cfg_ptr
+        _ck(self._lib.pf_recognizer_set_spk_model(self._h, None if pfwPath is None else str(pfwPath).encode("utf-8"), _spk_cfg_ptr(cfg)))
 
     def SetVadModel(self, pfwPath) -> None:
         """The FSMN-VAD model score for SetVad's segmentation: a `.pfw` of kind "fsmnvad" (python -m aliparaformerasr_amd.convert

@@ -33,6 +33,9 @@ engine.load_vad_model, never handed to an Engine as its weights.  The same
 holds for kind "cttransformer", the punctuation model (ct_transformer_config
 / punc_tensor_shapes / synth_punc_weights; tests/punc_ref.py;
 engine.load_punc_model): its vocabulary travels as the u8 tensor "vocab".
+Kind "campplus" is the speaker-embedding model (campplus_config /
+spk_tensor_shapes / synth_spk_weights; tests/spk_ref.py;
+engine.load_spk_model).
 """
 from __future__ import annotations
 
@@ -331,6 +334,79 @@ def synth_punc_weights(cfg: dict, seed: int = 42, decoder_scale: float = 1.0) ->
     dec["decoder.weight"] = (dec["decoder.weight"] * np.float32(decoder_scale)).astype(np.float32)
     w.update(dec)
     w["vocab"] = np.frombuffer("\n".join(synth_punc_vocab(int(cfg["vocab"]))).encode("utf-8"), dtype=np.uint8).copy()
+    return w
+
+
+CAMPPLUS_CONFIG = dict(
+    kind="campplus", n_mels=80, m_channels=32, init_channels=128, growth=32, bn_channels=128, blocks=(12, 24, 16),
+    dilations=(1, 2, 2), seg_len=100, embedding=192,
+)
+
+
+def campplus_config(**kw) -> dict:
+    """The config of a `.pfw` of kind "campplus" (the speaker-embedding model; the definition is tests/spk_ref.py).  The
+    defaults are the dimensions of 3D-Speaker's released speech_campplus_sv_zh-cn_16k-common as remembered, not read from a
+    file."""
+    cfg = dict(CAMPPLUS_CONFIG)
+    for k, v in kw.items():
+        if k not in cfg:
+            raise KeyError(k)
+        cfg[k] = v
+    cfg["blocks"] = [int(n) for n in cfg["blocks"]]
+    cfg["dilations"] = [int(d) for d in cfg["dilations"]]
+    return cfg
+
+
+def spk_channel_plan(cfg: dict) -> list:
+    """[(channels into block b, channels behind its last layer)] for the three dense blocks; a transit halves the second."""
+    C, plan = int(cfg["init_channels"]), []
+    for n in cfg["blocks"]:
+        plan.append((C, C + int(n) * int(cfg["growth"])))
+        C = plan[-1][1] // 2
+    return plan
+
+
+def spk_tensor_shapes(cfg: dict) -> dict:
+    """name -> shape of every tensor of a "campplus" container.  Every BatchNorm that can be folded is folded at convert time:
+    a convolution or Linear carries the folded scale in its weight and the folded shift as its bias; a BatchNorm that a ReLU
+    follows (bn1 of a dense layer, a transit's, the last one) stays as `scale` / `shift`.  Convolutions are [out, in, kf, kt]
+    (frequency, time), the TDNN and the dense layers' local convolution [out, in, k], Linear [out, in]."""
+    m, I, g, bn, E = (int(cfg[k]) for k in ("m_channels", "init_channels", "growth", "bn_channels", "embedding"))
+    sh = {"head.conv1.weight": (m, 1, 3, 3), "head.conv1.bias": (m,)}
+    for layer in (1, 2):
+        for blk in (0, 1):
+            p = "head.layer%d.%d." % (layer, blk)
+            sh.update({p + "conv1.weight": (m, m, 3, 3), p + "conv1.bias": (m,), p + "conv2.weight": (m, m, 3, 3), p + "conv2.bias": (m,)})
+            if blk == 0:
+                sh.update({p + "shortcut.weight": (m, m, 1, 1), p + "shortcut.bias": (m,)})
+    sh.update({"head.conv2.weight": (m, m, 3, 3), "head.conv2.bias": (m,)})
+    sh.update({"tdnn.weight": (I, m * (int(cfg["n_mels"]) // 8), 5), "tdnn.bias": (I,)})
+    for b, ((C0, C1), n) in enumerate(zip(spk_channel_plan(cfg), cfg["blocks"])):
+        for l in range(int(n)):
+            C, p = C0 + l * g, "block%d.%d." % (b + 1, l)
+            sh.update({p + "bn1.scale": (C,), p + "bn1.shift": (C,), p + "linear1.weight": (bn, C), p + "linear1.bias": (bn,),
+                       p + "local.weight": (g, bn, 3), p + "cam1.weight": (bn // 2, bn), p + "cam1.bias": (bn // 2,),
+                       p + "cam2.weight": (g, bn // 2), p + "cam2.bias": (g,)})
+        p = "transit%d." % (b + 1)
+        sh.update({p + "bn.scale": (C1,), p + "bn.shift": (C1,), p + "weight": (C1 // 2, C1)})
+    C = spk_channel_plan(cfg)[-1][1] // 2
+    sh.update({"out_bn.scale": (C,), "out_bn.shift": (C,), "dense.weight": (E, 2 * C), "dense.bias": (E,)})
+    return sh
+
+
+def synth_spk_weights(cfg: dict, seed: int = 42) -> dict:
+    """Seeded synthetic CAM++ weights: weights N(0, sqrt(2 / fan_in)) (a ReLU follows nearly every product), biases and shifts
+    N(0, 0.1), scales U(0.8, 1.2)."""
+    rng = np.random.default_rng(seed)
+    w = {}
+    for name, shape in spk_tensor_shapes(cfg).items():
+        if name.endswith(".scale"):
+            a = rng.uniform(0.8, 1.2, shape)
+        elif name.endswith((".bias", ".shift")):
+            a = 0.1 * rng.standard_normal(shape)
+        else:
+            a = rng.standard_normal(shape) * np.sqrt(2.0 / float(np.prod(shape[1:])))
+        w[name] = a.astype(np.float32)
     return w
 
 

@@ -224,6 +224,42 @@ namespace AliParaformerAsr.Hip
             }
         }
 
+        /// <summary>Not in the reference: the speaker label of every entry of Segments (OfflineRecognizer.SetSpeakerModel with
+        /// SetVad; empty without it): 0, 1, .. in the order of each speaker's first window, -1 when the stream has no window.</summary>
+        public List<int> SegmentSpeakers
+        {
+            get
+            {
+                var r = new List<int>();
+                ParaformerHip.Check(ParaformerHip.pf_stream_num_segments(Handle, out int n));
+                ParaformerHip.Check(ParaformerHip.pf_stream_num_spk_windows(Handle, out int w));
+                ParaformerHip.Check(ParaformerHip.pf_stream_num_speakers(Handle, out int k));
+                if (w == 0 && k == 0) return r;
+                for (int i = 0; i < n; i++)
+                {
+                    ParaformerHip.Check(ParaformerHip.pf_stream_segment_speaker(Handle, i, out int spk));
+                    r.Add(spk);
+                }
+                return r;
+            }
+        }
+
+        /// <summary>Not in the reference: speaker spk's centroid (pf_stream_speaker_centroid), for matching against enrolled voices.</summary>
+        public float[] SpeakerCentroid(int spk)
+        {
+            ParaformerHip.Check(ParaformerHip.pf_stream_speaker_centroid(Handle, spk, null, 0, out int e));
+            var c = new float[e];
+            ParaformerHip.Check(ParaformerHip.pf_stream_speaker_centroid(Handle, spk, c, e, out e));
+            return c;
+        }
+
+        /// <summary>Not in the reference: window i that was embedded, in ms, and its label (pf_stream_spk_window).</summary>
+        public (int BeginMs, int EndMs, int Label) SpeakerWindow(int i)
+        {
+            ParaformerHip.Check(ParaformerHip.pf_stream_spk_window(Handle, i, out int b, out int e, out int l));
+            return (b, e, l);
+        }
+
         /// <summary>Not in the reference: one sentence of the punctuated text: the words [WordBegin, WordEnd), its text, and
         /// [BeginMs, EndMs] when the result has exactly one Timestamps entry per word (HasTime).</summary>
         public sealed class Sentence
@@ -453,6 +489,23 @@ namespace AliParaformerAsr.Hip
         /// call in one batch (OfflineStream.Punctuated, PuncIds, Sentences); Text, Tokens and Timestamps stay what they are.  The rules
         /// and dimensions are stated, not validated on a real model.</summary>
         public void SetPuncModel(string? pfwPath) => ParaformerHip.Check(ParaformerHip.pf_recognizer_set_punc_model(_r, pfwPath));
+
+        /// <summary>Not in the reference: speaker labels for every long-audio GetResults that follows (pf_recognizer_set_spk_model): a
+        /// .pfw of kind "campplus", loaded once and attached to every engine of the pool; null clears.  cfg: null for the defaults
+        /// (DefaultSpeaker()).  Inert until SetVad, before or after it.  OfflineStream.SegmentSpeakers, SpeakerCentroid, SpeakerWindow;
+        /// everything else of a result stays what it is.  Nothing of this has been validated on a real model.</summary>
+        public void SetSpeakerModel(string? pfwPath, PfSpkConfig? cfg = null)
+        {
+            PfSpkConfig c = cfg ?? DefaultSpeaker();
+            ParaformerHip.Check(ParaformerHip.pf_recognizer_set_spk_model(_r, pfwPath, ref c));
+        }
+
+        /// <summary>The stated defaults of the speaker labels (pf_spk_default).</summary>
+        public static PfSpkConfig DefaultSpeaker()
+        {
+            ParaformerHip.Check(ParaformerHip.pf_spk_default(out PfSpkConfig c));
+            return c;
+        }
 
         /// <summary>The stated defaults that go with the model score (pf_vad_model_config: floor_pct = -1, abs_level = 9830).</summary>
         public static PfVadConfig DefaultVadModel()

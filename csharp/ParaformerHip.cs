@@ -52,6 +52,16 @@ namespace AliParaformerAsr.Native
                    split_search, reserved0, reserved1, reserved2, reserved3;
     }
 
+    /// <summary>pf_spk_config: the speaker labels' configuration (paraformer_hip.h "Speaker labels"); pf_spk_default fills in the
+    /// stated defaults, which nobody has validated on real speech.</summary>
+    [StructLayout(LayoutKind.Sequential)]
+    public struct PfSpkConfig
+    {
+        public int struct_size, win, shift, min_frames;
+        public float threshold;
+        public int num_speakers, min_cluster, reserved0, reserved1, reserved2, reserved3, reserved4;
+    }
+
     /// <summary>pf_batch_out: capacities in, L / V / cif_peak_len and the filled buffers out.</summary>
     [StructLayout(LayoutKind.Sequential)]
     internal struct PfBatchOut
@@ -282,6 +292,19 @@ namespace AliParaformerAsr.Native
         [DllImport(Lib)] internal static extern void pf_punc_model_free(IntPtr m);
         [DllImport(Lib)] internal static extern int pf_engine_set_punc_model(IntPtr e, IntPtr m);
         [DllImport(Lib)] internal static extern int pf_engine_punctuate(IntPtr e, int[] ids, int[] lens, int B, [Out] int[] puncIds, out int rounds);
+        // speaker labels (a .pfw of kind "campplus"): the loader, what it read, the defaults, the attach calls, a stream's result
+        [DllImport(Lib)] internal static extern int pf_spk_model_load([MarshalAs(UnmanagedType.LPUTF8Str)] string path, out IntPtr m);
+        [DllImport(Lib)] internal static extern int pf_spk_model_from_memory(byte[] data, long nbytes, out IntPtr m);
+        [DllImport(Lib)] internal static extern int pf_spk_model_info(IntPtr m, [Out] int[]? dims, out long imageBytes);
+        [DllImport(Lib)] internal static extern void pf_spk_model_free(IntPtr m);
+        [DllImport(Lib)] internal static extern int pf_spk_default(out PfSpkConfig cfg);
+        [DllImport(Lib)] internal static extern int pf_engine_set_spk_model(IntPtr e, IntPtr m);
+        [DllImport(Lib)] internal static extern int pf_recognizer_set_spk_model(IntPtr r, [MarshalAs(UnmanagedType.LPUTF8Str)] string? pfwPath, ref PfSpkConfig cfg);
+        [DllImport(Lib)] internal static extern int pf_stream_num_speakers(IntPtr s, out int n);
+        [DllImport(Lib)] internal static extern int pf_stream_segment_speaker(IntPtr s, int i, out int spk);
+        [DllImport(Lib)] internal static extern int pf_stream_speaker_centroid(IntPtr s, int spk, [Out] float[]? centroid, int cap, out int e);
+        [DllImport(Lib)] internal static extern int pf_stream_num_spk_windows(IntPtr s, out int n);
+        [DllImport(Lib)] internal static extern int pf_stream_spk_window(IntPtr s, int i, out int beginMs, out int endMs, out int label);
         [DllImport(Lib)] internal static extern int pf_recognizer_set_punc_model(IntPtr r, [MarshalAs(UnmanagedType.LPUTF8Str)] string? pfwPath);
         [DllImport(Lib)] internal static extern int pf_stream_punctuated(IntPtr s, out IntPtr textUtf8, out IntPtr puncIds, out int nWords);
         [DllImport(Lib)] internal static extern int pf_stream_num_sentences(IntPtr s, out int n);

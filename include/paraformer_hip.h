@@ -729,6 +729,82 @@ int pf_engine_set_punc_model(pf_engine* e, const pf_punc_model* m);
    PF_ERR_INVALID_ARG without an attached model or for an id outside the vocabulary. */
 int pf_engine_punctuate(pf_engine* e, const int32_t* ids, const int32_t* lens, int32_t B, int32_t* punc_ids, int32_t* rounds);
 
+/* ---- Speaker labels (additions to ABI 6; opt-in: with no model attached nothing of this is launched or allocated and every
+   result is bit for bit what it is without it) ----
+   Who speaks in each segment of a long recording: a CAM++ network (the speaker model FunASR's AutoModel takes as
+   spk_model="cam++") turns windows of fbank rows into embeddings, the cosines of a stream's embeddings are clustered on the
+   host, and a segment takes the label most of its windows hold.  The definition in numpy float64 is tests/spk_ref.py;
+   DESIGN.md 4.6m has the launch plan and the rounding points of the device form (csrc/k_spk.hip).  The network is stated from
+   memory of 3D-Speaker's CAMPPlus (speech_campplus_sv_zh-cn_16k-common, 192-d) and is THIS PROJECT'S definition.  NO REAL
+   MODEL FILE HAS BEEN LOADED AND NOTHING HERE IS VALIDATED ON ONE: no dimension, no threshold, and not the front-end (the
+   engine's fbank uses a Hamming window, the released model was trained with a Povey window).
+   The model is a `.pfw` of kind "campplus": n_mels, m_channels, init_channels, growth, bn_channels, blocks [3], dilations [3],
+   seg_len, embedding, and the BatchNorm-folded tensors weights.spk_tensor_shapes lists.
+   NETWORK, for a window of T <= PF_SPK_MAX_FRAMES rows x [T, n_mels] of the engine's own fbank: x - mean_t x; the FCM head
+   (conv1 3x3, two residual layers of two blocks each, the first of a layer with stride 2 in frequency and a 1x1 shortcut, conv2
+   with stride 2 in frequency; ReLU throughout) -> frames of m_channels * n_mels / 8 channels; a TDNN (k 5, stride 2, pad 2, ReLU)
+   -> T' = ceil(T / 2) frames; three densely connected blocks of CAM layers (h = ReLU(BN X); b = ReLU(W1 h + c1); a dilated
+   k-3 convolution of b times the mask sigmoid(W3 ReLU(W2 c + b2) + b3) of the context c[t] = mean_t b + the mean of b over
+   t's segment of seg_len frames; appended to X), each followed by a transit (ReLU(BN), a 1x1 halving the width); ReLU(BN);
+   per channel the mean and the unbiased standard deviation over T' (0 when T' = 1); a Linear to `embedding` values, fp32.
+   T = 0 gives zeros.  The device form multiplies f16 operands with fp32 accumulation, so its embeddings are close to, not
+   equal to, the definition's; a window's bits do not depend on what else is in the call.  Every math mode of an engine uses
+   the same f16 kernels for this network.
+   WINDOWS of a segment of frames [b, e) under pf_spk_config: none below min_frames; [b, e) up to win; otherwise
+   [b + k shift, + win) while they fit, plus [e - win, e) if the last does not end at e.  A stream with more than
+   PF_SPK_MAX_WINDOWS windows doubles its shift until it fits.
+   CLUSTERING (host, double, deterministic): average linkage over the cosines, cluster similarity updated as
+   (nA sAC + nB sBC) / (nA + nB); the pair of largest similarity merges, ties to the smallest first then second index (a
+   cluster's index is its earliest window); it stops when the largest similarity is below `threshold`, or, with
+   num_speakers > 0, when that many clusters are left (the threshold is then not consulted).  Without num_speakers every cluster
+   of fewer than min_cluster windows then joins the cluster of min_cluster or more windows it is most similar to, if there is
+   one.  Labels count from 0 in the order of each speaker's first window.  A segment without a window takes the label of the
+   labelled segment nearest in time (ties to the earlier), -1 when the stream has none.
+   Loading validates everything.  PF_ERR_INVALID_ARG: not such a container, truncated, a tensor extent outside the file, a
+   missing tensor, a wrong shape, a value that is not finite.  PF_ERR_UNSUPPORTED: n_mels no multiple of 8 or above 128;
+   m_channels no multiple of 8 or above 64; m_channels * n_mels / 8 > 512; init_channels or bn_channels > 128, bn_channels odd;
+   growth > 64; a block of more than 64 layers; a dilation > 8; seg_len < 4; a concatenated width that is odd or above 2048;
+   embedding > 512.  PF_ERR_IO: the file cannot be read. */
+#define PF_SPK_MAX_FRAMES 512
+#define PF_SPK_MAX_WINDOWS 8192
+typedef struct pf_spk_model pf_spk_model;
+int pf_spk_model_load(const char* path, pf_spk_model** m);
+int pf_spk_model_from_memory(const void* data, int64_t nbytes, pf_spk_model** m);
+/* dims [16]: n_mels, m_channels, init_channels, growth, bn_channels, blocks [3], dilations [3], seg_len, embedding, the frames'
+   width, the launches of one forward, 0; each output optional */
+int pf_spk_model_info(const pf_spk_model* m, int32_t* dims, int64_t* image_bytes);
+void pf_spk_model_free(pf_spk_model* m);
+typedef struct pf_spk_config {
+  int32_t struct_size;        /* = sizeof(pf_spk_config)                                                   */
+  int32_t win;                /* 150 frames per window (1 .. PF_SPK_MAX_FRAMES)                            */
+  int32_t shift;              /* 75                                                                        */
+  int32_t min_frames;         /* 20: a shorter segment has no window                                       */
+  float threshold;            /* 0.5, stated and not tuned                                                 */
+  int32_t num_speakers;       /* 0: the threshold decides                                                  */
+  int32_t min_cluster;        /* 4                                                                         */
+  int32_t reserved[5];
+} pf_spk_config;
+/* fills in struct_size and the defaults above */
+int pf_spk_default(pf_spk_config* cfg);
+/* Attaches the model to the engine (NULL detaches and frees what the attach and its runs allocated).  The engine takes a
+   reference of its own (pf_spk_model_free may follow at once) and uploads the weight image once.  PF_ERR_INVALID_ARG unless
+   the model's n_mels is the engine's.  Nothing else the engine computes changes; a pf_group forward is unaffected. */
+int pf_engine_set_spk_model(pf_engine* e, const pf_spk_model* m);
+/* The host half (plain C++, no device).  cfg == NULL: the defaults.
+   pf_host_spk_windows: the plan of ONE stream: seg [n_seg, 2] frame pairs -> win [cap, 3] (segment, begin, end; NULL with cap
+   0 to learn *n; PF_ERR_CAPACITY when cap < *n), *shift_used (optional).
+   pf_host_spk_cluster: S [N, N] fp32 (its upper triangle is read; a value that is not finite counts as -2) -> labels [N],
+   *n_speakers.
+   pf_host_spk_segment_labels: seg [n_seg, 2], the windows' segment and label [N] -> out [n_seg].
+   pf_host_spk_centroids: emb [N, E], labels [N] -> out [K, E]: the L2-normalised mean of each speaker's L2-normalised
+   embeddings (zeros for a speaker without a window). */
+int pf_host_spk_windows(const int32_t* seg, int32_t n_seg, const pf_spk_config* cfg, int32_t* win, int32_t cap, int32_t* n,
+                        int32_t* shift_used);
+int pf_host_spk_cluster(const float* S, int32_t N, const pf_spk_config* cfg, int32_t* labels, int32_t* n_speakers);
+int pf_host_spk_segment_labels(const int32_t* seg, int32_t n_seg, const int32_t* win_seg, const int32_t* win_label, int32_t N,
+                               int32_t* out);
+int pf_host_spk_centroids(const float* emb, const int32_t* labels, int32_t N, int32_t E, int32_t K, float* out);
+
 /* ------------------------------------------------------------------------ */
 /* 4b. Multi-GPU inside one process: one engine, one host thread and one HIP stream per listed
  *     device.  The reference builds a single ORT session (OfflineRecognizer.cs:23); what shards is the utterance
@@ -828,6 +904,16 @@ int pf_op_vad_model_levels(pf_engine* e, const float* rows, const int32_t* T, in
 int pf_op_punc_logits(pf_engine* e, const int32_t* ids, const int32_t* T, int32_t B, float* logits, float* x0);
 int pf_op_punc_window(pf_engine* e, const int32_t* ids, const int32_t* T, const int32_t* last, int32_t B, int32_t* p, int32_t* cut,
                       float* logits);
+/* exactly the attached speaker model's launches (k_spk.hip; PF_ERR_INVALID_ARG without pf_engine_set_spk_model) on caller
+   windows: rows = the concatenated fbank rows of B windows, T [B] rows each (0 .. PF_SPK_MAX_FRAMES, else PF_ERR_INVALID_ARG),
+   n_mels wide.  emb [B, embedding] fp32; frames (optional) [sum ceil(T / 2), the frames' width] fp32: the activations in front
+   of the pooling.  ONE forward (profile class "spk"): 15 launches whatever B and T.  A window's result does not depend on
+   what else is in the call.
+   pf_op_spk_affinity: emb = the concatenated embeddings of S streams, n [S] each, E wide -> out = the concatenated [n_s, n_s]
+   cosine blocks, fp32 in a fixed order of summation (a zero embedding has cosine 0 with everything); one launch of class
+   "spk".  Needs no model. */
+int pf_op_spk_embed(pf_engine* e, const float* rows, const int32_t* T, int32_t B, int32_t n_mels, float* emb, float* frames);
+int pf_op_spk_affinity(pf_engine* e, const float* emb, const int32_t* n, int32_t S, int32_t E, float* out);
 /* exactly the pipeline's top-k kernel (k_topk.hip) on the values as given: x [rows, ld] (ld >= V; nothing at or beyond V is
    read in a row), K: 1 .. PF_TOPK_MAX; ids [rows, K], val [rows, K], n [rows] as pf_fetch_topk. */
 int pf_op_topk(pf_engine* e, const float* x, int64_t rows, int32_t V, int32_t ld, int32_t K, int64_t* ids, float* val,
@@ -1370,6 +1456,25 @@ int pf_recognizer_set_vad_model(pf_recognizer* r, const char* pfw_path);
    Timestamps entry per word and they are not all the {0, 0} placeholders of a model without timestamps (*has_time), [begin of
    its first word, end of its last] in ms. */
 int pf_recognizer_set_punc_model(pf_recognizer* r, const char* pfw_path);
+/* Speaker labels of every long-audio GetResults that follows (see "Speaker labels"): pfw_path = a `.pfw` of kind "campplus",
+   loaded once and attached to every engine of the pool, present and future; NULL clears.  cfg == NULL: the defaults.  Inert
+   until pf_recognizer_set_vad, and may come before or after it.  GetResults then, behind the segmentation and on the fbank rows
+   it staged (no second fbank), plans the windows of all of the call's streams, embeds them (as many windows per forward as keep the activations within 2 GiB: about
+   1000 windows of 150 frames at the released dimensions), computes one cosine block per stream on the device and clusters each stream on the host.  Text,
+   Tokens, Timestamps, Scores, Segments, Punctuated and Sentences are what they are without it.  pf_group_* and the streaming
+   classes have no such switch.  Errors as pf_spk_model_load; PF_ERR_INVALID_ARG for a cfg outside its ranges or a model whose
+   n_mels is not the front-end's.
+   Of the stream's last long-audio GetResults, valid until its next one (0 / nothing without a model):
+   pf_stream_num_speakers; pf_stream_segment_speaker: the label of segment i (as pf_stream_segment counts them; -1: the stream
+   has no window at all); pf_stream_speaker_centroid: out [cap >= E] = speaker spk's centroid, the L2-normalised mean of its
+   windows' L2-normalised embeddings, for matching against enrolled voices (*E optional; out NULL with cap 0 to learn it);
+   pf_stream_spk_window: window i in ms and its label. */
+int pf_recognizer_set_spk_model(pf_recognizer* r, const char* pfw_path, const pf_spk_config* cfg);
+int pf_stream_num_speakers(pf_stream* s, int32_t* n);
+int pf_stream_segment_speaker(pf_stream* s, int32_t i, int32_t* spk);
+int pf_stream_speaker_centroid(pf_stream* s, int32_t spk, float* out, int32_t cap, int32_t* E);
+int pf_stream_num_spk_windows(pf_stream* s, int32_t* n);
+int pf_stream_spk_window(pf_stream* s, int32_t i, int32_t* begin_ms, int32_t* end_ms, int32_t* label);
 int pf_stream_punctuated(pf_stream* s, const char** text_utf8, const int32_t** punc_ids, int32_t* n_words);
 int pf_stream_num_sentences(pf_stream* s, int32_t* n);
 int pf_stream_sentence(pf_stream* s, int32_t i, int32_t* word_begin, int32_t* word_end, int32_t* has_time, int32_t* begin_ms,
