@@ -507,6 +507,9 @@ class Engine {
   }
   void prof_begin(const char* cls, double flops);
   void prof_end(const char* cls);
+  // a stand-alone op's timed launch loop (engine_ops.cpp): PF_OP_REPEAT launches, class "gemm_op" then "gemm_op_warm"
+  template <class Fn> void op_timed(double flops, Fn launch);
+  void* op_ws(const struct StageCarve& st);                  // ws_tmp_ grown to the carve's size (op_stage.h)
 
   // dither stream: seed of call c = hash(dither_seed, c); an engine built with the same seed replays the same
   // features for the same sequence of front-end calls

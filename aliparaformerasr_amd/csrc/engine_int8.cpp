@@ -17,6 +17,7 @@
 #include <string>
 
 #include "engine.h"
+#include "op_stage.h"
 
 namespace pf {
 
@@ -356,78 +357,74 @@ void Engine::op_qlinear(const float* x, const float* W, const float* bias, int M
   PF_CHECK(x && W && y && M > 0 && N > 0 && K > 0 && K % 4 == 0, PF_ERR_INVALID_ARG, "op_qlinear: bad arguments (K must be a multiple of 4)");
   const int Kp = (int)round_up(K, 128), ldy = (int)round_up(N, 4);
   const int64_t Mp = round_up(M, 256) + 256, Np = round_up(N, 128);
-  size_t off = 0;
-  const Carve carve{off, kAlignQ};
-  const size_t ox = carve((size_t)M * K * 4), ox16 = carve((size_t)M * K * 2), oW = carve((size_t)N * K * 4), ob = carve((size_t)(N + 8) * 4);
-  const size_t oa = carve((size_t)Mp * Kp), ors = carve((size_t)Mp * 4), opar = carve(64), osc = carve(quant_scratch_bytes());
-  const size_t ow = carve((size_t)Np * Kp), ocs = carve((size_t)(N + 8) * 4), ozp = carve((size_t)(N + 8) * 4), ows = carve((size_t)(N + 8) * 4);
-  const size_t oy = carve((size_t)Mp * ldy * 4);
   // bit 1 of x_is_f16: the f16-result kernel (deferred packed epilogue + the result's range for the next quantiser)
   const bool f16_result = (x_is_f16 & 2) != 0;
   x_is_f16 &= 1;
   const int ld16 = (int)round_up(N, 8), Kq = (int)round_up(N, 128);
-  const size_t oy16 = carve((size_t)Mp * ld16 * 2), odz = carve((size_t)(N + 8) * 4), orng = carve(quant_scratch_bytes()), osc2 = carve(quant_scratch_bytes());
-  const size_t oq2 = carve((size_t)Mp * Kq), ors2 = carve((size_t)Mp * 4), opa = carve(64), opb = carve(64);
-  ensure(ws_tmp_, off);
-  char* base = (char*)ws_tmp_.p;
-  PF_HIP(hipMemcpyAsync(base + ox, x, (size_t)M * K * 4, hipMemcpyHostToDevice, stream_));
-  PF_HIP(hipMemcpyAsync(base + oW, W, (size_t)N * K * 4, hipMemcpyHostToDevice, stream_));
-  if (bias) PF_HIP(hipMemcpyAsync(base + ob, bias, (size_t)N * 4, hipMemcpyHostToDevice, stream_));
-  PF_HIP(hipMemsetAsync(base + ow, 0, (size_t)Np * Kp, stream_));
-  PF_HIP(hipMemsetAsync(base + oa, 0, (size_t)Mp * Kp, stream_));
-  launch_quantize_weight(stream_, (const float*)(base + oW), N, K, (int8_t*)(base + ow), Kp, (int32_t*)(base + ocs), (int32_t*)(base + ozp),
-                         (float*)(base + ows));
+  const size_t scratch = quant_scratch_bytes() / 4;
+  StageCarve st{0, kAlignQ};
+  const auto dx = st.take<float>((size_t)M * K);
+  const auto dx16 = st.take<half_t>((size_t)M * K);
+  const auto dW = st.take<float>((size_t)N * K), db = st.take<float>((size_t)N + 8);
+  const auto da = st.take<int8_t>((size_t)Mp * Kp);
+  const auto drs = st.take<int32_t>(Mp);
+  const auto dpar = st.take<float>(16);
+  const auto dsc = st.take<unsigned>(scratch);
+  const auto dw = st.take<int8_t>((size_t)Np * Kp);
+  const auto dcs = st.take<int32_t>((size_t)N + 8), dzp = st.take<int32_t>((size_t)N + 8);
+  const auto dws = st.take<float>((size_t)N + 8), dy = st.take<float>((size_t)Mp * ldy);
+  const auto dy16 = st.take<half_t>((size_t)Mp * ld16);
+  const auto ddz = st.take<int32_t>((size_t)N + 8);
+  const auto drng = st.take<float>(scratch);
+  const auto dsc2 = st.take<unsigned>(scratch);
+  const auto dq2 = st.take<int8_t>((size_t)Mp * Kq);
+  const auto drs2 = st.take<int32_t>(Mp);
+  const auto dpa = st.take<float>(16), dpb = st.take<float>(16);
+  void* ws = op_ws(st);
+  upload(stream_, dx(ws), x, (size_t)M * K);
+  upload(stream_, dW(ws), W, (size_t)N * K);
+  if (bias) upload(stream_, db(ws), bias, N);
+  PF_HIP(hipMemsetAsync(dw(ws), 0, (size_t)Np * Kp, stream_));
+  PF_HIP(hipMemsetAsync(da(ws), 0, (size_t)Mp * Kp, stream_));
+  launch_quantize_weight(stream_, dW(ws), N, K, dw(ws), Kp, dcs(ws), dzp(ws), dws(ws));
   if (x_is_f16) {                                      // the activation arrives as f16 (attention context, FFN hidden): exact widening
-    launch_f32_to_f16(stream_, (const float*)(base + ox), M, K, K, (half_t*)(base + ox16), K);
-    launch_quantize_rows(stream_, nullptr, (const half_t*)(base + ox16), M, K, K, (int8_t*)(base + oa), Kp, (int32_t*)(base + ors),
-                         (float*)(base + opar), (unsigned*)(base + osc));
+    launch_f32_to_f16(stream_, dx(ws), M, K, K, dx16(ws), K);
+    launch_quantize_rows(stream_, nullptr, dx16(ws), M, K, K, da(ws), Kp, drs(ws), dpar(ws), dsc(ws));
   } else {
-    launch_quantize_rows(stream_, (const float*)(base + ox), nullptr, M, K, K, (int8_t*)(base + oa), Kp, (int32_t*)(base + ors),
-                         (float*)(base + opar), (unsigned*)(base + osc));
+    launch_quantize_rows(stream_, dx(ws), nullptr, M, K, K, da(ws), Kp, drs(ws), dpar(ws), dsc(ws));
   }
   GemmI8Args g{};
-  g.A = (int8_t*)(base + oa); g.lda = Kp; g.W = (int8_t*)(base + ow); g.ldw = Kp;
-  g.rowsum = (int32_t*)(base + ors); g.colsum = (int32_t*)(base + ocs); g.wzp = (int32_t*)(base + ozp); g.wscale = (float*)(base + ows);
-  g.aparams = (float*)(base + opar); g.bias = bias ? (const float*)(base + ob) : nullptr;
+  g.A = da(ws); g.lda = Kp; g.W = dw(ws); g.ldw = Kp;
+  g.rowsum = drs(ws); g.colsum = dcs(ws); g.wzp = dzp(ws); g.wscale = dws(ws);
+  g.aparams = dpar(ws); g.bias = bias ? db(ws) : nullptr;
   g.M = M; g.N = N; g.K = K; g.Kpad = Kp; g.relu = relu;
   float pa[2] = {0, 0}, pb[2] = {1, 1};
-  std::vector<uint16_t> y16;
   if (f16_result) {
-    launch_pack_dz(stream_, g.colsum, g.wzp, N, K, (int32_t*)(base + odz));
-    g.out_f16 = (half_t*)(base + oy16); g.ldc16 = ld16; g.dz = (int32_t*)(base + odz); g.out_padded = 1; g.range_out = (float*)(base + orng);
+    launch_pack_dz(stream_, g.colsum, g.wzp, N, K, ddz(ws));
+    g.out_f16 = dy16(ws); g.ldc16 = ld16; g.dz = ddz(ws); g.out_padded = 1; g.range_out = drng(ws);
     launch_gemm_i8(stream_, g);
     PF_CHECK(std::strncmp(last_gemm_kernel(), "gemm_i8f", 8) == 0, PF_ERR_DEVICE, "op_qlinear: the f16-result kernel was not selected");
     // the range the kernel reports must be the range a min / max pass over its output finds: quantise the output both ways
-    launch_quantize(stream_, nullptr, (const half_t*)(base + oy16), M, N, ld16, (int8_t*)(base + oq2), Kq, (int32_t*)(base + ors2),
-                    (float*)(base + opa), (const float*)(base + orng));
-    launch_quantize_rows(stream_, nullptr, (const half_t*)(base + oy16), M, N, ld16, (int8_t*)(base + oq2), Kq, (int32_t*)(base + ors2),
-                         (float*)(base + opb), (unsigned*)(base + osc2));
-    PF_HIP(hipMemcpyAsync(pa, base + opa, 8, hipMemcpyDeviceToHost, stream_));
-    PF_HIP(hipMemcpyAsync(pb, base + opb, 8, hipMemcpyDeviceToHost, stream_));
-    y16.resize((size_t)M * ld16);
-    PF_HIP(hipMemcpyAsync(y16.data(), base + oy16, y16.size() * 2, hipMemcpyDeviceToHost, stream_));
+    launch_quantize(stream_, nullptr, dy16(ws), M, N, ld16, dq2(ws), Kq, drs2(ws), dpa(ws), drng(ws));
+    launch_quantize_rows(stream_, nullptr, dy16(ws), M, N, ld16, dq2(ws), Kq, drs2(ws), dpb(ws), dsc2(ws));
+    download(stream_, pa, (const float*)dpa(ws), 2);
+    download(stream_, pb, (const float*)dpb(ws), 2);
+    download_f16(stream_, y, dy16(ws), M, N, ld16);
   } else {
-    g.out_f32 = (float*)(base + oy); g.ldc32 = ldy;
+    g.out_f32 = dy(ws); g.ldc32 = ldy;
     launch_gemm_i8(stream_, g);
-    PF_HIP(hipMemcpy2DAsync(y, (size_t)N * 4, base + oy, (size_t)ldy * 4, (size_t)N * 4, M, hipMemcpyDeviceToHost, stream_));
+    download2d(stream_, y, N, (const float*)dy(ws), ldy, N, M);
   }
   std::vector<int8_t> aq, wq;
   std::vector<int32_t> zp((size_t)N);
-  if (xq_out) { aq.resize((size_t)M * Kp); PF_HIP(hipMemcpyAsync(aq.data(), base + oa, aq.size(), hipMemcpyDeviceToHost, stream_)); }
-  if (wq_out) { wq.resize((size_t)N * Kp); PF_HIP(hipMemcpyAsync(wq.data(), base + ow, wq.size(), hipMemcpyDeviceToHost, stream_)); }
-  if (aparams_out) PF_HIP(hipMemcpyAsync(aparams_out, base + opar, 8, hipMemcpyDeviceToHost, stream_));
-  if (wscale_out) PF_HIP(hipMemcpyAsync(wscale_out, base + ows, (size_t)N * 4, hipMemcpyDeviceToHost, stream_));
-  if (wzp_out) PF_HIP(hipMemcpyAsync(zp.data(), base + ozp, (size_t)N * 4, hipMemcpyDeviceToHost, stream_));
+  if (xq_out) { aq.resize((size_t)M * Kp); download(stream_, aq.data(), (const int8_t*)da(ws), aq.size()); }
+  if (wq_out) { wq.resize((size_t)N * Kp); download(stream_, wq.data(), (const int8_t*)dw(ws), wq.size()); }
+  if (aparams_out) download(stream_, aparams_out, (const float*)dpar(ws), 2);
+  if (wscale_out) download(stream_, wscale_out, (const float*)dws(ws), N);
+  if (wzp_out) download(stream_, zp.data(), (const int32_t*)dzp(ws), N);
   PF_HIP(hipStreamSynchronize(stream_));
   PF_CHECK(!f16_result || (pa[0] == pb[0] && pa[1] == pb[1]), PF_ERR_DEVICE,
            "op_qlinear: the range reported by the GEMM epilogue differs from a min / max pass over its output");
-  if (f16_result)
-    for (int m = 0; m < M; ++m)
-      for (int n = 0; n < N; ++n) {
-        half_t h;
-        std::memcpy(&h, &y16[(size_t)m * ld16 + n], 2);
-        y[(size_t)m * N + n] = (float)h;
-      }
   if (xq_out)
     for (int m = 0; m < M; ++m)
       for (int k = 0; k < K; ++k) xq_out[(size_t)m * K + k] = (uint8_t)((int)aq[(size_t)m * Kp + k] + 128);
@@ -444,55 +441,13 @@ void Engine::op_qlinear(const float* x, const float* W, const float* bias, int M
 // every output sits in a sentinel-filled buffer: a result cell must come back written, every other cell with its sentinel.
 // A byte has no value a code cannot take, so the byte outputs run twice, on two sentinels: an unwritten cell holds both.
 namespace {
-constexpr uint32_t kSent32 = 0x7FC5A5A5u;                     // a NaN payload as a float; as an int32 no row / column sum or dz word
-constexpr uint16_t kSent16 = 0x7E5Au;
-constexpr uint8_t kSent8[2] = {0x5A, 0xA5};
 constexpr int kTail = 136;                                    // hostile cells behind a vector (more than one wave tile of columns)
-
-inline float hostile32(size_t i) { return std::ldexp(1.0f + (float)((i * 37u) & 0x3FFu) / 1024.0f, 100) * ((i & 1u) ? -1.0f : 1.0f); }
-inline half_t hostile16(size_t i) {                           // +-32768 .. +-65504
-  const uint16_t bits = (uint16_t)(0x7800u | (uint16_t)((i * 37u) & 0x3FFu) | (uint16_t)((i & 1u) << 15));
-  half_t h;
-  std::memcpy(&h, &bits, 2);
-  return h;
-}
-inline int32_t hostile_i32(size_t i) { return ((i & 1u) ? -1 : 1) * ((1 << 30) + (int32_t)((i * 37u) & 0xFFFFu)); }
 inline float quiet_nan() { return std::nanf(""); }
-
-template <class U>
-void upload(hipStream_t s, void* dev, const std::vector<U>& h) {
-  PF_HIP(hipMemcpyAsync(dev, h.data(), h.size() * sizeof(U), hipMemcpyHostToDevice, s));
-  PF_HIP(hipStreamSynchronize(s));
-}
-// A [rows, ld] buffer that held `before` at the launch, downloaded into `after`: outside [0, guard) x [0, N) every cell keeps its
-// bits; inside [0, M) x [0, N) (must_write) no cell holds the sentinel any more.  Vectors: ld = 1, N = 1.
-template <class U>
-void check_region(hipStream_t s, const std::string& what, const void* dev, const std::vector<U>& before, std::vector<U>& after, U sentinel,
-                  int64_t rows, int64_t ld, int64_t M, int64_t N, int64_t guard, bool must_write) {
-  after.resize(before.size());
-  PF_HIP(hipMemcpyAsync(after.data(), dev, after.size() * sizeof(U), hipMemcpyDeviceToHost, s));
-  PF_HIP(hipStreamSynchronize(s));
-  for (int64_t m = 0; m < rows; ++m)
-    for (int64_t n = 0; n < ld; ++n) {
-      const size_t i = (size_t)(m * ld + n);
-      const char* why = nullptr;
-      if (m < M && n < N) { if (must_write && after[i] == sentinel) why = "was not written"; }
-      else if ((n >= N || m >= guard) && after[i] != before[i]) why = n >= N ? "was written: a column the contract (kernels.h) calls never written"
-                                                                            : "was written: a row the contract (kernels.h) calls never written";
-      if (why)
-        throw Error(PF_ERR_DEVICE, what + " (" + std::to_string(M) + " x " + std::to_string(N) + ", ld " + std::to_string(ld) + "): cell (" +
-                                       std::to_string(m) + ", " + std::to_string(n) + ") " + why);
-    }
-}
-// the two runs of a byte output: a cell of [0, M) x [0, N) that holds its sentinel after both was written by neither
+// `n` sentinel words of which the first `m` must come back written and the rest untouched
+inline GuardGeom vector_geom(int64_t n, int64_t m) { return GuardGeom{n, 1, m, 1, m, false, true}; }
 void check_bytes_written(const std::string& what, const std::vector<uint8_t>& a0, const std::vector<uint8_t>& a1, int64_t ld, int64_t M, int64_t N) {
-  for (int64_t m = 0; m < M; ++m)
-    for (int64_t n = 0; n < N; ++n) {
-      const size_t i = (size_t)(m * ld + n);
-      if (a0[i] == kSent8[0] && a1[i] == kSent8[1])
-        throw Error(PF_ERR_DEVICE, what + ": cell (" + std::to_string(m) + ", " + std::to_string(n) + ") was not written");
-      if (a0[i] != a1[i]) throw Error(PF_ERR_DEVICE, what + ": cell (" + std::to_string(m) + ", " + std::to_string(n) + ") differs between two runs");
-    }
+  if (const GuardHit hit = bytes_written_scan(a0.data(), a1.data(), ld, M, N))
+    throw Error(PF_ERR_DEVICE, guard_message(what, GuardGeom{M, ld, M, N, M, false, true}, hit));
 }
 }  // namespace
 
@@ -504,57 +459,56 @@ void Engine::op_quantize(const float* x, int rows, int cols, int ldx, int x_is_f
            PF_ERR_INVALID_ARG, "op_quantize: cols, ldx and ld must be multiples of 4, ldx and ld at least cols");
   PF_CHECK(!ln || (gamma && beta && !x_is_f16 && ldx == cols), PF_ERR_INVALID_ARG, "op_quantize: LayerNorm rows are dense fp32 and need gamma and beta");
   const int64_t xr = rows + 8, orows = rows + 8;               // hostile rows behind x, guard rows behind the outputs
-  const size_t esz = x_is_f16 ? 2 : 4, part_words = quant_scratch_bytes() / 4;
-  size_t off = 0;
-  const Carve carve{off, kAlignQ};
-  const size_t ox = carve((size_t)xr * ldx * esz), og = carve((size_t)(cols + kTail) * 4), ob = carve((size_t)(cols + kTail) * 4);
-  const size_t oo = carve((size_t)orows * ld), ors = carve((size_t)orows * 4), opar = carve(64), opart = carve((part_words + 64) * 4);
-  ensure(ws_tmp_, off);
-  char* base = (char*)ws_tmp_.p;
+  const size_t part_words = quant_scratch_bytes() / 4;
+  StageCarve st{0, kAlignQ};
+  const auto dx = st.take<uint8_t>((size_t)xr * ldx * (x_is_f16 ? 2 : 4));     // (f16 or fp32)
+  const auto dg = st.take<float>((size_t)cols + kTail), db = st.take<float>((size_t)cols + kTail);
+  const auto dout = st.take<uint8_t>((size_t)orows * ld);
+  const auto drs = st.take<uint32_t>(orows), dpar = st.take<uint32_t>(16), dpart = st.take<uint32_t>(part_words + 64);
+  void* ws = op_ws(st);
+  const float* x32 = x_is_f16 ? nullptr : (const float*)dx(ws);
+  const half_t* x16 = x_is_f16 ? (const half_t*)dx(ws) : nullptr;
   // x: the tensor inside [rows, cols], the large finite pattern in the pad columns and in the rows behind it
   if (x_is_f16) {
     std::vector<half_t> h((size_t)xr * ldx);
     for (int64_t r = 0; r < xr; ++r)
       for (int c = 0; c < ldx; ++c) h[(size_t)r * ldx + c] = r < rows && c < cols ? (half_t)x[(size_t)r * cols + c] : hostile16((size_t)r * 131 + c);
-    upload(stream_, base + ox, h);
+    upload_sync(stream_, (half_t*)dx(ws), h);
   } else {
     std::vector<float> h((size_t)xr * ldx);
     for (int64_t r = 0; r < xr; ++r)
       for (int c = 0; c < ldx; ++c) h[(size_t)r * ldx + c] = r < rows && c < cols ? x[(size_t)r * cols + c] : hostile32((size_t)r * 131 + c);
-    upload(stream_, base + ox, h);
+    upload_sync(stream_, (float*)dx(ws), h);
   }
   if (ln) {
     std::vector<float> g((size_t)cols + kTail, quiet_nan()), b((size_t)cols + kTail, quiet_nan());
     std::copy(gamma, gamma + cols, g.begin());
     std::copy(beta, beta + cols, b.begin());
-    upload(stream_, base + og, g);
-    upload(stream_, base + ob, b);
+    upload_sync(stream_, dg(ws), g);
+    upload_sync(stream_, db(ws), b);
   }
-  const std::vector<uint32_t> rs0((size_t)orows, kSent32), par0(16, kSent32), part0(part_words + 64, kSent32);
-  std::vector<uint32_t> rs1, par1, part1;
+  const std::vector<uint32_t> rs0((size_t)orows, kSentinel32), par0(16, kSentinel32), part0(part_words + 64, kSentinel32);
+  std::vector<uint32_t> rs1, par1;
   std::vector<uint8_t> out1[2];
   for (int run = 0; run < 2; ++run) {
-    const std::vector<uint8_t> out0((size_t)orows * ld, kSent8[run]);
-    upload(stream_, base + oo, out0);
-    upload(stream_, base + ors, rs0);
-    upload(stream_, base + opar, par0);
-    upload(stream_, base + opart, part0);
-    float* part = (float*)(base + opart);
+    const std::vector<uint8_t> out0((size_t)orows * ld, kSentinel8[run]);
+    upload_sync(stream_, dout(ws), out0);
+    upload_sync(stream_, drs(ws), rs0);
+    upload_sync(stream_, dpar(ws), par0);
+    upload_sync(stream_, dpart(ws), part0);
+    int8_t* codes = (int8_t*)dout(ws); int32_t* rowsum = (int32_t*)drs(ws);
+    float* par = (float*)dpar(ws); float* part = (float*)dpart(ws);
     if (ln) {
-      launch_ln_minmax(stream_, (const float*)(base + ox), rows, cols, (const float*)(base + og), (const float*)(base + ob), part);
-      launch_ln_quantize(stream_, (const float*)(base + ox), rows, cols, (const float*)(base + og), (const float*)(base + ob), (int8_t*)(base + oo), ld,
-                         (int32_t*)(base + ors), (float*)(base + opar), part);
+      launch_ln_minmax(stream_, x32, rows, cols, dg(ws), db(ws), part);
+      launch_ln_quantize(stream_, x32, rows, cols, dg(ws), db(ws), codes, ld, rowsum, par, part);
     } else {
-      const float* x32 = x_is_f16 ? nullptr : (const float*)(base + ox);
-      const half_t* x16 = x_is_f16 ? (const half_t*)(base + ox) : nullptr;
       launch_minmax(stream_, x32, x16, rows, cols, ldx, part);
-      launch_quantize(stream_, x32, x16, rows, cols, ldx, (int8_t*)(base + oo), ld, (int32_t*)(base + ors), (float*)(base + opar), part);
+      launch_quantize(stream_, x32, x16, rows, cols, ldx, codes, ld, rowsum, par, part);
     }
-    check_region<uint8_t>(stream_, "op_quantize: the codes", base + oo, out0, out1[run], kSent8[run], orows, ld, rows, ld, rows, false);
-    check_region<uint32_t>(stream_, "op_quantize: rowsum", base + ors, rs0, rs1, kSent32, orows, 1, rows, 1, rows, true);
-    check_region<uint32_t>(stream_, "op_quantize: params", base + opar, par0, par1, kSent32, 16, 1, 2, 1, 2, true);
-    check_region<uint32_t>(stream_, "op_quantize: the {min, max} pairs", base + opart, part0, part1, kSent32, (int64_t)part_words + 64, 1,
-                           (int64_t)part_words, 1, (int64_t)part_words, true);
+    out1[run] = check_guard(stream_, "op_quantize: the codes", codes, kSentinel8[run], GuardGeom{orows, ld, rows, ld, rows, false, false}, &out0);
+    rs1 = check_guard(stream_, "op_quantize: rowsum", rowsum, kSentinel32, vector_geom(orows, rows), &rs0);
+    par1 = check_guard(stream_, "op_quantize: params", par, kSentinel32, vector_geom(16, 2), &par0);
+    check_guard(stream_, "op_quantize: the {min, max} pairs", part, kSentinel32, vector_geom((int64_t)part_words + 64, (int64_t)part_words), &part0);
   }
   check_bytes_written("op_quantize: the codes", out1[0], out1[1], ld, rows, ld);
   std::memcpy(codes_out, out1[1].data(), (size_t)rows * ld);
@@ -567,54 +521,52 @@ void Engine::op_weight(const float* W, const uint8_t* Q, const uint8_t* zp, cons
   PF_HIP(hipSetDevice(device_));
   PF_CHECK((W || (Q && zp && scale)) && w_out && colsum_out && wzp_out && wscale_out && dz_out && N > 0 && K > 0 && ld >= K, PF_ERR_INVALID_ARG,
            "op_quantize_weight / op_import_weight: bad arguments (ld >= K)");
-  const char* op = Q ? "op_import_weight" : "op_quantize_weight";
+  const std::string op = Q ? "op_import_weight" : "op_quantize_weight";
   const int64_t wr = N + 4, orows = N + 4, vn = N + kTail;
-  size_t off = 0;
-  const Carve carve{off, kAlignQ};
-  const size_t oW = carve((size_t)wr * K * 4), oQ = carve((size_t)wr * K), ozq = carve((size_t)vn), osq = carve((size_t)vn * 4);
-  const size_t oo = carve((size_t)orows * ld), ocs = carve((size_t)vn * 4), ozp = carve((size_t)vn * 4), ows = carve((size_t)vn * 4), odz = carve((size_t)vn * 4);
-  ensure(ws_tmp_, off);
-  char* base = (char*)ws_tmp_.p;
+  StageCarve st{0, kAlignQ};
+  const auto dW = st.take<float>((size_t)wr * K);
+  const auto dQ = st.take<uint8_t>((size_t)wr * K), dzq = st.take<uint8_t>(vn);
+  const auto dsq = st.take<float>(vn);
+  const auto dout = st.take<uint8_t>((size_t)orows * ld);
+  const Field<uint32_t> dvec[4] = {st.take<uint32_t>(vn), st.take<uint32_t>(vn), st.take<uint32_t>(vn), st.take<uint32_t>(vn)};   // colsum, wzp, wscale, dz
+  static const char* const vec_name[4] = {": colsum", ": wzp", ": wscale", ": dz"};
+  void* ws = op_ws(st);
   if (Q) {                                                     // the rows and vector cells behind N: the largest bytes, NaN scales
     std::vector<uint8_t> q((size_t)wr * K, 255), z((size_t)vn, 255);
     std::vector<float> sc((size_t)vn, quiet_nan());
     std::copy(Q, Q + (size_t)N * K, q.begin());
     std::copy(zp, zp + N, z.begin());
     std::copy(scale, scale + N, sc.begin());
-    upload(stream_, base + oQ, q);
-    upload(stream_, base + ozq, z);
-    upload(stream_, base + osq, sc);
+    upload_sync(stream_, dQ(ws), q);
+    upload_sync(stream_, dzq(ws), z);
+    upload_sync(stream_, dsq(ws), sc);
   } else {
     std::vector<float> w((size_t)wr * K);
     for (size_t i = 0; i < w.size(); ++i) w[i] = i < (size_t)N * K ? W[i] : hostile32(i);
-    upload(stream_, base + oW, w);
+    upload_sync(stream_, dW(ws), w);
   }
-  const std::vector<uint32_t> v0((size_t)vn, kSent32);
-  std::vector<uint32_t> cs1, zp1, ws1, dz1;
+  const std::vector<uint32_t> v0((size_t)vn, kSentinel32);
+  std::vector<uint32_t> vec1[4];
   std::vector<uint8_t> out1[2];
   for (int run = 0; run < 2; ++run) {
-    const std::vector<uint8_t> out0((size_t)orows * ld, kSent8[run]);
-    upload(stream_, base + oo, out0);
-    for (size_t o : {ocs, ozp, ows, odz}) upload(stream_, base + o, v0);
-    if (Q)
-      launch_import_weight(stream_, (const uint8_t*)(base + oQ), (const uint8_t*)(base + ozq), (const float*)(base + osq), N, K, (int8_t*)(base + oo), ld,
-                           (int32_t*)(base + ocs), (int32_t*)(base + ozp), (float*)(base + ows));
-    else
-      launch_quantize_weight(stream_, (const float*)(base + oW), N, K, (int8_t*)(base + oo), ld, (int32_t*)(base + ocs), (int32_t*)(base + ozp),
-                             (float*)(base + ows));
-    launch_pack_dz(stream_, (const int32_t*)(base + ocs), (const int32_t*)(base + ozp), N, K, (int32_t*)(base + odz));
-    check_region<uint8_t>(stream_, std::string(op) + ": w'", base + oo, out0, out1[run], kSent8[run], orows, ld, N, ld, N, false);
-    check_region<uint32_t>(stream_, std::string(op) + ": colsum", base + ocs, v0, cs1, kSent32, vn, 1, N, 1, N, true);
-    check_region<uint32_t>(stream_, std::string(op) + ": wzp", base + ozp, v0, zp1, kSent32, vn, 1, N, 1, N, true);
-    check_region<uint32_t>(stream_, std::string(op) + ": wscale", base + ows, v0, ws1, kSent32, vn, 1, N, 1, N, true);
-    check_region<uint32_t>(stream_, std::string(op) + ": dz", base + odz, v0, dz1, kSent32, vn, 1, N, 1, N, true);
+    const std::vector<uint8_t> out0((size_t)orows * ld, kSentinel8[run]);
+    upload_sync(stream_, dout(ws), out0);
+    for (const Field<uint32_t>& f : dvec) upload_sync(stream_, f(ws), v0);
+    int8_t* codes = (int8_t*)dout(ws);
+    int32_t* cs = (int32_t*)dvec[0](ws);
+    int32_t* wz = (int32_t*)dvec[1](ws);
+    if (Q) launch_import_weight(stream_, dQ(ws), dzq(ws), dsq(ws), N, K, codes, ld, cs, wz, (float*)dvec[2](ws));
+    else launch_quantize_weight(stream_, dW(ws), N, K, codes, ld, cs, wz, (float*)dvec[2](ws));
+    launch_pack_dz(stream_, cs, wz, N, K, (int32_t*)dvec[3](ws));
+    out1[run] = check_guard(stream_, op + ": w'", codes, kSentinel8[run], GuardGeom{orows, ld, N, ld, N, false, false}, &out0);
+    for (int i = 0; i < 4; ++i) vec1[i] = check_guard(stream_, op + vec_name[i], dvec[i](ws), kSentinel32, vector_geom(vn, N), &v0);
   }
-  check_bytes_written(std::string(op) + ": w'", out1[0], out1[1], ld, N, ld);
+  check_bytes_written(op + ": w'", out1[0], out1[1], ld, N, ld);
   std::memcpy(w_out, out1[1].data(), (size_t)N * ld);
-  std::memcpy(colsum_out, cs1.data(), (size_t)N * 4);
-  std::memcpy(wzp_out, zp1.data(), (size_t)N * 4);
-  std::memcpy(wscale_out, ws1.data(), (size_t)N * 4);
-  std::memcpy(dz_out, dz1.data(), (size_t)N * 4);
+  std::memcpy(colsum_out, vec1[0].data(), (size_t)N * 4);
+  std::memcpy(wzp_out, vec1[1].data(), (size_t)N * 4);
+  std::memcpy(wscale_out, vec1[2].data(), (size_t)N * 4);
+  std::memcpy(dz_out, vec1[3].data(), (size_t)N * 4);
 }
 
 void Engine::op_qgemm_ex(const pf_qgemm_desc& ds, const uint8_t* a_codes, const uint8_t* w_codes, float* y32, float* y16, float* range_out) {
@@ -631,14 +583,15 @@ void Engine::op_qgemm_ex(const pf_qgemm_desc& ds, const uint8_t* a_codes, const 
   const int64_t Mp = round_up(M, 256), Np = round_up(N, 128), Mo = Mp + 128, vn = N + kTail;
   const int ld32 = (int)round_up(N, 4) + 4, ld16 = kind == 1 ? (int)round_up(N, 8) + 8 : (int)round_up(N, 4) + 4;
   const size_t part_words = quant_scratch_bytes() / 4;
-  size_t off = 0;
-  const Carve carve{off, kAlignQ};
-  const size_t oa = carve((size_t)Mp * Kp), ow = carve((size_t)Np * Kp), ors = carve((size_t)Mp * 4), opar = carve(64);
-  const size_t ocs = carve((size_t)vn * 4), ozp = carve((size_t)vn * 4), odz = carve((size_t)vn * 4), ows = carve((size_t)vn * 4), ob = carve((size_t)vn * 4);
-  const size_t o32 = carve((size_t)Mo * ld32 * 4), o16 = carve((size_t)Mo * ld16 * 2), oR = carve((size_t)Mo * ld32 * 4), oD = carve((size_t)Mo * ld32 * 4);
-  const size_t opart = carve((part_words + 64) * 4);
-  ensure(ws_tmp_, off);
-  char* base = (char*)ws_tmp_.p;
+  StageCarve st{0, kAlignQ};
+  const auto da = st.take<int8_t>((size_t)Mp * Kp), dw = st.take<int8_t>((size_t)Np * Kp);
+  const auto drs = st.take<int32_t>(Mp); const auto dpar = st.take<float>(16);
+  const auto dcs = st.take<int32_t>(vn), dzp = st.take<int32_t>(vn), ddz = st.take<int32_t>(vn);
+  const auto dwsc = st.take<float>(vn), db = st.take<float>(vn);
+  const auto d32 = st.take<uint32_t>((size_t)Mo * ld32); const auto d16 = st.take<uint16_t>((size_t)Mo * ld16);
+  const auto dR = st.take<float>((size_t)Mo * ld32), dD = st.take<float>((size_t)Mo * ld32);
+  const auto dpart = st.take<uint32_t>(part_words + 64);
+  void* ws = op_ws(st);
   // a', w' with their sums and dz, on the host; pad columns 0 (the contract), pad rows the largest codes of both signs
   std::vector<int8_t> a((size_t)Mp * Kp, 0), w((size_t)Np * Kp, 0);
   std::vector<int32_t> rs((size_t)Mp), cs((size_t)vn), wz((size_t)vn), dz((size_t)vn);
@@ -668,46 +621,45 @@ void Engine::op_qgemm_ex(const pf_qgemm_desc& ds, const uint8_t* a_codes, const 
   }
   PF_CHECK(kind != 1 || K <= 16384, PF_ERR_UNSUPPORTED, "qgemm_ex: K too large for the packed column word");
   const float par[16] = {ds.a_scale, (float)ds.a_zp, quiet_nan(), quiet_nan()};
-  upload(stream_, base + oa, a);
-  upload(stream_, base + ow, w);
-  upload(stream_, base + ors, rs);
-  upload(stream_, base + ocs, cs);
-  upload(stream_, base + ozp, wz);
-  upload(stream_, base + odz, dz);
-  upload(stream_, base + ows, wsc);
-  upload(stream_, base + ob, bias);
-  PF_HIP(hipMemcpyAsync(base + opar, par, sizeof(par), hipMemcpyHostToDevice, stream_));
+  upload_sync(stream_, da(ws), a);
+  upload_sync(stream_, dw(ws), w);
+  upload_sync(stream_, drs(ws), rs);
+  upload_sync(stream_, dcs(ws), cs);
+  upload_sync(stream_, dzp(ws), wz);
+  upload_sync(stream_, ddz(ws), dz);
+  upload_sync(stream_, dwsc(ws), wsc);
+  upload_sync(stream_, db(ws), bias);
+  upload(stream_, dpar(ws), par, 16);
   // results: sentinels; a residual aliases the fp32 result where there is one (its cells of [M, N] hold the residual)
-  std::vector<uint32_t> c32((size_t)Mo * ld32, kSent32), after32;
-  std::vector<uint16_t> c16((size_t)Mo * ld16, kSent16), after16;
-  const std::vector<uint32_t> part0(part_words + 64, kSent32);
-  std::vector<uint32_t> part1;
-  auto pad32 = [&](const float* src, size_t dst_off, bool hostile) {       // [M, N] into [Mo, ld32]
+  std::vector<uint32_t> c32((size_t)Mo * ld32, kSentinel32), after32;
+  std::vector<uint16_t> c16((size_t)Mo * ld16, kSentinel16), after16;
+  const std::vector<uint32_t> part0(part_words + 64, kSentinel32);
+  auto pad32 = [&](const float* src, float* dst) {                       // [M, N] into [Mo, ld32], hostile around it
     std::vector<float> h((size_t)Mo * ld32);
     for (int64_t m = 0; m < Mo; ++m)
-      for (int n = 0; n < ld32; ++n) h[(size_t)m * ld32 + n] = m < M && n < N ? src[(size_t)m * N + n] : (hostile ? hostile32((size_t)m * 131 + n) : 0.f);
-    upload(stream_, base + dst_off, h);
+      for (int n = 0; n < ld32; ++n) h[(size_t)m * ld32 + n] = m < M && n < N ? src[(size_t)m * N + n] : hostile32((size_t)m * 131 + n);
+    upload_sync(stream_, dst, h);
   };
   const bool alias = has32 && ds.resid;
   if (alias)
     for (int m = 0; m < M; ++m) std::memcpy(&c32[(size_t)m * ld32], ds.resid + (size_t)m * N, (size_t)N * 4);
-  else if (ds.resid) pad32(ds.resid, oR, true);
-  if (ds.add2) pad32(ds.add2, oD, true);
-  if (has32) upload(stream_, base + o32, c32);
-  if (has16) upload(stream_, base + o16, c16);
-  upload(stream_, base + opart, part0);
+  else if (ds.resid) pad32(ds.resid, dR(ws));
+  if (ds.add2) pad32(ds.add2, dD(ws));
+  if (has32) upload_sync(stream_, d32(ws), c32);
+  if (has16) upload_sync(stream_, d16(ws), c16);
+  upload_sync(stream_, dpart(ws), part0);
   GemmI8Args g{};
-  g.A = (int8_t*)(base + oa); g.lda = Kp; g.W = (int8_t*)(base + ow); g.ldw = Kp;
-  g.rowsum = (int32_t*)(base + ors); g.colsum = (int32_t*)(base + ocs); g.wzp = (int32_t*)(base + ozp); g.wscale = (float*)(base + ows);
-  g.aparams = (float*)(base + opar); g.bias = ds.bias ? (const float*)(base + ob) : nullptr;
+  g.A = da(ws); g.lda = Kp; g.W = dw(ws); g.ldw = Kp;
+  g.rowsum = drs(ws); g.colsum = dcs(ws); g.wzp = dzp(ws); g.wscale = dwsc(ws);
+  g.aparams = dpar(ws); g.bias = ds.bias ? db(ws) : nullptr;
   g.M = M; g.N = N; g.K = K; g.Kpad = Kp;
   g.relu = ds.relu ? 1 : 0; g.scale_cols = ds.scale_cols; g.scale = ds.scale;
-  if (has32) { g.out_f32 = (float*)(base + o32); g.ldc32 = ld32; }
-  if (has16) { g.out_f16 = (half_t*)(base + o16); g.ldc16 = ld16; }
-  if (ds.resid) { g.resid = alias ? (const float*)(base + o32) : (const float*)(base + oR); g.ldr = ld32; }
-  if (ds.add2) { g.add2 = (const float*)(base + oD); g.ld2 = ld32; }
-  if (kind == 1) { g.dz = (int32_t*)(base + odz); g.out_padded = 1; }
-  if (ds.want_range) g.range_out = (float*)(base + opart);
+  if (has32) { g.out_f32 = (float*)d32(ws); g.ldc32 = ld32; }
+  if (has16) { g.out_f16 = (half_t*)d16(ws); g.ldc16 = ld16; }
+  if (ds.resid) { g.resid = alias ? (const float*)d32(ws) : dR(ws); g.ldr = ld32; }
+  if (ds.add2) { g.add2 = dD(ws); g.ld2 = ld32; }
+  if (kind == 1) { g.dz = ddz(ws); g.out_padded = 1; }
+  if (ds.want_range) g.range_out = (float*)dpart(ws);
   g.force_mi = ds.tile_rows == 128 ? 1 : (ds.tile_rows == 256 ? 2 : 0);
   prof_begin("gemm_op", 2.0 * M * (double)N * K);
   try {
@@ -720,10 +672,10 @@ void Engine::op_qgemm_ex(const pf_qgemm_desc& ds, const uint8_t* a_codes, const 
   PF_CHECK(std::strncmp(last_gemm_kernel(), kind == 1 ? "gemm_i8f_pp3" : "gemm_i8_pp3", kind == 1 ? 12 : 11) == 0, PF_ERR_DEVICE,
            "qgemm_ex: the result kind ran on another kernel than kernels.h names for it");
   const std::string tag = std::string("qgemm_ex [") + last_gemm_kernel() + "]: ";
-  if (has32) check_region<uint32_t>(stream_, tag + "the fp32 result", base + o32, c32, after32, kSent32, Mo, ld32, M, N, M, !alias);
-  if (has16) check_region<uint16_t>(stream_, tag + "the f16 result", base + o16, c16, after16, kSent16, Mo, ld16, M, N, kind == 1 ? Mp : M, true);
-  check_region<uint32_t>(stream_, tag + "the {min, max} pairs", base + opart, part0, part1, kSent32, (int64_t)part_words + 64, 1,
-                         ds.want_range ? (int64_t)part_words : 0, 1, ds.want_range ? (int64_t)part_words : 0, true);
+  const int64_t pw = ds.want_range ? (int64_t)part_words : 0;
+  if (has32) after32 = check_guard(stream_, tag + "the fp32 result", d32(ws), kSentinel32, GuardGeom{Mo, ld32, M, N, M, false, !alias}, &c32);
+  if (has16) after16 = check_guard(stream_, tag + "the f16 result", d16(ws), kSentinel16, GuardGeom{Mo, ld16, M, N, kind == 1 ? Mp : M, false, true}, &c16);
+  const std::vector<uint32_t> part1 = check_guard(stream_, tag + "the {min, max} pairs", dpart(ws), kSentinel32, vector_geom((int64_t)part_words + 64, pw), &part0);
   if (has32)
     for (int m = 0; m < M; ++m) std::memcpy(y32 + (size_t)m * N, &after32[(size_t)m * ld32], (size_t)N * 4);
   if (has16)
@@ -747,3 +699,4 @@ void Engine::op_qgemm_ex(const pf_qgemm_desc& ds, const uint8_t* a_codes, const 
 }
 
 }  // namespace pf
+

@@ -10,6 +10,7 @@
 #include <set>
 
 #include "hostutil.h"
+#include "op_stage.h"
 
 namespace pf {
 
@@ -22,80 +23,26 @@ namespace pf {
 // for their kernels: no store at or beyond row M (round_up(M, 64) for the blocked Q | K and V of the encoder tail), the fp32
 // residual's rows behind M - 1 hostile as well, sentinel bytes behind the split form's workspace.
 namespace {
-constexpr uint32_t kSentinel32 = 0x7FC5A5A5u;
-constexpr uint16_t kSentinel16 = 0x7E5Au;
 constexpr int kVLead = 64;                                    // rows in front of the V slice of the FSMN ops
-
-inline half_t hostile16(size_t i) {                           // +-32768 .. +-65504, never the same in neighbouring cells
-  const uint16_t bits = (uint16_t)(0x7800u | (uint16_t)((i * 37u) & 0x3FFu) | (uint16_t)((i & 1u) << 15));
-  half_t h;
-  std::memcpy(&h, &bits, 2);
-  return h;
-}
-
-// rows [row0, row1) of a row-major f16 matrix: columns [0, cols) hostile, [cols, ld) zero
-void fill_hostile_rows(hipStream_t s, half_t* base, int ld, int64_t row0, int64_t row1, int cols) {
-  if (row1 <= row0) return;
-  std::vector<half_t> h((size_t)(row1 - row0) * ld, (half_t)0.f);
-  for (int64_t r = 0; r < row1 - row0; ++r)
-    for (int c = 0; c < cols; ++c) h[(size_t)r * ld + c] = hostile16((size_t)(row0 + r) * 131 + c);
-  PF_HIP(hipMemcpyAsync(base + (size_t)row0 * ld, h.data(), h.size() * 2, hipMemcpyHostToDevice, s));
-  PF_HIP(hipStreamSynchronize(s));
-}
-// the same rows of a host image in the blocked activation layout (Kp columns, the first K of them hostile)
-void fill_hostile_blocked(std::vector<half_t>& img, int64_t row0, int64_t row1, int K, int Kp) {
-  for (int64_t m = row0; m < row1; ++m)
-    for (int k = 0; k < K; ++k)
-      img[(((size_t)(m >> 5) * (Kp >> 3) + (k >> 3)) * 32 + (m & 31)) * 8 + (k & 7)] = hostile16((size_t)m * 131 + k);
-}
-void fill_sentinel32(hipStream_t s, void* p, size_t count) { PF_HIP(hipMemsetD32Async((hipDeviceptr_t)p, (int)kSentinel32, count, s)); }
-void fill_sentinel16(hipStream_t s, void* p, size_t count) { PF_HIP(hipMemsetD16Async((hipDeviceptr_t)p, kSentinel16, count, s)); }
-
-// U = uint32_t (fp32 buffers) / uint16_t (f16): rows x ld cells of a buffer that was sentinel-filled before the launch.
-// blocked: the blocked activation layout (ld == N).  written = false: the buffer was not sentinel-filled inside [M, N]
-// (a result that aliases its residual), only the guard rows and columns are checked.  guard_row: the first row that must not
-// have been written (-1: round_up(M, 256), the padding the GEMM kernels declare; the layer kernels declare M or round_up(M, 64)).
-template <class U>
-void check_guard(hipStream_t s, const char* op, const char* what, const void* dev, U sentinel, int64_t rows, int M, int N, int ld,
-                 bool blocked, bool written = true, int64_t guard_row = -1) {
-  std::vector<U> h((size_t)rows * ld);
-  PF_HIP(hipMemcpyAsync(h.data(), dev, h.size() * sizeof(U), hipMemcpyDeviceToHost, s));
-  PF_HIP(hipStreamSynchronize(s));
-  const int64_t guard = guard_row >= 0 ? guard_row : round_up(M, 256);
-  auto at = [&](int64_t m, int n) -> U {
-    return blocked ? h[(((size_t)(m >> 5) * (N >> 3) + (n >> 3)) * 32 + (m & 31)) * 8 + (n & 7)] : h[(size_t)m * ld + n];
-  };
-  auto fail = [&](const char* why, int64_t m, int n) {
-    throw Error(PF_ERR_DEVICE, std::string(op) + ": " + what + " (" + std::to_string(M) + " x " + std::to_string(N) + ", ld " + std::to_string(ld) +
-                                   "): cell (" + std::to_string(m) + ", " + std::to_string(n) + ") " + why);
-  };
-  for (int64_t m = 0; m < rows; ++m)
-    for (int n = 0; n < ld; ++n) {
-      const bool is_sent = at(m, n) == sentinel;
-      if (m < M && n < N) { if (written && is_sent) fail("was not written", m, n); }
-      else if (n >= N) { if (!is_sent) fail("was written: a column beyond N", m, n); }
-      else if (m >= guard && !is_sent) fail(guard_row >= 0 ? "was written: a row the kernel's contract (kernels.h) calls never written"
-                                                           : "was written: a row at or beyond round_up(M, 256)", m, n);
-    }
-}
-// rows [row0, row1) of a row-major fp32 matrix [*, ld]: a large finite pattern (+-2^100 .. 2^101), as fill_hostile_rows
-void fill_hostile_rows32(hipStream_t s, float* base, int ld, int64_t row0, int64_t row1) {
-  if (row1 <= row0) return;
-  std::vector<float> h((size_t)(row1 - row0) * ld);
-  for (size_t i = 0; i < h.size(); ++i) h[i] = std::ldexp(1.0f + (float)((i * 37u) & 0x3FFu) / 1024.0f, 100) * ((i & 1u) ? -1.0f : 1.0f);
-  PF_HIP(hipMemcpyAsync(base + (size_t)row0 * ld, h.data(), h.size() * 4, hipMemcpyHostToDevice, s));
-  PF_HIP(hipStreamSynchronize(s));
-}
-// a sentinel-filled fp32 buffer (bytes % 4 == 0) that nothing may have touched
-void check_untouched32(hipStream_t s, const char* op, const char* what, const void* dev, size_t bytes) {
-  std::vector<uint32_t> h(bytes / 4);
-  PF_HIP(hipMemcpyAsync(h.data(), dev, h.size() * 4, hipMemcpyDeviceToHost, s));
-  PF_HIP(hipStreamSynchronize(s));
-  for (size_t i = 0; i < h.size(); ++i)
-    if (h[i] != kSentinel32) throw Error(PF_ERR_DEVICE, std::string(op) + ": " + what + ": word " + std::to_string(i) + " was written");
-}
 constexpr size_t kWsGuard = 4096;                             // sentinel bytes behind a kernel's workspace
 }  // namespace
+
+// the op's workspace: ws_tmp_, grown to what the carve measured
+void* Engine::op_ws(const StageCarve& st) {
+  ensure(ws_tmp_, st.off);
+  return ws_tmp_.p;
+}
+
+// tools/: PF_OP_REPEAT launches of one op, the first timed as class "gemm_op", the repeats (warm caches) as "gemm_op_warm"
+template <class Fn> void Engine::op_timed(double flops, Fn launch) {
+  const char* e = getenv("PF_OP_REPEAT");
+  const int reps = e ? std::max(1, atoi(e)) : 1;
+  for (int r = 0; r < reps; ++r) {
+    prof_begin(r == 0 ? "gemm_op" : "gemm_op_warm", flops);
+    launch();
+    prof_end(r == 0 ? "gemm_op" : "gemm_op_warm");
+  }
+}
 
 // ------------------------------------------------------------------ stand-alone ops -------
 void Engine::op_lfr_cmvn_pad(const float* const* fbank, const int32_t* t80, int B, int sentinel, float* out,
@@ -109,19 +56,19 @@ void Engine::op_lfr_cmvn_pad(const float* const* fbank, const int32_t* t80, int 
   const int64_t need = (int64_t)B * tmax * W;
   PF_CHECK(cap >= need, PF_ERR_CAPACITY, "lfr_cmvn_pad: out capacity < " + std::to_string(need));
   if (need == 0) return;
+  StageCarve st;                                                // of ws_meta_: the frame offsets, the frame counts
+  const auto doff = st.take<int64_t>((size_t)B + 1); const auto dt80 = st.take<int32_t>(B);
   ensure(ws_fbank_, (size_t)std::max<int64_t>(foff[B], 1) * nm * 4);
-  ensure(ws_meta_, (size_t)(B + 1) * 8 + (size_t)B * 4 + 64);
+  ensure(ws_meta_, st.off);
   ensure(ws_speech_, (size_t)need * 4);
+  void* meta = ws_meta_.p; float* rows = (float*)ws_fbank_.p;
   for (int b = 0; b < B; ++b)
-    if (t80[b] > 0)
-      PF_HIP(hipMemcpyAsync((float*)ws_fbank_.p + foff[b] * nm, fbank[b], (size_t)t80[b] * nm * 4,
-                            hipMemcpyHostToDevice, stream_));
-  PF_HIP(hipMemcpyAsync(ws_meta_.p, foff.data(), (size_t)(B + 1) * 8, hipMemcpyHostToDevice, stream_));
-  int32_t* t80d = (int32_t*)((char*)ws_meta_.p + (size_t)(B + 1) * 8);
-  PF_HIP(hipMemcpyAsync(t80d, t80, (size_t)B * 4, hipMemcpyHostToDevice, stream_));
-  launch_lfr_cmvn_pad(stream_, (const float*)ws_fbank_.p, (const int64_t*)ws_meta_.p, t80d, B, tmax, fc_.lfr_m,
-                      fc_.lfr_n, nm, cmvn_shift_, cmvn_scale_, cmvn_shift_ ? 1 : 0, sentinel, (float*)ws_speech_.p);
-  PF_HIP(hipMemcpyAsync(out, ws_speech_.p, (size_t)need * 4, hipMemcpyDeviceToHost, stream_));
+    if (t80[b] > 0) upload(stream_, rows + foff[b] * nm, fbank[b], (size_t)t80[b] * nm);
+  upload(stream_, doff(meta), foff.data(), (size_t)B + 1);
+  upload(stream_, dt80(meta), t80, B);
+  launch_lfr_cmvn_pad(stream_, rows, doff(meta), dt80(meta), B, tmax, fc_.lfr_m, fc_.lfr_n, nm, cmvn_shift_, cmvn_scale_, cmvn_shift_ ? 1 : 0,
+                      sentinel, (float*)ws_speech_.p);
+  download(stream_, out, (const float*)ws_speech_.p, (size_t)need);
   PF_HIP(hipStreamSynchronize(stream_));
 }
 
@@ -143,12 +90,12 @@ void Engine::op_fbank_batch(const float* const* samples, const int64_t* n, int B
 void Engine::op_argmax(const float* x, int64_t rows, int V, int64_t* ids) {
   PF_HIP(hipSetDevice(device_));
   if (rows == 0) return;
-  ensure(ws_tmp_, (size_t)rows * V * 4 + (size_t)rows * 8 + 256);
-  float* xd = (float*)ws_tmp_.p;
-  int64_t* idd = (int64_t*)((char*)ws_tmp_.p + round_up((int64_t)rows * V * 4, 256));
-  PF_HIP(hipMemcpyAsync(xd, x, (size_t)rows * V * 4, hipMemcpyHostToDevice, stream_));
-  launch_argmax(stream_, xd, rows, V, V, 0, idd);
-  PF_HIP(hipMemcpyAsync(ids, idd, (size_t)rows * 8, hipMemcpyDeviceToHost, stream_));
+  StageCarve st;
+  const auto dx = st.take<float>((size_t)rows * V); const auto did = st.take<int64_t>(rows);
+  void* ws = op_ws(st);
+  upload(stream_, dx(ws), x, (size_t)rows * V);
+  launch_argmax(stream_, dx(ws), rows, V, V, 0, did(ws));
+  download(stream_, ids, (const int64_t*)did(ws), rows);
   PF_HIP(hipStreamSynchronize(stream_));
 }
 
@@ -898,7 +845,7 @@ void Engine::op_nbest_search(const int64_t* ids, const float* val, const int32_t
   const Field<int32_t> d_col = c.take<int32_t>(g ? g->tok_col.size() : 0), d_tab = c.take<int32_t>(g ? g->table.size() : 0);
   ensure(ws_tmp_, c.off);
   void* ws = ws_tmp_.p;
-  fill_sentinel32(stream_, (char*)ws + k.begin, k.words() * 2);
+  fill_sentinel(stream_, (uint32_t*)((char*)ws + k.begin), k.words() * 2);
   if (rows > 0) {
     PF_HIP(hipMemcpyAsync(in.ids(ws), ids, in.ids.count * 8, hipMemcpyHostToDevice, stream_));
     PF_HIP(hipMemcpyAsync(in.val(ws), val, in.val.count * 4, hipMemcpyHostToDevice, stream_));
@@ -1004,41 +951,31 @@ void Engine::op_gemm(const float* A, const float* W, const float* bias, int M, i
   if (M == 0 || N == 0) return;
   const int Kp = (int)round_up(K, 64);
   const int64_t Mp = round_up(M, 256), Np = round_up(N, 256);
-  size_t off = 0;
-  const Carve carve{off};
-  const size_t oA = carve((size_t)M * K * 4), oW = carve((size_t)N * K * 4), ob = carve((size_t)N * 4);
-  const size_t oA16 = carve((size_t)Mp * Kp * 2), oW16 = carve((size_t)Np * Kp * 2), oC = carve((size_t)Mp * N * 4);
-  ensure(ws_tmp_, off);
-  char* base = (char*)ws_tmp_.p;
-  PF_HIP(hipMemcpyAsync(base + oA, A, (size_t)M * K * 4, hipMemcpyHostToDevice, stream_));
-  PF_HIP(hipMemcpyAsync(base + oW, W, (size_t)N * K * 4, hipMemcpyHostToDevice, stream_));
-  if (bias) PF_HIP(hipMemcpyAsync(base + ob, bias, (size_t)N * 4, hipMemcpyHostToDevice, stream_));
-  PF_HIP(hipMemsetAsync(base + oA16, 0, (size_t)Mp * Kp * 2, stream_));
-  PF_HIP(hipMemsetAsync(base + oW16, 0, (size_t)Np * Kp * 2, stream_));
-  launch_f32_to_f16(stream_, (const float*)(base + oA), M, K, K, (half_t*)(base + oA16), Kp);
-  launch_f32_to_f16(stream_, (const float*)(base + oW), N, K, K, (half_t*)(base + oW16), Kp);
+  StageCarve st;
+  const auto dA = st.take<float>((size_t)M * K), dW = st.take<float>((size_t)N * K), db = st.take<float>(N);
+  const auto dA16 = st.take<half_t>((size_t)Mp * Kp), dW16 = st.take<half_t>((size_t)Np * Kp);
+  const auto dC = st.take<float>((size_t)Mp * N);                // (the f16 result of epi 2 lives here too)
+  void* ws = op_ws(st);
+  if (bias) upload(stream_, db(ws), bias, N);
+  PF_HIP(hipMemsetAsync(dA16(ws), 0, (size_t)Mp * Kp * 2, stream_));
+  PF_HIP(hipMemsetAsync(dW16(ws), 0, (size_t)Np * Kp * 2, stream_));
+  upload_f16(stream_, dA(ws), A, M, K, dA16(ws), Kp);
+  upload_f16(stream_, dW(ws), W, N, K, dW16(ws), Kp);
   GemmArgs g{};
-  g.A = (half_t*)(base + oA16); g.lda = Kp; g.W = (half_t*)(base + oW16); g.ldw = Kp;
-  g.bias = bias ? (const float*)(base + ob) : nullptr;
+  g.A = dA16(ws); g.lda = Kp; g.W = dW16(ws); g.ldw = Kp;
+  g.bias = bias ? db(ws) : nullptr;
   g.M = M; g.N = N; g.K = Kp; g.relu = epi == 1;
   g.out_padded = 1;
   const bool f16out = epi == 2;
-  if (f16out) { g.out_f16 = (half_t*)(base + oC); g.ldc16 = N; }
-  else { g.out_f32 = (float*)(base + oC); g.ldc32 = N; }
+  if (f16out) { g.out_f16 = (half_t*)dC(ws); g.ldc16 = N; }
+  else { g.out_f32 = dC(ws); g.ldc32 = N; }
   prof_begin("gemm_op", 2.0 * M * (double)N * K);
   launch_gemm(stream_, g);
   prof_end("gemm_op");
   if (f16out) {
-    std::vector<uint16_t> tmp((size_t)M * N);
-    PF_HIP(hipMemcpyAsync(tmp.data(), base + oC, tmp.size() * 2, hipMemcpyDeviceToHost, stream_));
-    PF_HIP(hipStreamSynchronize(stream_));
-    for (size_t i = 0; i < tmp.size(); ++i) {
-      half_t hv;
-      std::memcpy(&hv, &tmp[i], 2);
-      C[i] = (float)hv;
-    }
+    download_f16(stream_, C, (const half_t*)dC(ws), M, N, N);
   } else {
-    PF_HIP(hipMemcpyAsync(C, base + oC, (size_t)M * N * 4, hipMemcpyDeviceToHost, stream_));
+    download(stream_, C, (const float*)dC(ws), (size_t)M * N);
     PF_HIP(hipStreamSynchronize(stream_));
   }
 }
@@ -1060,22 +997,19 @@ void Engine::op_linear32(const float* x, const float* W, const float* bias, cons
   PF_HIP(hipSetDevice(device_));
   const int ldc = (int)round_up(N, 4);
   const int64_t Mp = round_up(M, 256) + 128, Np = round_up(N, 256);
-  size_t off = 0;
-  const Carve carve{off};
-  const size_t ox = carve((size_t)Mp * K * 4), oW = carve((size_t)Np * K * 4), ob = carve((size_t)Np * 4), orr = carve((size_t)Mp * ldc * 4),
-               oy = carve((size_t)Mp * ldc * 4);
-  ensure(ws_tmp_, off);
-  char* base = (char*)ws_tmp_.p;
-  PF_HIP(hipMemsetAsync(base, 0, off, stream_));
-  PF_HIP(hipMemcpyAsync(base + ox, x, (size_t)M * K * 4, hipMemcpyHostToDevice, stream_));
-  PF_HIP(hipMemcpyAsync(base + oW, W, (size_t)N * K * 4, hipMemcpyHostToDevice, stream_));
-  if (bias) PF_HIP(hipMemcpyAsync(base + ob, bias, (size_t)N * 4, hipMemcpyHostToDevice, stream_));
-  if (resid) PF_HIP(hipMemcpy2DAsync(base + orr, (size_t)ldc * 4, resid, (size_t)N * 4, (size_t)N * 4, M, hipMemcpyHostToDevice, stream_));
-  gemm32((const float*)(base + ox), K, (const float*)(base + oW), K, bias ? (const float*)(base + ob) : nullptr, M, N, K, (float*)(base + oy), ldc,
-         resid ? (const float*)(base + orr) : nullptr, ldc, relu, 0, 1.f);
-  PF_HIP(hipMemcpy2DAsync(y, (size_t)N * 4, base + oy, (size_t)ldc * 4, (size_t)N * 4, M, hipMemcpyDeviceToHost, stream_));
+  StageCarve st;
+  const auto dx = st.take<float>((size_t)Mp * K), dW = st.take<float>((size_t)Np * K), db = st.take<float>(Np);
+  const auto dr = st.take<float>((size_t)Mp * ldc), dy = st.take<float>((size_t)Mp * ldc);
+  void* ws = op_ws(st);
+  PF_HIP(hipMemsetAsync(ws, 0, st.off, stream_));
+  upload(stream_, dx(ws), x, (size_t)M * K);
+  upload(stream_, dW(ws), W, (size_t)N * K);
+  if (bias) upload(stream_, db(ws), bias, N);
+  if (resid) upload2d(stream_, dr(ws), ldc, resid, N, N, M);
+  gemm32(dx(ws), K, dW(ws), K, bias ? db(ws) : nullptr, M, N, K, dy(ws), ldc, resid ? dr(ws) : nullptr, ldc, relu, 0, 1.f);
+  download2d(stream_, y, N, (const float*)dy(ws), ldc, N, M);
   PF_HIP(hipStreamSynchronize(stream_));
-  x3_forget((const float*)(base + oW));
+  x3_forget(dW(ws));
   x3a_src_ = nullptr;
 }
 
@@ -1084,26 +1018,22 @@ void Engine::op_ffn32(const float* x, const float* W1, const float* b1, const fl
   PF_CHECK(D % 4 == 0 && F % 4 == 0, PF_ERR_INVALID_ARG, "ffn32: D and F must be multiples of 4");
   PF_HIP(hipSetDevice(device_));
   const int64_t Mp = round_up(M, 256) + 128, Dp = round_up(D, 256), Fp = round_up(F, 256);
-  size_t off = 0;
-  const Carve carve{off};
-  const size_t ox = carve((size_t)Mp * D * 4), o1 = carve((size_t)Fp * D * 4), ob1 = carve((size_t)Fp * 4), o2 = carve((size_t)Dp * F * 4),
-               ob2 = carve((size_t)Dp * 4), oh = carve((size_t)Mp * F * 4), oy = carve((size_t)Mp * D * 4);
-  ensure(ws_tmp_, off);
-  char* base = (char*)ws_tmp_.p;
-  PF_HIP(hipMemsetAsync(base, 0, off, stream_));
-  PF_HIP(hipMemcpyAsync(base + ox, x, (size_t)M * D * 4, hipMemcpyHostToDevice, stream_));
-  PF_HIP(hipMemcpyAsync(base + o1, W1, (size_t)F * D * 4, hipMemcpyHostToDevice, stream_));
-  PF_HIP(hipMemcpyAsync(base + ob1, b1, (size_t)F * 4, hipMemcpyHostToDevice, stream_));
-  PF_HIP(hipMemcpyAsync(base + o2, W2, (size_t)D * F * 4, hipMemcpyHostToDevice, stream_));
-  PF_HIP(hipMemcpyAsync(base + ob2, b2, (size_t)D * 4, hipMemcpyHostToDevice, stream_));
-  const float* xd = (const float*)(base + ox);
-  gemm32(xd, D, (const float*)(base + o1), D, (const float*)(base + ob1), M, F, D, (float*)(base + oh), F, nullptr, 0, true, 0, 1.f, kX3OutPair);
-  gemm32((const float*)(base + oh), F, (const float*)(base + o2), F, (const float*)(base + ob2), M, D, F, (float*)(base + oy), D, xd, D, false, 0, 1.f,
-         kX3InPair);
-  PF_HIP(hipMemcpyAsync(y, base + oy, (size_t)M * D * 4, hipMemcpyDeviceToHost, stream_));
+  StageCarve st;
+  const auto dx = st.take<float>((size_t)Mp * D), d1 = st.take<float>((size_t)Fp * D), db1 = st.take<float>(Fp), d2 = st.take<float>((size_t)Dp * F),
+             db2 = st.take<float>(Dp), dh = st.take<float>((size_t)Mp * F), dy = st.take<float>((size_t)Mp * D);
+  void* ws = op_ws(st);
+  PF_HIP(hipMemsetAsync(ws, 0, st.off, stream_));
+  upload(stream_, dx(ws), x, (size_t)M * D);
+  upload(stream_, d1(ws), W1, (size_t)F * D);
+  upload(stream_, db1(ws), b1, F);
+  upload(stream_, d2(ws), W2, (size_t)D * F);
+  upload(stream_, db2(ws), b2, D);
+  gemm32(dx(ws), D, d1(ws), D, db1(ws), M, F, D, dh(ws), F, nullptr, 0, true, 0, 1.f, kX3OutPair);
+  gemm32(dh(ws), F, d2(ws), F, db2(ws), M, D, F, dy(ws), D, dx(ws), D, false, 0, 1.f, kX3InPair);
+  download(stream_, y, (const float*)dy(ws), (size_t)M * D);
   PF_HIP(hipStreamSynchronize(stream_));
-  x3_forget((const float*)(base + o1));
-  x3_forget((const float*)(base + o2));
+  x3_forget(d1(ws));
+  x3_forget(d2(ws));
   x3a_src_ = nullptr;
 }
 
@@ -1111,32 +1041,6 @@ void Engine::op_ffn32(const float* x, const float* W1, const float* b1, const fl
 // whose cells outside the matrix hold the large finite pattern (rows behind the last, the columns between the width and the row
 // stride), the three x3 arenas are filled with a large finite pattern before the call (so a pad row or pad column that reached
 // a cell of [M, N] would be seen), every result sits in a sentinel-filled buffer.
-namespace {
-constexpr uint16_t kPoison16 = 0x7A5Au;                       // 52 032 as f16; two of them are 2.8e35 as an fp32 word
-
-inline float hostile32(size_t i) { return std::ldexp(1.0f + (float)((i * 37u) & 0x3FFu) / 1024.0f, 100) * ((i & 1u) ? -1.0f : 1.0f); }
-
-// device image [rows, ld] of the host matrix src [m, n] (dense rows; null: nothing inside), hostile everywhere else
-void upload_hostile32(hipStream_t s, float* dev, int64_t rows, int ld, const float* src, int m, int n) {
-  std::vector<float> h((size_t)rows * ld);
-  for (size_t i = 0; i < h.size(); ++i) h[i] = hostile32(i);
-  if (src)
-    for (int r = 0; r < m; ++r) std::memcpy(&h[(size_t)r * ld], src + (size_t)r * n, (size_t)n * 4);
-  PF_HIP(hipMemcpyAsync(dev, h.data(), h.size() * 4, hipMemcpyHostToDevice, s));
-  PF_HIP(hipStreamSynchronize(s));
-}
-// f16 cells [row0, row1) x [0, ld) of an arena that was filled with kPoison16: nothing may have been stored there
-void check_poison16(hipStream_t s, const char* op, const char* what, const void* dev, int ld, int64_t row0, int64_t row1) {
-  if (row1 <= row0) return;
-  std::vector<uint16_t> h((size_t)(row1 - row0) * ld);
-  PF_HIP(hipMemcpyAsync(h.data(), (const uint16_t*)dev + (size_t)row0 * ld, h.size() * 2, hipMemcpyDeviceToHost, s));
-  PF_HIP(hipStreamSynchronize(s));
-  for (size_t i = 0; i < h.size(); ++i)
-    if (h[i] != kPoison16)
-      throw Error(PF_ERR_DEVICE, std::string(op) + ": " + what + ": cell (" + std::to_string(row0 + (int64_t)(i / ld)) + ", " + std::to_string(i % ld) + ") was written");
-}
-}  // namespace
-
 void Engine::x3_poison(int M, int N, int K) {
   if (!x3_mode_) return;
   const int64_t Mp = round_up(M, 256) + 128, Kp = round_up(K, 64);
@@ -1156,51 +1060,41 @@ void Engine::op_linear32_ex(const pf_linear32_desc& ds, const float* A, const fl
   PF_CHECK(lda >= K && ldw >= K && ldc >= N && ldr >= N, PF_ERR_INVALID_ARG, "linear32_ex: a row stride is narrower than its matrix");
   PF_CHECK(!alias || ds.resid, PF_ERR_INVALID_ARG, "linear32_ex: resid_aliases_out without a residual");
   const int64_t Mp = round_up(M, 256) + 128, Np = round_up(N, 256);
-  size_t off = 0;
-  const Carve carve{off};
-  const size_t oA = carve((size_t)Mp * lda * 4), oW = carve((size_t)Np * ldw * 4), ob = carve((size_t)Np * 4), oR = carve((size_t)Mp * ldr * 4),
-               oR2 = carve((size_t)Mp * ldr * 4), oC = carve((size_t)Mp * ldc * 4);
-  ensure(ws_tmp_, off);
-  char* base = (char*)ws_tmp_.p;
-  upload_hostile32(stream_, (float*)(base + oA), Mp, lda, A, M, K);
-  upload_hostile32(stream_, (float*)(base + oW), Np, ldw, W, N, K);
-  upload_hostile32(stream_, (float*)(base + ob), 1, (int)Np, ds.bias, 1, N);
-  if (ds.resid && !alias) upload_hostile32(stream_, (float*)(base + oR), Mp, ldr, ds.resid, M, N);
-  if (ds.resid2) upload_hostile32(stream_, (float*)(base + oR2), Mp, ldr, ds.resid2, M, N);
-  fill_sentinel32(stream_, base + oC, (size_t)Mp * ldc);
-  if (alias) PF_HIP(hipMemcpy2DAsync(base + oC, (size_t)ldc * 4, ds.resid, (size_t)N * 4, (size_t)N * 4, M, hipMemcpyHostToDevice, stream_));
+  StageCarve st;
+  const auto dA = st.take<float>((size_t)Mp * lda), dW = st.take<float>((size_t)Np * ldw), db = st.take<float>(Np);
+  const auto dR = st.take<float>((size_t)Mp * ldr), dR2 = st.take<float>((size_t)Mp * ldr), dC = st.take<float>((size_t)Mp * ldc);
+  void* ws = op_ws(st);
+  upload_hostile32(stream_, dA(ws), Mp, lda, A, M, K);
+  upload_hostile32(stream_, dW(ws), Np, ldw, W, N, K);
+  upload_hostile32(stream_, db(ws), 1, (int)Np, ds.bias, 1, N);
+  if (ds.resid && !alias) upload_hostile32(stream_, dR(ws), Mp, ldr, ds.resid, M, N);
+  if (ds.resid2) upload_hostile32(stream_, dR2(ws), Mp, ldr, ds.resid2, M, N);
+  float* out = dC(ws);
+  fill_sentinel(stream_, out, (size_t)Mp * ldc);
+  if (alias) upload2d(stream_, out, ldc, ds.resid, N, N, M);
   x3_poison(M, N, K);
-  const float* Wd = (const float*)(base + oW);
-  float* out = (float*)(base + oC);
-  auto done = [&] { x3_forget(Wd); x3a_src_ = nullptr; x3a_pair_only_ = false; x3_pair_live_ = false; cls32_ = "gemm32_misc"; };
-  try {
-    cls32_ = "gemm32_op";
-    gemm32((const float*)(base + oA), lda, Wd, ldw, ds.bias ? (const float*)(base + ob) : nullptr, M, N, K, out, ldc,
-           ds.resid ? (alias ? out : (const float*)(base + oR)) : nullptr, ldr, ds.relu != 0, ds.scale_cols, ds.scale, ds.flags,
-           ds.resid2 ? (const float*)(base + oR2) : nullptr);
-    check_guard<uint32_t>(stream_, "linear32_ex", "the fp32 result", out, kSentinel32, Mp, M, N, ldc, false, !alias, M);
-  } catch (...) {
-    done();
-    throw;
-  }
-  done();
-  PF_HIP(hipMemcpy2DAsync(C, (size_t)N * 4, out, (size_t)ldc * 4, (size_t)N * 4, M, hipMemcpyDeviceToHost, stream_));
+  const float* Wd = dW(ws);
+  const auto done = at_exit([&] { x3_forget(Wd); x3a_src_ = nullptr; x3a_pair_only_ = false; x3_pair_live_ = false; cls32_ = "gemm32_misc"; });
+  cls32_ = "gemm32_op";
+  gemm32(dA(ws), lda, Wd, ldw, ds.bias ? db(ws) : nullptr, M, N, K, out, ldc, ds.resid ? (alias ? out : dR(ws)) : nullptr, ldr, ds.relu != 0,
+         ds.scale_cols, ds.scale, ds.flags, ds.resid2 ? dR2(ws) : nullptr);
+  check_guard(stream_, "linear32_ex: the fp32 result", out, kSentinel32, result_geom(Mp, M, N, ldc, M, false, !alias));
+  download2d(stream_, C, N, (const float*)out, ldc, N, M);
   PF_HIP(hipStreamSynchronize(stream_));
 }
 
 void Engine::op_split_x3(const float* x, int rows, int K, int ldx, int ldo, int Kp, int swap, uint16_t* out) {
   PF_HIP(hipSetDevice(device_));
   const int64_t Rp = (int64_t)rows + 64;
-  size_t off = 0;
-  const Carve carve{off};
-  const size_t ox = carve((size_t)Rp * ldx * 4), oo = carve((size_t)Rp * ldo * 2);
-  ensure(ws_tmp_, off);
-  char* base = (char*)ws_tmp_.p;
-  upload_hostile32(stream_, (float*)(base + ox), Rp, ldx, x, rows, K);
-  fill_sentinel16(stream_, base + oo, (size_t)Rp * ldo);
-  launch_split_x3(stream_, (const float*)(base + ox), rows, K, ldx, (half_t*)(base + oo), ldo, Kp, swap);
-  check_guard<uint16_t>(stream_, "split_x3", "the pair", base + oo, kSentinel16, Rp, rows, 2 * Kp, ldo, false, true, rows);
-  PF_HIP(hipMemcpyAsync(out, base + oo, (size_t)rows * ldo * 2, hipMemcpyDeviceToHost, stream_));
+  StageCarve st;
+  const auto dx = st.take<float>((size_t)Rp * ldx);
+  const auto dout = st.take<half_t>((size_t)Rp * ldo);
+  void* ws = op_ws(st);
+  upload_hostile32(stream_, dx(ws), Rp, ldx, x, rows, K);
+  fill_sentinel(stream_, dout(ws), (size_t)Rp * ldo);
+  launch_split_x3(stream_, dx(ws), rows, K, ldx, dout(ws), ldo, Kp, swap);
+  check_guard(stream_, "split_x3: the pair", dout(ws), kSentinel16, result_geom(Rp, rows, 2 * Kp, ldo, rows));
+  download(stream_, out, (const uint16_t*)dout(ws), (size_t)rows * ldo);
   PF_HIP(hipStreamSynchronize(stream_));
 }
 
@@ -1211,63 +1105,57 @@ void Engine::op_layernorm32(const float* x, const float* gamma, const float* bet
   if (!W) N = 4;
   const int ldc = (int)round_up(N, 4), ldo = 2 * D + 8;
   const int64_t Mp = round_up(M, 256) + 128, Np = round_up(N, 256);
-  size_t off = 0;
-  const Carve carve{off};
-  const size_t ox = carve((size_t)Mp * D * 4), og = carve((size_t)D * 4), obt = carve((size_t)D * 4), on = carve((size_t)Mp * D * 4),
-               op = carve((size_t)Mp * ldo * 2), oW = carve((size_t)Np * D * 4), ob = carve((size_t)Np * 4), oy = carve((size_t)Mp * ldc * 4);
-  ensure(ws_tmp_, off);
-  char* base = (char*)ws_tmp_.p;
-  upload_hostile32(stream_, (float*)(base + ox), Mp, D, x, M, D);
-  PF_HIP(hipMemcpyAsync(base + og, gamma, (size_t)D * 4, hipMemcpyHostToDevice, stream_));
-  PF_HIP(hipMemcpyAsync(base + obt, beta, (size_t)D * 4, hipMemcpyHostToDevice, stream_));
-  const float* xd = (const float*)(base + ox);
-  float* xn = (float*)(base + on);
+  StageCarve st;
+  const auto dx = st.take<float>((size_t)Mp * D), dg = st.take<float>(D), dbt = st.take<float>(D), dn = st.take<float>((size_t)Mp * D);
+  const auto dp = st.take<uint16_t>((size_t)Mp * ldo);
+  const auto dW = st.take<float>((size_t)Np * D), db = st.take<float>(Np), dy = st.take<float>((size_t)Mp * ldc);
+  void* ws = op_ws(st);
+  upload_hostile32(stream_, dx(ws), Mp, D, x, M, D);
+  upload(stream_, dg(ws), gamma, D);
+  upload(stream_, dbt(ws), beta, D);
+  const float* xd = dx(ws);
+  float* xn = dn(ws);
   *wrote_pair = 0;
   if (direct_pair) {
     PF_CHECK(D == 512, PF_ERR_INVALID_ARG, "layernorm32: the pair kernel is the D = 512 kernel");
-    fill_sentinel16(stream_, base + op, (size_t)Mp * ldo);
-    launch_layernorm_pair(stream_, xd, M, (const float*)(base + og), (const float*)(base + obt), (half_t*)(base + op), ldo, D);
-    check_guard<uint16_t>(stream_, "layernorm32", "the pair", base + op, kSentinel16, Mp, M, 2 * D, ldo, false, true, M);
-    PF_HIP(hipMemcpy2DAsync(pair, (size_t)2 * D * 2, base + op, (size_t)ldo * 2, (size_t)2 * D * 2, M, hipMemcpyDeviceToHost, stream_));
+    fill_sentinel(stream_, dp(ws), (size_t)Mp * ldo);
+    launch_layernorm_pair(stream_, xd, M, dg(ws), dbt(ws), (half_t*)dp(ws), ldo, D);
+    check_guard(stream_, "layernorm32: the pair", dp(ws), kSentinel16, result_geom(Mp, M, 2 * D, ldo, M));
+    download2d(stream_, pair, 2 * D, (const uint16_t*)dp(ws), ldo, 2 * D, M);
     PF_HIP(hipStreamSynchronize(stream_));
     *wrote_pair = 1;
     return;
   }
   if (W) {
-    upload_hostile32(stream_, (float*)(base + oW), Np, D, W, N, D);
-    upload_hostile32(stream_, (float*)(base + ob), 1, (int)Np, bias, 1, N);
-    fill_sentinel32(stream_, base + oy, (size_t)Mp * ldc);
+    upload_hostile32(stream_, dW(ws), Np, D, W, N, D);
+    upload_hostile32(stream_, db(ws), 1, (int)Np, bias, 1, N);
+    fill_sentinel(stream_, dy(ws), (size_t)Mp * ldc);
   }
-  fill_sentinel32(stream_, xn, (size_t)Mp * D);
+  fill_sentinel(stream_, xn, (size_t)Mp * D);
   x3_poison(M, N, D);
-  const float* Wd = (const float*)(base + oW);
-  auto done = [&] { x3_forget(Wd); x3a_src_ = nullptr; x3a_pair_only_ = false; x3_pair_live_ = false; cls32_ = "gemm32_misc"; };
-  try {
-    LNp ln;
-    ln.g = (const float*)(base + og); ln.b = (const float*)(base + obt); ln.D = D;
-    layernorm32(xd, M, D, ln, xn);
-    if (x3a_pair_only_ && x3a_src_ == xn) {
-      *wrote_pair = 1;
-      check_untouched32(stream_, "layernorm32", "the fp32 row buffer beside the pair", xn, (size_t)Mp * D * 4);
-      check_poison16(stream_, "layernorm32", "the pair arena behind row M - 1", ws_x3a_.p, 2 * D, M, Mp);
-      PF_HIP(hipMemcpyAsync(pair, ws_x3a_.p, (size_t)M * 2 * D * 2, hipMemcpyDeviceToHost, stream_));
-    } else {
-      check_guard<uint32_t>(stream_, "layernorm32", "the fp32 rows", xn, kSentinel32, Mp, M, D, D, false, true, M);
-      PF_HIP(hipMemcpyAsync(out32, xn, (size_t)M * D * 4, hipMemcpyDeviceToHost, stream_));
-    }
-    PF_HIP(hipStreamSynchronize(stream_));
-    if (W) {
-      cls32_ = "gemm32_op";
-      gemm32(xn, D, Wd, D, bias ? (const float*)(base + ob) : nullptr, M, N, D, (float*)(base + oy), ldc, nullptr, 0, false, 0, 1.f);
-      check_guard<uint32_t>(stream_, "layernorm32", "the product behind it", base + oy, kSentinel32, Mp, M, N, ldc, false, true, M);
-      PF_HIP(hipMemcpy2DAsync(y, (size_t)N * 4, base + oy, (size_t)ldc * 4, (size_t)N * 4, M, hipMemcpyDeviceToHost, stream_));
-      PF_HIP(hipStreamSynchronize(stream_));
-    }
-  } catch (...) {
-    done();
-    throw;
+  const float* Wd = dW(ws);
+  const auto done = at_exit([&] { x3_forget(Wd); x3a_src_ = nullptr; x3a_pair_only_ = false; x3_pair_live_ = false; cls32_ = "gemm32_misc"; });
+  LNp ln;
+  ln.g = dg(ws); ln.b = dbt(ws); ln.D = D;
+  layernorm32(xd, M, D, ln, xn);
+  if (x3a_pair_only_ && x3a_src_ == xn) {
+    *wrote_pair = 1;
+    check_guard(stream_, "layernorm32: the fp32 row buffer beside the pair", xn, kSentinel32, untouched_geom(Mp * D));
+    check_guard(stream_, "layernorm32: the pair arena behind row M - 1", (const uint16_t*)ws_x3a_.p + (size_t)M * 2 * D, kPoison16,
+                untouched_geom(Mp - M, 2 * D), nullptr, M);
+    download(stream_, pair, (const uint16_t*)ws_x3a_.p, (size_t)M * 2 * D);
+  } else {
+    check_guard(stream_, "layernorm32: the fp32 rows", xn, kSentinel32, result_geom(Mp, M, D, D, M));
+    download(stream_, out32, (const float*)xn, (size_t)M * D);
   }
-  done();
+  PF_HIP(hipStreamSynchronize(stream_));
+  if (W) {
+    cls32_ = "gemm32_op";
+    gemm32(xn, D, Wd, D, bias ? db(ws) : nullptr, M, N, D, dy(ws), ldc, nullptr, 0, false, 0, 1.f);
+    check_guard(stream_, "layernorm32: the product behind it", dy(ws), kSentinel32, result_geom(Mp, M, N, ldc, M));
+    download2d(stream_, y, N, (const float*)dy(ws), ldc, N, M);
+    PF_HIP(hipStreamSynchronize(stream_));
+  }
 }
 
 void Engine::op_ffn32_ex(const float* x, const float* W1, const float* b1, const float* W2, const float* b2, int M, int D, int F, float hidden_scale,
@@ -1276,50 +1164,44 @@ void Engine::op_ffn32_ex(const float* x, const float* W1, const float* b1, const
   PF_CHECK(D % 4 == 0 && F % 4 == 0, PF_ERR_INVALID_ARG, "ffn32_ex: D and F must be multiples of 4");
   PF_HIP(hipSetDevice(device_));
   const int64_t Mp = round_up(M, 256) + 128, Dp = round_up(D, 256), Fp = round_up(F, 256);
-  size_t off = 0;
-  const Carve carve{off};
-  const size_t ox = carve((size_t)Mp * D * 4), o1 = carve((size_t)Fp * D * 4), ob1 = carve((size_t)Fp * 4), o2 = carve((size_t)Dp * F * 4),
-               ob2 = carve((size_t)Dp * 4), oh = carve((size_t)Mp * F * 4), oy = carve((size_t)Mp * D * 4);
-  ensure(ws_tmp_, off);
-  char* base = (char*)ws_tmp_.p;
-  upload_hostile32(stream_, (float*)(base + ox), Mp, D, x, M, D);
-  upload_hostile32(stream_, (float*)(base + o1), Fp, D, W1, F, D);
-  upload_hostile32(stream_, (float*)(base + ob1), 1, (int)Fp, b1, 1, F);
-  upload_hostile32(stream_, (float*)(base + o2), Dp, F, W2, D, F);
-  upload_hostile32(stream_, (float*)(base + ob2), 1, (int)Dp, b2, 1, D);
-  fill_sentinel32(stream_, base + oh, (size_t)Mp * F);
-  fill_sentinel32(stream_, base + oy, (size_t)Mp * D);
+  StageCarve st;
+  const auto dx = st.take<float>((size_t)Mp * D), d1 = st.take<float>((size_t)Fp * D), db1 = st.take<float>(Fp), d2 = st.take<float>((size_t)Dp * F),
+             db2 = st.take<float>(Dp), dh = st.take<float>((size_t)Mp * F), dy = st.take<float>((size_t)Mp * D);
+  void* ws = op_ws(st);
+  upload_hostile32(stream_, dx(ws), Mp, D, x, M, D);
+  upload_hostile32(stream_, d1(ws), Fp, D, W1, F, D);
+  upload_hostile32(stream_, db1(ws), 1, (int)Fp, b1, 1, F);
+  upload_hostile32(stream_, d2(ws), Dp, F, W2, D, F);
+  upload_hostile32(stream_, db2(ws), 1, (int)Dp, b2, 1, D);
+  fill_sentinel(stream_, dh(ws), (size_t)Mp * F);
+  fill_sentinel(stream_, dy(ws), (size_t)Mp * D);
   x3_poison(M, std::max(D, F), std::max(D, F));
-  const float* xd = (const float*)(base + ox);
-  const float* w1 = (const float*)(base + o1);
-  const float* w2 = (const float*)(base + o2);
-  auto done = [&] { x3_forget(w1); x3_forget(w2); x3a_src_ = nullptr; x3a_pair_only_ = false; x3_pair_live_ = false; cls32_ = "gemm32_misc"; };
+  const float* xd = dx(ws);
+  const float* w1 = d1(ws);
+  const float* w2 = d2(ws);
+  const auto done = at_exit([&] { x3_forget(w1); x3_forget(w2); x3a_src_ = nullptr; x3a_pair_only_ = false; x3_pair_live_ = false; cls32_ = "gemm32_misc"; });
   *pair_written = 0;
-  try {
-    const bool scaled = hidden_scale != 1.0f;
-    cls32_ = "gemm32_ffn1";
-    gemm32(xd, D, w1, D, (const float*)(base + ob1), M, F, D, (float*)(base + oh), F, nullptr, 0, true, scaled ? F : 0, hidden_scale, kX3OutPair);
-    if (x3_pair_live_) {
-      *pair_written = 1;
-      const int ldp = 2 * (int)round_up(F, 64);
-      check_untouched32(stream_, "ffn32_ex", "the fp32 hidden beside its pair", base + oh, (size_t)Mp * F * 4);
-      check_poison16(stream_, "ffn32_ex", "the pair arena at and beyond round_up(M, 256)", ws_x3h_.p, ldp, round_up(M, 256), Mp);
-      PF_HIP(hipMemcpy2DAsync(hidden_pair, (size_t)2 * F * 2, ws_x3h_.p, (size_t)ldp * 2, (size_t)F * 2, M, hipMemcpyDeviceToHost, stream_));
-      PF_HIP(hipMemcpy2DAsync(hidden_pair + F, (size_t)2 * F * 2, (const uint16_t*)ws_x3h_.p + ldp / 2, (size_t)ldp * 2, (size_t)F * 2, M,
-                              hipMemcpyDeviceToHost, stream_));
-      PF_HIP(hipStreamSynchronize(stream_));
-    } else {
-      check_guard<uint32_t>(stream_, "ffn32_ex", "the fp32 hidden", base + oh, kSentinel32, Mp, M, F, F, false, true, M);
-    }
-    cls32_ = "gemm32_ffn2";
-    gemm32((const float*)(base + oh), F, w2, F, (const float*)(base + ob2), M, D, F, (float*)(base + oy), D, xd, D, false, 0, 1.f, kX3InPair);
-    check_guard<uint32_t>(stream_, "ffn32_ex", "the fp32 result", base + oy, kSentinel32, Mp, M, D, D, false, true, M);
-  } catch (...) {
-    done();
-    throw;
+  const bool scaled = hidden_scale != 1.0f;
+  cls32_ = "gemm32_ffn1";
+  gemm32(xd, D, w1, D, db1(ws), M, F, D, dh(ws), F, nullptr, 0, true, scaled ? F : 0, hidden_scale, kX3OutPair);
+  if (x3_pair_live_) {
+    *pair_written = 1;
+    const int ldp = 2 * (int)round_up(F, 64);
+    const int64_t g0 = round_up(M, 256);
+    const uint16_t* arena = (const uint16_t*)ws_x3h_.p;
+    check_guard(stream_, "ffn32_ex: the fp32 hidden beside its pair", dh(ws), kSentinel32, untouched_geom(Mp * F));
+    check_guard(stream_, "ffn32_ex: the pair arena at and beyond round_up(M, 256)", arena + (size_t)g0 * ldp, kPoison16,
+                untouched_geom(Mp - g0, ldp), nullptr, g0);
+    download2d(stream_, hidden_pair, 2 * F, arena, ldp, F, M);
+    download2d(stream_, hidden_pair + F, 2 * F, arena + ldp / 2, ldp, F, M);
+    PF_HIP(hipStreamSynchronize(stream_));
+  } else {
+    check_guard(stream_, "ffn32_ex: the fp32 hidden", dh(ws), kSentinel32, result_geom(Mp, M, F, F, M));
   }
-  done();
-  PF_HIP(hipMemcpyAsync(y, base + oy, (size_t)M * D * 4, hipMemcpyDeviceToHost, stream_));
+  cls32_ = "gemm32_ffn2";
+  gemm32(dh(ws), F, w2, F, db2(ws), M, D, F, dy(ws), D, xd, D, false, 0, 1.f, kX3InPair);
+  check_guard(stream_, "ffn32_ex: the fp32 result", dy(ws), kSentinel32, result_geom(Mp, M, D, D, M));
+  download(stream_, y, (const float*)dy(ws), (size_t)M * D);
   PF_HIP(hipStreamSynchronize(stream_));
 }
 
@@ -1327,40 +1209,30 @@ void Engine::op_qkv32(const float* x, const float* W, const float* bias, int M, 
   PF_CHECK(fp32_mode_, PF_ERR_UNSUPPORTED, "qkv32: the engine was not created with math_mode 1 or 3");
   PF_HIP(hipSetDevice(device_));
   const int64_t Mp = round_up(M, 256) + 128, Np = round_up(3 * D, 256);
-  size_t off = 0;
-  const Carve carve{off};
-  const size_t ox = carve((size_t)Mp * K * 4), oW = carve((size_t)Np * K * 4), ob = carve((size_t)Np * 4);
-  size_t oq[3];
-  for (int i = 0; i < 3; ++i) oq[i] = carve((size_t)Mp * D * 4);
-  ensure(ws_tmp_, off);
-  char* base = (char*)ws_tmp_.p;
-  upload_hostile32(stream_, (float*)(base + ox), Mp, K, x, M, K);
-  upload_hostile32(stream_, (float*)(base + oW), Np, K, W, 3 * D, K);
-  upload_hostile32(stream_, (float*)(base + ob), 1, (int)Np, bias, 1, 3 * D);
-  for (int i = 0; i < 3; ++i) fill_sentinel32(stream_, base + oq[i], (size_t)Mp * D);
+  StageCarve st;
+  const auto dx = st.take<float>((size_t)Mp * K), dW = st.take<float>((size_t)Np * K), db = st.take<float>(Np);
+  const Field<float> dq[3] = {st.take<float>((size_t)Mp * D), st.take<float>((size_t)Mp * D), st.take<float>((size_t)Mp * D)};
+  void* ws = op_ws(st);
+  upload_hostile32(stream_, dx(ws), Mp, K, x, M, K);
+  upload_hostile32(stream_, dW(ws), Np, K, W, 3 * D, K);
+  upload_hostile32(stream_, db(ws), 1, (int)Np, bias, 1, 3 * D);
+  for (int i = 0; i < 3; ++i) fill_sentinel(stream_, dq[i](ws), (size_t)Mp * D);
   x3_poison(M, D, K);
-  const float* xd = (const float*)(base + ox);
-  const float* Wd = (const float*)(base + oW);
-  const float* bd = (const float*)(base + ob);
-  auto done = [&] {
+  const float* xd = dx(ws);
+  const float* Wd = dW(ws);
+  const float* bd = db(ws);
+  const auto done = at_exit([&] {
     for (int i = 0; i < 3; ++i) x3_forget(Wd + (size_t)i * D * K);
     x3a_src_ = nullptr; x3a_pair_only_ = false; x3_pair_live_ = false; cls32_ = "gemm32_misc";
-  };
+  });
   static const char* const cls[3] = {"gemm32_op_q", "gemm32_op_k", "gemm32_op_v"};
-  try {
-    for (int i = 0; i < 3; ++i) {                                // as enc_layer_fp32 launches the three
-      cls32_ = cls[i];
-      gemm32(xd, K, Wd + (size_t)i * D * K, K, bd + (size_t)i * D, M, D, K, (float*)(base + oq[i]), D, nullptr, 0, false, i == 0 ? D : 0,
-             i == 0 ? qscale : 1.f, i == 0 ? 0 : kX3SameInput);
-      check_guard<uint32_t>(stream_, "qkv32", cls[i], base + oq[i], kSentinel32, Mp, M, D, D, false, true, M);
-    }
-  } catch (...) {
-    done();
-    throw;
+  for (int i = 0; i < 3; ++i) {                                // as enc_layer_fp32 launches the three
+    cls32_ = cls[i];
+    gemm32(xd, K, Wd + (size_t)i * D * K, K, bd + (size_t)i * D, M, D, K, dq[i](ws), D, nullptr, 0, false, i == 0 ? D : 0,
+           i == 0 ? qscale : 1.f, i == 0 ? 0 : kX3SameInput);
+    check_guard(stream_, std::string("qkv32: ") + cls[i], dq[i](ws), kSentinel32, result_geom(Mp, M, D, D, M));
   }
-  done();
-  for (int i = 0; i < 3; ++i)
-    PF_HIP(hipMemcpy2DAsync(out + (size_t)i * D, (size_t)3 * D * 4, base + oq[i], (size_t)D * 4, (size_t)D * 4, M, hipMemcpyDeviceToHost, stream_));
+  for (int i = 0; i < 3; ++i) download2d(stream_, out + (size_t)i * D, 3 * D, (const float*)dq[i](ws), D, D, M);
   PF_HIP(hipStreamSynchronize(stream_));
 }
 
@@ -1380,43 +1252,26 @@ void Engine::op_gemm_ex(const pf_gemm_desc& ds, const float* A, const float* W, 
   const int Kp = (int)round_up(K, 64);
   const int64_t Mp = round_up(M, 256) + 128, Np = round_up(N, 256);
   const int ld32 = (int)round_up(N, 4), ld16 = (int)round_up(N, 8);
-  size_t off = 0;
-  const Carve carve{off};
-  const size_t oA = carve((size_t)M * K * 4), oW = carve((size_t)N * K * 4), ob = carve((size_t)N * 4);
-  const size_t oA16 = carve((size_t)Mp * Kp * 2), oW16 = carve((size_t)Np * Kp * 2);
-  const size_t oR = carve((size_t)Mp * ld32 * 4), oD = carve((size_t)Mp * ld32 * 4), oC = carve((size_t)Mp * std::max(ld32, ld16) * 4);
-  ensure(ws_tmp_, off);
-  char* base = (char*)ws_tmp_.p;
-  PF_HIP(hipMemsetAsync(base + oA16, 0, (size_t)Mp * Kp * 2, stream_));
-  PF_HIP(hipMemsetAsync(base + oW16, 0, (size_t)Np * Kp * 2, stream_));
-  std::vector<half_t> ablk;
-  if (ds.a_blocked) {
-    // host-side re-layout (independent of the kernel's own index arithmetic): element (m, k) at
-    // ((m/32 * Kp/8 + k/8) * 32 + m%32) * 8 + k%8
-    ablk.assign((size_t)Mp * Kp, (half_t)0.f);
-    for (int m = 0; m < M; ++m)
-      for (int k = 0; k < K; ++k)
-        ablk[(((size_t)(m >> 5) * (Kp >> 3) + (k >> 3)) * 32 + (m & 31)) * 8 + (k & 7)] = (half_t)A[(size_t)m * K + k];
-    fill_hostile_blocked(ablk, M, Mp, K, Kp);
-    PF_HIP(hipMemcpyAsync(base + oA16, ablk.data(), ablk.size() * 2, hipMemcpyHostToDevice, stream_));
-  } else {
-    fill_hostile_rows(stream_, (half_t*)(base + oA16), Kp, M, Mp, K);
-    PF_HIP(hipMemcpyAsync(base + oA, A, (size_t)M * K * 4, hipMemcpyHostToDevice, stream_));
-    launch_f32_to_f16(stream_, (const float*)(base + oA), M, K, K, (half_t*)(base + oA16), Kp);
-  }
-  fill_hostile_rows(stream_, (half_t*)(base + oW16), Kp, N, Np, K);
-  if (ds.out_kind == 0) fill_sentinel32(stream_, base + oC, (size_t)Mp * ld32);
-  else fill_sentinel16(stream_, base + oC, (size_t)Mp * (ds.out_kind == 2 ? N : ld16));
-  PF_HIP(hipMemcpyAsync(base + oW, W, (size_t)N * K * 4, hipMemcpyHostToDevice, stream_));
-  launch_f32_to_f16(stream_, (const float*)(base + oW), N, K, K, (half_t*)(base + oW16), Kp);
-  if (ds.bias) PF_HIP(hipMemcpyAsync(base + ob, ds.bias, (size_t)N * 4, hipMemcpyHostToDevice, stream_));
-  if (ds.resid)
-    PF_HIP(hipMemcpy2DAsync(base + oR, (size_t)ld32 * 4, ds.resid, (size_t)N * 4, (size_t)N * 4, M, hipMemcpyHostToDevice, stream_));
-  if (ds.add2)
-    PF_HIP(hipMemcpy2DAsync(base + oD, (size_t)ld32 * 4, ds.add2, (size_t)N * 4, (size_t)N * 4, M, hipMemcpyHostToDevice, stream_));
+  const int ldc16 = ds.out_kind == 2 ? N : ld16;
+  StageCarve st;
+  const auto dA = st.take<float>((size_t)M * K), dW = st.take<float>((size_t)N * K), db = st.take<float>(N);
+  const auto dA16 = st.take<half_t>((size_t)Mp * Kp), dW16 = st.take<half_t>((size_t)Np * Kp);
+  const auto dR = st.take<float>((size_t)Mp * ld32), dD = st.take<float>((size_t)Mp * ld32);
+  const auto dC = st.take<float>((size_t)Mp * std::max(ld32, ld16));     // (either result kind)
+  void* ws = op_ws(st);
+  float* c32 = dC(ws);
+  half_t* c16 = (half_t*)dC(ws);
+  if (ds.a_blocked) upload_blocked16(stream_, A, M, K, dA16(ws), Kp, Mp);
+  else upload_operand16(stream_, dA(ws), A, M, K, dA16(ws), Kp, Mp);
+  upload_operand16(stream_, dW(ws), W, N, K, dW16(ws), Kp, Np);
+  if (ds.out_kind == 0) fill_sentinel(stream_, c32, (size_t)Mp * ld32);
+  else fill_sentinel(stream_, c16, (size_t)Mp * ldc16);
+  if (ds.bias) upload(stream_, db(ws), ds.bias, N);
+  if (ds.resid) upload2d(stream_, dR(ws), ld32, ds.resid, N, N, M);
+  if (ds.add2) upload2d(stream_, dD(ws), ld32, ds.add2, N, N, M);
   GemmArgs g{};
-  g.A = (half_t*)(base + oA16); g.lda = Kp; g.W = (half_t*)(base + oW16); g.ldw = Kp;
-  g.bias = ds.bias ? (const float*)(base + ob) : nullptr;
+  g.A = dA16(ws); g.lda = Kp; g.W = dW16(ws); g.ldw = Kp;
+  g.bias = ds.bias ? db(ws) : nullptr;
   g.M = M; g.N = N; g.K = Kp; g.relu = ds.relu ? 1 : 0;
   g.scale_cols = ds.scale_cols; g.scale = ds.scale;
   g.out_padded = 1;
@@ -1424,36 +1279,22 @@ void Engine::op_gemm_ex(const pf_gemm_desc& ds, const float* A, const float* W, 
   g.force_mi = ds.tile_rows == 128 ? 1 : (ds.tile_rows == 256 ? 2 : (ds.tile_rows == 32 ? 4 : (ds.tile_rows == 1024 ? 5 : (ds.tile_rows == 2048 ? 6 : 0))));
   g.small_ws = small_ws_;
   if (ds.out_kind == 0) {
-    g.out_f32 = (float*)(base + oC); g.ldc32 = ld32;
-    if (ds.resid) { g.resid = (const float*)(base + oR); g.ldr = ld32; }
-    if (ds.add2) { g.add2 = (const float*)(base + oD); g.ld2 = ld32; }
+    g.out_f32 = c32; g.ldc32 = ld32;
+    if (ds.resid) { g.resid = dR(ws); g.ldr = ld32; }
+    if (ds.add2) { g.add2 = dD(ws); g.ld2 = ld32; }
   } else {
-    g.out_f16 = (half_t*)(base + oC); g.ldc16 = ds.out_kind == 2 ? N : ld16;
+    g.out_f16 = c16; g.ldc16 = ldc16;
     g.out_blocked = ds.out_kind == 2;
   }
-  static const int reps = [] { const char* e = getenv("PF_OP_REPEAT"); return e ? std::max(1, atoi(e)) : 1; }();   // tools/: warm-cache timing
-  for (int r = 0; r < reps; ++r) {
-    prof_begin(r == 0 ? "gemm_op" : "gemm_op_warm", 2.0 * M * (double)N * K);
-    launch_gemm(stream_, g);
-    prof_end(r == 0 ? "gemm_op" : "gemm_op_warm");
-  }
-  if (ds.out_kind == 0) check_guard<uint32_t>(stream_, "gemm_ex", "the fp32 result", base + oC, kSentinel32, Mp, M, N, ld32, false);
-  else check_guard<uint16_t>(stream_, "gemm_ex", "the f16 result", base + oC, kSentinel16, Mp, M, N, ds.out_kind == 2 ? N : ld16, ds.out_kind == 2);
+  op_timed(2.0 * M * (double)N * K, [&] { launch_gemm(stream_, g); });
   if (ds.out_kind == 0) {
-    PF_HIP(hipMemcpy2DAsync(C, (size_t)N * 4, base + oC, (size_t)ld32 * 4, (size_t)N * 4, M, hipMemcpyDeviceToHost, stream_));
+    check_guard(stream_, "gemm_ex: the fp32 result", c32, kSentinel32, result_geom(Mp, M, N, ld32, round_up(M, 256)));
+    download2d(stream_, C, N, (const float*)c32, ld32, N, M);
     PF_HIP(hipStreamSynchronize(stream_));
   } else {
-    const size_t rows = ds.out_kind == 2 ? (size_t)round_up(M, 32) : (size_t)M;
-    const size_t ld = ds.out_kind == 2 ? (size_t)N : (size_t)ld16;
-    std::vector<half_t> tmp(rows * ld);
-    PF_HIP(hipMemcpyAsync(tmp.data(), base + oC, tmp.size() * 2, hipMemcpyDeviceToHost, stream_));
-    PF_HIP(hipStreamSynchronize(stream_));
-    for (int m = 0; m < M; ++m)
-      for (int n = 0; n < N; ++n) {
-        const size_t idx = ds.out_kind == 2 ? (((size_t)(m >> 5) * (N >> 3) + (n >> 3)) * 32 + (m & 31)) * 8 + (n & 7)
-                                            : (size_t)m * ld + n;
-        C[(size_t)m * N + n] = (float)tmp[idx];
-      }
+    check_guard(stream_, "gemm_ex: the f16 result", c16, kSentinel16, result_geom(Mp, M, N, ldc16, round_up(M, 256), ds.out_kind == 2));
+    if (ds.out_kind == 2) download_blocked16(stream_, C, c16, M, N, 0, N);
+    else download_f16(stream_, C, c16, M, N, ld16);
   }
 }
 
@@ -1471,60 +1312,39 @@ void Engine::op_gemm_panel(int M, int N, int out_kind, int form, int padded, con
   const int64_t Mp = round_up(M, 256) + 128, Np = round_up(N, 256);
   const int ld = out_kind == 1 ? N + 64 : (int)round_up(N, 4);
   PF_CHECK(ld % 4 == 0, PF_ERR_INVALID_ARG, "gemm_panel: the f16 form needs N % 4 == 0");
-  const size_t esz = out_kind == 1 ? 2 : 4;
-  size_t off = 0;
-  const Carve carve{off};
-  const size_t oA = carve((size_t)M * K * 4), oW = carve((size_t)N * K * 4), ob = carve((size_t)N * 4);
-  const size_t oA16 = carve((size_t)Mp * K * 2), oW16 = carve((size_t)Np * K * 2), oI = carve(gemm_panel_image_bytes(N));
-  const size_t oC = carve((size_t)Mp * ld * esz);
-  ensure(ws_tmp_, off);
-  char* base = (char*)ws_tmp_.p;
-  PF_HIP(hipMemsetD16Async((hipDeviceptr_t)(base + oA16), 0x7E00, (size_t)Mp * K, stream_));     // NaN behind the operands
-  PF_HIP(hipMemsetD16Async((hipDeviceptr_t)(base + oW16), 0x7E00, (size_t)Np * K, stream_));
-  PF_HIP(hipMemcpyAsync(base + oA, A, (size_t)M * K * 4, hipMemcpyHostToDevice, stream_));
-  launch_f32_to_f16(stream_, (const float*)(base + oA), M, K, K, (half_t*)(base + oA16), K);
-  PF_HIP(hipMemcpyAsync(base + oW, W, (size_t)N * K * 4, hipMemcpyHostToDevice, stream_));
-  launch_f32_to_f16(stream_, (const float*)(base + oW), N, K, K, (half_t*)(base + oW16), K);
-  launch_gemm_panel_retile(stream_, (const half_t*)(base + oW16), K, N, (half_t*)(base + oI));
-  if (bias) PF_HIP(hipMemcpyAsync(base + ob, bias, (size_t)N * 4, hipMemcpyHostToDevice, stream_));
-  if (out_kind == 0) fill_sentinel32(stream_, base + oC, (size_t)Mp * ld);
-  else fill_sentinel16(stream_, base + oC, (size_t)Mp * ld);
+  StageCarve st;
+  const auto dA = st.take<float>((size_t)M * K), dW = st.take<float>((size_t)N * K), db = st.take<float>(N);
+  const auto dA16 = st.take<half_t>((size_t)Mp * K), dW16 = st.take<half_t>((size_t)Np * K), dI = st.take<half_t>(gemm_panel_image_bytes(N) / 2);
+  const auto dC = st.take<uint8_t>((size_t)Mp * ld * (out_kind == 1 ? 2 : 4));   // (either result kind)
+  void* ws = op_ws(st);
+  float* c32 = (float*)dC(ws);
+  half_t* c16 = (half_t*)dC(ws);
+  PF_HIP(hipMemsetD16Async((hipDeviceptr_t)dA16(ws), 0x7E00, (size_t)Mp * K, stream_));     // NaN behind the operands
+  PF_HIP(hipMemsetD16Async((hipDeviceptr_t)dW16(ws), 0x7E00, (size_t)Np * K, stream_));
+  upload_f16(stream_, dA(ws), A, M, K, dA16(ws), K);
+  upload_f16(stream_, dW(ws), W, N, K, dW16(ws), K);
+  launch_gemm_panel_retile(stream_, dW16(ws), K, N, dI(ws));
+  if (bias) upload(stream_, db(ws), bias, N);
+  if (out_kind == 0) fill_sentinel(stream_, c32, (size_t)Mp * ld);
+  else fill_sentinel(stream_, c16, (size_t)Mp * ld);
   GemmArgs g{};
-  g.A = (half_t*)(base + oA16); g.lda = K; g.W = (half_t*)(base + oW16); g.ldw = K; g.W_panel = (half_t*)(base + oI);
-  g.bias = bias ? (const float*)(base + ob) : nullptr;
+  g.A = dA16(ws); g.lda = K; g.W = dW16(ws); g.ldw = K; g.W_panel = dI(ws);
+  g.bias = bias ? db(ws) : nullptr;
   g.M = M; g.N = N; g.K = K;
   g.out_padded = padded ? 1 : 0;
   g.force_mi = form;
-  if (out_kind == 0) { g.out_f32 = (float*)(base + oC); g.ldc32 = ld; }
-  else { g.out_f16 = (half_t*)(base + oC); g.ldc16 = ld; }
-  static const int reps = [] { const char* e = getenv("PF_OP_REPEAT"); return e ? std::max(1, atoi(e)) : 1; }();   // tools/: warm-cache timing
-  for (int r = 0; r < reps; ++r) {
-    prof_begin(r == 0 ? "gemm_op" : "gemm_op_warm", 2.0 * M * (double)N * K);
-    launch_gemm(stream_, g);
-    prof_end(r == 0 ? "gemm_op" : "gemm_op_warm");
+  if (out_kind == 0) { g.out_f32 = c32; g.ldc32 = ld; }
+  else { g.out_f16 = c16; g.ldc16 = ld; }
+  op_timed(2.0 * M * (double)N * K, [&] { launch_gemm(stream_, g); });
+  const GuardGeom geom = result_geom(Mp, M, N, ld, padded ? round_up(M, 256) : M);   // (rows the destination does not declare writable)
+  if (out_kind == 0) {
+    check_guard(stream_, "gemm_panel: the fp32 result", c32, kSentinel32, geom);
+    download2d(stream_, C, N, (const float*)c32, ld, N, M);
+    PF_HIP(hipStreamSynchronize(stream_));
+  } else {
+    check_guard(stream_, "gemm_panel: the f16 result", c16, kSentinel16, geom);
+    download_f16(stream_, C, c16, M, N, ld);
   }
-  std::vector<char> h((size_t)Mp * ld * esz);
-  PF_HIP(hipMemcpyAsync(h.data(), base + oC, h.size(), hipMemcpyDeviceToHost, stream_));
-  PF_HIP(hipStreamSynchronize(stream_));
-  const int64_t guard = padded ? round_up(M, 256) : M;
-  for (int64_t m = 0; m < Mp; ++m)
-    for (int n = 0; n < ld; ++n) {
-      const size_t i = (size_t)m * ld + n;
-      const bool is_sent = out_kind == 1 ? reinterpret_cast<const uint16_t*>(h.data())[i] == kSentinel16
-                                         : reinterpret_cast<const uint32_t*>(h.data())[i] == kSentinel32;
-      const char* why = nullptr;
-      if (m < M && n < N) { if (is_sent) why = "was not written"; }
-      else if (n >= N) { if (!is_sent) why = "was written: a column beyond N"; }
-      else if (m >= guard && !is_sent) why = "was written: a row the destination does not declare writable";
-      if (why)
-        throw Error(PF_ERR_DEVICE, "gemm_panel (" + std::to_string(M) + " x " + std::to_string(N) + ", ld " + std::to_string(ld) + "): cell (" +
-                                       std::to_string(m) + ", " + std::to_string(n) + ") " + why);
-    }
-  for (int m = 0; m < M; ++m)
-    for (int n = 0; n < N; ++n) {
-      const size_t i = (size_t)m * ld + n;
-      C[(size_t)m * N + n] = out_kind == 1 ? (float)reinterpret_cast<const half_t*>(h.data())[i] : reinterpret_cast<const float*>(h.data())[i];
-    }
 }
 
 void Engine::op_gemm_rc(const pf_gemm_rc_desc& ds, const float* A, const float* W, float* x_out, float* n16_out,
@@ -1536,65 +1356,48 @@ void Engine::op_gemm_rc(const pf_gemm_rc_desc& ds, const float* A, const float* 
   PF_CHECK((ds.ln_gamma != nullptr) == (ds.ln_beta != nullptr), PF_ERR_INVALID_ARG, "gemm_rc: gamma and beta go together");
   const int64_t Mp = round_up(M, 256) + 128;
   const int k = ds.fsmn_k;
-  size_t off = 0;
-  const Carve carve{off};
-  const size_t o32 = carve((size_t)std::max<int64_t>((int64_t)M * std::max(K, N), (int64_t)N * K) * 4);
-  const size_t oA16 = carve((size_t)Mp * K * 2), oW16 = carve((size_t)N * K * 2), ob = carve((size_t)N * 4);
-  const size_t oR = carve((size_t)Mp * N * 4), oV = carve((size_t)(Mp + 128) * 3 * N * 2), owT = carve((size_t)std::max(k, 1) * N * 4);
-  const size_t og = carve((size_t)N * 4), obe = carve((size_t)N * 4), oX = carve((size_t)Mp * N * 4), oN16 = carve((size_t)Mp * N * 2);
-  const size_t oN32 = carve((size_t)Mp * N * 4);
-  ensure(ws_tmp_, off);
-  char* base = (char*)ws_tmp_.p;
-  PF_HIP(hipMemsetAsync(base + oA16, 0, (size_t)Mp * K * 2, stream_));
-  std::vector<half_t> ablk;
-  if (ds.a_blocked) {
-    ablk.assign((size_t)Mp * K, (half_t)0.f);
-    for (int m = 0; m < M; ++m)
-      for (int kk = 0; kk < K; ++kk)
-        ablk[(((size_t)(m >> 5) * (K >> 3) + (kk >> 3)) * 32 + (m & 31)) * 8 + (kk & 7)] = (half_t)A[(size_t)m * K + kk];
-    fill_hostile_blocked(ablk, M, Mp, K, K);
-    PF_HIP(hipMemcpyAsync(base + oA16, ablk.data(), ablk.size() * 2, hipMemcpyHostToDevice, stream_));
-  } else {
-    fill_hostile_rows(stream_, (half_t*)(base + oA16), K, M, Mp, K);
-    PF_HIP(hipMemcpyAsync(base + o32, A, (size_t)M * K * 4, hipMemcpyHostToDevice, stream_));
-    launch_f32_to_f16(stream_, (const float*)(base + o32), M, K, K, (half_t*)(base + oA16), K);
-    PF_HIP(hipStreamSynchronize(stream_));
-  }
-  PF_HIP(hipMemcpyAsync(base + o32, W, (size_t)N * K * 4, hipMemcpyHostToDevice, stream_));
-  launch_f32_to_f16(stream_, (const float*)(base + o32), N, K, K, (half_t*)(base + oW16), K);
-  PF_HIP(hipStreamSynchronize(stream_));
+  StageCarve st;
+  const auto d32 = st.take<float>((size_t)std::max<int64_t>((int64_t)M * std::max(K, N), (int64_t)N * K));   // the fp32 staging slot
+  const auto dA16 = st.take<half_t>((size_t)Mp * K), dW16 = st.take<half_t>((size_t)N * K);
+  const auto db = st.take<float>(N), dR = st.take<float>((size_t)Mp * N);
+  const auto dV = st.take<half_t>((size_t)(Mp + 128) * 3 * N);
+  const auto dwT = st.take<float>((size_t)std::max(k, 1) * N), dg = st.take<float>(N), dbe = st.take<float>(N), dX = st.take<float>((size_t)Mp * N);
+  const auto dN16 = st.take<half_t>((size_t)Mp * N);
+  const auto dN32 = st.take<float>((size_t)Mp * N);
+  void* ws = op_ws(st);
+  if (ds.a_blocked) upload_blocked16(stream_, A, M, K, dA16(ws), K, Mp);
+  else upload_operand16(stream_, d32(ws), A, M, K, dA16(ws), K, Mp);
+  upload_f16(stream_, d32(ws), W, N, K, dW16(ws), K);
   GemmRcArgs g{};
-  g.A = (half_t*)(base + oA16); g.lda = K; g.a_blocked = ds.a_blocked ? 1 : 0;
-  g.W = (half_t*)(base + oW16); g.ldw = K; g.M = M; g.K = K;
-  if (ds.bias) { PF_HIP(hipMemcpyAsync(base + ob, ds.bias, (size_t)N * 4, hipMemcpyHostToDevice, stream_)); g.bias = (const float*)(base + ob); }
-  if (ds.resid) { PF_HIP(hipMemcpyAsync(base + oR, ds.resid, (size_t)M * N * 4, hipMemcpyHostToDevice, stream_)); g.resid = (const float*)(base + oR); g.ldr = N; }
+  g.A = dA16(ws); g.lda = K; g.a_blocked = ds.a_blocked ? 1 : 0;
+  g.W = dW16(ws); g.ldw = K; g.M = M; g.K = K;
+  if (ds.bias) { upload(stream_, db(ws), ds.bias, N); g.bias = db(ws); }
+  if (ds.resid) { upload(stream_, dR(ws), ds.resid, (size_t)M * N); g.resid = dR(ws); g.ldr = N; }
   std::vector<float> wT;
   if (ds.fsmn_v) {
     // the V slice of a [M, 3*512] QKV buffer, as in the pipeline (row stride 1536 halves); the rows in front of it and
     // behind it, and the Q | K columns, are hostile
-    fill_hostile_rows(stream_, (half_t*)(base + oV), 3 * N, 0, Mp + 128, 3 * N);
-    half_t* vs = (half_t*)(base + oV) + (size_t)kVLead * 3 * N + 2 * N;
-    PF_HIP(hipMemcpyAsync(base + o32, ds.fsmn_v, (size_t)M * N * 4, hipMemcpyHostToDevice, stream_));
-    launch_f32_to_f16(stream_, (const float*)(base + o32), M, N, N, vs, 3 * N);
-    wT.resize((size_t)k * N);
-    for (int c = 0; c < N; ++c)
-      for (int j = 0; j < k; ++j) wT[(size_t)j * N + c] = ds.fsmn_w[(size_t)c * k + j];
-    PF_HIP(hipMemcpyAsync(base + owT, wT.data(), wT.size() * 4, hipMemcpyHostToDevice, stream_));
-    g.fsmn_v = vs; g.ldv = 3 * N; g.fsmn_wT = (const float*)(base + owT); g.fsmn_k = k;
+    fill_hostile_rows(stream_, dV(ws), 3 * N, 0, Mp + 128, 3 * N);
+    half_t* vs = dV(ws) + (size_t)kVLead * 3 * N + 2 * N;
+    upload_f16(stream_, d32(ws), ds.fsmn_v, M, N, vs, 3 * N);
+    wT = fsmn_taps(ds.fsmn_w, N, k);
+    upload(stream_, dwT(ws), wT.data(), wT.size());
+    g.fsmn_v = vs; g.ldv = 3 * N; g.fsmn_wT = dwT(ws); g.fsmn_k = k;
   }
   g.T = ds.T > 0 ? ds.T : M;
-  fill_sentinel32(stream_, base + oX, (size_t)Mp * N);
-  fill_sentinel16(stream_, base + oN16, (size_t)Mp * N);
-  fill_sentinel32(stream_, base + oN32, (size_t)Mp * N);
+  fill_sentinel(stream_, dX(ws), (size_t)Mp * N);
+  fill_sentinel(stream_, dN16(ws), (size_t)Mp * N);
+  fill_sentinel(stream_, dN32(ws), (size_t)Mp * N);
   if (ds.ln_gamma) {
-    PF_HIP(hipMemcpyAsync(base + og, ds.ln_gamma, (size_t)N * 4, hipMemcpyHostToDevice, stream_));
-    PF_HIP(hipMemcpyAsync(base + obe, ds.ln_beta, (size_t)N * 4, hipMemcpyHostToDevice, stream_));
-    g.ln_g = (const float*)(base + og); g.ln_b = (const float*)(base + obe); g.eps = 1e-12f;
-    if (n16_out) { g.out_n16 = (half_t*)(base + oN16); g.ldn16 = N; }
-    if (n32_out) { g.out_n32 = (float*)(base + oN32); g.ldn32 = N; }
+    upload(stream_, dg(ws), ds.ln_gamma, N);
+    upload(stream_, dbe(ws), ds.ln_beta, N);
+    g.ln_g = dg(ws); g.ln_b = dbe(ws); g.eps = 1e-12f;
+    if (n16_out) { g.out_n16 = dN16(ws); g.ldn16 = N; }
+    if (n32_out) { g.out_n32 = dN32(ws); g.ldn32 = N; }
   }
-  if (x_out) { g.out_x = (float*)(base + oX); g.ldx = N; }
+  if (x_out) { g.out_x = dX(ws); g.ldx = N; }
   PF_CHECK(!ds.split_k, PF_ERR_UNSUPPORTED, "gemm_rc: the split-K forms (k_gemm_sk.hip) were removed in round 5 — the fused FFN block replaced them (numbers: profiles/round4_splitk_pairs.txt)");
+  const GuardGeom geom = result_geom(Mp, M, N, N, round_up(M, 256));
   if (ds.short_input) {
     // the short-input forms of the same nodes, as enc_layer / the decoder run them for M <= 512 rows
     PF_CHECK(!ds.a_blocked, PF_ERR_INVALID_ARG, "gemm_rc: the short-input kernels take a row-major A");
@@ -1602,7 +1405,7 @@ void Engine::op_gemm_rc(const pf_gemm_rc_desc& ds, const float* A, const float* 
     q.A = g.A; q.lda = K; q.W = g.W; q.ldw = K; q.bias = g.bias; q.M = M; q.N = N; q.K = K; q.ws = small_ws_;
     q.resid = g.resid; q.ldr = N;
     const bool need_x = g.out_x || (g.ln_g && K <= 576);
-    if (need_x) { q.out_f32 = (float*)(base + oX); q.ldc32 = N; }
+    if (need_x) { q.out_f32 = dX(ws); q.ldc32 = N; }
     if (K <= 576) {
       q.fsmn_v = g.fsmn_v; q.ldv = g.ldv; q.fsmn_wT = g.fsmn_wT; q.fsmn_k = g.fsmn_k; q.T = g.T;
       prof_begin("gemm_op", 2.0 * M * (double)N * K);
@@ -1616,24 +1419,19 @@ void Engine::op_gemm_rc(const pf_gemm_rc_desc& ds, const float* A, const float* 
       launch_gemm_small(stream_, q);
       prof_end("gemm_op");
     }
-    if (q.out_f32) check_guard<uint32_t>(stream_, "gemm_rc", "x", base + oX, kSentinel32, Mp, M, N, N, false);
+    if (q.out_f32) check_guard(stream_, "gemm_rc: x", dX(ws), kSentinel32, geom);
   } else {
     prof_begin("gemm_op", 2.0 * M * (double)N * K);
     launch_gemm_rc(stream_, g);
     prof_end("gemm_op");
-    if (g.out_x) check_guard<uint32_t>(stream_, "gemm_rc", "x", base + oX, kSentinel32, Mp, M, N, N, false);
+    if (g.out_x) check_guard(stream_, "gemm_rc: x", dX(ws), kSentinel32, geom);
   }
-  if (g.out_n16) check_guard<uint16_t>(stream_, "gemm_rc", "the f16 LayerNorm result", base + oN16, kSentinel16, Mp, M, N, N, false);
-  if (g.out_n32) check_guard<uint32_t>(stream_, "gemm_rc", "the fp32 LayerNorm result", base + oN32, kSentinel32, Mp, M, N, N, false);
-  if (x_out) PF_HIP(hipMemcpyAsync(x_out, base + oX, (size_t)M * N * 4, hipMemcpyDeviceToHost, stream_));
-  if (g.out_n32) PF_HIP(hipMemcpyAsync(n32_out, base + oN32, (size_t)M * N * 4, hipMemcpyDeviceToHost, stream_));
-  std::vector<half_t> tmp;
-  if (g.out_n16) {
-    tmp.resize((size_t)M * N);
-    PF_HIP(hipMemcpyAsync(tmp.data(), base + oN16, tmp.size() * 2, hipMemcpyDeviceToHost, stream_));
-  }
+  if (g.out_n16) check_guard(stream_, "gemm_rc: the f16 LayerNorm result", dN16(ws), kSentinel16, geom);
+  if (g.out_n32) check_guard(stream_, "gemm_rc: the fp32 LayerNorm result", dN32(ws), kSentinel32, geom);
+  if (x_out) download(stream_, x_out, (const float*)dX(ws), (size_t)M * N);
+  if (g.out_n32) download(stream_, n32_out, (const float*)dN32(ws), (size_t)M * N);
   PF_HIP(hipStreamSynchronize(stream_));
-  for (size_t i = 0; i < tmp.size(); ++i) n16_out[i] = (float)tmp[i];
+  if (g.out_n16) download_f16(stream_, n16_out, dN16(ws), M, N, N);
 }
 
 // Encoder FFN as enc_layer() runs it: FFN-up writes the hidden in the blocked activation layout (kind 3),
@@ -1643,45 +1441,37 @@ void Engine::op_ffn(const float* x, const float* w1, const float* b1, const floa
   PF_HIP(hipSetDevice(device_));
   PF_CHECK(M > 0 && D % 64 == 0 && F % 64 == 0, PF_ERR_INVALID_ARG, "ffn: D and F must be multiples of 64");
   const int64_t Mp = round_up(M, 256) + 128, Fp = round_up(F, 256), Dp = round_up(D, 256);
-  size_t off = 0;
-  const Carve carve{off};
-  const size_t o32 = carve((size_t)std::max<int64_t>((int64_t)M * D, (int64_t)F * D) * 4);
-  const size_t ox16 = carve((size_t)Mp * D * 2), ow1 = carve((size_t)Fp * D * 2), ow2 = carve((size_t)Dp * F * 2);
-  const size_t ob1 = carve((size_t)F * 4), ob2 = carve((size_t)D * 4), oh = carve((size_t)Mp * F * 2);
-  const size_t oxr = carve((size_t)Mp * D * 4);
-  ensure(ws_tmp_, off);
-  char* base = (char*)ws_tmp_.p;
-  PF_HIP(hipMemsetAsync(base + ox16, 0, oxr - ox16, stream_));
-  auto up16 = [&](const float* src, int rows, int cols, size_t dst) {
-    PF_HIP(hipMemcpyAsync(base + o32, src, (size_t)rows * cols * 4, hipMemcpyHostToDevice, stream_));
-    launch_f32_to_f16(stream_, (const float*)(base + o32), rows, cols, cols, (half_t*)(base + dst), cols);
-    PF_HIP(hipStreamSynchronize(stream_));
-  };
-  fill_hostile_rows(stream_, (half_t*)(base + ox16), D, M, Mp, D);
-  fill_hostile_rows(stream_, (half_t*)(base + ow1), D, F, Fp, D);
-  fill_hostile_rows(stream_, (half_t*)(base + ow2), F, D, Dp, F);
-  fill_sentinel16(stream_, base + oh, (size_t)Mp * F);
-  fill_sentinel32(stream_, base + oxr, (size_t)Mp * D);
-  up16(x, M, D, ox16); up16(w1, F, D, ow1); up16(w2, D, F, ow2);
-  PF_HIP(hipMemcpyAsync(base + ob1, b1, (size_t)F * 4, hipMemcpyHostToDevice, stream_));
-  PF_HIP(hipMemcpyAsync(base + ob2, b2, (size_t)D * 4, hipMemcpyHostToDevice, stream_));
-  PF_HIP(hipMemcpyAsync(base + oxr, resid, (size_t)M * D * 4, hipMemcpyHostToDevice, stream_));
+  StageCarve st;
+  const auto d32 = st.take<float>((size_t)std::max<int64_t>((int64_t)M * D, (int64_t)F * D));   // the fp32 staging slot
+  const auto dx16 = st.take<half_t>((size_t)Mp * D), dw1 = st.take<half_t>((size_t)Fp * D), dw2 = st.take<half_t>((size_t)Dp * F);
+  const auto db1 = st.take<float>(F), db2 = st.take<float>(D);
+  const auto dh = st.take<half_t>((size_t)Mp * F);
+  const auto dxr = st.take<float>((size_t)Mp * D);
+  void* ws = op_ws(st);
+  fill_sentinel(stream_, dh(ws), (size_t)Mp * F);
+  fill_sentinel(stream_, dxr(ws), (size_t)Mp * D);
+  upload_operand16(stream_, d32(ws), x, M, D, dx16(ws), D, Mp);
+  upload_operand16(stream_, d32(ws), w1, F, D, dw1(ws), D, Fp);
+  upload_operand16(stream_, d32(ws), w2, D, F, dw2(ws), F, Dp);
+  upload(stream_, db1(ws), b1, F);
+  upload(stream_, db2(ws), b2, D);
+  upload(stream_, dxr(ws), resid, (size_t)M * D);
   Lin L1, L2;
-  L1.w = (half_t*)(base + ow1); L1.bias = (const float*)(base + ob1); L1.N = F; L1.K = D; L1.Kpad = D;
-  L2.w = (half_t*)(base + ow2); L2.bias = (const float*)(base + ob2); L2.N = D; L2.K = F; L2.Kpad = F;
-  float* xr = (float*)(base + oxr);
-  gemm("gemm_ffn1", L1, (half_t*)(base + ox16), D, M, nullptr, 0, (half_t*)(base + oh), F, nullptr, 0, nullptr, 0, true, 0, 1.f, true, 1);
-  gemm("gemm_ffn2", L2, (half_t*)(base + oh), F, M, xr, D, nullptr, 0, xr, D, nullptr, 0, false, 0, 1.f, true, 2);
-  check_guard<uint16_t>(stream_, "ffn", "the blocked hidden", base + oh, kSentinel16, Mp, M, F, F, true);
-  check_guard<uint32_t>(stream_, "ffn", "the result (in place on the residual)", xr, kSentinel32, Mp, M, D, D, false, false);
-  PF_HIP(hipMemcpyAsync(y, xr, (size_t)M * D * 4, hipMemcpyDeviceToHost, stream_));
+  L1.w = dw1(ws); L1.bias = db1(ws); L1.N = F; L1.K = D; L1.Kpad = D;
+  L2.w = dw2(ws); L2.bias = db2(ws); L2.N = D; L2.K = F; L2.Kpad = F;
+  float* xr = dxr(ws);
+  gemm("gemm_ffn1", L1, dx16(ws), D, M, nullptr, 0, dh(ws), F, nullptr, 0, nullptr, 0, true, 0, 1.f, true, 1);
+  gemm("gemm_ffn2", L2, dh(ws), F, M, xr, D, nullptr, 0, xr, D, nullptr, 0, false, 0, 1.f, true, 2);
+  check_guard(stream_, "ffn: the blocked hidden", dh(ws), kSentinel16, result_geom(Mp, M, F, F, round_up(M, 256), true));
+  check_guard(stream_, "ffn: the result (in place on the residual)", xr, kSentinel32, result_geom(Mp, M, D, D, round_up(M, 256), false, false));
+  download(stream_, y, (const float*)xr, (size_t)M * D);
   PF_HIP(hipStreamSynchronize(stream_));
 }
 
-// The encoder FFN block as enc_layer() launches it for long inputs: retile W1 / W2, then ONE launch of ffn_fused_kernel.
 // The decoder's FFN block in the split form of the fused kernel (k_ffn.hip), standalone: t = LN_F(relu(f16(x) W1^T + b1)) W2^T,
 // n = LayerNorm(t); x = the block's normalised input, or (ds.ctx) LayerNorm norm1 of x_out = resid + ctx Wo^T + bo computed by
-// the same launch.
+// the same launch.  A hostile host (see the top of the file): the operand rows behind M - 1 hold the large finite pattern, the
+// residual's too, every output and the bytes behind the workspace are sentinel-filled and checked against kernels.h's contract.
 void Engine::op_dec_ffn_fused(const pf_dec_ffn_desc& ds, float* t_out, float* n_out, float* x_out) {
   PF_HIP(hipSetDevice(device_));
   const int D = 512, F = 2048, M = ds.M, splits = ds.splits;
@@ -1690,69 +1480,59 @@ void Engine::op_dec_ffn_fused(const pf_dec_ffn_desc& ds, float* t_out, float* n_
            "dec_ffn_fused: splits must be 0 (automatic) | 1 | 2 | 3 | 4 | 8");
   const bool op = ds.ctx != nullptr;
   const int64_t Mp = round_up(M, 256) + 128;
-  size_t off = 0;
-  const Carve carve{off};
-  const size_t o32 = carve((size_t)std::max<int64_t>((int64_t)M * D, (int64_t)F * D) * 4);
-  const size_t ox16 = carve((size_t)Mp * D * 2), ow1 = carve((size_t)F * D * 2), ow2 = carve((size_t)D * F * 4);
   const size_t wsb = ffn_dec_workspace_bytes(M, splits);
-  const size_t oimg = carve(ffn_dec_image_bytes()), ows = carve(wsb + kWsGuard);
-  const size_t ob1 = carve((size_t)F * 4), ogf = carve((size_t)F * 4), obf = carve((size_t)F * 4), og = carve((size_t)D * 4), obe = carve((size_t)D * 4);
-  const size_t ot = carve((size_t)Mp * D * 4), on = carve((size_t)Mp * D * 4);
-  const size_t owo = carve((size_t)D * D * 2), owot = carve(ffn_outproj_weight_bytes()), obo = carve((size_t)D * 4);
-  const size_t og1 = carve((size_t)D * 4), obe1 = carve((size_t)D * 4), oxr = carve((size_t)Mp * D * 4), oxo = carve((size_t)Mp * D * 4);
-  ensure(ws_tmp_, off);
-  char* base = (char*)ws_tmp_.p;
-  // a hostile host (see the top of the file): the operand rows behind M - 1 hold the large finite pattern, the residual's too,
-  // every output and the bytes behind the workspace are sentinel-filled and checked against kernels.h's contract
-  fill_hostile_rows(stream_, (half_t*)(base + ox16), D, M, Mp, D);
-  fill_sentinel32(stream_, base + ot, (size_t)Mp * D);
-  fill_sentinel32(stream_, base + on, (size_t)Mp * D);
-  fill_sentinel32(stream_, base + oxo, (size_t)Mp * D);
-  fill_sentinel32(stream_, base + ows + wsb, kWsGuard / 4);
-  auto up16 = [&](const float* src, int rows, int cols, size_t dst, int ldo) {
-    PF_HIP(hipMemcpyAsync(base + o32, src, (size_t)rows * cols * 4, hipMemcpyHostToDevice, stream_));
-    launch_f32_to_f16(stream_, (const float*)(base + o32), rows, cols, cols, (half_t*)(base + dst), ldo);
-    PF_HIP(hipStreamSynchronize(stream_));
-  };
-  auto up = [&](const float* src, size_t n, size_t dst) { PF_HIP(hipMemcpyAsync(base + dst, src, n * 4, hipMemcpyHostToDevice, stream_)); };
-  up16(op ? ds.ctx : ds.x, M, D, ox16, D); up16(ds.w1, F, D, ow1, D);
-  up(ds.w2, (size_t)D * F, ow2); up(ds.b1, F, ob1); up(ds.gamma_f, F, ogf); up(ds.beta_f, F, obf);
-  if (ds.ln_gamma) { up(ds.ln_gamma, D, og); up(ds.ln_beta, D, obe); }
-  launch_ffn_dec_retile(stream_, (const half_t*)(base + ow1), D, (const float*)(base + ow2), (const float*)(base + ogf),
-                        (const float*)(base + obf), (const float*)(base + ob1), (half_t*)(base + oimg));
+  StageCarve st;
+  const auto d32 = st.take<float>((size_t)std::max<int64_t>((int64_t)M * D, (int64_t)F * D));   // the fp32 staging slot
+  const auto dx16 = st.take<half_t>((size_t)Mp * D), dw1 = st.take<half_t>((size_t)F * D);
+  const auto dw2 = st.take<float>((size_t)D * F);
+  const auto dimg = st.take<half_t>(ffn_dec_image_bytes() / 2);
+  const auto dws = st.take<uint8_t>(wsb + kWsGuard);
+  const auto db1 = st.take<float>(F), dgf = st.take<float>(F), dbf = st.take<float>(F), dg = st.take<float>(D), dbe = st.take<float>(D);
+  const auto dt = st.take<float>((size_t)Mp * D), dn = st.take<float>((size_t)Mp * D);
+  const auto dwo = st.take<half_t>((size_t)D * D), dwot = st.take<half_t>(ffn_outproj_weight_bytes() / 2);
+  const auto dbo = st.take<float>(D), dg1 = st.take<float>(D), dbe1 = st.take<float>(D);
+  const auto dxr = st.take<float>((size_t)Mp * D), dxo = st.take<float>((size_t)Mp * D);
+  void* ws = op_ws(st);
+  uint32_t* behind_ws = (uint32_t*)(dws(ws) + wsb);
+  fill_sentinel(stream_, dt(ws), (size_t)Mp * D);
+  fill_sentinel(stream_, dn(ws), (size_t)Mp * D);
+  fill_sentinel(stream_, dxo(ws), (size_t)Mp * D);
+  fill_sentinel(stream_, behind_ws, kWsGuard / 4);
+  upload_operand16(stream_, d32(ws), op ? ds.ctx : ds.x, M, D, dx16(ws), D, Mp);
+  upload_f16(stream_, d32(ws), ds.w1, F, D, dw1(ws), D);
+  upload(stream_, dw2(ws), ds.w2, (size_t)D * F); upload(stream_, db1(ws), ds.b1, F);
+  upload(stream_, dgf(ws), ds.gamma_f, F); upload(stream_, dbf(ws), ds.beta_f, F);
+  if (ds.ln_gamma) { upload(stream_, dg(ws), ds.ln_gamma, D); upload(stream_, dbe(ws), ds.ln_beta, D); }
+  launch_ffn_dec_retile(stream_, dw1(ws), D, dw2(ws), dgf(ws), dbf(ws), db1(ws), dimg(ws));
   FfnDecArgs f{};
-  f.A = (const half_t*)(base + ox16); f.lda = D; f.img = (const half_t*)(base + oimg); f.ws = base + ows; f.M = M; f.splits = splits;
+  f.A = dx16(ws); f.lda = D; f.img = dimg(ws); f.ws = dws(ws); f.M = M; f.splits = splits;
   f.eps_hidden = 1e-12f; f.eps = 1e-12f;
   if (op) {
-    up16(ds.wo, D, D, owo, D);
-    launch_ffn_retile_out(stream_, (const half_t*)(base + owo), D, (half_t*)(base + owot));
-    up(ds.bo, D, obo); up(ds.ln1_gamma, D, og1); up(ds.ln1_beta, D, obe1);
-    fill_hostile_rows32(stream_, (float*)(base + oxr), D, M, Mp);
-    up(ds.resid, (size_t)M * D, oxr);
-    f.A = nullptr; f.ctx = (const half_t*)(base + ox16); f.lda_c = D; f.Wot = (const half_t*)(base + owot); f.bo = (const float*)(base + obo);
-    f.resid = (const float*)(base + oxr); f.ldr = D; f.out_x = (float*)(base + oxo); f.ldx = D;
-    f.ln1_g = (const float*)(base + og1); f.ln1_b = (const float*)(base + obe1); f.eps1 = 1e-12f;
+    upload_f16(stream_, d32(ws), ds.wo, D, D, dwo(ws), D);
+    launch_ffn_retile_out(stream_, dwo(ws), D, dwot(ws));
+    upload(stream_, dbo(ws), ds.bo, D); upload(stream_, dg1(ws), ds.ln1_gamma, D); upload(stream_, dbe1(ws), ds.ln1_beta, D);
+    fill_hostile_rows32(stream_, dxr(ws), D, M, Mp);
+    upload(stream_, dxr(ws), ds.resid, (size_t)M * D);
+    f.A = nullptr; f.ctx = dx16(ws); f.lda_c = D; f.Wot = dwot(ws); f.bo = dbo(ws);
+    f.resid = dxr(ws); f.ldr = D; f.out_x = dxo(ws); f.ldx = D;
+    f.ln1_g = dg1(ws); f.ln1_b = dbe1(ws); f.eps1 = 1e-12f;
   }
-  if (t_out) { f.t32 = (float*)(base + ot); f.ldt = D; }
-  if (ds.ln_gamma) { f.ln_g = (const float*)(base + og); f.ln_b = (const float*)(base + obe); }
-  if (n_out) { f.n32 = (float*)(base + on); f.ldn32 = D; }
-  const char* rep = getenv("PF_OP_REPEAT");                        // tools/: repeated launches, timed as class "gemm_op_warm"
-  const int reps = rep ? std::max(1, atoi(rep)) : 1;
-  for (int r = 0; r < reps; ++r) {
-    prof_begin(r == 0 ? "gemm_op" : "gemm_op_warm", 4.0 * M * (double)D * F + (op ? 2.0 * M * (double)D * D : 0.0));
-    launch_ffn_dec(stream_, f);
-    prof_end(r == 0 ? "gemm_op" : "gemm_op_warm");
-  }
-  if (f.t32) check_guard<uint32_t>(stream_, "dec_ffn_fused", "t", base + ot, kSentinel32, Mp, M, D, D, false, true, M);
-  if (f.n32) check_guard<uint32_t>(stream_, "dec_ffn_fused", "the LayerNorm result", base + on, kSentinel32, Mp, M, D, D, false, true, M);
-  if (op) check_guard<uint32_t>(stream_, "dec_ffn_fused", "x_out", base + oxo, kSentinel32, Mp, M, D, D, false, true, M);
-  check_untouched32(stream_, "dec_ffn_fused", "the bytes behind ffn_dec_workspace_bytes", base + ows + wsb, kWsGuard);
-  if (t_out) PF_HIP(hipMemcpyAsync(t_out, base + ot, (size_t)M * D * 4, hipMemcpyDeviceToHost, stream_));
-  if (n_out) PF_HIP(hipMemcpyAsync(n_out, base + on, (size_t)M * D * 4, hipMemcpyDeviceToHost, stream_));
-  if (x_out && op) PF_HIP(hipMemcpyAsync(x_out, base + oxo, (size_t)M * D * 4, hipMemcpyDeviceToHost, stream_));
+  if (t_out) { f.t32 = dt(ws); f.ldt = D; }
+  if (ds.ln_gamma) { f.ln_g = dg(ws); f.ln_b = dbe(ws); }
+  if (n_out) { f.n32 = dn(ws); f.ldn32 = D; }
+  op_timed(4.0 * M * (double)D * F + (op ? 2.0 * M * (double)D * D : 0.0), [&] { launch_ffn_dec(stream_, f); });
+  const GuardGeom geom = result_geom(Mp, M, D, D, M);
+  if (f.t32) check_guard(stream_, "dec_ffn_fused: t", dt(ws), kSentinel32, geom);
+  if (f.n32) check_guard(stream_, "dec_ffn_fused: the LayerNorm result", dn(ws), kSentinel32, geom);
+  if (op) check_guard(stream_, "dec_ffn_fused: x_out", dxo(ws), kSentinel32, geom);
+  check_guard(stream_, "dec_ffn_fused: the bytes behind ffn_dec_workspace_bytes", behind_ws, kSentinel32, untouched_geom(kWsGuard / 4));
+  if (t_out) download(stream_, t_out, (const float*)dt(ws), (size_t)M * D);
+  if (n_out) download(stream_, n_out, (const float*)dn(ws), (size_t)M * D);
+  if (x_out && op) download(stream_, x_out, (const float*)dxo(ws), (size_t)M * D);
   PF_HIP(hipStreamSynchronize(stream_));
 }
 
+// The encoder FFN block as enc_layer() launches it for long inputs: retile W1 / W2, then ONE launch of ffn_fused_kernel.
 void Engine::op_ffn_fused(const float* x, const float* w1, const float* b1, const float* w2, const float* b2, const float* resid,
                           const float* g, const float* be, int M, float* x_out, float* n16_out, const pf_attn_ffn_desc* op) {
   PF_HIP(hipSetDevice(device_));
@@ -1760,113 +1540,87 @@ void Engine::op_ffn_fused(const float* x, const float* w1, const float* b1, cons
   PF_CHECK(M > 0, PF_ERR_INVALID_ARG, "ffn_fused: M must be positive");
   PF_CHECK(op || x, PF_ERR_INVALID_ARG, "ffn_fused: missing operand");
   const int64_t Mp = round_up(M, 256) + 128;
-  size_t off = 0;
-  const Carve carve{off};
-  const size_t o32 = carve((size_t)std::max<int64_t>((int64_t)M * D, (int64_t)F * D) * 4);
-  const size_t ox16 = carve((size_t)Mp * D * 2), ow1 = carve((size_t)F * D * 2), ow2 = carve((size_t)D * F * 2);
-  const size_t owt = carve(ffn_fused_weight_bytes());
-  const size_t ob1 = carve((size_t)F * 4), ob2 = carve((size_t)D * 4), og = carve((size_t)D * 4), obe = carve((size_t)D * 4);
-  const size_t oxr = carve((size_t)Mp * D * 4), oxo = carve((size_t)Mp * D * 4), on16 = carve((size_t)Mp * D * 2);
-  // out-projection form: Wo (f16 + its image), bias, the V slice inside a [M, 3 D] QKV-shaped buffer, taps, norm2, x_mid scratch
-  const size_t owo = carve((size_t)D * D * 2), owot = carve(ffn_outproj_weight_bytes()), obo = carve((size_t)D * 4);
-  const size_t ov = carve((size_t)(Mp + 128) * 3 * D * 2), owT = carve((size_t)11 * D * 4), og2 = carve((size_t)D * 4), obe2 = carve((size_t)D * 4);
   const bool tail = op && op->wqkv;
-  const size_t owq = carve((size_t)3 * D * D * 2), owqt = carve(3 * ffn_outproj_weight_bytes()), obq = carve((size_t)3 * D * 4);
-  const size_t oqk = carve((size_t)Mp * 2 * D * 2), ovo = carve((size_t)Mp * D * 2);
-  ensure(ws_tmp_, off);
-  char* base = (char*)ws_tmp_.p;
-  PF_HIP(hipMemsetAsync(base + ox16, 0, (size_t)Mp * D * 2, stream_));
-  PF_HIP(hipMemsetAsync(base + oxr, 0, (size_t)Mp * D * 4, stream_));
-  fill_hostile_rows32(stream_, (float*)(base + oxr), D, M, Mp);       // the residual rows behind M - 1 are never read (kernels.h)
-  if (tail) { fill_sentinel16(stream_, base + oqk, (size_t)Mp * 2 * D); fill_sentinel16(stream_, base + ovo, (size_t)Mp * D); }
-  auto up16 = [&](const float* src, int rows, int cols, size_t dst, int ldo) {
-    PF_HIP(hipMemcpyAsync(base + o32, src, (size_t)rows * cols * 4, hipMemcpyHostToDevice, stream_));
-    launch_f32_to_f16(stream_, (const float*)(base + o32), rows, cols, cols, (half_t*)(base + dst), ldo);
-    PF_HIP(hipStreamSynchronize(stream_));
-  };
-  fill_hostile_rows(stream_, (half_t*)(base + ox16), D, M, Mp, D);
-  fill_sentinel32(stream_, base + oxo, (size_t)Mp * D);
-  fill_sentinel16(stream_, base + on16, (size_t)Mp * D);
-  up16(op ? op->ctx : x, M, D, ox16, D); up16(w1, F, D, ow1, D); up16(w2, D, F, ow2, F);
-  PF_HIP(hipMemcpyAsync(base + ob1, b1, (size_t)F * 4, hipMemcpyHostToDevice, stream_));
-  PF_HIP(hipMemcpyAsync(base + ob2, b2, (size_t)D * 4, hipMemcpyHostToDevice, stream_));
-  if (resid) PF_HIP(hipMemcpyAsync(base + oxr, resid, (size_t)M * D * 4, hipMemcpyHostToDevice, stream_));
-  launch_ffn_retile(stream_, (half_t*)(base + ow1), D, (half_t*)(base + ow2), F, (half_t*)(base + owt));
+  StageCarve st;
+  const auto d32 = st.take<float>((size_t)std::max<int64_t>((int64_t)M * D, (int64_t)F * D));   // the fp32 staging slot
+  const auto dx16 = st.take<half_t>((size_t)Mp * D), dw1 = st.take<half_t>((size_t)F * D), dw2 = st.take<half_t>((size_t)D * F);
+  const auto dwt = st.take<half_t>(ffn_fused_weight_bytes() / 2);
+  const auto db1 = st.take<float>(F), db2 = st.take<float>(D), dg = st.take<float>(D), dbe = st.take<float>(D);
+  const auto dxr = st.take<float>((size_t)Mp * D), dxo = st.take<float>((size_t)Mp * D);
+  const auto dn16 = st.take<half_t>((size_t)Mp * D);
+  // out-projection form: Wo (f16 + its image), bias, the V slice inside a [M, 3 D] QKV-shaped buffer, taps, norm2
+  const auto dwo = st.take<half_t>((size_t)D * D), dwot = st.take<half_t>(ffn_outproj_weight_bytes() / 2);
+  const auto dbo = st.take<float>(D);
+  const auto dv = st.take<half_t>((size_t)(Mp + 128) * 3 * D);
+  const auto dwT = st.take<float>((size_t)11 * D), dg2 = st.take<float>(D), dbe2 = st.take<float>(D);
+  // the Q | K | V tail: the weight (f16 + its three images), bias, the blocked Q | K and the row-major V it writes
+  const auto dwq = st.take<half_t>((size_t)3 * D * D), dwqt = st.take<half_t>(3 * ffn_outproj_weight_bytes() / 2);
+  const auto dbq = st.take<float>((size_t)3 * D);
+  const auto dqk = st.take<half_t>((size_t)Mp * 2 * D), dvo = st.take<half_t>((size_t)Mp * D);
+  void* ws = op_ws(st);
+  PF_HIP(hipMemsetAsync(dxr(ws), 0, (size_t)Mp * D * 4, stream_));
+  fill_hostile_rows32(stream_, dxr(ws), D, M, Mp);                  // the residual rows behind M - 1 are never read (kernels.h)
+  if (tail) { fill_sentinel(stream_, dqk(ws), (size_t)Mp * 2 * D); fill_sentinel(stream_, dvo(ws), (size_t)Mp * D); }
+  fill_sentinel(stream_, dxo(ws), (size_t)Mp * D);
+  fill_sentinel(stream_, dn16(ws), (size_t)Mp * D);
+  upload_operand16(stream_, d32(ws), op ? op->ctx : x, M, D, dx16(ws), D, Mp);
+  upload_f16(stream_, d32(ws), w1, F, D, dw1(ws), D);
+  upload_f16(stream_, d32(ws), w2, D, F, dw2(ws), F);
+  upload(stream_, db1(ws), b1, F);
+  upload(stream_, db2(ws), b2, D);
+  if (resid) upload(stream_, dxr(ws), resid, (size_t)M * D);
+  launch_ffn_retile(stream_, dw1(ws), D, dw2(ws), F, dwt(ws));
   FfnFusedArgs f{};
-  f.A = (half_t*)(base + ox16); f.lda = D; f.Wt = (half_t*)(base + owt); f.b1 = (const float*)(base + ob1); f.b2 = (const float*)(base + ob2);
-  f.M = M; f.resid = resid || !op ? (const float*)(base + oxr) : nullptr; f.ldr = D; f.eps = 1e-12f;
+  f.A = dx16(ws); f.lda = D; f.Wt = dwt(ws); f.b1 = db1(ws); f.b2 = db2(ws);
+  f.M = M; f.resid = resid || !op ? dxr(ws) : nullptr; f.ldr = D; f.eps = 1e-12f;
   std::vector<float> wT;
   if (op) {
-    up16(op->wo, D, D, owo, D);
-    launch_ffn_retile_out(stream_, (half_t*)(base + owo), D, (half_t*)(base + owot));
-    fill_hostile_rows(stream_, (half_t*)(base + ov), 3 * D, 0, Mp + 128, 3 * D);      // as op_gemm_rc: hostile around the V slice
-    half_t* vs = (half_t*)(base + ov) + (size_t)kVLead * 3 * D + 2 * D;
-    PF_HIP(hipMemcpyAsync(base + o32, op->v, (size_t)M * D * 4, hipMemcpyHostToDevice, stream_));
-    launch_f32_to_f16(stream_, (const float*)(base + o32), M, D, D, vs, 3 * D);
-    PF_HIP(hipStreamSynchronize(stream_));
-    wT.resize((size_t)11 * D);
-    for (int c = 0; c < D; ++c)
-      for (int j = 0; j < 11; ++j) wT[(size_t)j * D + c] = op->fsmn_w[(size_t)c * 11 + j];
-    PF_HIP(hipMemcpyAsync(base + owT, wT.data(), wT.size() * 4, hipMemcpyHostToDevice, stream_));
-    PF_HIP(hipMemcpyAsync(base + obo, op->bo, (size_t)D * 4, hipMemcpyHostToDevice, stream_));
-    PF_HIP(hipMemcpyAsync(base + og2, op->ln2_gamma, (size_t)D * 4, hipMemcpyHostToDevice, stream_));
-    PF_HIP(hipMemcpyAsync(base + obe2, op->ln2_beta, (size_t)D * 4, hipMemcpyHostToDevice, stream_));
-    f.ctx = (half_t*)(base + ox16); f.lda_c = D; f.Wot = (half_t*)(base + owot); f.bo = (const float*)(base + obo);
-    f.fsmn_v = vs; f.ldv = 3 * D; f.fsmn_wT = (const float*)(base + owT); f.T = op->T > 0 ? op->T : M;
-    f.ln2_g = (const float*)(base + og2); f.ln2_b = (const float*)(base + obe2);
+    upload_f16(stream_, d32(ws), op->wo, D, D, dwo(ws), D);
+    launch_ffn_retile_out(stream_, dwo(ws), D, dwot(ws));
+    fill_hostile_rows(stream_, dv(ws), 3 * D, 0, Mp + 128, 3 * D);      // as op_gemm_rc: hostile around the V slice
+    half_t* vs = dv(ws) + (size_t)kVLead * 3 * D + 2 * D;
+    upload_f16(stream_, d32(ws), op->v, M, D, vs, 3 * D);
+    wT = fsmn_taps(op->fsmn_w, D, 11);
+    upload(stream_, dwT(ws), wT.data(), wT.size());
+    upload(stream_, dbo(ws), op->bo, D);
+    upload(stream_, dg2(ws), op->ln2_gamma, D);
+    upload(stream_, dbe2(ws), op->ln2_beta, D);
+    f.ctx = dx16(ws); f.lda_c = D; f.Wot = dwot(ws); f.bo = dbo(ws);
+    f.fsmn_v = vs; f.ldv = 3 * D; f.fsmn_wT = dwT(ws); f.T = op->T > 0 ? op->T : M;
+    f.ln2_g = dg2(ws); f.ln2_b = dbe2(ws);
     f.A = nullptr;
   }
   if (tail) {
     PF_CHECK(op->bqkv && g, PF_ERR_INVALID_ARG, "attn_ffn_fused: the Q | K | V tail needs its bias and the LayerNorm in front of it");
-    up16(op->wqkv, 3 * D, D, owq, D);
+    upload_f16(stream_, d32(ws), op->wqkv, 3 * D, D, dwq(ws), D);
     for (int part = 0; part < 3; ++part)
-      launch_ffn_retile_out(stream_, (half_t*)(base + owq) + (size_t)part * D * D, D,
-                            (half_t*)(base + owqt) + (size_t)part * (ffn_outproj_weight_bytes() / 2));
-    PF_HIP(hipMemcpyAsync(base + obq, op->bqkv, (size_t)3 * D * 4, hipMemcpyHostToDevice, stream_));
-    f.Wqt = (half_t*)(base + owqt); f.bq = (const float*)(base + obq); f.out_qk = (half_t*)(base + oqk); f.out_v = (half_t*)(base + ovo);
+      launch_ffn_retile_out(stream_, dwq(ws) + (size_t)part * D * D, D, dwqt(ws) + (size_t)part * (ffn_outproj_weight_bytes() / 2));
+    upload(stream_, dbq(ws), op->bqkv, (size_t)3 * D);
+    f.Wqt = dwqt(ws); f.bq = dbq(ws); f.out_qk = dqk(ws); f.out_v = dvo(ws);
     f.ldvo = D; f.qscale = 1.0f / std::sqrt(128.0f);
   }
-  if (x_out) { f.out_x = (float*)(base + oxo); f.ldx = D; }
+  if (x_out) { f.out_x = dxo(ws); f.ldx = D; }
   if (g) {
-    PF_HIP(hipMemcpyAsync(base + og, g, (size_t)D * 4, hipMemcpyHostToDevice, stream_));
-    PF_HIP(hipMemcpyAsync(base + obe, be, (size_t)D * 4, hipMemcpyHostToDevice, stream_));
-    f.ln_g = (const float*)(base + og); f.ln_b = (const float*)(base + obe);
-    if (n16_out) { f.out_n16 = (half_t*)(base + on16); f.ldn16 = D; }
+    upload(stream_, dg(ws), g, D);
+    upload(stream_, dbe(ws), be, D);
+    f.ln_g = dg(ws); f.ln_b = dbe(ws);
+    if (n16_out) { f.out_n16 = dn16(ws); f.ldn16 = D; }
   }
-  const char* rep = getenv("PF_OP_REPEAT");                        // tools/: repeated launches, timed as class "gemm_op_warm"
-  const int reps = rep ? std::max(1, atoi(rep)) : 1;
-  for (int r = 0; r < reps; ++r) {                                 // (resid is a separate buffer: repeats compute the same result)
-    prof_begin(r == 0 ? "gemm_op" : "gemm_op_warm", 4.0 * M * (double)D * F + (op ? 2.0 * M * (double)D * D : 0.0));
-    launch_ffn_fused(stream_, f);
-    prof_end(r == 0 ? "gemm_op" : "gemm_op_warm");
-  }
-  if (f.out_x) check_guard<uint32_t>(stream_, "ffn_fused", "x", base + oxo, kSentinel32, Mp, M, D, D, false, true, M);
-  if (f.out_n16) check_guard<uint16_t>(stream_, "ffn_fused", "the f16 LayerNorm result", base + on16, kSentinel16, Mp, M, D, D, false, true, M);
+  // (resid is a separate buffer: repeats compute the same result)
+  op_timed(4.0 * M * (double)D * F + (op ? 2.0 * M * (double)D * D : 0.0), [&] { launch_ffn_fused(stream_, f); });
+  if (f.out_x) check_guard(stream_, "ffn_fused: x", dxo(ws), kSentinel32, result_geom(Mp, M, D, D, M));
+  if (f.out_n16) check_guard(stream_, "ffn_fused: the f16 LayerNorm result", dn16(ws), kSentinel16, result_geom(Mp, M, D, D, M));
   if (tail) {
-    check_guard<uint16_t>(stream_, "attn_ffn_fused", "the blocked Q | K", base + oqk, kSentinel16, Mp, M, 2 * D, 2 * D, true, true, round_up(M, 64));
-    check_guard<uint16_t>(stream_, "attn_ffn_fused", "V", base + ovo, kSentinel16, Mp, M, D, D, false, true, round_up(M, 64));
+    check_guard(stream_, "attn_ffn_fused: the blocked Q | K", dqk(ws), kSentinel16, result_geom(Mp, M, 2 * D, 2 * D, round_up(M, 64), true));
+    check_guard(stream_, "attn_ffn_fused: V", dvo(ws), kSentinel16, result_geom(Mp, M, D, D, round_up(M, 64)));
   }
-  if (x_out) PF_HIP(hipMemcpyAsync(x_out, base + oxo, (size_t)M * D * 4, hipMemcpyDeviceToHost, stream_));
-  std::vector<half_t> n16;
-  if (f.out_n16) {
-    n16.resize((size_t)M * D);
-    PF_HIP(hipMemcpyAsync(n16.data(), base + on16, n16.size() * 2, hipMemcpyDeviceToHost, stream_));
-  }
+  if (x_out) download(stream_, x_out, (const float*)dxo(ws), (size_t)M * D);
   PF_HIP(hipStreamSynchronize(stream_));
-  if (f.out_n16)
-    for (size_t i = 0; i < n16.size(); ++i) n16_out[i] = (float)n16[i];
+  if (f.out_n16) download_f16(stream_, n16_out, dn16(ws), M, D, D);
   if (tail) {
-    std::vector<half_t> qk((size_t)Mp * 2 * D), vv((size_t)M * D);
-    PF_HIP(hipMemcpy(qk.data(), base + oqk, qk.size() * 2, hipMemcpyDeviceToHost));
-    PF_HIP(hipMemcpy(vv.data(), base + ovo, vv.size() * 2, hipMemcpyDeviceToHost));
-    for (int m = 0; m < M; ++m)
-      for (int n = 0; n < 2 * D; ++n) {                       // blocked [Mpad, 1024]: ((m / 32 * 128 + n / 8) * 32 + m % 32) * 8 + n % 8
-        const float val = (float)qk[(((size_t)(m >> 5) * 128 + (n >> 3)) * 32 + (m & 31)) * 8 + (n & 7)];
-        float* dst = n < D ? op->q_out : op->k_out;
-        if (dst) dst[(size_t)m * D + (n & (D - 1))] = val;
-      }
-    if (op->v_out)
-      for (size_t i = 0; i < vv.size(); ++i) op->v_out[i] = (float)vv[i];
+    if (op->q_out) download_blocked16(stream_, op->q_out, dqk(ws), M, 2 * D, 0, D);
+    if (op->k_out) download_blocked16(stream_, op->k_out, dqk(ws), M, 2 * D, D, D);
+    if (op->v_out) download_f16(stream_, op->v_out, dvo(ws), M, D, D);
   }
 }
 
@@ -1875,21 +1629,18 @@ void Engine::op_fsmn_enc(const float* v, const float* w, int B, int T, int D, in
   PF_HIP(hipSetDevice(device_));
   PF_CHECK(D % 8 == 0 && B > 0 && T > 0, PF_ERR_INVALID_ARG, "fsmn_enc: bad shape");
   const size_t n = (size_t)B * T * D;
-  std::vector<float> wT((size_t)D * k);
-  for (int c = 0; c < D; ++c)
-    for (int j = 0; j < k; ++j) wT[(size_t)j * D + c] = w[(size_t)c * k + j];
-  size_t off = 0;
-  const Carve carve{off};
-  const size_t ov = carve(n * 4), oq = carve(((size_t)B * T + 128) * 3 * D * 2), ow = carve(wT.size() * 4), oy = carve(n * 4);
-  ensure(ws_tmp_, off);
-  char* base = (char*)ws_tmp_.p;
-  PF_HIP(hipMemsetAsync(base + oq, 0, ((size_t)B * T + 128) * 3 * D * 2, stream_));
-  PF_HIP(hipMemcpyAsync(base + ov, v, n * 4, hipMemcpyHostToDevice, stream_));
-  PF_HIP(hipMemcpyAsync(base + ow, wT.data(), wT.size() * 4, hipMemcpyHostToDevice, stream_));
-  half_t* vs = (half_t*)(base + oq) + 2 * D;
-  launch_f32_to_f16(stream_, (const float*)(base + ov), (int64_t)B * T, D, D, vs, 3 * D);
-  launch_fsmn_enc(stream_, vs, 3 * D, (const float*)(base + ow), B, T, D, k, (float*)(base + oy));
-  PF_HIP(hipMemcpyAsync(y, base + oy, n * 4, hipMemcpyDeviceToHost, stream_));
+  const std::vector<float> wT = fsmn_taps(w, D, k);
+  StageCarve st;
+  const auto dv = st.take<float>(n);
+  const auto dq = st.take<half_t>(((size_t)B * T + 128) * 3 * D);
+  const auto dw = st.take<float>(wT.size()), dy = st.take<float>(n);
+  void* ws = op_ws(st);
+  PF_HIP(hipMemsetAsync(dq(ws), 0, dq.count * 2, stream_));
+  upload(stream_, dw(ws), wT.data(), wT.size());
+  half_t* vs = dq(ws) + 2 * D;
+  upload_f16(stream_, dv(ws), v, (int64_t)B * T, D, vs, 3 * D);
+  launch_fsmn_enc(stream_, vs, 3 * D, dw(ws), B, T, D, k, dy(ws));
+  download(stream_, y, (const float*)dy(ws), n);
   PF_HIP(hipStreamSynchronize(stream_));
 }
 
@@ -1898,22 +1649,30 @@ void Engine::op_fsmn_dec(const float* tn, const float* w, const int32_t* token_n
   PF_HIP(hipSetDevice(device_));
   PF_CHECK(D % 4 == 0 && B > 0 && L > 0, PF_ERR_INVALID_ARG, "fsmn_dec: bad shape");
   const size_t n = (size_t)B * L * D;
-  std::vector<float> wT((size_t)D * k);
-  for (int c = 0; c < D; ++c)
-    for (int j = 0; j < k; ++j) wT[(size_t)j * D + c] = w[(size_t)c * k + j];
-  size_t off = 0;
-  const Carve carve{off};
-  const size_t ot = carve(n * 4), ox = carve(n * 4), ow = carve(wT.size() * 4), on = carve((size_t)B * 4);
-  ensure(ws_tmp_, off);
-  char* base = (char*)ws_tmp_.p;
-  PF_HIP(hipMemcpyAsync(base + ot, tn, n * 4, hipMemcpyHostToDevice, stream_));
-  PF_HIP(hipMemcpyAsync(base + ox, x, n * 4, hipMemcpyHostToDevice, stream_));
-  PF_HIP(hipMemcpyAsync(base + ow, wT.data(), wT.size() * 4, hipMemcpyHostToDevice, stream_));
-  PF_HIP(hipMemcpyAsync(base + on, token_num, (size_t)B * 4, hipMemcpyHostToDevice, stream_));
-  launch_fsmn_dec(stream_, (const float*)(base + ot), (const float*)(base + ow), (const int32_t*)(base + on), B, L, D, k,
-                  (float*)(base + ox));
-  PF_HIP(hipMemcpyAsync(x, base + ox, n * 4, hipMemcpyDeviceToHost, stream_));
+  const std::vector<float> wT = fsmn_taps(w, D, k);
+  StageCarve st;
+  const auto dt = st.take<float>(n), dx = st.take<float>(n), dw = st.take<float>(wT.size());
+  const auto dnum = st.take<int32_t>(B);
+  void* ws = op_ws(st);
+  upload(stream_, dt(ws), tn, n);
+  upload(stream_, dx(ws), (const float*)x, n);
+  upload(stream_, dw(ws), wT.data(), wT.size());
+  upload(stream_, dnum(ws), token_num, B);
+  launch_fsmn_dec(stream_, dt(ws), dw(ws), dnum(ws), B, L, D, k, dx(ws));
+  download(stream_, x, (const float*)dx(ws), n);
   PF_HIP(hipStreamSynchronize(stream_));
+}
+
+// what both decoder-FSMN ops upload: tn [B, L, D] with the rows at l >= num[b] left as the device buffer holds them (hostile)
+static void upload_valid_rows(hipStream_t s, float* dev, const float* tn, const int32_t* num, int B, int L, int D) {
+  for (int b = 0; b < B; ++b) upload(s, dev + (size_t)b * L * D, tn + (size_t)b * L * D, (size_t)std::min(std::max(num[b], 0), L) * D);
+}
+// ... and what both require afterwards: a row of x at l >= num[b] comes back with the bits it went in with
+static void check_masked_rows(const char* op, const float* x_out, const float* x, const int32_t* num, int B, int L, int D) {
+  for (int b = 0; b < B; ++b)
+    for (int l = std::max(num[b], 0); l < L; ++l)
+      PF_CHECK(std::memcmp(x_out + ((size_t)b * L + l) * D, x + ((size_t)b * L + l) * D, (size_t)D * 4) == 0, PF_ERR_DEVICE,
+               std::string(op) + ": x changed at utterance " + std::to_string(b) + ", position " + std::to_string(l) + " >= token_num");
 }
 
 // The fused decoder FSMN + norm3 kernel (k_norm.hip fsmn_dec_ln_kernel<11 | 21>) alone, on a hostile host: the rows of tn at
@@ -1926,41 +1685,31 @@ void Engine::op_fsmn_dec_ln(const float* tn, const float* taps, const int32_t* t
   PF_CHECK(B > 0 && L > 0 && (k == 11 || k == 21), PF_ERR_INVALID_ARG, "fsmn_dec_ln: B, L > 0 and k = 11 | 21");
   const int M = B * L;
   const int64_t Mp = (int64_t)M + 64;
-  size_t off = 0;
-  const Carve carve{off};
-  const size_t ot = carve((size_t)Mp * D * 4), ox = carve((size_t)Mp * D * 4), on16 = carve((size_t)Mp * D * 2), ow = carve((size_t)k * D * 4);
-  const size_t og = carve((size_t)D * 4), ob = carve((size_t)D * 4), onum = carve((size_t)B * 4);
-  ensure(ws_tmp_, off);
-  char* base = (char*)ws_tmp_.p;
-  fill_hostile_rows32(stream_, (float*)(base + ot), D, 0, Mp);
-  for (int b = 0; b < B; ++b) {
-    const int nv = std::min(std::max(token_num[b], 0), L);
-    if (nv) PF_HIP(hipMemcpyAsync(base + ot + (size_t)b * L * D * 4, tn + (size_t)b * L * D, (size_t)nv * D * 4, hipMemcpyHostToDevice, stream_));
-  }
-  fill_sentinel32(stream_, base + ox, (size_t)Mp * D);
-  fill_sentinel16(stream_, base + on16, (size_t)Mp * D);
-  PF_HIP(hipMemcpyAsync(base + ox, x, (size_t)M * D * 4, hipMemcpyHostToDevice, stream_));
-  PF_HIP(hipMemcpyAsync(base + ow, taps, (size_t)k * D * 4, hipMemcpyHostToDevice, stream_));
-  PF_HIP(hipMemcpyAsync(base + og, gamma, (size_t)D * 4, hipMemcpyHostToDevice, stream_));
-  PF_HIP(hipMemcpyAsync(base + ob, beta, (size_t)D * 4, hipMemcpyHostToDevice, stream_));
-  PF_HIP(hipMemcpyAsync(base + onum, token_num, (size_t)B * 4, hipMemcpyHostToDevice, stream_));
+  StageCarve st;
+  const auto dt = st.take<float>((size_t)Mp * D), dx = st.take<float>((size_t)Mp * D);
+  const auto dn16 = st.take<half_t>((size_t)Mp * D);
+  const auto dw = st.take<float>((size_t)k * D), dg = st.take<float>(D), db = st.take<float>(D);
+  const auto dnum = st.take<int32_t>(B);
+  void* ws = op_ws(st);
+  fill_hostile_rows32(stream_, dt(ws), D, 0, Mp);
+  upload_valid_rows(stream_, dt(ws), tn, token_num, B, L, D);
+  fill_sentinel(stream_, dx(ws), (size_t)Mp * D);
+  fill_sentinel(stream_, dn16(ws), (size_t)Mp * D);
+  upload(stream_, dx(ws), x, (size_t)M * D);
+  upload(stream_, dw(ws), taps, (size_t)k * D);
+  upload(stream_, dg(ws), gamma, D);
+  upload(stream_, db(ws), beta, D);
+  upload(stream_, dnum(ws), token_num, B);
   prof_begin("gemm_op", 0);                       // ("gemm_" classes record the kernel the launcher notes)
-  const bool ran = launch_fsmn_dec_ln(stream_, (const float*)(base + ot), (const float*)(base + ow), (const int32_t*)(base + onum), B, L, D, k,
-                                      (float*)(base + ox), (const float*)(base + og), (const float*)(base + ob), (half_t*)(base + on16));
+  const bool ran = launch_fsmn_dec_ln(stream_, dt(ws), dw(ws), dnum(ws), B, L, D, k, dx(ws), dg(ws), db(ws), dn16(ws));
   prof_end("gemm_op");
   PF_CHECK(ran, PF_ERR_UNSUPPORTED, "fsmn_dec_ln: the launcher declined the geometry");
-  check_guard<uint32_t>(stream_, "fsmn_dec_ln", "x", base + ox, kSentinel32, Mp, M, D, D, false, false, M);
-  check_guard<uint16_t>(stream_, "fsmn_dec_ln", "the f16 LayerNorm result", base + on16, kSentinel16, Mp, M, D, D, false, true, M);
-  std::vector<half_t> n16((size_t)M * D);
-  PF_HIP(hipMemcpyAsync(x_out, base + ox, (size_t)M * D * 4, hipMemcpyDeviceToHost, stream_));
-  PF_HIP(hipMemcpyAsync(n16.data(), base + on16, n16.size() * 2, hipMemcpyDeviceToHost, stream_));
+  check_guard(stream_, "fsmn_dec_ln: x", dx(ws), kSentinel32, result_geom(Mp, M, D, D, M, false, false));
+  check_guard(stream_, "fsmn_dec_ln: the f16 LayerNorm result", dn16(ws), kSentinel16, result_geom(Mp, M, D, D, M));
+  download(stream_, x_out, (const float*)dx(ws), (size_t)M * D);
   PF_HIP(hipStreamSynchronize(stream_));
-  for (int b = 0; b < B; ++b)
-    for (int l = std::max(token_num[b], 0); l < L; ++l)
-      PF_CHECK(std::memcmp(x_out + ((size_t)b * L + l) * D, x + ((size_t)b * L + l) * D, (size_t)D * 4) == 0, PF_ERR_DEVICE,
-               "fsmn_dec_ln: x changed at utterance " + std::to_string(b) + ", position " + std::to_string(l) + " >= token_num");
-  if (xn16_out)
-    for (size_t i = 0; i < n16.size(); ++i) xn16_out[i] = (float)n16[i];
+  check_masked_rows("fsmn_dec_ln", x_out, x, token_num, B, L, D);
+  if (xn16_out) download_f16(stream_, xn16_out, dn16(ws), M, D, D);
 }
 
 // ---- the row kernels alone (k_norm.hip, the non-CIF half of k_misc.hip): thin wrappers, no arithmetic of their own.  Every result
@@ -1982,27 +1731,27 @@ void Engine::op_layernorm_ex(const float* x, const float* g, const float* b, int
   if (!out16) ld16 = 0;
   if (!out32) ld32 = 0;
   if (posenc_T) build_pe(posenc_T);                           // the table the encoder would use, by the call the encoder makes
-  size_t off = 0;
-  const Carve carve{off};
-  const size_t ox = carve((size_t)(rows + 2) * D * 4), og = carve((size_t)D * 4), ob = carve((size_t)D * 4);
-  const size_t o16 = carve((size_t)(rows + 2 * kG) * std::max(ld16, 1) * 2), o32 = carve((size_t)(rows + 2 * kG) * std::max(ld32, 1) * 4);
-  ensure(ws_tmp_, off);
-  char* base = (char*)ws_tmp_.p;
-  fill_hostile_rows32(stream_, (float*)(base + ox), D, rows, rows + 2);          // the rows behind rows - 1 are never read
-  PF_HIP(hipMemcpyAsync(base + ox, x, (size_t)rows * D * 4, hipMemcpyHostToDevice, stream_));
-  PF_HIP(hipMemcpyAsync(base + og, g, (size_t)D * 4, hipMemcpyHostToDevice, stream_));
-  PF_HIP(hipMemcpyAsync(base + ob, b, (size_t)D * 4, hipMemcpyHostToDevice, stream_));
-  if (out16) fill_sentinel16(stream_, base + o16, (size_t)(rows + 2 * kG) * ld16);
-  if (out32) fill_sentinel32(stream_, base + o32, (size_t)(rows + 2 * kG) * ld32);
-  half_t* d16 = out16 ? (half_t*)(base + o16) + (size_t)kG * ld16 : nullptr;
-  float* d32 = out32 ? (float*)(base + o32) + (size_t)kG * ld32 : nullptr;
+  const size_t n16 = (size_t)(rows + 2 * kG) * ld16, n32 = (size_t)(rows + 2 * kG) * ld32;
+  StageCarve st;
+  const auto dx = st.take<float>((size_t)(rows + 2) * D), dg = st.take<float>(D), db = st.take<float>(D);
+  const auto d16 = st.take<uint16_t>((size_t)(rows + 2 * kG) * std::max(ld16, 1));
+  const auto d32 = st.take<float>((size_t)(rows + 2 * kG) * std::max(ld32, 1));
+  void* ws = op_ws(st);
+  fill_hostile_rows32(stream_, dx(ws), D, rows, rows + 2);          // the rows behind rows - 1 are never read
+  upload(stream_, dx(ws), x, (size_t)rows * D);
+  upload(stream_, dg(ws), g, D);
+  upload(stream_, db(ws), b, D);
+  if (out16) fill_sentinel(stream_, d16(ws), n16);
+  if (out32) fill_sentinel(stream_, d32(ws), n32);
+  half_t* o16 = out16 ? (half_t*)d16(ws) + (size_t)kG * ld16 : nullptr;
+  float* o32 = out32 ? d32(ws) + (size_t)kG * ld32 : nullptr;
   if (posenc_T)
-    launch_posenc_ln_tab(stream_, (const float*)(base + ox), (int)(rows / posenc_T), posenc_T, D, std::sqrt((float)mc_.d_model),
-                         (const float*)ws_pe_.p, (const float*)(base + og), (const float*)(base + ob), d16, ld16);
+    launch_posenc_ln_tab(stream_, dx(ws), (int)(rows / posenc_T), posenc_T, D, std::sqrt((float)mc_.d_model), (const float*)ws_pe_.p, dg(ws), db(ws),
+                         o16, ld16);
   else
-    launch_layernorm(stream_, (const float*)(base + ox), rows, D, (const float*)(base + og), (const float*)(base + ob), d16, ld16, d32, ld32);
-  if (out16) PF_HIP(hipMemcpyAsync(out16, base + o16, (size_t)(rows + 2 * kG) * ld16 * 2, hipMemcpyDeviceToHost, stream_));
-  if (out32) PF_HIP(hipMemcpyAsync(out32, base + o32, (size_t)(rows + 2 * kG) * ld32 * 4, hipMemcpyDeviceToHost, stream_));
+    launch_layernorm(stream_, dx(ws), rows, D, dg(ws), db(ws), o16, ld16, o32, ld32);
+  if (out16) download(stream_, out16, (const uint16_t*)d16(ws), n16);
+  if (out32) download(stream_, out32, (const float*)d32(ws), n32);
   PF_HIP(hipStreamSynchronize(stream_));
 }
 
@@ -2010,19 +1759,19 @@ void Engine::op_layernorm_f16(const uint16_t* x, const float* g, const float* b,
   PF_HIP(hipSetDevice(device_));
   PF_CHECK(rows > 0 && rows < (1 << 24) && D > 0 && D % 8 == 0 && D <= 2048, PF_ERR_INVALID_ARG, "layernorm_f16: bad shape");
   const size_t cells = (size_t)(rows + 2 * kG) * D;
-  size_t off = 0;
-  const Carve carve{off};
-  const size_t ox = carve((size_t)rows * D * 2), og = carve((size_t)D * 4), ob = carve((size_t)D * 4), oo = carve(cells * 2);
-  ensure(ws_tmp_, off);
-  char* base = (char*)ws_tmp_.p;
-  fill_sentinel16(stream_, base + oo, cells);
-  half_t* dst = (half_t*)(base + oo) + (size_t)kG * D;
-  half_t* src = in_place ? dst : (half_t*)(base + ox);
-  PF_HIP(hipMemcpyAsync(src, x, (size_t)rows * D * 2, hipMemcpyHostToDevice, stream_));
-  PF_HIP(hipMemcpyAsync(base + og, g, (size_t)D * 4, hipMemcpyHostToDevice, stream_));
-  PF_HIP(hipMemcpyAsync(base + ob, b, (size_t)D * 4, hipMemcpyHostToDevice, stream_));
-  launch_layernorm_f16(stream_, src, rows, D, (const float*)(base + og), (const float*)(base + ob), dst);
-  PF_HIP(hipMemcpyAsync(out, base + oo, cells * 2, hipMemcpyDeviceToHost, stream_));
+  StageCarve st;
+  const auto dx = st.take<uint16_t>((size_t)rows * D);
+  const auto dg = st.take<float>(D), db = st.take<float>(D);
+  const auto dout = st.take<uint16_t>(cells);
+  void* ws = op_ws(st);
+  fill_sentinel(stream_, dout(ws), cells);
+  uint16_t* dst = dout(ws) + (size_t)kG * D;
+  uint16_t* src = in_place ? dst : dx(ws);
+  upload(stream_, src, x, (size_t)rows * D);
+  upload(stream_, dg(ws), g, D);
+  upload(stream_, db(ws), b, D);
+  launch_layernorm_f16(stream_, (half_t*)src, rows, D, dg(ws), db(ws), (half_t*)dst);
+  download(stream_, out, (const uint16_t*)dout(ws), cells);
   PF_HIP(hipStreamSynchronize(stream_));
 }
 
@@ -2032,29 +1781,24 @@ void Engine::op_fsmn_dec_stream(const float* tn, const float* taps, const int32_
   PF_HIP(hipSetDevice(device_));
   PF_CHECK(B > 0 && L > 0 && D > 0 && k >= 2 && (int64_t)B * L * D < (1 << 28), PF_ERR_INVALID_ARG, "fsmn_dec_stream: bad shape");
   const int CW = k - 1, M = B * L;
-  size_t off = 0;
-  const Carve carve{off};
-  const size_t ot = carve((size_t)M * D * 4), ow = carve((size_t)k * D * 4), on = carve((size_t)B * 4), oc = carve((size_t)B * D * CW * 4);
-  const size_t ox = carve((size_t)(M + 2 * kG) * D * 4), oco = carve((size_t)((int64_t)B * D + 2 * kG) * CW * 4);
-  ensure(ws_tmp_, off);
-  char* base = (char*)ws_tmp_.p;
-  fill_hostile_rows32(stream_, (float*)(base + ot), D, 0, M);
-  for (int bb = 0; bb < B; ++bb) {
-    const int nv = std::min(std::max(len[bb], 0), L);
-    if (nv) PF_HIP(hipMemcpyAsync(base + ot + (size_t)bb * L * D * 4, tn + (size_t)bb * L * D, (size_t)nv * D * 4, hipMemcpyHostToDevice, stream_));
-  }
-  PF_HIP(hipMemcpyAsync(base + ow, taps, (size_t)k * D * 4, hipMemcpyHostToDevice, stream_));
-  PF_HIP(hipMemcpyAsync(base + on, len, (size_t)B * 4, hipMemcpyHostToDevice, stream_));
-  PF_HIP(hipMemcpyAsync(base + oc, cache_in, (size_t)B * D * CW * 4, hipMemcpyHostToDevice, stream_));
-  fill_sentinel32(stream_, base + ox, (size_t)(M + 2 * kG) * D);
-  fill_sentinel32(stream_, base + oco, (size_t)((int64_t)B * D + 2 * kG) * CW);
-  float* dx = (float*)(base + ox) + (size_t)kG * D;
-  float* dc = (float*)(base + oco) + (size_t)kG * CW;
-  PF_HIP(hipMemcpyAsync(dx, x, (size_t)M * D * 4, hipMemcpyHostToDevice, stream_));
-  launch_fsmn_dec_stream(stream_, (const float*)(base + ot), (const float*)(base + ow), (const int32_t*)(base + on), (const float*)(base + oc),
-                         B, L, D, k, dx, dc);
-  PF_HIP(hipMemcpyAsync(x_out, base + ox, (size_t)(M + 2 * kG) * D * 4, hipMemcpyDeviceToHost, stream_));
-  PF_HIP(hipMemcpyAsync(cache_out, base + oco, (size_t)((int64_t)B * D + 2 * kG) * CW * 4, hipMemcpyDeviceToHost, stream_));
+  const size_t nx = (size_t)(M + 2 * kG) * D, nc = (size_t)((int64_t)B * D + 2 * kG) * CW;
+  StageCarve st;
+  const auto dt = st.take<float>((size_t)M * D), dw = st.take<float>((size_t)k * D);
+  const auto dlen = st.take<int32_t>(B);
+  const auto dc = st.take<float>((size_t)B * D * CW), dx = st.take<float>(nx), dco = st.take<float>(nc);
+  void* ws = op_ws(st);
+  fill_hostile_rows32(stream_, dt(ws), D, 0, M);
+  upload_valid_rows(stream_, dt(ws), tn, len, B, L, D);
+  upload(stream_, dw(ws), taps, (size_t)k * D);
+  upload(stream_, dlen(ws), len, B);
+  upload(stream_, dc(ws), cache_in, (size_t)B * D * CW);
+  fill_sentinel(stream_, dx(ws), nx);
+  fill_sentinel(stream_, dco(ws), nc);
+  float* xd = dx(ws) + (size_t)kG * D;
+  upload(stream_, xd, x, (size_t)M * D);
+  launch_fsmn_dec_stream(stream_, dt(ws), dw(ws), dlen(ws), dc(ws), B, L, D, k, xd, dco(ws) + (size_t)kG * CW);
+  download(stream_, x_out, (const float*)dx(ws), nx);
+  download(stream_, cache_out, (const float*)dco(ws), nc);
   PF_HIP(hipStreamSynchronize(stream_));
 }
 
@@ -2063,21 +1807,21 @@ void Engine::op_embed_gather(const float* table, const int32_t* ids, int rows, i
   PF_HIP(hipSetDevice(device_));
   PF_CHECK(rows > 0 && D > 0 && D % 4 == 0 && vocab > 0, PF_ERR_INVALID_ARG, "embed_gather: bad shape");
   const size_t cells = (size_t)(rows + 2 * kG) * D;
-  size_t off = 0;
-  const Carve carve{off};
-  const size_t ot = carve((size_t)(vocab + 2) * D * 4), oi = carve((size_t)rows * 4), o32 = carve(cells * 4), o16 = carve(cells * 2);
-  ensure(ws_tmp_, off);
-  char* base = (char*)ws_tmp_.p;
-  fill_hostile_rows32(stream_, (float*)(base + ot), D, 0, 1);
-  fill_hostile_rows32(stream_, (float*)(base + ot), D, vocab + 1, vocab + 2);
-  PF_HIP(hipMemcpyAsync(base + ot + (size_t)D * 4, table, (size_t)vocab * D * 4, hipMemcpyHostToDevice, stream_));
-  PF_HIP(hipMemcpyAsync(base + oi, ids, (size_t)rows * 4, hipMemcpyHostToDevice, stream_));
-  fill_sentinel32(stream_, base + o32, cells);
-  fill_sentinel16(stream_, base + o16, cells);
-  launch_embed_gather(stream_, (const float*)(base + ot) + D, (const int32_t*)(base + oi), rows, D, vocab, (float*)(base + o32) + (size_t)kG * D,
-                      out16 ? (half_t*)(base + o16) + (size_t)kG * D : nullptr);
-  PF_HIP(hipMemcpyAsync(out32, base + o32, cells * 4, hipMemcpyDeviceToHost, stream_));
-  if (out16) PF_HIP(hipMemcpyAsync(out16, base + o16, cells * 2, hipMemcpyDeviceToHost, stream_));
+  StageCarve st;
+  const auto dt = st.take<float>((size_t)(vocab + 2) * D);
+  const auto di = st.take<int32_t>(rows);
+  const auto d32 = st.take<float>(cells);
+  const auto d16 = st.take<uint16_t>(cells);
+  void* ws = op_ws(st);
+  fill_hostile_rows32(stream_, dt(ws), D, 0, 1);
+  fill_hostile_rows32(stream_, dt(ws), D, vocab + 1, vocab + 2);
+  upload(stream_, dt(ws) + D, table, (size_t)vocab * D);
+  upload(stream_, di(ws), ids, rows);
+  fill_sentinel(stream_, d32(ws), cells);
+  fill_sentinel(stream_, d16(ws), cells);
+  launch_embed_gather(stream_, dt(ws) + D, di(ws), rows, D, vocab, d32(ws) + (size_t)kG * D, out16 ? (half_t*)d16(ws) + (size_t)kG * D : nullptr);
+  download(stream_, out32, (const float*)d32(ws), cells);
+  if (out16) download(stream_, out16, (const uint16_t*)d16(ws), cells);
   PF_HIP(hipStreamSynchronize(stream_));
 }
 
@@ -2085,16 +1829,15 @@ void Engine::op_add_to_f16(const float* a, const float* b, int64_t rows, int D, 
   PF_HIP(hipSetDevice(device_));
   PF_CHECK(rows > 0 && rows < (1 << 24) && D > 0 && D % 4 == 0, PF_ERR_INVALID_ARG, "add_to_f16: bad shape");
   const size_t n = (size_t)rows * D, cells = (size_t)(rows + 2 * kG) * D;
-  size_t off = 0;
-  const Carve carve{off};
-  const size_t oa = carve(n * 4), ob = carve(n * 4), oo = carve(cells * 2);
-  ensure(ws_tmp_, off);
-  char* base = (char*)ws_tmp_.p;
-  PF_HIP(hipMemcpyAsync(base + oa, a, n * 4, hipMemcpyHostToDevice, stream_));
-  PF_HIP(hipMemcpyAsync(base + ob, b, n * 4, hipMemcpyHostToDevice, stream_));
-  fill_sentinel16(stream_, base + oo, cells);
-  launch_add_to_f16(stream_, (const float*)(base + oa), (const float*)(base + ob), rows, D, (half_t*)(base + oo) + (size_t)kG * D);
-  PF_HIP(hipMemcpyAsync(out16, base + oo, cells * 2, hipMemcpyDeviceToHost, stream_));
+  StageCarve st;
+  const auto da = st.take<float>(n), db = st.take<float>(n);
+  const auto dout = st.take<uint16_t>(cells);
+  void* ws = op_ws(st);
+  upload(stream_, da(ws), a, n);
+  upload(stream_, db(ws), b, n);
+  fill_sentinel(stream_, dout(ws), cells);
+  launch_add_to_f16(stream_, da(ws), db(ws), rows, D, (half_t*)dout(ws) + (size_t)kG * D);
+  download(stream_, out16, (const uint16_t*)dout(ws), cells);
   PF_HIP(hipStreamSynchronize(stream_));
 }
 
@@ -2103,23 +1846,23 @@ void Engine::op_seaco_merge(const float* dha, int ld_dha, const int64_t* dha_ids
                             const float* logits_in, int ld_logits, const int64_t* ids_in, float* logits_out, int64_t* ids_out) {
   PF_HIP(hipSetDevice(device_));
   PF_CHECK(rows > 0 && rows < (1 << 20) && V > 0 && ld_dha >= V && ld_logits >= V, PF_ERR_INVALID_ARG, "seaco_merge: bad shape");
-  size_t off = 0;
-  const Carve carve{off};
-  const size_t od = carve((size_t)rows * ld_dha * 4), odi = carve((size_t)rows * 8);
-  const size_t ol = carve((size_t)(rows + 2 * kG) * ld_logits * 4), oi = carve((size_t)(rows + 2 * kG) * 8);
-  ensure(ws_tmp_, off);
-  char* base = (char*)ws_tmp_.p;
-  PF_HIP(hipMemcpyAsync(base + od, dha, (size_t)rows * ld_dha * 4, hipMemcpyHostToDevice, stream_));
-  PF_HIP(hipMemcpyAsync(base + odi, dha_ids, (size_t)rows * 8, hipMemcpyHostToDevice, stream_));
-  fill_sentinel32(stream_, base + ol, (size_t)(rows + 2 * kG) * ld_logits);
-  fill_sentinel32(stream_, base + oi, (size_t)(rows + 2 * kG) * 2);
-  float* dl = (float*)(base + ol) + (size_t)kG * ld_logits;
-  int64_t* di = (int64_t*)(base + oi) + kG;
-  PF_HIP(hipMemcpyAsync(dl, logits_in, (size_t)rows * ld_logits * 4, hipMemcpyHostToDevice, stream_));
-  PF_HIP(hipMemcpyAsync(di, ids_in, (size_t)rows * 8, hipMemcpyHostToDevice, stream_));
-  launch_seaco_merge(stream_, (const float*)(base + od), ld_dha, (const int64_t*)(base + odi), rows, V, nobias, copy_logits, dl, ld_logits, di);
-  PF_HIP(hipMemcpyAsync(logits_out, base + ol, (size_t)(rows + 2 * kG) * ld_logits * 4, hipMemcpyDeviceToHost, stream_));
-  PF_HIP(hipMemcpyAsync(ids_out, base + oi, (size_t)(rows + 2 * kG) * 8, hipMemcpyDeviceToHost, stream_));
+  StageCarve st;
+  const auto dd = st.take<float>((size_t)rows * ld_dha);
+  const auto ddi = st.take<int64_t>(rows);
+  const auto dl = st.take<float>((size_t)(rows + 2 * kG) * ld_logits);
+  const auto di = st.take<int64_t>((size_t)(rows + 2 * kG));
+  void* ws = op_ws(st);
+  upload(stream_, dd(ws), dha, (size_t)rows * ld_dha);
+  upload(stream_, ddi(ws), dha_ids, rows);
+  fill_sentinel(stream_, dl(ws), dl.count);
+  fill_sentinel(stream_, (uint32_t*)di(ws), di.count * 2);
+  float* lg = dl(ws) + (size_t)kG * ld_logits;
+  int64_t* id = di(ws) + kG;
+  upload(stream_, lg, logits_in, (size_t)rows * ld_logits);
+  upload(stream_, id, ids_in, rows);
+  launch_seaco_merge(stream_, dd(ws), ld_dha, ddi(ws), rows, V, nobias, copy_logits, lg, ld_logits, id);
+  download(stream_, logits_out, (const float*)dl(ws), dl.count);
+  download(stream_, ids_out, (const int64_t*)di(ws), di.count);
   PF_HIP(hipStreamSynchronize(stream_));
 }
 
@@ -2138,46 +1881,48 @@ void Engine::op_dec_mid(const pf_dec_mid_desc& ds, float* x_out, float* q_out, f
   const int M = B * L;
   const int64_t Mp = round_up(M, 256) + 128;
   const size_t wsb = ffn_dec_workspace_bytes(M, splits);
-  size_t off = 0;
-  const Carve carve{off};
-  const size_t o32 = carve((size_t)std::max<int64_t>((int64_t)M * D, (int64_t)F * D) * 4);
-  const size_t oa16 = carve((size_t)Mp * D * 2), ow1 = carve((size_t)F * D * 2), ow2 = carve((size_t)D * F * 4);
-  const size_t oimg = carve(ffn_dec_image_bytes()), ows = carve(wsb + kWsGuard);
-  const size_t ob1 = carve((size_t)F * 4), ogf = carve((size_t)F * 4), obf = carve((size_t)F * 4);
-  const size_t og2 = carve((size_t)D * 4), ob2 = carve((size_t)D * 4), og3 = carve((size_t)D * 4), ob3 = carve((size_t)D * 4);
-  const size_t otap = carve((size_t)K * D * 4), onum = carve((size_t)B * 4), ox = carve((size_t)Mp * D * 4);
-  const size_t owq = carve((size_t)D * D * 2), owqt = carve(ffn_outproj_weight_bytes()), obq = carve((size_t)D * 4);
-  const size_t oq = carve((size_t)Mp * LDQ * 2), otn = carve((size_t)Mp * D * 4), oxn = carve((size_t)Mp * D * 2);
-  ensure(ws_tmp_, off);
-  char* base = (char*)ws_tmp_.p;
-  auto up16 = [&](const float* src, int rows, int cols, size_t dst) {
-    PF_HIP(hipMemcpyAsync(base + o32, src, (size_t)rows * cols * 4, hipMemcpyHostToDevice, stream_));
-    launch_f32_to_f16(stream_, (const float*)(base + o32), rows, cols, cols, (half_t*)(base + dst), cols);
-    PF_HIP(hipStreamSynchronize(stream_));
-  };
-  auto up = [&](const void* src, size_t n, size_t dst) { PF_HIP(hipMemcpyAsync(base + dst, src, n * 4, hipMemcpyHostToDevice, stream_)); };
-  fill_hostile_rows(stream_, (half_t*)(base + oa16), D, M, Mp, D);
-  fill_sentinel32(stream_, base + ows + wsb, kWsGuard / 4);
-  fill_sentinel32(stream_, base + ox, (size_t)Mp * D);
-  fill_sentinel16(stream_, base + oq, (size_t)Mp * LDQ);
-  fill_sentinel32(stream_, base + otn, (size_t)Mp * D);
-  fill_sentinel16(stream_, base + oxn, (size_t)Mp * D);
-  up16(ds.a, M, D, oa16); up16(ds.w1, F, D, ow1); up16(ds.wq, D, D, owq);
-  up(ds.w2, (size_t)D * F, ow2); up(ds.b1, F, ob1); up(ds.gamma_f, F, ogf); up(ds.beta_f, F, obf);
-  up(ds.n2_gamma, D, og2); up(ds.n2_beta, D, ob2); up(ds.n3_gamma, D, og3); up(ds.n3_beta, D, ob3);
-  up(ds.taps, (size_t)K * D, otap); up(ds.token_num, B, onum); up(ds.x, (size_t)M * D, ox); up(ds.bq, D, obq);
-  launch_ffn_dec_retile(stream_, (const half_t*)(base + ow1), D, (const float*)(base + ow2), (const float*)(base + ogf),
-                        (const float*)(base + obf), (const float*)(base + ob1), (half_t*)(base + oimg));
-  launch_ffn_retile_out(stream_, (const half_t*)(base + owq), D, (half_t*)(base + owqt));
+  StageCarve st;
+  const auto d32 = st.take<float>((size_t)std::max<int64_t>((int64_t)M * D, (int64_t)F * D));   // the fp32 staging slot
+  const auto da16 = st.take<half_t>((size_t)Mp * D), dw1 = st.take<half_t>((size_t)F * D);
+  const auto dw2 = st.take<float>((size_t)D * F);
+  const auto dimg = st.take<half_t>(ffn_dec_image_bytes() / 2);
+  const auto dws = st.take<uint8_t>(wsb + kWsGuard);
+  const auto db1 = st.take<float>(F), dgf = st.take<float>(F), dbf = st.take<float>(F);
+  const auto dg2 = st.take<float>(D), db2 = st.take<float>(D), dg3 = st.take<float>(D), db3 = st.take<float>(D), dtap = st.take<float>((size_t)K * D);
+  const auto dnum = st.take<int32_t>(B);
+  const auto dx = st.take<float>((size_t)Mp * D);
+  const auto dwq = st.take<half_t>((size_t)D * D), dwqt = st.take<half_t>(ffn_outproj_weight_bytes() / 2);
+  const auto dbq = st.take<float>(D);
+  const auto dq = st.take<half_t>((size_t)Mp * LDQ);
+  const auto dtn = st.take<float>((size_t)Mp * D);
+  const auto dxn = st.take<half_t>((size_t)Mp * D);
+  void* ws = op_ws(st);
+  uint32_t* behind_ws = (uint32_t*)(dws(ws) + wsb);
+  fill_sentinel(stream_, behind_ws, kWsGuard / 4);
+  fill_sentinel(stream_, dx(ws), (size_t)Mp * D);
+  fill_sentinel(stream_, dq(ws), (size_t)Mp * LDQ);
+  fill_sentinel(stream_, dtn(ws), (size_t)Mp * D);
+  fill_sentinel(stream_, dxn(ws), (size_t)Mp * D);
+  upload_operand16(stream_, d32(ws), ds.a, M, D, da16(ws), D, Mp);
+  upload_f16(stream_, d32(ws), ds.w1, F, D, dw1(ws), D);
+  upload_f16(stream_, d32(ws), ds.wq, D, D, dwq(ws), D);
+  upload(stream_, dw2(ws), ds.w2, (size_t)D * F); upload(stream_, db1(ws), ds.b1, F);
+  upload(stream_, dgf(ws), ds.gamma_f, F); upload(stream_, dbf(ws), ds.beta_f, F);
+  upload(stream_, dg2(ws), ds.n2_gamma, D); upload(stream_, db2(ws), ds.n2_beta, D);
+  upload(stream_, dg3(ws), ds.n3_gamma, D); upload(stream_, db3(ws), ds.n3_beta, D);
+  upload(stream_, dtap(ws), ds.taps, (size_t)K * D); upload(stream_, dnum(ws), ds.token_num, B);
+  upload(stream_, dx(ws), ds.x, (size_t)M * D); upload(stream_, dbq(ws), ds.bq, D);
+  launch_ffn_dec_retile(stream_, dw1(ws), D, dw2(ws), dgf(ws), dbf(ws), db1(ws), dimg(ws));
+  launch_ffn_retile_out(stream_, dwq(ws), D, dwqt(ws));
   const float qscale = 1.0f / std::sqrt(128.0f);
   FfnDecArgs f{};
-  f.A = (const half_t*)(base + oa16); f.lda = D; f.img = (const half_t*)(base + oimg); f.ws = base + ows; f.M = M; f.splits = splits;
+  f.A = da16(ws); f.lda = D; f.img = dimg(ws); f.ws = dws(ws); f.M = M; f.splits = splits;
   f.eps_hidden = 1e-12f; f.eps = 1e-12f;
-  const int32_t* num = (const int32_t*)(base + onum);
-  float* xd = (float*)(base + ox);
-  float* tn = (float*)(base + otn);
-  half_t* xn = (half_t*)(base + oxn);
-  half_t* q16 = (half_t*)(base + oq);
+  const int32_t* num = dnum(ws);
+  float* xd = dx(ws);
+  float* tn = dtn(ws);
+  half_t* xn = dxn(ws);
+  half_t* q16 = dq(ws);
   bool ran = true;
   if (form == 0) {
     f.no_finish = true;
@@ -2189,7 +1934,7 @@ void Engine::op_dec_mid(const pf_dec_mid_desc& ds, float* x_out, float* q_out, f
     {
       const int S = splits > 0 ? splits : ffn_dec_splits(M);
       const int64_t Mq = round_up(M, 64);
-      float* part = (float*)(base + ows);
+      float* part = (float*)dws(ws);
       float* stats = part + (size_t)S * Mq * D;
       for (int sh = 0; sh < S; ++sh) {
         for (int b = 0; b <= B; ++b) {
@@ -2200,57 +1945,48 @@ void Engine::op_dec_mid(const pf_dec_mid_desc& ds, float* x_out, float* q_out, f
       }
     }
     DecMidArgs m{};
-    m.ws = base + ows; m.img = f.img; m.splits = splits; m.eps_hidden = 1e-12f;
-    m.n2_g = (const float*)(base + og2); m.n2_b = (const float*)(base + ob2); m.eps2 = 1e-12f;
-    m.fsmn_wT = (const float*)(base + otap); m.k = K; m.token_num = num; m.B = B; m.L = L; m.x = xd;
-    m.n3_g = (const float*)(base + og3); m.n3_b = (const float*)(base + ob3);
-    m.Wqt = (const half_t*)(base + owqt); m.bq = (const float*)(base + obq); m.qscale = qscale; m.q16 = q16; m.ldq = LDQ;
+    m.ws = dws(ws); m.img = f.img; m.splits = splits; m.eps_hidden = 1e-12f;
+    m.n2_g = dg2(ws); m.n2_b = db2(ws); m.eps2 = 1e-12f;
+    m.fsmn_wT = dtap(ws); m.k = K; m.token_num = num; m.B = B; m.L = L; m.x = xd;
+    m.n3_g = dg3(ws); m.n3_b = db3(ws);
+    m.Wqt = dwqt(ws); m.bq = dbq(ws); m.qscale = qscale; m.q16 = q16; m.ldq = LDQ;
     prof_begin("gemm_op_mid", 2.0 * M * (double)D * D);
     ran = launch_dec_mid(stream_, m);
     prof_end("gemm_op_mid");
   } else {
-    f.ln_g = (const float*)(base + og2); f.ln_b = (const float*)(base + ob2); f.n32 = tn; f.ldn32 = D;
+    f.ln_g = dg2(ws); f.ln_b = db2(ws); f.n32 = tn; f.ldn32 = D;
     prof_begin("gemm_op", 4.0 * M * (double)D * F);
     launch_ffn_dec(stream_, f);
     prof_end("gemm_op");
-    check_guard<uint32_t>(stream_, "dec_mid", "tn", base + otn, kSentinel32, Mp, M, D, D, false, true, M);
+    check_guard(stream_, "dec_mid: tn", tn, kSentinel32, result_geom(Mp, M, D, D, M));
     if (form == 1) {
       prof_begin("gemm_op_mid", 0);
-      const bool fused = launch_fsmn_dec_ln(stream_, tn, (const float*)(base + otap), num, B, L, D, K, xd, (const float*)(base + og3),
-                                            (const float*)(base + ob3), xn);
+      const bool fused = launch_fsmn_dec_ln(stream_, tn, dtap(ws), num, B, L, D, K, xd, dg3(ws), db3(ws), xn);
       prof_end("gemm_op_mid");
       PF_CHECK(fused, PF_ERR_UNSUPPORTED, "dec_mid: the fused FSMN + LayerNorm launch declined the geometry");
     } else {
-      launch_fsmn_dec(stream_, tn, (const float*)(base + otap), num, B, L, D, K, xd);
-      launch_layernorm(stream_, xd, M, D, (const float*)(base + og3), (const float*)(base + ob3), xn, D, nullptr, 0);
+      launch_fsmn_dec(stream_, tn, dtap(ws), num, B, L, D, K, xd);
+      launch_layernorm(stream_, xd, M, D, dg3(ws), db3(ws), xn, D, nullptr, 0);
     }
-    check_guard<uint16_t>(stream_, "dec_mid", "xn16", base + oxn, kSentinel16, Mp, M, D, D, false, true, M);
+    check_guard(stream_, "dec_mid: xn16", xn, kSentinel16, result_geom(Mp, M, D, D, M));
     Lin Lq;
-    Lq.w = (half_t*)(base + owq); Lq.bias = (const float*)(base + obq); Lq.N = D; Lq.K = D; Lq.Kpad = D;
+    Lq.w = dwq(ws); Lq.bias = dbq(ws); Lq.N = D; Lq.K = D; Lq.Kpad = D;
     gemm("gemm_dec_q", Lq, xn, D, M, nullptr, 0, q16, LDQ, nullptr, 0, nullptr, 0, false, D, qscale);
   }
   if (ran_out) *ran_out = ran ? 1 : 0;
   if (!ran) return;
-  check_guard<uint32_t>(stream_, "dec_mid", "x", base + ox, kSentinel32, Mp, M, D, D, false, false, M);
+  check_guard(stream_, "dec_mid: x", xd, kSentinel32, result_geom(Mp, M, D, D, M, false, false));
   // (the q GEMM of forms 1 and 2 declares its destination padded to round_up(M, 256) rows, the fused kernel declares nothing)
-  check_guard<uint16_t>(stream_, "dec_mid", "q", base + oq, kSentinel16, Mp, M, D, LDQ, false, true, form == 0 ? (int64_t)M : -1);
-  check_untouched32(stream_, "dec_mid", "the bytes behind ffn_dec_workspace_bytes", base + ows + wsb, kWsGuard);
-  std::vector<half_t> h16((size_t)M * LDQ);
-  PF_HIP(hipMemcpyAsync(x_out, base + ox, (size_t)M * D * 4, hipMemcpyDeviceToHost, stream_));
-  PF_HIP(hipMemcpyAsync(h16.data(), base + oq, h16.size() * 2, hipMemcpyDeviceToHost, stream_));
+  check_guard(stream_, "dec_mid: q", q16, kSentinel16, result_geom(Mp, M, D, LDQ, form == 0 ? (int64_t)M : round_up(M, 256)));
+  check_guard(stream_, "dec_mid: the bytes behind ffn_dec_workspace_bytes", behind_ws, kSentinel32, untouched_geom(kWsGuard / 4));
+  download(stream_, x_out, (const float*)xd, (size_t)M * D);
   PF_HIP(hipStreamSynchronize(stream_));
-  for (int m = 0; m < M; ++m)
-    for (int n = 0; n < D; ++n) q_out[(size_t)m * D + n] = (float)h16[(size_t)m * LDQ + n];
-  for (int b = 0; b < B; ++b)
-    for (int l = std::max(ds.token_num[b], 0); l < L; ++l)
-      PF_CHECK(std::memcmp(x_out + ((size_t)b * L + l) * D, ds.x + ((size_t)b * L + l) * D, (size_t)D * 4) == 0, PF_ERR_DEVICE,
-               "dec_mid: x changed at utterance " + std::to_string(b) + ", position " + std::to_string(l) + " >= token_num");
+  download_f16(stream_, q_out, q16, M, D, LDQ);
+  check_masked_rows("dec_mid", x_out, ds.x, ds.token_num, B, L, D);
   if (form != 0) {
-    if (tn_out) PF_HIP(hipMemcpy(tn_out, base + otn, (size_t)M * D * 4, hipMemcpyDeviceToHost));
-    if (xn16_out) {
-      PF_HIP(hipMemcpy(h16.data(), base + oxn, (size_t)M * D * 2, hipMemcpyDeviceToHost));
-      for (size_t i = 0; i < (size_t)M * D; ++i) xn16_out[i] = (float)h16[i];
-    }
+    if (tn_out) download(stream_, tn_out, (const float*)tn, (size_t)M * D);
+    PF_HIP(hipStreamSynchronize(stream_));
+    if (xn16_out) download_f16(stream_, xn16_out, xn, M, D, D);
   }
 }
 
@@ -2263,22 +1999,21 @@ void Engine::op_lstm(const float* xg, const float* whh, int B, int T3, int D, in
   PF_CHECK(form >= 0 && form <= 4, PF_ERR_INVALID_ARG, "lstm: form must be 0..4");
   PF_HIP(hipSetDevice(device_));
   const size_t rows = (size_t)B * T3, nw = (size_t)ndir * 4 * D * D;
-  size_t off = 0;
-  const Carve carve{off};
-  const size_t o_xg = carve(rows * ndir * 4 * D * 4), o_w32 = carve(nw * 4), o_w16 = carve(nw * 2 * 2);
-  const size_t o_hs = carve((size_t)ndir * 4 * B * 2 * D * 2), o_cs = carve((size_t)ndir * B * D * 4), o_ho = carve(rows * ndir * D * 4);
-  const size_t o_sw = carve(256), o_xd = carve(rows * 4 * D * 4), o_g = carve((size_t)B * 4 * D * 4), o_h = carve((size_t)B * D * 4);
-  const size_t o_c = carve((size_t)B * D * 4);
-  ensure(ws_tmp_, off);
-  char* base = (char*)ws_tmp_.p;
-  float* xgd = (float*)(base + o_xg); float* w32 = (float*)(base + o_w32); half_t* w16 = (half_t*)(base + o_w16);
-  float* ho = (float*)(base + o_ho);
-  unsigned* sw = (unsigned*)(base + o_sw);
-  PF_HIP(hipMemcpyAsync(xgd, xg, rows * ndir * 4 * D * 4, hipMemcpyHostToDevice, stream_));
-  PF_HIP(hipMemcpyAsync(w32, whh, nw * 4, hipMemcpyHostToDevice, stream_));
+  StageCarve st;
+  const auto dxg = st.take<float>(rows * ndir * 4 * D), dw32 = st.take<float>(nw);
+  const auto dw16 = st.take<half_t>(nw * 2), dhs = st.take<half_t>((size_t)ndir * 4 * B * 2 * D);
+  const auto dcs = st.take<float>((size_t)ndir * B * D), dho = st.take<float>(rows * ndir * D);
+  const auto dsw = st.take<unsigned>(64);
+  const auto dxd = st.take<float>(rows * 4 * D), dg = st.take<float>((size_t)B * 4 * D), dh = st.take<float>((size_t)B * D), dc = st.take<float>((size_t)B * D);
+  void* ws = op_ws(st);
+  float* xgd = dxg(ws); float* w32 = dw32(ws); half_t* w16 = dw16(ws);
+  float* ho = dho(ws);
+  unsigned* sw = dsw(ws);
+  upload(stream_, xgd, xg, rows * ndir * 4 * D);
+  upload(stream_, w32, whh, nw);
   PF_HIP(hipMemsetAsync(ho, 0xFF, rows * ndir * D * 4, stream_));
   LstmArgs a{};
-  a.whh = w16; a.xg = xgd; a.hstate = (half_t*)(base + o_hs); a.cstate = (float*)(base + o_cs); a.hout = ho;
+  a.whh = w16; a.xg = xgd; a.hstate = dhs(ws); a.cstate = dcs(ws); a.hout = ho;
   a.B = B; a.T3 = T3; a.D = D; a.ndir = ndir;
   if (form <= 2) {
     launch_f32_to_f16(stream_, w32, (int64_t)ndir * 4 * D, D, D, w16, D);
@@ -2290,15 +2025,14 @@ void Engine::op_lstm(const float* xg, const float* whh, int B, int T3, int D, in
     a.cstate = nullptr;
     PF_CHECK(lstm_ring_x3(a, sw), PF_ERR_UNSUPPORTED, "lstm: the persistent recurrence does not fit on the device at this shape");
   } else {
-    float* xd = (float*)(base + o_xd);
+    float* xd = dxd(ws);
     for (int d = 0; d < ndir; ++d) {                  // lstm_fp32's gate inputs are one direction's [B * T3, 4D]
       PF_HIP(hipMemcpy2DAsync(xd, (size_t)4 * D * 4, xgd + (size_t)d * 4 * D, (size_t)ndir * 4 * D * 4, (size_t)4 * D * 4, rows,
                               hipMemcpyDeviceToDevice, stream_));
-      lstm_fp32_steps(xd, B, T3, w32 + (size_t)d * 4 * D * D, d == 1, (float*)(base + o_g), (float*)(base + o_h), (float*)(base + o_c), ho,
-                      ndir * D, d * D);
+      lstm_fp32_steps(xd, B, T3, w32 + (size_t)d * 4 * D * D, d == 1, dg(ws), dh(ws), dc(ws), ho, ndir * D, d * D);
     }
   }
-  PF_HIP(hipMemcpyAsync(hout, ho, rows * ndir * D * 4, hipMemcpyDeviceToHost, stream_));
+  download(stream_, hout, (const float*)ho, rows * ndir * D);
   PF_HIP(hipStreamSynchronize(stream_));
   check_async_errors();
 }
@@ -2310,24 +2044,23 @@ void Engine::op_us_peak(const float* hout, const float* w, const float* b0, floa
   PF_CHECK(B > 0 && T3 > 0 && W > 0 && W % 4 == 0, PF_ERR_INVALID_ARG, "us_peak: bad shape");
   PF_HIP(hipSetDevice(device_));
   const size_t rows = (size_t)B * T3;
-  size_t off = 0;
-  const Carve carve{off};
-  const size_t o_h = carve(rows * W * 4), o_w = carve((size_t)W * 4), o_b = carve(4), o_n = carve((size_t)B * 4), o_al = carve(rows * 4),
-               o_pk = carve(rows * 4);
-  ensure(ws_tmp_, off);
-  char* base = (char*)ws_tmp_.p;
-  float* al = (float*)(base + o_al); float* pk = (float*)(base + o_pk);
-  PF_HIP(hipMemcpyAsync(base + o_h, hout, rows * W * 4, hipMemcpyHostToDevice, stream_));
-  PF_HIP(hipMemcpyAsync(base + o_w, w, (size_t)W * 4, hipMemcpyHostToDevice, stream_));
-  PF_HIP(hipMemcpyAsync(base + o_b, b0, 4, hipMemcpyHostToDevice, stream_));
-  PF_HIP(hipMemcpyAsync(base + o_n, token_num, (size_t)B * 4, hipMemcpyHostToDevice, stream_));
+  StageCarve st;
+  const auto dh = st.take<float>(rows * W), dw = st.take<float>(W), db = st.take<float>(1);
+  const auto dn = st.take<int32_t>(B);
+  const auto dal = st.take<float>(rows), dpk = st.take<float>(rows);
+  void* ws = op_ws(st);
+  float* al = dal(ws); float* pk = dpk(ws);
+  upload(stream_, dh(ws), hout, rows * W);
+  upload(stream_, dw(ws), w, W);
+  upload(stream_, db(ws), b0, 1);
+  upload(stream_, dn(ws), token_num, B);
   PF_HIP(hipMemsetAsync(al, 0xFF, rows * 4, stream_));
   PF_HIP(hipMemsetAsync(pk, 0xFF, rows * 4, stream_));
-  launch_us_alpha(stream_, (const float*)(base + o_h), (int64_t)rows, W, (const float*)(base + o_w), (const float*)(base + o_b), smooth, noise, al);
-  PF_HIP(hipMemcpyAsync(alphas_raw, al, rows * 4, hipMemcpyDeviceToHost, stream_));
-  launch_us_peak(stream_, al, (const int32_t*)(base + o_n), B, T3, thr, pk);
-  PF_HIP(hipMemcpyAsync(alphas, al, rows * 4, hipMemcpyDeviceToHost, stream_));
-  PF_HIP(hipMemcpyAsync(peak, pk, rows * 4, hipMemcpyDeviceToHost, stream_));
+  launch_us_alpha(stream_, dh(ws), (int64_t)rows, W, dw(ws), db(ws), smooth, noise, al);
+  download(stream_, alphas_raw, (const float*)al, rows);
+  launch_us_peak(stream_, al, dn(ws), B, T3, thr, pk);
+  download(stream_, alphas, (const float*)al, rows);
+  download(stream_, peak, (const float*)pk, rows);
   PF_HIP(hipStreamSynchronize(stream_));
 }
 
@@ -2337,30 +2070,27 @@ void Engine::op_logsoftmax_argmax(const float* x, int64_t rows, int V, float* y,
   PF_HIP(hipSetDevice(device_));
   if (rows == 0) return;
   const int ld = (int)round_up(V, 4);
-  ensure(ws_tmp_, (size_t)rows * ld * 4 + (size_t)rows * 8 + 256);
-  float* xd = (float*)ws_tmp_.p;
-  int64_t* idd = (int64_t*)((char*)ws_tmp_.p + round_up((int64_t)rows * ld * 4, 256));
-  PF_HIP(hipMemcpy2DAsync(xd, (size_t)ld * 4, x, (size_t)V * 4, (size_t)V * 4, rows, hipMemcpyHostToDevice, stream_));
-  launch_argmax(stream_, xd, rows, V, ld, y ? 2 : 1, idd);
-  if (y) PF_HIP(hipMemcpy2DAsync(y, (size_t)V * 4, xd, (size_t)ld * 4, (size_t)V * 4, rows, hipMemcpyDeviceToHost, stream_));
-  PF_HIP(hipMemcpyAsync(ids, idd, (size_t)rows * 8, hipMemcpyDeviceToHost, stream_));
+  StageCarve st;
+  const auto dx = st.take<float>((size_t)rows * ld); const auto did = st.take<int64_t>(rows);
+  void* ws = op_ws(st);
+  upload2d(stream_, dx(ws), ld, x, V, V, rows);
+  launch_argmax(stream_, dx(ws), rows, V, ld, y ? 2 : 1, did(ws));
+  if (y) download2d(stream_, y, V, (const float*)dx(ws), ld, V, rows);
+  download(stream_, ids, (const int64_t*)did(ws), rows);
   PF_HIP(hipStreamSynchronize(stream_));
 }
 
 void Engine::op_layernorm(const float* x, const float* g, const float* b, int64_t rows, int D, float* y) {
   PF_HIP(hipSetDevice(device_));
   if (rows == 0) return;
-  size_t off = 0;
-  const Carve carve{off};
-  const size_t ox = carve((size_t)rows * D * 4), og = carve((size_t)D * 4), obb = carve((size_t)D * 4), oy = carve((size_t)rows * D * 4);
-  ensure(ws_tmp_, off);
-  char* base = (char*)ws_tmp_.p;
-  PF_HIP(hipMemcpyAsync(base + ox, x, (size_t)rows * D * 4, hipMemcpyHostToDevice, stream_));
-  PF_HIP(hipMemcpyAsync(base + og, g, (size_t)D * 4, hipMemcpyHostToDevice, stream_));
-  PF_HIP(hipMemcpyAsync(base + obb, b, (size_t)D * 4, hipMemcpyHostToDevice, stream_));
-  launch_layernorm(stream_, (const float*)(base + ox), rows, D, (const float*)(base + og), (const float*)(base + obb),
-                   nullptr, 0, (float*)(base + oy), D);
-  PF_HIP(hipMemcpyAsync(y, base + oy, (size_t)rows * D * 4, hipMemcpyDeviceToHost, stream_));
+  StageCarve st;
+  const auto dx = st.take<float>((size_t)rows * D), dg = st.take<float>(D), db = st.take<float>(D), dy = st.take<float>((size_t)rows * D);
+  void* ws = op_ws(st);
+  upload(stream_, dx(ws), x, (size_t)rows * D);
+  upload(stream_, dg(ws), g, D);
+  upload(stream_, db(ws), b, D);
+  launch_layernorm(stream_, dx(ws), rows, D, dg(ws), db(ws), nullptr, 0, dy(ws), D);
+  download(stream_, y, (const float*)dy(ws), (size_t)rows * D);
   PF_HIP(hipStreamSynchronize(stream_));
 }
 
@@ -2368,38 +2098,24 @@ void Engine::op_attention(const float* q, const float* k, const float* v, int B,
   PF_HIP(hipSetDevice(device_));
   const int Dm = H * 128;
   const int64_t nq = (int64_t)B * Lq, nk = (int64_t)B * Lk;
-  size_t off = 0;
-  const Carve carve{off};
-  const size_t oin = carve((size_t)std::max(nq, nk) * Dm * 4);
-  const size_t oq = carve((size_t)(nq + 128) * Dm * 2), ok = carve((size_t)(nk + 128) * Dm * 2);
-  const size_t ov = carve((size_t)(nk + 128) * Dm * 2), oo = carve((size_t)(nq + 128) * Dm * 2), oo32 = carve((size_t)nq * Dm * 4);
-  ensure(ws_tmp_, off);
-  char* base = (char*)ws_tmp_.p;
-  PF_HIP(hipMemsetAsync(base + oq, 0, off - oq, stream_));
-  auto up = [&](const float* src, int64_t rows, size_t dst) {
-    PF_HIP(hipMemcpyAsync(base + oin, src, (size_t)rows * Dm * 4, hipMemcpyHostToDevice, stream_));
-    launch_f32_to_f16(stream_, (const float*)(base + oin), rows, Dm, Dm, (half_t*)(base + dst), Dm);
-    PF_HIP(hipStreamSynchronize(stream_));
-  };
-  up(q, nq, oq); up(k, nk, ok); up(v, nk, ov);
+  StageCarve st;
+  const auto din = st.take<float>((size_t)std::max(nq, nk) * Dm);          // the fp32 staging slot
+  const auto dq = st.take<half_t>((size_t)(nq + 128) * Dm), dk = st.take<half_t>((size_t)(nk + 128) * Dm);
+  const auto dv = st.take<half_t>((size_t)(nk + 128) * Dm), dout = st.take<half_t>((size_t)(nq + 128) * Dm);
+  void* ws = op_ws(st);
+  PF_HIP(hipMemsetAsync(dq(ws), 0, st.off - dq.off, stream_));
+  upload_f16(stream_, din(ws), q, nq, Dm, dq(ws), Dm);
+  upload_f16(stream_, din(ws), k, nk, Dm, dk(ws), Dm);
+  upload_f16(stream_, din(ws), v, nk, Dm, dv(ws), Dm);
   AttnArgs a{};
-  a.q = (half_t*)(base + oq); a.k = (half_t*)(base + ok); a.v = (half_t*)(base + ov); a.o = (half_t*)(base + oo);
+  a.q = dq(ws); a.k = dk(ws); a.v = dv(ws); a.o = dout(ws);
   a.q_bstride = (int64_t)Lq * Dm; a.k_bstride = a.v_bstride = (int64_t)Lk * Dm; a.o_bstride = (int64_t)Lq * Dm;
   a.q_rstride = a.k_rstride = a.v_rstride = a.o_rstride = Dm;
   a.B = B; a.H = H; a.Lq = Lq; a.Lk = Lk;
   prof_begin("attn_op", 4.0 * B * (double)Lq * Lk * Dm);
   launch_attention(stream_, a);
   prof_end("attn_op");
-  // f16 -> f32 on the host side of the copy
-  std::vector<uint16_t> tmp((size_t)nq * Dm);
-  PF_HIP(hipMemcpyAsync(tmp.data(), base + oo, tmp.size() * 2, hipMemcpyDeviceToHost, stream_));
-  PF_HIP(hipStreamSynchronize(stream_));
-  for (size_t i = 0; i < tmp.size(); ++i) {
-    half_t hv;
-    std::memcpy(&hv, &tmp[i], 2);
-    o[i] = (float)hv;
-  }
-  (void)oo32;
+  download_f16(stream_, o, dout(ws), nq, Dm, Dm);
 }
 
 // The attention kernels on caller data, launched as the pipeline launches them (packed / interleaved / blocked operands, shared
@@ -2436,13 +2152,12 @@ void Engine::op_attention_ex(const float* q, const float* k, const float* v, int
   const size_t oes = kind == 1 ? 4 : 2;
   const size_t obytes = (size_t)(nq + kSlack) * orow * oes;
   PF_CHECK(raw_bytes == (int64_t)obytes, PF_ERR_INVALID_ARG, "attention_ex: raw_bytes must be " + std::to_string(obytes));
-  size_t off = 0;
-  const Carve carve{off};
-  size_t om[3];
-  for (int m = 0; m < 3; ++m) om[m] = carve((size_t)rows[m] * ld[m] * es);
-  const size_t oo = carve(obytes), org = carve(quant_scratch_bytes());
-  ensure(ws_tmp_, off);
-  char* base = (char*)ws_tmp_.p;
+  StageCarve st;
+  const Field<uint8_t> dm[3] = {st.take<uint8_t>((size_t)rows[0] * ld[0] * es), st.take<uint8_t>((size_t)rows[1] * ld[1] * es),
+                                st.take<uint8_t>((size_t)rows[2] * ld[2] * es)};     // (f16 or fp32 by kind)
+  const auto dout = st.take<uint8_t>(obytes);
+  const auto drg = st.take<float>(quant_scratch_bytes() / 4);
+  void* ws = op_ws(st);
   // host images
   std::vector<std::vector<uint16_t>> img16(3);
   std::vector<std::vector<float>> img32(3);
@@ -2456,55 +2171,48 @@ void Engine::op_attention_ex(const float* q, const float* k, const float* v, int
     for (int64_t r = 0; r < n_rows; ++r)
       for (int c = 0; c < Dm; ++c) {
         const float x = src[(size_t)r * Dm + c];
-        size_t at;
-        if (layout == 3 && which < 2) {
-          const int cc = col[which] + c;
-          at = (((size_t)(r >> 5) * (2 * Dm / 8) + (cc >> 3)) * 32 + (r & 31)) * 8 + (cc & 7);
-        } else {
-          at = (size_t)r * ld[m] + col[which] + c;
-        }
+        const size_t at = layout == 3 && which < 2 ? blocked_index(r, col[which] + c, 2 * Dm) : (size_t)r * ld[m] + col[which] + c;
         if (kind == 0) { const half_t hx = (half_t)x; std::memcpy(&img16[m][at], &hx, 2); }
         else img32[m][at] = x;
       }
   };
   put(0, q, nq); put(1, k, nk); put(2, v, nk);
   for (int m = 0; m < 3; ++m)
-    if (rows[m]) PF_HIP(hipMemcpyAsync(base + om[m], kind == 0 ? (const void*)img16[m].data() : (const void*)img32[m].data(),
-                                       (size_t)rows[m] * ld[m] * es, hipMemcpyHostToDevice, stream_));
+    upload(stream_, dm[m](ws), kind == 0 ? (const uint8_t*)img16[m].data() : (const uint8_t*)img32[m].data(), (size_t)rows[m] * ld[m] * es);
   std::vector<uint16_t> oimg(obytes / 2, (uint16_t)PF_ATTN_CANARY);
-  PF_HIP(hipMemcpyAsync(base + oo, oimg.data(), obytes, hipMemcpyHostToDevice, stream_));
+  upload(stream_, dout(ws), (const uint8_t*)oimg.data(), obytes);
   std::vector<float> rimg(quant_scratch_bytes() / 4, qnan);
-  PF_HIP(hipMemcpyAsync(base + org, rimg.data(), rimg.size() * 4, hipMemcpyHostToDevice, stream_));
+  upload(stream_, drg(ws), rimg.data(), rimg.size());
   const int64_t q_bs = (int64_t)Lq * ld[mat[0]], k_bs = ds.shared_kv ? 0 : (int64_t)Lk * ld[mat[1]], v_bs = ds.shared_kv ? 0 : (int64_t)Lk * ld[mat[2]];
   *ran = 1;
   if (kind == 0) {
     AttnArgs a{};
-    a.q = (half_t*)(base + om[mat[0]]) + col[0]; a.k = (half_t*)(base + om[mat[1]]) + col[1]; a.v = (half_t*)(base + om[mat[2]]) + col[2];
+    a.q = (half_t*)dm[mat[0]](ws) + col[0]; a.k = (half_t*)dm[mat[1]](ws) + col[1]; a.v = (half_t*)dm[mat[2]](ws) + col[2];
     a.q_bstride = q_bs; a.k_bstride = k_bs; a.v_bstride = v_bs;
     a.q_rstride = (int)ld[mat[0]]; a.k_rstride = (int)ld[mat[1]]; a.v_rstride = (int)ld[mat[2]];
     if (layout == 3) {
-      a.q = a.k = (half_t*)(base + om[0]);
+      a.q = a.k = (half_t*)dm[0](ws);
       a.qk_blocked = 1; a.blk_groups = 2 * Dm / 8; a.blk_brows = Lq; a.blk_kgrp = Dm / 8;
       a.q_rstride = a.k_rstride = 8;                        // ignored (alignment checks only)
     }
-    a.o = (half_t*)(base + oo); a.o_bstride = (int64_t)Lq * o_ld; a.o_rstride = o_ld;
+    a.o = (half_t*)dout(ws); a.o_bstride = (int64_t)Lq * o_ld; a.o_rstride = o_ld;
     a.B = B; a.H = H; a.Lq = Lq; a.Lk = Lk;
     a.force_nw = ds.form;
-    a.range = range_out ? (float*)(base + org) : nullptr;
+    a.range = range_out ? drg(ws) : nullptr;
     launch_attention(stream_, a);
   } else {
-    const float* qd = (const float*)(base + om[mat[0]]) + col[0];
-    const float* kd = (const float*)(base + om[mat[1]]) + col[1];
-    const float* vd = (const float*)(base + om[mat[2]]) + col[2];
+    const float* qd = (const float*)dm[mat[0]](ws) + col[0];
+    const float* kd = (const float*)dm[mat[1]](ws) + col[1];
+    const float* vd = (const float*)dm[mat[2]](ws) + col[2];
     if (kind == 1)
-      launch_attention_f32(stream_, qd, q_bs, (int)ld[mat[0]], kd, k_bs, (int)ld[mat[1]], vd, v_bs, (int)ld[mat[2]], (float*)(base + oo),
+      launch_attention_f32(stream_, qd, q_bs, (int)ld[mat[0]], kd, k_bs, (int)ld[mat[1]], vd, v_bs, (int)ld[mat[2]], (float*)dout(ws),
                            (int64_t)Lq * o_ld, o_ld, B, H, Lq, Lk);
     else if (!launch_attention_f32_pair(stream_, qd, q_bs, (int)ld[mat[0]], kd, k_bs, (int)ld[mat[1]], vd, v_bs, (int)ld[mat[2]],
-                                        (half_t*)(base + oo), (int64_t)Lq * 2 * o_ld, 2 * o_ld, o_ld, B, H, Lq, Lk))
+                                        (half_t*)dout(ws), (int64_t)Lq * 2 * o_ld, 2 * o_ld, o_ld, B, H, Lq, Lk))
       *ran = 0;
   }
-  PF_HIP(hipMemcpyAsync(raw, base + oo, obytes, hipMemcpyDeviceToHost, stream_));
-  if (range_out) PF_HIP(hipMemcpyAsync(range_out, base + org, 256 * 2 * sizeof(float), hipMemcpyDeviceToHost, stream_));
+  download(stream_, (uint8_t*)raw, (const uint8_t*)dout(ws), obytes);
+  if (range_out) download(stream_, range_out, (const float*)drg(ws), (size_t)256 * 2);
   PF_HIP(hipStreamSynchronize(stream_));
   for (int64_t r = 0; r < nq; ++r)
     for (int c = 0; c < Dm; ++c) {
@@ -2537,58 +2245,40 @@ void Engine::op_qkv_attention(const float* x, const float* w, const float* bias,
   const int Kpad = (int)round_up(K, 64);
   PF_CHECK(gemm_qkvp_applicable(M, Kpad, Kpad, Kpad, D), PF_ERR_INVALID_ARG, "qkv_attention: shape not covered by the 256 x 192 kernel");
   const int64_t Mp = round_up(M, 256) + 128;
-  size_t off = 0;
-  const Carve carve{off};
-  const size_t o32 = carve((size_t)std::max<int64_t>((int64_t)M * K, (int64_t)N * K) * 4), oA = carve((size_t)Mp * Kpad * 2);
-  const size_t oW = carve((size_t)N * Kpad * 2), oWp = carve((size_t)N * Kpad * 2), ob = carve((size_t)N * 4), obp = carve((size_t)N * 4);
-  const size_t oqk = carve((size_t)Mp * 2 * D * 2), ov = carve((size_t)Mp * D * 2), oc = carve((size_t)Mp * D * 2);
-  ensure(ws_tmp_, off);
-  char* base = (char*)ws_tmp_.p;
-  PF_HIP(hipMemsetAsync(base + oA, 0, (size_t)Mp * Kpad * 2, stream_));
-  PF_HIP(hipMemsetAsync(base + oW, 0, (size_t)N * Kpad * 2, stream_));
-  fill_hostile_rows(stream_, (half_t*)(base + oA), Kpad, M, Mp, K);
-  fill_sentinel16(stream_, base + oqk, (size_t)Mp * 2 * D);
-  fill_sentinel16(stream_, base + ov, (size_t)Mp * D);
-  PF_HIP(hipMemcpyAsync(base + o32, x, (size_t)M * K * 4, hipMemcpyHostToDevice, stream_));
-  launch_f32_to_f16(stream_, (const float*)(base + o32), M, K, K, (half_t*)(base + oA), Kpad);
-  PF_HIP(hipStreamSynchronize(stream_));
-  PF_HIP(hipMemcpyAsync(base + o32, w, (size_t)N * K * 4, hipMemcpyHostToDevice, stream_));
-  launch_f32_to_f16(stream_, (const float*)(base + o32), N, K, K, (half_t*)(base + oW), Kpad);
-  if (bias) PF_HIP(hipMemcpyAsync(base + ob, bias, (size_t)N * 4, hipMemcpyHostToDevice, stream_));
-  launch_qkv_permute(stream_, (half_t*)(base + oW), Kpad, bias ? (const float*)(base + ob) : nullptr, (half_t*)(base + oWp), (float*)(base + obp));
+  StageCarve st;
+  const auto d32 = st.take<float>((size_t)std::max<int64_t>((int64_t)M * K, (int64_t)N * K));   // the fp32 staging slot
+  const auto dA = st.take<half_t>((size_t)Mp * Kpad), dW = st.take<half_t>((size_t)N * Kpad), dWp = st.take<half_t>((size_t)N * Kpad);
+  const auto db = st.take<float>(N), dbp = st.take<float>(N);
+  const auto dqk = st.take<half_t>((size_t)Mp * 2 * D), dv = st.take<half_t>((size_t)Mp * D), dc = st.take<half_t>((size_t)Mp * D);
+  void* ws = op_ws(st);
+  half_t* qk = dqk(ws);
+  half_t* vb = dv(ws);
+  fill_sentinel(stream_, qk, (size_t)Mp * 2 * D);
+  fill_sentinel(stream_, vb, (size_t)Mp * D);
+  upload_operand16(stream_, d32(ws), x, M, K, dA(ws), Kpad, Mp);
+  upload_operand16(stream_, d32(ws), w, N, K, dW(ws), Kpad, N);
+  if (bias) upload(stream_, db(ws), bias, N);
+  launch_qkv_permute(stream_, dW(ws), Kpad, bias ? db(ws) : nullptr, dWp(ws), dbp(ws));
   const float qscale = 1.0f / std::sqrt((float)(D / H));
-  half_t* qk = (half_t*)(base + oqk);
-  half_t* vb = (half_t*)(base + ov);
   prof_begin("gemm_op", 2.0 * M * (double)N * K);
-  launch_gemm_qkvp(stream_, (half_t*)(base + oA), Kpad, (half_t*)(base + oWp), Kpad, (const float*)(base + obp), M, Kpad, qscale, qk, vb, D);
+  launch_gemm_qkvp(stream_, dA(ws), Kpad, dWp(ws), Kpad, dbp(ws), M, Kpad, qscale, qk, vb, D);
   prof_end("gemm_op");
-  check_guard<uint16_t>(stream_, "qkv_attention", "the blocked Q | K", qk, kSentinel16, Mp, M, 2 * D, 2 * D, true);
-  check_guard<uint16_t>(stream_, "qkv_attention", "V", vb, kSentinel16, Mp, M, D, D, false);
+  check_guard(stream_, "qkv_attention: the blocked Q | K", qk, kSentinel16, result_geom(Mp, M, 2 * D, 2 * D, round_up(M, 256), true));
+  check_guard(stream_, "qkv_attention: V", vb, kSentinel16, result_geom(Mp, M, D, D, round_up(M, 256)));
   AttnArgs a{};
   a.q = qk; a.k = qk; a.qk_blocked = 1; a.blk_groups = 2 * D / 8; a.blk_brows = T; a.blk_kgrp = D / 8;
   a.v = vb; a.v_bstride = (int64_t)T * D; a.v_rstride = D;
-  a.o = (half_t*)(base + oc); a.o_bstride = (int64_t)T * D; a.o_rstride = D;
+  a.o = dc(ws); a.o_bstride = (int64_t)T * D; a.o_rstride = D;
   a.q_rstride = a.k_rstride = 8;                          // ignored (alignment checks only)
   a.B = B; a.H = H; a.Lq = T; a.Lk = T;
   prof_begin("attn_op", 4.0 * B * (double)T * T * D);
   launch_attention(stream_, a);
   prof_end("attn_op");
-  std::vector<half_t> hqk((size_t)Mp * 2 * D), hv((size_t)M * D), hc((size_t)M * D);
-  PF_HIP(hipMemcpyAsync(hqk.data(), qk, hqk.size() * 2, hipMemcpyDeviceToHost, stream_));
-  PF_HIP(hipMemcpyAsync(hv.data(), vb, hv.size() * 2, hipMemcpyDeviceToHost, stream_));
-  PF_HIP(hipMemcpyAsync(hc.data(), base + oc, hc.size() * 2, hipMemcpyDeviceToHost, stream_));
+  if (q_out) download_blocked16(stream_, q_out, qk, M, 2 * D, 0, D);
+  if (k_out) download_blocked16(stream_, k_out, qk, M, 2 * D, D, D);
+  if (v_out) download_f16(stream_, v_out, vb, M, D, D);
+  if (ctx_out) download_f16(stream_, ctx_out, dc(ws), M, D, D);
   PF_HIP(hipStreamSynchronize(stream_));
-  const int G = 2 * D / 8;
-  for (int m = 0; m < M; ++m)
-    for (int c = 0; c < 2 * D; ++c) {
-      const float val = (float)hqk[(((size_t)(m >> 5) * G + (c >> 3)) * 32 + (m & 31)) * 8 + (c & 7)];
-      if (c < D) { if (q_out) q_out[(size_t)m * D + c] = val; }
-      else if (k_out) k_out[(size_t)m * D + c - D] = val;
-    }
-  for (size_t i = 0; i < hv.size(); ++i) {
-    if (v_out) v_out[i] = (float)hv[i];
-    if (ctx_out) ctx_out[i] = (float)hc[i];
-  }
 }
 
 void Engine::op_fsmn(const float* v, const float* w, const float* mask, int B, int T, int D, int k, float* y) {
@@ -2596,20 +2286,15 @@ void Engine::op_fsmn(const float* v, const float* w, const float* mask, int B, i
   PF_CHECK(D % 4 == 0, PF_ERR_INVALID_ARG, "fsmn: D must be a multiple of 4");
   const size_t n = (size_t)B * T * D;
   if (n == 0) return;
-  std::vector<float> wT((size_t)D * k);
-  for (int c = 0; c < D; ++c)
-    for (int j = 0; j < k; ++j) wT[(size_t)j * D + c] = w[(size_t)c * k + j];
-  size_t off = 0;
-  const Carve carve{off};
-  const size_t ov = carve(n * 4), ow = carve(wT.size() * 4), om = carve((size_t)B * T * 4), oy = carve(n * 4);
-  ensure(ws_tmp_, off);
-  char* base = (char*)ws_tmp_.p;
-  PF_HIP(hipMemcpyAsync(base + ov, v, n * 4, hipMemcpyHostToDevice, stream_));
-  PF_HIP(hipMemcpyAsync(base + ow, wT.data(), wT.size() * 4, hipMemcpyHostToDevice, stream_));
-  if (mask) PF_HIP(hipMemcpyAsync(base + om, mask, (size_t)B * T * 4, hipMemcpyHostToDevice, stream_));
-  launch_fsmn_f32(stream_, (const float*)(base + ov), (const float*)(base + ow), mask ? (const float*)(base + om) : nullptr,
-                  B, T, D, k, (float*)(base + oy));
-  PF_HIP(hipMemcpyAsync(y, base + oy, n * 4, hipMemcpyDeviceToHost, stream_));
+  const std::vector<float> wT = fsmn_taps(w, D, k);
+  StageCarve st;
+  const auto dv = st.take<float>(n), dw = st.take<float>(wT.size()), dm = st.take<float>((size_t)B * T), dy = st.take<float>(n);
+  void* ws = op_ws(st);
+  upload(stream_, dv(ws), v, n);
+  upload(stream_, dw(ws), wT.data(), wT.size());
+  if (mask) upload(stream_, dm(ws), mask, (size_t)B * T);
+  launch_fsmn_f32(stream_, dv(ws), dw(ws), mask ? dm(ws) : nullptr, B, T, D, k, dy(ws));
+  download(stream_, y, (const float*)dy(ws), n);
   PF_HIP(hipStreamSynchronize(stream_));
 }
 
@@ -2618,29 +2303,28 @@ void Engine::op_cif(const float* H, const float* alphas, int B, int T, int D, fl
   PF_HIP(hipSetDevice(device_));
   PF_CHECK(D % 4 == 0 && B > 0 && T > 0, PF_ERR_INVALID_ARG, "cif: bad shape");
   const int T1 = T + 1;
-  size_t off = 0;
-  const Carve carve{off};
-  const size_t oH = carve((size_t)B * T * D * 4);
-  const CifCarve o_cif(carve, B, T1);
-  const size_t oa = o_cif.al, oE = carve((size_t)B * std::max(Lcap, 1) * D * 4);
-  ensure(ws_tmp_, off);
-  char* base = (char*)ws_tmp_.p;
-  const CifPlan p = o_cif.plan(base);
-  PF_HIP(hipMemcpyAsync(base + oH, H, (size_t)B * T * D * 4, hipMemcpyHostToDevice, stream_));
-  PF_HIP(hipMemcpyAsync(base + oa, alphas, (size_t)B * T1 * 4, hipMemcpyHostToDevice, stream_));
-  if (mc_.cif_cumsum) launch_cif_scan_cumsum(stream_, (const float*)(base + oa), B, T1, p);
-  else launch_cif_scan(stream_, (const float*)(base + oa), B, T1, thr, p);
+  StageCarve st;
+  const auto dH = st.take<float>((size_t)B * T * D);
+  const CifCarve o_cif(Carve{st.off, st.align}, B, T1);             // the stage's arrays, in the order every arena keeps them
+  const Field<float> da{o_cif.al, (size_t)B * T1};
+  const auto dE = st.take<float>((size_t)B * std::max(Lcap, 1) * D);
+  void* ws = op_ws(st);
+  const CifPlan p = o_cif.plan(static_cast<char*>(ws));
+  upload(stream_, dH(ws), H, (size_t)B * T * D);
+  upload(stream_, da(ws), alphas, (size_t)B * T1);
+  if (mc_.cif_cumsum) launch_cif_scan_cumsum(stream_, da(ws), B, T1, p);
+  else launch_cif_scan(stream_, da(ws), B, T1, thr, p);
   int32_t L = 0;
-  PF_HIP(hipMemcpyAsync(&L, p.max_count, 4, hipMemcpyDeviceToHost, stream_));
-  PF_HIP(hipMemcpyAsync(fire_count, p.fire_count, (size_t)B * 4, hipMemcpyDeviceToHost, stream_));
-  PF_HIP(hipMemcpyAsync(token_num, p.token_num, (size_t)B * 4, hipMemcpyDeviceToHost, stream_));
+  download(stream_, &L, (const int32_t*)p.max_count, 1);
+  download(stream_, fire_count, (const int32_t*)p.fire_count, B);
+  download(stream_, token_num, (const int32_t*)p.token_num, B);
   PF_HIP(hipStreamSynchronize(stream_));
   if (L_out) *L_out = L;
   PF_CHECK(L <= Lcap, PF_ERR_CAPACITY, "cif: Lcap " + std::to_string(Lcap) + " < L = " + std::to_string(L));
   if (Lcap == 0) return;
-  if (mc_.cif_cumsum) launch_cif_gather_cumsum(stream_, (const float*)(base + oH), (const float*)(base + oa), B, T, D, T1, p, Lcap, (float*)(base + oE));
-  else launch_cif_gather(stream_, (const float*)(base + oH), B, T, D, T1, p, Lcap, (float*)(base + oE));
-  PF_HIP(hipMemcpyAsync(E, base + oE, (size_t)B * Lcap * D * 4, hipMemcpyDeviceToHost, stream_));
+  if (mc_.cif_cumsum) launch_cif_gather_cumsum(stream_, dH(ws), da(ws), B, T, D, T1, p, Lcap, dE(ws));
+  else launch_cif_gather(stream_, dH(ws), B, T, D, T1, p, Lcap, dE(ws));
+  download(stream_, E, (const float*)dE(ws), (size_t)B * Lcap * D);
   PF_HIP(hipStreamSynchronize(stream_));
 }
 
@@ -2652,22 +2336,21 @@ void Engine::op_cif_alphas(const float* H, int B, int T, float* alphas) {
   const int D = mc_.d_model, taps = mc_.cif_l_order + mc_.cif_r_order + 1;
   const int64_t M = (int64_t)B * T, Mp = round_up(M, 128) + 128;     // the pipeline's row padding (Engine::gemm: out_padded)
   PF_CHECK(M < (1ll << 31) / (taps * D), PF_ERR_INVALID_ARG, "cif_alphas: batch too large for 32-bit row indexing");
-  size_t off = 0;
-  const Carve carve{off};
-  const size_t oH = carve((size_t)M * D * 4), oa = carve((size_t)B * (T + 1) * 4), oH16 = carve((size_t)Mp * D * 2);
-  const size_t ocol = carve((size_t)Mp * taps * D * 4), oconv = carve((size_t)Mp * D * 4);
-  ensure(ws_tmp_, off);
-  char* base = (char*)ws_tmp_.p;
-  PF_HIP(hipMemcpyAsync(base + oH, H, (size_t)M * D * 4, hipMemcpyHostToDevice, stream_));
-  PF_HIP(hipMemsetAsync(base + oa, 0xFF, (size_t)B * (T + 1) * 4, stream_));          // NaN: an alpha nobody wrote shows
+  StageCarve st;
+  const auto dH = st.take<float>((size_t)M * D), da = st.take<float>((size_t)B * (T + 1));
+  const auto dH16 = st.take<half_t>((size_t)Mp * D);
+  const auto dcol = st.take<float>((size_t)Mp * taps * D), dconv = st.take<float>((size_t)Mp * D);   // (col: f16 in the f16 stage)
+  void* ws = op_ws(st);
+  upload(stream_, dH(ws), H, (size_t)M * D);
+  PF_HIP(hipMemsetAsync(da(ws), 0xFF, (size_t)B * (T + 1) * 4, stream_));          // NaN: an alpha nobody wrote shows
   if (fp32_mode_) {
-    cif_alpha_stage32((const float*)(base + oH), B, T, (float*)(base + ocol), (float*)(base + oconv), (float*)(base + oa));
+    cif_alpha_stage32(dH(ws), B, T, dcol(ws), dconv(ws), da(ws));
     x3a_src_ = nullptr;                                                                // (the operand lives in ws_tmp_)
   } else {
-    launch_f32_to_f16(stream_, (const float*)(base + oH), M, D, D, (half_t*)(base + oH16), D);
-    cif_alpha_stage((const half_t*)(base + oH16), B, T, (half_t*)(base + ocol), (float*)(base + oconv), (float*)(base + oa), nullptr);
+    launch_f32_to_f16(stream_, dH(ws), M, D, D, dH16(ws), D);
+    cif_alpha_stage(dH16(ws), B, T, (half_t*)dcol(ws), dconv(ws), da(ws), nullptr);
   }
-  PF_HIP(hipMemcpyAsync(alphas, base + oa, (size_t)B * (T + 1) * 4, hipMemcpyDeviceToHost, stream_));
+  download(stream_, alphas, (const float*)da(ws), (size_t)B * (T + 1));
   PF_HIP(hipStreamSynchronize(stream_));
 }
 
@@ -2676,10 +2359,11 @@ void Engine::op_encoder(const float* speech, int B, int T, float* H) {
   PF_CHECK(speech && H && B > 0 && T > 0, PF_ERR_INVALID_ARG, "encoder: bad arguments");
   const size_t n = (size_t)B * T * mc_.feat_dim;
   ensure(ws_speech_, n * 4);
-  PF_HIP(hipMemcpyAsync(ws_speech_.p, speech, n * 4, hipMemcpyHostToDevice, stream_));
+  upload(stream_, (float*)ws_speech_.p, speech, n);
   encoder((const float*)ws_speech_.p, B, T);
-  PF_HIP(hipMemcpyAsync(H, H32_, (size_t)B * T * mc_.d_model * 4, hipMemcpyDeviceToHost, stream_));
+  download(stream_, H, (const float*)H32_, (size_t)B * T * mc_.d_model);
   PF_HIP(hipStreamSynchronize(stream_));
 }
 
 }  // namespace pf
+
