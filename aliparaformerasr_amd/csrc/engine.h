@@ -182,6 +182,9 @@ class Engine {
   // multi-device groups (group.h): the decoder length becomes the maximum over all shards of the batch
   void set_l_hook(std::function<int(int)> h) { l_hook_ = std::move(h); }
   const HostBatchOut& last_result() const { return last_; }
+  // the same for a reader that lets go of the engine before it is done reading (Recognizer::Forward, after sync()): a copy, so
+  // the pf_fetch_* calls still serve this forward.  No logits: those are read from the device or live in a per-thread slot.
+  HostBatchOut result_copy() const { return last_; }
   void copy_logits(HostBatchOut& r);                 // host copy of the last forward's log-probs into r.logits
   const int64_t* ids_device() const { return ids_dev_; }
   const int32_t* token_num_device() const { return plan_.token_num; }

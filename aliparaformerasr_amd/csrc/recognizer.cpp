@@ -174,61 +174,6 @@ ResultEntity decode_multi_one(const TokenTable& table, const std::vector<int64_t
   });
 }
 
-TsList time_stamp_lfr6(const float* us_cif_peak, int n, const std::vector<int64_t>& tokens_in) {
-  // float32 arithmetic throughout, (int)(t*1000) truncation (quirk Q10)
-  const int START_END_THRESHOLD = 5, MAX_TOKEN_DURATION = 30;
-  volatile float tr0 = 10.0f * 6;
-  volatile float tr1 = tr0 / 1000;
-  const float TIME_RATE = tr1 / 3;
-  const float total_offset = -1.5f;
-  const int num_frames = n;
-  if (tokens_in.empty()) throw Error(PF_ERR_RECOGNITION, "Sequence contains no elements");   // tokens.Last()
-  std::vector<int64_t> tokens(tokens_in);
-  if (tokens.back() == 2) tokens.pop_back();
-  std::vector<float> fire;
-  for (int i = 0; i < n; ++i)
-    if ((double)us_cif_peak[i] > (double)1.0f - 1e-4) fire.push_back((float)i + total_offset);
-  if (fire.empty()) throw Error(PF_ERR_RECOGNITION, "Index was out of range (no CIF fire)");   // fire_place[0]
-  std::vector<std::array<float, 2>> tl;
-  std::vector<bool> nc;
-  if (fire[0] > (float)START_END_THRESHOLD) {
-    tl.push_back({0.0f, fire[0] * TIME_RATE});
-    nc.push_back(false);
-  }
-  const int nf = (int)fire.size();
-  for (int i = 0; i < nf - 1; ++i) {
-    if (i >= (int)tokens.size()) throw Error(PF_ERR_RECOGNITION, "Index was outside the bounds of the array");
-    nc.push_back(tokens[i] != 1);
-    if (i == nf - 2 || MAX_TOKEN_DURATION < 0 || fire[i + 1] - fire[i] < (float)MAX_TOKEN_DURATION) {
-      tl.push_back({fire[i] * TIME_RATE, fire[i + 1] * TIME_RATE});
-    } else {
-      const float split = fire[i] + (float)MAX_TOKEN_DURATION;
-      tl.push_back({fire[i] * TIME_RATE, split * TIME_RATE});
-      tl.push_back({split * TIME_RATE, fire[i + 1] * TIME_RATE});
-      nc.push_back(false);
-    }
-  }
-  if ((float)num_frames - fire.back() > (float)START_END_THRESHOLD) {
-    const float end = ((float)num_frames + fire.back()) / 2;
-    if (tl.empty()) throw Error(PF_ERR_RECOGNITION, "Sequence contains no elements");
-    tl.back()[1] = end * TIME_RATE;
-    tl.push_back({end * TIME_RATE, (float)num_frames * TIME_RATE});
-    nc.push_back(false);
-  } else {
-    if (tl.empty()) throw Error(PF_ERR_RECOGNITION, "Sequence contains no elements");
-    tl.back()[1] = (float)num_frames * TIME_RATE;
-  }
-  nc.push_back(true);
-  TsList out;
-  const size_t m = std::min(nc.size(), tl.size());
-  for (size_t i = 0; i < m; ++i) {
-    if (!nc[i]) continue;
-    volatile float a = tl[i][0] * 1000, b = tl[i][1] * 1000;
-    out.push_back({(int32_t)a, (int32_t)b});
-  }
-  return out;
-}
-
 std::vector<std::vector<int32_t>> hotword_ids(const std::vector<std::string>& tokens,
                                               const std::vector<std::string>& lines, int sos_eos_id) {
   std::vector<std::vector<int32_t>> hw;
@@ -500,7 +445,9 @@ Recognizer::Recognizer(const std::string& model, const std::string& config, cons
   engine_kind_ = engines_[0]->model().kind;
   plain_paraformer_ = engines_[0]->model().kind_id() == 0 && !engines_[0]->model().seaco;
   sv_device_prompt_ = engines_[0]->has_device_prompt();
-  if (engine_kind_ == "sensevoicesmall") { sv_embed_ = engines_[0]->embed_table(); sv_use_itn_ = engines_[0]->model().use_itn; }
+  if (engine_kind_ == "sensevoicesmall") {
+    sv_embed_ = engines_[0]->embed_table(); sv_use_itn_ = engines_[0]->model().use_itn; sv_width_ = engines_[0]->model().feat_dim;
+  }
   feat_m_ = (conf_.lfr_m != 1 || conf_.lfr_n != 1) ? conf_.lfr_m : 1;
   // the device form of a stream needs the batched front-end to compute exactly what AddSamples + PadSequence would
   device_streams_ = device_streams_ && engines_[0]->staged_frontend_matches_host();
@@ -683,7 +630,6 @@ void Recognizer::ForwardLong(const std::vector<Stream*>& streams, std::vector<Re
   if (streams.empty()) return;
   pf_vad_config cfg; int batch_max; int64_t budget; std::string sep;
   { std::lock_guard<std::mutex> lk(vad_mu_); cfg = vad_cfg_; batch_max = vad_batch_max_; budget = vad_budget_; sep = vad_sep_; }
-  struct Piece { int stream, b, e; };
   std::vector<Piece> pieces;
   try {
     if (disposed_) throw Error(PF_ERR_DISPOSED, "OfflineRecognizer");
@@ -710,44 +656,7 @@ void Recognizer::ForwardLong(const std::vector<Stream*>& streams, std::vector<Re
       { std::lock_guard<std::mutex> lk(vad_mu_); vm = vad_model_; }
       if (lease->vad_model() != vm) lease->set_vad_model(vm);
       lease->vad_segment_device(ptrs.data(), ns.data(), B, &cfg, seg.data(), cap, nseg.data());
-      // speaker labels: on the rows that launch staged, under the same lease (the batches below stage their own)
-      std::shared_ptr<const SpkModel> sm; pf_spk_config scfg;
-      { std::lock_guard<std::mutex> lk(spk_mu_); sm = spk_model_; scfg = spk_cfg_; }
-      for (Stream* s : streams) { s->SpkWindows.clear(); s->SegSpeakers.clear(); s->SpkCentroids.clear(); s->NumSpeakers = 0; s->SpkE = 0; }
-      if (sm) {
-        if (lease->spk_model() != sm) lease->set_spk_model(sm);
-        std::vector<int32_t> win, n_utt((size_t)B, 0), one;
-        for (int i = 0; i < B; ++i) {
-          host_spk_windows(seg.data() + (size_t)i * cap * 2, nseg[i], scfg, one, nullptr);
-          n_utt[(size_t)i] = (int32_t)(one.size() / 3);
-          for (size_t k = 0; k < one.size(); k += 3) win.insert(win.end(), {i, one[k + 1], one[k + 2], one[k]});      // + the segment
-        }
-        const int N = (int)(win.size() / 4), E = sm->embedding;
-        std::vector<int32_t> w3((size_t)N * 3);
-        int64_t cells = 0;
-        for (int k = 0; k < N; ++k) { w3[3 * (size_t)k] = win[4 * (size_t)k]; w3[3 * (size_t)k + 1] = win[4 * (size_t)k + 1]; w3[3 * (size_t)k + 2] = win[4 * (size_t)k + 2]; }
-        for (int i = 0; i < B; ++i) cells += (int64_t)n_utt[(size_t)i] * n_utt[(size_t)i];
-        std::vector<float> emb((size_t)N * E), aff((size_t)cells);
-        if (N > 0) lease->spk_staged(w3.data(), N, n_utt.data(), emb.data(), aff.data());
-        size_t w0 = 0, a0 = 0;
-        for (int i = 0; i < B; ++i) {
-          Stream* s = streams[i];
-          const int n = n_utt[(size_t)i];
-          std::vector<int32_t> labels((size_t)n), wseg((size_t)n);
-          int32_t K = 0;
-          host_spk_cluster(aff.data() + a0, n, scfg, labels.data(), &K);
-          for (int k = 0; k < n; ++k) {
-            wseg[(size_t)k] = win[4 * (w0 + (size_t)k) + 3];
-            s->SpkWindows.push_back({10 * win[4 * (w0 + (size_t)k) + 1], 10 * win[4 * (w0 + (size_t)k) + 2], labels[(size_t)k]});
-          }
-          s->SegSpeakers.assign((size_t)nseg[i], -1);
-          host_spk_segment_labels(seg.data() + (size_t)i * cap * 2, nseg[i], wseg.data(), labels.data(), n, s->SegSpeakers.data());
-          s->NumSpeakers = K; s->SpkE = E;
-          s->SpkCentroids.assign((size_t)K * E, 0.f);
-          host_spk_centroids(emb.data() + w0 * E, labels.data(), n, E, K, s->SpkCentroids.data());
-          w0 += (size_t)n; a0 += (size_t)n * n;
-        }
-      }
+      label_speakers(lease, streams, seg, nseg, cap);           // (the batches below stage their own rows)
     }
     // 2. the plan over the pooled pieces
     std::vector<int32_t> lens;
@@ -784,49 +693,101 @@ void Recognizer::ForwardLong(const std::vector<Stream*>& streams, std::vector<Re
       Forward(rows);
     }
     // 4. one result per stream, pieces in time order
-    std::vector<std::vector<int64_t>> ids(B); std::vector<TsList> ts(B); std::vector<std::vector<float>> sc(B);
-    for (Stream* s : streams) s->Segments.clear();
-    for (size_t j = 0; j < pieces.size(); ++j) {
-      const int i = pieces[j].stream, off_ms = 10 * pieces[j].b;
-      Stream* v = views[j].get();
-      auto shifted = [off_ms](const TsList& in) {               // every int of every entry onto the stream's clock
-        TsList o;
-        o.reserve(in.size());
-        for (const TsVec& t : in) {
-          std::vector<int32_t> x(t.begin(), t.end());
-          for (int32_t& y : x) y += off_ms;
-          o.emplace_back(x.data(), x.data() + x.size());
-        }
-        return o;
-      };
-      const TsList vt = shifted(v->Timestamps);
-      ResultEntity r = decode_multi_one(token_table_, v->Tokens, v->Timestamps);
-      Stream::Segment g;
-      g.begin_ms = off_ms; g.end_ms = 10 * pieces[j].e; g.batch = batch[j]; g.row = row[j];
-      g.tok_begin = (int)ids[i].size(); g.tok_end = g.tok_begin + (int)v->Tokens.size();
-      g.text = r.Text;
-      ResultEntity& o = out[i];
-      if (!streams[i]->Segments.empty()) o.Text += sep;
-      o.Text += r.Text;
-      o.Tokens.insert(o.Tokens.end(), r.Tokens.begin(), r.Tokens.end());
-      for (TsVec& t : shifted(r.Timestamps)) o.Timestamps.push_back(std::move(t));
-      ids[i].insert(ids[i].end(), v->Tokens.begin(), v->Tokens.end());
-      ts[i].insert(ts[i].end(), vt.begin(), vt.end());
-      sc[i].insert(sc[i].end(), v->Scores.begin(), v->Scores.end());
-      streams[i]->Segments.push_back(std::move(g));
-      v->dev_audio = nullptr; v->device_form = false;           // (the piece never owned it)
-    }
-    for (int i = 0; i < B; ++i) {
-      Stream* s = streams[i];
-      out[i].TextLen = utf16_length(out[i].Text);
-      s->Tokens.swap(ids[i]); s->Timestamps.swap(ts[i]); s->Scores.swap(sc[i]);
-      s->AltIds.clear(); s->AltVal.clear(); s->AltK = 0; s->Alternatives.clear();
-      s->AlignTs.clear(); s->AlignTok.clear(); s->AlignN = -1;
-      s->RemoveChunk();                                          // as Forward: a stream that produced a result gives up its audio
-    }
+    stitch_pieces(streams, pieces, views, batch, row, sep, out);
   } catch (const Error& ex) {
     if (ex.code == PF_ERR_RECOGNITION) throw;
     throw Error(PF_ERR_RECOGNITION, std::string("Offline recognition failed: ") + ex.what());           // :194-197
+  }
+}
+
+// ForwardLong's speaker labels: the window plan over the segments, one spk_staged over the rows vad_segment_device staged
+// (under the same lease), then per stream the clustering, the segment labels and the centroids
+void Recognizer::label_speakers(Lease& lease, const std::vector<Stream*>& streams, const std::vector<int32_t>& seg,
+                                const std::vector<int32_t>& nseg, int cap) {
+  const int B = (int)streams.size();
+  std::shared_ptr<const SpkModel> sm; pf_spk_config scfg;
+  { std::lock_guard<std::mutex> lk(spk_mu_); sm = spk_model_; scfg = spk_cfg_; }
+  for (Stream* s : streams) { s->SpkWindows.clear(); s->SegSpeakers.clear(); s->SpkCentroids.clear(); s->NumSpeakers = 0; s->SpkE = 0; }
+  if (sm) {
+    if (lease->spk_model() != sm) lease->set_spk_model(sm);
+    std::vector<int32_t> win, n_utt((size_t)B, 0), one;
+    for (int i = 0; i < B; ++i) {
+      host_spk_windows(seg.data() + (size_t)i * cap * 2, nseg[i], scfg, one, nullptr);
+      n_utt[(size_t)i] = (int32_t)(one.size() / 3);
+      for (size_t k = 0; k < one.size(); k += 3) win.insert(win.end(), {i, one[k + 1], one[k + 2], one[k]});      // + the segment
+    }
+    const int N = (int)(win.size() / 4), E = sm->embedding;
+    std::vector<int32_t> w3((size_t)N * 3);
+    int64_t cells = 0;
+    for (int k = 0; k < N; ++k) { w3[3 * (size_t)k] = win[4 * (size_t)k]; w3[3 * (size_t)k + 1] = win[4 * (size_t)k + 1]; w3[3 * (size_t)k + 2] = win[4 * (size_t)k + 2]; }
+    for (int i = 0; i < B; ++i) cells += (int64_t)n_utt[(size_t)i] * n_utt[(size_t)i];
+    std::vector<float> emb((size_t)N * E), aff((size_t)cells);
+    if (N > 0) lease->spk_staged(w3.data(), N, n_utt.data(), emb.data(), aff.data());
+    size_t w0 = 0, a0 = 0;
+    for (int i = 0; i < B; ++i) {
+      Stream* s = streams[i];
+      const int n = n_utt[(size_t)i];
+      std::vector<int32_t> labels((size_t)n), wseg((size_t)n);
+      int32_t K = 0;
+      host_spk_cluster(aff.data() + a0, n, scfg, labels.data(), &K);
+      for (int k = 0; k < n; ++k) {
+        wseg[(size_t)k] = win[4 * (w0 + (size_t)k) + 3];
+        s->SpkWindows.push_back({10 * win[4 * (w0 + (size_t)k) + 1], 10 * win[4 * (w0 + (size_t)k) + 2], labels[(size_t)k]});
+      }
+      s->SegSpeakers.assign((size_t)nseg[i], -1);
+      host_spk_segment_labels(seg.data() + (size_t)i * cap * 2, nseg[i], wseg.data(), labels.data(), n, s->SegSpeakers.data());
+      s->NumSpeakers = K; s->SpkE = E;
+      s->SpkCentroids.assign((size_t)K * E, 0.f);
+      host_spk_centroids(emb.data() + w0 * E, labels.data(), n, E, K, s->SpkCentroids.data());
+      w0 += (size_t)n; a0 += (size_t)n * n;
+    }
+  }
+}
+
+// ForwardLong's step 4: the pieces' results (views, in time order) into one result per stream
+void Recognizer::stitch_pieces(const std::vector<Stream*>& streams, const std::vector<Piece>& pieces,
+                               const std::vector<std::unique_ptr<Stream>>& views, const std::vector<int32_t>& batch,
+                               const std::vector<int32_t>& row, const std::string& sep, std::vector<ResultEntity>& out) {
+  const int B = (int)streams.size();
+  std::vector<std::vector<int64_t>> ids(B); std::vector<TsList> ts(B); std::vector<std::vector<float>> sc(B);
+  for (Stream* s : streams) s->Segments.clear();
+  for (size_t j = 0; j < pieces.size(); ++j) {
+    const int i = pieces[j].stream, off_ms = 10 * pieces[j].b;
+    Stream* v = views[j].get();
+    auto shifted = [off_ms](const TsList& in) {               // every int of every entry onto the stream's clock
+      TsList o;
+      o.reserve(in.size());
+      for (const TsVec& t : in) {
+        std::vector<int32_t> x(t.begin(), t.end());
+        for (int32_t& y : x) y += off_ms;
+        o.emplace_back(x.data(), x.data() + x.size());
+      }
+      return o;
+    };
+    const TsList vt = shifted(v->Timestamps);
+    ResultEntity r = decode_multi_one(token_table_, v->Tokens, v->Timestamps);
+    Stream::Segment g;
+    g.begin_ms = off_ms; g.end_ms = 10 * pieces[j].e; g.batch = batch[j]; g.row = row[j];
+    g.tok_begin = (int)ids[i].size(); g.tok_end = g.tok_begin + (int)v->Tokens.size();
+    g.text = r.Text;
+    ResultEntity& o = out[i];
+    if (!streams[i]->Segments.empty()) o.Text += sep;
+    o.Text += r.Text;
+    o.Tokens.insert(o.Tokens.end(), r.Tokens.begin(), r.Tokens.end());
+    for (TsVec& t : shifted(r.Timestamps)) o.Timestamps.push_back(std::move(t));
+    ids[i].insert(ids[i].end(), v->Tokens.begin(), v->Tokens.end());
+    ts[i].insert(ts[i].end(), vt.begin(), vt.end());
+    sc[i].insert(sc[i].end(), v->Scores.begin(), v->Scores.end());
+    streams[i]->Segments.push_back(std::move(g));
+    v->dev_audio = nullptr; v->device_form = false;           // (the piece never owned it)
+  }
+  for (int i = 0; i < B; ++i) {
+    Stream* s = streams[i];
+    out[i].TextLen = utf16_length(out[i].Text);
+    s->Tokens.swap(ids[i]); s->Timestamps.swap(ts[i]); s->Scores.swap(sc[i]);
+    s->AltIds.clear(); s->AltVal.clear(); s->AltK = 0; s->Alternatives.clear();
+    s->AlignTs.clear(); s->AlignTok.clear(); s->AlignN = -1;
+    s->RemoveChunk();                                          // as Forward: a stream that produced a result gives up its audio
   }
 }
 
@@ -1189,375 +1150,205 @@ void Recognizer::note_step(std::chrono::steady_clock::time_point t0) {
   step_ema_us_ = step_ema_us_ <= 0.0 ? us : 0.75 * step_ema_us_ + 0.25 * us;
 }
 
+// The hot words of a batch: the union of its streams' Hotwords (OfflineProjOfSeacoParaformer.cs:52-60, SelectMany), else the
+// constructor's list (hot-word file + [sos_eos_id] terminator, OfflineRecognizer.cs:72-90).  A null list throws inside the
+// reference's ModelProj: the SeACo decoder and the CTC beam mirror that (null_throws), the n-best search never has and reads
+// such a stream as one without hot words.
+std::vector<std::vector<int32_t>> Recognizer::batch_hotwords(const std::vector<Stream*>& streams, bool null_throws) const {
+  std::vector<std::vector<int32_t>> hw;
+  for (Stream* s : streams) {
+    if (null_throws && s->hotwords_null) throw Error(PF_ERR_RECOGNITION, "Value cannot be null (Hotwords)");
+    for (auto& w : s->Hotwords) hw.push_back(w);
+  }
+  if (hw.empty()) hw = hotwords_;
+  return hw;
+}
+
+// the form the two searches take them in: ids end to end with a length each, without the lone [sos_eos_id] terminator entry
+// GetHotwords appends
+struct FlatHotwords { std::vector<int32_t> ids, lens; };
+static FlatHotwords flat_hotwords(const std::vector<std::vector<int32_t>>& hw) {
+  FlatHotwords f;
+  for (auto& w : hw) {
+    if (w.size() == 1 && w[0] == 1) continue;
+    f.ids.insert(f.ids.end(), w.begin(), w.end());
+    f.lens.push_back((int32_t)w.size());
+  }
+  return f;
+}
+
+// SenseVoice split-embed variant: prepend [emb(lang), emb(1), emb(2), emb(textnorm)] to Speech IN PLACE
+// (OfflineProjOfSenseVoiceSmall.cs:78-106, quirk Q8); effective ids per quirk Q7
+void Recognizer::prepend_sv_prompt(Stream& s) const {
+  const int W = sv_width_;
+  const int order[4] = {sv_use_itn_ ? 14 : 15, 1, 2, 15};        // languageId, 1, 2, textnormId
+  std::vector<float> sp((size_t)4 * W + s.Speech.size());
+  for (int r = 0; r < 4; ++r) std::memcpy(&sp[(size_t)r * W], &sv_embed_[(size_t)order[r] * W], (size_t)W * 4);
+  std::memcpy(sp.data() + (size_t)4 * W, s.Speech.data(), s.Speech.size() * 4);
+  s.Speech.swap(sp);
+  s.SpeechLength = (int)s.Speech.size();
+}
+
+Recognizer::LmSetting Recognizer::lm_snapshot(bool search) {
+  std::lock_guard<std::mutex> lk(lm_mu_);
+  if (search) return {search_lm_, search_alpha_, search_beta_, search_flags_};
+  return {lm_, lm_alpha_, lm_beta_, lm_flags_};
+}
+
+bool Recognizer::prepare_streams(const std::vector<Stream*>& streams) {
+  for (Stream* s : streams) adopt(s);
+  // the fast form needs every stream in the device form; otherwise every stream is brought to the host form first
+  bool all_dev = device_streams_;
+  for (Stream* s : streams) all_dev = all_dev && s->device_form;
+  const bool sv = engine_kind_ == "sensevoicesmall";
+  if (all_dev && sv && !sv_device_prompt_) all_dev = false;
+  if (!all_dev) {
+    for (Stream* s : streams) s->materialize();
+    if (sv) {
+      PF_CHECK(sv_embed_.size() >= (size_t)16 * sv_width_, PF_ERR_FORMAT, "sensevoice: embed table missing from the container");
+      for (Stream* s : streams)
+        if (s->has_speech) prepend_sv_prompt(*s);
+    }
+  }
+  for (Stream* s : streams)
+    // PadSequence dereferences a null Speech -> NullReferenceException inside Forward's try
+    if (!s->has_speech || s->SpeechLength == 0) throw Error(PF_ERR_RECOGNITION, "Object reference not set (Speech is null)");
+  return all_dev;
+}
+
+// what this call runs with, on the engine it leased (which may have joined the pool after the Set* calls)
+ResultPlan Recognizer::configure_engine(Engine* e, const std::vector<Stream*>& streams) {
+  const ModelCfg& mc = e->model();
+  const int B = (int)streams.size();
+  if (e->decode_flags() != decode_flags_) e->set_decode(decode_flags_);
+  if (e->topk() != topk_k_) e->set_topk(topk_k_);
+  if (e->ctc_beam_w() != beam_w_ || e->ctc_beam_n() != beam_n_) e->set_ctc_beam(beam_w_, std::min<int>(beam_n_, beam_w_));
+  ResultPlan p;
+  p.dflags = e->decode_flags();
+  p.sensevoice = engine_kind_ == "sensevoicesmall";
+  p.nbest = nbest_n_;
+  p.ms_frame = conf_.lfr_n * 10;
+  const bool beam = p.sensevoice && !mc.seaco && (p.dflags & PF_DECODE_CTC_BEAM);
+  if (mc.seaco) {
+    // the bias decoder's list, PadList(…, 0, 10) (EmbedSeacoModel.cs)
+    const std::vector<std::vector<int32_t>> hw = batch_hotwords(streams, true);
+    std::vector<int32_t> pad;
+    for (auto& w : hw)
+      for (int j = 0; j < 10; ++j) pad.push_back(j < (int)w.size() ? w[j] : 0);
+    e->set_hotwords(pad.data(), (int)hw.size());
+  }
+  if (p.sensevoice && !mc.seaco) {
+    // hot words and the language model inside the beam search (SetHotwordBoost / SetLm beside SetCtcBeam): the engine keeps
+    // its automaton while the set is the same and uploads the model on first use
+    const float boost = hot_boost_;
+    if (boost > 0.f && beam) {
+      const FlatHotwords f = flat_hotwords(batch_hotwords(streams, true));
+      e->set_ctc_hotwords(f.ids.data(), f.lens.data(), (int)f.lens.size(), boost);
+    } else if (e->ctc_hotwords_on()) {
+      e->set_ctc_hotwords(nullptr, nullptr, 0, 0.f);
+    }
+    const LmSetting m = lm_snapshot(false);
+    if (m.lm && beam) e->set_ctc_lm(m.lm, m.alpha, m.beta, m.flags);
+    else if (e->ctc_lm_on()) e->set_ctc_lm(nullptr, 0.f, 0.f, 0);
+  }
+  // the n-best search (SetNBestSearch beside SetNBest(N > 1)): width, hot words and model of THIS call on this engine
+  p.search_on = plain_paraformer_ && search_w_ > 0 && p.nbest > 1 && (p.dflags & PF_DECODE_TOPK);
+  if (p.search_on) {
+    e->set_nbest_search(std::max<int>(search_w_, p.nbest), p.nbest);
+    const float boost = search_boost_;
+    if (boost > 0.f) {
+      const FlatHotwords f = flat_hotwords(batch_hotwords(streams, false));
+      e->set_nbest_hotwords(f.ids.data(), f.lens.data(), (int)f.lens.size(), boost);
+    } else {
+      e->set_nbest_hotwords(nullptr, nullptr, 0, 0.f);
+    }
+    const LmSetting m = lm_snapshot(true);
+    e->set_nbest_lm(m.lm, m.alpha, m.beta, m.flags);
+  } else if (e->nbest_search_w() != 0) {
+    e->set_nbest_search(0, 0);
+  }
+  p.hot_on = beam && e->ctc_hotwords_on();
+  p.lm_on = beam && e->ctc_lm_on();
+  e->drop_thread_result();              // this call's result is read back under the same lease, not from a slot
+  if (p.dflags & PF_DECODE_ALIGN) {
+    // the streams' targets of this batch (SetAlign): a stream without one gets len = -1
+    size_t cap = 1;
+    for (Stream* s : streams) { p.any_target = p.any_target || s->has_align; if (s->has_align) cap = std::max(cap, s->AlignIds.size()); }
+    std::vector<int64_t> t_ids((size_t)B * cap, 0);
+    std::vector<int32_t> t_len((size_t)B, -1);
+    for (int b = 0; b < B && p.any_target; ++b)
+      if (streams[b]->has_align) {
+        t_len[b] = (int32_t)streams[b]->AlignIds.size();
+        std::copy(streams[b]->AlignIds.begin(), streams[b]->AlignIds.end(), t_ids.begin() + (size_t)b * cap);
+      }
+    if (p.any_target) e->set_align_targets(t_ids.data(), t_len.data(), B, (int)cap);
+    else e->set_align_targets(nullptr, nullptr, 0, 0);
+  }
+  const int extras = PF_DECODE_TOPK | PF_DECODE_CTC_BEAM | PF_DECODE_ALIGN;      // none changes what Scores holds
+  p.want_scores = (p.dflags & ~extras) == PF_DECODE_SCORES && (!(p.dflags & extras) || (user_flags_ & PF_DECODE_SCORES));
+  return p;
+}
+
+// the forward, enqueued; returns when the step began (the device form only: what note_step times)
+std::chrono::steady_clock::time_point Recognizer::run(Engine* e, const std::vector<Stream*>& streams, bool all_dev, FwdClock& fc) {
+  const int B = (int)streams.size();
+  if (!all_dev) {
+    std::vector<const float*> ptrs;
+    std::vector<int32_t> lens;
+    for (Stream* s : streams) { ptrs.push_back(s->Speech.data()); lens.push_back((int32_t)s->Speech.size()); }
+    e->model_proj_host(ptrs.data(), lens.data(), B, false);
+    return {};
+  }
+  // the batched front-end over the samples where they are (fbank -> LFR + CMVN + PadSequence [+ the SenseVoice query
+  // rows]) and the model, one stream of launches: WavFrontend.cs:31-111 + Utils/PadHelper.cs:25 + ModelProj
+  std::vector<const float*> ptrs;
+  std::vector<int64_t> ns;
+  PF_HIP(hipSetDevice(device_));
+  for (Stream* s : streams) {
+    ptrs.push_back(s->dev_audio); ns.push_back(s->dev_n);
+    // staged uploads may still be landing: the engine's stream waits for them, the host does not
+    if (s->dev_ev_pending) PF_HIP(hipStreamWaitEvent(e->stream(), s->dev_ev, 0));
+  }
+  fc.lap(1);
+  stagger_start();
+  const auto t_step = std::chrono::steady_clock::now();
+  e->stage_device_audio(ptrs.data(), ns.data(), B);
+  fc.lap(2);
+  e->run_staged(false);
+  fc.lap(3);
+  return t_step;
+}
+
+// the one wait for the device, then the one copy of what the forward left on the host; the lease ends here
+HostBatchOut Recognizer::read(Lease& lease, const std::vector<Stream*>& streams, std::chrono::steady_clock::time_point t_step, FwdClock& fc) {
+  lease->sync();
+  for (Stream* s : streams)
+    if (s->dev_raw) s->wait_device_audio();   // AddPcm streams: the conversion has run, the raw bytes go back to the cache
+  if (t_step != std::chrono::steady_clock::time_point{}) note_step(t_step);
+  fc.lap(4);
+  HostBatchOut r = lease->result_copy();      // a copy: a caller of pf_recognizer_engine may still pf_fetch this forward
+  fc.lap(5);
+  lease.release();                            // the device work of this call is over: the text stage needs no engine
+  return r;
+}
+
 void Recognizer::Forward(const std::vector<Stream*>& streams) {
   if (streams.empty()) return;                                      // :120-123
   try {
     if (disposed_) throw Error(PF_ERR_DISPOSED, "OfflineRecognizer");
-    for (Stream* s : streams) adopt(s);
-    // the fast form needs every stream in the device form; otherwise every stream is brought to the host form first
-    bool all_dev = device_streams_;
-    for (Stream* s : streams) all_dev = all_dev && s->device_form;
-    const bool sv = engine_kind_ == "sensevoicesmall";
-    if (all_dev && sv && !sv_device_prompt_) all_dev = false;
-    if (!all_dev)
-      for (Stream* s : streams) s->materialize();
+    const bool all_dev = prepare_streams(streams);
     FwdClock fc;
-    std::chrono::steady_clock::time_point t_step;
-    bool timed_step = false;
     Lease lease = acquire();
-    Engine* e = lease.get();
-    const ModelCfg& mc = e->model();
-    const int W = mc.feat_dim;
-    const int B = (int)streams.size();
-    if (e->decode_flags() != decode_flags_) e->set_decode(decode_flags_);
-    if (e->topk() != topk_k_) e->set_topk(topk_k_);
-    if (e->ctc_beam_w() != beam_w_ || e->ctc_beam_n() != beam_n_) e->set_ctc_beam(beam_w_, std::min<int>(beam_n_, beam_w_));
-    const int dflags = e->decode_flags();
     fc.lap(0);
-    if (!all_dev && sv) {
-      // SenseVoice split-embed variant: prepend [emb(lang), emb(1), emb(2), emb(textnorm)] to Speech
-      // IN PLACE (OfflineProjOfSenseVoiceSmall.cs:78-106, quirk Q8); effective ids per quirk Q7.
-      const std::vector<float>& emb = e->embed_table();
-      PF_CHECK(emb.size() >= (size_t)16 * W, PF_ERR_FORMAT, "sensevoice: embed table missing from the container");
-      const int languageId = mc.use_itn ? 14 : 15, textnormId = 15;
-      const int order[4] = {languageId, 1, 2, textnormId};
-      for (Stream* s : streams) {
-        if (!s->has_speech) continue;
-        std::vector<float> sp((size_t)4 * W + s->Speech.size());
-        for (int r = 0; r < 4; ++r) std::memcpy(&sp[(size_t)r * W], &emb[(size_t)order[r] * W], (size_t)W * 4);
-        std::memcpy(sp.data() + (size_t)4 * W, s->Speech.data(), s->Speech.size() * 4);
-        s->Speech.swap(sp);
-        s->SpeechLength = (int)s->Speech.size();
-      }
-    }
-    for (Stream* s : streams)
-      // PadSequence dereferences a null Speech -> NullReferenceException inside Forward's try
-      if (!s->has_speech || s->SpeechLength == 0) throw Error(PF_ERR_RECOGNITION, "Object reference not set (Speech is null)");
-    if (mc.seaco) {
-      // OfflineProjOfSeacoParaformer.cs:52-60: hotwords = SelectMany over the streams' Hotwords (a null list
-      // throws inside ModelProj -> "Offline recognition failed"); empty -> the constructor's default list
-      // (hotword file + [sos_eos_id] terminator, OfflineRecognizer.cs:72-90).  PadList(…, 0, 10) (EmbedSeacoModel.cs).
-      std::vector<std::vector<int32_t>> hw;
-      for (Stream* s : streams) {
-        if (s->hotwords_null) throw Error(PF_ERR_RECOGNITION, "Value cannot be null (Hotwords)");
-        for (auto& w : s->Hotwords) hw.push_back(w);
-      }
-      if (hw.empty()) hw = hotwords_;
-      std::vector<int32_t> pad;
-      for (auto& w : hw)
-        for (int j = 0; j < 10; ++j) pad.push_back(j < (int)w.size() ? w[j] : 0);
-      e->set_hotwords(pad.data(), (int)hw.size());
-    }
-    if (sv && !mc.seaco) {
-      // hot words inside the beam search (SetHotwordBoost beside SetCtcBeam): the SeACo rule above for where they come from,
-      // without the [sos_eos_id] terminator entry GetHotwords appends; the engine keeps its automaton while the set is the same
-      const float boost = hot_boost_;
-      if (boost > 0.f && (dflags & PF_DECODE_CTC_BEAM)) {
-        std::vector<std::vector<int32_t>> hw;
-        for (Stream* s : streams) {
-          if (s->hotwords_null) throw Error(PF_ERR_RECOGNITION, "Value cannot be null (Hotwords)");
-          for (auto& w : s->Hotwords) hw.push_back(w);
-        }
-        if (hw.empty()) hw = hotwords_;
-        std::vector<int32_t> flat, lens;
-        for (auto& w : hw) {
-          if (w.size() == 1 && w[0] == 1) continue;
-          flat.insert(flat.end(), w.begin(), w.end());
-          lens.push_back((int32_t)w.size());
-        }
-        e->set_ctc_hotwords(flat.data(), lens.data(), (int)lens.size(), boost);
-      } else if (e->ctc_hotwords_on()) {
-        e->set_ctc_hotwords(nullptr, nullptr, 0, 0.f);
-      }
-    }
-    if (sv && !mc.seaco) {
-      // the language model inside the beam search (SetLm beside SetCtcBeam): this engine uploads the image on first use
-      std::shared_ptr<const LmImage> lm;
-      float la = 0.f, lb = 0.f;
-      int lf = 0;
-      { std::lock_guard<std::mutex> lk(lm_mu_); lm = lm_; la = lm_alpha_; lb = lm_beta_; lf = lm_flags_; }
-      if (lm && (dflags & PF_DECODE_CTC_BEAM)) e->set_ctc_lm(lm, la, lb, lf);
-      else if (e->ctc_lm_on()) e->set_ctc_lm(nullptr, 0.f, 0.f, 0);
-    }
-    // the n-best search (SetNBestSearch beside SetNBest(N > 1)): width, hot words and model of THIS call on this engine; the
-    // engine keeps its automaton while the set is the same and uploads the model on first use
-    const bool search_on = plain_paraformer_ && search_w_ > 0 && nbest_n_ > 1 && (dflags & PF_DECODE_TOPK);
-    if (search_on) {
-      const int n = nbest_n_;
-      e->set_nbest_search(std::max<int>(search_w_, n), n);
-      const float boost = search_boost_;
-      if (boost > 0.f) {
-        std::vector<std::vector<int32_t>> hw;
-        for (Stream* s : streams)
-          for (auto& w : s->Hotwords) hw.push_back(w);
-        if (hw.empty()) hw = hotwords_;
-        std::vector<int32_t> flat, lens;
-        for (auto& w : hw) {
-          if (w.size() == 1 && w[0] == 1) continue;   // the [sos_eos_id] terminator entry GetHotwords appends
-          flat.insert(flat.end(), w.begin(), w.end());
-          lens.push_back((int32_t)w.size());
-        }
-        e->set_nbest_hotwords(flat.data(), lens.data(), (int)lens.size(), boost);
-      } else {
-        e->set_nbest_hotwords(nullptr, nullptr, 0, 0.f);
-      }
-      std::shared_ptr<const LmImage> lm;
-      float la = 0.f, lb = 0.f;
-      int lf = 0;
-      { std::lock_guard<std::mutex> lk(lm_mu_); lm = search_lm_; la = search_alpha_; lb = search_beta_; lf = search_flags_; }
-      e->set_nbest_lm(lm, la, lb, lf);
-    } else if (e->nbest_search_w() != 0) {
-      e->set_nbest_search(0, 0);
-    }
-    const bool hot_on = sv && !mc.seaco && (dflags & PF_DECODE_CTC_BEAM) && e->ctc_hotwords_on();
-    const bool lm_on = sv && !mc.seaco && (dflags & PF_DECODE_CTC_BEAM) && e->ctc_lm_on();
-    e->drop_thread_result();              // this call's result is read back under the same lease, not from a slot
-    bool any_target = false;
-    if (dflags & PF_DECODE_ALIGN) {
-      // the streams' targets of this batch (SetAlign): a stream without one gets len = -1
-      size_t cap = 1;
-      for (Stream* s : streams) { any_target = any_target || s->has_align; if (s->has_align) cap = std::max(cap, s->AlignIds.size()); }
-      std::vector<int64_t> t_ids((size_t)B * cap, 0);
-      std::vector<int32_t> t_len((size_t)B, -1);
-      for (int b = 0; b < B && any_target; ++b)
-        if (streams[b]->has_align) {
-          t_len[b] = (int32_t)streams[b]->AlignIds.size();
-          std::copy(streams[b]->AlignIds.begin(), streams[b]->AlignIds.end(), t_ids.begin() + (size_t)b * cap);
-        }
-      if (any_target) e->set_align_targets(t_ids.data(), t_len.data(), B, (int)cap);
-      else e->set_align_targets(nullptr, nullptr, 0, 0);
-    }
-    if (all_dev) {
-      // the batched front-end over the samples where they are (fbank -> LFR + CMVN + PadSequence [+ the SenseVoice query
-      // rows]) and the model, one stream of launches: WavFrontend.cs:31-111 + Utils/PadHelper.cs:25 + ModelProj
-      std::vector<const float*> ptrs;
-      std::vector<int64_t> ns;
-      PF_HIP(hipSetDevice(device_));
-      for (Stream* s : streams) {
-        ptrs.push_back(s->dev_audio); ns.push_back(s->dev_n);
-        // staged uploads may still be landing: the engine's stream waits for them, the host does not
-        if (s->dev_ev_pending) PF_HIP(hipStreamWaitEvent(e->stream(), s->dev_ev, 0));
-      }
-      fc.lap(1);
-      stagger_start();
-      t_step = std::chrono::steady_clock::now();
-      timed_step = true;
-      e->stage_device_audio(ptrs.data(), ns.data(), B);
-      fc.lap(2);
-      e->run_staged(false);
-      fc.lap(3);
-    } else {
-      std::vector<const float*> ptrs;
-      std::vector<int32_t> lens;
-      for (Stream* s : streams) { ptrs.push_back(s->Speech.data()); lens.push_back((int32_t)s->Speech.size()); }
-      e->model_proj_host(ptrs.data(), lens.data(), B, false);
-    }
-    pf_batch_out out;
-    std::memset(&out, 0, sizeof(out));
-    out.struct_size = sizeof(out);
-    e->fetch(&out);                       // sync; learn L
-    for (Stream* s : streams)
-      if (s->dev_raw) s->wait_device_audio();   // AddPcm streams: the conversion has run, the raw bytes go back to the cache
-    if (timed_step) note_step(t_step);
-    fc.lap(4);
-    const int L = out.L;
-    std::vector<int64_t> ids((size_t)B * std::max(L, 1));
-    out.token_ids = ids.data();
-    out.l_cap = std::max(L, 1);
-    const int P = out.cif_peak_len;                                    // 3*Tmax for timestamp models (:172-183)
-    std::vector<float> peak((size_t)B * std::max(P, 1));
-    if (P > 0) { out.cif_peak = peak.data(); out.cif_peak_cap = (int64_t)peak.size(); }
-    std::vector<int32_t> tnum;                                         // the n-best list varies only below an utterance's own count
-    if (dflags & PF_DECODE_TOPK) { tnum.resize(B); out.token_num = tnum.data(); }
-    e->fetch(&out);
-    // decoding extras (SetDecode): host copies of what the forward left beside the ids
-    std::vector<float> scores;
-    std::vector<int64_t> c_ids; std::vector<int32_t> c_first, c_last, c_n; std::vector<float> c_score;
-    int c_cap = 0;
-    if (dflags & PF_DECODE_CTC) {
-      int32_t n_max = 0;
-      c_n.resize(B);
-      e->fetch_ctc(nullptr, nullptr, nullptr, nullptr, 0, c_n.data(), &n_max);
-      c_cap = std::max(n_max, 1);
-      c_ids.resize((size_t)B * c_cap); c_first.resize(c_ids.size()); c_last.resize(c_ids.size()); c_score.resize(c_ids.size());
-      e->fetch_ctc(c_ids.data(), c_first.data(), c_last.data(), c_score.data(), c_cap, nullptr, nullptr);
-    }
-    if ((dflags & PF_DECODE_SCORES) && (!(dflags & PF_DECODE_CTC) || (dflags & PF_DECODE_TOPK))) {
-      scores.resize((size_t)B * std::max(L, 1));
-      e->fetch_scores(scores.data(), (int64_t)scores.size(), nullptr);
-    }
-    std::vector<int64_t> k_ids; std::vector<float> k_val; std::vector<int32_t> k_n;
-    int K = 0;
-    if (dflags & PF_DECODE_TOPK) {
-      int32_t k = 0;
-      e->fetch_topk(nullptr, nullptr, nullptr, 0, nullptr, &k);
-      K = k;
-      const size_t rows = (size_t)B * std::max(L, 1);
-      k_ids.resize(rows * K); k_val.resize(rows * K); k_n.resize(rows);
-      e->fetch_topk(k_ids.data(), k_val.data(), k_n.data(), (int64_t)rows, nullptr, nullptr);
-    }
-    // the beam search's hypotheses (SetCtcBeam): ids [B, Nb, b_cap], lengths, float64 totals
-    std::vector<int64_t> b_ids; std::vector<int32_t> b_len, b_nhyp; std::vector<double> b_score;
-    std::vector<int32_t> b_hot; std::vector<double> b_llsum;      // with hot words: matched tokens, the unbiased totals
-    std::vector<double> b_lm;                                     // with a language model: lm_sum (and the unfused totals above)
-    int Nb = 0, b_cap = 0;
-    if (dflags & PF_DECODE_CTC_BEAM) {
-      int32_t len_max = 0, nb = 0;
-      b_nhyp.resize(B);
-      e->fetch_ctc_beam(nullptr, nullptr, nullptr, 0, b_nhyp.data(), &len_max, &nb);
-      Nb = nb;
-      b_cap = std::max(len_max, 1);
-      b_ids.resize((size_t)B * Nb * b_cap); b_len.resize((size_t)B * Nb); b_score.resize((size_t)B * Nb);
-      e->fetch_ctc_beam(b_ids.data(), b_len.data(), b_score.data(), b_cap, nullptr, nullptr, nullptr);
-      if (hot_on) {
-        b_hot.resize((size_t)B * Nb); b_llsum.resize((size_t)B * Nb);
-        e->fetch_ctc_beam_hot(b_hot.data(), b_llsum.data());
-      }
-      if (lm_on) {
-        b_lm.resize((size_t)B * Nb); b_llsum.resize((size_t)B * Nb);
-        e->fetch_ctc_beam_lm(b_lm.data(), b_llsum.data());
-      }
-    }
-    // the n-best search's hypotheses: ranks [B, Ns, L], float64 score / loglik_sum / lm_sum, matched
-    std::vector<int32_t> s_ranks, s_hot, s_nhyp; std::vector<double> s_score, s_ll, s_lm;
-    int Ns = 0;
-    if (search_on && L > 0) {
-      int32_t nn = 0;
-      e->fetch_nbest_search(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &nn);
-      Ns = nn;
-      const size_t cells = (size_t)B * Ns;
-      s_ranks.resize(cells * L); s_hot.resize(cells); s_nhyp.resize(B); s_score.resize(cells); s_ll.resize(cells); s_lm.resize(cells);
-      e->fetch_nbest_search(s_ranks.data(), s_score.data(), s_ll.data(), s_lm.data(), s_hot.data(), s_nhyp.data(), nullptr, nullptr);
-    }
-    // forced alignments (SetAlign): job 0 is the stream's own target when any stream of the batch has one, then the hypotheses
-    std::vector<float> a_path, a_tok; std::vector<double> a_ll; std::vector<int32_t> a_ok, a_len, a_first, a_last;
-    int Ha = 0, a_cap = 1;
-    if (dflags & PF_DECODE_ALIGN) {
-      int32_t hh = 0, len_max = 0;
-      e->fetch_align(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, &hh, &len_max);
-      Ha = hh;
-      a_cap = std::max(len_max, 1);
-      const size_t jobs = (size_t)B * Ha;
-      a_path.resize(jobs); a_ll.resize(jobs); a_ok.resize(jobs); a_len.resize(jobs);
-      a_first.resize(jobs * a_cap); a_last.resize(jobs * a_cap); a_tok.resize(jobs * a_cap);
-      if (Ha > 0)
-        e->fetch_align(a_path.data(), a_ll.data(), a_ok.data(), a_len.data(), a_first.data(), a_last.data(), a_tok.data(), a_cap, nullptr,
-                       nullptr);
-    }
-    const int a_hc = (Ha > 0 && any_target) ? 1 : 0;
-    const int nbest = nbest_n_;
-    const int extras = PF_DECODE_TOPK | PF_DECODE_CTC_BEAM | PF_DECODE_ALIGN;      // none changes what Scores holds
-    const bool want_scores = (dflags & ~extras) == PF_DECODE_SCORES && (!(dflags & extras) || (user_flags_ & PF_DECODE_SCORES));
-    fc.lap(5);
-    lease.release();                      // the device work of this call is over: the text stage below needs no engine
-    const int ms_frame = conf_.lfr_n * 10;          // a frame = lfr_n x 10 ms; the four prompt rows carry no audio
-    for (int b = 0; b < B; ++b) {
+    const ResultPlan plan = configure_engine(lease.get(), streams);
+    const auto t_step = run(lease.get(), streams, all_dev, fc);
+    const HostBatchOut r = read(lease, streams, t_step, fc);
+    for (size_t b = 0; b < streams.size(); ++b) {
       Stream* s = streams[b];
-      s->Tokens.assign(ids.begin() + (size_t)b * out.l_cap, ids.begin() + (size_t)b * out.l_cap + L);   // :187
-      s->Scores.clear();
-      if (want_scores) s->Scores.assign(scores.begin() + (size_t)b * L, scores.begin() + (size_t)b * L + L);
-      s->Timestamps.reserve(s->Timestamps.size() + (size_t)L);
-      if (dflags & PF_DECODE_CTC) {
-        // the collapsed hypothesis instead of the per-frame ids: one [begin, end] pair per token from its first / last frame
-        // (a frame = lfr_n x 10 ms; the four prompt rows carry no audio, so a run inside them gets {0, 0})
-        const size_t o = (size_t)b * c_cap;
-        const int n = c_n[b], ms = conf_.lfr_n * 10, Pr = 4;
-        s->Tokens.assign(c_ids.begin() + o, c_ids.begin() + o + n);
-        s->Scores.assign(c_score.begin() + o, c_score.begin() + o + n);
-        for (int k = 0; k < n; ++k)
-          s->Timestamps.push_back({ms * std::max(c_first[o + k] - Pr, 0), ms * std::max(c_last[o + k] + 1 - Pr, 0)});
-      } else if (P > 0) {
-        // :172-183: the peak row and ALL L arg-max ids go to time_stamp_lfr6_onnx
-        TsList ts = time_stamp_lfr6(peak.data() + (size_t)b * P, P, s->Tokens);
-        for (auto& t2 : ts) s->Timestamps.push_back(t2);
-      } else {
-        for (int l = 0; l < L; ++l) s->Timestamps.push_back({0, 0});                                    // :151,:188
-      }
-      s->AltIds.clear(); s->AltVal.clear(); s->AltK = 0; s->Alternatives.clear();
-      if (K > 0 && L > 0) {
-        const size_t r0 = (size_t)b * L;
-        s->AltK = K;
-        if (dflags & PF_DECODE_CTC) {
-          // per collapsed token: the alternatives of the run's peak frame — the first frame whose log-prob is the token's
-          // score bit for bit
-          const size_t o = (size_t)b * c_cap;
-          for (int k = 0; k < c_n[b]; ++k) {
-            int t = c_first[o + k];
-            for (int u = c_first[o + k]; u <= c_last[o + k]; ++u)
-              if (std::memcmp(&scores[r0 + u], &c_score[o + k], 4) == 0) { t = u; break; }
-            s->AltIds.insert(s->AltIds.end(), k_ids.begin() + (r0 + t) * K, k_ids.begin() + (r0 + t + 1) * K);
-            s->AltVal.insert(s->AltVal.end(), k_val.begin() + (r0 + t) * K, k_val.begin() + (r0 + t + 1) * K);
-          }
-        } else {
-          s->AltIds.assign(k_ids.begin() + r0 * K, k_ids.begin() + (r0 + L) * K);
-          s->AltVal.assign(k_val.begin() + r0 * K, k_val.begin() + (r0 + L) * K);
-        }
-        if (nbest > 1 && !sv && Ns > 0) {
-          // the fused order of the device search; each alternative is decoded like the host enumeration's below
-          const int got = s_nhyp[b];
-          s->Alternatives.resize((size_t)got);
-          for (int i = 0; i < got; ++i) {
-            const size_t x = (size_t)b * Ns + i;
-            Alternative& a = s->Alternatives[(size_t)i];
-            a.score = s_score[x]; a.loglik_sum = s_ll[x]; a.lm_sum = s_lm[x]; a.hot_tokens = s_hot[x];
-            a.ids.resize((size_t)L);
-            for (int l = 0; l < L; ++l) a.ids[(size_t)l] = k_ids[(r0 + l) * K + s_ranks[x * L + l]];
-          }
-        } else if (nbest > 1 && !sv) {
-          std::vector<int32_t> ranks((size_t)nbest * L);
-          std::vector<double> sc((size_t)nbest);
-          const int n_free = std::min(L, std::max(tnum[b], 0));
-          const int got = host_nbest(k_val.data() + r0 * K, k_n.data() + r0, L, K, n_free, nbest, ranks.data(), sc.data());
-          s->Alternatives.resize((size_t)got);
-          for (int i = 0; i < got; ++i) {
-            Alternative& a = s->Alternatives[(size_t)i];
-            a.score = sc[(size_t)i];
-            a.ids.resize((size_t)L);
-            for (int l = 0; l < L; ++l) a.ids[(size_t)l] = k_ids[(r0 + l) * K + ranks[(size_t)i * L + l]];
-          }
-        }
-      }
-      for (int i = 0; i < (Nb > 0 ? b_nhyp[b] : 0); ++i) {
-        const size_t x = (size_t)b * Nb + i;
-        Alternative a;
-        a.score = b_score[x];
-        a.ctc = true;
-        if (!b_hot.empty()) { a.hot_tokens = b_hot[x]; a.loglik_sum = b_llsum[x]; }
-        if (!b_lm.empty()) { a.lm_sum = b_lm[x]; a.loglik_sum = b_llsum[x]; }
-        a.ids.assign(b_ids.begin() + x * b_cap, b_ids.begin() + x * b_cap + b_len[x]);
-        if (Ha >= a_hc + Nb) {
-          const size_t j = (size_t)b * Ha + a_hc + i;
-          a.loglik = a_ll[j];
-          if (a_ok[j] && a_len[j] == b_len[x])
-            for (int k = 0; k < a_len[j]; ++k) {
-              a.ts.push_back(ms_frame * std::max(a_first[j * a_cap + k] - 4, 0));
-              a.ts.push_back(ms_frame * std::max(a_last[j * a_cap + k] + 1 - 4, 0));
-            }
-        }
-        s->Alternatives.push_back(std::move(a));
-      }
-      s->AlignTs.clear(); s->AlignTok.clear(); s->AlignPath = 0.f; s->AlignLoglik = 0.0; s->AlignOk = 0; s->AlignN = -1;
-      if (a_hc && a_len[(size_t)b * Ha] >= 0) {
-        const size_t j = (size_t)b * Ha;
-        s->AlignN = a_len[j]; s->AlignOk = a_ok[j]; s->AlignPath = a_path[j]; s->AlignLoglik = a_ll[j];
-        for (int k = 0; k < a_len[j] && a_ok[j]; ++k) {
-          s->AlignTs.push_back(ms_frame * std::max(a_first[j * a_cap + k] - 4, 0));
-          s->AlignTs.push_back(ms_frame * std::max(a_last[j * a_cap + k] + 1 - 4, 0));
-          s->AlignTok.push_back(a_tok[j * a_cap + k]);
-        }
-      }
-      if (all_dev && sv && s->Tokens.size() <= 2) {
-        // quirk Q8 on the device form: the reference has prepended the query rows to Speech IN PLACE, and a stream whose
-        // chunk RemoveChunk keeps (at most two ids) carries them into its next call: give it the host form with them
-        s->materialize();
-        const std::vector<float>& emb = sv_embed_;
-        const int order[4] = {sv_use_itn_ ? 14 : 15, 1, 2, 15};
-        std::vector<float> sp((size_t)4 * W + s->Speech.size());
-        for (int r = 0; r < 4; ++r) std::memcpy(&sp[(size_t)r * W], &emb[(size_t)order[r] * W], (size_t)W * 4);
-        std::memcpy(sp.data() + (size_t)4 * W, s->Speech.data(), s->Speech.size() * 4);
-        s->Speech.swap(sp);
-        s->SpeechLength = (int)s->Speech.size();
-      }
+      build_stream_result(r, plan, (int)b, *s);
+      // quirk Q8 on the device form: the reference has prepended the query rows to Speech IN PLACE, and a stream whose
+      // chunk RemoveChunk keeps (at most two ids) carries them into its next call: give it the host form with them
+      if (all_dev && plan.sensevoice && s->Tokens.size() <= 2) { s->materialize(); prepend_sv_prompt(*s); }
       s->RemoveChunk();                                                                                  // :189
     }
     fc.lap(6);

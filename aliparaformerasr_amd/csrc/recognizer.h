@@ -23,45 +23,9 @@
 #include "copycrew.h"
 #include "engine.h"
 #include "hostutil.h"
+#include "stream_result.h"
 
 namespace pf {
-
-// One timestamp, the reference's int[]: {begin_ms, end_ms} — or several pairs in a row where DecodeMulti merges word pieces
-// (OfflineRecognizer.cs:350-395).  Up to six ints live inside the object: a std::vector per token cost one heap allocation when
-// Forward pushes it, one when DecodeMulti copies it and a free each — 0.4 ms of host time per 32 x 30 s GetResults (round 6).
-class TsVec {
- public:
-  TsVec() = default;
-  TsVec(std::initializer_list<int32_t> l) { append(l.begin(), l.end()); }
-  TsVec(const int32_t* a, const int32_t* b) { append(a, b); }
-  const int32_t* data() const { return n_ <= kInline ? inl_ : big_.data(); }
-  size_t size() const { return n_; }
-  const int32_t* begin() const { return data(); }
-  const int32_t* end() const { return data() + n_; }
-  int32_t operator[](size_t i) const { return data()[i]; }
-  void append(const int32_t* a, const int32_t* b) {
-    const size_t k = (size_t)(b - a);
-    if (n_ > kInline) big_.insert(big_.end(), a, b);
-    else if (n_ + k <= kInline) std::copy(a, b, inl_ + n_);
-    else { big_.assign(inl_, inl_ + n_); big_.insert(big_.end(), a, b); }
-    n_ += (uint32_t)k;
-  }
-  bool operator==(const TsVec& o) const { return n_ == o.n_ && std::equal(begin(), end(), o.begin()); }
- private:
-  static constexpr uint32_t kInline = 6;
-  uint32_t n_ = 0;
-  int32_t inl_[kInline] = {0, 0, 0, 0, 0, 0};
-  std::vector<int32_t> big_;
-};
-using TsList = std::vector<TsVec>;
-
-// OfflineRecognizerResultEntity (Model/OfflineRecognizerResultEntity.cs:9-29)
-struct ResultEntity {
-  std::string Text;
-  int TextLen = 0;                              // UTF-16 length, as C# string.Length
-  std::vector<std::string> Tokens;
-  TsList Timestamps;
-};
 
 // DecodeMulti for one stream (OfflineRecognizer.cs:304-418)
 ResultEntity decode_multi_one(const std::vector<std::string>& tokens, const std::vector<int64_t>& ids,
@@ -75,33 +39,12 @@ struct TokenTable {
   std::vector<uint8_t> kind;
 };
 ResultEntity decode_multi_one(const TokenTable& table, const std::vector<int64_t>& ids, const TsList& timestamps);
-// One entry of a stream's n-best list (Recognizer::SetNBest): the ids of every position, the float64 sum of their log-probs
-// and what DecodeMulti makes of them
-struct Alternative {
-  std::vector<int64_t> ids;
-  double score = 0;
-  bool ctc = false;            // a labeling of the CTC beam search (SetCtcBeam): its own length, score = log of the summed alignments
-  // with SetAlign beside SetCtcBeam: the labeling's own forced alignment — [begin, end] ms per id (flat, 2 per id; empty without
-  // it or when the alignment is not ok) and the log of the sum over ALL of its alignments (NaN without it)
-  std::vector<int32_t> ts;
-  double loglik = std::nan("");
-  // with SetHotwordBoost beside SetCtcBeam: the hot-word tokens the labeling completed (score = loglik_sum + boost * these) and
-  // the unbiased log of the alignments the search summed (0 / NaN without it)
-  int hot_tokens = 0;
-  double loglik_sum = std::nan("");
-  // with SetLm beside SetCtcBeam: the weighted LM score of the labeling, score = (loglik_sum + boost * hot_tokens) + lm_sum (NaN
-  // without it; loglik_sum is then filled with or without hot words)
-  double lm_sum = std::nan("");
-  ResultEntity res;
-};
-// time_stamp_lfr6_onnx (OfflineRecognizer.cs:200-302); throws PF_ERR_RECOGNITION where the C#
-// would throw inside Forward's try block.
-TsList time_stamp_lfr6(const float* us_cif_peak, int n, const std::vector<int64_t>& tokens);
 // GetHotwords (OfflineRecognizer.cs:72-90) over in-memory lines; appends [sos_eos_id]
 std::vector<std::vector<int32_t>> hotword_ids(const std::vector<std::string>& tokens,
                                               const std::vector<std::string>& lines, int sos_eos_id);
 
 class Recognizer;
+struct FwdClock;               // PF_RECOGNIZER_TIMING's laps (recognizer.cpp)
 
 // Ownership: a stream shares ownership of its recognizer OBJECT (so a stream handle that outlives
 // pf_recognizer_free still reaches valid memory and answers PF_ERR_DISPOSED), the recognizer does not track
@@ -116,7 +59,7 @@ class Recognizer;
 // them.  A second AddSamples before GetResults, a SenseVoice stream that survives GetResults with its prompt rows
 // prepended (quirk Q8), or a front-end configuration the batched kernels do not cover turn the stream into the host form
 // (Speech = the feature floats, exactly as before): materialize().
-class Stream {
+class Stream : public StreamResult {        // (the fields a GetResults writes: stream_result.h)
  public:
   explicit Stream(std::shared_ptr<Recognizer> r);
   // The reference's PUBLIC constructor, new OfflineStream(mvnFilePath, confEntity) (OfflineStream.cs:20-28): a stream that
@@ -148,21 +91,8 @@ class Stream {
   void drop_device_audio();
   bool hotwords_null = false;
   std::vector<std::vector<int32_t>> Hotwords;
-  std::vector<int64_t> Tokens{0, 0};                          // OfflineStream.cs:26
-  TsList Timestamps;
-  std::vector<float> Scores;                                  // of the last GetResults (Recognizer::SetDecode); empty without a flag
-  // of the last GetResults (Recognizer::SetNBest); empty without it.  TokenAlternatives: AltK (id, log-prob) pairs per entry
-  // of Tokens, [n_tokens, AltK], slots past a position's count -1 / -inf
-  std::vector<int64_t> AltIds;
-  std::vector<float> AltVal;
-  int AltK = 0;
-  std::vector<Alternative> Alternatives;
-  // CTC forced alignment (Recognizer::SetAlign).  AlignIds: the stream's target (token ids), kept until cleared.  Of the last
-  // GetResults: [begin, end] ms per target id (flat), the token scores, the Viterbi score, the log-likelihood, ok; AlignN = -1
-  // when that GetResults aligned nothing for this stream
+  // CTC forced alignment (Recognizer::SetAlign): the stream's target (token ids), kept until cleared
   std::vector<int64_t> AlignIds; bool has_align = false;
-  std::vector<int32_t> AlignTs; std::vector<float> AlignTok;
-  float AlignPath = 0.f; double AlignLoglik = 0.0; int AlignOk = 0, AlignN = -1;
   // long-audio recognition (Recognizer::SetVad): the pieces the stream was cut into by the last GetResults, in time order —
   // [begin_ms, end_ms) on the stream's clock, where the piece ran (batch, row of the plan), its share [tok_begin, tok_end) of
   // Tokens / Scores / Timestamps, and its own text.  Empty without SetVad.
@@ -287,7 +217,22 @@ class Recognizer : public std::enable_shared_from_this<Recognizer> {
 
  private:
   void Forward(const std::vector<Stream*>& streams);          // :118-198
+  // Forward's stages, in the order they run; behind them build_stream_result (stream_result.h) per stream
+  bool prepare_streams(const std::vector<Stream*>& streams);                                  // -> every stream is in the device form
+  ResultPlan configure_engine(Engine* e, const std::vector<Stream*>& streams);
+  std::chrono::steady_clock::time_point run(Engine* e, const std::vector<Stream*>& streams, bool all_dev, FwdClock& fc);
+  HostBatchOut read(Lease& lease, const std::vector<Stream*>& streams, std::chrono::steady_clock::time_point t_step, FwdClock& fc);
+  std::vector<std::vector<int32_t>> batch_hotwords(const std::vector<Stream*>& streams, bool null_throws) const;
+  void prepend_sv_prompt(Stream& s) const;
+  struct LmSetting { std::shared_ptr<const LmImage> lm; float alpha = 0.f, beta = 0.f; int flags = 0; };
+  LmSetting lm_snapshot(bool search);                         // SetLm's (beam search) or SetNBestLm's (n-best search), under lm_mu_
   void ForwardLong(const std::vector<Stream*>& streams, std::vector<ResultEntity>& out);   // GetResults with SetVad
+  struct Piece { int stream, b, e; };                         // a speech piece of ForwardLong: frames [b, e) of streams[stream]
+  void label_speakers(Lease& lease, const std::vector<Stream*>& streams, const std::vector<int32_t>& seg, const std::vector<int32_t>& nseg,
+                      int cap);
+  void stitch_pieces(const std::vector<Stream*>& streams, const std::vector<Piece>& pieces, const std::vector<std::unique_ptr<Stream>>& views,
+                     const std::vector<int32_t>& batch, const std::vector<int32_t>& row, const std::string& sep,
+                     std::vector<ResultEntity>& out);
   void Punctuate(const std::vector<Stream*>& streams, const std::vector<ResultEntity>& out);
   std::mutex spk_mu_;                                         // guards spk_model_ and spk_cfg_
   std::shared_ptr<const SpkModel> spk_model_;
@@ -321,7 +266,9 @@ class Recognizer : public std::enable_shared_from_this<Recognizer> {
   // weights it points into alive (Dispose used to hipFree it under such a caller)
   std::shared_ptr<void> image_; int64_t image_bytes_ = 0;
   void free_device_side();                                    // audio cache + copy lanes + our image reference (Dispose, ~Recognizer)
-  std::vector<float> sv_embed_; bool sv_use_itn_ = false;     // SenseVoice prompt table, cached so quirk Q8 needs no engine lease
+  // SenseVoice prompt table, flag and row width: copies of engine 0's (every engine of the pool adopts the same image), so the
+  // prompt prepend (quirk Q8) needs no engine lease
+  std::vector<float> sv_embed_; bool sv_use_itn_ = false; int sv_width_ = 0;
   size_t audio_cache_cap_ = (size_t)1 << 30;                  // PF_RECOGNIZER_AUDIO_CACHE_MB
   std::map<size_t, std::vector<float*>> audio_cache_; size_t audio_cached_bytes_ = 0;
   // A copy lane = a stream + a ring of PINNED host memory.  AddSamples copies the caller's (pageable) samples into the ring piece by
