@@ -59,6 +59,12 @@ class PfVadConfig(C.Structure):
                [("reserved", C.c_int32 * 4)]
 
 
+class PfEndpointConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("struct_size", "rise", "margin_q", "abs_level", "window", "on_count", "off_count",
+                                         "pad_begin", "pad_end", "end_silence", "min_speech", "max_len")] + \
+               [("reserved", C.c_int32 * 4)]
+
+
 class PfSpkConfig(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("win", C.c_int32), ("shift", C.c_int32), ("min_frames", C.c_int32), ("threshold", C.c_float),
                 ("num_speakers", C.c_int32), ("min_cluster", C.c_int32), ("reserved", C.c_int32 * 5)]
@@ -68,6 +74,9 @@ PF_SPK_MAX_FRAMES = 512
 PF_SPK_MAX_WINDOWS = 8192
 PF_VAD_MAX_SEGMENTS = 65536
 PF_VAD_MAX_FRAMES = 1 << 22
+PF_ENDPOINT_STATE_INTS = 16
+PF_ENDPOINT_MAX_STREAM_FRAMES = 1 << 30
+PF_ENDPOINT_SILENCE, PF_ENDPOINT_FORCED, PF_ENDPOINT_FLUSH = 1, 2, 3
 
 
 class PfAttnDesc(C.Structure):
@@ -189,6 +198,11 @@ SIGNATURES = {
     "pf_host_vad_segments": (C.c_int, [_i32, C.c_int32, C.c_int32, C.c_int32, _P(PfVadConfig), _i32, C.c_int32, _i32]),
     "pf_host_long_plan": (C.c_int, [_i32, C.c_int32, C.c_int32, C.c_int64, _i32, _i32, _i32]),
     "pf_op_vad_levels": (C.c_int, [_vp, _f, C.c_int64, C.c_int32, _i32]),
+    "pf_endpoint_default": (C.c_int, [_P(PfEndpointConfig)]),
+    "pf_host_endpoint_update": (C.c_int, [_i32, _i32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P(PfEndpointConfig), _i32, C.c_int32,
+                                          _i32, _i32, _i32]),
+    "pf_op_endpoint_update": (C.c_int, [_vp, _i32, _i32, _i32, _i32, C.c_int32, C.c_int32, C.c_int32, _P(PfEndpointConfig), _i32,
+                                        C.c_int32, _i32, _i32, _i32]),
     "pf_vad_model_load": (C.c_int, [C.c_char_p, _P(_vp)]),
     "pf_vad_model_from_memory": (C.c_int, [_vp, C.c_int64, _P(_vp)]),
     "pf_vad_model_info": (C.c_int, [_vp, _i32, _i32, _i64]),
@@ -419,6 +433,13 @@ SIGNATURES = {
     "pf_online_stream_add_samples": (C.c_int, [_vp, _f, C.c_int64]),
     "pf_online_get_results": (C.c_int, [_vp, _P(_vp), C.c_int32]),
     "pf_online_result_text": (C.c_int, [_vp, C.c_int32, _cpp]),
+    "pf_online_recognizer_set_endpoint": (C.c_int, [_vp, _P(PfEndpointConfig)]),
+    "pf_online_recognizer_set_second_pass": (C.c_int, [_vp, _vp]),
+    "pf_online_stream_input_finished": (C.c_int, [_vp]),
+    "pf_online_stream_num_sentences": (C.c_int, [_vp, _i32]),
+    "pf_online_stream_sentence": (C.c_int, [_vp, C.c_int32, _i32, _i32, _i32, _P(C.c_char_p), _P(C.c_char_p)]),
+    "pf_online_stream_sentence_result": (C.c_int, [_vp, C.c_int32, _P(_vp)]),
+    "pf_online_stream_in_speech": (C.c_int, [_vp, _i32, _i32]),
     "pf_online_stream_tokens": (C.c_int, [_vp, _P(_i64), _i32]),
     "pf_online_stream_dispose": (None, [_vp]),
     "pf_online_stream_free": (None, [_vp]),

@@ -48,6 +48,7 @@ struct pf_online_recognizer {
 struct pf_online_stream {
   std::shared_ptr<OnlineStreamM> s;
   bool freed = false;
+  std::vector<std::shared_ptr<pf_stream>> views;    // borrowed offline-stream handles (pf_online_stream_sentence_result), by sentence
 };
 struct pf_group {
   std::mutex mu;
@@ -905,6 +906,45 @@ int pf_op_vad_segments(pf_engine* h, const int32_t* levels, const int32_t* T, in
   if (B > 0) { NEED(T); NEED(n); if (ld > 0) NEED(levels); if (cap > 0) NEED(seg); }
   std::lock_guard<std::mutex> lk(e->mutex());
   e->op_vad_segments(levels, T, B, ld, n_mels, cfg, seg, cap, n);
+  return PF_OK;
+  PF_CATCH
+}
+
+// ---- voice-activity endpointing, streaming ----
+int pf_endpoint_default(pf_endpoint_config* cfg) {
+  PF_TRY
+  NEED(cfg);
+  *cfg = endpoint_default();
+  return PF_OK;
+  PF_CATCH
+}
+int pf_host_endpoint_update(int32_t* state, const int32_t* levels, int32_t n_new, int32_t flush, int32_t n_mels, int32_t lfr_n,
+                            const pf_endpoint_config* cfg, int32_t* events, int32_t cap, int32_t* n_events, int32_t* in_speech,
+                            int32_t* open_begin) {
+  PF_TRY
+  NEED(state); NEED(n_events);
+  PF_CHECK(n_new >= 0 && n_mels >= 1 && n_mels <= 1024 && cap >= 0 && lfr_n >= 1, PF_ERR_INVALID_ARG, "endpoint_update: bad shape");
+  if (n_new > 0) NEED(levels);
+  if (cap > 0) NEED(events);
+  const pf_endpoint_config c = endpoint_check(cfg, lfr_n);
+  const std::vector<int32_t> ev = host_endpoint_update(state, levels, n_new, flush, n_mels, c, in_speech, open_begin);
+  *n_events = (int32_t)(ev.size() / 3);
+  const int k = std::min(*n_events, cap);
+  if (k > 0) std::memcpy(events, ev.data(), (size_t)k * 12);
+  PF_CHECK(*n_events <= cap, PF_ERR_CAPACITY, "endpoint: capacity " + std::to_string(cap) + " < " + std::to_string(*n_events) + " events");
+  return PF_OK;
+  PF_CATCH
+}
+int pf_op_endpoint_update(pf_engine* h, int32_t* states, const int32_t* levels, const int32_t* n_new, const int32_t* flush, int32_t B,
+                          int32_t ld, int32_t n_mels, const pf_endpoint_config* cfg, int32_t* events, int32_t cap, int32_t* n_events,
+                          int32_t* in_speech, int32_t* open_begin) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  PF_CHECK(B >= 0 && ld >= 0 && cap >= 0 && n_mels >= 1 && n_mels <= 1024, PF_ERR_INVALID_ARG, "endpoint_update: bad shape");
+  if (B > 0) { NEED(states); NEED(n_new); NEED(n_events); NEED(in_speech); NEED(open_begin); if (ld > 0) NEED(levels); if (cap > 0) NEED(events); }
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->op_endpoint_update(states, levels, n_new, flush, B, ld, n_mels, cfg, events, cap, n_events, in_speech, open_begin);
   return PF_OK;
   PF_CATCH
 }
@@ -2651,10 +2691,87 @@ void pf_online_stream_dispose(pf_online_stream* h) {
   h->s->disposed = true;
   std::vector<float>().swap(h->s->Speech);
 }
+int pf_online_recognizer_set_endpoint(pf_online_recognizer* h, const pf_endpoint_config* cfg) {
+  PF_TRY
+  OR(h)->SetEndpoint(cfg);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_online_recognizer_set_second_pass(pf_online_recognizer* h, pf_recognizer* offline) {
+  PF_TRY
+  std::shared_ptr<Recognizer> r;
+  if (offline) {
+    std::lock_guard<std::mutex> lk(offline->mu);
+    PF_CHECK(offline->r != nullptr, PF_ERR_DISPOSED, "OfflineRecognizer");
+    r = offline->r;
+  }
+  OR(h)->SetSecondPass(r);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_online_stream_input_finished(pf_online_stream* h) {
+  PF_TRY
+  OnlineStreamM* s = OS(h);
+  PF_CHECK(!s->owner->disposed(), PF_ERR_DISPOSED, "OnlineRecognizer");
+  s->InputFinished();
+  return PF_OK;
+  PF_CATCH
+}
+int pf_online_stream_num_sentences(pf_online_stream* h, int32_t* n) {
+  PF_TRY
+  OnlineStreamM* s = OS(h);
+  NEED(n);
+  std::lock_guard<std::mutex> lk(s->mu);
+  *n = (int32_t)s->Sentences.size();
+  return PF_OK;
+  PF_CATCH
+}
+int pf_online_stream_sentence(pf_online_stream* h, int32_t j, int32_t* begin_ms, int32_t* end_ms, int32_t* kind,
+                              const char** first_pass_utf8, const char** text_utf8) {
+  PF_TRY
+  OnlineStreamM* s = OS(h);
+  std::lock_guard<std::mutex> lk(s->mu);
+  PF_CHECK(j >= 0 && j < (int32_t)s->Sentences.size(), PF_ERR_INVALID_ARG, "sentence index out of range");
+  const OnlineStreamM::SentenceM& sen = s->Sentences[(size_t)j];
+  if (begin_ms) *begin_ms = sen.begin_ms;
+  if (end_ms) *end_ms = sen.end_ms;
+  if (kind) *kind = sen.kind;
+  if (first_pass_utf8) *first_pass_utf8 = sen.first_pass.c_str();
+  if (text_utf8) *text_utf8 = sen.text.c_str();
+  return PF_OK;
+  PF_CATCH
+}
+int pf_online_stream_sentence_result(pf_online_stream* h, int32_t j, pf_stream** offline_stream) {
+  PF_TRY
+  OnlineStreamM* s = OS(h);
+  NEED(offline_stream);
+  *offline_stream = nullptr;
+  std::lock_guard<std::mutex> lk(s->mu);
+  PF_CHECK(j >= 0 && j < (int32_t)s->Sentences.size(), PF_ERR_INVALID_ARG, "sentence index out of range");
+  if (!s->Sentences[(size_t)j].offline) return PF_OK;
+  if (h->views.size() < s->Sentences.size()) h->views.resize(s->Sentences.size());
+  if (!h->views[(size_t)j]) {
+    h->views[(size_t)j] = std::make_shared<pf_stream>();
+    h->views[(size_t)j]->s = s->Sentences[(size_t)j].offline;
+  }
+  *offline_stream = h->views[(size_t)j].get();
+  return PF_OK;
+  PF_CATCH
+}
+int pf_online_stream_in_speech(pf_online_stream* h, int32_t* in_speech, int32_t* begin_ms) {
+  PF_TRY
+  OnlineStreamM* s = OS(h);
+  std::lock_guard<std::mutex> lk(s->mu);
+  if (in_speech) *in_speech = s->InSpeech ? 1 : 0;
+  if (begin_ms) *begin_ms = s->OpenBeginMs;
+  return PF_OK;
+  PF_CATCH
+}
 void pf_online_stream_free(pf_online_stream* h) {
   if (!h || h->freed) return;
   if (h->s) h->s->disposed = true;
   h->s.reset();
+  h->views.clear();
   h->freed = true;
   online_stream_shells().retire(h);
 }

@@ -70,4 +70,10 @@ inline void set_max_lds(const void* kernel, int bytes) {
   PF_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
 }
 
+// ---- the state block of the streaming endpoint detector (paraformer_hip.h "Voice-activity endpointing, streaming"): the word
+// indices both forms use (hostutil.cpp host_endpoint_update, k_endpoint.hip)
+enum EndpointWord { kEpHist = 0, kEpState = 8, kEpLastOne = 9, kEpRunFirst = 10, kEpPrevEnd = 11, kEpCount = 12, kEpFloorLo = 13,
+                    kEpFloorHi = 14, kEpFlushed = 15 };
+static_assert(kEpFlushed + 1 == PF_ENDPOINT_STATE_INTS, "the endpoint state block");
+
 }  // namespace pf

@@ -310,6 +310,17 @@ class Engine {
   void op_spk_affinity(const float* emb, const int32_t* n, int S, int E, float* out);
   void op_vad_segments(const int32_t* levels, const int32_t* T, int B, int ld, int n_mels, const pf_vad_config* cfg, int32_t* seg,
                        int cap, int32_t* n);
+  // the streaming endpoint kernel (k_endpoint.hip) on caller state blocks and levels: ONE launch of class "endpoint" over B
+  // streams, through op_stage.h (sentinel-filled outputs, hostile levels behind n_new[b], the guard rule on events)
+  void op_endpoint_update(int32_t* states, const int32_t* levels, const int32_t* n_new, const int32_t* flush, int B, int ld, int n_mels,
+                          const pf_endpoint_config* cfg, int32_t* events, int cap, int32_t* n_events, int32_t* in_speech,
+                          int32_t* open_begin);
+  // The streaming recognizer's form (OnlineRecognizerM::Forward): B streams whose state blocks are states_dev [*, PF_ENDPOINT_STATE_INTS]
+  // at slot[b] (device memory the recognizer owns), rows = their new fbank rows concatenated [sum n_new, n_mels].  ONE upload
+  // (n_new | flush | slot | offsets | rows), the level launch over all rows, the endpoint launch (both profile class "endpoint"),
+  // ONE read-back: out = n_events [B] | in_speech [B] | open_begin [B] | events [B, cap, 3].  cap >= max n_new + 1 always suffices.
+  void endpoint_streams(int32_t* states_dev, const int32_t* slot, const float* rows, const int32_t* n_new, const int32_t* flush, int B,
+                        const pf_endpoint_config& c, int cap, std::vector<int32_t>& out);
   void op_ctc_collapse(const int64_t* ids, const float* scores, const int32_t* lens, int B, int T, int blank, int64_t* ids_out,
                        int32_t* first_out, int32_t* last_out, float* score_out, int cap, int32_t* n_out);
   // ---- streaming seams (OnlineRecognizer.cs EncoderProj / DecoderProj) ------

@@ -183,6 +183,98 @@ void Engine::op_vad_segments(const int32_t* levels, const int32_t* T, int B, int
   vad_read_back(stream_, ws, L, B, cap, dev_cap, seg, n);         // (waits for the stream: `off` is read by its copy until then)
 }
 
+// ---- streaming endpointing (k_endpoint.hip).  The levels behind n_new[b] are hostile, every output is sentinel-filled: the
+// counts and the status must have been written, of a stream's events exactly the first min(n, cap) rows.
+void Engine::op_endpoint_update(int32_t* states, const int32_t* levels, const int32_t* n_new, const int32_t* flush, int B, int ld,
+                                int n_mels, const pf_endpoint_config* cfg, int32_t* events, int cap, int32_t* n_events,
+                                int32_t* in_speech, int32_t* open_begin) {
+  const pf_endpoint_config c = endpoint_check(cfg, fc_.lfr_n);
+  for (int b = 0; b < B; ++b) {
+    PF_CHECK(n_new[b] >= 0 && n_new[b] <= ld, PF_ERR_INVALID_ARG, "endpoint_update: n_new[b] outside 0 .. ld");
+    endpoint_admit(states + (size_t)b * PF_ENDPOINT_STATE_INTS, n_new[b]);
+  }
+  PF_HIP(hipSetDevice(device_));
+  if (B == 0) return;
+  const int dev_cap = std::max(cap, 1);
+  const size_t nB = (size_t)B;
+  StageCarve st;
+  const auto d_state = st.take<int32_t>(nB * PF_ENDPOINT_STATE_INTS), d_lev = st.take<int32_t>(nB * ld + 1), d_new = st.take<int32_t>(nB),
+             d_flush = st.take<int32_t>(nB), d_ev = st.take<int32_t>(nB * dev_cap * 3), d_out = st.take<int32_t>(3 * nB);
+  void* ws = op_ws(st);
+  std::vector<int32_t> lev(nB * ld + 1), fl(nB, 0);
+  for (size_t i = 0; i < lev.size(); ++i) lev[i] = hostile_i32(i);
+  for (int b = 0; b < B; ++b) {
+    if (n_new[b] > 0) std::memcpy(&lev[(size_t)b * ld], levels + (size_t)b * ld, (size_t)n_new[b] * 4);
+    if (flush) fl[b] = flush[b];
+  }
+  upload(stream_, d_state(ws), (const int32_t*)states, d_state.count);
+  upload(stream_, d_lev(ws), (const int32_t*)lev.data(), lev.size());
+  upload(stream_, d_new(ws), n_new, nB);
+  upload(stream_, d_flush(ws), (const int32_t*)fl.data(), nB);
+  fill_sentinel(stream_, d_ev(ws), d_ev.count);
+  fill_sentinel(stream_, d_out(ws), d_out.count);
+  const EndpointParams p{c.rise, c.margin_q, c.abs_level, c.window, c.on_count, c.off_count, c.pad_begin, c.pad_end, c.end_silence,
+                         c.min_speech, c.max_len, n_mels};
+  prof_begin("endpoint", 0);
+  launch_endpoint_update(stream_, d_state(ws), nullptr, d_lev(ws), nullptr, ld, d_new(ws), d_flush(ws), B, p, d_ev(ws), dev_cap, d_out(ws), d_out(ws) + nB,
+                         d_out(ws) + 2 * nB);
+  prof_end("endpoint");
+  const std::vector<uint32_t> out = check_guard<uint32_t>(stream_, "endpoint_update: n_events | in_speech | open_begin", d_out(ws), kSentinel32,
+                                                          result_geom(3 * B, 3 * B, 1, 1, 3 * B));
+  std::vector<uint32_t> evh(d_ev.count);                         // the guard rule is applied per stream below
+  download(stream_, (int32_t*)evh.data(), (const int32_t*)d_ev(ws), d_ev.count);
+  download(stream_, states, (const int32_t*)d_state(ws), d_state.count);
+  PF_HIP(hipStreamSynchronize(stream_));
+  int worst = 0;
+  for (int b = 0; b < B; ++b) {
+    const int n = (int)out[b], k = std::min(n, dev_cap);
+    PF_CHECK(n >= 0, PF_ERR_DEVICE, "endpoint_update: a negative event count");
+    const uint32_t* e = evh.data() + (size_t)b * dev_cap * 3;
+    if (const GuardHit hit = guard_scan<uint32_t>(e, nullptr, kSentinel32, result_geom(dev_cap, k, 3, 3, k)))
+      throw Error(PF_ERR_DEVICE, guard_message("endpoint_update: events of stream " + std::to_string(b), result_geom(dev_cap, k, 3, 3, k), hit));
+    n_events[b] = n; in_speech[b] = (int32_t)out[nB + b]; open_begin[b] = (int32_t)out[2 * nB + b];
+    const int kc = std::min(n, cap);
+    if (kc > 0) std::memcpy(events + (size_t)b * cap * 3, e, (size_t)kc * 12);
+    worst = std::max(worst, n);
+  }
+  PF_CHECK(worst <= cap, PF_ERR_CAPACITY, "endpoint: capacity " + std::to_string(cap) + " < " + std::to_string(worst) + " events");
+}
+
+void Engine::endpoint_streams(int32_t* states_dev, const int32_t* slot, const float* rows, const int32_t* n_new, const int32_t* flush, int B,
+                              const pf_endpoint_config& c, int cap, std::vector<int32_t>& out) {
+  PF_HIP(hipSetDevice(device_));
+  out.clear();
+  if (B == 0) return;
+  const size_t nB = (size_t)B, nm = (size_t)fc_.n_mels;
+  const size_t meta_words = (4 * nB + 63) / 64 * 64;            // the rows behind the meta words start on a 256-byte boundary
+  std::vector<int32_t> stage(meta_words, 0);
+  size_t total = 0;
+  for (int b = 0; b < B; ++b) {
+    stage[b] = n_new[b]; stage[nB + b] = flush[b]; stage[2 * nB + b] = slot[b]; stage[3 * nB + b] = (int32_t)total;
+    total += (size_t)n_new[b];
+  }
+  stage.resize(meta_words + total * nm);
+  if (total) std::memcpy(stage.data() + meta_words, rows, total * nm * 4);
+  StageCarve st;
+  const auto d_in = st.take<int32_t>(stage.size() + 4), d_lev = st.take<int32_t>(total + 1), d_out = st.take<int32_t>(3 * nB + nB * cap * 3);
+  void* ws = op_ws(st);
+  upload(stream_, d_in(ws), (const int32_t*)stage.data(), stage.size());
+  const EndpointParams p{c.rise, c.margin_q, c.abs_level, c.window, c.on_count, c.off_count, c.pad_begin, c.pad_end, c.end_silence,
+                         c.min_speech, c.max_len, fc_.n_mels};
+  if (total) {
+    prof_begin("endpoint", 0);
+    launch_vad_levels(stream_, (const float*)(d_in(ws) + meta_words), (int64_t)total, fc_.n_mels, d_lev(ws));
+    prof_end("endpoint");
+  }
+  prof_begin("endpoint", 0);
+  launch_endpoint_update(stream_, states_dev, d_in(ws) + 2 * nB, d_lev(ws), d_in(ws) + 3 * nB, 0, d_in(ws), d_in(ws) + nB, B, p,
+                         d_out(ws) + 3 * nB, cap, d_out(ws), d_out(ws) + nB, d_out(ws) + 2 * nB);
+  prof_end("endpoint");
+  out.resize(d_out.count);
+  download(stream_, out.data(), (const int32_t*)d_out(ws), d_out.count);
+  PF_HIP(hipStreamSynchronize(stream_));
+}
+
 void Engine::vad_segment(const float* const* samples, const int64_t* n, int B, const pf_vad_config* cfg, int32_t* seg, int cap,
                          int32_t* n_seg) {
   vad_check(cfg, fc_.lfr_n);

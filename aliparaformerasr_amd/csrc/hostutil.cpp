@@ -1082,6 +1082,112 @@ std::vector<int32_t> host_vad_segments(const int32_t* lev, int T, int n_mels, co
   return seg;
 }
 
+// ---- streaming endpointing (paraformer_hip.h "Voice-activity endpointing, streaming"; tests/endpoint_ref.py) ----------------
+pf_endpoint_config endpoint_default() {
+  pf_endpoint_config c{};
+  c.struct_size = (int32_t)sizeof(pf_endpoint_config);
+  c.rise = 2; c.margin_q = 96; c.abs_level = INT32_MIN;
+  c.window = 20; c.on_count = 15; c.off_count = 15;
+  c.pad_begin = 30; c.pad_end = 5; c.end_silence = 80;
+  c.min_speech = 50; c.max_len = 3000;
+  return c;
+}
+
+pf_endpoint_config endpoint_check(const pf_endpoint_config* cfg, int lfr_n) {
+  if (!cfg) return endpoint_default();
+  const pf_endpoint_config c = *cfg;
+  PF_CHECK(c.struct_size == (int32_t)sizeof(pf_endpoint_config), PF_ERR_INVALID_ARG, "pf_endpoint_config.struct_size mismatch");
+  PF_CHECK(c.rise >= -1 && c.rise <= (1 << 20), PF_ERR_INVALID_ARG, "endpoint: rise outside -1 .. 1 << 20");
+  PF_CHECK(c.window >= 1 && c.window <= 256, PF_ERR_INVALID_ARG, "endpoint: window outside 1 .. 256");
+  PF_CHECK(c.on_count >= 1 && c.on_count <= c.window && c.off_count >= 1 && c.off_count <= c.window, PF_ERR_INVALID_ARG,
+           "endpoint: on_count / off_count outside 1 .. window");
+  PF_CHECK(c.on_count + c.off_count > c.window, PF_ERR_INVALID_ARG, "endpoint: on_count + off_count must exceed window");
+  PF_CHECK(c.pad_begin >= 0 && c.pad_begin <= 1024, PF_ERR_INVALID_ARG, "endpoint: pad_begin outside 0 .. 1024");
+  PF_CHECK(c.end_silence >= 1 && c.end_silence <= (1 << 16), PF_ERR_INVALID_ARG, "endpoint: end_silence outside 1 .. 1 << 16");
+  PF_CHECK(c.pad_end >= 0 && c.pad_end <= c.end_silence, PF_ERR_INVALID_ARG, "endpoint: pad_end outside 0 .. end_silence");
+  PF_CHECK((int64_t)c.min_speech >= 2 * (int64_t)std::max(lfr_n, 1), PF_ERR_INVALID_ARG, "endpoint: min_speech below 2 * lfr_n");
+  PF_CHECK(c.min_speech <= c.max_len && c.max_len <= PF_VAD_MAX_FRAMES, PF_ERR_INVALID_ARG,
+           "endpoint: max_len outside min_speech .. PF_VAD_MAX_FRAMES");
+  PF_CHECK(c.pad_begin < c.max_len, PF_ERR_INVALID_ARG, "endpoint: pad_begin must be below max_len");
+  return c;
+}
+
+void endpoint_admit(const int32_t* state, int n_new) {
+  PF_CHECK(n_new >= 0, PF_ERR_INVALID_ARG, "endpoint: negative frame count");
+  // a block no sequence of calls leaves behind is refused: the walk's integer arithmetic relies on these ranges
+  const int32_t count = state[kEpCount];
+  const int64_t F = (int64_t)(((uint64_t)(uint32_t)state[kEpFloorHi] << 32) | (uint32_t)state[kEpFloorLo]);
+  PF_CHECK(count >= 0 && count <= PF_ENDPOINT_MAX_STREAM_FRAMES && (state[kEpState] | 1) == 1 && (state[kEpFlushed] | 1) == 1 &&
+               state[kEpLastOne] >= 0 && state[kEpLastOne] <= count && state[kEpRunFirst] >= 0 && state[kEpRunFirst] <= count &&
+               state[kEpPrevEnd] >= 0 && state[kEpPrevEnd] <= count && F >= INT32_MIN && F <= INT32_MAX,
+           PF_ERR_INVALID_ARG, "endpoint: not a state block of this detector");
+  PF_CHECK(!(state[kEpFlushed] && n_new > 0), PF_ERR_INVALID_ARG, "endpoint: frames after a flush");
+  PF_CHECK((int64_t)count + n_new <= PF_ENDPOINT_MAX_STREAM_FRAMES, PF_ERR_CAPACITY,
+           "endpoint: more than PF_ENDPOINT_MAX_STREAM_FRAMES frames in one stream");
+}
+
+std::vector<int32_t> host_endpoint_update(int32_t* s, const int32_t* lev, int n_new, int flush, int n_mels, const pf_endpoint_config& c,
+                                          int32_t* in_speech, int32_t* open_begin) {
+  endpoint_admit(s, n_new);
+  std::vector<int32_t> ev;
+  uint32_t h[8];                                               // the 256-bit window, bit 255 the newest frame
+  for (int j = 0; j < 8; ++j) h[j] = (uint32_t)s[kEpHist + j];
+  int state = s[kEpState], last_one = s[kEpLastOne] - 1, run_first = s[kEpRunFirst] - 1, prev_end = s[kEpPrevEnd], count = s[kEpCount];
+  int64_t F = (int64_t)(((uint64_t)(uint32_t)s[kEpFloorHi] << 32) | (uint32_t)s[kEpFloorLo]);
+  const int64_t margin = (int64_t)c.margin_q * n_mels;
+  auto begin = [&] { return std::max(prev_end, run_first - c.pad_begin); };
+  auto emit = [&](int b, int e, int kind) { ev.push_back(b); ev.push_back(e); ev.push_back(kind); };
+  for (int i = 0; i < n_new; ++i) {
+    const int t = count;
+    const int64_t e = lev[i];
+    // 2' the tracked floor
+    int64_t thr = c.abs_level;
+    if (c.rise >= 0) {
+      F = t == 0 ? e : std::min(e, F + c.rise);
+      thr = std::max<int64_t>(F + margin, c.abs_level);
+    }
+    for (int j = 0; j < 7; ++j) h[j] = (h[j] >> 1) | (h[j + 1] << 31);
+    h[7] = (h[7] >> 1) | (e > thr ? 0x80000000u : 0u);
+    // 3 hysteresis: the newest w frames are the top w bits
+    const int w = std::min(c.window, t + 1);
+    int cnt = 0;
+    for (int k = 0; k < w; ++k) cnt += (int)((h[7 - (k >> 5)] >> (31 - (k & 31))) & 1u);
+    if (cnt >= c.on_count) state = 1;
+    else if (w - cnt >= c.off_count) state = 0;
+    // 4' events
+    if (state) {
+      if (run_first < 0) run_first = t;
+      last_one = t;
+    } else if (run_first >= 0 && t == last_one + c.end_silence) {
+      const int b = begin(), en = last_one + 1 + c.pad_end;
+      if (en - b >= c.min_speech) { emit(b, en, PF_ENDPOINT_SILENCE); prev_end = en; }
+      run_first = -1;
+    }
+    // 5' the forced cut
+    if (run_first >= 0 && t + 1 - begin() == c.max_len) {
+      emit(begin(), t + 1, PF_ENDPOINT_FORCED);
+      prev_end = t + 1;
+      if (!state) run_first = -1;
+    }
+    ++count;
+  }
+  if (flush && !s[kEpFlushed]) {
+    // 6 flush
+    if (run_first >= 0) {
+      const int b = begin(), en = std::min(count, last_one + 1 + c.pad_end);
+      if (en - b >= c.min_speech) { emit(b, en, PF_ENDPOINT_FLUSH); prev_end = en; }
+      run_first = -1;
+    }
+    s[kEpFlushed] = 1;
+  }
+  for (int j = 0; j < 8; ++j) s[kEpHist + j] = (int32_t)h[j];
+  s[kEpState] = state; s[kEpLastOne] = last_one + 1; s[kEpRunFirst] = run_first + 1; s[kEpPrevEnd] = prev_end; s[kEpCount] = count;
+  if (c.rise >= 0 && count > 0) { s[kEpFloorLo] = (int32_t)(uint32_t)(uint64_t)F; s[kEpFloorHi] = (int32_t)(uint32_t)((uint64_t)F >> 32); }
+  if (in_speech) *in_speech = run_first >= 0 ? 1 : 0;
+  if (open_begin) *open_begin = run_first >= 0 ? begin() : -1;
+  return ev;
+}
+
 int host_long_plan(const int32_t* len, int n, int batch_max, int64_t frame_budget, int32_t* batch, int32_t* row) {
   if (batch_max <= 0) batch_max = 32;
   if (frame_budget <= 0) frame_budget = 96000;

@@ -142,6 +142,18 @@ std::vector<int32_t> host_vad_segments(const int32_t* levels, int T, int n_mels,
 // the batch plan of long-audio recognition: batch / row per segment; returns the number of batches
 int host_long_plan(const int32_t* len, int n, int batch_max, int64_t frame_budget, int32_t* batch, int32_t* row);
 
+// ---- streaming endpointing (paraformer_hip.h "Voice-activity endpointing, streaming"; the definition is tests/endpoint_ref.py) ----
+// endpoint_default / endpoint_check: as vad_default / vad_check.  endpoint_admit: what both forms check about ONE stream's
+// call before anything changes (a block the detector cannot have left, frames after a flush: PF_ERR_INVALID_ARG; too many frames:
+// PF_ERR_CAPACITY).
+pf_endpoint_config endpoint_default();
+pf_endpoint_config endpoint_check(const pf_endpoint_config* cfg, int lfr_n);
+void endpoint_admit(const int32_t* state, int n_new);
+// The host twin of k_endpoint.hip for ONE stream, one frame at a time: n_new levels, then the flush.  state
+// [PF_ENDPOINT_STATE_INTS] in / out; returns every event as (b, e, kind) triples; *in_speech / *open_begin as the header says.
+std::vector<int32_t> host_endpoint_update(int32_t* state, const int32_t* levels, int n_new, int flush, int n_mels,
+                                          const pf_endpoint_config& c, int32_t* in_speech, int32_t* open_begin);
+
 // UTF-8 <-> code points
 std::vector<uint32_t> utf8_decode(const std::string& s);
 std::string utf8_encode(uint32_t cp);

@@ -67,19 +67,7 @@ void launch_vad_levels(hipStream_t s, const float* rows, int64_t T, int n_mels, 
 }
 
 // ------------------------------------------------------------------ steps 2-6: segments ------
-// bits [lo, hi] (inclusive, positions in the 320-bit array h[0] .. h[4]; lo may be negative) that are set
-__device__ __forceinline__ int vad_count_bits(const unsigned long long (&h)[5], int lo, int hi) {
-  int c = 0;
-#pragma unroll
-  for (int j = 0; j < 5; ++j) {
-    const int a = max(lo - 64 * j, 0), b = min(hi - 64 * j, 63);
-    if (a <= b) {
-      const unsigned long long m = (b == 63 ? ~0ull : ((1ull << (b + 1)) - 1ull)) & ~((1ull << a) - 1ull);
-      c += __popcll(h[j] & m);
-    }
-  }
-  return c;
-}
+// (vad_count_bits and vad_last_event_state, shared with k_endpoint.hip, are in kdev.h)
 
 // one closed padded run [b, e) of utterance levels `lev`: drop, split, store.  All arguments are wave-uniform.
 __device__ __forceinline__ void vad_emit_run(const int32_t* __restrict__ lev, int b, int e, const VadParams& p, int lane,
@@ -181,8 +169,7 @@ __global__ __launch_bounds__(64) void vad_segments_kernel(const int32_t* __restr
     const bool on = valid && cnt >= p.on_count;
     const bool offe = valid && !on && w - cnt >= p.off_count;
     const unsigned long long evm = __ballot(on || offe), onm = __ballot(on);
-    const unsigned long long ev_le = evm & le;
-    const bool st = valid && (ev_le ? ((onm >> (63 - __clzll((long long)ev_le))) & 1ull) != 0 : state_c != 0);
+    const bool st = valid && vad_last_event_state(evm, onm, le, state_c != 0);
     const unsigned long long sm = __ballot(st);
 
     // step 4 on runs: the first frame of a state run opens a padded run when nothing lies within `pads` behind it

@@ -53,6 +53,28 @@ __device__ __forceinline__ float wave_sum(float v) {
   return (a + b) + (c + d);
 }
 
+// ---- the 64-bit-ballot window of the voice-activity walks (k_vad.hip, k_endpoint.hip): h[0 .. 3] hold one bit per frame for
+// the 256 frames before a 64-frame chunk, h[4] the chunk's own ballot.  The set bits among positions [lo, hi] (inclusive; lo
+// may be negative) of that 320-bit array.
+__device__ __forceinline__ int vad_count_bits(const unsigned long long (&h)[5], int lo, int hi) {
+  int c = 0;
+#pragma unroll
+  for (int j = 0; j < 5; ++j) {
+    const int a = max(lo - 64 * j, 0), b = min(hi - 64 * j, 63);
+    if (a <= b) {
+      const unsigned long long m = (b == 63 ? ~0ull : ((1ull << (b + 1)) - 1ull)) & ~((1ull << a) - 1ull);
+      c += __popcll(h[j] & m);
+    }
+  }
+  return c;
+}
+// "the last event at or before the lane wins" (hysteresis): evm = the lanes with an event, onm = those whose event switches
+// on, le = the mask of the lanes at or below this one, carry = the state in front of the chunk
+__device__ __forceinline__ bool vad_last_event_state(unsigned long long evm, unsigned long long onm, unsigned long long le, bool carry) {
+  const unsigned long long ev_le = evm & le;
+  return ev_le ? ((onm >> (63 - __clzll((long long)ev_le))) & 1ull) != 0 : carry;
+}
+
 // ---- result stores.  The variants differ in cache policy and in what follows the store; each keeps its own name.
 
 // gemm_f16_pp3's deferred f16 result stores (k_gemm.hip).  Cache policy: 0 plain, 1 nt, 2 sc1 (write-through, line

@@ -513,6 +513,18 @@ struct VadParams { int32_t floor_pct, margin_q, abs_level, window, on_count, off
 void launch_vad_segments(hipStream_t s, const int32_t* levels, const int64_t* off, const int32_t* T, int B, const VadParams& p,
                          int32_t* seg, int cap, int32_t* n);
 
+// ---------------------------------------------------------------- streaming endpointing (k_endpoint.hip) ------
+// The detector of paraformer_hip.h "Voice-activity endpointing, streaming"; the definition in numpy is tests/endpoint_ref.py.
+// Steps 2' - 7 for B streams in one launch: stream b = its state block states [slot[b], PF_ENDPOINT_STATE_INTS] (read, then
+// written; slot null: block b; the slots of a launch are distinct) and n_new[b] new levels at levels + off[b] (off null: levels
+// + b * ld; nothing at or beyond n_new[b] is read), then its flush when flush[b] != 0 (flush may be null).  events [B, cap, 3] = (b, e, kind), cap >= 1: only the first min(n_events[b], cap) rows of a stream are written;
+// n_events / in_speech / open_begin [B] are always written.  cfg: validated by endpoint_check (hostutil.h).
+struct EndpointParams { int32_t rise, margin_q, abs_level, window, on_count, off_count, pad_begin, pad_end, end_silence, min_speech,
+                        max_len, n_mels; };
+void launch_endpoint_update(hipStream_t s, int32_t* states, const int32_t* slot, const int32_t* levels, const int32_t* off, int64_t ld,
+                            const int32_t* n_new, const int32_t* flush, int B, const EndpointParams& p, int32_t* events, int cap, int32_t* n_events, int32_t* in_speech,
+                            int32_t* open_begin);
+
 // ---------------------------------------------------------------- the FSMN-VAD model score (k_vadnet.hip) ------
 // The second form of step 1 of the voice-activity segmentation; the definition in numpy is tests/vadnet_ref.py.  One launch
 // of the 1 + n_layers that make a forward (the plan is at the head of k_vadnet.hip; Engine::run_vadnet fills these in).

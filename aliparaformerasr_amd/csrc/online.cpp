@@ -1,6 +1,7 @@
 // online.cpp — see online.h.  Host-side logic of the reference's streaming API restated in C++ (the reference is
 // compiled C#; no .NET toolchain exists in the build image); citations are relative to AliParaformerAsr/.
 #include "online.h"
+#include "recognizer.h"
 
 #include <algorithm>
 #include <cmath>
@@ -127,23 +128,59 @@ OnlineStreamM::OnlineStreamM(std::shared_ptr<OnlineRecognizerM> r) : owner(std::
   cache_samples_.assign((size_t)160 * owner->chunk_length(), 0.f);                  // :63: a chunk of SILENCE is queued first
 }
 
+OnlineStreamM::~OnlineStreamM() {
+  if (ep_slot_ >= 0 && owner) owner->release_slot(ep_slot_);
+}
+
 void OnlineStreamM::AddSamples(const float* samples, int64_t n) {
   if (disposed) throw Error(PF_ERR_DISPOSED, "OnlineStream");
   if (!samples) throw Error(PF_ERR_NULL_SAMPLES, "source");
   std::vector<float> s;
+  size_t n_caller = 0;
   {
     std::lock_guard<std::mutex> lk(mu);
+    if (finished_) throw Error(PF_ERR_INVALID_ARG, "OnlineStream: AddSamples after InputFinished");
     cache_samples_.insert(cache_samples_.end(), samples, samples + n);
     const size_t chunk = (size_t)160 * owner->chunk_length();
     if (cache_samples_.size() > chunk) {                        // ONE chunk per call (:94-102), the rest stays cached
       s.assign(cache_samples_.begin(), cache_samples_.begin() + (long)chunk);
       cache_samples_.erase(cache_samples_.begin(), cache_samples_.begin() + (long)chunk);
+      n_caller = chunks_in_++ == 0 ? 0 : chunk;                 // the first chunk is the constructor's silence
     }
   }
-  if (!s.empty()) InputSpeech(s);
+  if (!s.empty()) InputSpeech(s, n_caller);
 }
 
-void OnlineStreamM::InputSpeech(const std::vector<float>& samples) {
+void OnlineStreamM::InputFinished() {
+  if (disposed) throw Error(PF_ERR_DISPOSED, "OnlineStream");
+  const size_t chunk = (size_t)160 * owner->chunk_length();
+  for (;;) {
+    std::vector<float> s;
+    size_t n_caller = 0;
+    {
+      std::lock_guard<std::mutex> lk(mu);
+      finished_ = true;
+      if (cache_samples_.empty()) return;
+      const size_t take = std::min(chunk, cache_samples_.size());
+      s.assign(cache_samples_.begin(), cache_samples_.begin() + (long)take);
+      cache_samples_.erase(cache_samples_.begin(), cache_samples_.begin() + (long)take);
+      n_caller = chunks_in_++ == 0 ? 0 : take;
+      s.resize(chunk, 0.f);                                     // the tail: zero-padded to one chunk
+    }
+    InputSpeech(s, n_caller);
+  }
+}
+
+void OnlineStreamM::ResetDecoder() {                            // (the caller holds mu)
+  Tokens.clear();
+  for (std::vector<float>& st : States) std::fill(st.begin(), st.end(), 0.f);
+  CifHidden.assign(1, std::vector<float>((size_t)512, 0.f));
+  CifAlpha.assign(1, 0.f);
+  std::fill(cache_feats_.begin(), cache_feats_.end(), 0.f);
+  start_idx_ = 0;
+}
+
+void OnlineStreamM::InputSpeech(const std::vector<float>& samples, size_t n_caller) {
   std::shared_ptr<Engine> e = owner->engine();
   if (!e) throw Error(PF_ERR_DISPOSED, "OnlineRecognizer");
   std::vector<float> fb;
@@ -153,6 +190,14 @@ void OnlineStreamM::InputSpeech(const std::vector<float>& samples) {
     e->fbank_host(samples.data(), (int64_t)samples.size(), fb, t80);     // x 32768 + kaldi fbank (:129-130)
   }
   std::lock_guard<std::mutex> lk(mu);
+  if (n_caller > 0 && owner->endpoint_on() && !ep_flushed_) {             // the detector's share: the caller's frames and samples
+    if (ep_origin_ < 0) ep_origin_ = caller_samples_;
+    const size_t rows = std::min((n_caller + 159) / 160, (size_t)t80);
+    ep_rows_.insert(ep_rows_.end(), fb.begin(), fb.begin() + (long)(rows * 80));
+    ep_audio_.insert(ep_audio_.end(), samples.begin(), samples.begin() + (long)n_caller);
+    ep_samples_ += (int64_t)n_caller;
+  }
+  caller_samples_ += (int64_t)n_caller;
   if (first_input_ && t80 > 0) {                                          // :131-143: the first frame is repeated once
     Speech.insert(Speech.end(), fb.begin(), fb.begin() + 80);
     first_input_ = false;
@@ -232,8 +277,163 @@ void OnlineRecognizerM::Dispose() {
     if (disposed_.exchange(true)) return;
     e.swap(engine_);
   }
-  if (e) { std::lock_guard<std::mutex> lk(e->mutex()); }
+  if (e) {
+    std::lock_guard<std::mutex> lk(e->mutex());
+    std::lock_guard<std::mutex> lk2(ep_mu_);
+    if (ep_states_) { hipSetDevice(e->device()); hipFree(ep_states_); ep_states_ = nullptr; ep_cap_ = 0; ep_free_.clear(); }
+    second_.reset();
+  }
   e.reset();
+}
+
+// ------------------------------------------------------------------ endpointing and the second pass -------
+void OnlineRecognizerM::SetEndpoint(const pf_endpoint_config* cfg) {
+  if (disposed_) throw Error(PF_ERR_DISPOSED, "OnlineRecognizer");
+  if (!cfg) { ep_on_ = false; return; }
+  const pf_endpoint_config c = endpoint_check(cfg, (conf_.lfr_m == 1 && conf_.lfr_n == 1) ? 1 : conf_.lfr_n);
+  PF_CHECK(!conf_.snip_edges, PF_ERR_UNSUPPORTED, "endpoint: snip_edges = true is not supported");
+  PF_CHECK(conf_.n_mels == 80, PF_ERR_UNSUPPORTED, "endpoint: the streaming path carries 80 mel bins");
+  std::lock_guard<std::mutex> lk(ep_mu_);
+  ep_cfg_ = c;
+  ep_on_ = true;
+}
+
+void OnlineRecognizerM::SetSecondPass(std::shared_ptr<Recognizer> offline) {
+  if (disposed_) throw Error(PF_ERR_DISPOSED, "OnlineRecognizer");
+  if (offline) {
+    PF_CHECK(!offline->disposed(), PF_ERR_DISPOSED, "OfflineRecognizer");
+    PF_CHECK(!offline->vad_on(), PF_ERR_UNSUPPORTED, "second pass: the offline recognizer has SetVad on (one sentence must stay one stream)");
+  }
+  std::lock_guard<std::mutex> lk(ep_mu_);
+  second_ = std::move(offline);
+}
+
+void OnlineRecognizerM::release_slot(int slot) {
+  std::lock_guard<std::mutex> lk(ep_mu_);
+  if (ep_states_ && slot >= 0 && slot < ep_cap_) ep_free_.push_back(slot);
+}
+
+// The detector's launch set for the call's streams that have new caller frames or a flush to make, the sentences its events
+// close, then the second pass over those sentences (one GetResults of the attached offline recognizer).
+void OnlineRecognizerM::ForwardEndpoint(const std::vector<OnlineStreamM*>& streams) {
+  struct Closed { OnlineStreamM* s; size_t idx; std::vector<float> audio; };
+  std::vector<Closed> closed;
+  pf_endpoint_config c;
+  std::shared_ptr<Recognizer> second;
+  {
+    std::lock_guard<std::mutex> lk(ep_mu_);
+    c = ep_cfg_;
+    second = second_;
+  }
+  try {
+    std::shared_ptr<Engine> eh = engine();
+    if (disposed_ || !eh) throw Error(PF_ERR_DISPOSED, "OnlineRecognizer");
+    Engine* e = eh.get();
+    std::lock_guard<std::mutex> lk(e->mutex());
+    // who takes part: new rows, or the flush once the model has decoded every chunk of a finished input
+    std::vector<OnlineStreamM*> work;
+    std::vector<int32_t> n_new, flush, slot;
+    std::vector<float> rows;
+    const size_t CLF = (size_t)chunk_length() * 80;
+    for (OnlineStreamM* s : streams) {
+      std::lock_guard<std::mutex> ls(s->mu);
+      if (s->ep_flushed_ || std::find(work.begin(), work.end(), s) != work.end()) continue;
+      const bool fl = s->finished_ && s->cache_samples_.empty() && s->Speech.size() < CLF && s->ep_origin_ >= 0;
+      if (s->ep_rows_.empty() && !fl) continue;
+      const int n = (int)(s->ep_rows_.size() / 80);
+      PF_CHECK((int64_t)s->ep_fed_ + n <= PF_ENDPOINT_MAX_STREAM_FRAMES, PF_ERR_CAPACITY, "endpoint: more than PF_ENDPOINT_MAX_STREAM_FRAMES frames in one stream");
+      work.push_back(s);
+      n_new.push_back(n);
+      flush.push_back(fl ? 1 : 0);
+      rows.insert(rows.end(), s->ep_rows_.begin(), s->ep_rows_.end());
+    }
+    if (work.empty()) return;
+    const int B = (int)work.size();
+    {                                                           // a slot of the state buffer per stream, zeroed when handed out
+      std::lock_guard<std::mutex> ls(ep_mu_);
+      PF_HIP(hipSetDevice(e->device()));
+      for (OnlineStreamM* s : work) {
+        if (s->ep_slot_ >= 0) continue;
+        if (ep_free_.empty()) {
+          const int cap = std::max(64, 2 * ep_cap_);
+          int32_t* p = nullptr;
+          PF_HIP(hipMalloc((void**)&p, (size_t)cap * PF_ENDPOINT_STATE_INTS * 4));
+          if (ep_states_) {
+            PF_HIP(hipMemcpyAsync(p, ep_states_, (size_t)ep_cap_ * PF_ENDPOINT_STATE_INTS * 4, hipMemcpyDeviceToDevice, e->stream()));
+            PF_HIP(hipStreamSynchronize(e->stream()));
+            PF_HIP(hipFree(ep_states_));
+          }
+          for (int i = cap - 1; i >= ep_cap_; --i) ep_free_.push_back(i);
+          ep_states_ = p;
+          ep_cap_ = cap;
+        }
+        s->ep_slot_ = ep_free_.back();
+        ep_free_.pop_back();
+        PF_HIP(hipMemsetAsync(ep_states_ + (size_t)s->ep_slot_ * PF_ENDPOINT_STATE_INTS, 0, PF_ENDPOINT_STATE_INTS * 4, e->stream()));
+      }
+      for (OnlineStreamM* s : work) slot.push_back(s->ep_slot_);
+    }
+    const int cap = *std::max_element(n_new.begin(), n_new.end()) + 1;
+    std::vector<int32_t> out;
+    e->endpoint_streams(ep_states_, slot.data(), rows.data(), n_new.data(), flush.data(), B, c, cap, out);
+    for (int b = 0; b < B; ++b) {
+      OnlineStreamM* s = work[(size_t)b];
+      std::lock_guard<std::mutex> ls(s->mu);
+      s->ep_rows_.clear();
+      s->ep_fed_ += n_new[(size_t)b];
+      if (flush[(size_t)b]) s->ep_flushed_ = true;
+      const int n_ev = out[(size_t)b];
+      PF_CHECK(n_ev >= 0 && n_ev <= cap, PF_ERR_DEVICE, "endpoint: event count outside 0 .. cap");
+      const int32_t* ev = out.data() + 3 * (size_t)B + (size_t)b * cap * 3;
+      for (int k = 0; k < n_ev; ++k) {
+        const int64_t fb = ev[3 * k], fe = ev[3 * k + 1];
+        OnlineStreamM::SentenceM sen;
+        sen.begin_ms = (int)((s->ep_origin_ + 160 * fb) / 16);
+        sen.end_ms = (int)((s->ep_origin_ + 160 * fe) / 16);
+        sen.kind = ev[3 * k + 2];
+        sen.first_pass = online_decode_text(tokens_, s->Tokens);            // after this chunk's ids were appended
+        sen.text = sen.first_pass;
+        s->ResetDecoder();
+        const int64_t a0 = 160 * fb - s->ep_audio_base_, a1 = std::min<int64_t>(s->ep_samples_, 160 * fe) - s->ep_audio_base_;
+        PF_CHECK(a0 >= 0 && a1 > a0 && a1 <= (int64_t)s->ep_audio_.size(), PF_ERR_RECOGNITION, "endpoint: a sentence outside the retained audio");
+        if (second) closed.push_back(Closed{s, s->Sentences.size(), std::vector<float>(s->ep_audio_.begin() + a0, s->ep_audio_.begin() + a1)});
+        s->Sentences.push_back(std::move(sen));
+        s->ep_prev_end_ = (int)fe;
+      }
+      s->InSpeech = out[(size_t)B + b] != 0;
+      const int ob = out[2 * (size_t)B + b];
+      s->OpenBeginMs = s->InSpeech ? (int)((s->ep_origin_ + 160 * (int64_t)ob) / 16) : -1;
+      // what a sentence that is open, or opens later, can still need: from prev_end, and from the open begin or pad_begin + window
+      // frames behind the newest frame
+      const int64_t keep = 160 * (int64_t)std::max(s->ep_prev_end_, s->InSpeech ? ob : std::max(0, s->ep_fed_ - c.pad_begin - c.window));
+      if (keep > s->ep_audio_base_) {
+        const int64_t drop = std::min<int64_t>(keep - s->ep_audio_base_, (int64_t)s->ep_audio_.size());
+        s->ep_audio_.erase(s->ep_audio_.begin(), s->ep_audio_.begin() + drop);
+        s->ep_audio_base_ += drop;
+      }
+      if (s->ep_flushed_) { std::vector<float>().swap(s->ep_audio_); }
+    }
+  } catch (const Error& ex) {
+    if (ex.code != PF_ERR_RECOGNITION) throw;
+    throw Error(PF_ERR_RECOGNITION, std::string("Online recognition failed: ") + ex.what());
+  }
+  if (closed.empty() || !second) return;
+  // the second pass: one plain offline stream per sentence, in the call's stream order and then in time order, ONE GetResults
+  std::vector<std::shared_ptr<Stream>> off;
+  std::vector<Stream*> ptrs;
+  for (Closed& cl : closed) {
+    off.push_back(second->CreateOfflineStream());
+    off.back()->AddSamples(cl.audio.data(), (int64_t)cl.audio.size());
+    ptrs.push_back(off.back().get());
+  }
+  second->GetResults(ptrs);
+  const std::vector<ResultEntity>& res = second->results_of_this_thread();
+  for (size_t i = 0; i < closed.size(); ++i) {
+    std::lock_guard<std::mutex> ls(closed[i].s->mu);
+    OnlineStreamM::SentenceM& sen = closed[i].s->Sentences[closed[i].idx];
+    sen.text = i < res.size() ? res[i].Text : std::string();
+    sen.offline = off[i];
+  }
 }
 
 void OnlineRecognizerM::Forward(const std::vector<OnlineStreamM*>& streams) {
@@ -327,6 +527,7 @@ void OnlineRecognizerM::Forward(const std::vector<OnlineStreamM*>& streams) {
 
 std::vector<std::string> OnlineRecognizerM::GetResults(const std::vector<OnlineStreamM*>& streams) {
   Forward(streams);
+  if (endpoint_on()) ForwardEndpoint(streams);
   std::vector<std::string> out;
   for (OnlineStreamM* s : streams) out.push_back(online_decode_text(tokens_, s->Tokens));
   return out;

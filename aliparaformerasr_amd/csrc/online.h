@@ -35,11 +35,25 @@ void online_cif(const std::vector<std::vector<float>>& hiddens, const std::vecto
 std::string online_decode_text(const std::vector<std::string>& tokens, const std::vector<int64_t>& ids);
 
 class OnlineRecognizerM;
+class Recognizer;
+class Stream;
 
 class OnlineStreamM {
  public:
   explicit OnlineStreamM(std::shared_ptr<OnlineRecognizerM> r);
+  ~OnlineStreamM();
   void AddSamples(const float* samples, int64_t n);           // OnlineStream.cs:79-105
+  // ---- endpointing (OnlineRecognizerM::SetEndpoint; paraformer_hip.h "Streaming endpointing"; no counterpart in the reference)
+  // The input is complete: every cached chunk goes through InputSpeech, the samples short of a chunk zero-padded to one (the
+  // online model then decodes the tail too); the GetResults that has decoded the last chunk flushes the detector.  A later
+  // AddSamples throws PF_ERR_INVALID_ARG.
+  void InputFinished();
+  // a finished sentence: [begin_ms, end_ms) in the caller's audio, PF_ENDPOINT_* kind, the online model's text at the closing
+  // chunk, the second pass's text (= first_pass without one) and the offline stream that produced it (null without one)
+  struct SentenceM { int begin_ms = 0, end_ms = 0, kind = 0; std::string first_pass, text; std::shared_ptr<Stream> offline; };
+  std::vector<SentenceM> Sentences;
+  bool InSpeech = false;                                      // a sentence is open (as of the last GetResults)
+  int OpenBeginMs = -1;
   bool GetDecodeChunk(std::vector<float>& chunk);             // :162-208 (chunk = [10 cached ; 10 new] x 560), false = not enough frames
   std::vector<int64_t> Tokens{0, 0};                          // :52
   std::vector<std::vector<float>> States;                     // 16 x [512*10]
@@ -55,10 +69,22 @@ class OnlineStreamM {
   std::mutex mu;
 
  private:
-  void InputSpeech(const std::vector<float>& samples);        // :106-160
+  friend class OnlineRecognizerM;
+  // n_caller: how many of the chunk's leading samples are the caller's (0 for the chunk of silence the constructor queued)
+  void InputSpeech(const std::vector<float>& samples, size_t n_caller);   // :106-160
+  void ResetDecoder();                                        // the decoder context back to the constructor's, Tokens cleared
   std::vector<float> cache_samples_, cache_feats_, cache_lfr_splice_;
   bool first_input_ = true;                                   // _cacheInput.Length == 0
   int start_idx_ = 0;
+  int64_t chunks_in_ = 0, caller_samples_ = 0;                // chunks / caller samples that went through InputSpeech
+  bool finished_ = false;
+  // endpointing: the detector's frame 0 is the caller's sample ep_origin_; ep_rows_ = fbank rows not yet sent to the detector;
+  // ep_audio_ = the caller's samples from ep_audio_base_ (relative to ep_origin_) on; ep_fed_ = frames sent so far
+  int ep_slot_ = -1;
+  int64_t ep_origin_ = -1, ep_audio_base_ = 0, ep_samples_ = 0;
+  std::vector<float> ep_rows_, ep_audio_;
+  int ep_fed_ = 0, ep_prev_end_ = 0;
+  bool ep_flushed_ = false;
 };
 
 class OnlineRecognizerM : public std::enable_shared_from_this<OnlineRecognizerM> {
@@ -77,9 +103,27 @@ class OnlineRecognizerM : public std::enable_shared_from_this<OnlineRecognizerM>
   const std::vector<float>& shift() const { return shift_; }
   const std::vector<float>& scale() const { return scale_; }
   const std::vector<std::string>& tokens() const { return tokens_; }
+  // ---- endpointing and the second pass (paraformer_hip.h "Streaming endpointing") ----
+  // cfg != null: every GetResults that follows runs the streaming endpoint detector over the caller-audio fbank rows of its
+  // streams (one launch set for all of them), closes sentences at its events and resets their decoder context.  null: off —
+  // every path is then what it is without this call.  PF_ERR_INVALID_ARG as pf_endpoint_config; PF_ERR_UNSUPPORTED with snip_edges.
+  void SetEndpoint(const pf_endpoint_config* cfg);
+  // the offline recognizer that re-recognises every finished sentence (ONE GetResults per call over the sentences that closed
+  // in it); null: none.  PF_ERR_UNSUPPORTED for a recognizer with SetVad on (one sentence stays one stream).
+  void SetSecondPass(std::shared_ptr<Recognizer> offline);
+  bool endpoint_on() const { return ep_on_.load(); }
+  void release_slot(int slot);
 
  private:
   void Forward(const std::vector<OnlineStreamM*>& streams);   // :336-403
+  void ForwardEndpoint(const std::vector<OnlineStreamM*>& streams);
+  std::atomic<bool> ep_on_{false};
+  std::mutex ep_mu_;                                          // guards the five below
+  pf_endpoint_config ep_cfg_{};
+  std::shared_ptr<Recognizer> second_;
+  int32_t* ep_states_ = nullptr;                              // [ep_cap_, PF_ENDPOINT_STATE_INTS] on the device, a block per stream slot
+  int ep_cap_ = 0;
+  std::vector<int> ep_free_;
   std::mutex mu_;
   std::shared_ptr<Engine> engine_;
   ConfEntity conf_;

@@ -165,6 +165,7 @@ class Recognizer : public std::enable_shared_from_this<Recognizer> {
   // length (host_long_plan), forwards each batch over pointers into the streams' audio and stitches one result per stream.
   // cfg == null: off.  PF_ERR_UNSUPPORTED beside SetNBest / SetCtcBeam / SetAlign (either order).
   void SetVad(const pf_vad_config* cfg, int batch_max, int64_t frame_budget, const char* sep);
+  bool vad_on() { std::lock_guard<std::mutex> lk(vad_mu_); return vad_on_; }
   // The FSMN-VAD model score for SetVad's segmentation (paraformer_hip.h "Voice-activity segmentation, model score"): a `.pfw`
   // of kind "fsmnvad", loaded once and attached to every engine of the pool, present and future; "" clears.  Inert until SetVad.
   void SetVadModel(const std::string& pfw_path);

@@ -358,6 +358,48 @@ def host_vad_segments(levels, n_mels=80, cfg=None, lfr_n=6, cap=None) -> np.ndar
     return seg[: n.value].copy()
 
 
+def endpoint_config(**kw) -> "N.PfEndpointConfig":
+    """pf_endpoint_config with the stated defaults (pf_endpoint_default), fields overridden by keyword."""
+    c = N.PfEndpointConfig()
+    N.check(N.load().pf_endpoint_default(C.byref(c)))
+    for k, v in kw.items():
+        assert hasattr(c, k) and k not in ("struct_size", "reserved"), k
+        setattr(c, k, int(v))
+    return c
+
+
+def _endpoint_cfg_ptr(cfg):
+    if cfg is None:
+        return None
+    return C.byref(cfg if isinstance(cfg, N.PfEndpointConfig) else endpoint_config(**cfg))
+
+
+def endpoint_state() -> np.ndarray:
+    """A fresh stream's state block of the streaming endpoint detector: PF_ENDPOINT_STATE_INTS zeros."""
+    return np.zeros(N.PF_ENDPOINT_STATE_INTS, np.int32)
+
+
+def host_endpoint_update(state, levels, flush=False, n_mels=80, cfg=None, lfr_n=6, cap=None):
+    """The streaming endpoint detector for ONE stream in host code (pf_host_endpoint_update): `levels` (int32, any count, may be
+    empty) and then the flush.  state [PF_ENDPOINT_STATE_INTS] int32 is updated in place.  Returns (events [n, 3] = (begin, end,
+    kind) frames, in_speech, open_begin).  cap: the capacity handed over (default: what always suffices); too small raises
+    PfError(PF_ERR_CAPACITY) whose .n is the count and .events the first cap events."""
+    assert isinstance(state, np.ndarray) and state.dtype == np.int32 and state.shape == (N.PF_ENDPOINT_STATE_INTS,) and state.flags.c_contiguous
+    e = np.ascontiguousarray(levels, dtype=np.int32).reshape(-1)
+    cap = e.size + 1 if cap is None else cap                     # a frame gives at most one event, the flush one more
+    ev = np.full((max(cap, 1), 3), -7, np.int32)
+    n, ins, ob =C.c_int32(), C.c_int32(), C.c_int32()
+    rc = N.load().pf_host_endpoint_update(_i32p(state), _i32p(e), e.size, int(bool(flush)), int(n_mels), int(lfr_n), _endpoint_cfg_ptr(cfg),
+                                          _i32p(ev), int(cap), n, ins, ob)
+    if rc < 0:
+        try:
+            N.check(rc)
+        except N.PfError as ex:
+            ex.n, ex.events = n.value, ev[: min(n.value, cap)].copy()
+            raise
+    return ev[: n.value].copy(), ins.value, ob.value
+
+
 def vad_model_config(**kw) -> "N.PfVadConfig":
     """pf_vad_config with the defaults that go with the model score (pf_vad_model_config: floor_pct = -1, abs_level = 9830,
     stated and not tuned), fields overridden by keyword."""
@@ -1433,6 +1475,37 @@ class Engine:
                 ex.n, ex.seg = n[:B].copy(), seg[:B].copy()
                 raise
         return [seg[b, : n[b]].copy() for b in range(B)]
+
+    def op_endpoint_update(self, states, levels_list, flush=None, n_mels=80, cfg=None, cap=None, ld=None):
+        """The streaming endpoint kernel on caller state blocks and levels (pf_op_endpoint_update): ONE launch over all the
+        streams.  states [B, PF_ENDPOINT_STATE_INTS] int32, updated in place; levels_list: each stream's new levels (any
+        lengths, may be empty); flush: per-stream flags.  Returns (events per stream [n, 3], in_speech [B], open_begin [B]).
+        cap: the capacity handed over (default: what always suffices); too small raises PfError(PF_ERR_CAPACITY) whose .n is
+        n_events [B] and .events the [B, cap, 3] block."""
+        arrs = [np.ascontiguousarray(a, dtype=np.int32).reshape(-1) for a in levels_list]
+        B = len(arrs)
+        assert isinstance(states, np.ndarray) and states.dtype == np.int32 and states.flags.c_contiguous
+        assert states.shape == (B, N.PF_ENDPOINT_STATE_INTS)
+        ld = max([a.size for a in arrs] + [1]) if ld is None else ld
+        lev = np.full((max(B, 1), ld), 0x7FFFFFFF, np.int32)      # past n_new[b]: values that would change every answer if read
+        for b, a in enumerate(arrs):
+            lev[b, : min(a.size, ld)] = a[:ld]                    # (an ld below a stream's count is for the entry point to refuse)
+        n_new = np.ascontiguousarray([a.size for a in arrs] + [0] * (B == 0), dtype=np.int32)
+        fl =np.zeros(max(B, 1), np.int32)
+        if flush is not None:
+            fl[:B] = np.asarray(flush, dtype=bool).astype(np.int32)
+        cap = ld + 1 if cap is None else cap
+        ev = np.full((max(B, 1), max(cap, 1), 3), -7, np.int32)
+        n, ins, ob = np.zeros(max(B, 1), np.int32), np.zeros(max(B, 1), np.int32), np.zeros(max(B, 1), np.int32)
+        rc = self._lib.pf_op_endpoint_update(self._h, _i32p(states), _i32p(lev), _i32p(n_new), _i32p(fl), B, ld, int(n_mels),
+                                             _endpoint_cfg_ptr(cfg), _i32p(ev), int(cap), _i32p(n), _i32p(ins), _i32p(ob))
+        if rc < 0:
+            try:
+                N.check(rc)
+            except N.PfError as ex:
+                ex.n, ex.events = n[:B].copy(), ev[:B].copy()
+                raise
+        return [ev[b, : n[b]].copy() for b in range(B)], ins[:B].copy(), ob[:B].copy()
 
     def vad_segment(self, samples_list, cfg=None, cap=None):
         """Voice-activity segmentation of whole streams on the device (pf_vad_segment): upload, the one batched fbank

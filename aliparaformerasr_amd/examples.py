@@ -2,7 +2,7 @@
 
     python -m aliparaformerasr_amd.examples -type offline -method batch -base <dir> -model <name> \
         [-accuracy int8] [-threads 2] [-decode ctc|frames] [-intake host|device] [-nbest N [-topk K] [-beam W | -search W] [-hotboost S] [-lm FILE [-lmweight A] [-lmbonus B] [-lmeos]]] [-align FILE|beam] [-vad [key=value,...] [-vadmodel FILE] [-spk FILE [key=value,...]]] [-punc FILE] -files a.wav b.wav
-    python -m aliparaformerasr_amd.examples -type online -method one -base <dir> -model <name> -files a.wav
+    python -m aliparaformerasr_amd.examples -type online -method one -base <dir> -model <name> [-endpoint [key=value,...] [-secondpass <offline name>]] -files a.wav
 
 Mirrors (file:line in /root/reference/AliParaformerAsr.Examples):
   * argument handling and defaults — Program.cs:93-104, ParseArgs :197-252: the MANYSPEECH_BASE / _TYPE / _BATCH / _MODEL /
@@ -57,7 +57,14 @@ network and the thresholds are stated, not validated on a real model.
 cttransformer; under each result goes a `punctuated: ...` line and one `  [begin-end ms] sentence` line per sentence (without the
 times when the result has no timestamp per word).  Rules and dimensions are stated, not validated on a real model.
 `-align beam` (with `-nbest N -beam W`) aligns the beam search's labelings instead: under each `nbest[i]` line goes
-`align[i] loglik:<...> pairs:[begin,end],...`."""
+`align[i] loglik:<...> pairs:[begin,end],...`.
+`-endpoint [key=value,...]` (online; OnlineRecognizer.SetEndpoint) finds sentence ends while the file streams: above the partial
+text of a chunk goes one `[begin-end ms] text` line per sentence that closed in it, the partial text is that of the open sentence,
+and after the last chunk the input is declared finished (OnlineStream.InputFinished), which decodes the tail and closes what is
+open.  Keys: the pf_endpoint_config fields (rise, margin_q, abs_level, window, on_count, off_count, pad_begin, pad_end,
+end_silence, min_speech, max_len); the defaults are unvalidated on real speech.
+`-secondpass NAME` (with `-endpoint`; OnlineRecognizer.SetSecondPass) re-recognises every finished sentence with the OFFLINE model
+in directory NAME under -base (its files chosen as `-type offline` chooses them): the sentence lines then carry its text."""
 from __future__ import annotations
 
 import ctypes as C
@@ -207,6 +214,27 @@ def parse_vad_option(text: str) -> dict:
             out[k] = iv
         else:
             raise ValueError("Unknown -vad key: %s" % k)
+    return out
+
+
+ENDPOINT_KEYS = ("rise", "margin_q", "abs_level", "window", "on_count", "off_count", "pad_begin", "pad_end", "end_silence", "min_speech",
+                 "max_len")
+
+
+def parse_endpoint_option(text: str) -> dict:
+    """`key=value,...` of -endpoint -> {pf_endpoint_config fields}"""
+    out = {}
+    for item in [x for x in text.split(",") if x]:
+        k, eq, v = item.partition("=")
+        k = k.strip()
+        if not eq:
+            raise ValueError("-endpoint takes key=value pairs: %r" % item)
+        if k not in ENDPOINT_KEYS:
+            raise ValueError("Unknown -endpoint key: %s" % k)
+        try:
+            out[k] = int(v)
+        except ValueError:
+            raise ValueError("The -endpoint value of %s must be an integer" % k)
     return out
 
 
@@ -404,7 +432,7 @@ def get_file_chunk_samples(path: str, chunk: int = 160 * 6 * 10):
 
 
 def online_recognizer(method="one", model="speech_paraformer-large_asr_nat-zh-cn-16k-common-vocab8404-online-onnx",
-                      accuracy="int8", threads=2, files=None, base=None, out=sys.stdout):
+                      accuracy="int8", threads=2, files=None, base=None, out=sys.stdout, endpoint=None, secondpass=None):
     from .online_recognizer import OnlineRecognizer
     base = base or os.getcwd()
     if not model:
@@ -421,6 +449,21 @@ def online_recognizer(method="one", model="speech_paraformer-large_asr_nat-zh-cn
         print("Error occurred: %s" % ex, file=out)
         print("Init models failure!", file=out)
         return None
+    second = None
+    if endpoint is not None:
+        try:
+            rec.SetEndpoint(**endpoint)
+            if secondpass:                                  # the offline model's directory under -base, chosen as -type offline does
+                from .offline_recognizer import OfflineRecognizer
+                osel = select_model_files(base, secondpass, accuracy)
+                if osel is None:
+                    raise ValueError("no offline model in %s" % secondpass)
+                second = OfflineRecognizer(threadsNum=threads, **osel)
+                rec.SetSecondPass(second)
+        except Exception as ex:
+            print("Error occurred: %s" % ex, file=out)
+            print("Init models failure!", file=out)
+            return None
     print("init_models_elapsed_milliseconds:%s" % ((time.perf_counter() - t0) * 1e3), file=out)
     t0 = time.perf_counter()                                # :126: the window opens before the files are read
     if not files:
@@ -448,12 +491,28 @@ def online_recognizer(method="one", model="speech_paraformer-large_asr_nat-zh-cn
     if method == "one":                                     # :176-194 (the only method the reference runs)
         for chunks in samples_list:
             st = rec.CreateOnlineStream()
-            for c in chunks:
-                st.AddSamples(c)
+            shown = 0
+
+            def step():
+                nonlocal shown
                 r = rec.GetResult(st)
+                if endpoint is not None:                    # a line per sentence that closed in this call, then the open one's text
+                    sens = st.Sentences
+                    for sen in sens[shown:]:
+                        print("[%d-%d ms] %s" % (sen.begin_ms, sen.end_ms, sen.text), file=out)
+                    shown = len(sens)
                 print(r.Text, file=out)
                 texts.append(r.Text)
+            for c in chunks:
+                st.AddSamples(c)
+                step()
+            if endpoint is not None:
+                st.InputFinished()
+                for _ in range(3):                          # the padded tail, then the flush
+                    step()
     rec.Dispose()
+    if second is not None:
+        second.Dispose()
     elapsed = (time.perf_counter() - t0) * 1e3
     print("elapsed_milliseconds:%s" % elapsed, file=out)
     print("total_duration:%s" % total_ms, file=out)
@@ -537,6 +596,17 @@ def parse_args(argv, env=None):
                 i += 1
                 text = argv[i]
             cfg["vad"] = parse_vad_option(text)
+        elif a == "-endpoint":
+            text = ""
+            if i + 1 < len(argv) and not argv[i + 1].startswith("-") and "=" in argv[i + 1]:
+                i += 1
+                text = argv[i]
+            cfg["endpoint"] = parse_endpoint_option(text)
+        elif a == "-secondpass":
+            i += 1
+            if i >= len(argv) or argv[i].startswith("-"):
+                raise ValueError("-secondpass takes the offline model's directory name")
+            cfg["secondpass"] = argv[i]
         elif a == "-vadmodel":
             i += 1
             if i >= len(argv) or argv[i].startswith("-"):
@@ -596,6 +666,10 @@ def parse_args(argv, env=None):
         raise ValueError("-vad is an offline option")
     if "vad" in cfg and ("nbest" in cfg or "align" in cfg):
         raise ValueError("-vad does not go with -nbest or -align")
+    if "endpoint" in cfg and cfg["recognizerType"] != "online":
+        raise ValueError("-endpoint is an online option")
+    if "secondpass" in cfg and "endpoint" not in cfg:
+        raise ValueError("-secondpass goes with -endpoint")
     if "punc" in cfg and cfg["recognizerType"] != "offline":
         raise ValueError("-punc is an offline option")
     if "spk" in cfg and "vad" not in cfg:
@@ -617,7 +691,7 @@ def main(argv=None):
     # Program.cs:290-308
     if cfg["recognizerType"] == "online":
         online_recognizer(cfg["methodType"], cfg["modelName"], cfg["modelAccuracy"], cfg["threads"], cfg["files"],
-                          cfg["modelBasePath"] or None)
+                          cfg["modelBasePath"] or None, endpoint=cfg.get("endpoint"), secondpass=cfg.get("secondpass"))
     elif cfg["recognizerType"] == "offline":
         offline_recognizer(cfg["methodType"], cfg["modelName"], cfg["modelAccuracy"], cfg["threads"], cfg["files"],
                            cfg["modelBasePath"] or None, decode=cfg.get("decode", "frames"), intake=cfg.get("intake", "host"),

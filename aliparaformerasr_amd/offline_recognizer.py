@@ -434,7 +434,7 @@ class OfflineStream:
 
     def __del__(self):
         try:
-            if getattr(self, "_h", None):
+            if getattr(self, "_h", None) and getattr(self, "_borrowed", None) is None:
                 self._lib.pf_stream_free(self._h)
                 self._h = None
         except Exception:

@@ -16,9 +16,55 @@ class OnlineRecognizerResultEntity:
         self.Text = text
 
 
+class OnlineSentence:
+    """A sentence the endpoint detector has closed (OnlineRecognizer.SetEndpoint): [begin_ms, end_ms) in the caller's audio,
+    kind ("silence", "forced" or "flush"), first_pass (the online model's text at the closing chunk), text (the second pass's
+    text; first_pass without one) and result: the offline stream that produced it — Tokens, Timestamps (relative to begin_ms),
+    Scores, alternatives, punctuation, whatever the offline recognizer has set — or None without a second pass."""
+    KINDS = {N.PF_ENDPOINT_SILENCE: "silence", N.PF_ENDPOINT_FORCED: "forced", N.PF_ENDPOINT_FLUSH: "flush"}
+
+    def __init__(self, begin_ms, end_ms, kind, first_pass, text, result):
+        self.begin_ms, self.end_ms, self.kind, self.first_pass, self.text, self.result = begin_ms, end_ms, kind, first_pass, text, result
+
+    def __repr__(self):
+        return "OnlineSentence(%d, %d, %r, %r)" % (self.begin_ms, self.end_ms, self.kind, self.text)
+
+
 class OnlineStream:
     def __init__(self, lib, handle, recognizer):
         self._lib, self._h, self._recognizer = lib, handle, recognizer
+
+    def InputFinished(self) -> None:
+        """No more audio follows: the cached samples go through the front-end (the last ones zero-padded to one chunk, so the
+        online model decodes the tail too) and the GetResults that has decoded the last chunk flushes the endpoint detector.
+        A later AddSamples raises."""
+        _ck(self._lib.pf_online_stream_input_finished(self._h))
+
+    @property
+    def Sentences(self) -> List[OnlineSentence]:
+        """The sentences closed so far (empty without SetEndpoint), in time order."""
+        from .offline_recognizer import OfflineStream
+        n = C.c_int32()
+        _ck(self._lib.pf_online_stream_num_sentences(self._h, n))
+        out = []
+        for j in range(n.value):
+            b, e, k, fp, tx, h = C.c_int32(), C.c_int32(), C.c_int32(), C.c_char_p(), C.c_char_p(), C.c_void_p()
+            _ck(self._lib.pf_online_stream_sentence(self._h, j, b, e, k, C.byref(fp), C.byref(tx)))
+            _ck(self._lib.pf_online_stream_sentence_result(self._h, j, C.byref(h)))
+            res = None
+            if h.value:
+                res = OfflineStream(_lib=self._lib, _handle=h, _recognizer=None)
+                res._borrowed = self                     # the handle belongs to this stream: never freed by the view
+            out.append(OnlineSentence(b.value, e.value, OnlineSentence.KINDS.get(k.value, k.value), (fp.value or b"").decode("utf-8"),
+                                      (tx.value or b"").decode("utf-8"), res))
+        return out
+
+    @property
+    def InSpeech(self):
+        """(a sentence is open, its begin in ms or -1) as of the last GetResults."""
+        a, b = C.c_int32(), C.c_int32()
+        _ck(self._lib.pf_online_stream_in_speech(self._h, a, b))
+        return bool(a.value), b.value
 
     def AddSamples(self, samples) -> None:
         if samples is None:
@@ -60,6 +106,25 @@ class OnlineRecognizer:
         s = C.c_void_p()
         _ck(self._lib.pf_online_create_stream(self._h, C.byref(s)))
         return OnlineStream(self._lib, s, self)
+
+    def SetEndpoint(self, enabled=True, **keys) -> None:
+        """Endpoint detection for every GetResults that follows (off by default; SetEndpoint(False) turns it off again and
+        leaves every path as it is without it): a causal voice-activity detector on the device closes sentences —
+        stream.Sentences, stream.InSpeech — and resets the stream's decoder context at each; GetResults keeps returning the text
+        of the open sentence.  keys: pf_endpoint_config fields (rise, margin_q, abs_level, window, on_count, off_count, pad_begin,
+        pad_end, end_silence, min_speech, max_len).  The defaults are stated, not tuned: nobody has measured them on real speech."""
+        if enabled is None or enabled is False:
+            _ck(self._lib.pf_online_recognizer_set_endpoint(self._h, None))
+            return
+        from .engine import endpoint_config
+        c = enabled if isinstance(enabled, N.PfEndpointConfig) else endpoint_config(**keys)
+        _ck(self._lib.pf_online_recognizer_set_endpoint(self._h, C.byref(c)))
+
+    def SetSecondPass(self, offline) -> None:
+        """The OfflineRecognizer that re-recognises every finished sentence (None: none): the sentences that close in one
+        GetResults go through ONE GetResults of it, one plain stream each.  Refused for a recognizer with SetVad on."""
+        _ck(self._lib.pf_online_recognizer_set_second_pass(self._h, None if offline is None else offline._h))
+        self._second = offline                           # keeps it alive
 
     def GetResult(self, stream: OnlineStream) -> OnlineRecognizerResultEntity:
         return self.GetResults([stream])[0]

@@ -23,6 +23,16 @@ namespace AliParaformerAsr.Hip
         [DllImport(Lib)] internal static extern int pf_online_stream_add_samples(IntPtr s, float[] samples, long n);
         [DllImport(Lib)] internal static extern int pf_online_get_results(IntPtr r, IntPtr[] streams, int nStreams);
         [DllImport(Lib)] internal static extern int pf_online_result_text(IntPtr r, int i, out IntPtr utf8);
+        // streaming endpointing and the second pass (paraformer_hip.h "Streaming endpointing and the second pass")
+        [DllImport(Lib)] internal static extern int pf_online_recognizer_set_endpoint(IntPtr r, ref PfEndpointConfig cfg);
+        [DllImport(Lib)] internal static extern int pf_online_recognizer_set_endpoint(IntPtr r, IntPtr cfgNull);          // IntPtr.Zero: off
+        [DllImport(Lib)] internal static extern int pf_online_recognizer_set_second_pass(IntPtr r, IntPtr offlineRecognizer);
+        [DllImport(Lib)] internal static extern int pf_online_stream_input_finished(IntPtr s);
+        [DllImport(Lib)] internal static extern int pf_online_stream_num_sentences(IntPtr s, out int n);
+        [DllImport(Lib)] internal static extern int pf_online_stream_sentence(IntPtr s, int j, out int beginMs, out int endMs, out int kind,
+            out IntPtr firstPassUtf8, out IntPtr textUtf8);
+        [DllImport(Lib)] internal static extern int pf_online_stream_sentence_result(IntPtr s, int j, out IntPtr offlineStream);
+        [DllImport(Lib)] internal static extern int pf_online_stream_in_speech(IntPtr s, out int inSpeech, out int beginMs);
         [DllImport(Lib)] internal static extern void pf_online_stream_dispose(IntPtr s);
         [DllImport(Lib)] internal static extern void pf_online_stream_free(IntPtr s);
     }
@@ -35,6 +45,15 @@ namespace AliParaformerAsr.Hip
         // OnlineStream.AddSamples: appends audio; the library cuts it into 60-frame chunks and keeps the caches
         public void AddSamples(float[] samples)
             => ParaformerHip.Check(OnlineNative.pf_online_stream_add_samples(Handle, samples, samples == null ? 0 : samples.LongLength));
+
+        // no more audio follows: the tail is decoded, the next GetResults flushes the endpoint detector
+        public void InputFinished() => ParaformerHip.Check(OnlineNative.pf_online_stream_input_finished(Handle));
+
+        // the sentences the endpoint detector has closed so far
+        public int NumSentences
+        {
+            get { ParaformerHip.Check(OnlineNative.pf_online_stream_num_sentences(Handle, out int n)); return n; }
+        }
 
         public void Dispose()
         {
@@ -81,6 +100,19 @@ namespace AliParaformerAsr.Hip
             }
             return res;
         }
+
+        // Endpoint detection for every GetResults that follows (no counterpart in the reference; null: off).  The defaults
+        // (pf_endpoint_default) are stated, not tuned: nobody has measured them on real speech.
+        public void SetEndpoint(PfEndpointConfig? cfg)
+        {
+            if (cfg == null) { ParaformerHip.Check(OnlineNative.pf_online_recognizer_set_endpoint(_h, IntPtr.Zero)); return; }
+            PfEndpointConfig c = cfg.Value;
+            ParaformerHip.Check(OnlineNative.pf_online_recognizer_set_endpoint(_h, ref c));
+        }
+
+        // the offline recognizer's native handle that re-recognises every finished sentence (IntPtr.Zero: none)
+        public void SetSecondPass(IntPtr offlineRecognizerHandle)
+            => ParaformerHip.Check(OnlineNative.pf_online_recognizer_set_second_pass(_h, offlineRecognizerHandle));
 
         public void Dispose()                                                                      // :533
         {

@@ -52,6 +52,15 @@ namespace AliParaformerAsr.Native
                    split_search, reserved0, reserved1, reserved2, reserved3;
     }
 
+    /// <summary>pf_endpoint_config: the streaming endpoint detector's configuration (paraformer_hip.h "Voice-activity endpointing,
+    /// streaming"); pf_endpoint_default fills in the stated defaults, which nobody has validated on real speech.</summary>
+    [StructLayout(LayoutKind.Sequential)]
+    public struct PfEndpointConfig
+    {
+        public int struct_size, rise, margin_q, abs_level, window, on_count, off_count, pad_begin, pad_end, end_silence, min_speech,
+                   max_len, reserved0, reserved1, reserved2, reserved3;
+    }
+
     /// <summary>pf_spk_config: the speaker labels' configuration (paraformer_hip.h "Speaker labels"); pf_spk_default fills in the
     /// stated defaults, which nobody has validated on real speech.</summary>
     [StructLayout(LayoutKind.Sequential)]
@@ -269,6 +278,7 @@ namespace AliParaformerAsr.Native
         [DllImport(Lib)] internal static extern int pf_stream_alternative_timestamps(IntPtr s, int i, out IntPtr beginEnd, out int n, out double loglik);
         // long-audio recognition: voice-activity segmentation on the device, batches of similar length, one result per stream
         [DllImport(Lib)] internal static extern int pf_vad_default(out PfVadConfig cfg);
+        [DllImport(Lib)] internal static extern int pf_endpoint_default(out PfEndpointConfig cfg);
         // the FSMN-VAD model score (a .pfw of kind "fsmnvad"): the loader, what it read, the defaults that go with it, the attach calls
         [DllImport(Lib)] internal static extern int pf_vad_model_load([MarshalAs(UnmanagedType.LPUTF8Str)] string path, out IntPtr m);
         [DllImport(Lib)] internal static extern int pf_vad_model_from_memory(byte[] data, long nbytes, out IntPtr m);

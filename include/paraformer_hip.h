@@ -608,6 +608,82 @@ int pf_host_vad_segments(const int32_t* levels, int32_t T, int32_t n_mels, int32
 int pf_host_long_plan(const int32_t* len, int32_t n, int32_t batch_max, int64_t frame_budget, int32_t* batch, int32_t* row,
                       int32_t* n_batches);
 
+/* ---- Voice-activity endpointing, streaming (additions to ABI 6; nothing is launched or allocated unless one of these is
+   called) ----
+   The detector above made causal, for audio that is still coming in: it says where a sentence ends while the stream runs
+   (csrc/k_endpoint.hip).  The one non-causal step (the percentile floor) is replaced by a tracked floor, the padding step
+   becomes events.  Every value past the clamp of step 1 is an integer: the device form, the host form
+   (pf_host_endpoint_update) and the definition in numpy (tests/endpoint_ref.py) agree exactly, the state block included.
+   THE DEFAULTS ARE STATED, NOT TUNED: there is no speech corpus here, and nobody has measured them on real speech.
+   Frames v = 0, 1, ... are the 10 ms fbank rows of the caller's audio; frame v covers the caller's samples from 160 v.
+   1  level       e[v]: step 1 above (int32).
+   2' floor       F[v] = min(e[v], F[v-1] + rise), F[-1] = +inf (so F[0] = e[0]), in int64: a floor that follows a falling
+                  level at once and a rising one at `rise` per frame.  thr[v] = max(F[v] + margin_q * n_mels, abs_level);
+                  raw[v] = e[v] > thr[v].  rise = -1: no floor, thr = abs_level.  The floor does not look at the state: one
+                  frozen during speech would be a serial feedback loop.  The default rise keeps rise * max_len <
+                  margin_q * n_mels (6000 < 7680): a sentence that starts at the floor cannot lose its own speech to the
+                  rising floor before the forced cut.
+   3  hysteresis  step 3 above word for word (window, on_count, off_count, state[-1] = 0); it is causal as it stands.
+   4' events      A state run is a maximal [s0, s1) of state 1.  The first state-1 frame s0 met while no sentence is open opens
+                  one at b = max(prev_end, s0 - pad_begin); prev_end is the end of the last emitted sentence, 0 at first.  A
+                  run that starts while a sentence is open continues it.  At frame t = s1 - 1 + end_silence, if no state-1
+                  frame came in between, the sentence closes with e = s1 + pad_end (pad_end <= end_silence, so e <= t + 1).
+                  e - b < min_speech: it is dropped, no event, prev_end does not move.  Otherwise the event
+                  (b, e, PF_ENDPOINT_SILENCE) and prev_end = e.
+   5' forced cut  after step 4' of frame t, an open sentence with t + 1 - b == max_len gives (b, t + 1, PF_ENDPOINT_FORCED) and
+                  prev_end = t + 1.  With state[t] = 1 it stays open (so b = t + 1; its rest falls under min_speech like any
+                  sentence), otherwise it is closed.  There is no search for the quietest frame: that would need a level
+                  history in the state, and a forced cut is the exception.
+   6  flush       the input ends after T frames: an open sentence closes with e = min(T, s1 + pad_end) (T while the state is
+                  1), kind PF_ENDPOINT_FLUSH, under the min_speech rule.  Frames after a flush: PF_ERR_INVALID_ARG (a second
+                  flush without frames is a no-op).
+   7  status      in_speech = a sentence is open; open_begin = its b (-1 when none).
+   Event [b, e) covers the samples [160 b, min(n_samples, 160 e)).
+   The detector's whole memory between calls is the state block: PF_ENDPOINT_STATE_INTS int32 words, all zero for a fresh stream,
+   read and written alike by the host form and the kernel (a stream may change form between any two calls):
+     0 .. 7   the raw bits of the previous 256 frames as a 256-bit little-endian number: bit 255 - k is frame count - 1 - k
+     8        state of the last frame          9   the last state-1 frame + 1 (0: none)
+     10       the first state-1 frame of the open sentence + 1 (0: none open; its b is max(prev_end, that frame - pad_begin))
+     11       prev_end                         12  count, the frames seen
+     13, 14   F[count - 1] as an int64, low word first (written once count > 0 and rise >= 0)
+     15       flushed
+   PF_ERR_INVALID_ARG unless  -1 <= rise <= 1 << 20,  the window constraints above,  0 <= pad_begin <= 1024,
+   0 <= pad_end <= end_silence <= 1 << 16,  end_silence >= 1 (a run's end shows only at the first state-0 frame),
+   min_speech >= 2 * lfr_n,  min_speech <= max_len <= PF_VAD_MAX_FRAMES,  pad_begin < max_len (a sentence is no longer than
+   max_len at the frame that opens it); also for a state block no sequence of calls leaves behind (a word outside its range:
+   counts and frames in [0, count], flags 0 or 1, the floor inside int32).
+   PF_ERR_CAPACITY: count + n_new above PF_ENDPOINT_MAX_STREAM_FRAMES (nothing is changed), or more events than the caller's
+   cap: the counts are filled in first, the first cap events are written and the state block HAS advanced. */
+#define PF_ENDPOINT_STATE_INTS 16
+#define PF_ENDPOINT_MAX_STREAM_FRAMES (1 << 30)
+#define PF_ENDPOINT_SILENCE 1
+#define PF_ENDPOINT_FORCED 2
+#define PF_ENDPOINT_FLUSH 3
+typedef struct pf_endpoint_config {
+  int32_t struct_size;        /* = sizeof(pf_endpoint_config)                                              */
+  int32_t rise;               /* 2: the floor follows a rising level by this much per frame; -1 = no floor */
+  int32_t margin_q;           /* 96: speech is this far above the floor, in 1/64 log units per mel bin     */
+  int32_t abs_level;          /* INT32_MIN: a lower bound of the threshold                                 */
+  int32_t window;             /* 20 frames                                                                 */
+  int32_t on_count;           /* 15                                                                        */
+  int32_t off_count;          /* 15                                                                        */
+  int32_t pad_begin;          /* 30 frames kept in front of speech                                         */
+  int32_t pad_end;            /* 5 frames kept behind it                                                   */
+  int32_t end_silence;        /* 80 frames without speech end a sentence                                   */
+  int32_t min_speech;         /* 50                                                                        */
+  int32_t max_len;            /* 3000: the forced cut                                                      */
+  int32_t reserved[4];
+} pf_endpoint_config;
+/* fills in struct_size and the defaults above */
+int pf_endpoint_default(pf_endpoint_config* cfg);
+/* The host form (plain C++, no device), ONE stream: n_new levels, then the flush if flush != 0.  state
+   [PF_ENDPOINT_STATE_INTS] in / out; events [cap, 3] = (b, e, kind) in order, of which the first min(*n_events, cap) rows are
+   written (NULL with cap 0 is allowed); lfr_n as the engine's front-end has it; cfg == NULL: the defaults.  in_speech /
+   open_begin are optional.  n_new = 0 without a flush changes nothing and reports the status. */
+int pf_host_endpoint_update(int32_t* state, const int32_t* levels, int32_t n_new, int32_t flush, int32_t n_mels, int32_t lfr_n,
+                            const pf_endpoint_config* cfg, int32_t* events, int32_t cap, int32_t* n_events, int32_t* in_speech,
+                            int32_t* open_begin);
+
 /* ---- Voice-activity segmentation, model score (additions to ABI 6; opt-in: with no model attached nothing of this is launched
    or allocated and every result is bit for bit what it is without it) ----
    A second form of step 1: the level of a frame comes from an FSMN-VAD network (the detector FunASR pairs with paraformer and
@@ -891,6 +967,14 @@ int pf_op_vad_levels(pf_engine* e, const float* rows, int64_t T, int32_t n_mels,
    n [B].  PF_ERR_CAPACITY (n filled in, the first cap segments of each row stored) when a row has more than cap segments. */
 int pf_op_vad_segments(pf_engine* e, const int32_t* levels, const int32_t* T, int32_t B, int32_t ld, int32_t n_mels,
                        const pf_vad_config* cfg, int32_t* seg, int32_t cap, int32_t* n);
+/* exactly the streaming endpoint kernel (k_endpoint.hip, steps 2' - 7 of "Voice-activity endpointing, streaming") on caller
+   levels, B streams in ONE launch: states [B, PF_ENDPOINT_STATE_INTS] in / out, levels [B, ld] int32 of which stream b's first
+   n_new[b] (0 <= n_new[b] <= ld) are its new frames, flush [B] (NULL: none), cfg (NULL: the defaults; min_speech is checked
+   against the engine's lfr_n); events [B, cap, 3] of which the first min(n_events[b], cap) rows of a stream are written,
+   n_events / in_speech / open_begin [B].  Errors as pf_host_endpoint_update; on an argument error nothing is launched. */
+int pf_op_endpoint_update(pf_engine* e, int32_t* states, const int32_t* levels, const int32_t* n_new, const int32_t* flush,
+                          int32_t B, int32_t ld, int32_t n_mels, const pf_endpoint_config* cfg, int32_t* events, int32_t cap,
+                          int32_t* n_events, int32_t* in_speech, int32_t* open_begin);
 /* exactly the attached model's launches (k_vadnet.hip; PF_ERR_INVALID_ARG without pf_engine_set_vad_model) on caller rows: the
    concatenated frames of B utterances, T [B] frames each, rows [sum T, n_mels] fp32; out [sum T, output_dim] fp32 logits /
    out [sum T] int32 levels.  An utterance's result does not depend on its batch mates. */
@@ -1437,7 +1521,9 @@ int pf_recognizer_set_align(pf_recognizer* r, int32_t on);
    fails the call as PF_ERR_UNSUPPORTED inside Forward's try block ("Offline recognition failed: ...", PF_ERR_RECOGNITION).
    Allowed beside it: PF_DECODE_SCORES, PF_DECODE_CTC, timestamp models, SeACo hot words (the union of the call's
    stream.Hotwords goes to every batch).  PF_ERR_UNSUPPORTED beside it, whichever is set second: pf_recognizer_set_nbest,
-   pf_recognizer_set_ctc_beam, pf_recognizer_set_align.  pf_group_* and the streaming classes have no such switch.
+   pf_recognizer_set_ctc_beam, pf_recognizer_set_align.  pf_group_* and the streaming classes have no such switch (the streaming
+   classes find sentence ends with "Streaming endpointing and the second pass" instead, and may hand each sentence to a recognizer
+   WITHOUT this switch).
    PF_ERR_INVALID_ARG as for pf_vad_config; PF_ERR_UNSUPPORTED for a snip_edges = true front-end. */
 int pf_recognizer_set_vad(pf_recognizer* r, const pf_vad_config* cfg, int32_t batch_max, int64_t frame_budget, const char* sep_utf8);
 /* The FSMN-VAD model score for long-audio recognition (see "Voice-activity segmentation, model score"): pfw_path = a `.pfw` of
@@ -1570,6 +1656,36 @@ int pf_online_result_text(pf_online_recognizer* r, int32_t i, const char** utf8)
 int pf_online_stream_tokens(pf_online_stream* s, const int64_t** ids, int32_t* n);
 void pf_online_stream_dispose(pf_online_stream* s);
 void pf_online_stream_free(pf_online_stream* s);
+/* ---- Streaming endpointing and the second pass (additions to ABI 6; opt-in: without pf_online_recognizer_set_endpoint nothing
+   of this is launched or allocated and every streaming result is bit for bit what it is without it) ----
+   The detector of "Voice-activity endpointing, streaming" runs inside pf_online_get_results over the fbank rows of the CALLER's
+   audio (9600 samples at a time, as AddSamples hands them on; not the chunk of silence the constructor queues, not the repeated
+   first frame): one launch set for all the call's streams that have new frames — rows gathered, one upload, the level launch,
+   the endpoint launch, one read-back.  The state blocks live in one device buffer of the recognizer.
+   An event closes a sentence, at chunk granularity: its first-pass text is the online model's text after the ids of this
+   call's chunk were appended; the stream's decoder context is then reset (Tokens cleared, FSMN caches zeroed, the CIF carry
+   and the feature cache back to their initial values, the position index 0) while the fbank rows and the LFR splice cache
+   stay: the audio is continuous.  At a forced cut a token may straddle the cut.  pf_online_result_text keeps returning the text
+   of the OPEN sentence: the tokens since the last reset.
+   Second pass: the sentences that closed in one call, pooled over its streams in the call's stream order and then in time order,
+   each become one plain offline stream holding the caller's samples [160 b, min(n_samples, 160 e)) and go through ONE GetResults
+   of the attached offline recognizer (the batch is part of the definition: quirk Q2).  text is that result; without a second
+   pass text equals first_pass.  What the offline recognizer has set (punctuation, n-best, timestamps) simply applies;
+   PF_ERR_UNSUPPORTED for one with pf_recognizer_set_vad on.  The offline recognizer must outlive its use here.
+   pf_online_stream_input_finished: the cached samples go through the front-end, the last ones zero-padded to one chunk, so the
+   online model decodes the tail too; the pf_online_get_results that has decoded the last chunk flushes the detector (frames:
+   ceil(n_samples / 160)).  A later pf_online_stream_add_samples: PF_ERR_INVALID_ARG.
+   Times are milliseconds in the caller's audio.  pf_online_stream_sentence_result: the offline stream that produced sentence j
+   (borrowed: valid until the online stream is freed; NULL without a second pass) — every pf_stream_* getter works on it, times
+   inside it are relative to begin_ms. */
+int pf_online_recognizer_set_endpoint(pf_online_recognizer* r, const pf_endpoint_config* cfg);   /* NULL = off */
+int pf_online_recognizer_set_second_pass(pf_online_recognizer* r, pf_recognizer* offline);      /* NULL = none */
+int pf_online_stream_input_finished(pf_online_stream* s);
+int pf_online_stream_num_sentences(pf_online_stream* s, int32_t* n);
+int pf_online_stream_sentence(pf_online_stream* s, int32_t j, int32_t* begin_ms, int32_t* end_ms, int32_t* kind,
+                              const char** first_pass_utf8, const char** text_utf8);
+int pf_online_stream_sentence_result(pf_online_stream* s, int32_t j, pf_stream** offline_stream);
+int pf_online_stream_in_speech(pf_online_stream* s, int32_t* in_speech, int32_t* begin_ms);
 /* Device seams = the two InferenceSession.Run calls (OnlineRecognizer.cs:83, :296).
    encoder: speech [B,Tc,560] (scaled + position-encoded by the caller) -> enc [B,Tc,512], alphas [B,Tc].
    decoder: enc, acoustic_embeds [B,L,512] + lengths, in_cache [n_caches][B,512,10] -> log-probs [B,L,V] (optional),
