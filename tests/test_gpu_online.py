@@ -14,7 +14,10 @@ Tc = 5 (the un-fused sequence below 8 frames), 8 and 20 and with more rows than 
 the tolerances, every cache is checked for its exact structure: the columns that come from the old cache are its bits
 shifted by L, the masked positions are +0.  The inputs stand in tests/rows_ref.py; tests/test_rows_ref_cpu.py shows on the
 oracle alone that with them a cache rotated by one column, a mask one position late and a cache taken before masking each
-move a compared quantity by at least ten tolerances (90 to 600 at the chosen seeds and cache gain 1)."""
+move a compared quantity by at least ten tolerances (90 to 600 at the chosen seeds and cache gain 1).
+
+The exact tests of the whole path are in tests/test_gpu_online_lockstep.py: every id of every stream after every GetResults against
+tests/online_lockstep_ref.py, and byte-exact stream isolation at the two seams."""
 import numpy as np
 import pytest
 

@@ -15,6 +15,7 @@ import pytest
 
 import endpoint_ref as R
 import vad_ref as V
+from online_lockstep_ref import reset as _reset
 from aliparaformerasr_amd import _native as N
 from aliparaformerasr_amd import weights as W
 from oracle import frontend as fe
@@ -224,17 +225,8 @@ def test_without_a_second_pass_text_is_the_first_pass(models, audio):
     rec.Dispose()
 
 
-def _reset(o, nd):
-    """what a closed sentence resets, on the oracle's stream (oracle/online.py OnlineStream.__init__)"""
-    o.tokens = []
-    o.states = [np.zeros((512, 10), np.float32) for _ in range(nd)]
-    o.cif_hidden = [np.zeros(512, np.float32)]
-    o.cif_alpha = [np.float32(0.0)]
-    o.cache_feats = np.zeros((10, 560), np.float32)
-    o.start_idx = 0
-
-
 def test_reset_in_lockstep_with_the_oracle(models, audio):
+    """(lengths and four ids in five; the exact comparison with the endpoint on: tests/test_gpu_online_lockstep.py)"""
     on, _, cfg, w = models
     rec = _online(models)
     rec.SetEndpoint(end_silence=40)                                    # sentences close inside the first 4.5 s
