@@ -215,6 +215,11 @@ SIGNATURES = {
     "pf_engine_set_vad_model": (C.c_int, [_vp, _vp]),
     "pf_op_vad_model_logits": (C.c_int, [_vp, _f, _i32, C.c_int32, C.c_int32, _f]),
     "pf_op_vad_model_levels": (C.c_int, [_vp, _f, _i32, C.c_int32, C.c_int32, _i32]),
+    "pf_endpoint_model_config": (C.c_int, [_P(PfEndpointConfig)]),
+    "pf_vad_model_stream_state_bytes": (C.c_int, [_vp, _i64]),
+    "pf_host_vad_model_stream_state_bytes": (C.c_int, [_vp, _i64]),
+    "pf_host_vad_model_stream": (C.c_int, [_vp, _vp, _f, C.c_int32, C.c_int32, C.c_int32, _i32, _P(C.c_double), C.c_int32, _i32]),
+    "pf_op_vad_model_stream": (C.c_int, [_vp, _vp, _f, _i32, _i32, C.c_int32, C.c_int32, C.c_int32, _i32, _f, C.c_int32, _i32]),
     "pf_punc_model_load": (C.c_int, [C.c_char_p, _P(_vp)]),
     "pf_punc_model_from_memory": (C.c_int, [_vp, C.c_int64, _P(_vp)]),
     "pf_punc_model_info": (C.c_int, [_vp, _i32, _i64]),
@@ -434,6 +439,7 @@ SIGNATURES = {
     "pf_online_get_results": (C.c_int, [_vp, _P(_vp), C.c_int32]),
     "pf_online_result_text": (C.c_int, [_vp, C.c_int32, _cpp]),
     "pf_online_recognizer_set_endpoint": (C.c_int, [_vp, _P(PfEndpointConfig)]),
+    "pf_online_recognizer_set_endpoint_model": (C.c_int, [_vp, C.c_char_p]),
     "pf_online_recognizer_set_second_pass": (C.c_int, [_vp, _vp]),
     "pf_online_stream_input_finished": (C.c_int, [_vp]),
     "pf_online_stream_num_sentences": (C.c_int, [_vp, _i32]),

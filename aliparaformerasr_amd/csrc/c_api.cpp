@@ -1047,6 +1047,51 @@ int pf_op_vad_model_levels(pf_engine* h, const float* rows, const int32_t* T, in
   return op_vad_model(h, rows, T, B, n_mels, nullptr, out);
 }
 
+// ---- voice-activity endpointing, streaming, model score ----
+int pf_endpoint_model_config(pf_endpoint_config* cfg) {
+  PF_TRY
+  NEED(cfg);
+  *cfg = endpoint_model_default();
+  return PF_OK;
+  PF_CATCH
+}
+int pf_vad_model_stream_state_bytes(const pf_vad_model* m, int64_t* bytes) {
+  PF_TRY
+  NEED(m); NEED(bytes);
+  *bytes = vad_stream_layout(*m->p).bytes;
+  return PF_OK;
+  PF_CATCH
+}
+int pf_host_vad_model_stream_state_bytes(const pf_vad_model* m, int64_t* bytes) {
+  PF_TRY
+  NEED(m); NEED(bytes);
+  *bytes = host_vad_stream_state_bytes(*m->p);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_host_vad_model_stream(const pf_vad_model* m, void* state, const float* rows, int32_t n_new, int32_t flush, int32_t n_mels,
+                             int32_t* levels, double* logits, int32_t cap, int32_t* n_out) {
+  PF_TRY
+  NEED(m); NEED(state); NEED(n_out);
+  PF_CHECK(n_new >= 0 && cap >= 0 && n_mels >= 1 && n_mels <= 1024, PF_ERR_INVALID_ARG, "vad_model_stream: bad shape (n_mels 1 .. 1024)");
+  if (n_new > 0) NEED(rows);
+  *n_out = (int32_t)host_vad_model_stream(*m->p, state, rows, n_new, flush != 0, n_mels, levels, logits, cap);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_op_vad_model_stream(pf_engine* h, void* states, const float* rows, const int32_t* n_new, const int32_t* flush, int32_t B,
+                           int32_t ld, int32_t n_mels, int32_t* levels, float* logits, int32_t cap, int32_t* n_out) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  PF_CHECK(B >= 0 && ld >= 0 && cap >= 0 && n_mels >= 1 && n_mels <= 1024, PF_ERR_INVALID_ARG, "vad_model_stream: bad shape (n_mels 1 .. 1024)");
+  if (B > 0) { NEED(states); NEED(n_new); NEED(n_out); if (ld > 0) NEED(rows); }
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->op_vad_model_stream(states, rows, n_new, flush, B, ld, n_mels, levels, logits, cap, n_out);
+  return PF_OK;
+  PF_CATCH
+}
+
 // ---- speaker labels ----
 int pf_spk_model_load(const char* path, pf_spk_model** m) {
   return new_model_handle(m, path, "path", [&] { return spk_model_load(path); });
@@ -2694,6 +2739,12 @@ void pf_online_stream_dispose(pf_online_stream* h) {
 int pf_online_recognizer_set_endpoint(pf_online_recognizer* h, const pf_endpoint_config* cfg) {
   PF_TRY
   OR(h)->SetEndpoint(cfg);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_online_recognizer_set_endpoint_model(pf_online_recognizer* h, const char* pfw_path) {
+  PF_TRY
+  OR(h)->SetEndpointModel(pfw_path ? pfw_path : "");
   return PF_OK;
   PF_CATCH
 }

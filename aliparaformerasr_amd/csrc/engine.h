@@ -319,8 +319,20 @@ class Engine {
   // at slot[b] (device memory the recognizer owns), rows = their new fbank rows concatenated [sum n_new, n_mels].  ONE upload
   // (n_new | flush | slot | offsets | rows), the level launch over all rows, the endpoint launch (both profile class "endpoint"),
   // ONE read-back: out = n_events [B] | in_speech [B] | open_begin [B] | events [B, cap, 3].  cap >= max n_new + 1 always suffices.
+  // net_states_dev != null (the streaming model score): the attached FSMN-VAD model's stream launch (profile
+  // class "vadnet_stream", ONE launch) takes the place of the level launch, on the state blocks net_states_dev
+  // [*, vad_stream_layout().bytes] at the same slots, and hands its released counts to the endpoint launch as its n_new; a
+  // flush releases the held-back levels in the same launch set.  cap >= max n_new + lfr_m then always suffices.
   void endpoint_streams(int32_t* states_dev, const int32_t* slot, const float* rows, const int32_t* n_new, const int32_t* flush, int B,
-                        const pf_endpoint_config& c, int cap, std::vector<int32_t>& out);
+                        const pf_endpoint_config& c, int cap, std::vector<int32_t>& out, char* net_states_dev = nullptr);
+  // The attached model in streaming form (k_vadnet_stream.hip).  vad_stream_check: PF_ERR_UNSUPPORTED for a model whose two
+  // tiles and history window do not fit the LDS (kernels.h kVadStreamMaxLds).  op_vad_model_stream: ONE launch of class
+  // "vadnet_stream" over B caller streams through op_stage.h (hostile rows behind n_new[b], sentinel-filled outputs, the guard
+  // rule on levels and logits): states [B, state_bytes] in / out, rows [B, ld, n_mels], levels [B, cap] / logits
+  // [B, cap, output_dim] (either may be null), n_out [B].  An argument error launches nothing and changes nothing.
+  static void vad_stream_check(const VadModel& m);
+  void op_vad_model_stream(void* states, const float* rows, const int32_t* n_new, const int32_t* flush, int B, int ld, int n_mels,
+                           int32_t* levels, float* logits, int cap, int32_t* n_out);
   void op_ctc_collapse(const int64_t* ids, const float* scores, const int32_t* lens, int B, int T, int blank, int64_t* ids_out,
                        int32_t* first_out, int32_t* last_out, float* score_out, int cap, int32_t* n_out);
   // ---- streaming seams (OnlineRecognizer.cs EncoderProj / DecoderProj) ------
@@ -696,6 +708,9 @@ class Engine {
                int Tmax, int64_t total, int64_t totalp, char* scratch, float* emb_dev, float* frames_dev);
   static size_t spk_scratch_bytes(const SpkModel& m, int64_t total, int64_t totalp);
   void run_punc(const int32_t* ids, const int64_t* off, const int32_t* last, int B, float* logits, float* x0, int32_t* p, int32_t* cut);
+  void run_vadnet_stream(char* states_dev, const int32_t* slot_dev, const float* rows_dev, const int32_t* off_dev, int64_t ldx,
+                         const int32_t* n_new_dev, const int32_t* flush_dev, int B, float* logits_dev, int32_t* levels_dev, int64_t cap,
+                         int32_t* n_out_dev);
   void run_vadnet(const float* rows_dev, const int64_t* off_dev, int B, int64_t total, int n_mels, float* logits_dev, int32_t* levels_dev);
   float lm_alpha_ = 0.f, lm_beta_ = 0.f;
   int lm_flags_ = 0;

@@ -241,10 +241,11 @@ void Engine::op_endpoint_update(int32_t* states, const int32_t* levels, const in
 }
 
 void Engine::endpoint_streams(int32_t* states_dev, const int32_t* slot, const float* rows, const int32_t* n_new, const int32_t* flush, int B,
-                              const pf_endpoint_config& c, int cap, std::vector<int32_t>& out) {
+                              const pf_endpoint_config& c, int cap, std::vector<int32_t>& out, char* net_states_dev) {
   PF_HIP(hipSetDevice(device_));
   out.clear();
   if (B == 0) return;
+  PF_CHECK(!net_states_dev || vadnet_, PF_ERR_INVALID_ARG, "endpoint_streams: no model is attached");
   const size_t nB = (size_t)B, nm = (size_t)fc_.n_mels;
   const size_t meta_words = (4 * nB + 63) / 64 * 64;            // the rows behind the meta words start on a 256-byte boundary
   std::vector<int32_t> stage(meta_words, 0);
@@ -256,20 +257,33 @@ void Engine::endpoint_streams(int32_t* states_dev, const int32_t* slot, const fl
   stage.resize(meta_words + total * nm);
   if (total) std::memcpy(stage.data() + meta_words, rows, total * nm * 4);
   StageCarve st;
-  const auto d_in = st.take<int32_t>(stage.size() + 4), d_lev = st.take<int32_t>(total + 1), d_out = st.take<int32_t>(3 * nB + nB * cap * 3);
+  // with the model a stream's levels are its released ones: a row of lev_ld = max n_new + right cells per stream
+  const size_t lev_ld = net_states_dev ? (size_t)*std::max_element(n_new, n_new + B) + (size_t)vadnet_->lfr_m : 0;
+  const auto d_in = st.take<int32_t>(stage.size() + 4), d_lev = st.take<int32_t>(net_states_dev ? nB * lev_ld + nB : total + 1),
+             d_out = st.take<int32_t>(3 * nB + nB * cap * 3);
   void* ws = op_ws(st);
   upload(stream_, d_in(ws), (const int32_t*)stage.data(), stage.size());
   const EndpointParams p{c.rise, c.margin_q, c.abs_level, c.window, c.on_count, c.off_count, c.pad_begin, c.pad_end, c.end_silence,
                          c.min_speech, c.max_len, fc_.n_mels};
-  if (total) {
+  if (net_states_dev) {                                          // the released counts sit behind the level rows
+    int32_t* d_rel = d_lev(ws) + nB * lev_ld;
+    run_vadnet_stream(net_states_dev, d_in(ws) + 2 * nB, (const float*)(d_in(ws) + meta_words), d_in(ws) + 3 * nB, 0, d_in(ws), d_in(ws) + nB, B,
+                      nullptr, d_lev(ws), (int64_t)lev_ld, d_rel);
     prof_begin("endpoint", 0);
-    launch_vad_levels(stream_, (const float*)(d_in(ws) + meta_words), (int64_t)total, fc_.n_mels, d_lev(ws));
+    launch_endpoint_update(stream_, states_dev, d_in(ws) + 2 * nB, d_lev(ws), nullptr, (int64_t)lev_ld, d_rel, d_in(ws) + nB, B, p,
+                           d_out(ws) + 3 * nB, cap, d_out(ws), d_out(ws) + nB, d_out(ws) + 2 * nB);
+    prof_end("endpoint");
+  } else {
+    if (total) {
+      prof_begin("endpoint", 0);
+      launch_vad_levels(stream_, (const float*)(d_in(ws) + meta_words), (int64_t)total, fc_.n_mels, d_lev(ws));
+      prof_end("endpoint");
+    }
+    prof_begin("endpoint", 0);
+    launch_endpoint_update(stream_, states_dev, d_in(ws) + 2 * nB, d_lev(ws), d_in(ws) + 3 * nB, 0, d_in(ws), d_in(ws) + nB, B, p,
+                           d_out(ws) + 3 * nB, cap, d_out(ws), d_out(ws) + nB, d_out(ws) + 2 * nB);
     prof_end("endpoint");
   }
-  prof_begin("endpoint", 0);
-  launch_endpoint_update(stream_, states_dev, d_in(ws) + 2 * nB, d_lev(ws), d_in(ws) + 3 * nB, 0, d_in(ws), d_in(ws) + nB, B, p,
-                         d_out(ws) + 3 * nB, cap, d_out(ws), d_out(ws) + nB, d_out(ws) + 2 * nB);
-  prof_end("endpoint");
   out.resize(d_out.count);
   download(stream_, out.data(), (const int32_t*)d_out(ws), d_out.count);
   PF_HIP(hipStreamSynchronize(stream_));
@@ -426,6 +440,105 @@ void Engine::op_vad_model(const float* rows, const int32_t* T, int B, int n_mels
   if (logits) PF_HIP(hipMemcpyAsync(logits, d_z(ws), (size_t)total * O * 4, hipMemcpyDeviceToHost, stream_));
   if (levels) PF_HIP(hipMemcpyAsync(levels, d_e(ws), (size_t)total * 4, hipMemcpyDeviceToHost, stream_));
   PF_HIP(hipStreamSynchronize(stream_));                          // (`off` is read by its copy until then)
+}
+
+// ---- the FSMN-VAD model score, streaming (k_vadnet_stream.hip): ONE launch for B streams
+void Engine::vad_stream_check(const VadModel& m) {
+  PF_CHECK(vadnet_stream_lds_bytes(m.lds_ld, m.ldp, (m.lorder - 1) * m.lstride) <= kVadStreamMaxLds, PF_ERR_UNSUPPORTED,
+           "vad model stream: two [64, widest + 8] f16 tiles and the [(lorder - 1) * lstride + 64, proj + 4] fp32 window exceed 159 744 bytes of LDS");
+}
+
+void Engine::run_vadnet_stream(char* states_dev, const int32_t* slot_dev, const float* rows_dev, const int32_t* off_dev, int64_t ldx,
+                               const int32_t* n_new_dev, const int32_t* flush_dev, int B, float* logits_dev, int32_t* levels_dev,
+                               int64_t cap, int32_t* n_out_dev) {
+  const VadModel& m = *vadnet_;
+  vad_stream_check(m);
+  if (B <= 0) return;
+  VadNetStreamLaunch a{};
+  a.img = (const char*)vadnet_dev_.buf.p; a.ld = m.lds_ld; a.ldp = m.ldp; a.ldw = m.ldp + 4;
+  a.n_layers = m.n_layers; a.lorder = m.lorder; a.lstride = m.lstride; a.reach = (m.lorder - 1) * m.lstride;
+  a.states = states_dev; a.state_bytes = vad_stream_layout(m).bytes; a.words_off = vad_stream_layout(m).words_off; a.slot = slot_dev;
+  a.x = rows_dev; a.off = off_dev; a.ldx = ldx; a.n_mels = m.input_dim / m.lfr_m; a.lfr_m = m.lfr_m; a.in_dim = m.input_dim;
+  a.shift_off = m.shift_off; a.scale_off = m.scale_off;
+  a.n_new = n_new_dev; a.flush = flush_dev;
+  a.in1 = m.g_in1; a.in2 = m.g_in2; a.out1 = m.g_out1; a.out2 = m.g_out2;
+  for (int l = 0; l < m.n_layers; ++l) { a.lin[l] = m.g_lin[(size_t)l]; a.aff[l] = m.g_aff[(size_t)l]; a.taps_off[l] = m.taps_off[(size_t)l]; }
+  a.sil_off = m.sil_off; a.out_dim = m.output_dim; a.logits = logits_dev; a.levels = levels_dev; a.cap = cap; a.n_out = n_out_dev;
+  prof_begin("vadnet_stream", 0);
+  launch_vadnet_stream(stream_, a, B);
+  prof_end("vadnet_stream");
+}
+
+void Engine::op_vad_model_stream(void* states, const float* rows, const int32_t* n_new, const int32_t* flush, int B, int ld, int n_mels,
+                                 int32_t* levels, float* logits, int cap, int32_t* n_out) {
+  PF_CHECK(vadnet_ != nullptr, PF_ERR_INVALID_ARG, "op_vad_model_stream: no model is attached (pf_engine_set_vad_model)");
+  const VadModel& m = *vadnet_;
+  PF_CHECK((int64_t)n_mels * m.lfr_m == m.input_dim, PF_ERR_INVALID_ARG,
+           "op_vad_model_stream: n_mels * lfr_m does not equal the model's input width");
+  vad_stream_check(m);
+  const VadStreamLayout L = vad_stream_layout(m);
+  const size_t nB = (size_t)B, sbytes = (size_t)L.bytes, O = (size_t)m.output_dim;
+  std::vector<int32_t> want(nB, 0), fl(nB, 0);
+  for (int b = 0; b < B; ++b) {                                  // every stream is admitted before anything changes
+    PF_CHECK(n_new[b] >= 0 && n_new[b] <= ld, PF_ERR_INVALID_ARG, "op_vad_model_stream: n_new[b] outside 0 .. ld");
+    int32_t words[2];
+    std::memcpy(words, (const char*)states + b * sbytes + L.words_off, 8);
+    vad_stream_admit(words[0], words[1], n_new[b]);
+    if (flush) fl[(size_t)b] = flush[b] != 0;
+    want[(size_t)b] = (int32_t)(vad_stream_released(m, (int64_t)words[0] + n_new[b], fl[(size_t)b] || words[1]) -
+                                vad_stream_released(m, words[0], words[1] != 0));
+    PF_CHECK(want[(size_t)b] <= cap, PF_ERR_CAPACITY,
+             "vad model stream: capacity " + std::to_string(cap) + " < " + std::to_string(want[(size_t)b]) + " released levels");
+  }
+  PF_HIP(hipSetDevice(device_));
+  if (B == 0) return;
+  const size_t dev_cap = (size_t)std::max(cap, 1), row_cells = (size_t)ld * n_mels;
+  StageCarve st;
+  const auto d_state = st.take<char>(nB * sbytes);
+  const auto d_x = st.take<float>(nB * row_cells + 4);
+  const auto d_new = st.take<int32_t>(nB), d_flush = st.take<int32_t>(nB), d_lev = st.take<int32_t>(nB * dev_cap);
+  const auto d_z = st.take<float>(logits ? nB * dev_cap * O : 0);
+  const auto d_out = st.take<int32_t>(nB);
+  void* ws = op_ws(st);
+  std::vector<float> x(nB * row_cells + 4);                      // hostile behind every stream's n_new rows
+  for (size_t i = 0; i < x.size(); ++i) x[i] = hostile32(i);
+  for (int b = 0; b < B; ++b)
+    if (n_new[b] > 0) std::memcpy(&x[b * row_cells], rows + b * row_cells, (size_t)n_new[b] * n_mels * 4);
+  upload(stream_, d_state(ws), (const char*)states, d_state.count);
+  upload(stream_, d_x(ws), (const float*)x.data(), x.size());
+  upload(stream_, d_new(ws), n_new, nB);
+  upload(stream_, d_flush(ws), (const int32_t*)fl.data(), nB);
+  fill_sentinel(stream_, d_lev(ws), d_lev.count);
+  if (logits) fill_sentinel(stream_, d_z(ws), d_z.count);
+  fill_sentinel(stream_, d_out(ws), d_out.count);
+  run_vadnet_stream(d_state(ws), nullptr, d_x(ws), nullptr, ld, d_new(ws), d_flush(ws), B, logits ? d_z(ws) : nullptr, d_lev(ws),
+                    (int64_t)dev_cap, d_out(ws));
+  const std::vector<uint32_t> out = check_guard<uint32_t>(stream_, "vad_model_stream: n_out", d_out(ws), kSentinel32, result_geom(B, B, 1, 1, B));
+  std::vector<uint32_t> lev(d_lev.count), z(d_z.count);          // the guard rule is applied per stream below
+  download(stream_, (int32_t*)lev.data(), (const int32_t*)d_lev(ws), d_lev.count);
+  if (logits) download(stream_, (float*)z.data(), (const float*)d_z(ws), d_z.count);
+  PF_HIP(hipStreamSynchronize(stream_));
+  for (int b = 0; b < B; ++b) {
+    const int k = (int)out[(size_t)b];
+    PF_CHECK(k == want[(size_t)b], PF_ERR_DEVICE, "vad_model_stream: stream " + std::to_string(b) + " released " + std::to_string(k) +
+                                                      " levels where the schedule says " + std::to_string(want[(size_t)b]));
+    const GuardGeom gl = result_geom((int64_t)dev_cap, k, 1, 1, k);
+    if (const GuardHit hit = guard_scan<uint32_t>(lev.data() + b * dev_cap, nullptr, kSentinel32, gl))
+      throw Error(PF_ERR_DEVICE, guard_message("vad_model_stream: levels of stream " + std::to_string(b), gl, hit));
+    if (logits) {                                                // (a logit may be a NaN, never the sentinel's payload)
+      const GuardGeom gz = result_geom((int64_t)dev_cap, k, (int)O, (int)O, k);
+      if (const GuardHit hit = guard_scan<uint32_t>(z.data() + b * dev_cap * O, nullptr, kSentinel32, gz))
+        throw Error(PF_ERR_DEVICE, guard_message("vad_model_stream: logits of stream " + std::to_string(b), gz, hit));
+    }
+  }
+  download(stream_, (char*)states, (const char*)d_state(ws), d_state.count);
+  PF_HIP(hipStreamSynchronize(stream_));
+  for (int b = 0; b < B; ++b) {
+    const size_t k = (size_t)want[(size_t)b];
+    n_out[b] = (int32_t)k;
+    if (levels && k) std::memcpy(levels + (size_t)b * cap, lev.data() + b * dev_cap, k * 4);
+    if (logits && k) std::memcpy(logits + (size_t)b * cap * O, z.data() + b * dev_cap * O, k * O * 4);
+  }
 }
 
 // ---- the CAM++ speaker model (k_spk.hip; the launch plan is at the head of that file)

@@ -23,28 +23,21 @@
 // The softmax runs on the accumulators: every lane keeps (max, sum, silence sum) over its channels on line, the two lane
 // halves are merged with one shuffle, the four waves through 3 KB of LDS; e = rint((1 - 2 s) * 16384), -16384 when that is
 // not finite.  ReLU is x < 0 ? 0 : x, which keeps a NaN (fmaxf would drop it).
+// The FSMN sum, the softmax merge and the level formula are vadnet_dev.h's, shared with k_vadnet_stream.hip.
 // Nothing at or beyond an utterance's T is read; rows at or beyond the total are computed as zeros and never stored.
 #include "kdev.h"
 #include "kernels.h"
 #include "tile_rows.h"
+#include "vadnet_dev.h"
 
 namespace pf {
 
 namespace {
 
-constexpr int VN_ROWS = TR_ROWS;
-
 struct VnRowInfo {            // per tile row: the first row of its utterance and that utterance's length; T = 0: no such row
   long long start[VN_ROWS];
   int T[VN_ROWS];
 };
-
-// the f16 tile of the next product: Y [64, g.Npad], optional ReLU
-__device__ __forceinline__ void vn_stage(const char* __restrict__ img, const TileGemm& g, bool relu, const half_t* x, half_t* y, int ld,
-                                         int wave, int lane) {
-  const int r = lane & 31, h = lane >> 5;
-  tr_product(img, g, x, ld, wave, lane, [&](int nt, int i, const f16x& acc) { tr_put_f16(acc, relu, y, ld, i, nt, r, h); });
-}
 
 }  // namespace
 
@@ -90,13 +83,7 @@ __global__ __launch_bounds__(256) void vadnet_kernel(VadNetLaunch a) {
       const long long g = g0 + row, t = g - info.start[row];
       for (int c = lane; c < a.head_w; c += 64) {
         float v = 0.f;
-        if (T > 0 && c < a.ldp) {
-          v = a.p_in[g * a.ldp + c];
-          for (int k = 0; k < a.lorder; ++k) {
-            const long long d = (long long)(a.lorder - 1 - k) * a.lstride;
-            if (d <= t) v += taps[k * a.ldp + c] * a.p_in[(g - d) * a.ldp + c];
-          }
-        }
+        if (T > 0 && c < a.ldp) v = vn_fsmn_sum(a.p_in + g * a.ldp + c, a.ldp, taps + c, a.ldp, t, a.lorder, a.lstride);
         buf0[row * ld + c] = (half_t)v;
       }
     }
@@ -129,69 +116,14 @@ __global__ __launch_bounds__(256) void vadnet_kernel(VadNetLaunch a) {
 
   // ---- out_linear2, the softmax and the level
   const float* __restrict__ silf = reinterpret_cast<const float*>(a.img + a.sil_off);
-  float mx[2] = {-INFINITY, -INFINITY}, sum[2] = {0.f, 0.f}, sil[2] = {0.f, 0.f};
-  bool poisoned[2] = {false, false};
-  tr_product(a.img, a.last, cur, ld, wave, lane, [&](int nt, int i, const f16x& acc) {
-    const long long g = g0 + 32 * i + r;
-    float tm = -INFINITY;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int n = 32 * nt + 8 * q + 4 * h;
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (n + e < a.out_dim) {
-          const float v = acc[4 * q + e];
-          if (v != v) poisoned[i] = true;
-          tm = fmaxf(tm, v);
-          if (a.logits && g < a.total) a.logits[g * a.out_dim + n + e] = v;
-        }
-    }
-    if (tm == -INFINITY) return;                         // no valid column in this block for this lane half, or all -inf
-    const float nm = fmaxf(mx[i], tm);
-    const float sc = mx[i] == -INFINITY ? 0.f : expf(mx[i] - nm);
-    float s1 = sum[i] * sc, s2 = sil[i] * sc;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int n = 32 * nt + 8 * q + 4 * h;
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (n + e < a.out_dim) {
-          const float ex = expf(acc[4 * q + e] - nm);
-          s1 += ex;
-          s2 += ex * silf[n + e];
-        }
-    }
-    mx[i] = nm; sum[i] = s1; sil[i] = s2;
+  vn_softmax_merge(a.img, a.last, cur, ld, wave, lane, silf, a.out_dim, red, [&](int j) -> float* {
+    const long long g = g0 + j;
+    return a.logits && g < a.total ? a.logits + g * a.out_dim : nullptr;
   });
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    // the other lane half holds the other channels of the same row
-    const float om = __shfl_xor(mx[i], 32, 64), os = __shfl_xor(sum[i], 32, 64), oq = __shfl_xor(sil[i], 32, 64);
-    const bool op = __shfl_xor((int)poisoned[i], 32, 64) != 0;
-    const float nm = fmaxf(mx[i], om);
-    const float ca = mx[i] == -INFINITY ? 0.f : expf(mx[i] - nm), cb = om == -INFINITY ? 0.f : expf(om - nm);
-    float s1 = sum[i] * ca + os * cb, s2 = sil[i] * ca + oq * cb;
-    if (poisoned[i] || op) s1 = NAN;
-    if (h == 0) { red[wave][32 * i + r][0] = nm; red[wave][32 * i + r][1] = s1; red[wave][32 * i + r][2] = s2; }
-  }
   __syncthreads();
   if (tid < VN_ROWS) {
     const long long g = g0 + tid;
-    if (g < a.total && a.levels) {
-      float nm = -INFINITY;
-#pragma unroll
-      for (int w = 0; w < 4; ++w) nm = fmaxf(nm, red[w][tid][0]);
-      float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-      for (int w = 0; w < 4; ++w) {
-        const float m = red[w][tid][0];
-        const float c = m == -INFINITY ? 0.f : expf(m - nm);
-        s1 += red[w][tid][1] * c;
-        s2 += red[w][tid][2] * c;
-      }
-      const float v = (1.f - 2.f * (s2 / s1)) * 16384.f;
-      a.levels[g] = (v >= -16384.f && v <= 16384.f) ? (int)rintf(v) : -16384;
-    }
+    if (g < a.total && a.levels) a.levels[g] = vn_level(red, tid);
   }
 }
 

@@ -543,6 +543,28 @@ struct VadNetLaunch {
 size_t vadnet_lds_bytes(int ld);
 void launch_vadnet(hipStream_t s, const VadNetLaunch& a);
 
+// ---------------------------------------------------------------- the FSMN-VAD model score, streaming (k_vadnet_stream.hip) ------
+// paraformer_hip.h "Voice-activity endpointing, streaming, model score"; the release schedule in Python is
+// tests/vadnet_stream_ref.py.  ONE launch for B streams, one workgroup of four waves per stream: stream b = its state block
+// states + slot[b] * state_bytes (read, then written; slot null: block b; the slots of a launch are distinct; the layout is
+// vadnet.h VadStreamLayout) and n_new[b] new fbank rows at x + off[b] * n_mels (off null: x + b * ldx * n_mels; nothing at or
+// beyond n_new[b] is read), then its flush when flush[b] != 0 (flush may be null).  levels [B, cap] int32 / logits
+// [B, cap, out_dim] fp32 (either may be null): only the released ones of a stream are written, n_out[b] of them, and the
+// caller has made sure that cap holds them (vad_stream_released); n_out [B] is always written.
+struct VadNetStreamLaunch {
+  const char* img; int ld, ldp, ldw;                            // ld: f16 tile stride (halves); ldw: stride of the fp32 p window (floats)
+  int n_layers, lorder, lstride, reach;                         // reach = (lorder - 1) * lstride history rows per layer
+  char* states; int64_t state_bytes, words_off; const int32_t* slot;
+  const float* x; const int32_t* off; int64_t ldx; int n_mels, lfr_m, in_dim; int64_t shift_off, scale_off;
+  const int32_t* n_new; const int32_t* flush;
+  TileGemm in1, in2, out1, out2, lin[8], aff[8]; int64_t taps_off[8];
+  int64_t sil_off; int out_dim; float* logits; int32_t* levels; int64_t cap; int32_t* n_out;
+};
+// the dynamic LDS of a launch: two f16 tiles and the fp32 window of (reach + 64) rows; at most kVadStreamMaxLds
+constexpr size_t kVadStreamMaxLds = 156 * 1024;
+size_t vadnet_stream_lds_bytes(int ld, int ldp, int reach);
+void launch_vadnet_stream(hipStream_t s, const VadNetStreamLaunch& a, int B);
+
 // ---------------------------------------------------------------- the CT-Transformer punctuation model (k_punc.hip) ------
 // The definition in numpy is tests/punc_ref.py; the launch plan (2 + 2 n_layers launches per forward) is at the head of
 // k_punc.hip and Engine::run_punc fills these in.  img: the model's device image (punc.h); every *_off and TileGemm offset is a

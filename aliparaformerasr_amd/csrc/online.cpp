@@ -281,6 +281,8 @@ void OnlineRecognizerM::Dispose() {
     std::lock_guard<std::mutex> lk(e->mutex());
     std::lock_guard<std::mutex> lk2(ep_mu_);
     if (ep_states_) { hipSetDevice(e->device()); hipFree(ep_states_); ep_states_ = nullptr; ep_cap_ = 0; ep_free_.clear(); }
+    if (ep_net_states_) { hipSetDevice(e->device()); hipFree(ep_net_states_); ep_net_states_ = nullptr; }
+    ep_model_.reset();
     second_.reset();
   }
   e.reset();
@@ -296,6 +298,32 @@ void OnlineRecognizerM::SetEndpoint(const pf_endpoint_config* cfg) {
   std::lock_guard<std::mutex> lk(ep_mu_);
   ep_cfg_ = c;
   ep_on_ = true;
+}
+
+void OnlineRecognizerM::SetEndpointModel(const std::string& pfw_path) {
+  if (disposed_) throw Error(PF_ERR_DISPOSED, "OnlineRecognizer");
+  std::shared_ptr<const VadModel> vm;
+  if (!pfw_path.empty()) {
+    vm = vad_model_load(pfw_path);                              // throws before anything changes
+    Engine::vad_stream_check(*vm);
+  }
+  std::shared_ptr<Engine> eh = engine();
+  if (!eh) throw Error(PF_ERR_DISPOSED, "OnlineRecognizer");
+  std::lock_guard<std::mutex> lk(eh->mutex());
+  std::lock_guard<std::mutex> lk2(ep_mu_);
+  if (!vm && !ep_model_) return;
+  PF_CHECK((int)ep_free_.size() == ep_cap_, PF_ERR_UNSUPPORTED,
+           "endpoint model: a live stream has already fed the detector (attach or detach before the first GetResults with audio)");
+  eh->set_vad_model(vm);                                        // the refusals of pf_engine_set_vad_model
+  PF_HIP(hipSetDevice(eh->device()));
+  if (ep_net_states_) {
+    PF_HIP(hipStreamSynchronize(eh->stream()));
+    PF_HIP(hipFree(ep_net_states_));
+    ep_net_states_ = nullptr;
+  }
+  ep_model_ = vm;
+  ep_net_bytes_ = vm ? (size_t)vad_stream_layout(*vm).bytes : 0;
+  if (vm && ep_cap_ > 0) PF_HIP(hipMalloc((void**)&ep_net_states_, (size_t)ep_cap_ * ep_net_bytes_));
 }
 
 void OnlineRecognizerM::SetSecondPass(std::shared_ptr<Recognizer> offline) {
@@ -320,6 +348,7 @@ void OnlineRecognizerM::ForwardEndpoint(const std::vector<OnlineStreamM*>& strea
   std::vector<Closed> closed;
   pf_endpoint_config c;
   std::shared_ptr<Recognizer> second;
+  std::shared_ptr<const VadModel> net;
   {
     std::lock_guard<std::mutex> lk(ep_mu_);
     c = ep_cfg_;
@@ -330,6 +359,7 @@ void OnlineRecognizerM::ForwardEndpoint(const std::vector<OnlineStreamM*>& strea
     if (disposed_ || !eh) throw Error(PF_ERR_DISPOSED, "OnlineRecognizer");
     Engine* e = eh.get();
     std::lock_guard<std::mutex> lk(e->mutex());
+    { std::lock_guard<std::mutex> ls(ep_mu_); net = ep_model_; }      // (SetEndpointModel changes it under the engine's mutex)
     // who takes part: new rows, or the flush once the model has decoded every chunk of a finished input
     std::vector<OnlineStreamM*> work;
     std::vector<int32_t> n_new, flush, slot;
@@ -363,6 +393,16 @@ void OnlineRecognizerM::ForwardEndpoint(const std::vector<OnlineStreamM*>& strea
             PF_HIP(hipStreamSynchronize(e->stream()));
             PF_HIP(hipFree(ep_states_));
           }
+          if (net) {                                            // the network's states grow with the detector's
+            char* q = nullptr;
+            PF_HIP(hipMalloc((void**)&q, (size_t)cap * ep_net_bytes_));
+            if (ep_net_states_) {
+              PF_HIP(hipMemcpyAsync(q, ep_net_states_, (size_t)ep_cap_ * ep_net_bytes_, hipMemcpyDeviceToDevice, e->stream()));
+              PF_HIP(hipStreamSynchronize(e->stream()));
+              PF_HIP(hipFree(ep_net_states_));
+            }
+            ep_net_states_ = q;
+          }
           for (int i = cap - 1; i >= ep_cap_; --i) ep_free_.push_back(i);
           ep_states_ = p;
           ep_cap_ = cap;
@@ -370,12 +410,15 @@ void OnlineRecognizerM::ForwardEndpoint(const std::vector<OnlineStreamM*>& strea
         s->ep_slot_ = ep_free_.back();
         ep_free_.pop_back();
         PF_HIP(hipMemsetAsync(ep_states_ + (size_t)s->ep_slot_ * PF_ENDPOINT_STATE_INTS, 0, PF_ENDPOINT_STATE_INTS * 4, e->stream()));
+        if (net) PF_HIP(hipMemsetAsync(ep_net_states_ + (size_t)s->ep_slot_ * ep_net_bytes_, 0, ep_net_bytes_, e->stream()));
       }
       for (OnlineStreamM* s : work) slot.push_back(s->ep_slot_);
     }
-    const int cap = *std::max_element(n_new.begin(), n_new.end()) + 1;
+    // an event per level at most and one for the flush; with the model a call releases up to `right` levels more than it brought
+    const int right = net ? net->lfr_m - 1 - (net->lfr_m - 1) / 2 : 0;
+    const int cap = *std::max_element(n_new.begin(), n_new.end()) + right + 1;
     std::vector<int32_t> out;
-    e->endpoint_streams(ep_states_, slot.data(), rows.data(), n_new.data(), flush.data(), B, c, cap, out);
+    e->endpoint_streams(ep_states_, slot.data(), rows.data(), n_new.data(), flush.data(), B, c, cap, out, net ? ep_net_states_ : nullptr);
     for (int b = 0; b < B; ++b) {
       OnlineStreamM* s = work[(size_t)b];
       std::lock_guard<std::mutex> ls(s->mu);
@@ -405,7 +448,8 @@ void OnlineRecognizerM::ForwardEndpoint(const std::vector<OnlineStreamM*>& strea
       s->OpenBeginMs = s->InSpeech ? (int)((s->ep_origin_ + 160 * (int64_t)ob) / 16) : -1;
       // what a sentence that is open, or opens later, can still need: from prev_end, and from the open begin or pad_begin + window
       // frames behind the newest frame
-      const int64_t keep = 160 * (int64_t)std::max(s->ep_prev_end_, s->InSpeech ? ob : std::max(0, s->ep_fed_ - c.pad_begin - c.window));
+      // (with the model the detector has seen the released levels only: `right` frames fewer until the flush)
+      const int64_t keep = 160 * (int64_t)std::max(s->ep_prev_end_, s->InSpeech ? ob : std::max(0, s->ep_fed_ - right - c.pad_begin - c.window));
       if (keep > s->ep_audio_base_) {
         const int64_t drop = std::min<int64_t>(keep - s->ep_audio_base_, (int64_t)s->ep_audio_.size());
         s->ep_audio_.erase(s->ep_audio_.begin(), s->ep_audio_.begin() + drop);

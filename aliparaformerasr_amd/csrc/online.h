@@ -111,6 +111,12 @@ class OnlineRecognizerM : public std::enable_shared_from_this<OnlineRecognizerM>
   // the offline recognizer that re-recognises every finished sentence (ONE GetResults per call over the sentences that closed
   // in it); null: none.  PF_ERR_UNSUPPORTED for a recognizer with SetVad on (one sentence stays one stream).
   void SetSecondPass(std::shared_ptr<Recognizer> offline);
+  // The FSMN-VAD model score as the detector's level (paraformer_hip.h "Voice-activity endpointing, streaming, model score";
+  // DESIGN.md 4.6q): loads a `.pfw` of kind "fsmnvad" and attaches it to the engine; "" detaches.  Every stream's network state
+  // lives in a second device buffer, indexed by the detector's slot.  Inert until SetEndpoint.  Errors as vad_model_load and
+  // Engine::set_vad_model; PF_ERR_UNSUPPORTED for a model whose window does not fit the LDS, and while a live stream has already
+  // fed the detector (two kinds of level must not meet in one state block).
+  void SetEndpointModel(const std::string& pfw_path);
   bool endpoint_on() const { return ep_on_.load(); }
   void release_slot(int slot);
 
@@ -118,12 +124,15 @@ class OnlineRecognizerM : public std::enable_shared_from_this<OnlineRecognizerM>
   void Forward(const std::vector<OnlineStreamM*>& streams);   // :336-403
   void ForwardEndpoint(const std::vector<OnlineStreamM*>& streams);
   std::atomic<bool> ep_on_{false};
-  std::mutex ep_mu_;                                          // guards the five below
+  std::mutex ep_mu_;                                          // guards the eight below
   pf_endpoint_config ep_cfg_{};
   std::shared_ptr<Recognizer> second_;
   int32_t* ep_states_ = nullptr;                              // [ep_cap_, PF_ENDPOINT_STATE_INTS] on the device, a block per stream slot
   int ep_cap_ = 0;
   std::vector<int> ep_free_;
+  std::shared_ptr<const VadModel> ep_model_;                  // the model score (SetEndpointModel); null: the energy level
+  char* ep_net_states_ = nullptr;                             // [ep_cap_, ep_net_bytes_] on the device: the network's state per slot
+  size_t ep_net_bytes_ = 0;
   std::mutex mu_;
   std::shared_ptr<Engine> engine_;
   ConfEntity conf_;

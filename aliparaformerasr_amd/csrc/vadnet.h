@@ -41,6 +41,25 @@ void host_vad_model_logits(const VadModel& m, const float* rows, int64_t T, int 
 void host_vad_model_levels(const VadModel& m, const float* rows, int64_t T, int n_mels, int32_t* levels);
 pf_vad_config vad_model_default();      // vad_default() with floor_pct = -1, abs_level = 9830
 
+// ---- streaming (paraformer_hip.h "Voice-activity endpointing, streaming, model score"; the schedule is tests/vadnet_stream_ref.py)
+// the levels a stream of n received frames has released: max(0, n - right), all n once flushed
+int64_t vad_stream_released(const VadModel& m, int64_t n, bool flushed);
+// what both forms check about ONE stream's state words and its new frames before anything changes (as endpoint_admit)
+void vad_stream_admit(int64_t count, int32_t flushed, int64_t n_new);
+// the device form's state block (k_vadnet_stream.hip): fp32 history [n_layers, reach, ldp] | fp32 row tail [lfr_m - 1, n_mels] |
+// int32 count | int32 flushed in the block's last 8 bytes (words_off); all zero = a fresh stream
+struct VadStreamLayout { int64_t hist_floats = 0, tail_floats = 0, words_off = 0, bytes = 0; };
+VadStreamLayout vad_stream_layout(const VadModel& m);
+// The host twin for ONE stream, float64, on block64, the per-row code of host_vad_model_logits: n_new rows [n_new, n_mels], then
+// the flush.  state: host_vad_stream_state_bytes bytes, in / out, all zero = fresh (its layout is the twin's own: float64 history, the
+// row tail, and count | flushed in the last 8 bytes).  levels [cap]
+// / logits [cap, output_dim]: either may be null.  Returns the released count; PF_ERR_CAPACITY when cap is below it (nothing
+// changed), otherwise as vad_stream_admit.
+int64_t host_vad_stream_state_bytes(const VadModel& m);
+int64_t host_vad_model_stream(const VadModel& m, void* state, const float* rows, int64_t n_new, bool flush, int n_mels, int32_t* levels,
+                              double* logits, int64_t cap);
+pf_endpoint_config endpoint_model_default();   // endpoint_default() with rise = -1, abs_level = 9830
+
 }  // namespace pf
 
 // the C handle: a reference to an immutable model (an engine that attaches it takes a reference of its own)

@@ -479,6 +479,42 @@ def host_vad_model_levels(model: VadModel, rows) -> np.ndarray:
     return out
 
 
+def endpoint_model_config(**kw) -> "N.PfEndpointConfig":
+    """pf_endpoint_config with the defaults that go with the streaming model score (pf_endpoint_model_config: rise = -1,
+    abs_level = 9830, stated and not tuned), fields overridden by keyword."""
+    c = N.PfEndpointConfig()
+    N.check(N.load().pf_endpoint_model_config(C.byref(c)))
+    for k, v in kw.items():
+        assert hasattr(c, k) and k not in ("struct_size", "reserved"), k
+        setattr(c, k, int(v))
+    return c
+
+
+def vad_model_stream_state(model: VadModel, B=None, host=False) -> np.ndarray:
+    """Fresh (all-zero) state blocks of the streaming model score: uint8 [state_bytes], or [B, state_bytes] when B is given.
+    host=False: the device form's (pf_vad_model_stream_state_bytes); True: the host twin's own."""
+    n = C.c_int64()
+    fn = N.load().pf_host_vad_model_stream_state_bytes if host else N.load().pf_vad_model_stream_state_bytes
+    N.check(fn(model._h, C.byref(n)))
+    return np.zeros(n.value if B is None else (B, n.value), np.uint8)
+
+
+def host_vad_model_stream(model: VadModel, state, rows, flush=False, cap=None, n_mels=None):
+    """The streaming model score for ONE stream in host code, float64 (pf_host_vad_model_stream): `rows` [n_new, n_mels] (may be
+    empty) and then the flush.  state (vad_model_stream_state(model, host=True)) is updated in place.  Returns (levels [n_out]
+    int32, logits [n_out, output_dim] float64)."""
+    assert isinstance(state, np.ndarray) and state.dtype == np.uint8 and state.ndim == 1 and state.flags.c_contiguous
+    m = model.dims["input_dim"] // model.dims["lfr_m"] if n_mels is None else n_mels
+    x = _f32(np.asarray(rows, np.float32).reshape(-1, m))
+    cap = x.shape[0] + model.dims["lfr_m"] if cap is None else cap
+    lev = np.zeros(max(cap, 1), np.int32)
+    z = np.zeros((max(cap, 1), model.dims["output_dim"]), np.float64)
+    n = C.c_int32()
+    N.check(N.load().pf_host_vad_model_stream(model._h, state.ctypes.data_as(C.c_void_p), _fp(x), x.shape[0], int(bool(flush)), m,
+                                              _i32p(lev), _dp(z), int(cap), C.byref(n)))
+    return lev[: n.value].copy(), z[: n.value].copy()
+
+
 SPK_MODEL_DIMS = ("n_mels", "m_channels", "init_channels", "growth", "bn_channels", "blocks0", "blocks1", "blocks2", "dilation0",
                   "dilation1", "dilation2", "seg_len", "embedding", "frame_width", "launches")
 
@@ -1352,6 +1388,36 @@ class Engine:
     def op_vad_model_levels(self, rows_list) -> list:
         """As op_vad_model_logits, the levels [T_b] int32 (pf_op_vad_model_levels)."""
         return self._op_vad_model(rows_list, False)
+
+    def op_vad_model_stream(self, states, rows_list, flush=None, want_logits=True, cap=None, ld=None):
+        """The attached model's streaming launch on caller state blocks and rows (pf_op_vad_model_stream): ONE launch over all
+        the streams.  states [B, state_bytes] uint8 (vad_model_stream_state), updated in place; rows_list: each stream's new rows
+        [n_new_b, n_mels] (any counts, may be empty); flush: per-stream flags.  Returns (levels per stream [n_out_b] int32,
+        logits per stream [n_out_b, output_dim] float32 or None)."""
+        model = self._vad_model
+        if model is not None:
+            m = model.dims["input_dim"] // model.dims["lfr_m"]
+        else:                                                       # (without a model the call is refused)
+            m = np.asarray(rows_list[0]).shape[-1] if len(rows_list) else 80
+        arrs = [_f32(np.asarray(r, np.float32).reshape(-1, m)) for r in rows_list]
+        B = len(arrs)
+        assert isinstance(states, np.ndarray) and states.dtype == np.uint8 and states.flags.c_contiguous and states.shape[0] == B
+        ld = max([a.shape[0] for a in arrs] + [1]) if ld is None else ld
+        x = np.full((max(B, 1), ld, m), np.float32(3e38), np.float32)   # past n_new[b]: values that would change every answer if read
+        for b, a in enumerate(arrs):
+            x[b, : min(a.shape[0], ld)] = a[:ld]
+        n_new = np.ascontiguousarray([a.shape[0] for a in arrs] + [0] * (B == 0), dtype=np.int32)
+        fl = np.zeros(max(B, 1), np.int32)
+        if flush is not None:
+            fl[:B] = np.asarray(flush, dtype=bool).astype(np.int32)
+        O = model.dims["output_dim"] if model is not None else 1
+        cap = ld + (model.dims["lfr_m"] if model is not None else 0) if cap is None else cap
+        lev = np.full((max(B, 1), max(cap, 1)), -77777, np.int32)
+        z = np.full((max(B, 1), max(cap, 1), O), np.float32(-7e7), np.float32) if want_logits else None
+        n = np.zeros(max(B, 1), np.int32)
+        N.check(self._lib.pf_op_vad_model_stream(self._h, states.ctypes.data_as(C.c_void_p), _fp(x), _i32p(n_new), _i32p(fl), B, ld, m,
+                                                 _i32p(lev), _fp(z) if want_logits else None, int(cap), _i32p(n)))
+        return ([lev[b, : n[b]].copy() for b in range(B)], [z[b, : n[b]].copy() for b in range(B)] if want_logits else None)
 
     def set_spk_model(self, model):
         """Attaches a SpkModel (pf_engine_set_spk_model); None detaches and frees what the attach and its runs allocated."""

@@ -2,7 +2,7 @@
 
     python -m aliparaformerasr_amd.examples -type offline -method batch -base <dir> -model <name> \
         [-accuracy int8] [-threads 2] [-decode ctc|frames] [-intake host|device] [-nbest N [-topk K] [-beam W | -search W] [-hotboost S] [-lm FILE [-lmweight A] [-lmbonus B] [-lmeos]]] [-align FILE|beam] [-vad [key=value,...] [-vadmodel FILE] [-spk FILE [key=value,...]]] [-punc FILE] -files a.wav b.wav
-    python -m aliparaformerasr_amd.examples -type online -method one -base <dir> -model <name> [-endpoint [key=value,...] [-secondpass <offline name>]] -files a.wav
+    python -m aliparaformerasr_amd.examples -type online -method one -base <dir> -model <name> [-endpoint [key=value,...] [-vadmodel FILE] [-secondpass <offline name>]] -files a.wav
 
 Mirrors (file:line in /root/reference/AliParaformerAsr.Examples):
   * argument handling and defaults — Program.cs:93-104, ParseArgs :197-252: the MANYSPEECH_BASE / _TYPE / _BATCH / _MODEL /
@@ -63,6 +63,9 @@ text of a chunk goes one `[begin-end ms] text` line per sentence that closed in 
 and after the last chunk the input is declared finished (OnlineStream.InputFinished), which decodes the tail and closes what is
 open.  Keys: the pf_endpoint_config fields (rise, margin_q, abs_level, window, on_count, off_count, pad_begin, pad_end,
 end_silence, min_speech, max_len); the defaults are unvalidated on real speech.
+`-vadmodel FILE` (with `-endpoint`; OnlineRecognizer.SetEndpointModel) takes the detector's level from an FSMN-VAD network (a
+`.pfw` of kind fsmnvad, as above) with each stream's history carried between chunks; the model's default thresholds (rise=-1,
+abs_level=9830; unvalidated too) apply unless keys are given.  A sentence line can come one chunk later than with the energy level.
 `-secondpass NAME` (with `-endpoint`; OnlineRecognizer.SetSecondPass) re-recognises every finished sentence with the OFFLINE model
 in directory NAME under -base (its files chosen as `-type offline` chooses them): the sentence lines then carry its text."""
 from __future__ import annotations
@@ -432,7 +435,7 @@ def get_file_chunk_samples(path: str, chunk: int = 160 * 6 * 10):
 
 
 def online_recognizer(method="one", model="speech_paraformer-large_asr_nat-zh-cn-16k-common-vocab8404-online-onnx",
-                      accuracy="int8", threads=2, files=None, base=None, out=sys.stdout, endpoint=None, secondpass=None):
+                      accuracy="int8", threads=2, files=None, base=None, out=sys.stdout, endpoint=None, secondpass=None, vadmodel=None):
     from .online_recognizer import OnlineRecognizer
     base = base or os.getcwd()
     if not model:
@@ -452,7 +455,12 @@ def online_recognizer(method="one", model="speech_paraformer-large_asr_nat-zh-cn
     second = None
     if endpoint is not None:
         try:
-            rec.SetEndpoint(**endpoint)
+            if vadmodel:                                    # the model's default thresholds unless keys are given
+                from .engine import endpoint_model_config
+                rec.SetEndpointModel(vadmodel)
+                rec.SetEndpoint(endpoint_model_config(**endpoint))
+            else:
+                rec.SetEndpoint(**endpoint)
             if secondpass:                                  # the offline model's directory under -base, chosen as -type offline does
                 from .offline_recognizer import OfflineRecognizer
                 osel = select_model_files(base, secondpass, accuracy)
@@ -674,8 +682,8 @@ def parse_args(argv, env=None):
         raise ValueError("-punc is an offline option")
     if "spk" in cfg and "vad" not in cfg:
         raise ValueError("-spk goes with -vad")
-    if "vadmodel" in cfg and "vad" not in cfg:
-        raise ValueError("-vadmodel goes with -vad")
+    if "vadmodel" in cfg and "vad" not in cfg and "endpoint" not in cfg:
+        raise ValueError("-vadmodel goes with -vad (offline) or -endpoint (online)")
     if cfg.get("align") == "beam" and "beam" not in cfg:
         raise ValueError("-align beam needs -nbest N -beam W")
     return cfg
@@ -691,7 +699,8 @@ def main(argv=None):
     # Program.cs:290-308
     if cfg["recognizerType"] == "online":
         online_recognizer(cfg["methodType"], cfg["modelName"], cfg["modelAccuracy"], cfg["threads"], cfg["files"],
-                          cfg["modelBasePath"] or None, endpoint=cfg.get("endpoint"), secondpass=cfg.get("secondpass"))
+                          cfg["modelBasePath"] or None, endpoint=cfg.get("endpoint"), secondpass=cfg.get("secondpass"),
+                          vadmodel=cfg.get("vadmodel"))
     elif cfg["recognizerType"] == "offline":
         offline_recognizer(cfg["methodType"], cfg["modelName"], cfg["modelAccuracy"], cfg["threads"], cfg["files"],
                            cfg["modelBasePath"] or None, decode=cfg.get("decode", "frames"), intake=cfg.get("intake", "host"),

@@ -107,6 +107,13 @@ class OnlineRecognizer:
         _ck(self._lib.pf_online_create_stream(self._h, C.byref(s)))
         return OnlineStream(self._lib, s, self)
 
+    def SetEndpointModel(self, pfwPath) -> None:
+        """The FSMN-VAD model score as the endpoint detector's level (pf_online_recognizer_set_endpoint_model): a `.pfw` of kind
+        "fsmnvad"; None goes back to the energy level.  Inert until SetEndpoint; pass engine.endpoint_model_config()'s thresholds
+        there (stated, not tuned).  An event can fall one call later than with the energy level.  Refused once a live stream has
+        fed the detector."""
+        _ck(self._lib.pf_online_recognizer_set_endpoint_model(self._h, None if pfwPath is None else str(pfwPath).encode("utf-8")))
+
     def SetEndpoint(self, enabled=True, **keys) -> None:
         """Endpoint detection for every GetResults that follows (off by default; SetEndpoint(False) turns it off again and
         leaves every path as it is without it): a causal voice-activity detector on the device closes sentences —

@@ -26,6 +26,7 @@ namespace AliParaformerAsr.Hip
         // streaming endpointing and the second pass (paraformer_hip.h "Streaming endpointing and the second pass")
         [DllImport(Lib)] internal static extern int pf_online_recognizer_set_endpoint(IntPtr r, ref PfEndpointConfig cfg);
         [DllImport(Lib)] internal static extern int pf_online_recognizer_set_endpoint(IntPtr r, IntPtr cfgNull);          // IntPtr.Zero: off
+        [DllImport(Lib)] internal static extern int pf_online_recognizer_set_endpoint_model(IntPtr r, [MarshalAs(UnmanagedType.LPUTF8Str)] string? pfwPath);
         [DllImport(Lib)] internal static extern int pf_online_recognizer_set_second_pass(IntPtr r, IntPtr offlineRecognizer);
         [DllImport(Lib)] internal static extern int pf_online_stream_input_finished(IntPtr s);
         [DllImport(Lib)] internal static extern int pf_online_stream_num_sentences(IntPtr s, out int n);
@@ -109,6 +110,11 @@ namespace AliParaformerAsr.Hip
             PfEndpointConfig c = cfg.Value;
             ParaformerHip.Check(OnlineNative.pf_online_recognizer_set_endpoint(_h, ref c));
         }
+
+        // The FSMN-VAD model score as the detector's level (a .pfw of kind "fsmnvad"; null: the energy level).  Inert until
+        // SetEndpoint; pass pf_endpoint_model_config's thresholds there (stated, not tuned).
+        public void SetEndpointModel(string? pfwPath)
+            => ParaformerHip.Check(OnlineNative.pf_online_recognizer_set_endpoint_model(_h, pfwPath));
 
         // the offline recognizer's native handle that re-recognises every finished sentence (IntPtr.Zero: none)
         public void SetSecondPass(IntPtr offlineRecognizerHandle)

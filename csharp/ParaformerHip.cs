@@ -287,6 +287,8 @@ namespace AliParaformerAsr.Native
         [DllImport(Lib)] internal static extern int pf_vad_model_tensor(IntPtr m, [MarshalAs(UnmanagedType.LPUTF8Str)] string name, [Out] float[]? data,
                                                                        long cap, out long n);
         [DllImport(Lib)] internal static extern int pf_vad_model_config(out PfVadConfig cfg);
+        [DllImport(Lib)] internal static extern int pf_endpoint_model_config(out PfEndpointConfig cfg);
+        [DllImport(Lib)] internal static extern int pf_vad_model_stream_state_bytes(IntPtr m, out long bytes);
         [DllImport(Lib)] internal static extern void pf_vad_model_free(IntPtr m);
         [DllImport(Lib)] internal static extern int pf_engine_set_vad_model(IntPtr e, IntPtr m);
         [DllImport(Lib)] internal static extern int pf_recognizer_set_vad_model(IntPtr r, [MarshalAs(UnmanagedType.LPUTF8Str)] string? pfwPath);

@@ -731,6 +731,46 @@ int pf_host_vad_model_levels(const pf_vad_model* m, const float* rows, int64_t T
    front-end.  A pf_group forward is unaffected. */
 int pf_engine_set_vad_model(pf_engine* e, const pf_vad_model* m);
 
+/* ---- Voice-activity endpointing, streaming, model score (additions to ABI 6; opt-in: without one of these calls nothing of
+   this is launched or allocated and every result is bit for bit what it is without it) ----
+   The level of "Voice-activity endpointing, streaming" taken from the FSMN-VAD network of "Voice-activity segmentation, model
+   score" instead of the log-mel energy, for B streams per call with each stream's history carried between calls
+   (csrc/k_vadnet_stream.hip: ONE launch per call, one workgroup per stream).  The release schedule in Python
+   is tests/vadnet_stream_ref.py.
+   Let left = (lfr_m - 1) / 2 and right = lfr_m - 1 - left; a stream has received n frames so far.
+   The streaming levels (and logits) ARE the levels of "Voice-activity segmentation, model score" over the complete stream,
+   released causally; the device form's are bit-equal to the offline device form's, the host form's to the offline host form's.
+     - level t is released once frame t + right has arrived, or at the flush;
+     - before the flush a stream that has received n frames has released max(0, n - right) levels;
+     - the flush releases the rest, and it is the only place where the LFR upper clamp T - 1 applies (T = the frames received);
+     - the lower clamp to frame 0 and the zero history in front of frame 0 are the offline definition's: a tap whose source
+       lies before frame 0 is skipped, not added as a zero (d <= t on the absolute frame index).
+   The endpoint state machine (steps 2' - 7) is unchanged: it sees the released levels in order, so frame indices and times stay
+   on the caller's clock.  Because a level waits for `right` later frames, AN EVENT CAN FALL ONE CALL LATER than with the energy
+   level.  The decoder-context reset at a sentence end does not reset the network's state: the audio is continuous.
+   The state of a stream is opaque, pf_vad_model_stream_state_bytes bytes (a multiple of 16; about 40 KB at the released
+   dimensions), all zero for a fresh stream.  It holds per layer the last (lorder - 1) * lstride rows of p in fp32, proj padded to
+   32 wide; the last lfr_m - 1 fbank rows received; and in its last 8 bytes the frame count and the flushed flag (int32 each).  The host form has a state of its own
+   (float64 history; pf_host_vad_model_stream_state_bytes): a stream cannot change form between calls.
+   Frames after a flush: PF_ERR_INVALID_ARG, nothing is launched.  A second flush without frames is a no-op.  n_new = 0 without
+   a flush changes no byte of the state.  A count beyond PF_ENDPOINT_MAX_STREAM_FRAMES: PF_ERR_CAPACITY, nothing changed; so is a
+   cap below the levels a call releases (at most n_new + right).
+   LIMIT: the device form keeps two f16 tiles and a stream's fp32 window in LDS:
+     2 * 64 * (widest + 8) * 2 + ((lorder - 1) * lstride + 64) * (round_up(proj_dim, 32) + 4) * 4 <= 159 744 bytes,
+   widest = the widest of input_dim (padded to 16), affine_dim, linear_dim, proj_dim (padded to 32).  A model beyond it is
+   refused with PF_ERR_UNSUPPORTED by pf_op_vad_model_stream and pf_online_recognizer_set_endpoint_model (the released
+   dimensions need 148 272).
+   pf_endpoint_model_config: pf_endpoint_default with rise = -1 and abs_level = 9830, the rule pf_vad_model_config states;
+   these values are again stated, not tuned. */
+int pf_endpoint_model_config(pf_endpoint_config* cfg);
+int pf_vad_model_stream_state_bytes(const pf_vad_model* m, int64_t* bytes);
+/* The host form (plain C++, float64, the per-row code of pf_host_vad_model_logits), ONE stream: n_new rows [n_new, n_mels], then
+   the flush if flush != 0.  state [pf_host_vad_model_stream_state_bytes] in / out; levels [cap] int32 and logits
+   [cap, output_dim] float64 (either may be NULL), of which the first *n_out are written. */
+int pf_host_vad_model_stream_state_bytes(const pf_vad_model* m, int64_t* bytes);
+int pf_host_vad_model_stream(const pf_vad_model* m, void* state, const float* rows, int32_t n_new, int32_t flush, int32_t n_mels,
+                             int32_t* levels, double* logits, int32_t cap, int32_t* n_out);
+
 /* ---- Punctuation (additions to ABI 6; opt-in: with no model attached nothing of this is launched or allocated and every
    result is bit for bit what it is without it) ----
    A CT-Transformer (the punctuation model FunASR pairs with paraformer: VAD -> ASR -> punctuation) marks every word of a text
@@ -980,6 +1020,13 @@ int pf_op_endpoint_update(pf_engine* e, int32_t* states, const int32_t* levels, 
    out [sum T] int32 levels.  An utterance's result does not depend on its batch mates. */
 int pf_op_vad_model_logits(pf_engine* e, const float* rows, const int32_t* T, int32_t B, int32_t n_mels, float* out);
 int pf_op_vad_model_levels(pf_engine* e, const float* rows, const int32_t* T, int32_t B, int32_t n_mels, int32_t* out);
+/* exactly the attached model's streaming launch (k_vadnet_stream.hip, "Voice-activity endpointing, streaming, model score") on
+   caller state blocks and rows, B streams in ONE launch: states [B, pf_vad_model_stream_state_bytes] in / out, rows
+   [B, ld, n_mels] of which stream b's first n_new[b] are read, flush [B] (NULL: none); levels [B, cap] int32 and logits
+   [B, cap, output_dim] fp32 (either may be NULL) of which stream b's first n_out[b] are written; n_out [B].  Errors as stated
+   there; on an argument error nothing is launched and nothing changed. */
+int pf_op_vad_model_stream(pf_engine* e, void* states, const float* rows, const int32_t* n_new, const int32_t* flush, int32_t B,
+                           int32_t ld, int32_t n_mels, int32_t* levels, float* logits, int32_t cap, int32_t* n_out);
 /* exactly the attached punctuation model's launches (k_punc.hip; PF_ERR_INVALID_ARG without pf_engine_set_punc_model) on
    caller windows: the concatenated ids of B windows, T [B] ids each (0 .. PF_PUNC_MAX_WINDOW).
    pf_op_punc_logits: logits [sum T, n_punc] fp32 and, optionally, x0 [sum T, d_model] fp32, the input of layer 0 (1 + 2 n_layers
@@ -1679,6 +1726,16 @@ void pf_online_stream_free(pf_online_stream* s);
    (borrowed: valid until the online stream is freed; NULL without a second pass) — every pf_stream_* getter works on it, times
    inside it are relative to begin_ms. */
 int pf_online_recognizer_set_endpoint(pf_online_recognizer* r, const pf_endpoint_config* cfg);   /* NULL = off */
+/* The FSMN-VAD model score as the detector's level ("Voice-activity endpointing, streaming, model score"): loads the `.pfw` of
+   kind "fsmnvad" as pf_recognizer_set_vad_model does and attaches it to the recognizer's engine; NULL detaches.  The stream
+   launch (profile class "vadnet_stream") then runs where the level launch runs and hands its released counts to the endpoint
+   launch: still one upload and one read-back per call, and a flush releases the held-back levels and flushes the detector in
+   the same launch set, also when the call brought no new rows.  The network states live in a second device buffer of the
+   recognizer, indexed by the detector's slot.  Inert until pf_online_recognizer_set_endpoint; pass pf_endpoint_model_config's
+   thresholds there.  Errors as pf_vad_model_load and pf_engine_set_vad_model (input width, snip_edges); PF_ERR_UNSUPPORTED for a
+   model beyond the LDS limit, and for attaching or detaching while a live stream has already fed the detector: two kinds of
+   level must not meet in one state block. */
+int pf_online_recognizer_set_endpoint_model(pf_online_recognizer* r, const char* pfw_path);     /* NULL = the energy level */
 int pf_online_recognizer_set_second_pass(pf_online_recognizer* r, pf_recognizer* offline);      /* NULL = none */
 int pf_online_stream_input_finished(pf_online_stream* s);
 int pf_online_stream_num_sentences(pf_online_stream* s, int32_t* n);

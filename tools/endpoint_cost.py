@@ -9,9 +9,14 @@
                           online and 2 + 2 layer offline synthetic models: the forwards are NOT the cost of a real model), against
                           the same call without a second pass
 
+  --model                 instead of the above: the same GetResults for 1 and 32 streams with the ENERGY endpoint and with the
+                          FSMN-VAD model score attached (SetEndpointModel; released dimensions, synthetic weights: the cost does
+                          not depend on the values), two recognizers in one process, plus the device time of the classes
+                          `endpoint` and `vadnet_stream` per call (profiles/endpoint_model_cost.json)
+
 Audio: 0.001 N(0, 1) with 0.3 N(0, 1) bursts (tests/vad_ref.py burst_audio).
 
-    python tools/endpoint_cost.py [--steps 10] [--warmup 3] [--out FILE]"""
+    python tools/endpoint_cost.py [--steps 10] [--warmup 3] [--model] [--out FILE]"""
 import argparse
 import ctypes as C
 import json
@@ -37,6 +42,7 @@ from oracle import frontend as fe                                 # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("--steps", type=int, default=10)
 ap.add_argument("--warmup", type=int, default=3)
+ap.add_argument("--model", action="store_true")
 ap.add_argument("--out", default="")
 args = ap.parse_args()
 CHUNK = 9600
@@ -70,8 +76,9 @@ def engine_view(rec):
     return e
 
 
-def timed_calls(rec, n, profile=None):
-    """n fresh streams, warmup + steps calls of one chunk each: the wall clock of GetResults alone, and the `endpoint` class"""
+def timed_calls(rec, n, profile=None, classes=(("endpoint", 2),)):
+    """n fresh streams, warmup + steps calls of one chunk each: the wall clock of GetResults alone, and the device time of the
+    profile classes (name, launches expected per call), summed"""
     calls = args.warmup + args.steps
     audio = [V.burst_audio((calls + 2) * CHUNK // 16000 + 1, [(60, 200), (330, 480), (620, 700)], u) for u in range(n)]
     streams = [rec.CreateOnlineStream() for _ in range(n)]
@@ -90,11 +97,54 @@ def timed_calls(rec, n, profile=None):
         if k > args.warmup:
             wall.append(dt)
             if profile:
-                ms, launches, _ = profile.profile_get("endpoint")
-                assert launches == 2, launches
-                cls.append(ms)
+                total = 0.0
+                for name, expect in classes:
+                    ms, launches, _ = profile.profile_get(name)
+                    assert launches == expect, (name, launches)
+                    total += ms
+                cls.append(total)
     return wall, cls, sum(len(s.Sentences) for s in streams)
 
+
+def model_cost():
+    """the energy endpoint and the model endpoint side by side: one recognizer each (a model is attached before any stream feeds)"""
+    vcfg = W.fsmn_vad_config()
+    vpath = os.path.join(tempfile.mkdtemp(), "vad.pfw")
+    W.save_pfw(vpath, vcfg, W.synth_vad_weights(vcfg, 6))
+    from aliparaformerasr_amd.engine import endpoint_model_config
+    re_, rm = online(W.paraformer_large_config(), 42), online(W.paraformer_large_config(), 42)
+    re_.SetEndpoint()
+    rm.SetEndpointModel(vpath)
+    rm.SetEndpoint(endpoint_model_config())
+    ve, vm = engine_view(re_), engine_view(rm)
+    res = {}
+    for n in (1, 32):
+        e1, _, _ = timed_calls(re_, n)
+        m1, _, _ = timed_calls(rm, n)
+        e2, _, _ = timed_calls(re_, n)                            # the energy form again, behind the model runs: the spread of the box
+        m2, _, _ = timed_calls(rm, n)
+        ve.profile(True)
+        _, ce, _ = timed_calls(re_, n, profile=ve)
+        ve.profile(False)
+        vm.profile(True)
+        _, cm, _ = timed_calls(rm, n, profile=vm, classes=(("vadnet_stream", 1),))
+        _, cb, _ = timed_calls(rm, n, profile=vm, classes=(("vadnet_stream", 1), ("endpoint", 1)))
+        vm.profile(False)
+        res["streams_%d" % n] = dict(get_results_energy_ms=stats(e1 + e2), get_results_model_ms=stats(m1 + m2),
+                                     get_results_energy_runs_ms=[stats(e1), stats(e2)], get_results_model_runs_ms=[stats(m1), stats(m2)],
+                                     endpoint_class_energy_ms=stats(ce), vadnet_stream_class_ms=stats(cm),
+                                     vadnet_stream_plus_endpoint_class_ms=stats(cb))
+    ve._h = vm._h = None
+    re_.Dispose(); rm.Dispose()
+    return res
+
+
+if args.model:
+    line = json.dumps(model_cost())
+    print(line)
+    if args.out:
+        open(args.out, "w").write(line + "\n")
+    sys.exit(0)
 
 out = {}
 rec = online(W.paraformer_large_config(), 42)
