@@ -59,6 +59,15 @@ class PfVadConfig(C.Structure):
                [("reserved", C.c_int32 * 4)]
 
 
+class PfOnlineToken(C.Structure):
+    """pf_online_token (paraformer_hip.h "Streaming token times and scores")"""
+    _fields_ = [("id", C.c_int64), ("time_ms", C.c_int32), ("entry", C.c_int32), ("score", C.c_float), ("flags", C.c_int32)]
+
+
+PF_ONLINE_TOKEN_FIRED = 1
+PF_ONLINE_TOKEN_TIMED = 2
+
+
 class PfEndpointConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("struct_size", "rise", "margin_q", "abs_level", "window", "on_count", "off_count",
                                          "pad_begin", "pad_end", "end_silence", "min_speech", "max_len")] + \
@@ -447,6 +456,9 @@ SIGNATURES = {
     "pf_online_stream_sentence_result": (C.c_int, [_vp, C.c_int32, _P(_vp)]),
     "pf_online_stream_in_speech": (C.c_int, [_vp, _i32, _i32]),
     "pf_online_stream_tokens": (C.c_int, [_vp, _P(_i64), _i32]),
+    "pf_online_recognizer_set_token_info": (C.c_int, [_vp, C.c_int32]),
+    "pf_online_stream_token_info": (C.c_int, [_vp, _P(_P(PfOnlineToken)), _i32]),
+    "pf_online_stream_sentence_tokens": (C.c_int, [_vp, C.c_int32, _P(_P(PfOnlineToken)), _i32]),
     "pf_online_stream_dispose": (None, [_vp]),
     "pf_online_stream_free": (None, [_vp]),
     "pf_online_encoder": (C.c_int, [_vp, _f, C.c_int32, C.c_int32, _f, _f]),
@@ -455,6 +467,11 @@ SIGNATURES = {
     "pf_host_online_posenc": (C.c_int, [_f, C.c_int32, C.c_int32, C.c_int32]),
     "pf_host_online_dynamic_mask": (C.c_int, [_f, C.c_int32]),
     "pf_host_online_cif": (C.c_int, [_f, _f, C.c_int32, C.c_int32, C.c_float, _f, C.c_int32, _i32, _f, _f]),
+    "pf_host_online_cif_state_bytes": (C.c_int, [C.c_int32, _i64]),
+    "pf_host_online_cif_step": (C.c_int, [_vp, _f, _f, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_int32, _f, _i32, C.c_int32,
+                                          _i32]),
+    "pf_op_online_cif_step": (C.c_int, [_vp, _vp, _f, _f, _i32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, _f, _i32,
+                                        C.c_int32, _i32]),
     "pf_host_online_decode": (C.c_int, [_cpp, C.c_int32, _i64, C.c_int32, C.c_char_p, C.c_int32]),
     "pf_host_timestamps": (C.c_int, [_f, C.c_int32, _i64, C.c_int32, _i32, C.c_int32]),
     "pf_host_hotword_ids": (C.c_int, [_cpp, C.c_int32, _cpp, C.c_int32, _i32, C.c_int32, _i32, C.c_int32, _i32]),

@@ -2818,6 +2818,33 @@ int pf_online_stream_in_speech(pf_online_stream* h, int32_t* in_speech, int32_t*
   return PF_OK;
   PF_CATCH
 }
+int pf_online_recognizer_set_token_info(pf_online_recognizer* h, int32_t on) {
+  PF_TRY
+  OR(h)->SetTokenInfo(on != 0);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_online_stream_token_info(pf_online_stream* h, const pf_online_token** toks, int32_t* n) {
+  PF_TRY
+  OnlineStreamM* s = OS(h);
+  std::lock_guard<std::mutex> lk(s->mu);
+  const std::vector<pf_online_token>& t = s->token_info();
+  if (toks) *toks = t.data();
+  if (n) *n = (int32_t)t.size();
+  return PF_OK;
+  PF_CATCH
+}
+int pf_online_stream_sentence_tokens(pf_online_stream* h, int32_t j, const pf_online_token** toks, int32_t* n) {
+  PF_TRY
+  OnlineStreamM* s = OS(h);
+  std::lock_guard<std::mutex> lk(s->mu);
+  PF_CHECK(j >= 0 && j < (int32_t)s->Sentences.size(), PF_ERR_INVALID_ARG, "sentence index out of range");
+  const std::vector<pf_online_token>& t = s->Sentences[(size_t)j].tokens;
+  if (toks) *toks = t.data();
+  if (n) *n = (int32_t)t.size();
+  return PF_OK;
+  PF_CATCH
+}
 void pf_online_stream_free(pf_online_stream* h) {
   if (!h || h->freed) return;
   if (h->s) h->s->disposed = true;
@@ -2842,6 +2869,32 @@ int pf_online_decoder(pf_engine* h, const float* enc, int32_t B, int32_t Tc, con
   std::lock_guard<std::mutex> lk(eh_->mutex());
   PF_CHECK(n_caches == eh_->dec_layers(), PF_ERR_INVALID_ARG, "online_decoder: one cache per decoder layer expected");
   eh_->online_decoder(enc, B, Tc, embeds, L, embeds_len, caches_in, logits_out, ids_out, caches_out);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_host_online_cif_state_bytes(int32_t D, int64_t* bytes) {
+  PF_TRY
+  NEED(bytes);
+  PF_CHECK(D > 0 && D % 4 == 0, PF_ERR_INVALID_ARG, "online_cif_state_bytes: D % 4 == 0 expected");
+  *bytes = (int64_t)online_cif_state_bytes(D);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_host_online_cif_step(void* state, const float* hiddens, const float* alphas, int32_t Tc, int32_t D, float threshold, int32_t lo,
+                            int32_t hi, int32_t reset, float* fired, int32_t* fire_entry, int32_t cap, int32_t* count) {
+  PF_TRY
+  NEED(count);
+  *count = online_cif_step(state, hiddens, alphas, Tc, D, threshold, lo, hi, reset != 0, fired, fire_entry, cap);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_op_online_cif_step(pf_engine* h, void* states, const float* enc, const float* alphas, const int32_t* reset, int32_t B, int32_t Tc,
+                          int32_t D, float threshold, int32_t lo, int32_t hi, float* fired, int32_t* fire_entry, int32_t cap,
+                          int32_t* counts) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  std::lock_guard<std::mutex> lk(eh_->mutex());
+  eh_->op_online_cif_step(states, enc, alphas, reset, B, Tc, D, threshold, lo, hi, fired, fire_entry, cap, counts);
   return PF_OK;
   PF_CATCH
 }

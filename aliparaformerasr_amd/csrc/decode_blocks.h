@@ -89,6 +89,17 @@ struct AlignBlock : Block {
   }
 };
 
+// one stream's carried CIF pair (k_cif_stream.hip, online_cif_step in online.cpp): hidden [D] fp32, the carried frame already
+// divided by the carried integrate | integrate [G] fp32, ONE COPY per kCifStreamGroup channels, G = ceil(D / kCifStreamGroup)
+// (every workgroup of the kernel walks one group of channels and owns that group's copy: no workgroup reads a cell another
+// writes; all copies hold the same bits), padded to a multiple of four cells that nobody writes.  A zero-filled block is the
+// constructor's state.
+constexpr size_t kCifStreamGroup = 256;
+struct CifStreamBlock : Block {
+  Field<float> hidden, integrate; size_t groups;
+  CifStreamBlock(Cursor& c, size_t D) : Block(c), groups((D + kCifStreamGroup - 1) / kCifStreamGroup) { lay(c, hidden, D, integrate, (groups + 3) / 4 * 4); }
+};
+
 // a block on its own, from offset 0: the layout of a host vector
 template <class Blk, class... Dims> Blk block_at_zero(Dims... dims) {
   Cursor c;

@@ -13,6 +13,7 @@
 #include <set>
 
 #include "hostutil.h"
+#include "op_stage.h"
 #include "pfw.h"
 
 namespace pf {
@@ -112,6 +113,8 @@ void Engine::release() {
   if (aux_stream_) { hipStreamSynchronize(aux_stream_); hipStreamDestroy(aux_stream_); aux_stream_ = nullptr; }
   if (plan_host_) { hipHostFree(plan_host_); plan_host_ = nullptr; plan_host_dev_ = nullptr; plan_host_cap_ = 0; }
   if (ev_scan_) { hipEventDestroy(ev_scan_); ev_scan_ = nullptr; }
+  if (step_host_) { hipHostFree(step_host_); step_host_ = nullptr; step_host_dev_ = nullptr; step_host_cap_ = 0; }
+  if (ev_step_) { hipEventDestroy(ev_step_); ev_step_ = nullptr; }
   if (ts_stream_) { hipStreamSynchronize(ts_stream_); hipStreamDestroy(ts_stream_); ts_stream_ = nullptr; }
   if (ev_ts_) { hipEventDestroy(ev_ts_); ev_ts_ = nullptr; }
   if (ev_enc_) { hipEventDestroy(ev_enc_); ev_enc_ = nullptr; }
@@ -122,7 +125,7 @@ void Engine::release() {
   owned_.clear();
   DevBuf* bufs[] = {&ws_f32_, &ws_pcm_, &ws_audio_, &ws_meta_, &ws_fbank_, &ws_speech_, &ws_enc_, &ws_dec_, &ws_kv_, &ws_pe_, &ws_tmp_,
                     &ws_ts_, &ws_seaco_, &ws_seaco_in_, &ws_seaco_hw_, &ws_q_, &ws_qf_, &ws_seaco_q_, &ws_x3a_, &ws_x3t_, &ws_x3h_, &lm_inst_.buf, &lm_op_.buf, &nbs_hot_.buf, &ws_nbs_,
-                    &vadnet_dev_.buf, &ws_vadnet_, &punc_dev_.buf, &ws_punc_, &spk_dev_.buf, &ws_spk_};
+                    &ws_step_, &vadnet_dev_.buf, &ws_vadnet_, &punc_dev_.buf, &ws_punc_, &spk_dev_.buf, &ws_spk_};
   lm_inst_.src.reset(); lm_op_.src.reset(); lm_.reset(); nbs_lm_.reset();
   vadnet_dev_.src.reset(); vadnet_.reset();
   punc_dev_.src.reset(); punc_.reset();
@@ -1662,6 +1665,120 @@ void Engine::online_decoder(const float* enc, int B, int Tc, const float* embeds
   if (logits_out) PF_HIP(hipMemcpy2DAsync(logits_out, (size_t)V * 4, lg, (size_t)ldV * 4, (size_t)V * 4, Md, hipMemcpyDeviceToHost, stream_));
   PF_HIP(hipMemcpyAsync(ids_out, ids, (size_t)Md * 8, hipMemcpyDeviceToHost, stream_));
   PF_HIP(hipMemcpyAsync(caches_out, co, (size_t)nd * B * D * CW * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipStreamSynchronize(stream_));
+}
+
+// ---- the device-resident chunk step (engine.h) ----
+size_t Engine::online_slot_cache_off() const { return (size_t)round_up((int64_t)block_at_zero<CifStreamBlock>(mc_.d_model).bytes(), kAlign); }
+size_t Engine::online_slot_bytes() const {
+  return online_slot_cache_off() + (size_t)round_up((int64_t)dec_.layers.size() * mc_.d_model * (mc_.kernel - 1) * 4, kAlign);
+}
+
+void Engine::online_step(const float* speech, int B, int Tc, char* slots_dev, const int32_t* slot, const int32_t* cif_reset,
+                         const int32_t* cache_reset, int lo, int hi, OnlineStepOut& out) {
+  PF_CHECK(speech && slots_dev && slot && cif_reset && cache_reset && B > 0 && Tc > 0, PF_ERR_INVALID_ARG, "online_step: bad arguments");
+  PF_CHECK(mc_.kind != "sensevoicesmall", PF_ERR_UNSUPPORTED, "online_step: paraformer models only");
+  PF_CHECK(mc_.kernel == 11, PF_ERR_UNSUPPORTED, "online_step: FSMN kernel 11 (cache of 10 columns) only");
+  PF_HIP(hipSetDevice(device_));
+  const int D = mc_.d_model, F = mc_.ffn, V = mc_.vocab, nd = (int)dec_.layers.size(), CW = mc_.kernel - 1;
+  const int M = B * Tc, cap = Tc + 1;
+  const size_t nB = (size_t)B;
+  out.max_tok = 0; out.cap = cap;
+  out.counts.assign(nB, 0); out.fire_entry.assign(nB * cap, -1); out.ids.clear(); out.scores.clear();
+  // 1 - 3: the chunk up, the encoder, the alphas (online_encoder without its downloads)
+  const size_t n = (size_t)M * mc_.feat_dim;
+  ensure(ws_speech_, n * 4);
+  PF_HIP(hipMemcpyAsync(ws_speech_.p, speech, n * 4, hipMemcpyHostToDevice, stream_));
+  encoder((const float*)ws_speech_.p, B, Tc, true);
+  cif_alpha_stage(H16_, B, Tc, h16_, fsm_, alphas_, nullptr);
+  // 4: the carried CIF on the streams' blocks; slot | cif_reset | cache_reset in one upload, counts | fire entries in one export
+  StageCarve st;
+  const auto d_meta = st.take<int32_t>(3 * nB), d_words = st.take<int32_t>(nB + nB * cap);
+  const auto d_fired = st.take<float>(nB * cap * D);
+  ensure(ws_step_, st.off);
+  void* ws = ws_step_.p;
+  std::vector<int32_t> meta(3 * nB);
+  for (int b = 0; b < B; ++b) { meta[b] = slot[b]; meta[nB + b] = cif_reset[b]; meta[2 * nB + b] = cache_reset[b]; }
+  upload(stream_, d_meta(ws), (const int32_t*)meta.data(), meta.size());
+  const int32_t* d_slot = d_meta(ws);
+  int32_t* d_counts = d_words(ws);
+  const int64_t stride = (int64_t)online_slot_bytes(), cache_off = (int64_t)online_slot_cache_off();
+  CifStreamLaunch c{};
+  c.states = slots_dev; c.state_stride = stride; c.slot = d_slot;
+  c.enc = H32_; c.alphas = alphas_; c.lda = Tc + 1; c.reset = d_meta(ws) + nB;
+  c.B = B; c.Tc = Tc; c.D = D; c.threshold = mc_.cif_threshold; c.lo = lo; c.hi = hi;
+  c.fired = d_fired(ws); c.fire_entry = d_words(ws) + nB; c.cap = cap; c.counts = d_counts;
+  prof_begin("cif_stream", 0);
+  launch_cif_stream(stream_, c);
+  prof_end("cif_stream");
+  const int n_words = (int)d_words.count;
+  if (!step_host_tried_ || (step_host_ && step_host_cap_ < n_words)) {
+    step_host_tried_ = true;
+    if (step_host_) { PF_HIP(hipStreamSynchronize(stream_)); hipHostFree(step_host_); step_host_ = nullptr; step_host_dev_ = nullptr; step_host_cap_ = 0; }
+    void* p = nullptr; void* d = nullptr;
+    const int words = std::max(2 * n_words, 1024);
+    if (hipHostMalloc(&p, (size_t)words * 4, hipHostMallocMapped) == hipSuccess && hipHostGetDevicePointer(&d, p, 0) == hipSuccess) {
+      step_host_ = (int32_t*)p; step_host_dev_ = (int32_t*)d; step_host_cap_ = words;
+    } else {
+      (void)hipGetLastError();
+      if (p) hipHostFree(p);
+    }
+    if (!ev_step_) PF_HIP(hipEventCreateWithFlags(&ev_step_, hipEventDisableTiming));
+  }
+  std::vector<int32_t> words((size_t)n_words);
+  if (step_host_) {
+    launch_export_words(stream_, d_words(ws), n_words, step_host_dev_);
+    PF_HIP(hipEventRecord(ev_step_, stream_));
+    PF_HIP(hipEventSynchronize(ev_step_));
+    std::memcpy(words.data(), step_host_, (size_t)n_words * 4);
+  } else {
+    download(stream_, words.data(), (const int32_t*)d_words(ws), (size_t)n_words);
+    PF_HIP(hipStreamSynchronize(stream_));
+  }
+  // 5: the decoder length
+  int L = 0;
+  for (int b = 0; b < B; ++b) {
+    PF_CHECK(words[b] >= 0 && words[b] <= cap, PF_ERR_DEVICE, "online_step: a fire count outside 0 .. Tc + 1");
+    L = std::max(L, (int)words[b]);
+  }
+  std::copy(words.begin(), words.begin() + B, out.counts.begin());
+  std::copy(words.begin() + B, words.end(), out.fire_entry.begin());
+  if (L == 0) return;                                            // OnlineRecognizer.cs:380
+  out.max_tok = L;
+  // 6 - 12: online_decoder on what is already on the device
+  const int Md = B * L;
+  const int64_t Mp = round_up(M, 128) + 128, Mdp = round_up(Md, 128) + 128;
+  const int ldV = (int)round_up(V, 4);
+  half_t* e16 = nullptr; half_t* kv16 = nullptr; float* lg = nullptr; int64_t* ids = nullptr; float* best = nullptr;
+  float* ci = nullptr; float* co = nullptr;
+  DecRun r;
+  r.b = carve_into(ws_dec_, kAlign, [&](Arena& a) {
+    e16 = a.take<half_t>((size_t)Mp * D * 2); kv16 = a.take<half_t>((size_t)Mp * std::max(nd, 1) * 2 * D * 2);
+    const DecBufs d = carve_dec16(a, Mdp, F, false);
+    lg = a.take<float>((size_t)Mdp * ldV * 4); ids = a.take<int64_t>((size_t)Md * 8); best = a.take<float>((size_t)Md * 4);
+    ci = a.take<float>((size_t)nd * B * D * CW * 4); co = a.take<float>((size_t)nd * B * D * CW * 4);
+    return d;
+  });
+  float* xd = r.b.x; float* t32 = r.b.t32; half_t* xdn16 = r.b.xn16;
+  launch_cif_pack(stream_, d_fired(ws), B, cap, L, D, xd);
+  PF_HIP(hipMemsetAsync(e16, 0, (size_t)Mp * D * 2, stream_));
+  launch_f32_to_f16(stream_, H32_, M, D, D, e16, D);
+  const int ldkv = nd * 2 * D;
+  if (nd > 0) {
+    gemm("gemm_dec_kv", dec_.kv_all, e16, D, M, nullptr, 0, kv16, ldkv, nullptr, 0, nullptr, 0, false, 0, 1.f);
+    launch_cif_cache_gather(stream_, slots_dev, stride, cache_off, d_slot, d_meta(ws) + 2 * nB, B, nd, D * CW, ci);
+  }
+  r.B = B; r.L = L; r.token_num = d_counts;
+  r.kv = kv16; r.kv_rs = ldkv; r.kv_bs = (int64_t)Tc * ldkv; r.Lk = Tc;
+  r.cache_in = ci; r.cache_out = co;
+  decoder16(dec_, r);
+  launch_layernorm(stream_, t32, Md, D, dec_.after.g, dec_.after.b, xdn16, D, nullptr, 0);
+  gemm("gemm_vocab", dec_.out, xdn16, D, Md, lg, ldV, nullptr, 0, nullptr, 0, nullptr, 0, false, 0, 1.f);
+  launch_argmax(stream_, lg, Md, V, ldV, 1, ids, best);
+  if (nd > 0) launch_cif_cache_scatter(stream_, slots_dev, stride, cache_off, d_slot, B, nd, D * CW, co);
+  out.ids.resize((size_t)Md); out.scores.resize((size_t)Md);
+  PF_HIP(hipMemcpyAsync(out.ids.data(), ids, (size_t)Md * 8, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipMemcpyAsync(out.scores.data(), best, (size_t)Md * 4, hipMemcpyDeviceToHost, stream_));
   PF_HIP(hipStreamSynchronize(stream_));
 }
 

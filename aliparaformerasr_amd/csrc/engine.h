@@ -340,6 +340,24 @@ class Engine {
   void online_decoder(const float* enc, int B, int Tc, const float* embeds, int L, const int32_t* embeds_len,
                       const float* caches_in, float* logits_out, int64_t* ids_out, float* caches_out);
   int dec_layers() const { return (int)dec_.layers.size(); }
+  // ---- the device-resident chunk step (OnlineRecognizerM with SetTokenInfo) ----
+  // A stream's slot of the recognizer's device buffer: the carried CIF block (decode_blocks.h CifStreamBlock) at byte 0, the
+  // dec_layers() FSMN caches [D, k - 1] fp32 from online_slot_cache_off() on; online_slot_bytes() apart.
+  size_t online_slot_cache_off() const;
+  size_t online_slot_bytes() const;
+  // One chunk of B streams, from the upload of speech [B, Tc, feat_dim] to the ids, without the encoder output, the fired rows
+  // or the caches leaving the device: encoder, cif_alpha_stage, cif_stream_kernel on H32_ / alphas_ and the streams' blocks
+  // (slots_dev + slot[b] * online_slot_bytes(); cif_reset[b] != 0: from a zero block), counts and fire entries to the host
+  // through pinned memory and an event, max_tok = max(counts); 0: return (the carry is updated, the caches are not).  Else the
+  // pack, f32_to_f16 and the K | V product, the cache gather (every layer from the slot's layer-0 cache; cache_reset[b] != 0:
+  // zeros), decoder16 with L = max_tok exactly, layer norm, vocabulary product, arg-max with its winners' log-probs, the cache
+  // scatter, ids and scores back.  out: counts [B], fire_entry [B, Tc + 1], ids / scores [B, max_tok].
+  struct OnlineStepOut { int max_tok = 0, cap = 0; std::vector<int32_t> counts, fire_entry; std::vector<int64_t> ids; std::vector<float> scores; };
+  void online_step(const float* speech, int B, int Tc, char* slots_dev, const int32_t* slot, const int32_t* cif_reset,
+                   const int32_t* cache_reset, int lo, int hi, OnlineStepOut& out);
+  // exactly cif_stream_kernel's launch on caller data through op_stage.h: states [B, online_cif_state_bytes(D)] in / out
+  void op_online_cif_step(void* states, const float* enc, const float* alphas, const int32_t* reset, int B, int Tc, int D, float threshold,
+                          int lo, int hi, float* fired, int32_t* fire_entry, int cap, int32_t* counts);
 
   // ---- stand-alone ops (parity tests) -------------------------------------
   void op_lfr_cmvn_pad(const float* const* fbank, const int32_t* t80, int B, int sentinel, float* out,
@@ -543,6 +561,9 @@ class Engine {
   uint32_t next_dither_seed() { return fc_.dither_seed * 2654435761u + (dither_calls_++) * 40503u; }
   int device_ = 0;
   hipStream_t stream_ = nullptr;
+  int32_t* step_host_ = nullptr; int32_t* step_host_dev_ = nullptr; int step_host_cap_ = 0; bool step_host_tried_ = false;   // online_step: counts | fire entries, pinned
+  hipEvent_t ev_step_ = nullptr;
+  DevBuf ws_step_;                    // online_step: speech-independent scratch that must survive the decoder arena's growth
   int32_t* plan_host_ = nullptr; int32_t* plan_host_dev_ = nullptr; int plan_host_cap_ = 0;   // CIF counts exported into pinned host memory
   void ensure_plan_host(int B);
   void export_plan(int B);

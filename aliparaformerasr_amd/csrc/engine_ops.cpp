@@ -289,6 +289,55 @@ void Engine::endpoint_streams(int32_t* states_dev, const int32_t* slot, const fl
   PF_HIP(hipStreamSynchronize(stream_));
 }
 
+// ---- the carried CIF of the streaming path (k_cif_stream.hip).  The alphas travel with the pipeline's row stride Tc + 1, the
+// cell behind each row hostile, like the rows behind the encoder output; every output is sentinel-filled and must have been
+// written everywhere (the kernel zeroes what it does not fire); the cells behind the state blocks must keep their bits.
+void Engine::op_online_cif_step(void* states, const float* enc, const float* alphas, const int32_t* reset, int B, int Tc, int D, float threshold,
+                                int lo, int hi, float* fired, int32_t* fire_entry, int cap, int32_t* counts) {
+  PF_CHECK(states && enc && alphas && reset && fired && fire_entry && counts, PF_ERR_INVALID_ARG, "online_cif_step: null pointer");
+  PF_CHECK(B > 0 && Tc > 0 && D > 0 && D % 4 == 0 && cap >= Tc + 1, PF_ERR_INVALID_ARG,
+           "online_cif_step: B, Tc > 0, D % 4 == 0 and cap >= Tc + 1 expected");
+  PF_HIP(hipSetDevice(device_));
+  const size_t nB = (size_t)B, sb = block_at_zero<CifStreamBlock>(D).bytes(), lda = (size_t)Tc + 1, tail = 64;
+  StageCarve st;
+  const auto d_state = st.take<uint32_t>(nB * sb / 4 + tail);
+  const auto d_enc = st.take<float>(nB * Tc * D + (size_t)D), d_al = st.take<float>(nB * lda), d_fired = st.take<float>(nB * cap * D);
+  const auto d_reset = st.take<int32_t>(nB), d_ent = st.take<int32_t>(nB * cap), d_cnt = st.take<int32_t>(nB);
+  void* ws = op_ws(st);
+  std::vector<float> e(d_enc.count), al(d_al.count);
+  for (size_t i = 0; i < e.size(); ++i) e[i] = hostile32(i);
+  std::memcpy(e.data(), enc, nB * Tc * D * 4);
+  for (size_t i = 0; i < al.size(); ++i) al[i] = hostile32(i);
+  for (int b = 0; b < B; ++b) std::memcpy(&al[(size_t)b * lda], alphas + (size_t)b * Tc, (size_t)Tc * 4);
+  fill_sentinel(stream_, d_state(ws), d_state.count);
+  upload(stream_, d_state(ws), (const uint32_t*)states, nB * sb / 4);
+  upload(stream_, d_enc(ws), (const float*)e.data(), e.size());
+  upload(stream_, d_al(ws), (const float*)al.data(), al.size());
+  upload(stream_, d_reset(ws), reset, nB);
+  fill_sentinel(stream_, d_fired(ws), d_fired.count);
+  fill_sentinel(stream_, d_ent(ws), d_ent.count);
+  fill_sentinel(stream_, d_cnt(ws), d_cnt.count);
+  CifStreamLaunch c{};
+  c.states = (char*)d_state(ws); c.state_stride = (int64_t)sb; c.slot = nullptr;
+  c.enc = d_enc(ws); c.alphas = d_al(ws); c.lda = (int)lda; c.reset = d_reset(ws);
+  c.B = B; c.Tc = Tc; c.D = D; c.threshold = threshold; c.lo = lo; c.hi = hi;
+  c.fired = d_fired(ws); c.fire_entry = d_ent(ws); c.cap = cap; c.counts = d_cnt(ws);
+  prof_begin("cif_stream", 0);
+  launch_cif_stream(stream_, c);
+  prof_end("cif_stream");
+  const int rows = B * cap;
+  const std::vector<uint32_t> hf = check_guard<uint32_t>(stream_, "online_cif_step: fired", d_fired(ws), kSentinel32, result_geom(rows, rows, D, D, rows));
+  const std::vector<uint32_t> he = check_guard<uint32_t>(stream_, "online_cif_step: fire_entry", d_ent(ws), kSentinel32, result_geom(rows, rows, 1, 1, rows));
+  const std::vector<uint32_t> hc = check_guard<uint32_t>(stream_, "online_cif_step: counts", d_cnt(ws), kSentinel32, result_geom(B, B, 1, 1, B));
+  check_guard<uint32_t>(stream_, "online_cif_step: behind the state blocks", d_state(ws) + nB * sb / 4, kSentinel32, untouched_geom((int64_t)tail));
+  for (int b = 0; b < B; ++b) PF_CHECK((int32_t)hc[b] >= 0 && (int32_t)hc[b] <= Tc + 1, PF_ERR_DEVICE, "online_cif_step: a count outside 0 .. Tc + 1");
+  download(stream_, (uint32_t*)states, (const uint32_t*)d_state(ws), nB * sb / 4);
+  PF_HIP(hipStreamSynchronize(stream_));
+  std::memcpy(fired, hf.data(), hf.size() * 4);
+  std::memcpy(fire_entry, he.data(), he.size() * 4);
+  std::memcpy(counts, hc.data(), hc.size() * 4);
+}
+
 void Engine::vad_segment(const float* const* samples, const int64_t* n, int B, const pf_vad_config* cfg, int32_t* seg, int cap,
                          int32_t* n_seg) {
   vad_check(cfg, fc_.lfr_n);

@@ -525,6 +525,33 @@ void launch_endpoint_update(hipStream_t s, int32_t* states, const int32_t* slot,
                             const int32_t* n_new, const int32_t* flush, int B, const EndpointParams& p, int32_t* events, int cap, int32_t* n_events, int32_t* in_speech,
                             int32_t* open_begin);
 
+// ---------------------------------------------------------------- the carried CIF of the streaming path (k_cif_stream.hip) ------
+// The reference's streaming integrate-and-fire with the carried pair (OnlineRecognizer.cs:146-220); the host statement is
+// online_cif_step (online.cpp), the definition in numpy tests/cif_stream_ref.py.  ONE launch for B streams: stream b = its state
+// block at states + slot[b] * state_stride (slot null: block b; the slots of a launch are distinct; decode_blocks.h
+// CifStreamBlock; read, then written) and Tc rows of enc [B, Tc, D] (dense) with alphas + b * lda.  DynamicMask happens inside:
+// chunk positions < lo and >= hi walk with alpha 0.  reset[b] != 0 (reset may be null): the walk starts from a zero block.
+// Written: fired [B, cap, D], ALL of it (rows at and beyond counts[b] zero), fire_entry [B, cap] (-1 at and beyond counts[b]),
+// counts [B], the state block.  D % 4 == 0, cap >= Tc + 1 (a walk of Tc + 1 entries fires at most that often).
+struct CifStreamLaunch {
+  char* states; int64_t state_stride; const int32_t* slot;
+  const float* enc; const float* alphas; int lda; const int32_t* reset;
+  int B, Tc, D; float threshold; int lo, hi;
+  float* fired; int32_t* fire_entry; int cap; int32_t* counts;
+};
+void launch_cif_stream(hipStream_t s, const CifStreamLaunch& a);
+// The FSMN caches of the streaming decoder between a stream's slot and the decoder's batch.  A slot holds nd caches of DC =
+// D * (k - 1) floats from byte cache_off on.  gather: cin [nd, B, DC], EVERY layer from the slot's LAYER-0 cache (stack_states,
+// OnlineModel.cs:199-220), zeros where reset[b] != 0.  scatter: layer l of slot[b] = cout [l, b, :].  DC % 4 == 0.
+void launch_cif_cache_gather(hipStream_t s, const char* states, int64_t state_stride, int64_t cache_off, const int32_t* slot,
+                             const int32_t* reset, int B, int nd, int DC, float* cin);
+void launch_cif_cache_scatter(hipStream_t s, char* states, int64_t state_stride, int64_t cache_off, const int32_t* slot, int B, int nd,
+                              int DC, const float* cout);
+// rows [0, L) of every stream of fired [B, cap, D] as dst [B, L, D]
+void launch_cif_pack(hipStream_t s, const float* fired, int B, int cap, int L, int D, float* dst);
+// `n` int32 words into pinned host memory through its device alias (as export_plan_kernel): the counts and fire entries of a step
+void launch_export_words(hipStream_t s, const int32_t* src, int n, int32_t* dst_dev);
+
 // ---------------------------------------------------------------- the FSMN-VAD model score (k_vadnet.hip) ------
 // The second form of step 1 of the voice-activity segmentation; the definition in numpy is tests/vadnet_ref.py.  One launch
 // of the 1 + n_layers that make a forward (the plan is at the head of k_vadnet.hip; Engine::run_vadnet fills these in).

@@ -55,12 +55,14 @@ void online_dynamic_mask(std::vector<float>& a, int chunk_size, int lfr) {
 }
 
 void online_cif(const std::vector<std::vector<float>>& hiddens, const std::vector<float>& alphas, float threshold,
-                std::vector<std::vector<float>>& fired, float& carry_alpha, std::vector<float>& carry_hidden) {
+                std::vector<std::vector<float>>& fired, float& carry_alpha, std::vector<float>& carry_hidden,
+                std::vector<int32_t>* fire_entry) {
   // OnlineRecognizer.cs:152-197, float arithmetic, products and sums rounded separately
   const size_t D = hiddens.empty() ? 0 : hiddens[0].size();
   float integrate = 0.0f;
   std::vector<float> frames(D, 0.f);
   fired.clear();
+  if (fire_entry) fire_entry->clear();
   const size_t n = std::min(hiddens.size(), alphas.size());
   for (size_t j = 0; j < n; ++j) {
     const float alpha = alphas[j];
@@ -72,6 +74,7 @@ void online_cif(const std::vector<std::vector<float>>& hiddens, const std::vecto
       const float wgt = threshold - integrate;
       for (size_t k = 0; k < D; ++k) { const volatile float prod = wgt * h[k]; frames[k] += prod; }
       fired.push_back(frames);
+      if (fire_entry) fire_entry->push_back((int32_t)j);
       integrate += alpha;
       integrate -= threshold;
       for (size_t k = 0; k < D; ++k) frames[k] = integrate * h[k];
@@ -81,6 +84,38 @@ void online_cif(const std::vector<std::vector<float>>& hiddens, const std::vecto
   carry_hidden = frames;
   if (integrate > 0.0f)
     for (size_t k = 0; k < D; ++k) carry_hidden[k] = frames[k] / integrate;
+}
+
+// ---- one chunk step of one stream on its state block (decode_blocks.h CifStreamBlock): what cif_stream_kernel computes
+size_t online_cif_state_bytes(int D) { return block_at_zero<CifStreamBlock>(D).bytes(); }
+
+int online_cif_step(void* state, const float* hiddens, const float* alphas, int Tc, int D, float threshold, int lo, int hi, bool reset,
+                    float* fired, int32_t* fire_entry, int cap) {
+  PF_CHECK(state && hiddens && alphas && fired && fire_entry, PF_ERR_INVALID_ARG, "online_cif_step: null pointer");
+  PF_CHECK(Tc > 0 && D > 0 && D % 4 == 0 && cap >= Tc + 1, PF_ERR_INVALID_ARG, "online_cif_step: Tc > 0, D % 4 == 0 and cap >= Tc + 1 expected");
+  const CifStreamBlock blk = block_at_zero<CifStreamBlock>(D);
+  float* s_hidden = blk.hidden(state);
+  float* s_integrate = blk.integrate(state);
+  std::vector<std::vector<float>> h((size_t)Tc + 1);
+  std::vector<float> a((size_t)Tc + 1, 0.f);
+  h[0].assign((size_t)D, 0.f);                                  // entry 0: the carried pair (a reset: the constructor's)
+  if (!reset) { h[0].assign(s_hidden, s_hidden + D); a[0] = s_integrate[0]; }
+  for (int t = 0; t < Tc; ++t) {
+    h[(size_t)t + 1].assign(hiddens + (size_t)t * D, hiddens + (size_t)(t + 1) * D);
+    a[(size_t)t + 1] = (t >= lo && t < hi) ? alphas[t] : 0.f;   // DynamicMask
+  }
+  std::vector<std::vector<float>> f;
+  std::vector<float> ch;
+  std::vector<int32_t> ent;
+  float ca = 0.f;
+  online_cif(h, a, threshold, f, ca, ch, &ent);
+  std::memcpy(s_hidden, ch.data(), (size_t)D * 4);
+  for (size_t g = 0; g < blk.groups; ++g) s_integrate[g] = ca;  // one copy per channel group; the padding cells keep their bits
+  const int count = (int)f.size();                              // <= Tc + 1 <= cap
+  std::memset(fired, 0, (size_t)cap * D * 4);
+  for (int l = 0; l < cap; ++l) fire_entry[l] = l < count ? ent[(size_t)l] : -1;
+  for (int l = 0; l < count; ++l) std::memcpy(fired + (size_t)l * D, f[(size_t)l].data(), (size_t)D * 4);
+  return count;
 }
 
 static bool is_chinese_all(const std::string& s) {             // ^[一-龥]+$  (OnlineRecognizer.cs:446-458)
@@ -129,7 +164,13 @@ OnlineStreamM::OnlineStreamM(std::shared_ptr<OnlineRecognizerM> r) : owner(std::
 }
 
 OnlineStreamM::~OnlineStreamM() {
-  if (ep_slot_ >= 0 && owner) owner->release_slot(ep_slot_);
+  if (owner && (slot_ >= 0 || ep_joined_ || decoded_)) owner->release_stream(slot_, ep_joined_, decoded_);
+}
+
+const std::vector<pf_online_token>& OnlineStreamM::token_info() {
+  if (owner && owner->token_info_on())
+    while (TokenInfo.size() < Tokens.size()) TokenInfo.push_back(pf_online_token{Tokens[TokenInfo.size()], -1, -1, 0.f, 0});
+  return TokenInfo;
 }
 
 void OnlineStreamM::AddSamples(const float* samples, int64_t n) {
@@ -173,9 +214,16 @@ void OnlineStreamM::InputFinished() {
 
 void OnlineStreamM::ResetDecoder() {                            // (the caller holds mu)
   Tokens.clear();
-  for (std::vector<float>& st : States) std::fill(st.begin(), st.end(), 0.f);
-  CifHidden.assign(1, std::vector<float>((size_t)512, 0.f));
-  CifAlpha.assign(1, 0.f);
+  TokenInfo.clear();
+  if (owner->token_info_on()) {                                 // the context lives in the slot: its next step starts from zeros
+    cif_reset_ = cache_reset_ = true;
+  } else {
+    for (std::vector<float>& st : States) std::fill(st.begin(), st.end(), 0.f);
+    CifHidden.assign(1, std::vector<float>((size_t)512, 0.f));
+    CifAlpha.assign(1, 0.f);
+  }
+  std::fill(cache_idx_.begin(), cache_idx_.end(), (int64_t)-1); // the cached rows become zero rows: no provenance
+  carry_idx_ = -1;
   std::fill(cache_feats_.begin(), cache_feats_.end(), 0.f);
   start_idx_ = 0;
 }
@@ -197,12 +245,15 @@ void OnlineStreamM::InputSpeech(const std::vector<float>& samples, size_t n_call
     ep_audio_.insert(ep_audio_.end(), samples.begin(), samples.begin() + (long)n_caller);
     ep_samples_ += (int64_t)n_caller;
   }
+  const int64_t first = n_caller > 0 ? caller_samples_ : -1;             // the rows' provenance: frame r starts at first + 160 r
   caller_samples_ += (int64_t)n_caller;
   if (first_input_ && t80 > 0) {                                          // :131-143: the first frame is repeated once
     Speech.insert(Speech.end(), fb.begin(), fb.begin() + 80);
+    speech_idx_.push_back(first);
     first_input_ = false;
   }
   Speech.insert(Speech.end(), fb.begin(), fb.end());
+  for (int r = 0; r < t80; ++r) speech_idx_.push_back(first < 0 ? -1 : first + 160 * (int64_t)r);
 }
 
 bool OnlineStreamM::GetDecodeChunk(std::vector<float>& chunk) {
@@ -210,6 +261,9 @@ bool OnlineStreamM::GetDecodeChunk(std::vector<float>& chunk) {
   const int F = 80, CL = owner->chunk_length();
   if ((size_t)CL * F > Speech.size()) return false;
   std::vector<float> pad;
+  std::vector<int64_t> pidx(1, cache_lfr_splice_.empty() ? speech_idx_[0] : splice_idx_);   // provenance travels with the rows
+  pidx.insert(pidx.end(), speech_idx_.begin(), speech_idx_.begin() + CL);
+  splice_idx_ = pidx.back();
   if (!cache_lfr_splice_.empty()) pad = cache_lfr_splice_;                // :172-178
   else pad.assign(Speech.begin(), Speech.begin() + F);                    // :180-187: first frame once more
   pad.insert(pad.end(), Speech.begin(), Speech.begin() + (long)CL * F);
@@ -230,6 +284,14 @@ bool OnlineStreamM::GetDecodeChunk(std::vector<float>& chunk) {
   online_position_encode(x, timesteps, W, start_idx_);                    // :195-196
   chunk = cache_feats_;
   chunk.insert(chunk.end(), x.begin(), x.end());
+  const bool lfr = c.lfr_m != 1 || c.lfr_n != 1;
+  chunk_idx_ = cache_idx_;
+  for (int i = 0; i < timesteps; ++i) {                                   // an LFR frame takes the index of its first row
+    const size_t r = lfr ? (size_t)i * (size_t)c.lfr_n : (size_t)i;
+    chunk_idx_.push_back(r < pidx.size() ? pidx[r] : -1);
+  }
+  cache_idx_.assign(chunk_idx_.end() - (long)cache_idx_.size(), chunk_idx_.end());
+  speech_idx_.erase(speech_idx_.begin(), speech_idx_.begin() + CL);
   start_idx_ += timesteps;
   cache_feats_.assign(chunk.end() - (long)cache_feats_.size(), chunk.end());   // :201
   Speech.erase(Speech.begin(), Speech.begin() + (long)CL * F);            // RemoveChunk :210-224
@@ -282,6 +344,7 @@ void OnlineRecognizerM::Dispose() {
     std::lock_guard<std::mutex> lk2(ep_mu_);
     if (ep_states_) { hipSetDevice(e->device()); hipFree(ep_states_); ep_states_ = nullptr; ep_cap_ = 0; ep_free_.clear(); }
     if (ep_net_states_) { hipSetDevice(e->device()); hipFree(ep_net_states_); ep_net_states_ = nullptr; }
+    if (ti_states_) { hipSetDevice(e->device()); hipFree(ti_states_); ti_states_ = nullptr; }
     ep_model_.reset();
     second_.reset();
   }
@@ -312,7 +375,7 @@ void OnlineRecognizerM::SetEndpointModel(const std::string& pfw_path) {
   std::lock_guard<std::mutex> lk(eh->mutex());
   std::lock_guard<std::mutex> lk2(ep_mu_);
   if (!vm && !ep_model_) return;
-  PF_CHECK((int)ep_free_.size() == ep_cap_, PF_ERR_UNSUPPORTED,
+  PF_CHECK(ep_live_ == 0, PF_ERR_UNSUPPORTED,
            "endpoint model: a live stream has already fed the detector (attach or detach before the first GetResults with audio)");
   eh->set_vad_model(vm);                                        // the refusals of pf_engine_set_vad_model
   PF_HIP(hipSetDevice(eh->device()));
@@ -323,7 +386,10 @@ void OnlineRecognizerM::SetEndpointModel(const std::string& pfw_path) {
   }
   ep_model_ = vm;
   ep_net_bytes_ = vm ? (size_t)vad_stream_layout(*vm).bytes : 0;
-  if (vm && ep_cap_ > 0) PF_HIP(hipMalloc((void**)&ep_net_states_, (size_t)ep_cap_ * ep_net_bytes_));
+  if (vm && ep_cap_ > 0) {
+    PF_HIP(hipMalloc((void**)&ep_net_states_, (size_t)ep_cap_ * ep_net_bytes_));
+    PF_HIP(hipMemsetAsync(ep_net_states_, 0, (size_t)ep_cap_ * ep_net_bytes_, eh->stream()));
+  }
 }
 
 void OnlineRecognizerM::SetSecondPass(std::shared_ptr<Recognizer> offline) {
@@ -336,9 +402,60 @@ void OnlineRecognizerM::SetSecondPass(std::shared_ptr<Recognizer> offline) {
   second_ = std::move(offline);
 }
 
-void OnlineRecognizerM::release_slot(int slot) {
+void OnlineRecognizerM::release_stream(int slot, bool ep_joined, bool decoded) {
   std::lock_guard<std::mutex> lk(ep_mu_);
   if (ep_states_ && slot >= 0 && slot < ep_cap_) ep_free_.push_back(slot);
+  if (ep_joined) --ep_live_;
+  if (decoded) --decoded_live_;
+}
+
+void OnlineRecognizerM::SetTokenInfo(bool on) {
+  if (disposed_) throw Error(PF_ERR_DISPOSED, "OnlineRecognizer");
+  std::shared_ptr<Engine> eh = engine();
+  if (!eh) throw Error(PF_ERR_DISPOSED, "OnlineRecognizer");
+  std::lock_guard<std::mutex> lk(eh->mutex());
+  std::lock_guard<std::mutex> lk2(ep_mu_);
+  if (on == ti_on_.load()) return;
+  PF_CHECK(decoded_live_ == 0, PF_ERR_UNSUPPORTED,
+           "token info: a live stream has already decoded a chunk (turn the mode on or off before the first GetResults with audio)");
+  PF_HIP(hipSetDevice(eh->device()));
+  if (ti_states_) {
+    PF_HIP(hipStreamSynchronize(eh->stream()));
+    PF_HIP(hipFree(ti_states_));
+    ti_states_ = nullptr;
+  }
+  ti_bytes_ = on ? eh->online_slot_bytes() : 0;
+  if (on && ep_cap_ > 0) PF_HIP(hipMalloc((void**)&ti_states_, (size_t)ep_cap_ * ti_bytes_));
+  ti_on_ = on;
+}
+
+// grows one per-stream buffer from ep_cap_ to cap slots of `bytes` each (the old blocks copied on the device)
+template <class T> static void grow_slots(Engine* e, T*& buf, int old_cap, int cap, size_t bytes) {
+  T* p = nullptr;
+  PF_HIP(hipMalloc((void**)&p, (size_t)cap * bytes));
+  if (buf) {
+    PF_HIP(hipMemcpyAsync(p, buf, (size_t)old_cap * bytes, hipMemcpyDeviceToDevice, e->stream()));
+    PF_HIP(hipStreamSynchronize(e->stream()));
+    PF_HIP(hipFree(buf));
+  }
+  buf = p;
+}
+
+void OnlineRecognizerM::ensure_slot(OnlineStreamM* s, Engine* e) {
+  if (s->slot_ >= 0) return;
+  std::lock_guard<std::mutex> ls(ep_mu_);
+  PF_HIP(hipSetDevice(e->device()));
+  if (ep_free_.empty()) {
+    const int cap = std::max(64, 2 * ep_cap_);
+    grow_slots(e, ep_states_, ep_cap_, cap, (size_t)PF_ENDPOINT_STATE_INTS * 4);
+    if (ep_model_) grow_slots(e, ep_net_states_, ep_cap_, cap, ep_net_bytes_);   // the network's states grow with the detector's
+    if (ti_on_) grow_slots(e, ti_states_, ep_cap_, cap, ti_bytes_);              // and so does the decoder state
+    for (int i = cap - 1; i >= ep_cap_; --i) ep_free_.push_back(i);
+    ep_cap_ = cap;
+  }
+  s->slot_ = ep_free_.back();
+  ep_free_.pop_back();
+  s->cif_reset_ = s->cache_reset_ = true;                       // a reused slot's decoder state starts from zeros on its first step
 }
 
 // The detector's launch set for the call's streams that have new caller frames or a flush to make, the sentences its events
@@ -379,40 +496,20 @@ void OnlineRecognizerM::ForwardEndpoint(const std::vector<OnlineStreamM*>& strea
     }
     if (work.empty()) return;
     const int B = (int)work.size();
-    {                                                           // a slot of the state buffer per stream, zeroed when handed out
-      std::lock_guard<std::mutex> ls(ep_mu_);
-      PF_HIP(hipSetDevice(e->device()));
-      for (OnlineStreamM* s : work) {
-        if (s->ep_slot_ >= 0) continue;
-        if (ep_free_.empty()) {
-          const int cap = std::max(64, 2 * ep_cap_);
-          int32_t* p = nullptr;
-          PF_HIP(hipMalloc((void**)&p, (size_t)cap * PF_ENDPOINT_STATE_INTS * 4));
-          if (ep_states_) {
-            PF_HIP(hipMemcpyAsync(p, ep_states_, (size_t)ep_cap_ * PF_ENDPOINT_STATE_INTS * 4, hipMemcpyDeviceToDevice, e->stream()));
-            PF_HIP(hipStreamSynchronize(e->stream()));
-            PF_HIP(hipFree(ep_states_));
-          }
-          if (net) {                                            // the network's states grow with the detector's
-            char* q = nullptr;
-            PF_HIP(hipMalloc((void**)&q, (size_t)cap * ep_net_bytes_));
-            if (ep_net_states_) {
-              PF_HIP(hipMemcpyAsync(q, ep_net_states_, (size_t)ep_cap_ * ep_net_bytes_, hipMemcpyDeviceToDevice, e->stream()));
-              PF_HIP(hipStreamSynchronize(e->stream()));
-              PF_HIP(hipFree(ep_net_states_));
-            }
-            ep_net_states_ = q;
-          }
-          for (int i = cap - 1; i >= ep_cap_; --i) ep_free_.push_back(i);
-          ep_states_ = p;
-          ep_cap_ = cap;
-        }
-        s->ep_slot_ = ep_free_.back();
-        ep_free_.pop_back();
-        PF_HIP(hipMemsetAsync(ep_states_ + (size_t)s->ep_slot_ * PF_ENDPOINT_STATE_INTS, 0, PF_ENDPOINT_STATE_INTS * 4, e->stream()));
-        if (net) PF_HIP(hipMemsetAsync(ep_net_states_ + (size_t)s->ep_slot_ * ep_net_bytes_, 0, ep_net_bytes_, e->stream()));
+    for (OnlineStreamM* s : work) {
+      ensure_slot(s, e);
+      // The detector's and the network's block are zeroed where the stream JOINS the detector, not where its slot was handed
+      // out: a stream of a recognizer with SetTokenInfo holds its slot from its first decode on, and the network's buffer may
+      // have been allocated (SetEndpointModel) or the detector turned on since.
+      if (!s->ep_joined_) {
+        std::lock_guard<std::mutex> ls(ep_mu_);
+        PF_HIP(hipSetDevice(e->device()));
+        PF_HIP(hipMemsetAsync(ep_states_ + (size_t)s->slot_ * PF_ENDPOINT_STATE_INTS, 0, PF_ENDPOINT_STATE_INTS * 4, e->stream()));
+        if (net) PF_HIP(hipMemsetAsync(ep_net_states_ + (size_t)s->slot_ * ep_net_bytes_, 0, ep_net_bytes_, e->stream()));
+        s->ep_joined_ = true;
+        ++ep_live_;
       }
-      for (OnlineStreamM* s : work) slot.push_back(s->ep_slot_);
+      slot.push_back(s->slot_);
     }
     // an event per level at most and one for the flush; with the model a call releases up to `right` levels more than it brought
     const int right = net ? net->lfr_m - 1 - (net->lfr_m - 1) / 2 : 0;
@@ -436,6 +533,7 @@ void OnlineRecognizerM::ForwardEndpoint(const std::vector<OnlineStreamM*>& strea
         sen.kind = ev[3 * k + 2];
         sen.first_pass = online_decode_text(tokens_, s->Tokens);            // after this chunk's ids were appended
         sen.text = sen.first_pass;
+        sen.tokens = s->token_info();                                        // (cleared with Tokens at the reset)
         s->ResetDecoder();
         const int64_t a0 = 160 * fb - s->ep_audio_base_, a1 = std::min<int64_t>(s->ep_samples_, 160 * fe) - s->ep_audio_base_;
         PF_CHECK(a0 >= 0 && a1 > a0 && a1 <= (int64_t)s->ep_audio_.size(), PF_ERR_RECOGNITION, "endpoint: a sentence outside the retained audio");
@@ -482,6 +580,10 @@ void OnlineRecognizerM::ForwardEndpoint(const std::vector<OnlineStreamM*>& strea
 
 void OnlineRecognizerM::Forward(const std::vector<OnlineStreamM*>& streams) {
   if (streams.empty()) return;
+  if (token_info_on())                                          // the slots of a launch are distinct: refused before a chunk is taken
+    for (size_t i = 0; i < streams.size(); ++i)
+      for (size_t j = 0; j < i; ++j)
+        PF_CHECK(streams[i] != streams[j], PF_ERR_INVALID_ARG, "token info: a stream twice in one GetResults");
   std::vector<OnlineStreamM*> work;
   std::vector<std::vector<float>> chunks;
   for (OnlineStreamM* s : streams) {                            // :349-363
@@ -509,6 +611,9 @@ void OnlineRecognizerM::Forward(const std::vector<OnlineStreamM*>& streams) {
     }
     for (float& v : speech) v = v == 0.f ? -23.025850929940457f : v;
     const int Tc = (int)(maxlen / W);
+    for (OnlineStreamM* s : work)
+      if (!s->decoded_) { std::lock_guard<std::mutex> ls(ep_mu_); s->decoded_ = true; ++decoded_live_; }
+    if (token_info_on()) { ForwardDevice(e, work, speech, Tc); return; }
     // stack_states (OnlineModel.cs:199-220): EVERY layer's in_cache is built from the streams' LAYER-0 state
     std::vector<float> cin((size_t)nd * B * D * CW);
     for (int l = 0; l < nd; ++l)
@@ -566,6 +671,54 @@ void OnlineRecognizerM::Forward(const std::vector<OnlineStreamM*>& streams) {
   } catch (const Error& ex) {
     if (ex.code == PF_ERR_RECOGNITION && std::string(ex.what()).rfind("Online recognition failed", 0) == 0) throw;
     throw Error(PF_ERR_RECOGNITION, std::string("Online recognition failed: ") + ex.what());   // :397-400
+  }
+}
+
+// Forward with SetTokenInfo: the chunk step on the device (Engine::online_step), then ids, scores, fire entries and times per stream.
+// The decoder state of a stream is its slot of ti_states_; nothing of it is mirrored on the host.
+void OnlineRecognizerM::ForwardDevice(Engine* e, const std::vector<OnlineStreamM*>& work, const std::vector<float>& speech, int Tc) {
+  const int B = (int)work.size(), lo = 5, hi = 15;             // DynamicMask (OnlineModel.cs:141-165): chunk_size 5, lfr 10
+  PF_CHECK(speech.size() == (size_t)B * Tc * 560, PF_ERR_RECOGNITION, "Destination array was not long enough (PadSequence)");
+  for (int i = 0; i < B; ++i)                                   // (Forward has refused this already; a race with SetTokenInfo ends here)
+    for (int j = 0; j < i; ++j) PF_CHECK(work[(size_t)i] != work[(size_t)j], PF_ERR_INVALID_ARG, "token info: a stream twice in one GetResults");
+  std::vector<int32_t> slot((size_t)B), cif_reset((size_t)B), cache_reset((size_t)B);
+  for (int b = 0; b < B; ++b) {
+    OnlineStreamM* s = work[(size_t)b];
+    ensure_slot(s, e);
+    slot[(size_t)b] = s->slot_; cif_reset[(size_t)b] = s->cif_reset_ ? 1 : 0; cache_reset[(size_t)b] = s->cache_reset_ ? 1 : 0;
+  }
+  char* states = nullptr;
+  { std::lock_guard<std::mutex> ls(ep_mu_); states = ti_states_; }
+  PF_CHECK(states != nullptr, PF_ERR_DEVICE, "token info: no state buffer");
+  Engine::OnlineStepOut out;
+  e->online_step(speech.data(), B, Tc, states, slot.data(), cif_reset.data(), cache_reset.data(), lo, hi, out);
+  const int L = out.max_tok, cap = out.cap;
+  const int64_t fs = conf_.fs > 0 ? conf_.fs : 16000;
+  for (int b = 0; b < B; ++b) {
+    OnlineStreamM* s = work[(size_t)b];
+    std::lock_guard<std::mutex> ls(s->mu);
+    s->cif_reset_ = false;
+    if (L > 0) s->cache_reset_ = false;                         // (no decoder ran: the caches still await their reset)
+    s->token_info();
+    // the time rule: the first position >= p of this chunk whose frame has an index, else the caller samples consumed so far
+    auto index_from = [&](int p) {
+      for (int q = std::max(p, 0); q < Tc && q < (int)s->chunk_idx_.size(); ++q)
+        if (s->chunk_idx_[(size_t)q] >= 0) return s->chunk_idx_[(size_t)q];
+      return s->caller_samples_;
+    };
+    const int count = out.counts[(size_t)b];
+    for (int l = 0; l < L; ++l) {                               // :389: ALL max_tok positions are appended
+      pf_online_token t{out.ids[(size_t)b * L + l], -1, -1, out.scores[(size_t)b * L + l], 0};
+      if (l < count) {
+        t.entry = out.fire_entry[(size_t)b * cap + l];
+        const int64_t idx = t.entry == 0 ? (s->carry_idx_ >= 0 ? s->carry_idx_ : s->caller_samples_) : index_from(t.entry - 1);
+        t.time_ms = (int32_t)(idx * 1000 / fs);
+        t.flags = PF_ONLINE_TOKEN_FIRED | PF_ONLINE_TOKEN_TIMED;
+      }
+      s->Tokens.push_back(t.id);
+      s->TokenInfo.push_back(t);
+    }
+    s->carry_idx_ = index_from(hi - 1);                         // what a token fired on the next chunk's carry takes
   }
 }
 

@@ -30,7 +30,16 @@ void online_dynamic_mask(std::vector<float>& alphas, int chunk_size = 5, int lfr
 // one stream's share of PredictorProj (:146-197): integrate-and-fire over [carried pair ; new frames].
 // hiddens [n][D], alphas [n]; returns fired frames; carry_alpha / carry_hidden = the new cache
 void online_cif(const std::vector<std::vector<float>>& hiddens, const std::vector<float>& alphas, float threshold,
-                std::vector<std::vector<float>>& fired, float& carry_alpha, std::vector<float>& carry_hidden);
+                std::vector<std::vector<float>>& fired, float& carry_alpha, std::vector<float>& carry_hidden,
+                std::vector<int32_t>* fire_entry = nullptr);   // fire_entry: the walked entry that completed each fired frame
+// One chunk step of one stream on its carried state block (decode_blocks.h CifStreamBlock, online_cif_state_bytes(D) bytes; a
+// zero-filled block is the constructor's state): DynamicMask with [lo, hi) inside, online_cif over [carry ; Tc frames], the new
+// carry written back.  fired [cap, D] (rows at and beyond the count zero), fire_entry [cap] (entry 0 = the carry, entry j =
+// chunk position j - 1; -1 at and beyond the count).  Returns the count.  cif_stream_kernel (k_cif_stream.hip) is its device
+// twin, bit for bit.  PF_ERR_INVALID_ARG: null pointers, Tc <= 0, D % 4 != 0, cap < Tc + 1.
+size_t online_cif_state_bytes(int D);
+int online_cif_step(void* state, const float* hiddens, const float* alphas, int Tc, int D, float threshold, int lo, int hi, bool reset,
+                    float* fired, int32_t* fire_entry, int cap);
 // OnlineRecognizer.DecodeMulti (:405-437) for one stream
 std::string online_decode_text(const std::vector<std::string>& tokens, const std::vector<int64_t>& ids);
 
@@ -50,12 +59,19 @@ class OnlineStreamM {
   void InputFinished();
   // a finished sentence: [begin_ms, end_ms) in the caller's audio, PF_ENDPOINT_* kind, the online model's text at the closing
   // chunk, the second pass's text (= first_pass without one) and the offline stream that produced it (null without one)
-  struct SentenceM { int begin_ms = 0, end_ms = 0, kind = 0; std::string first_pass, text; std::shared_ptr<Stream> offline; };
+  struct SentenceM {
+    int begin_ms = 0, end_ms = 0, kind = 0; std::string first_pass, text; std::shared_ptr<Stream> offline;
+    std::vector<pf_online_token> tokens;                      // TokenInfo as of the closing call (empty without SetTokenInfo)
+  };
   std::vector<SentenceM> Sentences;
   bool InSpeech = false;                                      // a sentence is open (as of the last GetResults)
   int OpenBeginMs = -1;
   bool GetDecodeChunk(std::vector<float>& chunk);             // :162-208 (chunk = [10 cached ; 10 new] x 560), false = not enough frames
   std::vector<int64_t> Tokens{0, 0};                          // :52
+  // SetTokenInfo: what is known about Tokens[i], index for index (paraformer_hip.h "Streaming token times and scores");
+  // token_info() first brings it to Tokens' length (the constructor's zeros: no flags).  Empty with the mode off.
+  std::vector<pf_online_token> TokenInfo;
+  const std::vector<pf_online_token>& token_info();           // (the caller holds mu)
   std::vector<std::vector<float>> States;                     // 16 x [512*10]
   std::vector<std::vector<float>> CifHidden;                  // carried hidden(s)
   std::vector<float> CifAlpha;
@@ -80,7 +96,16 @@ class OnlineStreamM {
   bool finished_ = false;
   // endpointing: the detector's frame 0 is the caller's sample ep_origin_; ep_rows_ = fbank rows not yet sent to the detector;
   // ep_audio_ = the caller's samples from ep_audio_base_ (relative to ep_origin_) on; ep_fed_ = frames sent so far
-  int ep_slot_ = -1;
+  // slot_: the stream's slot in EVERY per-stream device buffer of the recognizer (detector state, network state, decoder state);
+  // taken when the first of them is needed, released in the destructor
+  int slot_ = -1;
+  bool ep_joined_ = false, decoded_ = false;                  // has fed the detector / has decoded a chunk (SetEndpointModel, SetTokenInfo)
+  // SetTokenInfo: the decoder context lives in the slot; these ask the next step to start the CIF block / the caches from zeros
+  bool cif_reset_ = true, cache_reset_ = true;
+  // provenance of the time rule: the caller-sample index (-1: none) of every row of Speech, of the splice row, of the ten cached
+  // feature rows, of the rows of the chunk GetDecodeChunk built last, and of position hi - 1 of the chunk decoded last
+  std::vector<int64_t> speech_idx_, cache_idx_ = std::vector<int64_t>(10, -1), chunk_idx_;
+  int64_t splice_idx_ = -1, carry_idx_ = -1;
   int64_t ep_origin_ = -1, ep_audio_base_ = 0, ep_samples_ = 0;
   std::vector<float> ep_rows_, ep_audio_;
   int ep_fed_ = 0, ep_prev_end_ = 0;
@@ -118,13 +143,24 @@ class OnlineRecognizerM : public std::enable_shared_from_this<OnlineRecognizerM>
   // fed the detector (two kinds of level must not meet in one state block).
   void SetEndpointModel(const std::string& pfw_path);
   bool endpoint_on() const { return ep_on_.load(); }
-  void release_slot(int slot);
+  // Token times and scores (paraformer_hip.h "Streaming token times and scores"): with the mode on Forward runs
+  // Engine::online_step — the carried CIF and the FSMN caches stay in the stream's slot of a device buffer — and fills
+  // OnlineStreamM::TokenInfo.  PF_ERR_UNSUPPORTED once a live stream has decoded a chunk; the value it already has is a no-op.
+  void SetTokenInfo(bool on);
+  bool token_info_on() const { return ti_on_.load(); }
+  void release_stream(int slot, bool ep_joined, bool decoded);   // ~OnlineStreamM
 
  private:
   void Forward(const std::vector<OnlineStreamM*>& streams);   // :336-403
   void ForwardEndpoint(const std::vector<OnlineStreamM*>& streams);
+  void ForwardDevice(Engine* e, const std::vector<OnlineStreamM*>& work, const std::vector<float>& speech, int Tc);
+  // a slot for a stream that has none (the engine's mutex is held): every per-stream buffer grows together by reallocate-and-copy
+  // on the device; the detector's and the network's blocks are zeroed where the stream joins the detector (ForwardEndpoint),
+  // the decoder state by its reset flags
+  void ensure_slot(OnlineStreamM* s, Engine* e);
+  std::atomic<bool> ti_on_{false};
   std::atomic<bool> ep_on_{false};
-  std::mutex ep_mu_;                                          // guards the eight below
+  std::mutex ep_mu_;                                          // guards the eight below and the four behind them
   pf_endpoint_config ep_cfg_{};
   std::shared_ptr<Recognizer> second_;
   int32_t* ep_states_ = nullptr;                              // [ep_cap_, PF_ENDPOINT_STATE_INTS] on the device, a block per stream slot
@@ -133,6 +169,9 @@ class OnlineRecognizerM : public std::enable_shared_from_this<OnlineRecognizerM>
   std::shared_ptr<const VadModel> ep_model_;                  // the model score (SetEndpointModel); null: the energy level
   char* ep_net_states_ = nullptr;                             // [ep_cap_, ep_net_bytes_] on the device: the network's state per slot
   size_t ep_net_bytes_ = 0;
+  char* ti_states_ = nullptr;                                 // [ep_cap_, ti_bytes_] on the device: CIF block | FSMN caches per slot (SetTokenInfo)
+  size_t ti_bytes_ = 0;
+  int ep_live_ = 0, decoded_live_ = 0;                        // live streams that have fed the detector / decoded a chunk
   std::mutex mu_;
   std::shared_ptr<Engine> engine_;
   ConfEntity conf_;

@@ -2,7 +2,7 @@
 
     python -m aliparaformerasr_amd.examples -type offline -method batch -base <dir> -model <name> \
         [-accuracy int8] [-threads 2] [-decode ctc|frames] [-intake host|device] [-nbest N [-topk K] [-beam W | -search W] [-hotboost S] [-lm FILE [-lmweight A] [-lmbonus B] [-lmeos]]] [-align FILE|beam] [-vad [key=value,...] [-vadmodel FILE] [-spk FILE [key=value,...]]] [-punc FILE] -files a.wav b.wav
-    python -m aliparaformerasr_amd.examples -type online -method one -base <dir> -model <name> [-endpoint [key=value,...] [-vadmodel FILE] [-secondpass <offline name>]] -files a.wav
+    python -m aliparaformerasr_amd.examples -type online -method one -base <dir> -model <name> [-endpoint [key=value,...] [-vadmodel FILE] [-secondpass <offline name>]] [-tokentimes] -files a.wav
 
 Mirrors (file:line in /root/reference/AliParaformerAsr.Examples):
   * argument handling and defaults — Program.cs:93-104, ParseArgs :197-252: the MANYSPEECH_BASE / _TYPE / _BATCH / _MODEL /
@@ -67,7 +67,9 @@ end_silence, min_speech, max_len); the defaults are unvalidated on real speech.
 `.pfw` of kind fsmnvad, as above) with each stream's history carried between chunks; the model's default thresholds (rise=-1,
 abs_level=9830; unvalidated too) apply unless keys are given.  A sentence line can come one chunk later than with the energy level.
 `-secondpass NAME` (with `-endpoint`; OnlineRecognizer.SetSecondPass) re-recognises every finished sentence with the OFFLINE model
-in directory NAME under -base (its files chosen as `-type offline` chooses them): the sentence lines then carry its text."""
+in directory NAME under -base (its files chosen as `-type offline` chooses them): the sentence lines then carry its text.
+`-tokentimes` (online; OnlineRecognizer.SetTokenInfo) prints under each result one line of `token[time_ms score]` for the tokens
+the stream fired (special tokens left out); with `-endpoint` also under each `[begin-end ms]` line, for the closed sentence.  A time is the start of the 60 ms frame in which the token fired, not a word boundary."""
 from __future__ import annotations
 
 import ctypes as C
@@ -434,8 +436,30 @@ def get_file_chunk_samples(path: str, chunk: int = 160 * 6 * 10):
     return [s[i: i + chunk] for i in range(0, len(s), chunk)], dur
 
 
+SPECIAL_TOKENS = ("</s>", "<s>", "<blank>", "<unk>")
+
+
+def read_token_table(path):
+    with open(path, encoding="utf-8") as f:
+        return [ln.rstrip("\n") for ln in f]
+
+
+def token_times_line(info, names):
+    """`token[time_ms score]` for the fired, non-special tokens of OnlineStream.TokenInfo, up to the first </s> (id 2: where
+    the text ends too)"""
+    out = []
+    for t in info:
+        if t.id == 2:
+            break
+        name = names[t.id] if 0 <= t.id < len(names) else "<%d>" % t.id
+        if t.fired and name not in SPECIAL_TOKENS:
+            out.append("%s[%d %.3f]" % (name, t.time_ms, t.score))
+    return " ".join(out)
+
+
 def online_recognizer(method="one", model="speech_paraformer-large_asr_nat-zh-cn-16k-common-vocab8404-online-onnx",
-                      accuracy="int8", threads=2, files=None, base=None, out=sys.stdout, endpoint=None, secondpass=None, vadmodel=None):
+                      accuracy="int8", threads=2, files=None, base=None, out=sys.stdout, endpoint=None, secondpass=None, vadmodel=None,
+                      tokentimes=False):
     from .online_recognizer import OnlineRecognizer
     base = base or os.getcwd()
     if not model:
@@ -453,6 +477,9 @@ def online_recognizer(method="one", model="speech_paraformer-large_asr_nat-zh-cn
         print("Init models failure!", file=out)
         return None
     second = None
+    if tokentimes:
+        rec.SetTokenInfo(True)
+        names = read_token_table(sel["tokensFilePath"])
     if endpoint is not None:
         try:
             if vadmodel:                                    # the model's default thresholds unless keys are given
@@ -508,8 +535,12 @@ def online_recognizer(method="one", model="speech_paraformer-large_asr_nat-zh-cn
                     sens = st.Sentences
                     for sen in sens[shown:]:
                         print("[%d-%d ms] %s" % (sen.begin_ms, sen.end_ms, sen.text), file=out)
+                        if tokentimes:                      # TokenInfo was cleared at the reset: the sentence kept its own
+                            print(token_times_line(sen.tokens, names), file=out)
                     shown = len(sens)
                 print(r.Text, file=out)
+                if tokentimes:
+                    print(token_times_line(st.TokenInfo, names), file=out)
                 texts.append(r.Text)
             for c in chunks:
                 st.AddSamples(c)
@@ -610,6 +641,8 @@ def parse_args(argv, env=None):
                 i += 1
                 text = argv[i]
             cfg["endpoint"] = parse_endpoint_option(text)
+        elif a == "-tokentimes":
+            cfg["tokentimes"] = True
         elif a == "-secondpass":
             i += 1
             if i >= len(argv) or argv[i].startswith("-"):
@@ -682,6 +715,8 @@ def parse_args(argv, env=None):
         raise ValueError("-punc is an offline option")
     if "spk" in cfg and "vad" not in cfg:
         raise ValueError("-spk goes with -vad")
+    if "tokentimes" in cfg and cfg.get("recognizerType") != "online":
+        raise ValueError("-tokentimes goes with -type online")
     if "vadmodel" in cfg and "vad" not in cfg and "endpoint" not in cfg:
         raise ValueError("-vadmodel goes with -vad (offline) or -endpoint (online)")
     if cfg.get("align") == "beam" and "beam" not in cfg:
@@ -700,7 +735,7 @@ def main(argv=None):
     if cfg["recognizerType"] == "online":
         online_recognizer(cfg["methodType"], cfg["modelName"], cfg["modelAccuracy"], cfg["threads"], cfg["files"],
                           cfg["modelBasePath"] or None, endpoint=cfg.get("endpoint"), secondpass=cfg.get("secondpass"),
-                          vadmodel=cfg.get("vadmodel"))
+                          vadmodel=cfg.get("vadmodel"), tokentimes=bool(cfg.get("tokentimes")))
     elif cfg["recognizerType"] == "offline":
         offline_recognizer(cfg["methodType"], cfg["modelName"], cfg["modelAccuracy"], cfg["threads"], cfg["files"],
                            cfg["modelBasePath"] or None, decode=cfg.get("decode", "frames"), intake=cfg.get("intake", "host"),

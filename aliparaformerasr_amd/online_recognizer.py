@@ -23,16 +23,46 @@ class OnlineSentence:
     Scores, alternatives, punctuation, whatever the offline recognizer has set — or None without a second pass."""
     KINDS = {N.PF_ENDPOINT_SILENCE: "silence", N.PF_ENDPOINT_FORCED: "forced", N.PF_ENDPOINT_FLUSH: "flush"}
 
-    def __init__(self, begin_ms, end_ms, kind, first_pass, text, result):
+    def __init__(self, begin_ms, end_ms, kind, first_pass, text, result, tokens=None):
         self.begin_ms, self.end_ms, self.kind, self.first_pass, self.text, self.result = begin_ms, end_ms, kind, first_pass, text, result
+        self.tokens = [] if tokens is None else tokens   # the stream's TokenInfo as of the closing call (OnlineRecognizer.SetTokenInfo)
 
     def __repr__(self):
         return "OnlineSentence(%d, %d, %r, %r)" % (self.begin_ms, self.end_ms, self.kind, self.text)
 
 
+class OnlineToken(tuple):
+    """(id, time_ms, score, fired) of one position of OnlineStream.Tokens; .entry: the walked entry of [carry ; chunk] that
+    completed the token (0: the carry, j: chunk position j - 1, -1: not fired); .score_bits: the score's float32 bits."""
+
+    def __new__(cls, t):
+        self = super().__new__(cls, (int(t.id), int(t.time_ms), float(t.score), bool(t.flags & N.PF_ONLINE_TOKEN_FIRED)))
+        self.entry, self.flags = int(t.entry), int(t.flags)
+        self.score_bits = int(np.float32(t.score).view(np.uint32))
+        return self
+
+    id = property(lambda self: self[0])
+    time_ms = property(lambda self: self[1])
+    score = property(lambda self: self[2])
+    fired = property(lambda self: self[3])
+
+
+def _tokens(p, n):
+    return [OnlineToken(p[i]) for i in range(n)]
+
+
 class OnlineStream:
     def __init__(self, lib, handle, recognizer):
         self._lib, self._h, self._recognizer = lib, handle, recognizer
+
+    @property
+    def TokenInfo(self) -> List[OnlineToken]:
+        """With OnlineRecognizer.SetTokenInfo: (id, time_ms, score, fired) for Tokens[i], index for index; [] with the mode off.
+        time_ms (-1 where fired is False) is the start of the 60 ms frame in which the integrator crossed the threshold, in the
+        caller's audio: not a word boundary, and not validated on real speech.  score: the log-probability of the id."""
+        p, n = C.POINTER(N.PfOnlineToken)(), C.c_int32()
+        _ck(self._lib.pf_online_stream_token_info(self._h, C.byref(p), n))
+        return _tokens(p, n.value)
 
     def InputFinished(self) -> None:
         """No more audio follows: the cached samples go through the front-end (the last ones zero-padded to one chunk, so the
@@ -55,8 +85,10 @@ class OnlineStream:
             if h.value:
                 res = OfflineStream(_lib=self._lib, _handle=h, _recognizer=None)
                 res._borrowed = self                     # the handle belongs to this stream: never freed by the view
+            tp, tn = C.POINTER(N.PfOnlineToken)(), C.c_int32()
+            _ck(self._lib.pf_online_stream_sentence_tokens(self._h, j, C.byref(tp), tn))
             out.append(OnlineSentence(b.value, e.value, OnlineSentence.KINDS.get(k.value, k.value), (fp.value or b"").decode("utf-8"),
-                                      (tx.value or b"").decode("utf-8"), res))
+                                      (tx.value or b"").decode("utf-8"), res, _tokens(tp, tn.value)))
         return out
 
     @property
@@ -106,6 +138,13 @@ class OnlineRecognizer:
         s = C.c_void_p()
         _ck(self._lib.pf_online_create_stream(self._h, C.byref(s)))
         return OnlineStream(self._lib, s, self)
+
+    def SetTokenInfo(self, on=True) -> None:
+        """Token times and scores (pf_online_recognizer_set_token_info; off by default): every chunk step then stays on the
+        device from the encoder to the ids, the carried CIF runs as a kernel, and every stream fills TokenInfo (closed sentences:
+        OnlineSentence.tokens).  Tokens and Text are what they are with the mode off.  Refused once a live stream of this
+        recognizer has decoded a chunk."""
+        _ck(self._lib.pf_online_recognizer_set_token_info(self._h, 1 if on else 0))
 
     def SetEndpointModel(self, pfwPath) -> None:
         """The FSMN-VAD model score as the endpoint detector's level (pf_online_recognizer_set_endpoint_model): a `.pfw` of kind

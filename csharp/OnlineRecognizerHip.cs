@@ -34,6 +34,9 @@ namespace AliParaformerAsr.Hip
             out IntPtr firstPassUtf8, out IntPtr textUtf8);
         [DllImport(Lib)] internal static extern int pf_online_stream_sentence_result(IntPtr s, int j, out IntPtr offlineStream);
         [DllImport(Lib)] internal static extern int pf_online_stream_in_speech(IntPtr s, out int inSpeech, out int beginMs);
+        [DllImport(Lib)] internal static extern int pf_online_recognizer_set_token_info(IntPtr r, int on);
+        [DllImport(Lib)] internal static extern int pf_online_stream_token_info(IntPtr s, out IntPtr toks, out int n);
+        [DllImport(Lib)] internal static extern int pf_online_stream_sentence_tokens(IntPtr s, int j, out IntPtr toks, out int n);
         [DllImport(Lib)] internal static extern void pf_online_stream_dispose(IntPtr s);
         [DllImport(Lib)] internal static extern void pf_online_stream_free(IntPtr s);
     }
@@ -54,6 +57,31 @@ namespace AliParaformerAsr.Hip
         public int NumSentences
         {
             get { ParaformerHip.Check(OnlineNative.pf_online_stream_num_sentences(Handle, out int n)); return n; }
+        }
+
+        // pf_online_token, 24 bytes: id, time_ms, entry, score, flags (flags 1: a token this stream fired; 2: TimeMs is set)
+        [StructLayout(LayoutKind.Sequential)]
+        public struct OnlineToken { public long Id; public int TimeMs; public int Entry; public float Score; public int Flags; }
+
+        static OnlineToken[] ReadTokens(IntPtr p, int n)
+        {
+            var t = new OnlineToken[n];
+            for (int i = 0; i < n; ++i) t[i] = Marshal.PtrToStructure<OnlineToken>(p + 24 * i);
+            return t;
+        }
+
+        // OnlineRecognizer.SetTokenInfo: what is known about Tokens[i], index for index.  TimeMs is the start of the 60 ms frame
+        // in which the integrator crossed the threshold: not a word boundary, not validated on real speech.
+        public OnlineToken[] TokenInfo
+        {
+            get { ParaformerHip.Check(OnlineNative.pf_online_stream_token_info(Handle, out IntPtr p, out int n)); return ReadTokens(p, n); }
+        }
+
+        // the token info sentence j kept from its first pass
+        public OnlineToken[] SentenceTokens(int j)
+        {
+            ParaformerHip.Check(OnlineNative.pf_online_stream_sentence_tokens(Handle, j, out IntPtr p, out int n));
+            return ReadTokens(p, n);
         }
 
         public void Dispose()
@@ -115,6 +143,11 @@ namespace AliParaformerAsr.Hip
         // SetEndpoint; pass pf_endpoint_model_config's thresholds there (stated, not tuned).
         public void SetEndpointModel(string? pfwPath)
             => ParaformerHip.Check(OnlineNative.pf_online_recognizer_set_endpoint_model(_h, pfwPath));
+
+        // Token times and scores: the chunk step stays on the device and every stream fills OnlineStream.TokenInfo.  Refused once
+        // a live stream has decoded a chunk.
+        public void SetTokenInfo(bool on = true)
+            => ParaformerHip.Check(OnlineNative.pf_online_recognizer_set_token_info(_h, on ? 1 : 0));
 
         // the offline recognizer's native handle that re-recognises every finished sentence (IntPtr.Zero: none)
         public void SetSecondPass(IntPtr offlineRecognizerHandle)

@@ -1743,6 +1743,43 @@ int pf_online_stream_sentence(pf_online_stream* s, int32_t j, int32_t* begin_ms,
                               const char** first_pass_utf8, const char** text_utf8);
 int pf_online_stream_sentence_result(pf_online_stream* s, int32_t j, pf_stream** offline_stream);
 int pf_online_stream_in_speech(pf_online_stream* s, int32_t* in_speech, int32_t* begin_ms);
+/* ---- Streaming token times and scores (additions to ABI 6; opt-in: without pf_online_recognizer_set_token_info(r, 1) every
+   streaming call makes the launches and returns the bytes it does without it) ----
+   With the mode on a chunk step stays on the device from the encoder to the ids (Engine::online_step): the carried CIF runs
+   as a kernel on a per-stream state block (k_cif_stream.hip; the host statement is pf_host_online_cif_step), the FSMN caches
+   live in the stream's slot of a device buffer, and only the fire counts and fire entries cross to the host in between.  The
+   ids are the ids of the mode-off path.  token_info[i] describes Tokens[i], index for index (n == number of Tokens):
+     id       Tokens[i]
+     flags    PF_ONLINE_TOKEN_FIRED: a token this stream's integrator fired.  0 for the constructor's two leading zeros and for
+              the positions a stream receives because ALL ids of a decoder batch are appended to every stream of the call
+              (OnlineRecognizer.cs:389); those positions still carry their arg-max score.
+     entry    the walked entry of [carry ; chunk] that completed the token: 0 the carry, j the chunk position j - 1; -1 unfired
+     score    the log-probability of id, bit for bit what pf_online_decoder stores at [b, l, id] of its log-probs
+     time_ms  with PF_ONLINE_TOKEN_TIMED, else -1.  THE START OF THE 60 ms FRAME IN WHICH THE INTEGRATOR CROSSED THE THRESHOLD,
+              in the caller's audio.  It is NOT a word boundary and has not been validated on real speech (there is no corpus
+              here).  It comes from provenance: every fbank row carries the caller-sample index of its frame start (row r of a
+              chunk whose first caller sample is c: c + 160 r; rows of the constructor's chunk of silence: none); the repeated
+              first row, the LFR splice row and the ten cached feature rows carry what they copy (after a sentence reset the
+              cached ten carry none); an LFR frame takes the index of its first row.  A token fired at chunk position p takes
+              the first position >= p of that chunk whose frame has an index (none: the caller samples that have gone through
+              the front-end so far); a token fired on the carry takes the time of position hi - 1 = 14 of the previous chunk.
+              time_ms = floor(index * 1000 / fs).  The rows pf_online_stream_input_finished pads behind the caller's
+              last sample keep the frame grid of their chunk, so a token fired there can report a time up to 600 ms past
+              the end of the caller's audio.
+   A sentence closed by the endpoint detector keeps the token info of its first pass (Tokens is cleared at the reset):
+   pf_online_stream_sentence_tokens.  The pointers stay valid until the stream's next pf_online_get_results or its free.
+   pf_online_recognizer_set_token_info: PF_ERR_UNSUPPORTED once a live stream of the recognizer has decoded a chunk (host-carried
+   and device-carried state must not meet in one stream); on == 0 on a fresh recognizer is a no-op.  With the mode off
+   pf_online_stream_token_info returns n == 0.  The streams' decoder state is then not readable from the host.
+   With the mode on a stream may be passed ONCE per pf_online_get_results (a stream's slot is written by one workgroup set per
+   launch): a list that names a stream twice is refused with PF_ERR_INVALID_ARG before any stream's chunk is taken.  The
+   mode-off path accepts such a list, as the reference does. */
+typedef struct { int64_t id; int32_t time_ms; int32_t entry; float score; int32_t flags; } pf_online_token;
+#define PF_ONLINE_TOKEN_FIRED 1   /* this position is a token this stream fired (not the two leading zeros, not batch padding) */
+#define PF_ONLINE_TOKEN_TIMED 2   /* time_ms is set */
+int pf_online_recognizer_set_token_info(pf_online_recognizer* r, int32_t on);
+int pf_online_stream_token_info(pf_online_stream* s, const pf_online_token** toks, int32_t* n);   /* n == number of Tokens, index for index */
+int pf_online_stream_sentence_tokens(pf_online_stream* s, int32_t j, const pf_online_token** toks, int32_t* n);
 /* Device seams = the two InferenceSession.Run calls (OnlineRecognizer.cs:83, :296).
    encoder: speech [B,Tc,560] (scaled + position-encoded by the caller) -> enc [B,Tc,512], alphas [B,Tc].
    decoder: enc, acoustic_embeds [B,L,512] + lengths, in_cache [n_caches][B,512,10] -> log-probs [B,L,V] (optional),
@@ -1759,6 +1796,21 @@ int pf_host_online_posenc(float* x, int32_t timesteps, int32_t dim, int32_t star
 int pf_host_online_dynamic_mask(float* alphas, int32_t n);
 int pf_host_online_cif(const float* hiddens, const float* alphas, int32_t n, int32_t D, float threshold, float* fired,
                        int32_t fired_cap, int32_t* n_fired, float* carry_alpha, float* carry_hidden);
+/* The carried CIF of one chunk step (k_cif_stream.hip), host statement and device op, bit-equal in every output and state byte.
+   state: one stream's block of pf_host_online_cif_state_bytes(D) bytes = hidden [D] fp32 (the carried frame, already divided by
+   the carried integrate) | the carried integrate, one equal copy per 256 channels, padded to four cells; zero-filled = the
+   constructor's state.  The step walks [carry ; Tc frames]: chunk positions < lo and >= hi with alpha 0 (DynamicMask: lo 5, hi
+   15), fire on !(alpha + integrate < threshold), products and sums rounded separately, the new carry = frames / integrate when
+   integrate > 0, else frames.  reset != 0: the walk starts from a zero block.  fired [cap, D] (rows at and beyond count zero),
+   fire_entry [cap] (0 = the carry, j = chunk position j - 1; -1 at and beyond count).  The op takes B streams (states [B,
+   state_bytes], enc [B, Tc, D], alphas [B, Tc], reset [B]) in ONE launch through the staging kit with its guards on every output.
+   PF_ERR_INVALID_ARG: null pointers, cap < Tc + 1, D % 4 != 0, B <= 0, Tc <= 0. */
+int pf_host_online_cif_state_bytes(int32_t D, int64_t* bytes);
+int pf_host_online_cif_step(void* state, const float* hiddens, const float* alphas, int32_t Tc, int32_t D, float threshold, int32_t lo,
+                            int32_t hi, int32_t reset, float* fired, int32_t* fire_entry, int32_t cap, int32_t* count);
+int pf_op_online_cif_step(pf_engine* e, void* states, const float* enc, const float* alphas, const int32_t* reset, int32_t B, int32_t Tc,
+                          int32_t D, float threshold, int32_t lo, int32_t hi, float* fired, int32_t* fire_entry, int32_t cap,
+                          int32_t* counts);
 int pf_host_online_decode(const char* const* tokens, int32_t n_tokens, const int64_t* ids, int32_t n_ids, char* out,
                           int32_t cap);
 

@@ -1,6 +1,7 @@
 """Streaming path timing (the reference publishes rtf 0.1064 for its online recogniser on an i7-10750H,
 README.EN.md:183-185): paraformer-large geometry, N concurrent streams fed 0.6 s pieces (= one 60-frame chunk per call),
-GetResults after every piece.  Prints rtf = wall / audio per stream count."""
+GetResults after every piece.  Prints rtf = wall / audio per stream count.  --token-info: with OnlineRecognizer.SetTokenInfo (the
+device-resident chunk step; tools/online_token_info_cost.py compares the two modes in alternated pairs)."""
 import os, sys, time, tempfile
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -18,6 +19,8 @@ open(os.path.join(d, "am.mvn"), "w").write(fe.format_mvn_text(sh, sc))
 open(os.path.join(d, "asr.yaml"), "w").write("model: paraformer\nfrontend_conf:\n  dither: 0\n")
 open(os.path.join(d, "tokens.txt"), "w").write("\n".join("t%d" % i for i in range(cfg["vocab"])) + "\n")
 rec = OnlineRecognizer(os.path.join(d, "model.pfw"), "", os.path.join(d, "asr.yaml"), os.path.join(d, "am.mvn"), os.path.join(d, "tokens.txt"))
+if "--token-info" in sys.argv[1:]:
+    rec.SetTokenInfo(True)
 SEC = 12
 for n in (1, 8, 32):
     audio = [W.synth_audio(16000 * SEC, u) for u in range(n)]
