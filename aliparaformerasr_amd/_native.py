@@ -388,6 +388,9 @@ SIGNATURES = {
     "pf_op_layernorm_ex": (C.c_int, [_vp, _f, _f, _f, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P(C.c_uint16), _f]),
     "pf_op_layernorm_f16": (C.c_int, [_vp, _P(C.c_uint16), _f, _f, C.c_int64, C.c_int32, C.c_int32, _P(C.c_uint16)]),
     "pf_op_fsmn_dec_stream": (C.c_int, [_vp, _f, _f, _i32, _f, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f, _f, _f]),
+    "pf_op_fsmn_enc_ex": (C.c_int, [_vp, _P(C.c_uint16), _f] + [C.c_int32] * 6 + [_f]),
+    "pf_op_fsmn_f32_ex": (C.c_int, [_vp, _f, _f, _f] + [C.c_int32] * 7 + [_f]),
+    "pf_op_fsmn_dec_ex": (C.c_int, [_vp, _f, _f, _i32] + [C.c_int32] * 5 + [_f, _f]),
     "pf_op_embed_gather": (C.c_int, [_vp, _f, _i32, C.c_int32, C.c_int32, C.c_int32, _f, _P(C.c_uint16)]),
     "pf_op_add_to_f16": (C.c_int, [_vp, _f, _f, C.c_int64, C.c_int32, _P(C.c_uint16)]),
     "pf_op_seaco_merge": (C.c_int, [_vp, _f, C.c_int32, _i64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _f, C.c_int32, _i64, _f, _i64]),

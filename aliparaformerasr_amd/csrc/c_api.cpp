@@ -1706,6 +1706,39 @@ int pf_op_fsmn_dec_stream(pf_engine* h, const float* tn, const float* taps, cons
   return PF_OK;
   PF_CATCH
 }
+int pf_op_fsmn_enc_ex(pf_engine* h, const uint16_t* v16, const float* taps, int32_t B, int32_t T, int32_t D, int32_t k, int32_t ldv,
+                      int32_t col, float* y_out) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  NEED(v16); NEED(taps); NEED(y_out);
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->op_fsmn_enc_ex(v16, taps, B, T, D, k, ldv, col, y_out);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_op_fsmn_f32_ex(pf_engine* h, const float* v, const float* taps, const float* mask, int32_t B, int32_t T, int32_t D, int32_t k,
+                      int32_t ldv, int32_t col, int32_t form, float* y_out) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  NEED(v); NEED(taps); NEED(y_out);
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->op_fsmn_f32_ex(v, taps, mask, B, T, D, k, ldv, col, form, y_out);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_op_fsmn_dec_ex(pf_engine* h, const float* tn, const float* taps, const int32_t* token_num, int32_t B, int32_t L, int32_t D,
+                      int32_t k, int32_t hostile, const float* x, float* x_out) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  NEED(tn); NEED(taps); NEED(token_num); NEED(x); NEED(x_out);
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->op_fsmn_dec_ex(tn, taps, token_num, B, L, D, k, hostile, x, x_out);
+  return PF_OK;
+  PF_CATCH
+}
 int pf_op_embed_gather(pf_engine* h, const float* table, const int32_t* ids, int32_t rows, int32_t D, int32_t vocab, float* out32,
                        uint16_t* out16) {
   PF_TRY

@@ -400,6 +400,12 @@ class Engine {
   void op_layernorm_f16(const uint16_t* x, const float* g, const float* b, int64_t rows, int D, int in_place, uint16_t* out);
   void op_fsmn_dec_stream(const float* tn, const float* taps, const int32_t* len, const float* cache_in, int B, int L, int D, int k,
                           const float* x, float* x_out, float* cache_out);
+  // the stand-alone FSMN memory blocks (k_misc.hip) on a hostile host, results guarded (tests/fsmn_ref.py); taps [k, D]
+  void op_fsmn_enc_ex(const uint16_t* v16, const float* taps, int B, int T, int D, int k, int ldv, int col, float* y_out);
+  void op_fsmn_f32_ex(const float* v, const float* taps, const float* mask, int B, int T, int D, int k, int ldv, int col, int form,
+                      float* y_out);
+  void op_fsmn_dec_ex(const float* tn, const float* taps, const int32_t* token_num, int B, int L, int D, int k, int hostile,
+                      const float* x, float* x_out);
   void op_embed_gather(const float* table, const int32_t* ids, int rows, int D, int vocab, float* out32, uint16_t* out16);
   void op_add_to_f16(const float* a, const float* b, int64_t rows, int D, uint16_t* out16);
   void op_seaco_merge(const float* dha, int ld_dha, const int64_t* dha_ids, int64_t rows, int V, int nobias, int copy_logits,
@@ -553,6 +559,7 @@ class Engine {
   void prof_end(const char* cls);
   // a stand-alone op's timed launch loop (engine_ops.cpp): PF_OP_REPEAT launches, class "gemm_op" then "gemm_op_warm"
   template <class Fn> void op_timed(double flops, Fn launch);
+  template <class Fn> void fsmn_timed(Fn launch);
   void* op_ws(const struct StageCarve& st);                  // ws_tmp_ grown to the carve's size (op_stage.h)
 
   // dither stream: seed of call c = hash(dither_seed, c); an engine built with the same seed replays the same

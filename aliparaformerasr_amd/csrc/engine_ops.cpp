@@ -2056,6 +2056,120 @@ void Engine::op_fsmn_dec_stream(const float* tn, const float* taps, const int32_
   PF_HIP(hipStreamSynchronize(stream_));
 }
 
+// ---- the stand-alone FSMN memory blocks of k_misc.hip (tests/fsmn_ref.py).  Each operand lies in a buffer that holds a large
+// finite pattern everywhere else (the Q | K columns beside V, kFsmnTailRows rows behind row B T - 1), each result in a guarded
+// buffer that goes back whole; the launch is timed as class "gemm_op" so that the kernel the launcher noted can be read.
+namespace {
+constexpr int kFsmnTailRows = 16;                 // more than the longest half window (k = 21: 10 rows)
+void fsmn_ex_shape(const char* op, int B, int T, int D, int k, int ldv, int col) {
+  PF_CHECK(B > 0 && T > 0 && D > 0 && k > 0 && k < 64 && (int64_t)B * T * std::max(ldv, D) < (1 << 26), PF_ERR_INVALID_ARG,
+           std::string(op) + ": bad shape");
+  PF_CHECK(col >= 0 && ldv >= col + D, PF_ERR_INVALID_ARG, std::string(op) + ": the V columns [col, col + D) must lie inside a row of ldv cells");
+}
+}  // namespace
+
+// one launch as class "gemm_op"; a launcher that refuses (it throws before it launches) leaves the class closed
+template <class Fn> void Engine::fsmn_timed(Fn launch) {
+  prof_begin("gemm_op", 0);
+  try {
+    launch();
+  } catch (...) {
+    prof_end("gemm_op");
+    throw;
+  }
+  prof_end("gemm_op");
+}
+
+void Engine::op_fsmn_enc_ex(const uint16_t* v16, const float* taps, int B, int T, int D, int k, int ldv, int col, float* y_out) {
+  PF_HIP(hipSetDevice(device_));
+  fsmn_ex_shape("fsmn_enc_ex", B, T, D, k, ldv, col);
+  const int64_t M = (int64_t)B * T, Mv = M + kFsmnTailRows;
+  const size_t ny = (size_t)(M + 2 * kG) * D;
+  StageCarve st;
+  const auto dv = st.take<uint16_t>((size_t)Mv * ldv);
+  const auto dw = st.take<float>((size_t)k * D), dy = st.take<float>(ny);
+  void* ws = op_ws(st);
+  {
+    std::vector<uint16_t> img((size_t)Mv * ldv);
+    for (size_t i = 0; i < img.size(); ++i) img[i] = hostile16_bits(i);
+    for (int64_t m = 0; m < M; ++m) std::memcpy(&img[(size_t)m * ldv + col], v16 + (size_t)m * D, (size_t)D * 2);
+    upload_sync(stream_, dv(ws), img);
+  }
+  upload(stream_, dw(ws), taps, (size_t)k * D);
+  fill_sentinel(stream_, dy(ws), ny);
+  fsmn_timed([&] { launch_fsmn_enc(stream_, (const half_t*)dv(ws) + col, ldv, dw(ws), B, T, D, k, dy(ws) + (size_t)kG * D); });
+  download(stream_, y_out, (const float*)dy(ws), ny);
+  PF_HIP(hipStreamSynchronize(stream_));
+}
+
+// form 0: what the pipeline launches — launch_fsmn_f32 on dense rows (ldv == D), launch_fsmn_f32_ld on strided ones (the fp32
+// engine's V third; no mask);  1: launch_fsmn_f32 with fsmn_f32_kernel<0> forced (dense rows, no mask);  2: launch_fsmn_f32 with
+// the result placed on the operand, which the launcher must refuse before anything runs.
+void Engine::op_fsmn_f32_ex(const float* v, const float* taps, const float* mask, int B, int T, int D, int k, int ldv, int col, int form,
+                            float* y_out) {
+  PF_HIP(hipSetDevice(device_));
+  fsmn_ex_shape("fsmn_f32_ex", B, T, D, k, ldv, col);
+  PF_CHECK(form >= 0 && form <= 2 && D % 4 == 0, PF_ERR_INVALID_ARG, "fsmn_f32_ex: form 0 | 1 | 2, D a multiple of 4");
+  const bool dense = ldv == D && col == 0;
+  PF_CHECK(dense || (form == 0 && !mask), PF_ERR_UNSUPPORTED, "fsmn_f32_ex: only the unmasked launcher's-choice form takes a row stride");
+  PF_CHECK(form != 1 || !mask, PF_ERR_INVALID_ARG, "fsmn_f32_ex: form 1 is the unmasked generic kernel");
+  const int64_t M = (int64_t)B * T, Mv = M + kFsmnTailRows;
+  const size_t ny = (size_t)(M + 2 * kG) * D;
+  StageCarve st;
+  const auto dv = st.take<float>((size_t)Mv * ldv), dw = st.take<float>((size_t)k * D), dm = st.take<float>((size_t)M);
+  const auto dy = st.take<float>(ny);
+  void* ws = op_ws(st);
+  {
+    std::vector<float> img((size_t)Mv * ldv);
+    for (size_t i = 0; i < img.size(); ++i) img[i] = hostile32(i);
+    for (int64_t m = 0; m < M; ++m) std::memcpy(&img[(size_t)m * ldv + col], v + (size_t)m * D, (size_t)D * 4);
+    upload_sync(stream_, dv(ws), img);
+  }
+  upload(stream_, dw(ws), taps, (size_t)k * D);
+  if (mask) upload(stream_, dm(ws), mask, (size_t)M);
+  fill_sentinel(stream_, dy(ws), ny);
+  float* yd = dy(ws) + (size_t)kG * D;
+  const float* vd = dv(ws) + col;
+  fsmn_timed([&] {
+    if (form == 2) launch_fsmn_f32(stream_, vd, dw(ws), mask ? dm(ws) : nullptr, B, T, D, k, dv(ws));
+    else if (dense) launch_fsmn_f32(stream_, vd, dw(ws), mask ? dm(ws) : nullptr, B, T, D, k, yd, form == 1);
+    else launch_fsmn_f32_ld(stream_, vd, ldv, dw(ws), B, T, D, k, yd);
+  });
+  download(stream_, y_out, (const float*)dy(ws), ny);
+  PF_HIP(hipStreamSynchronize(stream_));
+}
+
+// launch_fsmn_dec with upload_valid_rows: the rows of tn at l >= token_num[b] keep what the device buffer held, and that is
+// `hostile`: 0 the large finite pattern, 1 NaN, 2 +-Inf.  A row of x at l >= token_num[b] must come back with its bits.
+void Engine::op_fsmn_dec_ex(const float* tn, const float* taps, const int32_t* token_num, int B, int L, int D, int k, int hostile,
+                            const float* x, float* x_out) {
+  PF_HIP(hipSetDevice(device_));
+  fsmn_ex_shape("fsmn_dec_ex", B, L, D, k, D, 0);
+  PF_CHECK(D % 4 == 0 && hostile >= 0 && hostile <= 2, PF_ERR_INVALID_ARG, "fsmn_dec_ex: D a multiple of 4, hostile 0 | 1 | 2");
+  const int64_t M = (int64_t)B * L, Mv = M + kFsmnTailRows;
+  const size_t nx = (size_t)(M + 2 * kG) * D;
+  StageCarve st;
+  const auto dt = st.take<float>((size_t)Mv * D), dw = st.take<float>((size_t)k * D), dx = st.take<float>(nx);
+  const auto dnum = st.take<int32_t>(B);
+  void* ws = op_ws(st);
+  {
+    std::vector<float> img((size_t)Mv * D);
+    for (size_t i = 0; i < img.size(); ++i)
+      img[i] = hostile == 0 ? hostile32(i) : hostile == 1 ? std::nanf("") : ((i & 1u) ? -INFINITY : INFINITY);
+    upload_sync(stream_, dt(ws), img);
+  }
+  upload_valid_rows(stream_, dt(ws), tn, token_num, B, L, D);
+  upload(stream_, dw(ws), taps, (size_t)k * D);
+  upload(stream_, dnum(ws), token_num, B);
+  fill_sentinel(stream_, dx(ws), nx);
+  float* xd = dx(ws) + (size_t)kG * D;
+  upload(stream_, xd, x, (size_t)M * D);
+  fsmn_timed([&] { launch_fsmn_dec(stream_, dt(ws), dw(ws), dnum(ws), B, L, D, k, xd); });
+  download(stream_, x_out, (const float*)dx(ws), nx);
+  PF_HIP(hipStreamSynchronize(stream_));
+  check_masked_rows("fsmn_dec_ex", x_out + (size_t)kG * D, x, token_num, B, L, D);
+}
+
 // The table sits between two rows of the large finite pattern: an id clamped one row off returns them.
 void Engine::op_embed_gather(const float* table, const int32_t* ids, int rows, int D, int vocab, float* out32, uint16_t* out16) {
   PF_HIP(hipSetDevice(device_));

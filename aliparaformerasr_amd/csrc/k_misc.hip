@@ -106,7 +106,10 @@ __global__ __launch_bounds__(256) void fsmn_enc_kernel(const half_t* __restrict_
 
 void launch_fsmn_enc(hipStream_t s, const half_t* v, int ldv, const float* wT, int B, int T, int D, int k,
                      float* f) {
-
+  // one thread loads FS_CH f16 cells of a row at once and stores float4: a D with a remainder would leave channels unwritten
+  PF_CHECK(D > 0 && D % FS_CH == 0 && D % 4 == 0, PF_ERR_UNSUPPORTED, "fsmn: D must be a multiple of the channels per thread");
+  PF_CHECK(ldv >= D && ldv % FS_CH == 0 && (uintptr_t)v % (FS_CH * sizeof(half_t)) == 0, PF_ERR_UNSUPPORTED,
+           "fsmn: the V rows must start on the width of one thread's load (row stride and column offset)");
   const int tb = (T + FS_ROWS - 1) / FS_ROWS;
   const int64_t total = (int64_t)B * tb * (D / FS_CH);
   if (total == 0) return;
@@ -119,12 +122,17 @@ void launch_fsmn_enc(hipStream_t s, const half_t* v, int ldv, const float* wT, i
     case 3: hipLaunchKernelGGL(fsmn_enc_kernel<3>, grid, dim3(256), 0, s, v, ldv, wT, B, T, D, f); break;
     default: throw Error(PF_ERR_UNSUPPORTED, "fsmn: unsupported kernel size (3/5/7/9/11)");
   }
+  note_gemm_kernel(k == 11 ? "fsmn_enc_kernel<11>" : k == 9 ? "fsmn_enc_kernel<9>" : k == 7 ? "fsmn_enc_kernel<7>"
+                   : k == 5 ? "fsmn_enc_kernel<5>" : "fsmn_enc_kernel<3>");
   PF_HIP(hipGetLastError());
 }
 
 // ------------------------------------------------------------------ fp32 FSMN -------------
 // y = (dwconv(v*m) + v*m) * m ; m from token_num (l < token_num[b]) or a float mask or none.
 // accumulate != 0: out += y (decoder residual), else out = y.
+// token_num is the decoder's contract (kernels.h, launch_fsmn_dec): a row at l >= token_num[b] is never read, and with
+// accumulate its row of out is never written either (without: it is stored as +0).  A float mask keeps multiply semantics (a
+// fractional mask needs them): every row is read, a NaN under a zero mask value spreads.
 // KT > 0: compile-time tap count — all K rows are requested before the first FMA (the runtime-K loop
 // below serialises one L2 round trip per tap, which is what bounds the small decoder launches).
 template <int KT>
@@ -142,11 +150,13 @@ __global__ __launch_bounds__(256) void fsmn_f32_kernel(const float* __restrict__
   const int t = (int)(row % T);
   const int b = (int)(row / T);
   const int left = (K - 1) / 2;
-  auto m_at = [&](int tt) -> float {
-    if (token_num) return tt < token_num[b] ? 1.f : 0.f;
-    if (mask) return mask[(int64_t)b * T + tt];
-    return 1.f;
-  };
+  const int nv = token_num ? token_num[b] : T;              // rows [nv, T) are masked by token_num: skipped, not multiplied
+  float4* o = reinterpret_cast<float4*>(out + row * (int64_t)D + c4);
+  if (t >= nv) {
+    if (!accumulate) *o = make_float4(0.f, 0.f, 0.f, 0.f);
+    return;
+  }
+  auto m_at = [&](int tt) -> float { return mask && !token_num ? mask[(int64_t)b * T + tt] : 1.f; };
   const float mt = m_at(t);
   float4 acc;
   {
@@ -160,7 +170,7 @@ __global__ __launch_bounds__(256) void fsmn_f32_kernel(const float* __restrict__
 #pragma unroll
     for (int j = 0; j < KT; ++j) {
       const int tt = t + j - left;
-      ok[j] = tt >= 0 && tt < T;
+      ok[j] = tt >= 0 && tt < T && tt < nv;
       const int ttc = ok[j] ? tt : t;
       xs[j] = *reinterpret_cast<const float4*>(v + (row + (ttc - t)) * (int64_t)D + c4);
       ws[j] = *reinterpret_cast<const float4*>(wT + (int64_t)j * D + c4);
@@ -176,7 +186,7 @@ __global__ __launch_bounds__(256) void fsmn_f32_kernel(const float* __restrict__
   } else {
     for (int j = 0; j < K; ++j) {
       const int tt = t + j - left;
-      if (tt < 0 || tt >= T) continue;
+      if (tt < 0 || tt >= T || tt >= nv) continue;
       const float mm = m_at(tt);
       const float4 x = *reinterpret_cast<const float4*>(v + (row + (j - left)) * (int64_t)D + c4);
       const float4 w = *reinterpret_cast<const float4*>(wT + (int64_t)j * D + c4);
@@ -185,7 +195,6 @@ __global__ __launch_bounds__(256) void fsmn_f32_kernel(const float* __restrict__
     }
   }
   acc.x *= mt; acc.y *= mt; acc.z *= mt; acc.w *= mt;
-  float4* o = reinterpret_cast<float4*>(out + row * (int64_t)D + c4);
   if (accumulate) {
     const float4 p = *o;
     acc.x += p.x; acc.y += p.y; acc.z += p.z; acc.w += p.w;
@@ -258,6 +267,7 @@ void launch_fsmn_dec(hipStream_t s, const float* tn, const float* wT, const int3
   } else
     hipLaunchKernelGGL(fsmn_f32_kernel<0>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, tn, wT,
                        (const float*)nullptr, token_num, B, L, D, k, 1, x);
+  note_gemm_kernel(k == 11 ? "fsmn_dec_kernel<11>" : k == 21 ? "fsmn_dec_kernel<21>" : "fsmn_f32_kernel<0>");
   PF_HIP(hipGetLastError());
 }
 
@@ -298,7 +308,8 @@ void launch_fsmn_dec_stream(hipStream_t s, const float* tn, const float* wT, con
 
 // fp32 encoder FSMN without a mask (math_mode 1 / 3), register window: one thread = 4 channels x FS_ROWS consecutive frames; the
 // FS_ROWS + K - 1 input rows it needs are requested up front, then every output is formed in the order of fsmn_f32_kernel
-// (identity term first, taps 0 .. K-1) — the same roundings, a third of the time (that form re-reads every row K times
+// (identity term first, taps 0 .. K-1) — the same roundings (asserted bit for bit, dense and strided, by
+// tests/test_gpu_fsmn_conformance.py), a third of the time (that form re-reads every row K times
 // through L1 with one L2 round trip per tap: 38 us for 2 x 32 MB at the benchmark shape).
 template <int K>
 __global__ __launch_bounds__(256) void fsmn_f32_win_kernel(const float* __restrict__ v, int ldv, const float* __restrict__ wT, int B, int T, int D,
@@ -345,16 +356,20 @@ void launch_fsmn_f32_ld(hipStream_t s, const float* v, int ldv, const float* wT,
   const int64_t tot = (int64_t)B * ((T + FS_ROWS - 1) / FS_ROWS) * (D / 4);
   if (tot == 0) return;
   hipLaunchKernelGGL(fsmn_f32_win_kernel<11>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, v, ldv, wT, B, T, D, y);
+  note_gemm_kernel("fsmn_f32_win_kernel<11>");
   PF_HIP(hipGetLastError());
 }
 
 void launch_fsmn_f32(hipStream_t s, const float* v, const float* wT, const float* mask, int B, int T, int D,
-                     int k, float* y) {
+                     int k, float* y, bool force_generic) {
   const int64_t total = (int64_t)B * T * (D / 4);
   if (total == 0) return;
-  if (!mask && k == 11 && v != y) { launch_fsmn_f32_ld(s, v, D, wT, B, T, D, k, y); return; }
+  // every thread reads rows t - left .. t + right of v while its neighbours store theirs: in place no kernel here can be right
+  PF_CHECK(v != y, PF_ERR_INVALID_ARG, "fsmn_f32: v and y must be distinct buffers");
+  if (!mask && k == 11 && !force_generic) { launch_fsmn_f32_ld(s, v, D, wT, B, T, D, k, y); return; }
   hipLaunchKernelGGL(fsmn_f32_kernel<0>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, v, wT, mask,
                      (const int32_t*)nullptr, B, T, D, k, 0, y);
+  note_gemm_kernel("fsmn_f32_kernel<0>");
   PF_HIP(hipGetLastError());
 }
 

@@ -337,9 +337,16 @@ bool attention_reports_range(const AttnArgs& a);      // the launch has at most 
 
 // ------------------------------------------------------------------ misc ----
 void launch_f32_to_f16(hipStream_t s, const float* x, int64_t rows, int cols, int ldx, half_t* y, int ldy);
-// encoder FSMN: v f16 [B*T, ldv] (cols 0..D-1 used), w [D,k] -> f fp32 [B*T, D]: dwconv + identity
+// encoder FSMN: v f16 [B*T, ldv] (cols 0..D-1 used), w taps [k][D] -> f fp32 [B*T, D]: dwconv + identity; k = 3 | 5 | 7 | 9 | 11
+// (PF_ERR_UNSUPPORTED otherwise, and for a D that is no multiple of 4 and of the channels per thread, or a v / ldv off the
+// width of one thread's load)
+// read: v rows [0, B T) x columns [0, D) only (the columns beside them and the rows behind row B T - 1 may hold anything; a
+// window stops at the edges of its utterance);  written: f rows [0, B T) x [0, D), all of them; nothing behind row B T - 1
 void launch_fsmn_enc(hipStream_t s, const half_t* v, int ldv, const float* w, int B, int T, int D, int k, float* f);
-// decoder FSMN: x[B*L,D] += (dwconv(tn*m) + tn*m)*m ; tn fp32 [B*L,D]; valid l < token_num[b]
+// decoder FSMN: x[B*L,D] += (dwconv(tn*m) + tn*m)*m ; tn fp32 [B*L,D]; valid l < token_num[b]; any k (11 and 21: the register
+// window kernel, otherwise fsmn_f32_kernel<0> under the same contract)
+// read: tn rows with l < min(token_num[b], L) only (a masked row may hold anything), x rows with l < min(token_num[b], L);
+// written: x rows with l < min(token_num[b], L) (every other cell keeps its bits); nothing behind row B L - 1
 void launch_fsmn_dec(hipStream_t s, const float* tn, const float* w, const int32_t* token_num, int B, int L,
                      int D, int k, float* x);
 // LayerNorm of f16 rows -> f16 (may run in place); D % 8 == 0, D <= 2048
@@ -356,10 +363,19 @@ bool launch_fsmn_dec_ln(hipStream_t s, const float* tn, const float* w, const in
 // [B, D, K-1], all of it, a bitwise copy of its source columns; cache_out must not alias cache_in
 void launch_fsmn_dec_stream(hipStream_t s, const float* tn, const float* wT, const int32_t* len, const float* cache_in,
                             int B, int L, int D, int k, float* x, float* cache_out);
-// generic fp32 FSMN for the stand-alone op (mask [B,T] floats or null)
+// fp32 encoder FSMN of the V third of a fused [B T, ldv] Q | K | V result (fsmn_f32_win_kernel<11>): no mask, k = 11, ldv and D
+// multiples of 4, v 16-byte aligned; y = dwconv(v) + v, fp32 [B*T, D]
+// read: v rows [0, B T) x columns [0, D) only (Q and K beside them and the rows behind row B T - 1 may hold anything; the rows
+// of a window beyond its utterance's edge are re-reads of the edge row, never used);  written: y rows [0, B T) x [0, D), all of
+// them; nothing behind row B T - 1; v and y must not overlap
 void launch_fsmn_f32_ld(hipStream_t s, const float* v, int ldv, const float* wT, int B, int T, int D, int k, float* y);
+// generic fp32 FSMN (mask [B,T] floats or null, any k): y = (dwconv(v m) + v m) m over dense rows (ldv = D).  No mask and k = 11:
+// launch_fsmn_f32_ld (unless force_generic: the stand-alone op comparing the two kernels); otherwise fsmn_f32_kernel<0>
+// read: v rows [0, B T) x [0, D), all of them, and mask [B, T]: the mask MULTIPLIES (fractional values are allowed), so a NaN or
+// Inf under a zero mask value reaches y;  written: y rows [0, B T) x [0, D), all of them; nothing behind row B T - 1;
+// v == y is refused (PF_ERR_INVALID_ARG): every thread reads its neighbours' rows
 void launch_fsmn_f32(hipStream_t s, const float* v, const float* w, const float* mask, int B, int T, int D,
-                     int k, float* y);
+                     int k, float* y, bool force_generic = false);
 // CIF: im2col of H (f16) for the k=3 conv: [B*T, 3*D]
 void launch_cif_im2col(hipStream_t s, const half_t* H, int B, int T, int D, int l_order, int r_order, half_t* out);
 // alphas[b,t] = relu(sigmoid(dot(y[b,t,:], w) + b0)*smooth - noise), alphas[b,T] = tail

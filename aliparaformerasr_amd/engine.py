@@ -2008,6 +2008,47 @@ class Engine:
                                                 _fp(x), _fp(xo), _fp(co)))
         return xo, co
 
+    def op_fsmn_enc_ex(self, v16, taps, ldv=0, col=0) -> np.ndarray:
+        """launch_fsmn_enc (pf_op_fsmn_enc_ex): v16 [B, T, D] float16, taps [k, D]; on the device V is columns [col, col + D) of
+        rows of ldv cells (0 = D) amid a large finite pattern; returns y [B T + 4, D] float32."""
+        v = np.ascontiguousarray(v16, dtype=np.float16)
+        taps = _f32(taps)
+        B, T, D = v.shape
+        k = taps.shape[0]
+        assert taps.shape == (k, D)
+        y = np.zeros((B * T + 2 * self.OP_GUARD_ROWS, D), np.float32)
+        N.check(self._lib.pf_op_fsmn_enc_ex(self._h, v.view(np.uint16).ctypes.data_as(C.POINTER(C.c_uint16)), _fp(taps), B, T, D, k,
+                                            ldv or D, col, _fp(y)))
+        return y
+
+    def op_fsmn_f32_ex(self, v, taps, mask=None, ldv=0, col=0, form=0) -> np.ndarray:
+        """launch_fsmn_f32 / launch_fsmn_f32_ld (pf_op_fsmn_f32_ex): v [B, T, D], taps [k, D], mask [B, T] floats or None; form 0 =
+        the launcher's choice, 1 = fsmn_f32_kernel<0> forced, 2 = in place (refused); returns y [B T + 4, D]."""
+        v, taps = _f32(v), _f32(taps)
+        B, T, D = v.shape
+        k = taps.shape[0]
+        assert taps.shape == (k, D)
+        m = None if mask is None else _f32(mask)
+        assert m is None or m.shape == (B, T)
+        y = np.zeros((B * T + 2 * self.OP_GUARD_ROWS, D), np.float32)
+        N.check(self._lib.pf_op_fsmn_f32_ex(self._h, _fp(v), _fp(taps), None if m is None else _fp(m), B, T, D, k, ldv or D, col, form,
+                                            _fp(y)))
+        return y
+
+    def op_fsmn_dec_ex(self, tn, taps, token_num, x, hostile=0) -> np.ndarray:
+        """launch_fsmn_dec (pf_op_fsmn_dec_ex): tn, x [B, L, D], taps [k, D] (any k); the masked rows of tn hold a large finite
+        pattern (hostile 0), NaN (1) or Inf (2) on the device; returns x [B L + 4, D]."""
+        tn, taps, x = _f32(tn), _f32(taps), _f32(x)
+        B, L, D = tn.shape
+        k = taps.shape[0]
+        assert x.shape == tn.shape and taps.shape == (k, D)
+        t = np.ascontiguousarray(token_num, dtype=np.int32)
+        assert t.shape == (B,)
+        xo = np.zeros((B * L + 2 * self.OP_GUARD_ROWS, D), np.float32)
+        N.check(self._lib.pf_op_fsmn_dec_ex(self._h, _fp(tn), _fp(taps), t.ctypes.data_as(C.POINTER(C.c_int32)), B, L, D, k, hostile,
+                                            _fp(x), _fp(xo)))
+        return xo
+
     def op_embed_gather(self, table, ids, want16=True):
         """launch_embed_gather (pf_op_embed_gather): (out32 [rows + 4, D], out16 [rows + 4, D] uint16 | None)."""
         table = _f32(table)

@@ -1284,6 +1284,26 @@ int pf_op_layernorm_f16(pf_engine* e, const uint16_t* x, const float* gamma, con
    guarded [B D, k-1].  The rows of tn at l >= len[b] are replaced by a large finite pattern on the device. */
 int pf_op_fsmn_dec_stream(pf_engine* e, const float* tn, const float* taps, const int32_t* len, const float* cache_in, int32_t B, int32_t L,
                           int32_t D, int32_t k, const float* x, float* x_out, float* cache_out);
+/* The stand-alone FSMN memory blocks of k_misc.hip, each launcher alone (tests/fsmn_ref.py):
+     y[b,t,:] = m_t ((v m)[b,t,:] + sum_j taps[j] (v m)[b, t + j - (k - 1) / 2, :]),   zero outside [0, T);   taps [k,D].
+   On the device the operand lies in a buffer of B T + 16 rows of ldv cells that holds a large finite pattern everywhere outside
+   the V columns [col, col + D) of rows [0, B T); the result comes back guarded, [B T, D].  The kernel that ran is read with
+   pf_profile_kernel(e, "gemm_op") (profiling on).
+   launch_fsmn_enc: v16 [B T, D] as f16 bit patterns, no mask; k outside {3, 5, 7, 9, 11}, a D that is no multiple of 4 or an
+   ldv / col that is none is refused by the launcher (PF_ERR_UNSUPPORTED). */
+int pf_op_fsmn_enc_ex(pf_engine* e, const uint16_t* v16, const float* taps, int32_t B, int32_t T, int32_t D, int32_t k, int32_t ldv,
+                      int32_t col, float* y_out);
+/* launch_fsmn_f32 / launch_fsmn_f32_ld: v [B T, D] fp32, mask [B,T] floats (NULL: none; it multiplies, fractions allowed).
+   form 0: what the pipeline launches — launch_fsmn_f32 on dense rows (ldv == D, col == 0), launch_fsmn_f32_ld on strided ones
+   (no mask, k = 11);  1: launch_fsmn_f32 with the generic kernel forced (dense, no mask);  2: launch_fsmn_f32 with its result on
+   its operand, which the launcher refuses (PF_ERR_INVALID_ARG) before anything runs. */
+int pf_op_fsmn_f32_ex(pf_engine* e, const float* v, const float* taps, const float* mask, int32_t B, int32_t T, int32_t D, int32_t k,
+                      int32_t ldv, int32_t col, int32_t form, float* y_out);
+/* launch_fsmn_dec: x_out guarded [B L, D] = x + y with m = (l < token_num[b]), any k.  The rows of tn at l >= token_num[b] are
+   replaced on the device by `hostile`: 0 a large finite pattern, 1 NaN, 2 +-Inf; a row of x at l >= token_num[b] must come back
+   with the bits it went in with (PF_ERR_DEVICE otherwise). */
+int pf_op_fsmn_dec_ex(pf_engine* e, const float* tn, const float* taps, const int32_t* token_num, int32_t B, int32_t L, int32_t D,
+                      int32_t k, int32_t hostile, const float* x, float* x_out);
 /* launch_embed_gather: out32 guarded [rows, D] = table[clamp(ids[r], 0, vocab - 1)], out16 (may be NULL) its f16 rounding.  On the
    device the table lies between two rows of a large finite pattern. */
 int pf_op_embed_gather(pf_engine* e, const float* table, const int32_t* ids, int32_t rows, int32_t D, int32_t vocab, float* out32,
