@@ -255,6 +255,15 @@ SIGNATURES = {
     "pf_engine_punctuate": (C.c_int, [_vp, _i32, _i32, C.c_int32, _i32, _i32]),
     "pf_op_punc_logits": (C.c_int, [_vp, _i32, _i32, C.c_int32, _f, _f]),
     "pf_op_punc_window": (C.c_int, [_vp, _i32, _i32, _i32, C.c_int32, _i32, _i32, _f]),
+    "pf_punc_model_causal": (C.c_int, [_vp, _i32]),
+    "pf_punc_stream_state_bytes": (C.c_int, [_vp, _i64]),
+    "pf_host_punc_stream_state_bytes": (C.c_int, [_vp, _i64]),
+    "pf_host_punc_stream_step": (C.c_int, [_vp, _vp, _i32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _i32, _i32, _P(C.c_double), _i32]),
+    "pf_host_online_committed_words": (C.c_int, [_vp, _P(C.c_char_p), C.c_int32, _i64, C.c_int32, C.c_char_p, C.c_char_p, C.c_int64, _i64, _i32, _i32]),
+    "pf_online_recognizer_set_punc_model": (C.c_int, [_vp, C.c_char_p, C.c_int32]),
+    "pf_online_stream_punctuated": (C.c_int, [_vp, _cpp, _P(_i32), _P(_i32), _i32]),
+    "pf_online_stream_sentence_punctuated": (C.c_int, [_vp, C.c_int32, _cpp, _P(_i32), _i32]),
+    "pf_op_punc_stream_step": (C.c_int, [_vp, _vp, _i32, _i32, _i32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _i32, _i32, _f, _i32]),
     "pf_op_vad_segments": (C.c_int, [_vp, _i32, _i32, C.c_int32, C.c_int32, C.c_int32, _P(PfVadConfig), _i32, C.c_int32, _i32]),
     "pf_stream_add_pcm": (C.c_int, [_vp, _vp, C.c_int64, _P(PfPcmDesc)]),
     "pf_host_wav_info": (C.c_int, [C.c_char_p, _P(PfPcmDesc), _i64, _i64, C.POINTER(C.c_double)]),

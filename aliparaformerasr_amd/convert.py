@@ -16,7 +16,7 @@ mismatch with a real file fails loudly instead of producing a silently wrong mod
     python -m aliparaformerasr_amd.convert model.int8.onnx out.pfw [--eb model_eb.int8.onnx] [--kind ...]
         (ONNX graph walk, see onnx_to_state_dict; an int8 file's stored bytes are carried beside their float image)
     python -m aliparaformerasr_amd.convert vad.onnx|vad.pt out.pfw --kind fsmnvad --mvn vad.mvn [--sil 0,...] [--lfr-m 5]
-    python -m aliparaformerasr_amd.convert punc.pt|punc.onnx out.pfw --kind cttransformer --tokens tokens.json [--heads 8]
+    python -m aliparaformerasr_amd.convert punc.pt|punc.onnx out.pfw --kind cttransformer --tokens tokens.json [--heads 8] [--causal]
     python -m aliparaformerasr_amd.convert campplus.bin|.pt out.pfw --kind campplus [--seg-len 100] [--dilations 1,2,2]
         (FunASR's FSMN-VAD, the model score of the voice-activity segmentation: vad_state_dict_to_pfw / vad_onnx_to_state_dict.
          NO REAL FSMN-VAD FILE HAS BEEN THROUGH THIS ROUTE: the names are restated from the public FunASR sources and
@@ -429,8 +429,9 @@ def vad_to_pfw(model_path, mvn_path, sil_ids=(0,), lfr_m=5, lstride=1):
     return vad_state_dict_to_pfw(sd, shift, scale, sil_ids, lfr_m, lstride)
 
 
-def punc_state_dict_to_pfw(sd: dict, tokens, punc_list=None, sentence_end_id=None, heads: int = 8):
-    """FunASR CT-Transformer state dict (+ the vocabulary) -> (cfg, PFW weights) of kind "cttransformer".  FunASR's names:
+def punc_state_dict_to_pfw(sd: dict, tokens, punc_list=None, sentence_end_id=None, heads: int = 8, causal: bool = False):
+    """FunASR CT-Transformer state dict (+ the vocabulary) -> (cfg, PFW weights) of kind "cttransformer".  causal: the
+    streaming form (the same tensors; the header says causal = 1 and sanm_shift = (kernel - 1) / 2, all FSMN taps to the left).  FunASR's names:
     embed.weight (or embed.0.weight), encoder.encoders0.0.* for the first block and encoder.encoders.N.* for block N + 1, each
     with norm1, self_attn.linear_q_k_v, self_attn.fsmn_block.weight [d_model, 1, kernel], self_attn.linear_out, norm2,
     feed_forward.w_1 / w_2; encoder.after_norm; decoder.  Refuses anything else: no silent defaults for a missing tensor."""
@@ -475,6 +476,8 @@ def punc_state_dict_to_pfw(sd: dict, tokens, punc_list=None, sentence_end_id=Non
     cfg = W.ct_transformer_config(vocab=int(emb.shape[0]), d_model=int(emb.shape[1]), heads=int(heads), ffn=int(w["layers.0.ffn.w1.weight"].shape[0]),
                                   kernel=int(w["layers.0.attn.fsmn.weight"].shape[1]), n_layers=len(blocks), punc_list=punc_list,
                                   sentence_end_id=int(sentence_end_id))
+    if causal:
+        cfg.update(causal=1, sanm_shift=(int(cfg["kernel"]) - 1) // 2)
     for name, shape in W.punc_tensor_shapes(cfg).items():
         if tuple(w[name].shape) != tuple(shape):
             raise ValueError("cttransformer: %s has shape %s, expected %s" % (name, list(w[name].shape), list(shape)))
@@ -511,9 +514,12 @@ def punc_onnx_to_state_dict(graph) -> dict:
     return sd
 
 
-def punc_to_pfw(model_path, tokens_path, heads=8):
-    """model.pt | model.onnx + tokens -> (cfg, PFW weights) of kind "cttransformer"."""
+def punc_to_pfw(model_path, tokens_path, heads=8, causal=False):
+    """model.pt | model.onnx + tokens -> (cfg, PFW weights) of kind "cttransformer".  causal: the state-dict route only (an
+    ONNX export has its masks and its FSMN padding baked into the graph, and the walk does not read them)."""
     if str(model_path).endswith(".onnx"):
+        if causal:
+            raise ValueError("cttransformer: --causal works on a state dict (model.pt); an ONNX export does not say how it masks")
         from . import onnx_reader as R
         sd = punc_onnx_to_state_dict(R.load(model_path))
     else:
@@ -521,7 +527,7 @@ def punc_to_pfw(model_path, tokens_path, heads=8):
         sd = torch.load(model_path, map_location="cpu")
         sd = sd.get("state_dict", sd.get("model", sd)) if isinstance(sd, dict) else sd
         sd = {k: v.float().numpy() for k, v in sd.items() if hasattr(v, "numpy")}
-    return punc_state_dict_to_pfw(sd, read_punc_tokens(tokens_path), heads=heads)
+    return punc_state_dict_to_pfw(sd, read_punc_tokens(tokens_path), heads=heads, causal=causal)
 
 
 def read_punc_tokens(path):
@@ -661,7 +667,13 @@ def main(argv=None):
             print("--kind cttransformer needs --tokens tokens.json (or a file with one token per line)")
             return 2
         heads = int(argv[argv.index("--heads") + 1]) if "--heads" in argv else 8
-        cfg, wts = punc_to_pfw(argv[0], argv[argv.index("--tokens") + 1], heads)
+        try:
+            cfg, wts = punc_to_pfw(argv[0], argv[argv.index("--tokens") + 1], heads, causal="--causal" in argv)
+        except ValueError as ex:
+            if "--causal" not in str(ex):
+                raise
+            print(ex)
+            return 2
         W.save_pfw(argv[1], cfg, wts)
         print("wrote %s (%s, %d tensors)" % (argv[1], cfg["kind"], len(wts)))
         return 0

@@ -1379,6 +1379,53 @@ int pf_op_punc_window(pf_engine* h, const int32_t* ids, const int32_t* T, const 
   PF_CATCH
 }
 
+// ---- punctuation, streaming ----
+int pf_punc_model_causal(const pf_punc_model* m, int32_t* causal) {
+  PF_TRY
+  NEED(m); NEED(causal);
+  *causal = m->p->causal;
+  return PF_OK;
+  PF_CATCH
+}
+int pf_punc_stream_state_bytes(const pf_punc_model* m, int64_t* bytes) {
+  PF_TRY
+  NEED(m); NEED(bytes);
+  PF_CHECK(m->p->causal == 1, PF_ERR_UNSUPPORTED, "punc_stream_state_bytes: the model is not causal");
+  *bytes = punc_stream_layout(*m->p).bytes;
+  return PF_OK;
+  PF_CATCH
+}
+int pf_host_punc_stream_state_bytes(const pf_punc_model* m, int64_t* bytes) {
+  PF_TRY
+  NEED(m); NEED(bytes);
+  PF_CHECK(m->p->causal == 1, PF_ERR_UNSUPPORTED, "punc_stream_state_bytes: the model is not causal");
+  *bytes = host_punc_stream_state_bytes(*m->p);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_host_punc_stream_step(const pf_punc_model* m, void* state, const int32_t* ids, int32_t n_new, int32_t flush, int32_t max_context,
+                             int32_t flags, int32_t* marks, int32_t* mark_flags, double* logits, int32_t* flush_mark) {
+  PF_TRY
+  NEED(m); NEED(state);
+  if (n_new > 0) { NEED(ids); NEED(marks); NEED(mark_flags); }
+  host_punc_stream_step(*m->p, state, ids, n_new, flush != 0, max_context, flags, marks, mark_flags, logits, flush_mark);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_op_punc_stream_step(pf_engine* h, void* states, const int32_t* ids, const int32_t* n_new, const int32_t* flush, int32_t B,
+                           int32_t ld, int32_t max_context, int32_t flags, int32_t* marks, int32_t* mark_flags, float* logits,
+                           int32_t* flush_mark) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  PF_CHECK(B >= 0 && ld >= 0, PF_ERR_INVALID_ARG, "punc_stream_step: negative B or ld");
+  if (B > 0) { NEED(states); NEED(n_new); NEED(flush_mark); if (ld > 0) { NEED(ids); NEED(marks); NEED(mark_flags); } }
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->op_punc_stream_step(states, ids, n_new, flush, B, ld, max_context, flags, marks, mark_flags, logits, flush_mark);
+  return PF_OK;
+  PF_CATCH
+}
+
 int pf_op_topk(pf_engine* h, const float* x, int64_t rows, int32_t V, int32_t ld, int32_t K, int64_t* ids, float* val,
                int32_t* n) {
   PF_TRY
@@ -2878,6 +2925,36 @@ int pf_online_stream_sentence_tokens(pf_online_stream* h, int32_t j, const pf_on
   return PF_OK;
   PF_CATCH
 }
+int pf_online_recognizer_set_punc_model(pf_online_recognizer* h, const char* pfw_path, int32_t max_context) {
+  PF_TRY
+  OR(h)->SetPuncModel(pfw_path ? pfw_path : "", max_context);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_online_stream_punctuated(pf_online_stream* h, const char** text_utf8, const int32_t** punc_ids, const int32_t** punc_flags,
+                                int32_t* n_words) {
+  PF_TRY
+  OnlineStreamM* s = OS(h);
+  std::lock_guard<std::mutex> lk(s->mu);
+  if (text_utf8) *text_utf8 = s->Punctuated.c_str();
+  if (punc_ids) *punc_ids = s->PuncIds.data();
+  if (punc_flags) *punc_flags = s->PuncFlags.data();
+  if (n_words) *n_words = (int32_t)s->PuncIds.size();
+  return PF_OK;
+  PF_CATCH
+}
+int pf_online_stream_sentence_punctuated(pf_online_stream* h, int32_t j, const char** text_utf8, const int32_t** punc_ids, int32_t* n_words) {
+  PF_TRY
+  OnlineStreamM* s = OS(h);
+  std::lock_guard<std::mutex> lk(s->mu);
+  PF_CHECK(j >= 0 && j < (int32_t)s->Sentences.size(), PF_ERR_INVALID_ARG, "sentence index out of range");
+  const OnlineStreamM::SentenceM& sen = s->Sentences[(size_t)j];
+  if (text_utf8) *text_utf8 = sen.punctuated.c_str();
+  if (punc_ids) *punc_ids = sen.punc_ids.data();
+  if (n_words) *n_words = (int32_t)sen.punc_ids.size();
+  return PF_OK;
+  PF_CATCH
+}
 void pf_online_stream_free(pf_online_stream* h) {
   if (!h || h->freed) return;
   if (h->s) h->s->disposed = true;
@@ -2998,6 +3075,40 @@ int pf_host_online_decode(const char* const* tokens, int32_t n_tokens, const int
   const std::string t = online_decode_text(tk, idv);
   PF_CHECK((int32_t)t.size() + 1 <= cap, PF_ERR_CAPACITY, "online_decode: output capacity too small");
   std::memcpy(out, t.c_str(), t.size() + 1);
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_host_online_committed_words(const pf_punc_model* m, const char* const* tokens, int32_t n_tokens, const int64_t* ids, int32_t n_ids,
+                                   const char* before_utf8, char* out, int64_t cap, int64_t* out_len, int32_t* n_committed, int32_t* n_words) {
+  PF_TRY
+  NEED(m);
+  PF_CHECK(n_tokens >= 0 && n_ids >= 0 && cap >= 0, PF_ERR_INVALID_ARG, "online_committed_words: bad sizes");
+  if (n_tokens > 0) NEED(tokens);
+  if (n_ids > 0) NEED(ids);
+  std::vector<std::string> tk;
+  for (int i = 0; i < n_tokens; ++i) { PF_CHECK(tokens[i] != nullptr, PF_ERR_INVALID_ARG, "online_committed_words: null token"); tk.emplace_back(tokens[i]); }
+  const OnlineCommitted c = online_committed_words(*m->p, tk, std::vector<int64_t>(ids, ids + n_ids));
+  if (before_utf8) {                                             // the last call's committed words, one per line
+    std::vector<std::string> before;
+    const std::string all(before_utf8);
+    for (size_t pos = 0; pos < all.size();) {
+      size_t e = all.find('\n', pos);
+      if (e == std::string::npos) e = all.size();
+      before.push_back(all.substr(pos, e - pos));
+      pos = e + 1;
+    }
+    online_check_committed_prefix(before, c);
+  }
+  std::string joined;
+  for (size_t i = 0; i < c.words.size(); ++i) { if (i) joined += '\n'; joined += online_word(c, i); }
+  if (out_len) *out_len = (int64_t)joined.size();
+  if (n_committed) *n_committed = (int32_t)c.n_committed;
+  if (n_words) *n_words = (int32_t)c.words.size();
+  if (out || cap > 0) {
+    PF_CHECK(cap >= (int64_t)joined.size() && (out || joined.empty()), PF_ERR_CAPACITY, "online_committed_words: capacity below the length of the words");
+    if (!joined.empty()) std::memcpy(out, joined.data(), joined.size());
+  }
   return PF_OK;
   PF_CATCH
 }

@@ -289,6 +289,16 @@ class Engine {
   // the forward on caller windows: logits [sum T, n_punc], x0 [sum T, d_model] (layer 0's input), p [sum T] and cut [B] (the
   // cut launch runs when cut is asked for; it needs last [B]); every output may be null
   void op_punc(const int32_t* ids, const int32_t* T, const int32_t* last, int B, float* logits, float* x0, int32_t* p, int32_t* cut);
+  // The attached model in streaming form (k_punc_stream.hip; causal models only, PF_ERR_UNSUPPORTED otherwise).
+  // punc_stream_step: ONE launch of profile class "punc_stream" over B streams on device operands (kernels.h PuncStreamLaunch;
+  // the caller has admitted every stream, punc.h punc_stream_admit).  op_punc_stream_step: the same over B caller streams through
+  // op_stage.h (hostile ids behind n_new[b], sentinel-filled outputs, the guard rule): states [B, state bytes] in / out, ids
+  // [B, ld], marks / mark_flags [B, ld], logits [B, ld, n_punc] (may be null), flush_mark [B]; flags bit 0: no restarts
+  void punc_stream_step(char* states_dev, const int32_t* slot_dev, const int32_t* ids_dev, int64_t ld, const int32_t* n_new_dev,
+                        const int32_t* flush_dev, int B, int max_context, int flags, int32_t* marks_dev, int32_t* mark_flags_dev,
+                        float* logits_dev, int32_t* flush_mark_dev);
+  void op_punc_stream_step(void* states, const int32_t* ids, const int32_t* n_new, const int32_t* flush, int B, int ld, int max_context,
+                           int flags, int32_t* marks, int32_t* mark_flags, float* logits, int32_t* flush_mark);
   // The CAM++ speaker model (k_spk.hip, spk.h).  nullptr detaches and frees the image and the workspace (nothing of it is
   // launched or allocated then; attaching the model an engine still has costs no upload).  The engine keeps a reference and
   // uploads the image once.  PF_ERR_INVALID_ARG unless the model's n_mels is the front-end's.  A forward is profile class

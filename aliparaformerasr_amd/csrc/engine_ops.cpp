@@ -878,6 +878,7 @@ void Engine::run_punc(const int32_t* ids, const int64_t* off, const int32_t* las
 
 void Engine::op_punc(const int32_t* ids, const int32_t* T, const int32_t* last, int B, float* logits, float* x0, int32_t* p, int32_t* cut) {
   PF_CHECK(punc_ != nullptr, PF_ERR_INVALID_ARG, "op_punc: no model is attached (pf_engine_set_punc_model)");
+  PF_CHECK(!punc_->causal, PF_ERR_UNSUPPORTED, "op_punc: a causal model runs in streaming form only (pf_op_punc_stream_step)");
   PF_CHECK(B >= 0 && B <= PF_PUNC_MAX_BATCH, PF_ERR_INVALID_ARG, "op_punc: B outside 0 .. PF_PUNC_MAX_BATCH");
   std::vector<int64_t> off((size_t)B + 1, 0);
   for (int b = 0; b < B; ++b) {
@@ -891,8 +892,109 @@ void Engine::op_punc(const int32_t* ids, const int32_t* T, const int32_t* last, 
   run_punc(ids, off.data(), last, B, logits, x0, p, cut);
 }
 
+// ---- the punctuation model, streaming (k_punc_stream.hip): ONE launch for B streams
+void Engine::punc_stream_step(char* states_dev, const int32_t* slot_dev, const int32_t* ids_dev, int64_t ld, const int32_t* n_new_dev,
+                              const int32_t* flush_dev, int B, int max_context, int flags, int32_t* marks_dev, int32_t* mark_flags_dev,
+                              float* logits_dev, int32_t* flush_mark_dev) {
+  PF_CHECK(punc_ != nullptr, PF_ERR_INVALID_ARG, "punc_stream_step: no model is attached (pf_engine_set_punc_model)");
+  const PuncModel& m = *punc_;
+  PF_CHECK(m.causal == 1, PF_ERR_UNSUPPORTED, "punc_stream_step: the model is not causal (header key causal = 1)");
+  PF_CHECK(max_context >= 2 && max_context <= kPuncStreamMaxContext && (flags & ~1) == 0, PF_ERR_INVALID_ARG,
+           "punc_stream_step: max_context outside 2 .. 256 or an unknown flag");
+  if (B <= 0) return;
+  const PuncStreamLayout L = punc_stream_layout(m);
+  PuncStreamLaunch a{};
+  a.img = (const char*)punc_dev_.buf.p; a.n_layers = m.n_layers; a.kernel = m.kernel; a.n_punc = m.n_punc;
+  a.max_context = max_context; a.no_restart = flags & 1;
+  a.pe_off = m.pe_off; a.embed_off = m.embed_off; a.after_g = m.after_g_off; a.after_b = m.after_b_off; a.dec = m.dec;
+  for (int l = 0; l < m.n_layers; ++l) {
+    const PuncModel::LayerImg& g = m.limg[(size_t)l];
+    a.n1_g[l] = g.n1_g; a.n1_b[l] = g.n1_b; a.taps[l] = g.taps; a.n2_g[l] = g.n2_g; a.n2_b[l] = g.n2_b;
+    a.qkv[l] = g.qkv; a.out[l] = g.out; a.w1[l] = g.w1; a.w2[l] = g.w2;
+  }
+  a.states = states_dev; a.state_bytes = L.bytes; a.words_off = L.words_off; a.slot = slot_dev;
+  a.ids = ids_dev; a.ld = ld; a.n_new = n_new_dev; a.flush = flush_dev;
+  a.id_none = m.id_none; a.id_comma = m.id_comma; a.id_period = m.id_period; a.id_question = m.id_question; a.id_pause = m.id_pause;
+  a.sentence_end_id = m.sentence_end_id;
+  a.marks = marks_dev; a.mark_flags = mark_flags_dev; a.logits = logits_dev; a.flush_mark = flush_mark_dev;
+  prof_begin("punc_stream", 0);
+  launch_punc_stream(stream_, a, B);
+  prof_end("punc_stream");
+}
+
+void Engine::op_punc_stream_step(void* states, const int32_t* ids, const int32_t* n_new, const int32_t* flush, int B, int ld,
+                                 int max_context, int flags, int32_t* marks, int32_t* mark_flags, float* logits, int32_t* flush_mark) {
+  PF_CHECK(punc_ != nullptr, PF_ERR_INVALID_ARG, "op_punc_stream_step: no model is attached (pf_engine_set_punc_model)");
+  const PuncModel& m = *punc_;
+  PF_CHECK(m.causal == 1, PF_ERR_UNSUPPORTED, "op_punc_stream_step: the model is not causal (header key causal = 1)");
+  PF_CHECK(B >= 0 && B <= PF_PUNC_MAX_BATCH && ld >= 0, PF_ERR_INVALID_ARG, "op_punc_stream_step: B outside 0 .. PF_PUNC_MAX_BATCH or a negative ld");
+  const PuncStreamLayout L = punc_stream_layout(m);
+  const size_t nB = (size_t)B, sbytes = (size_t)L.bytes, nld = (size_t)ld, P = (size_t)m.n_punc;
+  std::vector<int32_t> fl(nB, 0);
+  for (int b = 0; b < B; ++b) {                                  // every stream is admitted before anything changes
+    PF_CHECK(n_new[b] >= 0 && n_new[b] <= ld, PF_ERR_INVALID_ARG, "op_punc_stream_step: n_new[b] outside 0 .. ld");
+    int32_t words[4];
+    std::memcpy(words, (const char*)states + b * sbytes + L.words_off, 16);
+    punc_stream_admit(m, words[0], ids + b * nld, n_new[b], max_context, flags);
+    if (flush) fl[(size_t)b] = flush[b] != 0;
+  }
+  PF_HIP(hipSetDevice(device_));
+  if (B == 0) return;
+  const size_t cells = std::max<size_t>(nB * nld, 1);
+  StageCarve st;
+  const auto d_state = st.take<char>(nB * sbytes);
+  const auto d_ids = st.take<int32_t>(cells), d_new = st.take<int32_t>(nB), d_flush = st.take<int32_t>(nB);
+  const auto d_marks = st.take<int32_t>(cells), d_mf = st.take<int32_t>(cells);
+  const auto d_z = st.take<float>(logits ? cells * P : 0);
+  const auto d_fm = st.take<int32_t>(nB);
+  void* ws = op_ws(st);
+  std::vector<int32_t> x(cells);                                 // hostile behind every stream's n_new ids
+  for (size_t i = 0; i < x.size(); ++i) x[i] = hostile_i32(i);
+  for (int b = 0; b < B; ++b)
+    if (n_new[b] > 0) std::memcpy(&x[b * nld], ids + b * nld, (size_t)n_new[b] * 4);
+  upload(stream_, d_state(ws), (const char*)states, d_state.count);
+  upload(stream_, d_ids(ws), (const int32_t*)x.data(), x.size());
+  upload(stream_, d_new(ws), n_new, nB);
+  upload(stream_, d_flush(ws), (const int32_t*)fl.data(), nB);
+  fill_sentinel(stream_, d_marks(ws), d_marks.count);
+  fill_sentinel(stream_, d_mf(ws), d_mf.count);
+  if (logits) fill_sentinel(stream_, d_z(ws), d_z.count);
+  fill_sentinel(stream_, d_fm(ws), d_fm.count);
+  punc_stream_step(d_state(ws), nullptr, d_ids(ws), ld, d_new(ws), d_flush(ws), B, max_context, flags, d_marks(ws), d_mf(ws),
+                   logits ? d_z(ws) : nullptr, d_fm(ws));
+  const std::vector<uint32_t> fm = check_guard<uint32_t>(stream_, "punc_stream_step: flush_mark", d_fm(ws), kSentinel32, result_geom(B, B, 1, 1, B));
+  std::vector<uint32_t> mk(cells), mf(cells), z(d_z.count);      // the guard rule is applied per stream below
+  download(stream_, (int32_t*)mk.data(), (const int32_t*)d_marks(ws), cells);
+  download(stream_, (int32_t*)mf.data(), (const int32_t*)d_mf(ws), cells);
+  if (logits) download(stream_, (float*)z.data(), (const float*)d_z(ws), d_z.count);
+  PF_HIP(hipStreamSynchronize(stream_));
+  for (int b = 0; b < B; ++b) {
+    const int k = n_new[b];
+    const GuardGeom g1 = result_geom(ld, k, 1, 1, k);
+    if (const GuardHit hit = guard_scan<uint32_t>(mk.data() + b * nld, nullptr, kSentinel32, g1))
+      throw Error(PF_ERR_DEVICE, guard_message("punc_stream_step: marks of stream " + std::to_string(b), g1, hit));
+    if (const GuardHit hit = guard_scan<uint32_t>(mf.data() + b * nld, nullptr, kSentinel32, g1))
+      throw Error(PF_ERR_DEVICE, guard_message("punc_stream_step: mark_flags of stream " + std::to_string(b), g1, hit));
+    if (logits) {                                                // (a logit may be a NaN, never the sentinel's payload)
+      const GuardGeom gz = result_geom(ld, k, (int)P, (int)P, k);
+      if (const GuardHit hit = guard_scan<uint32_t>(z.data() + b * nld * P, nullptr, kSentinel32, gz))
+        throw Error(PF_ERR_DEVICE, guard_message("punc_stream_step: logits of stream " + std::to_string(b), gz, hit));
+    }
+  }
+  download(stream_, (char*)states, (const char*)d_state(ws), d_state.count);
+  PF_HIP(hipStreamSynchronize(stream_));
+  for (int b = 0; b < B; ++b) {
+    const size_t k = (size_t)n_new[b];
+    flush_mark[b] = (int32_t)fm[(size_t)b];
+    if (k) std::memcpy(marks + b * nld, mk.data() + b * nld, k * 4);
+    if (k) std::memcpy(mark_flags + b * nld, mf.data() + b * nld, k * 4);
+    if (logits && k) std::memcpy(logits + b * nld * P, z.data() + b * nld * P, k * P * 4);
+  }
+}
+
 int Engine::punctuate(const int32_t* ids, const int32_t* lens, int B, int32_t* punc_ids) {
   PF_CHECK(punc_ != nullptr, PF_ERR_INVALID_ARG, "punctuate: no model is attached (pf_engine_set_punc_model)");
+  PF_CHECK(!punc_->causal, PF_ERR_UNSUPPORTED, "punctuate: a causal model runs in streaming form only (pf_op_punc_stream_step)");
   PF_CHECK(B >= 0 && B <= PF_PUNC_MAX_BATCH, PF_ERR_INVALID_ARG, "punctuate: B outside 0 .. PF_PUNC_MAX_BATCH");
   struct Text { int64_t begin = 0, n = 0, n_mini = 0, mini = 0, done = 0; std::vector<int32_t> win; };
   std::vector<Text> tx((size_t)B);

@@ -28,34 +28,17 @@
 // Rounding points (everything else is fp32): R0 the weights and R0e the embedding table, once, at attach time; R1 every
 // LayerNorm output; R2 q * dh^-0.5, k and v; R3 the softmax numerators exp(s - max) as the PV operand (their sum is taken
 // from the fp32 values); R4 ctx; R5 the FFN hidden after ReLU.  ReLU is x < 0 ? 0 : x, which keeps a NaN.
+// The tile geometry, the LayerNorm and the steps of the attention passes are punc_dev.h's, shared with k_punc_stream.hip.
 #include "kdev.h"
 #include "kernels.h"
+#include "punc_dev.h"
 #include "tile_rows.h"
 
 namespace pf {
 
 namespace {
 
-constexpr int PR_ROWS = TR_ROWS, PR_D = 256, PR_XLD = 260, PR_LD = 264;
-constexpr size_t PR_X_BYTES = (size_t)PR_ROWS * PR_XLD * 4, PR_BUF_BYTES = (size_t)PR_ROWS * PR_LD * 2;
 constexpr size_t PR_LDS_BYTES = PR_X_BYTES + 2 * PR_BUF_BYTES + PR_ROWS * 8 + PR_ROWS * 4;
-
-// LayerNorm of the fp32 tile into an f16 tile: one wave per row, four channels per lane                          (R1)
-__device__ __forceinline__ void pr_norm(const float* __restrict__ xs, const float* __restrict__ gam, const float* __restrict__ bet,
-                                        half_t* __restrict__ y, int wave, int lane) {
-  const float4 g4 = *reinterpret_cast<const float4*>(gam + 4 * lane), b4 = *reinterpret_cast<const float4*>(bet + 4 * lane);
-  for (int row = wave; row < PR_ROWS; row += 4) {
-    const float4 v = *reinterpret_cast<const float4a*>(xs + row * PR_XLD + 4 * lane);
-    const float mu = wave_sum((v.x + v.y) + (v.z + v.w)) * (1.f / PR_D);
-    const float d0 = v.x - mu, d1 = v.y - mu, d2 = v.z - mu, d3 = v.w - mu;
-    const float var = wave_sum((d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3)) * (1.f / PR_D);
-    const float inv = 1.f / sqrtf(var + 1e-12f);
-    h4 o;
-    o[0] = (half_t)(d0 * inv * g4.x + b4.x); o[1] = (half_t)(d1 * inv * g4.y + b4.y);
-    o[2] = (half_t)(d2 * inv * g4.z + b4.z); o[3] = (half_t)(d3 * inv * g4.w + b4.w);
-    *reinterpret_cast<h4a*>(y + row * PR_LD + 4 * lane) = o;
-  }
-}
 
 }  // namespace
 
@@ -271,26 +254,16 @@ __global__ __launch_bounds__(64) void punc_attn_kernel(PuncAttnLaunch a) {
   auto scores = [&](int kb, f16x* S) {
     const int kr = min(32 * kb + r, T - 1);
     const half_t* kp = base + (size_t)kr * (3 * PR_D) + PR_D + 8 * h;
-    const h8 k0 = *reinterpret_cast<const h8*>(kp), k1 = *reinterpret_cast<const h8*>(kp + 16);
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      f16x z;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) z[e] = 0.f;
-      z = __builtin_amdgcn_mfma_f32_32x32x16_f16(k0, qf[i][0], z, 0, 0, 0);
-      S[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(k1, qf[i][1], z, 0, 0, 0);
-    }
+    for (int i = 0; i < 2; ++i) S[i] = pa_scores(kp, qf[i]);
   };
-  // pass 1: the row maximum over the window's keys (register e of the accumulator is key 32 kb + (e & 3) + 8 (e >> 2) + 4 h)
+  // pass 1: the row maximum over the window's keys
   float mx[2] = {-INFINITY, -INFINITY};
   for (int kb = 0; kb < nkb; ++kb) {
     f16x S[2];
     scores(kb, S);
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int e = 0; e < 16; ++e)
-        if (32 * kb + (e & 3) + 8 * (e >> 2) + 4 * h < T) mx[i] = fmaxf(mx[i], S[i][e]);
+    for (int i = 0; i < 2; ++i) pa_max(S[i], 32 * kb + 4 * h, T, mx[i]);
   }
 #pragma unroll
   for (int i = 0; i < 2; ++i) mx[i] = fmaxf(mx[i], __shfl_xor(mx[i], 32, 64));
@@ -305,25 +278,9 @@ __global__ __launch_bounds__(64) void punc_attn_kernel(PuncAttnLaunch a) {
     f16x S[2];
     scores(kb, S);
     h8 vf[2];
+    pa_vfrag(vt + r * PA_VLD + 32 * kb + 4 * h, vf);
 #pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      const half_t* vp = vt + r * PA_VLD + 32 * kb + 16 * s + 4 * h;
-      const h4 lo = *reinterpret_cast<const h4a*>(vp), hi = *reinterpret_cast<const h4a*>(vp + 8);
-      vf[s] = h8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    }
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      h8 pf[2];
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        float p = 0.f;
-        if (32 * kb + (e & 3) + 8 * (e >> 2) + 4 * h < T) p = expf(S[i][e] - mx[i]);
-        sum[i] += p;
-        pf[e >> 3][e & 7] = (half_t)p;                                                       // R3
-      }
-      O[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf[0], pf[0], O[i], 0, 0, 0);
-      O[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf[1], pf[1], O[i], 0, 0, 0);
-    }
+    for (int i = 0; i < 2; ++i) pa_pv(S[i], mx[i], 32 * kb + 4 * h, T, vf, sum[i], O[i]);
   }
 #pragma unroll
   for (int i = 0; i < 2; ++i) {

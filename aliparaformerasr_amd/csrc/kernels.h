@@ -633,6 +633,25 @@ struct PuncCutLaunch {
 };
 void launch_punc_cut(hipStream_t s, const PuncCutLaunch& a);
 
+// ---------------------------------------------------------------- the punctuation model, streaming (k_punc_stream.hip) ------
+// paraformer_hip.h "Punctuation, streaming"; the definition in numpy is tests/punc_stream_ref.py.  ONE launch for B streams, one
+// workgroup of four waves per stream: stream b = its state block states + slot[b] * state_bytes (read, then written; slot null:
+// block b; the slots of a launch are distinct; the layout is punc.h PuncStreamLayout) and n_new[b] new word ids at ids + b * ld
+// (nothing at or beyond n_new[b] is read), then its flush when flush[b] != 0 (flush may be null).  marks / mark_flags [B, ld]
+// int32 and logits [B, ld, n_punc] fp32 (logits may be null): only a stream's first n_new[b] are written; flush_mark [B] is
+// always written.  The caller has admitted every stream (punc.h punc_stream_admit): ids inside the vocabulary, a count inside its
+// context and, with no_restart, count + n_new <= 256.
+struct PuncStreamLaunch {
+  const char* img; int n_layers, kernel, n_punc, max_context, no_restart;
+  int64_t pe_off, embed_off, n1_g[8], n1_b[8], taps[8], n2_g[8], n2_b[8], after_g, after_b;
+  TileGemm qkv[8], out[8], w1[8], w2[8], dec;
+  char* states; int64_t state_bytes, words_off; const int32_t* slot;
+  const int32_t* ids; int64_t ld; const int32_t* n_new; const int32_t* flush;
+  int id_none, id_comma, id_period, id_question, id_pause, sentence_end_id;
+  int32_t* marks; int32_t* mark_flags; float* logits; int32_t* flush_mark;
+};
+void launch_punc_stream(hipStream_t s, const PuncStreamLaunch& a, int B);
+
 // ---------------------------------------------------------------- the CAM++ speaker model (k_spk.hip) ------
 // The definition in numpy is tests/spk_ref.py; the launch plan (15 launches per forward) is at the head of k_spk.hip and
 // Engine::run_spk fills these in.  img: the model's device image (spk.h); every *_off and TileGemm offset is a byte offset into

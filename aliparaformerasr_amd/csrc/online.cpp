@@ -152,6 +152,32 @@ std::string online_decode_text(const std::vector<std::string>& tokens, const std
   return text;
 }
 
+// ---- streaming punctuation: the committed words of a partial text (tests/punc_stream_ref.py committed_words)
+OnlineCommitted online_committed_words(const PuncModel& m, const std::vector<std::string>& tokens, const std::vector<int64_t>& ids) {
+  OnlineCommitted c;
+  c.text = online_decode_text(tokens, ids);
+  c.words = host_punc_words(m, c.text);
+  const std::string* last = nullptr;                           // the last token that contributes text
+  for (int64_t id : ids) {
+    if (id == 2) break;
+    const std::string& tk = tokens[(size_t)id];                // (online_decode_text has checked the range)
+    if (tk != "</s>" && tk != "<s>" && tk != "<blank>" && tk != "<unk>") last = &tk;
+  }
+  const bool held = last && last->size() >= 2 && last->compare(last->size() - 2, 2, "@@") == 0 && !c.words.empty();
+  c.n_committed = c.words.size() - (held ? 1 : 0);
+  return c;
+}
+
+std::string online_word(const OnlineCommitted& c, size_t i) {
+  return c.text.substr((size_t)c.words[i].begin, (size_t)(c.words[i].end - c.words[i].begin));
+}
+
+void online_check_committed_prefix(const std::vector<std::string>& before, const OnlineCommitted& now) {
+  bool ok = before.size() <= now.n_committed;
+  for (size_t i = 0; ok && i < before.size(); ++i) ok = online_word(now, i) == before[i];
+  if (!ok) throw Error(PF_ERR_RECOGNITION, "streaming punctuation: the committed words of this call do not begin with the last call's");
+}
+
 // ------------------------------------------------------------------ OnlineStream -----------
 OnlineStreamM::OnlineStreamM(std::shared_ptr<OnlineRecognizerM> r) : owner(std::move(r)) {
   std::shared_ptr<Engine> e = owner->engine();
@@ -164,7 +190,7 @@ OnlineStreamM::OnlineStreamM(std::shared_ptr<OnlineRecognizerM> r) : owner(std::
 }
 
 OnlineStreamM::~OnlineStreamM() {
-  if (owner && (slot_ >= 0 || ep_joined_ || decoded_)) owner->release_stream(slot_, ep_joined_, decoded_);
+  if (owner && (slot_ >= 0 || ep_joined_ || decoded_ || pn_joined_)) owner->release_stream(slot_, ep_joined_, decoded_, pn_joined_);
 }
 
 const std::vector<pf_online_token>& OnlineStreamM::token_info() {
@@ -345,6 +371,10 @@ void OnlineRecognizerM::Dispose() {
     if (ep_states_) { hipSetDevice(e->device()); hipFree(ep_states_); ep_states_ = nullptr; ep_cap_ = 0; ep_free_.clear(); }
     if (ep_net_states_) { hipSetDevice(e->device()); hipFree(ep_net_states_); ep_net_states_ = nullptr; }
     if (ti_states_) { hipSetDevice(e->device()); hipFree(ti_states_); ti_states_ = nullptr; }
+    if (pn_states_) { hipSetDevice(e->device()); hipFree(pn_states_); pn_states_ = nullptr; }
+    if (pn_ws_) { hipSetDevice(e->device()); hipFree(pn_ws_); pn_ws_ = nullptr; pn_ws_bytes_ = 0; }
+    pn_model_.reset();
+    pn_on_ = false;
     ep_model_.reset();
     second_.reset();
   }
@@ -402,11 +432,43 @@ void OnlineRecognizerM::SetSecondPass(std::shared_ptr<Recognizer> offline) {
   second_ = std::move(offline);
 }
 
-void OnlineRecognizerM::release_stream(int slot, bool ep_joined, bool decoded) {
+void OnlineRecognizerM::release_stream(int slot, bool ep_joined, bool decoded, bool punc_joined) {
   std::lock_guard<std::mutex> lk(ep_mu_);
   if (ep_states_ && slot >= 0 && slot < ep_cap_) ep_free_.push_back(slot);
   if (ep_joined) --ep_live_;
   if (decoded) --decoded_live_;
+  if (punc_joined) --pn_live_;
+}
+
+void OnlineRecognizerM::SetPuncModel(const std::string& pfw_path, int max_context) {
+  if (disposed_) throw Error(PF_ERR_DISPOSED, "OnlineRecognizer");
+  std::shared_ptr<const PuncModel> pm;
+  const int mc = max_context == 0 ? kPuncStreamDefaultContext : max_context;
+  if (!pfw_path.empty()) {
+    pm = punc_model_load(pfw_path);                             // throws before anything changes
+    PF_CHECK(pm->causal == 1, PF_ERR_UNSUPPORTED, "streaming punctuation: the model is not causal (header key causal = 1)");
+    PF_CHECK(mc >= 2 && mc <= kPuncStreamMaxContext, PF_ERR_INVALID_ARG, "streaming punctuation: max_context outside 2 .. 256");
+  }
+  std::shared_ptr<Engine> eh = engine();
+  if (!eh) throw Error(PF_ERR_DISPOSED, "OnlineRecognizer");
+  std::lock_guard<std::mutex> lk(eh->mutex());
+  std::lock_guard<std::mutex> lk2(ep_mu_);
+  if (!pm && !pn_model_) return;
+  PF_CHECK(pn_live_ == 0, PF_ERR_UNSUPPORTED,
+           "streaming punctuation: a live stream holds punctuation state (attach or detach when no such stream is alive)");
+  eh->set_punc_model(pm);
+  PF_HIP(hipSetDevice(eh->device()));
+  if (pn_states_ || pn_ws_) {
+    PF_HIP(hipStreamSynchronize(eh->stream()));
+    if (pn_states_) PF_HIP(hipFree(pn_states_));
+    if (pn_ws_) PF_HIP(hipFree(pn_ws_));
+    pn_states_ = nullptr; pn_ws_ = nullptr; pn_ws_bytes_ = 0;
+  }
+  pn_model_ = pm;
+  pn_bytes_ = pm ? (size_t)punc_stream_layout(*pm).bytes : 0;
+  pn_max_context_ = mc;
+  if (pm && ep_cap_ > 0) PF_HIP(hipMalloc((void**)&pn_states_, (size_t)ep_cap_ * pn_bytes_));   // (a block is zeroed where a stream joins)
+  pn_on_ = pm != nullptr;
 }
 
 void OnlineRecognizerM::SetTokenInfo(bool on) {
@@ -450,6 +512,7 @@ void OnlineRecognizerM::ensure_slot(OnlineStreamM* s, Engine* e) {
     grow_slots(e, ep_states_, ep_cap_, cap, (size_t)PF_ENDPOINT_STATE_INTS * 4);
     if (ep_model_) grow_slots(e, ep_net_states_, ep_cap_, cap, ep_net_bytes_);   // the network's states grow with the detector's
     if (ti_on_) grow_slots(e, ti_states_, ep_cap_, cap, ti_bytes_);              // and so does the decoder state
+    if (pn_model_) grow_slots(e, pn_states_, ep_cap_, cap, pn_bytes_);           // and the punctuation state
     for (int i = cap - 1; i >= ep_cap_; --i) ep_free_.push_back(i);
     ep_cap_ = cap;
   }
@@ -476,7 +539,8 @@ void OnlineRecognizerM::ForwardEndpoint(const std::vector<OnlineStreamM*>& strea
     if (disposed_ || !eh) throw Error(PF_ERR_DISPOSED, "OnlineRecognizer");
     Engine* e = eh.get();
     std::lock_guard<std::mutex> lk(e->mutex());
-    { std::lock_guard<std::mutex> ls(ep_mu_); net = ep_model_; }      // (SetEndpointModel changes it under the engine's mutex)
+    std::shared_ptr<const PuncModel> punc;
+    { std::lock_guard<std::mutex> ls(ep_mu_); net = ep_model_; punc = pn_model_; }      // (both change under the engine's mutex)
     // who takes part: new rows, or the flush once the model has decoded every chunk of a finished input
     std::vector<OnlineStreamM*> work;
     std::vector<int32_t> n_new, flush, slot;
@@ -534,6 +598,12 @@ void OnlineRecognizerM::ForwardEndpoint(const std::vector<OnlineStreamM*>& strea
         sen.first_pass = online_decode_text(tokens_, s->Tokens);            // after this chunk's ids were appended
         sen.text = sen.first_pass;
         sen.tokens = s->token_info();                                        // (cleared with Tokens at the reset)
+        if (punc && !s->pn_close_.on) {                                      // the sentence's words, before the reset forgets them
+          s->pn_close_.c = online_committed_words(*punc, tokens_, s->Tokens);
+          online_check_committed_prefix(s->pn_words_, s->pn_close_.c);
+          s->pn_close_.sentence = s->Sentences.size();
+          s->pn_close_.on = true;
+        }
         s->ResetDecoder();
         const int64_t a0 = 160 * fb - s->ep_audio_base_, a1 = std::min<int64_t>(s->ep_samples_, 160 * fe) - s->ep_audio_base_;
         PF_CHECK(a0 >= 0 && a1 > a0 && a1 <= (int64_t)s->ep_audio_.size(), PF_ERR_RECOGNITION, "endpoint: a sentence outside the retained audio");
@@ -722,9 +792,126 @@ void OnlineRecognizerM::ForwardDevice(Engine* e, const std::vector<OnlineStreamM
   }
 }
 
+// Streaming punctuation: the newly committed words of the call's streams (at a sentence close and at the end of the input every
+// remaining word, with the flush) in ONE punc_stream launch: one staged copy up, one down; no launch when nothing is new.
+void OnlineRecognizerM::ForwardPunc(const std::vector<OnlineStreamM*>& streams) {
+  struct Job { OnlineStreamM* s; OnlineCommitted c; size_t n_send = 0, sentence = 0; bool flush = false, close = false, launch = false; int n_new = 0; };
+  try {
+    std::shared_ptr<Engine> eh = engine();
+    if (disposed_ || !eh) throw Error(PF_ERR_DISPOSED, "OnlineRecognizer");
+    Engine* e = eh.get();
+    std::lock_guard<std::mutex> lk(e->mutex());
+    std::shared_ptr<const PuncModel> pm;
+    int mc = 0;
+    { std::lock_guard<std::mutex> ls(ep_mu_); pm = pn_model_; mc = pn_max_context_; }
+    if (!pm) return;
+    std::vector<Job> jobs;
+    const size_t CLF = (size_t)chunk_length() * 80;
+    int B = 0, ld = 1;
+    for (OnlineStreamM* s : streams) {
+      bool seen = false;
+      for (const Job& j : jobs) seen = seen || j.s == s;
+      if (seen) continue;
+      std::lock_guard<std::mutex> ls(s->mu);
+      Job j;
+      j.s = s;
+      if (s->pn_close_.on) {
+        j.c = std::move(s->pn_close_.c);
+        j.sentence = s->pn_close_.sentence;
+        j.close = j.flush = true;
+        s->pn_close_ = OnlineStreamM::PuncPending();
+      } else {
+        if (s->pn_flushed_) continue;                          // the end-of-input flush was made: nothing follows it
+        j.c = online_committed_words(*pm, tokens_, s->Tokens);
+        online_check_committed_prefix(s->pn_words_, j.c);
+        j.flush = s->finished_ && s->cache_samples_.empty() && s->Speech.size() < CLF;
+      }
+      j.n_send = j.flush ? j.c.words.size() : j.c.n_committed;   // a flush takes the held-back word too
+      j.n_new = (int)(j.n_send - s->pn_words_.size());
+      j.launch = j.n_new > 0 || (j.flush && s->pn_joined_);
+      if (j.launch) { ++B; ld = std::max(ld, j.n_new); }
+      jobs.push_back(std::move(j));
+    }
+    std::vector<int32_t> down;
+    if (B > 0) {
+      PF_HIP(hipSetDevice(e->device()));
+      const size_t nB = (size_t)B, cells = nB * (size_t)ld, up_n = 3 * nB + cells, down_n = 2 * cells + nB;
+      std::vector<int32_t> up(up_n, 0);
+      int b = 0;
+      for (Job& j : jobs) {
+        if (!j.launch) continue;
+        OnlineStreamM* s = j.s;
+        ensure_slot(s, e);
+        if (!s->pn_joined_) {                                  // the block is zeroed where the stream first uses it
+          std::lock_guard<std::mutex> ls(ep_mu_);
+          PF_HIP(hipMemsetAsync(pn_states_ + (size_t)s->slot_ * pn_bytes_, 0, pn_bytes_, e->stream()));
+          s->pn_joined_ = true;
+          ++pn_live_;
+        }
+        up[(size_t)b] = s->slot_; up[nB + b] = j.n_new; up[2 * nB + b] = j.flush ? 1 : 0;
+        for (int i = 0; i < j.n_new; ++i) up[3 * nB + (size_t)b * ld + i] = j.c.words[j.n_send - (size_t)j.n_new + (size_t)i].id;
+        ++b;
+      }
+      char* states = nullptr;
+      {
+        std::lock_guard<std::mutex> ls(ep_mu_);
+        if (pn_ws_bytes_ < (up_n + down_n) * 4) {
+          if (pn_ws_) { PF_HIP(hipStreamSynchronize(e->stream())); PF_HIP(hipFree(pn_ws_)); pn_ws_ = nullptr; pn_ws_bytes_ = 0; }
+          PF_HIP(hipMalloc((void**)&pn_ws_, 2 * (up_n + down_n) * 4));
+          pn_ws_bytes_ = 2 * (up_n + down_n) * 4;
+        }
+        states = pn_states_;
+      }
+      PF_CHECK(states != nullptr, PF_ERR_DEVICE, "streaming punctuation: no state buffer");
+      int32_t* d_up = reinterpret_cast<int32_t*>(pn_ws_);
+      int32_t* d_down = d_up + up_n;
+      PF_HIP(hipMemcpyAsync(d_up, up.data(), up_n * 4, hipMemcpyHostToDevice, e->stream()));
+      e->punc_stream_step(states, d_up, d_up + 3 * nB, ld, d_up + nB, d_up + 2 * nB, B, mc, 0, d_down, d_down + cells, nullptr, d_down + 2 * cells);
+      down.resize(down_n);
+      PF_HIP(hipMemcpyAsync(down.data(), d_down, down_n * 4, hipMemcpyDeviceToHost, e->stream()));
+      PF_HIP(hipStreamSynchronize(e->stream()));
+    }
+    int b = 0;
+    for (Job& j : jobs) {
+      OnlineStreamM* s = j.s;
+      std::lock_guard<std::mutex> ls(s->mu);
+      if (j.launch) {
+        const size_t cells = (size_t)B * ld;
+        for (int i = 0; i < j.n_new; ++i) {
+          const int32_t p = down[(size_t)b * ld + i];
+          PF_CHECK(p >= 0 && p < pm->n_punc, PF_ERR_DEVICE, "streaming punctuation: a mark outside punc_list");
+          s->PuncIds.push_back(p);
+          s->PuncFlags.push_back(down[cells + (size_t)b * ld + i]);
+          s->pn_words_.push_back(online_word(j.c, j.n_send - (size_t)j.n_new + (size_t)i));
+        }
+        const int32_t fm = down[2 * cells + b];
+        if (j.flush && fm >= 0 && fm < pm->n_punc && !s->PuncIds.empty()) s->PuncIds.back() = fm;   // the flush's edit of the newest word
+        ++b;
+      }
+      std::vector<int32_t> ids(s->PuncIds);
+      ids.resize(j.c.words.size(), pm->id_none);               // a held-back word is written raw
+      const std::string text = host_punc_assemble(*pm, j.c.text, j.c.words, ids.data(), nullptr);
+      if (j.close) {
+        if (j.sentence < s->Sentences.size()) {
+          s->Sentences[j.sentence].punctuated = text;
+          s->Sentences[j.sentence].punc_ids = s->PuncIds;
+        }
+        s->PuncIds.clear(); s->PuncFlags.clear(); s->pn_words_.clear(); s->Punctuated.clear();   // the next sentence starts a fresh context
+      } else {
+        s->Punctuated = text;
+        if (j.flush) s->pn_flushed_ = true;
+      }
+    }
+  } catch (const Error& ex) {
+    if (ex.code != PF_ERR_RECOGNITION) throw;
+    throw Error(PF_ERR_RECOGNITION, std::string("Online recognition failed: ") + ex.what());
+  }
+}
+
 std::vector<std::string> OnlineRecognizerM::GetResults(const std::vector<OnlineStreamM*>& streams) {
   Forward(streams);
   if (endpoint_on()) ForwardEndpoint(streams);
+  if (punc_on()) ForwardPunc(streams);
   std::vector<std::string> out;
   for (OnlineStreamM* s : streams) out.push_back(online_decode_text(tokens_, s->Tokens));
   return out;

@@ -42,6 +42,14 @@ int online_cif_step(void* state, const float* hiddens, const float* alphas, int 
                     float* fired, int32_t* fire_entry, int cap);
 // OnlineRecognizer.DecodeMulti (:405-437) for one stream
 std::string online_decode_text(const std::vector<std::string>& tokens, const std::vector<int64_t>& ids);
+// Streaming punctuation (paraformer_hip.h "Punctuation, streaming"; tests/punc_stream_ref.py committed_words): the words of
+// online_decode_text(tokens, ids) as host_punc_words splits them.  While the last token that contributes text ends in "@@" the
+// last word is held back (n_committed = words.size() - 1): the next piece changes it.
+struct OnlineCommitted { std::string text; std::vector<PuncWord> words; size_t n_committed = 0; };
+OnlineCommitted online_committed_words(const PuncModel& m, const std::vector<std::string>& tokens, const std::vector<int64_t>& ids);
+std::string online_word(const OnlineCommitted& c, size_t i);
+// the committed words of one call must be a prefix of the next call's: PF_ERR_RECOGNITION otherwise
+void online_check_committed_prefix(const std::vector<std::string>& before, const OnlineCommitted& now);
 
 class OnlineRecognizerM;
 class Recognizer;
@@ -62,7 +70,13 @@ class OnlineStreamM {
   struct SentenceM {
     int begin_ms = 0, end_ms = 0, kind = 0; std::string first_pass, text; std::shared_ptr<Stream> offline;
     std::vector<pf_online_token> tokens;                      // TokenInfo as of the closing call (empty without SetTokenInfo)
+    std::string punctuated;                                   // SetPuncModel: first_pass under its marks, the flush's edit applied
+    std::vector<int32_t> punc_ids;
   };
+  // SetPuncModel: of the last GetResults, the open text under the marks of its committed words (a held-back word appended raw),
+  // the mark and the restart flags (bit 0 sentence end, bit 1 forced restart) of every committed word
+  std::string Punctuated;
+  std::vector<int32_t> PuncIds, PuncFlags;
   std::vector<SentenceM> Sentences;
   bool InSpeech = false;                                      // a sentence is open (as of the last GetResults)
   int OpenBeginMs = -1;
@@ -110,6 +124,12 @@ class OnlineStreamM {
   std::vector<float> ep_rows_, ep_audio_;
   int ep_fed_ = 0, ep_prev_end_ = 0;
   bool ep_flushed_ = false;
+  // streaming punctuation: the committed words already marked (the next call's must begin with them), whether the slot's
+  // punctuation state is in use, whether the end-of-input flush was made, and what an endpoint close left for this call's launch
+  std::vector<std::string> pn_words_;
+  bool pn_joined_ = false, pn_flushed_ = false;
+  struct PuncPending { bool on = false; size_t sentence = 0; OnlineCommitted c; };
+  PuncPending pn_close_;
 };
 
 class OnlineRecognizerM : public std::enable_shared_from_this<OnlineRecognizerM> {
@@ -148,12 +168,20 @@ class OnlineRecognizerM : public std::enable_shared_from_this<OnlineRecognizerM>
   // OnlineStreamM::TokenInfo.  PF_ERR_UNSUPPORTED once a live stream has decoded a chunk; the value it already has is a no-op.
   void SetTokenInfo(bool on);
   bool token_info_on() const { return ti_on_.load(); }
-  void release_stream(int slot, bool ep_joined, bool decoded);   // ~OnlineStreamM
+  // Streaming punctuation (paraformer_hip.h "Punctuation, streaming"): loads a causal `.pfw` of kind
+  // "cttransformer" and attaches it to the engine; "" detaches and frees.  Every GetResults then marks the newly committed
+  // words of all its streams in ONE punc_stream launch; a stream's keys and values live in one more slot-indexed device buffer.
+  // max_context 0: the default of 200.  PF_ERR_UNSUPPORTED for a model that is not causal and while a live stream holds
+  // punctuation state; PF_ERR_INVALID_ARG for max_context outside 2 .. 256.
+  void SetPuncModel(const std::string& pfw_path, int max_context);
+  bool punc_on() const { return pn_on_.load(); }
+  void release_stream(int slot, bool ep_joined, bool decoded, bool punc_joined);   // ~OnlineStreamM
 
  private:
   void Forward(const std::vector<OnlineStreamM*>& streams);   // :336-403
   void ForwardEndpoint(const std::vector<OnlineStreamM*>& streams);
   void ForwardDevice(Engine* e, const std::vector<OnlineStreamM*>& work, const std::vector<float>& speech, int Tc);
+  void ForwardPunc(const std::vector<OnlineStreamM*>& streams);
   // a slot for a stream that has none (the engine's mutex is held): every per-stream buffer grows together by reallocate-and-copy
   // on the device; the detector's and the network's blocks are zeroed where the stream joins the detector (ForwardEndpoint),
   // the decoder state by its reset flags
@@ -171,6 +199,12 @@ class OnlineRecognizerM : public std::enable_shared_from_this<OnlineRecognizerM>
   size_t ep_net_bytes_ = 0;
   char* ti_states_ = nullptr;                                 // [ep_cap_, ti_bytes_] on the device: CIF block | FSMN caches per slot (SetTokenInfo)
   size_t ti_bytes_ = 0;
+  std::atomic<bool> pn_on_{false};
+  std::shared_ptr<const PuncModel> pn_model_;                 // SetPuncModel
+  char* pn_states_ = nullptr;                                 // [ep_cap_, pn_bytes_] on the device: k | v and the count per slot
+  char* pn_ws_ = nullptr;                                     // the launch's staged operands and results
+  size_t pn_bytes_ = 0, pn_ws_bytes_ = 0;
+  int pn_max_context_ = 0, pn_live_ = 0;
   int ep_live_ = 0, decoded_live_ = 0;                        // live streams that have fed the detector / decoded a chunk
   std::mutex mu_;
   std::shared_ptr<Engine> engine_;

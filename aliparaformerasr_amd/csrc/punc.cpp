@@ -101,6 +101,15 @@ std::shared_ptr<const PuncModel> parse(const char* data, int64_t nbytes) {
   if (se < 0 || se >= P) bad("sentence_end_id is outside punc_list");
   m->vocab = (int)V; m->d_model = (int)D; m->heads = (int)H; m->ffn = (int)F; m->kernel = (int)K; m->n_layers = (int)NL;
   m->n_punc = (int)P; m->sentence_end_id = (int)se;
+  {
+    const int64_t causal = jc->int_or("causal", 0, INT32_MIN, INT32_MAX), shift = jc->int_or("sanm_shift", 0, INT32_MIN, INT32_MAX);
+    if (causal != 0 && causal != 1) bad("causal is neither 0 nor 1");
+    const int64_t left = (K - 1) / 2 + shift;
+    if (left < 0 || left > K - 1) bad("sanm_shift moves the FSMN taps outside the kernel");
+    PF_CHECK(causal ? left == K - 1 : shift == 0, PF_ERR_UNSUPPORTED,
+             "punc model: a causal model takes all its FSMN taps from the left (sanm_shift = (kernel - 1) / 2), any other model none");
+    m->causal = (int)causal; m->left = (int)left;
+  }
 
   const char* sec = data + fr.data_off;
   auto take = [&](const std::string& name, std::vector<int64_t> shape) { return pfw_take(ix, sec, name, shape, kPfwPuncModel); };
@@ -207,7 +216,7 @@ std::vector<PuncWord> host_punc_words(const PuncModel& m, const std::string& tex
 void host_punc_logits(const PuncModel& m, const int32_t* ids, int T, double* logits) {
   PF_CHECK(T >= 0 && T <= PF_PUNC_MAX_WINDOW, PF_ERR_INVALID_ARG, "punc: a window holds 0 .. PF_PUNC_MAX_WINDOW ids");
   if (T == 0) return;
-  const int D = m.d_model, H = m.heads, dh = D / H, K = m.kernel, left = (K - 1) / 2;
+  const int D = m.d_model, H = m.heads, dh = D / H, K = m.kernel, left = m.left;
   std::vector<float> pe;
   sinusoidal_pe(T, D, pe);
   std::vector<double> x((size_t)T * D), xn, qkv, att, h, y;
@@ -228,7 +237,8 @@ void host_punc_logits(const PuncModel& m, const int32_t* ids, int T, double* log
       for (int t = 0; t < T; ++t) {
         double mx = -INFINITY;
         bool nan = false;
-        for (int u = 0; u < T; ++u) {
+        const int nk = m.causal ? t + 1 : T;                  // a causal model's keys end at the query
+        for (int u = 0; u < nk; ++u) {
           double a = 0.0;
           for (int c = 0; c < dh; ++c) a += qkv[(size_t)t * 3 * D + hd * dh + c] * qs * qkv[(size_t)u * 3 * D + D + hd * dh + c];
           s[(size_t)u] = a;
@@ -236,10 +246,10 @@ void host_punc_logits(const PuncModel& m, const int32_t* ids, int T, double* log
           mx = std::max(mx, a);
         }
         double sum = 0.0;
-        for (int u = 0; u < T; ++u) { s[(size_t)u] = nan ? NAN : std::exp(s[(size_t)u] - mx); sum += s[(size_t)u]; }
+        for (int u = 0; u < nk; ++u) { s[(size_t)u] = nan ? NAN : std::exp(s[(size_t)u] - mx); sum += s[(size_t)u]; }
         for (int c = 0; c < dh; ++c) {
           double a = 0.0;
-          for (int u = 0; u < T; ++u) a += s[(size_t)u] * qkv[(size_t)u * 3 * D + 2 * D + hd * dh + c];
+          for (int u = 0; u < nk; ++u) a += s[(size_t)u] * qkv[(size_t)u * 3 * D + 2 * D + hd * dh + c];
           ctx[(size_t)t * D + hd * dh + c] = a / sum;
         }
       }
@@ -333,6 +343,110 @@ std::string host_punc_assemble(const PuncModel& m, const std::string& text, cons
     if (sent_end && (end || i + 1 == words.size())) sent_end->push_back((int32_t)i + 1);
   }
   return out;
+}
+
+// ---- streaming (paraformer_hip.h "Punctuation, streaming"; the definition is tests/punc_stream_ref.py)
+PuncStreamLayout punc_stream_layout(const PuncModel& m) {
+  const int64_t kv = (int64_t)m.n_layers * kPuncStreamMaxContext * 2 * m.d_model * 2;
+  return PuncStreamLayout{kv, kv + 16};
+}
+
+int64_t host_punc_stream_state_bytes(const PuncModel& m) { return (int64_t)m.n_layers * kPuncStreamMaxContext * 2 * m.d_model * 8 + 16; }
+
+void punc_stream_admit(const PuncModel& m, int32_t count, const int32_t* ids, int n_new, int max_context, int flags) {
+  PF_CHECK(m.causal == 1, PF_ERR_UNSUPPORTED, "punc stream: the model is not causal (header key causal = 1)");
+  PF_CHECK(max_context >= 2 && max_context <= kPuncStreamMaxContext, PF_ERR_INVALID_ARG, "punc stream: max_context outside 2 .. 256");
+  PF_CHECK(n_new >= 0 && (flags & ~1) == 0, PF_ERR_INVALID_ARG, "punc stream: a negative n_new or an unknown flag");
+  PF_CHECK(count >= 0 && count <= kPuncStreamMaxContext && ((flags & 1) || count < max_context), PF_ERR_INVALID_ARG,
+           "punc stream: the state block's count is outside its context (not a state of this model and max_context)");
+  PF_CHECK(!(flags & 1) || (int64_t)count + n_new <= kPuncStreamMaxContext, PF_ERR_INVALID_ARG,
+           "punc stream: without restarts a context holds at most 256 words");
+  for (int i = 0; i < n_new; ++i)
+    PF_CHECK(ids[i] >= 0 && ids[i] < m.vocab, PF_ERR_INVALID_ARG, "punc stream: a word id is outside the vocabulary");
+}
+
+void host_punc_stream_step(const PuncModel& m, void* state, const int32_t* ids, int n_new, bool flush, int max_context, int flags,
+                           int32_t* marks, int32_t* mark_flags, double* logits, int32_t* flush_mark) {
+  const int D = m.d_model, H = m.heads, dh = D / H, K = m.kernel, NL = m.n_layers, P = m.n_punc, C = kPuncStreamMaxContext;
+  char* words_at = static_cast<char*>(state) + (size_t)NL * C * 2 * D * 8;
+  int32_t words[4];
+  std::memcpy(words, words_at, 16);
+  punc_stream_admit(m, words[0], ids, n_new, max_context, flags);
+  double* kv = static_cast<double*>(state);                      // k | v [n_layers, 256, 2, d_model]
+  auto row = [&](int l, int t, int which) { return kv + (((size_t)l * C + t) * 2 + which) * D; };
+  int n = words[0], last = words[1];
+  std::vector<float> pe;
+  sinusoidal_pe(C, D, pe);
+  const float scale = (float)std::sqrt((double)D);
+  const double qs = 1.0 / std::sqrt((double)dh);
+  std::vector<double> x((size_t)D), xn, qkv, ctx((size_t)D), att, h, y, s((size_t)C);
+  for (int w = 0; w < n_new; ++w) {
+    const int t = n;                                             // the word's index in its context
+    for (int c = 0; c < D; ++c) {
+      const float a = m.embed[(size_t)ids[w] * D + c] * scale;
+      x[(size_t)c] = (double)(float)(a + pe[(size_t)t * D + c]);
+    }
+    for (int l = 0; l < NL; ++l) {
+      const PuncModel::Layer& L = m.layers[(size_t)l];
+      norm64(x, 1, D, L.n1_g, L.n1_b, xn);
+      affine64(xn, 1, D, L.qkv_w, &L.qkv_b, 3 * D, false, qkv);
+      std::memcpy(row(l, t, 0), qkv.data() + D, (size_t)D * 8);
+      std::memcpy(row(l, t, 1), qkv.data() + 2 * D, (size_t)D * 8);
+      for (int hd = 0; hd < H; ++hd) {
+        double mx = -INFINITY;
+        bool nan = false;
+        for (int u = 0; u <= t; ++u) {
+          double a = 0.0;
+          for (int c = 0; c < dh; ++c) a += qkv[(size_t)(hd * dh + c)] * qs * row(l, u, 0)[hd * dh + c];
+          s[(size_t)u] = a;
+          if (a != a) nan = true;
+          mx = std::max(mx, a);
+        }
+        double sum = 0.0;
+        for (int u = 0; u <= t; ++u) { s[(size_t)u] = nan ? NAN : std::exp(s[(size_t)u] - mx); sum += s[(size_t)u]; }
+        for (int c = 0; c < dh; ++c) {
+          double a = 0.0;
+          for (int u = 0; u <= t; ++u) a += s[(size_t)u] * row(l, u, 1)[hd * dh + c];
+          ctx[(size_t)(hd * dh + c)] = a / sum;
+        }
+      }
+      affine64(ctx, 1, D, L.out_w, &L.out_b, D, false, att);
+      for (int c = 0; c < D; ++c) {
+        double f = row(l, t, 1)[c];
+        for (int j = 0; j < K; ++j) {
+          const int u = t - (K - 1) + j;                         // a tap before the context's first word is skipped
+          if (u >= 0) f += (double)L.fsmn[(size_t)c * K + j] * row(l, u, 1)[c];
+        }
+        x[(size_t)c] += att[(size_t)c] + f;
+      }
+      norm64(x, 1, D, L.n2_g, L.n2_b, xn);
+      affine64(xn, 1, D, L.w1_w, &L.w1_b, m.ffn, true, h);
+      affine64(h, 1, m.ffn, L.w2_w, &L.w2_b, D, false, y);
+      for (int c = 0; c < D; ++c) x[(size_t)c] += y[(size_t)c];
+    }
+    norm64(x, 1, D, m.after_g, m.after_b, xn);
+    affine64(xn, 1, D, m.dec_w, &m.dec_b, P, false, y);
+    if (logits) std::memcpy(logits + (size_t)w * P, y.data(), (size_t)P * 8);
+    int32_t p = 0;
+    host_punc_argmax(m, y.data(), 1, &p);
+    int mf = 0;
+    n = t + 1;
+    last = p;
+    if (!(flags & 1)) {
+      if ((m.id_period >= 0 && p == m.id_period) || (m.id_question >= 0 && p == m.id_question)) { mf = 1; n = 0; }
+      else if (n == max_context) { mf = 2; n = 0; }
+    }
+    marks[w] = p;
+    mark_flags[w] = mf;
+  }
+  int fm = -1;
+  if (flush) {
+    if (n > 0) fm = punc_flush_mark(m, last);
+    n = 0;
+  }
+  if (flush_mark) *flush_mark = fm;
+  words[0] = n; words[1] = n > 0 ? last : 0;
+  std::memcpy(words_at, words, 16);
 }
 
 }  // namespace pf

@@ -1392,6 +1392,7 @@ void Recognizer::SetPuncModel(const std::string& pfw_path) {
   if (disposed_) throw Error(PF_ERR_DISPOSED, "OfflineRecognizer");
   std::shared_ptr<const PuncModel> pm;
   if (!pfw_path.empty()) pm = punc_model_load(pfw_path);                     // throws before anything changes
+  if (pm) PF_CHECK(!pm->causal, PF_ERR_UNSUPPORTED, "SetPuncModel: a causal model punctuates streams, not finished texts");
   std::vector<std::shared_ptr<Engine>> es;
   {
     std::lock_guard<std::mutex> lk(mu_);

@@ -629,6 +629,9 @@ class PuncModel:
         N.check(self._lib.pf_punc_model_info(self._h, _i32p(d), ib))
         self.dims = dict(zip(PUNC_MODEL_DIMS, d.tolist()))
         self.image_bytes = ib.value
+        c = C.c_int32()
+        N.check(self._lib.pf_punc_model_causal(self._h, C.byref(c)))
+        self.causal = bool(c.value)                     # the streaming form (header key causal = 1)
 
     def close(self):
         if self._h is not None:
@@ -651,6 +654,53 @@ def load_punc_model(source) -> PuncModel:
     else:
         N.check(N.load().pf_punc_model_load(str(source).encode("utf-8"), C.byref(h)))
     return PuncModel(h)
+
+
+PUNC_STREAM_MAX_CONTEXT = 256
+PUNC_STREAM_DEFAULT_CONTEXT = 200
+PUNC_STREAM_NO_RESTARTS = 1
+
+
+def punc_stream_state(model: PuncModel, B=None, host=False) -> np.ndarray:
+    """A fresh streaming punctuation state: zeros uint8 [state_bytes] (B given: [B, state_bytes]).  host=False: the device
+    form's (pf_punc_stream_state_bytes); True: the host twin's own."""
+    nb = C.c_int64()
+    fn = N.load().pf_host_punc_stream_state_bytes if host else N.load().pf_punc_stream_state_bytes
+    N.check(fn(model._h, C.byref(nb)))
+    return np.zeros(nb.value if B is None else (B, nb.value), np.uint8)
+
+
+def host_punc_stream_step(model: PuncModel, state, ids, flush=False, max_context=PUNC_STREAM_DEFAULT_CONTEXT, flags=0,
+                          want_logits=True):
+    """One call of ONE stream in host code, float64 (pf_host_punc_stream_step): the new word ids in order, then the flush.
+    state (punc_stream_state(model, host=True)) is updated in place.  Returns (marks [n] int32, mark_flags [n] int32, logits
+    [n, n_punc] float64 or None, flush_mark)."""
+    a = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+    assert isinstance(state, np.ndarray) and state.dtype == np.uint8 and state.flags.c_contiguous
+    P = model.dims["n_punc"]
+    mk, mf = np.full(max(a.size, 1), -77777, np.int32), np.full(max(a.size, 1), -77777, np.int32)
+    z = np.zeros((max(a.size, 1), P), np.float64) if want_logits else None
+    fm = C.c_int32(-77777)
+    N.check(N.load().pf_host_punc_stream_step(model._h, state.ctypes.data_as(C.c_void_p), _i32p(a), a.size, int(bool(flush)),
+                                              int(max_context), int(flags), _i32p(mk), _i32p(mf), _dp(z) if want_logits else None,
+                                              C.byref(fm)))
+    return mk[: a.size].copy(), mf[: a.size].copy(), (z[: a.size].copy() if want_logits else None), fm.value
+
+
+def host_online_committed_words(model: PuncModel, tokens, ids, before=None):
+    """The committed words of a streaming partial text (pf_host_online_committed_words): tokens = the token table, ids = the
+    stream's Tokens.  Returns (the committed words, the held-back word or None).  before: the committed words of the last call;
+    they must be a prefix of this call's (PF_ERR_RECOGNITION otherwise)."""
+    tk = (C.c_char_p * max(len(tokens), 1))(*[t.encode("utf-8") for t in tokens])
+    a = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+    ln, nc, nw = C.c_int64(), C.c_int32(), C.c_int32()
+    bf = None if before is None else "\n".join(before).encode("utf-8")
+    fn = N.load().pf_host_online_committed_words
+    N.check(fn(model._h, tk, len(tokens), a.ctypes.data_as(C.POINTER(C.c_int64)), a.size, bf, None, 0, ln, nc, nw))
+    buf = C.create_string_buffer(max(ln.value, 1))
+    N.check(fn(model._h, tk, len(tokens), a.ctypes.data_as(C.POINTER(C.c_int64)), a.size, bf, buf, ln.value, ln, nc, nw))
+    words = buf.raw[: ln.value].decode("utf-8").split("\n") if nw.value else []
+    return words[: nc.value], (words[nc.value] if nw.value > nc.value else None)
 
 
 def host_punc_words(model: PuncModel, text: str):
@@ -1501,6 +1551,37 @@ class Engine:
         if want_x0:
             return zs, [x0[off[b]: off[b + 1]].copy() for b in range(len(arrs))]
         return zs
+
+    def op_punc_stream_step(self, states, ids_list, flush=None, max_context=PUNC_STREAM_DEFAULT_CONTEXT, flags=0, want_logits=True,
+                            ld=None, out=None):
+        """The attached causal model's streaming launch on caller state blocks and ids (pf_op_punc_stream_step): ONE launch over
+        all the streams.  states [B, state_bytes] uint8 (punc_stream_state), updated in place; ids_list: each stream's new word
+        ids (any counts, may be empty); flush: per-stream flags.  Returns per stream (marks [n_b], mark_flags [n_b]), the
+        logits [n_b, n_punc] float32 or None, and flush_mark [B].  out: a dict that receives the raw output arrays (marks,
+        mark_flags, logits, flush_mark) with their fill values behind every stream's n_new (tests look at what lies beyond)."""
+        arrs = [np.ascontiguousarray(a, dtype=np.int32).reshape(-1) for a in ids_list]
+        B = len(arrs)
+        assert isinstance(states, np.ndarray) and states.dtype == np.uint8 and states.flags.c_contiguous and states.shape[0] == B
+        ld = max([a.size for a in arrs] + [1]) if ld is None else ld
+        x = np.full((max(B, 1), ld), 2 ** 30, np.int32)              # past n_new[b]: ids that would be refused or fault if read
+        for b, a in enumerate(arrs):
+            x[b, : min(a.size, ld)] = a[:ld]
+        n_new = np.ascontiguousarray([a.size for a in arrs] + [0] * (B == 0), dtype=np.int32)
+        fl = np.zeros(max(B, 1), np.int32)
+        if flush is not None:
+            fl[:B] = np.asarray(flush, dtype=bool).astype(np.int32)
+        P = self._punc_model.dims["n_punc"] if self._punc_model is not None else 1      # (without a model the call is refused)
+        mk = np.full((max(B, 1), ld), -77777, np.int32)
+        mf = np.full((max(B, 1), ld), -77777, np.int32)
+        z = np.full((max(B, 1), ld, P), np.float32(-7e7), np.float32) if want_logits else None
+        fm = np.full(max(B, 1), -77777, np.int32)
+        N.check(self._lib.pf_op_punc_stream_step(self._h, states.ctypes.data_as(C.c_void_p), _i32p(x), _i32p(n_new), _i32p(fl), B, ld,
+                                                 int(max_context), int(flags), _i32p(mk), _i32p(mf), _fp(z) if want_logits else None,
+                                                 _i32p(fm)))
+        if out is not None:
+            out.update(marks=mk, mark_flags=mf, logits=z, flush_mark=fm, n_new=n_new)
+        return ([(mk[b, : n_new[b]].copy(), mf[b, : n_new[b]].copy()) for b in range(B)],
+                [z[b, : n_new[b]].copy() for b in range(B)] if want_logits else None, fm[:B].copy())
 
     def op_punc_window(self, ids_list, last, want_logits=False):
         """As op_punc_logits with the cut launch behind it (pf_op_punc_window): last[b] marks a text's last window; returns

@@ -2,7 +2,7 @@
 
     python -m aliparaformerasr_amd.examples -type offline -method batch -base <dir> -model <name> \
         [-accuracy int8] [-threads 2] [-decode ctc|frames] [-intake host|device] [-nbest N [-topk K] [-beam W | -search W] [-hotboost S] [-lm FILE [-lmweight A] [-lmbonus B] [-lmeos]]] [-align FILE|beam] [-vad [key=value,...] [-vadmodel FILE] [-spk FILE [key=value,...]]] [-punc FILE] -files a.wav b.wav
-    python -m aliparaformerasr_amd.examples -type online -method one -base <dir> -model <name> [-endpoint [key=value,...] [-vadmodel FILE] [-secondpass <offline name>]] [-tokentimes] -files a.wav
+    python -m aliparaformerasr_amd.examples -type online -method one -base <dir> -model <name> [-endpoint [key=value,...] [-vadmodel FILE] [-secondpass <offline name>]] [-tokentimes] [-puncstream FILE[,max_context=N]] -files a.wav
 
 Mirrors (file:line in /root/reference/AliParaformerAsr.Examples):
   * argument handling and defaults — Program.cs:93-104, ParseArgs :197-252: the MANYSPEECH_BASE / _TYPE / _BATCH / _MODEL /
@@ -69,7 +69,10 @@ abs_level=9830; unvalidated too) apply unless keys are given.  A sentence line c
 `-secondpass NAME` (with `-endpoint`; OnlineRecognizer.SetSecondPass) re-recognises every finished sentence with the OFFLINE model
 in directory NAME under -base (its files chosen as `-type offline` chooses them): the sentence lines then carry its text.
 `-tokentimes` (online; OnlineRecognizer.SetTokenInfo) prints under each result one line of `token[time_ms score]` for the tokens
-the stream fired (special tokens left out); with `-endpoint` also under each `[begin-end ms]` line, for the closed sentence.  A time is the start of the 60 ms frame in which the token fired, not a word boundary."""
+the stream fired (special tokens left out); with `-endpoint` also under each `[begin-end ms]` line, for the closed sentence.  A time is the start of the 60 ms frame in which the token fired, not a word boundary.
+`-puncstream FILE[,max_context=N]` (online; OnlineRecognizer.SetPuncModel) punctuates the words as they arrive with a causal
+CT-Transformer on the GPU (FILE: a .pfw made by `convert --kind cttransformer --causal`): a `punctuated: ...` line under each
+partial result and under each finished sentence.  `-punc` stays an offline option.  Not validated on a real model."""
 from __future__ import annotations
 
 import ctypes as C
@@ -224,6 +227,25 @@ def parse_vad_option(text: str) -> dict:
 
 ENDPOINT_KEYS = ("rise", "margin_q", "abs_level", "window", "on_count", "off_count", "pad_begin", "pad_end", "end_silence", "min_speech",
                  "max_len")
+
+
+def parse_puncstream_option(text: str) -> dict:
+    """`FILE[,max_context=N]` of -puncstream -> {file, max_context}"""
+    parts = text.split(",")
+    out = {"file": parts[0], "max_context": 0}
+    if not parts[0]:
+        raise ValueError("-puncstream takes a causal .pfw file of kind cttransformer[,max_context=N]")
+    for item in parts[1:]:
+        k, _, v = item.partition("=")
+        if k != "max_context":
+            raise ValueError("Unknown -puncstream key: %s" % k)
+        try:
+            out["max_context"] = int(v)
+        except ValueError:
+            raise ValueError("The -puncstream value of max_context must be an integer")
+        if not 2 <= out["max_context"] <= 256:
+            raise ValueError("-puncstream max_context lies in 2 .. 256")
+    return out
 
 
 def parse_endpoint_option(text: str) -> dict:
@@ -459,7 +481,7 @@ def token_times_line(info, names):
 
 def online_recognizer(method="one", model="speech_paraformer-large_asr_nat-zh-cn-16k-common-vocab8404-online-onnx",
                       accuracy="int8", threads=2, files=None, base=None, out=sys.stdout, endpoint=None, secondpass=None, vadmodel=None,
-                      tokentimes=False):
+                      tokentimes=False, puncstream=None):
     from .online_recognizer import OnlineRecognizer
     base = base or os.getcwd()
     if not model:
@@ -480,6 +502,13 @@ def online_recognizer(method="one", model="speech_paraformer-large_asr_nat-zh-cn
     if tokentimes:
         rec.SetTokenInfo(True)
         names = read_token_table(sel["tokensFilePath"])
+    if puncstream:
+        try:
+            rec.SetPuncModel(puncstream["file"], puncstream.get("max_context", 0))
+        except Exception as ex:
+            print("Error occurred: %s" % ex, file=out)
+            print("Init models failure!", file=out)
+            return None
     if endpoint is not None:
         try:
             if vadmodel:                                    # the model's default thresholds unless keys are given
@@ -537,15 +566,19 @@ def online_recognizer(method="one", model="speech_paraformer-large_asr_nat-zh-cn
                         print("[%d-%d ms] %s" % (sen.begin_ms, sen.end_ms, sen.text), file=out)
                         if tokentimes:                      # TokenInfo was cleared at the reset: the sentence kept its own
                             print(token_times_line(sen.tokens, names), file=out)
+                        if puncstream:
+                            print("punctuated: " + sen.punctuated, file=out)
                     shown = len(sens)
                 print(r.Text, file=out)
                 if tokentimes:
                     print(token_times_line(st.TokenInfo, names), file=out)
+                if puncstream:
+                    print("punctuated: " + st.Punctuated, file=out)
                 texts.append(r.Text)
             for c in chunks:
                 st.AddSamples(c)
                 step()
-            if endpoint is not None:
+            if endpoint is not None or puncstream:
                 st.InputFinished()
                 for _ in range(3):                          # the padded tail, then the flush
                     step()
@@ -661,6 +694,11 @@ def parse_args(argv, env=None):
             if i + 1 < len(argv) and not argv[i + 1].startswith("-") and "=" in argv[i + 1]:
                 i += 1
                 cfg["spk"]["cfg"] = parse_spk_option(argv[i])
+        elif a == "-puncstream":
+            i += 1
+            if i >= len(argv) or argv[i].startswith("-"):
+                raise ValueError("-puncstream takes a causal .pfw file of kind cttransformer[,max_context=N]")
+            cfg["puncstream"] = parse_puncstream_option(argv[i])
         elif a == "-punc":
             i += 1
             if i >= len(argv) or argv[i].startswith("-"):
@@ -715,6 +753,8 @@ def parse_args(argv, env=None):
         raise ValueError("-punc is an offline option")
     if "spk" in cfg and "vad" not in cfg:
         raise ValueError("-spk goes with -vad")
+    if "puncstream" in cfg and cfg.get("recognizerType") != "online":
+        raise ValueError("-puncstream goes with -type online")
     if "tokentimes" in cfg and cfg.get("recognizerType") != "online":
         raise ValueError("-tokentimes goes with -type online")
     if "vadmodel" in cfg and "vad" not in cfg and "endpoint" not in cfg:
@@ -735,7 +775,7 @@ def main(argv=None):
     if cfg["recognizerType"] == "online":
         online_recognizer(cfg["methodType"], cfg["modelName"], cfg["modelAccuracy"], cfg["threads"], cfg["files"],
                           cfg["modelBasePath"] or None, endpoint=cfg.get("endpoint"), secondpass=cfg.get("secondpass"),
-                          vadmodel=cfg.get("vadmodel"), tokentimes=bool(cfg.get("tokentimes")))
+                          vadmodel=cfg.get("vadmodel"), tokentimes=bool(cfg.get("tokentimes")), puncstream=cfg.get("puncstream"))
     elif cfg["recognizerType"] == "offline":
         offline_recognizer(cfg["methodType"], cfg["modelName"], cfg["modelAccuracy"], cfg["threads"], cfg["files"],
                            cfg["modelBasePath"] or None, decode=cfg.get("decode", "frames"), intake=cfg.get("intake", "host"),

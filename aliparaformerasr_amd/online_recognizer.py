@@ -23,8 +23,10 @@ class OnlineSentence:
     Scores, alternatives, punctuation, whatever the offline recognizer has set — or None without a second pass."""
     KINDS = {N.PF_ENDPOINT_SILENCE: "silence", N.PF_ENDPOINT_FORCED: "forced", N.PF_ENDPOINT_FLUSH: "flush"}
 
-    def __init__(self, begin_ms, end_ms, kind, first_pass, text, result, tokens=None):
+    def __init__(self, begin_ms, end_ms, kind, first_pass, text, result, tokens=None, punctuated="", punc_ids=None):
         self.begin_ms, self.end_ms, self.kind, self.first_pass, self.text, self.result = begin_ms, end_ms, kind, first_pass, text, result
+        # OnlineRecognizer.SetPuncModel: first_pass under the marks of its words (the flush's edit applied), and the marks
+        self.punctuated, self.punc_ids = punctuated, [] if punc_ids is None else punc_ids
         self.tokens = [] if tokens is None else tokens   # the stream's TokenInfo as of the closing call (OnlineRecognizer.SetTokenInfo)
 
     def __repr__(self):
@@ -87,9 +89,33 @@ class OnlineStream:
                 res._borrowed = self                     # the handle belongs to this stream: never freed by the view
             tp, tn = C.POINTER(N.PfOnlineToken)(), C.c_int32()
             _ck(self._lib.pf_online_stream_sentence_tokens(self._h, j, C.byref(tp), tn))
+            pt, pi, pn = C.c_char_p(), C.POINTER(C.c_int32)(), C.c_int32()
+            _ck(self._lib.pf_online_stream_sentence_punctuated(self._h, j, C.byref(pt), C.byref(pi), pn))
             out.append(OnlineSentence(b.value, e.value, OnlineSentence.KINDS.get(k.value, k.value), (fp.value or b"").decode("utf-8"),
-                                      (tx.value or b"").decode("utf-8"), res, _tokens(tp, tn.value)))
+                                      (tx.value or b"").decode("utf-8"), res, _tokens(tp, tn.value),
+                                      (pt.value or b"").decode("utf-8"), [pi[i] for i in range(pn.value)]))
         return out
+
+    def _punctuated(self):
+        t, ids, fl, n = C.c_char_p(), C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)(), C.c_int32()
+        _ck(self._lib.pf_online_stream_punctuated(self._h, C.byref(t), C.byref(ids), C.byref(fl), n))
+        return (t.value or b"").decode("utf-8"), [ids[i] for i in range(n.value)], [fl[i] for i in range(n.value)]
+
+    @property
+    def Punctuated(self) -> str:
+        """With OnlineRecognizer.SetPuncModel: the open text of the last GetResults under the marks of its committed words; a
+        word whose last piece ends in "@@" is held back and appended raw.  "" without a model."""
+        return self._punctuated()[0]
+
+    @property
+    def PuncIds(self) -> List[int]:
+        """The mark of every committed word of the open text, as an index into the model's punc_list; never revised."""
+        return self._punctuated()[1]
+
+    @property
+    def PuncFlags(self) -> List[int]:
+        """Per committed word: bit 0 the word ended a sentence (the context restarted behind it), bit 1 a forced restart."""
+        return self._punctuated()[2]
 
     @property
     def InSpeech(self):
@@ -145,6 +171,14 @@ class OnlineRecognizer:
         OnlineSentence.tokens).  Tokens and Text are what they are with the mode off.  Refused once a live stream of this
         recognizer has decoded a chunk."""
         _ck(self._lib.pf_online_recognizer_set_token_info(self._h, 1 if on else 0))
+
+    def SetPuncModel(self, pfwPath, maxContext: int = 0) -> None:
+        """Streaming punctuation (pf_online_recognizer_set_punc_model; off by default): a causal `.pfw` of kind "cttransformer"
+        (convert --kind cttransformer --causal); None detaches and frees.  Every GetResults then marks the newly committed words
+        of all its streams in one launch on the GPU: stream.Punctuated / PuncIds / PuncFlags, sentence.punctuated / punc_ids.
+        Text and Tokens are what they are without it.  maxContext: the words a context holds before a forced restart (2 .. 256;
+        0: 200).  Refused while a live stream holds punctuation state.  Not validated on a real model."""
+        _ck(self._lib.pf_online_recognizer_set_punc_model(self._h, None if pfwPath is None else str(pfwPath).encode("utf-8"), int(maxContext)))
 
     def SetEndpointModel(self, pfwPath) -> None:
         """The FSMN-VAD model score as the endpoint detector's level (pf_online_recognizer_set_endpoint_model): a `.pfw` of kind

@@ -276,10 +276,12 @@ CT_TRANSFORMER_CONFIG = dict(
 def ct_transformer_config(**kw) -> dict:
     """The config of a `.pfw` of kind "cttransformer" (the punctuation model; the definition is tests/punc_ref.py).  The
     defaults are the dimensions of FunASR's released punc_ct-transformer_zh-cn-common-vocab272727 as remembered, not read from
-    a file."""
+    a file.  Two optional keys make the streaming form (tests/punc_stream_ref.py): causal (0 / 1) and sanm_shift, the FSMN
+    taps moved to the left of the word ((kernel - 1) / 2 for a causal model); a config without them writes the container it
+    always wrote."""
     cfg = dict(CT_TRANSFORMER_CONFIG)
     for k, v in kw.items():
-        if k not in cfg:
+        if k not in cfg and k not in ("causal", "sanm_shift"):
             raise KeyError(k)
         cfg[k] = v
     cfg["punc_list"] = [str(s) for s in cfg["punc_list"]]

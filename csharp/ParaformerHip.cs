@@ -289,6 +289,11 @@ namespace AliParaformerAsr.Native
         [DllImport(Lib)] internal static extern int pf_vad_model_config(out PfVadConfig cfg);
         [DllImport(Lib)] internal static extern int pf_endpoint_model_config(out PfEndpointConfig cfg);
         [DllImport(Lib)] internal static extern int pf_vad_model_stream_state_bytes(IntPtr m, out long bytes);
+        [DllImport(Lib)] internal static extern int pf_punc_model_causal(IntPtr m, out int causal);
+        [DllImport(Lib)] internal static extern int pf_punc_stream_state_bytes(IntPtr m, out long bytes);
+        [DllImport(Lib)] internal static extern int pf_online_recognizer_set_punc_model(IntPtr r, [MarshalAs(UnmanagedType.LPUTF8Str)] string? pfwPath, int maxContext);
+        [DllImport(Lib)] internal static extern int pf_online_stream_punctuated(IntPtr s, out IntPtr textUtf8, out IntPtr puncIds, out IntPtr puncFlags, out int nWords);
+        [DllImport(Lib)] internal static extern int pf_online_stream_sentence_punctuated(IntPtr s, int j, out IntPtr textUtf8, out IntPtr puncIds, out int nWords);
         [DllImport(Lib)] internal static extern void pf_vad_model_free(IntPtr m);
         [DllImport(Lib)] internal static extern int pf_engine_set_vad_model(IntPtr e, IntPtr m);
         [DllImport(Lib)] internal static extern int pf_recognizer_set_vad_model(IntPtr r, [MarshalAs(UnmanagedType.LPUTF8Str)] string? pfwPath);

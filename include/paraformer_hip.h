@@ -845,6 +845,53 @@ int pf_engine_set_punc_model(pf_engine* e, const pf_punc_model* m);
    PF_ERR_INVALID_ARG without an attached model or for an id outside the vocabulary. */
 int pf_engine_punctuate(pf_engine* e, const int32_t* ids, const int32_t* lens, int32_t B, int32_t* punc_ids, int32_t* rounds);
 
+/* ---- Punctuation, streaming (additions to ABI 6; opt-in: without these calls nothing of it is launched or allocated) ----
+   The causal form of the same network punctuates words as they arrive and carries the unfinished sentence between calls
+   (FunASR's two-pass runtime does this with its realtime CT-Transformer).  The definition in numpy float64 is
+   tests/punc_stream_ref.py; DESIGN.md 4.6s has the state layout, the launch plan and the rounding points of the device form
+   (csrc/k_punc_stream.hip: ONE launch per call, one workgroup per stream).  THE DEFINITION IS THIS PROJECT'S; the dimensions of
+   FunASR's punc_ct-transformer_zh-cn-common-vad_realtime-vocab272727 are as remembered, its "vad mask" is implied by the
+   causal mask in every layer, and whether its last layer is causal is not known here.  NOTHING IS VALIDATED ON A REAL MODEL.
+   THE MODEL is a container of kind "cttransformer" whose header adds causal = 1 and sanm_shift (both optional, default 0; a
+   container without them loads and behaves bit for bit as before).  The FSMN reach is left = (kernel - 1) / 2 + sanm_shift,
+   right = kernel - 1 - left; causal = 1 requires right == 0 and causal = 0 requires sanm_shift == 0, else PF_ERR_UNSUPPORTED.
+   pf_host_punc_logits honours both.  The offline device entries (pf_engine_punctuate, pf_op_punc_*,
+   pf_recognizer_set_punc_model) refuse a causal model with PF_ERR_UNSUPPORTED, the streaming entries a model that is not.
+   THE NETWORK runs on a context w_0 .. w_{n-1}, the words since the last restart: layer-0 input as above with the word's
+   index in the context + 1 as its position, attention over the keys j <= i, the FSMN sum
+   f_t = v_t + sum_j taps[:, j] v_{t - (kernel - 1) + j} with sources before index 0 skipped, everything else as above.  The
+   logits of w_t depend on w_0 .. w_t alone.
+   THE LOOP, per stream and per new word in order: the word is appended to the context and its mark is the arg-max of its
+   logits, ties to the larger index.  A mark "。" or "？" ends the sentence: the context is emptied behind this word
+   (mark_flags bit 0).  Otherwise a context that now holds max_context words (2 .. PF_PUNC_STREAM_MAX_CONTEXT, usually
+   PF_PUNC_STREAM_DEFAULT_CONTEXT) is emptied and the mark stays (bit 1: forced restart).  Marks are never revised by later
+   words.  THE FLUSH (flush != 0: end of input) edits at most the newest word of the context: *flush_mark is that word's mark,
+   with "_", "，" or "、" replaced by sentence_end_id, or -1 for an empty context or without a flush; the context is emptied.
+   flags bit 0 (PF_PUNC_STREAM_NO_RESTARTS): the pure network, no rule; a context then holds at most 256 words
+   (PF_ERR_INVALID_ARG beyond).
+   A stream's state is opaque, pf_punc_stream_state_bytes bytes (f16 keys and values [n_layers, 256, 2, 256] and the count:
+   about 1 MB at four layers); all zero is a fresh stream.  The host twin has a state form of its own (float64;
+   pf_host_punc_stream_state_bytes).  A word's logits and mark are bit-identical however the stream was cut into calls.
+   PF_ERR_INVALID_ARG: max_context or flags out of range, a negative n_new, an id outside the vocabulary, a state whose count
+   lies outside its context. */
+#define PF_PUNC_STREAM_MAX_CONTEXT 256
+#define PF_PUNC_STREAM_DEFAULT_CONTEXT 200
+#define PF_PUNC_STREAM_NO_RESTARTS 1
+int pf_punc_model_causal(const pf_punc_model* m, int32_t* causal);
+int pf_punc_stream_state_bytes(const pf_punc_model* m, int64_t* bytes);
+int pf_host_punc_stream_state_bytes(const pf_punc_model* m, int64_t* bytes);
+/* COMMITTED WORDS of a streaming recogniser's partial text: the words (as pf_host_punc_words splits them) of the text
+   pf_host_online_decode gives for ids; while the last token that contributes text ends in "@@" the last word is held back
+   (the next piece changes it).  out [cap]: all the words joined by newlines (no terminator; *out_len the length needed),
+   *n_committed of *n_words are committed.  before_utf8 (optional): the committed words of the last call, one per line; they must
+   be a prefix of this call's, PF_ERR_RECOGNITION otherwise. */
+int pf_host_online_committed_words(const pf_punc_model* m, const char* const* tokens, int32_t n_tokens, const int64_t* ids, int32_t n_ids,
+                                   const char* before_utf8, char* out, int64_t cap, int64_t* out_len, int32_t* n_committed, int32_t* n_words);
+/* one call of ONE stream in host code, float64: ids [n_new] in order, then the flush.  marks / mark_flags [n_new], logits
+   [n_new, n_punc] (optional), *flush_mark (optional) */
+int pf_host_punc_stream_step(const pf_punc_model* m, void* state, const int32_t* ids, int32_t n_new, int32_t flush, int32_t max_context,
+                             int32_t flags, int32_t* marks, int32_t* mark_flags, double* logits, int32_t* flush_mark);
+
 /* ---- Speaker labels (additions to ABI 6; opt-in: with no model attached nothing of this is launched or allocated and every
    result is bit for bit what it is without it) ----
    Who speaks in each segment of a long recording: a CAM++ network (the speaker model FunASR's AutoModel takes as
@@ -1035,6 +1082,17 @@ int pf_op_vad_model_stream(pf_engine* e, void* states, const float* rows, const 
 int pf_op_punc_logits(pf_engine* e, const int32_t* ids, const int32_t* T, int32_t B, float* logits, float* x0);
 int pf_op_punc_window(pf_engine* e, const int32_t* ids, const int32_t* T, const int32_t* last, int32_t B, int32_t* p, int32_t* cut,
                       float* logits);
+/* exactly the attached punctuation model's streaming launch (k_punc_stream.hip, "Punctuation, streaming") on caller state
+   blocks and ids, B streams (B <= PF_PUNC_MAX_BATCH) in ONE launch (profile class "punc_stream"): states
+   [B, pf_punc_stream_state_bytes] in / out, ids [B, ld] of which stream b's first n_new[b] are read, flush [B] (NULL: none);
+   marks / mark_flags [B, ld] int32 and logits [B, ld, n_punc] fp32 (logits may be NULL) of which stream b's first n_new[b] are
+   written; flush_mark [B].  A stream's result does not depend on its launch mates.  Errors as stated there; on an argument
+   error nothing is launched and nothing changed.  A test and tool entry, not the production path: it stages every stream's whole
+   state block up and down (about 1 MB each at four layers) and waits twice; pf_online_recognizer_set_punc_model keeps the
+   states on the device. */
+int pf_op_punc_stream_step(pf_engine* e, void* states, const int32_t* ids, const int32_t* n_new, const int32_t* flush, int32_t B,
+                           int32_t ld, int32_t max_context, int32_t flags, int32_t* marks, int32_t* mark_flags, float* logits,
+                           int32_t* flush_mark);
 /* exactly the attached speaker model's launches (k_spk.hip; PF_ERR_INVALID_ARG without pf_engine_set_spk_model) on caller
    windows: rows = the concatenated fbank rows of B windows, T [B] rows each (0 .. PF_SPK_MAX_FRAMES, else PF_ERR_INVALID_ARG),
    n_mels wide.  emb [B, embedding] fp32; frames (optional) [sum ceil(T / 2), the frames' width] fp32: the activations in front
@@ -1602,7 +1660,7 @@ int pf_recognizer_set_vad_model(pf_recognizer* r, const char* pfw_path);
    and attached to every engine of the pool; NULL clears.  GetResults then punctuates each stream's final text (with
    pf_recognizer_set_vad: the stitched text), all streams of the call in one pf_engine_punctuate, and keeps the result on the
    stream; Text, Tokens and Timestamps of the result are what they are without it.  Alternatives are not punctuated; pf_group_*
-   and the streaming classes have no such switch.  Errors as pf_punc_model_load.
+   has no such switch; the streaming classes have pf_online_recognizer_set_punc_model (a causal model).  Errors as pf_punc_model_load.
    pf_stream_punctuated: the punctuated text, the mark of every word (punc_list index) and the word count of the stream's last
    GetResults ("" / 0 without a model); each output optional; valid until the stream's next GetResults.
    pf_stream_sentence: sentence i: its words [word_begin, word_end), its punctuated text and, when the result has exactly one
@@ -1800,6 +1858,26 @@ typedef struct { int64_t id; int32_t time_ms; int32_t entry; float score; int32_
 int pf_online_recognizer_set_token_info(pf_online_recognizer* r, int32_t on);
 int pf_online_stream_token_info(pf_online_stream* s, const pf_online_token** toks, int32_t* n);   /* n == number of Tokens, index for index */
 int pf_online_stream_sentence_tokens(pf_online_stream* s, int32_t j, const pf_online_token** toks, int32_t* n);
+/* ---- Streaming punctuation on the recogniser (additions to ABI 6; see "Punctuation, streaming"; opt-in: without
+   pf_online_recognizer_set_punc_model nothing of it is launched, allocated or changed) ----
+   pf_online_recognizer_set_punc_model: pfw_path = a causal `.pfw` of kind "cttransformer", loaded once and attached to the
+   recogniser's engine; NULL or "" detaches and frees.  max_context 2 .. PF_PUNC_STREAM_MAX_CONTEXT, 0 = the default.  Every
+   pf_online_get_results then, behind the chunk step and the endpoint pass, gathers the newly COMMITTED words of its streams
+   (pf_host_online_committed_words) and marks them in ONE launch (profile class "punc_stream"); a stream's keys and values stay
+   in its slot of a device buffer; a call with no new word and no flush launches nothing.  Text, Tokens, TokenInfo and the
+   sentences' text are what they are without it.  When the endpoint detector closes a sentence its remaining words, a held-back
+   one included, go in with the flush before the decoder context is reset, and the next sentence starts a fresh context; the
+   pf_online_get_results that has decoded the last chunk after pf_online_stream_input_finished flushes likewise.  The flush's
+   edit is applied to the newest word's mark.  PF_ERR_UNSUPPORTED: a model that is not causal; a live stream holds punctuation
+   state.  PF_ERR_RECOGNITION: the committed words of a call do not begin with the last call's.
+   pf_online_stream_punctuated: of the last pf_online_get_results, the open text under the marks of its committed words (a
+   held-back word appended raw), the mark and the flags (bit 0 sentence end, bit 1 forced restart) of every committed word.
+   pf_online_stream_sentence_punctuated: the same for finished sentence j.  Each output optional; valid until the stream's next
+   pf_online_get_results or its free; "" / 0 without a model. */
+int pf_online_recognizer_set_punc_model(pf_online_recognizer* r, const char* pfw_path, int32_t max_context);
+int pf_online_stream_punctuated(pf_online_stream* s, const char** text_utf8, const int32_t** punc_ids, const int32_t** punc_flags,
+                                int32_t* n_words);
+int pf_online_stream_sentence_punctuated(pf_online_stream* s, int32_t j, const char** text_utf8, const int32_t** punc_ids, int32_t* n_words);
 /* Device seams = the two InferenceSession.Run calls (OnlineRecognizer.cs:83, :296).
    encoder: speech [B,Tc,560] (scaled + position-encoded by the caller) -> enc [B,Tc,512], alphas [B,Tc].
    decoder: enc, acoustic_embeds [B,L,512] + lengths, in_cache [n_caches][B,512,10] -> log-probs [B,L,V] (optional),
