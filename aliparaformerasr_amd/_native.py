@@ -469,6 +469,7 @@ SIGNATURES = {
     "pf_online_stream_in_speech": (C.c_int, [_vp, _i32, _i32]),
     "pf_online_stream_tokens": (C.c_int, [_vp, _P(_i64), _i32]),
     "pf_online_recognizer_set_token_info": (C.c_int, [_vp, C.c_int32]),
+    "pf_online_recognizer_set_device_frontend": (C.c_int, [_vp, C.c_int32]),
     "pf_online_stream_token_info": (C.c_int, [_vp, _P(_P(PfOnlineToken)), _i32]),
     "pf_online_stream_sentence_tokens": (C.c_int, [_vp, C.c_int32, _P(_P(PfOnlineToken)), _i32]),
     "pf_online_stream_dispose": (None, [_vp]),
@@ -479,6 +480,9 @@ SIGNATURES = {
     "pf_host_online_posenc": (C.c_int, [_f, C.c_int32, C.c_int32, C.c_int32]),
     "pf_host_online_dynamic_mask": (C.c_int, [_f, C.c_int32]),
     "pf_host_online_cif": (C.c_int, [_f, _f, C.c_int32, C.c_int32, C.c_float, _f, C.c_int32, _i32, _f, _f]),
+    "pf_host_online_frontend_state_bytes": (C.c_int, [C.c_int32, C.c_int32, _i64]),
+    "pf_host_online_frontend_step": (C.c_int, [_vp, _f, _f, _f, C.c_int32, _f]),
+    "pf_op_online_frontend_step": (C.c_int, [_vp, _vp, C.c_int32, _i32, _f, _i32, C.c_int32, _f]),
     "pf_host_online_cif_state_bytes": (C.c_int, [C.c_int32, _i64]),
     "pf_host_online_cif_step": (C.c_int, [_vp, _f, _f, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_int32, _f, _i32, C.c_int32,
                                           _i32]),

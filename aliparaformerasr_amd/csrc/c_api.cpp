@@ -2904,6 +2904,12 @@ int pf_online_recognizer_set_token_info(pf_online_recognizer* h, int32_t on) {
   return PF_OK;
   PF_CATCH
 }
+int pf_online_recognizer_set_device_frontend(pf_online_recognizer* h, int32_t on) {
+  PF_TRY
+  OR(h)->SetDeviceFrontend(on != 0);
+  return PF_OK;
+  PF_CATCH
+}
 int pf_online_stream_token_info(pf_online_stream* h, const pf_online_token** toks, int32_t* n) {
   PF_TRY
   OnlineStreamM* s = OS(h);
@@ -3005,6 +3011,29 @@ int pf_op_online_cif_step(pf_engine* h, void* states, const float* enc, const fl
   std::shared_ptr<Engine> eh_ = E(h);
   std::lock_guard<std::mutex> lk(eh_->mutex());
   eh_->op_online_cif_step(states, enc, alphas, reset, B, Tc, D, threshold, lo, hi, fired, fire_entry, cap, counts);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_host_online_frontend_state_bytes(int32_t n_mels, int32_t feat_dim, int64_t* bytes) {
+  PF_TRY
+  NEED(bytes);
+  PF_CHECK(n_mels > 0 && feat_dim > 0, PF_ERR_INVALID_ARG, "online_frontend_state_bytes: n_mels, feat_dim > 0 expected");
+  *bytes = (int64_t)online_frontend_state_bytes(n_mels, feat_dim);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_host_online_frontend_step(void* state, const float* fb_rows, const float* shift, const float* scale, int32_t reset, float* speech) {
+  PF_TRY
+  online_frontend_step(state, fb_rows, shift, scale, reset != 0, speech);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_op_online_frontend_step(pf_engine* h, void* states, int32_t n_states, const int32_t* slot, const float* samples, const int32_t* reset,
+                               int32_t B, float* speech) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  std::lock_guard<std::mutex> lk(eh_->mutex());
+  eh_->op_online_frontend_step(states, n_states, slot, samples, reset, B, speech);
   return PF_OK;
   PF_CATCH
 }

@@ -100,6 +100,20 @@ struct CifStreamBlock : Block {
   CifStreamBlock(Cursor& c, size_t D) : Block(c), groups((D + kCifStreamGroup - 1) / kCifStreamGroup) { lay(c, hidden, D, integrate, (groups + 3) / 4 * 4); }
 };
 
+// one stream's streaming front-end (k_frontend_stream.hip, online_frontend_step in online.cpp): carry [2, n_mels] fp32, fbank rows
+// 58 and 59 of the stream's previous chunk | cache [10, feat_dim] fp32, the ten feature rows of the previous step after the
+// position term | start_idx [kFrontendStreamFrames] int32, ONE COPY per LFR frame of a chunk (workgroup i of the kernel owns LFR
+// frame i and copy i: no workgroup reads a cell another writes; all copies hold the same value), padded to a multiple of four |
+// flags [4] int32, cell 0 bit 0 = `first`: the stream has stepped once, the carry holds rows (cells 1 .. 3 are padding).  The
+// padding cells are never written.  A zero-filled block is a new stream.
+constexpr size_t kFrontendStreamFrames = 10;
+struct FrontendStreamBlock : Block {
+  Field<float> carry, cache; Field<int32_t> start_idx, flags;
+  FrontendStreamBlock(Cursor& c, size_t n_mels, size_t feat_dim) : Block(c) {
+    lay(c, carry, 2 * n_mels, cache, kFrontendStreamFrames * feat_dim, start_idx, (kFrontendStreamFrames + 3) / 4 * 4, flags, 4);
+  }
+};
+
 // a block on its own, from offset 0: the layout of a host vector
 template <class Blk, class... Dims> Blk block_at_zero(Dims... dims) {
   Cursor c;

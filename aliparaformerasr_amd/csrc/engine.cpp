@@ -125,7 +125,7 @@ void Engine::release() {
   owned_.clear();
   DevBuf* bufs[] = {&ws_f32_, &ws_pcm_, &ws_audio_, &ws_meta_, &ws_fbank_, &ws_speech_, &ws_enc_, &ws_dec_, &ws_kv_, &ws_pe_, &ws_tmp_,
                     &ws_ts_, &ws_seaco_, &ws_seaco_in_, &ws_seaco_hw_, &ws_q_, &ws_qf_, &ws_seaco_q_, &ws_x3a_, &ws_x3t_, &ws_x3h_, &lm_inst_.buf, &lm_op_.buf, &nbs_hot_.buf, &ws_nbs_,
-                    &ws_step_, &vadnet_dev_.buf, &ws_vadnet_, &punc_dev_.buf, &ws_punc_, &spk_dev_.buf, &ws_spk_};
+                    &ws_step_, &ws_fe_, &fe_inv_, &fe_meta_, &vadnet_dev_.buf, &ws_vadnet_, &punc_dev_.buf, &ws_punc_, &spk_dev_.buf, &ws_spk_};
   lm_inst_.src.reset(); lm_op_.src.reset(); lm_.reset(); nbs_lm_.reset();
   vadnet_dev_.src.reset(); vadnet_.reset();
   punc_dev_.src.reset(); punc_.reset();
@@ -1680,16 +1680,26 @@ void Engine::online_step(const float* speech, int B, int Tc, char* slots_dev, co
   PF_CHECK(mc_.kind != "sensevoicesmall", PF_ERR_UNSUPPORTED, "online_step: paraformer models only");
   PF_CHECK(mc_.kernel == 11, PF_ERR_UNSUPPORTED, "online_step: FSMN kernel 11 (cache of 10 columns) only");
   PF_HIP(hipSetDevice(device_));
+  const size_t n = (size_t)B * Tc * mc_.feat_dim;
+  ensure(ws_speech_, n * 4);
+  PF_HIP(hipMemcpyAsync(ws_speech_.p, speech, n * 4, hipMemcpyHostToDevice, stream_));
+  online_step_device(nullptr, B, Tc, slots_dev, slot, cif_reset, cache_reset, lo, hi, out);
+}
+
+void Engine::online_step_device(const float* speech_dev, int B, int Tc, char* slots_dev, const int32_t* slot, const int32_t* cif_reset,
+                                const int32_t* cache_reset, int lo, int hi, OnlineStepOut& out) {
+  PF_CHECK(slots_dev && slot && cif_reset && cache_reset && B > 0 && Tc > 0, PF_ERR_INVALID_ARG, "online_step: bad arguments");
+  PF_CHECK(speech_dev || ws_speech_.bytes >= (size_t)B * Tc * mc_.feat_dim * 4, PF_ERR_INVALID_ARG, "online_step: no chunk on the device");
+  PF_CHECK(mc_.kind != "sensevoicesmall", PF_ERR_UNSUPPORTED, "online_step: paraformer models only");
+  PF_CHECK(mc_.kernel == 11, PF_ERR_UNSUPPORTED, "online_step: FSMN kernel 11 (cache of 10 columns) only");
+  PF_HIP(hipSetDevice(device_));
   const int D = mc_.d_model, F = mc_.ffn, V = mc_.vocab, nd = (int)dec_.layers.size(), CW = mc_.kernel - 1;
   const int M = B * Tc, cap = Tc + 1;
   const size_t nB = (size_t)B;
   out.max_tok = 0; out.cap = cap;
   out.counts.assign(nB, 0); out.fire_entry.assign(nB * cap, -1); out.ids.clear(); out.scores.clear();
-  // 1 - 3: the chunk up, the encoder, the alphas (online_encoder without its downloads)
-  const size_t n = (size_t)M * mc_.feat_dim;
-  ensure(ws_speech_, n * 4);
-  PF_HIP(hipMemcpyAsync(ws_speech_.p, speech, n * 4, hipMemcpyHostToDevice, stream_));
-  encoder((const float*)ws_speech_.p, B, Tc, true);
+  // 1 - 3: the chunk (up already), the encoder, the alphas (online_encoder without its downloads)
+  encoder(speech_dev ? speech_dev : (const float*)ws_speech_.p, B, Tc, true);
   cif_alpha_stage(H16_, B, Tc, h16_, fsm_, alphas_, nullptr);
   // 4: the carried CIF on the streams' blocks; slot | cif_reset | cache_reset in one upload, counts | fire entries in one export
   StageCarve st;
@@ -1780,6 +1790,74 @@ void Engine::online_step(const float* speech, int B, int Tc, char* slots_dev, co
   PF_HIP(hipMemcpyAsync(out.ids.data(), ids, (size_t)Md * 8, hipMemcpyDeviceToHost, stream_));
   PF_HIP(hipMemcpyAsync(out.scores.data(), best, (size_t)Md * 4, hipMemcpyDeviceToHost, stream_));
   PF_HIP(hipStreamSynchronize(stream_));
+}
+
+// ---- the streaming front-end on the device (engine.h) ----
+size_t Engine::online_frontend_slot_bytes() const {
+  return (size_t)round_up((int64_t)block_at_zero<FrontendStreamBlock>(fc_.n_mels, mc_.feat_dim).bytes(), kAlign);
+}
+
+void Engine::online_frontend_check() {
+  PF_CHECK(mc_.kind != "sensevoicesmall", PF_ERR_UNSUPPORTED, "online_frontend: paraformer models only");
+  PF_CHECK(fc_.n_mels == 80 && fc_.lfr_m == 7 && fc_.lfr_n == 6 && mc_.feat_dim == 560, PF_ERR_UNSUPPORTED,
+           "online_frontend: 80 mel bins, LFR 7 / 6 and 560 feature columns only");
+  PF_CHECK(!fc_.snip_edges, PF_ERR_UNSUPPORTED, "online_frontend: snip_edges = true is not supported");
+  PF_CHECK(!cmvn_shift_ || cmvn_dim_ == 560, PF_ERR_UNSUPPORTED, "online_frontend: a CMVN of 560 columns, or none");
+}
+
+// the two launches of a step on samples that are on the device: launch_fbank over the B chunks as B utterances of 9600 samples
+// (what fbank_host computes for each of them alone), then the front-end kernel on those rows
+void Engine::online_frontend_launch(const float* samples_dev, int B, char* states_dev, int64_t stride, const int32_t* slot_dev,
+                                    const int32_t* reset_dev, float* speech_dev) {
+  const size_t nB = (size_t)B;
+  if (!fe_inv_ready_) {                                          // the host's own timescales: exp is never recomputed on the device
+    const std::vector<float> inv = online_position_inv(mc_.feat_dim / 2);
+    ensure(fe_inv_, inv.size() * 4);
+    PF_HIP(hipMemcpyAsync(fe_inv_.p, inv.data(), inv.size() * 4, hipMemcpyHostToDevice, stream_));
+    PF_HIP(hipStreamSynchronize(stream_));
+    fe_inv_ready_ = true;
+  }
+  if (fe_meta_B_ < B) {                                          // audio_off | n_samples | frame_off of B chunks: a prefix serves fewer
+    const size_t cap = std::max<size_t>(64, 2 * nB);
+    std::vector<int64_t> meta(3 * cap);
+    for (size_t b = 0; b < cap; ++b) { meta[b] = (int64_t)b * 9600; meta[cap + b] = 9600; meta[2 * cap + b] = (int64_t)b * 60; }
+    PF_HIP(hipStreamSynchronize(stream_));                       // (an earlier step may still read the old table)
+    ensure(fe_meta_, meta.size() * 8);
+    PF_HIP(hipMemcpyAsync(fe_meta_.p, meta.data(), meta.size() * 8, hipMemcpyHostToDevice, stream_));
+    PF_HIP(hipStreamSynchronize(stream_));
+    fe_meta_B_ = (int)cap;
+  }
+  const int64_t* meta = (const int64_t*)fe_meta_.p;
+  ensure(ws_fbank_, nB * 60 * fc_.n_mels * 4);
+  prof_begin("fbank", 0);
+  launch_fbank(stream_, fb_, samples_dev, meta, meta + fe_meta_B_, meta + 2 * (size_t)fe_meta_B_, B, (int64_t)B * 60, 0, (float*)ws_fbank_.p,
+               fc_.dither, next_dither_seed());
+  prof_end("fbank");
+  OnlineFrontendLaunch a{};
+  a.fbank = (const float*)ws_fbank_.p; a.states = states_dev; a.state_stride = stride; a.slot = slot_dev; a.reset = reset_dev; a.B = B;
+  a.shift = cmvn_shift_; a.scale = cmvn_shift_ ? cmvn_scale_ : nullptr; a.inv = (const float*)fe_inv_.p; a.root = std::pow(512.0, 0.5);
+  a.speech = speech_dev;
+  prof_begin("online_frontend", 0);
+  launch_online_frontend(stream_, a);
+  prof_end("online_frontend");
+}
+
+void Engine::online_frontend(const float* samples, int B, char* states_dev, const int32_t* slot, const int32_t* reset) {
+  PF_CHECK(samples && states_dev && slot && reset && B > 0, PF_ERR_INVALID_ARG, "online_frontend: bad arguments");
+  online_frontend_check();
+  PF_HIP(hipSetDevice(device_));
+  const size_t nB = (size_t)B, chunk = 9600, head = (2 * nB + 3) / 4 * 4;     // slot | reset, the samples 16-byte aligned behind them
+  std::vector<float>& up = fe_up_;                               // (a member: the copy may still read it when this call returns)
+  up.resize(head + nB * chunk);
+  std::memcpy(up.data(), slot, nB * 4);
+  std::memcpy(up.data() + nB, reset, nB * 4);
+  std::memcpy(up.data() + head, samples, nB * chunk * 4);
+  ensure(ws_fe_, up.size() * 4);
+  ensure(ws_speech_, nB * 20 * mc_.feat_dim * 4);
+  PF_HIP(hipMemcpyAsync(ws_fe_.p, up.data(), up.size() * 4, hipMemcpyHostToDevice, stream_));
+  const int32_t* meta = (const int32_t*)ws_fe_.p;
+  online_frontend_launch((const float*)ws_fe_.p + head, B, states_dev, (int64_t)online_frontend_slot_bytes(), meta, meta + nB,
+                         (float*)ws_speech_.p);
 }
 
 void Engine::set_hotwords(const int32_t* hw, int n) {

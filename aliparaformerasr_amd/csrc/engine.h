@@ -141,6 +141,9 @@ struct DevBuf {       // grow-only device allocation
   size_t bytes = 0;
 };
 
+// the `half` float timescales of the streaming position term (online.cpp, beside online_position_encode which walks them)
+std::vector<float> online_position_inv(int half);
+
 class Engine {
  public:
   explicit Engine(const pf_engine_config& cfg);
@@ -368,6 +371,21 @@ class Engine {
   // exactly cif_stream_kernel's launch on caller data through op_stage.h: states [B, online_cif_state_bytes(D)] in / out
   void op_online_cif_step(void* states, const float* enc, const float* alphas, const int32_t* reset, int B, int Tc, int D, float threshold,
                           int lo, int hi, float* fired, int32_t* fire_entry, int cap, int32_t* counts);
+  // the same step on a chunk that is already on the device: speech_dev [B, Tc, feat_dim], or null for "ws_speech_ is filled"
+  // (online_frontend); no upload.  online_step is the upload and this.
+  void online_step_device(const float* speech_dev, int B, int Tc, char* slots_dev, const int32_t* slot, const int32_t* cif_reset,
+                          const int32_t* cache_reset, int lo, int hi, OnlineStepOut& out);
+  // ---- the streaming front-end on the device (OnlineRecognizerM with SetDeviceFrontend) ----
+  // A stream's block (decode_blocks.h FrontendStreamBlock for n_mels x feat_dim) sits in its slot of a buffer of the
+  // recognizer's, online_frontend_slot_bytes() apart.  online_frontend: the 9600-sample chunks of B streams, samples [B, 9600] on
+  // the host, and slot | reset go up in ONE staged copy; launch_fbank over the B chunks (B utterances of 9600 samples)
+  // and one launch_online_frontend fill ws_speech_ [B, 20, feat_dim] for online_step_device(nullptr, ...) and update the blocks.  PF_ERR_UNSUPPORTED unless 80 mels, LFR 7 / 6, feat_dim 560,
+  // snip_edges false and a CMVN of 560 columns or none.
+  size_t online_frontend_slot_bytes() const;
+  void online_frontend(const float* samples, int B, char* states_dev, const int32_t* slot, const int32_t* reset);
+  // exactly that launch on caller data through op_stage.h: states [n_states, online_frontend_state_bytes(80, 560)] in / out, the
+  // streams' blocks chosen by slot [B] (distinct, inside n_states); speech [B, 20, 560] out
+  void op_online_frontend_step(void* states, int n_states, const int32_t* slot, const float* samples, const int32_t* reset, int B, float* speech);
 
   // ---- stand-alone ops (parity tests) -------------------------------------
   void op_lfr_cmvn_pad(const float* const* fbank, const int32_t* t80, int B, int sentinel, float* out,
@@ -581,6 +599,13 @@ class Engine {
   int32_t* step_host_ = nullptr; int32_t* step_host_dev_ = nullptr; int step_host_cap_ = 0; bool step_host_tried_ = false;   // online_step: counts | fire entries, pinned
   hipEvent_t ev_step_ = nullptr;
   DevBuf ws_step_;                    // online_step: speech-independent scratch that must survive the decoder arena's growth
+  DevBuf ws_fe_, fe_inv_, fe_meta_;   // online_frontend: the staged (slot | reset | samples) upload; the position term's 280 timescales; launch_fbank's table
+  bool fe_inv_ready_ = false;
+  int fe_meta_B_ = 0;
+  std::vector<float> fe_up_;
+  void online_frontend_check();
+  void online_frontend_launch(const float* samples_dev, int B, char* states_dev, int64_t stride, const int32_t* slot_dev, const int32_t* reset_dev,
+                              float* speech_dev);
   int32_t* plan_host_ = nullptr; int32_t* plan_host_dev_ = nullptr; int plan_host_cap_ = 0;   // CIF counts exported into pinned host memory
   void ensure_plan_host(int B);
   void export_plan(int B);

@@ -338,6 +338,44 @@ void Engine::op_online_cif_step(void* states, const float* enc, const float* alp
   std::memcpy(counts, hc.data(), hc.size() * 4);
 }
 
+// ---- the streaming front-end (k_frontend_stream.hip).  A hostile chunk stands behind the samples, speech is sentinel-filled and
+// must have been written everywhere, the cells behind the state blocks must keep their bits; the blocks of streams that do not
+// take part travel up and down unchanged.
+void Engine::op_online_frontend_step(void* states, int n_states, const int32_t* slot, const float* samples, const int32_t* reset, int B,
+                                     float* speech) {
+  PF_CHECK(states && slot && samples && reset && speech, PF_ERR_INVALID_ARG, "online_frontend_step: null pointer");
+  PF_CHECK(B > 0 && n_states >= B, PF_ERR_INVALID_ARG, "online_frontend_step: B > 0 and n_states >= B expected");
+  for (int b = 0; b < B; ++b) {
+    PF_CHECK(slot[b] >= 0 && slot[b] < n_states, PF_ERR_INVALID_ARG, "online_frontend_step: a slot outside the state blocks");
+    for (int c = 0; c < b; ++c) PF_CHECK(slot[c] != slot[b], PF_ERR_INVALID_ARG, "online_frontend_step: a slot twice");
+  }
+  online_frontend_check();
+  PF_HIP(hipSetDevice(device_));
+  const size_t nB = (size_t)B, nS = (size_t)n_states, sb = block_at_zero<FrontendStreamBlock>(80, 560).bytes(), chunk = 9600, tail = 64;
+  const int rows = B * 20, W = 560;
+  StageCarve st;
+  const auto d_state = st.take<uint32_t>(nS * sb / 4 + tail);
+  const auto d_samples = st.take<float>((nB + 1) * chunk), d_speech = st.take<float>((size_t)rows * W + tail);
+  const auto d_slot = st.take<int32_t>(nB), d_reset = st.take<int32_t>(nB);
+  void* ws = op_ws(st);
+  std::vector<float> x(d_samples.count);
+  for (size_t i = 0; i < x.size(); ++i) x[i] = hostile32(i);
+  std::memcpy(x.data(), samples, nB * chunk * 4);
+  fill_sentinel(stream_, d_state(ws), d_state.count);
+  upload(stream_, d_state(ws), (const uint32_t*)states, nS * sb / 4);
+  upload(stream_, d_samples(ws), (const float*)x.data(), x.size());
+  upload(stream_, d_slot(ws), slot, nB);
+  upload(stream_, d_reset(ws), reset, nB);
+  fill_sentinel(stream_, d_speech(ws), d_speech.count);
+  online_frontend_launch(d_samples(ws), B, (char*)d_state(ws), (int64_t)sb, d_slot(ws), d_reset(ws), d_speech(ws));
+  const std::vector<uint32_t> hs = check_guard<uint32_t>(stream_, "online_frontend_step: speech", d_speech(ws), kSentinel32, result_geom(rows, rows, W, W, rows));
+  check_guard<uint32_t>(stream_, "online_frontend_step: behind speech", d_speech(ws) + (size_t)rows * W, kSentinel32, untouched_geom((int64_t)tail));
+  check_guard<uint32_t>(stream_, "online_frontend_step: behind the state blocks", d_state(ws) + nS * sb / 4, kSentinel32, untouched_geom((int64_t)tail));
+  download(stream_, (uint32_t*)states, (const uint32_t*)d_state(ws), nS * sb / 4);
+  PF_HIP(hipStreamSynchronize(stream_));
+  std::memcpy(speech, hs.data(), hs.size() * 4);
+}
+
 void Engine::vad_segment(const float* const* samples, const int64_t* n, int B, const pf_vad_config* cfg, int32_t* seg, int cap,
                          int32_t* n_seg) {
   vad_check(cfg, fc_.lfr_n);

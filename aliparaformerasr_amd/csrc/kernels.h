@@ -568,6 +568,24 @@ void launch_cif_pack(hipStream_t s, const float* fired, int B, int cap, int L, i
 // `n` int32 words into pinned host memory through its device alias (as export_plan_kernel): the counts and fire entries of a step
 void launch_export_words(hipStream_t s, const int32_t* src, int n, int32_t* dst_dev);
 
+// ---------------------------------------------------------------- the streaming front-end (k_frontend_stream.hip) ------
+// One chunk of B streams from its fbank rows to the encoder's input in ONE launch: the splice with the two carried rows, LFR 7 / 6
+// without left context, CMVN, the sqrt(512) scale, the position term, the ten-row feature cache and the streaming sentinel.  The
+// host statement is online_frontend_step (online.cpp).  Stream b = its block at states + slot[b] * state_stride (slot null: block
+// b; the slots of a launch are distinct; decode_blocks.h FrontendStreamBlock for 80 mels and 560 columns; read, then written).
+// reset[b] != 0 (reset may be null): the cache is zeros and start_idx 0 before the step; the carried rows are kept.
+//   read     fbank [B, 60, 80] (launch_fbank's rows of each stream's 9600 samples as an utterance of its own); shift, scale [560]
+//            (both null: no CMVN); inv [280] (online_position_inv); the blocks
+//   written  speech [B, 20, 560], all of it (every exact 0 as -23.025850929940457f), the blocks' carry, cache, start_idx copies
+//            and flags cell 0 — nothing else
+// root: the host's own pow(512.0, 0.5).
+struct OnlineFrontendLaunch {
+  const float* fbank; char* states; int64_t state_stride; const int32_t* slot; const int32_t* reset; int B;
+  const float* shift; const float* scale; const float* inv; double root;
+  float* speech;
+};
+void launch_online_frontend(hipStream_t s, const OnlineFrontendLaunch& a);
+
 // ---------------------------------------------------------------- the FSMN-VAD model score (k_vadnet.hip) ------
 // The second form of step 1 of the voice-activity segmentation; the definition in numpy is tests/vadnet_ref.py.  One launch
 // of the 1 + n_layers that make a forward (the plan is at the head of k_vadnet.hip; Engine::run_vadnet fills these in).

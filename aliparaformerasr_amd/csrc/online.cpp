@@ -26,15 +26,30 @@ std::vector<float> online_apply_lfr(const std::vector<float>& in, int n_mels, in
   return out;
 }
 
-void online_position_encode(std::vector<float>& x, int timesteps, int dim, int start_idx) {
-  // OnlineWavFrontend.cs:152-188, float / double mix as written there
-  const int half = dim / 2;
+std::vector<float> online_position_inv(int half) {
+  // OnlineWavFrontend.cs:152-170: the timescales, float / double mix as written there
   const float inc = (float)std::log((double)10000.0f) / (float)(half - 1);
   std::vector<float> inv((size_t)half);
   for (int i = 0; i < half; ++i) {
     const float v = (float)(i + 1) * (-inc);
     inv[(size_t)i] = (float)std::exp((double)v);
   }
+  return inv;
+}
+
+void online_cmvn_scale(std::vector<float>& x, const float* shift, const float* scale, size_t dim) {
+  if (shift && dim > 0) {                                                 // ApplyCmvn, OnlineWavFrontend.cs:46-62
+    for (size_t i = 0; i + dim <= x.size(); i += dim)
+      for (size_t k = 0; k < dim; ++k) { const volatile float s = x[i + k] + shift[k]; x[i + k] = s * scale[k]; }
+  }
+  const double root = std::pow(512.0, 0.5);
+  for (float& v : x) v = (float)((double)v * root);                       // OnlineStream.cs:193
+}
+
+void online_position_encode(std::vector<float>& x, int timesteps, int dim, int start_idx) {
+  // OnlineWavFrontend.cs:152-188, float / double mix as written there
+  const int half = dim / 2;
+  const std::vector<float> inv = online_position_inv(half);
   for (int t = 0; t < timesteps; ++t) {
     const float p = (float)(start_idx + t + 1);
     float* row = &x[(size_t)t * dim];
@@ -118,6 +133,42 @@ int online_cif_step(void* state, const float* hiddens, const float* alphas, int 
   return count;
 }
 
+// ---- one chunk step of one stream's front-end behind the fbank (decode_blocks.h FrontendStreamBlock): what
+// online_frontend_kernel computes from its tile on.  pad is GetDecodeChunk's in closed form: Speech holds [fb[0] ; fb[0 .. 59]]
+// after a stream's first InputSpeech and one row more than it decodes ever after, so a chunk's 61 rows are the two rows the
+// previous chunk left (its rows 58 and 59; on the first chunk the repeated first frame and the "first frame once more" splice,
+// both fb[0]) and this chunk's rows 0 .. 58.
+size_t online_frontend_state_bytes(int n_mels, int feat_dim) { return block_at_zero<FrontendStreamBlock>(n_mels, feat_dim).bytes(); }
+
+void online_frontend_step(void* state, const float* fb_rows, const float* shift, const float* scale, bool reset, float* speech) {
+  PF_CHECK(state && fb_rows && speech && (shift == nullptr) == (scale == nullptr), PF_ERR_INVALID_ARG, "online_frontend_step: bad arguments");
+  const int F = 80, W = 560, CL = 60, CR = (int)kFrontendStreamFrames;
+  const FrontendStreamBlock blk = block_at_zero<FrontendStreamBlock>(F, W);
+  float* carry = blk.carry(state);
+  float* cache = blk.cache(state);
+  int32_t* start = blk.start_idx(state);
+  int32_t* flags = blk.flags(state);
+  if (reset) {                                                  // ResetDecoder: the carried rows stay
+    std::fill(cache, cache + (size_t)CR * W, 0.f);
+    std::fill(start, start + CR, 0);
+  }
+  std::vector<float> pad;
+  if (flags[0] & 1) pad.assign(carry, carry + 2 * F);
+  else { pad.assign(fb_rows, fb_rows + F); pad.insert(pad.end(), fb_rows, fb_rows + F); }
+  pad.insert(pad.end(), fb_rows, fb_rows + (size_t)(CL - 1) * F);
+  std::memcpy(carry, fb_rows + (size_t)(CL - 2) * F, (size_t)2 * F * 4);
+  flags[0] |= 1;
+  std::vector<float> x = online_apply_lfr(pad, F, 7, 6);
+  online_cmvn_scale(x, shift, scale, (size_t)W);
+  online_position_encode(x, CR, W, start[0]);
+  for (int k = 0; k < CR * W; ++k) {
+    speech[k] = cache[k] == 0.f ? -23.025850929940457f : cache[k];
+    speech[CR * W + k] = x[(size_t)k] == 0.f ? -23.025850929940457f : x[(size_t)k];
+  }
+  std::memcpy(cache, x.data(), (size_t)CR * W * 4);
+  for (int i = 0; i < CR; ++i) start[i] += CR;                  // one copy per LFR frame; the padding cells keep their bits
+}
+
 static bool is_chinese_all(const std::string& s) {             // ^[一-龥]+$  (OnlineRecognizer.cs:446-458)
   const std::vector<uint32_t> cps = utf8_decode(s);
   if (cps.empty()) return false;
@@ -190,7 +241,7 @@ OnlineStreamM::OnlineStreamM(std::shared_ptr<OnlineRecognizerM> r) : owner(std::
 }
 
 OnlineStreamM::~OnlineStreamM() {
-  if (owner && (slot_ >= 0 || ep_joined_ || decoded_ || pn_joined_)) owner->release_stream(slot_, ep_joined_, decoded_, pn_joined_);
+  if (owner && (slot_ >= 0 || ep_joined_ || decoded_ || pn_joined_ || fed_)) owner->release_stream(slot_, ep_joined_, decoded_, pn_joined_, fed_);
 }
 
 const std::vector<pf_online_token>& OnlineStreamM::token_info() {
@@ -204,6 +255,7 @@ void OnlineStreamM::AddSamples(const float* samples, int64_t n) {
   if (!samples) throw Error(PF_ERR_NULL_SAMPLES, "source");
   std::vector<float> s;
   size_t n_caller = 0;
+  const bool dev = take_audio();
   {
     std::lock_guard<std::mutex> lk(mu);
     if (finished_) throw Error(PF_ERR_INVALID_ARG, "OnlineStream: AddSamples after InputFinished");
@@ -215,12 +267,73 @@ void OnlineStreamM::AddSamples(const float* samples, int64_t n) {
       n_caller = chunks_in_++ == 0 ? 0 : chunk;                 // the first chunk is the constructor's silence
     }
   }
-  if (!s.empty()) InputSpeech(s, n_caller);
+  if (s.empty()) return;
+  if (dev) QueueChunk(std::move(s), n_caller);
+  else InputSpeech(s, n_caller);
+}
+
+// The stream's first audio fixes its front-end for life (SetDeviceFrontend is refused from here on); true: the device's.
+bool OnlineStreamM::take_audio() {
+  if (!fed_) { fed_dev_ = owner->note_fed(); fed_ = true; }
+  return fed_dev_;
+}
+
+// SetDeviceFrontend: the cut chunk waits as samples for the GetResults that takes it; no engine mutex, no device call.  The rows'
+// provenance is noted as InputSpeech notes it (a chunk of 9600 samples is 60 rows with snip_edges false).
+void OnlineStreamM::QueueChunk(std::vector<float>&& samples, size_t n_caller) {
+  std::lock_guard<std::mutex> lk(mu);
+  note_rows(n_caller, owner->chunk_length());
+  raw_chunks_.push_back(std::move(samples));
+}
+
+bool OnlineStreamM::PopRawChunk(std::vector<float>& dst) {
+  std::lock_guard<std::mutex> lk(mu);
+  if (raw_chunks_.empty()) return false;
+  note_chunk(fe_spliced_, (int)kFrontendStreamFrames);
+  fe_spliced_ = true;
+  dst.insert(dst.end(), raw_chunks_.front().begin(), raw_chunks_.front().end());
+  raw_chunks_.pop_front();
+  return true;
+}
+
+bool OnlineStreamM::chunk_pending() const {
+  return fed_dev_ ? !raw_chunks_.empty() : Speech.size() >= (size_t)owner->chunk_length() * 80;
+}
+
+// the provenance of a chunk's t80 fbank rows (frame r starts at first + 160 r); true: the first frame is repeated once (:131-143)
+bool OnlineStreamM::note_rows(size_t n_caller, int t80) {
+  const int64_t first = n_caller > 0 ? caller_samples_ : -1;
+  caller_samples_ += (int64_t)n_caller;
+  const bool repeat = first_input_ && t80 > 0;
+  if (repeat) {
+    speech_idx_.push_back(first);
+    first_input_ = false;
+  }
+  for (int r = 0; r < t80; ++r) speech_idx_.push_back(first < 0 ? -1 : first + 160 * (int64_t)r);
+  return repeat;
+}
+
+// the provenance of the chunk that is being taken: the splice row and CL rows of speech_idx_ in, chunk_idx_ and cache_idx_ out
+void OnlineStreamM::note_chunk(bool have_splice, int timesteps) {
+  const int CL = owner->chunk_length();
+  const ConfEntity& c = owner->conf();
+  std::vector<int64_t> pidx(1, have_splice ? splice_idx_ : speech_idx_[0]);   // provenance travels with the rows
+  pidx.insert(pidx.end(), speech_idx_.begin(), speech_idx_.begin() + CL);
+  splice_idx_ = pidx.back();
+  const bool lfr = c.lfr_m != 1 || c.lfr_n != 1;
+  chunk_idx_ = cache_idx_;
+  for (int i = 0; i < timesteps; ++i) {                                   // an LFR frame takes the index of its first row
+    const size_t r = lfr ? (size_t)i * (size_t)c.lfr_n : (size_t)i;
+    chunk_idx_.push_back(r < pidx.size() ? pidx[r] : -1);
+  }
+  cache_idx_.assign(chunk_idx_.end() - (long)cache_idx_.size(), chunk_idx_.end());
+  speech_idx_.erase(speech_idx_.begin(), speech_idx_.begin() + CL);
 }
 
 void OnlineStreamM::InputFinished() {
   if (disposed) throw Error(PF_ERR_DISPOSED, "OnlineStream");
   const size_t chunk = (size_t)160 * owner->chunk_length();
+  const bool dev = take_audio();
   for (;;) {
     std::vector<float> s;
     size_t n_caller = 0;
@@ -234,7 +347,8 @@ void OnlineStreamM::InputFinished() {
       n_caller = chunks_in_++ == 0 ? 0 : take;
       s.resize(chunk, 0.f);                                     // the tail: zero-padded to one chunk
     }
-    InputSpeech(s, n_caller);
+    if (dev) QueueChunk(std::move(s), n_caller);
+    else InputSpeech(s, n_caller);
   }
 }
 
@@ -243,6 +357,7 @@ void OnlineStreamM::ResetDecoder() {                            // (the caller h
   TokenInfo.clear();
   if (owner->token_info_on()) {                                 // the context lives in the slot: its next step starts from zeros
     cif_reset_ = cache_reset_ = true;
+    fe_reset_ = true;                                           // (read with SetDeviceFrontend only: the slot's feature cache and start_idx)
   } else {
     for (std::vector<float>& st : States) std::fill(st.begin(), st.end(), 0.f);
     CifHidden.assign(1, std::vector<float>((size_t)512, 0.f));
@@ -271,15 +386,8 @@ void OnlineStreamM::InputSpeech(const std::vector<float>& samples, size_t n_call
     ep_audio_.insert(ep_audio_.end(), samples.begin(), samples.begin() + (long)n_caller);
     ep_samples_ += (int64_t)n_caller;
   }
-  const int64_t first = n_caller > 0 ? caller_samples_ : -1;             // the rows' provenance: frame r starts at first + 160 r
-  caller_samples_ += (int64_t)n_caller;
-  if (first_input_ && t80 > 0) {                                          // :131-143: the first frame is repeated once
-    Speech.insert(Speech.end(), fb.begin(), fb.begin() + 80);
-    speech_idx_.push_back(first);
-    first_input_ = false;
-  }
+  if (note_rows(n_caller, t80)) Speech.insert(Speech.end(), fb.begin(), fb.begin() + 80);   // :131-143: the first frame is repeated once
   Speech.insert(Speech.end(), fb.begin(), fb.end());
-  for (int r = 0; r < t80; ++r) speech_idx_.push_back(first < 0 ? -1 : first + 160 * (int64_t)r);
 }
 
 bool OnlineStreamM::GetDecodeChunk(std::vector<float>& chunk) {
@@ -287,9 +395,7 @@ bool OnlineStreamM::GetDecodeChunk(std::vector<float>& chunk) {
   const int F = 80, CL = owner->chunk_length();
   if ((size_t)CL * F > Speech.size()) return false;
   std::vector<float> pad;
-  std::vector<int64_t> pidx(1, cache_lfr_splice_.empty() ? speech_idx_[0] : splice_idx_);   // provenance travels with the rows
-  pidx.insert(pidx.end(), speech_idx_.begin(), speech_idx_.begin() + CL);
-  splice_idx_ = pidx.back();
+  const bool have_splice = !cache_lfr_splice_.empty();
   if (!cache_lfr_splice_.empty()) pad = cache_lfr_splice_;                // :172-178
   else pad.assign(Speech.begin(), Speech.begin() + F);                    // :180-187: first frame once more
   pad.insert(pad.end(), Speech.begin(), Speech.begin() + (long)CL * F);
@@ -298,26 +404,12 @@ bool OnlineStreamM::GetDecodeChunk(std::vector<float>& chunk) {
   std::vector<float> x = pad;
   if (c.lfr_m != 1 || c.lfr_n != 1) x = online_apply_lfr(pad, F, c.lfr_m, c.lfr_n);
   const std::vector<float>& sh = owner->shift();
-  const std::vector<float>& sc = owner->scale();
-  if (!sh.empty()) {                                                      // ApplyCmvn, OnlineWavFrontend.cs:46-62
-    const size_t dim = sh.size();
-    for (size_t i = 0; i + dim <= x.size(); i += dim)
-      for (size_t k = 0; k < dim; ++k) { const volatile float s = x[i + k] + sh[k]; x[i + k] = s * sc[k]; }
-  }
-  const double root = std::pow(512.0, 0.5);
-  for (float& v : x) v = (float)((double)v * root);                       // :193
+  online_cmvn_scale(x, sh.empty() ? nullptr : sh.data(), owner->scale().data(), sh.size());   // ApplyCmvn, then :193
   const int W = 560, timesteps = (int)(x.size() / W);
   online_position_encode(x, timesteps, W, start_idx_);                    // :195-196
   chunk = cache_feats_;
   chunk.insert(chunk.end(), x.begin(), x.end());
-  const bool lfr = c.lfr_m != 1 || c.lfr_n != 1;
-  chunk_idx_ = cache_idx_;
-  for (int i = 0; i < timesteps; ++i) {                                   // an LFR frame takes the index of its first row
-    const size_t r = lfr ? (size_t)i * (size_t)c.lfr_n : (size_t)i;
-    chunk_idx_.push_back(r < pidx.size() ? pidx[r] : -1);
-  }
-  cache_idx_.assign(chunk_idx_.end() - (long)cache_idx_.size(), chunk_idx_.end());
-  speech_idx_.erase(speech_idx_.begin(), speech_idx_.begin() + CL);
+  note_chunk(have_splice, timesteps);
   start_idx_ += timesteps;
   cache_feats_.assign(chunk.end() - (long)cache_feats_.size(), chunk.end());   // :201
   Speech.erase(Speech.begin(), Speech.begin() + (long)CL * F);            // RemoveChunk :210-224
@@ -373,6 +465,7 @@ void OnlineRecognizerM::Dispose() {
     if (ti_states_) { hipSetDevice(e->device()); hipFree(ti_states_); ti_states_ = nullptr; }
     if (pn_states_) { hipSetDevice(e->device()); hipFree(pn_states_); pn_states_ = nullptr; }
     if (pn_ws_) { hipSetDevice(e->device()); hipFree(pn_ws_); pn_ws_ = nullptr; pn_ws_bytes_ = 0; }
+    if (fe_states_) { hipSetDevice(e->device()); hipFree(fe_states_); fe_states_ = nullptr; }
     pn_model_.reset();
     pn_on_ = false;
     ep_model_.reset();
@@ -385,6 +478,7 @@ void OnlineRecognizerM::Dispose() {
 void OnlineRecognizerM::SetEndpoint(const pf_endpoint_config* cfg) {
   if (disposed_) throw Error(PF_ERR_DISPOSED, "OnlineRecognizer");
   if (!cfg) { ep_on_ = false; return; }
+  PF_CHECK(!device_frontend_on(), PF_ERR_UNSUPPORTED, "endpoint: not with SetDeviceFrontend (the detector takes host fbank rows at AddSamples)");
   const pf_endpoint_config c = endpoint_check(cfg, (conf_.lfr_m == 1 && conf_.lfr_n == 1) ? 1 : conf_.lfr_n);
   PF_CHECK(!conf_.snip_edges, PF_ERR_UNSUPPORTED, "endpoint: snip_edges = true is not supported");
   PF_CHECK(conf_.n_mels == 80, PF_ERR_UNSUPPORTED, "endpoint: the streaming path carries 80 mel bins");
@@ -432,8 +526,9 @@ void OnlineRecognizerM::SetSecondPass(std::shared_ptr<Recognizer> offline) {
   second_ = std::move(offline);
 }
 
-void OnlineRecognizerM::release_stream(int slot, bool ep_joined, bool decoded, bool punc_joined) {
+void OnlineRecognizerM::release_stream(int slot, bool ep_joined, bool decoded, bool punc_joined, bool fed) {
   std::lock_guard<std::mutex> lk(ep_mu_);
+  if (fed) --fed_live_;
   if (ep_states_ && slot >= 0 && slot < ep_cap_) ep_free_.push_back(slot);
   if (ep_joined) --ep_live_;
   if (decoded) --decoded_live_;
@@ -478,6 +573,7 @@ void OnlineRecognizerM::SetTokenInfo(bool on) {
   std::lock_guard<std::mutex> lk(eh->mutex());
   std::lock_guard<std::mutex> lk2(ep_mu_);
   if (on == ti_on_.load()) return;
+  PF_CHECK(on || !fe_on_.load(), PF_ERR_UNSUPPORTED, "token info: the device front-end is on (turn SetDeviceFrontend off first)");
   PF_CHECK(decoded_live_ == 0, PF_ERR_UNSUPPORTED,
            "token info: a live stream has already decoded a chunk (turn the mode on or off before the first GetResults with audio)");
   PF_HIP(hipSetDevice(eh->device()));
@@ -489,6 +585,40 @@ void OnlineRecognizerM::SetTokenInfo(bool on) {
   ti_bytes_ = on ? eh->online_slot_bytes() : 0;
   if (on && ep_cap_ > 0) PF_HIP(hipMalloc((void**)&ti_states_, (size_t)ep_cap_ * ti_bytes_));
   ti_on_ = on;
+}
+
+bool OnlineRecognizerM::note_fed() {
+  std::lock_guard<std::mutex> lk(ep_mu_);
+  ++fed_live_;
+  return fe_on_.load();
+}
+
+void OnlineRecognizerM::SetDeviceFrontend(bool on) {
+  if (disposed_) throw Error(PF_ERR_DISPOSED, "OnlineRecognizer");
+  std::shared_ptr<Engine> eh = engine();
+  if (!eh) throw Error(PF_ERR_DISPOSED, "OnlineRecognizer");
+  std::lock_guard<std::mutex> lk(eh->mutex());
+  std::lock_guard<std::mutex> lk2(ep_mu_);
+  if (on == fe_on_.load()) return;
+  PF_CHECK(fed_live_ == 0, PF_ERR_UNSUPPORTED,
+           "device front-end: a live stream has already taken audio (turn the mode on or off before the first AddSamples)");
+  if (on) {
+    PF_CHECK(ti_on_.load(), PF_ERR_UNSUPPORTED, "device front-end: SetTokenInfo(true) first (device-carried and host-carried state must not meet)");
+    PF_CHECK(!ep_on_.load(), PF_ERR_UNSUPPORTED, "device front-end: not with SetEndpoint (the detector takes host fbank rows at AddSamples)");
+    PF_CHECK(!conf_.snip_edges, PF_ERR_UNSUPPORTED, "device front-end: snip_edges = true is not supported");
+    PF_CHECK(chunk_length() == 60, PF_ERR_UNSUPPORTED, "device front-end: chunks of 60 fbank frames only");
+    PF_CHECK(conf_.n_mels == 80 && conf_.lfr_m == 7 && conf_.lfr_n == 6, PF_ERR_UNSUPPORTED, "device front-end: 80 mel bins and LFR 7 / 6 only");
+    PF_CHECK(shift_.empty() || shift_.size() == 560, PF_ERR_UNSUPPORTED, "device front-end: a CMVN of 560 columns, or none");
+  }
+  PF_HIP(hipSetDevice(eh->device()));
+  if (fe_states_) {
+    PF_HIP(hipStreamSynchronize(eh->stream()));
+    PF_HIP(hipFree(fe_states_));
+    fe_states_ = nullptr;
+  }
+  fe_bytes_ = on ? eh->online_frontend_slot_bytes() : 0;
+  if (on && ep_cap_ > 0) PF_HIP(hipMalloc((void**)&fe_states_, (size_t)ep_cap_ * fe_bytes_));   // (a block is zeroed where a stream takes its slot)
+  fe_on_ = on;
 }
 
 // grows one per-stream buffer from ep_cap_ to cap slots of `bytes` each (the old blocks copied on the device)
@@ -513,12 +643,14 @@ void OnlineRecognizerM::ensure_slot(OnlineStreamM* s, Engine* e) {
     if (ep_model_) grow_slots(e, ep_net_states_, ep_cap_, cap, ep_net_bytes_);   // the network's states grow with the detector's
     if (ti_on_) grow_slots(e, ti_states_, ep_cap_, cap, ti_bytes_);              // and so does the decoder state
     if (pn_model_) grow_slots(e, pn_states_, ep_cap_, cap, pn_bytes_);           // and the punctuation state
+    if (fe_on_) grow_slots(e, fe_states_, ep_cap_, cap, fe_bytes_);              // and the front-end's block
     for (int i = cap - 1; i >= ep_cap_; --i) ep_free_.push_back(i);
     ep_cap_ = cap;
   }
   s->slot_ = ep_free_.back();
   ep_free_.pop_back();
   s->cif_reset_ = s->cache_reset_ = true;                       // a reused slot's decoder state starts from zeros on its first step
+  if (fe_on_) PF_HIP(hipMemsetAsync(fe_states_ + (size_t)s->slot_ * fe_bytes_, 0, fe_bytes_, e->stream()));   // a zero block: a new stream
 }
 
 // The detector's launch set for the call's streams that have new caller frames or a flush to make, the sentences its events
@@ -654,6 +786,7 @@ void OnlineRecognizerM::Forward(const std::vector<OnlineStreamM*>& streams) {
     for (size_t i = 0; i < streams.size(); ++i)
       for (size_t j = 0; j < i; ++j)
         PF_CHECK(streams[i] != streams[j], PF_ERR_INVALID_ARG, "token info: a stream twice in one GetResults");
+  if (device_frontend_on()) { ForwardFrontend(streams); return; }
   std::vector<OnlineStreamM*> work;
   std::vector<std::vector<float>> chunks;
   for (OnlineStreamM* s : streams) {                            // :349-363
@@ -683,7 +816,11 @@ void OnlineRecognizerM::Forward(const std::vector<OnlineStreamM*>& streams) {
     const int Tc = (int)(maxlen / W);
     for (OnlineStreamM* s : work)
       if (!s->decoded_) { std::lock_guard<std::mutex> ls(ep_mu_); s->decoded_ = true; ++decoded_live_; }
-    if (token_info_on()) { ForwardDevice(e, work, speech, Tc); return; }
+    if (token_info_on()) {
+      PF_CHECK(speech.size() == (size_t)B * Tc * 560, PF_ERR_RECOGNITION, "Destination array was not long enough (PadSequence)");
+      ForwardDevice(e, work, speech.data(), Tc);
+      return;
+    }
     // stack_states (OnlineModel.cs:199-220): EVERY layer's in_cache is built from the streams' LAYER-0 state
     std::vector<float> cin((size_t)nd * B * D * CW);
     for (int l = 0; l < nd; ++l)
@@ -746,9 +883,42 @@ void OnlineRecognizerM::Forward(const std::vector<OnlineStreamM*>& streams) {
 
 // Forward with SetTokenInfo: the chunk step on the device (Engine::online_step), then ids, scores, fire entries and times per stream.
 // The decoder state of a stream is its slot of ti_states_; nothing of it is mirrored on the host.
-void OnlineRecognizerM::ForwardDevice(Engine* e, const std::vector<OnlineStreamM*>& work, const std::vector<float>& speech, int Tc) {
+// Forward with SetDeviceFrontend: one raw chunk per stream that has one, the front-end's two launches into the engine's speech buffer
+// (Engine::online_frontend), then the device form of the chunk step.  Only the samples go up.
+void OnlineRecognizerM::ForwardFrontend(const std::vector<OnlineStreamM*>& streams) {
+  std::vector<OnlineStreamM*> work;
+  std::vector<float> samples;
+  for (OnlineStreamM* s : streams)
+    if (s->PopRawChunk(samples)) work.push_back(s);             // what GetDecodeChunk consumes: one chunk per stream per call
+  if (work.empty()) return;
+  try {
+    std::shared_ptr<Engine> eh = engine();
+    if (disposed_ || !eh) throw Error(PF_ERR_DISPOSED, "OnlineRecognizer");
+    Engine* e = eh.get();
+    std::lock_guard<std::mutex> lk(e->mutex());
+    const int B = (int)work.size();
+    std::vector<int32_t> slot((size_t)B), reset((size_t)B);
+    for (int b = 0; b < B; ++b) {
+      OnlineStreamM* s = work[(size_t)b];
+      if (!s->decoded_) { std::lock_guard<std::mutex> ls(ep_mu_); s->decoded_ = true; ++decoded_live_; }
+      ensure_slot(s, e);
+      slot[(size_t)b] = s->slot_; reset[(size_t)b] = s->fe_reset_ ? 1 : 0;
+    }
+    char* states = nullptr;
+    { std::lock_guard<std::mutex> ls(ep_mu_); states = fe_states_; }
+    PF_CHECK(states != nullptr, PF_ERR_DEVICE, "device front-end: no state buffer");
+    e->online_frontend(samples.data(), B, states, slot.data(), reset.data());
+    for (OnlineStreamM* s : work) { std::lock_guard<std::mutex> ls(s->mu); s->fe_reset_ = false; }
+    ForwardDevice(e, work, nullptr, 20);
+  } catch (const Error& ex) {
+    if (ex.code == PF_ERR_RECOGNITION && std::string(ex.what()).rfind("Online recognition failed", 0) == 0) throw;
+    throw Error(PF_ERR_RECOGNITION, std::string("Online recognition failed: ") + ex.what());
+  }
+}
+
+// speech: the call's chunks [B, Tc, 560] on the host, or null when the front-end has left them on the device
+void OnlineRecognizerM::ForwardDevice(Engine* e, const std::vector<OnlineStreamM*>& work, const float* speech, int Tc) {
   const int B = (int)work.size(), lo = 5, hi = 15;             // DynamicMask (OnlineModel.cs:141-165): chunk_size 5, lfr 10
-  PF_CHECK(speech.size() == (size_t)B * Tc * 560, PF_ERR_RECOGNITION, "Destination array was not long enough (PadSequence)");
   for (int i = 0; i < B; ++i)                                   // (Forward has refused this already; a race with SetTokenInfo ends here)
     for (int j = 0; j < i; ++j) PF_CHECK(work[(size_t)i] != work[(size_t)j], PF_ERR_INVALID_ARG, "token info: a stream twice in one GetResults");
   std::vector<int32_t> slot((size_t)B), cif_reset((size_t)B), cache_reset((size_t)B);
@@ -761,7 +931,8 @@ void OnlineRecognizerM::ForwardDevice(Engine* e, const std::vector<OnlineStreamM
   { std::lock_guard<std::mutex> ls(ep_mu_); states = ti_states_; }
   PF_CHECK(states != nullptr, PF_ERR_DEVICE, "token info: no state buffer");
   Engine::OnlineStepOut out;
-  e->online_step(speech.data(), B, Tc, states, slot.data(), cif_reset.data(), cache_reset.data(), lo, hi, out);
+  if (speech) e->online_step(speech, B, Tc, states, slot.data(), cif_reset.data(), cache_reset.data(), lo, hi, out);
+  else e->online_step_device(nullptr, B, Tc, states, slot.data(), cif_reset.data(), cache_reset.data(), lo, hi, out);
   const int L = out.max_tok, cap = out.cap;
   const int64_t fs = conf_.fs > 0 ? conf_.fs : 16000;
   for (int b = 0; b < B; ++b) {
@@ -806,7 +977,6 @@ void OnlineRecognizerM::ForwardPunc(const std::vector<OnlineStreamM*>& streams) 
     { std::lock_guard<std::mutex> ls(ep_mu_); pm = pn_model_; mc = pn_max_context_; }
     if (!pm) return;
     std::vector<Job> jobs;
-    const size_t CLF = (size_t)chunk_length() * 80;
     int B = 0, ld = 1;
     for (OnlineStreamM* s : streams) {
       bool seen = false;
@@ -824,7 +994,7 @@ void OnlineRecognizerM::ForwardPunc(const std::vector<OnlineStreamM*>& streams) 
         if (s->pn_flushed_) continue;                          // the end-of-input flush was made: nothing follows it
         j.c = online_committed_words(*pm, tokens_, s->Tokens);
         online_check_committed_prefix(s->pn_words_, j.c);
-        j.flush = s->finished_ && s->cache_samples_.empty() && s->Speech.size() < CLF;
+        j.flush = s->finished_ && s->cache_samples_.empty() && !s->chunk_pending();
       }
       j.n_send = j.flush ? j.c.words.size() : j.c.n_committed;   // a flush takes the held-back word too
       j.n_new = (int)(j.n_send - s->pn_words_.size());

@@ -8,6 +8,7 @@
 // The two ONNX sessions (encoder, decoder) are replaced by Engine::online_encoder / online_decoder.
 #pragma once
 #include <atomic>
+#include <deque>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -41,6 +42,18 @@ size_t online_cif_state_bytes(int D);
 int online_cif_step(void* state, const float* hiddens, const float* alphas, int Tc, int D, float threshold, int lo, int hi, bool reset,
                     float* fired, int32_t* fire_entry, int cap);
 // OnlineRecognizer.DecodeMulti (:405-437) for one stream
+// ApplyCmvn (OnlineWavFrontend.cs:46-62; shift null: none) over rows of `dim` columns, then the sqrt(512) scale through a double
+// (OnlineStream.cs:193)
+void online_cmvn_scale(std::vector<float>& x, const float* shift, const float* scale, size_t dim);
+// One chunk step of one stream's front-end behind the fbank, on its state block (decode_blocks.h FrontendStreamBlock for 80 mels
+// and 560 columns, online_frontend_state_bytes(80, 560) bytes; a zero-filled block is a new stream): the 61-row splice of the
+// two carried rows and fb_rows [60, 80] (the chunk's fbank rows), LFR 7 / 6 without left context, online_cmvn_scale (shift null:
+// no CMVN), online_position_encode at the block's start_idx; speech [20, 560] = [the cached ten rows ; the new ten], every exact
+// 0 as the streaming sentinel; the new rows become the cache, rows 58 and 59 the carry, start_idx += 10.  reset: the cache is
+// zeros and start_idx 0 before the step (ResetDecoder), the carried rows stay.  Built from the three pieces above, it is what
+// GetDecodeChunk and Forward's sentinel compute for one stream; online_frontend_kernel (k_frontend_stream.hip) is its device twin.
+size_t online_frontend_state_bytes(int n_mels, int feat_dim);
+void online_frontend_step(void* state, const float* fb_rows, const float* shift, const float* scale, bool reset, float* speech);
 std::string online_decode_text(const std::vector<std::string>& tokens, const std::vector<int64_t>& ids);
 // Streaming punctuation (paraformer_hip.h "Punctuation, streaming"; tests/punc_stream_ref.py committed_words): the words of
 // online_decode_text(tokens, ids) as host_punc_words splits them.  While the last token that contributes text ends in "@@" the
@@ -103,6 +116,17 @@ class OnlineStreamM {
   // n_caller: how many of the chunk's leading samples are the caller's (0 for the chunk of silence the constructor queued)
   void InputSpeech(const std::vector<float>& samples, size_t n_caller);   // :106-160
   void ResetDecoder();                                        // the decoder context back to the constructor's, Tokens cleared
+  // the index arithmetic both front-ends share (the time rule's provenance lists below)
+  bool note_rows(size_t n_caller, int t80);
+  void note_chunk(bool have_splice, int timesteps);
+  // SetDeviceFrontend: the cut chunks wait as samples (raw_chunks_) for Forward, which pops one per call; the stream's features,
+  // splice rows and start_idx live in its slot's FrontendStreamBlock, fe_reset_ asks the next step to reset that block
+  bool take_audio();
+  void QueueChunk(std::vector<float>&& samples, size_t n_caller);
+  bool PopRawChunk(std::vector<float>& dst);                  // appends the oldest queued chunk to dst; false: none
+  bool chunk_pending() const;                                 // a chunk is waiting for a GetResults (the caller holds mu)
+  std::deque<std::vector<float>> raw_chunks_;
+  bool fed_ = false, fed_dev_ = false, fe_spliced_ = false, fe_reset_ = false;
   std::vector<float> cache_samples_, cache_feats_, cache_lfr_splice_;
   bool first_input_ = true;                                   // _cacheInput.Length == 0
   int start_idx_ = 0;
@@ -168,6 +192,15 @@ class OnlineRecognizerM : public std::enable_shared_from_this<OnlineRecognizerM>
   // OnlineStreamM::TokenInfo.  PF_ERR_UNSUPPORTED once a live stream has decoded a chunk; the value it already has is a no-op.
   void SetTokenInfo(bool on);
   bool token_info_on() const { return ti_on_.load(); }
+  // The front-end on the device (paraformer_hip.h "Streaming front-end on the device"): AddSamples / InputFinished
+  // then only queue the cut chunks (no engine mutex, no device call) and Forward runs Engine::online_frontend — fbank, splice,
+  // LFR, CMVN, scale, position term, feature cache and sentinel in two launches for all streams of the call — in front of the
+  // device form of the chunk step.  PF_ERR_UNSUPPORTED: token info off, SetEndpoint on, a live stream has already taken audio,
+  // snip_edges, a chunk length other than 60, a geometry other than 80 mels with LFR 7 / 6.  While it is on, SetEndpoint and
+  // SetTokenInfo(false) are refused.
+  void SetDeviceFrontend(bool on);
+  bool device_frontend_on() const { return fe_on_.load(); }
+  bool note_fed();                                            // a stream takes its first audio; returns device_frontend_on()
   // Streaming punctuation (paraformer_hip.h "Punctuation, streaming"): loads a causal `.pfw` of kind
   // "cttransformer" and attaches it to the engine; "" detaches and frees.  Every GetResults then marks the newly committed
   // words of all its streams in ONE punc_stream launch; a stream's keys and values live in one more slot-indexed device buffer.
@@ -175,12 +208,13 @@ class OnlineRecognizerM : public std::enable_shared_from_this<OnlineRecognizerM>
   // punctuation state; PF_ERR_INVALID_ARG for max_context outside 2 .. 256.
   void SetPuncModel(const std::string& pfw_path, int max_context);
   bool punc_on() const { return pn_on_.load(); }
-  void release_stream(int slot, bool ep_joined, bool decoded, bool punc_joined);   // ~OnlineStreamM
+  void release_stream(int slot, bool ep_joined, bool decoded, bool punc_joined, bool fed);   // ~OnlineStreamM
 
  private:
   void Forward(const std::vector<OnlineStreamM*>& streams);   // :336-403
   void ForwardEndpoint(const std::vector<OnlineStreamM*>& streams);
-  void ForwardDevice(Engine* e, const std::vector<OnlineStreamM*>& work, const std::vector<float>& speech, int Tc);
+  void ForwardFrontend(const std::vector<OnlineStreamM*>& streams);
+  void ForwardDevice(Engine* e, const std::vector<OnlineStreamM*>& work, const float* speech, int Tc);
   void ForwardPunc(const std::vector<OnlineStreamM*>& streams);
   // a slot for a stream that has none (the engine's mutex is held): every per-stream buffer grows together by reallocate-and-copy
   // on the device; the detector's and the network's blocks are zeroed where the stream joins the detector (ForwardEndpoint),
@@ -205,6 +239,10 @@ class OnlineRecognizerM : public std::enable_shared_from_this<OnlineRecognizerM>
   char* pn_ws_ = nullptr;                                     // the launch's staged operands and results
   size_t pn_bytes_ = 0, pn_ws_bytes_ = 0;
   int pn_max_context_ = 0, pn_live_ = 0;
+  std::atomic<bool> fe_on_{false};
+  char* fe_states_ = nullptr;                                 // [ep_cap_, fe_bytes_] on the device: FrontendStreamBlock per slot (SetDeviceFrontend)
+  size_t fe_bytes_ = 0;
+  int fed_live_ = 0;                                          // live streams that have taken audio
   int ep_live_ = 0, decoded_live_ = 0;                        // live streams that have fed the detector / decoded a chunk
   std::mutex mu_;
   std::shared_ptr<Engine> engine_;

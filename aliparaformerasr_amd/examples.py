@@ -2,7 +2,7 @@
 
     python -m aliparaformerasr_amd.examples -type offline -method batch -base <dir> -model <name> \
         [-accuracy int8] [-threads 2] [-decode ctc|frames] [-intake host|device] [-nbest N [-topk K] [-beam W | -search W] [-hotboost S] [-lm FILE [-lmweight A] [-lmbonus B] [-lmeos]]] [-align FILE|beam] [-vad [key=value,...] [-vadmodel FILE] [-spk FILE [key=value,...]]] [-punc FILE] -files a.wav b.wav
-    python -m aliparaformerasr_amd.examples -type online -method one -base <dir> -model <name> [-endpoint [key=value,...] [-vadmodel FILE] [-secondpass <offline name>]] [-tokentimes] [-puncstream FILE[,max_context=N]] -files a.wav
+    python -m aliparaformerasr_amd.examples -type online -method one -base <dir> -model <name> [-endpoint [key=value,...] [-vadmodel FILE] [-secondpass <offline name>]] [-tokentimes [-devicefrontend]] [-puncstream FILE[,max_context=N]] -files a.wav
 
 Mirrors (file:line in /root/reference/AliParaformerAsr.Examples):
   * argument handling and defaults — Program.cs:93-104, ParseArgs :197-252: the MANYSPEECH_BASE / _TYPE / _BATCH / _MODEL /
@@ -70,6 +70,8 @@ abs_level=9830; unvalidated too) apply unless keys are given.  A sentence line c
 in directory NAME under -base (its files chosen as `-type offline` chooses them): the sentence lines then carry its text.
 `-tokentimes` (online; OnlineRecognizer.SetTokenInfo) prints under each result one line of `token[time_ms score]` for the tokens
 the stream fired (special tokens left out); with `-endpoint` also under each `[begin-end ms]` line, for the closed sentence.  A time is the start of the 60 ms frame in which the token fired, not a word boundary.
+`-devicefrontend` (with `-tokentimes`, not with `-endpoint`; OnlineRecognizer.SetDeviceFrontend) runs the streaming front-end on
+the GPU too: fbank, LFR, CMVN, position term and feature cache for all streams of a GetResults at once.  The output is that of the run without it.
 `-puncstream FILE[,max_context=N]` (online; OnlineRecognizer.SetPuncModel) punctuates the words as they arrive with a causal
 CT-Transformer on the GPU (FILE: a .pfw made by `convert --kind cttransformer --causal`): a `punctuated: ...` line under each
 partial result and under each finished sentence.  `-punc` stays an offline option.  Not validated on a real model."""
@@ -481,7 +483,7 @@ def token_times_line(info, names):
 
 def online_recognizer(method="one", model="speech_paraformer-large_asr_nat-zh-cn-16k-common-vocab8404-online-onnx",
                       accuracy="int8", threads=2, files=None, base=None, out=sys.stdout, endpoint=None, secondpass=None, vadmodel=None,
-                      tokentimes=False, puncstream=None):
+                      tokentimes=False, puncstream=None, devicefrontend=False):
     from .online_recognizer import OnlineRecognizer
     base = base or os.getcwd()
     if not model:
@@ -502,6 +504,8 @@ def online_recognizer(method="one", model="speech_paraformer-large_asr_nat-zh-cn
     if tokentimes:
         rec.SetTokenInfo(True)
         names = read_token_table(sel["tokensFilePath"])
+    if devicefrontend:
+        rec.SetDeviceFrontend(True)
     if puncstream:
         try:
             rec.SetPuncModel(puncstream["file"], puncstream.get("max_context", 0))
@@ -676,6 +680,8 @@ def parse_args(argv, env=None):
             cfg["endpoint"] = parse_endpoint_option(text)
         elif a == "-tokentimes":
             cfg["tokentimes"] = True
+        elif a == "-devicefrontend":
+            cfg["devicefrontend"] = True
         elif a == "-secondpass":
             i += 1
             if i >= len(argv) or argv[i].startswith("-"):
@@ -757,6 +763,8 @@ def parse_args(argv, env=None):
         raise ValueError("-puncstream goes with -type online")
     if "tokentimes" in cfg and cfg.get("recognizerType") != "online":
         raise ValueError("-tokentimes goes with -type online")
+    if "devicefrontend" in cfg and ("tokentimes" not in cfg or "endpoint" in cfg):
+        raise ValueError("-devicefrontend goes with -tokentimes and not with -endpoint")
     if "vadmodel" in cfg and "vad" not in cfg and "endpoint" not in cfg:
         raise ValueError("-vadmodel goes with -vad (offline) or -endpoint (online)")
     if cfg.get("align") == "beam" and "beam" not in cfg:
@@ -775,7 +783,8 @@ def main(argv=None):
     if cfg["recognizerType"] == "online":
         online_recognizer(cfg["methodType"], cfg["modelName"], cfg["modelAccuracy"], cfg["threads"], cfg["files"],
                           cfg["modelBasePath"] or None, endpoint=cfg.get("endpoint"), secondpass=cfg.get("secondpass"),
-                          vadmodel=cfg.get("vadmodel"), tokentimes=bool(cfg.get("tokentimes")), puncstream=cfg.get("puncstream"))
+                          vadmodel=cfg.get("vadmodel"), tokentimes=bool(cfg.get("tokentimes")), puncstream=cfg.get("puncstream"),
+                          devicefrontend=bool(cfg.get("devicefrontend")))
     elif cfg["recognizerType"] == "offline":
         offline_recognizer(cfg["methodType"], cfg["modelName"], cfg["modelAccuracy"], cfg["threads"], cfg["files"],
                            cfg["modelBasePath"] or None, decode=cfg.get("decode", "frames"), intake=cfg.get("intake", "host"),

@@ -172,6 +172,16 @@ class OnlineRecognizer:
         recognizer has decoded a chunk."""
         _ck(self._lib.pf_online_recognizer_set_token_info(self._h, 1 if on else 0))
 
+    def SetDeviceFrontend(self, on=True) -> None:
+        """The streaming front-end on the device (pf_online_recognizer_set_device_frontend; off by default): AddSamples and
+        InputFinished then only queue the cut chunks (no engine lock, no device call), and every GetResults takes one chunk per
+        stream through fbank, LFR, CMVN, the position term and the feature cache on the device, all streams at once, in front of
+        the chunk step.
+        Tokens, Text and TokenInfo are what they are with the mode off.  Needs SetTokenInfo(True); refused with SetEndpoint on
+        (endpointing on this path is a follow-up), once a live stream has taken audio, with snip_edges, and for a geometry other
+        than 80 mels with LFR 7 / 6; while it is on, SetEndpoint and SetTokenInfo(False) are refused."""
+        _ck(self._lib.pf_online_recognizer_set_device_frontend(self._h, 1 if on else 0))
+
     def SetPuncModel(self, pfwPath, maxContext: int = 0) -> None:
         """Streaming punctuation (pf_online_recognizer_set_punc_model; off by default): a causal `.pfw` of kind "cttransformer"
         (convert --kind cttransformer --causal); None detaches and frees.  Every GetResults then marks the newly committed words

@@ -35,6 +35,7 @@ namespace AliParaformerAsr.Hip
         [DllImport(Lib)] internal static extern int pf_online_stream_sentence_result(IntPtr s, int j, out IntPtr offlineStream);
         [DllImport(Lib)] internal static extern int pf_online_stream_in_speech(IntPtr s, out int inSpeech, out int beginMs);
         [DllImport(Lib)] internal static extern int pf_online_recognizer_set_token_info(IntPtr r, int on);
+        [DllImport(Lib)] internal static extern int pf_online_recognizer_set_device_frontend(IntPtr r, int on);
         [DllImport(Lib)] internal static extern int pf_online_stream_token_info(IntPtr s, out IntPtr toks, out int n);
         [DllImport(Lib)] internal static extern int pf_online_stream_sentence_tokens(IntPtr s, int j, out IntPtr toks, out int n);
         [DllImport(Lib)] internal static extern void pf_online_stream_dispose(IntPtr s);
@@ -148,6 +149,11 @@ namespace AliParaformerAsr.Hip
         // a live stream has decoded a chunk.
         public void SetTokenInfo(bool on = true)
             => ParaformerHip.Check(OnlineNative.pf_online_recognizer_set_token_info(_h, on ? 1 : 0));
+
+        // The streaming front-end on the device: AddSamples only queues chunks, GetResults runs fbank, LFR, CMVN, the position term
+        // and the feature cache on the device for all streams at once.  Needs SetTokenInfo(true); refused with SetEndpoint on and once a stream has taken audio.
+        public void SetDeviceFrontend(bool on = true)
+            => ParaformerHip.Check(OnlineNative.pf_online_recognizer_set_device_frontend(_h, on ? 1 : 0));
 
         // the offline recognizer's native handle that re-recognises every finished sentence (IntPtr.Zero: none)
         public void SetSecondPass(IntPtr offlineRecognizerHandle)

@@ -1858,6 +1858,24 @@ typedef struct { int64_t id; int32_t time_ms; int32_t entry; float score; int32_
 int pf_online_recognizer_set_token_info(pf_online_recognizer* r, int32_t on);
 int pf_online_stream_token_info(pf_online_stream* s, const pf_online_token** toks, int32_t* n);   /* n == number of Tokens, index for index */
 int pf_online_stream_sentence_tokens(pf_online_stream* s, int32_t j, const pf_online_token** toks, int32_t* n);
+/* ---- Streaming front-end on the device (additions to ABI 6; opt-in: without pf_online_recognizer_set_device_frontend(r, 1) every
+   streaming call makes the launches and copies and returns the bytes it does without it) ----
+   With the mode on pf_online_stream_add_samples / pf_online_stream_input_finished only cut chunks of 9600 samples and queue them
+   on the stream: no engine mutex is taken and no device call is made, so a caller thread never waits behind a running
+   pf_online_get_results.  pf_online_get_results pops one chunk per stream that has one, uploads the samples of all of them in
+   ONE staged copy and takes them to the encoder's input on the device in two launches for all streams together: kaldi fbank (the
+   fbank kernel over the chunks as utterances of their own: the rows of pf_fbank on those 9600 samples, bit for bit at dither 0)
+   and k_frontend_stream.hip (profile class "online_frontend"): the splice with the two rows the stream's previous chunk left, LFR 7 / 6, CMVN, the sqrt(512) scale, the position term (fp64 sin / cos on the device:
+   a feature may differ from the host path's by one fp32 place where the two libraries round differently; none did in the tests)
+   and the ten-row feature cache, which lives in the stream's slot of a device buffer with the carried rows and start_idx.  The
+   chunk step then runs from that buffer.  Tokens, Text and TokenInfo are those of the host front-end.  dither != 0: the draw is
+   the fbank kernel's for (the launch's seed, the frame's index in the launch), not the one the host path makes chunk by chunk; like
+   that one it reproduces no other run's rows.
+   Requires pf_online_recognizer_set_token_info(r, 1).  PF_ERR_UNSUPPORTED: token info off; endpointing on (the detector takes
+   host fbank rows at add_samples; bringing it onto this path is a follow-up); a live stream has already taken audio; snip_edges;
+   a chunk length other than 60 frames; a geometry other than 80 mels with LFR 7 / 6.  While the mode is on,
+   pf_online_recognizer_set_endpoint and pf_online_recognizer_set_token_info(r, 0) are refused with PF_ERR_UNSUPPORTED. */
+int pf_online_recognizer_set_device_frontend(pf_online_recognizer* r, int32_t on);
 /* ---- Streaming punctuation on the recogniser (additions to ABI 6; see "Punctuation, streaming"; opt-in: without
    pf_online_recognizer_set_punc_model nothing of it is launched, allocated or changed) ----
    pf_online_recognizer_set_punc_model: pfw_path = a causal `.pfw` of kind "cttransformer", loaded once and attached to the
@@ -1909,6 +1927,24 @@ int pf_host_online_cif_step(void* state, const float* hiddens, const float* alph
 int pf_op_online_cif_step(pf_engine* e, void* states, const float* enc, const float* alphas, const int32_t* reset, int32_t B, int32_t Tc,
                           int32_t D, float threshold, int32_t lo, int32_t hi, float* fired, int32_t* fire_entry, int32_t cap,
                           int32_t* counts);
+/* The streaming front-end behind the fbank (k_frontend_stream.hip), host statement and device op.  state: one stream's block of
+   pf_host_online_frontend_state_bytes(80, 560) bytes = carry [2, 80] fp32 (fbank rows 58 and 59 of the previous chunk) | cache
+   [10, 560] fp32 | start_idx, ten equal int32 copies padded to twelve cells | flags [4] int32 (cell 0 bit 0: the stream has
+   stepped once); zero-filled = a new stream.  The host step takes the chunk's 60 fbank rows fb_rows [60, 80] and shift / scale
+   [560] (both NULL: no CMVN): pad = [carried rows, on the first step fb[0] twice ; fb[0 .. 58]], LFR 7 / 6 without left context,
+   (x + shift) * scale rounded twice, (float)((double)v * sqrt(512)), the position term at start_idx; speech [20, 560] = [cache ;
+   new rows] with every exact 0 as -23.025850929940457f; the new rows become the cache, start_idx += 10.  reset != 0: cache zeros
+   and start_idx 0 before the step, the carried rows stay.  The op takes samples [B, 9600] instead of fbank rows and the engine's
+   own CMVN, for the B blocks slot[b] (distinct) of states [n_states, state_bytes], through the staging kit (the fbank launch, then ONE
+   launch for all B streams): speech
+   [B, 20, 560] must be written everywhere, the cells behind the blocks keep their bits.  The carried rows, start_idx and flags
+   are equal on both sides; a speech or cache cell may differ by one fp32 place (the fp64 sin / cos of two libraries).
+   PF_ERR_INVALID_ARG: null pointers, B <= 0, a slot outside [0, n_states) or twice; PF_ERR_UNSUPPORTED: an engine that is not
+   80 mels, LFR 7 / 6, 560 columns, snip_edges false. */
+int pf_host_online_frontend_state_bytes(int32_t n_mels, int32_t feat_dim, int64_t* bytes);
+int pf_host_online_frontend_step(void* state, const float* fb_rows, const float* shift, const float* scale, int32_t reset, float* speech);
+int pf_op_online_frontend_step(pf_engine* e, void* states, int32_t n_states, const int32_t* slot, const float* samples,
+                               const int32_t* reset, int32_t B, float* speech);
 int pf_host_online_decode(const char* const* tokens, int32_t n_tokens, const int64_t* ids, int32_t n_ids, char* out,
                           int32_t cap);
 
