@@ -241,10 +241,12 @@ SIGNATURES = {
     "pf_engine_set_spk_model": (C.c_int, [_vp, _vp]),
     "pf_host_spk_windows": (C.c_int, [_i32, C.c_int32, _P(PfSpkConfig), _i32, C.c_int32, _i32, _i32]),
     "pf_host_spk_cluster": (C.c_int, [_f, C.c_int32, _P(PfSpkConfig), _i32, _i32]),
+    "pf_host_spk_cluster_trace": (C.c_int, [_f, C.c_int32, _P(PfSpkConfig), _i32, _i32, _i32, _P(C.c_double)]),
     "pf_host_spk_segment_labels": (C.c_int, [_i32, C.c_int32, _i32, _i32, C.c_int32, _i32]),
     "pf_host_spk_centroids": (C.c_int, [_f, _i32, C.c_int32, C.c_int32, C.c_int32, _f]),
     "pf_op_spk_embed": (C.c_int, [_vp, _f, _i32, C.c_int32, C.c_int32, _f, _f]),
     "pf_op_spk_affinity": (C.c_int, [_vp, _f, _i32, C.c_int32, C.c_int32, _f]),
+    "pf_op_spk_cluster": (C.c_int, [_vp, _f, _i32, C.c_int32, _P(PfSpkConfig), _i32, _i32, _i32, _P(C.c_double)]),
     "pf_host_punc_words": (C.c_int, [_vp, C.c_char_p, _i32, _i32, _i32, C.c_int32, _i32]),
     "pf_host_punc_logits": (C.c_int, [_vp, _i32, C.c_int32, _P(C.c_double)]),
     "pf_host_punc_cut": (C.c_int, [_vp, _i32, C.c_int32, C.c_int32, _i32]),
@@ -335,6 +337,7 @@ SIGNATURES = {
     "pf_recognizer_set_vad_model": (C.c_int, [_vp, C.c_char_p]),
     "pf_recognizer_set_punc_model": (C.c_int, [_vp, C.c_char_p]),
     "pf_recognizer_set_spk_model": (C.c_int, [_vp, C.c_char_p, _P(PfSpkConfig)]),
+    "pf_recognizer_set_spk_cluster": (C.c_int, [_vp, C.c_int32]),
     "pf_stream_num_speakers": (C.c_int, [_vp, _i32]),
     "pf_stream_segment_speaker": (C.c_int, [_vp, C.c_int32, _i32]),
     "pf_stream_speaker_centroid": (C.c_int, [_vp, C.c_int32, _f, C.c_int32, _i32]),

@@ -1160,6 +1160,16 @@ int pf_host_spk_cluster(const float* S, int32_t N, const pf_spk_config* cfg, int
   return PF_OK;
   PF_CATCH
 }
+int pf_host_spk_cluster_trace(const float* S, int32_t N, const pf_spk_config* cfg, int32_t* labels, int32_t* n_speakers, int32_t* merges,
+                              double* heights) {
+  PF_TRY
+  PF_CHECK(N >= 0 && N <= PF_SPK_MAX_WINDOWS, PF_ERR_INVALID_ARG, "spk_cluster: N outside 0 .. PF_SPK_MAX_WINDOWS");
+  if (N > 0) { NEED(S); NEED(labels); }
+  const pf_spk_config c = spk_cfg_or_default(cfg);
+  host_spk_cluster(S, N, c, labels, n_speakers, merges, heights);
+  return PF_OK;
+  PF_CATCH
+}
 int pf_host_spk_segment_labels(const int32_t* seg, int32_t n_seg, const int32_t* win_seg, const int32_t* win_label, int32_t N,
                                int32_t* out) {
   PF_TRY
@@ -1204,6 +1214,25 @@ int pf_op_spk_affinity(pf_engine* h, const float* emb, const int32_t* n, int32_t
   if (rows > 0) { NEED(emb); NEED(out); }
   std::lock_guard<std::mutex> lk(e->mutex());
   e->op_spk_affinity(emb, n, S, E_, out);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_op_spk_cluster(pf_engine* h, const float* S, const int32_t* n, int32_t n_streams, const pf_spk_config* cfg, int32_t* labels,
+                      int32_t* n_speakers, int32_t* merges, double* heights) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  PF_CHECK(n_streams >= 0 && n_streams <= 65535, PF_ERR_INVALID_ARG, "spk_cluster: n_streams outside 0 .. 65535");
+  if (n_streams > 0) { NEED(n); NEED(n_speakers); }
+  int64_t rows = 0;
+  for (int s = 0; s < n_streams; ++s) {
+    PF_CHECK(n[s] >= 0 && n[s] <= PF_SPK_MAX_WINDOWS, PF_ERR_INVALID_ARG, "spk_cluster: a stream outside 0 .. PF_SPK_MAX_WINDOWS windows");
+    rows += n[s];
+  }
+  if (rows > 0) { NEED(S); NEED(labels); }
+  const pf_spk_config c = spk_cfg_or_default(cfg);
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->op_spk_cluster(S, n, n_streams, c, labels, n_speakers, merges, heights);
   return PF_OK;
   PF_CATCH
 }
@@ -2379,6 +2408,14 @@ int pf_recognizer_set_spk_model(pf_recognizer* h, const char* pfw_path, const pf
   std::shared_ptr<Recognizer> r = R(h);
   PF_CHECK(!r->disposed(), PF_ERR_DISPOSED, "OfflineRecognizer");
   r->SetSpkModel(pfw_path ? pfw_path : "", cfg);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_recognizer_set_spk_cluster(pf_recognizer* h, int32_t on_device) {
+  PF_TRY
+  std::shared_ptr<Recognizer> r = R(h);
+  PF_CHECK(!r->disposed(), PF_ERR_DISPOSED, "OfflineRecognizer");
+  r->SetSpkCluster(on_device != 0);
   return PF_OK;
   PF_CATCH
 }

@@ -318,9 +318,18 @@ class Engine {
   // 150 frames at the released dimensions, 300 of 512), and computes one cosine block per utterance in one launch:
   // emb [N, embedding], aff = the concatenated [n, n] blocks.
   static constexpr size_t kSpkScratchBudget = (size_t)2 << 30;
-  void spk_staged(const int32_t* win, int N, const int32_t* n_utt, float* emb, float* aff);
+  // cluster (optional): the clustering runs on the device too (k_spk_cluster.hip, behind the affinity launch on the same stream,
+  // its work matrices in the forward's dead scratch): labels [N] and n_speakers [st_B] come down and aff (may be null) does not.
+  void spk_staged(const int32_t* win, int N, const int32_t* n_utt, float* emb, float* aff, const pf_spk_config* cluster = nullptr,
+                  int32_t* labels = nullptr, int32_t* n_speakers = nullptr);
   // the cosine blocks of S streams of n[s] embeddings (host arrays in and out; one launch of class "spk"; needs no model)
   void op_spk_affinity(const float* emb, const int32_t* n, int S, int E, float* out);
+  // host_spk_cluster on the device over the concatenated [n_s, n_s] blocks of `streams` streams (host arrays in and out, through
+  // op_stage.h; needs no model): labels [sum n], n_speakers [streams], and optionally the trace, merges [sum max(n - 1, 0), 2] /
+  // heights.  Class "spk": two launches per group of streams whose fp64 work matrices fit kSpkClusterBudget bytes.
+  static constexpr size_t kSpkClusterBudget = (size_t)2 << 30;
+  void op_spk_cluster(const float* S, const int32_t* n, int streams, const pf_spk_config& c, int32_t* labels, int32_t* n_speakers,
+                      int32_t* merges, double* heights);
   void op_vad_segments(const int32_t* levels, const int32_t* T, int B, int ld, int n_mels, const pf_vad_config* cfg, int32_t* seg,
                        int cap, int32_t* n);
   // the streaming endpoint kernel (k_endpoint.hip) on caller state blocks and levels: ONE launch of class "endpoint" over B
@@ -770,6 +779,11 @@ class Engine {
   void run_spk(const float* rows_dev, const int32_t* T_dev, const int64_t* toff_dev, const int64_t* tpoff_dev, const int64_t* xoff_dev, int B,
                int Tmax, int64_t total, int64_t totalp, char* scratch, float* emb_dev, float* frames_dev);
   static size_t spk_scratch_bytes(const SpkModel& m, int64_t total, int64_t totalp);
+  // the clustering launches over blocks that are on the device: the plan's groups in order, two launches each.  off_dev: the
+  // plan's table; sim: plan.sim_bytes bytes, reused by every group (the groups run in order on stream_)
+  void run_spk_cluster(const struct SpkClusterPlan& plan, const pf_spk_config& c, const float* S_dev, const int32_t* n_dev,
+                       const int64_t* off_dev, double* sim, int32_t* nn0, double* bv0, int32_t* labels_dev, int32_t* n_speakers_dev,
+                       int32_t* merges_dev, double* heights_dev);
   void run_punc(const int32_t* ids, const int64_t* off, const int32_t* last, int B, float* logits, float* x0, int32_t* p, int32_t* cut);
   void run_vadnet_stream(char* states_dev, const int32_t* slot_dev, const float* rows_dev, const int32_t* off_dev, int64_t ldx,
                          const int32_t* n_new_dev, const int32_t* flush_dev, int B, float* logits_dev, int32_t* levels_dev, int64_t cap,

@@ -733,7 +733,8 @@ void Engine::op_spk_embed(const float* rows, const int32_t* T, int B, int n_mels
   PF_HIP(hipStreamSynchronize(stream_));                          // (`off` and T are read by their copies until then)
 }
 
-void Engine::spk_staged(const int32_t* win, int N, const int32_t* n_utt, float* emb, float* aff) {
+void Engine::spk_staged(const int32_t* win, int N, const int32_t* n_utt, float* emb, float* aff, const pf_spk_config* cluster,
+                        int32_t* labels, int32_t* n_speakers) {
   PF_CHECK(spk_ != nullptr, PF_ERR_INVALID_ARG, "spk_staged: no model is attached");
   const SpkModel& m = *spk_;
   const int B = st_B_, E = m.embedding;
@@ -784,10 +785,22 @@ void Engine::spk_staged(const int32_t* win, int N, const int32_t* n_utt, float* 
   const int64_t cells = aoff[2 * (size_t)B + 1];
   size_t at = 0;
   auto take = [&](size_t bytes) { const size_t a0 = at; at += (size_t)round_up((int64_t)bytes + 16, 256); return a0; };
+  // with the clustering on the device: its tables and results, and its work matrices in the scratch the forwards have left
+  SpkClusterPlan plan;
+  if (cluster) {
+    PF_CHECK(labels && n_speakers, PF_ERR_INVALID_ARG, "spk_staged: the device clustering needs labels and n_speakers");
+    plan = spk_cluster_plan(n_utt, B, kSpkClusterBudget);
+  }
   const size_t o_off = take(off.size() * 8), o_T = take((size_t)N * 4), o_aoff = take(aoff.size() * 8), o_emb = take((size_t)N * E * 4),
-               o_aff = take((size_t)cells * 4), o_scr = take(scratch);
+               o_aff = take((size_t)cells * 4), o_coff = take(plan.off.size() * 8), o_n = take(cluster ? (size_t)B * 4 : 0),
+               o_nn = take(cluster ? (size_t)N * 4 : 0), o_bv = take(cluster ? (size_t)N * 8 : 0), o_lab = take(cluster ? (size_t)N * 4 : 0),
+               o_nsp = take(cluster ? (size_t)B * 4 : 0), o_scr = take(std::max(scratch, plan.sim_bytes));
   ensure(ws_spk_, at);
   char* ws = (char*)ws_spk_.p;
+  if (cluster) {
+    PF_HIP(hipMemcpyAsync(ws + o_coff, plan.off.data(), plan.off.size() * 8, hipMemcpyHostToDevice, stream_));
+    PF_HIP(hipMemcpyAsync(ws + o_n, n_utt, (size_t)B * 4, hipMemcpyHostToDevice, stream_));
+  }
   PF_HIP(hipMemcpyAsync(ws + o_off, off.data(), off.size() * 8, hipMemcpyHostToDevice, stream_));
   PF_HIP(hipMemcpyAsync(ws + o_T, T.data(), (size_t)N * 4, hipMemcpyHostToDevice, stream_));
   PF_HIP(hipMemcpyAsync(ws + o_aoff, aoff.data(), aoff.size() * 8, hipMemcpyHostToDevice, stream_));
@@ -805,7 +818,13 @@ void Engine::spk_staged(const int32_t* win, int N, const int32_t* n_utt, float* 
     prof_begin("spk", 6.0 * E * (double)cells);
     launch_spk_affinity(stream_, a);
     prof_end("spk");
-    PF_HIP(hipMemcpyAsync(aff, ws + o_aff, (size_t)cells * 4, hipMemcpyDeviceToHost, stream_));
+    if (!cluster) PF_HIP(hipMemcpyAsync(aff, ws + o_aff, (size_t)cells * 4, hipMemcpyDeviceToHost, stream_));
+  }
+  if (cluster) {
+    run_spk_cluster(plan, *cluster, (const float*)(ws + o_aff), (const int32_t*)(ws + o_n), (const int64_t*)(ws + o_coff), (double*)(ws + o_scr),
+                    (int32_t*)(ws + o_nn), (double*)(ws + o_bv), (int32_t*)(ws + o_lab), (int32_t*)(ws + o_nsp), nullptr, nullptr);
+    PF_HIP(hipMemcpyAsync(labels, ws + o_lab, (size_t)N * 4, hipMemcpyDeviceToHost, stream_));
+    PF_HIP(hipMemcpyAsync(n_speakers, ws + o_nsp, (size_t)B * 4, hipMemcpyDeviceToHost, stream_));
   }
   PF_HIP(hipMemcpyAsync(emb, ws + o_emb, (size_t)N * E * 4, hipMemcpyDeviceToHost, stream_));
   PF_HIP(hipStreamSynchronize(stream_));                          // (the tables are read by their copies until then)
@@ -838,6 +857,74 @@ void Engine::op_spk_affinity(const float* emb, const int32_t* n, int S, int E, f
   prof_end("spk");
   PF_HIP(hipMemcpyAsync(out, ws + o_s, (size_t)cells * 4, hipMemcpyDeviceToHost, stream_));
   PF_HIP(hipStreamSynchronize(stream_));
+}
+
+// the clustering on the device (k_spk_cluster.hip): per group of the plan one prep and one merge launch, class "spk"
+void Engine::run_spk_cluster(const SpkClusterPlan& plan, const pf_spk_config& c, const float* S_dev, const int32_t* n_dev, const int64_t* off_dev,
+                             double* sim, int32_t* nn0, double* bv0, int32_t* labels_dev, int32_t* n_speakers_dev, int32_t* merges_dev,
+                             double* heights_dev) {
+  const size_t S1 = (size_t)plan.streams + 1;
+  for (size_t g = 0; g + 1 < plan.first.size(); ++g) {
+    const int s0 = plan.first[g], s1 = plan.first[g + 1];
+    SpkClusterLaunch a{};
+    a.S = S_dev; a.n = n_dev + s0; a.woff = off_dev + s0; a.soff = off_dev + S1 + s0; a.moff = off_dev + 2 * S1 + s0;
+    a.streams = s1 - s0;
+    for (int s = s0; s < s1; ++s) a.nmax = std::max(a.nmax, (int)(plan.woff()[s + 1] - plan.woff()[s]));
+    a.threshold = c.threshold; a.num_speakers = c.num_speakers; a.min_cluster = c.min_cluster;
+    a.sim = sim; a.sim_first = plan.soff()[s0]; a.nn0 = nn0; a.bv0 = bv0;
+    a.labels = labels_dev; a.n_speakers = n_speakers_dev + s0; a.merges = merges_dev; a.heights = heights_dev;
+    const double cells = (double)(plan.soff()[s1] - plan.soff()[s0]);
+    prof_begin("spk", cells);
+    launch_spk_cluster_prep(stream_, a);
+    prof_end("spk");
+    prof_begin("spk", 4.0 * cells);
+    launch_spk_cluster_merge(stream_, a);
+    prof_end("spk");
+  }
+}
+
+void Engine::op_spk_cluster(const float* S, const int32_t* n, int streams, const pf_spk_config& c, int32_t* labels, int32_t* n_speakers,
+                            int32_t* merges, double* heights) {
+  if (streams <= 0) return;
+  const SpkClusterPlan plan = spk_cluster_plan(n, streams, kSpkClusterBudget);
+  PF_HIP(hipSetDevice(device_));
+  constexpr size_t kBehind = 64;                                    // sentinel cells behind every output
+  const size_t W = (size_t)plan.windows(), M = (size_t)plan.merges();
+  StageCarve st;
+  const auto d_off = st.take<int64_t>(plan.off.size());
+  const auto d_n = st.take<int32_t>((size_t)streams);
+  const auto d_S = st.take<float>((size_t)plan.cells());
+  const auto d_nn = st.take<int32_t>(W);
+  const auto d_bv = st.take<double>(W);
+  const auto d_lab = st.take<uint32_t>(W + kBehind);
+  const auto d_nsp = st.take<uint32_t>((size_t)streams + kBehind);
+  const auto d_mer = st.take<uint32_t>(2 * M + kBehind);
+  const auto d_hei = st.take<uint32_t>(2 * M + kBehind);            // doubles, filled and checked as pairs of words
+  const auto d_sim = st.take<char>(plan.sim_bytes);
+  void* ws = op_ws(st);
+  upload(stream_, d_off(ws), plan.off.data(), plan.off.size());
+  upload(stream_, d_n(ws), n, (size_t)streams);
+  upload(stream_, d_S(ws), S, (size_t)plan.cells());
+  fill_sentinel(stream_, d_lab(ws), d_lab.count);
+  fill_sentinel(stream_, d_nsp(ws), d_nsp.count);
+  fill_sentinel(stream_, d_mer(ws), d_mer.count);
+  fill_sentinel(stream_, d_hei(ws), d_hei.count);
+  run_spk_cluster(plan, c, d_S(ws), d_n(ws), d_off(ws), (double*)d_sim(ws), d_nn(ws), d_bv(ws), (int32_t*)d_lab(ws), (int32_t*)d_nsp(ws),
+                  merges ? (int32_t*)d_mer(ws) : nullptr, heights ? (double*)d_hei(ws) : nullptr);
+  // the guard rule: every label, count and trace row written, nothing behind them (a height's word may be any pattern)
+  const std::vector<uint32_t> lab = check_guard<uint32_t>(stream_, "spk_cluster: labels", d_lab(ws), kSentinel32,
+                                                          result_geom((int64_t)d_lab.count, (int)W, 1, 1, (int64_t)W));
+  const std::vector<uint32_t> nsp = check_guard<uint32_t>(stream_, "spk_cluster: n_speakers", d_nsp(ws), kSentinel32,
+                                                          result_geom((int64_t)d_nsp.count, streams, 1, 1, streams));
+  const size_t Mw = merges ? 2 * M : 0, Hw = heights ? 2 * M : 0;
+  const std::vector<uint32_t> mer = check_guard<uint32_t>(stream_, "spk_cluster: merges", d_mer(ws), kSentinel32,
+                                                          result_geom((int64_t)d_mer.count, (int)Mw, 1, 1, (int64_t)Mw));
+  const std::vector<uint32_t> hei = check_guard<uint32_t>(stream_, "spk_cluster: heights", d_hei(ws), kSentinel32,
+                                                          result_geom((int64_t)d_hei.count, (int)Hw, 1, 1, (int64_t)Hw, false, false));
+  if (W) std::memcpy(labels, lab.data(), W * 4);
+  std::memcpy(n_speakers, nsp.data(), (size_t)streams * 4);
+  if (Mw) std::memcpy(merges, mer.data(), Mw * 4);
+  if (Hw) std::memcpy(heights, hei.data(), Hw * 4);
 }
 
 // ---- the CT-Transformer punctuation model (k_punc.hip; the launch plan is at the head of that file)

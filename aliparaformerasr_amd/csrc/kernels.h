@@ -699,5 +699,19 @@ void launch_spk_pool(hipStream_t s, const SpkPoolLaunch& a);
 // the cosine blocks of S streams: stream s holds n[s] = eoff[s + 1] - eoff[s] embeddings, its block starts at out + ooff[s]
 struct SpkAffinityLaunch { const float* emb; const int64_t* eoff; const int64_t* ooff; int S, E, nmax; float* out; };
 void launch_spk_affinity(hipStream_t s, const SpkAffinityLaunch& a);
+// the clustering of `streams` streams' cosine blocks (k_spk_cluster.hip: host_spk_cluster on the device).  Stream s holds n[s]
+// windows (0 .. PF_SPK_MAX_WINDOWS; nmax: the largest); its block is S + soff[s], its labels and its nn0 / bv0 slices start at
+// woff[s], its merge trace at moff[s] (max(n - 1, 0) rows per stream).  sim: the fp64 work matrices of these streams, stream
+// s's at sim + (soff[s] - sim_first).  prep fills sim, nn0, bv0; merge reads them and writes labels, n_speakers and, where
+// given, merges [.., 2] (unused rows -1) and heights (unused 0.0).
+struct SpkClusterLaunch {
+  const float* S; const int32_t* n; const int64_t* woff; const int64_t* soff; const int64_t* moff;
+  int streams, nmax;
+  float threshold; int num_speakers, min_cluster;
+  double* sim; int64_t sim_first; int32_t* nn0; double* bv0;
+  int32_t* labels; int32_t* n_speakers; int32_t* merges; double* heights;
+};
+void launch_spk_cluster_prep(hipStream_t s, const SpkClusterLaunch& a);
+void launch_spk_cluster_merge(hipStream_t s, const SpkClusterLaunch& a);
 
 }  // namespace pf

@@ -721,15 +721,18 @@ void Recognizer::label_speakers(Lease& lease, const std::vector<Stream*>& stream
     int64_t cells = 0;
     for (int k = 0; k < N; ++k) { w3[3 * (size_t)k] = win[4 * (size_t)k]; w3[3 * (size_t)k + 1] = win[4 * (size_t)k + 1]; w3[3 * (size_t)k + 2] = win[4 * (size_t)k + 2]; }
     for (int i = 0; i < B; ++i) cells += (int64_t)n_utt[(size_t)i] * n_utt[(size_t)i];
-    std::vector<float> emb((size_t)N * E), aff((size_t)cells);
-    if (N > 0) lease->spk_staged(w3.data(), N, n_utt.data(), emb.data(), aff.data());
+    const bool on_device = spk_cluster_dev_.load();
+    std::vector<float> emb((size_t)N * E), aff(on_device ? 0 : (size_t)cells);
+    std::vector<int32_t> dev_labels(on_device ? (size_t)N : 0), dev_k(on_device ? (size_t)B : 0, 0);
+    if (N > 0) lease->spk_staged(w3.data(), N, n_utt.data(), emb.data(), aff.data(), on_device ? &scfg : nullptr, dev_labels.data(), dev_k.data());
     size_t w0 = 0, a0 = 0;
     for (int i = 0; i < B; ++i) {
       Stream* s = streams[i];
       const int n = n_utt[(size_t)i];
       std::vector<int32_t> labels((size_t)n), wseg((size_t)n);
       int32_t K = 0;
-      host_spk_cluster(aff.data() + a0, n, scfg, labels.data(), &K);
+      if (on_device) { std::copy(dev_labels.begin() + (ptrdiff_t)w0, dev_labels.begin() + (ptrdiff_t)w0 + n, labels.begin()); K = dev_k[(size_t)i]; }
+      else host_spk_cluster(aff.data() + a0, n, scfg, labels.data(), &K);
       for (int k = 0; k < n; ++k) {
         wseg[(size_t)k] = win[4 * (w0 + (size_t)k) + 3];
         s->SpkWindows.push_back({10 * win[4 * (w0 + (size_t)k) + 1], 10 * win[4 * (w0 + (size_t)k) + 2], labels[(size_t)k]});

@@ -179,6 +179,10 @@ class Recognizer : public std::enable_shared_from_this<Recognizer> {
   // call's streams are planned, embedded and turned into one cosine block per stream on the device, each stream is clustered on
   // the host.  Text / Tokens / Timestamps / Scores / Segments / Punctuated / Sentences stay what they are without it.
   void SetSpkModel(const std::string& pfw_path, const pf_spk_config* cfg);
+  // where each stream is clustered: on the host (the default), or on the device behind the cosines (k_spk_cluster.hip: the same
+  // labels; the cosines are then not copied back).  A recogniser's setting, read at every GetResults: it holds for every engine
+  // of the pool, present and future, may come before or after SetSpkModel / SetVad and is inert without them.
+  void SetSpkCluster(bool on_device) { spk_cluster_dev_.store(on_device); }
   bool disposed() const { return disposed_.load(); }
   // engine 0 (nullptr once disposed): what pf_recognizer_engine hands out; callers lock engine->mutex() themselves
   std::shared_ptr<Engine> engine() { std::lock_guard<std::mutex> lk(mu_); return engines_.empty() ? nullptr : engines_[0]; }
@@ -238,6 +242,7 @@ class Recognizer : public std::enable_shared_from_this<Recognizer> {
   std::mutex spk_mu_;                                         // guards spk_model_ and spk_cfg_
   std::shared_ptr<const SpkModel> spk_model_;
   pf_spk_config spk_cfg_{};
+  std::atomic<bool> spk_cluster_dev_{false};
   std::mutex punc_mu_;                                        // guards punc_model_
   std::shared_ptr<const PuncModel> punc_model_;
   std::mutex vad_mu_;                                         // guards the five below

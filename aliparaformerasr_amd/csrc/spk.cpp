@@ -240,10 +240,14 @@ void host_spk_windows(const int32_t* seg, int32_t n_seg, const pf_spk_config& c,
   if (shift_used) *shift_used = (int32_t)std::min<int64_t>(shift, INT32_MAX);
 }
 
-void host_spk_cluster(const float* S, int32_t N, const pf_spk_config& c, int32_t* labels, int32_t* n_speakers) {
+void host_spk_cluster(const float* S, int32_t N, const pf_spk_config& c, int32_t* labels, int32_t* n_speakers, int32_t* merges,
+                      double* heights) {
   if (n_speakers) *n_speakers = 0;
   if (N <= 0) return;
   const size_t n = (size_t)N;
+  if (merges) std::fill(merges, merges + 2 * (n - 1), -1);              // the trace only records: no decision reads it
+  if (heights) std::fill(heights, heights + (n - 1), 0.0);
+  size_t n_merges = 0;
   std::vector<double> sim(n * n, 0.0);
   for (size_t i = 0; i < n; ++i)
     for (size_t j = i + 1; j < n; ++j) {
@@ -274,6 +278,9 @@ void host_spk_cluster(const float* S, int32_t N, const pf_spk_config& c, int32_t
     for (size_t a = 0; a < n; ++a)
       if (live[a] && nn[a] >= 0 && sim[a * n + (size_t)nn[a]] > best) { best = sim[a * n + (size_t)nn[a]]; i = a; j = (size_t)nn[a]; }
     if (c.num_speakers <= 0 && best < threshold) break;
+    if (merges) { merges[2 * n_merges] = (int32_t)i; merges[2 * n_merges + 1] = (int32_t)j; }
+    if (heights) heights[n_merges] = best;
+    ++n_merges;
     for (size_t k = 0; k < n; ++k) {
       if (!live[k] || k == i || k == j) continue;
       const double v = ((double)size[i] * sim[i * n + k] + (double)size[j] * sim[j * n + k]) / (double)(size[i] + size[j]);
@@ -317,6 +324,27 @@ void host_spk_cluster(const float* S, int32_t N, const pf_spk_config& c, int32_t
   for (size_t k = 0; k < alive.size(); ++k) label[(size_t)alive[k]] = (int32_t)k;
   for (size_t w = 0; w < n; ++w) labels[w] = label[(size_t)owner[w]];
   if (n_speakers) *n_speakers = (int32_t)alive.size();
+}
+
+SpkClusterPlan spk_cluster_plan(const int32_t* n, int streams, size_t budget) {
+  SpkClusterPlan p;
+  p.streams = std::max(streams, 0);
+  const size_t S = (size_t)p.streams;
+  p.off.assign(3 * (S + 1), 0);
+  size_t group = 0;                                                // bytes of the group that is open
+  for (size_t s = 0; s < S; ++s) {
+    PF_CHECK(n[s] >= 0 && n[s] <= PF_SPK_MAX_WINDOWS, PF_ERR_INVALID_ARG, "spk cluster: a stream of fewer than 0 or more than PF_SPK_MAX_WINDOWS windows");
+    const size_t bytes = (size_t)n[s] * (size_t)n[s] * sizeof(double);
+    if (p.first.empty() || group + bytes > budget || (int)s - p.first.back() >= 65535) { p.first.push_back((int)s); group = 0; }
+    group += bytes;
+    p.sim_bytes = std::max(p.sim_bytes, group);
+    p.off[s + 1] = p.off[s] + n[s];
+    p.off[S + 1 + s + 1] = p.off[S + 1 + s] + (int64_t)n[s] * n[s];
+    p.off[2 * (S + 1) + s + 1] = p.off[2 * (S + 1) + s] + std::max(n[s] - 1, 0);
+    p.nmax = std::max(p.nmax, (int)n[s]);
+  }
+  p.first.push_back(p.streams);
+  return p;
 }
 
 void host_spk_segment_labels(const int32_t* seg, int32_t n_seg, const int32_t* win_seg, const int32_t* win_label, int32_t N,

@@ -56,8 +56,27 @@ pf_spk_config spk_default();
 void spk_check_config(const pf_spk_config& c);                         // PF_ERR_INVALID_ARG on a value outside its range
 // the window plan of ONE stream: seg [n_seg, 2] frame pairs -> win [*, 3] (segment, begin, end), the shift used
 void host_spk_windows(const int32_t* seg, int32_t n_seg, const pf_spk_config& c, std::vector<int32_t>& win, int32_t* shift_used);
-// average-linkage agglomeration over S [N, N] fp32 (tests/spk_ref.py cluster) -> labels [N], the number of speakers
-void host_spk_cluster(const float* S, int32_t N, const pf_spk_config& c, int32_t* labels, int32_t* n_speakers);
+// average-linkage agglomeration over S [N, N] fp32 (tests/spk_ref.py cluster) -> labels [N], the number of speakers and, where
+// given, the trace: merges [max(N - 1, 0), 2] (i < j in the order they merged; unused rows -1) and the similarity each merged
+// at, heights [max(N - 1, 0)] (unused 0.0).  k_spk_cluster.hip is the same walk on the device.
+void host_spk_cluster(const float* S, int32_t N, const pf_spk_config& c, int32_t* labels, int32_t* n_speakers, int32_t* merges = nullptr,
+                      double* heights = nullptr);
+// where the device form of the clustering keeps what belongs to each of `streams` streams of n[s] windows, and how the streams
+// go into launches: consecutive streams whose fp64 work matrices (8 n^2 bytes each) fit `budget` bytes form a group, of at
+// least one stream and at most 65535
+struct SpkClusterPlan {
+  int streams = 0, nmax = 0;
+  std::vector<int64_t> off;                 // woff | soff | moff, [streams + 1] each: windows, cells, trace rows in front of a stream
+  std::vector<int> first;                   // every group's first stream, then `streams`
+  size_t sim_bytes = 0;                     // the largest group's work matrices
+  const int64_t* woff() const { return off.data(); }
+  const int64_t* soff() const { return off.data() + streams + 1; }
+  const int64_t* moff() const { return off.data() + 2 * ((size_t)streams + 1); }
+  int64_t windows() const { return woff()[streams]; }
+  int64_t cells() const { return soff()[streams]; }
+  int64_t merges() const { return moff()[streams]; }
+};
+SpkClusterPlan spk_cluster_plan(const int32_t* n, int streams, size_t budget);
 // the label per segment from its windows' (win_seg [N], win_label [N])
 void host_spk_segment_labels(const int32_t* seg, int32_t n_seg, const int32_t* win_seg, const int32_t* win_label, int32_t N,
                              int32_t* out);

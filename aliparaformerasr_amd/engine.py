@@ -593,6 +593,19 @@ def host_spk_cluster(S, cfg=None):
     return labels[: a.shape[0]].copy(), k.value
 
 
+def host_spk_cluster_trace(S, cfg=None):
+    """host_spk_cluster and the walk it took (pf_host_spk_cluster_trace): S [N, N] fp32 -> (labels [N] int32, speakers, merges
+    [max(N - 1, 0), 2] int32 with unused rows -1, heights [max(N - 1, 0)] float64 with unused 0.0)."""
+    a = _f32(S)
+    n = a.shape[0]
+    a = a.reshape(n, n) if a.size else a.reshape(0, 0)
+    labels, k = np.zeros(max(n, 1), np.int32), C.c_int32()
+    merges, heights = np.zeros((max(n - 1, 1), 2), np.int32), np.zeros(max(n - 1, 1), np.float64)
+    N.check(N.load().pf_host_spk_cluster_trace(_fp(a), n, _spk_cfg_ptr(cfg), _i32p(labels), k, _i32p(merges),
+                                               heights.ctypes.data_as(C.POINTER(C.c_double))))
+    return labels[:n].copy(), k.value, merges[: max(n - 1, 0)].copy(), heights[: max(n - 1, 0)].copy()
+
+
 def host_spk_segment_labels(segs, win_seg, win_label) -> np.ndarray:
     """The label of every segment from its windows' (pf_host_spk_segment_labels)."""
     s = np.ascontiguousarray(segs, dtype=np.int32).reshape(-1, 2)
@@ -1506,6 +1519,24 @@ class Engine:
         N.check(self._lib.pf_op_spk_affinity(self._h, _fp(x), _i32p(n), S, E_, _fp(out)))
         off = np.concatenate([[0], np.cumsum(cells)]).astype(np.int64)
         return [out[off[s]: off[s + 1]].reshape(int(n[s]), int(n[s])).copy() for s in range(S)]
+
+    def op_spk_cluster(self, S_list, cfg=None, want_trace=True) -> list:
+        """host_spk_cluster_trace on the device for every stream of S_list ([n_s, n_s] fp32 each) in ONE call
+        (pf_op_spk_cluster) -> per stream (labels, speakers, merges, heights); merges / heights are None without want_trace."""
+        arrs = [_f32(a).reshape(np.shape(a)[0], np.shape(a)[0]) for a in S_list]
+        S = len(arrs)
+        n = np.ascontiguousarray([a.shape[0] for a in arrs] + [0] * (S == 0), dtype=np.int32)
+        x = np.ascontiguousarray(np.concatenate([a.reshape(-1) for a in arrs])) if S and int(n.sum()) else np.zeros(1, np.float32)
+        woff = np.concatenate([[0], np.cumsum(n[:S])]).astype(np.int64)
+        moff = np.concatenate([[0], np.cumsum(np.maximum(n[:S] - 1, 0))]).astype(np.int64)
+        labels, k = np.zeros(max(int(woff[-1]), 1), np.int32), np.zeros(max(S, 1), np.int32)
+        merges, heights = np.zeros((max(int(moff[-1]), 1), 2), np.int32), np.zeros(max(int(moff[-1]), 1), np.float64)
+        N.check(self._lib.pf_op_spk_cluster(self._h, _fp(x), _i32p(n), S, _spk_cfg_ptr(cfg), _i32p(labels), _i32p(k),
+                                            _i32p(merges) if want_trace else None,
+                                            heights.ctypes.data_as(C.POINTER(C.c_double)) if want_trace else None))
+        return [(labels[woff[s]: woff[s + 1]].copy(), int(k[s]),
+                 merges[moff[s]: moff[s + 1]].copy() if want_trace else None,
+                 heights[moff[s]: moff[s + 1]].copy() if want_trace else None) for s in range(S)]
 
     def set_punc_model(self, model):
         """Attaches a PuncModel (pf_engine_set_punc_model); None detaches and frees what the attach and its runs allocated."""

@@ -1,7 +1,7 @@
 """Command-line harness mirroring AliParaformerAsr.Examples (`-type offline` and `-type online`).
 
     python -m aliparaformerasr_amd.examples -type offline -method batch -base <dir> -model <name> \
-        [-accuracy int8] [-threads 2] [-decode ctc|frames] [-intake host|device] [-nbest N [-topk K] [-beam W | -search W] [-hotboost S] [-lm FILE [-lmweight A] [-lmbonus B] [-lmeos]]] [-align FILE|beam] [-vad [key=value,...] [-vadmodel FILE] [-spk FILE [key=value,...]]] [-punc FILE] -files a.wav b.wav
+        [-accuracy int8] [-threads 2] [-decode ctc|frames] [-intake host|device] [-nbest N [-topk K] [-beam W | -search W] [-hotboost S] [-lm FILE [-lmweight A] [-lmbonus B] [-lmeos]]] [-align FILE|beam] [-vad [key=value,...] [-vadmodel FILE] [-spk FILE[,cluster=device] [key=value,...]]] [-punc FILE] -files a.wav b.wav
     python -m aliparaformerasr_amd.examples -type online -method one -base <dir> -model <name> [-endpoint [key=value,...] [-vadmodel FILE] [-secondpass <offline name>]] [-tokentimes [-devicefrontend]] [-puncstream FILE[,max_context=N]] -files a.wav
 
 Mirrors (file:line in /root/reference/AliParaformerAsr.Examples):
@@ -51,7 +51,8 @@ log-mel energy: FILE is a `.pfw` of kind fsmnvad (`python -m aliparaformerasr_am
 --mvn vad.mvn`); the model's default thresholds (floor_pct=-1, abs_level=9830; unvalidated too) apply unless keys are given.
 `-spk FILE [key=value,...]` (with `-vad`; OfflineRecognizer.SetSpeakerModel) says who speaks in each segment: FILE is a `.pfw` of
 kind campplus (`python -m aliparaformerasr_amd.convert campplus.bin out.pfw --kind campplus`); each segment line becomes
-`[begin-end ms] spkN text`.  Keys: the pf_spk_config fields (win, shift, min_frames, threshold, num_speakers, min_cluster).  The
+`[begin-end ms] spkN text`.  Keys: the pf_spk_config fields (win, shift, min_frames, threshold, num_speakers, min_cluster), and
+`cluster=device` (also as `FILE,cluster=device`; OfflineRecognizer.SetSpeakerClustering) to cluster on the GPU as well: the same lines.  The
 network and the thresholds are stated, not validated on a real model.
 `-punc FILE` (OfflineRecognizer.SetPuncModel) punctuates every result on the GPU with a CT-Transformer: FILE is a `.pfw` of kind
 cttransformer; under each result goes a `punctuated: ...` line and one `  [begin-end ms] sentence` line per sentence (without the
@@ -270,6 +271,20 @@ def parse_endpoint_option(text: str) -> dict:
 SPK_KEYS = ("win", "shift", "min_frames", "threshold", "num_speakers", "min_cluster")
 
 
+def split_spk_cluster(text: str):
+    """the `cluster=device|host` item of -spk's `key=value,...` apart from the pf_spk_config keys -> (the rest, "device" | "host" | None)"""
+    rest, where = [], None
+    for item in [x for x in text.split(",") if x]:
+        k, eq, v = item.partition("=")
+        if k.strip() != "cluster":
+            rest.append(item)
+            continue
+        where = v.strip()
+        if not eq or where not in ("device", "host"):
+            raise ValueError("The -spk value of cluster must be device or host")
+    return ",".join(rest), where
+
+
 def parse_spk_option(text: str) -> dict:
     """`key=value,...` of -spk -> {pf_spk_config fields}"""
     out = {}
@@ -351,6 +366,8 @@ def offline_recognizer(method="one", model="paraformer-seaco-large-zh-timestamp-
         rec.SetVad(vcfg, vad["batch_max"], vad["frame_budget"], vad["sep"])
     if spk:
         rec.SetSpeakerModel(spk["file"], spk["cfg"] or None)
+        if spk.get("cluster"):
+            rec.SetSpeakerClustering(spk["cluster"])
     if punc:
         rec.SetPuncModel(punc)
     targets = None
@@ -696,10 +713,17 @@ def parse_args(argv, env=None):
             i += 1
             if i >= len(argv) or argv[i].startswith("-"):
                 raise ValueError("-spk takes a .pfw file of kind campplus")
-            cfg["spk"] = {"file": argv[i], "cfg": {}}
+            path, comma, opts = argv[i].partition(",")                # FILE, FILE,key=value,... or FILE key=value,...
+            if not (comma and "=" in opts):
+                path, opts = argv[i], ""
+            cfg["spk"] = {"file": path, "cfg": {}}
             if i + 1 < len(argv) and not argv[i + 1].startswith("-") and "=" in argv[i + 1]:
                 i += 1
-                cfg["spk"]["cfg"] = parse_spk_option(argv[i])
+                opts = ",".join(x for x in (opts, argv[i]) if x)
+            opts, where = split_spk_cluster(opts)
+            cfg["spk"]["cfg"] = parse_spk_option(opts)
+            if where:
+                cfg["spk"]["cluster"] = where                      # (apart from the pf_spk_config keys; absent: the host)
         elif a == "-puncstream":
             i += 1
             if i >= len(argv) or argv[i].startswith("-"):

@@ -557,6 +557,14 @@ class OfflineRecognizer:
         from .engine import _spk_cfg_ptr
         _ck(self._lib.pf_recognizer_set_spk_model(self._h, None if pfwPath is None else str(pfwPath).encode("utf-8"), _spk_cfg_ptr(cfg)))
 
+    def SetSpeakerClustering(self, where: str) -> None:
+        """Where each stream's windows are clustered (pf_recognizer_set_spk_cluster): "host" (the default) or "device", the same
+        walk in double behind the cosines on the device, whose blocks are then not copied back.  The results are the same.  May
+        be set before or after SetSpeakerModel / SetVad and is inert without them."""
+        if where not in ("device", "host"):
+            raise ValueError('SetSpeakerClustering takes "device" or "host"')
+        _ck(self._lib.pf_recognizer_set_spk_cluster(self._h, 1 if where == "device" else 0))
+
     def SetVadModel(self, pfwPath) -> None:
         """The FSMN-VAD model score for SetVad's segmentation: a `.pfw` of kind "fsmnvad" (python -m aliparaformerasr_amd.convert
         ... --kind fsmnvad), loaded once and attached to every engine of the pool, present and future; None clears.  Inert

@@ -500,6 +500,15 @@ namespace AliParaformerAsr.Hip
             ParaformerHip.Check(ParaformerHip.pf_recognizer_set_spk_model(_r, pfwPath, ref c));
         }
 
+        /// <summary>Not in the reference: where each stream's windows are clustered (pf_recognizer_set_spk_cluster): "host" (the
+        /// default) or "device", the same walk in double behind the cosines, whose blocks are then not copied back.  The results are
+        /// the same.  Before or after SetSpeakerModel / SetVad; inert without them.</summary>
+        public void SetSpeakerClustering(string where)
+        {
+            if (where != "device" && where != "host") throw new ArgumentException("SetSpeakerClustering takes \"device\" or \"host\"", nameof(where));
+            ParaformerHip.Check(ParaformerHip.pf_recognizer_set_spk_cluster(_r, where == "device" ? 1 : 0));
+        }
+
         /// <summary>The stated defaults of the speaker labels (pf_spk_default).</summary>
         public static PfSpkConfig DefaultSpeaker()
         {

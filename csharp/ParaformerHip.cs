@@ -317,6 +317,7 @@ namespace AliParaformerAsr.Native
         [DllImport(Lib)] internal static extern int pf_spk_default(out PfSpkConfig cfg);
         [DllImport(Lib)] internal static extern int pf_engine_set_spk_model(IntPtr e, IntPtr m);
         [DllImport(Lib)] internal static extern int pf_recognizer_set_spk_model(IntPtr r, [MarshalAs(UnmanagedType.LPUTF8Str)] string? pfwPath, ref PfSpkConfig cfg);
+        [DllImport(Lib)] internal static extern int pf_recognizer_set_spk_cluster(IntPtr r, int onDevice);
         [DllImport(Lib)] internal static extern int pf_stream_num_speakers(IntPtr s, out int n);
         [DllImport(Lib)] internal static extern int pf_stream_segment_speaker(IntPtr s, int i, out int spk);
         [DllImport(Lib)] internal static extern int pf_stream_speaker_centroid(IntPtr s, int spk, [Out] float[]? centroid, int cap, out int e);

@@ -916,7 +916,8 @@ int pf_host_punc_stream_step(const pf_punc_model* m, void* state, const int32_t*
    WINDOWS of a segment of frames [b, e) under pf_spk_config: none below min_frames; [b, e) up to win; otherwise
    [b + k shift, + win) while they fit, plus [e - win, e) if the last does not end at e.  A stream with more than
    PF_SPK_MAX_WINDOWS windows doubles its shift until it fits.
-   CLUSTERING (host, double, deterministic): average linkage over the cosines, cluster similarity updated as
+   CLUSTERING (host, double, deterministic; pf_recognizer_set_spk_cluster moves the same walk onto the device, in double, with
+   the same labels, merge order and merge heights: csrc/k_spk_cluster.hip): average linkage over the cosines, cluster similarity updated as
    (nA sAC + nB sBC) / (nA + nB); the pair of largest similarity merges, ties to the smallest first then second index (a
    cluster's index is its earliest window); it stops when the largest similarity is below `threshold`, or, with
    num_speakers > 0, when that many clusters are left (the threshold is then not consulted).  Without num_speakers every cluster
@@ -958,12 +959,17 @@ int pf_engine_set_spk_model(pf_engine* e, const pf_spk_model* m);
    0 to learn *n; PF_ERR_CAPACITY when cap < *n), *shift_used (optional).
    pf_host_spk_cluster: S [N, N] fp32 (its upper triangle is read; a value that is not finite counts as -2) -> labels [N],
    *n_speakers.
+   pf_host_spk_cluster_trace: the same, and the walk it took (each optional): merges [max(N - 1, 0), 2] = the pairs (i < j) in the
+   order they merged, unused rows -1; heights [max(N - 1, 0)] = the similarity each pair merged at, unused 0.0.  The trace only
+   records: labels and *n_speakers are pf_host_spk_cluster's.
    pf_host_spk_segment_labels: seg [n_seg, 2], the windows' segment and label [N] -> out [n_seg].
    pf_host_spk_centroids: emb [N, E], labels [N] -> out [K, E]: the L2-normalised mean of each speaker's L2-normalised
    embeddings (zeros for a speaker without a window). */
 int pf_host_spk_windows(const int32_t* seg, int32_t n_seg, const pf_spk_config* cfg, int32_t* win, int32_t cap, int32_t* n,
                         int32_t* shift_used);
 int pf_host_spk_cluster(const float* S, int32_t N, const pf_spk_config* cfg, int32_t* labels, int32_t* n_speakers);
+int pf_host_spk_cluster_trace(const float* S, int32_t N, const pf_spk_config* cfg, int32_t* labels, int32_t* n_speakers, int32_t* merges,
+                              double* heights);
 int pf_host_spk_segment_labels(const int32_t* seg, int32_t n_seg, const int32_t* win_seg, const int32_t* win_label, int32_t N,
                                int32_t* out);
 int pf_host_spk_centroids(const float* emb, const int32_t* labels, int32_t N, int32_t E, int32_t K, float* out);
@@ -1100,7 +1106,15 @@ int pf_op_punc_stream_step(pf_engine* e, void* states, const int32_t* ids, const
    what else is in the call.
    pf_op_spk_affinity: emb = the concatenated embeddings of S streams, n [S] each, E wide -> out = the concatenated [n_s, n_s]
    cosine blocks, fp32 in a fixed order of summation (a zero embedding has cosine 0 with everything); one launch of class
-   "spk".  Needs no model. */
+   "spk".  Needs no model.
+   pf_op_spk_cluster: pf_host_spk_cluster_trace on the device (k_spk_cluster.hip), for n_streams streams in one call: S = the
+   concatenated [n_s, n_s] fp32 blocks, n [n_streams] (each 0 .. PF_SPK_MAX_WINDOWS, else PF_ERR_INVALID_ARG), cfg as
+   pf_host_spk_cluster (NULL: the defaults) -> labels [sum n_s], n_speakers [n_streams] and, each optional, merges
+   [sum max(n_s - 1, 0), 2] and heights [sum max(n_s - 1, 0)], stream after stream.  Labels, counts and merges equal the host's;
+   the heights are bit for bit the host's doubles.  A stream's result does not depend on what else is in the call.  Class "spk":
+   two launches per group of consecutive streams whose fp64 work matrices (8 n_s^2 bytes each) fit 2 GiB.  Needs no model. */
+int pf_op_spk_cluster(pf_engine* e, const float* S, const int32_t* n, int32_t n_streams, const pf_spk_config* cfg, int32_t* labels,
+                      int32_t* n_speakers, int32_t* merges, double* heights);
 int pf_op_spk_embed(pf_engine* e, const float* rows, const int32_t* T, int32_t B, int32_t n_mels, float* emb, float* frames);
 int pf_op_spk_affinity(pf_engine* e, const float* emb, const int32_t* n, int32_t S, int32_t E, float* out);
 /* exactly the pipeline's top-k kernel (k_topk.hip) on the values as given: x [rows, ld] (ld >= V; nothing at or beyond V is
@@ -1679,8 +1693,14 @@ int pf_recognizer_set_punc_model(pf_recognizer* r, const char* pfw_path);
    pf_stream_num_speakers; pf_stream_segment_speaker: the label of segment i (as pf_stream_segment counts them; -1: the stream
    has no window at all); pf_stream_speaker_centroid: out [cap >= E] = speaker spk's centroid, the L2-normalised mean of its
    windows' L2-normalised embeddings, for matching against enrolled voices (*E optional; out NULL with cap 0 to learn it);
-   pf_stream_spk_window: window i in ms and its label. */
+   pf_stream_spk_window: window i in ms and its label.
+   pf_recognizer_set_spk_cluster: on_device != 0 clusters each stream on the device, behind the cosines on the same HIP stream
+   (two more launches of class "spk" per call while the call's work matrices fit 2 GiB); labels [N] and the speaker counts come
+   back and the cosine blocks do not.  0 (the default): on the host.  Every result is the same either way.  Holds for every
+   engine of the pool, present and future; may come before or after pf_recognizer_set_spk_model / pf_recognizer_set_vad and is
+   inert without them. */
 int pf_recognizer_set_spk_model(pf_recognizer* r, const char* pfw_path, const pf_spk_config* cfg);
+int pf_recognizer_set_spk_cluster(pf_recognizer* r, int32_t on_device);
 int pf_stream_num_speakers(pf_stream* s, int32_t* n);
 int pf_stream_segment_speaker(pf_stream* s, int32_t i, int32_t* spk);
 int pf_stream_speaker_centroid(pf_stream* s, int32_t spk, float* out, int32_t cap, int32_t* E);
