@@ -42,6 +42,8 @@ PF_NBEST_MAX = 64
 # PCM intake (pf_pcm_format, pf_pcm_desc.flags)
 PF_PCM_U8, PF_PCM_S16, PF_PCM_S24, PF_PCM_S32, PF_PCM_F32, PF_PCM_F64, PF_PCM_ALAW, PF_PCM_MULAW = range(1, 9)
 PF_PCM_DOWNMIX_ALWAYS = 1
+PF_PCM_RESAMPLE_SINC = 2          # the band-limited polyphase resampler instead of the linear rule (inert at the engine's rate)
+PF_RESAMPLE_TILE = 1024           # outputs per tile of its kernel
 # name -> (pf_pcm_format, bytes per value, numpy dtype a caller's array must have; 24-bit values travel as bytes)
 PCM_FORMATS = {"u8": (PF_PCM_U8, 1, "u1"), "s16": (PF_PCM_S16, 2, "<i2"), "s24": (PF_PCM_S24, 3, "u1"),
                "s32": (PF_PCM_S32, 4, "<i4"), "f32": (PF_PCM_F32, 4, "<f4"), "f64": (PF_PCM_F64, 8, "<f8"),
@@ -51,6 +53,20 @@ PCM_FORMATS = {"u8": (PF_PCM_U8, 1, "u1"), "s16": (PF_PCM_S16, 2, "<i2"), "s24":
 class PfPcmDesc(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("format", C.c_int32), ("sample_rate", C.c_int32), ("channels", C.c_int32),
                 ("flags", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class PfResampleConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("zeros", C.c_int32), ("rolloff", C.c_double), ("beta", C.c_double)]
+
+
+def resample_config(zeros=None, rolloff=None, beta=None) -> "PfResampleConfig":
+    """pf_resample_default with the given fields replaced"""
+    c = PfResampleConfig()
+    check(load().pf_resample_default(C.byref(c)))
+    for k, v in (("zeros", zeros), ("rolloff", rolloff), ("beta", beta)):
+        if v is not None:
+            setattr(c, k, int(v) if k == "zeros" else float(v))
+    return c
 
 
 class PfVadConfig(C.Structure):
@@ -96,9 +112,38 @@ class PfAttnDesc(C.Structure):
 PF_ATTN_CANARY = 0x4D2B
 
 
-def pcm_desc(sample_rate, channels=1, format="s16", downmix_always=False) -> "PfPcmDesc":
+def pcm_desc(sample_rate, channels=1, format="s16", downmix_always=False, sinc=False) -> "PfPcmDesc":
     fmt = PCM_FORMATS[format][0] if isinstance(format, str) else int(format)
-    return PfPcmDesc(C.sizeof(PfPcmDesc), fmt, int(sample_rate), int(channels), PF_PCM_DOWNMIX_ALWAYS if downmix_always else 0)
+    flags = (PF_PCM_DOWNMIX_ALWAYS if downmix_always else 0) | (PF_PCM_RESAMPLE_SINC if sinc else 0)
+    return PfPcmDesc(C.sizeof(PfPcmDesc), fmt, int(sample_rate), int(channels), flags)
+
+
+def host_pcm_convert(data, desc, fs=16000, cfg=None):
+    """pf_host_pcm_convert: the PCM intake on the host -> float32 samples (what Engine.op_pcm_convert computes on the device)."""
+    import numpy as np
+    raw, nv = pcm_bytes(data, desc.format)
+    cp = None if cfg is None else C.byref(cfg)
+    n = C.c_int64()
+    ptr = raw.ctypes.data if raw.size else None
+    check(load().pf_host_pcm_convert(ptr, nv, C.byref(desc), fs, cp, None, 0, C.byref(n)))
+    out = np.zeros(max(n.value, 1), np.float32)
+    check(load().pf_host_pcm_convert(ptr, nv, C.byref(desc), fs, cp, out.ctypes.data_as(C.POINTER(C.c_float)), out.size, C.byref(n)))
+    return out[:n.value]
+
+
+def host_resample_sinc(samples, sr_in, sr_out, channels=1, cfg=None):
+    """pf_host_resample_sinc: float32 samples (interleaved when channels == 2) -> the band-limited resampler's output, the host
+    twin of the device kernel; cfg: a PfResampleConfig or None for the defaults."""
+    import numpy as np
+    x = np.ascontiguousarray(samples, np.float32).reshape(-1)
+    fp = C.POINTER(C.c_float)
+    cp = None if cfg is None else C.byref(cfg)
+    n = C.c_int64()
+    src = x.ctypes.data_as(fp) if x.size else None
+    check(load().pf_host_resample_sinc(src, x.size, sr_in, sr_out, channels, cp, None, 0, C.byref(n)))
+    out = np.zeros(max(n.value, 1), np.float32)
+    check(load().pf_host_resample_sinc(src, x.size, sr_in, sr_out, channels, cp, out.ctypes.data_as(fp), out.size, C.byref(n)))
+    return out[:n.value]
 
 
 def pcm_bytes(data, format="s16"):
@@ -272,6 +317,11 @@ SIGNATURES = {
     "pf_engine_set_hotwords": (C.c_int, [_vp, C.POINTER(C.c_int32), C.c_int32]),
     "pf_run_staged": (C.c_int, [_vp]),
     "pf_host_wav_read": (C.c_int, [C.c_char_p, _f, C.c_int64, _i64, _i32, _i32, C.POINTER(C.c_double)]),
+    "pf_resample_default": (C.c_int, [_P(PfResampleConfig)]),
+    "pf_engine_set_resample": (C.c_int, [_vp, _P(PfResampleConfig)]),
+    "pf_recognizer_set_resample": (C.c_int, [_vp, _P(PfResampleConfig)]),
+    "pf_host_resample_sinc": (C.c_int, [_f, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P(PfResampleConfig), _f, C.c_int64, _i64]),
+    "pf_host_pcm_convert": (C.c_int, [_vp, C.c_int64, _P(PfPcmDesc), C.c_int32, _P(PfResampleConfig), _f, C.c_int64, _i64]),
     "pf_host_resample": (C.c_int, [_f, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _f, C.c_int64, _i64]),
     "pf_host_is_audio": (C.c_int, [C.c_char_p, _i32]),
     "pf_group_create": (C.c_int, [_P(PfEngineConfig), _i32, C.c_int32, _P(_vp)]),

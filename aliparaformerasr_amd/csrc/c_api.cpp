@@ -1017,6 +1017,15 @@ int pf_host_vad_model_levels(const pf_vad_model* m, const float* rows, int64_t T
   return PF_OK;
   PF_CATCH
 }
+int pf_engine_set_resample(pf_engine* h, const pf_resample_config* cfg) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->set_resample(cfg);
+  return PF_OK;
+  PF_CATCH
+}
 int pf_engine_set_vad_model(pf_engine* h, const pf_vad_model* m) {
   PF_TRY
   std::shared_ptr<Engine> eh_ = E(h);
@@ -2411,6 +2420,14 @@ int pf_recognizer_set_spk_model(pf_recognizer* h, const char* pfw_path, const pf
   return PF_OK;
   PF_CATCH
 }
+int pf_recognizer_set_resample(pf_recognizer* h, const pf_resample_config* cfg) {
+  PF_TRY
+  std::shared_ptr<Recognizer> r = R(h);
+  PF_CHECK(!r->disposed(), PF_ERR_DISPOSED, "OfflineRecognizer");
+  r->SetResample(cfg);
+  return PF_OK;
+  PF_CATCH
+}
 int pf_recognizer_set_spk_cluster(pf_recognizer* h, int32_t on_device) {
   PF_TRY
   std::shared_ptr<Recognizer> r = R(h);
@@ -3322,6 +3339,45 @@ int pf_host_resample(const float* src, int64_t n, int32_t sr_in, int32_t sr_out,
   *n_out = (int64_t)v.size();
   if (out) {
     PF_CHECK(cap >= (int64_t)v.size(), PF_ERR_CAPACITY, "resample: output capacity too small");
+    if (!v.empty()) std::memcpy(out, v.data(), v.size() * 4);
+  }
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_resample_default(pf_resample_config* cfg) {
+  PF_TRY
+  NEED(cfg);
+  *cfg = resample_default();
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_host_resample_sinc(const float* src, int64_t n, int32_t sr_in, int32_t sr_out, int32_t channels, const pf_resample_config* cfg,
+                          float* out, int64_t cap, int64_t* n_out) {
+  PF_TRY
+  NEED(n_out);
+  PF_CHECK(n >= 0 && (n == 0 || src), PF_ERR_INVALID_ARG, "resample: bad arguments");
+  std::vector<float> in(src, src + n);
+  std::vector<float> v = resample_sinc(in, sr_in, sr_out, channels, resample_check(cfg));
+  *n_out = (int64_t)v.size();
+  if (out) {
+    PF_CHECK(cap >= (int64_t)v.size(), PF_ERR_CAPACITY, "resample: output capacity too small");
+    if (!v.empty()) std::memcpy(out, v.data(), v.size() * 4);
+  }
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_host_pcm_convert(const void* data, int64_t n_values, const pf_pcm_desc* desc, int32_t fs, const pf_resample_config* cfg, float* out,
+                        int64_t cap, int64_t* n_out) {
+  PF_TRY
+  NEED(desc); NEED(n_out);
+  PF_CHECK(data || n_values == 0, PF_ERR_INVALID_ARG, "pcm: null data");
+  const std::vector<float> v = pcm_to_samples(data, n_values, *desc, fs, cfg);
+  *n_out = (int64_t)v.size();
+  if (out) {
+    PF_CHECK(cap >= (int64_t)v.size(), PF_ERR_CAPACITY, "pcm_convert: output capacity too small");
     if (!v.empty()) std::memcpy(out, v.data(), v.size() * 4);
   }
   return PF_OK;

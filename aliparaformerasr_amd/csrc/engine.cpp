@@ -873,6 +873,7 @@ void Engine::stage_pcm(const void* const* data, const int64_t* n_values, const p
   st_t80_.resize(B);
   std::vector<int64_t> meta(3 * (size_t)(B + 1), 0);   // audio_off | n_samples | frame_off
   std::vector<PcmJob> jobs((size_t)B);
+  std::vector<int> sinc;                               // the utterances with PF_PCM_RESAMPLE_SINC: their own launch (k_resample.hip)
   std::vector<size_t> raw_bytes((size_t)B);
   int64_t tot = 0, frames = 0, raw_tot = 0, max_out = 0;
   int tmax = 0;
@@ -881,7 +882,10 @@ void Engine::stage_pcm(const void* const* data, const int64_t* n_values, const p
     const PcmPlan p = pcm_plan(d, fc_.fs, n_values[b]);
     PF_CHECK(data[b] || n_values[b] == 0, PF_ERR_INVALID_ARG, "pcm: null data");
     raw_bytes[b] = (size_t)n_values[b] * p.bytes_per_value;
-    jobs[b] = PcmJob{raw_tot, tot, p.n_mono, p.n_out, p.ratio, d.format, p.downmix ? 1 : 0, p.resample ? 1 : 0, 0};
+    // (a flagged utterance is an empty job of the linear launch: n_out 0 there)
+    jobs[b] = PcmJob{raw_tot, tot, p.n_mono, p.sinc ? 0 : p.n_out, p.ratio, d.format, p.downmix ? 1 : 0, p.resample ? 1 : 0, 0};
+    if (p.sinc) sinc.push_back(b);
+    else max_out = std::max(max_out, p.n_out);
     st_n_[b] = p.n_out;
     meta[b] = tot;
     meta[(B + 1) + b] = p.n_out;
@@ -891,13 +895,19 @@ void Engine::stage_pcm(const void* const* data, const int64_t* n_values, const p
     raw_tot += round_up((int64_t)raw_bytes[b], 16);
     frames += st_t80_[b];
     tmax = std::max(tmax, num_lfr_frames(p.n_out));
-    max_out = std::max(max_out, p.n_out);
   }
   meta[2 * (B + 1) + B] = frames;
   st_total_frames_ = frames;
   st_T_ = std::max(tmax, force_T);
   const size_t jobs_off = (size_t)round_up(std::max<int64_t>(raw_tot, 16), 256);
-  ensure(ws_pcm_, jobs_off + std::max<size_t>(jobs.size(), 1) * sizeof(PcmJob));
+  const size_t sinc_off = (size_t)round_up((int64_t)(jobs_off + std::max<size_t>(jobs.size(), 1) * sizeof(PcmJob)), 256);
+  std::vector<ResampleJob> sjobs;
+  for (int b : sinc) {
+    const pf_pcm_desc& d = descs[n_descs == 1 ? 0 : b];
+    sjobs.push_back(resample_.job(d.sample_rate, fc_.fs, d.format, jobs[b].downmix != 0, jobs[b].n_mono, st_n_[b], jobs[b].in_off,
+                                  jobs[b].out_off, (int)sinc.size()));
+  }
+  ensure(ws_pcm_, sinc.empty() ? jobs_off + std::max<size_t>(jobs.size(), 1) * sizeof(PcmJob) : sinc_off + sjobs.size() * sizeof(ResampleJob));
   ensure(ws_audio_, (size_t)std::max<int64_t>(tot, 1) * 4);
   ensure(ws_meta_, meta.size() * 8 + (size_t)B * 4 + 64);
   for (int b = 0; b < B; ++b)
@@ -907,6 +917,13 @@ void Engine::stage_pcm(const void* const* data, const int64_t* n_values, const p
   prof_begin("pcm_to_samples", 0);
   launch_pcm_to_samples(stream_, (const PcmJob*)((char*)ws_pcm_.p + jobs_off), B, max_out, ws_pcm_.p, (float*)ws_audio_.p);
   prof_end("pcm_to_samples");
+  if (!sjobs.empty()) {
+    PF_HIP(hipMemcpyAsync((char*)ws_pcm_.p + sinc_off, sjobs.data(), sjobs.size() * sizeof(ResampleJob), hipMemcpyHostToDevice, stream_));
+    prof_begin("resample_sinc", 0);
+    launch_resample_sinc(stream_, (const ResampleJob*)((char*)ws_pcm_.p + sinc_off), sjobs.data(), (int)sjobs.size(), ws_pcm_.p,
+                         (float*)ws_audio_.p);
+    prof_end("resample_sinc");
+  }
   PF_HIP(hipMemcpyAsync(ws_meta_.p, meta.data(), meta.size() * 8, hipMemcpyHostToDevice, stream_));
   PF_HIP(hipMemcpyAsync((char*)ws_meta_.p + meta.size() * 8, st_t80_.data(), (size_t)B * 4, hipMemcpyHostToDevice,
                         stream_));

@@ -172,6 +172,9 @@ class Engine {
   // writes the float samples into the layout stage_audio fills — everything behind it (frame counts, force_T, decode
   // lengths, the dither's per-sample counters) follows from the per-utterance n_out.  descs: n_descs == B, or 1 for all
   void stage_pcm(const void* const* data, const int64_t* n_values, const pf_pcm_desc* descs, int n_descs, int B, int force_T = 0);
+  // the filter shape of descriptors with PF_PCM_RESAMPLE_SINC (null = the defaults): those utterances of a stage_pcm batch go to
+  // ONE launch of k_resample.hip beside the others' pcm_to_samples launch; banks are built per rate on first use
+  void set_resample(const pf_resample_config* cfg) { PF_HIP(hipSetDevice(device_)); resample_.set(cfg); }
   void run_staged(bool want_logits);
   void fetch(pf_batch_out* out);
   void fetch_ids_device(int64_t* ids_dev, int l_cap, int32_t* L_out);   // last forward's ids -> caller's device buffer [B, l_cap], -1 padded
@@ -712,6 +715,7 @@ class Engine {
   float* small_ws_ = nullptr;        // short-input GEMM: split partials
   float* cif_conv_w32_ = nullptr;    // fp32 mode: the CIF conv as a [D][taps*D] GEMM operand
   float* ts_up_w32_ = nullptr;       // fp32 mode: the transposed conv as a [(j, out)][in] GEMM operand
+  ResampleBanks resample_;
   DevBuf ws_pcm_;                   // stage_pcm: the raw bytes of the batch | its PcmJob table
   DevBuf ws_audio_, ws_meta_, ws_fbank_, ws_speech_, ws_enc_, ws_dec_, ws_decffn_, ws_kv_, ws_pe_, ws_tmp_, ws_ts_, ws_seaco_, ws_seaco_in_, ws_seaco_hw_;
   bool seaco_hw_valid_ = false;     // ws_seaco_hw_ holds the embedder output / K,V rows of the CURRENT hot-word list (f16 path)

@@ -1,5 +1,7 @@
 // hostutil.cpp — see hostutil.h
 #include "hostutil.h"
+
+#include <numeric>
 #include "lm.h"
 #include "lm_dev.h"
 
@@ -397,14 +399,20 @@ PcmPlan pcm_plan(const pf_pcm_desc& d, int fs, int64_t n_values) {
     const double r = n_values == 0 ? 0.0 : std::nearbyint((double)p.n_mono / p.ratio);   // Math.Round: half to even
     PF_CHECK(r <= (double)INT32_MAX, PF_ERR_INVALID_ARG, "pcm: resampled length exceeds 2^31 - 1");
     p.n_out = std::max((int64_t)r, (int64_t)0);
+    if (d.flags & PF_PCM_RESAMPLE_SINC) {
+      const int g = std::gcd(d.sample_rate, fs);
+      p.sinc = true; p.L = fs / g; p.M = d.sample_rate / g;
+      PF_CHECK(p.L <= PF_RESAMPLE_MAX_PHASES, PF_ERR_UNSUPPORTED, "pcm: the band-limited resampler serves at most 1024 phases (fs / gcd(sample_rate, fs))");
+    }
   }
   return p;
 }
 
-std::vector<float> pcm_to_samples(const void* data, int64_t n_values, const pf_pcm_desc& d, int fs) {
+std::vector<float> pcm_to_samples(const void* data, int64_t n_values, const pf_pcm_desc& d, int fs, const pf_resample_config* rs) {
   const PcmPlan p = pcm_plan(d, fs, n_values);
   std::vector<float> x((size_t)n_values);
   pcm_decode(data, (size_t)n_values, d.format, x.data());
+  if (p.sinc) return resample_sinc(x, d.sample_rate, fs, d.channels, resample_check(rs));
   if (p.resample) return resample_linear(x, d.sample_rate, fs, d.channels);
   if (p.downmix) {
     std::vector<float> m((size_t)p.n_mono);
@@ -437,6 +445,95 @@ std::vector<float> resample_linear(const std::vector<float>& src, int sr_in, int
     if (idx >= last) { out[i] = m[last < 0 ? 0 : last]; continue; }
     out[i] = (float)((1 - fr) * m[idx] + fr * m[idx + 1]);
   }
+  return out;
+}
+
+// ---- band-limited resampling (hostutil.h; tests/resample_ref.py is the definition) ----
+pf_resample_config resample_default() {
+  pf_resample_config c{};
+  c.struct_size = (int32_t)sizeof(pf_resample_config); c.zeros = 24; c.rolloff = 0.94; c.beta = 10.0;
+  return c;
+}
+
+pf_resample_config resample_check(const pf_resample_config* cfg) {
+  if (!cfg) return resample_default();
+  PF_CHECK(cfg->struct_size == (int32_t)sizeof(pf_resample_config), PF_ERR_INVALID_ARG, "pf_resample_config.struct_size mismatch");
+  PF_CHECK(cfg->zeros >= 1 && cfg->zeros <= 64, PF_ERR_INVALID_ARG, "resample: zeros must be in [1, 64]");
+  PF_CHECK(std::isfinite(cfg->rolloff) && cfg->rolloff > 0.0 && cfg->rolloff <= 1.0, PF_ERR_INVALID_ARG, "resample: rolloff must be in (0, 1]");
+  PF_CHECK(std::isfinite(cfg->beta) && cfg->beta >= 0.0 && cfg->beta <= 20.0, PF_ERR_INVALID_ARG, "resample: beta must be in [0, 20]");
+  return *cfg;
+}
+
+// modified Bessel function of the first kind, order 0, by its power series: sum over m of ((x / 2)^m / m!)^2
+static double bessel_i0(double x) {
+  const double q = 0.25 * x * x;
+  double term = 1.0, sum = 1.0;
+  for (int m = 1; m < 500; ++m) {
+    term *= q / ((double)m * (double)m);
+    sum += term;
+    if (term < 1e-17 * sum) break;
+  }
+  return sum;
+}
+
+ResampleBank resample_bank(int sr_in, int sr_out, const pf_resample_config& cfg) {
+  PF_CHECK(sr_in > 0 && sr_out > 0, PF_ERR_INVALID_ARG, "resample: sample rates must be positive");
+  const int g = std::gcd(sr_in, sr_out);
+  ResampleBank b;
+  b.L = sr_out / g; b.M = sr_in / g;
+  PF_CHECK(b.L <= PF_RESAMPLE_MAX_PHASES, PF_ERR_UNSUPPORTED, "resample: more than 1024 phases");
+  const double pi = 3.14159265358979323846;
+  const double c = cfg.rolloff * std::min(1.0, (double)b.L / (double)b.M);
+  const double Hd = std::ceil((double)cfg.zeros / c);
+  PF_CHECK(2.0 * Hd <= (double)PF_RESAMPLE_MAX_TAPS, PF_ERR_UNSUPPORTED, "resample: more than 1024 taps");
+  b.H = (int)Hd; b.taps = 2 * b.H; b.stride = b.taps + 1;
+  b.h.assign((size_t)b.L * b.stride, 0.f);
+  const double i0b = bessel_i0(cfg.beta);
+  for (int p = 0; p < b.L; ++p)
+    for (int k = 0; k < b.taps; ++k) {
+      const double tau = (double)(k - (b.H - 1)) - (double)p / (double)b.L;
+      const double u = tau * c / (double)cfg.zeros;
+      double v = 0.0;
+      if (std::fabs(u) < 1.0) {
+        const double w = bessel_i0(cfg.beta * std::sqrt(1.0 - u * u)) / i0b;
+        const double x = c * tau;
+        v = c * (x == 0.0 ? 1.0 : std::sin(pi * x) / (pi * x)) * w;
+      }
+      b.h[(size_t)p * b.stride + k] = (float)v;
+    }
+  return b;
+}
+
+void resample_sinc_mono(const float* m, int64_t n_mono, const ResampleBank& bank, float* out, int64_t n_out) {
+  for (int64_t i = 0; i < n_out; ++i) {
+    const int64_t pos = i * (int64_t)bank.M, b = pos / bank.L;
+    const float* h = bank.h.data() + (size_t)(pos % bank.L) * bank.stride;
+    float acc = 0.0f;
+    for (int k = 0; k < bank.taps; ++k) {
+      const int64_t j = b - bank.H + 1 + k;
+      acc = std::fmaf(h[k], (j >= 0 && j < n_mono) ? m[j] : 0.0f, acc);     // the zero extension is multiplied in
+    }
+    out[i] = acc;
+  }
+}
+
+std::vector<float> resample_sinc(const std::vector<float>& src, int sr_in, int sr_out, int channels, const pf_resample_config& cfg) {
+  PF_CHECK(sr_in > 0 && sr_out > 0, PF_ERR_INVALID_ARG, "resample: sample rates must be positive");
+  PF_CHECK(channels == 1 || channels == 2, PF_ERR_INVALID_ARG, "resample: only 1 or 2 channels");
+  std::vector<float> mono_buf;
+  const std::vector<float>* mono = &src;
+  if (channels == 2) {
+    mono_buf.resize(src.size() / 2);
+    for (size_t i = 0; i < mono_buf.size(); ++i) mono_buf[i] = (src[2 * i] + src[2 * i + 1]) * 0.5f;
+    mono = &mono_buf;
+  }
+  if (sr_in == sr_out) return *mono;
+  const ResampleBank bank = resample_bank(sr_in, sr_out, cfg);
+  if (src.empty()) return {};
+  const double r = std::nearbyint((double)mono->size() / ((double)sr_in / sr_out));       // resample_linear's length
+  PF_CHECK(r <= (double)INT32_MAX, PF_ERR_INVALID_ARG, "resample: resampled length exceeds 2^31 - 1");
+  std::vector<float> out((size_t)std::max((int64_t)r, (int64_t)0));
+  resample_sinc_mono(mono->data(), (int64_t)mono->size(), bank, out.data(), (int64_t)out.size());
   return out;
 }
 

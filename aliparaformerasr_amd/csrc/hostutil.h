@@ -54,9 +54,25 @@ int pcm_bytes_per_value(int format);                           // throws PF_ERR_
 void pcm_decode(const void* data, size_t n_values, int format, float* out);
 // PCM intake (paraformer_hip.h "PCM intake"): what GetFileSample does to n_values interleaved values of `d` for an engine at
 // rate fs — validated (PF_ERR_INVALID_ARG) and sized here, carried out by pcm_to_samples on the host or k_pcm.hip on the device
-struct PcmPlan { bool resample = false, downmix = false; int bytes_per_value = 0; int64_t n_mono = 0, n_out = 0; double ratio = 1.0; };
+// sinc: PF_PCM_RESAMPLE_SINC is set and resample is (the band-limited rule below replaces the interpolation; L, M as there)
+struct PcmPlan { bool resample = false, downmix = false; int bytes_per_value = 0; int64_t n_mono = 0, n_out = 0; double ratio = 1.0;
+                 bool sinc = false; int L = 1, M = 1; };
 PcmPlan pcm_plan(const pf_pcm_desc& d, int fs, int64_t n_values);
-std::vector<float> pcm_to_samples(const void* data, int64_t n_values, const pf_pcm_desc& d, int fs);
+// rs: the filter shape of a flagged descriptor (null = the defaults)
+std::vector<float> pcm_to_samples(const void* data, int64_t n_values, const pf_pcm_desc& d, int fs, const pf_resample_config* rs = nullptr);
+// ---- band-limited resampling (paraformer_hip.h "PCM intake", PF_PCM_RESAMPLE_SINC; the definition is tests/resample_ref.py) ----
+// resample_default: the stated defaults.  resample_check: cfg (null = the defaults) validated (PF_ERR_INVALID_ARG), by value.
+pf_resample_config resample_default();
+pf_resample_config resample_check(const pf_resample_config* cfg);
+// The coefficient bank of one rate pair: h[p * stride + k], 0 <= p < L, 0 <= k < taps = 2 H, float64 rounded to float32 once;
+// stride is odd (taps + 1, the pad is 0).  The ONE builder: the host twin and the device read the same floats.
+// PF_ERR_UNSUPPORTED for L > PF_RESAMPLE_MAX_PHASES or taps > PF_RESAMPLE_MAX_TAPS.
+struct ResampleBank { int L = 1, M = 1, H = 0, taps = 0, stride = 1; std::vector<float> h; };
+ResampleBank resample_bank(int sr_in, int sr_out, const pf_resample_config& cfg);
+// out[i], 0 <= i < n_out, from the mono sequence m[0 .. n_mono): the fmaf chain of the definition
+void resample_sinc_mono(const float* m, int64_t n_mono, const ResampleBank& bank, float* out, int64_t n_out);
+// resample_linear's down-mix and length with that chain
+std::vector<float> resample_sinc(const std::vector<float>& src, int sr_in, int sr_out, int channels, const pf_resample_config& cfg);
 // Resample(sourceData, sourceSampleRate, targetSampleRate, sourceChannels) (:223-279): stereo -> mono
 // average first, then linear interpolation in double precision; target length = Round(n / ratio) (banker's)
 std::vector<float> resample_linear(const std::vector<float>& src, int sr_in, int sr_out, int channels);

@@ -518,6 +518,34 @@ void launch_pcm_to_samples(hipStream_t s, const PcmJob* jobs_dev, int B, int64_t
 // the same kernel for ONE utterance, its job passed in the kernel arguments (no table in device memory)
 void launch_pcm_to_samples_one(hipStream_t s, const PcmJob& job, const void* raw, float* samples);
 
+// ---------------------------------------------------------------- band-limited resampling (k_resample.hip) ------
+// PF_PCM_RESAMPLE_SINC (paraformer_hip.h "PCM intake"; the definition is tests/resample_ref.py, the host twin resample_sinc_mono).
+// One utterance of a resample launch: raw values as in PcmJob -> n_out samples, output i = the fmaf chain over row (i M) % L of
+// `bank` (device memory, row stride `stride` floats) and the mono samples from (i M) / L - H + 1 on.  tile: outputs per tile
+// (PF_RESAMPLE_TILE, halved until the tile's input span fits in_cap <= kResampleInCap floats); gx: workgroups that share the
+// utterance's tiles; bank_lds: the bank is copied into LDS behind the input tile, else read from global memory.
+constexpr int kResampleInCap = 16384;
+struct ResampleJob { int64_t in_off, out_off, n_mono, n_out; const float* bank;
+                     int32_t L, M, H, stride, format, downmix, tile, in_cap, gx, bank_lds; };
+void launch_resample_sinc(hipStream_t s, const ResampleJob* jobs_dev, const ResampleJob* jobs_host, int B, const void* raw, float* samples);
+void launch_resample_sinc_one(hipStream_t s, const ResampleJob& job, const void* raw, float* samples);
+// The filter shape and the device banks built from it, one per input rate, on first use; set() drops them.  Thread-safe.
+struct ResampleBankDev { int L = 1, M = 1, H = 0, stride = 1; float* dev = nullptr; };
+class ResampleBanks {
+ public:
+  ResampleBanks();
+  ~ResampleBanks();
+  void set(const pf_resample_config* cfg);                 // null = the defaults; validated before anything changes
+  pf_resample_config config();
+  // the job of one flagged utterance (gx is sized for `sharers` utterances in the launch)
+  ResampleJob job(int sample_rate, int fs, int format, bool downmix, int64_t n_mono, int64_t n_out, int64_t in_off, int64_t out_off,
+                  int sharers);
+  void clear();                                            // frees the device banks (the device must be current and idle on them)
+ private:
+  struct Impl;
+  Impl* d_;
+};
+
 // ---------------------------------------------------------------- voice-activity segmentation (k_vad.hip) ------
 // The detector of paraformer_hip.h "Voice-activity segmentation"; the definition in numpy is tests/vad_ref.py.
 // Step 1: rows [T, n_mels] fp32 (row stride n_mels) -> levels [T] int32.

@@ -319,7 +319,13 @@ void Stream::AddPcm(const void* data, int64_t n_values, const pf_pcm_desc& d) {
         ds = owner->audio_alloc((size_t)p.n_out * 4, &got);
         raw = owner->audio_alloc(rb, &got_raw);
         const PcmJob job{0, 0, p.n_mono, p.n_out, p.ratio, d.format, p.downmix ? 1 : 0, p.resample ? 1 : 0, 0};
-        const std::function<void(hipStream_t)> convert = [&](hipStream_t st) { launch_pcm_to_samples_one(st, job, raw, ds); };
+        ResampleJob sjob{};                                         // PF_PCM_RESAMPLE_SINC: the band-limited kernel instead
+        if (p.sinc) PF_HIP(hipSetDevice(owner->device_));
+        if (p.sinc) sjob = owner->resample_.job(d.sample_rate, fs, d.format, p.downmix, p.n_mono, p.n_out, 0, 0, 1);
+        const std::function<void(hipStream_t)> convert = [&](hipStream_t st) {
+          if (p.sinc) launch_resample_sinc_one(st, sjob, raw, ds);
+          else launch_pcm_to_samples_one(st, job, raw, ds);
+        };
         owner->upload(raw, (const float*)data, rb, &dev_ev, &dev_ev_pending, &convert);
       }
     } catch (const Error& ex) {
@@ -341,7 +347,9 @@ void Stream::AddPcm(const void* data, int64_t n_values, const pf_pcm_desc& d) {
     }
   }
   static const float kNone = 0.f;
-  const std::vector<float> x = pcm_to_samples(data, n_values, d, fs);
+  pf_resample_config rs = resample_default();
+  if (owner) rs = owner->resample_.config();
+  const std::vector<float> x = pcm_to_samples(data, n_values, d, fs, &rs);
   AddSamples(x.empty() ? &kNone : x.data(), (int64_t)x.size());
 }
 
@@ -464,7 +472,25 @@ std::shared_ptr<Engine> Recognizer::make_engine() {
   std::shared_ptr<const SpkModel> sm;
   { std::lock_guard<std::mutex> lk(spk_mu_); sm = spk_model_; }
   if (sm) e->set_spk_model(sm);
+  const pf_resample_config rs = resample_.config();
+  e->set_resample(&rs);
   return e;
+}
+
+void Recognizer::SetResample(const pf_resample_config* cfg) {
+  if (disposed_) throw Error(PF_ERR_DISPOSED, "OfflineRecognizer");
+  std::vector<std::shared_ptr<Engine>> es;
+  {
+    std::lock_guard<std::mutex> lk(mu_);
+    if (disposed_ || engines_.empty()) throw Error(PF_ERR_DISPOSED, "OfflineRecognizer");
+    es = engines_;
+  }
+  PF_HIP(hipSetDevice(device_));
+  resample_.set(cfg);                                                        // validates; engines made from here on copy it
+  for (auto& e : es) {
+    std::lock_guard<std::mutex> lk(e->mutex());
+    e->set_resample(cfg);
+  }
 }
 
 void Recognizer::SetDecode(int flags) {
@@ -1083,6 +1109,7 @@ void Recognizer::Dispose() {
 
 void Recognizer::free_device_side() {
   hipSetDevice(device_);
+  resample_.clear();
   for (auto& kv : audio_cache_)
     for (float* p : kv.second) hipFree(p);
   audio_cache_.clear();

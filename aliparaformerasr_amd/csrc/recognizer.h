@@ -183,6 +183,10 @@ class Recognizer : public std::enable_shared_from_this<Recognizer> {
   // labels; the cosines are then not copied back).  A recogniser's setting, read at every GetResults: it holds for every engine
   // of the pool, present and future, may come before or after SetSpkModel / SetVad and is inert without them.
   void SetSpkCluster(bool on_device) { spk_cluster_dev_.store(on_device); }
+  // The shape of the band-limited resampler (paraformer_hip.h "PCM intake", PF_PCM_RESAMPLE_SINC) for the AddPcm calls that follow —
+  // the device form launches k_resample.hip from the recognizer's own banks, the host form runs the host twin — and for every
+  // engine of the pool, present and future.  null = the defaults.  A descriptor's flag is what selects the filter.
+  void SetResample(const pf_resample_config* cfg);
   bool disposed() const { return disposed_.load(); }
   // engine 0 (nullptr once disposed): what pf_recognizer_engine hands out; callers lock engine->mutex() themselves
   std::shared_ptr<Engine> engine() { std::lock_guard<std::mutex> lk(mu_); return engines_.empty() ? nullptr : engines_[0]; }
@@ -239,6 +243,7 @@ class Recognizer : public std::enable_shared_from_this<Recognizer> {
                      const std::vector<int32_t>& batch, const std::vector<int32_t>& row, const std::string& sep,
                      std::vector<ResultEntity>& out);
   void Punctuate(const std::vector<Stream*>& streams, const std::vector<ResultEntity>& out);
+  ResampleBanks resample_;                                    // AddPcm's device form (its own lock)
   std::mutex spk_mu_;                                         // guards spk_model_ and spk_cfg_
   std::shared_ptr<const SpkModel> spk_model_;
   pf_spk_config spk_cfg_{};

@@ -1252,6 +1252,12 @@ class Engine:
         da = (N.PfPcmDesc * len(dl))(*dl)
         return ptrs, ns, da, len(dl), B, raws
 
+    def set_resample(self, zeros=None, rolloff=None, beta=None) -> None:
+        """The shape of the band-limited resampler for descriptors made with pcm_desc(..., sinc=True) (pf_engine_set_resample);
+        the defaults for what is not given.  Banks are rebuilt per rate on the next use."""
+        cfg = N.resample_config(zeros, rolloff, beta)
+        N.check(self._lib.pf_engine_set_resample(self._h, C.byref(cfg)))
+
     def pcm_num_samples(self, desc, n_values: int, fs: int = 16000) -> int:
         n = C.c_int64()
         N.check(self._lib.pf_pcm_num_samples(C.byref(desc), fs, n_values, C.byref(n)))

@@ -1,7 +1,7 @@
 """Command-line harness mirroring AliParaformerAsr.Examples (`-type offline` and `-type online`).
 
     python -m aliparaformerasr_amd.examples -type offline -method batch -base <dir> -model <name> \
-        [-accuracy int8] [-threads 2] [-decode ctc|frames] [-intake host|device] [-nbest N [-topk K] [-beam W | -search W] [-hotboost S] [-lm FILE [-lmweight A] [-lmbonus B] [-lmeos]]] [-align FILE|beam] [-vad [key=value,...] [-vadmodel FILE] [-spk FILE[,cluster=device] [key=value,...]]] [-punc FILE] -files a.wav b.wav
+        [-accuracy int8] [-threads 2] [-decode ctc|frames] [-intake host|device] [-resample linear|sinc] [-nbest N [-topk K] [-beam W | -search W] [-hotboost S] [-lm FILE [-lmweight A] [-lmbonus B] [-lmeos]]] [-align FILE|beam] [-vad [key=value,...] [-vadmodel FILE] [-spk FILE[,cluster=device] [key=value,...]]] [-punc FILE] -files a.wav b.wav
     python -m aliparaformerasr_amd.examples -type online -method one -base <dir> -model <name> [-endpoint [key=value,...] [-vadmodel FILE] [-secondpass <offline name>]] [-tokentimes [-devicefrontend]] [-puncstream FILE[,max_context=N]] -files a.wav
 
 Mirrors (file:line in /root/reference/AliParaformerAsr.Examples):
@@ -24,6 +24,9 @@ timestamps (OfflineRecognizer.SetDecode); `-decode frames`, the default, is the 
 `-intake device` (offline) reads only the wav header on the host (pf_host_wav_info) and hands the payload to
 OfflineStream.AddPcm raw: decode, down-mix and resample run on the device and give the samples GetFileSample gives;
 `-intake host`, the default, is the path above, untouched.
+`-resample sinc` (offline; not in the reference) resamples files that are not at 16 kHz with the band-limited polyphase filter
+instead of the reference's linear interpolation — on the GPU with `-intake device`, by its host twin with `-intake host`: the
+same samples either way.  `-resample linear` is the default.
 `-nbest N [-topk K]` (offline, paraformer models; OfflineRecognizer.SetNBest) prints under each result line the N best
 hypotheses, one `nbest[i] score:<sum of log-probs> text:<text>` line each, best first; line 0 is the result itself.
 `-nbest N -beam W` (offline, SenseVoice models; OfflineRecognizer.SetCtcBeam) prints the N best labelings of a CTC prefix
@@ -332,7 +335,8 @@ def _punc_lines(st):
 
 def offline_recognizer(method="one", model="paraformer-seaco-large-zh-timestamp-onnx-offline", accuracy="int8",
                        threads=2, files=None, base=None, out=sys.stdout, decode="frames", intake="host", nbest=0, topk=4,
-                       beam=0, align=None, hotboost=0.0, vad=None, lm=None, lmweight=0.5, lmbonus=0.0, lmeos=False, search=0, vadmodel=None, punc=None, spk=None):
+                       beam=0, align=None, hotboost=0.0, vad=None, lm=None, lmweight=0.5, lmbonus=0.0, lmeos=False, search=0, vadmodel=None, punc=None, spk=None,
+                       resample="linear"):
     from .offline_recognizer import OfflineRecognizer
     base = base or os.getcwd()
     sel = select_model_files(base, model, accuracy)
@@ -387,6 +391,9 @@ def offline_recognizer(method="one", model="paraformer-seaco-large-zh-timestamp-
         if intake == "device":
             pcm = get_file_pcm(f)
             s, dur = pcm[:4], pcm[4]
+        elif resample == "sinc":                           # the same intake on the host: the kernel's host twin
+            pcm = get_file_pcm(f)
+            s, dur = N.host_pcm_convert(pcm[0], N.pcm_desc(pcm[1], pcm[2], pcm[3], sinc=True)), pcm[4]
         else:
             s, dur = get_file_sample(f)
         paths.append(f); samples.append(s); total_ms += dur
@@ -400,7 +407,7 @@ def offline_recognizer(method="one", model="paraformer-seaco-large-zh-timestamp-
 
     def add(st, s):
         if isinstance(s, tuple):
-            st.AddPcm(s[0], s[1], s[2], s[3])
+            st.AddPcm(s[0], s[1], s[2], s[3], resample=resample)
         else:
             st.AddSamples(s)
 
@@ -638,6 +645,11 @@ def parse_args(argv, env=None):
             if i >= len(argv) or argv[i].lower() not in ("ctc", "frames"):
                 raise ValueError("The decode type must be ctc or frames")
             cfg["decode"] = argv[i].lower()
+        elif a == "-resample":
+            i += 1
+            if i >= len(argv) or argv[i].lower() not in ("linear", "sinc"):
+                raise ValueError("The resample type must be linear or sinc")
+            cfg["resample"] = argv[i].lower()
         elif a == "-intake":
             i += 1
             if i >= len(argv) or argv[i].lower() not in ("host", "device"):
@@ -815,7 +827,8 @@ def main(argv=None):
                            nbest=cfg.get("nbest", 0), topk=cfg.get("topk", 4), beam=cfg.get("beam", 0), align=cfg.get("align"),
                            hotboost=cfg.get("hotboost", 0.0), vad=cfg.get("vad"), lm=cfg.get("lm"), lmweight=cfg.get("lmweight", 0.5),
                            lmbonus=cfg.get("lmbonus", 0.0), lmeos=cfg.get("lmeos", False), search=cfg.get("search", 0),
-                           vadmodel=cfg.get("vadmodel"), punc=cfg.get("punc"), spk=cfg.get("spk"))
+                           vadmodel=cfg.get("vadmodel"), punc=cfg.get("punc"), spk=cfg.get("spk"),
+                           resample=cfg.get("resample", "linear"))
     else:
         print("the recognizer type must be online or offline")
         return 2

@@ -175,17 +175,23 @@ class OfflineStream:
         x = np.ascontiguousarray(samples, dtype=np.float32)
         _ck(self._lib.pf_stream_add_samples(self._h, x.ctypes.data_as(C.POINTER(C.c_float)), x.shape[0]))
 
-    def AddPcm(self, data, sample_rate: int, channels: int = 1, format: str = "s16", downmix_always: bool = False) -> None:
+    def AddPcm(self, data, sample_rate: int, channels: int = 1, format: str = "s16", downmix_always: bool = False,
+               resample: str = "linear") -> None:
         """AddSamples for audio as callers hold it: raw interleaved PCM (bytes, or a numpy array of the format's dtype —
         "u8", "s16", "s24" (bytes), "s32", "f32", "f64", "alaw", "mulaw") at any rate, mono or stereo.  Decoded, down-mixed and
         resampled to the model's rate exactly as the Examples' GetFileSample does (a stereo stream AT the model's rate stays
-        interleaved unless downmix_always), on the device for the first call on a recognizer's stream."""
+        interleaved unless downmix_always), on the device for the first call on a recognizer's stream.  resample="sinc" (not in
+        the reference) replaces the linear interpolation by the band-limited polyphase filter of OfflineRecognizer.SetResampler:
+        the same length, no aliasing."""
+        if resample not in ("linear", "sinc"):
+            raise ValueError('AddPcm: resample takes "linear" or "sinc"')
+        desc = N.pcm_desc(sample_rate, channels, format, downmix_always, sinc=resample == "sinc")
         if data is None:
-            _ck(self._lib.pf_stream_add_pcm(self._h, None, 0, C.byref(N.pcm_desc(sample_rate, channels, format, downmix_always))))
+            _ck(self._lib.pf_stream_add_pcm(self._h, None, 0, C.byref(desc)))
             return
         raw, n = N.pcm_bytes(data, format)
         keep = raw if raw.size else np.zeros(1, np.uint8)
-        _ck(self._lib.pf_stream_add_pcm(self._h, keep.ctypes.data, n, C.byref(N.pcm_desc(sample_rate, channels, format, downmix_always))))
+        _ck(self._lib.pf_stream_add_pcm(self._h, keep.ctypes.data, n, C.byref(desc)))
 
     @property
     def Hotwords(self) -> Optional[List[List[int]]]:
@@ -556,6 +562,13 @@ class OfflineRecognizer:
         stated, not validated."""
         from .engine import _spk_cfg_ptr
         _ck(self._lib.pf_recognizer_set_spk_model(self._h, None if pfwPath is None else str(pfwPath).encode("utf-8"), _spk_cfg_ptr(cfg)))
+
+    def SetResampler(self, zeros=None, rolloff=None, beta=None) -> None:
+        """The shape of the band-limited resampler that AddPcm(resample="sinc") selects (pf_recognizer_set_resample): zeros
+        (1 .. 64, default 24) zero crossings per side, rolloff (0 .. 1, default 0.94) of the narrower Nyquist, Kaiser beta
+        (0 .. 20, default 10).  Holds for the calls that follow on every engine of the pool.  Not validated on speech."""
+        cfg = N.resample_config(zeros, rolloff, beta)
+        _ck(self._lib.pf_recognizer_set_resample(self._h, C.byref(cfg)))
 
     def SetSpeakerClustering(self, where: str) -> None:
         """Where each stream's windows are clustered (pf_recognizer_set_spk_cluster): "host" (the default) or "device", the same

@@ -32,18 +32,18 @@ namespace AliParaformerAsr.Hip
         /// (ParaformerHip.PF_PCM_*) at any rate, mono or stereo.  Decoded, down-mixed and resampled to the model's rate exactly
         /// as the Examples' GetFileSample does (a stereo stream AT the model's rate stays interleaved unless downmixAlways), on
         /// the device for the first call on a recognizer's stream.</summary>
-        public void AddPcm(byte[] data, int sampleRate, int channels, int format = ParaformerHip.PF_PCM_S16, bool downmixAlways = false)
+        public void AddPcm(byte[] data, int sampleRate, int channels, int format = ParaformerHip.PF_PCM_S16, bool downmixAlways = false, bool sinc = false)
         {
-            PfPcmDesc d = PfPcmDesc.Of(format, sampleRate, channels, downmixAlways);
+            PfPcmDesc d = PfPcmDesc.Of(format, sampleRate, channels, downmixAlways, sinc);
             int bytesPerValue = format == ParaformerHip.PF_PCM_S16 ? 2 : format == ParaformerHip.PF_PCM_S24 ? 3
                               : format == ParaformerHip.PF_PCM_S32 || format == ParaformerHip.PF_PCM_F32 ? 4 : format == ParaformerHip.PF_PCM_F64 ? 8 : 1;
             ParaformerHip.Check(ParaformerHip.pf_stream_add_pcm(Handle, data, data == null ? 0 : data.LongLength / bytesPerValue, ref d));
         }
 
         /// <summary>16-bit PCM as most capture APIs deliver it.</summary>
-        public void AddPcm(short[] samples, int sampleRate, int channels = 1, bool downmixAlways = false)
+        public void AddPcm(short[] samples, int sampleRate, int channels = 1, bool downmixAlways = false, bool sinc = false)
         {
-            PfPcmDesc d = PfPcmDesc.Of(ParaformerHip.PF_PCM_S16, sampleRate, channels, downmixAlways);
+            PfPcmDesc d = PfPcmDesc.Of(ParaformerHip.PF_PCM_S16, sampleRate, channels, downmixAlways, sinc);
             ParaformerHip.Check(ParaformerHip.pf_stream_add_pcm(Handle, samples, samples == null ? 0 : samples.LongLength, ref d));
         }
 
@@ -498,6 +498,15 @@ namespace AliParaformerAsr.Hip
         {
             PfSpkConfig c = cfg ?? DefaultSpeaker();
             ParaformerHip.Check(ParaformerHip.pf_recognizer_set_spk_model(_r, pfwPath, ref c));
+        }
+
+        /// <summary>Not in the reference: the shape of the band-limited resampler that AddPcm(..., sinc: true) selects
+        /// (pf_recognizer_set_resample): zero crossings per side (1..64), roll-off (0..1] of the narrower Nyquist, Kaiser beta (0..20).</summary>
+        public void SetResampler(int zeros = 24, double rolloff = 0.94, double beta = 10.0)
+        {
+            ParaformerHip.Check(ParaformerHip.pf_resample_default(out ParaformerHip.PfResampleConfig c));
+            c.zeros = zeros; c.rolloff = rolloff; c.beta = beta;
+            ParaformerHip.Check(ParaformerHip.pf_recognizer_set_resample(_r, ref c));
         }
 
         /// <summary>Not in the reference: where each stream's windows are clustered (pf_recognizer_set_spk_cluster): "host" (the

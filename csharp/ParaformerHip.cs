@@ -31,15 +31,16 @@ namespace AliParaformerAsr.Native
     }
 
     /// <summary>pf_pcm_desc: what a block of raw interleaved PCM holds (paraformer_hip.h "PCM intake").  format: 1 u8, 2 s16,
-    /// 3 s24, 4 s32, 5 float32, 6 float64, 7 A-law, 8 mu-law; flags: PF_PCM_DOWNMIX_ALWAYS = 1.</summary>
+    /// 3 s24, 4 s32, 5 float32, 6 float64, 7 A-law, 8 mu-law; flags: PF_PCM_DOWNMIX_ALWAYS = 1,
+    /// PF_PCM_RESAMPLE_SINC = 2 (the band-limited polyphase resampler instead of the linear rule).</summary>
     [StructLayout(LayoutKind.Sequential)]
     internal struct PfPcmDesc
     {
         public int struct_size, format, sample_rate, channels, flags, reserved0, reserved1, reserved2;
-        internal static PfPcmDesc Of(int format, int sampleRate, int channels, bool downmixAlways = false) => new PfPcmDesc
+        internal static PfPcmDesc Of(int format, int sampleRate, int channels, bool downmixAlways = false, bool sinc = false) => new PfPcmDesc
         {
             struct_size = Marshal.SizeOf<PfPcmDesc>(), format = format, sample_rate = sampleRate, channels = channels,
-            flags = downmixAlways ? ParaformerHip.PF_PCM_DOWNMIX_ALWAYS : 0,
+            flags = (downmixAlways ? ParaformerHip.PF_PCM_DOWNMIX_ALWAYS : 0) | (sinc ? ParaformerHip.PF_PCM_RESAMPLE_SINC : 0),
         };
     }
 
@@ -225,7 +226,17 @@ namespace AliParaformerAsr.Native
         // PCM intake (additions to ABI 6): raw interleaved values, decoded / down-mixed / resampled on the device in front of the
         // fbank, bit for bit what GetFileSample (Examples/Utils/AudioHelper.cs:12-32) returns; nValues counts interleaved values
         internal const int PF_PCM_U8 = 1, PF_PCM_S16 = 2, PF_PCM_S24 = 3, PF_PCM_S32 = 4, PF_PCM_F32 = 5, PF_PCM_F64 = 6, PF_PCM_ALAW = 7,
-                           PF_PCM_MULAW = 8, PF_PCM_DOWNMIX_ALWAYS = 1;
+                           PF_PCM_MULAW = 8, PF_PCM_DOWNMIX_ALWAYS = 1, PF_PCM_RESAMPLE_SINC = 2;
+        /// <summary>pf_resample_config: the shape of the band-limited resampler (zeros 24, rolloff 0.94, beta 10 by default).</summary>
+        [StructLayout(LayoutKind.Sequential)]
+        internal struct PfResampleConfig { public int struct_size, zeros; public double rolloff, beta; }
+        [DllImport(Lib)] internal static extern int pf_resample_default(out PfResampleConfig cfg);
+        [DllImport(Lib)] internal static extern int pf_engine_set_resample(IntPtr e, ref PfResampleConfig cfg);
+        [DllImport(Lib)] internal static extern int pf_recognizer_set_resample(IntPtr r, ref PfResampleConfig cfg);
+        [DllImport(Lib)] internal static extern int pf_host_resample_sinc(float[] src, long n, int srIn, int srOut, int channels, ref PfResampleConfig cfg,
+                                                                          float[]? dst, long cap, out long nOut);
+        [DllImport(Lib)] internal static extern int pf_host_pcm_convert(byte[]? data, long nValues, ref PfPcmDesc desc, int fs, ref PfResampleConfig cfg,
+                                                                        float[]? dst, long cap, out long nOut);
         [DllImport(Lib)] internal static extern int pf_pcm_num_samples(ref PfPcmDesc desc, int fs, long nValues, out long nOut);
         [DllImport(Lib)] internal static extern int pf_stage_pcm(IntPtr e, IntPtr[] data, long[] nValues, PfPcmDesc[] descs, int nDescs, int B);
         [DllImport(Lib)] internal static extern int pf_recognize_pcm(IntPtr e, IntPtr[] data, long[] nValues, PfPcmDesc[] descs, int nDescs,

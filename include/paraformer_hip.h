@@ -531,11 +531,33 @@ int pf_host_ctc_align(const float* lp, int64_t ld, int32_t T, int32_t V, const i
    PF_ERR_INVALID_ARG: data NULL with n_values > 0, channels not 1 or 2, sample_rate <= 0, unknown format, n_values above
    2^31 - 1 (the host definition indexes with int), struct_size mismatch.
    Out of scope: the streaming recognizer's AddSamples (resampling across chunks needs a carried phase the reference's
-   one-shot Resample does not define), pf_group_*, more than two channels, compressed containers, sinc / polyphase
-   filtering (the reference's linear interpolation is the definition, aliasing included). */
+   one-shot Resample does not define), pf_group_*, more than two channels, compressed containers.  The reference's linear
+   interpolation (aliasing included) is the DEFAULT resampling rule; PF_PCM_RESAMPLE_SINC below selects a band-limited one.
+
+   PF_PCM_RESAMPLE_SINC (opt-in, not in the reference; inert when sample_rate == fs): the resampling step becomes a polyphase
+   Kaiser-windowed sinc filter (csrc/k_resample.hip; the definition is tests/resample_ref.py).  Decode, down-mix and the
+   OUTPUT LENGTH stay what they are — only sample values change.  With g = gcd(sample_rate, fs), L = fs / g, M = sample_rate / g
+   and a pf_resample_config (zeros, rolloff, beta): c = rolloff * min(1, L / M), H = ceil(zeros / c), taps = 2 H,
+     h[p][k] = c * sinc(c * tau) * I0(beta * sqrt(1 - u * u)) / I0(beta),  tau = (k - (H - 1)) - p / L,  u = tau * c / zeros
+   (0 where |u| >= 1), computed in float64 on the host and rounded to float32 once; output i with b = (i * M) / L, p = (i * M) % L is
+   the chain acc = fmaf(h[p][k], m[b - H + 1 + k], acc) over k = 0 .. taps - 1 from acc = +0, m = +0 outside the mono sequence:
+   each step ONE correctly rounded fp32 fused multiply-add, on the device and in pf_host_resample_sinc alike (bit-equal).
+   Defaults (pf_resample_default): zeros 24, rolloff 0.94, beta 10.  PF_ERR_INVALID_ARG: zeros outside [1, 64], rolloff outside
+   (0, 1], beta outside [0, 20], non-finite values.  PF_ERR_UNSUPPORTED: L > 1024 (e.g. 16001 -> 16000; checked wherever a flagged
+   descriptor is planned, pf_pcm_num_samples included) or taps > 1024 (checked where the bank is built).
+   pf_engine_set_resample / pf_recognizer_set_resample set only the SHAPE of the filter (NULL = the defaults) — a descriptor's
+   flag is what selects it.  Banks are built on first use per sample rate and kept on the device until the shape changes.
+   Not validated on speech. */
 typedef enum pf_pcm_format { PF_PCM_U8 = 1, PF_PCM_S16, PF_PCM_S24, PF_PCM_S32, PF_PCM_F32, PF_PCM_F64, PF_PCM_ALAW, PF_PCM_MULAW } pf_pcm_format;
 #define PF_PCM_DOWNMIX_ALWAYS 1
+#define PF_PCM_RESAMPLE_SINC 2
+#define PF_RESAMPLE_TILE 1024            /* outputs per tile of the resampling kernel (for tests that straddle it) */
+#define PF_RESAMPLE_MAX_PHASES 1024
+#define PF_RESAMPLE_MAX_TAPS 1024
 typedef struct pf_pcm_desc { int32_t struct_size, format, sample_rate, channels, flags, reserved[3]; } pf_pcm_desc;
+typedef struct pf_resample_config { int32_t struct_size, zeros; double rolloff, beta; } pf_resample_config;
+int pf_resample_default(pf_resample_config* cfg);
+int pf_engine_set_resample(pf_engine* e, const pf_resample_config* cfg);
 /* Host only: the sample count the conversion yields (to size buffers, or for pf_frontend_num_frames). */
 int pf_pcm_num_samples(const pf_pcm_desc* desc, int32_t fs, int64_t n_values, int64_t* n_out);
 /* pf_stage_audio for raw PCM: utterance b = n_values[b] values at data[b], described by descs[b] (n_descs == B) or by
@@ -1701,6 +1723,9 @@ int pf_recognizer_set_punc_model(pf_recognizer* r, const char* pfw_path);
    inert without them. */
 int pf_recognizer_set_spk_model(pf_recognizer* r, const char* pfw_path, const pf_spk_config* cfg);
 int pf_recognizer_set_spk_cluster(pf_recognizer* r, int32_t on_device);
+/* The shape of the band-limited resampler ("PCM intake", PF_PCM_RESAMPLE_SINC) for pf_stream_add_pcm calls that follow, in the
+   device and the host form, and for every engine of the pool, present and future.  NULL = the defaults. */
+int pf_recognizer_set_resample(pf_recognizer* r, const pf_resample_config* cfg);
 int pf_stream_num_speakers(pf_stream* s, int32_t* n);
 int pf_stream_segment_speaker(pf_stream* s, int32_t i, int32_t* spk);
 int pf_stream_speaker_centroid(pf_stream* s, int32_t spk, float* out, int32_t cap, int32_t* E);
@@ -2000,6 +2025,14 @@ int pf_host_wav_read(const char* path, float* out, int64_t cap, int64_t* n_out, 
                      int32_t* channels, double* duration_ms);
 int pf_host_resample(const float* src, int64_t n, int32_t sr_in, int32_t sr_out, int32_t channels, float* out,
                      int64_t cap, int64_t* n_out);
+/* pf_host_resample with the band-limited rule of PF_PCM_RESAMPLE_SINC ("PCM intake"; cfg NULL = the defaults): the same
+   down-mix and output length, the host twin of csrc/k_resample.hip.  sr_in == sr_out copies (after the down-mix). */
+int pf_host_resample_sinc(const float* src, int64_t n, int32_t sr_in, int32_t sr_out, int32_t channels,
+                          const pf_resample_config* cfg, float* out, int64_t cap, int64_t* n_out);
+/* The whole PCM intake on the host (decode, down-mix, resample by the descriptor's rule; cfg as pf_engine_set_resample): what
+   pf_op_pcm_convert computes on the device, bit for bit, and what pf_stream_add_pcm's host form feeds to AddSamples. */
+int pf_host_pcm_convert(const void* data, int64_t n_values, const pf_pcm_desc* desc, int32_t fs, const pf_resample_config* cfg,
+                        float* out, int64_t cap, int64_t* n_out);
 int pf_host_is_audio(const char* path, int32_t* is_audio);
 /* The header walk of pf_host_wav_read WITHOUT the sample loop: what the file holds (desc: format, rate, channels; flags 0) and
    where (data_offset / data_bytes of the payload inside the file, data_bytes clamped to the file; n_values = data_bytes /
