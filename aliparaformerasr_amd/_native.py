@@ -131,6 +131,65 @@ def host_pcm_convert(data, desc, fs=16000, cfg=None):
     return out[:n.value]
 
 
+class HostPcmStream:
+    """pf_host_pcm_stream_*: one stream's PCM converter, the host twin of csrc/k_pcm_stream.hip.  push(bytes) and finish() return
+    the float32 samples that became final; their concatenation is host_pcm_convert of the concatenated bytes, bit for bit, for
+    every cut.  A converter that Engine-side pf_op_online_pcm_step steps (op_online_pcm_step below) takes bytes through append()."""
+
+    def __init__(self, desc, fs=16000, cfg=None):
+        self._lib, self._h, self.desc = load(), C.c_void_p(), desc
+        check(self._lib.pf_host_pcm_stream_create(C.byref(desc), fs, None if cfg is None else C.byref(cfg), C.byref(self._h)))
+
+    def _take(self, call):
+        import numpy as np
+        n = C.c_int64()
+        check(self._lib.pf_host_pcm_stream_pending(self._h, C.byref(n)))
+        out = np.zeros(max(n.value, 1), np.float32)
+        check(call(out.ctypes.data_as(C.POINTER(C.c_float)), out.size, C.byref(n)))
+        return out[:n.value]
+
+    def append(self, data, finish=False) -> None:
+        import numpy as np
+        raw = np.frombuffer(bytes(data), np.uint8)
+        check(self._lib.pf_host_pcm_stream_push(self._h, raw.ctypes.data if raw.size else None, raw.size, None, 0, None))
+        if finish:
+            check(self._lib.pf_host_pcm_stream_finish(self._h, None, 0, None))
+
+    def push(self, data):
+        self.append(data)
+        return self._take(lambda o, cap, n: self._lib.pf_host_pcm_stream_push(self._h, None, 0, o, cap, n))
+
+    def finish(self):
+        check(self._lib.pf_host_pcm_stream_finish(self._h, None, 0, None))
+        return self._take(lambda o, cap, n: self._lib.pf_host_pcm_stream_finish(self._h, o, cap, n))
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            self._lib.pf_host_pcm_stream_free(self._h)
+            self._h = None
+
+
+def pcm_stream_state_bytes() -> int:
+    n = C.c_int64()
+    check(load().pf_host_pcm_stream_state_bytes(C.byref(n)))
+    return n.value
+
+
+def op_online_pcm_step(engine, states, slots, streams, n_out):
+    """pf_op_online_pcm_step: ONE launch of csrc/k_pcm_stream.hip over the HostPcmStream converters `streams` (fed by append), up
+    to n_out[b] samples each, on blocks slots[b] of states [n_states, pcm_stream_state_bytes()] uint8 (updated in place).  Returns
+    (samples [B, 9600] float32, n_written [B])."""
+    import numpy as np
+    B = len(streams)
+    sl, no = np.ascontiguousarray(slots, np.int32), np.ascontiguousarray(n_out, np.int32)
+    hs = (C.c_void_p * B)(*[s._h for s in streams])
+    out, nw = np.zeros((B, 9600), np.float32), np.zeros(B, np.int32)
+    check(load().pf_op_online_pcm_step(engine._h, states.ctypes.data_as(C.c_void_p), states.shape[0], sl.ctypes.data_as(C.POINTER(C.c_int32)),
+                                       hs, no.ctypes.data_as(C.POINTER(C.c_int32)), B, out.ctypes.data_as(C.POINTER(C.c_float)),
+                                       nw.ctypes.data_as(C.POINTER(C.c_int32))))
+    return out, nw
+
+
 def host_resample_sinc(samples, sr_in, sr_out, channels=1, cfg=None):
     """pf_host_resample_sinc: float32 samples (interleaved when channels == 2) -> the band-limited resampler's output, the host
     twin of the device kernel; cfg: a PfResampleConfig or None for the defaults."""
@@ -536,6 +595,15 @@ SIGNATURES = {
     "pf_host_online_frontend_state_bytes": (C.c_int, [C.c_int32, C.c_int32, _i64]),
     "pf_host_online_frontend_step": (C.c_int, [_vp, _f, _f, _f, C.c_int32, _f]),
     "pf_op_online_frontend_step": (C.c_int, [_vp, _vp, C.c_int32, _i32, _f, _i32, C.c_int32, _f]),
+    "pf_online_stream_add_pcm": (C.c_int, [_vp, _vp, C.c_int64, _P(PfPcmDesc)]),
+    "pf_online_recognizer_set_resample": (C.c_int, [_vp, _P(PfResampleConfig)]),
+    "pf_host_pcm_stream_create": (C.c_int, [_P(PfPcmDesc), C.c_int32, _P(PfResampleConfig), _P(C.c_void_p)]),
+    "pf_host_pcm_stream_push": (C.c_int, [_vp, _vp, C.c_int64, _f, C.c_int64, _i64]),
+    "pf_host_pcm_stream_finish": (C.c_int, [_vp, _f, C.c_int64, _i64]),
+    "pf_host_pcm_stream_pending": (C.c_int, [_vp, _i64]),
+    "pf_host_pcm_stream_free": (None, [_vp]),
+    "pf_host_pcm_stream_state_bytes": (C.c_int, [_i64]),
+    "pf_op_online_pcm_step": (C.c_int, [_vp, _vp, C.c_int32, _i32, _P(C.c_void_p), _i32, C.c_int32, _f, _i32]),
     "pf_host_online_cif_state_bytes": (C.c_int, [C.c_int32, _i64]),
     "pf_host_online_cif_step": (C.c_int, [_vp, _f, _f, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_int32, _f, _i32, C.c_int32,
                                           _i32]),

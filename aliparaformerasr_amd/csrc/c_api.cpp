@@ -2839,6 +2839,21 @@ int pf_online_stream_add_samples(pf_online_stream* h, const float* samples, int6
   return PF_OK;
   PF_CATCH
 }
+int pf_online_stream_add_pcm(pf_online_stream* h, const void* data, int64_t n_bytes, const pf_pcm_desc* desc) {
+  PF_TRY
+  OnlineStreamM* s = OS(h);
+  NEED(desc);
+  PF_CHECK(!s->owner->disposed(), PF_ERR_DISPOSED, "OnlineRecognizer");
+  s->AddPcm(data, n_bytes, *desc);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_online_recognizer_set_resample(pf_online_recognizer* h, const pf_resample_config* cfg) {
+  PF_TRY
+  OR(h)->SetResample(cfg);
+  return PF_OK;
+  PF_CATCH
+}
 int pf_online_get_results(pf_online_recognizer* h, pf_online_stream* const* streams, int32_t n) {
   PF_TRY
   std::shared_ptr<OnlineRecognizerM> r = OR(h);
@@ -3380,6 +3395,69 @@ int pf_host_pcm_convert(const void* data, int64_t n_values, const pf_pcm_desc* d
     PF_CHECK(cap >= (int64_t)v.size(), PF_ERR_CAPACITY, "pcm_convert: output capacity too small");
     if (!v.empty()) std::memcpy(out, v.data(), v.size() * 4);
   }
+  return PF_OK;
+  PF_CATCH
+}
+
+struct pf_pcm_stream { PcmStream s; pf_pcm_stream(const pf_pcm_desc& d, int fs, const pf_resample_config* c) : s(d, fs, c) {} };
+
+int pf_host_pcm_stream_create(const pf_pcm_desc* desc, int32_t fs, const pf_resample_config* cfg, pf_pcm_stream** out) {
+  PF_TRY
+  NEED(desc); NEED(out);
+  *out = nullptr;
+  *out = new pf_pcm_stream(*desc, fs, cfg);
+  return PF_OK;
+  PF_CATCH
+}
+static int64_t pcm_stream_take(pf_pcm_stream* h, float* out, int64_t cap) {
+  if (!out || cap <= 0) return 0;
+  const std::vector<float> v = h->s.take(cap);
+  if (!v.empty()) std::memcpy(out, v.data(), v.size() * 4);
+  return (int64_t)v.size();
+}
+int pf_host_pcm_stream_push(pf_pcm_stream* h, const void* data, int64_t n_bytes, float* out, int64_t cap, int64_t* n_out) {
+  PF_TRY
+  NEED(h);
+  h->s.append(data, n_bytes);
+  const int64_t n = pcm_stream_take(h, out, cap);
+  if (n_out) *n_out = n;
+  return PF_OK;
+  PF_CATCH
+}
+int pf_host_pcm_stream_finish(pf_pcm_stream* h, float* out, int64_t cap, int64_t* n_out) {
+  PF_TRY
+  NEED(h);
+  h->s.close();
+  const int64_t n = pcm_stream_take(h, out, cap);
+  if (n_out) *n_out = n;
+  return PF_OK;
+  PF_CATCH
+}
+int pf_host_pcm_stream_pending(pf_pcm_stream* h, int64_t* n) {
+  PF_TRY
+  NEED(h); NEED(n);
+  *n = h->s.n_final() - h->s.n_taken();
+  return PF_OK;
+  PF_CATCH
+}
+void pf_host_pcm_stream_free(pf_pcm_stream* h) { delete h; }
+int pf_host_pcm_stream_state_bytes(int64_t* bytes) {
+  PF_TRY
+  NEED(bytes);
+  *bytes = (int64_t)block_at_zero<PcmStreamBlock>().bytes();
+  return PF_OK;
+  PF_CATCH
+}
+int pf_op_online_pcm_step(pf_engine* h, void* states, int32_t n_states, const int32_t* slot, pf_pcm_stream* const* streams,
+                          const int32_t* n_out, int32_t B, float* samples, int32_t* n_written) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  NEED(streams);
+  PF_CHECK(B > 0, PF_ERR_INVALID_ARG, "online_pcm_step: B > 0 expected");
+  std::vector<PcmStream*> ps((size_t)B);
+  for (int b = 0; b < B; ++b) { NEED(streams[b]); ps[(size_t)b] = &streams[b]->s; }
+  std::lock_guard<std::mutex> lk(eh_->mutex());
+  eh_->op_online_pcm_step(states, n_states, slot, ps.data(), n_out, B, samples, n_written);
   return PF_OK;
   PF_CATCH
 }

@@ -114,6 +114,16 @@ struct FrontendStreamBlock : Block {
   }
 };
 
+// one stream's streaming PCM intake (k_pcm_stream.hip, PcmStream::cut in hostutil.cpp): tail [2, kPcmStreamTail] fp32, two buffers
+// of decoded mono frames.  The host says which one is current (the step's parity) and how many frames it holds; a step reads only
+// that one and ONE workgroup writes the next tail into the other, so no workgroup reads a cell another writes.  Nothing is read
+// that was not written by an earlier step: a new stream has tail_len 0, and the block needs no zeroing.
+constexpr size_t kPcmStreamTail = 1024;                    // PF_RESAMPLE_MAX_TAPS: a window's worth of frames
+struct PcmStreamBlock : Block {
+  Field<float> tail;
+  explicit PcmStreamBlock(Cursor& c) : Block(c) { lay(c, tail, 2 * kPcmStreamTail); }
+};
+
 // a block on its own, from offset 0: the layout of a host vector
 template <class Blk, class... Dims> Blk block_at_zero(Dims... dims) {
   Cursor c;

@@ -1877,6 +1877,65 @@ void Engine::online_frontend(const float* samples, int B, char* states_dev, cons
                          (float*)ws_speech_.p);
 }
 
+// ---- the streaming PCM intake (engine.h) ----
+size_t Engine::online_pcm_slot_bytes() const { return (size_t)round_up((int64_t)block_at_zero<PcmStreamBlock>().bytes(), kAlign); }
+
+PcmStreamJob Engine::pcm_stream_job(const PcmStream& ps, const PcmStreamStep& st, ResampleBanks& banks, int row, int slot, int64_t raw_off) {
+  PF_CHECK(ps.fs() == fc_.fs, PF_ERR_INVALID_ARG, "pcm stream: made for another engine rate");
+  PcmStreamJob j{};
+  j.ratio = ps.ratio(); j.raw_off = raw_off; j.in_first = st.in_first; j.o0 = st.o0; j.n_total = st.n_total; j.next_first = st.next_first;
+  j.row = row; j.slot = slot; j.n_new = st.n_new; j.n_out = st.n_out; j.tail_parity = st.tail_parity; j.tail_len = st.tail_len;
+  j.next_len = st.next_len; j.write_tail = st.write_tail; j.format = ps.desc().format; j.downmix = ps.downmix() ? 1 : 0; j.rule = ps.rule();
+  if (j.rule == 2) {
+    const pf_resample_config a = banks.config(), b = ps.config();
+    PF_CHECK(a.zeros == b.zeros && a.rolloff == b.rolloff && a.beta == b.beta, PF_ERR_INVALID_ARG,
+             "pcm stream: the resampler's shape was changed after the stream's first audio");
+    const ResampleJob r = banks.job(ps.desc().sample_rate, fc_.fs, j.format, ps.downmix(), 0, 0, 0, 0, 1);
+    j.bank = r.bank; j.L = r.L; j.M = r.M; j.H = r.H; j.stride = r.stride;
+  }
+  pcm_stream_fit(j);
+  return j;
+}
+
+void Engine::online_frontend_pcm(const float* samples, int Bs, const OnlinePcmIn* pcm, int Bp, ResampleBanks& banks, char* pcm_states_dev,
+                                 int n_slots, char* states_dev, const int32_t* slot, const int32_t* reset) {
+  if (Bp == 0) { online_frontend(samples, Bs, states_dev, slot, reset); return; }     // the copies, launches and bytes of a call without AddPcm
+  PF_CHECK(pcm && pcm_states_dev && states_dev && slot && reset && Bs >= 0 && Bp > 0 && (Bs == 0 || samples), PF_ERR_INVALID_ARG,
+           "online_frontend: bad arguments");
+  online_frontend_check();
+  PF_HIP(hipSetDevice(device_));
+  const size_t B = (size_t)Bs + (size_t)Bp, chunk = kPcmStreamRow;
+  auto up16 = [](size_t v) { return (v + 15) / 16 * 16; };
+  const size_t jobs_off = up16(2 * B * 4), raw_off0 = up16(jobs_off + (size_t)Bp * sizeof(PcmStreamJob));
+  fe_jobs_.resize((size_t)Bp);
+  size_t raw_bytes = 0;
+  for (int p = 0; p < Bp; ++p) {
+    fe_jobs_[(size_t)p] = pcm_stream_job(*pcm[p].stream, *pcm[p].step, banks, Bs + p, pcm[p].slot, (int64_t)raw_bytes);
+    raw_bytes += up16(pcm[p].step->raw.size());
+  }
+  const size_t rows_off = up16(raw_off0 + raw_bytes);
+  std::vector<float>& up = fe_up_;                               // (a member: the copy may still read it when this call returns)
+  up.resize(rows_off / 4 + (size_t)Bs * chunk);
+  char* u = (char*)up.data();
+  std::memcpy(u, slot, B * 4);
+  std::memcpy(u + B * 4, reset, B * 4);
+  std::memcpy(u + jobs_off, fe_jobs_.data(), (size_t)Bp * sizeof(PcmStreamJob));
+  for (int p = 0; p < Bp; ++p)
+    if (!pcm[p].step->raw.empty()) std::memcpy(u + raw_off0 + fe_jobs_[(size_t)p].raw_off, pcm[p].step->raw.data(), pcm[p].step->raw.size());
+  if (Bs > 0) std::memcpy(u + rows_off, samples, (size_t)Bs * chunk * 4);
+  ensure(ws_fe_, rows_off + B * chunk * 4);
+  ensure(ws_speech_, B * 20 * mc_.feat_dim * 4);
+  PF_HIP(hipMemcpyAsync(ws_fe_.p, u, up.size() * 4, hipMemcpyHostToDevice, stream_));
+  char* d = (char*)ws_fe_.p;
+  prof_begin("pcm_stream", 0);
+  launch_pcm_stream(stream_, (const PcmStreamJob*)(d + jobs_off), fe_jobs_.data(), Bp, d + raw_off0, (int64_t)raw_bytes, pcm_states_dev,
+                    (int64_t)online_pcm_slot_bytes(), n_slots, (float*)(d + rows_off), (int)B);
+  prof_end("pcm_stream");
+  const int32_t* meta = (const int32_t*)ws_fe_.p;
+  online_frontend_launch((const float*)(d + rows_off), (int)B, states_dev, (int64_t)online_frontend_slot_bytes(), meta, meta + B,
+                         (float*)ws_speech_.p);
+}
+
 void Engine::set_hotwords(const int32_t* hw, int n) {
   PF_CHECK(n >= 0 && (n == 0 || hw), PF_ERR_INVALID_ARG, "set_hotwords: bad arguments");
   if (n == n_hotwords_ && hotwords_.size() == (size_t)n * 10 && (n == 0 || std::memcmp(hotwords_.data(), hw, (size_t)n * 40) == 0)) return;

@@ -15,6 +15,7 @@
 #include "punc.h"
 #include "json.h"
 #include "kernels.h"
+#include "hostutil.h"
 #include "shards.h"
 
 namespace pf {
@@ -398,6 +399,20 @@ class Engine {
   // exactly that launch on caller data through op_stage.h: states [n_states, online_frontend_state_bytes(80, 560)] in / out, the
   // streams' blocks chosen by slot [B] (distinct, inside n_states); speech [B, 20, 560] out
   void op_online_frontend_step(void* states, int n_states, const int32_t* slot, const float* samples, const int32_t* reset, int B, float* speech);
+  // ---- the streaming PCM intake (OnlineStreamM::AddPcm with SetDeviceFrontend) ----
+  // online_frontend with Bp PCM-fed streams behind the Bs sample-fed ones (slot / reset [Bs + Bp] in that order): the job table
+  // and the raw frames of the PCM streams' steps ride in the SAME staged copy (slot | reset | jobs | raw | the Bs sample rows),
+  // one launch_pcm_stream (profile class "pcm_stream") writes rows Bs .. of the samples block from them and the streams'
+  // PcmStreamBlocks (pcm_states_dev, online_pcm_slot_bytes() apart, n_slots of them), then the two launches of online_frontend.
+  struct OnlinePcmIn { const PcmStream* stream; const PcmStreamStep* step; int slot; };
+  size_t online_pcm_slot_bytes() const;
+  void online_frontend_pcm(const float* samples, int Bs, const OnlinePcmIn* pcm, int Bp, ResampleBanks& banks, char* pcm_states_dev, int n_slots,
+                           char* states_dev, const int32_t* slot, const int32_t* reset);
+  // exactly that launch on caller data through op_stage.h: stream b is cut by up to n_out[b] outputs (PcmStream::cut) and stepped on
+  // block slot[b] of states [n_states, pcm_stream_state_bytes]; samples [B, 9600] out, n_written [B].  A sentinel row stands
+  // behind every row and a sentinel block behind every state block.
+  void op_online_pcm_step(void* states, int n_states, const int32_t* slot, PcmStream* const* streams, const int32_t* n_out, int B,
+                          float* samples, int32_t* n_written);
 
   // ---- stand-alone ops (parity tests) -------------------------------------
   void op_lfr_cmvn_pad(const float* const* fbank, const int32_t* t80, int B, int sentinel, float* out,
@@ -615,6 +630,8 @@ class Engine {
   bool fe_inv_ready_ = false;
   int fe_meta_B_ = 0;
   std::vector<float> fe_up_;
+  std::vector<PcmStreamJob> fe_jobs_;
+  PcmStreamJob pcm_stream_job(const PcmStream& ps, const PcmStreamStep& st, ResampleBanks& banks, int row, int slot, int64_t raw_off);
   void online_frontend_check();
   void online_frontend_launch(const float* samples_dev, int B, char* states_dev, int64_t stride, const int32_t* slot_dev, const int32_t* reset_dev,
                               float* speech_dev);

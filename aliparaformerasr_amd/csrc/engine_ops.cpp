@@ -376,6 +376,63 @@ void Engine::op_online_frontend_step(void* states, int n_states, const int32_t* 
   std::memcpy(speech, hs.data(), hs.size() * 4);
 }
 
+// ---- the streaming PCM intake (k_pcm_stream.hip).  Stream b's row is row 2 b of a sentinel-filled [2 B, 9600] block and its state
+// block is block 2 slot[b] of a sentinel-filled [2 n_states] run: every odd row and every odd block must keep its bits, every even
+// row must have been written everywhere; hostile bytes stand behind the raw frames.
+void Engine::op_online_pcm_step(void* states, int n_states, const int32_t* slot, PcmStream* const* streams, const int32_t* n_out, int B,
+                                float* samples, int32_t* n_written) {
+  PF_CHECK(states && slot && streams && n_out && samples && n_written, PF_ERR_INVALID_ARG, "online_pcm_step: null pointer");
+  PF_CHECK(B > 0 && n_states >= B, PF_ERR_INVALID_ARG, "online_pcm_step: B > 0 and n_states >= B expected");
+  for (int b = 0; b < B; ++b) {
+    PF_CHECK(streams[b] && n_out[b] >= 0 && n_out[b] <= kPcmStreamRow, PF_ERR_INVALID_ARG, "online_pcm_step: a null stream or n_out outside 0 .. 9600");
+    PF_CHECK(slot[b] >= 0 && slot[b] < n_states, PF_ERR_INVALID_ARG, "online_pcm_step: a slot outside the state blocks");
+    for (int c = 0; c < b; ++c) PF_CHECK(slot[c] != slot[b] && streams[c] != streams[b], PF_ERR_INVALID_ARG, "online_pcm_step: a slot or a stream twice");
+  }
+  PF_HIP(hipSetDevice(device_));
+  const size_t nB = (size_t)B, nS = (size_t)n_states, sb = block_at_zero<PcmStreamBlock>().bytes(), row = kPcmStreamRow, tail = 64;
+  std::vector<PcmStreamStep> steps(nB);
+  std::vector<PcmStreamJob> jobs(nB);
+  std::vector<unsigned char> raw;
+  for (size_t b = 0; b < nB; ++b) {
+    steps[b] = streams[b]->cut(n_out[b]);
+    jobs[b] = pcm_stream_job(*streams[b], steps[b], resample_, (int)(2 * b), 2 * slot[b], (int64_t)raw.size());
+    raw.insert(raw.end(), steps[b].raw.begin(), steps[b].raw.end());
+    raw.resize((raw.size() + 15) / 16 * 16, 0xA5);
+    n_written[b] = steps[b].n_out;
+  }
+  const size_t raw_bytes = raw.size();
+  for (size_t i = 0; i < tail; ++i) raw.push_back((unsigned char)(0x7F ^ (i * 37u)));
+  StageCarve st;
+  const auto d_state = st.take<uint32_t>(2 * nS * sb / 4);
+  const auto d_rows = st.take<float>(2 * nB * row);
+  const auto d_jobs = st.take<PcmStreamJob>(nB);
+  const auto d_raw = st.take<unsigned char>(raw.size());
+  void* ws = op_ws(st);
+  std::vector<uint32_t> hst(d_state.count, kSentinel32);
+  for (size_t k = 0; k < nS; ++k) std::memcpy(&hst[2 * k * sb / 4], (const char*)states + k * sb, sb);
+  upload(stream_, d_state(ws), (const uint32_t*)hst.data(), hst.size());
+  fill_sentinel(stream_, d_rows(ws), d_rows.count);
+  upload(stream_, d_jobs(ws), (const PcmStreamJob*)jobs.data(), nB);
+  upload(stream_, d_raw(ws), (const unsigned char*)raw.data(), raw.size());
+  launch_pcm_stream(stream_, d_jobs(ws), jobs.data(), B, d_raw(ws), (int64_t)raw_bytes, (char*)d_state(ws), (int64_t)sb, 2 * n_states, d_rows(ws),
+                    2 * B);
+  for (size_t b = 0; b < nB; ++b) {
+    const std::vector<uint32_t> h = check_guard<uint32_t>(stream_, "online_pcm_step: row " + std::to_string(b), d_rows(ws) + 2 * b * row, kSentinel32,
+                                                         result_geom(1, 1, (int)row, (int)row, 1));
+    std::memcpy(samples + b * row, h.data(), row * 4);
+    check_guard<uint32_t>(stream_, "online_pcm_step: behind row " + std::to_string(b), d_rows(ws) + (2 * b + 1) * row, kSentinel32,
+                          untouched_geom((int64_t)row));
+  }
+  std::vector<uint32_t> hs2(d_state.count);
+  download(stream_, hs2.data(), (const uint32_t*)d_state(ws), hs2.size());
+  PF_HIP(hipStreamSynchronize(stream_));
+  for (size_t k = 0; k < nS; ++k) {
+    for (size_t i = 0; i < sb / 4; ++i)
+      PF_CHECK(hs2[(2 * k + 1) * sb / 4 + i] == kSentinel32, PF_ERR_DEVICE, "online_pcm_step: behind state block " + std::to_string(k) + ": a cell was written");
+    std::memcpy((char*)states + k * sb, &hs2[2 * k * sb / 4], sb);
+  }
+}
+
 void Engine::vad_segment(const float* const* samples, const int64_t* n, int B, const pf_vad_config* cfg, int32_t* seg, int cap,
                          int32_t* n_seg) {
   vad_check(cfg, fc_.lfr_n);

@@ -1,5 +1,6 @@
 // hostutil.cpp — see hostutil.h
 #include "hostutil.h"
+#include "decode_blocks.h"
 
 #include <numeric>
 #include "lm.h"
@@ -535,6 +536,136 @@ std::vector<float> resample_sinc(const std::vector<float>& src, int sr_in, int s
   std::vector<float> out((size_t)std::max((int64_t)r, (int64_t)0));
   resample_sinc_mono(mono->data(), (int64_t)mono->size(), bank, out.data(), (int64_t)out.size());
   return out;
+}
+
+// ---- the PCM intake in pieces (hostutil.h) ----
+PcmStream::PcmStream(const pf_pcm_desc& d, int fs, const pf_resample_config* rs) : d_(d), fs_(fs) {
+  plan_ = pcm_plan(d, fs, 0);
+  const pf_resample_config c = cfg_ = resample_check(rs);
+  frame_bytes_ = plan_.bytes_per_value * (plan_.downmix ? 2 : 1);
+  if (plan_.sinc) bank_ = resample_bank(d.sample_rate, fs, c);
+}
+
+void PcmStream::append(const void* bytes, int64_t n) {
+  PF_CHECK(n >= 0 && (n == 0 || bytes), PF_ERR_INVALID_ARG, "pcm stream: bad arguments");
+  PF_CHECK(!closed_, PF_ERR_INVALID_ARG, "pcm stream: bytes after the end of the input");
+  const int64_t held = q_first_ * frame_bytes_ + (int64_t)q_.size();
+  PF_CHECK((held + n) / plan_.bytes_per_value <= INT32_MAX, PF_ERR_INVALID_ARG, "pcm: value count must be in [0, 2^31 - 1]");
+  q_.insert(q_.end(), (const unsigned char*)bytes, (const unsigned char*)bytes + n);
+  arrived_ = q_first_ + (int64_t)q_.size() / frame_bytes_;
+}
+
+void PcmStream::close() {
+  closed_ = true;
+  q_.resize((size_t)((arrived_ - q_first_) * frame_bytes_));      // the partial frame and the unpaired stereo value are dropped
+}
+
+int64_t PcmStream::n_out_of(int64_t n) const {
+  if (!plan_.resample) return n;
+  return n == 0 ? 0 : std::max((int64_t)std::nearbyint((double)n / plan_.ratio), (int64_t)0);     // pcm_plan's length
+}
+
+int64_t PcmStream::lo_frame(int64_t i) const {
+  if (!plan_.resample) return i;
+  if (plan_.sinc) return i * plan_.M / plan_.L - bank_.H + 1;
+  return (int64_t)((double)i * plan_.ratio);
+}
+
+int64_t PcmStream::hi_frame(int64_t i) const {
+  if (!plan_.resample) return i;
+  if (plan_.sinc) return i * plan_.M / plan_.L + bank_.H;
+  return (int64_t)((double)i * plan_.ratio) + 1;
+}
+
+int64_t PcmStream::n_final() const {
+  const int64_t n = arrived_, cap = n_out_of(n);
+  if (closed_) return cap;
+  int64_t c = n;                                                  // outputs whose highest frame is below n
+  if (plan_.sinc) {
+    const int64_t a = n - bank_.H;                                // (i M) / L <= a - 1
+    c = a >= 1 ? (a * plan_.L - 1) / plan_.M + 1 : 0;
+  } else if (plan_.resample) {
+    c = n < 2 ? 0 : (int64_t)((double)(n - 1) / plan_.ratio);     // an estimate, then the rule's own arithmetic decides
+    while (c > 0 && hi_frame(c - 1) > n - 1) --c;
+    while (n >= 2 && hi_frame(c) <= n - 1) ++c;
+  }
+  return std::min(c, cap);
+}
+
+void PcmStream::trim(int64_t first) {
+  first = std::min(std::max(first, q_first_), arrived_);
+  q_.erase(q_.begin(), q_.begin() + (long)((first - q_first_) * frame_bytes_));
+  q_first_ = first;
+}
+
+void PcmStream::mono(int64_t first, int64_t n, float* out) const {
+  PF_CHECK(first >= q_first_ && n >= 0 && first + n <= arrived_, PF_ERR_DEVICE, "pcm stream: a frame that is no longer kept");
+  const unsigned char* p = q_.data() + (size_t)((first - q_first_) * frame_bytes_);
+  if (!plan_.downmix) { pcm_decode(p, (size_t)n, d_.format, out); return; }
+  std::vector<float> x((size_t)(2 * n));
+  pcm_decode(p, x.size(), d_.format, x.data());
+  for (int64_t i = 0; i < n; ++i) out[i] = (x[2 * i] + x[2 * i + 1]) * 0.5f;
+}
+
+std::vector<float> PcmStream::take(int64_t n_max) {
+  PF_CHECK(mode_ != 2 && n_max >= 0, PF_ERR_INVALID_ARG, "pcm stream: take on a stream that is cut into device steps");
+  mode_ = 1;
+  const int64_t n = std::min(n_max, n_final() - taken_), last = arrived_ - 1;
+  std::vector<float> out((size_t)n);
+  if (n > 0) {
+    const int64_t lo = std::max(std::min(lo_frame(taken_), last), (int64_t)0), hi = std::min(hi_frame(taken_ + n - 1), last);
+    std::vector<float> mv((size_t)(hi - lo + 1));
+    mono(lo, (int64_t)mv.size(), mv.data());
+    const auto m = [&](int64_t g) { return mv[(size_t)(g - lo)]; };   // frame g
+    for (int64_t k = 0; k < n; ++k) {
+      const int64_t i = taken_ + k;
+      if (!plan_.resample) { out[k] = m(i); continue; }
+      if (!plan_.sinc) {                                          // resample_linear's statement
+        const double pos = (double)i * plan_.ratio;
+        const int64_t idx = (int64_t)pos;
+        const double fr = pos - (double)idx;
+        if (idx >= last) { out[k] = m(last); continue; }
+        out[k] = (float)((1 - fr) * m(idx) + fr * m(idx + 1));
+        continue;
+      }
+      const int64_t pos = i * (int64_t)bank_.M, b = pos / bank_.L;  // resample_sinc_mono's
+      const float* h = bank_.h.data() + (size_t)(pos % bank_.L) * bank_.stride;
+      float acc = 0.0f;
+      for (int t = 0; t < bank_.taps; ++t) {
+        const int64_t j = b - bank_.H + 1 + t;
+        acc = std::fmaf(h[t], (j >= 0 && j <= last) ? m(j) : 0.0f, acc);
+      }
+      out[k] = acc;
+    }
+  }
+  taken_ += n;
+  trim(std::max(std::min(lo_frame(taken_), arrived_ - 1), (int64_t)0));   // the last frame always stays: the linear rule's end reads it
+  return out;
+}
+
+PcmStreamStep PcmStream::cut(int64_t n_max) {
+  PF_CHECK(mode_ != 1 && n_max >= 0, PF_ERR_INVALID_ARG, "pcm stream: cut on a stream that is converted on the host");
+  mode_ = 2;
+  PcmStreamStep s;
+  const int64_t n = std::min(n_max, n_final() - taken_), last = arrived_ - 1;
+  s.o0 = taken_; s.n_out = (int32_t)n; s.in_first = q_first_; s.n_total = closed_ ? arrived_ : -1;
+  s.tail_parity = tail_parity_; s.tail_len = (int32_t)(q_first_ - tail_first_);
+  if (n > 0) {
+    const int64_t lo = std::min(lo_frame(taken_), last);
+    PF_CHECK(lo < 0 || lo >= tail_first_, PF_ERR_DEVICE, "pcm stream: a frame below the carried tail");
+    s.n_new = (int32_t)std::max(std::min(hi_frame(taken_ + n - 1), last) + 1 - q_first_, (int64_t)0);
+    s.raw.assign(q_.begin(), q_.begin() + (long)((int64_t)s.n_new * frame_bytes_));
+  }
+  taken_ += n;
+  const int64_t dev_end = q_first_ + s.n_new;                     // the device holds the frames below it after the step
+  const int64_t nf = std::min(std::max(std::min(lo_frame(taken_), dev_end - 1), tail_first_), dev_end);
+  s.next_first = nf; s.next_len = (int32_t)(dev_end - nf);
+  PF_CHECK(dev_end - nf <= (int64_t)kPcmStreamTail, PF_ERR_UNSUPPORTED, "pcm stream: the next output reaches back over more than 1024 frames");
+  s.write_tail = (s.n_new > 0 || nf != tail_first_) ? 1 : 0;
+  if (s.write_tail) tail_parity_ ^= 1;
+  tail_first_ = nf;
+  trim(dev_end);
+  return s;
 }
 
 std::vector<float> get_file_sample(const std::string& path, double* duration_ms) {

@@ -73,6 +73,59 @@ ResampleBank resample_bank(int sr_in, int sr_out, const pf_resample_config& cfg)
 void resample_sinc_mono(const float* m, int64_t n_mono, const ResampleBank& bank, float* out, int64_t n_out);
 // resample_linear's down-mix and length with that chain
 std::vector<float> resample_sinc(const std::vector<float>& src, int sr_in, int sr_out, int channels, const pf_resample_config& cfg);
+// ---- the PCM intake in pieces (paraformer_hip.h "Streaming PCM intake") ----
+// One stream's converter: raw bytes arrive in any cut, outputs leave once they are FINAL, and the total is bit for bit
+// pcm_to_samples over the concatenated bytes.  A "frame" is what one mono sample is decoded from (two values under the down-mix);
+// a trailing partial frame waits for its remainder.  Output i is final when (a) every frame its rule reads has arrived
+// (band-limited: up to (i M) / L + H; linear: (int)(i ratio) + 1; copy: i) and (b) i < n_out(frames arrived), pcm_plan's length,
+// which never shrinks.  close() makes the rest final with the one-shot's end (+0 beyond the sequence multiplied in; m[last];
+// the unpaired trailing stereo value dropped).  Only the bytes that an output not yet taken can still read are kept.
+// Two ways to take the final outputs, never mixed on one object (PF_ERR_INVALID_ARG):
+//   take  converts them here, the host twin: the one-shot's helpers and arithmetic on the kept frames;
+//   cut   describes them as ONE step of k_pcm_stream.hip: the frames to upload beyond the tail the device already holds, where the
+//         outputs start, and the tail the step leaves (the frames the next output can still read, at most kPcmStreamTail).
+struct PcmStreamStep {
+  int64_t o0 = 0, in_first = 0, n_total = -1, next_first = 0;   // first output; first uploaded frame; total frames (-1: open)
+  int32_t n_out = 0, n_new = 0, tail_parity = 0, tail_len = 0, next_len = 0, write_tail = 0;
+  std::vector<unsigned char> raw;                                 // frames [in_first, in_first + n_new)
+};
+class PcmStream {
+ public:
+  PcmStream(const pf_pcm_desc& d, int fs, const pf_resample_config* rs);   // validated as pcm_plan / resample_bank validate
+  void append(const void* bytes, int64_t n);                      // PF_ERR_INVALID_ARG after close, or beyond 2^31 - 1 values
+  void close();
+  bool closed() const { return closed_; }
+  int64_t n_final() const;                                        // outputs that are final, taken ones included
+  int64_t n_taken() const { return taken_; }
+  std::vector<float> take(int64_t n_max = INT64_MAX);
+  PcmStreamStep cut(int64_t n_max);
+  std::vector<float> push(const void* bytes, int64_t n) { append(bytes, n); return take(); }
+  std::vector<float> finish() { close(); return take(); }
+  const pf_pcm_desc& desc() const { return d_; }
+  int rule() const { return !plan_.resample ? 0 : plan_.sinc ? 2 : 1; }     // copy, linear, band-limited
+  bool downmix() const { return plan_.downmix; }
+  double ratio() const { return plan_.ratio; }
+  const ResampleBank& bank() const { return bank_; }
+  const pf_resample_config& config() const { return cfg_; }
+  int fs() const { return fs_; }
+ private:
+  int64_t n_out_of(int64_t n_frames) const;
+  int64_t lo_frame(int64_t i) const;                              // the lowest / highest frame output i reads (unclamped)
+  int64_t hi_frame(int64_t i) const;
+  void trim(int64_t first);                                       // forget the frames below `first`
+  void mono(int64_t first, int64_t n, float* out) const;          // frames [first, first + n) decoded and down-mixed
+  pf_pcm_desc d_;
+  pf_resample_config cfg_;
+  int fs_ = 0;
+  PcmPlan plan_;                                                  // of an empty sequence: the rule, the ratio, L and M
+  ResampleBank bank_;
+  int frame_bytes_ = 1, mode_ = 0;                                // mode: 0 undecided, 1 take, 2 cut
+  bool closed_ = false;
+  std::vector<unsigned char> q_;                                  // the kept bytes: frames from q_first_ on, then a partial frame
+  int64_t q_first_ = 0, arrived_ = 0, taken_ = 0;                 // complete frames so far; outputs taken
+  int64_t tail_first_ = 0;                                        // cut: the device's tail is frames [tail_first_, q_first_)
+  int tail_parity_ = 0;
+};
 // Resample(sourceData, sourceSampleRate, targetSampleRate, sourceChannels) (:223-279): stereo -> mono
 // average first, then linear interpolation in double precision; target length = Round(n / ratio) (banker's)
 std::vector<float> resample_linear(const std::vector<float>& src, int sr_in, int sr_out, int channels);

@@ -529,6 +529,23 @@ struct ResampleJob { int64_t in_off, out_off, n_mono, n_out; const float* bank;
                      int32_t L, M, H, stride, format, downmix, tile, in_cap, gx, bank_lds; };
 void launch_resample_sinc(hipStream_t s, const ResampleJob* jobs_dev, const ResampleJob* jobs_host, int B, const void* raw, float* samples);
 void launch_resample_sinc_one(hipStream_t s, const ResampleJob& job, const void* raw, float* samples);
+// ---------------------------------------------------------------- streaming PCM intake (k_pcm_stream.hip) ------
+// paraformer_hip.h "Streaming PCM intake"; the host statement is PcmStream::take (hostutil.cpp), bit for bit.
+// One stream's step (PcmStream::cut): outputs o0 .. o0 + n_out - 1 of the stream go to samples + row * kPcmStreamRow, cells
+// [n_out, kPcmStreamRow) of the row are written as +0.  Mono frame g of the stream is: +0 for g < 0 or (n_total >= 0 and
+// g >= n_total); cell g - (in_first - tail_len) of buffer tail_parity of the stream's PcmStreamBlock (states + slot * stride) for
+// g < in_first; frame g - in_first of the n_new raw frames at raw + raw_off (16-byte aligned) otherwise.  rule: 0 copy, 1 the
+// linear rule at `ratio`, 2 the band-limited rule over `bank` (L, M, H, stride as ResampleJob).  write_tail: workgroup 0 of the
+// stream writes frames [next_first, next_first + next_len) into the OTHER tail buffer.  tile: outputs per tile, a power of two
+// <= PF_RESAMPLE_TILE whose input span fits kResampleInCap floats of LDS.
+constexpr int kPcmStreamRow = 9600;
+struct PcmStreamJob { const float* bank; double ratio; int64_t raw_off, in_first, o0, n_total, next_first;
+                      int32_t row, slot, n_new, n_out, tail_parity, tail_len, next_len, write_tail,
+                      format, downmix, rule, L, M, H, stride, tile; };
+void pcm_stream_fit(PcmStreamJob& j);                      // sets j.tile from the rule's fields
+// jobs_host: the same B entries on the host (checked here, PF_ERR_INVALID_ARG; sizes the grid); raw_bytes: what `raw` holds
+void launch_pcm_stream(hipStream_t s, const PcmStreamJob* jobs_dev, const PcmStreamJob* jobs_host, int B, const void* raw, int64_t raw_bytes,
+                       char* states, int64_t state_stride, int n_slots, float* samples, int n_rows);
 // The filter shape and the device banks built from it, one per input rate, on first use; set() drops them.  Thread-safe.
 struct ResampleBankDev { int L = 1, M = 1, H = 0, stride = 1; float* dev = nullptr; };
 class ResampleBanks {

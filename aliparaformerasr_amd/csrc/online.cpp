@@ -253,6 +253,68 @@ const std::vector<pf_online_token>& OnlineStreamM::token_info() {
 void OnlineStreamM::AddSamples(const float* samples, int64_t n) {
   if (disposed) throw Error(PF_ERR_DISPOSED, "OnlineStream");
   if (!samples) throw Error(PF_ERR_NULL_SAMPLES, "source");
+  {
+    std::lock_guard<std::mutex> lk(mu);
+    PF_CHECK(!pcm_, PF_ERR_INVALID_ARG, "OnlineStream: AddSamples on a stream that is fed by AddPcm");
+    sample_fed_ = true;
+  }
+  add_samples_(samples, n);
+}
+
+void OnlineStreamM::AddPcm(const void* data, int64_t n_bytes, const pf_pcm_desc& d) {
+  if (disposed) throw Error(PF_ERR_DISPOSED, "OnlineStream");
+  PF_CHECK(n_bytes >= 0 && (data || n_bytes == 0), PF_ERR_INVALID_ARG, "OnlineStream: AddPcm: null data");
+  {
+    std::lock_guard<std::mutex> lk(mu);
+    PF_CHECK(!sample_fed_, PF_ERR_INVALID_ARG, "OnlineStream: AddPcm on a stream that is fed by AddSamples");
+    PF_CHECK(!finished_, PF_ERR_INVALID_ARG, "OnlineStream: AddPcm after InputFinished");
+    PF_CHECK(!pcm_failed_, PF_ERR_RECOGNITION, "OnlineStream: AddPcm: the stream's PCM intake failed in an earlier GetResults");
+    if (!pcm_) {
+      const pf_resample_config cfg = owner->resample_config();
+      pcm_.reset(new PcmStream(d, owner->conf().fs > 0 ? owner->conf().fs : 16000, &cfg));
+    } else {
+      PF_CHECK(std::memcmp(&d, &pcm_->desc(), sizeof(d)) == 0, PF_ERR_INVALID_ARG, "OnlineStream: AddPcm: the descriptor differs from the stream's first");
+    }
+  }
+  if (take_audio()) {                                           // the bytes wait; no engine mutex, no device call
+    std::lock_guard<std::mutex> lk(mu);
+    pcm_->append(data, n_bytes);
+    CutPcmChunk();
+    return;
+  }
+  std::vector<float> v;
+  {
+    std::lock_guard<std::mutex> lk(mu);
+    v = pcm_->push(data, n_bytes);
+  }
+  const float none = 0.f;
+  add_samples_(v.empty() ? &none : v.data(), (int64_t)v.size());
+}
+
+// ONE chunk per call once more than a chunk is cached, the constructor's chunk of silence first: what add_samples_ does with the
+// samples, done with their count.  Chunk c >= 1 is outputs [(c - 1) 9600, c 9600) of the converter.
+bool OnlineStreamM::CutPcmChunk() {
+  const int64_t chunk = (int64_t)160 * owner->chunk_length();
+  const bool silence = chunks_in_ == 0;
+  const int64_t cached = (silence ? chunk : 0) + pcm_->n_final() - pcm_->n_taken();
+  if (finished_ ? cached == 0 : cached <= chunk) return false;
+  pcm_chunks_.push_back(pcm_->cut(silence ? 0 : chunk));
+  ++chunks_in_;
+  note_rows(silence ? 0 : (size_t)pcm_chunks_.back().n_out, owner->chunk_length());
+  return true;
+}
+
+bool OnlineStreamM::PopPcmChunk(PcmStreamStep& dst) {
+  std::lock_guard<std::mutex> lk(mu);
+  if (pcm_chunks_.empty()) return false;
+  note_chunk(fe_spliced_, (int)kFrontendStreamFrames);
+  fe_spliced_ = true;
+  dst = std::move(pcm_chunks_.front());
+  pcm_chunks_.pop_front();
+  return true;
+}
+
+void OnlineStreamM::add_samples_(const float* samples, int64_t n) {
   std::vector<float> s;
   size_t n_caller = 0;
   const bool dev = take_audio();
@@ -297,7 +359,7 @@ bool OnlineStreamM::PopRawChunk(std::vector<float>& dst) {
 }
 
 bool OnlineStreamM::chunk_pending() const {
-  return fed_dev_ ? !raw_chunks_.empty() : Speech.size() >= (size_t)owner->chunk_length() * 80;
+  return fed_dev_ ? !raw_chunks_.empty() || !pcm_chunks_.empty() : Speech.size() >= (size_t)owner->chunk_length() * 80;
 }
 
 // the provenance of a chunk's t80 fbank rows (frame r starts at first + 160 r); true: the first frame is repeated once (:131-143)
@@ -334,6 +396,18 @@ void OnlineStreamM::InputFinished() {
   if (disposed) throw Error(PF_ERR_DISPOSED, "OnlineStream");
   const size_t chunk = (size_t)160 * owner->chunk_length();
   const bool dev = take_audio();
+  if (pcm_ && dev) {                                            // the converter's rest in chunks, the last one short (its row is padded on the device)
+    std::lock_guard<std::mutex> lk(mu);
+    finished_ = true;
+    pcm_->close();
+    while (CutPcmChunk()) {}
+    return;
+  }
+  if (pcm_) {                                                   // the converter's rest through AddSamples, then the tail as ever
+    std::vector<float> v;
+    { std::lock_guard<std::mutex> lk(mu); if (!finished_) v = pcm_->finish(); }
+    if (!v.empty()) add_samples_(v.data(), (int64_t)v.size());
+  }
   for (;;) {
     std::vector<float> s;
     size_t n_caller = 0;
@@ -466,6 +540,9 @@ void OnlineRecognizerM::Dispose() {
     if (pn_states_) { hipSetDevice(e->device()); hipFree(pn_states_); pn_states_ = nullptr; }
     if (pn_ws_) { hipSetDevice(e->device()); hipFree(pn_ws_); pn_ws_ = nullptr; pn_ws_bytes_ = 0; }
     if (fe_states_) { hipSetDevice(e->device()); hipFree(fe_states_); fe_states_ = nullptr; }
+    if (pcm_states_) { hipSetDevice(e->device()); hipFree(pcm_states_); pcm_states_ = nullptr; }
+    hipSetDevice(e->device());
+    resample_.clear();
     pn_model_.reset();
     pn_on_ = false;
     ep_model_.reset();
@@ -593,6 +670,16 @@ bool OnlineRecognizerM::note_fed() {
   return fe_on_.load();
 }
 
+void OnlineRecognizerM::SetResample(const pf_resample_config* cfg) {
+  if (disposed_) throw Error(PF_ERR_DISPOSED, "OnlineRecognizer");
+  std::shared_ptr<Engine> eh = engine();
+  if (!eh) throw Error(PF_ERR_DISPOSED, "OnlineRecognizer");
+  std::lock_guard<std::mutex> lk(eh->mutex());
+  PF_HIP(hipSetDevice(eh->device()));
+  PF_HIP(hipStreamSynchronize(eh->stream()));                   // (no launch still reads a bank that set() frees)
+  resample_.set(cfg);
+}
+
 void OnlineRecognizerM::SetDeviceFrontend(bool on) {
   if (disposed_) throw Error(PF_ERR_DISPOSED, "OnlineRecognizer");
   std::shared_ptr<Engine> eh = engine();
@@ -615,6 +702,11 @@ void OnlineRecognizerM::SetDeviceFrontend(bool on) {
     PF_HIP(hipStreamSynchronize(eh->stream()));
     PF_HIP(hipFree(fe_states_));
     fe_states_ = nullptr;
+  }
+  if (pcm_states_) {                                            // (no stream is alive that has taken audio: none holds a tail)
+    PF_HIP(hipStreamSynchronize(eh->stream()));
+    PF_HIP(hipFree(pcm_states_));
+    pcm_states_ = nullptr;
   }
   fe_bytes_ = on ? eh->online_frontend_slot_bytes() : 0;
   if (on && ep_cap_ > 0) PF_HIP(hipMalloc((void**)&fe_states_, (size_t)ep_cap_ * fe_bytes_));   // (a block is zeroed where a stream takes its slot)
@@ -644,6 +736,7 @@ void OnlineRecognizerM::ensure_slot(OnlineStreamM* s, Engine* e) {
     if (ti_on_) grow_slots(e, ti_states_, ep_cap_, cap, ti_bytes_);              // and so does the decoder state
     if (pn_model_) grow_slots(e, pn_states_, ep_cap_, cap, pn_bytes_);           // and the punctuation state
     if (fe_on_) grow_slots(e, fe_states_, ep_cap_, cap, fe_bytes_);              // and the front-end's block
+    if (pcm_states_) grow_slots(e, pcm_states_, ep_cap_, cap, pcm_bytes_);       // and the PCM intake's tails
     for (int i = cap - 1; i >= ep_cap_; --i) ep_free_.push_back(i);
     ep_cap_ = cap;
   }
@@ -886,10 +979,20 @@ void OnlineRecognizerM::Forward(const std::vector<OnlineStreamM*>& streams) {
 // Forward with SetDeviceFrontend: one raw chunk per stream that has one, the front-end's two launches into the engine's speech buffer
 // (Engine::online_frontend), then the device form of the chunk step.  Only the samples go up.
 void OnlineRecognizerM::ForwardFrontend(const std::vector<OnlineStreamM*>& streams) {
-  std::vector<OnlineStreamM*> work;
+  std::vector<OnlineStreamM*> work, pwork;                      // the sample-fed streams, then the PCM-fed ones: their rows come last
   std::vector<float> samples;
-  for (OnlineStreamM* s : streams)
-    if (s->PopRawChunk(samples)) work.push_back(s);             // what GetDecodeChunk consumes: one chunk per stream per call
+  std::vector<PcmStreamStep> steps;
+  for (OnlineStreamM* s : streams) {                            // (before any chunk is popped)
+    std::lock_guard<std::mutex> ls(s->mu);
+    if (s->pcm_failed_) throw Error(PF_ERR_RECOGNITION, "Online recognition failed: a stream's PCM intake failed in an earlier GetResults");
+  }
+  for (OnlineStreamM* s : streams) {
+    PcmStreamStep st;
+    if (s->PopPcmChunk(st)) { pwork.push_back(s); steps.push_back(std::move(st)); }
+    else if (s->PopRawChunk(samples)) work.push_back(s);        // what GetDecodeChunk consumes: one chunk per stream per call
+  }
+  const int Bs = (int)work.size(), Bp = (int)pwork.size();
+  work.insert(work.end(), pwork.begin(), pwork.end());
   if (work.empty()) return;
   try {
     std::shared_ptr<Engine> eh = engine();
@@ -905,12 +1008,25 @@ void OnlineRecognizerM::ForwardFrontend(const std::vector<OnlineStreamM*>& strea
       slot[(size_t)b] = s->slot_; reset[(size_t)b] = s->fe_reset_ ? 1 : 0;
     }
     char* states = nullptr;
-    { std::lock_guard<std::mutex> ls(ep_mu_); states = fe_states_; }
+    char* pstates = nullptr;
+    int n_slots = 0;
+    {
+      std::lock_guard<std::mutex> ls(ep_mu_);
+      states = fe_states_;
+      if (Bp > 0 && !pcm_states_) {                             // the tails' buffer: made by the first PCM-fed chunk (a new stream reads none of it)
+        pcm_bytes_ = e->online_pcm_slot_bytes();
+        PF_HIP(hipMalloc((void**)&pcm_states_, (size_t)ep_cap_ * pcm_bytes_));
+      }
+      pstates = pcm_states_; n_slots = ep_cap_;
+    }
     PF_CHECK(states != nullptr, PF_ERR_DEVICE, "device front-end: no state buffer");
-    e->online_frontend(samples.data(), B, states, slot.data(), reset.data());
+    std::vector<Engine::OnlinePcmIn> pin((size_t)Bp);
+    for (int p = 0; p < Bp; ++p) pin[(size_t)p] = Engine::OnlinePcmIn{pwork[(size_t)p]->pcm_.get(), &steps[(size_t)p], pwork[(size_t)p]->slot_};
+    e->online_frontend_pcm(samples.data(), Bs, pin.data(), Bp, resample_, pstates, n_slots, states, slot.data(), reset.data());
     for (OnlineStreamM* s : work) { std::lock_guard<std::mutex> ls(s->mu); s->fe_reset_ = false; }
     ForwardDevice(e, work, nullptr, 20);
   } catch (const Error& ex) {
+    for (OnlineStreamM* s : pwork) { std::lock_guard<std::mutex> ls(s->mu); s->pcm_failed_ = true; }   // (online.h: host and device tails may differ now)
     if (ex.code == PF_ERR_RECOGNITION && std::string(ex.what()).rfind("Online recognition failed", 0) == 0) throw;
     throw Error(PF_ERR_RECOGNITION, std::string("Online recognition failed: ") + ex.what());
   }

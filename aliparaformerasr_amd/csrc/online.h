@@ -73,6 +73,12 @@ class OnlineStreamM {
   explicit OnlineStreamM(std::shared_ptr<OnlineRecognizerM> r);
   ~OnlineStreamM();
   void AddSamples(const float* samples, int64_t n);           // OnlineStream.cs:79-105
+  // Streaming PCM intake (paraformer_hip.h "Streaming PCM intake"; no counterpart in the reference): raw bytes of
+  // the format `d` names, in any cut.  The stream's converter (hostutil.h PcmStream) makes the samples final; with the host
+  // front-end they go through AddSamples, with SetDeviceFrontend the bytes wait on the stream and are converted in front of the
+  // fbank launch of the GetResults that takes their chunk.  PF_ERR_INVALID_ARG: AddSamples and AddPcm on one stream, a
+  // descriptor that differs from the stream's first, audio after InputFinished.
+  void AddPcm(const void* data, int64_t n_bytes, const pf_pcm_desc& d);
   // ---- endpointing (OnlineRecognizerM::SetEndpoint; paraformer_hip.h "Streaming endpointing"; no counterpart in the reference)
   // The input is complete: every cached chunk goes through InputSpeech, the samples short of a chunk zero-padded to one (the
   // online model then decodes the tail too); the GetResults that has decoded the last chunk flushes the detector.  A later
@@ -122,6 +128,15 @@ class OnlineStreamM {
   // SetDeviceFrontend: the cut chunks wait as samples (raw_chunks_) for Forward, which pops one per call; the stream's features,
   // splice rows and start_idx live in its slot's FrontendStreamBlock, fe_reset_ asks the next step to reset that block
   bool take_audio();
+  void add_samples_(const float* samples, int64_t n);         // AddSamples behind its refusals
+  std::unique_ptr<PcmStream> pcm_;                            // AddPcm: the stream's converter, made by its first call
+  bool sample_fed_ = false;                                   // AddSamples was called
+  std::deque<PcmStreamStep> pcm_chunks_;                      // AddPcm with SetDeviceFrontend: the cut chunks as device steps
+  // cut() has advanced the converter's view of the device tail before the launch that writes it.  A GetResults that failed between
+  // popping a step and issuing its launch leaves the two apart, so it sets this, and AddPcm and every later GetResults refuse the stream.
+  bool pcm_failed_ = false;
+  bool CutPcmChunk();                                         // AddSamples' rule on the converter's final outputs (the caller holds mu)
+  bool PopPcmChunk(PcmStreamStep& dst);
   void QueueChunk(std::vector<float>&& samples, size_t n_caller);
   bool PopRawChunk(std::vector<float>& dst);                  // appends the oldest queued chunk to dst; false: none
   bool chunk_pending() const;                                 // a chunk is waiting for a GetResults (the caller holds mu)
@@ -199,6 +214,10 @@ class OnlineRecognizerM : public std::enable_shared_from_this<OnlineRecognizerM>
   // snip_edges, a chunk length other than 60, a geometry other than 80 mels with LFR 7 / 6.  While it is on, SetEndpoint and
   // SetTokenInfo(false) are refused.
   void SetDeviceFrontend(bool on);
+  // the shape of the band-limited resampler for streams whose first AddPcm follows (pf_online_recognizer_set_resample; null = the
+  // defaults); validated before anything changes
+  void SetResample(const pf_resample_config* cfg);
+  pf_resample_config resample_config() { return resample_.config(); }
   bool device_frontend_on() const { return fe_on_.load(); }
   bool note_fed();                                            // a stream takes its first audio; returns device_frontend_on()
   // Streaming punctuation (paraformer_hip.h "Punctuation, streaming"): loads a causal `.pfw` of kind
@@ -242,6 +261,9 @@ class OnlineRecognizerM : public std::enable_shared_from_this<OnlineRecognizerM>
   std::atomic<bool> fe_on_{false};
   char* fe_states_ = nullptr;                                 // [ep_cap_, fe_bytes_] on the device: FrontendStreamBlock per slot (SetDeviceFrontend)
   size_t fe_bytes_ = 0;
+  char* pcm_states_ = nullptr;                                // [ep_cap_, pcm_bytes_] on the device: PcmStreamBlock per slot, made by the first PCM-fed chunk
+  size_t pcm_bytes_ = 0;
+  ResampleBanks resample_;                                    // AddPcm's banks on the device (its own lock)
   int fed_live_ = 0;                                          // live streams that have taken audio
   int ep_live_ = 0, decoded_live_ = 0;                        // live streams that have fed the detector / decoded a chunk
   std::mutex mu_;

@@ -2,7 +2,7 @@
 
     python -m aliparaformerasr_amd.examples -type offline -method batch -base <dir> -model <name> \
         [-accuracy int8] [-threads 2] [-decode ctc|frames] [-intake host|device] [-resample linear|sinc] [-nbest N [-topk K] [-beam W | -search W] [-hotboost S] [-lm FILE [-lmweight A] [-lmbonus B] [-lmeos]]] [-align FILE|beam] [-vad [key=value,...] [-vadmodel FILE] [-spk FILE[,cluster=device] [key=value,...]]] [-punc FILE] -files a.wav b.wav
-    python -m aliparaformerasr_amd.examples -type online -method one -base <dir> -model <name> [-endpoint [key=value,...] [-vadmodel FILE] [-secondpass <offline name>]] [-tokentimes [-devicefrontend]] [-puncstream FILE[,max_context=N]] -files a.wav
+    python -m aliparaformerasr_amd.examples -type online -method one -base <dir> -model <name> [-endpoint [key=value,...] [-vadmodel FILE] [-secondpass <offline name>]] [-tokentimes [-devicefrontend]] [-puncstream FILE[,max_context=N]] [-intake host|device] [-resample linear|sinc] -files a.wav
 
 Mirrors (file:line in /root/reference/AliParaformerAsr.Examples):
   * argument handling and defaults — Program.cs:93-104, ParseArgs :197-252: the MANYSPEECH_BASE / _TYPE / _BATCH / _MODEL /
@@ -27,6 +27,9 @@ OfflineStream.AddPcm raw: decode, down-mix and resample run on the device and gi
 `-resample sinc` (offline; not in the reference) resamples files that are not at 16 kHz with the band-limited polyphase filter
 instead of the reference's linear interpolation — on the GPU with `-intake device`, by its host twin with `-intake host`: the
 same samples either way.  `-resample linear` is the default.
+`-type online -intake device [-resample sinc]` (not in the reference) reads only the wav header on the host and hands the payload
+to OnlineStream.AddPcm in pieces of 0.6 s of the file's own format and rate, then InputFinished: the stream's converter makes the
+16 kHz samples, on the device in front of the fbank with `-devicefrontend`, by its host twin without.
 `-nbest N [-topk K]` (offline, paraformer models; OfflineRecognizer.SetNBest) prints under each result line the N best
 hypotheses, one `nbest[i] score:<sum of log-probs> text:<text>` line each, best first; line 0 is the result itself.
 `-nbest N -beam W` (offline, SenseVoice models; OfflineRecognizer.SetCtcBeam) prints the N best labelings of a CTC prefix
@@ -507,7 +510,7 @@ def token_times_line(info, names):
 
 def online_recognizer(method="one", model="speech_paraformer-large_asr_nat-zh-cn-16k-common-vocab8404-online-onnx",
                       accuracy="int8", threads=2, files=None, base=None, out=sys.stdout, endpoint=None, secondpass=None, vadmodel=None,
-                      tokentimes=False, puncstream=None, devicefrontend=False):
+                      tokentimes=False, puncstream=None, devicefrontend=False, intake="host", resample="linear"):
     from .online_recognizer import OnlineRecognizer
     base = base or os.getcwd()
     if not model:
@@ -569,6 +572,15 @@ def online_recognizer(method="one", model="speech_paraformer-large_asr_nat-zh-cn
         if not os.path.isfile(f):
             continue
         if is_audio_by_header(f):
+            if intake == "device":                          # the payload as it is, 0.6 s of whole frames a piece
+                raw, sr, ch, fmt, dur = get_file_pcm(f)
+                step_bytes = max(1, int(0.6 * sr)) * ch * N.PCM_FORMATS[fmt][1]
+                chunks = [(raw[i: i + step_bytes], sr, ch, fmt) for i in range(0, len(raw), step_bytes)]
+                if chunks:
+                    samples_list.append(chunks)
+                    total_ms += dur
+                n += 1
+                continue
             chunks, dur = get_file_chunk_samples(f)
             if chunks:
                 chunks += [np.zeros(400, np.float32) for _ in range(6)]          # :160-163
@@ -604,9 +616,12 @@ def online_recognizer(method="one", model="speech_paraformer-large_asr_nat-zh-cn
                     print("punctuated: " + st.Punctuated, file=out)
                 texts.append(r.Text)
             for c in chunks:
-                st.AddSamples(c)
+                if isinstance(c, tuple):
+                    st.AddPcm(c[0], c[1], c[2], c[3], resample=resample)
+                else:
+                    st.AddSamples(c)
                 step()
-            if endpoint is not None or puncstream:
+            if endpoint is not None or puncstream or intake == "device":
                 st.InputFinished()
                 for _ in range(3):                          # the padded tail, then the flush
                     step()
@@ -799,6 +814,8 @@ def parse_args(argv, env=None):
         raise ValueError("-puncstream goes with -type online")
     if "tokentimes" in cfg and cfg.get("recognizerType") != "online":
         raise ValueError("-tokentimes goes with -type online")
+    if "resample" in cfg and cfg.get("recognizerType") == "online" and cfg.get("intake") != "device":
+        raise ValueError("-resample goes with -intake device for -type online")
     if "devicefrontend" in cfg and ("tokentimes" not in cfg or "endpoint" in cfg):
         raise ValueError("-devicefrontend goes with -tokentimes and not with -endpoint")
     if "vadmodel" in cfg and "vad" not in cfg and "endpoint" not in cfg:
@@ -820,7 +837,8 @@ def main(argv=None):
         online_recognizer(cfg["methodType"], cfg["modelName"], cfg["modelAccuracy"], cfg["threads"], cfg["files"],
                           cfg["modelBasePath"] or None, endpoint=cfg.get("endpoint"), secondpass=cfg.get("secondpass"),
                           vadmodel=cfg.get("vadmodel"), tokentimes=bool(cfg.get("tokentimes")), puncstream=cfg.get("puncstream"),
-                          devicefrontend=bool(cfg.get("devicefrontend")))
+                          devicefrontend=bool(cfg.get("devicefrontend")), intake=cfg.get("intake", "host"),
+                          resample=cfg.get("resample", "linear"))
     elif cfg["recognizerType"] == "offline":
         offline_recognizer(cfg["methodType"], cfg["modelName"], cfg["modelAccuracy"], cfg["threads"], cfg["files"],
                            cfg["modelBasePath"] or None, decode=cfg.get("decode", "frames"), intake=cfg.get("intake", "host"),

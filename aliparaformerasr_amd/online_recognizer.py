@@ -131,6 +131,20 @@ class OnlineStream:
         x = np.ascontiguousarray(samples, dtype=np.float32)
         _ck(self._lib.pf_online_stream_add_samples(self._h, x.ctypes.data_as(C.POINTER(C.c_float)), x.shape[0]))
 
+    def AddPcm(self, data, sample_rate: int, channels: int = 1, format: str = "s16", downmix: bool = False,
+               resample: str = "linear") -> None:
+        """AddSamples for audio as callers hold it (pf_online_stream_add_pcm; not in the reference): raw bytes of any PCM format
+        ("u8", "s16", "s24", "s32", "f32", "f64", "alaw", "mulaw") at any rate, mono or stereo, cut anywhere — even inside a
+        value.  For every cut the recognised samples are those of the one-shot conversion of all the bytes; an output waits
+        until the frames it reads have arrived (resample="sinc": about 3 ms at 8 kHz) or InputFinished is called.  With
+        SetDeviceFrontend the bytes are converted on the device in front of the fbank.  One stream takes AddSamples or AddPcm,
+        never both, and one descriptor.  Not validated on speech."""
+        if resample not in ("linear", "sinc"):
+            raise ValueError('AddPcm: resample takes "linear" or "sinc"')
+        desc = N.pcm_desc(sample_rate, channels, format, downmix, sinc=resample == "sinc")
+        raw = np.frombuffer(bytes(data if data is not None else b""), np.uint8)
+        _ck(self._lib.pf_online_stream_add_pcm(self._h, raw.ctypes.data if raw.size else None, raw.size, C.byref(desc)))
+
     @property
     def Tokens(self) -> List[int]:
         p, n = C.POINTER(C.c_int64)(), C.c_int32()
@@ -181,6 +195,12 @@ class OnlineRecognizer:
         (endpointing on this path is a follow-up), once a live stream has taken audio, with snip_edges, and for a geometry other
         than 80 mels with LFR 7 / 6; while it is on, SetEndpoint and SetTokenInfo(False) are refused."""
         _ck(self._lib.pf_online_recognizer_set_device_frontend(self._h, 1 if on else 0))
+
+    def SetResample(self, zeros=None, rolloff=None, beta=None) -> None:
+        """The shape of the band-limited resampler of AddPcm(resample="sinc") (pf_online_recognizer_set_resample), as
+        OfflineRecognizer.SetResampler; for streams whose first AddPcm follows."""
+        cfg = N.resample_config(zeros, rolloff, beta)
+        _ck(self._lib.pf_online_recognizer_set_resample(self._h, C.byref(cfg)))
 
     def SetPuncModel(self, pfwPath, maxContext: int = 0) -> None:
         """Streaming punctuation (pf_online_recognizer_set_punc_model; off by default): a causal `.pfw` of kind "cttransformer"

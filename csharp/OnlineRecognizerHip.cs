@@ -21,6 +21,8 @@ namespace AliParaformerAsr.Hip
         [DllImport(Lib)] internal static extern void pf_online_recognizer_free(IntPtr r);
         [DllImport(Lib)] internal static extern int pf_online_create_stream(IntPtr r, out IntPtr stream);
         [DllImport(Lib)] internal static extern int pf_online_stream_add_samples(IntPtr s, float[] samples, long n);
+        [DllImport(Lib)] internal static extern int pf_online_stream_add_pcm(IntPtr s, byte[]? data, long nBytes, ref PfPcmDesc desc);
+        [DllImport(Lib)] internal static extern int pf_online_recognizer_set_resample(IntPtr r, ref ParaformerHip.PfResampleConfig cfg);
         [DllImport(Lib)] internal static extern int pf_online_get_results(IntPtr r, IntPtr[] streams, int nStreams);
         [DllImport(Lib)] internal static extern int pf_online_result_text(IntPtr r, int i, out IntPtr utf8);
         // streaming endpointing and the second pass (paraformer_hip.h "Streaming endpointing and the second pass")

@@ -1921,6 +1921,46 @@ int pf_online_stream_sentence_tokens(pf_online_stream* s, int32_t j, const pf_on
    a chunk length other than 60 frames; a geometry other than 80 mels with LFR 7 / 6.  While the mode is on,
    pf_online_recognizer_set_endpoint and pf_online_recognizer_set_token_info(r, 0) are refused with PF_ERR_UNSUPPORTED. */
 int pf_online_recognizer_set_device_frontend(pf_online_recognizer* r, int32_t on);
+/* ---- Streaming PCM intake (additions to ABI 6; opt-in: a stream that never calls pf_online_stream_add_pcm makes the launches
+   and copies and returns the bytes it does without it; not in the reference) ----
+   pf_online_stream_add_pcm takes audio as the caller holds it: n_bytes raw bytes of desc's format (any pf_pcm_format, 1 or 2
+   channels, any rate; PF_PCM_DOWNMIX_ALWAYS and PF_PCM_RESAMPLE_SINC as in "PCM intake"), cut anywhere, even inside a value.
+   DEFINITION: for every way of cutting the bytes into calls, the samples the stream recognises are bit for bit those of
+   pf_host_pcm_convert over the concatenated bytes.  A call makes FINAL the outputs whose every input frame has arrived
+   (band-limited rule: frames up to (i M) / L + H; linear rule: (int)(i ratio) + 1) and whose index is below the length
+   pf_pcm_num_samples gives for the frames so far (half-to-even rounding can make that the smaller number); the rest waits for
+   more bytes or for pf_online_stream_input_finished, which ends the sequence as the one-shot does (+0 beyond it multiplied in
+   for the band-limited rule, m[last] for the linear rule, an unpaired trailing stereo value dropped).  The band-limited rule
+   therefore adds H input frames of latency (26 frames = 3.25 ms at 8 kHz with the default shape).  Token times stay
+   floor(index * 1000 / fs) in converted samples, i.e. in the caller's audio.
+   Host front-end: the final samples go through pf_online_stream_add_samples' path at once; endpointing, second pass and
+   punctuation work unchanged.  pf_online_recognizer_set_device_frontend on: the call only queues bytes (no engine mutex, no
+   device call) and cuts chunks by pf_online_stream_add_samples' rule on the final outputs; pf_online_get_results uploads, per
+   PCM-fed stream, only the raw frames its chunk needs beyond a tail of decoded frames kept on the device, inside the one staged
+   copy, and ONE launch of csrc/k_pcm_stream.hip (profile class "pcm_stream") writes the chunks of all PCM-fed streams of the
+   call into the block the fbank kernel reads.
+   pf_online_recognizer_set_resample: the filter shape (NULL = the defaults) for streams whose first pf_online_stream_add_pcm follows.
+   PF_ERR_INVALID_ARG: pf_online_stream_add_samples and pf_online_stream_add_pcm on one stream; a descriptor that differs from
+   the stream's first; audio after pf_online_stream_input_finished; more than 2^31 - 1 values in all; more than two channels.
+   PF_ERR_UNSUPPORTED: L > 1024 or more than 1024 taps, as in "PCM intake".  Not validated on speech. */
+int pf_online_stream_add_pcm(pf_online_stream* s, const void* data, int64_t n_bytes, const pf_pcm_desc* desc);
+int pf_online_recognizer_set_resample(pf_online_recognizer* r, const pf_resample_config* cfg);
+/* The host twin, the normative statement: one stream's converter.  push appends n_bytes (data may be NULL for 0) and then writes
+   up to cap final samples to out (out NULL or cap 0: none; they stay pending); finish ends the input first.  pending: final
+   samples not yet written.  The op steps B converters on the device instead (never both on one converter: PF_ERR_INVALID_ARG):
+   stream b yields up to n_out[b] (0 .. 9600) final samples into samples [B, 9600] (the rest of its row +0), n_written[b] of them,
+   on block slot[b] of states [n_states, pf_host_pcm_stream_state_bytes] (any content for a new stream: nothing is read that no
+   step wrote), through the staging kit: a sentinel row behind every row and a sentinel block behind every state block must keep
+   their bits, every row must be written everywhere. */
+typedef struct pf_pcm_stream pf_pcm_stream;
+int pf_host_pcm_stream_create(const pf_pcm_desc* desc, int32_t fs, const pf_resample_config* cfg, pf_pcm_stream** out);
+int pf_host_pcm_stream_push(pf_pcm_stream* p, const void* data, int64_t n_bytes, float* out, int64_t cap, int64_t* n_out);
+int pf_host_pcm_stream_finish(pf_pcm_stream* p, float* out, int64_t cap, int64_t* n_out);
+int pf_host_pcm_stream_pending(pf_pcm_stream* p, int64_t* n);
+void pf_host_pcm_stream_free(pf_pcm_stream* p);
+int pf_host_pcm_stream_state_bytes(int64_t* bytes);
+int pf_op_online_pcm_step(pf_engine* e, void* states, int32_t n_states, const int32_t* slot, pf_pcm_stream* const* streams,
+                          const int32_t* n_out, int32_t B, float* samples, int32_t* n_written);
 /* ---- Streaming punctuation on the recogniser (additions to ABI 6; see "Punctuation, streaming"; opt-in: without
    pf_online_recognizer_set_punc_model nothing of it is launched, allocated or changed) ----
    pf_online_recognizer_set_punc_model: pfw_path = a causal `.pfw` of kind "cttransformer", loaded once and attached to the
