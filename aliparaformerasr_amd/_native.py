@@ -36,6 +36,9 @@ PF_LM_IMAGE_BYTES_MAX = 1024 * 1024 * 1024
 PF_LM_EOS = 1
 PF_DECODE_ALIGN = 32
 PF_ALIGN_MAX_TOKENS = 1023
+PF_SPOT_MAX_TOKENS = 32
+PF_SPOT_MAX_KEYWORDS = 1024
+PF_SPOT_MAX_HITS = 64
 PF_TOPK_MAX = 8
 PF_NBEST_MAX = 64
 
@@ -470,6 +473,13 @@ SIGNATURES = {
     "pf_op_ctc_align": (C.c_int, [_vp, _f, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _i32, _i32, _i32, C.c_int32, C.c_int32,
                                   _f, _P(C.c_double), _i32, _i32, _i32, _f]),
     "pf_recognizer_set_align": (C.c_int, [_vp, C.c_int32]),
+    "pf_engine_set_spotter": (C.c_int, [_vp, _i32, _i32, C.c_int32, C.c_float, C.c_int32]),
+    "pf_fetch_spot": (C.c_int, [_vp, _i32, _i32, _f]),
+    "pf_host_ctc_spot": (C.c_int, [_f, C.c_int64, C.c_int32, C.c_int32, _i32, C.c_int32, C.c_float, C.c_int32, _i32, _i32, _f]),
+    "pf_op_ctc_spot": (C.c_int, [_vp, _f, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _i32, _i32, C.c_int32, _i32, C.c_float, C.c_int32,
+                                 _i32, _i32, _f]),
+    "pf_recognizer_set_keywords": (C.c_int, [_vp, _i32, _i32, C.c_int32, C.c_float, C.c_int32]),
+    "pf_stream_keyword_hits": (C.c_int, [_vp, _P(_i32), _P(_i32), _P(_P(C.c_double)), _i32]),
     "pf_stream_set_align_ids": (C.c_int, [_vp, _i64, C.c_int32]),
     "pf_stream_alignment": (C.c_int, [_vp, _P(_i32), _P(_f), _i32, _f, _P(C.c_double), _i32]),
     "pf_stream_alternative_timestamps": (C.c_int, [_vp, C.c_int32, _P(_i32), _i32, _P(C.c_double)]),

@@ -632,6 +632,35 @@ int pf_fetch_align(pf_engine* h, float* path_score, double* loglik, int32_t* ok,
   PF_CATCH
 }
 
+int pf_engine_set_spotter(pf_engine* h, const int32_t* ids, const int32_t* lens, int32_t n_keywords, float thr, int32_t max_hits) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->set_spotter(ids, lens, n_keywords, thr, max_hits);
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_fetch_spot(pf_engine* h, int32_t* n_hits, int32_t* begin_end, float* score) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->fetch_spot(n_hits, begin_end, score);
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_host_ctc_spot(const float* lp, int64_t ld, int32_t T, int32_t V, const int32_t* y, int32_t U, float thr, int32_t max_hits,
+                     int32_t* n_hits, int32_t* begin_end, float* score) {
+  PF_TRY
+  NEED(n_hits);
+  *n_hits = host_ctc_spot(lp, ld, T, V, y, U, thr, max_hits, begin_end, score);
+  return PF_OK;
+  PF_CATCH
+}
+
 int pf_host_ctc_align(const float* lp, int64_t ld, int32_t T, int32_t V, const int64_t* y, int32_t U, float* path_score,
                       double* loglik, int32_t* ok, int32_t* first, int32_t* last, float* tok_score) {
   PF_TRY
@@ -1575,6 +1604,23 @@ int pf_op_ctc_align(pf_engine* h, const float* lp, int32_t B, int32_t T, int32_t
   PF_CATCH
 }
 
+int pf_op_ctc_spot(pf_engine* h, const float* lp, int32_t B, int32_t T, int32_t V, int32_t ld, const int32_t* ids,
+                   const int32_t* phrase_lens, int32_t n_keywords, const int32_t* lens, float thr, int32_t max_hits,
+                   int32_t* n_hits, int32_t* begin_end, float* score) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  PF_CHECK(B >= 0 && B <= 65535 && T >= 0 && V >= 1 && ld >= V, PF_ERR_INVALID_ARG, "ctc_spot: bad shape (ld >= V >= 1, B <= 65535)");
+  if (B > 0) {
+    NEED(lens); NEED(n_hits); NEED(begin_end); NEED(score);
+    if (T > 0) NEED(lp);
+  }
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->op_ctc_spot(lp, B, T, V, ld, ids, phrase_lens, n_keywords, lens, thr, max_hits, n_hits, begin_end, score);
+  return PF_OK;
+  PF_CATCH
+}
+
 int pf_op_ctc_collapse(pf_engine* h, const int64_t* ids, const float* scores, const int32_t* lens, int32_t B, int32_t T,
                        int32_t blank, int64_t* ids_out, int32_t* first_out, int32_t* last_out, float* score_out, int32_t cap,
                        int32_t* n_out) {
@@ -2388,6 +2434,16 @@ int pf_recognizer_set_align(pf_recognizer* h, int32_t on) {
   PF_CATCH
 }
 
+int pf_recognizer_set_keywords(pf_recognizer* h, const int32_t* ids, const int32_t* lens, int32_t n, float thr, int32_t max_hits) {
+  PF_TRY
+  std::shared_ptr<Recognizer> r = R(h);
+  PF_CHECK(!r->disposed(), PF_ERR_DISPOSED, "OfflineRecognizer");
+  PF_CHECK(n >= 0, PF_ERR_INVALID_ARG, "SetKeywords: negative n");
+  r->SetKeywords(ids, lens, n, thr, max_hits);
+  return PF_OK;
+  PF_CATCH
+}
+
 int pf_recognizer_set_vad(pf_recognizer* h, const pf_vad_config* cfg, int32_t batch_max, int64_t frame_budget, const char* sep_utf8) {
   PF_TRY
   std::shared_ptr<Recognizer> r = R(h);
@@ -2632,6 +2688,17 @@ int pf_stream_alignment(pf_stream* h, const int32_t** begin_end, const float** t
   if (path_score) *path_score = s->AlignPath;
   if (loglik) *loglik = s->AlignLoglik;
   if (ok) *ok = s->AlignOk;
+  return PF_OK;
+  PF_CATCH
+}
+
+int pf_stream_keyword_hits(pf_stream* h, const int32_t** phrase, const int32_t** begin_end_ms, const double** conf, int32_t* n) {
+  PF_TRY
+  Stream* s = S(h);
+  if (phrase) *phrase = s->KwPhrase.data();
+  if (begin_end_ms) *begin_end_ms = s->KwTs.data();
+  if (conf) *conf = s->KwConf.data();
+  if (n) *n = s->KwN;
   return PF_OK;
   PF_CATCH
 }

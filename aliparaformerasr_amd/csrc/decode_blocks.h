@@ -89,6 +89,19 @@ struct AlignBlock : Block {
   }
 };
 
+// CTC phrase spotting (k_ctcspot.hip): n_hits [B, K] int32 | begin_end [B, K, max_hits, 2] int32 | score [B, K, max_hits] fp32
+// Its input, the packed phrase list (spot_pack, hostutil.h): one 32-bit word per lane of a 64-lane row — the state's column in
+// bits 0 .. 23 | kSpotHead (state 0 of a chain: the restart; nothing is taken from the lanes below) | kSpotSkip (the skip from
+// s - 2 is allowed) | kSpotExit (state S - 1: this lane owns the phrase's hits) | kSpotIdle (no state)
+constexpr uint32_t kSpotLabel = (1u << 24) - 1, kSpotHead = 1u << 28, kSpotSkip = 1u << 29, kSpotExit = 1u << 30, kSpotIdle = 1u << 31;
+constexpr int kSpotLanes = 64, kSpotRowsPerGroup = 4;
+struct SpotBlock : Block {
+  Field<int32_t> n_hits, begin_end; Field<float> score;
+  SpotBlock(Cursor& c, size_t B, size_t K, size_t max_hits) : Block(c) {
+    lay(c, n_hits, B * K, begin_end, B * K * max_hits * 2, score, B * K * max_hits);
+  }
+};
+
 // one stream's carried CIF pair (k_cif_stream.hip, online_cif_step in online.cpp): hidden [D] fp32, the carried frame already
 // divided by the carried integrate | integrate [G] fp32, ONE COPY per kCifStreamGroup channels, G = ceil(D / kCifStreamGroup)
 // (every workgroup of the kernel walks one group of channels and owns that group's copy: no workgroup reads a cell another
@@ -165,6 +178,9 @@ struct HostBatchOut { // results of a forward, host side
   BeamLmBlock beam_lm_block() const { return block_at_zero<BeamLmBlock>(B, beam_n); }
   NbestSearchBlock nbs_block() const { return block_at_zero<NbestSearchBlock>(B, nbs_n, L); }
   AlignBlock align_block() const { return block_at_zero<AlignBlock>(B, align_h, align_cap); }
+  std::vector<int64_t> spot;       // empty when the forward ran without a phrase list (Engine::set_spotter)
+  int spot_k = 0, spot_hits = 0;   // phrases and max_hits of that forward
+  SpotBlock spot_block() const { return block_at_zero<SpotBlock>(B, spot_k, spot_hits); }
 };
 
 }  // namespace pf

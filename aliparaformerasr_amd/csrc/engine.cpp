@@ -2271,7 +2271,7 @@ void Engine::set_nbest_hotwords(const int32_t* ids, const int32_t* lens, int n, 
 }
 
 float* Engine::score_buf(int64_t rows) {
-  if (!decode_flags_) return nullptr;
+  if (!run_flags()) return nullptr;
   ensure(ws_score_, (size_t)std::max<int64_t>(rows, 1) * 4);
   return (float*)ws_score_.p;
 }
@@ -2280,11 +2280,12 @@ void Engine::queue_decode_results(int B, int L) {
   std::vector<int32_t>& len = ctc_len_;              // (a member: the host-to-device copies below may read it after this call returns)
   len.clear();
   len.swap(dec_len_);                                // consumed: a later forward without lengths decodes every row
-  if (!decode_flags_ || B * L == 0) return;
+  const int flags = run_flags();
+  if (!flags || B * L == 0) return;
   const float* sc = (const float*)ws_score_.p;
   last_.scores.resize((size_t)B * L);
   PF_HIP(hipMemcpyAsync(last_.scores.data(), sc, (size_t)B * L * 4, hipMemcpyDeviceToHost, stream_));
-  if (decode_flags_ & (PF_DECODE_CTC | PF_DECODE_CTC_BEAM | PF_DECODE_ALIGN)) {
+  if (flags & (PF_DECODE_CTC | PF_DECODE_CTC_BEAM | PF_DECODE_ALIGN)) {
     if ((int)len.size() != B) len.assign(B, L);
     for (int b = 0; b < B; ++b) len[b] = std::min(std::max(len[b], 0), L);
   }
@@ -2292,6 +2293,7 @@ void Engine::queue_decode_results(int B, int L) {
   if ((decode_flags_ & PF_DECODE_TOPK) && nbs_w_ > 0) queue_nbest_search(B, L);
   if (decode_flags_ & PF_DECODE_CTC_BEAM) queue_ctc_beam(B, L);      // (set_decode: implies TOPK)
   if (decode_flags_ & PF_DECODE_ALIGN) queue_align(B, L);
+  if (spot_.K > 0) queue_spot(B, L);
   if (decode_flags_ & PF_DECODE_CTC) queue_ctc_collapse(B, L);
 }
 
@@ -2426,6 +2428,44 @@ void Engine::queue_align(int B, int L) {
   PF_HIP(hipMemcpyAsync(last_.align.data(), ws, k.words() * 8, hipMemcpyDeviceToHost, stream_));
 }
 
+void Engine::set_spotter(const int32_t* ids, const int32_t* lens, int n, float thr, int max_hits) {
+  PF_CHECK(mc_.kind_id() == 1 && !mc_.seaco, PF_ERR_UNSUPPORTED, "set_spotter: only a SenseVoice model has a CTC head");
+  PF_CHECK(n >= 0, PF_ERR_INVALID_ARG, "set_spotter: negative n_keywords");
+  if (!ids || n == 0) { spot_.K = 0; spot_.rows = 0; return; }   // (the image stays where it is; nothing reads it)
+  spot_check_params(thr, max_hits);
+  SpotImage img;
+  spot_pack(ids, lens, n, mc_.vocab, img);           // throws before anything changes
+  PF_HIP(hipSetDevice(device_));
+  PF_HIP(hipStreamSynchronize(stream_));             // a queued launch may still read the image about to be replaced
+  const size_t cells = img.lanes.size();
+  ensure(spot_.buf, cells * 8);
+  // on stream_, behind the zero fill that ensure() queues there when it allocates (as install_hotwords)
+  PF_HIP(hipMemcpyAsync(spot_.buf.p, img.lanes.data(), cells * 4, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipMemcpyAsync((uint32_t*)spot_.buf.p + cells, img.lane_kw.data(), cells * 4, hipMemcpyHostToDevice, stream_));
+  PF_HIP(hipStreamSynchronize(stream_));             // (img goes with this scope)
+  spot_.K = img.K; spot_.rows = img.rows; spot_.thr = thr; spot_.max_hits = max_hits;
+}
+
+void Engine::queue_spot(int B, int L) {
+  // the kernel reads the in-place log-prob rows (argmax_mode) and the lengths the collapse uses
+  const int K = spot_.K, Hm = spot_.max_hits;
+  const size_t cells = (size_t)spot_.rows * kSpotLanes;
+  Cursor c;
+  const SpotBlock k(c, B, K, Hm);
+  const Field<int32_t> len_d = c.take<int32_t>(B);
+  ensure(ws_spot_, c.off);
+  last_.spot.resize(k.words());
+  last_.spot_k = K;
+  last_.spot_hits = Hm;
+  void* ws = ws_spot_.p;
+  PF_HIP(hipMemcpyAsync(len_d(ws), ctc_len_.data(), ctc_len_.size() * 4, hipMemcpyHostToDevice, stream_));
+  prof_begin("ctc_spot", 0);
+  launch_ctc_spot(stream_, logits_, logits_ld_, last_.V, (const uint32_t*)spot_.buf.p, (const int32_t*)spot_.buf.p + cells, spot_.rows,
+                  len_d(ws), B, L, K, spot_.thr, Hm, k.n_hits(ws), k.begin_end(ws), k.score(ws));
+  prof_end("ctc_spot");
+  PF_HIP(hipMemcpyAsync(last_.spot.data(), ws, k.words() * 8, hipMemcpyDeviceToHost, stream_));
+}
+
 void Engine::queue_ctc_collapse(int B, int L) {
   const int cap = L;
   Cursor c;
@@ -2452,6 +2492,7 @@ void Engine::forward_device(const float* speech_dev, int B, int T, bool want_log
   last_.topk.clear(); last_.topk_k = 0;
   last_.beam.clear(); last_.beam_n = 0; last_.beam_cap = 0; last_.beam_hot.clear(); last_.beam_lm.clear(); last_.beam_biased = false;
   last_.align.clear(); last_.align_h = 0; last_.align_cap = 0;
+  last_.spot.clear(); last_.spot_k = 0; last_.spot_hits = 0;
   last_.nbs.clear(); last_.nbs_n = 0;
   if (align_B_ != 0 && align_B_ != B) {             // before anything is launched; the targets are dropped
     const int want = align_B_;
@@ -2710,6 +2751,17 @@ void Engine::fetch_align(float* path_score, double* loglik, int32_t* ok, int32_t
   copy_rows_padded(first, cap, k.first(p), r.align_cap, jobs, -1);
   copy_rows_padded(last, cap, k.last(p), r.align_cap, jobs, -1);
   copy_rows_padded(tok_score, cap, k.tok(p), r.align_cap, jobs, 0.f);
+}
+
+void Engine::fetch_spot(int32_t* n_hits, int32_t* begin_end, float* score) {
+  const char* refusal = "fetch_spot: the last forward ran without a phrase list (pf_engine_set_spotter)";
+  const HostBatchOut& r = fetch_result(0, refusal);
+  PF_CHECK(!r.spot.empty(), PF_ERR_INVALID_ARG, refusal);
+  const SpotBlock k = r.spot_block();
+  const void* p = r.spot.data();
+  if (n_hits) std::memcpy(n_hits, k.n_hits(p), k.n_hits.count * 4);
+  if (begin_end) std::memcpy(begin_end, k.begin_end(p), k.begin_end.count * 4);
+  if (score) std::memcpy(score, k.score(p), k.score.count * 4);
 }
 
 void Engine::fetch_ctc(int64_t* ids, int32_t* first, int32_t* last, float* score, int32_t cap, int32_t* n, int32_t* n_max) {

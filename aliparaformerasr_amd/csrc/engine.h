@@ -266,6 +266,14 @@ class Engine {
                    int32_t cap, int32_t* H_out, int32_t* len_max);
   void op_ctc_align(const float* lp, int B, int T, int V, int ld, const int32_t* tgt, const int32_t* tlen, const int32_t* lens, int H,
                     int cap, float* path_score, double* loglik, int32_t* ok, int32_t* first, int32_t* last, float* tok_score);
+  // Phrase spotting (SenseVoice; paraformer_hip.h "CTC phrase spotting", the definition is tests/ctcspot_ref.py): with a list
+  // installed one kernel (k_ctcspot.hip) behind the other decode launches finds where each phrase was said in each utterance.
+  // n == 0 or null ids clears; without a list nothing is launched, allocated or changed.
+  void set_spotter(const int32_t* ids, const int32_t* lens, int n, float thr, int max_hits);
+  bool spotter_on() const { return spot_.K > 0; }
+  void fetch_spot(int32_t* n_hits, int32_t* begin_end, float* score);
+  void op_ctc_spot(const float* lp, int B, int T, int V, int ld, const int32_t* ids, const int32_t* phrase_lens, int n,
+                   const int32_t* lens, float thr, int max_hits, int32_t* n_hits, int32_t* begin_end, float* score);
   void op_pcm_convert(const void* data, int64_t n_values, const pf_pcm_desc& desc, float* out, int64_t cap, int64_t* n_out);
   // voice-activity segmentation (k_vad.hip): stage_audio, run_staged's one fbank launch, then the two detector launches (profile
   // class "vad") over all B utterances; only n [B] and the segment lists come back.  seg [B, cap, 2].
@@ -824,7 +832,19 @@ class Engine {
   std::vector<int32_t> align_tgt_, align_len_, align_tgt_q_, align_len_q_;
   int align_B_ = 0, align_cap_ = 0;
   DevBuf ws_align_;                  // the result block (HostBatchOut::align) | jobs | len [B] | targets | back-pointers; with the flag only
-  int argmax_mode(bool want_logits) const { return (want_logits || (decode_flags_ & (PF_DECODE_TOPK | PF_DECODE_ALIGN))) ? 2 : 1; }
+  // an installed phrase list (set_spotter): the packed image lanes | lane_kw [rows * 64] each, uploaded by the setter only
+  struct SpotDev {
+    int K = 0, rows = 0, max_hits = 0; // K > 0: a list is installed
+    float thr = 0.f;
+    DevBuf buf;
+  };
+  SpotDev spot_;
+  DevBuf ws_spot_;                   // the result block (HostBatchOut::spot) | len [B]; allocated by a forward with a list only
+  void queue_spot(int B, int L);
+  // what the forward runs: the caller's flags, and with a phrase list installed PF_DECODE_ALIGN's switch (the log-softmax rows
+  // stay in place, the clamped lengths are made) without its launches or its fetch
+  int run_flags() const { return decode_flags_ | (spot_.K > 0 ? PF_DECODE_ALIGN | PF_DECODE_SCORES : 0); }
+  int argmax_mode(bool want_logits) const { return (want_logits || (run_flags() & (PF_DECODE_TOPK | PF_DECODE_ALIGN))) ? 2 : 1; }
   // Behind the ids copy: the scores' copy, then one step per decoder flag.  A step lays out its ws_* buffer with the block
   // type of decode_blocks.h (the result block, its scratch behind it), launches, and queues the one copy of the block.
   void queue_decode_results(int B, int L);

@@ -1458,6 +1458,40 @@ void Engine::op_ctc_align(const float* lp, int B, int T, int V, int ld, const in
   PF_HIP(hipStreamSynchronize(stream_));
 }
 
+void Engine::op_ctc_spot(const float* lp, int B, int T, int V, int ld, const int32_t* ids, const int32_t* phrase_lens, int n,
+                         const int32_t* lens, float thr, int max_hits, int32_t* n_hits, int32_t* begin_end, float* score) {
+  PF_HIP(hipSetDevice(device_));
+  spot_check_params(thr, max_hits);
+  SpotImage img;
+  spot_pack(ids, phrase_lens, n, V, img);
+  if (B == 0) return;
+  const size_t rows = (size_t)B * T, cells = img.lanes.size(), guard = 64;
+  Cursor c;
+  const SpotBlock k(c, B, n, max_hits);
+  const Field<uint32_t> d_guard = c.take<uint32_t>(guard);                  // sentinel cells behind the block: nothing may touch them
+  const Field<uint32_t> d_lanes = c.take<uint32_t>(cells);
+  const Field<int32_t> d_kw = c.take<int32_t>(cells), d_len = c.take<int32_t>(B);
+  const Field<float> d_lp = c.take<float>(rows * ld);
+  ensure(ws_tmp_, c.off);
+  void* ws = ws_tmp_.p;
+  upload(stream_, d_lp(ws), lp, d_lp.count);
+  upload(stream_, d_lanes(ws), img.lanes.data(), cells);
+  upload(stream_, d_kw(ws), img.lane_kw.data(), cells);
+  upload(stream_, d_len(ws), lens, (size_t)B);
+  fill_sentinel(stream_, (uint32_t*)((char*)ws + k.begin), (d_guard.off + guard * 4 - k.begin) / 4);
+  launch_ctc_spot(stream_, d_lp(ws), ld, V, d_lanes(ws), d_kw(ws), img.rows, d_len(ws), B, T, n, thr, max_hits, k.n_hits(ws),
+                  k.begin_end(ws), k.score(ws));
+  // every slot of the block written, the cells behind it untouched
+  const int64_t slots = (int64_t)(k.bytes() / 4);
+  const std::vector<uint32_t> h = check_guard<uint32_t>(stream_, "ctc_spot: result block", (char*)ws + k.begin, kSentinel32,
+                                                        result_geom(1, 1, (int)slots, (int)((d_guard.off - k.begin) / 4 + guard), 1));
+  const SpotBlock hk = block_at_zero<SpotBlock>(B, n, max_hits);
+  const void* p = h.data();
+  std::memcpy(n_hits, hk.n_hits(p), hk.n_hits.count * 4);
+  std::memcpy(begin_end, hk.begin_end(p), hk.begin_end.count * 4);
+  std::memcpy(score, hk.score(p), hk.score.count * 4);
+}
+
 void Engine::op_ctc_collapse(const int64_t* ids, const float* scores, const int32_t* lens, int B, int T, int blank,
                              int64_t* ids_out, int32_t* first_out, int32_t* last_out, float* score_out, int cap, int32_t* n_out) {
   PF_HIP(hipSetDevice(device_));

@@ -1216,6 +1216,98 @@ int host_ctc_align(const float* lp, int64_t ld, int T, int V, const int64_t* y, 
   return 1;
 }
 
+// ---- CTC phrase spotting (paraformer_hip.h "CTC phrase spotting"; tests/ctcspot_ref.py) ---------------------------------------
+void spot_check_params(float thr, int max_hits) {
+  PF_CHECK(thr <= 0.f, PF_ERR_INVALID_ARG, "ctc_spot: the threshold is a mean log-prob per frame, <= 0 and not NaN");
+  PF_CHECK(max_hits >= 1 && max_hits <= PF_SPOT_MAX_HITS, PF_ERR_INVALID_ARG, "ctc_spot: max_hits is 1 .. " + std::to_string(PF_SPOT_MAX_HITS));
+}
+
+static void spot_check_phrase(const int32_t* y, int U, int V) {
+  PF_CHECK(U >= 1 && U <= PF_SPOT_MAX_TOKENS, PF_ERR_INVALID_ARG, "ctc_spot: a phrase has 1 .. " + std::to_string(PF_SPOT_MAX_TOKENS) + " tokens");
+  for (int u = 0; u < U; ++u) PF_CHECK(y[u] >= 1 && y[u] < V, PF_ERR_INVALID_ARG, "ctc_spot: a phrase id outside [1, V)");
+}
+
+int host_ctc_spot(const float* lp, int64_t ld, int T, int V, const int32_t* y, int U, float thr, int max_hits, int32_t* begin_end,
+                  float* score) {
+  PF_CHECK(y && begin_end && score && (T <= 0 || lp), PF_ERR_INVALID_ARG, "ctc_spot: null argument");
+  PF_CHECK(T >= 0 && V >= 1 && ld >= V, PF_ERR_INVALID_ARG, "ctc_spot: bad T / V / ld");
+  spot_check_params(thr, max_hits);
+  spot_check_phrase(y, U, V);
+  const float kNegF = -INFINITY;
+  const int S = 2 * U - 1;
+  std::vector<float> v((size_t)S, kNegF), nv((size_t)S);
+  std::vector<int32_t> st((size_t)S, -1), nst((size_t)S);
+  int n = 0;
+  bool open = false;
+  int c_begin = 0, c_end = 0, c_dur = 0;
+  float c_e = 0.f;
+  auto close = [&] {
+    if (n < max_hits) { begin_end[2 * n] = c_begin; begin_end[2 * n + 1] = c_end; score[n] = c_e; }
+    ++n;
+  };
+  for (int t = 0; t < T; ++t) {
+    const float* row = lp + (size_t)t * ld;
+    for (int s = 0; s < S; ++s) {
+      const float x = row[(s & 1) ? 0 : y[s >> 1]];
+      if (s == 0) { nv[0] = x; nst[0] = t; continue; }
+      float best = v[(size_t)s];
+      int32_t from = st[(size_t)s];
+      if (v[(size_t)s - 1] > best) { best = v[(size_t)s - 1]; from = st[(size_t)s - 1]; }
+      if (!(s & 1) && y[s >> 1] != y[(s >> 1) - 1] && v[(size_t)s - 2] > best) { best = v[(size_t)s - 2]; from = st[(size_t)s - 2]; }
+      nv[(size_t)s] = x + best;
+      nst[(size_t)s] = from;
+    }
+    v.swap(nv);
+    st.swap(nst);
+    const float e = v[(size_t)S - 1];
+    const int begin = st[(size_t)S - 1], dur = t - begin + 1;
+    if (!(e > kNegF) || !(e >= thr * (float)dur)) continue;
+    if (!open || begin > c_end) {
+      if (open) close();
+      open = true;
+    } else if (!(e * (float)c_dur > c_e * (float)dur)) {
+      continue;
+    }
+    c_begin = begin; c_end = t; c_dur = dur; c_e = e;
+  }
+  if (open) close();
+  for (int i = std::min(n, max_hits); i < max_hits; ++i) { begin_end[2 * i] = -1; begin_end[2 * i + 1] = -1; score[i] = 0.f; }
+  return n;
+}
+
+void spot_pack(const int32_t* ids, const int32_t* lens, int n, int V, SpotImage& out) {
+  PF_CHECK(n >= 1 && ids && lens, PF_ERR_INVALID_ARG, "ctc_spot: an empty phrase list");
+  PF_CHECK(n <= PF_SPOT_MAX_KEYWORDS, PF_ERR_CAPACITY, "ctc_spot: " + std::to_string(n) + " phrases > PF_SPOT_MAX_KEYWORDS");
+  PF_CHECK(V >= 1 && (uint32_t)V <= kSpotLabel + 1, PF_ERR_INVALID_ARG, "ctc_spot: the vocabulary does not fit a lane word");
+  size_t off = 0;
+  for (int k = 0; k < n; ++k) { spot_check_phrase(ids + off, lens[k], V); off += (size_t)lens[k]; }
+  std::vector<int> used;                             // lanes taken per row
+  out.lanes.clear(); out.lane_kw.clear();
+  off = 0;
+  for (int k = 0; k < n; ++k) {
+    const int32_t* y = ids + off;
+    const int U = lens[k], S = 2 * U - 1;
+    size_t r = 0;
+    while (r < used.size() && used[r] + S > kSpotLanes) ++r;   // first fit
+    if (r == used.size()) {
+      used.push_back(0);
+      out.lanes.resize(used.size() * kSpotLanes, kSpotIdle);
+      out.lane_kw.resize(used.size() * kSpotLanes, -1);
+    }
+    for (int s = 0; s < S; ++s) {
+      const size_t x = r * kSpotLanes + (size_t)used[r] + s;
+      uint32_t w = (s & 1) ? 0u : (uint32_t)y[s >> 1];
+      if (s == 0) w |= kSpotHead;
+      if (!(s & 1) && s >= 2 && y[s >> 1] != y[(s >> 1) - 1]) w |= kSpotSkip;
+      if (s == S - 1) { w |= kSpotExit; out.lane_kw[x] = k; }
+      out.lanes[x] = w;
+    }
+    used[r] += S;
+    off += (size_t)U;
+  }
+  out.rows = (int)used.size();
+  out.K = n;
+}
 
 // ---- voice-activity segmentation (paraformer_hip.h "Voice-activity segmentation"; tests/vad_ref.py) --------------------------
 pf_vad_config vad_default() {

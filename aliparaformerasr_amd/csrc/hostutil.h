@@ -200,6 +200,23 @@ int host_nbest_search(const int64_t* ids, const float* val, const int32_t* n, in
 int host_ctc_align(const float* lp, int64_t ld, int T, int V, const int64_t* y, int U, float* path_score, double* loglik,
                    int32_t* first, int32_t* last, float* tok_score);
 
+// ---- CTC phrase spotting (paraformer_hip.h "CTC phrase spotting"; the definition is tests/ctcspot_ref.py) ----
+// The host twin of k_ctcspot.hip for one utterance and one phrase: lp [T, ld] (V read per row), y [U] ids in [1, V), float32 as
+// defined.  begin_end [max_hits, 2] / score [max_hits]: every slot is written.  Returns the number of closed hits.
+int host_ctc_spot(const float* lp, int64_t ld, int T, int V, const int32_t* y, int U, float thr, int max_hits, int32_t* begin_end,
+                  float* score);
+// thr <= 0 and not NaN, 1 <= max_hits <= PF_SPOT_MAX_HITS (PF_ERR_INVALID_ARG)
+void spot_check_params(float thr, int max_hits);
+// The kernel's image of a phrase list: the phrases' state chains (S = 2U - 1 lanes each) laid end to end into rows of 64 lanes,
+// first fit in the given order, a chain never straddling a row.  lanes [rows * 64]: the lane words of decode_blocks.h
+// (kSpot*); lane_kw [rows * 64]: the phrase of an exit lane, -1 elsewhere.  Validates like pf_engine_set_spotter.
+struct SpotImage {
+  std::vector<uint32_t> lanes;
+  std::vector<int32_t> lane_kw;
+  int rows = 0, K = 0;
+};
+void spot_pack(const int32_t* ids, const int32_t* lens, int n, int V, SpotImage& out);
+
 // ---- voice-activity segmentation (paraformer_hip.h "Voice-activity segmentation"; the definition is tests/vad_ref.py) ----
 // The host twins of k_vad.hip.  vad_default: the stated defaults.  vad_check: cfg (null = the defaults) validated against the
 // constraints of the header (PF_ERR_INVALID_ARG), returned by value.

@@ -508,6 +508,16 @@ void launch_ctc_align(hipStream_t s, const float* lp, int64_t ld, int V, const i
 void launch_ctc_align_jobs(hipStream_t s, const int32_t* c_tgt, const int32_t* c_len, int c_cap, const int32_t* b_ids,
                            const int32_t* b_len, const int32_t* b_nhyp, int N, int b_cap, int B, int H, int cap, int32_t* tgt,
                            int32_t* tlen);
+// ------------------------------------------------------------------ CTC phrase spotting -------
+// Per (utterance b, phrase k) the hits of the free-start / free-exit Viterbi DP of paraformer_hip.h "CTC phrase spotting" over
+// the rows lp[(b * T + t) * ld + v], t < min(max(len[b], 0), T) (k_ctcspot.hip; the definition is tests/ctcspot_ref.py).  The
+// phrases come as the packed image of spot_pack (hostutil.h): lanes / lane_kw [rows * 64], a wave per row, a lane per state.
+// n_hits [B, K], begin_end [B, K, max_hits, 2], score [B, K, max_hits]: every slot is written, (-1, -1, 0) at and beyond n_hits.
+// Nothing at or beyond len[b] or V is read.  B <= 65535, 1 <= max_hits <= PF_SPOT_MAX_HITS.
+constexpr int kSpotRing = 16;                        // frames of log-probs a lane keeps in registers
+void launch_ctc_spot(hipStream_t s, const float* lp, int64_t ld, int V, const uint32_t* lanes, const int32_t* lane_kw, int rows,
+                     const int32_t* len, int B, int T, int K, float thr, int max_hits, int32_t* n_hits, int32_t* begin_end,
+                     float* score);
 
 // ---------------------------------------------------------------- PCM intake (k_pcm.hip) ------
 // One utterance of a pcm_to_samples launch: n raw values of `format` (pf_pcm_format) at raw + in_off (bytes, 16-byte aligned)

@@ -472,6 +472,10 @@ std::shared_ptr<Engine> Recognizer::make_engine() {
   std::shared_ptr<const SpkModel> sm;
   { std::lock_guard<std::mutex> lk(spk_mu_); sm = spk_model_; }
   if (sm) e->set_spk_model(sm);
+  {
+    std::lock_guard<std::mutex> lk(kw_mu_);
+    if (!kw_lens_.empty()) e->set_spotter(kw_ids_.data(), kw_lens_.data(), (int)kw_lens_.size(), kw_thr_, kw_hits_);
+  }
   const pf_resample_config rs = resample_.config();
   e->set_resample(&rs);
   return e;
@@ -512,6 +516,43 @@ void Recognizer::SetAlign(bool on) {
   } catch (...) {
     align_on_ = false;
     throw;
+  }
+}
+
+void Recognizer::SetKeywords(const int32_t* ids, const int32_t* lens, int n, float thr, int max_hits) {
+  if (disposed_) throw Error(PF_ERR_DISPOSED, "OfflineRecognizer");
+  const bool on = ids && n != 0;
+  if (on) {
+    { std::lock_guard<std::mutex> lk(vad_mu_); if (vad_on_) throw Error(PF_ERR_UNSUPPORTED, "SetKeywords: not available beside SetVad (long-audio recognition)"); }
+    if (engine_kind_ != "sensevoicesmall") throw Error(PF_ERR_UNSUPPORTED, "SetKeywords: only a SenseVoice model has a CTC head");
+  }
+  std::vector<std::shared_ptr<Engine>> es;
+  {
+    std::lock_guard<std::mutex> lk(mu_);
+    if (disposed_ || engines_.empty()) throw Error(PF_ERR_DISPOSED, "OfflineRecognizer");
+    es = engines_;
+  }
+  if (on) {                                          // the engines' own refusals, before anything changes
+    SpotImage img;
+    spot_check_params(thr, max_hits);
+    spot_pack(ids, lens, n, es[0]->model().vocab, img);
+  }
+  {
+    std::lock_guard<std::mutex> lk(kw_mu_);          // engines made from here on install it themselves
+    kw_ids_.clear(); kw_lens_.clear();
+    if (on) {
+      kw_lens_.assign(lens, lens + n);
+      size_t total = 0;
+      for (int32_t l : kw_lens_) total += (size_t)l;
+      kw_ids_.assign(ids, ids + total);
+      kw_thr_ = thr; kw_hits_ = max_hits;
+    }
+    kw_on_ = on;
+  }
+  for (auto& e : es) {
+    std::lock_guard<std::mutex> lk(e->mutex());
+    if (on) e->set_spotter(ids, lens, n, thr, max_hits);
+    else if (e->spotter_on()) e->set_spotter(nullptr, nullptr, 0, 0.f, 1);
   }
 }
 
@@ -619,6 +660,7 @@ void Recognizer::SetVad(const pf_vad_config* cfg, int batch_max, int64_t frame_b
   if (nbest_n_ > 0 || beam_on_ || align_on_)
     throw Error(PF_ERR_UNSUPPORTED, "SetVad: not available beside SetNBest, SetCtcBeam or SetAlign");
   if (search_w_ > 0) throw Error(PF_ERR_UNSUPPORTED, "SetVad: not available beside SetNBestSearch");
+  if (kw_on_) throw Error(PF_ERR_UNSUPPORTED, "SetVad: not available beside SetKeywords");
   std::lock_guard<std::mutex> lk(vad_mu_);
   vad_on_ = true; vad_cfg_ = c;
   vad_batch_max_ = batch_max == 0 ? 32 : batch_max;
@@ -816,7 +858,8 @@ void Recognizer::stitch_pieces(const std::vector<Stream*>& streams, const std::v
     s->Tokens.swap(ids[i]); s->Timestamps.swap(ts[i]); s->Scores.swap(sc[i]);
     s->AltIds.clear(); s->AltVal.clear(); s->AltK = 0; s->Alternatives.clear();
     s->AlignTs.clear(); s->AlignTok.clear(); s->AlignN = -1;
-    s->RemoveChunk();                                          // as Forward: a stream that produced a result gives up its audio
+    s->KwPhrase.clear(); s->KwTs.clear(); s->KwConf.clear(); s->KwN = -1;
+    s->RemoveChunk();                                        // as Forward: a stream that produced a result gives up its audio
   }
 }
 

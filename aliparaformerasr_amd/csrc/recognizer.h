@@ -145,6 +145,10 @@ class Recognizer : public std::enable_shared_from_this<Recognizer> {
   // SenseVoice only (paraformer_hip.h "CTC forced alignment"): PF_DECODE_ALIGN on every engine — a stream's target (AlignIds)
   // is aligned to its audio, and with SetCtcBeam every Alternative gets its own times and log-likelihood
   void SetAlign(bool on);
+  // SenseVoice only (paraformer_hip.h "CTC phrase spotting"): the phrase list of every GetResults that follows, on every engine
+  // of the pool, present and future — a stream's hits land in Kw* (stream_result.h).  n == 0 or null ids clears.
+  // PF_ERR_UNSUPPORTED beside SetVad (either order).
+  void SetKeywords(const int32_t* ids, const int32_t* lens, int n, float thr, int max_hits);
   // SenseVoice only (paraformer_hip.h "CTC hot words"): boost per matched hot-word token inside the beam search of SetCtcBeam
   // (inert without it); 0 = off.  The hot words of a batch: the union of its streams' Hotwords, else the hot-word file's.
   void SetHotwordBoost(float s);
@@ -328,6 +332,10 @@ class Recognizer : public std::enable_shared_from_this<Recognizer> {
   int search_flags_ = 0;
   std::atomic<bool> beam_on_{false};
   std::atomic<bool> align_on_{false};
+  std::mutex kw_mu_;                    // SetKeywords: the list as given (empty: none), for the engines that join the pool later
+  std::vector<int32_t> kw_ids_, kw_lens_;
+  float kw_thr_ = 0.f; int kw_hits_ = 0;
+  std::atomic<bool> kw_on_{false};
   int extra_flags() const { return (nbest_n_ > 0 ? PF_DECODE_TOPK : 0) | (beam_on_ ? PF_DECODE_CTC_BEAM : 0) | (align_on_ ? PF_DECODE_ALIGN : 0); }
   void set_decode_all(int flags, int k);
   friend class Stream;

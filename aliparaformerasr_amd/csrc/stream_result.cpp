@@ -200,6 +200,25 @@ void build_stream_result(const HostBatchOut& r, const ResultPlan& p, int b, Stre
       s.AlignTok.assign(ab.tok(ap) + j * a_cap, ab.tok(ap) + j * a_cap + n);
     }
   }
+
+  // phrase spotting: the stored hits of every phrase, frames to ms as above
+  s.KwPhrase.clear(); s.KwTs.clear(); s.KwConf.clear(); s.KwN = -1;
+  if (!r.spot.empty()) {
+    const SpotBlock sb = r.spot_block();
+    const void* sp = r.spot.data();
+    const size_t K = (size_t)r.spot_k, H2 = (size_t)r.spot_hits;
+    for (size_t k = 0; k < K; ++k) {
+      const size_t x = (size_t)b * K + k;
+      for (size_t i = 0; i < std::min<size_t>((size_t)std::max(sb.n_hits(sp)[x], 0), H2); ++i) {
+        const int32_t* be = sb.begin_end(sp) + (x * H2 + i) * 2;
+        const TsVec t = frame_ms(p.ms_frame, be[0], be[1]);
+        s.KwPhrase.push_back((int32_t)k);
+        s.KwTs.insert(s.KwTs.end(), t.begin(), t.end());
+        s.KwConf.push_back(std::exp((double)sb.score(sp)[x * H2 + i] / (double)(be[1] - be[0] + 1)));
+      }
+    }
+    s.KwN = (int)s.KwPhrase.size();
+  }
 }
 
 }  // namespace pf

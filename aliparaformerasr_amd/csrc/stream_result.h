@@ -88,6 +88,10 @@ struct StreamResult {
   // the Viterbi score, the log-likelihood, ok; AlignN = -1 when that GetResults aligned nothing for this stream
   std::vector<int32_t> AlignTs; std::vector<float> AlignTok;
   float AlignPath = 0.f; double AlignLoglik = 0.0; int AlignOk = 0, AlignN = -1;
+  // phrase spotting (Recognizer::SetKeywords) of the last GetResults: per hit the phrase's index, [begin, end] ms (flat) and
+  // the confidence exp(e / dur); KwN = -1 when that GetResults ran without a phrase list
+  std::vector<int32_t> KwPhrase, KwTs; std::vector<double> KwConf;
+  int KwN = -1;
 };
 
 // What a GetResults call knows before its forward runs (Recognizer::configure_engine)

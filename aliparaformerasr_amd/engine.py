@@ -3,6 +3,7 @@ from __future__ import annotations
 
 import ctypes as C
 
+import math
 import numpy as np
 
 from . import _native as N
@@ -316,6 +317,34 @@ def host_ctc_align(lp, y, V=None) -> AlignResult:
                                        _fp(tok)))
     return AlignResult(np.array([[ps.value]], np.float32), np.array([[ll.value]], np.float64), np.array([[ok.value]], np.int32),
                        np.array([[U]], np.int32), first[:, :, :U], last[:, :, :U], tok[:, :, :U])
+
+
+class SpotResult:
+    """CTC phrase spotting (Engine.set_spotter), K phrases per utterance: n_hits [B, K] int32 (every closed hit), begin_end
+    [B, K, max_hits, 2] int32 frame indices and score [B, K, max_hits] float32 of the first max_hits of them; slots at and
+    beyond n_hits hold (-1, -1, 0).  Confidence of a hit: exp(score / (end - begin + 1))."""
+
+    def __init__(self, n_hits, begin_end, score):
+        self.n_hits, self.begin_end, self.score = n_hits, begin_end, score
+
+
+def _flat_phrases(phrases):
+    lens = np.array([len(p) for p in phrases], np.int32)
+    ids = np.array([t for p in phrases for t in p], np.int32)
+    return ids, lens
+
+
+def host_ctc_spot(lp, y, thr, max_hits, V=None) -> SpotResult:
+    """The hits of ONE phrase in ONE utterance in host code (pf_host_ctc_spot, the twin of the device kernel): lp [T, ld]
+    log-prob rows (V <= ld entries read per row), y [U] ids in [1, V) -> SpotResult with B = K = 1."""
+    x = _f32(lp)
+    T, ld = x.shape
+    yy = np.ascontiguousarray(y, dtype=np.int32).reshape(-1)
+    n = C.c_int32()
+    be, sc = np.zeros((1, 1, max(max_hits, 1), 2), np.int32), np.zeros((1, 1, max(max_hits, 1)), np.float32)
+    N.check(N.load().pf_host_ctc_spot(_fp(x), ld, T, int(ld if V is None else V), _i32p(yy), yy.shape[0], float(thr), int(max_hits), n,
+                                      _i32p(be), _fp(sc)))
+    return SpotResult(np.array([[n.value]], np.int32), be, sc)
 
 
 def vad_config(**kw) -> "N.PfVadConfig":
@@ -784,6 +813,7 @@ def host_long_plan(lens, batch_max=0, frame_budget=0):
 class BatchResult:
     def __init__(self, token_ids, token_num, L, V, logits=None, cif_peak=None, scores=None, ctc=None, topk=None, beam=None,
                  align=None, search=None):
+        self.spot = None                # SpotResult (Engine.set_spotter) or None
         self.search = search            # NbestSearchResult (PF_DECODE_TOPK with Engine.set_nbest_search) or None
         self.align = align              # AlignResult (Engine.set_decode(PF_DECODE_ALIGN) with targets or CTC_BEAM) or None
         self.token_ids = token_ids      # [B, L] int64
@@ -949,8 +979,15 @@ def _collect_result(lib, fetch_fn, call, B, want_logits, decode=None):
     search = None
     if decode is not None and decode[1] & N.PF_DECODE_TOPK and len(decode) > 5 and decode[5]:
         search = _fetch_nbest_search(lib, decode[0], B)
+    spot = None
+    if decode is not None and len(decode) > 6 and decode[6] and B * L > 0:
+        K, H = decode[6]
+        spot = SpotResult(np.zeros((B, K), np.int32), np.zeros((B, K, H, 2), np.int32), np.zeros((B, K, H), np.float32))
+        N.check(lib.pf_fetch_spot(decode[0], _i32p(spot.n_hits), _i32p(spot.begin_end), _fp(spot.score)))
     N.check(fetch_fn(C.byref(out)))
-    return BatchResult(ids[:, :L].copy(), tn, L, V, logits, peak, scores, ctc, topk, beam, align, search)
+    res = BatchResult(ids[:, :L].copy(), tn, L, V, logits, peak, scores, ctc, topk, beam, align, search)
+    res.spot = spot
+    return res
 
 
 class Engine:
@@ -981,6 +1018,7 @@ class Engine:
         self._punc_model = None
         self._spk_model = None
         self._search_w = 0
+        self._spot = None
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1020,7 +1058,7 @@ class Engine:
     # ---- forward ------------------------------------------------------------
     def _collect(self, call, B, want_logits):
         return _collect_result(self._lib, lambda o: self._lib.pf_fetch(self._h, o), call, B, want_logits,
-                               (self._h, self._decode, self._beam_n, self._hot, self._lm is not None, self._search_w > 0))
+                               (self._h, self._decode, self._beam_n, self._hot, self._lm is not None, self._search_w > 0, self._spot))
 
     def set_decode(self, flags: int):
         """Decoding extras of the forwards that follow (_native.PF_DECODE_SCORES | PF_DECODE_CTC; 0 = off, the reference
@@ -1059,6 +1097,32 @@ class Engine:
         N.check(self._lib.pf_op_ctc_align(self._h, _fp(x), B, T, int(ld if V is None else V), ld, _i32p(y), _i32p(tl), _i32p(ln), H,
                                           cap, _fp(ps), _dp(ll), _i32p(ok), _i32p(first), _i32p(last), _fp(tok)))
         return AlignResult(ps, ll, ok, tl.copy(), first, last, tok)
+
+    def set_spotter(self, phrases, thr: float = math.log(0.5), max_hits: int = 8):
+        """SenseVoice: the phrase list (lists of token ids) of the forwards that follow — BatchResult.spot says where each
+        phrase was said.  thr: the required mean log-prob per frame (<= 0); an empty list clears."""
+        if not phrases:
+            N.check(self._lib.pf_engine_set_spotter(self._h, None, None, 0, 0.0, 1))
+            self._spot = None
+            return
+        ids, lens = _flat_phrases(phrases)
+        N.check(self._lib.pf_engine_set_spotter(self._h, _i32p(ids), _i32p(lens), len(phrases), float(thr), int(max_hits)))
+        self._spot = (len(phrases), int(max_hits))
+
+    host_ctc_spot = staticmethod(host_ctc_spot)
+
+    def op_ctc_spot(self, lp, phrases, lens, thr, max_hits, V=None) -> SpotResult:
+        """The pipeline's spotting kernel behind its packer on caller data: lp [B, T, ld] (V <= ld entries read per row),
+        phrases = lists of token ids, lens [B]."""
+        x = _f32(lp)
+        B, T, ld = x.shape
+        ids, pl = _flat_phrases(phrases)
+        ln = np.ascontiguousarray(lens, dtype=np.int32)
+        K, H = len(phrases), int(max_hits)
+        out = SpotResult(np.zeros((B, K), np.int32), np.zeros((B, K, max(H, 1), 2), np.int32), np.zeros((B, K, max(H, 1)), np.float32))
+        N.check(self._lib.pf_op_ctc_spot(self._h, _fp(x), B, T, int(ld if V is None else V), ld, _i32p(ids), _i32p(pl), K, _i32p(ln),
+                                         float(thr), H, _i32p(out.n_hits), _i32p(out.begin_end), _fp(out.score)))
+        return out
 
     def set_ctc_beam(self, W: int = 16, n_best: int = 16):
         """Beam width W and list length n_best (1 <= n_best <= W <= 64, default 16 / 16) of PF_DECODE_CTC_BEAM for the

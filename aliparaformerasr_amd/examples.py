@@ -1,7 +1,7 @@
 """Command-line harness mirroring AliParaformerAsr.Examples (`-type offline` and `-type online`).
 
     python -m aliparaformerasr_amd.examples -type offline -method batch -base <dir> -model <name> \
-        [-accuracy int8] [-threads 2] [-decode ctc|frames] [-intake host|device] [-resample linear|sinc] [-nbest N [-topk K] [-beam W | -search W] [-hotboost S] [-lm FILE [-lmweight A] [-lmbonus B] [-lmeos]]] [-align FILE|beam] [-vad [key=value,...] [-vadmodel FILE] [-spk FILE[,cluster=device] [key=value,...]]] [-punc FILE] -files a.wav b.wav
+        [-accuracy int8] [-threads 2] [-decode ctc|frames] [-intake host|device] [-resample linear|sinc] [-nbest N [-topk K] [-beam W | -search W] [-hotboost S] [-lm FILE [-lmweight A] [-lmbonus B] [-lmeos]]] [-align FILE|beam] [-spot FILE [-spotthreshold P] [-spothits N]] [-vad [key=value,...] [-vadmodel FILE] [-spk FILE[,cluster=device] [key=value,...]]] [-punc FILE] -files a.wav b.wav
     python -m aliparaformerasr_amd.examples -type online -method one -base <dir> -model <name> [-endpoint [key=value,...] [-vadmodel FILE] [-secondpass <offline name>]] [-tokentimes [-devicefrontend]] [-puncstream FILE[,max_context=N]] [-intake host|device] [-resample linear|sinc] -files a.wav
 
 Mirrors (file:line in /root/reference/AliParaformerAsr.Examples):
@@ -63,6 +63,10 @@ network and the thresholds are stated, not validated on a real model.
 `-punc FILE` (OfflineRecognizer.SetPuncModel) punctuates every result on the GPU with a CT-Transformer: FILE is a `.pfw` of kind
 cttransformer; under each result goes a `punctuated: ...` line and one `  [begin-end ms] sentence` line per sentence (without the
 times when the result has no timestamp per word).  Rules and dimensions are stated, not validated on a real model.
+`-spot FILE` (offline, SenseVoice models; OfflineRecognizer.SetKeywords) looks for each phrase of FILE (one per line, tokenised
+the way the hot-word file's lines are) in every input and prints `spot: <phrase> [begin-end ms] conf` per hit under the result
+line.  `-spotthreshold P` is the required confidence, a probability in (0, 1] (0.5 is a stated default, unvalidated on real
+speech); `-spothits N` the hits kept per phrase.  Not beside -vad.
 `-align beam` (with `-nbest N -beam W`) aligns the beam search's labelings instead: under each `nbest[i]` line goes
 `align[i] loglik:<...> pairs:[begin,end],...`.
 `-endpoint [key=value,...]` (online; OnlineRecognizer.SetEndpoint) finds sentence ends while the file streams: above the partial
@@ -339,7 +343,7 @@ def _punc_lines(st):
 def offline_recognizer(method="one", model="paraformer-seaco-large-zh-timestamp-onnx-offline", accuracy="int8",
                        threads=2, files=None, base=None, out=sys.stdout, decode="frames", intake="host", nbest=0, topk=4,
                        beam=0, align=None, hotboost=0.0, vad=None, lm=None, lmweight=0.5, lmbonus=0.0, lmeos=False, search=0, vadmodel=None, punc=None, spk=None,
-                       resample="linear"):
+                       resample="linear", spot=None, spotthreshold=0.5, spothits=8):
     from .offline_recognizer import OfflineRecognizer
     base = base or os.getcwd()
     sel = select_model_files(base, model, accuracy)
@@ -382,6 +386,11 @@ def offline_recognizer(method="one", model="paraformer-seaco-large-zh-timestamp-
         rec.SetAlign(True)
         if align != "beam":
             targets = dict(zip(files or [], read_align_file(align)))
+    phrases = None
+    if spot:
+        with open(spot, encoding="utf-8") as f:
+            phrases = [ln.strip() for ln in f if ln.strip()]
+        rec.SetKeywords(phrases, threshold=spotthreshold, max_hits=spothits)
     print("init_models_elapsed_milliseconds:%s" % ((time.perf_counter() - t0) * 1e3), file=out)
     if not files:
         files = []
@@ -416,7 +425,8 @@ def offline_recognizer(method="one", model="paraformer-seaco-large-zh-timestamp-
 
     def extra_lines(st):
         return (_nbest_lines(st, align == "beam") if nbest else []) + (_align_lines(st) if targets is not None else []) + \
-            (_segment_lines(st, bool(spk)) if vad is not None else []) + (_punc_lines(st) if punc else [])
+            (_segment_lines(st, bool(spk)) if vad is not None else []) + (_punc_lines(st) if punc else []) + \
+            (["spot: %s [%d-%d ms] %.4f" % (phrases[k], b, e, c) for k, b, e, c in st.KeywordHits or []] if phrases else [])
     print("Recognition results:\r\n", file=out)
     try:
         if method == "one":
@@ -710,6 +720,25 @@ def parse_args(argv, env=None):
             if i >= len(argv) or argv[i].startswith("-"):
                 raise ValueError("-align takes a file of token ids, or `beam`")
             cfg["align"] = argv[i]
+        elif a == "-spot":
+            i += 1
+            if i >= len(argv) or argv[i].startswith("-"):
+                raise ValueError("-spot takes a file with one phrase per line")
+            cfg["spot"] = argv[i]
+        elif a == "-spotthreshold":
+            try:
+                i += 1
+                cfg["spotthreshold"] = float(argv[i])
+            except (IndexError, ValueError):
+                cfg["spotthreshold"] = float("nan")
+            if not 0.0 < cfg["spotthreshold"] <= 1.0:
+                raise ValueError("The spotthreshold value is a probability in (0, 1]")
+        elif a == "-spothits":
+            try:
+                i += 1
+                cfg["spothits"] = int(argv[i])
+            except (IndexError, ValueError):
+                raise ValueError("The spothits value must be an integer in 1 .. 64")
         elif a == "-vad":
             text = ""
             if i + 1 < len(argv) and not argv[i + 1].startswith("-") and "=" in argv[i + 1]:
@@ -798,6 +827,12 @@ def parse_args(argv, env=None):
         raise ValueError("-nbest is an offline option")
     if "align" in cfg and cfg["recognizerType"] != "offline":
         raise ValueError("-align is an offline option")
+    if "spot" in cfg and cfg["recognizerType"] != "offline":
+        raise ValueError("-spot is an offline option")
+    if "spot" in cfg and "vad" in cfg:
+        raise ValueError("-spot does not go with -vad")
+    if ("spotthreshold" in cfg or "spothits" in cfg) and "spot" not in cfg:
+        raise ValueError("-spotthreshold and -spothits go with -spot FILE")
     if "vad" in cfg and cfg["recognizerType"] != "offline":
         raise ValueError("-vad is an offline option")
     if "vad" in cfg and ("nbest" in cfg or "align" in cfg):
@@ -846,7 +881,8 @@ def main(argv=None):
                            hotboost=cfg.get("hotboost", 0.0), vad=cfg.get("vad"), lm=cfg.get("lm"), lmweight=cfg.get("lmweight", 0.5),
                            lmbonus=cfg.get("lmbonus", 0.0), lmeos=cfg.get("lmeos", False), search=cfg.get("search", 0),
                            vadmodel=cfg.get("vadmodel"), punc=cfg.get("punc"), spk=cfg.get("spk"),
-                           resample=cfg.get("resample", "linear"))
+                           resample=cfg.get("resample", "linear"), spot=cfg.get("spot"), spotthreshold=cfg.get("spotthreshold", 0.5),
+                           spothits=cfg.get("spothits", 8))
     else:
         print("the recognizer type must be online or offline")
         return 2

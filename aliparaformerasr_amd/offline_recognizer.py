@@ -11,6 +11,7 @@ ctypes stub a Python caller uses, exactly as INTEGRATION.md's P/Invoke stub is f
 from __future__ import annotations
 
 import ctypes as C
+import math
 from dataclasses import dataclass, field
 from typing import List, Optional
 
@@ -379,6 +380,17 @@ class OfflineStream:
                          Timestamps=[[pt[2 * j], pt[2 * j + 1]] for j in range(k)], Scores=[ps[j] for j in range(k)])
 
     @property
+    def KeywordHits(self) -> Optional[list]:
+        """The hits of the recognizer's phrase list (OfflineRecognizer.SetKeywords) in the last GetResults:
+        [(phrase_index, begin_ms, end_ms, confidence)], phrase by phrase, each phrase's in time order; None when that
+        GetResults ran without a list."""
+        ph, ts, cf, n = C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)(), C.POINTER(C.c_double)(), C.c_int32()
+        _ck(self._lib.pf_stream_keyword_hits(self._h, C.byref(ph), C.byref(ts), C.byref(cf), n))
+        if n.value < 0:
+            return None
+        return [(ph[j], ts[2 * j], ts[2 * j + 1], cf[j]) for j in range(n.value)]
+
+    @property
     def Timestamps(self) -> List[List[int]]:
         n = C.c_int32()
         _ck(self._lib.pf_stream_num_timestamps(self._h, n))
@@ -458,6 +470,7 @@ class OfflineRecognizer:
                                            enc(tokensFilePath), enc(modelebFilePath), enc(hotwordFilePath),
                                            batchSize, threadsNum, device, C.byref(h)))
         self._h = h
+        self._tokens_path = tokensFilePath
 
     def CreateOfflineStream(self) -> OfflineStream:
         s = C.c_void_p()
@@ -531,6 +544,41 @@ class OfflineRecognizer:
         in the audio, and log P(text | audio); with SetCtcBeam every Alternative gets Timestamps of its own and LogLik.
         Tokens, Timestamps, Scores, the result text and the alternatives' order and scores stay as they are."""
         _ck(self._lib.pf_recognizer_set_align(self._h, 1 if on else 0))
+
+    def SetKeywords(self, phrases, threshold: float = 0.5, max_hits: int = 8) -> None:
+        """SenseVoice models: phrase spotting on the device for every GetResults that follows (off by default; None or an
+        empty list turns it off again).  phrases: lists of token ids, or lines of text tokenised the way the hot-word file's
+        lines are (per character against the token table, unknown characters dropped — pass ids where sentencepiece pieces
+        are needed).  A stream's KeywordHits then says where each phrase was said and how sure the model is.  threshold: the
+        required confidence in (0, 1], the geometric mean of the path's per-frame probabilities (0.5 is a stated default;
+        nobody has validated it on real speech); max_hits: hits kept per phrase and stream (1 .. 64).  Tokens, Timestamps,
+        Scores and the result text stay as they are.  Not available beside SetVad."""
+        if not phrases:
+            _ck(self._lib.pf_recognizer_set_keywords(self._h, None, None, 0, 0.0, 1))
+            return
+        if not 0.0 < float(threshold) <= 1.0:
+            raise ValueError("SetKeywords: the threshold is a probability in (0, 1]")
+        text = [p for p in phrases if isinstance(p, str)]
+        spelled = iter(self._tokenise(text)) if text else iter(())
+        ids = [next(spelled) if isinstance(p, str) else [int(t) for t in p] for p in phrases]
+        flat = [t for p in ids for t in p]
+        a = (C.c_int32 * max(len(flat), 1))(*flat)
+        ln = (C.c_int32 * len(ids))(*[len(p) for p in ids])
+        _ck(self._lib.pf_recognizer_set_keywords(self._h, a, ln, len(ids), math.log(float(threshold)), int(max_hits)))
+
+    def _tokenise(self, lines):
+        """GetHotwords' rule (pf_host_hotword_ids) over the recognizer's token table: one id list per line"""
+        with open(self._tokens_path, encoding="utf-8") as f:
+            toks = f.read().splitlines()
+        enc = lambda xs: (C.c_char_p * len(xs))(*[x.encode("utf-8") for x in xs])
+        cap = sum(len(x) for x in lines) + len(lines) + 1
+        ids, lens, n = (C.c_int32 * cap)(), (C.c_int32 * (len(lines) + 1))(), C.c_int32()
+        _ck(self._lib.pf_host_hotword_ids(enc(toks), len(toks), enc(lines), len(lines), ids, cap, lens, len(lines) + 1, n))
+        out, off = [], 0
+        for i in range(len(lines)):
+            out.append(list(ids[off: off + lens[i]]))
+            off += lens[i]
+        return out
 
     def SetVad(self, cfg=True, batch_max: int = 0, frame_budget: int = 0, sep: str = "") -> None:
         """Long-audio recognition for every GetResults that follows (off by default; SetVad(None) turns it off again): each

@@ -333,6 +333,23 @@ namespace AliParaformerAsr.Hip
             }
         }
 
+        /// <summary>Not in the reference: the hits of the recognizer's phrase list (OfflineRecognizer.SetKeywords) in the last
+        /// GetResults as (phrase index, begin ms, end ms, confidence), phrase by phrase, each phrase's in time order; null when
+        /// that GetResults ran without a list.</summary>
+        public List<(int Phrase, int BeginMs, int EndMs, double Confidence)>? KeywordHits
+        {
+            get
+            {
+                ParaformerHip.Check(ParaformerHip.pf_stream_keyword_hits(Handle, out IntPtr ph, out IntPtr ts, out IntPtr cf, out int n));
+                if (n < 0) return null;
+                var k = new int[n]; var flat = new int[2 * n]; var c = new double[n];
+                if (n > 0) { Marshal.Copy(ph, k, 0, n); Marshal.Copy(ts, flat, 0, 2 * n); Marshal.Copy(cf, c, 0, n); }
+                var r = new List<(int, int, int, double)>(n);
+                for (int j = 0; j < n; j++) r.Add((k[j], flat[2 * j], flat[2 * j + 1], c[j]));
+                return r;
+            }
+        }
+
         public List<int[]> Timestamps                                           // OfflineStream.cs:33
         {
             get
@@ -468,6 +485,20 @@ namespace AliParaformerAsr.Hip
         /// follows (off by default): a stream with a target (OfflineStream.SetAlignIds) gets OfflineStream.Alignment, and with
         /// SetCtcBeam every Alternative gets Timestamps of its own and LogLik.  Everything else stays as it is.</summary>
         public void SetAlign(bool on = true) => ParaformerHip.Check(ParaformerHip.pf_recognizer_set_align(_r, on ? 1 : 0));
+
+        /// <summary>Not in the reference: SenseVoice models — phrase spotting on the device for every GetResults that follows (off
+        /// by default; null or an empty list turns it off again).  phrases: token ids per phrase; threshold: the required
+        /// confidence in (0, 1], the geometric mean of the path's per-frame probabilities (0.5 is a stated default, not validated
+        /// on real speech); maxHits: hits kept per phrase and stream (1 .. 64).  OfflineStream.KeywordHits then says where each
+        /// phrase was said.  Tokens, Timestamps, Scores and the result text stay as they are.  Not available beside SetVad.</summary>
+        public void SetKeywords(IList<int[]>? phrases, double threshold = 0.5, int maxHits = 8)
+        {
+            if (phrases == null || phrases.Count == 0) { ParaformerHip.Check(ParaformerHip.pf_recognizer_set_keywords(_r, null, null, 0, 0f, 1)); return; }
+            if (!(threshold > 0.0 && threshold <= 1.0)) throw new ArgumentOutOfRangeException(nameof(threshold));
+            var ids = new List<int>(); var lens = new int[phrases.Count];
+            for (int i = 0; i < phrases.Count; i++) { ids.AddRange(phrases[i]); lens[i] = phrases[i].Length; }
+            ParaformerHip.Check(ParaformerHip.pf_recognizer_set_keywords(_r, ids.ToArray(), lens, lens.Length, (float)Math.Log(threshold), maxHits));
+        }
 
         /// <summary>Not in the reference: long-audio recognition for every GetResults that follows (off by default; null turns it
         /// off again).  Each stream is cut into speech segments on the device, the call's segments are batched by length, forwarded

@@ -283,6 +283,11 @@ namespace AliParaformerAsr.Native
         [DllImport(Lib)] internal static extern int pf_recognizer_set_nbest(IntPtr r, int N, int K);
         [DllImport(Lib)] internal static extern int pf_recognizer_set_ctc_beam(IntPtr r, int N, int W, int K);
         [DllImport(Lib)] internal static extern int pf_recognizer_set_align(IntPtr r, int on);
+        // phrase spotting (SenseVoice): a phrase list on the engine / on every engine of a recognizer's pool, the hits per stream
+        [DllImport(Lib)] internal static extern int pf_engine_set_spotter(IntPtr e, int[]? ids, int[]? lens, int nKeywords, float thr, int maxHits);
+        [DllImport(Lib)] internal static extern int pf_fetch_spot(IntPtr e, [Out] int[]? nHits, [Out] int[]? beginEnd, [Out] float[]? score);
+        [DllImport(Lib)] internal static extern int pf_recognizer_set_keywords(IntPtr r, int[]? ids, int[]? lens, int n, float thr, int maxHits);
+        [DllImport(Lib)] internal static extern int pf_stream_keyword_hits(IntPtr s, out IntPtr phrase, out IntPtr beginEndMs, out IntPtr conf, out int n);
         [DllImport(Lib)] internal static extern int pf_stream_set_align_ids(IntPtr s, long[]? ids, int n);
         [DllImport(Lib)] internal static extern int pf_stream_alignment(IntPtr s, out IntPtr beginEnd, out IntPtr tokScore, out int n, out float pathScore,
                                                                        out double loglik, out int ok);

@@ -516,6 +516,45 @@ int pf_fetch_align(pf_engine* e, float* path_score, double* loglik, int32_t* ok,
 int pf_host_ctc_align(const float* lp, int64_t ld, int32_t T, int32_t V, const int64_t* y, int32_t U, float* path_score,
                       double* loglik, int32_t* ok, int32_t* first, int32_t* last, float* tok_score);
 
+/* ---- CTC phrase spotting (additions to ABI 6; nothing is launched, allocated or changed without a phrase list) ---------
+   WHERE in an utterance was a phrase said, and how sure are we: with a phrase list installed one kernel (csrc/k_ctcspot.hip)
+   behind the other decode launches runs, for every (utterance, phrase), a Viterbi DP over the log-prob rows with a FREE START
+   at every frame and an EXIT at every frame.  SenseVoice only, every math_mode; there is no decode bit of its own: installing
+   the list makes the forward keep the log-softmax rows exactly as PF_DECODE_ALIGN does.  PF_ERR_UNSUPPORTED for a paraformer
+   or SeACo model and for a pf_group forward.  The API takes token IDS, as forced alignment does.
+   INPUTS per (utterance b, phrase k): the rows lp[t, :] of the frames t < n_b (n_b as for PF_DECODE_CTC, prompt rows included)
+   and the phrase y[0 .. U), 1 <= U <= PF_SPOT_MAX_TOKENS, ids in [1, V); the blank is id 0.
+   STATES s in [0, 2U - 1): even s is token y[s/2], odd s the blank; no leading or trailing blank, so a hit spans the first
+   frame of the first token to the last frame of the last token.
+   RECURRENCE, float32, one add per cell: v_t[0] = lp_t[y0] with start_t[0] = t (the restart); for s >= 1
+   v_t[s] = lp_t[lab(s)] + best of v_{t-1}[s] (stay), v_{t-1}[s-1] (step), v_{t-1}[s-2] (skip: even s >= 2 with
+   y[s/2] != y[s/2 - 1] only), scanned in that order, replaced only on strictly greater; start_t[s] is the chosen
+   predecessor's.  Unreached states hold -inf / -1; at t = 0 only state 0 is reached.
+   CANDIDATES: at every frame t the exit state gives e = v_t[2U - 2], begin = start_t[2U - 2], dur = t - begin + 1; a candidate
+   iff e > -inf and e >= thr * (float)dur (one float32 product; thr <= 0 is the required mean log-prob per frame).
+   HITS, inline, left to right, one open hit `cur`: a candidate with begin > cur.end (or the first) closes cur as a hit and opens
+   itself; otherwise it replaces cur iff e * (float)cur.dur > cur.e * (float)dur (two float32 products, strictly), else it is
+   dropped; after the last frame cur is closed.  n_hits counts every closed hit; the first max_hits are stored as
+   (begin, end, e), the slots at and beyond n_hits hold (-1, -1, 0).  Confidence = exp(e / dur), the caller's to compute.
+   Rows must be finite or -inf; the definition in numpy is tests/ctcspot_ref.py.  token_ids and every other pf_fetch_* are what
+   they are without the list. */
+#define PF_SPOT_MAX_TOKENS 32
+#define PF_SPOT_MAX_KEYWORDS 1024
+#define PF_SPOT_MAX_HITS 64
+/* The phrase list of the forwards that FOLLOW on this engine: n_keywords phrases, phrase i = lens[i] ids at ids[sum of the lens
+   before]; packed and uploaded once here.  ids == NULL or n_keywords == 0 clears it.  PF_ERR_INVALID_ARG: an id outside [1, V),
+   a length outside [1, PF_SPOT_MAX_TOKENS], max_hits outside [1, PF_SPOT_MAX_HITS], thr > 0 or NaN; PF_ERR_CAPACITY: more than
+   PF_SPOT_MAX_KEYWORDS phrases (the installed list stays). */
+int pf_engine_set_spotter(pf_engine* e, const int32_t* ids, const int32_t* lens, int32_t n_keywords, float thr, int32_t max_hits);
+/* n_hits [B, K], begin_end [B, K, max_hits, 2] (frame indices in the row, as pf_fetch_ctc), score [B, K, max_hits], each
+   optional; K and max_hits as installed for that forward.  PF_ERR_INVALID_ARG when that forward ran without a phrase list.  Call
+   it BEFORE the pf_fetch that receives token_ids (it releases the thread's slot). */
+int pf_fetch_spot(pf_engine* e, int32_t* n_hits, int32_t* begin_end, float* score);
+/* The same for ONE utterance and ONE phrase in plain host code (the twin of the kernel): lp [T, ld] (V read per row), y [U];
+   begin_end [max_hits, 2], score [max_hits], every slot written. */
+int pf_host_ctc_spot(const float* lp, int64_t ld, int32_t T, int32_t V, const int32_t* y, int32_t U, float thr, int32_t max_hits,
+                     int32_t* n_hits, int32_t* begin_end, float* score);
+
 /* ---- PCM intake (additions to ABI 6) --------------------------------------------------------------------------------
    The audio in the form callers hold it — a wav payload, PCM off a socket — uploaded RAW and turned into the engine's
    float32 mono samples at `fs` by one kernel (csrc/k_pcm.hip) in front of the unchanged fbank.  The result is bit for bit
@@ -1181,6 +1220,13 @@ int pf_op_lm_score(pf_engine* e, const pf_lm* lm, const int32_t* ids, const int3
 int pf_op_ctc_align(pf_engine* e, const float* lp, int32_t B, int32_t T, int32_t V, int32_t ld, const int32_t* tgt,
                     const int32_t* tlen, const int32_t* lens, int32_t H, int32_t cap, float* path_score, double* loglik,
                     int32_t* ok, int32_t* first, int32_t* last, float* tok_score);
+/* exactly the pipeline's spotting kernel (k_ctcspot.hip) behind its packer on caller arrays: lp [B * T, ld] (V read per row),
+   the phrases as for pf_engine_set_spotter (same refusals), lens [B] (clamped to 0 .. T; nothing at or beyond lens[b] or V is
+   read).  Outputs as pf_fetch_spot, every slot written (checked: PF_ERR_DEVICE names a slot the kernel left, or a cell behind
+   the block that it touched). */
+int pf_op_ctc_spot(pf_engine* e, const float* lp, int32_t B, int32_t T, int32_t V, int32_t ld, const int32_t* ids,
+                   const int32_t* phrase_lens, int32_t n_keywords, const int32_t* lens, float thr, int32_t max_hits,
+                   int32_t* n_hits, int32_t* begin_end, float* score);
 /* C = A[M,K] * W[N,K]^T + bias, f16 operands / f32 accumulate; epilogue 0 none, 1 relu,
    2 = f16 result store (the path the pipeline uses), returned widened to fp32. */
 /* One dynamically quantised Linear, the building block of math_mode 2 (the reference's default model.int8.onnx:
@@ -1656,6 +1702,17 @@ int pf_recognizer_set_ctc_beam(pf_recognizer* r, int32_t N, int32_t W, int32_t K
    Timestamps, Scores, the result text and the alternatives' order and scores are what they are without it.  The pointers stay
    valid until the stream's next GetResults. */
 int pf_recognizer_set_align(pf_recognizer* r, int32_t on);
+/* SenseVoice only (see "CTC phrase spotting"; PF_ERR_UNSUPPORTED otherwise).  The phrase list (token IDS, as for
+   pf_engine_set_spotter, same refusals) of every GetResults that follows, on every engine of the pool, present and future;
+   ids == NULL or n == 0 clears it.  thr = the required mean log-prob per frame (<= 0), max_hits in 1 .. PF_SPOT_MAX_HITS.
+   After GetResults pf_stream_keyword_hits gives the stream's hits, phrase by phrase in list order, each phrase's in time order:
+   phrase [*n] (index into the list), begin_end_ms [*n, 2] (begin = ms * max(first - 4, 0), end = ms * max(last + 1 - 4, 0),
+   ms = lfr_n * 10, exactly as pf_stream_alignment), conf [*n] = exp(e / dur) in double; *n = -1 when that GetResults ran
+   without a list.  Tokens, Timestamps, Scores and the result text are what they are without it.  The pointers stay valid until
+   the stream's next GetResults.  PF_ERR_UNSUPPORTED while pf_recognizer_set_vad is on, and pf_recognizer_set_vad is refused
+   while a list is installed (spotting across stitched segments is not offered). */
+int pf_recognizer_set_keywords(pf_recognizer* r, const int32_t* ids, const int32_t* lens, int32_t n, float thr, int32_t max_hits);
+int pf_stream_keyword_hits(pf_stream* s, const int32_t** phrase, const int32_t** begin_end_ms, const double** conf, int32_t* n);
 /* SenseVoice only (see "CTC hot words"; PF_ERR_UNSUPPORTED otherwise).  boost > 0: the beam search of
    pf_recognizer_set_ctc_beam is biased towards the batch's hot words by `boost` per matched token; 0 = off; inert until
    pf_recognizer_set_ctc_beam is set.  The hot words of a GetResults call follow the SeACo rule: the union of the batch's
