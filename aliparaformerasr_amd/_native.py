@@ -364,6 +364,15 @@ SIGNATURES = {
     "pf_engine_punctuate": (C.c_int, [_vp, _i32, _i32, C.c_int32, _i32, _i32]),
     "pf_op_punc_logits": (C.c_int, [_vp, _i32, _i32, C.c_int32, _f, _f]),
     "pf_op_punc_window": (C.c_int, [_vp, _i32, _i32, _i32, C.c_int32, _i32, _i32, _f]),
+    "pf_nnlm_model_load": (C.c_int, [C.c_char_p, _P(_vp)]),
+    "pf_nnlm_model_from_memory": (C.c_int, [_vp, C.c_int64, _P(_vp)]),
+    "pf_nnlm_model_info": (C.c_int, [_vp, _i32, _i64]),
+    "pf_nnlm_model_free": (None, [_vp]),
+    "pf_engine_set_nnlm": (C.c_int, [_vp, _vp]),
+    "pf_engine_nnlm_score": (C.c_int, [_vp, _i32, _i32, C.c_int32, C.c_int32, _f, _f]),
+    "pf_op_nnlm_logp": (C.c_int, [_vp, _i32, _i32, C.c_int32, C.c_int32, _f, _f]),
+    "pf_host_nnlm_logp": (C.c_int, [_vp, _i32, C.c_int32, _P(C.c_double)]),
+    "pf_host_nnlm_fuse": (C.c_int, [_P(C.c_double), _P(C.c_double), _i32, C.c_int32, C.c_double, C.c_double, _P(C.c_double), _i32]),
     "pf_punc_model_causal": (C.c_int, [_vp, _i32]),
     "pf_punc_stream_state_bytes": (C.c_int, [_vp, _i64]),
     "pf_host_punc_stream_state_bytes": (C.c_int, [_vp, _i64]),
@@ -448,6 +457,8 @@ SIGNATURES = {
     "pf_recognizer_set_vad": (C.c_int, [_vp, _P(PfVadConfig), C.c_int32, C.c_int64, C.c_char_p]),
     "pf_recognizer_set_vad_model": (C.c_int, [_vp, C.c_char_p]),
     "pf_recognizer_set_punc_model": (C.c_int, [_vp, C.c_char_p]),
+    "pf_recognizer_set_nnlm": (C.c_int, [_vp, C.c_char_p, C.c_double, C.c_double, C.c_int32]),
+    "pf_stream_alternative_nnlm": (C.c_int, [_vp, C.c_int32, _P(C.c_double)]),
     "pf_recognizer_set_spk_model": (C.c_int, [_vp, C.c_char_p, _P(PfSpkConfig)]),
     "pf_recognizer_set_spk_cluster": (C.c_int, [_vp, C.c_int32]),
     "pf_stream_num_speakers": (C.c_int, [_vp, _i32]),

@@ -18,6 +18,7 @@ mismatch with a real file fails loudly instead of producing a silently wrong mod
     python -m aliparaformerasr_amd.convert vad.onnx|vad.pt out.pfw --kind fsmnvad --mvn vad.mvn [--sil 0,...] [--lfr-m 5]
     python -m aliparaformerasr_amd.convert punc.pt|punc.onnx out.pfw --kind cttransformer --tokens tokens.json [--heads 8] [--causal]
     python -m aliparaformerasr_amd.convert campplus.bin|.pt out.pfw --kind campplus [--seg-len 100] [--dilations 1,2,2]
+    python -m aliparaformerasr_amd.convert lm.pt out.pfw --kind transformerlm [--heads 8]
         (FunASR's FSMN-VAD, the model score of the voice-activity segmentation: vad_state_dict_to_pfw / vad_onnx_to_state_dict.
          NO REAL FSMN-VAD FILE HAS BEEN THROUGH THIS ROUTE: the names are restated from the public FunASR sources and
          exercised on tests/fsmn_vad_like.py)
@@ -636,6 +637,48 @@ def spk_to_pfw(model_path, seg_len=100, dilations=(1, 2, 2)):
     return spk_state_dict_to_pfw(sd, seg_len, dilations)
 
 
+def nnlm_state_dict_to_pfw(sd: dict, heads: int = 8):
+    """ESPnet TransformerLM state dict -> (cfg, PFW weights) of kind "transformerlm" (weights.nnlm_tensor_shapes).  The names
+    are ESPnet's as remembered (embed.weight, encoder.embed.0 / .1, encoder.encoders.N.{norm1, norm2, self_attn.linear_{q, k, v,
+    out}, feed_forward.w_{1, 2}}, encoder.after_norm, decoder), not read from a released file; q, k and v are concatenated."""
+    def get(name):
+        if name not in sd:
+            raise ValueError("transformerlm: the state dict lacks %r" % name)
+        return np.asarray(sd[name], dtype=np.float32)
+    n_layers = 1 + max([int(m.group(1)) for k in sd for m in [re.match(r"encoder\.encoders\.(\d+)\.", k)] if m], default=-1)
+    if n_layers < 1:
+        raise ValueError("transformerlm: the state dict holds no encoder.encoders.N layer")
+    w = {"embed.weight": get("embed.weight")}
+    for dst, src in (("input.linear", "encoder.embed.0"), ("input.norm", "encoder.embed.1"), ("after_norm", "encoder.after_norm"),
+                     ("decoder", "decoder")):
+        w[dst + ".weight"], w[dst + ".bias"] = get(src + ".weight"), get(src + ".bias")
+    for l in range(n_layers):
+        s, p = "encoder.encoders.%d." % l, "layers.%d." % l
+        for part in ("weight", "bias"):
+            w[p + "attn.qkv." + part] = np.concatenate([get(s + "self_attn.linear_%s.%s" % (x, part)) for x in "qkv"], axis=0)
+        for dst, src in (("norm1", "norm1"), ("norm2", "norm2"), ("attn.out", "self_attn.linear_out"), ("ffn.w1", "feed_forward.w_1"),
+                         ("ffn.w2", "feed_forward.w_2")):
+            w[p + dst + ".weight"], w[p + dst + ".bias"] = get(s + src + ".weight"), get(s + src + ".bias")
+    V, E = w["embed.weight"].shape
+    D, F = w["input.linear.weight"].shape[0], w["layers.0.ffn.w1.weight"].shape[0]
+    cfg = W.transformer_lm_config(vocab=int(V), embed=int(E), d_model=int(D), heads=int(heads), ffn=int(F), n_layers=n_layers)
+    shapes = W.nnlm_tensor_shapes(cfg)
+    for name, shape in shapes.items():
+        if tuple(w[name].shape) != tuple(shape):
+            raise ValueError("transformerlm: %s has shape %r, expected %r" % (name, tuple(w[name].shape), tuple(shape)))
+    return cfg, {name: np.ascontiguousarray(w[name], dtype=np.float32) for name in shapes}
+
+
+def nnlm_to_pfw(model_path, heads=8):
+    """model.pt (a state dict; the ONNX route does not exist) -> (cfg, PFW weights) of kind "transformerlm"."""
+    if str(model_path).endswith(".onnx"):
+        raise ValueError("transformerlm: the converter reads a state dict (.pt / .pb), not an ONNX export")
+    import torch
+    sd = torch.load(model_path, map_location="cpu")
+    sd = sd.get("state_dict", sd.get("model", sd)) if isinstance(sd, dict) else sd
+    return nnlm_state_dict_to_pfw({k: v.float().numpy() for k, v in sd.items() if hasattr(v, "numpy")}, heads)
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     if len(argv) < 2:
@@ -644,6 +687,12 @@ def main(argv=None):
     kind, ts = "paraformer", None
     if "--kind" in argv:
         kind = argv[argv.index("--kind") + 1]
+    if kind == "transformerlm":
+        heads = int(argv[argv.index("--heads") + 1]) if "--heads" in argv else 8
+        cfg, wts = nnlm_to_pfw(argv[0], heads)
+        W.save_pfw(argv[1], cfg, wts)
+        print("wrote %s (%s, %d tensors)" % (argv[1], cfg["kind"], len(wts)))
+        return 0
     if kind == "fsmnvad":
         if "--mvn" not in argv:
             print("--kind fsmnvad needs --mvn vad.mvn (the model's own CMVN)")

@@ -1446,6 +1446,82 @@ int pf_op_punc_window(pf_engine* h, const int32_t* ids, const int32_t* T, const 
   PF_CATCH
 }
 
+// ---- neural LM rescoring ----
+int pf_nnlm_model_load(const char* path, pf_nnlm_model** m) {
+  return new_model_handle(m, path, "path", [&] { return nnlm_model_load(path); });
+}
+int pf_nnlm_model_from_memory(const void* data, int64_t nbytes, pf_nnlm_model** m) {
+  return new_model_handle(m, data, "data", [&] { return nnlm_model_from_memory(data, nbytes); });
+}
+int pf_nnlm_model_info(const pf_nnlm_model* m, int32_t* dims, int64_t* image_bytes) {
+  PF_TRY
+  NEED(m);
+  const NnlmModel& v = *m->p;
+  if (dims) {
+    const int32_t d[8] = {v.vocab, v.embed_dim, v.d_model, v.heads, v.ffn, v.n_layers, v.sos(), 0};
+    std::memcpy(dims, d, sizeof(d));
+  }
+  if (image_bytes) *image_bytes = (int64_t)v.image.size();
+  return PF_OK;
+  PF_CATCH
+}
+void pf_nnlm_model_free(pf_nnlm_model* m) { delete m; }
+int pf_engine_set_nnlm(pf_engine* h, const pf_nnlm_model* m) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->set_nnlm(m ? m->p : nullptr);
+  return PF_OK;
+  PF_CATCH
+}
+// the argument checks pf_engine_nnlm_score and pf_op_nnlm_logp share
+static void nnlm_need(const int32_t* ids, const int32_t* lens, int32_t B) {
+  PF_CHECK(B >= 0, PF_ERR_INVALID_ARG, "nnlm: negative B");
+  int64_t total = 0;
+  if (B > 0) NEED(lens);
+  for (int b = 0; b < B; ++b) total += std::max(lens[b], 0);
+  if (total > 0) NEED(ids);
+}
+int pf_engine_nnlm_score(pf_engine* h, const int32_t* ids, const int32_t* lens, int32_t B, int32_t flags, float* lm_sum, float* logp) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  nnlm_need(ids, lens, B);
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->nnlm_score(ids, lens, B, flags, lm_sum, logp);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_op_nnlm_logp(pf_engine* h, const int32_t* ids, const int32_t* lens, int32_t B, int32_t flags, float* logp, float* lm_sum) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  nnlm_need(ids, lens, B);
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->op_nnlm_logp(ids, lens, B, flags, logp, lm_sum);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_host_nnlm_logp(const pf_nnlm_model* m, const int32_t* ids, int32_t n, double* logp) {
+  PF_TRY
+  NEED(m); NEED(logp);
+  PF_CHECK(n >= 0 && n <= PF_NNLM_MAX_TOKENS, PF_ERR_INVALID_ARG, "nnlm_logp: a hypothesis holds 0 .. PF_NNLM_MAX_TOKENS tokens");
+  if (n > 0) NEED(ids);
+  host_nnlm_logp(*m->p, ids, n, logp);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_host_nnlm_fuse(const double* base, const double* lm_sum, const int32_t* n_tokens, int32_t N, double weight, double bonus,
+                      double* score, int32_t* order) {
+  PF_TRY
+  PF_CHECK(N >= 0, PF_ERR_INVALID_ARG, "nnlm_fuse: negative N");
+  if (N > 0) { NEED(base); NEED(lm_sum); NEED(n_tokens); NEED(score); NEED(order); }
+  host_nnlm_fuse(base, lm_sum, n_tokens, N, weight, bonus, score, order);
+  return PF_OK;
+  PF_CATCH
+}
+
 // ---- punctuation, streaming ----
 int pf_punc_model_causal(const pf_punc_model* m, int32_t* causal) {
   PF_TRY
@@ -2465,6 +2541,22 @@ int pf_recognizer_set_punc_model(pf_recognizer* h, const char* pfw_path) {
   std::shared_ptr<Recognizer> r = R(h);
   PF_CHECK(!r->disposed(), PF_ERR_DISPOSED, "OfflineRecognizer");
   r->SetPuncModel(pfw_path ? pfw_path : "");
+  return PF_OK;
+  PF_CATCH
+}
+int pf_recognizer_set_nnlm(pf_recognizer* h, const char* pfw_path, double weight, double bonus, int32_t flags) {
+  PF_TRY
+  std::shared_ptr<Recognizer> r = R(h);
+  PF_CHECK(!r->disposed(), PF_ERR_DISPOSED, "OfflineRecognizer");
+  r->SetRescoreModel(pfw_path ? pfw_path : "", weight, bonus, flags);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_stream_alternative_nnlm(pf_stream* h, int32_t i, double* nnlm_sum) {
+  PF_TRY
+  Stream* s = S(h);
+  PF_CHECK(i >= 0 && i < (int32_t)s->Alternatives.size(), PF_ERR_INVALID_ARG, "alternative index out of range");
+  if (nnlm_sum) *nnlm_sum = s->Alternatives[(size_t)i].nnlm_sum;
   return PF_OK;
   PF_CATCH
 }

@@ -12,6 +12,7 @@
 #include "lm.h"
 #include "vadnet.h"
 #include "spk.h"
+#include "nnlm.h"
 #include "punc.h"
 #include "json.h"
 #include "kernels.h"
@@ -314,6 +315,16 @@ class Engine {
                         float* logits_dev, int32_t* flush_mark_dev);
   void op_punc_stream_step(void* states, const int32_t* ids, const int32_t* n_new, const int32_t* flush, int B, int ld, int max_context,
                            int flags, int32_t* marks, int32_t* mark_flags, float* logits, int32_t* flush_mark);
+  // The causal Transformer LM (k_nnlm.hip, nnlm.h).  nullptr detaches and frees the image and the workspace (nothing of it is
+  // launched or allocated then).  The engine keeps a reference and uploads the image once.  A forward is profile class "nnlm":
+  // 2 + 2 n_layers launches whatever B and the lengths.
+  void set_nnlm(const std::shared_ptr<const NnlmModel>& m);
+  const std::shared_ptr<const NnlmModel>& nnlm_model() const { return nnlm_; }
+  // B hypotheses from the host (ids = their concatenated tokens, lens [B]): one upload, one forward, one copy back.  lm_sum [B],
+  // logp [sum (lens + 1)]; either may be null.  flags: PF_NNLM_EOS
+  void nnlm_score(const int32_t* ids, const int32_t* lens, int B, int flags, float* lm_sum, float* logp);
+  // the same through op_stage.h: hostile workspace and ids behind the rows, sentinel-filled outputs with guard cells, checked
+  void op_nnlm_logp(const int32_t* ids, const int32_t* lens, int B, int flags, float* logp, float* lm_sum);
   // The CAM++ speaker model (k_spk.hip, spk.h).  nullptr detaches and frees the image and the workspace (nothing of it is
   // launched or allocated then; attaching the model an engine still has costs no upload).  The engine keeps a reference and
   // uploads the image once.  PF_ERR_INVALID_ARG unless the model's n_mels is the front-end's.  A forward is profile class
@@ -799,6 +810,11 @@ class Engine {
   std::shared_ptr<const PuncModel> punc_;
   ModelDev<PuncModel> punc_dev_;
   DevBuf ws_punc_;
+  // the LM (set_nnlm): as above; ws_nnlm_ holds offsets, ids, targets, x, the two q | k | v buffers, ctx, logp and lm_sum
+  std::shared_ptr<const NnlmModel> nnlm_;
+  ModelDev<NnlmModel> nnlm_dev_;
+  DevBuf ws_nnlm_;
+  void run_nnlm(const int32_t* ids, const int32_t* lens, int B, int flags, float* lm_sum, float* logp, bool guarded);
   // the speaker model (set_spk_model): as above; ws_spk_ holds the window table, the rows, the head's three activation buffers,
   // the TDNN's frames, the four X buffers, the embeddings and the frames asked for
   std::shared_ptr<const SpkModel> spk_;

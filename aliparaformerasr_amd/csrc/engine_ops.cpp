@@ -1074,6 +1074,121 @@ void Engine::op_punc(const int32_t* ids, const int32_t* T, const int32_t* last, 
   run_punc(ids, off.data(), last, B, logits, x0, p, cut);
 }
 
+// ---- the causal Transformer LM (k_nnlm.hip; the launch plan is at the head of that file)
+void Engine::set_nnlm(const std::shared_ptr<const NnlmModel>& m) { attach_model(nnlm_, nnlm_dev_, ws_nnlm_, m); }
+
+// one forward over B hypotheses (host arrays in, host arrays out; returns after the results have arrived).  guarded: the
+// op_stage.h form, G guard cells behind ids, targets, lm_sum and logp, the activations poisoned before the first launch
+void Engine::run_nnlm(const int32_t* ids, const int32_t* lens, int B, int flags, float* lm_sum, float* logp, bool guarded) {
+  PF_CHECK(nnlm_ != nullptr, PF_ERR_INVALID_ARG, "nnlm: no model is attached (pf_engine_set_nnlm)");
+  PF_CHECK(B >= 0 && B <= PF_NNLM_MAX_BATCH && (flags & ~PF_NNLM_EOS) == 0, PF_ERR_INVALID_ARG,
+           "nnlm: B outside 0 .. PF_NNLM_MAX_BATCH or an unknown flag");
+  const NnlmModel& m = *nnlm_;
+  std::vector<int64_t> off((size_t)B + 1, 0);
+  int64_t n_ids = 0;
+  for (int b = 0; b < B; ++b) {
+    PF_CHECK(lens[b] >= 0 && lens[b] <= PF_NNLM_MAX_TOKENS, PF_ERR_INVALID_ARG, "nnlm: a hypothesis holds 0 .. PF_NNLM_MAX_TOKENS tokens");
+    nnlm_admit(m, ids + n_ids, lens[b]);
+    n_ids += lens[b];
+    off[(size_t)b + 1] = off[(size_t)b] + lens[b] + 1;
+  }
+  if (B == 0) return;
+  PF_CHECK(off[(size_t)B] <= PF_NNLM_MAX_ROWS, PF_ERR_CAPACITY, "nnlm: more than PF_NNLM_MAX_ROWS rows in one call");
+  PF_HIP(hipSetDevice(device_));
+  const size_t total = (size_t)off[(size_t)B], nB = (size_t)B, G = guarded ? 64 : 0;
+  const int D = m.d_model, NL = m.n_layers;
+  // the one upload: offsets | input ids [sos, y_1 .. y_n] | targets [y_1 .. y_n, eos]
+  std::vector<char> stage((nB + 1) * 8 + 2 * (total + G) * 4);
+  int64_t* s_off = reinterpret_cast<int64_t*>(stage.data());
+  int32_t* s_ids = reinterpret_cast<int32_t*>(stage.data() + (nB + 1) * 8);
+  int32_t* s_tgt = s_ids + total + G;
+  std::copy(off.begin(), off.end(), s_off);
+  for (size_t b = 0, at = 0; b < nB; ++b) {
+    int32_t* in = s_ids + off[b];
+    int32_t* tg = s_tgt + off[b];
+    in[0] = m.sos();
+    for (int t = 0; t < lens[b]; ++t) { in[t + 1] = ids[at + (size_t)t]; tg[t] = ids[at + (size_t)t]; }
+    tg[lens[b]] = m.sos();
+    at += (size_t)lens[b];
+  }
+  for (size_t i = 0; i < G; ++i) { s_ids[total + i] = hostile_i32(i); s_tgt[total + i] = hostile_i32(i + 1); }
+
+  Cursor c;
+  const Field<char> d_stage = c.take<char>(stage.size());
+  c.off = (size_t)round_up((int64_t)c.off, 256);
+  const Field<float> d_out = c.take<float>(nB + G + total + G);            // lm_sum [B] | guard | logp [total] | guard
+  c.off = (size_t)round_up((int64_t)c.off, 256);
+  const Field<float> d_x = c.take<float>(total * D);
+  c.off = (size_t)round_up((int64_t)c.off, 256);
+  const Field<half_t> d_qkv = c.take<half_t>(total * 3 * D), d_ctx = c.take<half_t>(total * D);
+  ensure(ws_nnlm_, c.off);
+  void* ws = ws_nnlm_.p;
+  const int64_t* p_off = reinterpret_cast<const int64_t*>(d_stage(ws));
+  const int32_t* p_ids = reinterpret_cast<const int32_t*>(d_stage(ws) + (nB + 1) * 8);
+  const int32_t* p_tgt = p_ids + total + G;
+  float* p_sum = d_out(ws);
+  float* p_logp = p_sum + nB + G;
+  PF_HIP(hipMemcpyAsync(d_stage(ws), stage.data(), stage.size(), hipMemcpyHostToDevice, stream_));
+  if (guarded) {
+    fill_sentinel(stream_, d_out(ws), d_out.count);
+    PF_HIP(hipMemsetD16Async((hipDeviceptr_t)d_x(ws), kPoison16, total * D * 2, stream_));
+    PF_HIP(hipMemsetD16Async((hipDeviceptr_t)d_qkv(ws), kPoison16, total * 3 * D, stream_));
+    PF_HIP(hipMemsetD16Async((hipDeviceptr_t)d_ctx(ws), kPoison16, total * D, stream_));
+  }
+  const double rows = (double)round_up((int64_t)total, 32);
+  const double f_qkv = 2.0 * 3 * D * D, f_layer = 2.0 * D * D + 4.0 * D * m.ffn;
+  auto tail = [&](NnlmRowsLaunch& a, int l) {       // what follows layer l - 1 (l = 0: the input layer)
+    if (l < NL) {
+      a.tail = 0; a.n_g = m.limg[(size_t)l].n1_g; a.n_b = m.limg[(size_t)l].n1_b; a.last = m.limg[(size_t)l].qkv; a.qkv_out = d_qkv(ws);
+    } else {
+      a.tail = 1; a.n_g = m.after_g_off; a.n_b = m.after_b_off; a.last = m.dec; a.tgt = p_tgt; a.V = m.vocab; a.logp = p_logp;
+    }
+  };
+  NnlmRowsLaunch a{};
+  a.img = (const char*)nnlm_dev_.buf.p; a.off = p_off; a.B = B; a.total = (int64_t)total; a.x = d_x(ws);
+  a.head = 0; a.ids = p_ids; a.embed_off = m.embed_off; a.E = m.embed_dim; a.in = m.in; a.in_g = m.in_g_off; a.in_b = m.in_b_off;
+  tail(a, 0);
+  prof_begin("nnlm", (2.0 * D * m.embed_dim + f_qkv) * rows);
+  launch_nnlm_rows(stream_, a);
+  prof_end("nnlm");
+  for (int l = 0; l < NL; ++l) {
+    const NnlmModel::LayerImg& g = m.limg[(size_t)l];
+    prof_begin("nnlm", 0);                          // (2 T^2 d_model per sequence: not counted, T varies per sequence)
+    launch_nnlm_attn(stream_, NnlmAttnLaunch{d_qkv(ws), p_off, B, d_ctx(ws)});
+    prof_end("nnlm");
+    NnlmRowsLaunch r{};
+    r.img = a.img; r.off = a.off; r.B = B; r.total = a.total; r.x = a.x;
+    r.head = 1; r.ctx = d_ctx(ws); r.out = g.out; r.n2_g = g.n2_g; r.n2_b = g.n2_b; r.w1 = g.w1; r.w2 = g.w2;
+    tail(r, l + 1);
+    prof_begin("nnlm", (f_layer + (l + 1 < NL ? f_qkv : 2.0 * m.dec.Npad * D)) * rows);
+    launch_nnlm_rows(stream_, r);
+    prof_end("nnlm");
+  }
+  prof_begin("nnlm", 0);
+  launch_nnlm_sum(stream_, NnlmSumLaunch{p_logp, p_off, B, (flags & PF_NNLM_EOS) ? 1 : 0, p_sum});
+  prof_end("nnlm");
+  std::vector<uint32_t> out(d_out.count);                           // the one copy back
+  PF_HIP(hipMemcpyAsync(out.data(), d_out(ws), out.size() * 4, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipStreamSynchronize(stream_));
+  if (guarded) {
+    const GuardGeom gs = result_geom((int64_t)(nB + G), B, 1, 1, B), gl = result_geom((int64_t)(total + G), (int)total, 1, 1, (int64_t)total);
+    if (const GuardHit hit = guard_scan<uint32_t>(out.data(), nullptr, kSentinel32, gs))
+      throw Error(PF_ERR_DEVICE, guard_message("nnlm: lm_sum", gs, hit));
+    if (const GuardHit hit = guard_scan<uint32_t>(out.data() + nB + G, nullptr, kSentinel32, gl))
+      throw Error(PF_ERR_DEVICE, guard_message("nnlm: logp", gl, hit));
+  }
+  if (lm_sum) std::memcpy(lm_sum, out.data(), nB * 4);
+  if (logp) std::memcpy(logp, out.data() + nB + G, total * 4);
+}
+
+void Engine::nnlm_score(const int32_t* ids, const int32_t* lens, int B, int flags, float* lm_sum, float* logp) {
+  run_nnlm(ids, lens, B, flags, lm_sum, logp, false);
+}
+
+void Engine::op_nnlm_logp(const int32_t* ids, const int32_t* lens, int B, int flags, float* logp, float* lm_sum) {
+  run_nnlm(ids, lens, B, flags, lm_sum, logp, true);
+}
+
 // ---- the punctuation model, streaming (k_punc_stream.hip): ONE launch for B streams
 void Engine::punc_stream_step(char* states_dev, const int32_t* slot_dev, const int32_t* ids_dev, int64_t ld, const int32_t* n_new_dev,
                               const int32_t* flush_dev, int B, int max_context, int flags, int32_t* marks_dev, int32_t* mark_flags_dev,

@@ -725,6 +725,30 @@ struct PuncStreamLaunch {
 };
 void launch_punc_stream(hipStream_t s, const PuncStreamLaunch& a, int B);
 
+// ---------------------------------------------------------------- the causal Transformer LM (k_nnlm.hip) ------
+// paraformer_hip.h "Neural LM rescoring"; the definition in numpy is tests/nnlm_ref.py; the launch plan (2 + 2 n_layers launches
+// per forward) is at the head of k_nnlm.hip and Engine::run_nnlm fills these in.  img: the model's device image (nnlm.h); every
+// *_off and TileGemm offset is a byte offset into it.  Rows: `total` input ids, sequence b at rows [off[b], off[b + 1]), 1 ..
+// 256 rows each ([sos, y_1 .. y_n]); tgt [total]: the row's target id ([y_1 .. y_n, eos]).  Nothing at or beyond `total` is
+// read from ids / tgt or stored anywhere.
+struct NnlmRowsLaunch {
+  const char* img; const int64_t* off; int B; int64_t total;
+  int head;                                                     // 0: embed -> input Linear -> LayerNorm -> ReLU -> x; 1: the layer behind its attention
+  int tail;                                                     // 0: LayerNorm (n_g, n_b) + `last` = qkv -> qkv_out; 1: + `last` = decoder -> logp
+  float* x;                                                     // the residual stream fp32 [total, 512], updated in place
+  const int32_t* ids; int64_t embed_off; int E; TileGemm in; int64_t in_g, in_b;         // head 0: embed f16 [V, E]
+  const half_t* ctx; TileGemm out; int64_t n2_g, n2_b; TileGemm w1, w2;                  // head 1
+  int64_t n_g, n_b; TileGemm last;
+  half_t* qkv_out;                                              // tail 0: f16 [total, 1536], q pre-scaled by dh^-0.5 = 1 / 8
+  const int32_t* tgt; int V; float* logp;                       // tail 1: logp [total] = log softmax(decoder)[tgt], the logits are never stored
+};
+void launch_nnlm_rows(hipStream_t s, const NnlmRowsLaunch& a);
+struct NnlmAttnLaunch { const half_t* qkv; const int64_t* off; int B; half_t* ctx; };      // ctx f16 [total, 512]
+void launch_nnlm_attn(hipStream_t s, const NnlmAttnLaunch& a);
+// lm_sum [B]: the sequential fp32 sum of a sequence's logp rows but the last, plus the last (the eos row) when eos != 0
+struct NnlmSumLaunch { const float* logp; const int64_t* off; int B; int eos; float* lm_sum; };
+void launch_nnlm_sum(hipStream_t s, const NnlmSumLaunch& a);
+
 // ---------------------------------------------------------------- the CAM++ speaker model (k_spk.hip) ------
 // The definition in numpy is tests/spk_ref.py; the launch plan (15 launches per forward) is at the head of k_spk.hip and
 // Engine::run_spk fills these in.  img: the model's device image (spk.h); every *_off and TileGemm offset is a byte offset into

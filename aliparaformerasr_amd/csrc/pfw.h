@@ -32,6 +32,7 @@ constexpr PfwPolicy kPfwWeights{PF_ERR_FORMAT, "weights: ", true, 16};
 constexpr PfwPolicy kPfwVadModel{PF_ERR_INVALID_ARG, "vad model: ", false, 1};
 constexpr PfwPolicy kPfwPuncModel{PF_ERR_INVALID_ARG, "punc model: ", true, 1};
 constexpr PfwPolicy kPfwSpkModel{PF_ERR_INVALID_ARG, "spk model: ", false, 1};
+constexpr PfwPolicy kPfwNnlmModel{PF_ERR_INVALID_ARG, "nnlm model: ", false, 1};
 
 [[noreturn]] void pfw_bad(const PfwPolicy& p, const std::string& m);      // throws Error(p.code, p.prefix + m)
 // an Error on its way out of a loader: p.code and PF_ERR_UNSUPPORTED pass as they are, anything else (a JSON error from

@@ -662,6 +662,7 @@ void Recognizer::SetVad(const pf_vad_config* cfg, int batch_max, int64_t frame_b
   if (search_w_ > 0) throw Error(PF_ERR_UNSUPPORTED, "SetVad: not available beside SetNBestSearch");
   if (kw_on_) throw Error(PF_ERR_UNSUPPORTED, "SetVad: not available beside SetKeywords");
   std::lock_guard<std::mutex> lk(vad_mu_);
+  if (nnlm_on_) throw Error(PF_ERR_UNSUPPORTED, "SetVad: not available beside SetRescoreModel");
   vad_on_ = true; vad_cfg_ = c;
   vad_batch_max_ = batch_max == 0 ? 32 : batch_max;
   vad_budget_ = frame_budget == 0 ? 96000 : frame_budget;
@@ -1530,6 +1531,94 @@ void Recognizer::Punctuate(const std::vector<Stream*>& streams, const std::vecto
   }
 }
 
+void Recognizer::SetRescoreModel(const std::string& pfw_path, double weight, double bonus, int flags) {
+  if (disposed_) throw Error(PF_ERR_DISPOSED, "OfflineRecognizer");
+  std::shared_ptr<const NnlmModel> nm;
+  if (!pfw_path.empty()) {
+    PF_CHECK((flags & ~PF_NNLM_EOS) == 0 && std::isfinite(weight) && std::isfinite(bonus), PF_ERR_INVALID_ARG,
+             "SetRescoreModel: an unknown flag, or a weight or bonus that is not finite");
+    nm = nnlm_model_load(pfw_path);                                          // throws before anything changes
+  }
+  std::vector<std::shared_ptr<Engine>> es;
+  {
+    std::lock_guard<std::mutex> lk(mu_);
+    if (disposed_ || engines_.empty()) throw Error(PF_ERR_DISPOSED, "OfflineRecognizer");
+    es = engines_;
+  }
+  if (nm) PF_CHECK(nm->vocab == es[0]->model().vocab, PF_ERR_INVALID_ARG, "SetRescoreModel: the LM's vocabulary is not the recogniser's");
+  {
+    std::lock_guard<std::mutex> vlk(vad_mu_);                                // SetVad reads nnlm_on_ under the same lock: of the pair,
+    if (nm && vad_on_)                                                       // the second to arrive is the one refused
+      throw Error(PF_ERR_UNSUPPORTED, "SetRescoreModel: not available beside SetVad (a stitched result carries no Alternatives)");
+    std::lock_guard<std::mutex> lk(nnlm_mu_);
+    nnlm_model_ = nm; nnlm_weight_ = weight; nnlm_bonus_ = bonus; nnlm_flags_ = flags;
+    nnlm_on_ = nm != nullptr;
+  }
+  if (!nm)                                                                   // (Rescore attaches it under its lease; a clear
+    for (auto& e : es) {                                                     //  frees the image and the workspace everywhere)
+      std::lock_guard<std::mutex> lk(e->mutex());
+      e->set_nnlm(nullptr);
+    }
+}
+
+// every Alternatives list of the call through the LM: ONE pf_engine_nnlm_score over all of them (in turns only beyond a batch's
+// hypotheses or rows), then per stream the fusion and the stable sort
+void Recognizer::Rescore(const std::vector<Stream*>& streams) {
+  std::shared_ptr<const NnlmModel> nm;
+  double weight, bonus;
+  int flags;
+  { std::lock_guard<std::mutex> lk(nnlm_mu_); nm = nnlm_model_; weight = nnlm_weight_; bonus = nnlm_bonus_; flags = nnlm_flags_; }
+  if (!nm) return;
+  std::vector<Stream*> todo;
+  std::vector<int32_t> ids, lens;
+  for (Stream* s : streams) {
+    bool ok = !s->Alternatives.empty();
+    for (const Alternative& a : s->Alternatives) {
+      ok = ok && a.ids.size() <= (size_t)PF_NNLM_MAX_TOKENS;
+      for (int64_t id : a.ids) ok = ok && id >= 0 && id < nm->vocab;
+    }
+    if (!ok) continue;
+    todo.push_back(s);
+    for (const Alternative& a : s->Alternatives) {
+      for (int64_t id : a.ids) ids.push_back((int32_t)id);
+      lens.push_back((int32_t)a.ids.size());
+    }
+  }
+  if (lens.empty()) return;
+  std::vector<float> lm(lens.size());
+  for (size_t at = 0, first = 0; at < lens.size();) {
+    size_t n = 0, rows = 0, toks = 0;
+    while (at + n < lens.size() && n < (size_t)PF_NNLM_MAX_BATCH && rows + (size_t)lens[at + n] + 1 <= (size_t)PF_NNLM_MAX_ROWS) {
+      rows += (size_t)lens[at + n] + 1; toks += (size_t)lens[at + n]; ++n;
+    }
+    Lease lease = acquire();
+    if (lease->nnlm_model() != nm) lease->set_nnlm(nm);
+    lease->nnlm_score(ids.data() + first, lens.data() + at, (int)n, flags, lm.data() + at, nullptr);
+    at += n; first += toks;
+  }
+  size_t at = 0;
+  for (Stream* s : todo) {
+    const size_t N = s->Alternatives.size();
+    std::vector<double> base(N), sum(N), score(N);
+    std::vector<int32_t> n(N), order(N);
+    for (size_t i = 0; i < N; ++i) {
+      const Alternative& a = s->Alternatives[i];
+      base[i] = a.loglik_sum == a.loglik_sum ? a.loglik_sum : a.score;
+      sum[i] = (double)lm[at + i];
+      n[i] = (int32_t)a.ids.size();
+    }
+    host_nnlm_fuse(base.data(), sum.data(), n.data(), (int)N, weight, bonus, score.data(), order.data());
+    std::vector<Alternative> sorted(N);
+    for (size_t i = 0; i < N; ++i) {
+      sorted[i] = std::move(s->Alternatives[(size_t)order[i]]);
+      sorted[i].nnlm_sum = sum[(size_t)order[i]];
+      sorted[i].score = score[(size_t)order[i]];
+    }
+    s->Alternatives = std::move(sorted);
+    at += N;
+  }
+}
+
 void Recognizer::GetResults(const std::vector<Stream*>& streams) {
   bool vad;
   { std::lock_guard<std::mutex> lk(vad_mu_); vad = vad_on_; }
@@ -1541,6 +1630,16 @@ void Recognizer::GetResults(const std::vector<Stream*>& streams) {
     if (vad) break;
     s->Segments.clear();
     out.push_back(decode_multi_one(token_table_, s->Tokens, s->Timestamps));
+  }
+  // rescoring comes before the list's texts (its order is final from here).  An error in this opt-in step must not take the
+  // recognition results away: the streams keep the search's lists, the results are stored, and the error is thrown last
+  std::exception_ptr rescore_error;
+  if (nnlm_on_) {
+    try {
+      Rescore(streams);
+    } catch (...) {
+      rescore_error = std::current_exception();
+    }
   }
   for (Stream* s : streams)                                   // the n-best list goes through the same DecodeMulti
     for (Alternative& a : s->Alternatives) {                  // (a beam hypothesis has no per-token times without SetAlign:
@@ -1566,6 +1665,7 @@ void Recognizer::GetResults(const std::vector<Stream*>& streams) {
     for (Stream* s : streams) { s->Punctuated.clear(); s->PuncIds.clear(); s->Sentences.clear(); }
     throw;
   }
+  if (rescore_error) std::rethrow_exception(rescore_error);
 }
 
 const std::vector<ResultEntity>& Recognizer::results_of_this_thread() {

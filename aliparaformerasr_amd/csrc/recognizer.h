@@ -177,6 +177,14 @@ class Recognizer : public std::enable_shared_from_this<Recognizer> {
   // once; "" clears.  GetResults then punctuates each stream's final Text (with SetVad: the stitched text), all streams of the
   // call in one pf_engine_punctuate on a leased engine, and keeps the result on the stream; Text / Tokens / Timestamps stay.
   void SetPuncModel(const std::string& pfw_path);
+  // Second-pass rescoring of every Alternatives list that follows (paraformer_hip.h "Neural LM rescoring"): a `.pfw` of kind
+  // "transformerlm" whose vocabulary is the recogniser's (PF_ERR_INVALID_ARG otherwise), loaded once; "" clears.  After a
+  // GetResults whose plan produced Alternatives, ONE pf_engine_nnlm_score over all alternatives of all streams of the call on
+  // a leased engine, then per stream score' = base + weight * nnlm_sum + bonus * n (base: loglik_sum where the list has one,
+  // else score) and a stable sort by score' descending.  Text / Tokens / Timestamps / Scores stay; a stream with an
+  // alternative above PF_NNLM_MAX_TOKENS ids keeps its list as it is (nnlm_sum NaN).  Refused beside SetVad (whichever is
+  // set second): a stitched long-audio result carries no Alternatives.
+  void SetRescoreModel(const std::string& pfw_path, double weight, double bonus, int flags);
   // Speaker labels of every long-audio GetResults that follows (paraformer_hip.h "Speaker labels"): a `.pfw` of kind "campplus",
   // loaded once and attached to every engine of the pool, present and future; "" clears.  Inert until SetVad, and may be set
   // before or after it.  Behind the segmentation, on the fbank rows it staged, under the same lease: the windows of all of the
@@ -254,7 +262,12 @@ class Recognizer : public std::enable_shared_from_this<Recognizer> {
   std::atomic<bool> spk_cluster_dev_{false};
   std::mutex punc_mu_;                                        // guards punc_model_
   std::shared_ptr<const PuncModel> punc_model_;
-  std::mutex vad_mu_;                                         // guards the five below
+  void Rescore(const std::vector<Stream*>& streams);
+  std::mutex nnlm_mu_;                                        // guards the four below
+  std::shared_ptr<const NnlmModel> nnlm_model_;
+  double nnlm_weight_ = 0.5, nnlm_bonus_ = 0.0; int nnlm_flags_ = 0;
+  std::atomic<bool> nnlm_on_{false};
+  std::mutex vad_mu_;                                        // guards the five below
   std::shared_ptr<const VadModel> vad_model_;
   bool vad_on_ = false; pf_vad_config vad_cfg_{}; int vad_batch_max_ = 32; int64_t vad_budget_ = 96000; std::string vad_sep_;
   std::shared_ptr<Engine> make_engine();

@@ -67,6 +67,9 @@ struct Alternative {
   // with SetLm beside SetCtcBeam: the weighted LM score of the labeling, score = (loglik_sum + boost * hot_tokens) + lm_sum (NaN
   // without it; loglik_sum is then filled with or without hot words)
   double lm_sum = std::nan("");
+  // with SetRescoreModel: the Transformer LM's sum of log-probabilities of the ids (NaN without it); score is then
+  // base + weight * nnlm_sum + bonus * ids.size(), base = loglik_sum where that is filled, else the search's score
+  double nnlm_sum = std::nan("");
   ResultEntity res;
 };
 // time_stamp_lfr6_onnx (OfflineRecognizer.cs:200-302); throws PF_ERR_RECOGNITION where the C#

@@ -91,6 +91,34 @@ __device__ __forceinline__ void tr_product(const char* __restrict__ img, const T
   }
 }
 
+// ---- the one-half form (k_nnlm.hip): a tile of 32 rows, so a weight fragment meets one activation fragment.  The lane layout,
+// the k order and the padding rule are those above with i = 0; a wave still takes the blocks nt = wave, wave + 4, ...
+__device__ __forceinline__ void tr_mma1(const h8* wp, int nks, const half_t* x0, f16x& c0) {
+  h8 wn = wp[0];
+  for (int ks = 0; ks < nks; ++ks) {
+    const h8 wf = wn;
+    if (ks + 1 < nks) wn = wp[(size_t)(ks + 1) * 64];
+    const h8 b0 = *reinterpret_cast<const h8a*>(x0 + 16 * ks);
+    c0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf, b0, c0, 0, 0, 0);
+  }
+}
+
+// X [32, g.Kpad] (LDS, row stride ld halves) times W^T over the whole K: epi(nt, acc) per 32-row block nt of W
+template <class Epi>
+__device__ __forceinline__ void tr_product1(const char* __restrict__ img, const TileGemm& g, const half_t* __restrict__ x, int ld, int wave,
+                                            int lane, Epi&& epi) {
+  const int r = lane & 31, h = lane >> 5, KS = g.Kpad >> 4;
+  const h8* __restrict__ wt = reinterpret_cast<const h8*>(img + g.w_off);
+  const float* __restrict__ bias = reinterpret_cast<const float*>(img + g.b_off);
+  const half_t* x0 = x + r * ld + 8 * h;
+  for (int nt = wave; nt < (g.Npad >> 5); nt += 4) {
+    f16x acc;
+    tr_bias(bias, nt, h, acc);
+    tr_mma1(wt + ((size_t)nt * KS) * 64 + lane, KS, x0, acc);
+    epi(nt, acc);
+  }
+}
+
 // one accumulator (tile half i) into the f16 tile y at the columns of block nb, optional ReLU: x < 0 ? 0 : x, which keeps a NaN
 __device__ __forceinline__ void tr_put_f16(const f16x& acc, bool relu, half_t* y, int ld, int i, int nb, int r, int h) {
 #pragma unroll

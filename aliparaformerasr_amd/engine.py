@@ -698,6 +698,66 @@ def load_punc_model(source) -> PuncModel:
     return PuncModel(h)
 
 
+NNLM_MODEL_DIMS = ("vocab", "embed", "d_model", "heads", "ffn", "n_layers", "sos")
+NNLM_MAX_TOKENS = 255
+NNLM_EOS = 1
+
+
+class NnlmModel:
+    """A causal Transformer LM for n-best rescoring: a `.pfw` of kind "transformerlm" loaded and validated on the host
+    (pf_nnlm_model_load / pf_nnlm_model_from_memory; see "Neural LM rescoring" in the header).  Release with close() (an engine
+    that attached it keeps its own reference)."""
+
+    def __init__(self, handle):
+        self._lib = N.load()
+        self._h = handle
+        d, ib = np.zeros(8, np.int32), C.c_int64()
+        N.check(self._lib.pf_nnlm_model_info(self._h, _i32p(d), ib))
+        self.dims = dict(zip(NNLM_MODEL_DIMS, d.tolist()))
+        self.image_bytes = ib.value
+
+    def close(self):
+        if self._h is not None:
+            self._lib.pf_nnlm_model_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def load_nnlm_model(source) -> NnlmModel:
+    """A `.pfw` of kind "transformerlm" from a path or from bytes -> NnlmModel."""
+    h = C.c_void_p()
+    if isinstance(source, (bytes, bytearray, memoryview)):
+        buf = bytes(source)
+        N.check(N.load().pf_nnlm_model_from_memory(C.cast(C.c_char_p(buf), C.c_void_p), len(buf), C.byref(h)))
+    else:
+        N.check(N.load().pf_nnlm_model_load(str(source).encode("utf-8"), C.byref(h)))
+    return NnlmModel(h)
+
+
+def host_nnlm_logp(model: NnlmModel, ids) -> np.ndarray:
+    """The network on ONE hypothesis in host code, float64 (pf_host_nnlm_logp): ids [n] -> logp [n + 1]."""
+    a = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+    out = np.zeros(a.size + 1, np.float64)
+    N.check(N.load().pf_host_nnlm_logp(model._h, _i32p(a), a.size, _dp(out)))
+    return out
+
+
+def host_nnlm_fuse(base, lm_sum, n_tokens, weight=0.5, bonus=0.0):
+    """score' = base + weight * lm_sum + bonus * n in float64 and the stable order by score' descending (pf_host_nnlm_fuse):
+    (score float64 [N], order int32 [N])."""
+    b, l = (np.ascontiguousarray(x, dtype=np.float64).reshape(-1) for x in (base, lm_sum))
+    n = np.ascontiguousarray(n_tokens, dtype=np.int32).reshape(-1)
+    assert b.size == l.size == n.size
+    score, order = np.zeros(max(b.size, 1), np.float64), np.zeros(max(b.size, 1), np.int32)
+    N.check(N.load().pf_host_nnlm_fuse(_dp(b), _dp(l), _i32p(n), b.size, float(weight), float(bonus), _dp(score), _i32p(order)))
+    return score[: b.size].copy(), order[: b.size].copy()
+
+
 PUNC_STREAM_MAX_CONTEXT = 256
 PUNC_STREAM_DEFAULT_CONTEXT = 200
 PUNC_STREAM_NO_RESTARTS = 1
@@ -1607,6 +1667,25 @@ class Engine:
         return [(labels[woff[s]: woff[s + 1]].copy(), int(k[s]),
                  merges[moff[s]: moff[s + 1]].copy() if want_trace else None,
                  heights[moff[s]: moff[s + 1]].copy() if want_trace else None) for s in range(S)]
+
+    def set_nnlm(self, model):
+        """Attaches an NnlmModel (pf_engine_set_nnlm); None detaches and frees what the attach and its runs allocated."""
+        N.check(self._lib.pf_engine_set_nnlm(self._h, None if model is None else model._h))
+
+    def nnlm_score(self, hyps, eos=False, want_logp=True, op=False, out=None):
+        """Scores the hypotheses of `hyps` (token id lists) under the attached LM in ONE call: (lm_sum float32 [B], each
+        hypothesis's logp float32 [n + 1] or None).  op: through pf_op_nnlm_logp (hostile staging, guarded outputs) instead of
+        pf_engine_nnlm_score.  out: a float32 buffer of at least sum (n + 1) values for logp (tests look at what lies beyond)."""
+        arrs, n, ids, _ = self._punc_batch(hyps)
+        off = np.concatenate([[0], np.cumsum(n[: len(arrs)] + 1)]).astype(np.int64)
+        lm = np.zeros(max(len(arrs), 1), np.float32)
+        lp = (np.zeros(max(int(off[-1]), 1), np.float32) if out is None else out) if want_logp else None
+        flags = NNLM_EOS if eos else 0
+        if op:
+            N.check(self._lib.pf_op_nnlm_logp(self._h, _i32p(ids), _i32p(n), len(arrs), flags, None if lp is None else _fp(lp), _fp(lm)))
+        else:
+            N.check(self._lib.pf_engine_nnlm_score(self._h, _i32p(ids), _i32p(n), len(arrs), flags, _fp(lm), None if lp is None else _fp(lp)))
+        return lm[: len(arrs)].copy(), ([lp[off[b]: off[b + 1]].copy() for b in range(len(arrs))] if want_logp else None)
 
     def set_punc_model(self, model):
         """Attaches a PuncModel (pf_engine_set_punc_model); None detaches and frees what the attach and its runs allocated."""

@@ -1,7 +1,7 @@
 """Command-line harness mirroring AliParaformerAsr.Examples (`-type offline` and `-type online`).
 
     python -m aliparaformerasr_amd.examples -type offline -method batch -base <dir> -model <name> \
-        [-accuracy int8] [-threads 2] [-decode ctc|frames] [-intake host|device] [-resample linear|sinc] [-nbest N [-topk K] [-beam W | -search W] [-hotboost S] [-lm FILE [-lmweight A] [-lmbonus B] [-lmeos]]] [-align FILE|beam] [-spot FILE [-spotthreshold P] [-spothits N]] [-vad [key=value,...] [-vadmodel FILE] [-spk FILE[,cluster=device] [key=value,...]]] [-punc FILE] -files a.wav b.wav
+        [-accuracy int8] [-threads 2] [-decode ctc|frames] [-intake host|device] [-resample linear|sinc] [-nbest N [-topk K] [-beam W | -search W] [-hotboost S] [-lm FILE [-lmweight A] [-lmbonus B] [-lmeos]] [-rescore FILE [-rescoreweight A] [-rescorebonus B] [-rescoreeos]]] [-align FILE|beam] [-spot FILE [-spotthreshold P] [-spothits N]] [-vad [key=value,...] [-vadmodel FILE] [-spk FILE[,cluster=device] [key=value,...]]] [-punc FILE] -files a.wav b.wav
     python -m aliparaformerasr_amd.examples -type online -method one -base <dir> -model <name> [-endpoint [key=value,...] [-vadmodel FILE] [-secondpass <offline name>]] [-tokentimes [-devicefrontend]] [-puncstream FILE[,max_context=N]] [-intake host|device] [-resample linear|sinc] -files a.wav
 
 Mirrors (file:line in /root/reference/AliParaformerAsr.Examples):
@@ -40,6 +40,10 @@ beam search of width W in the same form; the score is the log of the summed alig
 of width W over the per-token alternatives on the device instead of the exact enumeration; `-hotboost`, `-lm`, `-lmweight`,
 `-lmbonus` and `-lmeos` then go to that search (SetNBestHotwordBoost, SetNBestLm) and decide which prefixes survive a position;
 each `nbest[i]` line ends in ` hot:<matched tokens> lm:<lm_sum> loglik_sum:<sum of log-probs>`.
+`-rescore FILE [-rescoreweight A] [-rescorebonus B] [-rescoreeos]` (with `-nbest`; OfflineRecognizer.SetRescoreModel) re-scores
+the n-best list with a causal Transformer LM on the GPU: FILE is a `.pfw` of kind transformerlm on the recogniser's vocabulary;
+score becomes base + A * nnlm_sum + B * tokens and the list is re-ordered by it; each `nbest[i]` line then ends in
+` nnlm:<nnlm_sum>`.  The default weight 0.5 is a stated default: nobody has tuned it on real speech.
 `-lm FILE [-lmweight A] [-lmbonus B] [-lmeos]` (with `-nbest N -beam W`; OfflineRecognizer.SetLm) fuses the ARPA n-gram language
 model FILE into that search with weight A (default 0.5), per-token bonus B (default 0) and, with `-lmeos`, the end-of-sentence
 step; each `nbest[i]` line then ends in ` hot:<matched tokens> lm:<lm_sum> loglik_sum:<unfused score>`.
@@ -197,6 +201,8 @@ def _nbest_lines(stream, align=False) -> list:
             hot = ' hot:%d lm:%.6f loglik_sum:%.6f' % (a.HotwordTokens, a.LmSum, a.LogLikSum)
         else:
             hot = '' if a.LogLikSum is None else ' hot:%d loglik_sum:%.6f' % (a.HotwordTokens, a.LogLikSum)
+        if a.NnlmSum is not None:
+            hot += ' nnlm:%.6f' % a.NnlmSum
         out.append('nbest[%d] score:%.6f text:%s%s' % (i, a.Score, a.Text, hot))
         if align and a.LogLik is not None:
             out.append('align[%d] loglik:%.6f pairs:%s' % (i, a.LogLik, _pairs(a.Timestamps)))
@@ -343,7 +349,7 @@ def _punc_lines(st):
 def offline_recognizer(method="one", model="paraformer-seaco-large-zh-timestamp-onnx-offline", accuracy="int8",
                        threads=2, files=None, base=None, out=sys.stdout, decode="frames", intake="host", nbest=0, topk=4,
                        beam=0, align=None, hotboost=0.0, vad=None, lm=None, lmweight=0.5, lmbonus=0.0, lmeos=False, search=0, vadmodel=None, punc=None, spk=None,
-                       resample="linear", spot=None, spotthreshold=0.5, spothits=8):
+                       resample="linear", spot=None, spotthreshold=0.5, spothits=8, rescore=None, rescoreweight=0.5, rescorebonus=0.0, rescoreeos=False):
     from .offline_recognizer import OfflineRecognizer
     base = base or os.getcwd()
     sel = select_model_files(base, model, accuracy)
@@ -368,6 +374,8 @@ def offline_recognizer(method="one", model="paraformer-seaco-large-zh-timestamp-
                 rec.SetNBestHotwordBoost(hotboost)
             if lm:
                 rec.SetNBestLm(lm, lmweight, lmbonus, 1 if lmeos else 0)
+    if rescore:
+        rec.SetRescoreModel(rescore, rescoreweight, rescorebonus, rescoreeos)
     if vad is not None:
         vcfg = vad["cfg"] or True
         if vadmodel:                                       # the model's default thresholds unless keys are given
@@ -785,6 +793,19 @@ def parse_args(argv, env=None):
             if i >= len(argv) or argv[i].startswith("-"):
                 raise ValueError("-puncstream takes a causal .pfw file of kind cttransformer[,max_context=N]")
             cfg["puncstream"] = parse_puncstream_option(argv[i])
+        elif a == "-rescore":
+            i += 1
+            if i >= len(argv) or argv[i].startswith("-"):
+                raise ValueError("-rescore takes a .pfw file of kind transformerlm")
+            cfg["rescore"] = argv[i]
+        elif a in ("-rescoreweight", "-rescorebonus"):
+            try:
+                i += 1
+                cfg[a[1:]] = float(argv[i])
+            except (IndexError, ValueError):
+                raise ValueError("%s takes a number" % a)
+        elif a == "-rescoreeos":
+            cfg["rescoreeos"] = True
         elif a == "-punc":
             i += 1
             if i >= len(argv) or argv[i].startswith("-"):
@@ -841,6 +862,10 @@ def parse_args(argv, env=None):
         raise ValueError("-endpoint is an online option")
     if "secondpass" in cfg and "endpoint" not in cfg:
         raise ValueError("-secondpass goes with -endpoint")
+    if "rescore" in cfg and "nbest" not in cfg:
+        raise ValueError("-rescore goes with -nbest")
+    if any(k in cfg for k in ("rescoreweight", "rescorebonus", "rescoreeos")) and "rescore" not in cfg:
+        raise ValueError("-rescoreweight, -rescorebonus and -rescoreeos go with -rescore")
     if "punc" in cfg and cfg["recognizerType"] != "offline":
         raise ValueError("-punc is an offline option")
     if "spk" in cfg and "vad" not in cfg:
@@ -882,7 +907,8 @@ def main(argv=None):
                            lmbonus=cfg.get("lmbonus", 0.0), lmeos=cfg.get("lmeos", False), search=cfg.get("search", 0),
                            vadmodel=cfg.get("vadmodel"), punc=cfg.get("punc"), spk=cfg.get("spk"),
                            resample=cfg.get("resample", "linear"), spot=cfg.get("spot"), spotthreshold=cfg.get("spotthreshold", 0.5),
-                           spothits=cfg.get("spothits", 8))
+                           spothits=cfg.get("spothits", 8), rescore=cfg.get("rescore"), rescoreweight=cfg.get("rescoreweight", 0.5),
+                           rescorebonus=cfg.get("rescorebonus", 0.0), rescoreeos=cfg.get("rescoreeos", False))
     else:
         print("the recognizer type must be online or offline")
         return 2

@@ -84,6 +84,9 @@ class Alternative:
     # OfflineRecognizer.SetLm beside SetCtcBeam: the weighted language-model score of the labeling, Score = (LogLikSum + boost *
     # HotwordTokens) + LmSum (None when the search ran without a model; LogLikSum is then filled with or without hot words)
     LmSum: Optional[float] = None
+    # with OfflineRecognizer.SetRescoreModel: the Transformer LM's sum of log-probabilities of Ids (None without a model); Score is
+    # then base + weight * NnlmSum + bonus * len(Ids), base = LogLikSum where the list has one, else the search's score
+    NnlmSum: Optional[float] = None
 
 
 @dataclass
@@ -267,11 +270,13 @@ class OfflineStream:
             _ck(self._lib.pf_stream_alternative_timestamps(self._h, i, C.byref(pt), nts, C.byref(ll)))
             hm, hs = C.c_int32(), C.c_double()
             _ck(self._lib.pf_stream_alternative_hot(self._h, i, hm, hs))
-            lm = C.c_double()
+            lm, nn = C.c_double(), C.c_double()
             _ck(self._lib.pf_stream_alternative_lm(self._h, i, lm, None))
+            _ck(self._lib.pf_stream_alternative_nnlm(self._h, i, nn))
             out.append(Alternative(Ids=[p[m] for m in range(k.value)], Score=sc.value, HotwordTokens=hm.value,
                                    LogLikSum=None if hs.value != hs.value else hs.value,
                                    LmSum=None if lm.value != lm.value else lm.value,
+                                   NnlmSum=None if nn.value != nn.value else nn.value,
                                    Text=(txt.value or b"").decode("utf-8"), Tokens=toks,
                                    Timestamps=[[pt[2 * j], pt[2 * j + 1]] for j in range(nts.value)],
                                    LogLik=None if ll.value != ll.value else ll.value))
@@ -600,6 +605,17 @@ class OfflineRecognizer:
         all streams of a call in one batch: stream.Punctuated, .PuncIds, .Sentences.  Text, Tokens and Timestamps of the result
         stay what they are.  No real model file has been through this path: the rules and dimensions are stated, not validated."""
         _ck(self._lib.pf_recognizer_set_punc_model(self._h, None if pfwPath is None else str(pfwPath).encode("utf-8")))
+
+    def SetRescoreModel(self, pfwPath, weight: float = 0.5, bonus: float = 0.0, eos: bool = False) -> None:
+        """Second-pass rescoring of every Alternatives list that follows with a causal Transformer LM on the device: a `.pfw` of
+        kind "transformerlm" (python -m aliparaformerasr_amd.convert lm.pt out.pfw --kind transformerlm) on the recogniser's own
+        vocabulary; None clears.  After a GetResults that produced Alternatives (SetNBest with N > 1, SetNBestSearch, SetCtcBeam)
+        all alternatives of all streams are scored in one call; each gets NnlmSum and Score = base + weight * NnlmSum + bonus *
+        len(Ids) (base: LogLikSum where the list has one, else the search's score; eos: the end-of-sentence row counts too), and
+        the list is stable-sorted by Score.  Text, Tokens, Timestamps and Scores stay.  Not available beside SetVad.  weight 0.5
+        is a stated default: nobody has tuned it on real speech, and no real model file has been through this path."""
+        path = None if pfwPath is None else str(pfwPath).encode("utf-8")
+        _ck(self._lib.pf_recognizer_set_nnlm(self._h, path, float(weight), float(bonus), 1 if eos else 0))
 
     def SetSpeakerModel(self, pfwPath, cfg=None) -> None:
         """Speaker labels for every long-audio GetResults that follows: a `.pfw` of kind "campplus" (python -m

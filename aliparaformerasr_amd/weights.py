@@ -339,6 +339,56 @@ def synth_punc_weights(cfg: dict, seed: int = 42, decoder_scale: float = 1.0) ->
     return w
 
 
+TRANSFORMER_LM_CONFIG = dict(kind="transformerlm", vocab=8404, embed=128, d_model=512, heads=8, ffn=2048, n_layers=16)
+
+
+def transformer_lm_config(**kw) -> dict:
+    """The config of a `.pfw` of kind "transformerlm" (the LM that rescores n-best lists; the definition is tests/nnlm_ref.py).
+    The defaults are the dimensions of FunASR's speech_transformer_lm_zh-cn-common-vocab8404-pytorch as remembered, not read from
+    a file.  sos = eos = vocab - 1."""
+    cfg = dict(TRANSFORMER_LM_CONFIG)
+    for k, v in kw.items():
+        if k not in cfg:
+            raise KeyError(k)
+        cfg[k] = v
+    return cfg
+
+
+def nnlm_tensor_shapes(cfg: dict) -> dict:
+    """name -> shape of every tensor of a "transformerlm" container."""
+    V, E, D, F = (int(cfg[k]) for k in ("vocab", "embed", "d_model", "ffn"))
+    sh = {"embed.weight": (V, E), "input.linear.weight": (D, E), "input.linear.bias": (D,), "input.norm.weight": (D,),
+          "input.norm.bias": (D,)}
+    for l in range(int(cfg["n_layers"])):
+        p = "layers.%d." % l
+        sh.update({p + "norm1.weight": (D,), p + "norm1.bias": (D,), p + "attn.qkv.weight": (3 * D, D), p + "attn.qkv.bias": (3 * D,),
+                   p + "attn.out.weight": (D, D), p + "attn.out.bias": (D,), p + "norm2.weight": (D,), p + "norm2.bias": (D,),
+                   p + "ffn.w1.weight": (F, D), p + "ffn.w1.bias": (F,), p + "ffn.w2.weight": (D, F), p + "ffn.w2.bias": (D,)})
+    sh.update({"after_norm.weight": (D,), "after_norm.bias": (D,), "decoder.weight": (V, D), "decoder.bias": (V,)})
+    return sh
+
+
+def synth_nnlm_weights(cfg: dict, seed: int = 42, decoder_scale: float = 1.0) -> dict:
+    """Seeded synthetic Transformer LM weights: the embedding N(0, 1), the layers as synth_weights draws them, the decoder
+    N(0, decoder_scale / sqrt(d_model)).  decoder_scale scales the logits and their f16 error alike, and with the error the
+    band inside which two fused scores may change places, while the acoustic scores of tests/nnlm_ref.py's lists do not scale
+    with it: at the default 1 that band holds at most 5 % of the adjacent pairs of those lists (tests/test_nnlm_cpu.py)."""
+    rng = np.random.default_rng(seed)
+    V, E, D = (int(cfg[k]) for k in ("vocab", "embed", "d_model"))
+    w = {"embed.weight": rng.standard_normal((V, E), dtype=np.float32)}
+    w.update(_linear(rng, D, E, prefix="input.linear"))
+    w.update(_ln(rng, D, "input.norm"))
+    for l in range(int(cfg["n_layers"])):
+        layer = _enc_layer(rng, dict(cfg, kernel=1), "layers.%d" % l, D)
+        layer.pop("layers.%d.attn.fsmn.weight" % l)
+        w.update(layer)
+    w.update(_ln(rng, D, "after_norm"))
+    dec = _linear(rng, V, D, prefix="decoder")
+    dec["decoder.weight"] = (dec["decoder.weight"] * np.float32(decoder_scale)).astype(np.float32)
+    w.update(dec)
+    return w
+
+
 CAMPPLUS_CONFIG = dict(
     kind="campplus", n_mels=80, m_channels=32, init_channels=128, growth=32, bn_channels=128, blocks=(12, 24, 16),
     dilations=(1, 2, 2), seg_len=100, embedding=192,

@@ -190,6 +190,8 @@ namespace AliParaformerAsr.Hip
                     a.LogLikSum = llSum;
                     ParaformerHip.Check(ParaformerHip.pf_stream_alternative_lm(Handle, i, out double lmSum, out double _));
                     a.LmSum = lmSum;
+                    ParaformerHip.Check(ParaformerHip.pf_stream_alternative_nnlm(Handle, i, out double nnlmSum));
+                    a.NnlmSum = nnlmSum;
                     r.Add(a);
                 }
                 return r;
@@ -400,6 +402,9 @@ namespace AliParaformerAsr.Hip
         /// <summary>SetLm beside SetCtcBeam: the weighted language-model score of the labeling, Score = (LogLikSum + boost *
         /// HotwordTokens) + LmSum (NaN when the search ran without a model; LogLikSum is then filled with or without hot words).</summary>
         public double LmSum = double.NaN;
+        /// <summary>SetRescoreModel: the Transformer LM's sum of log-probabilities of Ids (NaN without a model); Score is then
+        /// base + weight * NnlmSum + bonus * Ids.Length, base = LogLikSum where the list has one, else the search's score.</summary>
+        public double NnlmSum = double.NaN;
     }
 
     /// <summary>OfflineStream.Alignment: where each id of a known text lies in the audio.  Ok = false: the target does not fit the
@@ -470,6 +475,12 @@ namespace AliParaformerAsr.Hip
         /// Alternatives then come in the fused order, each with Score, LogLikSum, LmSum and HotwordTokens; Text, Tokens, Timestamps,
         /// Scores and TokenAlternatives stay as they are.  Not available beside SetVad.</summary>
         public void SetNBestSearch(int W) => ParaformerHip.Check(ParaformerHip.pf_recognizer_set_nbest_search(_r, W));
+        /// <summary>Not in the reference: second-pass rescoring of every Alternatives list that follows with a causal Transformer LM
+        /// on the device (a .pfw of kind "transformerlm" on the recogniser's own vocabulary; null clears).  Each alternative gets
+        /// NnlmSum and Score = base + weight * NnlmSum + bonus * Ids.Length; the list is stable-sorted by Score.  Text, Tokens,
+        /// Timestamps and Scores stay.  Not available beside SetVad.  weight 0.5 is a stated default, not tuned on real speech.</summary>
+        public void SetRescoreModel(string? pfwPath, double weight = 0.5, double bonus = 0.0, bool eos = false) =>
+            ParaformerHip.Check(ParaformerHip.pf_recognizer_set_nnlm(_r, pfwPath, weight, bonus, eos ? 1 : 0));
 
         /// <summary>Not in the reference: paraformer models only.  An ARPA n-gram language model fused into the search of
         /// SetNBestSearch (inert without it; null or "" clears it) with weight alpha, per-token bonus beta and flags.  A paraformer

@@ -325,6 +325,21 @@ namespace AliParaformerAsr.Native
         [DllImport(Lib)] internal static extern void pf_punc_model_free(IntPtr m);
         [DllImport(Lib)] internal static extern int pf_engine_set_punc_model(IntPtr e, IntPtr m);
         [DllImport(Lib)] internal static extern int pf_engine_punctuate(IntPtr e, int[] ids, int[] lens, int B, [Out] int[] puncIds, out int rounds);
+        // neural LM rescoring (a .pfw of kind "transformerlm"): the loader, what it read, the attach call, the scores of B hypotheses
+        [DllImport(Lib)] internal static extern int pf_nnlm_model_load([MarshalAs(UnmanagedType.LPUTF8Str)] string path, out IntPtr m);
+        [DllImport(Lib)] internal static extern int pf_nnlm_model_from_memory(byte[] data, long nbytes, out IntPtr m);
+        [DllImport(Lib)] internal static extern int pf_nnlm_model_info(IntPtr m, [Out] int[]? dims, out long imageBytes);
+        [DllImport(Lib)] internal static extern void pf_nnlm_model_free(IntPtr m);
+        [DllImport(Lib)] internal static extern int pf_engine_set_nnlm(IntPtr e, IntPtr m);
+        [DllImport(Lib)] internal static extern int pf_recognizer_set_nnlm(IntPtr r, [MarshalAs(UnmanagedType.LPUTF8Str)] string? pfwPath, double weight,
+                                                                           double bonus, int flags);
+        [DllImport(Lib)] internal static extern int pf_stream_alternative_nnlm(IntPtr s, int i, out double nnlmSum);
+        [DllImport(Lib)] internal static extern int pf_op_nnlm_logp(IntPtr e, int[] ids, int[] lens, int B, int flags, [Out] float[]? logp, [Out] float[]? lmSum);
+        [DllImport(Lib)] internal static extern int pf_host_nnlm_logp(IntPtr m, int[] ids, int n, [Out] double[] logp);
+        [DllImport(Lib)] internal static extern int pf_host_nnlm_fuse(double[] @base, double[] lmSum, int[] nTokens, int N, double weight, double bonus,
+                                                                      [Out] double[] score, [Out] int[] order);
+        [DllImport(Lib)] internal static extern int pf_engine_nnlm_score(IntPtr e, int[] ids, int[] lens, int B, int flags, [Out] float[]? lmSum,
+                                                                         [Out] float[]? logp);
         // speaker labels (a .pfw of kind "campplus"): the loader, what it read, the defaults, the attach calls, a stream's result
         [DllImport(Lib)] internal static extern int pf_spk_model_load([MarshalAs(UnmanagedType.LPUTF8Str)] string path, out IntPtr m);
         [DllImport(Lib)] internal static extern int pf_spk_model_from_memory(byte[] data, long nbytes, out IntPtr m);

@@ -1035,6 +1035,46 @@ int pf_host_spk_segment_labels(const int32_t* seg, int32_t n_seg, const int32_t*
                                int32_t* out);
 int pf_host_spk_centroids(const float* emb, const int32_t* labels, int32_t N, int32_t E, int32_t K, float* out);
 
+/* Neural LM rescoring (the definition in numpy float64 is tests/nnlm_ref.py): a causal Transformer LM scores
+   the hypotheses of an n-best list, and the scores are fused into the list on the host.  Opt-in: with no model attached nothing
+   is launched, allocated or changed.
+   THE MODEL is a `.pfw` of kind "transformerlm" (weights.py transformer_lm_config; convert.py --kind transformerlm): an
+   embedding [V, E], Linear(E -> D) + LayerNorm + ReLU (no positional encoding), n_layers pre-norm blocks (x += out(attn(norm1
+   x)); x += w2(relu(w1(norm2 x))); strictly causal attention, scale dh^-0.5), after_norm, decoder Linear(D -> V), log-softmax;
+   sos = eos = V - 1.  This is ESPnet's TransformerLM as remembered; no released file was at hand (DESIGN says so).
+   Supported: D = 512 with 8 heads, E a multiple of 16 up to 512, ffn a multiple of 256 up to 4096, 1 .. 24 layers,
+   2 <= V <= 2^20 (PF_ERR_UNSUPPORTED otherwise; PF_ERR_INVALID_ARG for a malformed container).
+   A HYPOTHESIS y_1 .. y_n, 0 <= n <= PF_NNLM_MAX_TOKENS, is n + 1 rows: inputs [sos, y_1 .. y_n], targets [y_1 .. y_n, eos],
+   logp[t] = log P(target_t | input_0 .. t).  lm_sum is the sequential float32 sum of logp[0 .. n - 1], plus logp[n] iff
+   PF_NNLM_EOS is set in flags.  An id outside [0, V) refuses the call.
+   pf_nnlm_model_info: dims [8] = {vocab, embed, d_model, heads, ffn, n_layers, sos, 0}. */
+#define PF_NNLM_MAX_TOKENS 255
+#define PF_NNLM_MAX_BATCH 4096
+#define PF_NNLM_MAX_ROWS 262144
+#define PF_NNLM_EOS 1
+typedef struct pf_nnlm_model pf_nnlm_model;
+int pf_nnlm_model_load(const char* path, pf_nnlm_model** m);
+int pf_nnlm_model_from_memory(const void* data, int64_t nbytes, pf_nnlm_model** m);
+int pf_nnlm_model_info(const pf_nnlm_model* m, int32_t* dims, int64_t* image_bytes);
+void pf_nnlm_model_free(pf_nnlm_model* m);
+/* Attaches the model to the engine (NULL detaches and frees what the attach and its runs allocated).  The engine takes a
+   reference of its own and uploads the weight image once.  Nothing else the engine computes changes. */
+int pf_engine_set_nnlm(pf_engine* e, const pf_nnlm_model* m);
+/* Scores B hypotheses (B <= PF_NNLM_MAX_BATCH) given from the host: ids = their concatenated tokens, lens [B].  ONE upload, one
+   forward of profile class "nnlm" (2 + 2 n_layers launches whatever B and the lengths), one copy back: lm_sum [B] fp32 and,
+   optionally, logp [sum (lens + 1)] fp32.  A hypothesis's bits do not depend on what else is in the call.
+   The workspace is 6 KB per row, n + 1 rows per hypothesis; a call of more than PF_NNLM_MAX_ROWS rows (1.6 GB) is PF_ERR_CAPACITY.
+   PF_ERR_INVALID_ARG without a model, for a length outside 0 .. PF_NNLM_MAX_TOKENS, an id outside the vocabulary or an
+   unknown flag: nothing is launched then. */
+int pf_engine_nnlm_score(pf_engine* e, const int32_t* ids, const int32_t* lens, int32_t B, int32_t flags, float* lm_sum, float* logp);
+/* The host twin in float64, ONE hypothesis: logp [n + 1]. */
+int pf_host_nnlm_logp(const pf_nnlm_model* m, const int32_t* ids, int32_t n, double* logp);
+/* The fusion, float64: score [N] = base + weight * lm_sum + bonus * n_tokens; order [N] = the indices stable-sorted by score
+   descending, so ties keep the list's order.  base is a hypothesis's ACOUSTIC score (its loglik_sum where the list has one,
+   else its score), never an n-gram-fused one: the two LMs do not stack silently.  A NaN score is refused. */
+int pf_host_nnlm_fuse(const double* base, const double* lm_sum, const int32_t* n_tokens, int32_t N, double weight, double bonus,
+                      double* score, int32_t* order);
+
 /* ------------------------------------------------------------------------ */
 /* 4b. Multi-GPU inside one process: one engine, one host thread and one HIP stream per listed
  *     device.  The reference builds a single ORT session (OfflineRecognizer.cs:23); what shards is the utterance
@@ -1160,6 +1200,11 @@ int pf_op_punc_window(pf_engine* e, const int32_t* ids, const int32_t* T, const 
 int pf_op_punc_stream_step(pf_engine* e, void* states, const int32_t* ids, const int32_t* n_new, const int32_t* flush, int32_t B,
                            int32_t ld, int32_t max_context, int32_t flags, int32_t* marks, int32_t* mark_flags, float* logits,
                            int32_t* flush_mark);
+/* exactly pf_engine_nnlm_score's launches (k_nnlm.hip; PF_ERR_INVALID_ARG without pf_engine_set_nnlm) through the staging kit:
+   the workspace rows and the ids behind the last row hold a hostile pattern, lm_sum and logp are sentinel-filled with guard
+   cells behind them, and a row that was not written or a cell beyond [rows] / [B] that was is PF_ERR_DEVICE.  logp [sum (lens +
+   1)] and lm_sum [B], either may be NULL. */
+int pf_op_nnlm_logp(pf_engine* e, const int32_t* ids, const int32_t* lens, int32_t B, int32_t flags, float* logp, float* lm_sum);
 /* exactly the attached speaker model's launches (k_spk.hip; PF_ERR_INVALID_ARG without pf_engine_set_spk_model) on caller
    windows: rows = the concatenated fbank rows of B windows, T [B] rows each (0 .. PF_SPK_MAX_FRAMES, else PF_ERR_INVALID_ARG),
    n_mels wide.  emb [B, embedding] fp32; frames (optional) [sum ceil(T / 2), the frames' width] fp32: the activations in front
@@ -1760,6 +1805,20 @@ int pf_recognizer_set_vad_model(pf_recognizer* r, const char* pfw_path);
    Timestamps entry per word and they are not all the {0, 0} placeholders of a model without timestamps (*has_time), [begin of
    its first word, end of its last] in ms. */
 int pf_recognizer_set_punc_model(pf_recognizer* r, const char* pfw_path);
+/* Not in the reference: second-pass rescoring of the n-best list ("Neural LM rescoring" above; OfflineRecognizer.SetRescoreModel).
+   pfw_path: a `.pfw` of kind "transformerlm" whose vocabulary size is the recogniser's (PF_ERR_INVALID_ARG otherwise), loaded
+   once; NULL clears and frees what it allocated.  After every GetResults whose plan produced Alternatives (SetNBest with N > 1,
+   SetNBestSearch, SetCtcBeam), ONE pf_engine_nnlm_score runs over all alternatives of all streams of the call on a leased
+   engine; per stream score' = base + weight * nnlm_sum + bonus * n_ids in float64, base = the alternative's loglik_sum where
+   the list has one, else its score (never the n-gram-fused score: with SetLm / SetNBestLm both terms are reported, lm_sum and
+   nnlm_sum, and base stays acoustic), then a stable sort by score' descending.  Each alternative's score becomes score' and
+   pf_stream_alternative_nnlm gives its nnlm_sum (NaN without a model).  Text / Tokens / Timestamps / Scores of the result stay
+   what they are.  A stream holding an alternative of more than PF_NNLM_MAX_TOKENS ids keeps its list as the search left it.
+   flags: PF_NNLM_EOS.  weight 0.5 is a stated default; nobody has tuned it on real speech.  PF_ERR_UNSUPPORTED beside
+   SetVad, whichever is set second (a stitched long-audio result carries no Alternatives), and for a pf_group forward on an
+   engine with a model attached. */
+int pf_recognizer_set_nnlm(pf_recognizer* r, const char* pfw_path, double weight, double bonus, int32_t flags);
+int pf_stream_alternative_nnlm(pf_stream* s, int32_t i, double* nnlm_sum);
 /* Speaker labels of every long-audio GetResults that follows (see "Speaker labels"): pfw_path = a `.pfw` of kind "campplus",
    loaded once and attached to every engine of the pool, present and future; NULL clears.  cfg == NULL: the defaults.  Inert
    until pf_recognizer_set_vad, and may come before or after it.  GetResults then, behind the segmentation and on the fbank rows
