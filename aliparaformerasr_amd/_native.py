@@ -373,6 +373,9 @@ SIGNATURES = {
     "pf_op_nnlm_logp": (C.c_int, [_vp, _i32, _i32, C.c_int32, C.c_int32, _f, _f]),
     "pf_host_nnlm_logp": (C.c_int, [_vp, _i32, C.c_int32, _P(C.c_double)]),
     "pf_host_nnlm_fuse": (C.c_int, [_P(C.c_double), _P(C.c_double), _i32, C.c_int32, C.c_double, C.c_double, _P(C.c_double), _i32]),
+    "pf_host_consensus": (C.c_int, [_i32, _i32, C.c_int32, _P(C.c_double), _P(C.c_double), C.c_double, _i32, _P(C.c_double), _P(C.c_double), _i32, _P(C.c_double)]),
+    "pf_engine_consensus": (C.c_int, [_vp, _i32, _i32, _i32, C.c_int32, _P(C.c_double), _i32, _P(C.c_double), _P(C.c_double), _i32]),
+    "pf_op_consensus": (C.c_int, [_vp, _i32, _i32, _i32, C.c_int32, _P(C.c_double), _i32, _P(C.c_double), _P(C.c_double), _i32]),
     "pf_punc_model_causal": (C.c_int, [_vp, _i32]),
     "pf_punc_stream_state_bytes": (C.c_int, [_vp, _i64]),
     "pf_host_punc_stream_state_bytes": (C.c_int, [_vp, _i64]),
@@ -459,6 +462,9 @@ SIGNATURES = {
     "pf_recognizer_set_punc_model": (C.c_int, [_vp, C.c_char_p]),
     "pf_recognizer_set_nnlm": (C.c_int, [_vp, C.c_char_p, C.c_double, C.c_double, C.c_int32]),
     "pf_stream_alternative_nnlm": (C.c_int, [_vp, C.c_int32, _P(C.c_double)]),
+    "pf_recognizer_set_consensus": (C.c_int, [_vp, C.c_int32, C.c_double]),
+    "pf_stream_consensus": (C.c_int, [_vp, _i32, _P(C.c_double), C.c_int32, _i32]),
+    "pf_stream_alternative_consensus": (C.c_int, [_vp, C.c_int32, _P(C.c_double), _P(C.c_double)]),
     "pf_recognizer_set_spk_model": (C.c_int, [_vp, C.c_char_p, _P(PfSpkConfig)]),
     "pf_recognizer_set_spk_cluster": (C.c_int, [_vp, C.c_int32]),
     "pf_stream_num_speakers": (C.c_int, [_vp, _i32]),

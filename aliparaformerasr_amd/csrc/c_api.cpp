@@ -1522,6 +1522,50 @@ int pf_host_nnlm_fuse(const double* base, const double* lm_sum, const int32_t* n
   PF_CATCH
 }
 
+// ---- consensus inside n-best lists ----
+int pf_host_consensus(const int32_t* ids, const int32_t* lens, int32_t N, const double* p, const double* scores, double scale,
+                      int32_t* winner, double* risk, double* conf, int32_t* D, double* post) {
+  PF_TRY
+  PF_CHECK(N >= 1 && N <= PF_CONSENSUS_MAX_HYPS, PF_ERR_INVALID_ARG, "consensus: a list holds 1 .. PF_CONSENSUS_MAX_HYPS hypotheses");
+  NEED(lens); NEED(winner); NEED(risk); NEED(conf);
+  std::vector<double> w((size_t)N);
+  if (p) {
+    std::copy(p, p + N, w.begin());
+  } else {
+    NEED(scores);
+    PF_CHECK(scale > 0.0 && std::isfinite(scale), PF_ERR_INVALID_ARG, "consensus: scale > 0");
+    PF_CHECK(host_consensus_posterior(scores, N, scale, w.data()), PF_ERR_INVALID_ARG, "consensus: a score is not finite");
+  }
+  consensus_admit(lens, N, w.data());
+  int64_t total = 0;
+  for (int i = 0; i < N; ++i) total += lens[i];
+  if (total > 0) NEED(ids);
+  host_consensus(ids, lens, N, w.data(), winner, risk, conf, D);
+  if (post) std::copy(w.begin(), w.end(), post);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_engine_consensus(pf_engine* h, const int32_t* ids, const int32_t* lens, const int32_t* n_hyp, int32_t L, const double* p,
+                        int32_t* winner, double* risk, double* conf, int32_t* D) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->consensus(ids, lens, n_hyp, L, p, winner, risk, conf, D);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_op_consensus(pf_engine* h, const int32_t* ids, const int32_t* lens, const int32_t* n_hyp, int32_t L, const double* p,
+                    int32_t* winner, double* risk, double* conf, int32_t* D) {
+  PF_TRY
+  std::shared_ptr<Engine> eh_ = E(h);
+  Engine* e = eh_.get();
+  std::lock_guard<std::mutex> lk(e->mutex());
+  e->op_consensus(ids, lens, n_hyp, L, p, winner, risk, conf, D);
+  return PF_OK;
+  PF_CATCH
+}
+
 // ---- punctuation, streaming ----
 int pf_punc_model_causal(const pf_punc_model* m, int32_t* causal) {
   PF_TRY
@@ -2557,6 +2601,33 @@ int pf_stream_alternative_nnlm(pf_stream* h, int32_t i, double* nnlm_sum) {
   Stream* s = S(h);
   PF_CHECK(i >= 0 && i < (int32_t)s->Alternatives.size(), PF_ERR_INVALID_ARG, "alternative index out of range");
   if (nnlm_sum) *nnlm_sum = s->Alternatives[(size_t)i].nnlm_sum;
+  return PF_OK;
+  PF_CATCH
+}
+int pf_recognizer_set_consensus(pf_recognizer* h, int32_t on, double scale) {
+  PF_TRY
+  std::shared_ptr<Recognizer> r = R(h);
+  PF_CHECK(!r->disposed(), PF_ERR_DISPOSED, "OfflineRecognizer");
+  r->SetConsensus(on != 0, scale);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_stream_consensus(pf_stream* h, int32_t* index, double* conf, int32_t cap, int32_t* n) {
+  PF_TRY
+  Stream* s = S(h);
+  PF_CHECK(cap >= 0 && (cap == 0 || conf), PF_ERR_INVALID_ARG, "pf_stream_consensus: cap < 0, or no buffer for cap > 0");
+  if (index) *index = s->ConsIndex;
+  if (n) *n = (int32_t)s->ConsConf.size();
+  std::copy(s->ConsConf.begin(), s->ConsConf.begin() + std::min((size_t)cap, s->ConsConf.size()), conf);
+  return PF_OK;
+  PF_CATCH
+}
+int pf_stream_alternative_consensus(pf_stream* h, int32_t i, double* posterior, double* risk) {
+  PF_TRY
+  Stream* s = S(h);
+  PF_CHECK(i >= 0 && i < (int32_t)s->Alternatives.size(), PF_ERR_INVALID_ARG, "alternative index out of range");
+  if (posterior) *posterior = s->Alternatives[(size_t)i].posterior;
+  if (risk) *risk = s->Alternatives[(size_t)i].risk;
   return PF_OK;
   PF_CATCH
 }

@@ -125,7 +125,7 @@ void Engine::release() {
   owned_.clear();
   DevBuf* bufs[] = {&ws_f32_, &ws_pcm_, &ws_audio_, &ws_meta_, &ws_fbank_, &ws_speech_, &ws_enc_, &ws_dec_, &ws_kv_, &ws_pe_, &ws_tmp_,
                     &ws_ts_, &ws_seaco_, &ws_seaco_in_, &ws_seaco_hw_, &ws_q_, &ws_qf_, &ws_seaco_q_, &ws_x3a_, &ws_x3t_, &ws_x3h_, &lm_inst_.buf, &lm_op_.buf, &nbs_hot_.buf, &ws_nbs_,
-                    &ws_step_, &ws_fe_, &fe_inv_, &fe_meta_, &vadnet_dev_.buf, &ws_vadnet_, &punc_dev_.buf, &ws_punc_, &spk_dev_.buf, &ws_spk_, &nnlm_dev_.buf, &ws_nnlm_};
+                    &ws_step_, &ws_fe_, &fe_inv_, &fe_meta_, &vadnet_dev_.buf, &ws_vadnet_, &punc_dev_.buf, &ws_punc_, &spk_dev_.buf, &ws_spk_, &nnlm_dev_.buf, &ws_nnlm_, &ws_consensus_};
   lm_inst_.src.reset(); lm_op_.src.reset(); lm_.reset(); nbs_lm_.reset();
   vadnet_dev_.src.reset(); vadnet_.reset();
   punc_dev_.src.reset(); punc_.reset();

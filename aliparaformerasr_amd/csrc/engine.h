@@ -325,6 +325,15 @@ class Engine {
   void nnlm_score(const int32_t* ids, const int32_t* lens, int B, int flags, float* lm_sum, float* logp);
   // the same through op_stage.h: hostile workspace and ids behind the rows, sentinel-filled outputs with guard cells, checked
   void op_nnlm_logp(const int32_t* ids, const int32_t* lens, int B, int flags, float* logp, float* lm_sum);
+  // Consensus inside n-best lists (k_consensus.hip; paraformer_hip.h "Consensus choice and token confidence"): L lists from the
+  // host, n_hyp [L] hypotheses each, lens / p per hypothesis, ids concatenated.  One upload, two launches of profile class
+  // "consensus", one copy back: winner [L], risk [sum n_hyp], conf [L, 256], D [sum n_hyp^2] or null.  Refusals come before
+  // anything is launched; the workspace exists from the first call on (release() frees it).
+  void consensus(const int32_t* ids, const int32_t* lens, const int32_t* n_hyp, int L, const double* p, int32_t* winner, double* risk,
+                 double* conf, int32_t* D);
+  // the same through op_stage.h: a hostile pattern behind the ids, sentinel-filled outputs with guard cells, checked
+  void op_consensus(const int32_t* ids, const int32_t* lens, const int32_t* n_hyp, int L, const double* p, int32_t* winner, double* risk,
+                    double* conf, int32_t* D);
   // The CAM++ speaker model (k_spk.hip, spk.h).  nullptr detaches and frees the image and the workspace (nothing of it is
   // launched or allocated then; attaching the model an engine still has costs no upload).  The engine keeps a reference and
   // uploads the image once.  PF_ERR_INVALID_ARG unless the model's n_mels is the front-end's.  A forward is profile class
@@ -815,6 +824,10 @@ class Engine {
   ModelDev<NnlmModel> nnlm_dev_;
   DevBuf ws_nnlm_;
   void run_nnlm(const int32_t* ids, const int32_t* lens, int B, int flags, float* lm_sum, float* logp, bool guarded);
+  // consensus: the upload (offsets, lengths, ids, weights), D and the results
+  DevBuf ws_consensus_;
+  void run_consensus(const int32_t* ids, const int32_t* lens, const int32_t* n_hyp, int L, const double* p, int32_t* winner,
+                     double* risk, double* conf, int32_t* D, bool guarded);
   // the speaker model (set_spk_model): as above; ws_spk_ holds the window table, the rows, the head's three activation buffers,
   // the TDNN's frames, the four X buffers, the embeddings and the frames asked for
   std::shared_ptr<const SpkModel> spk_;

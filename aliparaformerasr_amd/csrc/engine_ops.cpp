@@ -1189,6 +1189,104 @@ void Engine::op_nnlm_logp(const int32_t* ids, const int32_t* lens, int B, int fl
   run_nnlm(ids, lens, B, flags, lm_sum, logp, true);
 }
 
+// ---- consensus inside n-best lists (k_consensus.hip; the launch plan is at the head of that file)
+// host arrays in, host arrays out; returns after the results have arrived.  guarded: the op_stage.h form, G hostile ids behind
+// the ids and G guard cells behind winner, risk, conf and D
+void Engine::run_consensus(const int32_t* ids, const int32_t* lens, const int32_t* n_hyp, int L, const double* p, int32_t* winner,
+                           double* risk, double* conf, int32_t* D, bool guarded) {
+  PF_CHECK(L >= 1 && n_hyp && lens && p && winner && risk && conf, PF_ERR_INVALID_ARG, "consensus: L < 1 or a null argument");
+  PF_CHECK(L <= PF_CONSENSUS_MAX_LISTS, PF_ERR_CAPACITY, "consensus: more than PF_CONSENSUS_MAX_LISTS lists in one call");
+  const size_t nL = (size_t)L, G = guarded ? 64 : 0, kConf = PF_CONSENSUS_MAX_TOKENS + 1;
+  std::vector<int64_t> item_off(nL + 1, 0);
+  std::vector<int32_t> hyp_off(nL + 1, 0), d_off(nL + 1, 0);
+  for (size_t l = 0; l < nL; ++l) {
+    const int N = n_hyp[l];
+    consensus_admit(lens + hyp_off[l], N, p + hyp_off[l]);
+    hyp_off[l + 1] = hyp_off[l] + N;
+    d_off[l + 1] = d_off[l] + N * N;
+    item_off[l + 1] = item_off[l] + N * (N - 1) / 2 + 1;
+  }
+  const size_t H = (size_t)hyp_off[nL], dtot = (size_t)d_off[nL];
+  std::vector<int32_t> id_off(H + 1, 0);
+  for (size_t h = 0; h < H; ++h) id_off[h + 1] = id_off[h] + lens[h];
+  const size_t total = (size_t)id_off[H];
+  PF_CHECK(total == 0 || ids, PF_ERR_INVALID_ARG, "consensus: null ids");
+  PF_HIP(hipSetDevice(device_));
+  // the one upload: item_off | p | hyp_off | d_off | len | id_off | ids (| hostile)
+  Cursor u;
+  const Field<int64_t> f_item = u.take<int64_t>(nL + 1);
+  const Field<double> f_p = u.take<double>(H);
+  const Field<int32_t> f_hyp = u.take<int32_t>(nL + 1), f_d = u.take<int32_t>(nL + 1), f_len = u.take<int32_t>(H), f_ido = u.take<int32_t>(H),
+                       f_ids = u.take<int32_t>(total + G);
+  std::vector<char> stage(u.off);
+  std::copy(item_off.begin(), item_off.end(), f_item(stage.data()));
+  std::copy(p, p + H, f_p(stage.data()));
+  std::copy(hyp_off.begin(), hyp_off.end(), f_hyp(stage.data()));
+  std::copy(d_off.begin(), d_off.end(), f_d(stage.data()));
+  std::copy(lens, lens + H, f_len(stage.data()));
+  std::copy(id_off.begin(), id_off.end() - 1, f_ido(stage.data()));
+  if (total) std::copy(ids, ids + total, f_ids(stage.data()));
+  for (size_t i = 0; i < G; ++i) f_ids(stage.data())[total + i] = hostile_i32(i);
+  // the results: risk | conf | winner | D, each with its guard cells
+  Cursor c;
+  const size_t out0 = (size_t)round_up((int64_t)u.off, 256);
+  const Field<double> f_risk = c.take<double>(H + G), f_conf = c.take<double>(nL * kConf + G);
+  const Field<int32_t> f_win = c.take<int32_t>(nL + G);
+  const size_t back_small = c.off;
+  const Field<int32_t> f_D = c.take<int32_t>(dtot + G);
+  const size_t back_all = c.off;
+  ensure(ws_consensus_, out0 + back_all);
+  char* ws = (char*)ws_consensus_.p;
+  char* wo = ws + out0;
+  PF_HIP(hipMemcpyAsync(ws, stage.data(), stage.size(), hipMemcpyHostToDevice, stream_));
+  if (guarded) fill_sentinel(stream_, reinterpret_cast<uint32_t*>(wo), back_all / 4);
+  ConsensusLaunch a{};
+  a.L = L; a.hyp_off = f_hyp(ws); a.item_off = f_item(ws); a.d_off = f_d(ws); a.len = f_len(ws); a.id_off = f_ido(ws); a.ids = f_ids(ws);
+  a.p = f_p(ws); a.D = f_D(wo); a.winner = f_win(wo); a.risk = f_risk(wo); a.conf = f_conf(wo);
+  prof_begin("consensus", 0);
+  launch_consensus_dist(stream_, a, item_off[nL]);
+  prof_end("consensus");
+  prof_begin("consensus", 0);
+  launch_consensus_pick(stream_, a);
+  prof_end("consensus");
+  const size_t back = (D || guarded) ? back_all : back_small;           // the one copy back
+  std::vector<uint64_t> out((back + 7) / 8);
+  PF_HIP(hipMemcpyAsync(out.data(), wo, back, hipMemcpyDeviceToHost, stream_));
+  PF_HIP(hipStreamSynchronize(stream_));
+  const char* o = reinterpret_cast<const char*>(out.data());
+  if (guarded) {
+    constexpr uint64_t kSentinel64 = ((uint64_t)kSentinel32 << 32) | kSentinel32;
+    const auto scan64 = [&](const char* what, const double* at, size_t n) {
+      const GuardGeom g = result_geom((int64_t)(n + G), (int)n, 1, 1, (int64_t)n);
+      if (const GuardHit hit = guard_scan<uint64_t>(reinterpret_cast<const uint64_t*>(at), nullptr, kSentinel64, g))
+        throw Error(PF_ERR_DEVICE, guard_message(what, g, hit));
+    };
+    const auto scan32 = [&](const char* what, const int32_t* at, size_t n) {
+      const GuardGeom g = result_geom((int64_t)(n + G), (int)n, 1, 1, (int64_t)n);
+      if (const GuardHit hit = guard_scan<uint32_t>(reinterpret_cast<const uint32_t*>(at), nullptr, kSentinel32, g))
+        throw Error(PF_ERR_DEVICE, guard_message(what, g, hit));
+    };
+    scan64("consensus: risk", f_risk(o), H);
+    scan64("consensus: conf", f_conf(o), nL * kConf);
+    scan32("consensus: winner", f_win(o), nL);
+    scan32("consensus: D", f_D(o), dtot);
+  }
+  std::copy(f_risk(o), f_risk(o) + H, risk);
+  std::copy(f_conf(o), f_conf(o) + nL * kConf, conf);
+  std::copy(f_win(o), f_win(o) + nL, winner);
+  if (D) std::copy(f_D(o), f_D(o) + dtot, D);
+}
+
+void Engine::consensus(const int32_t* ids, const int32_t* lens, const int32_t* n_hyp, int L, const double* p, int32_t* winner, double* risk,
+                       double* conf, int32_t* D) {
+  run_consensus(ids, lens, n_hyp, L, p, winner, risk, conf, D, false);
+}
+
+void Engine::op_consensus(const int32_t* ids, const int32_t* lens, const int32_t* n_hyp, int L, const double* p, int32_t* winner,
+                          double* risk, double* conf, int32_t* D) {
+  run_consensus(ids, lens, n_hyp, L, p, winner, risk, conf, D, true);
+}
+
 // ---- the punctuation model, streaming (k_punc_stream.hip): ONE launch for B streams
 void Engine::punc_stream_step(char* states_dev, const int32_t* slot_dev, const int32_t* ids_dev, int64_t ld, const int32_t* n_new_dev,
                               const int32_t* flush_dev, int B, int max_context, int flags, int32_t* marks_dev, int32_t* mark_flags_dev,

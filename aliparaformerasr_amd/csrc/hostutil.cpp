@@ -1309,6 +1309,90 @@ void spot_pack(const int32_t* ids, const int32_t* lens, int n, int V, SpotImage&
   out.K = n;
 }
 
+// ---- consensus inside an n-best list (paraformer_hip.h "Consensus choice and token confidence"; tests/consensus_ref.py) -----
+void consensus_admit(const int32_t* lens, int N, const double* p) {
+  PF_CHECK(N >= 1 && N <= PF_CONSENSUS_MAX_HYPS, PF_ERR_INVALID_ARG, "consensus: a list holds 1 .. PF_CONSENSUS_MAX_HYPS hypotheses");
+  PF_CHECK(lens && p, PF_ERR_INVALID_ARG, "consensus: null argument");
+  for (int i = 0; i < N; ++i) {
+    PF_CHECK(lens[i] >= 0 && lens[i] <= PF_CONSENSUS_MAX_TOKENS, PF_ERR_INVALID_ARG, "consensus: a hypothesis holds 0 .. PF_CONSENSUS_MAX_TOKENS ids");
+    PF_CHECK(std::isfinite(p[i]) && p[i] >= 0.0, PF_ERR_INVALID_ARG, "consensus: a weight is finite and >= 0");
+  }
+}
+
+bool host_consensus_posterior(const double* scores, int N, double scale, double* post) {
+  double top = scores[0];
+  for (int i = 0; i < N; ++i) {
+    if (!std::isfinite(scores[i])) return false;
+    top = std::max(top, scores[i]);
+  }
+  std::vector<double> e((size_t)N);
+  double sum = 0.0;
+  for (int i = 0; i < N; ++i) { e[(size_t)i] = std::exp(scale * (scores[i] - top)); sum += e[(size_t)i]; }
+  for (int i = 0; i < N; ++i) post[i] = e[(size_t)i] / sum;
+  return true;
+}
+
+namespace {
+
+// the table E of x (rows) against y (columns), (nx + 1) x (ny + 1) row-major
+void levenshtein_table(const int32_t* x, int nx, const int32_t* y, int ny, std::vector<int32_t>& E) {
+  const int ld = ny + 1;
+  E.resize((size_t)(nx + 1) * ld);
+  for (int b = 0; b <= ny; ++b) E[(size_t)b] = b;
+  for (int a = 1; a <= nx; ++a) {
+    E[(size_t)a * ld] = a;
+    for (int b = 1; b <= ny; ++b)
+      E[(size_t)a * ld + b] = std::min({E[(size_t)(a - 1) * ld + b - 1] + (x[a - 1] != y[b - 1] ? 1 : 0), E[(size_t)(a - 1) * ld + b] + 1,
+                                        E[(size_t)a * ld + b - 1] + 1});
+  }
+}
+
+}  // namespace
+
+void host_consensus(const int32_t* ids, const int32_t* lens, int N, const double* p, int32_t* winner, double* risk, double* conf,
+                    int32_t* D) {
+#pragma clang fp contract(off)
+  std::vector<size_t> off((size_t)N + 1, 0);
+  for (int i = 0; i < N; ++i) off[(size_t)i + 1] = off[(size_t)i] + (size_t)lens[i];
+  std::vector<int32_t> dist((size_t)N * N, 0), E;
+  for (int i = 0; i < N; ++i)
+    for (int j = i + 1; j < N; ++j) {
+      levenshtein_table(ids + off[(size_t)i], lens[i], ids + off[(size_t)j], lens[j], E);
+      dist[(size_t)i * N + j] = dist[(size_t)j * N + i] = E.back();
+    }
+  if (D) std::copy(dist.begin(), dist.end(), D);
+  int w = 0;
+  for (int i = 0; i < N; ++i) {
+    double r = 0.0;
+    for (int j = 0; j < N; ++j) {
+      const double term = p[j] * (double)dist[(size_t)i * N + j];
+      r = r + term;
+    }
+    risk[i] = r;
+    if (r < risk[w]) w = i;
+  }
+  *winner = w;
+  const int nw = lens[w];
+  const int32_t* x = ids + off[(size_t)w];
+  std::fill(conf, conf + PF_CONSENSUS_MAX_TOKENS + 1, 0.0);
+  std::vector<uint8_t> m((size_t)nw);
+  for (int j = 0; j < N; ++j) {
+    const int32_t* y = ids + off[(size_t)j];
+    const int nj = lens[j], ld = nj + 1;
+    levenshtein_table(x, nw, y, nj, E);
+    std::fill(m.begin(), m.end(), (uint8_t)0);
+    for (int a = nw, b = nj; a > 0 && b > 0;) {         // a border forces the rest: up steps match nothing
+      const int32_t e = E[(size_t)a * ld + b];
+      const bool same = x[a - 1] == y[b - 1];
+      if (e == E[(size_t)(a - 1) * ld + b - 1] + (same ? 0 : 1)) { m[(size_t)a - 1] = same; --a; --b; }
+      else if (e == E[(size_t)(a - 1) * ld + b] + 1) --a;
+      else --b;
+    }
+    for (int t = 0; t < nw; ++t)
+      if (m[(size_t)t]) conf[t] = conf[t] + p[j];
+  }
+}
+
 // ---- voice-activity segmentation (paraformer_hip.h "Voice-activity segmentation"; tests/vad_ref.py) --------------------------
 pf_vad_config vad_default() {
   pf_vad_config c{};

@@ -217,6 +217,17 @@ struct SpotImage {
 };
 void spot_pack(const int32_t* ids, const int32_t* lens, int n, int V, SpotImage& out);
 
+// ---- consensus inside an n-best list (paraformer_hip.h "Consensus choice and token confidence"; tests/consensus_ref.py) ----
+// consensus_admit: what the twin and the engine check about ONE list before anything runs (PF_ERR_INVALID_ARG): 1 <= N <=
+// PF_CONSENSUS_MAX_HYPS, every length in 0 .. PF_CONSENSUS_MAX_TOKENS, every weight finite and >= 0.
+void consensus_admit(const int32_t* lens, int N, const double* p);
+// the posterior of scores [N] under scale > 0 in float64, as defined; false (nothing written) when a score is not finite
+bool host_consensus_posterior(const double* scores, int N, double scale, double* post);
+// The host twin of k_consensus.hip for one admitted list: winner, risk [N], conf [256] (n_w valid, the rest 0), D [N, N] or null.
+// Bit-equal to the definition and the kernel: products and sums are rounded one by one.
+void host_consensus(const int32_t* ids, const int32_t* lens, int N, const double* p, int32_t* winner, double* risk, double* conf,
+                    int32_t* D);
+
 // ---- voice-activity segmentation (paraformer_hip.h "Voice-activity segmentation"; the definition is tests/vad_ref.py) ----
 // The host twins of k_vad.hip.  vad_default: the stated defaults.  vad_check: cfg (null = the defaults) validated against the
 // constraints of the header (PF_ERR_INVALID_ARG), returned by value.

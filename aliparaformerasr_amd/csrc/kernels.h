@@ -749,6 +749,21 @@ void launch_nnlm_attn(hipStream_t s, const NnlmAttnLaunch& a);
 struct NnlmSumLaunch { const float* logp; const int64_t* off; int B; int eos; float* lm_sum; };
 void launch_nnlm_sum(hipStream_t s, const NnlmSumLaunch& a);
 
+// ---------------------------------------------------------------- consensus inside n-best lists (k_consensus.hip) ------
+// paraformer_hip.h "Consensus choice and token confidence"; the definition is tests/consensus_ref.py.  L lists; list l holds the
+// hypotheses [hyp_off[l], hyp_off[l + 1]) (1 .. 64 of them), hypothesis h the ids [id_off[h], id_off[h] + len[h]) (0 .. 255) and
+// the weight p[h]; the list's N x N distances start at D + d_off[l] and its work items (its pairs and one for the diagonal) at
+// item_off[l].  winner [L], risk [hypotheses], conf [L, 256].  Two launches: dist fills D, pick reads it.  Nothing at or beyond
+// a list's extent is read or stored.
+struct ConsensusLaunch {
+  int L;
+  const int32_t* hyp_off; const int64_t* item_off; const int32_t* d_off;       // [L + 1] each
+  const int32_t* len; const int32_t* id_off; const int32_t* ids; const double* p;
+  int32_t* D; int32_t* winner; double* risk; double* conf;
+};
+void launch_consensus_dist(hipStream_t s, const ConsensusLaunch& a, int64_t items);
+void launch_consensus_pick(hipStream_t s, const ConsensusLaunch& a);
+
 // ---------------------------------------------------------------- the CAM++ speaker model (k_spk.hip) ------
 // The definition in numpy is tests/spk_ref.py; the launch plan (15 launches per forward) is at the head of k_spk.hip and
 // Engine::run_spk fills these in.  img: the model's device image (spk.h); every *_off and TileGemm offset is a byte offset into

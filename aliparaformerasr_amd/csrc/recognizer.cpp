@@ -858,6 +858,7 @@ void Recognizer::stitch_pieces(const std::vector<Stream*>& streams, const std::v
     out[i].TextLen = utf16_length(out[i].Text);
     s->Tokens.swap(ids[i]); s->Timestamps.swap(ts[i]); s->Scores.swap(sc[i]);
     s->AltIds.clear(); s->AltVal.clear(); s->AltK = 0; s->Alternatives.clear();
+    s->ConsIndex = -1; s->ConsConf.clear();
     s->AlignTs.clear(); s->AlignTok.clear(); s->AlignN = -1;
     s->KwPhrase.clear(); s->KwTs.clear(); s->KwConf.clear(); s->KwN = -1;
     s->RemoveChunk();                                        // as Forward: a stream that produced a result gives up its audio
@@ -1619,6 +1620,62 @@ void Recognizer::Rescore(const std::vector<Stream*>& streams) {
   }
 }
 
+void Recognizer::SetConsensus(bool on, double scale) {
+  if (disposed_) throw Error(PF_ERR_DISPOSED, "OfflineRecognizer");
+  if (on) {
+    PF_CHECK(scale > 0.0 && std::isfinite(scale), PF_ERR_INVALID_ARG, "SetConsensus: the scale is > 0 and finite");
+    consensus_scale_ = scale;
+  }
+  consensus_on_ = on;
+}
+
+// every Alternatives list of the call in ONE pf_engine_consensus (in turns only beyond PF_CONSENSUS_MAX_LISTS streams)
+void Recognizer::Consensus(const std::vector<Stream*>& streams) {
+  const double scale = consensus_scale_;
+  std::vector<Stream*> todo;
+  std::vector<int32_t> ids, lens, n_hyp;
+  std::vector<double> post;
+  for (Stream* s : streams) {
+    const size_t N = s->Alternatives.size();
+    bool ok = N >= 1 && N <= (size_t)PF_CONSENSUS_MAX_HYPS;
+    std::vector<double> sc(N), w(N);
+    for (size_t i = 0; i < N; ++i) {
+      ok = ok && s->Alternatives[i].ids.size() <= (size_t)PF_CONSENSUS_MAX_TOKENS;
+      sc[i] = s->Alternatives[i].score;
+    }
+    if (!ok || !host_consensus_posterior(sc.data(), (int)N, scale, w.data())) continue;
+    todo.push_back(s);
+    n_hyp.push_back((int32_t)N);
+    post.insert(post.end(), w.begin(), w.end());
+    for (const Alternative& a : s->Alternatives) {
+      for (int64_t id : a.ids) ids.push_back((int32_t)id);
+      lens.push_back((int32_t)a.ids.size());
+    }
+  }
+  if (todo.empty()) return;
+  const size_t kConf = PF_CONSENSUS_MAX_TOKENS + 1;
+  std::vector<int32_t> winner(todo.size());
+  std::vector<double> risk(lens.size()), conf(todo.size() * kConf);
+  for (size_t at = 0, h = 0, first = 0; at < todo.size();) {
+    const size_t n = std::min(todo.size() - at, (size_t)PF_CONSENSUS_MAX_LISTS);
+    size_t hyps = 0, toks = 0;
+    for (size_t l = 0; l < n; ++l) hyps += (size_t)n_hyp[at + l];
+    for (size_t i = 0; i < hyps; ++i) toks += (size_t)lens[h + i];
+    Lease lease = acquire();
+    lease->consensus(ids.data() + first, lens.data() + h, n_hyp.data() + at, (int)n, post.data() + h, winner.data() + at, risk.data() + h,
+                     conf.data() + at * kConf, nullptr);
+    at += n; h += hyps; first += toks;
+  }
+  size_t h = 0;
+  for (size_t l = 0; l < todo.size(); ++l) {
+    Stream* s = todo[l];
+    for (Alternative& a : s->Alternatives) { a.posterior = post[h]; a.risk = risk[h]; ++h; }
+    s->ConsIndex = winner[l];
+    const size_t nw = s->Alternatives[(size_t)winner[l]].ids.size();
+    s->ConsConf.assign(conf.begin() + (ptrdiff_t)(l * kConf), conf.begin() + (ptrdiff_t)(l * kConf + nw));
+  }
+}
+
 void Recognizer::GetResults(const std::vector<Stream*>& streams) {
   bool vad;
   { std::lock_guard<std::mutex> lk(vad_mu_); vad = vad_on_; }
@@ -1639,6 +1696,17 @@ void Recognizer::GetResults(const std::vector<Stream*>& streams) {
       Rescore(streams);
     } catch (...) {
       rescore_error = std::current_exception();
+    }
+  }
+  if (consensus_on_ && !vad) {                                // on the lists as Rescore left them; the same rule for its errors
+    try {
+      Consensus(streams);
+    } catch (...) {
+      for (Stream* s : streams) {
+        s->ConsIndex = -1; s->ConsConf.clear();
+        for (Alternative& a : s->Alternatives) a.posterior = a.risk = std::nan("");
+      }
+      if (!rescore_error) rescore_error = std::current_exception();
     }
   }
   for (Stream* s : streams)                                   // the n-best list goes through the same DecodeMulti

@@ -185,6 +185,13 @@ class Recognizer : public std::enable_shared_from_this<Recognizer> {
   // alternative above PF_NNLM_MAX_TOKENS ids keeps its list as it is (nnlm_sum NaN).  Refused beside SetVad (whichever is
   // set second): a stitched long-audio result carries no Alternatives.
   void SetRescoreModel(const std::string& pfw_path, double weight, double bonus, int flags);
+  // The consensus choice inside every Alternatives list that follows (paraformer_hip.h "Consensus choice and token confidence").
+  // After a GetResults whose plan produced Alternatives, and after Rescore, ONE pf_engine_consensus over the lists of all
+  // streams of the call on a leased engine, the weights the posterior of the alternatives' scores under `scale` (> 0 and finite,
+  // PF_ERR_INVALID_ARG otherwise; 1.0 is a stated default, not tuned).  Each stream gets ConsIndex / ConsConf, each alternative
+  // posterior / risk; the list's order, Text / Tokens / Timestamps / Scores stay.  A stream without alternatives, with one above
+  // PF_CONSENSUS_MAX_TOKENS ids or with a score that is not finite is left out (-1, NaN).  Inert beside SetVad.
+  void SetConsensus(bool on, double scale);
   // Speaker labels of every long-audio GetResults that follows (paraformer_hip.h "Speaker labels"): a `.pfw` of kind "campplus",
   // loaded once and attached to every engine of the pool, present and future; "" clears.  Inert until SetVad, and may be set
   // before or after it.  Behind the segmentation, on the fbank rows it staged, under the same lease: the windows of all of the
@@ -263,6 +270,9 @@ class Recognizer : public std::enable_shared_from_this<Recognizer> {
   std::mutex punc_mu_;                                        // guards punc_model_
   std::shared_ptr<const PuncModel> punc_model_;
   void Rescore(const std::vector<Stream*>& streams);
+  void Consensus(const std::vector<Stream*>& streams);
+  std::atomic<bool> consensus_on_{false};
+  std::atomic<double> consensus_scale_{1.0};
   std::mutex nnlm_mu_;                                        // guards the four below
   std::shared_ptr<const NnlmModel> nnlm_model_;
   double nnlm_weight_ = 0.5, nnlm_bonus_ = 0.0; int nnlm_flags_ = 0;

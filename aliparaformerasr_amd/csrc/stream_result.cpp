@@ -103,6 +103,7 @@ void build_stream_result(const HostBatchOut& r, const ResultPlan& p, int b, Stre
   }
 
   s.AltIds.clear(); s.AltVal.clear(); s.AltK = 0; s.Alternatives.clear();
+  s.ConsIndex = -1; s.ConsConf.clear();
   const int K = (dflags & PF_DECODE_TOPK) ? r.topk_k : 0;
   if (K > 0 && L > 0) {
     const TopkBlock tb = r.topk_block();

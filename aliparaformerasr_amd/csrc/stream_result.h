@@ -70,6 +70,9 @@ struct Alternative {
   // with SetRescoreModel: the Transformer LM's sum of log-probabilities of the ids (NaN without it); score is then
   // base + weight * nnlm_sum + bonus * ids.size(), base = loglik_sum where that is filled, else the search's score
   double nnlm_sum = std::nan("");
+  // with SetConsensus: the alternative's posterior inside its list (from score as it stands after every earlier step) and its
+  // expected token error under that posterior (NaN without it)
+  double posterior = std::nan(""), risk = std::nan("");
   ResultEntity res;
 };
 // time_stamp_lfr6_onnx (OfflineRecognizer.cs:200-302); throws PF_ERR_RECOGNITION where the C#
@@ -87,6 +90,10 @@ struct StreamResult {
   std::vector<float> AltVal;
   int AltK = 0;
   std::vector<Alternative> Alternatives;
+  // consensus (Recognizer::SetConsensus) of the last GetResults: the place in Alternatives of the entry of minimal risk and the
+  // confidence of each of its ids; -1 / empty when that GetResults chose nothing for this stream
+  int ConsIndex = -1;
+  std::vector<double> ConsConf;
   // CTC forced alignment (Recognizer::SetAlign) of the last GetResults: [begin, end] ms per target id (flat), the token scores,
   // the Viterbi score, the log-likelihood, ok; AlignN = -1 when that GetResults aligned nothing for this stream
   std::vector<int32_t> AlignTs; std::vector<float> AlignTok;

@@ -758,6 +758,39 @@ def host_nnlm_fuse(base, lm_sum, n_tokens, weight=0.5, bonus=0.0):
     return score[: b.size].copy(), order[: b.size].copy()
 
 
+CONSENSUS_MAX_HYPS = 64
+CONSENSUS_MAX_TOKENS = 255
+CONSENSUS_MAX_LISTS = 1024
+
+
+class ConsensusResult:
+    """The consensus choice inside ONE n-best list: winner (the place of the hypothesis of minimal risk), risk float64 [N]
+    (expected token error under the weights), conf float64 [n_winner] (per token of the winner, the weight of the hypotheses
+    that agree with it), D int32 [N, N] (Levenshtein distances; None when not asked for), post float64 [N] (the weights used)."""
+
+    def __init__(self, winner, risk, conf, D, post):
+        self.winner, self.risk, self.conf, self.D, self.post = winner, risk, conf, D, post
+
+
+def host_consensus(hyps, p=None, scores=None, scale=1.0, want_D=True) -> ConsensusResult:
+    """ONE list in host code, float64 and integers (pf_host_consensus, the twin of k_consensus.hip): hyps = the hypotheses' id
+    lists; the weights are p or, without it, the posterior of scores under scale (1.0 is a stated default, not tuned)."""
+    arrs = [np.ascontiguousarray(a, dtype=np.int32).reshape(-1) for a in hyps]
+    n = len(arrs)
+    lens = np.ascontiguousarray([a.size for a in arrs] + [0], dtype=np.int32)
+    ids = np.ascontiguousarray(np.concatenate(arrs + [np.zeros(1, np.int32)]))
+    w = None if p is None else np.ascontiguousarray(p, dtype=np.float64).reshape(-1)
+    s = None if scores is None else np.ascontiguousarray(scores, dtype=np.float64).reshape(-1)
+    assert all(x is None or x.size == n for x in (w, s))
+    winner, risk, conf = np.zeros(1, np.int32), np.zeros(n + 1, np.float64), np.zeros(CONSENSUS_MAX_TOKENS + 1, np.float64)
+    D, post = (np.zeros(n * n + 1, np.int32) if want_D else None), np.zeros(n + 1, np.float64)
+    N.check(N.load().pf_host_consensus(_i32p(ids), _i32p(lens), n, None if w is None else _dp(w), None if s is None else _dp(s),
+                                       float(scale), _i32p(winner), _dp(risk), _dp(conf), None if D is None else _i32p(D), _dp(post)))
+    k = int(winner[0])
+    return ConsensusResult(k, risk[:n].copy(), conf[: arrs[k].size].copy(), None if D is None else D[: n * n].reshape(n, n).copy(),
+                           post[:n].copy())
+
+
 PUNC_STREAM_MAX_CONTEXT = 256
 PUNC_STREAM_DEFAULT_CONTEXT = 200
 PUNC_STREAM_NO_RESTARTS = 1
@@ -1686,6 +1719,29 @@ class Engine:
         else:
             N.check(self._lib.pf_engine_nnlm_score(self._h, _i32p(ids), _i32p(n), len(arrs), flags, _fp(lm), None if lp is None else _fp(lp)))
         return lm[: len(arrs)].copy(), ([lp[off[b]: off[b + 1]].copy() for b in range(len(arrs))] if want_logp else None)
+
+    def consensus(self, lists, weights, want_D=True, op=False):
+        """The consensus choice inside every list of `lists` (each a list of id lists) under `weights` (a float64 weight per
+        hypothesis, list by list) in ONE call: two launches of k_consensus.hip (pf_engine_consensus).  Returns a ConsensusResult
+        per list.  op: through pf_op_consensus (a hostile pattern behind the ids, guarded outputs)."""
+        n_hyp = np.ascontiguousarray([len(l) for l in lists] + [0], dtype=np.int32)
+        arrs, lens, ids, _ = self._punc_batch([h for l in lists for h in l])
+        p = np.ascontiguousarray(np.concatenate([np.asarray(w, np.float64).reshape(-1) for w in weights] + [np.zeros(1)]))
+        L, H = len(lists), len(arrs)
+        assert p.size == H + 1
+        winner, risk = np.zeros(L + 1, np.int32), np.zeros(H + 1, np.float64)
+        conf = np.zeros((L + 1, CONSENSUS_MAX_TOKENS + 1), np.float64)
+        D = np.zeros(int((n_hyp.astype(np.int64) ** 2).sum()) + 1, np.int32) if want_D else None
+        fn = self._lib.pf_op_consensus if op else self._lib.pf_engine_consensus
+        N.check(fn(self._h, _i32p(ids), _i32p(lens), _i32p(n_hyp), L, _dp(p), _i32p(winner), _dp(risk), _dp(conf),
+                   None if D is None else _i32p(D)))
+        out, h, d = [], 0, 0
+        for l, hyps in enumerate(lists):
+            n, k = len(hyps), int(winner[l])
+            out.append(ConsensusResult(k, risk[h: h + n].copy(), conf[l, : arrs[h + k].size].copy(),
+                                       None if D is None else D[d: d + n * n].reshape(n, n).copy(), p[h: h + n].copy()))
+            h, d = h + n, d + n * n
+        return out
 
     def set_punc_model(self, model):
         """Attaches a PuncModel (pf_engine_set_punc_model); None detaches and frees what the attach and its runs allocated."""

@@ -1,7 +1,7 @@
 """Command-line harness mirroring AliParaformerAsr.Examples (`-type offline` and `-type online`).
 
     python -m aliparaformerasr_amd.examples -type offline -method batch -base <dir> -model <name> \
-        [-accuracy int8] [-threads 2] [-decode ctc|frames] [-intake host|device] [-resample linear|sinc] [-nbest N [-topk K] [-beam W | -search W] [-hotboost S] [-lm FILE [-lmweight A] [-lmbonus B] [-lmeos]] [-rescore FILE [-rescoreweight A] [-rescorebonus B] [-rescoreeos]]] [-align FILE|beam] [-spot FILE [-spotthreshold P] [-spothits N]] [-vad [key=value,...] [-vadmodel FILE] [-spk FILE[,cluster=device] [key=value,...]]] [-punc FILE] -files a.wav b.wav
+        [-accuracy int8] [-threads 2] [-decode ctc|frames] [-intake host|device] [-resample linear|sinc] [-nbest N [-topk K] [-beam W | -search W] [-hotboost S] [-lm FILE [-lmweight A] [-lmbonus B] [-lmeos]] [-rescore FILE [-rescoreweight A] [-rescorebonus B] [-rescoreeos]] [-consensus [SCALE]]] [-align FILE|beam] [-spot FILE [-spotthreshold P] [-spothits N]] [-vad [key=value,...] [-vadmodel FILE] [-spk FILE[,cluster=device] [key=value,...]]] [-punc FILE] -files a.wav b.wav
     python -m aliparaformerasr_amd.examples -type online -method one -base <dir> -model <name> [-endpoint [key=value,...] [-vadmodel FILE] [-secondpass <offline name>]] [-tokentimes [-devicefrontend]] [-puncstream FILE[,max_context=N]] [-intake host|device] [-resample linear|sinc] -files a.wav
 
 Mirrors (file:line in /root/reference/AliParaformerAsr.Examples):
@@ -44,6 +44,9 @@ each `nbest[i]` line ends in ` hot:<matched tokens> lm:<lm_sum> loglik_sum:<sum 
 the n-best list with a causal Transformer LM on the GPU: FILE is a `.pfw` of kind transformerlm on the recogniser's vocabulary;
 score becomes base + A * nnlm_sum + B * tokens and the list is re-ordered by it; each `nbest[i]` line then ends in
 ` nnlm:<nnlm_sum>`.  The default weight 0.5 is a stated default: nobody has tuned it on real speech.
+`-consensus [SCALE]` (with `-nbest`; OfflineRecognizer.SetConsensus) picks, inside the n-best list, the entry of lowest expected
+token error under the list's posterior softmax(SCALE * score) on the GPU: each `nbest[i]` line then ends in ` post:<posterior>
+risk:<expected errors>` and a `consensus: #i token[conf] ...` line follows the list.  SCALE 1.0 is a stated default, not tuned.
 `-lm FILE [-lmweight A] [-lmbonus B] [-lmeos]` (with `-nbest N -beam W`; OfflineRecognizer.SetLm) fuses the ARPA n-gram language
 model FILE into that search with weight A (default 0.5), per-token bonus B (default 0) and, with `-lmeos`, the end-of-sentence
 step; each `nbest[i]` line then ends in ` hot:<matched tokens> lm:<lm_sum> loglik_sum:<unfused score>`.
@@ -203,9 +206,16 @@ def _nbest_lines(stream, align=False) -> list:
             hot = '' if a.LogLikSum is None else ' hot:%d loglik_sum:%.6f' % (a.HotwordTokens, a.LogLikSum)
         if a.NnlmSum is not None:
             hot += ' nnlm:%.6f' % a.NnlmSum
+        if a.Posterior is not None:
+            hot += ' post:%.6f risk:%.6f' % (a.Posterior, a.Risk)
         out.append('nbest[%d] score:%.6f text:%s%s' % (i, a.Score, a.Text, hot))
         if align and a.LogLik is not None:
             out.append('align[%d] loglik:%.6f pairs:%s' % (i, a.LogLik, _pairs(a.Timestamps)))
+    k = stream.ConsensusIndex
+    if k >= 0:
+        alts = stream.Alternatives
+        toks = alts[k].Tokens if len(alts[k].Tokens) == len(alts[k].Ids) else [str(i) for i in alts[k].Ids]
+        out.append('consensus: #%d %s' % (k, ' '.join('%s[%.3f]' % tc for tc in zip(toks, stream.ConsensusConfidence))))
     return out
 
 
@@ -349,7 +359,7 @@ def _punc_lines(st):
 def offline_recognizer(method="one", model="paraformer-seaco-large-zh-timestamp-onnx-offline", accuracy="int8",
                        threads=2, files=None, base=None, out=sys.stdout, decode="frames", intake="host", nbest=0, topk=4,
                        beam=0, align=None, hotboost=0.0, vad=None, lm=None, lmweight=0.5, lmbonus=0.0, lmeos=False, search=0, vadmodel=None, punc=None, spk=None,
-                       resample="linear", spot=None, spotthreshold=0.5, spothits=8, rescore=None, rescoreweight=0.5, rescorebonus=0.0, rescoreeos=False):
+                       resample="linear", spot=None, spotthreshold=0.5, spothits=8, rescore=None, rescoreweight=0.5, rescorebonus=0.0, rescoreeos=False, consensus=None):
     from .offline_recognizer import OfflineRecognizer
     base = base or os.getcwd()
     sel = select_model_files(base, model, accuracy)
@@ -376,6 +386,8 @@ def offline_recognizer(method="one", model="paraformer-seaco-large-zh-timestamp-
                 rec.SetNBestLm(lm, lmweight, lmbonus, 1 if lmeos else 0)
     if rescore:
         rec.SetRescoreModel(rescore, rescoreweight, rescorebonus, rescoreeos)
+    if consensus is not None:
+        rec.SetConsensus(True, consensus)
     if vad is not None:
         vcfg = vad["cfg"] or True
         if vadmodel:                                       # the model's default thresholds unless keys are given
@@ -806,6 +818,16 @@ def parse_args(argv, env=None):
                 raise ValueError("%s takes a number" % a)
         elif a == "-rescoreeos":
             cfg["rescoreeos"] = True
+        elif a == "-consensus":
+            cfg["consensus"] = 1.0
+            if i + 1 < len(argv) and not argv[i + 1].startswith("-"):
+                i += 1
+                try:
+                    cfg["consensus"] = float(argv[i])
+                except ValueError:
+                    raise ValueError("-consensus takes an optional scale > 0")
+                if not cfg["consensus"] > 0:
+                    raise ValueError("-consensus takes an optional scale > 0")
         elif a == "-punc":
             i += 1
             if i >= len(argv) or argv[i].startswith("-"):
@@ -862,6 +884,8 @@ def parse_args(argv, env=None):
         raise ValueError("-endpoint is an online option")
     if "secondpass" in cfg and "endpoint" not in cfg:
         raise ValueError("-secondpass goes with -endpoint")
+    if "consensus" in cfg and "nbest" not in cfg:
+        raise ValueError("-consensus goes with -nbest")
     if "rescore" in cfg and "nbest" not in cfg:
         raise ValueError("-rescore goes with -nbest")
     if any(k in cfg for k in ("rescoreweight", "rescorebonus", "rescoreeos")) and "rescore" not in cfg:
@@ -908,7 +932,7 @@ def main(argv=None):
                            vadmodel=cfg.get("vadmodel"), punc=cfg.get("punc"), spk=cfg.get("spk"),
                            resample=cfg.get("resample", "linear"), spot=cfg.get("spot"), spotthreshold=cfg.get("spotthreshold", 0.5),
                            spothits=cfg.get("spothits", 8), rescore=cfg.get("rescore"), rescoreweight=cfg.get("rescoreweight", 0.5),
-                           rescorebonus=cfg.get("rescorebonus", 0.0), rescoreeos=cfg.get("rescoreeos", False))
+                           rescorebonus=cfg.get("rescorebonus", 0.0), rescoreeos=cfg.get("rescoreeos", False), consensus=cfg.get("consensus"))
     else:
         print("the recognizer type must be online or offline")
         return 2

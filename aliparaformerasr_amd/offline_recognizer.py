@@ -87,6 +87,10 @@ class Alternative:
     # with OfflineRecognizer.SetRescoreModel: the Transformer LM's sum of log-probabilities of Ids (None without a model); Score is
     # then base + weight * NnlmSum + bonus * len(Ids), base = LogLikSum where the list has one, else the search's score
     NnlmSum: Optional[float] = None
+    # with OfflineRecognizer.SetConsensus: the alternative's posterior inside its list (from Score as it stands after every
+    # earlier step) and its expected token error under that posterior (None without it)
+    Posterior: Optional[float] = None
+    Risk: Optional[float] = None
 
 
 @dataclass
@@ -251,6 +255,25 @@ class OfflineStream:
         K = k.value
         return [[(pi[t * K + j], pv[t * K + j]) for j in range(K)] for t in range(n.value)]
 
+    def _consensus(self):
+        idx, n = C.c_int32(), C.c_int32()
+        conf = (C.c_double * 256)()
+        _ck(self._lib.pf_stream_consensus(self._h, idx, conf, 256, n))
+        return idx.value, [conf[t] for t in range(n.value)]
+
+    @property
+    def ConsensusIndex(self) -> int:
+        """OfflineRecognizer.SetConsensus: the place in Alternatives of the entry of minimal expected token error under the
+        list's posterior; -1 when the last GetResults chose nothing for this stream (option off, no list, an alternative above
+        255 ids)."""
+        return self._consensus()[0]
+
+    @property
+    def ConsensusConfidence(self) -> List[float]:
+        """Per id of Alternatives[ConsensusIndex]: the posterior mass of the alternatives whose canonical alignment agrees with
+        it at that id (empty when ConsensusIndex is -1)."""
+        return self._consensus()[1]
+
     @property
     def Alternatives(self) -> List["Alternative"]:
         """The n-best list of the last GetResults (paraformer, OfflineRecognizer.SetNBest with N > 1: entry 0 is the result
@@ -273,10 +296,14 @@ class OfflineStream:
             lm, nn = C.c_double(), C.c_double()
             _ck(self._lib.pf_stream_alternative_lm(self._h, i, lm, None))
             _ck(self._lib.pf_stream_alternative_nnlm(self._h, i, nn))
+            po, ri = C.c_double(), C.c_double()
+            _ck(self._lib.pf_stream_alternative_consensus(self._h, i, po, ri))
             out.append(Alternative(Ids=[p[m] for m in range(k.value)], Score=sc.value, HotwordTokens=hm.value,
                                    LogLikSum=None if hs.value != hs.value else hs.value,
                                    LmSum=None if lm.value != lm.value else lm.value,
                                    NnlmSum=None if nn.value != nn.value else nn.value,
+                                   Posterior=None if po.value != po.value else po.value,
+                                   Risk=None if ri.value != ri.value else ri.value,
                                    Text=(txt.value or b"").decode("utf-8"), Tokens=toks,
                                    Timestamps=[[pt[2 * j], pt[2 * j + 1]] for j in range(nts.value)],
                                    LogLik=None if ll.value != ll.value else ll.value))
@@ -616,6 +643,21 @@ class OfflineRecognizer:
         is a stated default: nobody has tuned it on real speech, and no real model file has been through this path."""
         path = None if pfwPath is None else str(pfwPath).encode("utf-8")
         _ck(self._lib.pf_recognizer_set_nnlm(self._h, path, float(weight), float(bonus), 1 if eos else 0))
+
+    def SetConsensus(self, on: bool = True, scale: float = 1.0) -> None:
+        """Not in the reference: the consensus (minimum-Bayes-risk) choice inside every Alternatives list that follows, on the
+        device (k_consensus.hip).  After a GetResults that produced Alternatives (and after SetRescoreModel's step) each
+        alternative gets Posterior = softmax(scale * Score) inside its list and Risk = its expected Levenshtein distance to the
+        others under it; the stream gets ConsensusIndex (minimal Risk, ties to the higher-ranked) and ConsensusConfidence (per
+        id of that entry, the posterior mass of the alternatives that agree with it).  The list's order, Text, Tokens,
+        Timestamps and Scores stay.  Inert beside SetVad.  scale 1.0 is a stated default, not tuned on speech, and whether the
+        choice lowers the error rate on real speech has not been measured."""
+        if not isinstance(on, (bool, int)):
+            raise TypeError("SetConsensus: on is a bool")
+        scale = float(scale)
+        if on and not (scale > 0.0 and math.isfinite(scale)):
+            raise ValueError("SetConsensus: the scale is > 0 and finite")
+        _ck(self._lib.pf_recognizer_set_consensus(self._h, 1 if on else 0, scale))
 
     def SetSpeakerModel(self, pfwPath, cfg=None) -> None:
         """Speaker labels for every long-audio GetResults that follows: a `.pfw` of kind "campplus" (python -m

@@ -192,9 +192,35 @@ namespace AliParaformerAsr.Hip
                     a.LmSum = lmSum;
                     ParaformerHip.Check(ParaformerHip.pf_stream_alternative_nnlm(Handle, i, out double nnlmSum));
                     a.NnlmSum = nnlmSum;
+                    ParaformerHip.Check(ParaformerHip.pf_stream_alternative_consensus(Handle, i, out double posterior, out double risk));
+                    a.Posterior = posterior;
+                    a.Risk = risk;
                     r.Add(a);
                 }
                 return r;
+            }
+        }
+
+        /// <summary>Not in the reference (OfflineRecognizer.SetConsensus): the place in Alternatives of the entry of minimal expected
+        /// token error under the list's posterior; -1 when the last GetResults chose nothing for this stream.</summary>
+        public int ConsensusIndex
+        {
+            get
+            {
+                ParaformerHip.Check(ParaformerHip.pf_stream_consensus(Handle, out int index, null, 0, out int _));
+                return index;
+            }
+        }
+
+        /// <summary>Per id of Alternatives[ConsensusIndex]: the posterior mass of the alternatives whose canonical alignment agrees
+        /// with it at that id (empty when ConsensusIndex is -1).</summary>
+        public double[] ConsensusConfidence
+        {
+            get
+            {
+                var buf = new double[256];
+                ParaformerHip.Check(ParaformerHip.pf_stream_consensus(Handle, out int _, buf, buf.Length, out int n));
+                return buf.AsSpan(0, n).ToArray();
             }
         }
 
@@ -405,6 +431,9 @@ namespace AliParaformerAsr.Hip
         /// <summary>SetRescoreModel: the Transformer LM's sum of log-probabilities of Ids (NaN without a model); Score is then
         /// base + weight * NnlmSum + bonus * Ids.Length, base = LogLikSum where the list has one, else the search's score.</summary>
         public double NnlmSum = double.NaN;
+        /// <summary>SetConsensus: the alternative's posterior inside its list (from Score as it stands after every earlier step) and
+        /// its expected token error under that posterior (NaN without it).</summary>
+        public double Posterior = double.NaN, Risk = double.NaN;
     }
 
     /// <summary>OfflineStream.Alignment: where each id of a known text lies in the audio.  Ok = false: the target does not fit the
@@ -481,6 +510,11 @@ namespace AliParaformerAsr.Hip
         /// Timestamps and Scores stay.  Not available beside SetVad.  weight 0.5 is a stated default, not tuned on real speech.</summary>
         public void SetRescoreModel(string? pfwPath, double weight = 0.5, double bonus = 0.0, bool eos = false) =>
             ParaformerHip.Check(ParaformerHip.pf_recognizer_set_nnlm(_r, pfwPath, weight, bonus, eos ? 1 : 0));
+        /// <summary>Not in the reference: the consensus (minimum-Bayes-risk) choice inside every Alternatives list that follows, on
+        /// the device.  Each alternative gets Posterior and Risk, the stream ConsensusIndex and ConsensusConfidence; the list's order,
+        /// Text, Tokens, Timestamps and Scores stay.  Inert beside SetVad.  scale 1.0 is a stated default, not tuned on real speech.</summary>
+        public void SetConsensus(bool on = true, double scale = 1.0) =>
+            ParaformerHip.Check(ParaformerHip.pf_recognizer_set_consensus(_r, on ? 1 : 0, scale));
 
         /// <summary>Not in the reference: paraformer models only.  An ARPA n-gram language model fused into the search of
         /// SetNBestSearch (inert without it; null or "" clears it) with weight alpha, per-token bonus beta and flags.  A paraformer

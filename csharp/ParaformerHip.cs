@@ -334,6 +334,17 @@ namespace AliParaformerAsr.Native
         [DllImport(Lib)] internal static extern int pf_recognizer_set_nnlm(IntPtr r, [MarshalAs(UnmanagedType.LPUTF8Str)] string? pfwPath, double weight,
                                                                            double bonus, int flags);
         [DllImport(Lib)] internal static extern int pf_stream_alternative_nnlm(IntPtr s, int i, out double nnlmSum);
+        // consensus inside n-best lists: the recogniser option, a stream's results, the engine call, its guarded form and the host twin
+        [DllImport(Lib)] internal static extern int pf_recognizer_set_consensus(IntPtr r, int on, double scale);
+        [DllImport(Lib)] internal static extern int pf_stream_consensus(IntPtr s, out int index, [Out] double[]? conf, int cap, out int n);
+        [DllImport(Lib)] internal static extern int pf_stream_alternative_consensus(IntPtr s, int i, out double posterior, out double risk);
+        [DllImport(Lib)] internal static extern int pf_engine_consensus(IntPtr e, int[] ids, int[] lens, int[] nHyp, int L, double[] p, [Out] int[] winner,
+                                                                        [Out] double[] risk, [Out] double[] conf, [Out] int[]? D);
+        [DllImport(Lib)] internal static extern int pf_op_consensus(IntPtr e, int[] ids, int[] lens, int[] nHyp, int L, double[] p, [Out] int[] winner,
+                                                                    [Out] double[] risk, [Out] double[] conf, [Out] int[]? D);
+        [DllImport(Lib)] internal static extern int pf_host_consensus(int[] ids, int[] lens, int N, double[]? p, double[]? scores, double scale,
+                                                                      [Out] int[] winner, [Out] double[] risk, [Out] double[] conf, [Out] int[]? D,
+                                                                      [Out] double[]? post);
         [DllImport(Lib)] internal static extern int pf_op_nnlm_logp(IntPtr e, int[] ids, int[] lens, int B, int flags, [Out] float[]? logp, [Out] float[]? lmSum);
         [DllImport(Lib)] internal static extern int pf_host_nnlm_logp(IntPtr m, int[] ids, int n, [Out] double[] logp);
         [DllImport(Lib)] internal static extern int pf_host_nnlm_fuse(double[] @base, double[] lmSum, int[] nTokens, int N, double weight, double bonus,

@@ -1075,6 +1075,39 @@ int pf_host_nnlm_logp(const pf_nnlm_model* m, const int32_t* ids, int32_t n, dou
 int pf_host_nnlm_fuse(const double* base, const double* lm_sum, const int32_t* n_tokens, int32_t N, double weight, double bonus,
                       double* score, int32_t* order);
 
+/* Consensus choice and token confidence (the definition in plain Python is tests/consensus_ref.py): inside an
+   n-best list, the hypothesis of lowest expected token error under the list's own posterior (minimum Bayes risk), and for each
+   of its tokens the posterior mass of the hypotheses that agree with it.  Opt-in and not in the reference: with the option off
+   nothing is launched, allocated or changed.
+   A LIST is N hypotheses, 1 <= N <= PF_CONSENSUS_MAX_HYPS; hypothesis i has n_i ids, 0 <= n_i <= PF_CONSENSUS_MAX_TOKENS, each an
+   int32 compared on all 32 bits, and a weight p_i, a finite float64 >= 0.  From scores the weight is the posterior
+   p_i = exp(scale (s_i - max s)) / sum_k exp(scale (s_k - max s)), the sum over k ascending, scale > 0.
+   D[i][j]: the Levenshtein distance of the id sequences (unit costs).  risk_i = sum_j p_j D[i][j] in float64, j ascending, each
+   product rounded, then added (no fused multiply-add).  The winner w is the smallest i of minimal risk.
+   The canonical alignment of h_j to h_w: E[a][b] over a = 0 .. n_w, b = 0 .. n_j, E[0][b] = b, E[a][0] = a, E[a][b] =
+   min(E[a-1][b-1] + (x_a != y_b), E[a-1][b] + 1, E[a][b-1] + 1) with x = h_w, y = h_j; back from (n_w, n_j): where the diagonal
+   term gives E[a][b] step diagonally and set m_j[a-1] = (x_a == y_b), else where the up term does step up (m_j[a-1] = 0), else
+   step left; on a border the step is forced.  conf[t] = sum_j p_j m_j[t], j ascending in float64, t < n_w.
+   UNVALIDATED: the default scale 1.0 is a stated default, not tuned on speech, and whether the consensus choice lowers the
+   character error rate on real speech has not been measured (there is no corpus here). */
+#define PF_CONSENSUS_MAX_HYPS 64
+#define PF_CONSENSUS_MAX_TOKENS 255
+#define PF_CONSENSUS_MAX_LISTS 1024
+/* The host twin, ONE list: ids = the concatenated ids, lens [N].  The weights are p [N] or, where p is NULL, the posterior of
+   scores [N] under scale (PF_ERR_INVALID_ARG unless scale > 0 and the scores are finite).  winner [1], risk [N], conf
+   [PF_CONSENSUS_MAX_TOKENS + 1] (n_w valid, the rest 0); D [N, N] and post [N] (the weights used) may be NULL.
+   PF_ERR_INVALID_ARG for N or a length out of range, or a weight that is negative or not finite. */
+int pf_host_consensus(const int32_t* ids, const int32_t* lens, int32_t N, const double* p, const double* scores, double scale,
+                      int32_t* winner, double* risk, double* conf, int32_t* D, double* post);
+/* L lists from the host: n_hyp [L] hypotheses each, lens [sum n_hyp], ids concatenated, p [sum n_hyp].  ONE upload, two
+   launches of profile class "consensus" (k_consensus.hip: the pair distances, then risk / winner / alignments / confidence),
+   one copy back: winner [L], risk [sum n_hyp], conf [L, PF_CONSENSUS_MAX_TOKENS + 1] and, unless NULL, D [sum n_hyp^2] (list
+   after list, row-major).  A list's bits do not depend on what else is in the call and equal pf_host_consensus's.
+   PF_ERR_INVALID_ARG for an n_hyp outside 1 .. PF_CONSENSUS_MAX_HYPS, a length outside 0 .. PF_CONSENSUS_MAX_TOKENS, a weight
+   that is negative or not finite, or L < 1; PF_ERR_CAPACITY for L > PF_CONSENSUS_MAX_LISTS: nothing is launched then. */
+int pf_engine_consensus(pf_engine* e, const int32_t* ids, const int32_t* lens, const int32_t* n_hyp, int32_t L, const double* p,
+                        int32_t* winner, double* risk, double* conf, int32_t* D);
+
 /* ------------------------------------------------------------------------ */
 /* 4b. Multi-GPU inside one process: one engine, one host thread and one HIP stream per listed
  *     device.  The reference builds a single ORT session (OfflineRecognizer.cs:23); what shards is the utterance
@@ -1205,6 +1238,11 @@ int pf_op_punc_stream_step(pf_engine* e, void* states, const int32_t* ids, const
    cells behind them, and a row that was not written or a cell beyond [rows] / [B] that was is PF_ERR_DEVICE.  logp [sum (lens +
    1)] and lm_sum [B], either may be NULL. */
 int pf_op_nnlm_logp(pf_engine* e, const int32_t* ids, const int32_t* lens, int32_t B, int32_t flags, float* logp, float* lm_sum);
+/* exactly pf_engine_consensus's launches (k_consensus.hip) through the staging kit: a hostile pattern lies behind the ids,
+   winner, risk, conf and D are sentinel-filled with guard cells behind them, and a result that was not written or a guard
+   cell that was is PF_ERR_DEVICE. */
+int pf_op_consensus(pf_engine* e, const int32_t* ids, const int32_t* lens, const int32_t* n_hyp, int32_t L, const double* p,
+                    int32_t* winner, double* risk, double* conf, int32_t* D);
 /* exactly the attached speaker model's launches (k_spk.hip; PF_ERR_INVALID_ARG without pf_engine_set_spk_model) on caller
    windows: rows = the concatenated fbank rows of B windows, T [B] rows each (0 .. PF_SPK_MAX_FRAMES, else PF_ERR_INVALID_ARG),
    n_mels wide.  emb [B, embedding] fp32; frames (optional) [sum ceil(T / 2), the frames' width] fp32: the activations in front
@@ -1819,6 +1857,20 @@ int pf_recognizer_set_punc_model(pf_recognizer* r, const char* pfw_path);
    engine with a model attached. */
 int pf_recognizer_set_nnlm(pf_recognizer* r, const char* pfw_path, double weight, double bonus, int32_t flags);
 int pf_stream_alternative_nnlm(pf_stream* s, int32_t i, double* nnlm_sum);
+/* Not in the reference: the consensus choice inside every Alternatives list that follows ("Consensus choice and token
+   confidence" above; OfflineRecognizer.SetConsensus).  on != 0 needs scale > 0 and finite (PF_ERR_INVALID_ARG otherwise); 1.0 is
+   a stated default, not tuned on speech.  After every GetResults whose plan produced Alternatives, and after the rescoring of
+   pf_recognizer_set_nnlm when that is on, ONE pf_engine_consensus runs over the lists of all streams of the call on a leased
+   engine; the weights are the posterior of each alternative's score as it then stands (with rescoring: the fused score).  The
+   list's order and Text / Tokens / Timestamps / Scores stay exactly what they are.  pf_stream_consensus: *index = the winner's
+   place in the list and conf = its per-token confidence, cap doubles at most; returns in *n how many the winner has.
+   pf_stream_alternative_consensus: the alternative's posterior and risk.  A stream without alternatives, or with one above
+   PF_CONSENSUS_MAX_TOKENS ids, or whose scores are not finite, reports index -1, n = 0 and NaN and is left out of the call.
+   An error inside the step keeps the recognition results and is reported last.  With pf_recognizer_set_vad the step is inert:
+   a stitched long-audio result carries no lists. */
+int pf_recognizer_set_consensus(pf_recognizer* r, int32_t on, double scale);
+int pf_stream_consensus(pf_stream* s, int32_t* index, double* conf, int32_t cap, int32_t* n);
+int pf_stream_alternative_consensus(pf_stream* s, int32_t i, double* posterior, double* risk);
 /* Speaker labels of every long-audio GetResults that follows (see "Speaker labels"): pfw_path = a `.pfw` of kind "campplus",
    loaded once and attached to every engine of the pool, present and future; NULL clears.  cfg == NULL: the defaults.  Inert
    until pf_recognizer_set_vad, and may come before or after it.  GetResults then, behind the segmentation and on the fbank rows
